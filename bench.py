@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- RTFx of the Parakeet hot path (mel -> FastConformer encoder -> TDT greedy decode) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).  --full adds
+what the headline figure does not need, after the timed steps: the sustained windows, the stage split and per-kernel timing with
+the roofline of the dominant kernel, the parity of the timed batch against the CPU oracle with the CPU baselines, and the secondary
+configurations (`also`).  --dump-outputs DIR writes what the last timed step computed (token ids, lengths, frames, confidences,
+margins, as a caller of pk_batch_run reads them back) as DIR/<name>.npy in float32 / float64; the inputs are seeded, so two builds
+can be compared output for output.
 
 One "step" = one batch of 64 synthetic 10 s / 16 kHz clips (BASELINE.json configs[1]: tdt-ctc-110m, batch 64 x 10 s,
 TDT decode, fp32), PCM already resident in HBM, through the C ABI (libparakeet_amd.so).  value = total audio seconds
@@ -299,7 +306,8 @@ def also_measurements(model, capi, synth, np):
     py = sys.executable
     d = run_json([py, os.path.join(ROOT, "tools", "bench_mixed.py"), "--steps", "10", "--warmup", "3", "--clips", "256", "--oracle-sample", "2"], 240)
     also.append(dict({"name": "mixed_length (reference roadmap: batch inference, README.md:513 -- packed, no padding)"}, **d))
-    d = run_json([py, os.path.abspath(__file__), "--config", "tdt-600m", "--bf16", "--steps", "10", "--warmup", "3", "--sustain-seconds", "0", "--no-also"], 420)
+    d = run_json([py, os.path.abspath(__file__), "--config", "tdt-600m", "--bf16", "--steps", "10", "--warmup", "3", "--sustain-seconds", "0", "--no-also",
+                  "--full"], 420)
     for k in ("kernels", "ms_per_step_per_rank", "collective_ranks", "collective_backend", "sustained"):
         d.pop(k, None)
     also.append(dict({"name": "configs[2] tdt-600m 32x30s bf16"}, **d))
@@ -308,6 +316,42 @@ def also_measurements(model, capi, synth, np):
     d = run_json([py, os.path.join(ROOT, "tools", "bench_stream.py"), "--chunks", "100", "--warmup", "10", "--bf16"], 300)
     also.append(dict({"name": "configs[4] nemotron-600m streaming, 16 streams/GPU, tolerance-class mode (bf16 operands: kernels/gemm_smallm_bf16.hip)"}, **d))
     return also
+
+
+def last_step_outputs(L, capi, batch, n_cap, dec):
+    """What the last timed step computed, as a caller of pk_batch_run reads it back (pk_batch_results_back(0) after pk_batch_sync):
+    token ids, start / end frames and confidences [clips][max_tokens] (-1 / 0 past each clip's length), lengths [clips] and, for TDT,
+    the smallest top-1 / top-2 label log-prob margin of every clip.  Integers are stored as float64 (exact)."""
+    import ctypes as C
+    import numpy as np
+    mt = L.pk_batch_max_tokens(batch)
+    ids = np.zeros((n_cap, mt), np.int32); st = np.zeros((n_cap, mt), np.int32); en = np.zeros((n_cap, mt), np.int32)
+    cf = np.zeros((n_cap, mt), np.float32); lens = np.zeros(n_cap, np.int32); n = C.c_int(0)
+    capi.check(L.pk_batch_results_back(batch, 0, C.byref(n), ids.ctypes.data_as(capi.i32p), lens.ctypes.data_as(capi.i32p),
+                                       st.ctypes.data_as(capi.i32p), en.ctypes.data_as(capi.i32p), cf.ctypes.data_as(capi.f32p)))
+    B = n.value
+    past = np.arange(mt)[None, :] >= np.maximum(lens[:B], 0)[:, None]
+    out = {"token_ids": np.where(past, -1, ids[:B]).astype(np.float64), "token_lens": lens[:B].astype(np.float64),
+           "token_start_frames": np.where(past, -1, st[:B]).astype(np.float64), "token_end_frames": np.where(past, -1, en[:B]).astype(np.float64),
+           "token_confidence": np.where(past, 0.0, cf[:B]).astype(np.float32)}
+    if dec == 1:
+        mg = np.zeros(n_cap, np.float32)
+        if L.pk_batch_margins(batch, 0, mg.ctypes.data_as(capi.f32p)) == 0:
+            out["min_top1_top2_margin"] = mg[:B].copy()
+    return out
+
+
+def dump_outputs(dirname, outputs, rank, world):
+    """--dump-outputs: one DIR/<name>.npy per array (DIR/<name>_rank<r>.npy when several ranks run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed the 64 MB bound")
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), a)
+    log(f"[bench] wrote {len(outputs)} arrays ({total} bytes) of the last timed step to {dirname}")
 
 
 def free_port():
@@ -381,9 +425,13 @@ def main():
                     help="pk_batch_set_decode_overlap: 1 = decode under the next encoder on a second stream, 0 = on the encoder's stream after it; "
                          "-1 = the configuration's default (1 for tdt-ctc-110m)")
     ap.add_argument("--sustain-seconds", type=float, default=3.0,
-                    help="after the timed K steps: keep stepping in windows of K for about this long and report the median window (0 = skip)")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary configurations (`also`) the default N = 1 headline run appends after "
-                    "its own timed region: configs[2] tdt-600m bf16, configs[4] streaming, mixed-length batches, the PCIe-inclusive rate")
+                    help="with --full, after the timed K steps: keep stepping in windows of K for about this long and report the median window (0 = skip)")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the secondary configurations (`also`) the N = 1 headline run appends "
+                    "after its own timed region: configs[2] tdt-600m bf16, configs[4] streaming, mixed-length batches, the PCIe-inclusive rate")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline figure does not need: "
+                    "sustained windows, stage split, per-kernel timing and roofline, parity against the CPU oracle, CPU baselines, `also`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--rendezvous-only", action="store_true", help="launcher + collective plumbing over gloo without a GPU (CPU test hook)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -478,6 +526,9 @@ def main():
             mg_ = np.zeros(args.batch, np.float32)
             if L.pk_batch_margins(batch, back, mg_.ctypes.data_as(capi.f32p)) == 0:
                 timed_margin = min(timed_margin, float(mg_[:n_.value].min()))
+    last = last_step_outputs(L, capi, batch, args.batch, dec)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
     per_rank_s = [elapsed]
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -486,61 +537,62 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, per_rank_s = float(tt.item()), [float(x) for x in allr.tolist()]
 
-    # Sustained figure (NOT `value`): the timed region of 20 steps lasts ~0.4 s -- too short for the driver's GPU-busy sampling to see and
-    # ~1 % above the steady state.  Keep stepping in windows of K steps for --sustain-seconds and report the median window.
-    sustained = None
-    if args.sustain_seconds > 0:
-        if group > 1:
-            capi.check(L.pk_batch_set_decode_group(batch, group))
-        wins, t_all = [], time.perf_counter()
-        while time.perf_counter() - t_all < args.sustain_seconds and len(wins) < 64:
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                capi.check(L.pk_batch_run(batch, dec))
-            capi.check(L.pk_batch_sync(batch))
-            wins.append((time.perf_counter() - t1) / args.steps * 1e3)
-        ws = sorted(wins)
-        sustained = {"windows": len(wins), "steps_per_window": args.steps, "seconds": round(time.perf_counter() - t_all, 2),
-                     "ms_per_step_median": round(ws[len(ws) // 2], 3), "ms_per_step_min": round(ws[0], 3), "ms_per_step_max": round(ws[-1], 3),
-                     "rtfx_median": round(args.batch * CLIP_SECONDS / (ws[len(ws) // 2] * 1e-3), 1)}
-        # the same protocol with decode_group = 1 (round-1 protocol: decode(k) under encoder(k+1)), for round-over-round comparison
-        if group > 1:
-            capi.check(L.pk_batch_set_decode_group(batch, 1))
-            for _ in range(2):
-                capi.check(L.pk_batch_run(batch, dec))
-            capi.check(L.pk_batch_sync(batch))
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                capi.check(L.pk_batch_run(batch, dec))
-            capi.check(L.pk_batch_sync(batch))
-            sustained["decode_group_1_ms_per_step"] = round((time.perf_counter() - t1) / args.steps * 1e3, 3)
-        elif dec == 1:
-            capi.check(L.pk_batch_set_decode_group(batch, 1))
+    sustained, kernels, ms = None, {}, None
+    if args.full:
+        # Sustained figure (NOT `value`): the timed region of 20 steps lasts ~0.4 s -- too short for the driver's GPU-busy sampling to see and
+        # ~1 % above the steady state.  Keep stepping in windows of K steps for --sustain-seconds and report the median window.
+        if args.sustain_seconds > 0:
+            if group > 1:
+                capi.check(L.pk_batch_set_decode_group(batch, group))
+            wins, t_all = [], time.perf_counter()
+            while time.perf_counter() - t_all < args.sustain_seconds and len(wins) < 64:
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    capi.check(L.pk_batch_run(batch, dec))
+                capi.check(L.pk_batch_sync(batch))
+                wins.append((time.perf_counter() - t1) / args.steps * 1e3)
+            ws = sorted(wins)
+            sustained = {"windows": len(wins), "steps_per_window": args.steps, "seconds": round(time.perf_counter() - t_all, 2),
+                         "ms_per_step_median": round(ws[len(ws) // 2], 3), "ms_per_step_min": round(ws[0], 3), "ms_per_step_max": round(ws[-1], 3),
+                         "rtfx_median": round(args.batch * CLIP_SECONDS / (ws[len(ws) // 2] * 1e-3), 1)}
+            # the same protocol with decode_group = 1 (round-1 protocol: decode(k) under encoder(k+1)), for round-over-round comparison
+            if group > 1:
+                capi.check(L.pk_batch_set_decode_group(batch, 1))
+                for _ in range(2):
+                    capi.check(L.pk_batch_run(batch, dec))
+                capi.check(L.pk_batch_sync(batch))
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    capi.check(L.pk_batch_run(batch, dec))
+                capi.check(L.pk_batch_sync(batch))
+                sustained["decode_group_1_ms_per_step"] = round((time.perf_counter() - t1) / args.steps * 1e3, 3)
+            elif dec == 1:
+                capi.check(L.pk_batch_set_decode_group(batch, 1))
 
-    if dec == 1:
-        capi.check(L.pk_batch_set_decode_group(batch, 1))            # the stage / kernel timers below run one un-pipelined step at a time
-    # stage split + per-kernel timing of one extra (untimed) step, hipEvents on the library's own stream
-    ms = (C.c_float * 4)()
-    capi.check(L.pk_batch_run_timed(batch, dec, ms))
-    # per-kernel HIP-event timing (events on the library's own stream around every launch): three extra, untimed steps, averaged
-    kernels = {}
-    N_PROF = 3
-    for _ in range(N_PROF):
-        stats = (capi.PkKernelStat * 64)()
-        nk = L.pk_batch_profile(batch, dec, stats, 64)
-        for i in range(max(0, min(nk, 64))):
-            s_ = stats[i]
-            k = kernels.setdefault(s_.name.decode(), {"launches": 0, "ms": 0.0, "gflop": 0.0, "mbytes": 0.0})
-            k["launches"] += s_.launches; k["ms"] += s_.total_ms; k["gflop"] += s_.flops / 1e9; k["mbytes"] += s_.bytes / 1e6
-    for k in kernels.values():                       # back to per-step figures
-        k["launches"] //= N_PROF
-        k["ms"] = round(k["ms"] / N_PROF, 4); k["gflop"] = round(k["gflop"] / N_PROF, 3); k["mbytes"] = round(k["mbytes"] / N_PROF, 3)
-    mt = L.pk_batch_max_tokens(batch)
-    ids = np.zeros((args.batch, mt), np.int32)
-    lens = np.zeros(args.batch, np.int32)
-    st_fr = np.zeros((args.batch, mt), np.int32); en_fr = np.zeros((args.batch, mt), np.int32)
-    capi.check(L.pk_batch_results(batch, ids.ctypes.data_as(capi.i32p), lens.ctypes.data_as(capi.i32p), st_fr.ctypes.data_as(capi.i32p),
-                                  en_fr.ctypes.data_as(capi.i32p), None))
+        if dec == 1:
+            capi.check(L.pk_batch_set_decode_group(batch, 1))            # the stage / kernel timers below run one un-pipelined step at a time
+        # stage split + per-kernel timing of one extra (untimed) step, hipEvents on the library's own stream
+        ms = (C.c_float * 4)()
+        capi.check(L.pk_batch_run_timed(batch, dec, ms))
+        # per-kernel HIP-event timing (events on the library's own stream around every launch): three extra, untimed steps, averaged
+        kernels = {}
+        N_PROF = 3
+        for _ in range(N_PROF):
+            stats = (capi.PkKernelStat * 64)()
+            nk = L.pk_batch_profile(batch, dec, stats, 64)
+            for i in range(max(0, min(nk, 64))):
+                s_ = stats[i]
+                k = kernels.setdefault(s_.name.decode(), {"launches": 0, "ms": 0.0, "gflop": 0.0, "mbytes": 0.0})
+                k["launches"] += s_.launches; k["ms"] += s_.total_ms; k["gflop"] += s_.flops / 1e9; k["mbytes"] += s_.bytes / 1e6
+        for k in kernels.values():                       # back to per-step figures
+            k["launches"] //= N_PROF
+            k["ms"] = round(k["ms"] / N_PROF, 4); k["gflop"] = round(k["gflop"] / N_PROF, 3); k["mbytes"] = round(k["mbytes"] / N_PROF, 3)
+        mt = L.pk_batch_max_tokens(batch)
+        ids = np.zeros((args.batch, mt), np.int32)
+        lens = np.zeros(args.batch, np.int32)
+        st_fr = np.zeros((args.batch, mt), np.int32); en_fr = np.zeros((args.batch, mt), np.int32)
+        capi.check(L.pk_batch_results(batch, ids.ctypes.data_as(capi.i32p), lens.ctypes.data_as(capi.i32p), st_fr.ctypes.data_as(capi.i32p),
+                                      en_fr.ctypes.data_as(capi.i32p), None))
 
     if rank == 0:
         audio_s = args.steps * args.batch * CLIP_SECONDS * n_gpus
@@ -550,7 +602,7 @@ def main():
         # average over its launches measured above, in this run.  Peak by arithmetic type (MI355X_MICROARCH.md): fp32 MFMA 157.3 TF,
         # dense bf16 MFMA 2500 TF.
         peak = PEAK_BF16_MFMA_TFLOPS if args.bf16 else PEAK_F32_MFMA_TFLOPS
-        dom = kernels.get("ffn_fc1_silu")
+        dom = kernels.get("ffn_fc1_silu")           # --full only: empty otherwise
         roof = None
         if dom and dom["launches"]:
             per_launch_flop = dom["gflop"] * 1e9 / dom["launches"]
@@ -578,7 +630,6 @@ def main():
                     "flop_per_launch": per_launch_flop, "us_per_launch": round(per_launch_s * 1e6, 2),
                     "encoder_gemms": {"tflops": round(g_fl / max(g_ms, 1e-9), 2), "gflop": round(g_fl, 1), "ms": round(g_ms, 3),
                                       "frac_of_peak": round(g_fl / max(g_ms, 1e-9) / peak, 4)}}
-        enc_ms = float(ms[1])
         out = {
             "metric": f"RTFx (audio-sec/wall-sec), mel+encoder+TDT decode, {args.config} {int(CLIP_SECONDS)}s@b{args.batch}",
             "value": round(value, 1), "unit": "x real-time", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -590,25 +641,30 @@ def main():
                        "decode_group": group, "decode_loop": args.decode_loop, "decode_overlap": overlap},
             "ms_per_step_per_rank": [round(x / args.steps * 1e3, 3) for x in per_rank_s],
             "collective_ranks": (dist.get_world_size() if use_dist else 1), "collective_backend": ("nccl (RCCL)" if use_dist else None),
-            "sustained": sustained,
             # smallest top-1 / top-2 label log-prob margin over every decision of the timed runs read back: how far the closest greedy
             # decision was from another token (the early warning of the tolerance-class bf16 mode)
             "min_top1_top2_margin": (round(timed_margin, 6) if timed_margin != float("inf") else None),
-            "encoder_ms_per_clip": round(enc_ms / args.batch, 4),
-            "stage_ms": {"mel": round(float(ms[0]), 3), "encoder": round(enc_ms, 3), "decode": round(float(ms[2]), 3), "total": round(float(ms[3]), 3)},
-            "encoder_tflops": round(ENCODER_FLOP_PER_CLIP * args.batch / (enc_ms * 1e-3) / 1e12, 2),
-            "encoder_frac_of_mfma_peak": round(ENCODER_FLOP_PER_CLIP * args.batch / (enc_ms * 1e-3) / 1e12 / peak, 4),
-            "decode_tokens_per_clip": round(float(lens.mean()), 1),
-            "roofline": roof,
-            "kernels": kernels,
+            "decode_tokens_per_clip": round(float(last["token_lens"].mean()), 1),      # the last timed step
         }
+        if args.full:
+            enc_ms = float(ms[1])
+            out.update({
+                "sustained": sustained,
+                "encoder_ms_per_clip": round(enc_ms / args.batch, 4),
+                "stage_ms": {"mel": round(float(ms[0]), 3), "encoder": round(enc_ms, 3), "decode": round(float(ms[2]), 3), "total": round(float(ms[3]), 3)},
+                "encoder_tflops": round(ENCODER_FLOP_PER_CLIP * args.batch / (enc_ms * 1e-3) / 1e12, 2),
+                "encoder_frac_of_mfma_peak": round(ENCODER_FLOP_PER_CLIP * args.batch / (enc_ms * 1e-3) / 1e12 / peak, 4),
+                "roofline": roof,
+                "kernels": kernels,
+            })
         # Parity of the TIMED configuration + CPU baselines, on this box's host cores (rank 0, N = 1 only).  The oracle decodes
         # every clip of the timed batch (bit-exact contract: token ids must be identical); the reference's own Transcriber decodes a
-        # bounded prefix of it.  A mismatch against the oracle fails the run.
+        # bounded prefix of it.  A mismatch against the oracle fails the run.  --full only.
         rc = 0
-        gpu_ids = [ids[b, :lens[b]].tolist() for b in range(args.batch)]
+        full_cpu = args.full and n_gpus == 1 and not args.no_cpu_baseline and args.decoder == "tdt"
+        gpu_ids = [ids[b, :lens[b]].tolist() for b in range(args.batch)] if full_cpu else None
         threads = min(8, os.cpu_count() or 1)
-        if n_gpus == 1 and not args.no_cpu_baseline and args.decoder == "tdt" and (big or args.bf16):
+        if full_cpu and (big or args.bf16):
             # configs[2] / the bf16 mode: the 24-layer oracle is too slow for the whole batch, so parity comes from the committed full-depth
             # fixture (tests/golden/tdt600m_depth24_seed42.npz = the oracle's and the reference code's outputs for the FIRST clips of exactly
             # this batch, tools/make_golden_600m.py) and the CPU baseline is the fp32 oracle timed live on ONE clip (~10 s of CPU work).
@@ -628,7 +684,7 @@ def main():
                 out["cpu_baseline"] = port
             except Exception as e:
                 out["cpu_baseline"] = {"value": None, "error": repr(e)}
-        elif n_gpus == 1 and not args.no_cpu_baseline and args.decoder == "tdt":
+        elif full_cpu:
             try:
                 if W is None:
                     W = synth.synth_weights(cfg, seed=42)
@@ -668,7 +724,7 @@ def main():
         # Secondary configurations, AFTER the headline's timed region and outside `value` (round-3 verdict: configs[2] and configs[4] were only
         # ever builder-run): each is one short, bounded measurement -- own process where it needs another model -- and a failure or timeout
         # is reported inside its entry, never at the expense of the headline line.
-        if n_gpus == 1 and not args.no_also and args.config == "tdt-ctc-110m" and not args.bf16 and args.decoder == "tdt":
+        if args.full and n_gpus == 1 and not args.no_also and args.config == "tdt-ctc-110m" and not args.bf16 and args.decoder == "tdt":
             out["also"] = also_measurements(model, capi, synth, np)
         print(json.dumps(out), flush=True)
         if rc:

@@ -5,7 +5,7 @@ out=gpurun_out/dec_graph_ab.txt
 : > $out
 for rep in 1 2; do
   for g in 0 1; do
-    line=$(PK_DEC_GRAPH=$g timeout 120 python bench.py --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | tail -1)
+    line=$(PK_DEC_GRAPH=$g timeout 120 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | tail -1)
     echo "graph=$g $(python -c "import json,sys; d=json.loads(sys.argv[1]); print('ms_per_step=%.3f rtfx=%.0f stage_ms=%s'%(d['ms_per_step'],d['value'],d['stage_ms']))" "$line")" >> $out
   done
 done

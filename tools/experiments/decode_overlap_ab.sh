@@ -5,7 +5,7 @@
 out=${1:-gpurun_out/decode_overlap_ab.txt}
 run() {  # label, env, args...
     label=$1; envs=$2; shift 2
-    line=$(env $envs timeout 300 python bench.py --no-cpu-baseline --sustain-seconds 1.5 "$@" 2>/dev/null | tail -1)
+    line=$(env $envs timeout 300 python bench.py --full --no-cpu-baseline --sustain-seconds 1.5 "$@" 2>/dev/null | tail -1)
     echo "$label | $envs | $* | $(echo "$line" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["sustained"]["ms_per_step_median"], d["stage_ms"]["encoder"])' 2>/dev/null)" | tee -a "$out"
 }
 : > "$out"

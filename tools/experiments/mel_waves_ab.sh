@@ -7,7 +7,7 @@ out=gpurun_out/mel_waves_ab.txt
 for rep in 1 2; do
   for w in 12 16; do
     lib=parakeet.cpp_amd/libparakeet_amd_mel$w.so; [ $w = 16 ] && lib=parakeet.cpp_amd/libparakeet_amd.so
-    line=$(PK_LIB=$PWD/$lib timeout 120 python bench.py --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
+    line=$(PK_LIB=$PWD/$lib timeout 120 python bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
     echo "waves=$w $(python -c "import json,sys; d=json.loads(sys.argv[1]); k=d['kernels']; print('ms_per_step=%.3f mel_logmel_ms=%.4f mel_normalize_ms=%.4f stage_mel=%.3f'%(d['ms_per_step'],k['mel_logmel']['ms'],k['mel_normalize']['ms'],d['stage_ms']['mel']))" "$line")" >> $out
   done
 done

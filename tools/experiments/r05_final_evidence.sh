@@ -13,9 +13,9 @@ run() { # tag title cmd...
   python tools/pmc_sq_summary.py $o/$t $o/pmc_sq_$t.md "# rocprofv3 --pmc (8 SQ counters + GRBM_GUI_ACTIVE), $title.  Mean per dispatch." > /dev/null 2>&1
   rm -rf $o/$t $o/$t.log
 }
-B="--steps 2 --warmup 1 --no-cpu-baseline --no-also --sustain-seconds 0"
-run 110m "\`python bench.py $B\` (configs[1], fp32)" python bench.py $B
-run 600m_bf16 "\`python bench.py --config tdt-600m --bf16 $B\` (configs[2], production library)" python bench.py --config tdt-600m --bf16 $B
+B="--steps 2 --warmup 1 --no-cpu-baseline --no-also --sustain-seconds 0 --full"
+run 110m "\`python bench.py --full $B\` (configs[1], fp32)" python bench.py --full $B
+run 600m_bf16 "\`python bench.py --full --config tdt-600m --bf16 $B\` (configs[2], production library)" python bench.py --full --config tdt-600m --bf16 $B
 run stream_fp32 "\`python tools/bench_stream.py --chunks 30 --warmup 5\` (configs[4], exact mode)" python tools/bench_stream.py --chunks 30 --warmup 5
 run stream_bf16 "\`python tools/bench_stream.py --bf16 --chunks 30 --warmup 5\` (configs[4], tolerance-class mode)" python tools/bench_stream.py --bf16 --chunks 30 --warmup 5
 for m in fp32 bf16; do

@@ -19,5 +19,5 @@ done
 PK_LIB=$exp PK_SB_CT=2 PK_SB_NT=1 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o kt -- python tools/bench_stream.py --bf16 --chunks 45 --warmup 5 > $o/prof.log 2>&1
 python tools/rocprof_summary.py $(ls $o/prof/*/kt_kernel_trace.csv $o/prof/kt_kernel_trace.csv 2>/dev/null | head -1) $o/stream_bf16_ct2_kernel_stats.md > /dev/null 2>&1
 rm -rf $o/prof
-timeout 500 python bench.py > $o/bench.json 2> $o/bench.err
+timeout 500 python bench.py --full > $o/bench.json 2> $o/bench.err
 tail -5 $o/new_tests.log; tail -3 $o/all_tests.log; cat $o/sb_ab.txt; head -c 400 $o/bench.json

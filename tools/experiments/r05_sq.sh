@@ -13,10 +13,10 @@ run() { # tag title cmd...
   python tools/pmc_sq_summary.py $o/$tag $o/sq_$tag.md "# rocprofv3 --pmc (8 SQ counters + GRBM_GUI_ACTIVE), $title.  Mean per dispatch." > /dev/null 2>&1
   rm -rf $o/$tag
 }
-B="--steps 2 --warmup 1 --no-cpu-baseline --no-also --sustain-seconds 0"
-run 110m "\`python bench.py $B\` (configs[1], fp32)" python bench.py $B
+B="--steps 2 --warmup 1 --no-cpu-baseline --no-also --sustain-seconds 0 --full"
+run 110m "\`python bench.py --full $B\` (configs[1], fp32)" python bench.py --full $B
 for p in 0 2 4; do
-  PK_LIB=$exp PK_BF16_PERSIST=$p run 600m_bf16_p$p "\`PK_BF16_PERSIST=$p python bench.py --config tdt-600m --bf16 $B\` (configs[2]; EXPERIMENTAL build)" python bench.py --config tdt-600m --bf16 $B
+  PK_LIB=$exp PK_BF16_PERSIST=$p run 600m_bf16_p$p "\`PK_BF16_PERSIST=$p python bench.py --full --config tdt-600m --bf16 $B\` (configs[2]; EXPERIMENTAL build)" python bench.py --full --config tdt-600m --bf16 $B
 done
 run stream_fp32 "\`python tools/bench_stream.py --chunks 30 --warmup 5\` (configs[4], exact mode)" python tools/bench_stream.py --chunks 30 --warmup 5
 run stream_bf16 "\`python tools/bench_stream.py --bf16 --chunks 30 --warmup 5\` (configs[4], tolerance-class mode)" python tools/bench_stream.py --bf16 --chunks 30 --warmup 5

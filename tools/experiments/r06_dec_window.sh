@@ -12,7 +12,7 @@ for rep in 1 2 3; do for sw in 0 1; do
   echo "dec_win=$sw $(PK_LIB=$exp PK_DEC_WIN=$sw timeout 200 python tools/latency_single.py 2>&1 | tr '\n' ' ')" >> $o/ab.txt
 done; done
 for rep in 1 2; do for sw in 0 1; do for b in 1 4; do
-  line=$(PK_LIB=$exp PK_DEC_WIN=$sw timeout 300 python bench.py --batch $b --no-cpu-baseline --no-also --steps 50 --warmup 5 --sustain-seconds 0 2>/dev/null | tail -1)
+  line=$(PK_LIB=$exp PK_DEC_WIN=$sw timeout 300 python bench.py --full --batch $b --no-cpu-baseline --no-also --steps 50 --warmup 5 --sustain-seconds 0 2>/dev/null | tail -1)
   echo "batch=$b dec_win=$sw $(python -c "import json,sys; d=json.loads(sys.argv[1]); print('ms_per_step=%.3f stage_ms=%s parity=%s' % (d['ms_per_step'], d['stage_ms'], d.get('parity', d.get('ids_equal_oracle'))))" "$line")" >> $o/ab.txt
 done; done; done
 cat $o/ab.txt; tail -5 $o/tests.log

@@ -8,7 +8,7 @@ echo "tests rc=$?" >> $o/tests.log
 : > $o/ab.txt
 for rep in 1 2 3; do
   for sw in 0 1; do
-    line=$(PK_LIB=$exp PK_DEC_FAST=$sw timeout 300 python bench.py --config tdt-600m --bf16 --no-cpu-baseline --no-also --steps 10 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
+    line=$(PK_LIB=$exp PK_DEC_FAST=$sw timeout 300 python bench.py --full --config tdt-600m --bf16 --no-cpu-baseline --no-also --steps 10 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
     echo "600m-bf16 dec_fast=$sw $(python -c "import json,sys; d=json.loads(sys.argv[1]); k=d['kernels']; print('ms_per_step=%.3f stage_ms=%s tdt_decide=%.3f' % (d['ms_per_step'], d['stage_ms'], k.get('tdt_decide',{}).get('ms',0)))" "$line")" >> $o/ab.txt
   done
 done

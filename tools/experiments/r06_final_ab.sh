@@ -7,12 +7,12 @@ A=$PWD/parakeet.cpp_amd/libparakeet_amd_prev.so; B=$PWD/parakeet.cpp_amd/libpara
 : > $o/ab.txt
 for rep in 1 2 3; do for l in A B; do
   lib=$A; [ $l = B ] && lib=$B
-  line=$(PK_LIB=$lib timeout 300 python bench.py --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
+  line=$(PK_LIB=$lib timeout 300 python bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
   echo "headline lib=$l $(python -c "import json,sys; d=json.loads(sys.argv[1]); k=d['kernels']; print('ms_per_step=%.3f enc=%.3f attention=%.3f layernorm=%.3f decide=%.3f' % (d['ms_per_step'], d['stage_ms']['encoder'], k['relpos_attention']['ms'], k['layernorm']['ms'], k['tdt_decide']['ms']))" "$line")" >> $o/ab.txt
 done; done
 for rep in 1 2; do for l in A B; do
   lib=$A; [ $l = B ] && lib=$B
-  line=$(PK_LIB=$lib timeout 300 python bench.py --config tdt-600m --bf16 --no-cpu-baseline --no-also --steps 10 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
+  line=$(PK_LIB=$lib timeout 300 python bench.py --full --config tdt-600m --bf16 --no-cpu-baseline --no-also --steps 10 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
   echo "600m-bf16 lib=$l $(python -c "import json,sys; d=json.loads(sys.argv[1]); print('ms_per_step=%.3f stage_ms=%s' % (d['ms_per_step'], d['stage_ms']))" "$line")" >> $o/ab.txt
 done; done
 for rep in 1 2 3; do for l in A B; do

@@ -12,5 +12,5 @@ for L in 24 4 2; do
     echo "layers=$L $f $(timeout 300 python tools/bench_stream.py $f --layers $L --chunks 150 --warmup 20 2>/dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["latency_ms_median"], d["latency_ms_p95"], d["latency_ms_mean"])')" >> $o/stream_layers.txt
   done
 done
-timeout 600 python bench.py > $o/bench.json 2> $o/bench.err
+timeout 600 python bench.py --full > $o/bench.json 2> $o/bench.err
 cat $o/l2_warm.txt; cat $o/stream_layers.txt; head -c 600 $o/bench.json

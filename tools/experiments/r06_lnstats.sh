@@ -8,7 +8,7 @@ echo "tests rc=$?" >> $o/tests.log
 : > $o/ab.txt
 for rep in 1 2 3; do
   for sw in 0 1; do
-    line=$(PK_LIB=$exp PK_LN_STATS=$sw timeout 200 python bench.py --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
+    line=$(PK_LIB=$exp PK_LN_STATS=$sw timeout 200 python bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
     echo "ln_stats=$sw $(python -c "import json,sys; d=json.loads(sys.argv[1]); r=d['roofline']; k=d['kernels']; print('ms_per_step=%.3f enc=%.3f fc1_us=%.1f | '%(d['ms_per_step'],d['stage_ms']['encoder'],r['us_per_launch'])+' '.join('%s=%.3f'%(n.replace('ffn_','').replace('attn_','').replace('conv_',''),k[n]['ms']) for n in ('ffn_fc1_silu','ffn_fc2_resid','attn_qkv','attn_out_resid','conv_pw1_glu','conv_pw2_resid','layernorm','layernorm_stats','layernorm_then_stats','relpos_attention') if n in k))" "$line")" >> $o/ab.txt
   done
 done

@@ -10,6 +10,6 @@ for rep in 1 2 3; do for n in 1 8; do for sw in 0 1; do
   echo "clips=$n poll_ahead=$sw $(PK_LIB=$exp PK_DEC_POLL_AHEAD=$sw PK_LAT_CLIPS=$n timeout 200 python tools/latency_single.py 2>&1 | head -1)" >> $o/ab.txt
 done; done; done
 for rep in 1 2 3; do for sw in 0 1; do
-  echo "headline poll_ahead=$sw $(PK_LIB=$exp PK_DEC_POLL_AHEAD=$sw timeout 300 python bench.py --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'])")" >> $o/ab.txt
+  echo "headline poll_ahead=$sw $(PK_LIB=$exp PK_DEC_POLL_AHEAD=$sw timeout 300 python bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'])")" >> $o/ab.txt
 done; done
 cat $o/ab.txt; tail -3 $o/tests.log

@@ -10,6 +10,6 @@ for rep in 1 2 3; do for n in 1 8; do for l in A B; do
 done; done; done
 for rep in 1; do for l in A B; do
   lib=$A; [ $l = B ] && lib=$B
-  echo "headline lib=$l $(PK_LIB=$lib timeout 300 python bench.py --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']; print(d['ms_per_step'], k['lstm_hh_cell']['ms'], k['joint_pred_act']['ms'], k['joint_heads_gemv']['ms'])")" >> $o/ab.txt
+  echo "headline lib=$l $(PK_LIB=$lib timeout 300 python bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']; print(d['ms_per_step'], k['lstm_hh_cell']['ms'], k['joint_pred_act']['ms'], k['joint_heads_gemv']['ms'])")" >> $o/ab.txt
 done; done
 cat $o/ab.txt; tail -3 $o/tests.log

@@ -9,7 +9,7 @@ echo "tests rc=$?" >> $o/tests.log
 : > $o/ab.txt
 for rep in 1 2 3; do for l in A B; do
   lib=$A; [ $l = B ] && lib=$B
-  line=$(PK_LIB=$lib timeout 300 python bench.py --config tdt-600m --bf16 --no-cpu-baseline --no-also --steps 10 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
+  line=$(PK_LIB=$lib timeout 300 python bench.py --full --config tdt-600m --bf16 --no-cpu-baseline --no-also --steps 10 --warmup 3 --sustain-seconds 0 2>/dev/null | tail -1)
   echo "600m-bf16 lib=$l $(python -c "import json,sys; d=json.loads(sys.argv[1]); print('ms_per_step=%.3f decode_stage=%.3f' % (d['ms_per_step'], d['stage_ms']['decode']))" "$line")" >> $o/ab.txt
   echo "stream-bf16 lib=$l $(PK_LIB=$lib timeout 200 python tools/bench_stream.py --bf16 --chunks 100 --warmup 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['latency_ms_median'], d['latency_ms_p95'])")" >> $o/ab.txt
 done; done
