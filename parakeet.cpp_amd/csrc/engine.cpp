@@ -374,16 +374,7 @@ void Model::to_gpu(int device) {
         int lo = 0, hi = 0;
         PK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));   // numerically lowest = highest priority
         int prio = hi;                                        // the decode loop of batch k-1 runs at the highest priority
-#ifdef PK_EXPERIMENTAL
-        if (const char *e = getenv("PK_DEC_PRIORITY")) {      // experiment builds only (tools/): "normal" / "low"
-            if (!strcmp(e, "normal")) prio = 0;
-            else if (!strcmp(e, "low")) prio = lo;
-        }
-#endif
         (void)lo;
-#ifdef PK_EXPERIMENTAL
-        if (const char *e = getenv("PK_DEC_NT")) dec_nt_weights = atoi(e);
-#endif
         PK_HIP(hipStreamCreateWithPriority(&stream_dec, hipStreamNonBlocking, prio));
     }
     PK_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_done), sizeof(int), hipHostMallocDefault));
@@ -850,34 +841,15 @@ bool Model::ln_folds(const GemmArgs &g, int epi, int64_t rows) const {
 // products that take the norm pay more than that -- fc1 152 -> 163 us with the three operations per element in front of the staging stores, 167 us with
 // them moved under the MFMAs of an earlier sub-step (the wait for the K tile in flight moves with them), qkv + 5 %, pw1 + 8-12 %: the step 18.46 -> 18.87 / 19.1 ms
 // (profiles/r06_ln_stats_fold_ab.txt).  The global -> VGPR -> LDS staging is what the fp32 loop is bound by; anything added to it costs more
-// than a memory-bound launch of 13 us.  EXPERIMENTAL builds: PK_LN_STATS=1 switches it on.
-static bool ln_stats_on() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_LN_STATS"); return e ? atoi(e) != 0 : false; }();
-    return on;
-#else
-    return false;
-#endif
-}
-bool Model::ln_stats_folds(const GemmArgs &g, int epi, const float *ng, const float *nb, const float *x, const float *stats) const {
-    if (cfg.gemm_bf16 || !ln_stats_on()) return false;
-    GemmArgs fg = g;
-    fg.A = x; fg.lda = cfg.hidden_size; fg.a_sigma = 0; fg.a_bf16 = 0; fg.ln_g = ng; fg.ln_b = nb; fg.ln_eps = 1e-5f; fg.ln_stats = stats;
-    return fg.K == cfg.hidden_size && gemm_ln_stats_applies(fg, epi);
-}
-// norm_state: 0 = x is un-normalised, 1 = n holds the normalised rows (a previous kernel wrote them), 2 = n holds the rows' statistics for this norm
-void Model::ln_gemm(const char *name, const GemmArgs &g, int epi, const float *ng, const float *nb, int norm_state, int ymode, const float *x, float *n,
+// than a memory-bound launch of 13 us.  (The engine's statistics path existed up to 4fb176f, switched on by PK_LN_STATS=1 in EXPERIMENTAL builds; the
+// kernels stay, reached by pk_diag_ln_gemm.)
+// norm_done: n holds the normalised rows already (a previous kernel wrote them)
+void Model::ln_gemm(const char *name, const GemmArgs &g, int epi, const float *ng, const float *nb, bool norm_done, int ymode, const float *x, float *n,
                     int64_t rows, hipStream_t s) {
     const int d = cfg.hidden_size;
-    if (norm_state != 1) {
+    if (!norm_done) {
         GemmArgs fg = g;
         fg.A = x; fg.lda = d; fg.a_sigma = 0; fg.a_bf16 = 0; fg.ln_g = ng; fg.ln_b = nb; fg.ln_eps = 1e-5f;
-        if (norm_state == 2 || ln_stats_folds(g, epi, ng, nb, x, n)) {
-            if (norm_state != 2) KL("layernorm_stats", 0.0, 1.0 * rows * d * 4, launch_layernorm_stats(x, rows, d, 1e-5f, n, s));
-            fg.ln_stats = n;
-            run_gemm(name, fg, epi, s);
-            return;
-        }
         if (ln_folds(fg, epi, rows)) { run_gemm(name, fg, epi, s); return; }
         KL("layernorm", 0.0, (cfg.gemm_bf16 ? 1.5 : 2.0) * rows * d * 4, launch_layernorm(x, rows, d, ng, nb, 1e-5f, n, s, ymode));
     }
@@ -885,7 +857,7 @@ void Model::ln_gemm(const char *name, const GemmArgs &g, int epi, const float *n
 }
 
 // FeedForward::forward (src/encoder.cpp:39-46): x += 0.5 * fc2(silu(fc1(LN(x))))
-void Model::ffn(Workspace &w, const LayerW &L, bool second, int64_t rows, hipStream_t s, int norm_state, const SigW *sg) {
+void Model::ffn(Workspace &w, const LayerW &L, bool second, int64_t rows, hipStream_t s, bool norm_done, const SigW *sg) {
     const int d = cfg.hidden_size, f = cfg.ffn_intermediate;
     float *x = w.x.as<float>(), *n = w.n.as<float>(), *h = w.hbuf.as<float>();
     // bf16 mode: the normalised rows and the fc1 activations exist only as GEMM operands -- their producers round them to bf16 (RNE, the
@@ -902,7 +874,7 @@ void Model::ffn(Workspace &w, const LayerW &L, bool second, int64_t rows, hipStr
     g1.out_blocked = blocked ? 1 : 0;
     if (sg) { g1.a_sigma = 1; g1.W_sig = second ? sg->ffn2_w1 : sg->ffn1_w1; g1.sigma_cols = f; }
     // (the first FFN's norm rides on the previous block's final_norm_ kernel, see run_layers -- unless the product folds it in: ln_gemm)
-    ln_gemm("ffn_fc1_silu", g1, EPI_SILU, second ? L.ffn2_ng : L.ffn1_ng, second ? L.ffn2_nb : L.ffn1_nb, norm_state, sg ? 2 : a16, x, n, rows, s);
+    ln_gemm("ffn_fc1_silu", g1, EPI_SILU, second ? L.ffn2_ng : L.ffn1_ng, second ? L.ffn2_nb : L.ffn1_nb, norm_done, sg ? 2 : a16, x, n, rows, s);
     GemmArgs g2{h, f, second ? L.ffn2_w2 : L.ffn1_w2, f, second ? L.ffn2_b2 : L.ffn1_b2, x, d, x, d, 0.5f, (int)rows, d, f};
     g2.a_bf16 = a16;
     g2.a_blocked = blocked ? 1 : 0;
@@ -957,14 +929,14 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
     const std::vector<SigW> *sigv = (!a16 && rows <= kSmallMRows) ? &sigma_weights() : nullptr;
     const bool sgm = sigv && !sigv->empty();
     const int ymode = sgm ? 2 : a16;                                 // LayerNorm / attention / conv output mode: 0 fp32, 1 bf16, 2 fp32 sigma
-    int ffn1_norm_state = 0;                                         // (ln_gemm: 1 = n holds the next ffn1's normalised rows, 2 = their statistics)
+    bool ffn1_norm_done = false;                                     // (ln_gemm: n holds the next ffn1's normalised rows)
     for (int l = first_layer; l < cfg.num_layers; ++l) {
         if (l > stop_layer || (l == stop_layer && stop_stage == 0)) break;
         const LayerW &L = layers[l];
         const int stage_cap = (l == stop_layer) ? stop_stage : 5;
         const SigW *sg = sgm ? &(*sigv)[l] : nullptr;
-        ffn(w, L, false, rows, s, ffn1_norm_state, sg);                              // ffn1_  :197
-        ffn1_norm_state = 0;
+        ffn(w, L, false, rows, s, ffn1_norm_done, sg);                               // ffn1_  :197
+        ffn1_norm_done = false;
         if (stage_cap == 1) break;
         // ConformerAttention::forward  :180-186
         {
@@ -974,7 +946,7 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
             g.a_bf16 = a16;
             g.out_bf16 = att16 ? 1 : 0;
             if (sg) { g.a_sigma = 1; g.W_sig = sg->wqkv; }
-            ln_gemm("attn_qkv", g, EPI_NONE, L.att_ng, L.att_nb, 0, ymode, x, n, rows, s);
+            ln_gemm("attn_qkv", g, EPI_NONE, L.att_ng, L.att_nb, false, ymode, x, n, rows, s);
         }
         const int hd = d / cfg.num_heads;
         double fl = 0.0;                                             // QK^T + QP^T (needed band) + AV over every (utterance, head)
@@ -1002,7 +974,7 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
             g.a_bf16 = a16;
             g.fast_act = a16;
             if (sg) { g.a_sigma = 1; g.W_sig = sg->pw1; }
-            ln_gemm("conv_pw1_glu", g, EPI_GLU, L.cv_ng, L.cv_nb, 0, ymode, x, n, rows, s);
+            ln_gemm("conv_pw1_glu", g, EPI_GLU, L.cv_ng, L.cv_nb, false, ymode, x, n, rows, s);
         }
         KL("dwconv_bn_silu", (double)rows * d * cfg.conv_kernel_size * 2.0, 2.0 * rows * d * 4,
            launch_dwconv_bn_silu(w.g.as<float>(), rg ? 1 : B, rg ? (int)rows : T, d, cfg.conv_kernel_size, L.dw_w, L.dw_b, L.bn_mean, L.bn_rstd, L.bn_g, L.bn_b,
@@ -1014,7 +986,7 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
             run_gemm("conv_pw2_resid", g, EPI_RESID, s);
         }
         if (stage_cap == 3) break;
-        ffn(w, L, true, rows, s, 0, sg);                                             // ffn2_  :201
+        ffn(w, L, true, rows, s, false, sg);                                         // ffn2_  :201
         if (stage_cap == 4) break;
         const bool next_runs = l + 1 < cfg.num_layers && !(l + 1 > stop_layer || (l + 1 == stop_layer && stop_stage == 0));
         bool next_folds = false;   // the next block's fc1 folds its own norm in (small fp32 batches): final_norm_ alone here
@@ -1023,18 +995,10 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
             pg.W_sig = (*sigv)[l + 1].ffn1_w1; pg.ln_g = layers[l + 1].ffn1_ng; pg.ln_b = layers[l + 1].ffn1_nb;
             next_folds = ln_folds(pg, EPI_SILU, rows);
         }
-        bool next_stats = false;   // large fp32 batches: the next block's fc1 normalises from row statistics -- final_norm_ written, its rows' statistics beside it
-        if (next_runs && !next_folds && !sg) {
-            GemmArgs pg{n, d, layers[l + 1].ffn1_w1, d, layers[l + 1].ffn1_b1, w.hbuf.as<float>(), cfg.ffn_intermediate, nullptr, 0, 1.0f, (int)rows, cfg.ffn_intermediate, d};
-            next_stats = ln_stats_folds(pg, EPI_SILU, layers[l + 1].ffn1_ng, layers[l + 1].ffn1_nb, x, n);
-        }
-        if (next_runs && next_stats) {
-            KL("layernorm_then_stats", 0.0, 2.0 * rows * d * 4, launch_layernorm_then_stats(x, rows, d, L.fin_g, L.fin_b, 1e-5f, x, n, s));
-            ffn1_norm_state = 2;
-        } else if (next_runs && !next_folds) {   // final_norm_ :202 and the next block's ffn1_ norm :40 in one pass over the rows
+        if (next_runs && !next_folds) {   // final_norm_ :202 and the next block's ffn1_ norm :40 in one pass over the rows
             KL("layernorm", 0.0, 3.0 * rows * d * 4,
                launch_layernorm2(x, rows, d, L.fin_g, L.fin_b, layers[l + 1].ffn1_ng, layers[l + 1].ffn1_nb, 1e-5f, x, n, s, ymode));
-            ffn1_norm_state = 1;
+            ffn1_norm_done = true;
         } else {
             KL("layernorm", 0.0, 2.0 * rows * d * 4, launch_layernorm(x, rows, d, L.fin_g, L.fin_b, 1e-5f, x, s));   // final_norm_ :202
         }
@@ -1117,28 +1081,11 @@ void Model::run_ctc(Workspace &w, const float *d_enc, int B, int T, bool want_lo
                            w.start.as<int>(), w.end.as<int>(), w.conf.as<float>(), s, pitch, seq));
 }
 
-// The decode loop's poll ahead of the chunk's end (run_tdt_loop).  EXPERIMENTAL builds: PK_DEC_POLL_AHEAD=0 keeps the synchronising poll.
-static bool poll_ahead_on() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_DEC_POLL_AHEAD"); return e ? atoi(e) != 0 : true; }();
-    return on;
-#else
-    return true;
-#endif
-}
-
 // Frame window of the small-batch decode loop (TdtState::F): the largest lock-step batch that gets one.  Measured (profiles/r06_dec_window_ab.txt, pk_transcribe_pcm,
 // median of 100 calls): one clip 4.96-5.00 -> 4.84 ms on the benchmark's clips (81 tokens in 112 decisions: a blank-poor case); two clips no change; four clips
 // + 4 % (the walked decisions of one utterance hold up the step of the other three, and a window of four frames ends at the first long blank) -> single
-// utterances only.  EXPERIMENTAL builds: PK_DEC_WIN=<largest batch> (0: off).
-static int decode_window_rows() {
-#ifdef PK_EXPERIMENTAL
-    static const int n = [] { const char *e = getenv("PK_DEC_WIN"); return e ? atoi(e) : 1; }();
-    return n;
-#else
-    return 1;
-#endif
-}
+// utterances only.
+static constexpr int kDecodeWindowRows = 1;
 
 // tdt_greedy_decode(_with_timestamps) / rnnt_greedy_decode  (src/tdt.cpp:36-201, src/rnnt.cpp:56-177)
 // enc_proj_ hoisted out of the symbol loop: one GEMM over all frames (the reference recomputes it per symbol, src/tdt.cpp:17)
@@ -1193,9 +1140,6 @@ void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t
     // what they produced the step before -- those rows are skipped (~2/3 of all utterance-steps on the benchmark's clips).  Per-phase loop only
     // (the single-launch loop keeps every row), lock-step batches up to kMaxListRows.
     bool pred_cache = B <= kMaxListRows && decode_loop != PK_DECODE_LOOP_PERSISTENT;
-#ifdef PK_EXPERIMENTAL
-    { static const bool off = [] { const char *e = getenv("PK_DEC_NOCACHE"); return e && atoi(e) != 0; }(); if (off) pred_cache = false; }
-#endif
     if (pred_cache) {
         st.need = ib + 6 * B + 8;                                    // (behind done_count and the persistent loop's two spare words)
         st.pp = w.pp.as<float>();
@@ -1204,7 +1148,7 @@ void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t
         // Frame window (TdtState::F): at B <= 8 the heads product's 16-row tile has room for the joint of the next frames under the unchanged prediction-net
         // state, and the decision kernel walks through the blanks inside it.  Offline greedy decode of the exact fp32 phases only.
         const bool dec16_ = cfg.gemm_bf16 && Hp % 32 == 0 && J % 32 == 0 && wld16;
-        if (B <= decode_window_rows() && !keep_state && !boost_on && !w.force_label && !dec16_ && !dec_nt_weights && J <= 1024 && V + D <= 5 * 256)
+        if (B <= kDecodeWindowRows && !keep_state && !boost_on && !w.force_label && !dec16_ && J <= 1024 && V + D <= 5 * 256)
             st.F = B <= 2 ? 8 : B <= 4 ? 4 : B <= 8 ? 2 : 1;
         w.z.reserve((size_t)B * st.F * J * sizeof(float));
         w.logits.reserve((size_t)B * st.F * (V + D) * sizeof(float));
@@ -1246,8 +1190,6 @@ void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t
         SkinnyArgs &a = P.heads;
         a.X = w.z.as<float>(); a.W = wld_s; a.B = B * st.F; a.N = V + D; a.K = J; a.bias = bld; a.out = w.logits.as<float>(); a.ldo = V + D;   // (rows b * F + f)
     }
-    for (int l = 0; l < L; ++l) P.cell[l].nt_weights = dec_nt_weights;
-    P.act.nt_weights = P.heads.nt_weights = dec_nt_weights;
     if (pred_cache) {
         for (int l = 0; l < L; ++l) P.cell[l].need = st.need;
         P.act.need = st.need;
@@ -1298,9 +1240,6 @@ void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t
     // a streaming chunk of 1-3 frames is done after T + (symbols of its busiest stream) steps -- every step launched beyond that is four no-op
     // kernels of ~6 us each, more than the poll costs
     int chunk = T + 2 < 4 ? 4 : (T + 2 < 16 ? T + 2 : 16);
-#ifdef PK_EXPERIMENTAL
-    { static const int c = [] { const char *e = getenv("PK_DEC_CHUNK"); return e ? atoi(e) : 0; }(); if (c > 0) chunk = c; }
-#endif
     auto skinny = [&](const SkinnyArgs &a, int epi) { if (dec16) launch_skinny_gemm_bf16(a, epi, s); else launch_skinny_gemm(a, epi, s); };
     auto enqueue_step = [&]() {
         for (int l = 0; l < L; ++l) {
@@ -1345,7 +1284,7 @@ void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t
     // steps behind it keep the GPU busy while the host wakes up and enqueues the next chunk (a wake-up measured at 20-24 us per poll in the single-clip
     // trace, profiles/r06_single_clip_kernel_stats.md; if the copy says "finished", the steps behind it were two no-op steps).  A streaming chunk's loop
     // (before_poll set: its result copies ride on the poll and must be the last thing enqueued) keeps the plain form.
-    const int ahead = (!w.before_poll && !keep_state && chunk >= 8 && poll_ahead_on()) ? 2 : 0;
+    const int ahead = (!w.before_poll && !keep_state && chunk >= 8) ? 2 : 0;
     if (ahead && !w.poll_ev) PK_HIP(hipEventCreateWithFlags(&w.poll_ev, hipEventDisableTiming));
     bool copy_pending = false;                                         // a poll's copy into h_done is enqueued and has not been waited for
     for (int step = 0; step < st.max_steps; ++step) {

@@ -223,15 +223,6 @@ __global__ __launch_bounds__(256) void tdt_decide_kernel(TdtState st) {
     extern __shared__ __attribute__((aligned(16))) float sm[];     // x[V+D], e[V+D], scratch[16] (+ BOOST: mask, active sets)
     tdt_decide_one<BOOST, false, SCORE, FAST, NC>(st, blockIdx.x, sm);
 }
-// The tolerance-class mode's plain greedy step on the register-resident form (decode_dev.hpp: FAST).  EXPERIMENTAL builds: PK_DEC_FAST=0 keeps the exact form.
-static bool decide_fast_on() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_DEC_FAST"); return e ? atoi(e) != 0 : true; }();
-    return on;
-#else
-    return true;
-#endif
-}
 void launch_tdt_decide(const TdtState &st, hipStream_t s) {
     const size_t lds = (size_t)(((st.F > 1 ? st.F : 1) + 1) * (st.V + st.D) + 16) * sizeof(float);     // (frame window: its F rows in front of the scratch)
     if (st.F > 1 && (st.V + st.D > 5 * 256 || st.F > kDecWindowMax || st.trie.off || st.force_label || st.h_bf16)) {
@@ -242,7 +233,7 @@ void launch_tdt_decide(const TdtState &st, hipStream_t s) {
         hipLaunchKernelGGL(tdt_decide_kernel<true>, dim3(st.B), dim3(256), lds + extra, s, st);
     } else if (st.force_label) {
         hipLaunchKernelGGL((tdt_decide_kernel<false, true>), dim3(st.B), dim3(256), lds, s, st);      // pk_tdt_score
-    } else if (st.h_bf16 && st.V + st.D <= 33 * 256 && st.V >= 2 && decide_fast_on()) {
+    } else if (st.h_bf16 && st.V + st.D <= 33 * 256 && st.V >= 2) {         // the tolerance-class mode's plain greedy step on the register-resident form (decode_dev.hpp: FAST)
         if (st.L * st.Hp <= 3 * 256) hipLaunchKernelGGL((tdt_decide_kernel<false, false, true, 3>), dim3(st.B), dim3(256), lds, s, st);
         else if (st.L * st.Hp <= 6 * 256) hipLaunchKernelGGL((tdt_decide_kernel<false, false, true, 6>), dim3(st.B), dim3(256), lds, s, st);
         else hipLaunchKernelGGL((tdt_decide_kernel<false, false, true>), dim3(st.B), dim3(256), lds, s, st);

@@ -49,15 +49,6 @@ template <bool COH> __device__ __forceinline__ void dd_sti(int *p, int v) {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// 16 bytes of the weight stream: plain, or with the non-temporal (streaming) hint
-template <bool NT> __device__ __forceinline__ float4 dd_ldw(const float4 *p) {
-    if constexpr (NT) {
-        const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
-        return make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        return *p;
-    }
-}
 
 __device__ __forceinline__ int sigma16(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
 
@@ -106,13 +97,11 @@ __device__ __forceinline__ int dd_build_rowlist(const int *need, int B, int *lst
 // COH = the operands other workgroups of the SAME kernel produced (X, c, the token / frame words, gi of the upper LSTM layers) are
 // read, and the outputs written, with system-scope accesses (sc0 sc1: no cache between the workgroups) -- the persistent decode
 // kernel (decode_persist.hip) runs every phase of a step inside one launch.
-// NTW: the weight stream is loaded non-temporally (streaming hint: the decode weights of the large heads -- 42 MB per symbol step for tdt-600m --
-// pass through each XCD's 4 MB L2 once per step and otherwise evict the operand tiles of the encoder GEMMs running beside the loop).
 // WF > 1 (SK_ACT only): the frame-window form of the joint activation (TdtState::F) -- utterance b's rows b * F + f of z take relu(enc_proj[t_b + f] + pp), f < a.F <= WF.
 // PRED (a.need set, B <= 16: the whole batch is one row tile): no compacted row list -- the need flags are requested FIRST, together with every other operand, the
 // launch leaves after the first operand chunk is under way if no flag is set, and the epilogue stores only the flagged rows.  Building the list first put a memory
 // round trip (flags) in front of the launch's own loads: ~1 us of a ~5 us launch, twice per symbol step.  A row's chain does not depend on its neighbours: same bits.
-template <int EPI, int NCH, bool COH, bool NTW = false, int WF = 1, bool PRED = false>
+template <int EPI, int NCH, bool COH, int WF = 1, bool PRED = false>
 __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgroup, float (*tile)[16][17], const int *rows = nullptr, int n_rows = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, kq = lane >> 4;
@@ -191,7 +180,7 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
 #define SK_LOAD(X_, W_, c_)                                                         \
     _Pragma("unroll") for (int i = 0; i < CH; ++i) {                               \
         X_[i] = dd_ld4<COH>(xq + 4 * ((c_) * CH + i));                              \
-        W_[i] = dd_ldw<NTW>(wq + 4 * ((c_) * CH + i));                               \
+        W_[i] = wq[4 * ((c_) * CH + i)];                               \
     }                                                                               \
     __builtin_amdgcn_sched_barrier(0);
 #define SK_MMA(X_, W_)                                                              \

@@ -27,9 +27,6 @@
 #include "gemm_pipe.hpp"
 #include "gemm_bf16.hpp"
 #include "gemm_bf16_glds.hpp"
-#ifdef PK_EXPERIMENTAL
-#include "gemm_bf16_ring.hpp"
-#endif
 
 namespace pk {
 
@@ -197,63 +194,30 @@ static void launch_one(const GemmArgs &a, hipStream_t s) {
 // Tile choice, from tools/ubench/gemm_sweep on MI355X (profiles/r01_gemm_sweep.txt): the pipelined kernels win where
 // the K loop is short (most of the encoder is K = 512); wide outputs like 128x128 tiles on 8 waves, long-K / narrow-N
 // products 128x64, everything else 64x64 (more resident workgroups to overlap one tile's epilogue with another's MFMAs).
-// Variant mask of the tile table.  Bits: 1 = long-K single-round products (fc2, sub_proj) on the single-buffered 128x128 / 8 waves of 32x64 /
-// BK 64 tile; 2 = wide outputs (fc1, qkv, sub_pw) single-buffered; 4 = out_proj / pw2 on sb 64x128 / 4 waves; 8 = GLU on sb; 16 = wide outputs
-// on sb BK 64; 64 = out_proj / pw2 on sb 128x128 / 8 waves; 256 = the long-K single-round products (fc2, sub_proj) on 8 waves of 64x32 / BK 32 / sb (round 6: fc2 -1.4 %,
-// step -0.1 ms interleaved, profiles/r06_gemm_sweep_fc2_variants.txt).  331 = 75 + 256; 75 = what the engine measurements of round 2 picked
-// (profiles/r02_gemm_variant_ab.txt: step 20.44 -> 19.73 ms with 11; bit 4 is level; bit 64 takes out_proj / pw2 from 0.81 to 0.77 ms per step).
-// A production build has NO run-time switch: the mask is a constant.  Experiment builds (make EXPERIMENTAL=1 -> -DPK_EXPERIMENTAL) read
-// PK_GEMM_VARIANT for the interleaved A/B runs of tools/experiments/gemm_variant_ab.sh.
-static int gemm_variant_mask() {
-#ifdef PK_EXPERIMENTAL
-    static const int m = [] { const char *e = getenv("PK_GEMM_VARIANT"); return e ? atoi(e) : 331; }();
-    return m;
-#else
-    return 331;
-#endif
-}
-
+// The tile table of the round-2 and round-6 engine measurements (profiles/r02_gemm_variant_ab.txt: step 20.44 -> 19.73 ms; r06_gemm_sweep_fc2_variants.txt).
+// Variants measured and not kept (up to 4fb176f a run-time mask of EXPERIMENTAL builds, PK_GEMM_VARIANT): out_proj / pw2 on single-buffered
+// 64x128 tiles (level), wide outputs on BK 64 (behind), 192x128 tiles where they make a whole round of workgroups (profiles/r04_gemm_tile192_ab.txt:
+// qkv 1.97 -> 1.99 ms per step -- workgroups are handed out as slots free up, so a CU never idles for a 'round'), and the double-buffered forms of
+// the single-buffered tiles below.
 template <int EPI>
 static void launch_epi(const GemmArgs &a, hipStream_t s) {
     if (a.K < 64) { launch_one<64, 64, EPI>(a, s); return; }           // pipelined kernels need >= 2 K tiles
-    const int vm = gemm_variant_mask();
     // measured table: profiles/r01_gemm_sweep_v5.txt (128x128 tile on 8 waves of 32x64 wins for every wide output and for the
     // 321k-row subsampling products; long-K / narrow-N products like fc2 of the 110M model take 128x64)
     // long-K products whose 128x128 tiles fill the chip exactly once (fc2 / sub_proj of the 110M model: 252 tiles for 256 CUs): one
-    // 8-wave workgroup per CU with BK = 64 -- half the barriers per k, nothing to share the CU with (-6 % vs two 128x64 workgroups)
+    // 8-wave workgroup per CU, single-buffered -- 8 waves of 64 x 32, BK 32 (round 6): 2-3 % ahead of the BK 64 tile of 32 x 64 waves in the sweep
+    // (profiles/r06_gemm_sweep_fc2_variants.txt: 137 vs 140.5 us), which was itself -6 % against two 128x64 workgroups
     const int64_t tiles128 = (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (a.M >= 1024 && a.N >= 256 && a.K >= 1024 && a.K % 64 == 0 && tiles128 <= 256) {
-        // bit 256 (round 6): 8 waves of 64 x 32, BK 32, single-buffered -- 2-3 % ahead of the BK 64 tile in the sweep (profiles/r06_gemm_sweep_fc2_variants.txt: 137 vs 140.5 us)
-        if (vm & 256) launch_gemm_pipe<2, 4, 2, 1, 32, EPI, 1>(a, s);
-        else if (vm & 1) launch_gemm_pipe<4, 2, 1, 2, 64, EPI, 1>(a, s);
-        else launch_gemm_pipe<2, 4, 2, 1, 64, EPI>(a, s);
-        return;
-    }
+    if (a.M >= 1024 && a.N >= 256 && a.K >= 1024 && a.K % 64 == 0 && tiles128 <= 256) { launch_gemm_pipe<2, 4, 2, 1, 32, EPI, 1>(a, s); return; }
     // round 2: the SINGLE-buffered loop (template parameter NBUF = 1: half the LDS, two barriers per K tile) is ahead of the double-buffered
     // one on every large shape, in the micro-benchmark (tools/ubench/gemm_sweep ml: main loop 130-135 vs 118-125 TF) and, by less, in the
-    // engine (fc2 -8 %, fc1 -3.6 %, qkv -5 %, GLU -3 %): gemm_variant_mask().
+    // engine (fc2 -8 %, fc1 -3.6 %, qkv -5 %, GLU -3 %).
     if constexpr (EPI == EPI_NONE || EPI == EPI_RELU || EPI == EPI_SILU) {
         if (a.ln_stats) { launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, true>(a, s); return; }    // (gemm_ln_stats_applies: the wide-output tile below, LayerNorm applied while staging A)
     }
-    if (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))) {
-        // bit 128: 192x128 tiles (8 waves of 96x32) where they turn a fractional second round of the 512 resident 128x128 workgroups into one
-        // full round (attn_qkv of the 110M model at 64 x 10 s: 63 x 12 = 756 tiles = 1.48 rounds -> 42 x 12 = 504)
-        // Measured (profiles/r04_gemm_tile192_ab.txt): NO gain, qkv 1.97 -> 1.99 ms per step -- workgroups are handed out as slots free up, so a
-        // CU never idles for a 'round'; the bit stays off (results are bit-identical either way: same k order).
-        if constexpr (EPI != EPI_GLU) {
-            const int64_t tiles192 = (int64_t)((a.M + 191) / 192) * ((a.N + 127) / 128);
-            if ((vm & 128) && tiles192 <= 512 && tiles128 > 512 && tiles128 < 900) { launch_gemm_pipe<2, 4, 3, 1, 32, EPI, 1>(a, s); return; }
-        }
-        if ((vm & 16) && a.K % 64 == 0 && a.K >= 128) launch_gemm_pipe<4, 2, 1, 2, 64, EPI, 1>(a, s);
-        else if (vm & 2) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1>(a, s);
-        else launch_gemm_pipe<4, 2, 1, 2, 32, EPI>(a, s);
-    }
+    if (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1>(a, s);
     else if (a.M >= 1024 && a.N >= 256 && a.K >= 1024) launch_gemm_pipe<2, 2, 2, 1, 32, EPI>(a, s);
-    else if (a.M >= 1024 && a.N >= 256) {
-        if (vm & 64) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1>(a, s);
-        else if (vm & 4) launch_gemm_pipe<2, 2, 1, 2, 32, EPI, 1>(a, s);
-        else launch_gemm_pipe<2, 4, 1, 1, 32, EPI>(a, s);      // 64x128 on 8 waves of 32x32: out_proj / pw2 (-7 %)
-    }
+    else if (a.M >= 1024 && a.N >= 256) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1>(a, s);   // out_proj / pw2 on 128x128 / 8 waves (0.81 -> 0.77 ms per step)
     else launch_gemm_pipe<2, 2, 1, 1, 32, EPI>(a, s);
 }
 
@@ -285,8 +249,7 @@ void launch_gemm(const GemmArgs &a, int epi, hipStream_t s) {
     case EPI_GLU:
         if (a.K < 64) launch_one<128, 128, EPI_GLU>(a, s);
         else if (a.ln_stats) launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1, true>(a, s);
-        else if (gemm_variant_mask() & 8) launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1>(a, s);
-        else launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU>(a, s);
+        else launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1>(a, s);
         break;
     default: break;
     }
@@ -294,71 +257,41 @@ void launch_gemm(const GemmArgs &a, int epi, hipStream_t s) {
 
 // bf16 operands / fp32 accumulate (a.W points to bf16 weights [N][K]); K % 64 == 0
 // The direct-to-LDS bf16 kernel (gemm_bf16_glds.hpp; activations already bf16 in HBM), 256x256 macro tiles.  Measured inside the engine on
-// tdt-600m (profiles/r03_bf16_tile_ab.txt, PK_BF16_TILE in EXPERIMENTAL builds): it is ahead of the register-staged 128x128 kernel where one
-// operand is large -- fc1 (N = 4096: 6.70 -> 6.60 ms per step) and fc2 (K = 4096: 6.51 -> 6.11) -- and behind on qkv (2.50 -> 2.70), the GLU
-// product (1.75 -> 2.03) and the N = 1024 / K = 1024 products; 256x128 and 128x128-on-4-waves variants lose everywhere.  The second pass
-// (tools/ubench/gemm_bf16_k.cpp) found why: the 256-row tile count of those products falls between two rounds of the 256 CUs; with the tile
-// height chosen per product (below) the kernel is ahead everywhere.  Modes (EXPERIMENTAL builds, PK_BF16_TILE): 0 = off, 1 = that rule,
-// 2 = 256x128 everywhere, 3 = 128x128 on 4 waves of 64x64, 4 = 256x256 everywhere, 5 = 192x256 everywhere.
-// Persistent form of the direct-to-LDS kernel (gemm_bf16_glds.hpp: PERSIST; one workgroup per CU walks its tiles, the next tile's first K tile is
-// requested under the epilogue).  Built and measured in round 4 (profiles/r04_bf16_persist_ab.txt, interleaved A/B on one box, tdt-600m 32 x 30 s):
-// bit-for-bit the same results, qkv 2.45 -> 2.41 ms and GLU 1.82 -> 1.77 ms per step, but fc1 6.75 -> 7.17 (140 -> 150 us) and the step 27.62 ->
-// 27.94 ms: inside one launch the next tile cannot start before `s_waitcnt vmcnt(0)` has ALSO drained the epilogue's stores (gfx950 counts loads
-// and stores in one counter, and they complete out of order relative to each other), which costs more than the cold prologue and the
-// re-dispatch it removes; and the epilogue, confined to one 64 KB buffer, needs 8 row bands instead of 4.  OFF by default; EXPERIMENTAL builds:
-// PK_BF16_PERSIST=1 selects it.
-// Round 5: 2 = the persistent form with the DIRECT register epilogue (gemm_bf16_glds.hpp: operands swapped in the MFMA, no LDS / barrier / vector load
-// in the epilogue, both first K tiles of the next output tile requested before it) -- the production setting for the products without a residual
-// read whose tiles exceed one round of the CUs: bit-identical results, fc1 142 -> 134 us, qkv / GLU -4 %, the tdt-600m step 27.11 -> 26.73 ms
-// (profiles/r05_bf16_direct_epilogue_ab.txt, r05_bf16_ring_ab.txt: three interleaved repetitions each).  3 = the direct epilogue on one tile per
-// workgroup (-1.5 % on fc1 alone).  4 = the continuous-stream kernel of gemm_bf16_ring.hpp (ring of four 32-k slots, counted vmcnt): correct and
-// NOT faster than 2 -- the K loop is not bound by the DMA's latency (r05_bf16_ring_ab.txt; SQ counters r05_pmc_sq_600m_bf16_p*.md: the matrix pipe
-// is busy 31-33 % of the launch in every form).  EXPERIMENTAL builds: PK_BF16_PERSIST selects.
-static int bf16_glds_persist() {
-#ifdef PK_EXPERIMENTAL
-    static const int m = [] { const char *e = getenv("PK_BF16_PERSIST"); return e ? atoi(e) : 2; }();
-    return m;
-#else
-    return 2;
-#endif
-}
-// Instantiation flags of the direct-to-LDS bf16 kernels (gemm_bf16_glds.hpp / gemm_bf16_ring.hpp), EXPERIMENTAL builds: PK_BF16_FLAGS bit 1 = STAGGER,
-// bit 2 = ASMFRAG (hand-counted fragment reads), bit 4 = row-block walk of the persistent form (XCD x owns a block of tile rows:
-// fetch bytes per fc1 launch 176 -> 150 MB, time +1.5 %: off -- profiles/r05_bf16_rowblock_ab.txt), bit 8 = residual products accumulate ONTO the residual (GemmArgs::resid_init:
-// the accumulators start from resid / alpha + bias, read beside the first K tiles, instead of 49 MB of residual reads next to the 49 MB of stores at
-// the tail).  Measured (profiles/r05_bf16_resid_init_ab.txt): fc2 123 -> 144 us, out_proj / pw2 24.5 -> 34.5 us -- in the MFMA's C layout the residual
-// arrives as 96 four-byte loads per wave in front of the first MFMA, dearer than the coalesced float4 reads of the LDS epilogue: off.
-// Production: 2 (ASMFRAG: bit-identical, -0.7 % per tdt-600m step, profiles/r05_bf16_asmfrag_ab.txt).  With PK_BF16_PERSIST=4 the low two bits select
-// the ring kernel's form instead: 0 plain, 1 STAGGER, 2 PHASED, 3 PHASED + s_setprio -- every one of them measured level with the persistent
-// form on fc1 (117 us) and behind it on the step (profiles/r05_bf16_ring_ab.txt, r05_bf16_phased_ab.txt): three different K-loop schedules, one
-// time -- the loop is bound by what a CU can pull from L2 into LDS (64 KB per 64-k tile at ~14 B/clock against the 32 B/clock the MFMAs could use),
-// not by how the pulls are scheduled.
-static int bf16_glds_flags() {
-#ifdef PK_EXPERIMENTAL
-    static const int m = [] { const char *e = getenv("PK_BF16_FLAGS"); return e ? atoi(e) : 18; }();
-    return m;
-#else
-    return 18;
-#endif
-}
-static int bf16_glds_mode() {
-#ifdef PK_EXPERIMENTAL
-    static const int m = [] { const char *e = getenv("PK_BF16_TILE"); return e ? atoi(e) : 1; }();
-    return m;
-#else
-    return 1;
-#endif
-}
+// tdt-600m (profiles/r03_bf16_tile_ab.txt): it is ahead of the register-staged 128x128 kernel where one operand is large -- fc1 (N = 4096:
+// 6.70 -> 6.60 ms per step) and fc2 (K = 4096: 6.51 -> 6.11) -- and behind on qkv (2.50 -> 2.70), the GLU product (1.75 -> 2.03) and the
+// N = 1024 / K = 1024 products; 256x128 and 128x128-on-4-waves variants lose everywhere.  The second pass (tools/ubench/gemm_bf16_k.cpp) found
+// why: the 256-row tile count of those products falls between two rounds of the 256 CUs; with the tile height chosen per product (below) the
+// kernel is ahead everywhere.  (Up to 4fb176f, EXPERIMENTAL builds selected the other tile forms -- 256x128, 128x128 on 4 waves of 64x64, 256x256
+// or 192x256 everywhere -- with PK_BF16_TILE.)
+// Forms of the direct-to-LDS kernel measured and not kept (up to 4fb176f selected in EXPERIMENTAL builds by PK_BF16_PERSIST / PK_BF16_FLAGS):
+//  * persistent with the LDS epilogue (round 4, profiles/r04_bf16_persist_ab.txt, interleaved A/B on one box, tdt-600m 32 x 30 s): bit-for-bit
+//    the same results, qkv 2.45 -> 2.41 ms and GLU 1.82 -> 1.77 ms per step, but fc1 6.75 -> 7.17 (140 -> 150 us) and the step 27.62 -> 27.94 ms:
+//    inside one launch the next tile cannot start before `s_waitcnt vmcnt(0)` has ALSO drained the epilogue's stores (gfx950 counts loads and
+//    stores in one counter, and they complete out of order relative to each other), which costs more than the cold prologue and the re-dispatch
+//    it removes; and the epilogue, confined to one 64 KB buffer, needs 8 row bands instead of 4;
+//  * the continuous-stream kernel (ring of four 32-k slots, counted vmcnt; plain, STAGGER, PHASED, PHASED + s_setprio): correct and NOT faster
+//    than the persistent form -- the K loop is not bound by the DMA's latency (r05_bf16_ring_ab.txt, r05_bf16_phased_ab.txt; SQ counters
+//    r05_pmc_sq_600m_bf16_p*.md: the matrix pipe is busy 31-33 % of the launch in every form): it is bound by what a CU can pull from L2 into
+//    LDS (64 KB per 64-k tile at ~14 B/clock against the 32 B/clock the MFMAs could use), not by how the pulls are scheduled;
+//  * STAGGER (half the waves of a SIMD issue their DMA after the first MFMA group, profiles/r05_bf16_stagger_template_ab.txt) and the row-block walk of
+//    the persistent form (XCD x owns a block of tile rows: fetch bytes per fc1 launch 176 -> 150 MB, time +1.5 %, profiles/r05_bf16_rowblock_ab.txt);
+//  * residual products accumulated onto the residual in the un-swapped MFMA layout (GemmArgs::resid_init, profiles/r05_bf16_resid_init_ab.txt):
+//    fc2 123 -> 144 us, out_proj / pw2 24.5 -> 34.5 us -- the residual arrived as 96 four-byte loads per wave in front of the first MFMA, dearer
+//    than the coalesced float4 reads of the LDS epilogue.  The register residual epilogue of round 6 does the same arithmetic with 16-byte accesses.
+// What production runs (launch_gemm_bf16_glds): the persistent form with the DIRECT register epilogue (round 5) for the products without a residual
+// read whose tiles exceed one round of the CUs -- bit-identical results, fc1 142 -> 134 us, qkv / GLU -4 %, the tdt-600m step 27.11 -> 26.73 ms
+// (profiles/r05_bf16_direct_epilogue_ab.txt, r05_bf16_ring_ab.txt: three interleaved repetitions each) -- the direct epilogue on one tile per
+// workgroup otherwise, the register residual epilogue for the residual products (round 6), and hand-counted fragment reads (ASMFRAG: bit-identical,
+// -0.7 % per tdt-600m step, profiles/r05_bf16_asmfrag_ab.txt).
 
 // the one rule both launch_bf16_epi and gemm_bf16_blocked_handoff apply: the product runs on the tile-height-per-product direct-to-LDS kernels
 static bool bf16_glds_rule(int M, int N, int K) {
-    return bf16_glds_mode() == 1 && M >= 8192 && N >= 512 && K >= 128 && (int64_t)N * K >= (int64_t)1024 * 1024 && (N & 3) == 0;
+    return M >= 8192 && N >= 512 && K >= 128 && (int64_t)N * K >= (int64_t)1024 * 1024 && (N & 3) == 0;
 }
 bool gemm_bf16_blocked_handoff(int M, int N, int K, int epi, bool producer) {
     if (!bf16_glds_rule(M, N, K) || (N % 16) != 0 || (K % 64) != 0) return false;
-    if (!producer) return bf16_glds_persist() != 4;                 // every gemm_bf16_glds_kernel form reads the blocked A (the ring kernel does not)
-    const int p = bf16_glds_persist();
-    return (p == 2 || p == 3) && epi != EPI_RESID && (int64_t)(M + 31) * N < ((int64_t)1 << 31);   // the register epilogue writes it (callers set fast_act: bf16 mode)
+    if (!producer) return true;                                     // every gemm_bf16_glds_kernel form reads the blocked A
+    return epi != EPI_RESID && (int64_t)(M + 31) * N < ((int64_t)1 << 31);   // the register epilogue writes it (callers set fast_act: bf16 mode)
 }
 [[noreturn]] static void bf16_layout_bug(const char *what) {
     fprintf(stderr, "parakeet_amd: internal error: %s (GemmArgs::out_blocked / a_blocked on a kernel that does not implement it)\n", what);
@@ -368,53 +301,20 @@ bool gemm_bf16_blocked_handoff(int M, int N, int K, int epi, bool producer) {
 template <int EPI, bool A16>
 static void launch_bf16_epi(const GemmArgs &a, hipStream_t s) {
     if constexpr (A16) {
-        const int mode = bf16_glds_mode();
-        if (mode && a.M >= 2048 && a.N >= 512 && a.K >= 128 && (a.lda % 8) == 0 && (a.ldw % 8) == 0 && a.remap_rows == 0 && (a.ldo & 3) == 0 && (a.N & 3) == 0) {
-            if (mode != 1 && a.out_blocked) bf16_layout_bug("blocked output outside the production tile rule");
-            if (mode == 3) { launch_gemm_bf16_glds<2, 2, 2, 2, EPI>(a, s); return; }
-            if (mode == 2) { launch_gemm_bf16_glds<4, 2, 2, 2, EPI>(a, s); return; }
-            if (mode == 4) { launch_gemm_bf16_glds<4, 2, 2, 4, EPI>(a, s); return; }
-            if (mode == 5) { launch_gemm_bf16_glds<2, 4, 3, 2, EPI>(a, s); return; }
+        if (a.M >= 8192 && a.N >= 512 && a.K >= 128 && (a.lda % 8) == 0 && (a.ldw % 8) == 0 && a.remap_rows == 0 && (a.ldo & 3) == 0 && (a.N & 3) == 0 &&
+            (int64_t)a.N * a.K >= (int64_t)1024 * 1024) {
             // One tile per CU and round (128 KB of LDS): the kernel's time is rounds x (tile's K loop + ~12 us of prologue / epilogue), so the tile
             // HEIGHT is chosen per product for the fewest, fullest rounds of the 256 CUs (tools/ubench/gemm_bf16_k.cpp, profiles/r03_gemm_bf16_k.txt:
             // main loop 1.3 PF on either tile).  tdt-600m (M = 12032): fc1 (N 4096) 752 tiles of 256 rows = 2.94 rounds; fc2 / out / pw2 (N 1024) 252
             // tiles of 192 rows = ONE round (188 of 256 rows leave 68 CUs idle: 113 -> 99 us); qkv (N 3072) 756 of 192 = 2.95 rounds (564 of 256 = 2.2).
-            if (mode == 1 && a.M >= 8192 && (int64_t)a.N * a.K >= (int64_t)1024 * 1024) {
-                constexpr int NOUT = (EPI == EPI_GLU) ? 128 : 256;
-                auto est = [&](int R) {
-                    const int64_t tiles = (int64_t)((a.M + R - 1) / R) * ((a.N + NOUT - 1) / NOUT);
-                    return (double)((tiles + 255) / 256) * ((double)R * a.K * 1.008e-4 + 12.0);
-                };
-                const bool tall = !(est(192) < est(256));
-#ifdef PK_EXPERIMENTAL                                             // (measured level with / behind the persistent form: not in the production library)
-                if constexpr (EPI != EPI_RESID) {
-                    // the continuous-stream form (gemm_bf16_ring.hpp): more tiles than CUs, no residual read
-                    constexpr int NO = (EPI == EPI_GLU) ? 128 : 256;
-                    const int64_t tiles = (int64_t)((a.M + (tall ? 256 : 192) - 1) / (tall ? 256 : 192)) * ((a.N + NO - 1) / NO);
-                    if (bf16_glds_persist() == 4 && tiles > 256 && gemm_bf16_ring_applies<EPI>(a)) {
-                        if (tall) launch_gemm_bf16_ring<4, 2, 2, 4, EPI>(a, s, bf16_glds_flags() & 3);
-                        else launch_gemm_bf16_ring<2, 4, 3, 2, EPI>(a, s, bf16_glds_flags() & 3);
-                        return;
-                    }
-                }
-#endif
-#ifdef PK_EXPERIMENTAL
-                if constexpr (EPI == EPI_RESID) {
-                    if ((bf16_glds_flags() & 8) != 0 && a.alpha != 0.0f && a.remap_rows == 0) {                      // (bit 8: measured 16-42 % slower per product: off)
-                        GemmArgs b = a;
-                        b.resid_init = 1;
-                        if (!tall) launch_gemm_bf16_glds<2, 4, 3, 2, EPI>(b, s, bf16_glds_persist(), (bf16_glds_flags() & 1) != 0, (bf16_glds_flags() & 2) != 0, (bf16_glds_flags() & 4) != 0);
-                        else launch_gemm_bf16_glds<4, 2, 2, 4, EPI>(b, s, bf16_glds_persist(), (bf16_glds_flags() & 1) != 0, (bf16_glds_flags() & 2) != 0, (bf16_glds_flags() & 4) != 0);
-                        return;
-                    }
-                }
-#endif
-                // bit 16 (round 6, production): residual products on the register epilogue with the accumulators started from the residual (gemm_bf16_glds.hpp)
-                const bool rd = (bf16_glds_flags() & 16) != 0;
-                if (!tall) launch_gemm_bf16_glds<2, 4, 3, 2, EPI>(a, s, bf16_glds_persist(), (bf16_glds_flags() & 1) != 0, (bf16_glds_flags() & 2) != 0, (bf16_glds_flags() & 4) != 0, rd);
-                else launch_gemm_bf16_glds<4, 2, 2, 4, EPI>(a, s, bf16_glds_persist(), (bf16_glds_flags() & 1) != 0, (bf16_glds_flags() & 2) != 0, (bf16_glds_flags() & 4) != 0, rd);
-                return;
-            }
+            constexpr int NOUT = (EPI == EPI_GLU) ? 128 : 256;
+            auto est = [&](int R) {
+                const int64_t tiles = (int64_t)((a.M + R - 1) / R) * ((a.N + NOUT - 1) / NOUT);
+                return (double)((tiles + 255) / 256) * ((double)R * a.K * 1.008e-4 + 12.0);
+            };
+            if (est(192) < est(256)) launch_gemm_bf16_glds<2, 4, 3, 2, EPI>(a, s);
+            else launch_gemm_bf16_glds<4, 2, 2, 4, EPI>(a, s);
+            return;
         }
     }
     if (a.out_blocked || a.a_blocked) bf16_layout_bug("blocked activation layout requested for the register-staged bf16 kernel");

@@ -180,7 +180,7 @@ __device__ __forceinline__ void gl_epilogue_direct(const GemmArgs &g, bg_f32x16 
 // of the tile next to the first two K tiles' DMA, and the accumulators are initialised with fma(resid, 1 / alpha, bias) (the bias through the scalar cache).  After
 // the K loop the epilogue is 24 multiplications by alpha and 16-byte stores from registers: no LDS round trip, no barrier, no load -- the three-band LDS
 // epilogue with its residual reads at the start of every band was a third of the narrow products' time.  Round 5 had tried the accumulate-onto-the-residual idea
-// in the UN-swapped layout (GemmArgs::resid_init: the residual as 96 four-byte loads per wave in front of the first MFMA) and measured it 16-42 % slower; this is
+// in the UN-swapped layout (GemmArgs::resid_init up to 4fb176f: the residual as 96 four-byte loads per wave in front of the first MFMA) and measured it 16-42 % slower; this is
 // the same arithmetic with 16-byte accesses.  alpha = 0.5 / 1: the scaling by 1 / alpha is exact; the K partial sums are added onto a value of the residual's
 // magnitude, i.e. rounded at ITS ulp (tolerance-class mode only: tests/test_gpu_bf16.py bounds it).  In place (out == resid): every lane reads and later writes its own elements.
 template <int WGM, int WGN, int TM, int TN>
@@ -245,13 +245,11 @@ __device__ __forceinline__ void gl_epilogue_resid_direct(const GemmArgs &g, bg_f
 
 // PERSIST (round 4): ONE workgroup per CU walks its tiles inside the launch.  Measured in round 3 (tools/ubench/gemm_bf16_k.cpp): the K loop runs
 // at 1.25-1.3 PF, the products of this model lose ~14 us per ROUND of tiles -- a cold two-tile DMA prologue on every CU at once, the epilogue,
-// the re-dispatch -- on K loops of only 16 tiles.  Here the first K tile of tile i+1 is requested (DMA into the staging buffer the last K tile
-// of tile i did not use) BEFORE the epilogue of tile i, which turns its accumulators row-major through the OTHER buffer only (64 KB: bands of
-// 32 rows); the second K tile follows right after the epilogue, and the K loop of tile i+1 starts on data that has long landed.  XCD x owns
-// the same contiguous range of tiles as in the one-tile-per-workgroup launch, dealt round-robin to its 32 workgroups.
-// PERSIST + DIRECT (round 5): with the register epilogue nothing after the last K tile's barrier touches LDS, so BOTH first K tiles of the next
-// output tile are requested before the epilogue starts; the wait at the top of the loop then covers DMA that landed microseconds ago and the
-// epilogue's own stores (one counter for loads and stores on gfx950), instead of a cold two-tile prologue per round of tiles.
+// the re-dispatch -- on K loops of only 16 tiles.  XCD x owns the same contiguous range of tiles as in the one-tile-per-workgroup launch, dealt
+// round-robin to its 32 workgroups.  With the register epilogue (DIRECT, round 5) nothing after the last K tile's barrier touches LDS, so BOTH
+// first K tiles of the next output tile are requested before the epilogue starts; the wait at the top of the loop then covers DMA that landed
+// microseconds ago and the epilogue's own stores (one counter for loads and stores on gfx950), instead of a cold two-tile prologue per round of
+// tiles.  (Round 4's persistent form with the LDS epilogue, measured slower, existed up to 4fb176f: gemm.hip.)
 // ASMFRAG (round 5): the fragment reads are inline-asm ds_read_b128 with hand-counted s_waitcnt lgkmcnt(N).  Left to the compiler, two of the
 // four MFMA groups of a K tile were preceded by `s_waitcnt lgkmcnt(0)` -- its wait for the fragments loaded one sub-step earlier also drained
 // the six reads just issued for the NEXT sub-step (it does not count across the loop's back edge), i.e. a whole LDS round trip in front of the
@@ -259,8 +257,10 @@ __device__ __forceinline__ void gl_epilogue_resid_direct(const GemmArgs &g, bg_f
 // Here the reads of sub-step s+1 stay in flight (lgkmcnt(TM + TN)) while the MFMAs of sub-step s issue; LDS reads return in order and no
 // scalar load is outstanding inside the loop.  The destination registers are tied to the wait by empty "+v" statements (cdna_hip_programming.md
 // 5.7 items 1 and 3), sched_barrier(0) keeps the MFMA builtins below them.
-template <int WGM, int WGN, int TM, int TN, int EPI, bool PERSIST = false, bool DIRECT = false, bool STAGGER = false, bool ASMFRAG = false>
-__global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs g, int tiles_n, int n_tiles, int rowblock = 0) {
+// Forms launched (launch_gemm_bf16_glds): PERSIST + DIRECT, DIRECT on one tile (with the register residual epilogue for EPI_RESID), and one tile with
+// the LDS epilogue of gemm_pipe.hpp (products the register epilogue does not take).
+template <int WGM, int WGN, int TM, int TN, int EPI, bool PERSIST, bool DIRECT, bool ASMFRAG>
+__global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs g, int tiles_n, int n_tiles) {
     constexpr int BK = 64, NSUB = BK / 16;                          // bf16 elements per tile row; MFMA k-steps per K tile
     constexpr int NT = 64 * WGM * WGN, NW = WGM * WGN;
     constexpr int WM = TM * 32, WN = TN * 32, BM = WGM * WM, BN = WGN * WN;
@@ -269,6 +269,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
     static_assert(NBLK % NW == 0, "blocks must split evenly over the waves");
     constexpr int NOUT = (EPI == EPI_GLU) ? BN / 2 : BN;
     static_assert(EPI != EPI_GLU || (TN % 2 == 0), "GLU needs an even number of column tiles per wave");
+    static_assert(!PERSIST || (DIRECT && EPI != EPI_RESID), "the persistent walk needs the register epilogue (and the residual one runs one tile per workgroup)");
     extern __shared__ __attribute__((aligned(16))) unsigned char gl_smem_raw[];
     __bf16 *smem = reinterpret_cast<__bf16 *>(gl_smem_raw);
     float *smem_f = reinterpret_cast<float *>(gl_smem_raw);
@@ -277,11 +278,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     const int wm = wave / WGN, wn = wave % WGN;
-    // STAGGER (round 5): waves w and w + NW / 2 share a SIMD; the second half requests its DMA pieces after the MFMA group that follows the
-    // barrier instead of before it, so that one wave of a SIMD issues LDS-DMA (60-185 clocks per 1 KB piece) while the other feeds the matrix
-    // pipe.  A template parameter: as a run-time flag the extra branches in the K loop cost more than the stagger gains
-    // (profiles/r05_bf16_stagger_runtime_flags_ab.txt).
-    const bool late = STAGGER && wv >= NW / 2;
     const int nk = g.K / BK;
     const __bf16 *A16 = reinterpret_cast<const __bf16 *>(g.A);
     const __bf16 *W16 = reinterpret_cast<const __bf16 *>(g.W);
@@ -301,20 +297,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
     const int x_first = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq, x_count = xq + (xcd < xr ? 1 : 0);
     const int per_xcd = PERSIST ? (int)(gridDim.x >> 3) : 1;        // workgroups per XCD walking that range (persistent: stride)
     int loc = idx;                                                  // index inside the XCD's range
-    // rowblock (persistent walk, round 5): XCD x owns a BLOCK OF TILE ROWS (tiles_m split as evenly as it goes) and walks it row-fastest -- its
-    // A rows (a few MB) stay in ITS L2 for the whole launch and only W streams through, instead of every XCD streaming (nearly) all of both.
-    // Measured (profiles/r05_bf16_rowblock_ab.txt, fc1 of tdt-600m): L2 fetch bytes per launch 176 -> 150 MB, bit-identical, and 1.5 % SLOWER
-    // (119.3 -> 121.2 us) -- the K loop is not waiting for the fabric behind L2.  Off in production (the launcher's rowblock_ok).
-    const int tiles_m_all = n_tiles / tiles_n;
-    const int rq = tiles_m_all >> 3, rr = tiles_m_all & 7;
-    const int r_first = xcd < rr ? xcd * (rq + 1) : rr * (rq + 1) + (xcd - rr) * rq, r_cnt = rq + (xcd < rr ? 1 : 0);
-    const bool rb = PERSIST && rowblock != 0;
-    const int x_cnt = rb ? r_cnt * tiles_n : x_count;
-    auto origin_of = [&](int l, int &m0, int &n0) {
-        if (rb) { m0 = (r_first + l % r_cnt) * BM; n0 = (l / r_cnt) * NOUT; }
-        else tile_origin(x_first + l, m0, n0);
-    };
-    if (loc >= x_cnt) return;                                       // (one-tile launches have exactly n_tiles workgroups)
+    if (loc >= x_count) return;                                     // (one-tile launches have exactly n_tiles workgroups)
 
     // DMA sources: wave w fills blocks w, w + NW, ...; lane q of block b supplies (row 8 b + q / 8, logical chunk (q % 8) ^ ((row >> 1) & 7)).
     // Rows 0 .. BM-1 of the stacked tile are A rows, BM .. BM+BN-1 are W rows.
@@ -416,7 +399,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
 
     const __bf16 *src[NBPW];
     int m0, n0;
-    origin_of(loc, m0, n0);
+    tile_origin(x_first + loc, m0, n0);
     set_src(m0, n0, src);
     int cur = 0;
     int tr_tile = 0;
@@ -425,30 +408,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
     if (nk > 1) dma(src, 1, 1);
     for (;;) {
         GL_STAMP(tr_tile, 0);
-        bool resid_in_acc = false;                                  // (EXPERIMENTAL builds only: measured slower, gemm.hip bf16_glds_flags bit 8)
-#ifdef PK_EXPERIMENTAL
-        if constexpr (EPI == EPI_RESID && !DIRECT && !PERSIST) resid_in_acc = g.resid_init != 0;
-#endif
         if constexpr (DIRECT && EPI == EPI_RESID) {
             gl_resid_init<WGM, WGN, TM, TN>(g, acc, m0, n0);        // (requested behind the first two K tiles' DMA: lands under the prologue wait)
-        } else if (resid_in_acc) {
-            // out = resid + alpha (A W^T + bias) accumulated ONTO the residual (GemmArgs::resid_init, tolerance-class mode): the accumulators start
-            // from resid / alpha + bias -- requested here, next to the first K tiles' DMA, instead of 49 MB of residual reads competing with the
-            // 49 MB of output stores at the kernel's tail -- and the epilogue stores alpha * acc.  C layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-            const float inv_alpha = 1.0f / g.alpha;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int col = n0 + wn * WN + j * 32 + (lane & 31);
-                const bool col_ok = col < g.N;
-                const float bs = (g.bias && col_ok) ? g.bias[col] : 0.0f;
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                        acc[i][j][r] = (col_ok && row < g.M) ? __builtin_fmaf(g.resid[(int64_t)row * g.ldr + col], inv_alpha, bs) : 0.0f;
-                    }
-            }
         } else {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -477,9 +438,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
             __syncthreads();               // ... for every wave; and every wave holds its last fragments of tile kt: buffer `cur` is free
             GL_STAMP(tr_tile, 2 + kt);
             if (more1) fragload(cur ^ 1, 0, 0);
-            if (more2 && !late) dma(src, kt + 2, cur);
+            if (more2) dma(src, kt + 2, cur);
             GL_SB(); mma((NSUB - 1) & 1); GL_SB();
-            if constexpr (STAGGER) { if (more2 && late) dma(src, kt + 2, cur); }
             // (compiler-scheduled reads only; ASMFRAG counts by hand)
             // The fragments read after the barrier are long in their registers by now (eight DMA issues and eight MFMAs later); saying so HERE
             // keeps the compiler from draining LDS at the top of the loop instead -- where its wait (it cannot count across the back edge: lgkmcnt(0))
@@ -491,13 +451,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
         // `cur` = the buffer the last K tile did NOT use (free since the barrier of the last iteration); the other one is free too once every
         // wave has passed that barrier -- which the epilogue's own first barrier guarantees again
         GL_STAMP(tr_tile, 2 + nk);
-        static_assert(!(PERSIST && DIRECT && EPI == EPI_RESID), "the register residual epilogue runs one tile per workgroup");
-        if constexpr (PERSIST && DIRECT) {
+        if constexpr (PERSIST) {
             const int em0 = m0, en0 = n0;
             loc += per_xcd;
-            const bool more = loc < x_cnt;
+            const bool more = loc < x_count;
             if (more) {                    // both staging buffers are free (every wave is past the last K tile's barrier, the epilogue uses none)
-                origin_of(loc, m0, n0);
+                tile_origin(x_first + loc, m0, n0);
                 set_src(m0, n0, src);
                 dma(src, 0, cur);
                 if (nk > 1) dma(src, 1, cur ^ 1);
@@ -512,34 +471,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
         } else if constexpr (DIRECT) {
             gl_epilogue_direct<WGM, WGN, TM, TN, EPI>(g, acc, m0, n0);
             break;
-        } else if constexpr (PERSIST) {
-            const int em0 = m0, en0 = n0;
-            loc += per_xcd;
-            const bool more = loc < x_cnt;
-            if (more) {                    // next tile: its first K tile streams into `cur` UNDER this tile's epilogue
-                origin_of(loc, m0, n0);
-                set_src(m0, n0, src);
-                dma(src, 0, cur);
-            }
-            gp_epilogue<WGM, WGN, TM, TN, EPI, BUF / 2, true>(g, acc, smem_f + (cur ^ 1) * (BUF / 2), em0, en0);   // one buffer: BUF bf16 = BUF / 2 floats
-            if (!more) break;
-            __syncthreads();               // every wave has read its last band out of the epilogue's buffer
-            if (nk > 1) dma(src, 1, cur ^ 1);
         } else {
-            if constexpr (EPI == EPI_RESID) {
-                if (resid_in_acc) {                                 // bias and residual are in the accumulators: scale, then the plain LDS epilogue
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) acc[i][j][r] = acc[i][j][r] * g.alpha;
-                    GemmArgs g2 = g;
-                    g2.bias = nullptr;
-                    gp_epilogue<WGM, WGN, TM, TN, EPI_NONE, BUF, true>(g2, acc, smem_f, m0, n0);
-                    break;
-                }
-            }
             gp_epilogue<WGM, WGN, TM, TN, EPI, BUF, true>(g, acc, smem_f, m0, n0);      // 2 buffers x BUF bf16 = BUF floats
             break;
         }
@@ -549,101 +481,42 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_glds_kernel(GemmArgs
 #undef GL_WAIT_LGKM0
 }
 
-// persist: 0 = one tile per workgroup, 1 = persistent with the LDS epilogue (round 4), 2 = persistent (more than 256 tiles) with the DIRECT
-// register epilogue, 3 = the direct epilogue on one tile per workgroup
+// The production forms (gemm.hip has the measurements): products without a residual read on the DIRECT register epilogue -- persistent (one
+// workgroup per CU) when the tiles exceed one round of the 256 CUs, one tile per workgroup otherwise -- residual products on the register residual
+// epilogue, and whatever the register epilogues cannot take (sigma columns, remapped rows, ragged N, polynomial activations, ...) on the LDS epilogue.
+template <int WGM, int WGN, int TM, int TN, int EPI, bool PERSIST, bool DIRECT, bool ASMFRAG>
+static void launch_gl_kernel(const GemmArgs &a, hipStream_t s, int grid, int tiles_n, int n_tiles) {
+    constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
+    constexpr size_t lds = 2 * (size_t)(BM + BN) * 64 * 2;
+    auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, PERSIST, DIRECT, ASMFRAG>;
+    static DynLdsSlots slots;
+    ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles);
+}
 template <int WGM, int WGN, int TM, int TN, int EPI>
-static void launch_gemm_bf16_glds(const GemmArgs &a, hipStream_t s, int persist = 0, bool stagger = false, bool asmfrag = false, bool rowblock_ok = false,
-                                  bool resid_direct = false) {
+static void launch_gemm_bf16_glds(const GemmArgs &a, hipStream_t s) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
     constexpr int NOUT = (EPI == EPI_GLU) ? BN / 2 : BN;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + NOUT - 1) / NOUT;
     const int n_tiles = tiles_m * tiles_n;
-    constexpr size_t lds = 2 * (size_t)(BM + BN) * 64 * 2;
-    // persistent walk by row blocks per XCD (kernel comment) when no XCD needs an extra round for it
-    const int rb_tiles = ((tiles_m + 7) / 8) * tiles_n, even_tiles = (n_tiles + 7) / 8;
-    const int rowblock = (rowblock_ok && tiles_m >= 8 && (rb_tiles + 31) / 32 <= (even_tiles + 31) / 32) ? 1 : 0;
     if constexpr (EPI != EPI_RESID) {
         const bool direct_ok = a.sigma_cols == 0 && a.remap_rows == 0 && (a.N % 16) == 0 && (a.ldo % 8) == 0 &&
                                (a.fast_act || (EPI != EPI_SILU && EPI != EPI_GLU)) && ((int64_t)(a.M + 31) * a.ldo < ((int64_t)1 << 31));
-        if (persist >= 2 && direct_ok) {
-            if (persist == 2 && n_tiles > 256) {
-#ifdef PK_EXPERIMENTAL
-                if (stagger) {
-                    auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, true, true, true>;
-                    static DynLdsSlots slots;
-                    ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-                    hipLaunchKernelGGL(kern, dim3(256), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, rowblock);
-                    return;
-                }
-#endif
-                if (asmfrag) {
-                    auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, true, true, false, true>;
-                    static DynLdsSlots slots;
-                    ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-                    hipLaunchKernelGGL(kern, dim3(256), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, rowblock);
-                    return;
-                }
-                auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, true, true>;
-                static DynLdsSlots slots;
-                ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-                hipLaunchKernelGGL(kern, dim3(256), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, rowblock);
-                return;
-            }
-            auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, false, true>;
-            static DynLdsSlots slots;
-            ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-            hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, 0);
+        if (direct_ok) {
+            if (n_tiles > 256) launch_gl_kernel<WGM, WGN, TM, TN, EPI, true, true, true>(a, s, 256, tiles_n, n_tiles);
+            else launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, true, false>(a, s, n_tiles, tiles_n, n_tiles);
             return;
         }
     }
     if (a.out_blocked) { fprintf(stderr, "parakeet_amd: internal error: blocked output on the LDS epilogue\n"); abort(); }
     if constexpr (EPI == EPI_RESID) {
         // the register residual epilogue (gl_resid_init / gl_epilogue_resid_direct): row-major fp32 in and out, whole 16-column groups, 32-bit offsets
-        const bool rd_ok = resid_direct && persist >= 2 && a.resid && a.alpha != 0.0f && !a.out_bf16 && !a.resid_init && a.sigma_cols == 0 && a.remap_rows == 0 &&
+        const bool rd_ok = a.resid && a.alpha != 0.0f && !a.out_bf16 && a.sigma_cols == 0 && a.remap_rows == 0 &&
                            (a.N % 16) == 0 && (a.ldo % 4) == 0 && (a.ldr % 4) == 0 && ((int64_t)(a.M + 31) * a.ldo < ((int64_t)1 << 31)) &&
                            ((int64_t)(a.M + 31) * a.ldr < ((int64_t)1 << 31));
-        if (rd_ok) {
-            if (asmfrag) {
-                auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, false, true, false, true>;
-                static DynLdsSlots slots;
-                ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-                hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, 0);
-            } else {
-                auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, false, true>;
-                static DynLdsSlots slots;
-                ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-                hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, 0);
-            }
-            return;
-        }
+        if (rd_ok) { launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, true, true>(a, s, n_tiles, tiles_n, n_tiles); return; }
     }
-#ifdef PK_EXPERIMENTAL
-    if (persist == 1 && n_tiles > 256) {                                // more than one round of the 256 CUs: one persistent workgroup per CU
-        auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, true>;
-        static DynLdsSlots slots;
-        ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-        hipLaunchKernelGGL(kern, dim3(256), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, rowblock);
-        return;
-    }
-    if (stagger) {
-        auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, false, false, true>;
-        static DynLdsSlots slots;
-        ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, 0);
-        return;
-    }
-#endif
-    if (asmfrag) {
-        auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, false, false, false, true>;
-        static DynLdsSlots slots;
-        ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, 0);
-        return;
-    }
-    auto kern = &gemm_bf16_glds_kernel<WGM, WGN, TM, TN, EPI, false>;
-    static DynLdsSlots slots;
-    ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
-    hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles, 0);
+    launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, false, true>(a, s, n_tiles, tiles_n, n_tiles);
 }
 
 }  // namespace pk

@@ -47,9 +47,6 @@ typedef float sb_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 sb_bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kSbMaxWaves = 8;      // waves per workgroup (2 per SIMD: 256 VGPRs each -- the up-front slices need them)
-#ifdef PK_EXPERIMENTAL
-__device__ int sb_sum_rev = 0;      // (set once from PK_SB_SUMREV by launch_gemm_smallm_bf16)
-#endif
 
 // Phase stamps for tools/ubench/smallm_bf16_trace.cpp (-DSB_TRACE): shader clock of lane 0 of every wave -- [workgroup][wave][8]: 0 kernel entry,
 // 1 every load of the slice issued, 2 activation rows arrived (first use), 3 LayerNorm applied / rows converted, 4 weights arrived + MFMAs issued,
@@ -63,7 +60,7 @@ __device__ unsigned long long *sb_trace;
 
 template <int EPI, int STEPS /* MFMA steps (32 k each) per K slice */, int RT /* 16-row MFMA tiles per wave */, bool A16 /* A is bf16 [M][lda] */,
           bool LN /* fold LayerNorm(A; ln_g, ln_b, ln_eps) in: A fp32, STEPS = 8 or 4, one slice per wave */,
-          int CT = 1 /* 16-column tiles per wave: the activation registers of a K slice feed CT weight tiles (round 5) */, bool NTW = false /* non-temporal weight loads */,
+          int CT = 1 /* 16-column tiles per wave: the activation registers of a K slice feed CT weight tiles (round 5) */,
           bool WT = false /* weights from the operand-tile copy GemmArgs::W_t16 */, bool DW = false /* EPI_GLU: the depthwise-conv tail (DwTail) */,
           bool AT = false /* A16: the rows in 8-row operand tiles (GemmArgs::a_t8) */,
           bool AL = false /* fp32 rows: the wave's K slice of the rows travels global -> LDS by DMA (1 KB of consecutive addresses per instruction) */,
@@ -225,8 +222,7 @@ __global__ __launch_bounds__(64 * kSbMaxWaves) void gemm_smallm_bf16_kernel(Gemm
 #pragma unroll
                 for (int s = 0; s < STEPS; ++s) {
                     const sb_bf16x8 *src = reinterpret_cast<const sb_bf16x8 *>(WT ? wp[h][c] + (k0 / 32 + s) * 512 : wp[h][c] + k0 + 32 * s);
-                    if constexpr (NTW) w[h][c][s] = __builtin_nontemporal_load(src);      // each weight byte is read once per chunk: do not keep it
-                    else w[h][c][s] = *src;
+                    w[h][c][s] = *src;
                 }
         __builtin_amdgcn_sched_barrier(0);                          // every load of the slice is issued before anything waits
         SB_STAMP(1);
@@ -386,23 +382,11 @@ __global__ __launch_bounds__(64 * kSbMaxWaves) void gemm_smallm_bf16_kernel(Gemm
     const int t = et;                                               // this wave finishes row tile et of column tile ec
     sb_f32x4 v = acc[0][0][0], gt = acc[NW - 1][0][0];              // (split == 1: RT = CT = 1)
     if (split > 1) {
-#ifdef PK_EXPERIMENTAL
-        if (sb_sum_rev) {                                           // PK_SB_SUMREV=1: the slices met in REVERSE wave order (round 6: how much of the mode's distance from fp32 is summation order)
-            v = part(split - 1, 0, ec, t)[lane];
-            for (int w2 = split - 2; w2 >= 0; --w2) v += part(w2, 0, ec, t)[lane];
-            if constexpr (EPI == EPI_GLU) {
-                gt = part(split - 1, 1, ec, t)[lane];
-                for (int w2 = split - 2; w2 >= 0; --w2) gt += part(w2, 1, ec, t)[lane];
-            }
-        } else
-#endif
-        {
         v = part(0, 0, ec, t)[lane];
         for (int w2 = 1; w2 < split; ++w2) v += part(w2, 0, ec, t)[lane];
         if constexpr (EPI == EPI_GLU) {
             gt = part(0, 1, ec, t)[lane];
             for (int w2 = 1; w2 < split; ++w2) gt += part(w2, 1, ec, t)[lane];
-        }
         }
     }
     if (col >= g.N) return;
@@ -503,23 +487,10 @@ static int sb_rows_per_wg(const GemmArgs &a, int nslices, bool glu, int tiles) {
     return 8;
 }
 
-// Tuning of the column tiles per wave (CT) and the weight-load cache policy.  A production build has the heuristic below; experiment builds
-// (make EXPERIMENTAL=1) read PK_SB_CT (0 = the heuristic) / PK_SB_NT / PK_SB_ROWS (0 = the heuristic) / PK_SB_WT (0: ignore the operand-tile
-// copy) / PK_SB_AL (0: fp32 rows by per-lane loads instead of LDS-DMA) for A/B runs (tools/experiments/).
-struct SbTune { int ct, nt, rows, wt, al; };
-static SbTune sb_tune() {
-#ifdef PK_EXPERIMENTAL
-    static const SbTune t = [] {
-        auto rd = [](const char *k, int d) { const char *e = getenv(k); return e ? atoi(e) : d; };
-        return SbTune{rd("PK_SB_CT", 0), rd("PK_SB_NT", 0), rd("PK_SB_ROWS", 0), rd("PK_SB_WT", 1), rd("PK_SB_AL", 1)};
-    }();
-    return t;
-#else
-    return SbTune{0, 0, 0, 1, 1};
-#endif
-}
-
-template <int EPI, int STEPS, bool A16, bool LN, int CT, bool NTW, bool WT>
+// Launch forms measured and not kept (up to 4fb176f selected in EXPERIMENTAL builds by PK_SB_CT / PK_SB_NT / PK_SB_ROWS / PK_SB_WT / PK_SB_AL):
+// forced column tiles per wave or rows per workgroup, non-temporal weight loads, the weights in their natural layout where the operand-tile copy
+// exists, and fp32 rows by per-lane loads instead of LDS-DMA.
+template <int EPI, int STEPS, bool A16, bool LN, int CT, bool WT>
 static void launch_sb_ct(const GemmArgs &a, hipStream_t s, int R) {
     const int nslices = a.K / (32 * STEPS);
     const int split = nslices < kSbMaxWaves ? nslices : kSbMaxWaves;
@@ -527,90 +498,68 @@ static void launch_sb_ct(const GemmArgs &a, hipStream_t s, int R) {
     if (EPI == EPI_GLU && R == 32) R = 16;
     if (R == 32 && (CT > 1 || split < 2 || a.pre_g)) R = 16;                   // two row tiles per wave: one column tile (registers), a wave per output tile
     const dim3 grid(tiles, (a.M + R - 1) / R), block(64 * split);
-    if constexpr (EPI == EPI_RESID && A16 && CT == 1 && !NTW) {
-        if (a.a_t8 && R == 32) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 2, A16, LN, 1, false, WT, false, true>), grid, block, 0, s, a, split, 16, DwTail{}); return; }
+    if constexpr (EPI == EPI_RESID && A16 && CT == 1) {
+        if (a.a_t8 && R == 32) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 2, A16, LN, 1, WT, false, true>), grid, block, 0, s, a, split, 16, DwTail{}); return; }
     }
     if constexpr (EPI != EPI_GLU && CT == 1) {
-        if (R == 32) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 2, A16, LN, CT, NTW, WT>), grid, block, 0, s, a, split, 16, DwTail{}); return; }
+        if (R == 32) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 2, A16, LN, CT, WT>), grid, block, 0, s, a, split, 16, DwTail{}); return; }
     }
     // a norm in front of the folded one (GemmArgs::pre_g; the caller checked gemm_smallm_bf16_pre_applies): fc1 of a streaming block
-    if constexpr (LN && EPI == EPI_SILU && !NTW && STEPS == 8) {
+    if constexpr (LN && EPI == EPI_SILU && STEPS == 8) {
         if (a.pre_g) {
             if constexpr (WT) {
-                if (sb_tune().al) {
-                    constexpr size_t lds = (size_t)kSbMaxWaves * 16 * (4 * 32 * STEPS + 16);
-                    static DynLdsSlots slots_pre;
-                    ensure_dyn_lds(slots_pre, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, false, WT, false, false, true, true>), lds);
-                    hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, false, WT, false, false, true, true>), grid, block, lds, s, a, split, R, DwTail{});
-                    return;
-                }
+                constexpr size_t lds = (size_t)kSbMaxWaves * 16 * (4 * 32 * STEPS + 16);
+                static DynLdsSlots slots_pre;
+                ensure_dyn_lds(slots_pre, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true, true>), lds);
+                hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true, true>), grid, block, lds, s, a, split, R, DwTail{});
+            } else {
+                hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, false, true>), grid, block, 0, s, a, split, R, DwTail{});
             }
-            hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, false, WT, false, false, false, true>), grid, block, 0, s, a, split, R, DwTail{});
             return;
         }
     }
-    // fp32 rows of one row tile: the wave's slice of the rows by LDS-DMA (template AL) -- production: with the operand-tiled weights
-    if constexpr (!A16 && STEPS == 8 && WT && !NTW) {
-        if (sb_tune().al) {
-            constexpr size_t lds = (size_t)kSbMaxWaves * 16 * (4 * 32 * STEPS + 16);
-            static DynLdsSlots slots, slots_dw;
-            if constexpr (EPI == EPI_GLU && CT == 1) {
-                if (a.dw_tail) {
-                    ensure_dyn_lds(slots_dw, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, false, WT, true, false, true>), lds);
-                    hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, false, WT, true, false, true>), grid, block, lds, s, a, split, R, *a.dw_tail);
-                    return;
-                }
+    if constexpr (!A16 && STEPS == 8 && WT) {
+        // fp32 rows of one row tile: the wave's slice of the rows by LDS-DMA (template AL), with the operand-tiled weights
+        constexpr size_t lds = (size_t)kSbMaxWaves * 16 * (4 * 32 * STEPS + 16);
+        static DynLdsSlots slots, slots_dw;
+        if constexpr (EPI == EPI_GLU && CT == 1) {
+            if (a.dw_tail) {
+                ensure_dyn_lds(slots_dw, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, true, false, true>), lds);
+                hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, true, false, true>), grid, block, lds, s, a, split, R, *a.dw_tail);
+                return;
             }
-            ensure_dyn_lds(slots, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, false, WT, false, false, true>), lds);
-            hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, false, WT, false, false, true>), grid, block, lds, s, a, split, R, DwTail{});
-            return;
         }
+        ensure_dyn_lds(slots, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true>), lds);
+        hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true>), grid, block, lds, s, a, split, R, DwTail{});
+    } else {
+        if constexpr (EPI == EPI_GLU && CT == 1) {
+            if (a.dw_tail) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, true>), grid, block, 0, s, a, split, R, *a.dw_tail); return; }
+        }
+        if constexpr (EPI == EPI_RESID && A16 && CT == 1) {
+            if (a.a_t8) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, false, true>), grid, block, 0, s, a, split, R, DwTail{}); return; }
+        }
+        hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT>), grid, block, 0, s, a, split, R, DwTail{});
     }
-    if constexpr (EPI == EPI_GLU && CT == 1 && !NTW) {
-        if (a.dw_tail) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, false, WT, true>), grid, block, 0, s, a, split, R, *a.dw_tail); return; }
-    }
-    if constexpr (EPI == EPI_RESID && A16 && CT == 1 && !NTW) {
-        if (a.a_t8) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, false, WT, false, true>), grid, block, 0, s, a, split, R, DwTail{}); return; }
-    }
-    hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, NTW, WT>), grid, block, 0, s, a, split, R, DwTail{});
 }
 
 template <int EPI, int STEPS, bool A16, bool LN, bool WT>
 static void launch_sb_wt(const GemmArgs &a, hipStream_t s) {
-    SbTune t = sb_tune();
-    // The folded second norm (pre_g), the depthwise-conv tail and the 8-row activation tiles exist only in the !NTW instantiations of launch_sb_ct: an
-    // A/B run with PK_SB_NT=1 keeps the default load policy for the products that carry one (round-5 advisor finding: they used to fall through to
-    // the generic kernel, which ignores all three -- wrong numbers, silently).
-    if (a.pre_g || a.dw_tail || a.a_t8 || a.out_t8) t.nt = 0;
     const int nslices = a.K / (32 * STEPS);
     const int split = nslices < kSbMaxWaves ? nslices : kSbMaxWaves;
     const int tiles1 = (a.N + 15) / 16;
-    int R = t.rows ? t.rows : sb_rows_per_wg(a, nslices, EPI == EPI_GLU, tiles1);
+    const int R = sb_rows_per_wg(a, nslices, EPI == EPI_GLU, tiles1);
     // Two column tiles per wave (the activation registers of a K slice feed both) where that lowers what the busiest CU pulls: fp32 rows (4 bytes
     // per k and row against 2 per k and column) of products wide enough to keep every CU busy with 16 rows x 32 columns per workgroup -- fc1 and
     // qkv of the 600M models: K (16 * 4 + 32 * 2) = 128 KB per CU instead of K (32 * 4 + 16 * 2) = 160 KB.
-    int ct = 1;
     if constexpr (!A16 && EPI != EPI_GLU) {
-        if (R == 32 && split >= 2 && a.N % 32 == 0 && (tiles1 / 2) * ((a.M + 15) / 16) >= 192) ct = 2;
-        if (t.ct) ct = (t.ct == 2 && split >= 2 && a.N % 32 == 0) ? 2 : 1;
-        if (ct == 2) {
-            if (!t.rows) R = 16;
-#ifdef PK_EXPERIMENTAL
-            if (t.nt) { launch_sb_ct<EPI, STEPS, A16, LN, 2, true, WT>(a, s, R); return; }
-#endif
-            launch_sb_ct<EPI, STEPS, A16, LN, 2, false, WT>(a, s, R);
-            return;
-        }
+        if (R == 32 && split >= 2 && a.N % 32 == 0 && (tiles1 / 2) * ((a.M + 15) / 16) >= 192) { launch_sb_ct<EPI, STEPS, A16, LN, 2, WT>(a, s, 16); return; }
     }
-#ifdef PK_EXPERIMENTAL
-    if (t.nt) { launch_sb_ct<EPI, STEPS, A16, LN, 1, true, WT>(a, s, R); return; }
-#endif
-    launch_sb_ct<EPI, STEPS, A16, LN, 1, false, WT>(a, s, R);
+    launch_sb_ct<EPI, STEPS, A16, LN, 1, WT>(a, s, R);
 }
 
 template <int EPI, int STEPS, bool A16, bool LN>
 static void launch_sb(const GemmArgs &a, hipStream_t s) {
-    if (a.W_t16 && a.N % 16 == 0 && sb_tune().wt) launch_sb_wt<EPI, STEPS, A16, LN, true>(a, s);
+    if (a.W_t16 && a.N % 16 == 0) launch_sb_wt<EPI, STEPS, A16, LN, true>(a, s);
     else launch_sb_wt<EPI, STEPS, A16, LN, false>(a, s);
 }
 
@@ -645,52 +594,7 @@ void launch_tile_copy_bf16(const float *src16, float *dst16, int64_t rows, int K
                        reinterpret_cast<uint4 *>(dst16), n, K / 32, ld / 8);
 }
 
-#ifdef PK_EXPERIMENTAL
-// Round 6, verdict item 1 -- the CEILING of "take the weight fetch off the dependent chain": PK_SB_PREWARM=1 puts a launch in front of every product that
-// touches one dword of every 128-byte line of the product's operand tiles FROM THE XCD THAT WILL READ THEM (a toucher reads HW_REG_XCC_ID and takes the
-// column tiles x with x % 8 == its id: workgroup (x, y) of the product runs on XCD (y gridDim.x + x) % 8 = x % 8, gridDim.x a multiple of 8);
-// PK_SB_PREWARM=2 takes the tiles of XCD (id + 3) % 8 instead (lines in the memory-side cache only).  The product's own duration in a kernel trace is then
-// what it would cost if something had requested its weights for free (tools/experiments/r06_prewarm.sh; the toucher's own time is NOT free: this is a
-// measurement, never a production path).
-__global__ __launch_bounds__(256) void sb_prewarm_kernel(const char *base, int tile_bytes /* per column tile: K / 32 KB */, int ntiles, int shift, unsigned *sink) {
-    unsigned id;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
-    const int x = ((int)(id & 7) + shift) & 7;
-    const int per_xcd = gridDim.x / 8, sub = blockIdx.x / 8;
-    const int lines = tile_bytes / 128;
-    const long total = (long)((ntiles - x + 7) / 8) * lines;
-    unsigned acc = 0;
-    for (long i = (long)sub * 256 + threadIdx.x; i < total; i += (long)per_xcd * 256) {
-        const long t = i / lines, l = i - t * lines;
-        acc ^= *reinterpret_cast<const unsigned *>(base + (size_t)(x + 8 * t) * tile_bytes + (size_t)l * 128);
-    }
-    if (acc == 0x9e3779b9u) *sink = acc;
-}
-static void sb_prewarm(const GemmArgs &a, int epi, hipStream_t s) {
-    static const int mode = [] { const char *e = getenv("PK_SB_PREWARM"); return e ? atoi(e) : 0; }();
-    if (!mode || !a.W_t16 || a.N % 16 != 0) return;
-    static unsigned *sink = nullptr;
-    if (!sink && hipMalloc(&sink, 64) != hipSuccess) return;
-    const int rows = epi == EPI_GLU ? 2 * a.N : a.N;
-    // (two column tiles per wave: workgroup x reads tiles 2x, 2x + 1 -- pairs of tiles alternate XCDs in pairs; granularity 2 tiles then)
-    const int tiles1 = (a.N + 15) / 16, nsl = a.K / 256;
-    const bool ct2 = !a.a_bf16 && epi != EPI_GLU && sb_rows_per_wg(a, nsl, false, tiles1) == 32 && nsl >= 2 && a.N % 32 == 0 && (tiles1 / 2) * ((a.M + 15) / 16) >= 192;   // launch_sb_wt's rule
-    const int g = ct2 ? 2 : 1;
-    hipLaunchKernelGGL(sb_prewarm_kernel, dim3(256), dim3(256), 0, s, reinterpret_cast<const char *>(a.W_t16), g * (a.K / 32) * 1024, rows / 16 / g, mode == 2 ? 3 : 0, sink);
-}
-#endif
-
 void launch_gemm_smallm_bf16(const GemmArgs &a, int epi, hipStream_t s) {
-#ifdef PK_EXPERIMENTAL
-    static const bool sumrev_set = [] {
-        const char *e = getenv("PK_SB_SUMREV");
-        const int v = e ? atoi(e) : 0;
-        if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(sb_sum_rev), &v, sizeof(v));
-        return true;
-    }();
-    (void)sumrev_set;
-    sb_prewarm(a, epi, s);
-#endif
     switch (epi) {
     case EPI_NONE: launch_sb_epi<EPI_NONE>(a, s); break;
     case EPI_RELU: launch_sb_epi<EPI_RELU>(a, s); break;

@@ -293,15 +293,6 @@ static void launch_c1d1_c2(const float *feats, int B, int Tm, int F, int C, cons
     hipLaunchKernelGGL((sub_conv1_dw1_c2_kernel<XC, YS>), dim3((unsigned)((n_strips + spb - 1) / spb)), dim3(256), lds, s, feats, Tm, F, C, w1, b1,
                        wd, bd, H1, W1, H2, W2, n_xc, n_ys, n_strips, out, rag);
 }
-// the two-channel packed kernel on batches (EXPERIMENTAL builds: PK_SUB_C2=0 keeps the one-channel kernel)
-static bool sub_c2_on() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_SUB_C2"); return e ? atoi(e) != 0 : true; }();
-    return on;
-#else
-    return true;
-#endif
-}
 static constexpr int64_t kSmallStripRows = 1024;
 int sub_conv1_dw1_strip_rows(int64_t total_h2_rows) { return total_h2_rows <= kSmallStripRows ? 2 : 8; }
 void launch_sub_conv1_dw1(const float *feats, int B, int Tm, int F, int C, const float *w1, const float *b1, const float *wd,
@@ -315,7 +306,7 @@ void launch_sub_conv1_dw1(const float *feats, int B, int Tm, int F, int C, const
     // (ragged batch: the caller built rag.strips with rag.strip_rows = sub_conv1_dw1_strip_rows(total H2 rows) rows per unit)
     const bool small = rag.strips.u ? rag.strip_rows == 2 : (int64_t)B * H2 <= kSmallStripRows;
     // batches: two channels per thread on packed fp32 (sub_conv1_dw1_c2_kernel), chunks of 4 columns; C even with 256 % (C / 2) == 0 (8-byte aligned weight pairs)
-    const bool c2 = !small && sub_c2_on() && C % 2 == 0 && C >= 64 && 256 % (C / 2) == 0;
+    const bool c2 = !small && C % 2 == 0 && C >= 64 && 256 % (C / 2) == 0;
     if (W2 <= 20 || W2 % 20 == 0) {
         if (small) launch_c1d1<20, 2>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);
         else if (c2) launch_c1d1_c2<4>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);

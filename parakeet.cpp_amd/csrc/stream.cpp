@@ -19,59 +19,6 @@
 
 namespace pk {
 
-// Fold the LayerNorm of a product's input rows into the product (GemmArgs::ln_g; tolerance-class mode: kernels/gemm_smallm_bf16.hip, exact mode:
-// gemm_smallm_ln_kernel in kernels/gemm_smallm.hip, bit for bit) -- four of a block's fifteen launches go.  EXPERIMENTAL builds: PK_STREAM_FUSE_LN=0 switches it off for the A/B of tools/experiments/stream_bf16_ab.sh.
-// The depthwise conv + BatchNorm + SiLU of the conv module in the GLU epilogue of pw1 (kernels.hpp: DwTail) -- one launch less per block,
-// bit-identical to the separate kernel (both modes).  EXPERIMENTAL builds: PK_STREAM_FUSE_DW=0 switches it off.
-static bool stream_fuse_dw() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_STREAM_FUSE_DW"); return e ? atoi(e) != 0 : true; }();
-    return on;
-#else
-    return true;
-#endif
-}
-// Tolerance-class mode: fc1 -> fc2 activations in the small-M bf16 kernel's 8-row operand tiles.  EXPERIMENTAL builds: PK_STREAM_ACT_TILES=0 keeps rows.
-static bool stream_act_tiles() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_STREAM_ACT_TILES"); return e ? atoi(e) != 0 : true; }();
-    return on;
-#else
-    return true;
-#endif
-}
-// A block's final_norm_ folded into the first product of the NEXT block (GemmArgs::pre_g: that product normalises twice and
-// its first column tile writes the normalised rows -- the next block's residual stream -- into the other of two buffers): one launch less per block
-// (both modes; the exact mode's kernel normalises exactly as the separate launch does: bit-identical).
-// EXPERIMENTAL builds: PK_STREAM_FUSE_FIN=0 keeps the separate LayerNorm launch.
-static bool stream_fuse_final() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_STREAM_FUSE_FIN"); return e ? atoi(e) != 0 : true; }();
-    return on;
-#else
-    return true;
-#endif
-}
-// The block chain of a steady-state chunk as a hipGraph (stream.hpp EncGraph): built, correct (the streaming fixtures pass on it) and SLOWER on this
-// runtime -- median 1.79 -> 1.82 ms, p95 1.81 -> 2.6 ms per 16-session chunk (profiles/r05_stream_graph_ab.txt): hipGraphLaunch of ~250 kernel nodes costs
-// more host time than the launches it replaces, the same finding as for the decode loop's graph in round 3.  EXPERIMENTAL builds: PK_STREAM_GRAPH=1.
-static bool stream_graph() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_STREAM_GRAPH"); return e ? atoi(e) != 0 : false; }();
-    return on;
-#else
-    return false;
-#endif
-}
-static bool stream_fuse_ln() {
-#ifdef PK_EXPERIMENTAL
-    static const bool on = [] { const char *e = getenv("PK_STREAM_FUSE_LN"); return e ? atoi(e) != 0 : true; }();
-    return on;
-#else
-    return true;
-#endif
-}
-
 StreamBatch::StreamBatch(Model &m, int n_streams, int att_left, int att_right) : S(n_streams), m_(m), left_(att_left), right_(att_right) {
     m_.require_gpu();
     if (S <= 0 || att_left < 0 || att_right < 0) fail(PK_ERR_INVALID, "n_streams / attention context");
@@ -236,8 +183,10 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
     // the previous block's final norm, when it rides on this block's first product (set at the end of a block, consumed by the next ffn1 fc1)
     const float *pend_g = nullptr, *pend_b = nullptr;
     float *x_other = nullptr;
+    // The LayerNorm of a product's input rows folds into the product where the kernel can (GemmArgs::ln_g; tolerance-class mode:
+    // kernels/gemm_smallm_bf16.hip, exact mode: gemm_smallm_ln_kernel in kernels/gemm_smallm.hip, bit for bit) -- four of a block's fifteen launches go.
     auto ln_gemm = [&](const char *name, const GemmArgs &g, int epi, const float *ng, const float *nb, bool norm_done) {
-        if (!norm_done && stream_fuse_ln()) {
+        if (!norm_done) {
             GemmArgs fg = g;
             fg.A = x; fg.lda = d; fg.a_bf16 = 0; fg.a_sigma = 0; fg.ln_g = ng; fg.ln_b = nb; fg.ln_eps = 1e-5f;
             if (pend_g) {                                            // (checked when it was set: gemm_smallm_bf16_pre_applies)
@@ -254,15 +203,18 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
         m_.run_gemm(name, g, epi, st);
     };
     bool ln_folds = false;                                                                                // the next block's ffn1 norm will be folded into its fc1
-    if (stream_fuse_ln()) {
+    {
         GemmArgs pg{x, d, m_.layers[0].ffn1_w1, d, nullptr, hb, f, nullptr, 0, 1.0f, (int)rows, f, d};
         pg.ln_g = m_.layers[0].ffn1_ng; pg.ln_b = m_.layers[0].ffn1_nb; pg.out_bf16 = a16;
         if (sg) pg.W_sig = (*sig_)[0].ffn1_w1;
         if (wt) pg.W_t16 = (*sig_)[0].ffn1_w1;
         ln_folds = a16 ? gemm_smallm_bf16_ln_applies(pg, EPI_SILU) : (sg && gemm_smallm_ln_applies(pg, EPI_SILU));
     }
-    bool fin_folds = false;                                                                               // ... and the block's final norm with it
-    if (ln_folds && stream_fuse_final() && cfg.num_layers > 1) {
+    // ... and the block's final norm with it (GemmArgs::pre_g: that product normalises twice and its first column tile writes the normalised rows -- the
+    // next block's residual stream -- into the other of two buffers): one launch less per block (both modes; the exact mode's kernel normalises exactly
+    // as the separate launch does: bit-identical)
+    bool fin_folds = false;
+    if (ln_folds && cfg.num_layers > 1) {
         x_alt_.reserve((size_t)rows * d * 4);
         x_other = x_alt_.as<float>();
         GemmArgs pg{x, d, m_.layers[1].ffn1_w1, d, nullptr, hb, f, nullptr, 0, 1.0f, (int)rows, f, d};
@@ -275,10 +227,10 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
         GemmArgs g1{n, d, second ? L.ffn2_w1 : L.ffn1_w1, d, second ? L.ffn2_b1 : L.ffn1_b1, hb, f, nullptr, 0, 1.0f, (int)rows, f, d};
         g1.a_sigma = sg; (wt ? g1.W_t16 : g1.W_sig) = second ? Ls.ffn2_w1 : Ls.ffn1_w1;
         g1.a_bf16 = a16; g1.out_bf16 = a16;
-        // tolerance-class mode, both products on the small-M bf16 kernel: the fc1 activations in its 8-row operand tiles (GemmArgs::out_t8 / a_t8)
+        // tolerance-class mode, both products on the small-M bf16 kernel: the fc1 -> fc2 activations in its 8-row operand tiles (GemmArgs::out_t8 / a_t8)
         GemmArgs p1 = g1, p2{hb, f, second ? L.ffn2_w2 : L.ffn1_w2, f, nullptr, x, d, x, d, 0.5f, (int)rows, d, f};
         p1.out_t8 = 1; p2.a_bf16 = 1; p2.a_t8 = 1;
-        const bool t8 = a16 && stream_act_tiles() && gemm_smallm_bf16_applies(p1, EPI_SILU) && gemm_smallm_bf16_applies(p2, EPI_RESID);
+        const bool t8 = a16 && gemm_smallm_bf16_applies(p1, EPI_SILU) && gemm_smallm_bf16_applies(p2, EPI_RESID);
         g1.out_t8 = t8;
         g1.sigma_cols = sg ? f : 0;                                                                       // h is fc2's A operand
         ln_gemm("ffn_fc1_silu", g1, EPI_SILU, second ? L.ffn2_ng : L.ffn1_ng, second ? L.ffn2_nb : L.ffn1_nb, norm_done);
@@ -287,32 +239,6 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
         g2.a_bf16 = a16; g2.a_t8 = t8;
         m_.run_gemm("ffn_fc2_resid", g2, EPI_RESID, st);
     };
-    // ---- hipGraph of the block chain (stream.hpp: EncGraph) ----
-    bool steady = stream_graph() && !m_.prof && left_ > 0 && cfg.num_layers > 0;
-    int parity = 0;
-    std::vector<uintptr_t> gkey;
-    if (steady) {                                                   // (EXPERIMENTAL builds with PK_STREAM_GRAPH=1 only: a production chunk skips all of this)
-        parity = layers_[0]->cur;
-        for (const auto &Lp : layers_) steady = steady && Lp->n_kv == left_ && Lp->has_conv == 1 && Lp->cur == parity && Lp->ccur == parity;
-    }
-    if (steady) {
-        const void *ptrs[] = {ws_.x.p, ws_.n.p, ws_.hbuf.p, ws_.qkv.p, ws_.ctx.p, ws_.g.p, ws_.dwb.p, x_alt_.p, ptab, sig_, st, x_other};
-        for (const void *q : ptrs) gkey.push_back(reinterpret_cast<uintptr_t>(q));
-        const int ints[] = {S, c, (int)rows, left_, right_, sg, wt ? 1 : 0, a16, ln_folds ? 1 : 0, fin_folds ? 1 : 0, parity};
-        for (int v : ints) gkey.push_back((uintptr_t)v);
-        EncGraph &G = enc_graph_[parity];
-        if (G.exec && G.key == gkey) {
-            PK_HIP(hipGraphLaunch(G.exec, st));
-            for (auto &Lp : layers_) { Lp->cur ^= 1; Lp->ccur ^= 1; }     // what the captured chain does to the host-side state (full caches stay full)
-            return c;
-        }
-        if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
-        PK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    }
-    struct CaptureGuard {                                           // an exception inside the captured region must not leave the stream capturing
-        hipStream_t st; bool on;
-        ~CaptureGuard() { if (on) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); } }
-    } cap_guard{st, steady};
     bool ffn1_norm_done = false;
     for (int l = 0; l < cfg.num_layers; ++l) {
         const LayerW &L = m_.layers[l];
@@ -345,11 +271,13 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
             g.a_bf16 = a16;
             // the depthwise conv in pw1's epilogue where the small-M bf16 kernel can (rows stream-major, c = 1 / 2 / 4 frames per stream)
             DwTail tail{Ls.conv[Ls.ccur].as<float>(), Ls.conv[Ls.ccur ^ 1].as<float>(), Ls.has_conv, c, L.dw_w, L.dw_b, L.bn_mean, L.bn_rstd, L.bn_g, L.bn_b, sg};
+            // The depthwise conv + BatchNorm + SiLU of the conv module in the GLU epilogue of pw1 (kernels.hpp: DwTail) -- one launch less per block,
+            // bit-identical to the separate kernel (both modes)
             GemmArgs probe = g;                                                                          // what ln_gemm will launch when the norm folds
-            if (stream_fuse_ln()) { probe.A = x; probe.a_bf16 = 0; probe.a_sigma = 0; probe.ln_g = L.cv_ng; probe.ln_b = L.cv_nb; probe.ln_eps = 1e-5f; }
+            probe.A = x; probe.a_bf16 = 0; probe.a_sigma = 0; probe.ln_g = L.cv_ng; probe.ln_b = L.cv_nb; probe.ln_eps = 1e-5f;
             // (tolerance-class mode: with or without the folded norm; exact mode: the tail lives in the kernel with the norm folded in)
-            const bool fused_dw = stream_fuse_dw() && (a16 ? gemm_smallm_bf16_dw_applies(probe, EPI_GLU, c, K) && gemm_smallm_bf16_dw_applies(g, EPI_GLU, c, K)
-                                                           : sg && stream_fuse_ln() && gemm_smallm_dw_applies(probe, EPI_GLU, c, K));
+            const bool fused_dw = a16 ? gemm_smallm_bf16_dw_applies(probe, EPI_GLU, c, K) && gemm_smallm_bf16_dw_applies(g, EPI_GLU, c, K)
+                                      : sg && gemm_smallm_dw_applies(probe, EPI_GLU, c, K);
             if (fused_dw) { g.dw_tail = &tail; g.out = ws_.dwb.as<float>(); }
             ln_gemm("conv_pw1_glu", g, EPI_GLU, L.cv_ng, L.cv_nb, false);
             if (!fused_dw)
@@ -375,17 +303,6 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
             launch_layernorm(x, rows, d, L.fin_g, L.fin_b, 1e-5f, ws_.x.as<float>(), st);            // final_norm_ (the last block's lands in ws_.x)
             x = ws_.x.as<float>();
         }
-    }
-    if (steady) {                                                   // the chain was recorded, not run: instantiate, keep, launch
-        hipGraph_t graph = nullptr;
-        cap_guard.on = false;
-        PK_HIP(hipStreamEndCapture(st, &graph));
-        EncGraph &G = enc_graph_[parity];
-        const hipError_t e = hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { G.exec = nullptr; fail(PK_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-        G.key = gkey;
-        PK_HIP(hipGraphLaunch(G.exec, st));
     }
     PK_CHECK_LAUNCH();
     return c;
@@ -426,7 +343,6 @@ void StreamBatch::decode_device(const float *d_enc, int c, int max_tokens) {
 }
 
 StreamBatch::~StreamBatch() {
-    for (EncGraph &G : enc_graph_) if (G.exec) (void)hipGraphExecDestroy(G.exec);
     if (pin_tok_) (void)hipHostFree(pin_tok_);
     if (pin_pcm_) (void)hipHostFree(pin_pcm_);
 }

@@ -90,8 +90,8 @@ def test_bf16_glds_gemm_against_float64(M, N, K, epi):
     err = np.abs(got - want)
     bound = 2e-6 * mag + 1e-6
     if epi == "resid":
-        # (covers the EXPERIMENTAL form that accumulates the product ONTO the residual, GemmArgs::resid_init: accumulators starting from resid / alpha +
-        #  bias round a sum of that size once per MFMA step -- worst case half an ulp of |resid| / alpha per step, times alpha at the end)
+        # (the register residual epilogue of the direct-to-LDS kernel accumulates the product ONTO the residual, gl_resid_init: accumulators starting from
+        #  resid / alpha + bias round a sum of that size once per MFMA step -- worst case half an ulp of |resid| / alpha per step, times alpha at the end)
         bound = bound + 6e-8 * (K / 16) * np.abs(resid)
     assert np.all(err <= bound), f"max err {err.max():.3e} (bound there {float(bound.flat[err.argmax()]):.3e}) at {np.unravel_index(err.argmax(), err.shape)}"
 

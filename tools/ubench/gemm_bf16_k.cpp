@@ -9,6 +9,7 @@
 #include <vector>
 #include "kernels/gemm.hip"
 #include "kernels/gemm_smallm.hip"
+#include "kernels/gemm_smallm_bf16.hip"   // (launch_gemm_bf16 routes small M there)
 
 using namespace pk;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
