@@ -510,6 +510,19 @@ pk_status pk_diag_ln_gemm(int M, int N, int K, const float *A, const float *pre_
                           const float *W, const float *bias, int epi, int fold, float *out, float *y1);
 /* sum64 of each row of x[rows][n] (the canonical wavefront reduction). */
 pk_status pk_diag_sum64(const float *x, int rows, int n, float *out);
+/* One relative-position attention layer alone (reference src/encoder.cpp:135-171), on the production kernel the encoder runs:
+ * kernel 0 = the fp32 kernel (kernels/attention.hip; hd 32 / 64 / 96 / 128; past its LDS limit the global-scratch variant),
+ * kernel 1 = the bf16 kernel of the tolerance-class mode (kernels/attention_bf16.hip; hd 64 / 128; qkv and pos are rounded to bf16 here, RNE,
+ * and c = (v - u) . P is formed on the device by the engine's kernel).  hd = d / n_heads.
+ * qkv [rows][3 d] natural columns (q | k | v), pos [2 pos_T - 1][d] (the projected position table of pos_T >= T frames: the kernel reads its
+ * window, rows pos_T - T ..), bias_u / bias_v [d].  lens = NULL: a uniform batch of B x T frames (rows = B T); otherwise a ragged (packed) batch of
+ * B utterances of lens[b] frames (rows = sum lens; T is ignored, pos_T >= max lens).
+ * ctx receives [rows + PK_DIAG_ATTENTION_GUARD_ROWS][d] floats (bf16 results widened): the device buffer is filled with a NaN pattern before the
+ * launch -- fp32 0x7FC5A5A5, bf16 0x7FC5 (widened 0x7FC50000) -- so elements the kernel did not write come back as that pattern.
+ * variant (may be NULL): bit 0 = the score block went to global scratch, bit 1 = ragged instantiation, bit 2 = the bf16 kernel. */
+#define PK_DIAG_ATTENTION_GUARD_ROWS 128
+pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int pos_T,
+                                   const float *bias_u, const float *bias_v, float *ctx, int *variant);
 
 #ifdef __cplusplus
 }

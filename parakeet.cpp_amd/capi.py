@@ -107,6 +107,8 @@ def lib():
     L.pk_diag_layernorm.argtypes = [f32p, C.c_int64, C.c_int, f32p, f32p, C.c_float, f32p]
     L.pk_diag_ln_gemm.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_float, f32p, f32p, C.c_int, C.c_int, f32p, f32p]
     L.pk_diag_sum64.argtypes = [f32p, C.c_int, C.c_int, f32p]
+    L.pk_diag_relpos_attention.argtypes = [C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, f32p, f32p,
+                                           C.POINTER(C.c_int)]
     for name, at in _LATE_SIGNATURES.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = at
@@ -573,6 +575,32 @@ def diag_sum64(x):
     out = np.empty(x.shape[0], np.float32)
     check(lib().pk_diag_sum64(_f(x), x.shape[0], x.shape[1], _f(out)))
     return out
+
+
+ATT_GUARD_ROWS = 128                     # PK_DIAG_ATTENTION_GUARD_ROWS
+ATT_UNWRITTEN = {"fp32": 0x7FC5A5A5, "bf16": 0x7FC50000}   # bit pattern of an element the kernel did not write
+
+
+def diag_relpos_attention(kernel, qkv, pos, bias_u, bias_v, n_heads, B=1, lens=None):
+    """pk_diag_relpos_attention: one relative-position attention layer on the production kernel ("fp32" or "bf16").
+    qkv [rows][3 d] (rows = B T, or sum(lens) for a packed ragged batch), pos [2 pos_T - 1][d] -> (ctx [rows + ATT_GUARD_ROWS][d] fp32 with the
+    guard rows, variant bits: 1 global scratch, 2 ragged, 4 bf16)."""
+    qkv, pos, bu, bv = _c(qkv), _c(pos), _c(bias_u), _c(bias_v)
+    rows, d = qkv.shape[0], qkv.shape[1] // 3
+    pos_T = (pos.shape[0] + 1) // 2
+    assert qkv.shape[1] == 3 * d and pos.shape == (2 * pos_T - 1, d) and bu.shape == (d,) and bv.shape == (d,)
+    if lens is not None:
+        ln = np.ascontiguousarray(lens, np.int32)
+        assert int(ln.sum()) == rows
+        B, T, lp = len(ln), int(ln.max()), _i(ln)
+    else:
+        assert rows % B == 0
+        T, lp = rows // B, None
+    out = np.empty((rows + ATT_GUARD_ROWS, d), np.float32)
+    var = C.c_int(-1)
+    check(lib().pk_diag_relpos_attention({"fp32": 0, "bf16": 1}[kernel], B, lp, T, d, n_heads, _f(qkv), _f(pos), pos_T, _f(bu), _f(bv), _f(out),
+                                         C.byref(var)))
+    return out, var.value
 
 
 class Batch:

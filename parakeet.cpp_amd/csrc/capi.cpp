@@ -2113,4 +2113,100 @@ pk_status pk_diag_sum64(const float *x, int rows, int n, float *out) {
     });
 }
 
+// One relative-position attention layer alone, launched as run_layers launches it: the operands laid out the way their producing GEMMs
+// write them (fp32: q / k thirds and the table in the sigma columns; bf16: everything rounded to bf16, natural columns, c vector on the device),
+// a ragged batch described by the engine's RagBatch, the long-sequence scratch where the score block does not fit LDS.
+pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int pos_T,
+                                   const float *bias_u, const float *bias_v, float *ctx, int *variant) {
+    return guard([&] {
+        need(kernel == 0 || kernel == 1, "kernel must be 0 (fp32) or 1 (bf16)");
+        need(qkv && pos && bias_u && bias_v && ctx && B > 0 && d > 0 && n_heads > 0 && d % n_heads == 0, "qkv/pos/bias_u/bias_v/ctx/B/d/n_heads");
+        const int hd = d / n_heads;
+        int t_max = T;
+        int64_t rows = (int64_t)B * T;
+        if (lens) {
+            t_max = 0; rows = 0;
+            for (int b = 0; b < B; ++b) { need(lens[b] > 0, "lens"); t_max = std::max(t_max, (int)lens[b]); rows += lens[b]; }
+        }
+        need(t_max > 0 && pos_T >= t_max, "T > 0 and pos_T >= T (ragged: >= max(lens))");
+        T = t_max;                                                   // (ragged: the launchers size the launch by the longest utterance, as run_layers passes it)
+        if (kernel == 1) need(relpos_attention_bf16_lds_bytes(t_max, hd) > 0 && relpos_attention_bf16_lds_bytes(t_max, hd) <= 160 * 1024, "bf16 kernel: hd 64 or 128");
+        else need(relpos_attention_lds_bytes(t_max, hd) > 0, "fp32 kernel: hd 32, 64, 96 or 128");
+        diag_device();
+        const int64_t Ptab = 2 * (int64_t)pos_T - 1, n_ctx = (rows + PK_DIAG_ATTENTION_GUARD_ROWS) * d;
+        RagBatch r;
+        DevBuf rag_img;
+        SeqRag rag;
+        if (lens) {                                                  // the encoder-frame batch of pk_conformer_blocks_ragged, device views as set_ragged forms them
+            r.build_from_frames(lens, B, kernel == 1 ? relpos_attention_bf16_block_rows(hd) : 32);
+            rag_img.reserve(r.image.size() * 4);
+            PK_HIP(hipMemcpy(rag_img.p, r.image.data(), r.image.size() * 4, hipMemcpyHostToDevice));
+            const int32_t *dv = rag_img.as<int32_t>();
+            rag.units = {reinterpret_cast<const RagUnit *>(dv + r.o_u_att), r.n_u_att};
+            rag.T = dv + r.o_T; rag.T_off = dv + r.o_T_off; rag.T_max = r.T_max; rag.pos_T = pos_T;
+        }
+        Scratch s;
+        s.c.reserve((size_t)d * 4);
+        s.d.reserve((size_t)d * 4);
+        PK_HIP(hipMemcpy(s.c.p, bias_u, (size_t)d * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(s.d.p, bias_v, (size_t)d * 4, hipMemcpyHostToDevice));
+        int var = lens ? 2 : 0;
+        if (kernel == 1) {
+            auto to16 = [](const float *x, size_t n) {               // round to nearest even, as pk_diag_gemm_bf16 rounds W
+                std::vector<uint16_t> y(n);
+                for (size_t i = 0; i < n; ++i) {
+                    uint32_t u;
+                    memcpy(&u, &x[i], 4);
+                    u += 0x7fffu + ((u >> 16) & 1u);
+                    y[i] = (uint16_t)(u >> 16);
+                }
+                return y;
+            };
+            const std::vector<uint16_t> q16 = to16(qkv, (size_t)rows * 3 * d), p16 = to16(pos, (size_t)Ptab * d);
+            s.a.reserve(q16.size() * 2);
+            s.b.reserve(p16.size() * 2);
+            s.e.reserve((size_t)n_heads * Ptab * 4);
+            DevBuf out;
+            out.reserve((size_t)n_ctx * 2);
+            PK_HIP(hipMemcpy(s.a.p, q16.data(), q16.size() * 2, hipMemcpyHostToDevice));
+            PK_HIP(hipMemcpy(s.b.p, p16.data(), p16.size() * 2, hipMemcpyHostToDevice));
+            PK_HIP(hipMemsetD16(out.p, 0x7fc5, (size_t)n_ctx));
+            launch_pos_cvec(s.b.p, s.c.as<float>(), s.d.as<float>(), (int)Ptab, d, n_heads, s.e.as<float>(), nullptr);
+            launch_relpos_attention_bf16(s.a.p, B, T, d, n_heads, s.b.p, s.e.as<float>(), s.c.as<float>(), out.p, nullptr, pos_T, rag);
+            PK_CHECK_LAUNCH();
+            std::vector<uint16_t> o16((size_t)n_ctx);
+            PK_HIP(hipMemcpy(o16.data(), out.p, o16.size() * 2, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < o16.size(); ++i) {
+                const uint32_t u = (uint32_t)o16[i] << 16;
+                memcpy(&ctx[i], &u, 4);
+            }
+            if (variant) *variant = var | 4;
+            return;
+        }
+        // fp32: columns < 2 d of qkv and every column of the table in the sigma layout (GemmArgs::sigma_cols: 2 d for the qkv GEMM, d for pos_proj)
+        auto sig = [](int c) { return (c & ~15) | ((c & 3) << 2) | ((c >> 2) & 3); };
+        std::vector<float> qs((size_t)rows * 3 * d), ps((size_t)Ptab * d);
+        for (int64_t i = 0; i < rows; ++i)
+            for (int c = 0; c < 3 * d; ++c) qs[(size_t)i * 3 * d + (c < 2 * d ? sig(c) : c)] = qkv[(size_t)i * 3 * d + c];
+        for (int64_t p = 0; p < Ptab; ++p)
+            for (int c = 0; c < d; ++c) ps[(size_t)p * d + sig(c)] = pos[(size_t)p * d + c];
+        s.a.reserve(qs.size() * 4);
+        s.b.reserve(ps.size() * 4);
+        s.e.reserve((size_t)n_ctx * 4);
+        PK_HIP(hipMemcpy(s.a.p, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(s.b.p, ps.data(), ps.size() * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemsetD32(s.e.p, 0x7fc5a5a5, (size_t)n_ctx));
+        DevBuf scratch;                                              // run_layers: a [32][T] score block past the LDS goes to global scratch
+        if (relpos_attention_lds_bytes(t_max, hd) > 160 * 1024) {
+            scratch.reserve(lens ? relpos_attention_scratch_bytes_units(r.n_u_att, t_max, n_heads, hd) : relpos_attention_scratch_bytes(B, T, n_heads, hd));
+            var |= 1;
+        }
+        launch_relpos_attention(s.a.as<float>(), B, T, d, n_heads, s.b.as<float>(), s.c.as<float>(), s.d.as<float>(), s.e.as<float>(), nullptr, 0.0f,
+                                scratch.as<float>(), 0, pos_T - T, rag);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpy(ctx, s.e.p, (size_t)n_ctx * 4, hipMemcpyDeviceToHost));
+        if (variant) *variant = var;
+    });
+}
+
 }  // extern "C"
