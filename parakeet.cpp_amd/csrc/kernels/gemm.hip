@@ -199,6 +199,14 @@ static void launch_one(const GemmArgs &a, hipStream_t s) {
 // 64x128 tiles (level), wide outputs on BK 64 (behind), 192x128 tiles where they make a whole round of workgroups (profiles/r04_gemm_tile192_ab.txt:
 // qkv 1.97 -> 1.99 ms per step -- workgroups are handed out as slots free up, so a CU never idles for a 'round'), and the double-buffered forms of
 // the single-buffered tiles below.
+// Every single-buffered tile runs the hand-placed K loop (gemm_pipe_kernel SCHED = 2: staging spread over the MFMA gaps of the last sub-step,
+// its last two k-steps after the second barrier under the next K tile's first fragment reads).  tools/ubench/gemm_sched on MI355X
+// (profiles/r07_gemm_sched_sweep.txt), bit-equal everywhere: per launch fc1 + LayerNorm fold 181.7 -> 167.3 us, fc2 144.7 -> 128.8, qkv + fold
+// 127.6 -> 123.7, GLU + fold 87.3 -> 76.4, out_proj / pw2 40.2 -> 39.1; main loop e.g. fc1 + fold 120.9 -> 131.7 TF.  SCHED = 1 and 3 are
+// behind SCHED = 2 or level on every shape; the GLU product without the fold is the only level one (139.0 / 139.2 TF).  One exception, from the
+// kernel trace of the bench (profiles/r07_kernel_stats_ab.txt): the long-K tile without an epilogue function (sub_proj, once per step) is
+// slower with it (172 -> 185 us), so that product keeps the compiler-placed loop.
+constexpr int kSbSched = 2;
 template <int EPI>
 static void launch_epi(const GemmArgs &a, hipStream_t s) {
     if (a.K < 64) { launch_one<64, 64, EPI>(a, s); return; }           // pipelined kernels need >= 2 K tiles
@@ -208,16 +216,16 @@ static void launch_epi(const GemmArgs &a, hipStream_t s) {
     // 8-wave workgroup per CU, single-buffered -- 8 waves of 64 x 32, BK 32 (round 6): 2-3 % ahead of the BK 64 tile of 32 x 64 waves in the sweep
     // (profiles/r06_gemm_sweep_fc2_variants.txt: 137 vs 140.5 us), which was itself -6 % against two 128x64 workgroups
     const int64_t tiles128 = (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (a.M >= 1024 && a.N >= 256 && a.K >= 1024 && a.K % 64 == 0 && tiles128 <= 256) { launch_gemm_pipe<2, 4, 2, 1, 32, EPI, 1>(a, s); return; }
+    if (a.M >= 1024 && a.N >= 256 && a.K >= 1024 && a.K % 64 == 0 && tiles128 <= 256) { launch_gemm_pipe<2, 4, 2, 1, 32, EPI, 1, false, EPI == EPI_NONE ? 0 : kSbSched>(a, s); return; }
     // round 2: the SINGLE-buffered loop (template parameter NBUF = 1: half the LDS, two barriers per K tile) is ahead of the double-buffered
     // one on every large shape, in the micro-benchmark (tools/ubench/gemm_sweep ml: main loop 130-135 vs 118-125 TF) and, by less, in the
     // engine (fc2 -8 %, fc1 -3.6 %, qkv -5 %, GLU -3 %).
     if constexpr (EPI == EPI_NONE || EPI == EPI_RELU || EPI == EPI_SILU) {
-        if (a.ln_stats) { launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, true>(a, s); return; }    // (gemm_ln_stats_applies: the wide-output tile below, LayerNorm applied while staging A)
+        if (a.ln_stats) { launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, true, kSbSched>(a, s); return; }    // (gemm_ln_stats_applies: the wide-output tile below, LayerNorm applied while staging A)
     }
-    if (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1>(a, s);
+    if (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, false, kSbSched>(a, s);
     else if (a.M >= 1024 && a.N >= 256 && a.K >= 1024) launch_gemm_pipe<2, 2, 2, 1, 32, EPI>(a, s);
-    else if (a.M >= 1024 && a.N >= 256) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1>(a, s);   // out_proj / pw2 on 128x128 / 8 waves (0.81 -> 0.77 ms per step)
+    else if (a.M >= 1024 && a.N >= 256) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, false, kSbSched>(a, s);   // out_proj / pw2 on 128x128 / 8 waves (0.81 -> 0.77 ms per step)
     else launch_gemm_pipe<2, 2, 1, 1, 32, EPI>(a, s);
 }
 
@@ -248,8 +256,8 @@ void launch_gemm(const GemmArgs &a, int epi, hipStream_t s) {
     case EPI_RESID: launch_epi<EPI_RESID>(a, s); break;
     case EPI_GLU:
         if (a.K < 64) launch_one<128, 128, EPI_GLU>(a, s);
-        else if (a.ln_stats) launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1, true>(a, s);
-        else launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1>(a, s);
+        else if (a.ln_stats) launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1, true, kSbSched>(a, s);
+        else launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1, false, kSbSched>(a, s);
         break;
     default: break;
     }

@@ -222,9 +222,13 @@ __device__ __forceinline__ void gp_epilogue(const GemmArgs &g_, gp_f32x16 (&acc)
 // the global load of a chunk and its LDS store every element goes through exactly layernorm_kernel's y = fma((x - mean) * rstd, gamma, beta): the
 // values that reach the MFMAs are bit for bit the ones the separate launch would have written -- but they are never written (nor read back): a
 // batch's LayerNorm becomes a statistics pass (one read of x, 8 bytes per row out) instead of a read + write of the whole tensor.
-template <int WGM, int WGN, int TM, int TN, int BK, int EPI, int NBUF = 2, bool LNA = false>
+// SCHED (single-buffered loop only): 0 = the compiler places the staging stores / loads of a K tile in one burst after the first barrier;
+// SCHED = h > 0 = the hand-placed loop (below): the staging chunks spread over the MFMA gaps of the last sub-step, and the last h of its 4 k-steps run after the
+// second barrier, under the next K tile's first fragment reads.
+template <int WGM, int WGN, int TM, int TN, int BK, int EPI, int NBUF = 2, bool LNA = false, int SCHED = 0>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs g, int tiles_n, int n_tiles) {
     static_assert(NBUF == 1 || NBUF == 2, "LDS staging buffers");
+    static_assert(SCHED >= 0 && SCHED < 4 && (SCHED == 0 || NBUF == 1), "SCHED: 0..3 k-steps after the second barrier, single-buffered loop only");
     constexpr int NT = 64 * WGM * WGN;
     constexpr int WM = TM * 32, WN = TN * 32, BM = WGM * WM, BN = WGN * WN;
     constexpr int PITCH = BK + 4, BUF = (BM + BN) * PITCH, NSUB = BK / 8, C4R = BK / 4;   // C4R float4 chunks per tile row
@@ -305,6 +309,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs g, i
 
     float4 ra[A_CH], rw[W_CH];
     [[maybe_unused]] float4 rg4, rb4;
+    // staging chunk q of a K tile: q < A_CH is ra[q], the rest rw[q - A_CH] (the SCHED loop issues them one at a time)
+    auto gload_chunk = [&](int q, int kt) {
+        if (q < A_CH) ra[q] = *reinterpret_cast<const float4 *>(a_src[q] + kt * BK);
+        else rw[q - A_CH] = *reinterpret_cast<const float4 *>(w_src[q - A_CH] + kt * BK);
+    };
     auto gload = [&](int kt) {
 #pragma unroll
         for (int i = 0; i < A_CH; ++i) ra[i] = *reinterpret_cast<const float4 *>(a_src[i] + kt * BK);
@@ -349,6 +358,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs g, i
             }
         }
     };
+    auto lstore_chunk = [&](int q) {
+        if (q < A_CH) st2(smem + a_dst[q], ra[q].x, ra[q].z, ra[q].y, ra[q].w);
+        else st2(smem + w_dst[q - A_CH], rw[q - A_CH].x, rw[q - A_CH].z, rw[q - A_CH].y, rw[q - A_CH].w);
+    };
     auto lstore = [&](int buf) {
         float *base = smem + buf * BUF;
 #pragma unroll
@@ -392,6 +405,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs g, i
             }
         }
     };
+    auto mma_one = [&](int slot, int e, int i, int j) {         // k-step e of sub-step `slot` on accumulator (i, j)
+        const float a = e == 0 ? fa[slot][i].x : e == 1 ? fa[slot][i].y : e == 2 ? fa[slot][i].z : fa[slot][i].w;
+        const float b = e == 0 ? fb[slot][j].x : e == 1 ? fb[slot][j].y : e == 2 ? fb[slot][j].z : fb[slot][j].w;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[i][j], 0, 0, 0);
+    };
     auto epilogue = [&](int m0, int n0) { gp_epilogue<WGM, WGN, TM, TN, EPI, NBUF * BUF, false, true>(g, acc, smem, m0, n0); };
 #define GP_SB() __builtin_amdgcn_sched_barrier(0)
 #ifndef GP_LNORM_AT
@@ -409,7 +427,54 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs g, i
     fragload(0, 0, 0);
     int cur = 0;
     zero_acc();
-    if constexpr (NBUF == 1) {
+    if constexpr (NBUF == 1 && SCHED > 0) {
+        // Hand-placed single-buffered loop: the same operations and the same k order per accumulator as the loop below, with every
+        // instruction group pinned by sched_barrier(0) fences.  Between the two barriers the M1 MFMAs of the first 4 - SCHED k-steps of the
+        // last sub-step share the staging chunks (a chunk: 4 ds_write_b32, 2 ds_write_b64 for EPI_NONE, then the global load that refills
+        // its registers) evenly over their gaps, instead of 16 stores in one burst in front of them; after the second barrier the next K tile's first
+        // fragment reads go out in front of the remaining SCHED k-steps, so their latency is covered by MFMAs instead of a wait.  The body
+        // is branch-free: past the last K tile the stores write data nobody reads (the epilogue starts with a barrier) and the loads re-read
+        // the last K tile of A / W, both in bounds.
+        constexpr int NCH = A_CH + W_CH, E1 = 4 - SCHED, M1 = E1 * TM * TN;
+        for (int kt = 0; kt < nk; ++kt) {
+            const bool more1 = kt + 1 < nk;
+            const int kl = kt + 2 < nk ? kt + 2 : nk - 1;
+#pragma unroll
+            for (int s = 0; s < NSUB - 1; ++s) {
+                fragload(0, s + 1, (s + 1) & 1);
+                GP_SB(); mma(s & 1); GP_SB();
+                if (LNA && s == GP_LNORM_AT && more1) { lnorm(); GP_SB(); }
+            }
+            constexpr int SL = (NSUB - 1) & 1;
+            __syncthreads();
+            GP_SB();
+#pragma unroll
+            for (int q = 0; q < M1; ++q) {
+                const int e = q / (TM * TN), i = (q / TN) % TM, j = q % TN;
+                mma_one(SL, e, i, j);
+                GP_SB();
+#pragma unroll
+                for (int c = q * NCH / M1; c < (q + 1) * NCH / M1; ++c) { lstore_chunk(c); GP_SB(); gload_chunk(c, kl); GP_SB(); }
+            }
+            if constexpr (LNA) {
+                rg4 = *reinterpret_cast<const float4 *>(gam_src + kl * BK);
+                rb4 = *reinterpret_cast<const float4 *>(bet_src + kl * BK);
+                GP_SB();
+            }
+            lds_store_fence();
+            __syncthreads();
+            GP_SB();
+            fragload(0, 0, 0);
+            GP_SB();
+#pragma unroll
+            for (int e = E1; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) mma_one(SL, e, i, j);
+            GP_SB();
+        }
+    } else if constexpr (NBUF == 1) {
         // Single staging buffer (half the LDS, two barriers per K tile: one when every wave has its last fragments in registers, one
         // when the next tile is stored; the last sub-step's MFMAs run between them).  Level with the double-buffered loop in the
         // engine (profiles/r02_bench_v2_sb.json); kept as a variant of the sweep.
@@ -451,7 +516,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs g, i
 #undef GP_SB
 }
 
-template <int WGM, int WGN, int TM, int TN, int BK, int EPI, int NBUF = 2, bool LNA = false>
+template <int WGM, int WGN, int TM, int TN, int BK, int EPI, int NBUF = 2, bool LNA = false, int SCHED = 0>
 static void launch_gemm_pipe(const GemmArgs &a, hipStream_t s) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
     constexpr int NOUT = (EPI == EPI_GLU) ? BN / 2 : BN;
@@ -460,7 +525,7 @@ static void launch_gemm_pipe(const GemmArgs &a, hipStream_t s) {
     constexpr size_t lds = NBUF * (size_t)(BM + BN) * (BK + 4) * sizeof(float);
     if (a.fast_act || a.out_bf16) { fprintf(stderr, "parakeet_amd: internal error: bf16-mode switches on the fp32 GEMM\n"); abort(); }
     if (LNA != (a.ln_stats != nullptr)) { fprintf(stderr, "parakeet_amd: internal error: GemmArgs::ln_stats on a kernel without the folded LayerNorm (or the reverse)\n"); abort(); }
-    auto kern = &gemm_pipe_kernel<WGM, WGN, TM, TN, BK, EPI, NBUF, LNA>;
+    auto kern = &gemm_pipe_kernel<WGM, WGN, TM, TN, BK, EPI, NBUF, LNA, SCHED>;
     static DynLdsSlots slots;
     ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
     hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles);

@@ -509,7 +509,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_pipe_kernel(GemmArgs g, i
 #endif
 }
 
-template <int WGM, int WGN, int TM, int TN, int BK, int EPI, int NBUF = 2, bool LNA = false /* round 6: the product header's folded LayerNorm -- not in this instrumented copy */>
+template <int WGM, int WGN, int TM, int TN, int BK, int EPI, int NBUF = 2, bool LNA = false /* round 6: the product header's folded LayerNorm -- not in this instrumented copy */,
+          int SCHED = 0 /* the product header's hand-placed single-buffered loop -- not in this instrumented copy (tools/ubench/gemm_sched times it) */>
 static void launch_gemm_pipe(const GemmArgs &a, hipStream_t s) {
     if (LNA) { fprintf(stderr, "gemm_pipe_exp.hpp: no LNA instantiation\n"); abort(); }
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
