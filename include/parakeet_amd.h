@@ -121,6 +121,17 @@ pk_status pk_model_config(const pk_model *m, pk_config *out);
  * GRAPH: the 16-step chunk of PHASES captured once as a hipGraph and replayed. */
 enum { PK_DECODE_LOOP_PHASES = 0, PK_DECODE_LOOP_PERSISTENT = 1, PK_DECODE_LOOP_GRAPH = 2 };
 pk_status pk_model_set_decode_loop(pk_model *m, int mode);
+/* Limited-context ("local") self-attention of the offline encoder: each query frame i attends only to the encoder frames
+ * [i - left, i + right] of its utterance (left, right >= 0; (-1, -1) = full attention, the default; anything else PK_ERR_INVALID).
+ * NeMo's rel_pos_local_attn with att_context_size [L, L] is (L, L).  Attention cost and memory become linear in the clip length: no
+ * length limit from the attention, no global score scratch, and a projected position table of left + right + 1 rows per layer
+ * instead of 2 T - 1.  left + right must fit the band kernel's LDS score block ([32][left + right + 32]): at most 1136 / 1072 / 1008 / 1072
+ * at head size 32 / 64 / 96 / 128, otherwise PK_ERR_UNSUPPORTED.  Applies to pk_encode*, pk_conformer_blocks*, pk_transcribe_* and
+ * the batch API of this model; not to the streaming path, pk_transformer_* or Sortformer.  fp32 mode: bit-identical to full attention when
+ * the band covers the utterance (left, right >= T - 1).  gemm_bf16 mode: the attention runs on the fp32 band kernel with a bf16 context.
+ * Switching back to (-1, -1) gives exactly the results of a model that never set it.  Not to be changed while a batch is in flight. */
+pk_status pk_model_set_attention_context(pk_model *m, int left, int right);
+pk_status pk_model_get_attention_context(const pk_model *m, int *left, int *right);
 
 /* ---- stage entry points (host buffers; used by the parity tests and the C++ facade) ----------------------- */
 /* preprocess_audio (src/audio.cpp:100-158): n_clips clips of n_samples each -> feats[n_clips][n_frames][mel_bins],
@@ -308,6 +319,8 @@ typedef struct pk_group pk_group;
 pk_status pk_group_create(const char *safetensors_path, const char *vocab_path_or_null, const pk_config *cfg, const int *devices,
                           int n_devices, pk_group **out);
 void pk_group_free(pk_group *g);
+/* pk_model_set_attention_context on every replica of the group. */
+pk_status pk_group_set_attention_context(pk_group *g, int left, int right);
 int pk_group_size(const pk_group *g);
 pk_status pk_group_transcribe_pcm(pk_group *g, const float *pcm, const int64_t *offsets, int n_clips, const pk_options *opt,
                                   pk_result **results);
@@ -523,6 +536,14 @@ pk_status pk_diag_sum64(const float *x, int rows, int n, float *out);
 #define PK_DIAG_ATTENTION_GUARD_ROWS 128
 pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int pos_T,
                                    const float *bias_u, const float *bias_v, float *ctx, int *variant);
+/* One limited-context attention layer alone on the band kernel the encoder runs in local mode (kernels/attention_local.hip): query row i of an
+ * utterance attends to keys [max(0, i - left), min(T - 1, i + right)] (left, right >= 0).  qkv, bias_u, bias_v, B, lens, T as for
+ * pk_diag_relpos_attention; pos [left + right + 1][d] is the LOCAL table, row r the projected position i - j = left - r.  out_mode 0: fp32 ctx,
+ * 1: ctx rounded to bf16 (the engine's gemm_bf16 mode; widened to fp32 here, unwritten pattern 0x7FC50000).  ctx: [rows +
+ * PK_DIAG_ATTENTION_GUARD_ROWS][d], NaN-filled before the launch as above.  PK_ERR_UNSUPPORTED past the LDS limit of
+ * pk_model_set_attention_context.  variant (may be NULL): bit 1 = ragged instantiation, bit 3 = the band kernel ran, bit 4 = bf16 output. */
+pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
+                                         const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant);
 
 #ifdef __cplusplus
 }

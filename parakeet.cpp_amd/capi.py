@@ -168,6 +168,11 @@ _LATE_SIGNATURES = {
     "pk_group_transcribe_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkOptions), C.POINTER(C.POINTER(PkResult))],
     "pk_group_last_stats": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), i32p],
     "pk_group_verify_exchange": [C.c_void_p, C.POINTER(PkResult), C.c_int, C.POINTER(C.c_int)],
+    "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
+    "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
+    "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
+                                       C.POINTER(C.c_int)],
 }
 
 
@@ -577,6 +582,27 @@ def diag_sum64(x):
     return out
 
 
+def diag_relpos_local_attention(qkv, pos, bias_u, bias_v, n_heads, left, right, B=1, lens=None, out_mode=0):
+    """pk_diag_relpos_local_attention: one limited-context attention layer on the band kernel.  qkv [rows][3 d] as for
+    diag_relpos_attention, pos the LOCAL table [left + right + 1][d] (row r: position i - j = left - r), out_mode 0 fp32 / 1 bf16 ctx ->
+    (ctx [rows + ATT_GUARD_ROWS][d] fp32 with the guard rows, variant bits: 2 ragged, 8 band kernel, 16 bf16 output)."""
+    qkv, pos, bu, bv = _c(qkv), _c(pos), _c(bias_u), _c(bias_v)
+    rows, d = qkv.shape[0], qkv.shape[1] // 3
+    assert qkv.shape[1] == 3 * d and pos.shape[1] == d and bu.shape == (d,) and bv.shape == (d,)
+    if lens is not None:
+        ln = np.ascontiguousarray(lens, np.int32)
+        assert int(ln.sum()) == rows
+        B, T, lp = len(ln), int(ln.max()), _i(ln)
+    else:
+        assert rows % B == 0
+        T, lp = rows // B, None
+    out = np.empty((rows + ATT_GUARD_ROWS, d), np.float32)
+    var = C.c_int(-1)
+    check(lib().pk_diag_relpos_local_attention(B, lp, T, d, n_heads, _f(qkv), _f(pos), int(left), int(right), _f(bu), _f(bv), int(out_mode),
+                                               _f(out), C.byref(var)))
+    return out, var.value
+
+
 ATT_GUARD_ROWS = 128                     # PK_DIAG_ATTENTION_GUARD_ROWS
 ATT_UNWRITTEN = {"fp32": 0x7FC5A5A5, "bf16": 0x7FC50000}   # bit pattern of an element the kernel did not write
 
@@ -779,6 +805,10 @@ class Group:
                 self.rccl_ranks = ranks.value
         return _transcribe(lib().pk_group_transcribe_pcm, self._h, clips, decoder, timestamps, boost_phrases, boost_score, with_raw=raw)
 
+    def set_attention_context(self, left, right):
+        """pk_group_set_attention_context: Model.set_attention_context on every replica."""
+        check(lib().pk_group_set_attention_context(self._h, int(left), int(right)))
+
     def last_stats(self):
         wall, audio = C.c_double(0), C.c_double(0)
         per = np.zeros(self.size(), np.int32)
@@ -819,6 +849,16 @@ class Model:
     def to_gpu(self, device: int = 0):
         check(lib().pk_model_to_gpu(self._h, device))
         return self
+
+    def set_attention_context(self, left, right):
+        """pk_model_set_attention_context: limited-context attention over encoder frames [i - left, i + right] (NeMo's local attention
+        [L, L] is (L, L)); (-1, -1) restores full attention."""
+        check(lib().pk_model_set_attention_context(self._h, int(left), int(right)))
+
+    def attention_context(self):
+        l, r = C.c_int(0), C.c_int(0)
+        check(lib().pk_model_get_attention_context(self._h, C.byref(l), C.byref(r)))
+        return l.value, r.value
 
     def set_decode_loop(self, mode):
         """pk_model_set_decode_loop: "phases" (default) | "persistent" | "graph" -- same results, different launch structure."""

@@ -151,6 +151,18 @@ pk_status pk_model_set_decode_loop(pk_model *m, int mode) {
     });
 }
 
+pk_status pk_model_set_attention_context(pk_model *m, int left, int right) {
+    return guard([&] { need(m, "model"); m->m->set_attention_context(left, right); });
+}
+
+pk_status pk_model_get_attention_context(const pk_model *m, int *left, int *right) {
+    return guard([&] {
+        need(m && left && right, "model/left/right");
+        *left = m->m->att_left;
+        *right = m->m->att_right;
+    });
+}
+
 pk_status pk_model_config(const pk_model *m, pk_config *out) {
     return guard([&] { need(m && out, "model/out"); *out = m->m->cfg; });
 }
@@ -1386,6 +1398,13 @@ pk_status pk_group_create(const char *weights, const char *vocab, const pk_confi
 }
 
 void pk_group_free(pk_group *g) { delete g; }
+pk_status pk_group_set_attention_context(pk_group *g, int left, int right) {
+    return guard([&] {
+        need(g && !g->models.empty(), "group");
+        g->models[0]->set_attention_context(left, right);           // (validated once: every replica has the same configuration)
+        for (auto &m : g->models) m->set_attention_context(left, right);
+    });
+}
 int pk_group_size(const pk_group *g) { return g ? (int)g->devices.size() : 0; }
 
 pk_status pk_group_transcribe_pcm(pk_group *g, const float *pcm, const int64_t *offsets, int n_clips, const pk_options *opt, pk_result **results) {
@@ -2206,6 +2225,74 @@ pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T
         PK_CHECK_LAUNCH();
         PK_HIP(hipMemcpy(ctx, s.e.p, (size_t)n_ctx * 4, hipMemcpyDeviceToHost));
         if (variant) *variant = var;
+    });
+}
+
+// One limited-context attention layer alone on the band kernel (kernels/attention_local.hip), launched as run_layers launches it in local mode.
+pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
+                                         const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant) {
+    return guard([&] {
+        need(qkv && pos && bias_u && bias_v && ctx && B > 0 && d > 0 && n_heads > 0 && d % n_heads == 0, "qkv/pos/bias_u/bias_v/ctx/B/d/n_heads");
+        need(out_mode == 0 || out_mode == 1, "out_mode must be 0 (fp32) or 1 (bf16)");
+        need((left == -1 && right == -1) || (left >= 0 && right >= 0), "left / right: both >= 0");
+        need(left >= 0, "pk_diag_relpos_local_attention runs the band kernel: left, right >= 0");
+        const int hd = d / n_heads, span = relpos_local_attention_max_span(hd);
+        if (span < 0) fail(PK_ERR_UNSUPPORTED, "band kernel: hd 32, 64, 96 or 128 (got %d)", hd);
+        if ((int64_t)left + right > span)
+            fail(PK_ERR_UNSUPPORTED, "attention context (%d, %d): left + right is at most %d at head size %d", left, right, span, hd);
+        int t_max = T;
+        int64_t rows = (int64_t)B * T;
+        if (lens) {
+            t_max = 0; rows = 0;
+            for (int b = 0; b < B; ++b) { need(lens[b] > 0, "lens"); t_max = std::max(t_max, (int)lens[b]); rows += lens[b]; }
+        }
+        need(t_max > 0, "T > 0 (ragged: lens > 0)");
+        T = t_max;
+        diag_device();
+        const int64_t Ptab = (int64_t)left + right + 1, n_ctx = (rows + PK_DIAG_ATTENTION_GUARD_ROWS) * d;
+        RagBatch r;
+        DevBuf rag_img;
+        SeqRag rag;
+        if (lens) {
+            r.build_from_frames(lens, B, 32);
+            rag_img.reserve(r.image.size() * 4);
+            PK_HIP(hipMemcpy(rag_img.p, r.image.data(), r.image.size() * 4, hipMemcpyHostToDevice));
+            const int32_t *dv = rag_img.as<int32_t>();
+            rag.units = {reinterpret_cast<const RagUnit *>(dv + r.o_u_att), r.n_u_att};
+            rag.T = dv + r.o_T; rag.T_off = dv + r.o_T_off; rag.T_max = r.T_max;
+        }
+        auto sig = [](int c) { return (c & ~15) | ((c & 3) << 2) | ((c >> 2) & 3); };
+        std::vector<float> qs((size_t)rows * 3 * d), ps((size_t)Ptab * d);
+        for (int64_t i = 0; i < rows; ++i)
+            for (int c = 0; c < 3 * d; ++c) qs[(size_t)i * 3 * d + (c < 2 * d ? sig(c) : c)] = qkv[(size_t)i * 3 * d + c];
+        for (int64_t p = 0; p < Ptab; ++p)
+            for (int c = 0; c < d; ++c) ps[(size_t)p * d + sig(c)] = pos[(size_t)p * d + c];
+        Scratch s;
+        s.a.reserve(qs.size() * 4);
+        s.b.reserve(ps.size() * 4);
+        s.c.reserve((size_t)d * 4);
+        s.d.reserve((size_t)d * 4);
+        s.e.reserve((size_t)n_ctx * (out_mode == 1 ? 2 : 4));
+        PK_HIP(hipMemcpy(s.a.p, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(s.b.p, ps.data(), ps.size() * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(s.c.p, bias_u, (size_t)d * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(s.d.p, bias_v, (size_t)d * 4, hipMemcpyHostToDevice));
+        if (out_mode == 1) PK_HIP(hipMemsetD16(s.e.p, 0x7fc5, (size_t)n_ctx));
+        else PK_HIP(hipMemsetD32(s.e.p, 0x7fc5a5a5, (size_t)n_ctx));
+        launch_relpos_local_attention(s.a.as<float>(), B, T, d, n_heads, s.b.as<float>(), s.c.as<float>(), s.d.as<float>(), s.e.as<float>(), nullptr,
+                                      out_mode, left, right, rag);
+        PK_CHECK_LAUNCH();
+        if (out_mode == 1) {
+            std::vector<uint16_t> o16((size_t)n_ctx);
+            PK_HIP(hipMemcpy(o16.data(), s.e.p, o16.size() * 2, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < o16.size(); ++i) {
+                const uint32_t u = (uint32_t)o16[i] << 16;
+                memcpy(&ctx[i], &u, 4);
+            }
+        } else {
+            PK_HIP(hipMemcpy(ctx, s.e.p, (size_t)n_ctx * 4, hipMemcpyDeviceToHost));
+        }
+        if (variant) *variant = 8 | (lens ? 2 : 0) | (out_mode == 1 ? 16 : 0);
     });
 }
 

@@ -747,7 +747,7 @@ void Model::run_mel_ws(Workspace &w, const float *d_pcm, int B, hipStream_t s) {
 // sinusoidal_position_embedding (src/encoder.cpp:9-30): float math on the host, exactly as the reference does,
 // then pos_proj_ of every layer (src/encoder.cpp:148) -- batch-independent, so computed once per sequence length.
 bool Model::attn_bf16(int T) const {
-    if (!cfg.gemm_bf16) return false;
+    if (!cfg.gemm_bf16 || att_local()) return false;               // (local mode: the fp32 band kernel, output mode 1 in the bf16 mode)
     const size_t lds = relpos_attention_bf16_lds_bytes(T, cfg.hidden_size / cfg.num_heads);
     return lds > 0 && lds <= (size_t)150 * 1024;
 }
@@ -797,6 +797,47 @@ void Model::ensure_pos_tables(int T, hipStream_t s) {
         run_gemm("pos_proj", g, EPI_NONE, s);
     }
     pos_T = T;
+}
+
+void Model::set_attention_context(int left, int right) {
+    if (!((left == -1 && right == -1) || (left >= 0 && right >= 0)))
+        fail(PK_ERR_INVALID, "attention context (%d, %d): (-1, -1) for full attention or left, right >= 0", left, right);
+    if (left >= 0) {
+        const int hd = cfg.hidden_size / cfg.num_heads, span = relpos_local_attention_max_span(hd);
+        if (span < 0) fail(PK_ERR_UNSUPPORTED, "limited-context attention: head size %d (the band kernel takes 32, 64, 96 or 128)", hd);
+        if ((int64_t)left + right > span)
+            fail(PK_ERR_UNSUPPORTED, "attention context (%d, %d): left + right is at most %d at head size %d (a block's [32][left + right + 32] score block must fit LDS)",
+                 left, right, span, hd);
+    }
+    att_left = left;
+    att_right = right;
+}
+
+// The local table: row r is the sinusoid of position i - j = left - r (src/encoder.cpp:9-30, the float math of ensure_pos_tables: bit for bit
+// the full table's row of that position), through each layer's pos_proj_ into the sigma columns the band kernel loads.  Rebuilt when (left, right) changes.
+void Model::ensure_local_pos_table(hipStream_t s) {
+    if (pos_local.left == att_left && pos_local.right == att_right) return;
+    const int d = cfg.hidden_size, P = att_left + att_right + 1;
+    std::vector<float> pe((size_t)P * d);
+    for (int p = 0; p < P; ++p) {
+        const float position = (float)(att_left - p);
+        for (int i = 0; i < d; i += 2) {
+            const float div_term = std::exp((float)i * (-std::log(10000.0f) / (float)d));
+            pe[(size_t)p * d + i] = std::sin(position * div_term);
+            if (i + 1 < d) pe[(size_t)p * d + i + 1] = std::cos(position * div_term);
+        }
+    }
+    PK_HIP(hipStreamSynchronize(s));       // previous users of pos_pe / the table
+    pos_pe.reserve(pe.size() * 4);
+    pos_local.proj.reserve((size_t)cfg.num_layers * P * d * 4);
+    PK_HIP(hipMemcpy(pos_pe.p, pe.data(), pe.size() * 4, hipMemcpyHostToDevice));
+    for (int l = 0; l < cfg.num_layers; ++l) {
+        GemmArgs g{pos_pe.as<float>(), d, layers[l].wpos, d, nullptr, pos_local.proj.as<float>() + (size_t)l * P * d, d, nullptr, 0, 1.0f, P, d, d};
+        g.sigma_cols = d;
+        run_gemm("pos_proj", g, EPI_NONE, s);
+    }
+    pos_local.left = att_left;
+    pos_local.right = att_right;
 }
 
 void Model::run_subsample(Workspace &w, const float *d_feats, int B, int Tm, float *d_x, hipStream_t s) {
@@ -900,7 +941,8 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
     if (stop_layer < 0 || stop_layer > cfg.num_layers) { stop_layer = cfg.num_layers; stop_stage = 0; }
     if (stop_layer == 0 && stop_stage == 0) return;
     float *att_scratch_p = nullptr;
-    if (!attn_bf16(T) && relpos_attention_lds_bytes(T, d / cfg.num_heads) > 160 * 1024) {
+    const bool local = att_local();
+    if (!local && !attn_bf16(T) && relpos_attention_lds_bytes(T, d / cfg.num_heads) > 160 * 1024) {
         // a [32][T] score block no longer fits LDS (> ~85 s of audio): the same kernel with its score blocks in global scratch
         const size_t need = rg ? relpos_attention_scratch_bytes_units(w.rag.n_u_att, T, cfg.num_heads, d / cfg.num_heads)
                                : relpos_attention_scratch_bytes(B, T, cfg.num_heads, d / cfg.num_heads);
@@ -910,10 +952,12 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
         att_scratch.reserve(need);
         att_scratch_p = att_scratch.as<float>();
     }
-    ensure_pos_tables(T, s);
+    if (local) ensure_local_pos_table(s);
+    else ensure_pos_tables(T, s);
     const PosTab &ptab = pos_tab(T);                                 // the resident set of this batch's attention format
     const int pos_T = ptab.T, P = 2 * pos_T - 1;                     // its rows (built for pos_T >= T frames)
     const DevBuf &pos_proj = ptab.proj, &pos_cvec = ptab.cvec;
+    const int P_loc = att_left + att_right + 1;                      // local mode: rows of the local table
     const int a16 = cfg.gemm_bf16 ? 1 : 0;                           // bf16 mode: LayerNorm outputs stored as bf16 GEMM operands (ffn())
     const bool att16 = attn_bf16(T);                                 // ... and q / k / v as bf16 for the bf16-MFMA attention kernel
     if (rg) {
@@ -950,9 +994,22 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
         }
         const int hd = d / cfg.num_heads;
         double fl = 0.0;                                             // QK^T + QP^T (needed band) + AV over every (utterance, head)
-        if (rg) for (int tb : w.rag.T) fl += (double)cfg.num_heads * (2.0 * tb * tb * hd * 2 + 2.0 * tb * tb * hd);
+        if (local) {                                                 // local mode: the band's (query, key) pairs instead of T^2
+            auto pairs = [&](int64_t tb) {
+                const int64_t L_ = att_left, R_ = att_right;
+                int64_t n = 0;                                       // sum over i of min(tb - 1, i + R) - max(0, i - L) + 1
+                for (int64_t o = -L_; o <= R_; ++o) n += std::max<int64_t>(0, tb - (o < 0 ? -o : o));
+                return (double)n;
+            };
+            if (rg) for (int tb : w.rag.T) fl += (double)cfg.num_heads * 6.0 * pairs(tb) * hd;
+            else fl = (double)B * cfg.num_heads * 6.0 * pairs(T) * hd;
+        } else if (rg) for (int tb : w.rag.T) fl += (double)cfg.num_heads * (2.0 * tb * tb * hd * 2 + 2.0 * tb * tb * hd);
         else fl = (double)B * cfg.num_heads * (2.0 * T * T * hd * 2 + 2.0 * T * T * hd);
-        if (att16) {
+        if (local) {
+            KL("relpos_attention", fl, 0.0,
+               launch_relpos_local_attention(w.qkv.as<float>(), B, T, d, cfg.num_heads, pos_local.proj.as<float>() + (size_t)l * P_loc * d, L.pos_u, L.pos_v,
+                                             w.ctx.as<float>(), s, ymode, att_left, att_right, rg ? w.rv.att : no_rag));
+        } else if (att16) {
             KL("relpos_attention", fl, 0.0,
                launch_relpos_attention_bf16(w.qkv.p, B, T, d, cfg.num_heads, reinterpret_cast<const __bf16 *>(pos_proj.p) + (size_t)l * P * d,
                                             pos_cvec.as<float>() + (size_t)l * cfg.num_heads * P, L.pos_u, w.ctx.p, s, pos_T, rg ? w.rv.att : no_rag));

@@ -181,6 +181,17 @@ class Model {
     bool attn_bf16(int T) const;    // the bf16-MFMA attention kernel applies (gemm_bf16 mode, head size 64 / 128, strip + c band fit LDS)
     DevBuf att_scratch;         // score blocks of the attention kernel for sequences too long for LDS (grow-only)
     void ensure_pos_tables(int T, hipStream_t s);
+    // Limited-context attention (pk_model_set_attention_context): query row i attends to keys [i - att_left, i + att_right] only, on the band
+    // kernel (kernels/attention_local.hip) with a per-layer LOCAL table of att_left + att_right + 1 rows.  (-1, -1): full attention (default).
+    // In local mode the 2T-1 tables are neither built nor grown, no attention scratch is reserved and attn_bf16() is false.
+    int att_left = -1, att_right = -1;
+    bool att_local() const { return att_left >= 0; }
+    void set_attention_context(int left, int right);
+    struct LocalPosTab {
+        int left = -1, right = -1;          // the (left, right) it was built for
+        DevBuf proj;                        // pos_proj_ of every layer [L][left + right + 1][d], sigma columns
+    } pos_local;
+    void ensure_local_pos_table(hipStream_t s);
 
     // stage drivers (device pointers, enqueue on `s`, never synchronise)
     void run_mel(const float *d_pcm, int B, int64_t n_samples, float *d_logmel, float *d_feats, hipStream_t s, const RagDev *rv = nullptr);

@@ -206,6 +206,13 @@ void launch_relpos_attention(const float *qkv, int B, int T, int d, int n_heads,
                              const float *bias_v, float *ctx, hipStream_t s, float scale = 0.0f, float *scratch = nullptr, int ctx_bf16 = 0,
                              int pos_row0 = 0, const SeqRag &rag = SeqRag());
 size_t relpos_attention_scratch_bytes_units(int64_t n_units, int T_max, int n_heads, int hd);   // ragged form of relpos_attention_scratch_bytes
+// Limited-context ("band") form, kernels/attention_local.hip: query row i attends to keys [max(0, i - left), min(T - 1, i + right)] only.
+// qkv as above (fp32, q / k sigma columns), pos = the layer's LOCAL table [left + right + 1][d] (sigma columns; row r = position i - j = left - r).
+// rag set (units = 32-row blocks): packed rows, per-utterance T; the local table is the same for every utterance.  ctx_bf16: 0 fp32, 1 bf16, 2 fp32 sigma.
+// Every block's score block is [32][<= left + right + 32] in LDS: left + right <= relpos_local_attention_max_span(hd) (-1: unsupported head size).
+int relpos_local_attention_max_span(int hd);
+void launch_relpos_local_attention(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u, const float *bias_v,
+                                   float *ctx, hipStream_t s, int ctx_bf16, int left, int right, const SeqRag &rag = SeqRag());
 // The tolerance-class (pk_config.gemm_bf16) attention, kernels/attention_bf16.hip: q / k / v as bf16 [B*T][3d] (natural columns, written by the
 // qkv GEMM), the projected position table of the layer as bf16 [2T-1][d], cvec[h][p] = (v_h - u_h) . P_p (fp32, launch_pos_cvec), ctx as bf16.
 // Head sizes 64 and 128; relpos_attention_bf16_lds_bytes returns 0 for any other.

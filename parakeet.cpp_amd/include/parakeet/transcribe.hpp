@@ -83,6 +83,15 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         g_ = nullptr;
         check(pk_group_create(weights_path_.c_str(), vocab_path_.empty() ? nullptr : vocab_path_.c_str(), &cfg_,
                               devices.empty() ? nullptr : devices.data(), (int)devices.size(), &g_));
+        check(pk_group_set_attention_context(g_, att_left_, att_right_));
+    }
+    // New: limited-context encoder attention over frames [i - left, i + right] (pk_model_set_attention_context; NeMo's local attention
+    // [L, L] is (L, L)); (-1, -1) = full attention.  Applies to this engine's model and its replicas.
+    void set_attention_context(int left, int right) {
+        check(pk_model_set_attention_context(m_, left, right));
+        if (g_) check(pk_group_set_attention_context(g_, left, right));
+        att_left_ = left;
+        att_right_ = right;
     }
     int num_gpus() const { return g_ ? pk_group_size(g_) : (on_gpu_ ? 1 : 0); }
 
@@ -137,6 +146,7 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     std::string weights_path_, vocab_path_;
     pk_config cfg_;
     pk_model *m_ = nullptr;
+    int att_left_ = -1, att_right_ = -1;
     pk_group *g_ = nullptr;
     Tokenizer tok_;
     bool on_gpu_ = false;
@@ -158,6 +168,8 @@ class Transcriber {
     /// New: a replica on every GPU of the node (or on `devices`); transcribe_batch() then shards its clips over them.
     void to_all_gpus(const std::vector<int> &devices = {}) { eng_.to_all_gpus(devices); }
     int num_gpus() const { return eng_.num_gpus(); }
+    /// New: limited-context attention for long audio (Engine::set_attention_context); (-1, -1) restores full attention.
+    void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
 
     TranscribeResult transcribe(const std::string &audio_path, Decoder decoder = Decoder::TDT, bool timestamps = false) {
         return eng_.run_file(audio_path, options(decoder, timestamps));
@@ -211,6 +223,8 @@ class TDTTranscriber {
     void to_gpu(int device) { eng_.to_gpu(device); }
     void to_all_gpus(const std::vector<int> &devices = {}) { eng_.to_all_gpus(devices); }
     int num_gpus() const { return eng_.num_gpus(); }
+    /// New: limited-context attention for long audio (Engine::set_attention_context); (-1, -1) restores full attention.
+    void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
 
     TranscribeResult transcribe(const std::string &audio_path, bool timestamps = false) { return eng_.run_file(audio_path, options(timestamps)); }
     TranscribeResult transcribe(const std::string &audio_path, const TranscribeOptions &opts) { return eng_.run_file(audio_path, tdt(opts)); }
