@@ -304,6 +304,54 @@ pk_status pk_plan_batches(const int64_t *n_samples, int n_clips, int32_t *batch_
  * depthwise-conv strips, subsampling strips of the packed batch -- what the ragged kernels' grids are sized by. */
 pk_status pk_ragged_extents(const int64_t *n_samples, int n_clips, int32_t *n_mel_frames, int32_t *n_enc_frames, int64_t *totals);
 void pk_results_free(pk_result *results, int n_clips);
+
+/* ---- CTC prefix beam search with n-best output and alignment -------------------------------------------------------------
+ * The reference's roadmap line "Beam search decoding -- CTC prefix beam search ... with configurable width" (README.md:494, tier 1; the gate of
+ * its "N-gram LM shallow fusion" :495 and "Neural LM rescoring -- N-best reranking" :514 lines, which need an n-best list with scores).  The search, its per-frame token pruning, every tie rule and the
+ * forced alignment that gives a hypothesis its timestamps are specified operation by operation in DESIGN.md section 5.5
+ * (tests/ctc_beam_ref.py is that specification in Python; the device result equals it bit for bit).  All of it runs on the device
+ * (kernels/ctc_beam.hip).  No language model, no phrase boost inside the beam; pk_group and streaming sessions have no beam variant. */
+typedef struct pk_beam_options {
+    int32_t beam_width;         /* W: prefixes kept per frame, 1..32 */
+    int32_t token_prune;        /* K: non-blank tokens considered per frame (the K most probable), 1..32, clamped to V - 1 */
+    int32_t n_best;             /* N: hypotheses returned per utterance, 1..beam_width */
+    int32_t timestamps;         /* != 0: forced (Viterbi) alignment of every returned hypothesis -> start / end / conf */
+} pk_beam_options;
+/* README.md:494 "with configurable width": the defaults W = 8, K = 16, N = 1, no timestamps */
+void pk_beam_options_default(pk_beam_options *out);
+/* README.md:494 "CTC prefix beam search", the search alone: HOST log-probs in, n-best out.  Needs a device, no model.
+ * logp: n_frames == NULL: [B][T][V]; else packed [sum_b n_frames[b]][V] and T is ignored (the arrays are pitched for the longest utterance,
+ * Tmax).  Outputs: ids / start / end / conf [B][N][Tmax] (start / end / conf optional, written only with opt->timestamps), lens / score
+ * [B][N]; hypotheses best first, score = log(p_blank + p_non_blank) of the prefix after the last frame.  A slot the beam cannot fill (fewer
+ * than N prefixes exist, e.g. T = 1) has lens 0 and score -inf; unused token slots are 0.  opt == NULL: the defaults.
+ * Timestamps past 3200 frames, or more than 1 GiB of alignment back-pointers (B N T (2 T + 1) bytes): PK_ERR_UNSUPPORTED. */
+pk_status pk_ctc_beam_search(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
+                             int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf);
+/* CTC head + log-softmax (the kernels of pk_ctc_decode) + the search on the model's stream (README.md:494 on the encoder's
+ * output); the log-probs never leave the device.  enc [B][T][hidden] resp. packed with n_frames[B]; outputs as above with
+ * Tmax = T resp. max n_frames.  PK_ERR_UNSUPPORTED for a model without a CTC head or with a boost trie set. */
+pk_status pk_ctc_beam_decode(pk_model *m, const float *enc, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
+                             float *score, int32_t *start, int32_t *end, float *conf);
+pk_status pk_ctc_beam_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const pk_beam_options *opt, int32_t *ids,
+                                    int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf);
+/* Stage timers of the search (tools/bench_ctc_beam.py): the CTC head + log-softmax + greedy collapse (what pk_ctc_decode runs), then top-K +
+ * walk + back-trace / alignment, each between hipEvents on the model's stream; medians of `reps` passes after one warm-up.  n_frames NULL:
+ * uniform [B][T].  ms[0] = greedy CTC stage, ms[1] = beam search stage. */
+pk_status pk_ctc_beam_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
+                                   float ms[2]);
+/* One call from PCM to n-best (what README.md:514 "N-best reranking" consumes): clips packed into ragged batches by the policy of pk_transcribe_pcm
+ * (pk_plan_batches), encoded, searched.  results[i]: the n_hyp <= N hypotheses of clip i, best first: hyp[j] a pk_result as pk_transcribe_pcm
+ * fills it (text through the model's vocabulary, words through the grouping of pk_group_timestamps when opt->timestamps), score[j] its
+ * log-probability.  Owned by the library until pk_nbest_free. */
+typedef struct pk_nbest {
+    int32_t n_hyp;
+    const pk_result *hyp;
+    const float *score;
+} pk_nbest;
+pk_status pk_transcribe_pcm_nbest(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
+                                  pk_nbest **results);
+void pk_nbest_free(pk_nbest *results, int n_clips);
+
 /* ---- one node, several GPUs: utterance shards (the reference has no multi-device path, README.md:513) ----------
  * A pk_group is one model REPLICA per device of this process: the safetensors file is mapped once and every replica is built from that
  * one host image by its own host thread (each device uploads over its own PCIe link).  pk_group_transcribe_pcm deals the clips, longest

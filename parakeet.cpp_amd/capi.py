@@ -60,6 +60,14 @@ class PkResult(C.Structure):
                 ("end_frame", i32p), ("confidence", f32p), ("n_words", C.c_int32), ("words", C.POINTER(PkWord))]
 
 
+class PkBeamOptions(C.Structure):
+    _fields_ = [("beam_width", C.c_int32), ("token_prune", C.c_int32), ("n_best", C.c_int32), ("timestamps", C.c_int32)]
+
+
+class PkNbest(C.Structure):
+    _fields_ = [("n_hyp", C.c_int32), ("hyp", C.POINTER(PkResult)), ("score", f32p)]
+
+
 def to_pk_config(cfg: ModelConfig) -> PkConfig:
     c = PkConfig()
     c.mel_bins, c.subsampling_channels, c.hidden_size = cfg.mel_bins, cfg.subsampling_channels, cfg.hidden_size
@@ -168,6 +176,13 @@ _LATE_SIGNATURES = {
     "pk_group_transcribe_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkOptions), C.POINTER(C.POINTER(PkResult))],
     "pk_group_last_stats": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), i32p],
     "pk_group_verify_exchange": [C.c_void_p, C.POINTER(PkResult), C.c_int, C.POINTER(C.c_int)],
+    "pk_beam_options_default": [C.POINTER(PkBeamOptions)],
+    "pk_ctc_beam_search": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p],
+    "pk_ctc_beam_decode": [C.c_void_p, f32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p],
+    "pk_ctc_beam_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p],
+    "pk_ctc_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), C.c_int, f32p],
+    "pk_transcribe_pcm_nbest": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkBeamOptions), C.POINTER(C.POINTER(PkNbest))],
+    "pk_nbest_free": [C.POINTER(PkNbest), C.c_int],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -212,6 +227,42 @@ def ragged_extents(n_samples):
 
 def device_count():
     return lib().pk_device_count()
+
+
+# ---- CTC prefix beam search (include/parakeet_amd.h) ------------------------------
+def beam_options(beam_width=None, token_prune=None, n_best=None, timestamps=False):
+    """pk_beam_options: the library's defaults (W = 8, K = 16, N = 1) with the given fields replaced."""
+    o = PkBeamOptions()
+    lib().pk_beam_options_default(C.byref(o))
+    if beam_width is not None:
+        o.beam_width = beam_width
+    if token_prune is not None:
+        o.token_prune = token_prune
+    if n_best is not None:
+        o.n_best = n_best
+    o.timestamps = 1 if timestamps else 0
+    return o
+
+
+def _beam_call(fn, head, B, tmax, o):
+    N = max(1, o.n_best)
+    ids = np.zeros((B, N, tmax), np.int32); st = np.zeros((B, N, tmax), np.int32); en = np.zeros((B, N, tmax), np.int32)
+    cf = np.zeros((B, N, tmax), np.float32); lens = np.zeros((B, N), np.int32); score = np.zeros((B, N), np.float32)
+    check(fn(*head, C.byref(o), _i(ids), _i(lens), _f(score), _i(st), _i(en), _f(cf)))
+    return dict(ids=ids, lens=lens, score=score, start=st, end=en, conf=cf)
+
+
+def ctc_beam_search(logp, blank, beam_width=None, token_prune=None, n_best=None, timestamps=False):
+    """pk_ctc_beam_search: logp [B][T][V] (uniform) or a list of [T_b][V] matrices (ragged) -> dict of ids / start / end / conf
+    [B][N][Tmax], lens / score [B][N]; hypotheses best first, an unfilled slot has lens 0 and score -inf.  Needs a device, no model."""
+    o = beam_options(beam_width, token_prune, n_best, timestamps)
+    if isinstance(logp, (list, tuple)):
+        T = np.asarray([x.shape[0] for x in logp], np.int32)
+        lp = _c(np.concatenate([_c(x) for x in logp], axis=0))
+        return _beam_call(lib().pk_ctc_beam_search, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), len(T), int(T.max()), o)
+    lp = _c(logp)
+    B, T, V = lp.shape
+    return _beam_call(lib().pk_ctc_beam_search, (_f(lp), None, B, T, V, blank), B, T, o)
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -997,6 +1048,56 @@ class Model:
     def transcribe_pcm(self, clips, decoder="tdt", timestamps=False, boost_phrases=(), boost_score=5.0):
         """pk_transcribe_pcm: Transcriber::transcribe (transcribe.hpp:91-180) on in-memory clips -> list of dicts."""
         return _transcribe(lib().pk_transcribe_pcm, self._h, clips, decoder, timestamps, boost_phrases, boost_score)
+
+    def ctc_beam_decode(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False):
+        """pk_ctc_beam_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_beam_search."""
+        o = beam_options(beam_width, token_prune, n_best, timestamps)
+        if isinstance(enc, (list, tuple)):
+            T = np.asarray([e.shape[0] for e in enc], np.int32)
+            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
+            return _beam_call(lib().pk_ctc_beam_decode_ragged, (self._h, _f(x), _i(T), len(T)), len(T), int(T.max()), o)
+        x = _c(enc)
+        B, T, _ = x.shape
+        return _beam_call(lib().pk_ctc_beam_decode, (self._h, _f(x), B, T), B, T, o)
+
+    def ctc_beam_decode_timed(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, reps=5):
+        """pk_ctc_beam_decode_timed -> (greedy CTC stage ms, beam search stage ms), HIP events, medians of reps passes."""
+        o = beam_options(beam_width, token_prune, n_best, timestamps)
+        ms = np.zeros(2, np.float32)
+        if isinstance(enc, (list, tuple)):
+            T = np.asarray([e.shape[0] for e in enc], np.int32)
+            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
+            check(lib().pk_ctc_beam_decode_timed(self._h, _f(x), _i(T), len(T), 0, C.byref(o), reps, _f(ms)))
+        else:
+            x = _c(enc)
+            check(lib().pk_ctc_beam_decode_timed(self._h, _f(x), None, x.shape[0], x.shape[1], C.byref(o), reps, _f(ms)))
+        return float(ms[0]), float(ms[1])
+
+    def transcribe_nbest(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False):
+        """pk_transcribe_pcm_nbest: per clip a list of hypotheses, best first: dicts as transcribe_pcm returns them + "score"."""
+        if isinstance(clips, tuple):
+            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
+        else:
+            pcm, off = pack_clips(clips)
+        n = len(off) - 1
+        o = beam_options(beam_width, token_prune, n_best, timestamps)
+        res = C.POINTER(PkNbest)()
+        check(lib().pk_transcribe_pcm_nbest(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res)))
+        out = []
+        for i in range(n):
+            hyps = []
+            for j in range(res[i].n_hyp):
+                r = res[i].hyp[j]
+                d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]))
+                if timestamps:
+                    d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
+                    d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
+                    d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
+                    d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
+                hyps.append(d)
+            out.append(hyps)
+        lib().pk_nbest_free(res, n)
+        return out
 
     def ctc_decode(self, enc, return_logp=False):
         enc = _c(enc)

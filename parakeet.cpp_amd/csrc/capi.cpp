@@ -1296,8 +1296,7 @@ static std::unique_ptr<ResultStore> new_store(int n_clips) {
     return store;
 }
 // hands the store over to the caller as a pk_result array (freed by pk_results_free)
-static pk_result *publish_store(std::unique_ptr<ResultStore> store, int n_clips, bool ts) {
-    ResultStore &R = *store;
+static void point_results(ResultStore &R, int n_clips, bool ts) {
     for (int c = 0; c < n_clips; ++c) {
         pk_result &r = R.res[c];
         r.text = R.text[c].c_str();
@@ -1309,6 +1308,10 @@ static pk_result *publish_store(std::unique_ptr<ResultStore> store, int n_clips,
         r.n_words = (int32_t)R.words[c].size();
         r.words = R.words[c].data();
     }
+}
+static pk_result *publish_store(std::unique_ptr<ResultStore> store, int n_clips, bool ts) {
+    ResultStore &R = *store;
+    point_results(R, n_clips, ts);
     memset(&R.res[n_clips], 0, sizeof(pk_result));
     R.res[n_clips].text = reinterpret_cast<const char *>(store.get());   // back-pointer for pk_results_free
     pk_result *out = R.res.data();
@@ -1326,6 +1329,231 @@ pk_status pk_transcribe_pcm(pk_model *h, const float *pcm, const int64_t *offset
         transcribe_clips(*h->m, pcm, offsets, all, opt, *store);
         *results = publish_store(std::move(store), n_clips, opt && opt->timestamps);
     });
+}
+
+/* ---- CTC prefix beam search (kernels/ctc_beam.hip; reference roadmap README.md:494) ------------------------------------------------ */
+void pk_beam_options_default(pk_beam_options *out) {
+    if (!out) return;
+    out->beam_width = 8; out->token_prune = 16; out->n_best = 1; out->timestamps = 0;
+}
+static pk_beam_options beam_options_of(const pk_beam_options *opt) {
+    pk_beam_options o;
+    pk_beam_options_default(&o);
+    if (opt) o = *opt;
+    return o;
+}
+// what the model entry points refuse (include/parakeet_amd.h); -> the CTC vocabulary and its blank
+static void beam_model_checks(Model &m, const pk_beam_options &o, int &V, int &blank) {
+    m.require_gpu();
+    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC beam search needs one");
+    if (m.boost_on) fail(PK_ERR_UNSUPPORTED, "CTC beam search has no phrase-boosted variant: clear the boost phrases of the model first");
+    V = m.cfg.ctc_vocab_size;
+    blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;           // (as Model::run_ctc)
+    beam_check_options(o, V, blank);
+}
+
+pk_status pk_ctc_beam_search(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
+                             int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf) {
+    return guard([&] {
+        need(logp && ids && lens && B > 0, "logp/ids/lens/B");
+        need(n_frames || T > 0, "T");
+        const pk_beam_options o = beam_options_of(opt);
+        beam_check_options(o, V, blank);
+        int nd = 0;
+        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) fail(PK_ERR_NO_DEVICE, "no HIP device available (this engine has no CPU path)");
+        int64_t rows = (int64_t)B * T;
+        std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
+        if (n_frames) {
+            tab.resize(2 * (size_t)B + 1);
+            rows = 0; T = 0;
+            for (int b = 0; b < B; ++b) {
+                need(n_frames[b] > 0, "n_frames[b] must be positive");
+                tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
+                rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
+                need(rows < ((int64_t)1 << 31), "too many frames");
+            }
+            tab[2 * (size_t)B] = (int32_t)rows;
+        }
+        BeamWs ws;
+        DevBuf d_lp, d_tab;
+        d_lp.reserve((size_t)rows * V * 4);
+        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
+        SeqRag rag;
+        if (n_frames) {
+            d_tab.reserve(tab.size() * 4);
+            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
+        }
+        run_ctc_beam(ws, d_lp.as<float>(), B, T, rows, rag, V, blank, o, nullptr);
+        PK_CHECK_LAUNCH();
+        const bool ts = o.timestamps != 0;
+        beam_copy_out(ws, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, nullptr);
+    });
+}
+
+pk_status pk_ctc_beam_decode(pk_model *h, const float *enc, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
+                             float *score, int32_t *start, int32_t *end, float *conf) {
+    return guard([&] {
+        need(h && enc && ids && lens && B > 0 && T > 0, "model/enc/ids/lens/B/T");
+        Model &m = *h->m;
+        const pk_beam_options o = beam_options_of(opt);
+        int V = 0, blank = 0;
+        beam_model_checks(m, o, V, blank);
+        size_ws_for_T(m, B, T);
+        const size_t rows = (size_t)B * T;
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+        run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, SeqRag(), V, blank, o, m.stream);
+        PK_CHECK_LAUNCH();
+        const bool ts = o.timestamps != 0;
+        beam_copy_out(m.beam, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, m.stream);
+    });
+}
+
+pk_status pk_ctc_beam_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const pk_beam_options *opt, int32_t *ids,
+                                    int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf) {
+    return guard([&] {
+        need(h && enc && n_frames && ids && lens && B > 0, "model/enc/n_frames/ids/lens/B");
+        Model &m = *h->m;
+        const pk_beam_options o = beam_options_of(opt);
+        int V = 0, blank = 0;
+        beam_model_checks(m, o, V, blank);
+        const int T = size_ws_for_frames(m, n_frames, B);              // the token arrays are [B][N][T], T = the longest utterance
+        const size_t rows = (size_t)m.ws.rag.sum_T;
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+        run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, m.ws.rv.seq, V, blank, o, m.stream);
+        PK_CHECK_LAUNCH();
+        const bool ts = o.timestamps != 0;
+        beam_copy_out(m.beam, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, m.stream);
+    });
+}
+
+pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
+                                   float ms[2]) {
+    return guard([&] {
+        need(h && enc && ms && B > 0 && reps > 0 && (n_frames || T > 0), "model/enc/ms/B/T/reps");
+        Model &m = *h->m;
+        const pk_beam_options o = beam_options_of(opt);
+        int V = 0, blank = 0;
+        beam_model_checks(m, o, V, blank);
+        if (n_frames) T = size_ws_for_frames(m, n_frames, B);
+        else size_ws_for_T(m, B, T);
+        const size_t rows = n_frames ? (size_t)m.ws.rag.sum_T : (size_t)B * T;
+        const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        std::vector<float> greedy, beam;
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+            m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, rag, V, blank, o, m.stream);
+            PK_HIP(hipEventRecord(ev.e[2], m.stream));
+            PK_HIP(hipStreamSynchronize(m.stream));
+            PK_CHECK_LAUNCH();
+            float a = 0, b = 0;
+            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+            if (r > 0) { greedy.push_back(a); beam.push_back(b); }
+        }
+        std::sort(greedy.begin(), greedy.end()); std::sort(beam.begin(), beam.end());
+        ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
+    });
+}
+
+namespace {
+struct NbestStore {           // owns everything a pk_nbest array points into
+    std::vector<pk_nbest> out;                              // one hidden trailing slot keeps the store pointer
+    std::vector<std::unique_ptr<ResultStore>> clip;        // the hypotheses of one clip: a ResultStore of n_hyp results
+    std::vector<std::vector<float>> score;
+};
+}  // namespace
+
+pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
+                                  pk_nbest **results) {
+    return guard([&] {
+        need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
+        Model &m = *h->m;
+        const pk_beam_options o = beam_options_of(opt);
+        int V = 0, blank = 0;
+        beam_model_checks(m, o, V, blank);
+        const bool ts = o.timestamps != 0;
+        const int N = o.n_best;
+        auto store = std::make_unique<NbestStore>();
+        store->out.resize((size_t)n_clips + 1); store->clip.resize(n_clips); store->score.resize(n_clips);
+        std::vector<int64_t> clip_len(n_clips);
+        for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+        std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
+        plan_batches(clip_len.data(), n_clips, order, bstart);
+        std::vector<int32_t> ids, lens, st, en;
+        std::vector<float> sc, cf;
+        std::vector<int64_t> blens;
+        for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+            const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+            blens.resize(nc);
+            for (int i = 0; i < nc; ++i) blens[i] = clip_len[order[c0 + i]];
+            const int64_t longest = blens[0];
+            RagBatch r;
+            r.build_from_samples(blens.data(), nc, att_block_rows_of(m, pk_encoder_num_frames(pk_mel_num_frames(longest))));
+            m.ws.size_ragged(m.cfg, nc, r.n_samples, longest, /*own_pcm=*/true);
+            m.ws.set_ragged(r, m.stream);
+            for (int i = 0; i < nc; ++i)
+                PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[order[c0 + i]], (size_t)blens[i] * 4, hipMemcpyHostToDevice, m.stream));
+            m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), nc, m.stream);
+            m.run_encoder(m.ws, m.ws.feats.as<float>(), nc, 0, -1, 0, m.stream);
+            const int T = r.T_max;
+            m.run_ctc(m.ws, m.ws.x.as<float>(), nc, T, true, m.stream);
+            run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream);
+            PK_CHECK_LAUNCH();
+            const size_t hyps = (size_t)nc * N, tok = hyps * T;
+            ids.resize(tok); lens.resize(hyps); sc.resize(hyps);
+            if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
+            beam_copy_out(m.beam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, ts ? cf.data() : nullptr, m.stream);
+            for (int i = 0; i < nc; ++i) {
+                const int c = order[c0 + i];
+                int nh = 0;
+                while (nh < N && sc[(size_t)i * N + nh] > -__builtin_huge_valf()) ++nh;
+                store->clip[c] = new_store(nh);
+                ResultStore &R = *store->clip[c];
+                store->score[c].assign(sc.begin() + (size_t)i * N, sc.begin() + (size_t)i * N + nh);
+                for (int j = 0; j < nh; ++j) {
+                    const size_t hy = (size_t)i * N + j, o0 = hy * T;
+                    const int n = lens[hy];
+                    R.ids[j].assign(ids.begin() + o0, ids.begin() + o0 + n);
+                    std::vector<int> iv(R.ids[j].begin(), R.ids[j].end());
+                    if (m.tok.loaded()) R.text[j] = m.tok.decode(iv);
+                    if (!ts) continue;
+                    R.start[j].assign(st.begin() + o0, st.begin() + o0 + n);
+                    R.end[j].assign(en.begin() + o0, en.begin() + o0 + n);
+                    R.conf[j].assign(cf.begin() + o0, cf.begin() + o0 + n);
+                    if (m.tok.loaded()) {                          // group_timestamps as in transcribe_clips
+                        std::vector<TimestampedToken> tt(n);
+                        for (int q = 0; q < n; ++q) tt[q] = {R.ids[j][q], R.start[j][q], R.end[j][q], R.conf[j][q]};
+                        auto words = group_timestamps(tt, m.tok.pieces(), false);
+                        for (auto &wd : words) R.word_text[j].push_back(wd.word);
+                        for (size_t q = 0; q < words.size(); ++q)
+                            R.words[j].push_back({R.word_text[j][q].c_str(), words[q].start, words[q].end, words[q].confidence});
+                    }
+                }
+                point_results(R, nh, ts);
+                store->out[c].n_hyp = nh;
+                store->out[c].hyp = R.res.data();
+                store->out[c].score = store->score[c].data();
+            }
+        }
+        pk_nbest &tail = store->out[n_clips];
+        tail.n_hyp = 0; tail.score = nullptr;
+        tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
+        *results = store->out.data();
+        store.release();
+    });
+}
+
+void pk_nbest_free(pk_nbest *results, int n_clips) {
+    if (!results || n_clips < 0) return;
+    delete reinterpret_cast<NbestStore *>(const_cast<pk_result *>(results[n_clips].hyp));
 }
 
 /* ---- one node, several GPUs ------------------------------------------------------------------------------------------------ */

@@ -264,6 +264,31 @@ struct TrieDev {
 };
 void launch_ctc_boosted(const float *logp, int B, int T, int V, int blank, const TrieDev &trie, int *ids, int *lens, int *start, int *end,
                         float *conf, hipStream_t s, int pitch = 0, const SeqRag &rag = SeqRag());
+// CTC prefix beam search (kernels/ctc_beam.hip) over log-softmax rows lp[rows][V] (uniform: B x T rows; rag set: packed).
+constexpr int kBeamMaxWidth = 32, kBeamMaxPrune = 32;
+constexpr int kBeamMaxVocab = 1 << 24;          // the token id's field of a candidate key
+// top-K: tk_val / tk_id [rows][K] sorted (value down, id up), blank left out (K <= V - 1); lpb[rows] = lp[row][blank]
+void launch_ctc_beam_topk(const float *lp, int64_t rows, int V, int blank, int K, float *tk_val, int *tk_id, float *lpb, hipStream_t s);
+struct BeamWalkArgs {
+    const float *tk_val; const int *tk_id; const float *lpb;
+    int B, T, W, K, N;
+    int2 *nodes;                                // [B][node_pitch] (parent node, token); node 0 = the empty prefix, node 1 + t W + r = born in frame t at rank r
+    int64_t node_pitch;                         // >= (longest utterance) * W + 1
+    int *hyp_node, *hyp_len; float *hyp_score;  // [B][N]: the N best prefixes of the last frame (a slot the beam does not fill: 0, 0, -inf)
+    SeqRag rg;
+};
+void launch_ctc_beam_walk(const BeamWalkArgs &a, hipStream_t s);
+struct BeamAlignArgs {
+    const float *lp; int V, blank;
+    const int2 *nodes; int64_t node_pitch;
+    const int *hyp_node, *hyp_len;
+    int B, T, N, pitch;                         // token arrays [B][N][pitch], pitch >= the longest utterance
+    int timestamps;                             // 0: ids / lens only
+    int *ids, *lens, *start, *end; float *conf;
+    unsigned char *bp; int64_t bp_pitch;        // back-pointers: bp_pitch >= T (2 T + 1) bytes per hypothesis (timestamps only)
+    SeqRag rg;
+};
+void launch_ctc_beam_align(const BeamAlignArgs &a, hipStream_t s);
 struct TdtState {
     int B, T, V, D, L, Hp, blank, max_symbols, max_tokens, max_steps;
     TrieDev trie;

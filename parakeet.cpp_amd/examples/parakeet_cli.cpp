@@ -1,7 +1,8 @@
 // examples/parakeet_cli.cpp -- the reference's command line (src/main.cpp:12-37, :642-727) on the MI355X engine: same positional
 // arguments, --model types and options; every model type runs through the drop-in facade classes.
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
-//                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu]
+//                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K]]
+// New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
 #include <chrono>
 #include <cstdio>
@@ -18,7 +19,8 @@ using Clock = std::chrono::high_resolution_clock;
 static void usage(const char *prog) {
     std::cerr << "Usage: " << prog << " <model.safetensors> <audio.wav> [options]\n"
               << "  --model TYPE   tdt-ctc-110m (default), tdt-600m, rnnt-600m, eou-120m, nemotron-600m, sortformer, diarized\n"
-              << "  --ctc | --tdt  decoder (default: TDT)\n"
+              << "  --ctc | --tdt | --decoder ctc|tdt  decoder (default: TDT)\n"
+              << "  --beam W [--nbest N] [--prune K]  CTC prefix beam search (needs the CTC decoder), N best hypotheses\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
 }
@@ -62,7 +64,7 @@ int main(int argc, char **argv) {
         const std::string weights = argv[1], audio_path = argv[2];
         std::string model = "tdt-ctc-110m", vocab, sf_weights;
         bool use_ctc = false, timestamps = false;
-        int latency = 0;
+        int latency = 0, beam = 0, nbest = 1, prune = 16;
         std::vector<std::string> boost;
         float boost_score = 5.0f;
         for (int i = 3; i < argc; ++i) {
@@ -70,6 +72,14 @@ int main(int argc, char **argv) {
             if (a == "--model" && i + 1 < argc) model = argv[++i];
             else if (a == "--ctc") use_ctc = true;
             else if (a == "--tdt") use_ctc = false;
+            else if (a == "--decoder" && i + 1 < argc) {
+                const std::string d = argv[++i];
+                if (d != "ctc" && d != "tdt") { std::cerr << "Unknown decoder: " << d << "\n"; return 1; }
+                use_ctc = d == "ctc";
+            }
+            else if (a == "--beam" && i + 1 < argc) beam = std::stoi(argv[++i]);
+            else if (a == "--nbest" && i + 1 < argc) nbest = std::stoi(argv[++i]);
+            else if (a == "--prune" && i + 1 < argc) prune = std::stoi(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
             else if (a == "--latency" && i + 1 < argc) latency = std::stoi(argv[++i]);
@@ -90,6 +100,21 @@ int main(int argc, char **argv) {
             Transcriber t(weights, vocab);
             t.to_gpu();
             if (!boost.empty()) std::cout << "Phrase boost: " << boost.size() << " phrases\n";
+            if (beam > 0) {
+                if (!use_ctc) { std::cerr << "Error: --beam needs the CTC decoder (--ctc / --decoder ctc)\n"; return 1; }
+                if (!boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
+                BeamOptions bo;
+                bo.beam_width = beam; bo.n_best = nbest; bo.token_prune = prune; bo.timestamps = timestamps;
+                const auto t0 = Clock::now();
+                const auto hyps = t.transcribe_nbest(audio_path, bo);
+                const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+                std::cout << "Beam search: width " << beam << ", " << hyps.size() << " hypotheses\n";
+                for (size_t j = 0; j < hyps.size(); ++j) {
+                    std::cout << "\n=== Hypothesis " << j << " score " << std::setprecision(9) << std::defaultfloat << hyps[j].score << " ===\n";
+                    print_result(hyps[j].result, timestamps, ms);
+                }
+                return 0;
+            }
             const auto t0 = Clock::now();
             const auto r = t.transcribe(audio_path, opts);
             print_result(r, timestamps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());

@@ -41,6 +41,19 @@ struct TranscribeResult {
 
 enum class Decoder { CTC, TDT };
 
+/// New (the reference's roadmap "Beam search decoding", README.md:494): one hypothesis of the CTC prefix beam search and its log-probability.
+struct ScoredResult {
+    TranscribeResult result;
+    float score = 0.0f;
+};
+/// Parameters of Transcriber::transcribe_nbest (pk_beam_options); TranscribeOptions is untouched.
+struct BeamOptions {
+    int beam_width = 8;     // prefixes kept per frame, 1..32
+    int token_prune = 16;   // most probable non-blank tokens considered per frame, 1..32
+    int n_best = 1;         // hypotheses returned, 1..beam_width
+    bool timestamps = false;
+};
+
 struct TranscribeOptions {
     Decoder decoder = Decoder::TDT;
     bool timestamps = false;
@@ -130,6 +143,40 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return out;
     }
 
+    // pk_transcribe_pcm_nbest on one clip: the CTC prefix beam search's hypotheses, best first (single device; replicas are not used)
+    std::vector<ScoredResult> run_nbest(const float *pcm, size_t n, const BeamOptions &opts) {
+        if (!on_gpu_) to_gpu(0);
+        pk_beam_options o;
+        pk_beam_options_default(&o);
+        o.beam_width = opts.beam_width; o.token_prune = opts.token_prune; o.n_best = opts.n_best; o.timestamps = opts.timestamps ? 1 : 0;
+        const int64_t offsets[2] = {0, (int64_t)n};
+        pk_nbest *res = nullptr;
+        check(pk_transcribe_pcm_nbest(m_, pcm, offsets, 1, &o, &res));
+        std::vector<ScoredResult> out(res[0].n_hyp);
+        for (int j = 0; j < res[0].n_hyp; ++j) {
+            const pk_result &r = res[0].hyp[j];
+            out[j].score = res[0].score[j];
+            out[j].result.text = r.text ? r.text : "";
+            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
+            if (opts.timestamps) {
+                for (int k = 0; k < r.n_tokens; ++k)
+                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
+                for (int k = 0; k < r.n_words; ++k)
+                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
+            }
+        }
+        pk_nbest_free(res, 1);
+        return out;
+    }
+    std::vector<ScoredResult> run_nbest_file(const std::string &audio_path, const BeamOptions &opts) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_nbest(pcm, (size_t)n, opts);
+    }
+
     TranscribeResult run_file(const std::string &audio_path, const TranscribeOptions &opts) {
         float *pcm = nullptr;
         int64_t n = 0;
@@ -190,6 +237,12 @@ class Transcriber {
         std::vector<std::pair<const float *, size_t>> v;
         for (auto &c : clips) v.emplace_back(c.data(), c.size());
         return eng_.run(v, opts);
+    }
+    /// New (roadmap "Beam search decoding", README.md:494): CTC prefix beam search on the device, the n best hypotheses with scores, best first.
+    std::vector<ScoredResult> transcribe_nbest(const std::string &audio_path, const BeamOptions &opts = {}) { return eng_.run_nbest_file(audio_path, opts); }
+    std::vector<ScoredResult> transcribe_nbest(const float *pcm, size_t n, const BeamOptions &opts = {}) { return eng_.run_nbest(pcm, n, opts); }
+    std::vector<ScoredResult> transcribe_nbest(const std::vector<float> &samples, const BeamOptions &opts = {}) {
+        return eng_.run_nbest(samples.data(), samples.size(), opts);
     }
 
     const Tokenizer &tokenizer() const { return eng_.tokenizer(); }
