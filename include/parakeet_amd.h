@@ -592,6 +592,22 @@ pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T
  * pk_model_set_attention_context.  variant (may be NULL): bit 1 = ragged instantiation, bit 3 = the band kernel ran, bit 4 = bf16 output. */
 pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
                                          const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant);
+/* Which instantiation of the convolution kernels outside the GEMM the engine launches for this model and batch, computed by the functions the
+ * launchers themselves switch on (kernels/kernels.hpp: sub_conv1_dw1_inst, sub_dw_inst, dwconv_inst, stream_dwconv_inst).  Host arithmetic only: no
+ * device is needed.  The batch is B utterances of Tm mel frames each (n_mel_frames = NULL), or a ragged batch of B utterances of n_mel_frames[b]
+ * frames (Tm ignored).  A batch of B x T encoder frames handed to pk_conformer_blocks is described by Tm = 8 T - 7.  stream_c > 0 adds the
+ * streaming conv kernel for a chunk of stream_c encoder frames per session.  out receives PK_DIAG_CONV_VARIANT_WORDS words:
+ *   [0..4]   conv1 + dw1:   instantiation id, 1 = the packed two-channel kernel / 0 = one channel per thread, XC (columns per chunk), YS (rows per
+ *                           strip), the batch's total rows after dw1
+ *   [5..6]   dw2:           instantiation id, XO (output columns per thread)
+ *   [7..11]  conv module:   instantiation id, KC (taps), TT (frames per strip), body (0 = all rows loaded first, 1 = sliding window), total encoder frames
+ *   [12..16] streaming conv (-1 each when stream_c <= 0): instantiation id, KC, CMAX, body (0 = the chunk in registers, 1 = the frame loop),
+ *                           1 if that chunk size and conv size may instead run as the epilogue of the preceding product (kernels.hpp DwTail), else 0
+ * pk_diag_conv_instantiations lists every instantiation those launchers can take as rows of five words {launcher (0 conv1 + dw1, 1 dw2, 2 conv
+ * module, 3 streaming conv), instantiation id, and the three parameters reported above}; returns the number of rows (at most cap_rows are written). */
+#define PK_DIAG_CONV_VARIANT_WORDS 17
+pk_status pk_diag_conv_variants(const pk_model *m, int B, int Tm, const int32_t *n_mel_frames, int stream_c, int32_t *out);
+int pk_diag_conv_instantiations(int32_t *out, int cap_rows);
 
 #ifdef __cplusplus
 }

@@ -186,6 +186,8 @@ _LATE_SIGNATURES = {
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
+    "pk_diag_conv_variants": [C.c_void_p, C.c_int, C.c_int, i32p, C.c_int, i32p],
+    "pk_diag_conv_instantiations": [i32p, C.c_int],
     "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
                                        C.POINTER(C.c_int)],
 }
@@ -654,6 +656,18 @@ def diag_relpos_local_attention(qkv, pos, bias_u, bias_v, n_heads, left, right, 
     return out, var.value
 
 
+CONV_VARIANT_WORDS = 17                  # PK_DIAG_CONV_VARIANT_WORDS
+
+
+def diag_conv_instantiations():
+    """pk_diag_conv_instantiations: every instantiation of the conv1 + dw1, dw2, conv-module and streaming-conv launchers, as the tuples
+    Model.conv_variants reports."""
+    n = lib().pk_diag_conv_instantiations(None, 0)
+    out = np.zeros((n, 5), np.int32)
+    lib().pk_diag_conv_instantiations(_i(out), n)
+    return [tuple(int(x) for x in row) for row in out]
+
+
 ATT_GUARD_ROWS = 128                     # PK_DIAG_ATTENTION_GUARD_ROWS
 ATT_UNWRITTEN = {"fp32": 0x7FC5A5A5, "bf16": 0x7FC50000}   # bit pattern of an element the kernel did not write
 
@@ -1000,6 +1014,25 @@ class Model:
             mg = np.zeros(B, np.float32)
             if lib().pk_decode_margins(self._h, _f(mg), B) == 0:
                 r["min_margin"] = mg
+        return r
+
+    def conv_variants(self, B=1, Tm=1, T=None, n_mel_frames=None, stream_c=0):
+        """pk_diag_conv_variants: the instantiations the engine launches for this model and batch (B utterances of Tm mel frames, or of T encoder
+        frames as conformer_blocks takes them, or a ragged batch of n_mel_frames[b] mel frames; stream_c: frames per streaming chunk) ->
+        dict of tuples, each the row pk_diag_conv_instantiations lists for it: c1d1 (0, id, packed, XC, YS), dw2 (1, id, 0, XO, 0),
+        dwconv (2, id, KC, TT, body), stream (3, id, KC, CMAX, 0) or None; rows_h2 / rows_t; stream_body (0 registers, 1 frame loop) and
+        stream_fusable (the chunk may run as the preceding product's epilogue instead)."""
+        out = np.zeros(CONV_VARIANT_WORDS, np.int32)
+        if n_mel_frames is not None:
+            tm = np.ascontiguousarray(n_mel_frames, np.int32)
+            check(lib().pk_diag_conv_variants(self._h, len(tm), 0, _i(tm), int(stream_c), _i(out)))
+        else:
+            check(lib().pk_diag_conv_variants(self._h, int(B), int(Tm) if T is None else 8 * int(T) - 7, None, int(stream_c), _i(out)))
+        v = [int(x) for x in out]
+        r = dict(c1d1=(0, v[0], v[1], v[2], v[3]), rows_h2=v[4], dw2=(1, v[5], 0, v[6], 0), dwconv=(2, v[7], v[8], v[9], v[10]), rows_t=v[11],
+                 stream=None, stream_body=None, stream_fusable=None)
+        if stream_c > 0:
+            r.update(stream=(3, v[12], v[13], v[14], 0), stream_body=v[15], stream_fusable=bool(v[16]))
         return r
 
     def subsample(self, feats):

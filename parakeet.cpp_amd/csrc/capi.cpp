@@ -2360,6 +2360,41 @@ pk_status pk_diag_sum64(const float *x, int rows, int n, float *out) {
     });
 }
 
+// The launchers' own selection functions (kernels/kernels.hpp) for a model and a batch: what tests/test_gpu_conv_variants.py asks before it compares bits.
+pk_status pk_diag_conv_variants(const pk_model *h, int B, int Tm, const int32_t *n_mel_frames, int stream_c, int32_t *out) {
+    return guard([&] {
+        need(h && out && B > 0 && (n_mel_frames || Tm > 0), "model/out/B/Tm");
+        const pk_config &cfg = h->m->cfg;
+        auto sl = [](int n) { return (n - 1) / 2 + 1; };
+        int64_t rows_h2 = 0, rows_t = 0;
+        for (int b = 0; b < B; ++b) {
+            const int tm = n_mel_frames ? n_mel_frames[b] : Tm;
+            need(tm > 0, "every utterance needs at least one mel frame");
+            const int h2 = sl(sl(tm));
+            rows_h2 += h2; rows_t += sl(h2);
+        }
+        const int W2 = sl(sl(cfg.mel_bins)), W3 = sl(W2);
+        const int c1 = sub_conv1_dw1_inst(sub_conv1_dw1_strip_rows(rows_h2), cfg.subsampling_channels, W2), d2 = sub_dw_inst(W3);
+        const int dw = dwconv_inst(rows_t, cfg.conv_kernel_size), sd = stream_dwconv_inst(cfg.conv_kernel_size);
+        const ConvInst *i0 = conv_inst(0, c1), *i1 = conv_inst(1, d2), *i2 = conv_inst(2, dw), *i3 = conv_inst(3, sd);
+        if (!i0 || !i1 || !i2 || !i3) fail(PK_ERR_UNSUPPORTED, "no kernel instantiation for this configuration");
+        const int32_t v[PK_DIAG_CONV_VARIANT_WORDS] = {
+            c1, i0->p0, i0->p1, i0->p2, (int32_t)rows_h2, d2, i1->p1, dw, i2->p0, i2->p1, i2->p2, (int32_t)rows_t,
+            stream_c > 0 ? sd : -1, stream_c > 0 ? i3->p0 : -1, stream_c > 0 ? i3->p1 : -1, stream_c > 0 ? (stream_c <= i3->p1 ? 0 : 1) : -1,
+            stream_c > 0 ? (int32_t)stream_dwconv_tail_fusable(stream_c, cfg.conv_kernel_size) : -1};
+        memcpy(out, v, sizeof v);
+    });
+}
+int pk_diag_conv_instantiations(int32_t *out, int cap_rows) {
+    const int n = (int)(sizeof(kConvInsts) / sizeof(kConvInsts[0]));
+    for (int i = 0; out && i < n && i < cap_rows; ++i) {
+        const ConvInst &c = kConvInsts[i];
+        const int32_t row[5] = {c.launcher, c.inst, c.p0, c.p1, c.p2};
+        memcpy(out + 5 * i, row, sizeof row);
+    }
+    return n;
+}
+
 // One relative-position attention layer alone, launched as run_layers launches it: the operands laid out the way their producing GEMMs
 // write them (fp32: q / k thirds and the table in the sigma columns; bf16: everything rounded to bf16, natural columns, c vector on the device),
 // a ragged batch described by the engine's RagBatch, the long-sequence scratch where the score block does not fit LDS.

@@ -8,6 +8,7 @@
 // BatchNorm is applied as written ((y-mean)*rstd*gamma+beta, rstd precomputed on the host) rather
 // than folded into the taps, so the result is bit-identical to the oracle.
 #include "../pk_devmath.h"
+#include "../common.hpp"
 #include "kernels.hpp"
 
 namespace pk {
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(256) void dwconv_bn_silu_kernel(const float *__rest
         }
         return v;
     };
-    if constexpr (KC + TT - 1 <= 16) {
+    if constexpr (dwconv_loads_first(KC, TT)) {
         // every input row of the strip is requested before the first is used: KC + TT - 1 independent 16-byte loads in flight per
         // thread (a load issued inside the frame loop stalled every frame for a full memory round trip: 34 us -> see DESIGN.md 8)
         float4 win[KC + TT - 1];                                        // win[i] = input row t0 + i - HALF
@@ -111,24 +112,34 @@ __global__ __launch_bounds__(256) void dwconv_bn_silu_kernel(const float *__rest
     }
 }
 
-template <int TT>
-static void launch_dwconv_tt(const float *g, int B, int T, int d, int kc, const float *w, const float *bias, const float *bn_mean,
-                             const float *bn_rstd, const float *bn_g, const float *bn_b, float *out, hipStream_t s, int out_bf16, const SeqRag &rag) {
+template <int KC, int TT>
+static void launch_dwconv_inst(const float *g, int B, int T, int d, const float *w, const float *bias, const float *bn_mean,
+                               const float *bn_rstd, const float *bn_g, const float *bn_b, float *out, hipStream_t s, int out_bf16, const SeqRag &rag) {
     const int n_strips = (T + TT - 1) / TT;
     const int64_t n_items = (rag.units.u ? (int64_t)rag.units.count : (int64_t)B * n_strips) * (d / 4);          // d % 4 == 0 (hidden sizes are multiples of 32)
     const dim3 grid((unsigned)((n_items + 255) / 256));
-    if (kc == 9) hipLaunchKernelGGL((dwconv_bn_silu_kernel<9, TT>), grid, dim3(256), 0, s, g, T, d, n_strips, w, bias, bn_mean, bn_rstd, bn_g, bn_b, n_items, out, out_bf16, rag);
-    else if (kc == 31) hipLaunchKernelGGL((dwconv_bn_silu_kernel<31, TT>), grid, dim3(256), 0, s, g, T, d, n_strips, w, bias, bn_mean, bn_rstd, bn_g, bn_b, n_items, out, out_bf16, rag);
+    hipLaunchKernelGGL((dwconv_bn_silu_kernel<KC, TT>), grid, dim3(256), 0, s, g, T, d, n_strips, w, bias, bn_mean, bn_rstd, bn_g, bn_b, n_items, out, out_bf16, rag);
 }
 
+int dwconv_strip_frames(int64_t total_rows) { return total_rows <= 2048 ? 2 : 8; }
+DwconvInst dwconv_inst(int64_t total_rows, int kc) {
+    const bool tt2 = dwconv_strip_frames(total_rows) == 2;
+    if (kc == 9) return tt2 ? DWCONV_K9_T2 : DWCONV_K9_T8;
+    if (kc == 31) return tt2 ? DWCONV_K31_T2 : DWCONV_K31_T8;
+    return DWCONV_N;
+}
 void launch_dwconv_bn_silu(const float *g, int B, int T, int d, int kc, const float *w, const float *bias, const float *bn_mean,
                            const float *bn_rstd, const float *bn_g, const float *bn_b, float *out, hipStream_t s, int out_bf16, const SeqRag &rag) {
     // strips of 8 frames per thread amortise the window loads on large batches; a single utterance (the latency-bound small-batch route) has
     // only a handful of workgroups that way -- strips of 2 frames: four times the threads, a quarter of the serial work each
     // (ragged batch: B * T = the total number of packed rows, and rag.units holds strips of dwconv_strip_frames(that total) frames)
-    if (dwconv_strip_frames((int64_t)B * T) == 2) launch_dwconv_tt<2>(g, B, T, d, kc, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, s, out_bf16, rag);
-    else launch_dwconv_tt<8>(g, B, T, d, kc, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, s, out_bf16, rag);
+    switch (dwconv_inst((int64_t)B * T, kc)) {
+    case DWCONV_K9_T2: launch_dwconv_inst<9, 2>(g, B, T, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, s, out_bf16, rag); break;
+    case DWCONV_K9_T8: launch_dwconv_inst<9, 8>(g, B, T, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, s, out_bf16, rag); break;
+    case DWCONV_K31_T2: launch_dwconv_inst<31, 2>(g, B, T, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, s, out_bf16, rag); break;
+    case DWCONV_K31_T8: launch_dwconv_inst<31, 8>(g, B, T, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, s, out_bf16, rag); break;
+    case DWCONV_N: fail(PK_ERR_UNSUPPORTED, "launch_dwconv_bn_silu: conv_kernel_size %d (9 or 31)", kc);
+    }
 }
-int dwconv_strip_frames(int64_t total_rows) { return total_rows <= 2048 ? 2 : 8; }
 
 }  // namespace pk

@@ -464,7 +464,7 @@ bool gemm_smallm_pre_applies(const GemmArgs &a, int epi) {
     return gemm_smallm_ln_applies(a, epi) && smallm_ln_one_round(a, epi);
 }
 bool gemm_smallm_dw_applies(const GemmArgs &a, int epi, int c, int kc) {
-    if (epi != EPI_GLU || kc != 9 || !(c == 1 || c == 2 || c == 4) || a.M % c != 0 || a.remap_rows != 0 || a.sigma_cols != 0) return false;
+    if (epi != EPI_GLU || !stream_dwconv_tail_fusable(c, kc) || a.M % c != 0 || a.remap_rows != 0 || a.sigma_cols != 0) return false;
     return gemm_smallm_ln_applies(a, epi) && smallm_ln_one_round(a, epi);
 }
 bool gemm_smallm_ln_applies(const GemmArgs &a, int epi) {

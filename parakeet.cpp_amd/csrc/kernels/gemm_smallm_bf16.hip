@@ -467,7 +467,7 @@ bool gemm_smallm_bf16_pre_applies(const GemmArgs &a, int epi) {
     return gemm_smallm_bf16_ln_applies(a, epi);
 }
 bool gemm_smallm_bf16_dw_applies(const GemmArgs &a, int epi, int c, int kc) {
-    if (epi != EPI_GLU || kc != 9 || !(c == 1 || c == 2 || c == 4) || a.M % c != 0 || a.N % 16 != 0 || a.out_bf16) return false;
+    if (epi != EPI_GLU || !stream_dwconv_tail_fusable(c, kc) || a.M % c != 0 || a.N % 16 != 0 || a.out_bf16) return false;
     return a.ln_g ? gemm_smallm_bf16_ln_applies(a, epi) : gemm_smallm_bf16_applies(a, epi);
 }
 bool gemm_smallm_bf16_ln_applies(const GemmArgs &a, int epi) {

@@ -188,6 +188,12 @@ double gemm_flops(const GemmArgs &a, int epi);
 // ---- conv subsampling (src/encoder.cpp:219-241), channels-last ---------------------------------------
 // rag set (strips = units of sub_conv1_dw1_strip_rows(...) rows of H2): packed feats [sum Tm][F] -> out [sum H2][W2][C]; B / Tm ignored
 int sub_conv1_dw1_strip_rows(int64_t total_h2_rows);       // output rows per strip the launcher will use for a batch with that many H2 rows
+// Which instantiation a launcher of this file's conv kernels takes.  The launchers switch on these functions' results and pk_diag_conv_variants
+// reports them (tests/test_gpu_conv_variants.py asks instead of re-deriving a threshold); kConvInsts below lists every one of them.
+enum SubC1d1Inst { C1D1_X20_Y2, C1D1_X16_Y2, C1D1_C2_X4_Y8, C1D1_X10_Y8, C1D1_X8_Y8, C1D1_N };   // sub_conv1_dw1_kernel<XC, YS> / sub_conv1_dw1_c2_kernel<XC, YS>
+SubC1d1Inst sub_conv1_dw1_inst(int strip_rows /* sub_conv1_dw1_strip_rows(total H2 rows) */, int C, int W2);
+enum SubDwInst { SUBDW_X5, SUBDW_X4, SUBDW_N };                                                  // sub_dw4_kernel<XO>
+SubDwInst sub_dw_inst(int Wo);
 void launch_sub_conv1_dw1(const float *feats, int B, int Tm, int F, int C, const float *w1, const float *b1, const float *wd,
                           const float *bd, float *out, hipStream_t s, const SubRag &rag = SubRag());
 // rag set (strips = one unit per output row): packed in [sum H2][W][C] -> out [sum T][Wo][C]; B / H ignored
@@ -227,6 +233,10 @@ void launch_dwconv_bn_silu(const float *g, int B, int T, int d, int kc, const fl
                            const float *bn_rstd, const float *bn_g, const float *bn_b, float *out, hipStream_t s, int out_bf16 = 0,
                            const SeqRag &rag = SeqRag());
 int dwconv_strip_frames(int64_t total_rows);   // frames per strip launch_dwconv_bn_silu uses for a batch of that many rows (rag.units granularity)
+enum DwconvInst { DWCONV_K9_T2, DWCONV_K9_T8, DWCONV_K31_T2, DWCONV_K31_T8, DWCONV_N };          // dwconv_bn_silu_kernel<KC, TT>; DWCONV_N: no kernel for that size
+DwconvInst dwconv_inst(int64_t total_rows, int kc);
+// the kernel's two bodies: every input row of the strip loaded before the first is used (true), or a window of KC rows sliding through registers
+__host__ __device__ constexpr bool dwconv_loads_first(int kc, int tt) { return kc + tt - 1 <= 16; }
 
 // ---- streaming encoder pieces (src/streaming_encoder.cpp) -----------------------------------------------------------------------
 // StreamingConformerAttention::forward_cached (:162-272) core for S streams x c query rows: keys / values = nc cached rows
@@ -246,6 +256,26 @@ void launch_stream_cache_update(const float *cache_in, int nc, const float *qkv_
 void launch_stream_dwconv(const float *g, const float *cache_in, int has_cache, int S, int c, int d, int kc, const float *w, const float *bias,
                           const float *bn_mean, const float *bn_rstd, const float *bn_g, const float *bn_b, float *out, float *cache_out,
                           hipStream_t s, int out_sigma = 0 /* out channels in the sigma layout */);
+enum StreamDwconvInst { STREAM_DW_K9_C4, STREAM_DW_K31_C2, STREAM_DW_N };                      // stream_dwconv_kernel<KC, CMAX>; STREAM_DW_N: no kernel for that size
+StreamDwconvInst stream_dwconv_inst(int kc);
+bool stream_dwconv_tail_fusable(int c, int kc);   // the chunk sizes / conv size for which the conv may run as a product's epilogue instead (DwTail)
+
+// Every instantiation the four launchers above can take: {launcher (0 conv1 + dw1, 1 dw2, 2 conv module, 3 streaming conv), instantiation, p0, p1, p2}.
+//   conv1 + dw1: p0 = 1 for the packed two-channel kernel, p1 = XC, p2 = YS;  dw2: p1 = XO;  conv module: p0 = KC, p1 = TT, p2 = 1 sliding window /
+//   0 loads first;  streaming conv: p0 = KC, p1 = CMAX (p2 there is the body a chunk takes: 0 registers when c <= CMAX, 1 the frame loop)
+struct ConvInst { int launcher, inst, p0, p1, p2; };
+constexpr ConvInst kConvInsts[] = {
+    {0, C1D1_X20_Y2, 0, 20, 2}, {0, C1D1_X16_Y2, 0, 16, 2}, {0, C1D1_C2_X4_Y8, 1, 4, 8}, {0, C1D1_X10_Y8, 0, 10, 8}, {0, C1D1_X8_Y8, 0, 8, 8},
+    {1, SUBDW_X5, 0, 5, 0}, {1, SUBDW_X4, 0, 4, 0},
+    {2, DWCONV_K9_T2, 9, 2, !dwconv_loads_first(9, 2)}, {2, DWCONV_K9_T8, 9, 8, !dwconv_loads_first(9, 8)},
+    {2, DWCONV_K31_T2, 31, 2, !dwconv_loads_first(31, 2)}, {2, DWCONV_K31_T8, 31, 8, !dwconv_loads_first(31, 8)},
+    {3, STREAM_DW_K9_C4, 9, 4, 0}, {3, STREAM_DW_K31_C2, 31, 2, 0},
+};
+static_assert(sizeof(kConvInsts) / sizeof(kConvInsts[0]) == C1D1_N + SUBDW_N + DWCONV_N + STREAM_DW_N, "kConvInsts must list every instantiation");
+inline const ConvInst *conv_inst(int launcher, int inst) {
+    for (const ConvInst &c : kConvInsts) if (c.launcher == launcher && c.inst == inst) return &c;
+    return nullptr;
+}
 
 // ---- decoders -------------------------------------------------------------------------------------------
 void launch_logsoftmax_argmax(const float *logits, int64_t rows, int ld, int n, float *lp_out, int *best_idx, float *best_lp, hipStream_t s);

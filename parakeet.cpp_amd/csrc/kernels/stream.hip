@@ -412,13 +412,18 @@ __global__ void stream_dwconv_kernel(const float *__restrict__ g, const float *_
 #pragma unroll
     for (int r = 0; r < CL; ++r) cache_out[((int64_t)sidx * CL + r) * d + ch] = keep[r];
 }
+StreamDwconvInst stream_dwconv_inst(int kc) { return kc == 9 ? STREAM_DW_K9_C4 : kc == 31 ? STREAM_DW_K31_C2 : STREAM_DW_N; }
+bool stream_dwconv_tail_fusable(int c, int kc) { return kc == 9 && (c == 1 || c == 2 || c == 4); }
 void launch_stream_dwconv(const float *g, const float *cache_in, int has_cache, int S, int c, int d, int kc, const float *w, const float *bias,
                           const float *bn_mean, const float *bn_rstd, const float *bn_g, const float *bn_b, float *out, float *cache_out,
                           hipStream_t s, int out_sigma) {
     const int64_t n = (int64_t)S * d;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (kc == 9) hipLaunchKernelGGL((stream_dwconv_kernel<9, 4>), grid, dim3(256), 0, s, g, cache_in, has_cache, c, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, cache_out, n, out_sigma);
-    else if (kc == 31) hipLaunchKernelGGL((stream_dwconv_kernel<31, 2>), grid, dim3(256), 0, s, g, cache_in, has_cache, c, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, cache_out, n, out_sigma);
+    switch (stream_dwconv_inst(kc)) {
+    case STREAM_DW_K9_C4: hipLaunchKernelGGL((stream_dwconv_kernel<9, 4>), grid, dim3(256), 0, s, g, cache_in, has_cache, c, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, cache_out, n, out_sigma); break;
+    case STREAM_DW_K31_C2: hipLaunchKernelGGL((stream_dwconv_kernel<31, 2>), grid, dim3(256), 0, s, g, cache_in, has_cache, c, d, w, bias, bn_mean, bn_rstd, bn_g, bn_b, out, cache_out, n, out_sigma); break;
+    case STREAM_DW_N: fail(PK_ERR_UNSUPPORTED, "launch_stream_dwconv: conv_kernel_size %d (9 or 31)", kc);
+    }
 }
 
 }  // namespace pk

@@ -9,6 +9,7 @@
 //  sub_dw:         depthwise 3x3 s2 p1 on a channels-last tensor.
 // Tap order (ky,kx) and "bias after the chain" follow the oracle exactly (bit-identical results).
 #include "../pk_devmath.h"
+#include "../common.hpp"
 #include "kernels.hpp"
 
 namespace pk {
@@ -125,7 +126,9 @@ __global__ __launch_bounds__(256) void sub_conv1_dw1_kernel(const float *__restr
 // ALUs ~90 % busy at four waves per SIMD) and every one of its fmas is a scalar-per-lane v_fma_f32 -- half the vector fp32 rate -- fed by one broadcast LDS read per
 // window value.  Here a lane carries channels (c, c + 1): weights, accumulators and the three conv1 rows are 2-vectors, the window value is the SAME for both
 // halves, so every tap is ONE v_pk_fma_f32 (weight pair, splat operand, accumulator pair) and one LDS read serves two channels; outputs leave as 8-byte stores.
-// Each half is the identical IEEE fma chain in the identical tap order: bit-identical results (tests/test_gpu_encoder.py, test_gpu_ragged.py).  Chunks of XC = 4
+// Each half is the identical IEEE fma chain in the identical tap order: bit-identical results (tests/test_gpu_conv_variants.py: every
+// width, row count and ragged layout against the oracle; tests/test_gpu_600m.py and test_gpu_ragged.py reach it too -- tests/test_gpu_encoder.py stays under the
+// row threshold and does not).  Chunks of XC = 4
 // output columns (three rows of 9 two-vectors: 122 VGPRs, four waves per SIMD; chunks of 5 need 132 and measured 8 % slower).  80 mel bins: 0.250 -> 0.183 ms per
 // 64 x 10 s batch, 128 bins: 0.561 -> 0.420 ms per 32 x 30 s batch (profiles/r06_sub_conv_packed_ab.txt).
 template <int XC, int YS = 8>
@@ -237,38 +240,6 @@ __global__ __launch_bounds__(256) void sub_conv1_dw1_c2_kernel(const float *__re
     }
 }
 
-__global__ __launch_bounds__(256) void sub_dw_kernel(const float *__restrict__ in, int H, int W, int C,
-                                                     const float *__restrict__ wd /*[9][C]*/, const float *__restrict__ bd,
-                                                     int Ho, int Wo, int64_t n_pix, float *__restrict__ out, SubRag rg) {
-    const int ppb = 256 / C;
-    const int c = threadIdx.x % C;
-    const int64_t pix = (int64_t)blockIdx.x * ppb + threadIdx.x / C;
-    if (pix >= n_pix) return;
-    const int xo = (int)(pix % Wo);
-    int yo = (int)((pix / Wo) % Ho);
-    const float *src;
-    if (rg.strips.u) {                                          // ragged batch: output row pix / Wo of the packed axis = (utterance, local row)
-        const RagUnit un = rg.strips.u[pix / Wo];
-        yo = un.r0; H = rg.H2[un.b];
-        src = in + (int64_t)rg.H2_off[un.b] * W * C;
-    } else {
-        src = in + (pix / ((int64_t)Wo * Ho)) * H * W * C;
-    }
-    float acc = 0.0f;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int iy = 2 * yo + ky - 1;
-        if (iy < 0 || iy >= H) continue;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int ix = 2 * xo + kx - 1;
-            if (ix < 0 || ix >= W) continue;
-            acc = __builtin_fmaf(wd[(ky * 3 + kx) * C + c], src[((int64_t)iy * W + ix) * C + c], acc);
-        }
-    }
-    out[pix * C + c] = acc + bd[c];
-}
-
 template <int XC, int YS = 8>
 static void launch_c1d1(const float *feats, int B, int Tm, int F, int C, const float *w1, const float *b1, const float *wd,
                         const float *bd, int H1, int W1, int H2, int W2, float *out, hipStream_t s, const SubRag &rag) {
@@ -295,26 +266,32 @@ static void launch_c1d1_c2(const float *feats, int B, int Tm, int F, int C, cons
 }
 static constexpr int64_t kSmallStripRows = 1024;
 int sub_conv1_dw1_strip_rows(int64_t total_h2_rows) { return total_h2_rows <= kSmallStripRows ? 2 : 8; }
+// batches: 80 mel bins -> two 10-column chunks per output row; 128 -> four chunks of 8.  (Round 4: chunks of 20 / 16 hold three conv1 rows of
+// 41 / 33 values in registers, 169 / 144 VGPRs = three waves per SIMD; half the chunk = 108 VGPRs, four waves: 0.317 -> 0.243 ms at 64 x 10 s
+// for 5 % more conv1 columns; chunks of 5 measure the same.)  One or two utterances keep the wide chunk:
+// a strip of 8 output rows per thread shares its conv1 rows; one or two utterances give only a few dozen such strips -- strips of 2 rows
+// (1.5x the conv1 work, four times the workgroups, a quarter of the serial chain each: 77 -> ~25 us for one 10 s clip)
+SubC1d1Inst sub_conv1_dw1_inst(int strip_rows, int C, int W2) {
+    const bool small = strip_rows == 2;
+    // batches: two channels per thread on packed fp32 (sub_conv1_dw1_c2_kernel), chunks of 4 columns; C even with 256 % (C / 2) == 0 (8-byte aligned weight pairs)
+    const bool c2 = !small && C % 2 == 0 && C >= 64 && 256 % (C / 2) == 0;
+    const bool wide20 = W2 <= 20 || W2 % 20 == 0;
+    if (small) return wide20 ? C1D1_X20_Y2 : C1D1_X16_Y2;
+    if (c2) return C1D1_C2_X4_Y8;
+    return wide20 ? C1D1_X10_Y8 : C1D1_X8_Y8;
+}
 void launch_sub_conv1_dw1(const float *feats, int B, int Tm, int F, int C, const float *w1, const float *b1, const float *wd,
                           const float *bd, float *out, hipStream_t s, const SubRag &rag) {
     const int H1 = (Tm - 1) / 2 + 1, W1 = (F - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
-    // batches: 80 mel bins -> two 10-column chunks per output row; 128 -> four chunks of 8.  (Round 4: chunks of 20 / 16 hold three conv1 rows of
-    // 41 / 33 values in registers, 169 / 144 VGPRs = three waves per SIMD; half the chunk = 108 VGPRs, four waves: 0.317 -> 0.243 ms at 64 x 10 s
-    // for 5 % more conv1 columns; chunks of 5 measure the same.)  One or two utterances keep the wide chunk:
-    // a strip of 8 output rows per thread shares its conv1 rows; one or two utterances give only a few dozen such strips -- strips of 2 rows
-    // (1.5x the conv1 work, four times the workgroups, a quarter of the serial chain each: 77 -> ~25 us for one 10 s clip)
     // (ragged batch: the caller built rag.strips with rag.strip_rows = sub_conv1_dw1_strip_rows(total H2 rows) rows per unit)
-    const bool small = rag.strips.u ? rag.strip_rows == 2 : (int64_t)B * H2 <= kSmallStripRows;
-    // batches: two channels per thread on packed fp32 (sub_conv1_dw1_c2_kernel), chunks of 4 columns; C even with 256 % (C / 2) == 0 (8-byte aligned weight pairs)
-    const bool c2 = !small && C % 2 == 0 && C >= 64 && 256 % (C / 2) == 0;
-    if (W2 <= 20 || W2 % 20 == 0) {
-        if (small) launch_c1d1<20, 2>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);
-        else if (c2) launch_c1d1_c2<4>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);
-        else launch_c1d1<10>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);
-    } else {
-        if (small) launch_c1d1<16, 2>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);
-        else if (c2) launch_c1d1_c2<4>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);
-        else launch_c1d1<8>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag);
+    const int strip_rows = rag.strips.u ? (rag.strip_rows == 2 ? 2 : 8) : sub_conv1_dw1_strip_rows((int64_t)B * H2);
+    switch (sub_conv1_dw1_inst(strip_rows, C, W2)) {
+    case C1D1_X20_Y2: launch_c1d1<20, 2>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag); break;
+    case C1D1_X16_Y2: launch_c1d1<16, 2>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag); break;
+    case C1D1_C2_X4_Y8: launch_c1d1_c2<4>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag); break;
+    case C1D1_X10_Y8: launch_c1d1<10>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag); break;
+    case C1D1_X8_Y8: launch_c1d1<8>(feats, B, Tm, F, C, w1, b1, wd, bd, H1, W1, H2, W2, out, s, rag); break;
+    case C1D1_N: break;
     }
 }
 // Depthwise 3x3 stride-2 conv (dw2, src/encoder.cpp:230), channels-last.  One thread = 4 adjacent channels x XO adjacent output
@@ -394,17 +371,16 @@ static void launch_dw4(const float *in, int B, int H, int W, int C, const float 
     hipLaunchKernelGGL(sub_dw4_kernel<XO>, dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, in, H, W, C, wd, bd, Ho, Wo, n_xc, n_items, n_blocks, out, rag);
 }
 
+SubDwInst sub_dw_inst(int Wo) { return Wo % 5 == 0 ? SUBDW_X5 : SUBDW_X4; }
 void launch_sub_dw(const float *in, int B, int H, int W, int C, const float *wd, const float *bd, float *out, hipStream_t s, const SubRag &rag) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    if (C % 4 == 0 && 256 % (C / 4) == 0 && C >= 16) {
-        if (Wo % 5 == 0) launch_dw4<5>(in, B, H, W, C, wd, bd, Ho, Wo, out, s, rag);
-        else launch_dw4<4>(in, B, H, W, C, wd, bd, Ho, Wo, out, s, rag);
-        return;
+    // four channels per thread as one float4, a whole number of items per workgroup: every accepted subsampling_channels (32, 64, 128, 256)
+    if (C % 4 != 0 || C < 16 || 256 % (C / 4) != 0) fail(PK_ERR_UNSUPPORTED, "launch_sub_dw: %d subsampling channels (need a multiple of 4 with 256 %% (C / 4) == 0)", C);
+    switch (sub_dw_inst(Wo)) {
+    case SUBDW_X5: launch_dw4<5>(in, B, H, W, C, wd, bd, Ho, Wo, out, s, rag); break;
+    case SUBDW_X4: launch_dw4<4>(in, B, H, W, C, wd, bd, Ho, Wo, out, s, rag); break;
+    case SUBDW_N: break;
     }
-    const int64_t n_pix = rag.strips.u ? (int64_t)rag.strips.count * Wo : (int64_t)B * Ho * Wo;
-    const int ppb = 256 / C;
-    hipLaunchKernelGGL(sub_dw_kernel, dim3((unsigned)((n_pix + ppb - 1) / ppb)), dim3(256), 0, s, in, H, W, C, wd, bd, Ho, Wo,
-                       n_pix, out, rag);
 }
 
 }  // namespace pk

@@ -14,7 +14,8 @@ def make_pair(tmpdir, cfg, seed=42, with_vocab=False):
     """Returns (weights dict, oracle Model, product capi.Model on GPU 0)."""
     import oracle
     from parakeet_cpp_amd import capi
-    key = (cfg.name, cfg.num_layers, cfg.hidden_size, seed, cfg.head, cfg.num_lstm_layers)
+    key = (cfg.name, cfg.num_layers, cfg.hidden_size, seed, cfg.head, cfg.num_lstm_layers, cfg.mel_bins, cfg.subsampling_channels, cfg.conv_kernel_size,
+           bool(getattr(cfg, "gemm_bf16", False)))
     if key in _CACHE:
         return _CACHE[key]
     W = synth.synth_weights(cfg, seed=seed)

@@ -90,3 +90,28 @@ def test_strict_weight_loading_errors(tmp_path):
     with pytest.raises(capi.PkError) as e:             # reference: std::runtime_error("Cannot open vocab file: ...") vocab.cpp:12-14
         capi.Model(str(wp), cfg, vocab_path=str(tmp_path / "no_vocab.txt"))
     assert "Cannot open vocab file" in str(e.value)
+
+
+def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
+    """pk_diag_conv_variants / pk_diag_conv_instantiations (what tests/test_gpu_conv_variants.py asks before it compares bits) need no device:
+    every reported variant is a row of the list, a ragged batch of equal lengths is the uniform batch, and T describes pk_conformer_blocks' input."""
+    every = capi.diag_conv_instantiations()
+    assert len(every) >= 13 and len(set(every)) == len(every) and {e[0] for e in every} == {0, 1, 2, 3}
+    for kc in (9, 31):
+        cfg = pk.make_tiny_config(conv_kernel_size=kc)
+        wp = tmp_path / f"t{kc}.safetensors"
+        synth.save_weights(str(wp), synth.synth_weights(cfg))
+        m = capi.Model(str(wp), cfg)
+        v = m.conv_variants(B=3, Tm=203, stream_c=2)
+        assert (v["rows_h2"], v["rows_t"]) == (3 * 51, 3 * 26) and v["dwconv"][2] == kc and v["stream"][2] == kc
+        assert all(v[k] in every for k in ("c1d1", "dw2", "dwconv", "stream"))
+        assert v == m.conv_variants(n_mel_frames=[203, 203, 203], stream_c=2)
+        assert m.conv_variants(B=5, T=37)["rows_t"] == 5 * 37 and m.conv_variants(B=1, Tm=9)["stream"] is None
+        assert m.conv_variants(stream_c=1, Tm=9)["stream_fusable"] == (kc == 9) and not m.conv_variants(stream_c=3, Tm=9)["stream_fusable"]
+        # more rows never go back to the small-batch strips
+        ys = [m.conv_variants(B=B, Tm=1001)["c1d1"][4] for B in range(1, 40)]
+        tt = [m.conv_variants(B=B, Tm=1001)["dwconv"][3] for B in range(1, 40)]
+        assert ys == sorted(ys) and tt == sorted(tt) and {2, 8} == set(ys) == set(tt)
+        with pytest.raises(capi.PkError):
+            m.conv_variants(n_mel_frames=[5, 0])
+        m.close()

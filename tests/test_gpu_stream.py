@@ -13,13 +13,17 @@ from parakeet_cpp_amd import capi, synth
 pytestmark = pytest.mark.gpu
 
 
-def run_pair(om, gm, orc, S, left, right, chunk, n_chunks, seed):
+def run_pair(om, gm, orc, S, left, right, chunk, n_chunks, seed, seen=None):
+    """chunk: samples per push, or a list of them (n_chunks is then ignored).  seen (a set) collects (frames of the chunk, 1 if it was the session's
+    first chunk with frames -- no conv cache yet -- else 0)."""
     gs = capi.Stream(gm, S, left, right)
     os_ = [orc.Stream(om, left, right) for _ in range(S)]
-    pcm = synth.synth_pcm(S, chunk * n_chunks, seed=seed)
+    sched = [chunk] * n_chunks if np.isscalar(chunk) else list(chunk)
+    at = np.concatenate([[0], np.cumsum(sched)]).astype(np.int64)
+    pcm = synth.synth_pcm(S, int(at[-1]), seed=seed)
     n_tok, n_enc = 0, 0
-    for i in range(n_chunks):
-        seg = pcm[:, i * chunk:(i + 1) * chunk]
+    for i in range(len(sched)):
+        seg = pcm[:, at[i]:at[i + 1]]
         gmel = gs.mel(seg)
         omel = [o.mel(seg[s]) for s, o in enumerate(os_)]
         assert gmel.shape[1] == omel[0].shape[0]
@@ -32,6 +36,8 @@ def run_pair(om, gm, orc, S, left, right, chunk, n_chunks, seed):
         if genc.shape[1] == 0:
             continue
         G.assert_bits_equal(genc, np.stack(oenc), f"stream encoder, chunk {i}")
+        if seen is not None:
+            seen.add((genc.shape[1], int(n_enc == 0)))
         n_enc += genc.shape[1]
         g = gs.decode(genc)
         for s, o in enumerate(os_):
@@ -52,6 +58,35 @@ def test_stream_stages_tiny(tmp_path_factory, orc, left, right, chunk):
     W, om, gm = G.make_pair(tmp_path_factory.mktemp("ts"), cfg, seed=5)
     n_enc, n_tok = run_pair(om, gm, orc, 3, left, right, chunk, 14, seed=left + chunk)
     assert n_enc >= 10
+
+
+# Pushes of 80 .. 400 ms: chunks of 1 .. 5 encoder frames.  (taps, first push of the schedule, the instantiation of kernels/stream.hip's
+# stream_dwconv_kernel<KC, CMAX> as pk_diag_conv_instantiations lists it); tests/test_gpu_conv_variants.py counts these cases in its coverage check.
+STREAM_SCHED = [2560, 1280, 5120, 3840, 2560, 2560, 6400, 1280, 1280, 3840, 5120, 2560]
+STREAM_CONV_CASES = [(kc, rot, want) for kc, want in ((9, (3, 0, 9, 4, 0)), (31, (3, 1, 31, 2, 0))) for rot in (0, 1, 2, 6)]
+
+
+@pytest.mark.parametrize("kc,rot,want", STREAM_CONV_CASES)
+def test_stream_stages_tiny_conv_sizes(tmp_path_factory, orc, kc, rot, want):
+    """test_stream_stages_tiny's comparison for both conv sizes the streaming conv kernel is instantiated for (9 and 31 taps: a carried conv cache of
+    8 / 30 frames per layer), over chunk sizes on both sides of the kernel's two bodies (the chunk in registers up to CMAX = 4 / 2 frames, the
+    frame loop beyond), with the session's first chunk (no cache yet: zero left padding) taking each of them.  The instantiation and the body
+    are asked of the library (pk_diag_conv_variants); with 31 taps the conv can never ride on the preceding product's epilogue."""
+    cfg = G.tiny(num_layers=2, conv_kernel_size=kc, name=f"tiny-stream-k{kc}")
+    W, om, gm = G.make_pair(tmp_path_factory.mktemp("tsk"), cfg, seed=5)
+    seen = set()
+    sched = (STREAM_SCHED[rot:] + STREAM_SCHED[:rot]) * 2
+    n_enc, n_tok = run_pair(om, gm, orc, 3, 10, 1, sched, None, seed=kc + rot, seen=seen)
+    assert n_enc >= 40
+    bodies = set()
+    for c, first in seen:
+        v = gm.conv_variants(stream_c=c)
+        assert v["stream"] == want and v["stream_body"] == (0 if c <= want[3] else 1), (c, v)
+        if kc == 31:
+            assert v["stream_fusable"] is False, "31 taps take the separate kernel"
+        bodies.add((v["stream_body"], first))
+    print(f"{kc} taps, first push {sched[0]} samples: chunks seen (frames, first) {sorted(seen)}")
+    assert {b for b, _ in bodies} == {0, 1} and any(f for _, f in bodies), f"chunk shapes seen (frames, first): {sorted(seen)}"
 
 
 @pytest.mark.parametrize("left,right,chunk", [(70, 1, 4000), (10, 0, 5600), (6, 2, 1600), (70, 3, 10240)])

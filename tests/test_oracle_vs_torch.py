@@ -57,6 +57,37 @@ def test_conformer_block_matches_torch(orc, tiny_cfg, tiny_weights, tiny_oracle,
     assert rel_err(out, ref) < 2e-5
 
 
+@pytest.mark.parametrize("C", [32, 64])
+@pytest.mark.parametrize("mel_bins", [72, 96])
+def test_subsampling_matches_torch_other_widths(orc, mel_bins, C):
+    """Mel widths whose subsampled widths (18 / 24 after two stride-2 stages, 9 / 12 after three) are not the 20 / 32 and 10 / 16 of the presets:
+    the kernels split those rows into column chunks with a partial last chunk, so the oracle they are compared with is pinned here first."""
+    from conftest import pk
+    cfg = pk.make_tiny_config(mel_bins=mel_bins, subsampling_channels=C)
+    W = synth.synth_weights(cfg, seed=42)
+    feats = np.random.default_rng(mel_bins + C).standard_normal((2, 203, mel_bins)).astype(np.float32)
+    out = orc.Model(cfg, W).subsampling(feats)
+    ref = torch_ref.subsampling(W, feats)
+    assert out.shape == ref.shape == (2, 26, cfg.hidden_size)
+    assert rel_err(out, ref) < 2e-5
+
+
+@pytest.mark.parametrize("T", [1, 7, 16, 37])
+@pytest.mark.parametrize("stop", [3, 0])
+def test_conformer_block_31_taps_matches_torch(orc, stop, T):
+    """conv_kernel_size = 31 (the other size the engine instantiates): after the conv module and after the whole block.  T <= 15: every window of
+    31 taps hangs over both ends of the utterance."""
+    from conftest import pk
+    cfg = pk.make_tiny_config(conv_kernel_size=31)
+    W = synth.synth_weights(cfg, seed=42)
+    assert W["encoder_.layers_.1.conv_.depthwise_conv_.weight"].shape[-1] == 31
+    x = np.random.default_rng(T).standard_normal((2, T, cfg.hidden_size)).astype(np.float32)
+    pe = orc.pos_emb(T, cfg.hidden_size)
+    out = orc.Model(cfg, W).conformer_block(1, x, pe, stop_after=stop)
+    ref = torch_ref.conformer_block(W, 1, x, pe, cfg.num_heads, stop_after=stop)
+    assert rel_err(out, ref) < 2e-5
+
+
 def test_pos_emb_matches_numpy_float(orc):
     pe = orc.pos_emb(20, 64)
     ref = torch_ref.pos_emb(20, 64)

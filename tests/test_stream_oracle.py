@@ -37,6 +37,33 @@ def test_stream_oracle_matches_torch(orc, left, right, chunk):
     assert n_enc >= 10
 
 
+def test_stream_oracle_31_taps_matches_torch(orc):
+    """conv_kernel_size = 31: a conv cache of 30 frames per layer carried from chunk to chunk (zeros in front of the first), same tolerances."""
+    left, right, chunk = 10, 1, 2560
+    cfg = pk.make_tiny_config(num_layers=2, conv_kernel_size=31)
+    W = synth.synth_weights(cfg, seed=5)
+    st = orc.Stream(orc.Model(cfg, W), left, right)
+    ts = TorchStream(cfg, W, orc.mel_filterbank(n_mels=cfg.mel_bins), left, right)
+    pcm = synth.synth_pcm(1, chunk * 24, seed=31)[0]
+    n_enc = 0
+    for i in range(24):                                           # past 30 frames: the cache fills and rotates
+        seg = pcm[i * chunk:(i + 1) * chunk]
+        m, tm = st.mel(seg), ts.mel(seg)
+        assert (tm is None) == (m.shape[0] == 0)
+        if tm is None:
+            continue
+        assert m.shape == tuple(tm.shape)
+        assert np.abs(m - tm.numpy()).max() < 2e-3
+        e, te = st.encode(m), ts.encode(torch_from(m))
+        assert (te is None) == (e.shape[0] == 0)
+        if te is None:
+            continue
+        assert e.shape == tuple(te.shape)
+        assert np.abs(e - te.numpy()).max() < 2e-4, f"chunk {i}"
+        n_enc += e.shape[0]
+    assert n_enc > 31
+
+
 def torch_from(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a))
