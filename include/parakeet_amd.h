@@ -608,6 +608,34 @@ pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int 
 #define PK_DIAG_CONV_VARIANT_WORDS 17
 pk_status pk_diag_conv_variants(const pk_model *m, int B, int Tm, const int32_t *n_mel_frames, int stream_c, int32_t *out);
 int pk_diag_conv_instantiations(int32_t *out, int cap_rows);
+/* ONE launch of a skinny product of the TDT / RNNT decode loop (kernels/decode_gemv.hip, kernels/decode_gemv_bf16.hip; kernels.hpp SkinnyArgs).
+ * Every operand is given in its NATURAL layout as fp32 and packed here by the functions the loader packs with (csrc/dec_pack.hpp): fp32 mode = the
+ * sigma K order of X / W / X2 / W2; bf16 mode = X / X2 rounded to bf16 (RNE), W / W2 in the kernel's per-lane tile order, rounded to bf16.
+ *   epi 0 (bias):        out[b][n] = X[b] . W[n] (+ bias[n]);  out fp32 [out_rows][ldo], ldo >= N.
+ *   epi 1 (activation):  p = X[b] . W[n] (+ bias[n]); pp_out[b][n] = p (pp_out may be NULL); z[b][n] = relu(ep[r0_b + min(t[b], Tb_b - 1)][n] + p) with
+ *                        Tb_b = Tb ? Tb[b] : T and r0_b = row0 ? row0[b] : b * T;  ep [ep_rows][N].  z: [out_rows][N]; fp32 mode: sigma column order,
+ *                        and with F > 1 (fp32 only; needs `need` and B <= 16) the rows b * F + f take the frames t[b] + f, f < F.
+ *   epi 2 (LSTM cell):   N is the hidden size Hp; W [4 Hp][K]; gates = gi + X[b] . W[g Hp + j] with gi = gi_tab[gi_row ? gi_row[b] : b][g Hp + j] (row
+ *                        stride gi_ld), or, when W2 is set, gi = X2[b] . W2[g Hp + j] + bias2[g Hp + j];  c' = sigmoid(f) c + sigmoid(i) tanh(g) -> cn [out_rows][Hp]
+ *                        fp32; h' = sigmoid(o) tanh(c') -> out [out_rows][Hp] (fp32 mode: sigma column order).
+ * bf16 mode stores z / h' as bf16: out then holds uint16 words.  need (may be NULL): [B] flags; only rows with a set flag are computed (B <= 16: the flags as
+ * predicates; 16 < B <= 2048: the compacted row list; PK_ERR_INVALID above that).  out / cn / pp_out are BOTH input and output: the caller fills them with a
+ * pattern, they are copied to the device, the kernel runs, they are copied back whole -- out_rows >= B * F, the rows past the batch and (epi 0) the columns
+ * past N show stores that left the output.  Shapes: bf16 K % 32 == 0 and (cell) Hp % 4 == 0; fp32 K % 16 == 0 and (activation / cell) N % 16 == 0. */
+typedef struct pk_skinny_diag {
+    int32_t bf16, epi, B, N, K;
+    const float *X, *W, *bias;
+    const float *gi; int32_t gi_rows, gi_ld; const int32_t *gi_row; const float *c;
+    const float *X2, *W2, *bias2;
+    const float *ep; int64_t ep_rows; const int32_t *t; int32_t T; const int32_t *Tb, *row0; int32_t F;
+    const int32_t *need;
+    int32_t out_rows, ldo;
+    void *out; float *cn, *pp_out;
+} pk_skinny_diag;
+pk_status pk_diag_skinny_gemm(const pk_skinny_diag *a);
+/* Prediction-net caching of the per-phase decode loop (kernels.hpp TdtState::need) on / off; process-wide test switch, default on.  Off: every
+ * phase launch covers every utterance at any batch size -- the same words, bit for bit (tests/test_gpu_bf16_decode_batch.py). */
+pk_status pk_diag_pred_cache(int on);
 
 #ifdef __cplusplus
 }

@@ -357,6 +357,82 @@ def diag_smallm_bf16_tiles(on):
     check(L.pk_diag_smallm_bf16_tiles(int(on)))
 
 
+class PkSkinnyDiag(C.Structure):
+    _fields_ = [("bf16", C.c_int32), ("epi", C.c_int32), ("B", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("X", f32p), ("W", f32p), ("bias", f32p),
+                ("gi", f32p), ("gi_rows", C.c_int32), ("gi_ld", C.c_int32), ("gi_row", i32p), ("c", f32p),
+                ("X2", f32p), ("W2", f32p), ("bias2", f32p),
+                ("ep", f32p), ("ep_rows", C.c_int64), ("t", i32p), ("T", C.c_int32), ("Tb", i32p), ("row0", i32p), ("F", C.c_int32),
+                ("need", i32p), ("out_rows", C.c_int32), ("ldo", C.c_int32), ("out", C.c_void_p), ("cn", f32p), ("pp_out", f32p)]
+
+
+SKINNY_EPI = {"bias": 0, "act": 1, "cell": 2}
+SKINNY_FILL32, SKINNY_FILL16 = 0x7FC5A5A5, 0x7FC5          # what an element no store reached comes back as (fp32 / bf16 outputs)
+
+
+def sigma16(n):
+    """the fp32 decode kernels' column order (decode_dev.hpp sigma16; its own inverse): the 4x4 index transpose inside every block of 16"""
+    k = np.arange(n)
+    return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3)
+
+
+def diag_skinny_gemm(epi, X, W, bias=None, bf16=False, gi=None, gi_row=None, c=None, X2=None, W2=None, bias2=None, ep=None, t=None, T=0,
+                     Tb=None, row0=None, F=1, want_pp=False, need=None, pad_rows=3, pad_cols=5):
+    """pk_diag_skinny_gemm: one launch of a decode-loop product on operands in natural layout (include/parakeet_amd.h).  Returns a dict of the WHOLE
+    output buffers, pattern-filled before the launch (SKINNY_FILL32 / SKINNY_FILL16) and pad_rows rows longer than the batch: `out` ([B F + pad][N + pad_cols]
+    fp32 for "bias"; [B F + pad][N] for "act" / "cell": uint16 bf16 words in the bf16 mode, else fp32 words with the sigma column order undone), `cn`
+    (cell) and `pp` (act with want_pp) as uint32 words."""
+    e = SKINNY_EPI[epi]
+    X, W = _c(X), _c(W)
+    B, K = X.shape
+    N = W.shape[0] // 4 if epi == "cell" else W.shape[0]
+    F = int(F) if epi == "act" else 1
+    rows = B * F + pad_rows
+    keep = [X, W]
+
+    def opt(a, dt=np.float32):
+        if a is None:
+            return None
+        a = _c(a, dt)
+        keep.append(a)
+        return a.ctypes.data_as(f32p if dt == np.float32 else i32p)
+
+    d = PkSkinnyDiag()
+    d.bf16, d.epi, d.B, d.N, d.K = int(bool(bf16)), e, B, N, K
+    d.X, d.W, d.bias = _f(X), _f(W), opt(bias)
+    if gi is not None:
+        gi = _c(gi)
+        d.gi_rows, d.gi_ld = gi.shape
+    d.gi, d.gi_row, d.c = opt(gi), opt(gi_row, np.int32), opt(c)
+    d.X2, d.W2, d.bias2 = opt(X2), opt(W2), opt(bias2)
+    if ep is not None:
+        ep = _c(ep).reshape(-1, N)
+        d.ep_rows = ep.shape[0]
+    d.ep, d.t, d.T, d.Tb, d.row0, d.F = opt(ep), opt(t, np.int32), int(T), opt(Tb, np.int32), opt(row0, np.int32), F
+    d.need = opt(need, np.int32)
+    ld = N + pad_cols if epi == "bias" else N
+    half = bool(bf16) and epi != "bias"
+    out = np.full((rows, ld), SKINNY_FILL16 if half else SKINNY_FILL32, np.uint16 if half else np.uint32)
+    cn = np.full((rows, N), SKINNY_FILL32, np.uint32) if epi == "cell" else None
+    pp = np.full((rows, N), SKINNY_FILL32, np.uint32) if (epi == "act" and want_pp) else None
+    d.out_rows, d.ldo, d.out = rows, ld, out.ctypes.data_as(C.c_void_p)
+    d.cn = cn.ctypes.data_as(f32p) if cn is not None else None
+    d.pp_out = pp.ctypes.data_as(f32p) if pp is not None else None
+    L = lib()
+    L.pk_diag_skinny_gemm.argtypes = [C.POINTER(PkSkinnyDiag)]
+    check(L.pk_diag_skinny_gemm(C.byref(d)))
+    if not half and epi != "bias":
+        out = np.ascontiguousarray(out[:, sigma16(N)])
+    return dict(out=out, cn=cn, pp=pp)
+
+
+def diag_pred_cache(on):
+    """pk_diag_pred_cache: prediction-net caching of the per-phase decode loop on / off (test switch, process-wide, default on)."""
+    L = lib()
+    L.pk_diag_pred_cache.argtypes = [C.c_int]
+    check(L.pk_diag_pred_cache(int(on)))
+
+
 def diag_ffn_bf16_smallm(x, gamma, beta, W1, b1, W2, b2, act_tiles, eps=1e-5):
     """pk_diag_ffn_bf16_smallm: x + 0.5 * ffn(LN(x)) of a streaming chunk on the small-M bf16 kernel; act_tiles = fc1 activations in 8-row operand tiles."""
     x, gamma, beta, W1, b1, W2, b2 = (_c(v) for v in (x, gamma, beta, W1, b1, W2, b2))

@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "engine.hpp"
+#include "dec_pack.hpp"
 #include "rccl_dyn.hpp"
 
 namespace pk {
@@ -2287,6 +2288,108 @@ pk_status pk_diag_ffn_bf16_smallm(int M, int d, int f, const float *x, const flo
         launch_gemm_bf16(g2, EPI_RESID, nullptr);
         PK_CHECK_LAUNCH();
         PK_HIP(hipMemcpy(out, ob.p, (size_t)M * d * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+pk_status pk_diag_pred_cache(int on) { g_diag_pred_cache.store(on ? 1 : 0); return PK_OK; }
+
+pk_status pk_diag_skinny_gemm(const pk_skinny_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const int B = d->B, N = d->N, K = d->K, epi = d->epi;
+        const bool b16 = d->bf16 != 0, cell = epi == SK_CELL, act = epi == SK_ACT;
+        need(epi == SK_BIAS || act || cell, "epi");
+        need(d->X && d->W && d->out && B > 0 && N > 0 && K > 0, "X/W/out/B/N/K");
+        const int F = act && d->F > 1 ? d->F : 1;
+        const int wrows = cell ? 4 * N : N;
+        if (b16) {
+            need(K % 32 == 0, "bf16: K must be a multiple of 32");
+            need(!cell || N % 4 == 0, "bf16 cell: Hp must be a multiple of 4");
+            need(F == 1, "the frame window is an fp32 form");
+        } else {
+            need(K % 16 == 0, "fp32: K must be a multiple of 16");
+            need(epi == SK_BIAS || N % 16 == 0, "fp32 activation / cell: N must be a multiple of 16 (sigma layout of the output)");
+            need(F <= kDecWindowMax, "F");
+            need(F == 1 || (d->need && B <= 16), "the frame window comes with need flags and B <= 16");
+        }
+        need(!d->need || B <= kMaxListRows, "need flags: B <= 2048");
+        need(d->out_rows >= B * F, "out_rows >= B * F");
+        const int ld = epi == SK_BIAS ? d->ldo : N;
+        need(ld >= N, "ldo >= N");
+        if (cell) {
+            need(d->c && d->cn, "cell: c/cn");
+            if (d->W2) need(d->X2 && d->bias2, "cell: X2/bias2 with W2");
+            else {
+                need(d->gi && d->gi_ld >= 4 * N && d->gi_rows > 0, "cell: gi/gi_ld/gi_rows");
+                for (int b = 0; b < B; ++b) {
+                    const int r = d->gi_row ? d->gi_row[b] : b;
+                    need(r >= 0 && r < d->gi_rows, "cell: gi_row out of range");
+                }
+            }
+        }
+        if (act) {
+            need(d->ep && d->t && d->ep_rows > 0, "activation: ep/t/ep_rows");
+            for (int b = 0; b < B; ++b) {
+                const int Tb = d->Tb ? d->Tb[b] : d->T;
+                const int64_t r0 = d->row0 ? (int64_t)d->row0[b] : (int64_t)b * d->T;
+                need(Tb >= 1 && r0 >= 0 && r0 + Tb <= d->ep_rows && d->t[b] >= 0, "activation: frames out of range");
+            }
+        }
+        diag_device();
+        const size_t out_el = epi != SK_BIAS && b16 ? 2 : 4;
+        DevBuf dX, dW, dX2, dW2, dbias, dbias2, dgi, dgr, dc, dep, dt, dTb, dr0, dneed, dout, dcn, dpp;
+        auto up = [](DevBuf &buf, const void *src, size_t bytes) {
+            buf.reserve(bytes);
+            PK_HIP(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
+        };
+        auto up16 = [&](DevBuf &buf, const float *src, size_t n) {
+            std::vector<uint16_t> h(n);
+            for (size_t i = 0; i < n; ++i) h[i] = bf16_rne(src[i]);
+            up(buf, h.data(), n * 2);
+        };
+        auto up_x = [&](DevBuf &buf, const float *x) {
+            if (b16) up16(buf, x, (size_t)B * K);
+            else { const std::vector<float> p = pack_sigma(x, B, K); up(buf, p.data(), p.size() * 4); }
+        };
+        auto up_w = [&](DevBuf &buf, const float *w) {
+            if (b16) { const std::vector<float> p = pack_dec16(w, wrows, K, cell); up16(buf, p.data(), p.size()); }
+            else { const std::vector<float> p = pack_sigma(w, wrows, K); up(buf, p.data(), p.size() * 4); }
+        };
+        SkinnyArgs a{};
+        up_x(dX, d->X); up_w(dW, d->W);
+        a.X = dX.as<float>(); a.W = dW.as<float>(); a.B = B; a.N = wrows; a.K = K;
+        if (d->bias && !cell) { up(dbias, d->bias, (size_t)N * 4); a.bias = dbias.as<float>(); }
+        up(dout, d->out, (size_t)d->out_rows * ld * out_el);
+        a.out = dout.as<float>(); a.ldo = ld;
+        a.F = F;
+        if (cell) {
+            a.Hp = N;
+            up(dc, d->c, (size_t)B * N * 4); a.c = dc.as<float>();
+            up(dcn, d->cn, (size_t)d->out_rows * N * 4); a.cn = dcn.as<float>();
+            if (d->W2) {
+                up_x(dX2, d->X2); up_w(dW2, d->W2); up(dbias2, d->bias2, (size_t)4 * N * 4);
+                a.X2 = dX2.as<float>(); a.W2 = dW2.as<float>(); a.bias2 = dbias2.as<float>();
+                a.gi_ld = 4 * N;
+            } else {
+                up(dgi, d->gi, (size_t)d->gi_rows * d->gi_ld * 4); a.gi = dgi.as<float>(); a.gi_ld = d->gi_ld;
+                if (d->gi_row) { up(dgr, d->gi_row, (size_t)B * 4); a.gi_row = dgr.as<int>(); }
+            }
+        }
+        if (act) {
+            up(dep, d->ep, (size_t)d->ep_rows * N * 4); a.ep = dep.as<float>();
+            up(dt, d->t, (size_t)B * 4); a.t = dt.as<int>(); a.T = d->T;
+            if (d->Tb) { up(dTb, d->Tb, (size_t)B * 4); a.Tb = dTb.as<int>(); }
+            if (d->row0) { up(dr0, d->row0, (size_t)B * 4); a.row0 = dr0.as<int>(); }
+            if (d->pp_out) { up(dpp, d->pp_out, (size_t)d->out_rows * N * 4); a.pp_out = dpp.as<float>(); }
+        }
+        if (d->need) { up(dneed, d->need, (size_t)B * 4); a.need = dneed.as<int>(); }
+        if (b16) launch_skinny_gemm_bf16(a, epi, nullptr);
+        else launch_skinny_gemm(a, epi, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        PK_HIP(hipMemcpy(d->out, dout.p, (size_t)d->out_rows * ld * out_el, hipMemcpyDeviceToHost));
+        if (cell) PK_HIP(hipMemcpy(d->cn, dcn.p, (size_t)d->out_rows * N * 4, hipMemcpyDeviceToHost));
+        if (act && d->pp_out) PK_HIP(hipMemcpy(d->pp_out, dpp.p, (size_t)d->out_rows * N * 4, hipMemcpyDeviceToHost));
     });
 }
 

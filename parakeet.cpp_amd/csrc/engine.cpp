@@ -1,5 +1,6 @@
 // parakeet.cpp_amd/csrc/engine.cpp -- model lifetime, weight upload / derived tables, stage drivers.
 #include "engine.hpp"
+#include "dec_pack.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -8,6 +9,8 @@
 #include <cstring>
 
 namespace pk {
+
+std::atomic<int> g_diag_pred_cache{1};
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string &msg) { g_last_error = msg; }
@@ -102,15 +105,6 @@ const HostTensor &Model::host_tensor(const std::string &name, const std::vector<
         fail(PK_ERR_WEIGHTS, "tensor '%s' has shape [ %s], expected [ %s]", name.c_str(), got.c_str(), want.c_str());
     }
     return *t;
-}
-
-// fp32 -> bf16, round to nearest even (what v_cvt_pk_bf16_f32 does to the activations on the device)
-static inline uint16_t bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
 }
 
 // Weight of a Linear / 1x1 conv that runs on the MFMA GEMM: fp32 as is, or (pk_config.gemm_bf16) rounded to bf16 once here.
@@ -274,32 +268,13 @@ void Model::upload_weights() {
     }
 
     const int V = cfg.vocab_size, Hp = cfg.pred_hidden, J = cfg.joint_hidden, D = cfg.num_durations;
-    // "sigma" K layout of the decode-loop weights (kernels/decode_gemv.hip): inside every block of 16 input features the
-    // 4x4 index matrix is transposed, so one float4 holds a lane's k = 4s+kq operands of four consecutive MFMA steps.
-    auto sigma = [](int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); };
+    // decode-loop weight layouts (dec_pack.hpp): the fp32 kernels' "sigma" K order, the bf16 kernels' per-lane load order
     auto upload_sigma = [&](const float *w, int rows, int K) {
-        std::vector<float> p((size_t)rows * K);
-        for (int r = 0; r < rows; ++r)
-            for (int k = 0; k < K; ++k) p[(size_t)r * K + sigma(k)] = w[(size_t)r * K + k];
+        const std::vector<float> p = pack_sigma(w, rows, K);
         return upload(p.data(), p.size());
     };
-    // bf16 decode weights (tolerance-class mode) in the LOAD ORDER of skinny_gemm_bf16_kernel: per (16-output tile, 32-k block) one 1 KB block
-    // [lane][8] -- lane (col = lane & 15, kq = lane >> 4) holds W[row(tile, col)][32 blk + 8 kq .. + 7], so a wave's load instruction reads 1 KB of
-    // consecutive addresses and a tile's weight stream is one contiguous run.  cell: the tile's columns are (gate, unit) pairs of the LSTM,
-    // row = (col >> 2) * Hp + 4 tile + (col & 3); otherwise row = 16 tile + col (clamped to the last row: the kernel never stores those columns).
     auto upload_dec16 = [&](const float *w, int rows, int K, bool cell) {
-        const int n_tiles = cell ? rows / 16 : (rows + 15) / 16, nblk = K / 32, hp = rows / 4;
-        std::vector<float> p((size_t)n_tiles * nblk * 512);
-        for (int t = 0; t < n_tiles; ++t)
-            for (int blk = 0; blk < nblk; ++blk)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int col = lane & 15, kq = lane >> 4;
-                    int row = cell ? (col >> 2) * hp + 4 * t + (col & 3) : 16 * t + col;
-                    row = row < rows ? row : rows - 1;
-                    const float *src = w + (size_t)row * K + 32 * blk + 8 * kq;
-                    float *dst = p.data() + (((size_t)t * nblk + blk) * 64 + lane) * 8;
-                    for (int e = 0; e < 8; ++e) dst[e] = src[e];
-                }
+        const std::vector<float> p = pack_dec16(w, rows, K, cell);
         return upload_gemm_weight(p.data(), p.size());
     };
     if (cfg.ctc_vocab_size > 0) {
@@ -1196,7 +1171,7 @@ void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t
     // Prediction-net caching (kernels.hpp TdtState::need): after a blank the cells and pred_proj of the next step would recompute, bit for bit,
     // what they produced the step before -- those rows are skipped (~2/3 of all utterance-steps on the benchmark's clips).  Per-phase loop only
     // (the single-launch loop keeps every row), lock-step batches up to kMaxListRows.
-    bool pred_cache = B <= kMaxListRows && decode_loop != PK_DECODE_LOOP_PERSISTENT;
+    bool pred_cache = B <= kMaxListRows && decode_loop != PK_DECODE_LOOP_PERSISTENT && g_diag_pred_cache.load() != 0;
     if (pred_cache) {
         st.need = ib + 6 * B + 8;                                    // (behind done_count and the persistent loop's two spare words)
         st.pp = w.pp.as<float>();

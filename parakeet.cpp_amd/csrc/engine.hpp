@@ -4,6 +4,7 @@
 // derived tables built) once in to_gpu(); activations live in a grow-only workspace; every stage is a
 // short, fixed sequence of hand-written kernels on one HIP stream.
 #pragma once
+#include <atomic>
 #include <map>
 #include <functional>
 #include <memory>
@@ -266,6 +267,10 @@ class Model {
 
 // thread-local error slot of the C ABI
 void set_last_error(const std::string &msg);
+
+// pk_diag_pred_cache (test switch, process-wide, default 1): 0 = Model::run_tdt_loop runs without prediction-net caching -- every phase launch of the
+// per-phase loop covers every row at any batch size
+extern std::atomic<int> g_diag_pred_cache;
 
 }  // namespace pk
 

@@ -175,7 +175,8 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
     }
     // software pipeline: chunks of 4 float4 pairs (16 MFMAs, ~640 cycles) with the next chunk's loads in flight
     constexpr int CH = 4;
-    const int nchunks = a.K / (16 * CH);
+    const int nq = a.K / 16;                                       // float4 pairs per lane (K % 16 == 0)
+    const int nchunks = (nq + CH - 1) / CH;                        // runtime trip count: the last chunk may be partial (K % 64 != 0)
     float4 xa[CH], wa[CH], xb[CH], wb[CH];
 #define SK_LOAD(X_, W_, c_)                                                         \
     _Pragma("unroll") for (int i = 0; i < CH; ++i) {                               \
@@ -189,6 +190,24 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X_[i].y, W_[i].y, acc, 0, 0, 0); \
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X_[i].z, W_[i].z, acc, 0, 0, 0); \
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X_[i].w, W_[i].w, acc, 0, 0, 0); \
+    }                                                                               \
+    __builtin_amdgcn_sched_barrier(0);
+    // runtime trip count: a partial last chunk re-loads the row's last pair (no access past the row) and leaves its MFMAs out
+#define SK_LOADG(X_, W_, c_)                                                        \
+    _Pragma("unroll") for (int i = 0; i < CH; ++i) {                               \
+        const int q_ = (c_) * CH + i < nq ? (c_) * CH + i : nq - 1;                 \
+        X_[i] = dd_ld4<COH>(xq + 4 * q_);                                           \
+        W_[i] = wq[4 * q_];                                                         \
+    }                                                                               \
+    __builtin_amdgcn_sched_barrier(0);
+#define SK_MMAG(X_, W_, c_)                                                         \
+    _Pragma("unroll") for (int i = 0; i < CH; ++i) {                               \
+        if ((c_) * CH + i < nq) {                                                   \
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X_[i].x, W_[i].x, acc, 0, 0, 0); \
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X_[i].y, W_[i].y, acc, 0, 0, 0); \
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X_[i].z, W_[i].z, acc, 0, 0, 0); \
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(X_[i].w, W_[i].w, acc, 0, 0, 0); \
+        }                                                                           \
     }                                                                               \
     __builtin_amdgcn_sched_barrier(0);
     // one single-chain product acc = X W^T over K (natural k order) through the two-set prefetch ring
@@ -215,16 +234,16 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
                 if (c + 1 < NCH) { SK_MMA(xb, wb) }
             }
         } else {
-            SK_LOAD(xa, wa, 0)
+            SK_LOADG(xa, wa, 0)
             if constexpr (PRED) {
                 const bool mine = EPI == SK_CELL ? nd_cell != 0 : (nd_out[0] | nd_out[1] | nd_out[2] | nd_out[3]) != 0;
                 if (__builtin_amdgcn_ballot_w64(mine) == 0) { pred_skip = true; return acc; }
             }
             for (int c = 0; c < nchunks; c += 2) {
-                if (c + 1 < nchunks) { SK_LOAD(xb, wb, c + 1) }
-                SK_MMA(xa, wa)
-                if (c + 2 < nchunks) { SK_LOAD(xa, wa, c + 2) }
-                if (c + 1 < nchunks) { SK_MMA(xb, wb) }
+                if (c + 1 < nchunks) { SK_LOADG(xb, wb, c + 1) }
+                SK_MMAG(xa, wa, c)
+                if (c + 2 < nchunks) { SK_LOADG(xa, wa, c + 2) }
+                if (c + 1 < nchunks) { SK_MMAG(xb, wb, c + 1) }
             }
         }
         return acc;
@@ -241,12 +260,15 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
     if constexpr (PRED) { if (pred_skip) return; }
 #undef SK_LOAD
 #undef SK_MMA
+#undef SK_LOADG
+#undef SK_MMAG
     // C/D layout of 16x16x4: column = lane & 15, row (utterance) = 4 * (lane >> 4) + r
     if (EPI == SK_BIAS) {
         const int n = 16 * nt + col;
         if (n < a.N) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
+                if constexpr (PRED) { if (!nd_out[r]) continue; }
                 if (m0 + 4 * kq + r < NB) dd_stf<COH>(a.out + (int64_t)rb_out[r] * a.ldo + n, a.bias ? acc[r] + e_bias : acc[r]);
             }
         }

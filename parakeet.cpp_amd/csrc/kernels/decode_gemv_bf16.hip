@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_bf16_kernel(SkinnyArgs a) {
         if (n < a.N) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (m0 + 4 * kq + r < NB) a.out[(int64_t)rb_out[r] * a.ldo + n] = a.bias ? acc[r] + e_bias : acc[r];
+                if (m0 + 4 * kq + r < NB && nd_out[r]) a.out[(int64_t)rb_out[r] * a.ldo + n] = a.bias ? acc[r] + e_bias : acc[r];
         }
     } else if (EPI == SK_ACT) {
         // z = relu(enc_proj(enc_t) + pred_proj(pred) [+ bp])   src/tdt.cpp:17-18 ; stored as bf16 (it is only ever the heads' operand)
