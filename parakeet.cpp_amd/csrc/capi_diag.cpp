@@ -1,0 +1,563 @@
+// parakeet.cpp_amd/csrc/capi_diag.cpp -- the pk_diag_* entry points of the C boundary: single kernels and launcher decisions, run alone on
+// operands the caller hands over, for the kernel-level tests.  Nothing here is kept between calls: every call stages its operands afresh.
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <initializer_list>
+
+#include "capi_util.hpp"
+#include "dec_pack.hpp"
+
+using namespace pk;
+
+namespace {
+// The one way an operand is staged: its device buffer reserved and filled from the host.  src == nullptr (an optional operand the caller
+// left out) only reserves the buffer.
+void up(DevBuf &buf, const void *src, size_t bytes) {
+    buf.reserve(bytes);
+    if (src) PK_HIP(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
+}
+// ... rounded to bf16 on the host (nearest even), as the weights are at upload and as the producing kernels of the bf16 mode store activations
+void up16(DevBuf &buf, const float *src, size_t n) {
+    std::vector<uint16_t> h(n);
+    for (size_t i = 0; i < n; ++i) h[i] = bf16_rne(src[i]);
+    up(buf, h.data(), n * 2);
+}
+// ... several vectors of n floats one behind the other in one buffer (LayerNorm gamma / beta, ...); a null one leaves its slot unwritten
+void up_rows(DevBuf &buf, std::initializer_list<const float *> rows, size_t n) {
+    buf.reserve(rows.size() * n * 4);
+    float *dst = buf.as<float>();
+    for (const float *r : rows) {
+        if (r) PK_HIP(hipMemcpy(dst, r, n * 4, hipMemcpyHostToDevice));
+        dst += n;
+    }
+}
+void down(void *dst, const DevBuf &buf, size_t bytes) { PK_HIP(hipMemcpy(dst, buf.p, bytes, hipMemcpyDeviceToHost)); }
+// a bf16 array of the device, widened to fp32
+void down16(float *dst, const DevBuf &buf, size_t n) {
+    std::vector<uint16_t> h(n);
+    down(h.data(), buf, n * 2);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t u = (uint32_t)h[i] << 16;
+        memcpy(&dst[i], &u, 4);
+    }
+}
+}  // namespace
+
+extern "C" {
+
+pk_status pk_diag_math(int fn, const float *in, float *out, int64_t n) {
+    return guard([&] {
+        need(in && out && n > 0, "in/out/n");
+        need_device();
+        DevBuf x, y;
+        up(x, in, n * 4);
+        y.reserve(n * 4);
+        launch_math(fn, x.as<float>(), y.as<float>(), n, nullptr);
+        PK_CHECK_LAUNCH();
+        down(out, y, n * 4);
+    });
+}
+
+pk_status pk_diag_math_exhaustive(int fn, uint64_t *checked, uint64_t *mismatches, uint64_t *first_bad) {
+    return guard([&] {
+        need(fn == 3 || fn == 4 || fn == 13 || fn == 14, "fn must be 3, 4, 13 or 14");
+        need(checked && mismatches && first_bad, "checked/mismatches/first_bad");
+        need_device();
+        DevBuf acc;
+        const uint64_t init[3] = {0, 0, 1ull << 32};
+        up(acc, init, sizeof init);
+        launch_math_exhaustive(fn, acc.as<unsigned long long>(), nullptr);
+        PK_CHECK_LAUNCH();
+        uint64_t res[3];
+        down(res, acc, sizeof res);
+        *checked = res[0]; *mismatches = res[1]; *first_bad = res[2];
+    });
+}
+
+// The bf16 diag products run as a streaming session runs them: weights also as operand tiles of the small-M kernel (GemmArgs::W_t16) where the
+// shape allows (rows % 16 == 0, K % 32 == 0).  pk_diag_smallm_bf16_tiles(0) keeps the natural layout only (both are tested, bit for bit).
+static std::atomic<int> g_diag_tiles{1};
+pk_status pk_diag_smallm_bf16_tiles(int on) { g_diag_tiles.store(on ? 1 : 0); return PK_OK; }
+static const float *diag_operand_tiles(DevBuf &buf, const float *w16, int64_t rows, int K) {
+    if (!g_diag_tiles.load() || rows % 16 != 0 || K % 32 != 0) return nullptr;
+    buf.reserve((size_t)rows * K * 2);
+    launch_tile_copy_bf16(w16, buf.as<float>(), rows, K, K, nullptr);
+    return buf.as<float>();
+}
+
+// out = epi(alpha * A W^T + bias [, resid]) on one launcher -- the body of the four product diagnostics below.  bf16: W rounded to bf16, the
+// bf16 launcher (a16: A handed over as bf16 too, GemmArgs::a_bf16; gamma / beta: the LayerNorm of the rows of A folded into the product).
+static void diag_product(int M, int N, int K, const float *A, const float *W, const float *bias, int epi, const float *resid, float alpha, float *out,
+                         bool bf16, bool a16 = false, const float *gamma = nullptr, const float *beta = nullptr, float eps = 0.0f) {
+    need(epi >= 0 && epi <= 4, "epi");
+    need(epi != EPI_RESID || resid, "resid");
+    need_device();
+    const int wrows = epi == EPI_GLU ? 2 * N : N;
+    DevBuf a, w, b, r, o, gb, wt;
+    if (a16) up16(a, A, (size_t)M * K);
+    else up(a, A, (size_t)M * K * 4);
+    if (bf16) up16(w, W, (size_t)wrows * K);
+    else up(w, W, (size_t)wrows * K * 4);
+    if (gamma) up_rows(gb, {gamma, beta}, K);
+    up(b, bias, (size_t)wrows * 4);
+    up(r, resid, (size_t)M * N * 4);
+    o.reserve((size_t)M * N * 4);
+    GemmArgs g{a.as<float>(), K, w.as<float>(), K, bias ? b.as<float>() : nullptr, o.as<float>(), N,
+               resid ? r.as<float>() : nullptr, N, alpha, M, N, K};
+    if (a16) g.a_bf16 = 1;
+    if (gamma) { g.ln_g = gb.as<float>(); g.ln_b = gb.as<float>() + K; g.ln_eps = eps; }
+    if (bf16) g.W_t16 = diag_operand_tiles(wt, w.as<float>(), wrows, K);
+    if (gamma && !gemm_smallm_bf16_ln_applies(g, epi)) fail(PK_ERR_UNSUPPORTED, "pk_diag_ln_gemm_bf16: M <= %d, K = 256 * (1 .. 8; glu: .. 4)", kSmallMRowsBf16);
+    if (bf16) launch_gemm_bf16(g, epi, nullptr);
+    else launch_gemm(g, epi, nullptr);
+    PK_CHECK_LAUNCH();
+    down(out, o, (size_t)M * N * 4);
+}
+
+pk_status pk_diag_gemm(int M, int N, int K, const float *A, const float *W, const float *bias, int epi, const float *resid,
+                       float alpha, float *out) {
+    return guard([&] {
+        need(A && W && out && M > 0 && N > 0 && K > 0, "A/W/out/M/N/K");
+        need(K % 32 == 0, "K must be a multiple of 32");
+        diag_product(M, N, K, A, W, bias, epi, resid, alpha, out, /*bf16=*/false);
+    });
+}
+
+pk_status pk_diag_gemm_bf16(int M, int N, int K, const float *A, const float *W, const float *bias, int epi, const float *resid,
+                            float alpha, float *out) {
+    return guard([&] {
+        need(A && W && out && M > 0 && N > 0 && K > 0, "A/W/out/M/N/K");
+        need(K % 64 == 0, "K must be a multiple of 64");
+        diag_product(M, N, K, A, W, bias, epi, resid, alpha, out, /*bf16=*/true);
+    });
+}
+
+/* the same product with the activations handed over as bf16 (GemmArgs::a_bf16: what the producing kernels of the bf16 mode store) */
+pk_status pk_diag_gemm_bf16_a16(int M, int N, int K, const float *A, const float *W, const float *bias, int epi, const float *resid,
+                                float alpha, float *out) {
+    return guard([&] {
+        need(A && W && out && M > 0 && N > 0 && K > 0, "A/W/out/M/N/K");
+        need(K % 64 == 0, "K must be a multiple of 64");
+        diag_product(M, N, K, A, W, bias, epi, resid, alpha, out, /*bf16=*/true, /*a16=*/true);
+    });
+}
+
+/* ... and with the LayerNorm of the input rows folded into the product (the streaming chunks of the tolerance-class mode) */
+pk_status pk_diag_ln_gemm_bf16(int M, int N, int K, const float *A, const float *gamma, const float *beta, float eps, const float *W,
+                               const float *bias, int epi, const float *resid, float alpha, float *out) {
+    return guard([&] {
+        need(A && gamma && beta && W && out && M > 0 && N > 0 && K > 0, "A/gamma/beta/W/out/M/N/K");
+        diag_product(M, N, K, A, W, bias, epi, resid, alpha, out, /*bf16=*/true, /*a16=*/false, gamma, beta, eps);
+    });
+}
+
+pk_status pk_diag_ln2_gemm_bf16(int M, int N, int K, const float *A, const float *pre_gamma, const float *pre_beta, const float *gamma, const float *beta,
+                                float eps, const float *W, const float *bias, float *out, float *pre_out) {
+    return guard([&] {
+        need(M > 0 && N > 0 && K > 0 && A && pre_gamma && pre_beta && gamma && beta && W && out && pre_out, "arguments");
+        need_device();
+        DevBuf a, w, b, gb, o, po, wt_buf;
+        up(a, A, (size_t)M * K * 4);
+        up16(w, W, (size_t)N * K);
+        if (bias) up(b, bias, (size_t)N * 4);
+        up_rows(gb, {pre_gamma, pre_beta, gamma, beta}, K);
+        o.reserve((size_t)M * N * 4);
+        po.reserve((size_t)M * K * 4);
+        GemmArgs g{a.as<float>(), K, w.as<float>(), K, bias ? b.as<float>() : nullptr, o.as<float>(), N, nullptr, 0, 1.0f, M, N, K};
+        g.fast_act = 1;
+        g.pre_g = gb.as<float>(); g.pre_b = gb.as<float>() + K; g.ln_g = gb.as<float>() + 2 * (size_t)K; g.ln_b = gb.as<float>() + 3 * (size_t)K; g.ln_eps = eps;
+        g.pre_out = po.as<float>(); g.pre_ldo = K;
+        g.W_t16 = diag_operand_tiles(wt_buf, w.as<float>(), N, K);
+        if (!gemm_smallm_bf16_pre_applies(g, EPI_SILU)) fail(PK_ERR_UNSUPPORTED, "pk_diag_ln2_gemm_bf16: M <= %d, K = 256 * (1 .. 8)", kSmallMRowsBf16);
+        launch_gemm_bf16(g, EPI_SILU, nullptr);
+        PK_CHECK_LAUNCH();
+        down(out, o, (size_t)M * N * 4);
+        down(pre_out, po, (size_t)M * K * 4);
+    });
+}
+
+pk_status pk_diag_glu_dwconv_bf16(int n_streams, int c, int d, const float *A, const float *gamma, const float *beta, float eps, const float *W,
+                                  const float *bias, const float *cache_in, int has_cache, const float *dw_w, const float *dw_bias,
+                                  const float *bn_mean, const float *bn_rstd, const float *bn_g, const float *bn_b, int fused, float *out,
+                                  float *cache_out) {
+    return guard([&] {
+        need(n_streams > 0 && c > 0 && d > 0 && A && W && cache_in && dw_w && dw_bias && bn_mean && bn_rstd && bn_g && bn_b && out && cache_out, "arguments");
+        need((gamma != nullptr) == (beta != nullptr), "gamma and beta: both or neither");
+        need_device();
+        const int M = n_streams * c, K = d, N = d;
+        DevBuf a, w, b, gb, ci, co, par, glu, o;
+        up(a, A, (size_t)M * K * 4);
+        up16(w, W, (size_t)2 * N * K);
+        if (bias) up(b, bias, (size_t)2 * N * 4);
+        if (gamma) up_rows(gb, {gamma, beta}, K);
+        up(ci, cache_in, (size_t)n_streams * 8 * d * 4);
+        co.reserve((size_t)n_streams * 8 * d * 4);
+        par.reserve((size_t)(9 + 5) * d * 4);                      // the depthwise weights [9][d], then the five per-channel vectors
+        float *pp = par.as<float>();
+        PK_HIP(hipMemcpy(pp, dw_w, (size_t)9 * d * 4, hipMemcpyHostToDevice));
+        const float *five[5] = {dw_bias, bn_mean, bn_rstd, bn_g, bn_b};
+        for (int i = 0; i < 5; ++i) PK_HIP(hipMemcpy(pp + (size_t)(9 + i) * d, five[i], (size_t)d * 4, hipMemcpyHostToDevice));
+        glu.reserve((size_t)M * N * 4);
+        o.reserve((size_t)M * N * 4);
+        GemmArgs g{a.as<float>(), K, w.as<float>(), K, bias ? b.as<float>() : nullptr, glu.as<float>(), N, nullptr, 0, 1.0f, M, N, K};
+        g.fast_act = 1;
+        if (gamma) { g.ln_g = gb.as<float>(); g.ln_b = gb.as<float>() + K; g.ln_eps = eps; }
+        if (!(gamma ? gemm_smallm_bf16_ln_applies(g, EPI_GLU) : gemm_smallm_bf16_applies(g, EPI_GLU)))
+            fail(PK_ERR_UNSUPPORTED, "pk_diag_glu_dwconv_bf16: M <= %d, d = 256 * (1 .. 4)", kSmallMRowsBf16);
+        DevBuf wt_buf;
+        g.W_t16 = diag_operand_tiles(wt_buf, w.as<float>(), 2 * N, K);
+        DwTail tail{ci.as<float>(), co.as<float>(), has_cache, c, pp, pp + 9 * (size_t)d, pp + 10 * (size_t)d, pp + 11 * (size_t)d, pp + 12 * (size_t)d, pp + 13 * (size_t)d};
+        if (fused) {
+            if (!gemm_smallm_bf16_dw_applies(g, EPI_GLU, c, 9)) fail(PK_ERR_UNSUPPORTED, "pk_diag_glu_dwconv_bf16: the fused tail takes c = 1, 2 or 4 frames per stream");
+            g.dw_tail = &tail; g.out = o.as<float>();
+            launch_gemm_bf16(g, EPI_GLU, nullptr);
+        } else {
+            launch_gemm_bf16(g, EPI_GLU, nullptr);
+            launch_stream_dwconv(glu.as<float>(), tail.cache_in, has_cache, n_streams, c, d, 9, tail.w, tail.bias, tail.bn_mean, tail.bn_rstd, tail.bn_g, tail.bn_b,
+                                 o.as<float>(), tail.cache_out, nullptr, 0);
+        }
+        PK_CHECK_LAUNCH();
+        down(out, o, (size_t)M * N * 4);
+        down(cache_out, co, (size_t)n_streams * 8 * d * 4);
+    });
+}
+
+pk_status pk_diag_ffn_bf16_smallm(int M, int d, int f, const float *x, const float *gamma, const float *beta, float eps, const float *W1, const float *b1,
+                                  const float *W2, const float *b2, int act_tiles, float *out) {
+    return guard([&] {
+        need(M > 0 && d > 0 && f > 0 && x && gamma && beta && W1 && b1 && W2 && b2 && out, "arguments");
+        need_device();
+        DevBuf xb, gb, w1b, w2b, b1b, b2b, hb, ob;
+        up(xb, x, (size_t)M * d * 4); up16(w1b, W1, (size_t)f * d); up16(w2b, W2, (size_t)d * f); up(b1b, b1, (size_t)f * 4); up(b2b, b2, (size_t)d * 4);
+        up_rows(gb, {gamma, beta}, d);
+        hb.reserve((size_t)((M + 7) / 8 * 8) * f * 2);
+        up(ob, x, (size_t)M * d * 4);                                   // the residual stream: out = x + 0.5 * ffn(LN(x))
+        GemmArgs g1{xb.as<float>(), d, w1b.as<float>(), d, b1b.as<float>(), hb.as<float>(), f, nullptr, 0, 1.0f, M, f, d};
+        g1.ln_g = gb.as<float>(); g1.ln_b = gb.as<float>() + d; g1.ln_eps = eps; g1.out_bf16 = 1; g1.fast_act = 1; g1.out_t8 = act_tiles ? 1 : 0;
+        GemmArgs g2{hb.as<float>(), f, w2b.as<float>(), f, b2b.as<float>(), ob.as<float>(), d, ob.as<float>(), d, 0.5f, M, d, f};
+        g2.a_bf16 = 1; g2.a_t8 = act_tiles ? 1 : 0;
+        DevBuf wt1, wt2;
+        g1.W_t16 = diag_operand_tiles(wt1, w1b.as<float>(), f, d);
+        g2.W_t16 = diag_operand_tiles(wt2, w2b.as<float>(), d, f);
+        if (!gemm_smallm_bf16_ln_applies(g1, EPI_SILU) || !gemm_smallm_bf16_applies(g2, EPI_RESID))
+            fail(PK_ERR_UNSUPPORTED, "pk_diag_ffn_bf16_smallm: M <= %d (act_tiles: M %% 8 == 0), d = 256 * (1 .. 8), f %% 256 == 0", kSmallMRowsBf16);
+        launch_gemm_bf16(g1, EPI_SILU, nullptr);
+        launch_gemm_bf16(g2, EPI_RESID, nullptr);
+        PK_CHECK_LAUNCH();
+        down(out, ob, (size_t)M * d * 4);
+    });
+}
+
+pk_status pk_diag_pred_cache(int on) { g_diag_pred_cache.store(on ? 1 : 0); return PK_OK; }
+
+pk_status pk_diag_skinny_gemm(const pk_skinny_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const int B = d->B, N = d->N, K = d->K, epi = d->epi;
+        const bool b16 = d->bf16 != 0, cell = epi == SK_CELL, act = epi == SK_ACT;
+        need(epi == SK_BIAS || act || cell, "epi");
+        need(d->X && d->W && d->out && B > 0 && N > 0 && K > 0, "X/W/out/B/N/K");
+        const int F = act && d->F > 1 ? d->F : 1;
+        const int wrows = cell ? 4 * N : N;
+        if (b16) {
+            need(K % 32 == 0, "bf16: K must be a multiple of 32");
+            need(!cell || N % 4 == 0, "bf16 cell: Hp must be a multiple of 4");
+            need(F == 1, "the frame window is an fp32 form");
+        } else {
+            need(K % 16 == 0, "fp32: K must be a multiple of 16");
+            need(epi == SK_BIAS || N % 16 == 0, "fp32 activation / cell: N must be a multiple of 16 (sigma layout of the output)");
+            need(F <= kDecWindowMax, "F");
+            need(F == 1 || (d->need && B <= 16), "the frame window comes with need flags and B <= 16");
+        }
+        need(!d->need || B <= kMaxListRows, "need flags: B <= 2048");
+        need(d->out_rows >= B * F, "out_rows >= B * F");
+        const int ld = epi == SK_BIAS ? d->ldo : N;
+        need(ld >= N, "ldo >= N");
+        if (cell) {
+            need(d->c && d->cn, "cell: c/cn");
+            if (d->W2) need(d->X2 && d->bias2, "cell: X2/bias2 with W2");
+            else {
+                need(d->gi && d->gi_ld >= 4 * N && d->gi_rows > 0, "cell: gi/gi_ld/gi_rows");
+                for (int b = 0; b < B; ++b) {
+                    const int r = d->gi_row ? d->gi_row[b] : b;
+                    need(r >= 0 && r < d->gi_rows, "cell: gi_row out of range");
+                }
+            }
+        }
+        if (act) {
+            need(d->ep && d->t && d->ep_rows > 0, "activation: ep/t/ep_rows");
+            for (int b = 0; b < B; ++b) {
+                const int Tb = d->Tb ? d->Tb[b] : d->T;
+                const int64_t r0 = d->row0 ? (int64_t)d->row0[b] : (int64_t)b * d->T;
+                need(Tb >= 1 && r0 >= 0 && r0 + Tb <= d->ep_rows && d->t[b] >= 0, "activation: frames out of range");
+            }
+        }
+        need_device();
+        const size_t out_el = epi != SK_BIAS && b16 ? 2 : 4;
+        DevBuf dX, dW, dX2, dW2, dbias, dbias2, dgi, dgr, dc, dep, dt, dTb, dr0, dneed, dout, dcn, dpp;
+        auto up_x = [&](DevBuf &buf, const float *x) {
+            if (b16) up16(buf, x, (size_t)B * K);
+            else { const std::vector<float> p = pack_sigma(x, B, K); up(buf, p.data(), p.size() * 4); }
+        };
+        auto up_w = [&](DevBuf &buf, const float *w) {
+            if (b16) { const std::vector<float> p = pack_dec16(w, wrows, K, cell); up16(buf, p.data(), p.size()); }
+            else { const std::vector<float> p = pack_sigma(w, wrows, K); up(buf, p.data(), p.size() * 4); }
+        };
+        SkinnyArgs a{};
+        up_x(dX, d->X); up_w(dW, d->W);
+        a.X = dX.as<float>(); a.W = dW.as<float>(); a.B = B; a.N = wrows; a.K = K;
+        if (d->bias && !cell) { up(dbias, d->bias, (size_t)N * 4); a.bias = dbias.as<float>(); }
+        up(dout, d->out, (size_t)d->out_rows * ld * out_el);
+        a.out = dout.as<float>(); a.ldo = ld;
+        a.F = F;
+        if (cell) {
+            a.Hp = N;
+            up(dc, d->c, (size_t)B * N * 4); a.c = dc.as<float>();
+            up(dcn, d->cn, (size_t)d->out_rows * N * 4); a.cn = dcn.as<float>();
+            if (d->W2) {
+                up_x(dX2, d->X2); up_w(dW2, d->W2); up(dbias2, d->bias2, (size_t)4 * N * 4);
+                a.X2 = dX2.as<float>(); a.W2 = dW2.as<float>(); a.bias2 = dbias2.as<float>();
+                a.gi_ld = 4 * N;
+            } else {
+                up(dgi, d->gi, (size_t)d->gi_rows * d->gi_ld * 4); a.gi = dgi.as<float>(); a.gi_ld = d->gi_ld;
+                if (d->gi_row) { up(dgr, d->gi_row, (size_t)B * 4); a.gi_row = dgr.as<int>(); }
+            }
+        }
+        if (act) {
+            up(dep, d->ep, (size_t)d->ep_rows * N * 4); a.ep = dep.as<float>();
+            up(dt, d->t, (size_t)B * 4); a.t = dt.as<int>(); a.T = d->T;
+            if (d->Tb) { up(dTb, d->Tb, (size_t)B * 4); a.Tb = dTb.as<int>(); }
+            if (d->row0) { up(dr0, d->row0, (size_t)B * 4); a.row0 = dr0.as<int>(); }
+            if (d->pp_out) { up(dpp, d->pp_out, (size_t)d->out_rows * N * 4); a.pp_out = dpp.as<float>(); }
+        }
+        if (d->need) { up(dneed, d->need, (size_t)B * 4); a.need = dneed.as<int>(); }
+        if (b16) launch_skinny_gemm_bf16(a, epi, nullptr);
+        else launch_skinny_gemm(a, epi, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(d->out, dout, (size_t)d->out_rows * ld * out_el);
+        if (cell) down(d->cn, dcn, (size_t)d->out_rows * N * 4);
+        if (act && d->pp_out) down(d->pp_out, dpp, (size_t)d->out_rows * N * 4);
+    });
+}
+
+pk_status pk_diag_layernorm(const float *x, int64_t rows, int d, const float *gamma, const float *beta, float eps, float *y) {
+    return guard([&] {
+        need(x && gamma && beta && y && rows > 0 && d > 0 && d <= 1024, "x/gamma/beta/y/rows/d (d <= 1024)");
+        need_device();
+        DevBuf xb, g, b, yb;
+        up(xb, x, (size_t)rows * d * 4);
+        up(g, gamma, (size_t)d * 4);
+        up(b, beta, (size_t)d * 4);
+        yb.reserve((size_t)rows * d * 4);
+        launch_layernorm(xb.as<float>(), rows, d, g.as<float>(), b.as<float>(), eps, yb.as<float>(), nullptr);
+        PK_CHECK_LAUNCH();
+        down(y, yb, (size_t)rows * d * 4);
+    });
+}
+
+pk_status pk_diag_ln_gemm(int M, int N, int K, const float *A, const float *pre_gamma, const float *pre_beta, const float *gamma, const float *beta, float eps,
+                          const float *W, const float *bias, int epi, int fold, float *out, float *y1) {
+    return guard([&] {
+        need(A && gamma && beta && W && out && M > 0 && N > 0 && K > 0 && K <= 1024, "A/gamma/beta/W/out/M/N/K (K <= 1024)");
+        need((pre_gamma == nullptr) == (pre_beta == nullptr), "pre_gamma and pre_beta: both or neither");
+        need(epi == EPI_NONE || epi == EPI_RELU || epi == EPI_SILU || epi == EPI_GLU, "epi: none / relu / silu / glu");
+        need_device();
+        const int wrows = epi == EPI_GLU ? 2 * N : N;
+        DevBuf a, w, b, gb, o, n, x1;
+        up(a, A, (size_t)M * K * 4);
+        up(w, W, (size_t)wrows * K * 4);
+        if (bias) up(b, bias, (size_t)wrows * 4);
+        up_rows(gb, {gamma, beta, pre_gamma, pre_beta}, K);
+        const float *dg = gb.as<float>(), *db = dg + K, *dpg = dg + 2 * (size_t)K, *dpb = dg + 3 * (size_t)K;
+        o.reserve((size_t)M * N * 4);
+        n.reserve((size_t)M * K * 4);
+        x1.reserve((size_t)M * K * 4);
+        const float *X = a.as<float>();
+        GemmArgs g{n.as<float>(), K, w.as<float>(), K, bias ? b.as<float>() : nullptr, o.as<float>(), N, nullptr, 0, 1.0f, M, N, K};
+        if (fold) {
+            if (pre_gamma) { launch_layernorm_then_stats(X, M, K, dpg, dpb, eps, x1.as<float>(), n.as<float>(), nullptr); X = x1.as<float>(); }
+            else launch_layernorm_stats(X, M, K, eps, n.as<float>(), nullptr);
+            g.A = X; g.ln_g = dg; g.ln_b = db; g.ln_eps = eps; g.ln_stats = n.as<float>();
+            if (!gemm_ln_stats_applies(g, epi)) fail(PK_ERR_UNSUPPORTED, "pk_diag_ln_gemm: fold = 1 needs M > %d, K %% 32 == 0 and a wide (N >= 1024) or glu product", kSmallMRows);
+        } else {
+            if (pre_gamma) launch_layernorm2(X, M, K, dpg, dpb, dg, db, eps, x1.as<float>(), n.as<float>(), nullptr);
+            else launch_layernorm(X, M, K, dg, db, eps, n.as<float>(), nullptr);
+        }
+        launch_gemm(g, epi, nullptr);
+        PK_CHECK_LAUNCH();
+        down(out, o, (size_t)M * N * 4);
+        if (y1 && pre_gamma) down(y1, x1, (size_t)M * K * 4);
+    });
+}
+
+pk_status pk_diag_sum64(const float *x, int rows, int n, float *out) {
+    return guard([&] {
+        need(x && out && rows > 0 && n > 0, "x/out/rows/n");
+        need_device();
+        DevBuf xb, sums;
+        up(xb, x, (size_t)rows * n * 4);
+        sums.reserve((size_t)rows * 4);
+        launch_sum64_rows(xb.as<float>(), rows, n, sums.as<float>(), nullptr);
+        PK_CHECK_LAUNCH();
+        down(out, sums, (size_t)rows * 4);
+    });
+}
+
+// The launchers' own selection functions (kernels/kernels.hpp) for a model and a batch: what tests/test_gpu_conv_variants.py asks before it compares bits.
+pk_status pk_diag_conv_variants(const pk_model *h, int B, int Tm, const int32_t *n_mel_frames, int stream_c, int32_t *out) {
+    return guard([&] {
+        need(h && out && B > 0 && (n_mel_frames || Tm > 0), "model/out/B/Tm");
+        const pk_config &cfg = h->m->cfg;
+        auto sl = [](int n) { return (n - 1) / 2 + 1; };
+        int64_t rows_h2 = 0, rows_t = 0;
+        for (int b = 0; b < B; ++b) {
+            const int tm = n_mel_frames ? n_mel_frames[b] : Tm;
+            need(tm > 0, "every utterance needs at least one mel frame");
+            const int h2 = sl(sl(tm));
+            rows_h2 += h2; rows_t += sl(h2);
+        }
+        const int W2 = sl(sl(cfg.mel_bins)), W3 = sl(W2);
+        const int c1 = sub_conv1_dw1_inst(sub_conv1_dw1_strip_rows(rows_h2), cfg.subsampling_channels, W2), d2 = sub_dw_inst(W3);
+        const int dw = dwconv_inst(rows_t, cfg.conv_kernel_size), sd = stream_dwconv_inst(cfg.conv_kernel_size);
+        const ConvInst *i0 = conv_inst(0, c1), *i1 = conv_inst(1, d2), *i2 = conv_inst(2, dw), *i3 = conv_inst(3, sd);
+        if (!i0 || !i1 || !i2 || !i3) fail(PK_ERR_UNSUPPORTED, "no kernel instantiation for this configuration");
+        const int32_t v[PK_DIAG_CONV_VARIANT_WORDS] = {
+            c1, i0->p0, i0->p1, i0->p2, (int32_t)rows_h2, d2, i1->p1, dw, i2->p0, i2->p1, i2->p2, (int32_t)rows_t,
+            stream_c > 0 ? sd : -1, stream_c > 0 ? i3->p0 : -1, stream_c > 0 ? i3->p1 : -1, stream_c > 0 ? (stream_c <= i3->p1 ? 0 : 1) : -1,
+            stream_c > 0 ? (int32_t)stream_dwconv_tail_fusable(stream_c, cfg.conv_kernel_size) : -1};
+        memcpy(out, v, sizeof v);
+    });
+}
+int pk_diag_conv_instantiations(int32_t *out, int cap_rows) {
+    const int n = (int)(sizeof(kConvInsts) / sizeof(kConvInsts[0]));
+    for (int i = 0; out && i < n && i < cap_rows; ++i) {
+        const ConvInst &c = kConvInsts[i];
+        const int32_t row[5] = {c.launcher, c.inst, c.p0, c.p1, c.p2};
+        memcpy(out + 5 * i, row, sizeof row);
+    }
+    return n;
+}
+
+/* ---- one attention layer alone ------------------------------------------------------------------------------------------------------ */
+// The batch of an attention diagnostic: B utterances of T frames, or (lens) of lens[b] frames each, packed.  -> the frames of the batch; T
+// becomes the longest utterance (the launchers size the launch by it, as run_layers passes it).
+static int64_t att_extents(const int32_t *lens, int B, int &T) {
+    if (!lens) return (int64_t)B * T;
+    int64_t rows = 0;
+    T = 0;
+    for (int b = 0; b < B; ++b) { need(lens[b] > 0, "lens"); T = std::max(T, (int)lens[b]); rows += lens[b]; }
+    return rows;
+}
+// The encoder-frame batch of pk_conformer_blocks_ragged as the attention launchers take it: the engine's RagBatch of lens in attention blocks
+// of block_rows rows, its image on the device, the views Workspace::set_ragged forms.  Uniform batch (no lens): the empty view.
+static SeqRag att_rag(RagBatch &r, DevBuf &img, const int32_t *lens, int B, int block_rows, int pos_T) {
+    SeqRag rag;
+    if (!lens) return rag;
+    r.build_from_frames(lens, B, block_rows);
+    up(img, r.image.data(), r.image.size() * 4);
+    const int32_t *dv = img.as<int32_t>();
+    rag.units = {reinterpret_cast<const RagUnit *>(dv + r.o_u_att), r.n_u_att};
+    rag.T = dv + r.o_T; rag.T_off = dv + r.o_T_off; rag.T_max = r.T_max; rag.pos_T = pos_T;
+    return rag;
+}
+// [rows][cols] with the columns below n_sigma in the sigma layout, the way the producing GEMM writes them (GemmArgs::sigma_cols: 2 d of the
+// 3 d columns of the qkv GEMM, every column of pos_proj)
+static std::vector<float> att_sigma(const float *x, int64_t rows, int cols, int n_sigma) {
+    std::vector<float> y((size_t)rows * cols);
+    for (int64_t i = 0; i < rows; ++i)
+        for (int c = 0; c < cols; ++c) y[(size_t)i * cols + (c < n_sigma ? dec_sigma(c) : c)] = x[(size_t)i * cols + c];
+    return y;
+}
+
+// One relative-position attention layer alone, launched as run_layers launches it: the operands laid out the way their producing GEMMs
+// write them (fp32: q / k thirds and the table in the sigma columns; bf16: everything rounded to bf16, natural columns, c vector on the device),
+// a ragged batch described by the engine's RagBatch, the long-sequence scratch where the score block does not fit LDS.
+pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int pos_T,
+                                   const float *bias_u, const float *bias_v, float *ctx, int *variant) {
+    return guard([&] {
+        need(kernel == 0 || kernel == 1, "kernel must be 0 (fp32) or 1 (bf16)");
+        need(qkv && pos && bias_u && bias_v && ctx && B > 0 && d > 0 && n_heads > 0 && d % n_heads == 0, "qkv/pos/bias_u/bias_v/ctx/B/d/n_heads");
+        const int hd = d / n_heads;
+        const int64_t rows = att_extents(lens, B, T);
+        need(T > 0 && pos_T >= T, "T > 0 and pos_T >= T (ragged: >= max(lens))");
+        if (kernel == 1) need(relpos_attention_bf16_lds_bytes(T, hd) > 0 && relpos_attention_bf16_lds_bytes(T, hd) <= 160 * 1024, "bf16 kernel: hd 64 or 128");
+        else need(relpos_attention_lds_bytes(T, hd) > 0, "fp32 kernel: hd 32, 64, 96 or 128");
+        need_device();
+        const int64_t Ptab = 2 * (int64_t)pos_T - 1, n_ctx = (rows + PK_DIAG_ATTENTION_GUARD_ROWS) * d;
+        RagBatch r;
+        DevBuf rag_img, q, p, bu, bv, out;
+        const SeqRag rag = att_rag(r, rag_img, lens, B, kernel == 1 ? relpos_attention_bf16_block_rows(hd) : 32, pos_T);
+        up(bu, bias_u, (size_t)d * 4);
+        up(bv, bias_v, (size_t)d * 4);
+        int var = lens ? 2 : 0;
+        if (kernel == 1) {
+            DevBuf cvec;
+            up16(q, qkv, (size_t)rows * 3 * d);
+            up16(p, pos, (size_t)Ptab * d);
+            cvec.reserve((size_t)n_heads * Ptab * 4);
+            out.reserve((size_t)n_ctx * 2);
+            PK_HIP(hipMemsetD16(out.p, 0x7fc5, (size_t)n_ctx));
+            launch_pos_cvec(p.p, bu.as<float>(), bv.as<float>(), (int)Ptab, d, n_heads, cvec.as<float>(), nullptr);
+            launch_relpos_attention_bf16(q.p, B, T, d, n_heads, p.p, cvec.as<float>(), bu.as<float>(), out.p, nullptr, pos_T, rag);
+            PK_CHECK_LAUNCH();
+            down16(ctx, out, (size_t)n_ctx);
+            if (variant) *variant = var | 4;
+            return;
+        }
+        const std::vector<float> qs = att_sigma(qkv, rows, 3 * d, 2 * d), ps = att_sigma(pos, Ptab, d, d);
+        up(q, qs.data(), qs.size() * 4);
+        up(p, ps.data(), ps.size() * 4);
+        out.reserve((size_t)n_ctx * 4);
+        PK_HIP(hipMemsetD32(out.p, 0x7fc5a5a5, (size_t)n_ctx));
+        DevBuf scratch;                                              // run_layers: a [32][T] score block past the LDS goes to global scratch
+        if (relpos_attention_lds_bytes(T, hd) > 160 * 1024) {
+            scratch.reserve(lens ? relpos_attention_scratch_bytes_units(r.n_u_att, T, n_heads, hd) : relpos_attention_scratch_bytes(B, T, n_heads, hd));
+            var |= 1;
+        }
+        launch_relpos_attention(q.as<float>(), B, T, d, n_heads, p.as<float>(), bu.as<float>(), bv.as<float>(), out.as<float>(), nullptr, 0.0f,
+                                scratch.as<float>(), 0, pos_T - T, rag);
+        PK_CHECK_LAUNCH();
+        down(ctx, out, (size_t)n_ctx * 4);
+        if (variant) *variant = var;
+    });
+}
+
+// One limited-context attention layer alone on the band kernel (kernels/attention_local.hip), launched as run_layers launches it in local mode.
+pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
+                                         const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant) {
+    return guard([&] {
+        need(qkv && pos && bias_u && bias_v && ctx && B > 0 && d > 0 && n_heads > 0 && d % n_heads == 0, "qkv/pos/bias_u/bias_v/ctx/B/d/n_heads");
+        need(out_mode == 0 || out_mode == 1, "out_mode must be 0 (fp32) or 1 (bf16)");
+        need((left == -1 && right == -1) || (left >= 0 && right >= 0), "left / right: both >= 0");
+        need(left >= 0, "pk_diag_relpos_local_attention runs the band kernel: left, right >= 0");
+        const int hd = d / n_heads, span = relpos_local_attention_max_span(hd);
+        if (span < 0) fail(PK_ERR_UNSUPPORTED, "band kernel: hd 32, 64, 96 or 128 (got %d)", hd);
+        if ((int64_t)left + right > span)
+            fail(PK_ERR_UNSUPPORTED, "attention context (%d, %d): left + right is at most %d at head size %d", left, right, span, hd);
+        const int64_t rows = att_extents(lens, B, T);
+        need(T > 0, "T > 0 (ragged: lens > 0)");
+        need_device();
+        const int64_t Ptab = (int64_t)left + right + 1, n_ctx = (rows + PK_DIAG_ATTENTION_GUARD_ROWS) * d;
+        RagBatch r;
+        DevBuf rag_img, q, p, bu, bv, out;
+        const SeqRag rag = att_rag(r, rag_img, lens, B, 32, /*pos_T=*/0);
+        const std::vector<float> qs = att_sigma(qkv, rows, 3 * d, 2 * d), ps = att_sigma(pos, Ptab, d, d);
+        up(q, qs.data(), qs.size() * 4);
+        up(p, ps.data(), ps.size() * 4);
+        up(bu, bias_u, (size_t)d * 4);
+        up(bv, bias_v, (size_t)d * 4);
+        out.reserve((size_t)n_ctx * (out_mode == 1 ? 2 : 4));
+        if (out_mode == 1) PK_HIP(hipMemsetD16(out.p, 0x7fc5, (size_t)n_ctx));
+        else PK_HIP(hipMemsetD32(out.p, 0x7fc5a5a5, (size_t)n_ctx));
+        launch_relpos_local_attention(q.as<float>(), B, T, d, n_heads, p.as<float>(), bu.as<float>(), bv.as<float>(), out.as<float>(), nullptr,
+                                      out_mode, left, right, rag);
+        PK_CHECK_LAUNCH();
+        if (out_mode == 1) down16(ctx, out, (size_t)n_ctx);
+        else down(ctx, out, (size_t)n_ctx * 4);
+        if (variant) *variant = 8 | (lens ? 2 : 0) | (out_mode == 1 ? 16 : 0);
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,426 @@
+// parakeet.cpp_amd/csrc/capi_stages.cpp -- the stage entry points of the C boundary on caller buffers: mel, subsample, encode, conformer blocks,
+// CTC / TDT decode and scoring (uniform and ragged forms), and the CTC prefix beam search.
+#include <algorithm>
+#include <cstring>
+
+#include "capi_util.hpp"
+
+using namespace pk;
+
+static void size_ws_for_T(Model &m, int B, int T) {
+    // a mel length that subsamples to exactly T frames: Tm = 8(T-1)+1
+    m.ws.size_for(m.cfg, B, 0, 8 * (T - 1) + 1);
+    if (m.ws.T != T) fail(PK_ERR_INVALID, "internal: workspace T %d != %d", m.ws.T, T);
+}
+
+// workspace of the host-buffer decode entry points for B utterances of n_frames[b] encoder frames (packed); returns the longest
+static int size_ws_for_frames(Model &m, const int32_t *n_frames, int B) {
+    int t_max = 0;
+    for (int i = 0; i < B; ++i) t_max = std::max(t_max, (int)n_frames[i]);
+    RagBatch r;
+    r.build_from_frames(n_frames, B, att_block_rows_of(m, t_max));
+    m.ws.size_ragged(m.cfg, B, r.sum_T, t_max, false, /*level=*/2);
+    m.ws.set_ragged(r, m.stream);
+    return t_max;
+}
+
+// The uniform and the ragged form of a stage share one body: n_frames == nullptr is B utterances of T frames each, otherwise utterance b has
+// n_frames[b] frames, packed.  Sizes the workspace; -> the longest utterance, and the frames of the batch in `rows`.
+static int size_ws(Model &m, const int32_t *n_frames, int B, int T, size_t &rows) {
+    if (n_frames) T = size_ws_for_frames(m, n_frames, B);
+    else size_ws_for_T(m, B, T);
+    rows = n_frames ? (size_t)m.ws.rag.sum_T : (size_t)B * T;
+    return T;
+}
+
+static void conformer_blocks(Model &m, const float *x_in, const int32_t *n_frames, int B, int T, int first_layer, int n_layers, float *x_out) {
+    m.require_gpu();
+    need(first_layer >= 0 && n_layers >= 0 && first_layer + n_layers <= m.cfg.num_layers, "layer range");
+    size_t rows;
+    size_ws(m, n_frames, B, T, rows);
+    const size_t n = rows * m.cfg.hidden_size;
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, x_in, n * 4, hipMemcpyHostToDevice, m.stream));
+    if (n_layers > 0) m.run_layers(m.ws, B, first_layer, first_layer + n_layers, 0, m.stream);
+    PK_CHECK_LAUNCH();
+    PK_HIP(hipMemcpyAsync(x_out, m.ws.x.p, n * 4, hipMemcpyDeviceToHost, m.stream));
+    PK_HIP(hipStreamSynchronize(m.stream));
+}
+
+// The token arrays of the decode that was just queued, [B][pitch] each (start / end / conf optional), then one more array the decoder has
+// (CTC: the log-probs, TDT: the step counts; optional); waits for the stream and zeroes the entries past lens[b].
+static void copy_out_tokens(Model &m, int B, int pitch, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf, void *extra,
+                            const void *d_extra, size_t extra_bytes) {
+    const size_t tok = (size_t)B * pitch;
+    PK_HIP(hipMemcpyAsync(ids, m.ws.ids.p, tok * 4, hipMemcpyDeviceToHost, m.stream));
+    PK_HIP(hipMemcpyAsync(lens, m.ws.lens.p, (size_t)B * 4, hipMemcpyDeviceToHost, m.stream));
+    if (start) PK_HIP(hipMemcpyAsync(start, m.ws.start.p, tok * 4, hipMemcpyDeviceToHost, m.stream));
+    if (end) PK_HIP(hipMemcpyAsync(end, m.ws.end.p, tok * 4, hipMemcpyDeviceToHost, m.stream));
+    if (conf) PK_HIP(hipMemcpyAsync(conf, m.ws.conf.p, tok * 4, hipMemcpyDeviceToHost, m.stream));
+    if (extra) PK_HIP(hipMemcpyAsync(extra, d_extra, extra_bytes, hipMemcpyDeviceToHost, m.stream));
+    PK_HIP(hipStreamSynchronize(m.stream));
+    zero_tail(ids, lens, B, pitch); zero_tail(start, lens, B, pitch); zero_tail(end, lens, B, pitch); zero_tail(conf, lens, B, pitch);
+}
+
+static void ctc_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end,
+                       float *conf, float *logp) {
+    m.require_gpu();
+    size_t rows;
+    T = size_ws(m, n_frames, B, T, rows);                          // the token arrays are [B][T], T = the longest utterance
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, logp != nullptr, m.stream);
+    PK_CHECK_LAUNCH();
+    copy_out_tokens(m, B, T, ids, lens, start, end, conf, logp, m.ws.ctc_lp.p, rows * m.cfg.ctc_vocab_size * 4);
+}
+
+// -> true when at least one utterance hit the safety cap on joint evaluations (lens[b] = -1)
+static bool tdt_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start,
+                       int32_t *end, float *conf, int32_t *steps) {
+    m.require_gpu();
+    size_t rows;
+    T = size_ws(m, n_frames, B, T, rows);
+    need(max_tokens <= m.ws.max_tokens,
+         n_frames ? "max_tokens exceeds (longest utterance) * max_symbols_per_step" : "max_tokens exceeds T * max_symbols_per_step");
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_tdt(m.ws, m.ws.x.as<float>(), B, T, max_tokens, m.stream);
+    PK_CHECK_LAUNCH();
+    copy_out_tokens(m, B, max_tokens, ids, lens, start, end, conf, steps, m.ws.ints.as<int>() + 4 * B, (size_t)B * 4);
+    bool cap_hit = false;
+    for (int b = 0; b < B; ++b) cap_hit = cap_hit || lens[b] < 0;
+    return cap_hit;
+}
+// the status of a TDT decode entry point: a decode that ran but hit the cap is PK_ERR_DECODE_CAP (the arrays are filled all the same)
+static pk_status tdt_status(pk_status st, bool cap_hit) {
+    if (st != PK_OK || !cap_hit) return st;
+    set_last_error("TDT decode hit the safety cap on joint evaluations for at least one utterance (lens = -1)");
+    return PK_ERR_DECODE_CAP;
+}
+
+pk_beam_options pk::beam_options_of(const pk_beam_options *opt) {
+    pk_beam_options o;
+    pk_beam_options_default(&o);
+    if (opt) o = *opt;
+    return o;
+}
+// what the model entry points refuse (include/parakeet_amd.h); -> the CTC vocabulary and its blank
+void pk::beam_model_checks(Model &m, const pk_beam_options &o, int &V, int &blank) {
+    m.require_gpu();
+    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC beam search needs one");
+    if (m.boost_on) fail(PK_ERR_UNSUPPORTED, "CTC beam search has no phrase-boosted variant: clear the boost phrases of the model first");
+    V = m.cfg.ctc_vocab_size;
+    blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;           // (as Model::run_ctc)
+    beam_check_options(o, V, blank);
+}
+
+static void ctc_beam_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
+                            float *score, int32_t *start, int32_t *end, float *conf) {
+    const pk_beam_options o = beam_options_of(opt);
+    int V = 0, blank = 0;
+    beam_model_checks(m, o, V, blank);
+    size_t rows;
+    T = size_ws(m, n_frames, B, T, rows);                          // the token arrays are [B][N][T], T = the longest utterance
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+    run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, n_frames ? m.ws.rv.seq : SeqRag(), V, blank, o, m.stream);
+    PK_CHECK_LAUNCH();
+    const bool ts = o.timestamps != 0;
+    beam_copy_out(m.beam, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, m.stream);
+}
+
+extern "C" {
+
+pk_status pk_mel(pk_model *h, const float *pcm, int n_clips, int64_t n_samples, float *feats, float *logmel) {
+    return guard([&] {
+        need(h && pcm && feats && n_clips > 0, "model/pcm/feats/n_clips");
+        need(n_samples > 256, "n_samples must exceed n_fft/2 (reflect padding)");
+        Model &m = *h->m;
+        m.require_gpu();
+        const int nf = pk_mel_num_frames(n_samples), F = m.cfg.mel_bins;
+        const size_t n_in = (size_t)n_clips * n_samples, n_lm = (size_t)n_clips * F * nf;
+        const int pitch = mel_logmel_pitch(nf);                      // the device's log-mel rows are padded to 16 frames (kernels.hpp)
+        m.io_in.reserve(n_in * 4);
+        m.io_tmp.reserve((size_t)n_clips * F * pitch * 4);
+        m.io_out.reserve(n_lm * 4);
+        PK_HIP(hipMemcpyAsync(m.io_in.p, pcm, n_in * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_mel(m.io_in.as<float>(), n_clips, n_samples, m.io_tmp.as<float>(), m.io_out.as<float>(), m.stream);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(feats, m.io_out.p, n_lm * 4, hipMemcpyDeviceToHost, m.stream));
+        if (logmel) PK_HIP(hipMemcpy2DAsync(logmel, (size_t)nf * 4, m.io_tmp.p, (size_t)pitch * 4, (size_t)nf * 4, (size_t)n_clips * F, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+
+pk_status pk_subsample(pk_model *h, const float *feats, int B, int Tm, float *out) {
+    return guard([&] {
+        need(h && feats && out && B > 0 && Tm > 0, "model/feats/out/B/Tm");
+        Model &m = *h->m;
+        m.require_gpu();
+        m.ws.size_for(m.cfg, B, 0, Tm);
+        const size_t nin = (size_t)B * Tm * m.cfg.mel_bins, nout = (size_t)B * m.ws.T * m.cfg.hidden_size;
+        PK_HIP(hipMemcpyAsync(m.ws.feats.p, feats, nin * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_subsample(m.ws, m.ws.feats.as<float>(), B, Tm, m.ws.x.as<float>(), m.stream);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(out, m.ws.x.p, nout * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+pk_status pk_encode(pk_model *h, const float *feats, int B, int Tm, int stop_layer, int stop_stage, float *enc) {
+    return guard([&] {
+        need(h && feats && enc && B > 0 && Tm > 0, "model/feats/enc/B/Tm");
+        need(stop_stage >= 0 && stop_stage <= 4, "stop_stage");
+        Model &m = *h->m;
+        m.require_gpu();
+        m.ws.size_for(m.cfg, B, 0, Tm);
+        const size_t nin = (size_t)B * Tm * m.cfg.mel_bins, nout = (size_t)B * m.ws.T * m.cfg.hidden_size;
+        PK_HIP(hipMemcpyAsync(m.ws.feats.p, feats, nin * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_encoder(m.ws, m.ws.feats.as<float>(), B, Tm, stop_layer, stop_stage, m.stream);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(enc, m.ws.x.p, nout * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+pk_status pk_conformer_blocks(pk_model *h, const float *x_in, int B, int T, int first_layer, int n_layers, float *x_out) {
+    return guard([&] {
+        need(h && x_in && x_out && B > 0 && T > 0, "model/x_in/x_out/B/T");
+        conformer_blocks(*h->m, x_in, nullptr, B, T, first_layer, n_layers, x_out);
+    });
+}
+
+pk_status pk_ctc_decode(pk_model *h, const float *enc, int B, int T, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end,
+                        float *conf, float *logp) {
+    return guard([&] {
+        need(h && enc && ids && lens && B > 0 && T > 0, "model/enc/ids/lens/B/T");
+        ctc_decode(*h->m, enc, nullptr, B, T, ids, lens, start, end, conf, logp);
+    });
+}
+
+pk_status pk_tdt_decode(pk_model *h, const float *enc, int B, int T, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start,
+                        int32_t *end, float *conf, int32_t *steps) {
+    bool cap_hit = false;
+    const pk_status st = guard([&] {
+        need(h && enc && ids && lens && B > 0 && T > 0 && max_tokens > 0, "model/enc/ids/lens/B/T/max_tokens");
+        cap_hit = tdt_decode(*h->m, enc, nullptr, B, T, max_tokens, ids, lens, start, end, conf, steps);
+    });
+    return tdt_status(st, cap_hit);
+}
+
+/* ---- ragged (mixed-length) forms of the stage entry points: every tensor PACKED along the time axis ---------------------------------- */
+pk_status pk_mel_ragged(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, float *feats, float *logmel) {
+    return guard([&] {
+        need(h && pcm && offsets && feats && n_clips > 0, "model/pcm/offsets/feats/n_clips");
+        Model &m = *h->m;
+        m.require_gpu();
+        std::vector<int64_t> lens(n_clips);
+        int64_t longest = 0;
+        for (int i = 0; i < n_clips; ++i) { lens[i] = offsets[i + 1] - offsets[i]; longest = std::max(longest, lens[i]); }
+        RagBatch r;
+        r.build_from_samples(lens.data(), n_clips, 32);
+        m.ws.size_ragged(m.cfg, n_clips, r.n_samples, longest, /*own_pcm=*/true);
+        m.ws.set_ragged(r, m.stream);
+        const size_t n_lm = (size_t)r.sum_Tm * m.cfg.mel_bins;
+        for (int i = 0; i < n_clips; ++i)        // (the clips need not be contiguous in the caller's buffer)
+            PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[i], (size_t)lens[i] * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), n_clips, m.stream);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(feats, m.ws.feats.p, n_lm * 4, hipMemcpyDeviceToHost, m.stream));
+        if (logmel) {                                               // per clip: [mel_bins][pitch] on the device -> [mel_bins][Tm] for the caller
+            const int F = m.cfg.mel_bins;
+            size_t dev_off = 0, host_off = 0;
+            for (int i = 0; i < n_clips; ++i) {
+                const int tm = r.Tm[i], pitch = mel_logmel_pitch(tm);
+                PK_HIP(hipMemcpy2DAsync(logmel + host_off, (size_t)tm * 4, m.ws.logmel.as<float>() + dev_off, (size_t)pitch * 4, (size_t)tm * 4, (size_t)F,
+                                        hipMemcpyDeviceToHost, m.stream));
+                dev_off += (size_t)F * pitch; host_off += (size_t)F * tm;
+            }
+        }
+        PK_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+pk_status pk_encode_ragged(pk_model *h, const float *feats, const int32_t *n_mel_frames, int B, int stop_layer, int stop_stage, float *enc) {
+    return guard([&] {
+        need(h && feats && n_mel_frames && enc && B > 0, "model/feats/n_mel_frames/enc/B");
+        need(stop_stage >= 0 && stop_stage <= 4, "stop_stage");
+        Model &m = *h->m;
+        m.require_gpu();
+        int tm_max = 0;
+        for (int i = 0; i < B; ++i) tm_max = std::max(tm_max, (int)n_mel_frames[i]);
+        RagBatch r;
+        r.build_from_mel(n_mel_frames, B, att_block_rows_of(m, pk_encoder_num_frames(tm_max)));
+        m.ws.size_ragged(m.cfg, B, r.sum_Tm, tm_max, false, /*level=*/1);
+        m.ws.set_ragged(r, m.stream);
+        PK_HIP(hipMemcpyAsync(m.ws.feats.p, feats, (size_t)r.sum_Tm * m.cfg.mel_bins * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_encoder(m.ws, m.ws.feats.as<float>(), B, 0, stop_layer, stop_stage, m.stream);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(enc, m.ws.x.p, (size_t)r.sum_T * m.cfg.hidden_size * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+pk_status pk_conformer_blocks_ragged(pk_model *h, const float *x_in, const int32_t *n_frames, int B, int first_layer, int n_layers, float *x_out) {
+    return guard([&] {
+        need(h && x_in && x_out && n_frames && B > 0, "model/x_in/x_out/n_frames/B");
+        conformer_blocks(*h->m, x_in, n_frames, B, 0, first_layer, n_layers, x_out);
+    });
+}
+
+pk_status pk_ctc_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, int32_t *ids, int32_t *lens, int32_t *start,
+                               int32_t *end, float *conf, float *logp) {
+    return guard([&] {
+        need(h && enc && n_frames && ids && lens && B > 0, "model/enc/n_frames/ids/lens/B");
+        ctc_decode(*h->m, enc, n_frames, B, 0, ids, lens, start, end, conf, logp);
+    });
+}
+
+pk_status pk_tdt_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, int max_tokens, int32_t *ids, int32_t *lens,
+                               int32_t *start, int32_t *end, float *conf, int32_t *steps) {
+    bool cap_hit = false;
+    const pk_status st = guard([&] {
+        need(h && enc && n_frames && ids && lens && B > 0 && max_tokens > 0, "model/enc/n_frames/ids/lens/B/max_tokens");
+        cap_hit = tdt_decode(*h->m, enc, n_frames, B, 0, max_tokens, ids, lens, start, end, conf, steps);
+    });
+    return tdt_status(st, cap_hit);
+}
+
+/* tdt_greedy_decode's loop (src/tdt.cpp:62-106) along a GIVEN decision path, recording the joint's outputs (TDTJoint::forward, :15-24) */
+pk_status pk_tdt_score(pk_model *h, const float *enc, int T, const int32_t *labels, const int32_t *dur_idx, int n_steps, float *label_logp,
+                       float *dur_logp, int *n_done) {
+    return guard([&] {
+        need(h && enc && labels && dur_idx && T > 0 && n_steps > 0 && (label_logp || dur_logp), "model/enc/labels/dur_idx/T/n_steps/outputs");
+        Model &m = *h->m;
+        m.require_gpu();
+        need(m.cfg.vocab_size > 0 && !m.cfg.rnnt_head && m.cfg.num_durations > 0, "pk_tdt_score needs a TDT joint (label + duration heads)");
+        const int V = m.cfg.vocab_size, D = m.cfg.num_durations;
+        for (int k = 0; k < n_steps; ++k)
+            need(labels[k] >= 0 && labels[k] < V && dur_idx[k] >= 0 && dur_idx[k] < D, "labels[k] / dur_idx[k] out of range");
+        size_ws_for_T(m, 1, T);
+        Workspace &w = m.ws;
+        const size_t nl = (size_t)n_steps * V, nd = (size_t)n_steps * D;
+        m.io_in.reserve((size_t)2 * n_steps * sizeof(int));
+        m.io_out.reserve((nl + nd) * 4);
+        int *d_lab = m.io_in.as<int>(), *d_dur = d_lab + n_steps;
+        float *d_sl = m.io_out.as<float>(), *d_sd = d_sl + nl;
+        PK_HIP(hipMemcpyAsync(d_lab, labels, (size_t)n_steps * 4, hipMemcpyHostToDevice, m.stream));
+        PK_HIP(hipMemcpyAsync(d_dur, dur_idx, (size_t)n_steps * 4, hipMemcpyHostToDevice, m.stream));
+        PK_HIP(hipMemsetAsync(d_sl, 0, (nl + nd) * 4, m.stream));
+        PK_HIP(hipMemcpyAsync(w.x.p, enc, (size_t)T * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        struct Scope { Workspace &w; ~Scope() { w.force_label = w.force_dur = nullptr; w.score_lab = w.score_dur = nullptr; w.n_force = 0; } } scope{w};
+        w.force_label = d_lab; w.force_dur = d_dur; w.n_force = n_steps; w.score_lab = d_sl; w.score_dur = d_sd;
+        m.run_tdt(w, w.x.as<float>(), 1, T, w.max_tokens, m.stream);
+        PK_CHECK_LAUNCH();
+        int steps = 0;
+        PK_HIP(hipMemcpyAsync(&steps, w.ints.as<int>() + 4, sizeof(int), hipMemcpyDeviceToHost, m.stream));      // st.steps[0] (B = 1)
+        if (label_logp) PK_HIP(hipMemcpyAsync(label_logp, d_sl, nl * 4, hipMemcpyDeviceToHost, m.stream));
+        if (dur_logp) PK_HIP(hipMemcpyAsync(dur_logp, d_sd, nd * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
+        if (n_done) *n_done = steps;
+    });
+}
+
+pk_status pk_decode_margins(pk_model *h, float *min_margin, int B) {
+    return guard([&] {
+        need(h && min_margin && B > 0, "model/min_margin/B");
+        Model &m = *h->m;
+        m.require_gpu();
+        need(B <= m.ws.B && m.ws.margin.p, "B exceeds the last pk_tdt_decode call");
+        need(!m.boost_on, "margins are reported for unboosted decodes");
+        PK_HIP(hipMemcpy(min_margin, m.ws.margin.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+/* ---- CTC prefix beam search (kernels/ctc_beam.hip; reference roadmap README.md:494) ------------------------------------------------ */
+void pk_beam_options_default(pk_beam_options *out) {
+    if (!out) return;
+    out->beam_width = 8; out->token_prune = 16; out->n_best = 1; out->timestamps = 0;
+}
+
+pk_status pk_ctc_beam_search(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
+                             int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf) {
+    return guard([&] {
+        need(logp && ids && lens && B > 0, "logp/ids/lens/B");
+        need(n_frames || T > 0, "T");
+        const pk_beam_options o = beam_options_of(opt);
+        beam_check_options(o, V, blank);
+        need_device();
+        int64_t rows = (int64_t)B * T;
+        std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
+        if (n_frames) {
+            tab.resize(2 * (size_t)B + 1);
+            rows = 0; T = 0;
+            for (int b = 0; b < B; ++b) {
+                need(n_frames[b] > 0, "n_frames[b] must be positive");
+                tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
+                rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
+                need(rows < ((int64_t)1 << 31), "too many frames");
+            }
+            tab[2 * (size_t)B] = (int32_t)rows;
+        }
+        BeamWs ws;
+        DevBuf d_lp, d_tab;
+        d_lp.reserve((size_t)rows * V * 4);
+        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
+        SeqRag rag;
+        if (n_frames) {
+            d_tab.reserve(tab.size() * 4);
+            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
+        }
+        run_ctc_beam(ws, d_lp.as<float>(), B, T, rows, rag, V, blank, o, nullptr);
+        PK_CHECK_LAUNCH();
+        const bool ts = o.timestamps != 0;
+        beam_copy_out(ws, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, nullptr);
+    });
+}
+
+pk_status pk_ctc_beam_decode(pk_model *h, const float *enc, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
+                             float *score, int32_t *start, int32_t *end, float *conf) {
+    return guard([&] {
+        need(h && enc && ids && lens && B > 0 && T > 0, "model/enc/ids/lens/B/T");
+        ctc_beam_decode(*h->m, enc, nullptr, B, T, opt, ids, lens, score, start, end, conf);
+    });
+}
+
+pk_status pk_ctc_beam_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const pk_beam_options *opt, int32_t *ids,
+                                    int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf) {
+    return guard([&] {
+        need(h && enc && n_frames && ids && lens && B > 0, "model/enc/n_frames/ids/lens/B");
+        ctc_beam_decode(*h->m, enc, n_frames, B, 0, opt, ids, lens, score, start, end, conf);
+    });
+}
+
+pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
+                                   float ms[2]) {
+    return guard([&] {
+        need(h && enc && ms && B > 0 && reps > 0 && (n_frames || T > 0), "model/enc/ms/B/T/reps");
+        Model &m = *h->m;
+        const pk_beam_options o = beam_options_of(opt);
+        int V = 0, blank = 0;
+        beam_model_checks(m, o, V, blank);
+        size_t rows;
+        T = size_ws(m, n_frames, B, T, rows);
+        const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        std::vector<float> greedy, beam;
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+            m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, rag, V, blank, o, m.stream);
+            PK_HIP(hipEventRecord(ev.e[2], m.stream));
+            PK_HIP(hipStreamSynchronize(m.stream));
+            PK_CHECK_LAUNCH();
+            float a = 0, b = 0;
+            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+            if (r > 0) { greedy.push_back(a); beam.push_back(b); }
+        }
+        std::sort(greedy.begin(), greedy.end()); std::sort(beam.begin(), beam.end());
+        ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
+    });
+}
+
+}  // extern "C"

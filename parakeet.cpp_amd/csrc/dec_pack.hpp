@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/dec_pack.hpp -- host-side layouts of the decode-loop weights (kernels/decode_gemv.hip, kernels/decode_gemv_bf16.hip).
-// The loader (engine.cpp upload_weights) and the kernel-level diagnostic (capi.cpp pk_diag_skinny_gemm) pack through these functions.
+// The loader (engine.cpp upload_weights) and the kernel-level diagnostic (capi_diag.cpp pk_diag_skinny_gemm) pack through these functions.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -507,7 +507,7 @@ void Workspace::reserve_decode(const pk_config &c) {
     margin.reserve((size_t)B * f);
 }
 
-// decode-only workspace (no encoder buffers): the lock-step TDT state of a GROUP of pipelined batches (capi.cpp)
+// decode-only workspace (no encoder buffers): the lock-step TDT state of a GROUP of pipelined batches (capi_batch.cpp)
 void Workspace::size_decode(const pk_config &c, int B_, int T_, size_t rows_cap) {
     B = B_; T = T_run = T_;
     ragged = false;
@@ -1134,7 +1134,7 @@ void Model::run_tdt(Workspace &w, const float *d_enc, int B, int T, int max_toke
 }
 
 // The greedy loop over w.ep = enc_proj of B utterances of T frames (rows b*T + t).  B may span several batches of the pipelined path
-// (capi.cpp: decode groups): the utterances are independent, a lock-step batch of 2B costs the same number of launches as one of B.
+// (capi_batch.cpp: decode groups): the utterances are independent, a lock-step batch of 2B costs the same number of launches as one of B.
 void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t s, bool keep_state) {
     w.poll_hit = false;
     const int Hp = cfg.pred_hidden, J = cfg.joint_hidden, V = cfg.vocab_size, D = cfg.rnnt_head ? 0 : cfg.num_durations;

@@ -119,7 +119,7 @@ struct Workspace {
     Workspace(const Workspace &) = delete;
     Workspace &operator=(const Workspace &) = delete;
     // the per-utterance token arrays are pitched B x T x max_symbols: the only buffers that grow with (clips x longest clip); released when a
-    // pipeline is re-sized for much shorter clips (capi.cpp model_pipeline), re-reserved by the next size_* call
+    // pipeline is re-sized for much shorter clips (capi_batch.cpp model_pipeline), re-reserved by the next size_* call
     void release_tokens() { ids.release(); start.release(); end.release(); conf.release(); }
     size_t token_bytes() const { return ids.cap + start.cap + end.cap + conf.cap; }
     void size_for(const pk_config &cfg, int B, int64_t n_samples, int Tm);
@@ -237,7 +237,7 @@ class Model {
     BeamWs beam;        // scratch and results of the CTC prefix beam search entry points (ctc_beam.hpp)
     int decode_loop = PK_DECODE_LOOP_PHASES;   // pk_model_set_decode_loop: how run_tdt_loop issues the greedy loop
     int *h_done = nullptr;   // pinned host word for the decode loop's "all utterances finished" poll
-    // the two-stream batch pipeline of the one-call API (struct pk_batch, capi.cpp), owned by the model; freed first in ~Model
+    // the two-stream batch pipeline of the one-call API (struct pk_batch, capi_batch.cpp), owned by the model; freed first in ~Model
     void *pipe = nullptr;
     void (*pipe_free)(void *) = nullptr;
 

@@ -3,7 +3,7 @@
 // themselves (README "Speaker Diarization": preprocess_audio(audio.samples, {.normalize = false})).  Same kernels, same bits.
 #include <cstring>
 
-#include "engine.hpp"
+#include "capi_util.hpp"
 
 namespace pk {
 
@@ -69,34 +69,20 @@ struct pk_frontend {
 extern "C" {
 
 pk_status pk_frontend_create(int n_mels, int normalize, int stft_window_centered, int device, pk_frontend **out) {
-    try {
+    return guard([&] {
         if (!out) fail(PK_ERR_INVALID, "invalid argument: out");
         auto h = std::make_unique<pk_frontend>();
         h->f = std::make_unique<MelFrontend>(n_mels, normalize != 0, stft_window_centered != 0, device);
         *out = h.release();
-        return PK_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return PK_ERR_INVALID;
-    }
+    });
 }
 
 pk_status pk_frontend_features(pk_frontend *f, const float *pcm, int64_t n_samples, float *feats, int *n_frames) {
-    try {
+    return guard([&] {
         if (!f || !pcm || !feats || n_samples <= 256) fail(PK_ERR_INVALID, "invalid argument: frontend/pcm/feats/n_samples (> 256)");
         const int nf = f->f->features(pcm, n_samples, feats);
         if (n_frames) *n_frames = nf;
-        return PK_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return PK_ERR_INVALID;
-    }
+    });
 }
 
 void pk_frontend_free(pk_frontend *f) { delete f; }

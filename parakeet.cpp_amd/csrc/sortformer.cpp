@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "capi_util.hpp"
 #include "stream.hpp"
 #include "transformer.hpp"
 
@@ -144,19 +145,6 @@ struct pk_sortformer {
     std::unique_ptr<Sortformer> s;
 };
 
-static pk_status sf_guard(const std::function<void()> &fn) {
-    try {
-        fn();
-        return PK_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return PK_ERR_INVALID;
-    }
-}
-
 extern "C" {
 
 void pk_sortformer_config_preset(pk_sortformer_config *out) {       // make_sortformer_117m_config (sortformer.hpp:43-76)
@@ -176,7 +164,7 @@ void pk_sortformer_config_preset(pk_sortformer_config *out) {       // make_sort
 }
 
 pk_status pk_sortformer_load(const char *safetensors_path, const pk_sortformer_config *cfg, int device, pk_sortformer **out) {
-    return sf_guard([&] {
+    return guard([&] {
         if (!safetensors_path || !cfg || !out) fail(PK_ERR_INVALID, "invalid argument: path/cfg/out");
         auto h = std::make_unique<pk_sortformer>();
         h->s = std::make_unique<Sortformer>(safetensors_path, *cfg, device);
@@ -187,7 +175,7 @@ pk_status pk_sortformer_load(const char *safetensors_path, const pk_sortformer_c
 void pk_sortformer_free(pk_sortformer *s) { delete s; }
 
 pk_status pk_sortformer_forward(pk_sortformer *s, const float *feats, int B, int Tm, float *probs, int *T_out) {
-    return sf_guard([&] {
+    return guard([&] {
         if (!s || !feats || !probs || B <= 0 || Tm <= 0) fail(PK_ERR_INVALID, "invalid argument: sortformer/feats/probs/B/Tm");
         const int T = s->s->forward_feats(feats, B, Tm, probs);
         if (T_out) *T_out = T;
@@ -195,7 +183,7 @@ pk_status pk_sortformer_forward(pk_sortformer *s, const float *feats, int B, int
 }
 
 pk_status pk_sortformer_forward_pcm(pk_sortformer *s, const float *pcm, int n_clips, int64_t n_samples, float *probs, int *T_out) {
-    return sf_guard([&] {
+    return guard([&] {
         if (!s || !pcm || !probs || n_clips <= 0 || n_samples <= 256) fail(PK_ERR_INVALID, "invalid argument: sortformer/pcm/probs/n_clips/n_samples");
         const int T = s->s->forward_pcm(pcm, n_clips, n_samples, probs);
         if (T_out) *T_out = T;
@@ -203,7 +191,7 @@ pk_status pk_sortformer_forward_pcm(pk_sortformer *s, const float *pcm, int n_cl
 }
 
 pk_status pk_sortformer_diarize_chunk(pk_sortformer *s, const float *feats, int n_frames, float *probs, int cap_frames, int *T_out) {
-    return sf_guard([&] {
+    return guard([&] {
         if (!s || !feats || !probs || n_frames <= 0 || cap_frames <= 0) fail(PK_ERR_INVALID, "invalid argument: sortformer/feats/probs/n_frames/cap_frames");
         const int c = s->s->forward_chunk(feats, n_frames, probs, cap_frames);
         if (T_out) *T_out = c;
@@ -211,7 +199,7 @@ pk_status pk_sortformer_diarize_chunk(pk_sortformer *s, const float *feats, int 
 }
 
 pk_status pk_sortformer_stream_reset(pk_sortformer *s) {
-    return sf_guard([&] {
+    return guard([&] {
         if (!s) fail(PK_ERR_INVALID, "invalid argument: sortformer");
         s->s->reset_stream();
     });

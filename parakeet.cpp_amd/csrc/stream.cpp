@@ -15,6 +15,7 @@
 #include <map>
 #include <utility>
 
+#include "capi_util.hpp"
 #include "stream.hpp"
 
 namespace pk {
@@ -488,24 +489,10 @@ using namespace pk;
 
 struct pk_stream { std::unique_ptr<StreamBatch> s; };
 
-template <class F>
-static pk_status stream_guard(F &&fn) {
-    try {
-        fn();
-        return PK_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return PK_ERR_INVALID;
-    }
-}
-
 extern "C" {
 
 pk_status pk_stream_create(pk_model *m, int n_streams, int att_context_left, int att_context_right, pk_stream **out) {
-    return stream_guard([&] {
+    return guard([&] {
         if (!m || !out) fail(PK_ERR_INVALID, "invalid argument: model/out");
         auto h = std::make_unique<pk_stream>();
         h->s = std::make_unique<StreamBatch>(*m->m, n_streams, att_context_left, att_context_right);
@@ -514,37 +501,37 @@ pk_status pk_stream_create(pk_model *m, int n_streams, int att_context_left, int
 }
 void pk_stream_free(pk_stream *s) { delete s; }
 pk_status pk_stream_reset(pk_stream *s) {
-    return stream_guard([&] { if (!s) fail(PK_ERR_INVALID, "stream"); s->s->reset(); });
+    return guard([&] { if (!s) fail(PK_ERR_INVALID, "stream"); s->s->reset(); });
 }
 pk_status pk_stream_push(pk_stream *s, const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start,
                          int32_t *end, float *conf) {
-    return stream_guard([&] {
+    return guard([&] {
         if (!s || !pcm || !ids || !lens || n_samples <= 0 || max_tokens <= 0) fail(PK_ERR_INVALID, "invalid argument: stream/pcm/ids/lens/sizes");
         s->s->push(pcm, n_samples, max_tokens, ids, lens, start, end, conf);
     });
 }
 pk_status pk_stream_mel(pk_stream *s, const float *pcm, int n_samples, float *out, int cap_frames, int *n_frames) {
-    return stream_guard([&] {
+    return guard([&] {
         if (!s || !pcm || !out || !n_frames) fail(PK_ERR_INVALID, "invalid argument: stream/pcm/out/n_frames");
         *n_frames = s->s->mel(pcm, n_samples, out, cap_frames);
     });
 }
 pk_status pk_stream_encode(pk_stream *s, const float *mel, int n_frames, float *enc, int cap_frames, int *n_out) {
-    return stream_guard([&] {
+    return guard([&] {
         if (!s || !mel || !enc || !n_out) fail(PK_ERR_INVALID, "invalid argument: stream/mel/enc/n_out");
         *n_out = s->s->encode(mel, n_frames, enc, cap_frames);
     });
 }
 pk_status pk_stream_decode(pk_stream *s, const float *enc, int n_frames, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start,
                            int32_t *end, float *conf) {
-    return stream_guard([&] {
+    return guard([&] {
         if (!s || !enc || !ids || !lens) fail(PK_ERR_INVALID, "invalid argument: stream/enc/ids/lens");
         s->s->decode(enc, n_frames, max_tokens, ids, lens, start, end, conf);
     });
 }
 pk_status pk_stream_score(pk_stream *s, const float *enc, int n_frames, const int32_t *labels, const int32_t *dur_idx, const int32_t *n_steps,
                           int cap, float *label_logp, float *dur_logp, int32_t *n_done) {
-    return stream_guard([&] {
+    return guard([&] {
         if (!s) fail(PK_ERR_INVALID, "stream");
         s->s->score(enc, n_frames, labels, dur_idx, n_steps, cap, label_logp, dur_logp, n_done);
     });

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "capi_util.hpp"
 #include "transformer.hpp"
 
 namespace pk {
@@ -153,33 +154,19 @@ extern "C" {
 
 pk_status pk_transformer_load(const char *safetensors_path, const char *prefix, const pk_transformer_config *cfg, int device,
                               pk_transformer **out) {
-    try {
+    return guard([&] {
         if (!safetensors_path || !cfg || !out) fail(PK_ERR_INVALID, "invalid argument: path/cfg/out");
         auto h = std::make_unique<pk_transformer>();
         h->t = std::make_unique<TransformerEncoder>(safetensors_path, prefix ? prefix : "", *cfg, device);
         *out = h.release();
-        return PK_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return PK_ERR_INVALID;
-    }
+    });
 }
 
 pk_status pk_transformer_forward(pk_transformer *t, const float *x, int B, int T, float *y) {
-    try {
+    return guard([&] {
         if (!t || !x || !y || B <= 0 || T <= 0) fail(PK_ERR_INVALID, "invalid argument: transformer/x/y/B/T");
         t->t->forward(x, B, T, y);
-        return PK_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return PK_ERR_INVALID;
-    }
+    });
 }
 
 void pk_transformer_free(pk_transformer *t) { delete t; }
