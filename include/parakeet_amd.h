@@ -592,6 +592,24 @@ pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T
  * pk_model_set_attention_context.  variant (may be NULL): bit 1 = ragged instantiation, bit 3 = the band kernel ran, bit 4 = bf16 output. */
 pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
                                          const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant);
+/* The cached attention of the streaming encoder alone (kernels/stream.hip; reference src/streaming_encoder.cpp:162-272), launched as a session
+ * launches it for S lock-step streams: qkv_new [S c][3 d] natural columns (q | k | v of the chunk's c rows per stream), kcache / vcache
+ * [S][cache_rows][d] of which the first nc rows of every stream are valid, pos [P][d] the projected position table (the kernel reads its last
+ * nc + c rows), bias_u / bias_v [d], the [att_left, att_right] context (-1, -1: no mask), hd = d / n_heads (a multiple of 4).  rotate != 0: the
+ * same launch writes the new caches, the last min(keep_max, nc + c) rows of [cache ; chunk] per stream, to cache_k_out / cache_v_out.
+ * ctx_sigma != 0: the columns of ctx in the sigma layout the out-projection reads (d a multiple of 16).
+ * ctx receives [S c + PK_DIAG_ATTENTION_GUARD_ROWS][d] floats, cache_k_out / cache_v_out (may be NULL when rotate == 0) [S cache_rows +
+ * PK_DIAG_ATTENTION_GUARD_ROWS][d]: all three device buffers are filled with the pattern 0x7FC5A5A5 before the launch, so a word the launch did
+ * not write comes back as that pattern.  form (may be NULL): the launch taken, by the function the launcher switches on.
+ * PK_ERR_INVALID, and nothing is launched, for c <= 0, nc > cache_rows, P < nc + c, keep_max > cache_rows with rotate. */
+#define PK_DIAG_STREAM_ATT_GENERAL_1W 0   /* stream_attention_kernel, one wavefront */
+#define PK_DIAG_STREAM_ATT_GENERAL_2W 1   /* ... two wavefronts (more than 64 keys) */
+#define PK_DIAG_STREAM_ATT_TILES_HD64 2   /* stream_attention_tiles_kernel, head size 64 */
+#define PK_DIAG_STREAM_ATT_TILES_HD128 3  /* ... head size 128 */
+pk_status pk_diag_stream_attention(int S, int c, int nc, int cache_rows, int d, int n_heads, const float *qkv_new, const float *kcache,
+                                   const float *vcache, const float *pos, int P, const float *bias_u, const float *bias_v, int att_left,
+                                   int att_right, int keep_max, int ctx_sigma, int rotate, float *ctx, float *cache_k_out, float *cache_v_out,
+                                   int *form);
 /* Which instantiation of the convolution kernels outside the GEMM the engine launches for this model and batch, computed by the functions the
  * launchers themselves switch on (kernels/kernels.hpp: sub_conv1_dw1_inst, sub_dw_inst, dwconv_inst, stream_dwconv_inst).  Host arithmetic only: no
  * device is needed.  The batch is B utterances of Tm mel frames each (n_mel_frames = NULL), or a ragged batch of B utterances of n_mel_frames[b]

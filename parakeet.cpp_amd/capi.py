@@ -190,6 +190,7 @@ _LATE_SIGNATURES = {
     "pk_diag_conv_instantiations": [i32p, C.c_int],
     "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
                                        C.POINTER(C.c_int)],
+    "pk_diag_stream_attention": [C.c_int] * 6 + [f32p] * 4 + [C.c_int, f32p, f32p] + [C.c_int] * 5 + [f32p] * 3 + [C.POINTER(C.c_int)],
 }
 
 
@@ -768,6 +769,27 @@ def diag_relpos_attention(kernel, qkv, pos, bias_u, bias_v, n_heads, B=1, lens=N
     check(lib().pk_diag_relpos_attention({"fp32": 0, "bf16": 1}[kernel], B, lp, T, d, n_heads, _f(qkv), _f(pos), pos_T, _f(bu), _f(bv), _f(out),
                                          C.byref(var)))
     return out, var.value
+
+
+STREAM_ATT_FORMS = ("general-1w", "general-2w", "tiles-hd64", "tiles-hd128")   # PK_DIAG_STREAM_ATT_*
+
+
+def diag_stream_attention(qkv_new, kcache, vcache, nc, pos, bias_u, bias_v, n_heads, left, right, keep_max, ctx_sigma=False, rotate=True):
+    """pk_diag_stream_attention: the cached attention of one streaming chunk alone, launched as a session launches it.  qkv_new [S][c][3 d]
+    (natural columns), kcache / vcache [S][cache_rows][d] with nc valid rows per stream, pos [P][d] -> (ctx [S c + ATT_GUARD_ROWS][d],
+    cache_k_out, cache_v_out [S cache_rows + ATT_GUARD_ROWS][d], form: one of STREAM_ATT_FORMS).  Every output word the launch did not write
+    holds ATT_UNWRITTEN["fp32"]; ctx_sigma: the columns of ctx in the sigma layout; rotate: the launch also writes the new caches."""
+    qkv, kc, vc, pos, bu, bv = _c(qkv_new), _c(kcache), _c(vcache), _c(pos), _c(bias_u), _c(bias_v)
+    S, c, d = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    cache_rows = kc.shape[1]
+    assert qkv.shape == (S, c, 3 * d) and kc.shape == vc.shape == (S, cache_rows, d) and pos.shape[1] == d and bu.shape == bv.shape == (d,)
+    ctx = np.empty((S * c + ATT_GUARD_ROWS, d), np.float32)
+    ko, vo = (np.empty((S * cache_rows + ATT_GUARD_ROWS, d), np.float32) for _ in range(2))
+    form = C.c_int(-1)
+    check(lib().pk_diag_stream_attention(S, c, int(nc), cache_rows, d, n_heads, _f(qkv), _f(kc), _f(vc), _f(pos), pos.shape[0], _f(bu), _f(bv),
+                                         int(left), int(right), int(keep_max), int(bool(ctx_sigma)), int(bool(rotate)), _f(ctx), _f(ko), _f(vo),
+                                         C.byref(form)))
+    return ctx, ko, vo, STREAM_ATT_FORMS[form.value]
 
 
 class Batch:

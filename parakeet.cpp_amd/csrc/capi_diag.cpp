@@ -560,4 +560,46 @@ pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int 
     });
 }
 
+// The cached attention of a streaming chunk alone, launched as StreamBatch::encode launches it (stream.cpp): natural columns, the rotation of
+// the caches into a second buffer pair riding on the same launch.
+pk_status pk_diag_stream_attention(int S, int c, int nc, int cache_rows, int d, int n_heads, const float *qkv_new, const float *kcache,
+                                   const float *vcache, const float *pos, int P, const float *bias_u, const float *bias_v, int att_left,
+                                   int att_right, int keep_max, int ctx_sigma, int rotate, float *ctx, float *cache_k_out, float *cache_v_out,
+                                   int *form) {
+    return guard([&] {
+        need(qkv_new && kcache && vcache && pos && bias_u && bias_v && ctx, "qkv_new/kcache/vcache/pos/bias_u/bias_v/ctx");
+        need(S > 0 && d > 0 && n_heads > 0 && d % n_heads == 0 && (d / n_heads) % 4 == 0, "S/d/n_heads (head size a multiple of 4)");
+        need(c > 0, "c > 0");
+        need(cache_rows > 0 && nc >= 0 && nc <= cache_rows, "0 <= nc <= cache_rows, cache_rows > 0");
+        need(P >= nc + c, "P >= nc + c");
+        need(!ctx_sigma || d % 16 == 0, "ctx_sigma: d must be a multiple of 16");
+        need(!rotate || (cache_k_out && cache_v_out && keep_max <= cache_rows), "rotate: cache_k_out/cache_v_out, keep_max <= cache_rows");
+        need_device();
+        const size_t n_ctx = ((size_t)S * c + PK_DIAG_ATTENTION_GUARD_ROWS) * d, n_cache = ((size_t)S * cache_rows + PK_DIAG_ATTENTION_GUARD_ROWS) * d;
+        DevBuf q, kc, vc, p, bu, bv, out, ko, vo;
+        up(q, qkv_new, (size_t)S * c * 3 * d * 4);
+        up(kc, kcache, (size_t)S * cache_rows * d * 4);
+        up(vc, vcache, (size_t)S * cache_rows * d * 4);
+        up(p, pos, (size_t)P * d * 4);
+        up(bu, bias_u, (size_t)d * 4);
+        up(bv, bias_v, (size_t)d * 4);
+        out.reserve(n_ctx * 4);
+        ko.reserve(n_cache * 4);
+        vo.reserve(n_cache * 4);
+        PK_HIP(hipMemsetD32(out.p, 0x7fc5a5a5, n_ctx));
+        PK_HIP(hipMemsetD32(ko.p, 0x7fc5a5a5, n_cache));
+        PK_HIP(hipMemsetD32(vo.p, 0x7fc5a5a5, n_cache));
+        launch_stream_attention(q.as<float>(), kc.as<float>(), vc.as<float>(), cache_rows, S, c, nc, d, n_heads, p.as<float>(), P, bu.as<float>(),
+                                bv.as<float>(), att_left, att_right, out.as<float>(), nullptr, rotate ? ko.as<float>() : nullptr,
+                                rotate ? vo.as<float>() : nullptr, keep_max, ctx_sigma ? 1 : 0);
+        PK_CHECK_LAUNCH();
+        down(ctx, out, n_ctx * 4);
+        if (cache_k_out) down(cache_k_out, ko, n_cache * 4);
+        if (cache_v_out) down(cache_v_out, vo, n_cache * 4);
+        static_assert(STREAM_ATT_GENERAL_1W == PK_DIAG_STREAM_ATT_GENERAL_1W && STREAM_ATT_GENERAL_2W == PK_DIAG_STREAM_ATT_GENERAL_2W &&
+                      STREAM_ATT_TILES_HD64 == PK_DIAG_STREAM_ATT_TILES_HD64 && STREAM_ATT_TILES_HD128 == PK_DIAG_STREAM_ATT_TILES_HD128, "form values");
+        if (form) *form = (int)stream_attention_form(nc + c, c, d / n_heads);
+    });
+}
+
 }  // extern "C"

@@ -246,11 +246,14 @@ void launch_stream_attention(const float *qkv_new, const float *kcache, const fl
                              int n_heads, const float *pos /*[P][d]*/, int P, const float *bias_u, const float *bias_v, int att_left,
                              int att_right, float *ctx, hipStream_t s, float *cache_k_out = nullptr, float *cache_v_out = nullptr, int keep_max = 0,
                              int ctx_sigma = 0 /* ctx columns in the sigma layout (GemmArgs::a_sigma of the out-projection) */);
-// (cache_k_out / cache_v_out set: the same launch also rotates the K / V caches of every (stream, head) into those buffers -- the last
-//  min(keep_max, nc + c) rows of [cache ; new], what two launch_stream_cache_update calls would write)
-// new cache = the last min(keep_max, nc + c) rows of [cache(nc rows) ; new(c rows)]  (:193-209); row stride of both caches: cache_rows*d
-void launch_stream_cache_update(const float *cache_in, int nc, const float *qkv_new, int col0, int S, int c, int d, int cache_rows,
-                                int keep_max, float *cache_out, hipStream_t s);
+// cache_k_out / cache_v_out set and keep = min(keep_max, nc + c) > 0: the same launch also rotates the K / V caches of every (stream, head)
+// into those buffers (:193-209) -- row r < keep of the new cache = row nc + c - keep + r of [cache(nc rows) ; new(c rows)], so with keep < c the
+// whole new cache comes from the chunk.  The outputs must not alias the caches the attention blocks still read; their rows keep .. cache_rows - 1
+// and everything else in them stay untouched.  Row stride of all four caches: cache_rows * d per stream (keep_max <= cache_rows).
+// The form of a launch, by the function the launcher switches on: the general kernel with one wavefront or (more than 64 keys) two, or the
+// LDS-tile kernel (kv <= 80 keys, c <= 8 new rows, head size 64 / 128).
+enum StreamAttentionForm { STREAM_ATT_GENERAL_1W, STREAM_ATT_GENERAL_2W, STREAM_ATT_TILES_HD64, STREAM_ATT_TILES_HD128 };
+StreamAttentionForm stream_attention_form(int kv, int c, int hd);
 // CausalConformerConvModule::forward_cached middle (:51-73): depthwise conv over [cache(K-1 rows, zeros when !has_cache) ; g(c rows)],
 // BatchNorm, SiLU -> out[S*c][d]; cache_out = last K-1 rows of the concatenation.
 void launch_stream_dwconv(const float *g, const float *cache_in, int has_cache, int S, int c, int d, int kc, const float *w, const float *bias,

@@ -297,6 +297,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     SA_STAMP(5);
 }
 
+// The form a launch takes (the launcher below switches on it, pk_diag_stream_attention reports it): the LDS-tile kernel for the steady state
+// of a session, the general kernel -- one wavefront, or two past 64 keys -- for everything else.
+StreamAttentionForm stream_attention_form(int kv, int c, int hd) {
+    if (kv <= kSaKv && c <= kSaNew && (hd == 128 || hd == 64)) return hd == 128 ? STREAM_ATT_TILES_HD128 : STREAM_ATT_TILES_HD64;
+    return kv > 64 ? STREAM_ATT_GENERAL_2W : STREAM_ATT_GENERAL_1W;
+}
+
 void launch_stream_attention(const float *qkv_new, const float *kcache, const float *vcache, int cache_rows, int S, int c, int nc, int d,
                              int n_heads, const float *pos, int P, const float *bias_u, const float *bias_v, int att_left, int att_right,
                              float *ctx, hipStream_t s, float *cache_k_out, float *cache_v_out, int keep_max, int ctx_sigma) {
@@ -306,43 +313,30 @@ void launch_stream_attention(const float *qkv_new, const float *kcache, const fl
     if (n_heads <= 0 || d % n_heads || hd % 4 || d % 4 || !al16(qkv_new) || !al16(kcache) || !al16(vcache) || !al16(pos) || !al16(ctx) ||
         !al16(cache_k_out) || !al16(cache_v_out))
         fail(PK_ERR_INVALID, "launch_stream_attention: head size %d / hidden size %d must be multiples of 4 and every buffer 16-byte aligned", hd, d);
+    if (ctx_sigma && d % 16) fail(PK_ERR_INVALID, "launch_stream_attention: the sigma layout of ctx permutes groups of 16 columns (hidden size %d)", d);
     const float scale = 1.0f / sqrtf((float)hd);
     const size_t lds = (size_t)(2 * hd + nc + c + 2) * sizeof(float);
     const int kv = nc + c, keep = kv > keep_max ? keep_max : kv;
     const bool rotate = cache_k_out && cache_v_out && keep > 0;
-    if (kv <= kSaKv && c <= kSaNew && (hd == 128 || hd == 64)) {    // steady state of a session: the LDS-tile form
-        const size_t lds_t = (size_t)(2 * hd + kSaKv + 8 + 2 * (kv + 1) * (hd + 4)) * sizeof(float);
-        const dim3 grid(S * n_heads, c + (rotate ? 1 : 0));
+    const dim3 grid(S * n_heads, c + (rotate ? 1 : 0));
+    const size_t lds_t = (size_t)(2 * hd + kSaKv + 8 + 2 * (kv + 1) * (hd + 4)) * sizeof(float);
 #define PK_SAT_LAUNCH(HD4V) do { \
-            static DynLdsSlots slots; \
-            ensure_dyn_lds(slots, reinterpret_cast<const void *>(&stream_attention_tiles_kernel<HD4V>), (size_t)(2 * hd + kSaKv + 8 + 2 * (kSaKv + 1) * (hd + 4)) * sizeof(float)); \
-            hipLaunchKernelGGL((stream_attention_tiles_kernel<HD4V>), grid, dim3(256), lds_t, s, qkv_new, kcache, vcache, cache_rows, c, nc, d, n_heads, pos, P, bias_u, \
-                               bias_v, att_left, att_right, scale, ctx, rotate ? cache_k_out : nullptr, rotate ? cache_v_out : nullptr, keep, ctx_sigma); \
-        } while (0)
-        if (hd == 128) PK_SAT_LAUNCH(32); else PK_SAT_LAUNCH(16);
-#undef PK_SAT_LAUNCH
-        return;
+        static DynLdsSlots slots; \
+        ensure_dyn_lds(slots, reinterpret_cast<const void *>(&stream_attention_tiles_kernel<HD4V>), (size_t)(2 * hd + kSaKv + 8 + 2 * (kSaKv + 1) * (hd + 4)) * sizeof(float)); \
+        hipLaunchKernelGGL((stream_attention_tiles_kernel<HD4V>), grid, dim3(256), lds_t, s, qkv_new, kcache, vcache, cache_rows, c, nc, d, n_heads, pos, P, bias_u, \
+                           bias_v, att_left, att_right, scale, ctx, rotate ? cache_k_out : nullptr, rotate ? cache_v_out : nullptr, keep, ctx_sigma); \
+    } while (0)
+    const StreamAttentionForm form = stream_attention_form(kv, c, hd);
+    switch (form) {
+    case STREAM_ATT_TILES_HD128: PK_SAT_LAUNCH(32); break;         // steady state of a session: the LDS-tile form
+    case STREAM_ATT_TILES_HD64: PK_SAT_LAUNCH(16); break;
+    case STREAM_ATT_GENERAL_1W:
+    case STREAM_ATT_GENERAL_2W:
+        hipLaunchKernelGGL(stream_attention_kernel, grid, dim3(form == STREAM_ATT_GENERAL_2W ? 128 : 64), lds, s, qkv_new, kcache, vcache, cache_rows, c, nc, d,
+                           n_heads, pos, P, bias_u, bias_v, att_left, att_right, scale, ctx, rotate ? cache_k_out : nullptr, rotate ? cache_v_out : nullptr, keep, ctx_sigma);
+        break;
     }
-    hipLaunchKernelGGL(stream_attention_kernel, dim3(S * n_heads, c + (rotate ? 1 : 0)), dim3(kv > 64 ? 128 : 64), lds, s, qkv_new, kcache, vcache, cache_rows, c, nc, d,
-                       n_heads, pos, P, bias_u, bias_v, att_left, att_right, scale, ctx, rotate ? cache_k_out : nullptr, rotate ? cache_v_out : nullptr, keep, ctx_sigma);
-}
-
-__global__ void stream_cache_update_kernel(const float *__restrict__ cache_in, int nc, const float *__restrict__ qkv, int col0, int c, int d,
-                                           int cache_rows, int keep, float *__restrict__ cache_out, int64_t n) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    const int e = (int)(idx % d), r = (int)((idx / d) % keep), sidx = (int)(idx / ((int64_t)d * keep));
-    const int j = nc + c - keep + r;                                // row of [cache ; new]
-    cache_out[((int64_t)sidx * cache_rows + r) * d + e] =
-        j < nc ? cache_in[((int64_t)sidx * cache_rows + j) * d + e] : qkv[((int64_t)sidx * c + (j - nc)) * 3 * d + col0 + e];
-}
-void launch_stream_cache_update(const float *cache_in, int nc, const float *qkv_new, int col0, int S, int c, int d, int cache_rows,
-                                int keep_max, float *cache_out, hipStream_t s) {
-    const int kv = nc + c, keep = kv > keep_max ? keep_max : kv;
-    if (keep <= 0) return;
-    const int64_t n = (int64_t)S * keep * d;
-    hipLaunchKernelGGL(stream_cache_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cache_in, nc, qkv_new, col0, c, d, cache_rows,
-                       keep, cache_out, n);
+#undef PK_SAT_LAUNCH
 }
 
 // One thread per (stream, channel).  Everything the thread reads -- its column of [cache ; g] (KC - 1 + c values), the KC taps, bias and the four

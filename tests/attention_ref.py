@@ -93,12 +93,25 @@ def head_reference(kind, q, k, v, Pw, u, vb, rows=None, scale=None):
     shift = (lambda x: rel_shift(x)) if rows is None else (lambda x: band_gather(x, I, T))
     z = (qu @ k.T + shift(pos)) * scale
     mag = np.abs(qu) @ np.abs(k).T + shift(pos_abs)
+    return softmax_pv_bounds(kind, z, mag, v, scale, hd)
+
+
+def softmax_pv_bounds(kind, z, mag, v, scale, hd, live=None):
+    """ctx = softmax(z) v of one (utterance, head) with the bound and sigma of the docstring above.  z [n_rows][T] the exact scaled scores,
+    mag [n_rows][T] the sums of |terms| of their dot products (C_j), v [T][hd].  live (boolean [n_rows][T], None: every key): False marks a
+    key whose score was REPLACED by a mask constant (z holds that constant) -- its probability is exactly 0 in the reference and in any
+    implementation, so it is left out of the |z| terms of the bound (a constant of 1e9 there would make the bound pass anything).
+    Returns ctx, bound, sigma [n_rows][hd] (float64)."""
+    T = v.shape[0]
     e = np.exp(z - z.max(axis=1, keepdims=True))
     p = e / e.sum(axis=1, keepdims=True)
     va = np.abs(v)
     ctx = p @ v
     A = p @ va
-    zabs = np.abs(z) + np.abs(z).max(axis=1, keepdims=True)
+    az = np.abs(z)
+    if live is not None:
+        az, mag = np.where(live, az, 0.0), np.where(live, mag, 0.0)
+    zabs = az + az.max(axis=1, keepdims=True)
 
     def score_term(n_dot):
         d = scale * n_dot * U32 * mag + 8 * U32 * zabs + E_EXP
