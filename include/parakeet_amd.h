@@ -654,6 +654,56 @@ pk_status pk_diag_skinny_gemm(const pk_skinny_diag *a);
 /* Prediction-net caching of the per-phase decode loop (kernels.hpp TdtState::need) on / off; process-wide test switch, default on.  Off: every
  * phase launch covers every utterance at any batch size -- the same words, bit for bit (tests/test_gpu_bf16_decode_batch.py). */
 pk_status pk_diag_pred_cache(int on);
+/* n_steps >= 1 back-to-back launches of the greedy decision kernel of the TDT / RNNT decode loop (kernels/decode.hip launch_tdt_decide; kernels.hpp
+ * TdtState) on state the CALLER sets -- no initialisation launch runs, so a call may start in the middle of an utterance.  Scalars as TdtState names them
+ * (D = 0: the RNNT step).  Per step k: logits [n_steps][B F][V + D] and the candidate LSTM state hn / cn [n_steps][L][B][Hp] (h_bf16: h / hn hold bf16 words,
+ * Hp even).  Every other array is BOTH input and output, as pk_diag_skinny_gemm's: copied up whole, copied back whole after the last launch.
+ *   [rows] (rows >= B: the rows past the batch show stray stores): t, steps, n_out, nsym, done, token, lens, margin (may be NULL), need (may be NULL), n_act
+ *   [rows][max_tokens]: ids, start, end, conf;  [1]: done_count;  h: h_words 32-bit words (>= L B Hp, h_bf16: L B Hp / 2), c: c_words (>= L B Hp)
+ *   need set (prediction-net caching): pp [B][J], ep [ep_rows][J], z of z_words 32-bit words (>= B F J fp32 in the sigma column order; h_bf16: B J bf16 words,
+ *   natural order), utterance b's enc_proj rows start at row0[b] (NULL: b T) and it has Tb[b] frames (NULL: T).  Tb set also makes the cap per utterance.
+ *   trie_off set (phrase boosting): the trie in CSR form, trie_off [trie_nodes + 1], trie_tok / trie_node [trie_off[trie_nodes]], boost; act [rows][64], n_act.
+ *   force_label set (forced scoring): force_label / force_dur [force_len], utterance b walks n_force_b[b] (NULL: n_force) steps from element b force_stride;
+ *   score_lab [score_rows][V] / score_dur [score_rows][D] (either may be NULL) receive the rows b force_stride + step.
+ * form (may be NULL): the launch taken, by the function the launcher switches on: PK_DIAG_TDT_KERNEL(form) exact / fast / boost / score, PK_DIAG_TDT_SLOTS(form)
+ * the 256-element slots of LSTM state per thread (3 / 6 / 12), PK_DIAG_TDT_ROW(form) how the logits row is staged (5 or 33 register slots -- the fast kernel's NQ --,
+ * batches of 8, the frame window).
+ * PK_ERR_INVALID, and nothing is launched, for what the engine never launches: L Hp > 3072; F > 1 outside the plain exact step with V + D <= 1280, F <= 8 and
+ * J <= 1024; more than 160 KB of LDS; D > 16, or D > 8 with a logits row whose duration maximum is not among the first 8 (TdtState holds 8 durations); state words,
+ * frames, trie nodes or forced decisions out of range. */
+#define PK_DIAG_TDT_KERNEL(form) ((form) >> 4)         /* 0 exact, 1 fast, 2 boost, 3 score */
+#define PK_DIAG_TDT_SLOTS(form) (3 << (((form) >> 2) & 3))
+#define PK_DIAG_TDT_ROW(form) ((form) & 3)             /* 0: 5 slots, 1: 33 slots, 2: batches of 8, 3: frame window */
+typedef struct pk_tdt_decide_diag {
+    int32_t B, T, V, D, L, Hp, blank, max_symbols, max_tokens, max_steps, keep_state, h_bf16, F, J;
+    int32_t durations[8];
+    int32_t n_steps, rows;
+    const float *logits; const void *hn; const float *cn;
+    int32_t *t, *steps, *n_out, *nsym, *done, *token, *lens, *done_count;
+    void *h; float *c; int64_t h_words, c_words;
+    int32_t *ids, *start, *end; float *conf;
+    float *margin;
+    int32_t *need; const float *pp, *ep; int64_t ep_rows; void *z; int64_t z_words;
+    const int32_t *Tb, *row0;
+    const int32_t *trie_off, *trie_tok, *trie_node; int32_t trie_nodes; float boost; int32_t *act, *n_act;
+    const int32_t *force_label, *force_dur; int64_t force_len; int32_t n_force; const int32_t *n_force_b; int32_t force_stride;
+    float *score_lab, *score_dur; int64_t score_rows;
+} pk_tdt_decide_diag;
+pk_status pk_diag_tdt_decide(const pk_tdt_decide_diag *a, int *form);
+/* The CTC greedy kernels alone (kernels/decode.hip): the row log-softmax + first-max argmax over logits [frames][ld] (n <= ld values per row), once without and
+ * once with the log-prob rows (best_idx2 / best_lp2, then lp / best_idx / best_lp), then the collapse -- or, trie_off set, the boosted walk over lp.  B utterances
+ * of T frames, or n_frames[b] frames each, packed.  All outputs are in/out as above: lp [lp_rows][n], best_* [lp_rows] (lp_rows >= frames), ids / start / end /
+ * conf [out_rows][pitch] (pitch >= the longest utterance), lens [out_rows] (out_rows >= B). */
+typedef struct pk_ctc_greedy_diag {
+    int32_t B, T, n, ld, blank, pitch, out_rows;
+    const int32_t *n_frames;
+    const float *logits;
+    int64_t lp_rows;
+    float *lp; int32_t *best_idx; float *best_lp; int32_t *best_idx2; float *best_lp2;
+    int32_t *ids, *lens, *start, *end; float *conf;
+    const int32_t *trie_off, *trie_tok, *trie_node; int32_t trie_nodes; float boost;
+} pk_ctc_greedy_diag;
+pk_status pk_diag_ctc_greedy(const pk_ctc_greedy_diag *a);
 
 #ifdef __cplusplus
 }

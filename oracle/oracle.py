@@ -334,6 +334,18 @@ class Model:
         return dict(ids=ids, lens=lens, start=st, conf=cf)
 
 
+def log_softmax_rows(x):
+    """the decoders' row log-softmax (max-subtracted, canonical sum64) over the last axis, as every decode loop of the oracle applies it"""
+    x = _c(x)
+    n = x.shape[-1]
+    y = _out(x.shape)
+    L = lib()
+    L.orc_log_softmax_rows.argtypes = [f32p, C.c_int64, C.c_int, f32p]
+    L.orc_log_softmax_rows.restype = None
+    L.orc_log_softmax_rows(_f(x), x.size // n, n, _f(y))
+    return y
+
+
 def ctc_greedy(logp, blank_id):
     """ctc_greedy_decode(+_with_timestamps): src/ctc.cpp:40-127."""
     logp = _c(logp)

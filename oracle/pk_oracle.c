@@ -1076,6 +1076,10 @@ static void log_softmax_row(const float *x, int n, float *y) {
     for (int i = 0; i < n; ++i) y[i] = (x[i] - mx) - lse;
     if (e != tmp) free(e);
 }
+/* the same rows for tests that restate a decoder's decision: x[rows][n] -> out[rows][n] */
+void orc_log_softmax_rows(const float *x, int64_t rows, int n, float *out) {
+    for (int64_t r = 0; r < rows; ++r) log_softmax_row(x + r * n, n, out + r * n);
+}
 static int argmax_first(const float *x, int n) { /* strict '>' : lowest index wins ties (src/ctc.cpp:59-66) */
     int best = 0;
     float bv = x[0];

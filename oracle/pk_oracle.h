@@ -70,6 +70,7 @@ int orc_subsampling(orc_model *m, const float *feats, int B, int Tm, float *out,
 int orc_conformer_block(orc_model *m, int layer, float *x, int B, int T, const float *pos_emb, int stop_after);
 int orc_encoder(orc_model *m, const float *feats, int B, int Tm, float *out, float *layer_taps);
 int orc_ctc_logprobs(orc_model *m, const float *enc, int B, int T, float *logp);
+void orc_log_softmax_rows(const float *x, int64_t rows, int n, float *out);   /* the decoders' row log-softmax (x must not alias out) */
 void orc_ctc_greedy(const float *logp, int B, int T, int V, int blank_id, int32_t *ids, int32_t *lens,
                     int32_t *start, int32_t *end, float *conf);
 int orc_tdt_greedy(orc_model *m, const float *enc, int B, int T, int max_tokens, int max_steps, int32_t *ids,

@@ -427,6 +427,166 @@ def diag_skinny_gemm(epi, X, W, bias=None, bf16=False, gi=None, gi_row=None, c=N
     return dict(out=out, cn=cn, pp=pp)
 
 
+class PkTdtDecideDiag(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("B", "T", "V", "D", "L", "Hp", "blank", "max_symbols", "max_tokens", "max_steps", "keep_state", "h_bf16", "F", "J")]
+                + [("durations", C.c_int32 * 8), ("n_steps", C.c_int32), ("rows", C.c_int32),
+                   ("logits", f32p), ("hn", C.c_void_p), ("cn", f32p)]
+                + [(k, i32p) for k in ("t", "steps", "n_out", "nsym", "done", "token", "lens", "done_count")]
+                + [("h", C.c_void_p), ("c", f32p), ("h_words", C.c_int64), ("c_words", C.c_int64),
+                   ("ids", i32p), ("start", i32p), ("end", i32p), ("conf", f32p), ("margin", f32p),
+                   ("need", i32p), ("pp", f32p), ("ep", f32p), ("ep_rows", C.c_int64), ("z", C.c_void_p), ("z_words", C.c_int64),
+                   ("Tb", i32p), ("row0", i32p),
+                   ("trie_off", i32p), ("trie_tok", i32p), ("trie_node", i32p), ("trie_nodes", C.c_int32), ("boost", C.c_float), ("act", i32p), ("n_act", i32p),
+                   ("force_label", i32p), ("force_dur", i32p), ("force_len", C.c_int64), ("n_force", C.c_int32), ("n_force_b", i32p), ("force_stride", C.c_int32),
+                   ("score_lab", f32p), ("score_dur", f32p), ("score_rows", C.c_int64)])
+
+
+class PkCtcGreedyDiag(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("B", "T", "n", "ld", "blank", "pitch", "out_rows")]
+                + [("n_frames", i32p), ("logits", f32p), ("lp_rows", C.c_int64), ("lp", f32p), ("best_idx", i32p), ("best_lp", f32p), ("best_idx2", i32p), ("best_lp2", f32p),
+                   ("ids", i32p), ("lens", i32p), ("start", i32p), ("end", i32p), ("conf", f32p),
+                   ("trie_off", i32p), ("trie_tok", i32p), ("trie_node", i32p), ("trie_nodes", C.c_int32), ("boost", C.c_float)])
+
+
+TDT_KERNELS = ("exact", "fast", "boost", "score")                  # PK_DIAG_TDT_KERNEL
+TDT_ROWS = ("row5", "row33", "batch8", "window")                   # PK_DIAG_TDT_ROW
+
+
+def tdt_form(form):
+    """PK_DIAG_TDT_KERNEL / _SLOTS / _ROW of a form word -> (kernel, NC, row staging)"""
+    return TDT_KERNELS[form >> 4], 3 << ((form >> 2) & 3), TDT_ROWS[form & 3]
+
+
+def _padded(a, lead, dt, pad):
+    """`a` (its first axis = lead rows) as dt words with `pad` pattern-filled rows behind it"""
+    a = np.ascontiguousarray(a)
+    assert a.shape[0] == lead and a.dtype.itemsize == np.dtype(dt).itemsize, (a.shape, a.dtype, lead)
+    out = np.full((lead + pad,) + a.shape[1:], SKINNY_FILL32, np.uint32).view(dt)
+    out[:lead] = a.view(dt)
+    return out
+
+
+def _flat_guard(a, guard):
+    """a's bytes as 32-bit words with `guard` pattern words behind them"""
+    w = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    assert w.size % 4 == 0
+    out = np.full(w.size // 4 + guard, SKINNY_FILL32, np.uint32)
+    out[: w.size // 4] = w.view(np.uint32)
+    return out
+
+
+def diag_tdt_decide(sc, logits, hn, cn, st, pad_rows=3, guard=32):
+    """pk_diag_tdt_decide (include/parakeet_amd.h): logits [n_steps][B F][V + D], hn / cn [n_steps][L][B][Hp] (hn uint16 bf16 words when sc["h_bf16"]).
+    sc: the scalars of the struct (durations a list).  st: the batch's state, arrays with B leading rows -- t, steps, n_out, nsym, done, token, lens, ids, start,
+    end, conf, h, c and done_count; optional margin; need + pp + ep + z (z natural columns, [B F][J] fp32 or [B][J] uint16); Tb, row0; trie = (off, tok, node,
+    boost) + act + n_act; force = (label, dur, n_force, n_force_b, stride) + score_lab / score_dur.  Returns the WHOLE buffers after the last launch: the per-row
+    arrays pad_rows pattern-filled rows longer than the batch, h / c / z as flat uint32 words with `guard` pattern words behind them (z: fp32 words back in
+    natural order), and "form"."""
+    B, F, J = sc["B"], max(1, sc.get("F", 1)), sc.get("J", 0)
+    logits, cn = _c(logits), _c(cn)
+    hn = np.ascontiguousarray(hn, np.uint16 if sc.get("h_bf16") else np.float32)
+    d = PkTdtDecideDiag()
+    for k in ("B", "T", "V", "D", "L", "Hp", "blank", "max_symbols", "max_tokens", "max_steps", "keep_state", "h_bf16", "F", "J"):
+        setattr(d, k, int(sc.get(k, 0)))
+    d.F = F
+    for i, v in enumerate(sc.get("durations", [])):
+        if i < 8:
+            d.durations[i] = int(v)
+    d.n_steps, d.rows = logits.shape[0], B + pad_rows
+    keep = [logits, hn, cn]
+    out = {}
+
+    def io(name, dt, lead=B):
+        a = _padded(np.asarray(st[name]), lead, dt, pad_rows)
+        out[name] = a
+        return a.ctypes.data_as(f32p if dt == np.float32 else i32p)
+
+    def ro(a, dt=np.int32):
+        a = _c(a, dt)
+        keep.append(a)
+        return a.ctypes.data_as(f32p if dt == np.float32 else i32p)
+
+    d.logits, d.hn, d.cn = _f(logits), hn.ctypes.data_as(C.c_void_p), _f(cn)
+    for k in ("t", "steps", "n_out", "nsym", "done", "token", "lens", "ids", "start", "end"):
+        setattr(d, k, io(k, np.int32))
+    d.conf = io("conf", np.float32)
+    out["done_count"] = np.asarray([st["done_count"]], np.int32)
+    d.done_count = _i(out["done_count"])
+    out["h"], out["c"] = _flat_guard(st["h"], guard), _flat_guard(st["c"], guard)
+    d.h, d.c, d.h_words, d.c_words = out["h"].ctypes.data_as(C.c_void_p), out["c"].ctypes.data_as(f32p), out["h"].size, out["c"].size
+    if st.get("margin") is not None:
+        d.margin = io("margin", np.float32)
+    if st.get("need") is not None:
+        d.need = io("need", np.int32)
+        ep = _c(st["ep"]).reshape(-1, J)
+        d.pp, d.ep, d.ep_rows = ro(st["pp"], np.float32), ro(ep, np.float32), ep.shape[0]
+        z = np.ascontiguousarray(st["z"])
+        if not sc.get("h_bf16"):
+            z = np.ascontiguousarray(z.reshape(B * F, J)[:, sigma16(J)])
+        out["z"] = _flat_guard(z, guard)
+        d.z, d.z_words = out["z"].ctypes.data_as(C.c_void_p), out["z"].size
+    if st.get("Tb") is not None:
+        d.Tb = ro(st["Tb"])
+    if st.get("row0") is not None:
+        d.row0 = ro(st["row0"])
+    if st.get("trie") is not None:
+        off, tok, node, boost = st["trie"]
+        d.trie_off, d.trie_tok, d.trie_node = ro(off), ro(tok if len(tok) else [0]), ro(node if len(node) else [0])
+        d.trie_nodes, d.boost = len(off) - 1, float(boost)
+        d.act, d.n_act = io("act", np.int32), io("n_act", np.int32)
+    if st.get("force") is not None:
+        lab, dur, n_force, n_force_b, stride = st["force"]
+        d.force_label, d.force_dur, d.force_len, d.n_force, d.force_stride = ro(lab), ro(dur), len(lab), int(n_force), int(stride)
+        if n_force_b is not None:
+            d.n_force_b = ro(n_force_b)
+        for k in ("score_lab", "score_dur"):
+            if st.get(k) is not None:
+                out[k] = np.ascontiguousarray(st[k], np.float32).copy()
+                setattr(d, k, _f(out[k]))
+                d.score_rows = out[k].shape[0]
+    form = C.c_int(-1)
+    L = lib()
+    L.pk_diag_tdt_decide.argtypes = [C.POINTER(PkTdtDecideDiag), C.POINTER(C.c_int)]
+    check(L.pk_diag_tdt_decide(C.byref(d), C.byref(form)))
+    if "z" in out and not sc.get("h_bf16"):
+        body = out["z"][: B * F * J].reshape(B * F, J)[:, sigma16(J)]
+        out["z"] = np.concatenate([body.reshape(-1), out["z"][B * F * J:]])
+    out["form"] = form.value
+    return out
+
+
+def diag_ctc_greedy(logits, n, blank, B=None, T=0, n_frames=None, pitch=None, trie=None, pad_rows=3):
+    """pk_diag_ctc_greedy: logits [frames][ld] (the first n columns of a row are its values).  Uniform batch: B x T frames; ragged: n_frames [B], packed.
+    trie = (off, tok, node, boost): the boosted kernel instead of the collapse.  Returns the whole pattern-filled buffers: lp [frames + pad][n], best_idx /
+    best_lp (the launch with log-prob rows) and best_idx2 / best_lp2 (without) [frames + pad], ids / start / end / conf [B + pad][pitch], lens [B + pad]."""
+    logits = _c(logits)
+    frames, ld = logits.shape
+    nf = _c(n_frames, np.int32) if n_frames is not None else None
+    B = len(nf) if nf is not None else B
+    tmax = int(nf.max()) if nf is not None else T
+    pitch = pitch or tmax
+    fill = lambda shape, dt: np.full(shape, SKINNY_FILL32, np.uint32).view(dt)
+    o = dict(lp=fill((frames + pad_rows, n), np.float32), best_idx=fill(frames + pad_rows, np.int32), best_lp=fill(frames + pad_rows, np.float32),
+             best_idx2=fill(frames + pad_rows, np.int32), best_lp2=fill(frames + pad_rows, np.float32), lens=fill(B + pad_rows, np.int32),
+             ids=fill((B + pad_rows, pitch), np.int32), start=fill((B + pad_rows, pitch), np.int32), end=fill((B + pad_rows, pitch), np.int32),
+             conf=fill((B + pad_rows, pitch), np.float32))
+    d = PkCtcGreedyDiag()
+    d.B, d.T, d.n, d.ld, d.blank, d.pitch, d.out_rows, d.lp_rows = B, int(T), n, ld, blank, pitch, B + pad_rows, frames + pad_rows
+    d.n_frames = _i(nf) if nf is not None else None
+    d.logits = _f(logits)
+    for k, a in o.items():
+        setattr(d, k, a.ctypes.data_as(f32p if a.dtype == np.float32 else i32p))
+    keep = []
+    if trie is not None:
+        off, tok, node, boost = trie
+        keep = [_c(off, np.int32), _c(tok if len(tok) else [0], np.int32), _c(node if len(node) else [0], np.int32)]
+        d.trie_off, d.trie_tok, d.trie_node, d.trie_nodes, d.boost = _i(keep[0]), _i(keep[1]), _i(keep[2]), len(off) - 1, float(boost)
+    L = lib()
+    L.pk_diag_ctc_greedy.argtypes = [C.POINTER(PkCtcGreedyDiag)]
+    check(L.pk_diag_ctc_greedy(C.byref(d)))
+    return o
+
+
 def diag_pred_cache(on):
     """pk_diag_pred_cache: prediction-net caching of the per-phase decode loop on / off (test switch, process-wide, default on)."""
     L = lib()

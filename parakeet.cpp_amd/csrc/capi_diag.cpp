@@ -342,6 +342,187 @@ pk_status pk_diag_skinny_gemm(const pk_skinny_diag *d) {
     });
 }
 
+pk_status pk_diag_tdt_decide(const pk_tdt_decide_diag *d, int *form) {
+    return guard([&] {
+        need(d, "args");
+        const int B = d->B, V = d->V, D = d->D, L = d->L, Hp = d->Hp, F = d->F > 1 ? d->F : 1, J = d->J, rows = d->rows, mt = d->max_tokens, VD = V + D;
+        need(B > 0 && rows >= B && d->n_steps >= 1 && d->T >= 1, "B/rows/n_steps/T");
+        need(V >= 1 && D >= 0 && D <= 16 && d->blank >= 0 && d->blank < V && mt >= 1 && d->max_symbols >= 1 && d->max_steps >= 0, "V/D/blank/max_tokens/max_symbols/max_steps");
+        need(L >= 1 && L <= 4 && Hp >= 1 && (!d->h_bf16 || Hp % 2 == 0), "L/Hp");
+        need(d->logits && d->hn && d->cn && d->h && d->c, "logits/hn/cn/h/c");
+        need(d->t && d->steps && d->n_out && d->nsym && d->done && d->token && d->lens && d->done_count && d->ids && d->start && d->end && d->conf, "state words / token arrays");
+        const size_t hp_h = d->h_bf16 ? Hp / 2 : Hp, n_h = (size_t)L * B * hp_h, n_c = (size_t)L * B * Hp;
+        need((size_t)d->h_words >= n_h && (size_t)d->c_words >= n_c, "h_words/c_words");
+        TdtState st{};
+        st.B = B; st.T = d->T; st.V = V; st.D = D; st.L = L; st.Hp = Hp; st.blank = d->blank; st.max_symbols = d->max_symbols; st.max_tokens = mt;
+        st.max_steps = d->max_steps; st.keep_state = d->keep_state; st.h_bf16 = d->h_bf16 ? 1 : 0; st.F = F; st.J = J;
+        for (int i = 0; i < 8; ++i) st.durations[i] = d->durations[i];
+        const bool pred = d->need != nullptr, boost = d->trie_off != nullptr, score = d->force_label != nullptr;
+        // what the engine itself never launches (launch_tdt_decide would abort, or the kernel would leave its buffers)
+        // (the form depends on WHETHER these three are set, nothing reads through them here: the caller's own arrays stand in until the device copies exist)
+        st.need = d->need; st.trie.off = d->trie_off; st.force_label = d->force_label;
+        need(tdt_decide_launchable(st), "L * Hp <= 3072; F > 1 only for the plain exact step with V + D <= 1280, F <= 8, J <= 1024");
+        need(tdt_decide_lds_bytes(st) <= 160 * 1024, "LDS above 160 KB");
+        need(!(boost && score), "trie and forced path together");
+        const int64_t n_rows = (int64_t)d->n_steps * B * F;
+        for (int64_t r = 0; D > 8 && r < n_rows; ++r) {            // TdtState holds 8 durations: a longer head must never choose past them
+            const float *dl = d->logits + r * VD + V;
+            float m8 = dl[0];
+            for (int i = 1; i < 8; ++i) m8 = dl[i] > m8 ? dl[i] : m8;
+            for (int i = 8; i < D; ++i) need(dl[i] < m8, "D > 8: the duration argmax must stay below index 8");
+        }
+        for (int b = 0; b < B; ++b) {
+            need(d->t[b] >= 0 && d->steps[b] >= 0 && d->n_out[b] >= 0 && d->nsym[b] >= 0, "state words must not be negative");
+            need(!d->Tb || d->Tb[b] >= 1, "Tb");
+        }
+        if (pred) {
+            need(d->pp && d->ep && d->z && J >= 1 && d->ep_rows > 0, "need: pp/ep/z/J/ep_rows");
+            need((size_t)d->z_words >= (d->h_bf16 ? ((size_t)B * J + 1) / 2 : (size_t)B * F * J), "z_words");
+            need(d->h_bf16 || J % 16 == 0, "fp32 z: J must be a multiple of 16 (sigma layout)");
+            for (int b = 0; b < B; ++b) {
+                const int64_t r0 = d->row0 ? (int64_t)d->row0[b] : (int64_t)b * d->T;
+                need(r0 >= 0 && r0 + (d->Tb ? d->Tb[b] : d->T) <= d->ep_rows, "need: enc_proj rows out of range");
+            }
+        }
+        int n_edges = 0;
+        if (boost) {
+            need(d->trie_tok && d->trie_node && d->act && d->n_act && d->trie_nodes >= 1 && d->trie_off[0] == 0, "trie");
+            for (int i = 0; i < d->trie_nodes; ++i) need(d->trie_off[i + 1] >= d->trie_off[i], "trie: offsets must not decrease");
+            n_edges = d->trie_off[d->trie_nodes];
+            for (int e = 0; e < n_edges; ++e) need(d->trie_node[e] >= 0 && d->trie_node[e] < d->trie_nodes, "trie: child node out of range");
+            for (int b = 0; b < B; ++b) {
+                need(d->n_act[b] >= 0 && d->n_act[b] <= kTrieMaxActive, "trie: n_act");
+                for (int a = 0; a < d->n_act[b]; ++a) {
+                    const int sn = d->act[(size_t)b * kTrieMaxActive + a];
+                    need(sn >= 0 && sn < d->trie_nodes, "trie: active state out of range");
+                }
+            }
+        }
+        int64_t n_force_el = 0;
+        if (score) {
+            need(D >= 1 && D <= 8 && d->force_dur && d->force_stride >= 0, "forced path: 1 <= D <= 8, force_dur, force_stride");
+            for (int b = 0; b < B; ++b) {
+                const int nf = d->n_force_b ? d->n_force_b[b] : d->n_force;
+                if (nf <= 0) continue;
+                n_force_el = std::max(n_force_el, (int64_t)b * d->force_stride + nf);
+                need(d->done[b] || d->steps[b] < nf, "forced path: steps past the path");
+            }
+            need(n_force_el <= d->force_len, "force_len");
+            for (int64_t k = 0; k < d->force_len; ++k)
+                need(d->force_label[k] >= 0 && d->force_label[k] < V && d->force_dur[k] >= 0 && d->force_dur[k] < D, "forced label / duration out of range");
+            need((!d->score_lab && !d->score_dur) || d->score_rows >= n_force_el, "score_rows");
+        }
+        need_device();
+        const size_t nb = (size_t)rows * 4, ntok = (size_t)rows * mt * 4;
+        DevBuf lg, hn, cn, h, c, t, steps, n_out, nsym, done, token, lens, dc, ids, start, end, conf, margin, nd, pp, ep, z, Tb, row0, toff, ttok, tnode, act, nact, fl, fd,
+            nfb, sl, sd;
+        const size_t hn_step = n_h * 4, cn_step = n_c * 4, lg_step = (size_t)B * F * VD * 4;
+        up(lg, d->logits, lg_step * d->n_steps); up(hn, d->hn, hn_step * d->n_steps); up(cn, d->cn, cn_step * d->n_steps);
+        up(h, d->h, (size_t)d->h_words * 4); up(c, d->c, (size_t)d->c_words * 4);
+        up(t, d->t, nb); up(steps, d->steps, nb); up(n_out, d->n_out, nb); up(nsym, d->nsym, nb); up(done, d->done, nb); up(token, d->token, nb); up(lens, d->lens, nb);
+        up(dc, d->done_count, 4);
+        up(ids, d->ids, ntok); up(start, d->start, ntok); up(end, d->end, ntok); up(conf, d->conf, ntok);
+        st.h = h.as<float>(); st.c = c.as<float>();
+        st.token = token.as<int>(); st.t = t.as<int>(); st.nsym = nsym.as<int>(); st.n_out = n_out.as<int>(); st.steps = steps.as<int>(); st.done = done.as<int>();
+        st.lens = lens.as<int>(); st.done_count = dc.as<int>(); st.ids = ids.as<int>(); st.start = start.as<int>(); st.end = end.as<int>(); st.conf = conf.as<float>();
+        if (d->margin) { up(margin, d->margin, nb); st.margin = margin.as<float>(); }
+        st.need = nullptr; st.trie = TrieDev{}; st.force_label = nullptr;
+        if (pred) {
+            up(nd, d->need, nb); up(pp, d->pp, (size_t)B * J * 4); up(ep, d->ep, (size_t)d->ep_rows * J * 4); up(z, d->z, (size_t)d->z_words * 4);
+            st.need = nd.as<int>(); st.pp = pp.as<float>(); st.ep = ep.as<float>(); st.z = z.as<float>();
+        }
+        if (d->Tb) { up(Tb, d->Tb, (size_t)B * 4); st.Tb = Tb.as<int>(); }
+        if (d->row0) { up(row0, d->row0, (size_t)B * 4); st.row0 = row0.as<int>(); }
+        if (boost) {
+            up(toff, d->trie_off, (size_t)(d->trie_nodes + 1) * 4); up(ttok, d->trie_tok, (size_t)std::max(n_edges, 1) * 4); up(tnode, d->trie_node, (size_t)std::max(n_edges, 1) * 4);
+            up(act, d->act, (size_t)rows * kTrieMaxActive * 4); up(nact, d->n_act, nb);
+            st.trie = TrieDev{toff.as<int>(), ttok.as<int>(), tnode.as<int>(), d->trie_nodes, d->boost, act.as<int>(), nact.as<int>()};
+        }
+        if (score) {
+            up(fl, d->force_label, (size_t)std::max<int64_t>(d->force_len, 1) * 4); up(fd, d->force_dur, (size_t)std::max<int64_t>(d->force_len, 1) * 4);
+            st.force_label = fl.as<int>(); st.force_dur = fd.as<int>(); st.n_force = d->n_force; st.force_stride = d->force_stride;
+            if (d->n_force_b) { up(nfb, d->n_force_b, (size_t)B * 4); st.n_force_b = nfb.as<int>(); }
+            if (d->score_lab) { up(sl, d->score_lab, (size_t)d->score_rows * V * 4); st.score_lab = sl.as<float>(); }
+            if (d->score_dur) { up(sd, d->score_dur, (size_t)d->score_rows * D * 4); st.score_dur = sd.as<float>(); }
+        }
+        for (int k = 0; k < d->n_steps; ++k) {
+            st.logits = reinterpret_cast<const float *>(static_cast<const char *>(lg.p) + lg_step * k);
+            st.hn = reinterpret_cast<const float *>(static_cast<const char *>(hn.p) + hn_step * k);
+            st.cn = reinterpret_cast<const float *>(static_cast<const char *>(cn.p) + cn_step * k);
+            launch_tdt_decide(st, nullptr);
+        }
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(d->h, h, (size_t)d->h_words * 4); down(d->c, c, (size_t)d->c_words * 4);
+        down(d->t, t, nb); down(d->steps, steps, nb); down(d->n_out, n_out, nb); down(d->nsym, nsym, nb); down(d->done, done, nb); down(d->token, token, nb);
+        down(d->lens, lens, nb); down(d->done_count, dc, 4);
+        down(d->ids, ids, ntok); down(d->start, start, ntok); down(d->end, end, ntok); down(d->conf, conf, ntok);
+        if (d->margin) down(d->margin, margin, nb);
+        if (pred) { down(d->need, nd, nb); down(d->z, z, (size_t)d->z_words * 4); }
+        if (boost) { down(d->act, act, (size_t)rows * kTrieMaxActive * 4); down(d->n_act, nact, nb); }
+        if (score && d->score_lab) down(d->score_lab, sl, (size_t)d->score_rows * V * 4);
+        if (score && d->score_dur) down(d->score_dur, sd, (size_t)d->score_rows * D * 4);
+        constexpr int kForm = (int)tdt_decide_form_of(TDT_K_SCORE, TDT_NC6, TDT_ROW_BATCH8);
+        static_assert(PK_DIAG_TDT_KERNEL(kForm) == TDT_K_SCORE && PK_DIAG_TDT_SLOTS(kForm) == 6 && PK_DIAG_TDT_ROW(kForm) == TDT_ROW_BATCH8, "form fields");
+        if (form) *form = (int)tdt_decide_form(st);
+    });
+}
+
+pk_status pk_diag_ctc_greedy(const pk_ctc_greedy_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const int B = d->B, T = d->T, n = d->n, ld = d->ld, rows_out = d->out_rows, pitch = d->pitch;
+        need(d->logits && d->lp && d->best_idx && d->best_lp && d->best_idx2 && d->best_lp2, "logits/lp/best_idx/best_lp/best_idx2/best_lp2");
+        need(d->ids && d->lens && d->start && d->end && d->conf, "token arrays");
+        need(B > 0 && n >= 1 && ld >= n && d->blank >= 0 && d->blank < n && rows_out >= B, "B/n/ld/blank/out_rows");
+        int64_t rows = 0;
+        int tmax = 0;
+        std::vector<int32_t> img;                                      // SeqRag::T [B] then T_off [B + 1]
+        if (d->n_frames) {
+            img.assign(d->n_frames, d->n_frames + B);
+            img.push_back(0);
+            for (int b = 0; b < B; ++b) { need(d->n_frames[b] >= 1, "n_frames"); tmax = std::max(tmax, (int)d->n_frames[b]); rows += d->n_frames[b]; img.push_back((int32_t)rows); }
+        } else {
+            need(T >= 1, "T");
+            rows = (int64_t)B * T; tmax = T;
+        }
+        need(pitch >= tmax, "pitch >= the longest utterance");
+        need(d->lp_rows >= rows, "lp_rows >= the frames of the batch");
+        const bool boost = d->trie_off != nullptr;
+        int n_edges = 0;
+        if (boost) {
+            need(d->trie_tok && d->trie_node && d->trie_nodes >= 1 && d->trie_off[0] == 0, "trie");
+            for (int i = 0; i < d->trie_nodes; ++i) need(d->trie_off[i + 1] >= d->trie_off[i], "trie: offsets must not decrease");
+            n_edges = d->trie_off[d->trie_nodes];
+            for (int e = 0; e < n_edges; ++e) need(d->trie_node[e] >= 0 && d->trie_node[e] < d->trie_nodes, "trie: child node out of range");
+        }
+        need_device();
+        DevBuf lg, lp, bi, bl, bi2, bl2, ids, lens, start, end, conf, rimg, toff, ttok, tnode;
+        const size_t nl = (size_t)d->lp_rows, ntok = (size_t)rows_out * pitch * 4;
+        up(lg, d->logits, (size_t)rows * ld * 4);
+        up(lp, d->lp, nl * n * 4); up(bi, d->best_idx, nl * 4); up(bl, d->best_lp, nl * 4); up(bi2, d->best_idx2, nl * 4); up(bl2, d->best_lp2, nl * 4);
+        up(ids, d->ids, ntok); up(start, d->start, ntok); up(end, d->end, ntok); up(conf, d->conf, ntok); up(lens, d->lens, (size_t)rows_out * 4);
+        SeqRag rag;
+        if (d->n_frames) {
+            up(rimg, img.data(), img.size() * 4);
+            rag.T = rimg.as<int>(); rag.T_off = rimg.as<int>() + B; rag.T_max = tmax;
+        }
+        launch_logsoftmax_argmax(lg.as<float>(), rows, ld, n, nullptr, bi2.as<int>(), bl2.as<float>(), nullptr);      // without the log-prob rows ...
+        launch_logsoftmax_argmax(lg.as<float>(), rows, ld, n, lp.as<float>(), bi.as<int>(), bl.as<float>(), nullptr);  // ... and with them
+        if (boost) {
+            up(toff, d->trie_off, (size_t)(d->trie_nodes + 1) * 4); up(ttok, d->trie_tok, (size_t)std::max(n_edges, 1) * 4); up(tnode, d->trie_node, (size_t)std::max(n_edges, 1) * 4);
+            const TrieDev trie{toff.as<int>(), ttok.as<int>(), tnode.as<int>(), d->trie_nodes, d->boost, nullptr, nullptr};
+            launch_ctc_boosted(lp.as<float>(), B, T, n, d->blank, trie, ids.as<int>(), lens.as<int>(), start.as<int>(), end.as<int>(), conf.as<float>(), nullptr, pitch, rag);
+        } else {
+            launch_ctc_collapse(bi.as<int>(), bl.as<float>(), B, T, d->blank, ids.as<int>(), lens.as<int>(), start.as<int>(), end.as<int>(), conf.as<float>(), nullptr, pitch, rag);
+        }
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(d->lp, lp, nl * n * 4); down(d->best_idx, bi, nl * 4); down(d->best_lp, bl, nl * 4); down(d->best_idx2, bi2, nl * 4); down(d->best_lp2, bl2, nl * 4);
+        down(d->ids, ids, ntok); down(d->start, start, ntok); down(d->end, end, ntok); down(d->conf, conf, ntok); down(d->lens, lens, (size_t)rows_out * 4);
+    });
+}
+
 pk_status pk_diag_layernorm(const float *x, int64_t rows, int d, const float *gamma, const float *beta, float eps, float *y) {
     return guard([&] {
         need(x && gamma && beta && y && rows > 0 && d > 0 && d <= 1024, "x/gamma/beta/y/rows/d (d <= 1024)");

@@ -223,24 +223,46 @@ __global__ __launch_bounds__(256) void tdt_decide_kernel(TdtState st) {
     extern __shared__ __attribute__((aligned(16))) float sm[];     // x[V+D], e[V+D], scratch[16] (+ BOOST: mask, active sets)
     tdt_decide_one<BOOST, false, SCORE, FAST, NC>(st, blockIdx.x, sm);
 }
+TdtDecideForm tdt_decide_form(const TdtState &st) {
+    const int VD = st.V + st.D, n_state = st.L * st.Hp;
+    const int kernel = st.trie.off ? TDT_K_BOOST : st.force_label ? TDT_K_SCORE                          // (force_label: pk_tdt_score)
+                       : (st.h_bf16 && VD <= 33 * 256 && st.V >= 2) ? TDT_K_FAST : TDT_K_EXACT;        // the tolerance-class mode's plain greedy step on the register-resident form (decode_dev.hpp: FAST)
+    const int slots = (kernel == TDT_K_BOOST || kernel == TDT_K_SCORE) ? TDT_NC12 : n_state <= 3 * 256 ? TDT_NC3 : n_state <= 6 * 256 ? TDT_NC6 : TDT_NC12;
+    const int row = (kernel == TDT_K_EXACT && st.F > 1) ? TDT_ROW_WINDOW : VD <= 5 * 256 ? TDT_ROW_5 : VD <= 33 * 256 ? TDT_ROW_33 : TDT_ROW_BATCH8;
+    return tdt_decide_form_of(kernel, slots, row);
+}
+size_t tdt_decide_lds_bytes(const TdtState &st) {
+    size_t lds = (size_t)(((st.F > 1 ? st.F : 1) + 1) * (st.V + st.D) + 16) * sizeof(float);           // (frame window: its F rows in front of the scratch)
+    if (st.trie.off) lds += (size_t)((st.V + 31) / 32 + 2 * kTrieMaxActive + 1) * sizeof(int);
+    return lds;
+}
+bool tdt_decide_launchable(const TdtState &st) {
+    if (st.L * st.Hp > kTdtMaxState) return false;
+    return st.F <= 1 || !(st.V + st.D > 5 * 256 || st.F > kDecWindowMax || st.trie.off || st.force_label || st.h_bf16 || (st.need && st.J > kTdtWindowMaxJ));
+}
+// A vocabulary of 8193 + 5 durations already takes 65 648 bytes: past 64 KB the kernel's limit is raised like every other launcher's.
+template <bool BOOST, bool SCORE, bool FAST, int NC>
+static void launch_tdt_decide_inst(const TdtState &st, size_t lds, hipStream_t s) {
+    static DynLdsSlots slots;
+    if (lds > 64 * 1024) ensure_dyn_lds(slots, reinterpret_cast<const void *>(&tdt_decide_kernel<BOOST, SCORE, FAST, NC>), lds);
+    hipLaunchKernelGGL((tdt_decide_kernel<BOOST, SCORE, FAST, NC>), dim3(st.B), dim3(256), lds, s, st);
+}
 void launch_tdt_decide(const TdtState &st, hipStream_t s) {
-    const size_t lds = (size_t)(((st.F > 1 ? st.F : 1) + 1) * (st.V + st.D) + 16) * sizeof(float);     // (frame window: its F rows in front of the scratch)
-    if (st.F > 1 && (st.V + st.D > 5 * 256 || st.F > kDecWindowMax || st.trie.off || st.force_label || st.h_bf16)) {
-        fprintf(stderr, "parakeet_amd: decode window outside its conditions -- engine bug\n"); abort();
+    if (!tdt_decide_launchable(st)) {
+        fprintf(stderr, "parakeet_amd: decode window outside its conditions, or L * Hp > %d -- engine bug\n", kTdtMaxState); abort();
     }
-    if (st.trie.off) {
-        const size_t extra = (size_t)((st.V + 31) / 32 + 2 * kTrieMaxActive + 1) * sizeof(int);
-        hipLaunchKernelGGL(tdt_decide_kernel<true>, dim3(st.B), dim3(256), lds + extra, s, st);
-    } else if (st.force_label) {
-        hipLaunchKernelGGL((tdt_decide_kernel<false, true>), dim3(st.B), dim3(256), lds, s, st);      // pk_tdt_score
-    } else if (st.h_bf16 && st.V + st.D <= 33 * 256 && st.V >= 2) {         // the tolerance-class mode's plain greedy step on the register-resident form (decode_dev.hpp: FAST)
-        if (st.L * st.Hp <= 3 * 256) hipLaunchKernelGGL((tdt_decide_kernel<false, false, true, 3>), dim3(st.B), dim3(256), lds, s, st);
-        else if (st.L * st.Hp <= 6 * 256) hipLaunchKernelGGL((tdt_decide_kernel<false, false, true, 6>), dim3(st.B), dim3(256), lds, s, st);
-        else hipLaunchKernelGGL((tdt_decide_kernel<false, false, true>), dim3(st.B), dim3(256), lds, s, st);
-    } else {
-        if (st.L * st.Hp <= 3 * 256) hipLaunchKernelGGL((tdt_decide_kernel<false, false, false, 3>), dim3(st.B), dim3(256), lds, s, st);
-        else if (st.L * st.Hp <= 6 * 256) hipLaunchKernelGGL((tdt_decide_kernel<false, false, false, 6>), dim3(st.B), dim3(256), lds, s, st);
-        else hipLaunchKernelGGL(tdt_decide_kernel<false>, dim3(st.B), dim3(256), lds, s, st);
+    const size_t lds = tdt_decide_lds_bytes(st);
+    const TdtDecideForm form = tdt_decide_form(st);
+    switch (form >> 2) {                                             // (kernel, slots): the row path is the kernel's own branch on the same sizes
+    case tdt_decide_form_of(TDT_K_BOOST, TDT_NC12, 0) >> 2: launch_tdt_decide_inst<true, false, false, 12>(st, lds, s); break;
+    case tdt_decide_form_of(TDT_K_SCORE, TDT_NC12, 0) >> 2: launch_tdt_decide_inst<false, true, false, 12>(st, lds, s); break;
+    case tdt_decide_form_of(TDT_K_FAST, TDT_NC3, 0) >> 2: launch_tdt_decide_inst<false, false, true, 3>(st, lds, s); break;
+    case tdt_decide_form_of(TDT_K_FAST, TDT_NC6, 0) >> 2: launch_tdt_decide_inst<false, false, true, 6>(st, lds, s); break;
+    case tdt_decide_form_of(TDT_K_FAST, TDT_NC12, 0) >> 2: launch_tdt_decide_inst<false, false, true, 12>(st, lds, s); break;
+    case tdt_decide_form_of(TDT_K_EXACT, TDT_NC3, 0) >> 2: launch_tdt_decide_inst<false, false, false, 3>(st, lds, s); break;
+    case tdt_decide_form_of(TDT_K_EXACT, TDT_NC6, 0) >> 2: launch_tdt_decide_inst<false, false, false, 6>(st, lds, s); break;
+    case tdt_decide_form_of(TDT_K_EXACT, TDT_NC12, 0) >> 2: launch_tdt_decide_inst<false, false, false, 12>(st, lds, s); break;
+    default: fprintf(stderr, "parakeet_amd: no decision kernel for form %d -- engine bug\n", (int)form); abort();
     }
 }
 

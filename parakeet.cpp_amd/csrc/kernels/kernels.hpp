@@ -374,6 +374,20 @@ void launch_lstm_cell(const float *gi, int gi_ld, const int *gi_row, const float
                       float *cn, hipStream_t s);
 void launch_joint_act(const float *ep, const int *t, int T, int J, const float *pp, const float *bp, int B, float *z, hipStream_t s);
 void launch_tdt_decide(const TdtState &st, hipStream_t s);
+// The form of a decision launch, by the function the launcher switches on: value = kernel * 16 + slots * 4 + row.
+//   kernel: tdt_decide_kernel's instantiation -- the exact greedy step, the register-resident step of the tolerance-class mode (h_bf16), phrase boosting, forced scoring
+//   slots:  NC, the 256-element slots of candidate LSTM state a thread carries: 3 / 6 / 12 by L * Hp (boost and score: always 12)
+//   row:    how the logits row reaches the workgroup: 5 or 33 register slots per thread by V + D (fast: its NQ), batches of 8 above 33 x 256, or the frame window (F > 1)
+enum TdtDecideKernel { TDT_K_EXACT = 0, TDT_K_FAST = 1, TDT_K_BOOST = 2, TDT_K_SCORE = 3 };
+enum TdtDecideSlots { TDT_NC3 = 0, TDT_NC6 = 1, TDT_NC12 = 2 };
+enum TdtDecideRow { TDT_ROW_5 = 0, TDT_ROW_33 = 1, TDT_ROW_BATCH8 = 2, TDT_ROW_WINDOW = 3 };
+enum TdtDecideForm : int {};
+constexpr TdtDecideForm tdt_decide_form_of(int kernel, int slots, int row) { return (TdtDecideForm)(kernel * 16 + slots * 4 + row); }
+constexpr int kTdtMaxState = 12 * 256;       // L * Hp the decision kernel can carry
+constexpr int kTdtWindowMaxJ = 4 * 256;      // J up to which the decision kernel forms every z row of the next window
+TdtDecideForm tdt_decide_form(const TdtState &st);
+size_t tdt_decide_lds_bytes(const TdtState &st);
+bool tdt_decide_launchable(const TdtState &st);   // false: launch_tdt_decide would abort (a window outside its conditions, L * Hp > kTdtMaxState)
 
 // skinny products of the decode loop (kernels/decode_gemv.hip).  X and W are in the "sigma" K layout
 // (4x4 index transpose inside every block of 16 k); K % 16 == 0.

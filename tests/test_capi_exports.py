@@ -71,6 +71,14 @@ def test_no_gpu_is_a_loud_error(tmp_path):
     assert e.value.code == -4
     with pytest.raises(capi.PkError):
         capi.diag_math("exp", [0.0])
+    import tdt_decide_ref as R                        # the decision-kernel diagnostics: valid arguments, no device
+    o = R.make_case(R.CASES[0])
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_tdt_decide(o["sc"], o["logits"], o["hn"], o["cn"], o["st"])
+    assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_ctc_greedy(np.zeros((4, 9), np.float32), 9, 8, B=1, T=4)
+    assert e.value.code == -4
     with pytest.raises(capi.PkError) as e:             # the multi-GPU entry point as well
         capi.Group(str(wp), cfg)
     assert e.value.code == -4
