@@ -704,6 +704,56 @@ typedef struct pk_ctc_greedy_diag {
     const int32_t *trie_off, *trie_tok, *trie_node; int32_t trie_nodes; float boost;
 } pk_ctc_greedy_diag;
 pk_status pk_diag_ctc_greedy(const pk_ctc_greedy_diag *a);
+/* ONE product of the fp32 small-M GEMM family alone (kernels/gemm_smallm.hip; kernels.hpp GemmArgs), staged and launched as the engine launches it:
+ * out = epi(X W^T + bias), M <= 1536, K % 64 == 0; epi 0 none / 1 relu / 2 silu / 3 out = resid + alpha * (..) / 4 glu (W [2N][K], bias [2N]).
+ * Every operand is given in its NATURAL layout: A [M][lda] (lda >= K), W [N][K], bias, resid [M][N].
+ *   w_sig:   a copy of W in the kernel's tiled load order is built on the device (launch_sigma_copy; N % 16 == 0) and handed over as GemmArgs::W_sig.
+ *   a_sigma: the rows of A reach the product with their K axis in the sigma order (GemmArgs::a_sigma): written so by the LayerNorm in front (ln_g set,
+ *            fused = 0: launch_layernorm mode 2, with pre_g launch_layernorm2), else permuted at upload.
+ *   sigma_cols (a multiple of 16, <= N): the output columns below it are written in the sigma order.  remap_rows > 0: the output offset of (row, col) is
+ *            (row / remap_rows) remap_gs + (row % remap_rows) remap_rs + col remap_cs instead of row ldo + col.
+ *   ln_g / ln_b / eps: X = LayerNorm(A).  fused = 1: folded into the product (gemm_smallm_ln_kernel; needs w_sig, K = 512 / 1024; a_sigma is ignored);
+ *            fused = 0: the separate LayerNorm launch, then the product on its rows.
+ *   pre_g / pre_b (with ln_g; epi silu): X = LN(LN(A; pre); ln), pre_out [M][K] receives LN(A; pre).  fused = 0: launch_layernorm2, then the product.
+ *   dw (with ln_g; epi glu; N = K = d; rows = [M / dw_c streams][dw_c frames]): the streaming conv module's depthwise conv (kernel 9) + BatchNorm + SiLU over
+ *            [cache_in ; GLU rows] of every stream (kernels.hpp DwTail): out receives the activations (dw_out_sigma: columns in the sigma order), cache_out
+ *            the streams' new caches.  cache_in [M / dw_c][8][d], cache_out [cache_streams >= M / dw_c][8][d], dw_w [9][d], the five vectors [d].
+ *            fused = 0: LayerNorm, the GLU product, then launch_stream_dwconv.
+ * out (out_words floats: every offset the product may write lies inside), cache_out and pre_out come back WHOLE and exactly as the launches left them --
+ * permuted columns stay permuted --; their device buffers are filled with the pattern 0x7FC5A5A5 before the first launch.
+ * form receives the form of the product launch, by the function the launcher switches on (kernels.hpp gemm_smallm_form): PK_DIAG_SMALLM_KERNEL 0 chain /
+ * 1 two row tiles per wave / 2 LayerNorm folded in, PK_DIAG_SMALLM_EPI, PK_DIAG_SMALLM_RING the ring depth 8 / 2 / 1 (two row tiles: 4; folded: K / 64),
+ * PK_DIAG_SMALLM_SIG / _DW / _PRE.  pk_diag_gemm_smallm_forms lists every form the launcher can take (host arithmetic; returns their number, writes at most cap).
+ * PK_ERR_UNSUPPORTED, and nothing is launched, for what the engine refuses: a_sigma without w_sig (or N % 16 != 0), a folded norm / second norm / conv tail
+ * outside gemm_smallm_ln_applies / gemm_smallm_pre_applies / gemm_smallm_dw_applies. */
+#define PK_DIAG_SMALLM_KERNEL(form) ((form) >> 12)
+#define PK_DIAG_SMALLM_EPI(form) (((form) >> 9) & 7)
+#define PK_DIAG_SMALLM_RING(form) (((form) >> 3) & 63)
+#define PK_DIAG_SMALLM_SIG(form) (((form) >> 2) & 1)
+#define PK_DIAG_SMALLM_DW(form) (((form) >> 1) & 1)
+#define PK_DIAG_SMALLM_PRE(form) ((form) & 1)
+typedef struct pk_smallm_gemm_diag {
+    int32_t M, N, K, epi, w_sig, a_sigma, sigma_cols, fused;
+    const float *A; int64_t lda;
+    const float *W, *bias, *resid; float alpha;
+    int32_t remap_rows; int64_t remap_gs, remap_rs, remap_cs;
+    const float *ln_g, *ln_b; float eps;
+    const float *pre_g, *pre_b; float *pre_out;
+    int32_t dw, dw_c, dw_has_cache, dw_out_sigma, cache_streams;
+    const float *cache_in; float *cache_out;
+    const float *dw_w, *dw_bias, *bn_mean, *bn_rstd, *bn_g, *bn_b;
+    int64_t ldo, out_words; float *out;
+    int32_t form;
+} pk_smallm_gemm_diag;
+pk_status pk_diag_gemm_smallm(pk_smallm_gemm_diag *a);
+int pk_diag_gemm_smallm_forms(int32_t *out, int cap);
+/* The layouts those products read, alone: the tiled weight copy dst [rows K] of src [rows][ld] (launch_sigma_copy; rows % 16 == 0, K % 64 == 0, ld >= K);
+ * LayerNorm with the output columns in the sigma order (launch_layernorm mode 2); and y1 = LN(x; g1, b1), y2 = LN(y1; g2, b2) in one pass with y2_sigma != 0:
+ * y2's columns in the sigma order (launch_layernorm2).  d <= 1024, a multiple of 16. */
+pk_status pk_diag_sigma_copy(const float *src, int64_t rows, int K, int64_t ld, float *dst);
+pk_status pk_diag_layernorm_sigma(const float *x, int64_t rows, int d, const float *gamma, const float *beta, float eps, float *y);
+pk_status pk_diag_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
+                             int y2_sigma, float *y1, float *y2);
 
 #ifdef __cplusplus
 }

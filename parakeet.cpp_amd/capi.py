@@ -952,6 +952,116 @@ def diag_stream_attention(qkv_new, kcache, vcache, nc, pos, bias_u, bias_v, n_he
     return ctx, ko, vo, STREAM_ATT_FORMS[form.value]
 
 
+class PkSmallmGemmDiag(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("M", "N", "K", "epi", "w_sig", "a_sigma", "sigma_cols", "fused")]
+                + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("bias", f32p), ("resid", f32p), ("alpha", C.c_float),
+                   ("remap_rows", C.c_int32), ("remap_gs", C.c_int64), ("remap_rs", C.c_int64), ("remap_cs", C.c_int64),
+                   ("ln_g", f32p), ("ln_b", f32p), ("eps", C.c_float), ("pre_g", f32p), ("pre_b", f32p), ("pre_out", f32p)]
+                + [(k, C.c_int32) for k in ("dw", "dw_c", "dw_has_cache", "dw_out_sigma", "cache_streams")]
+                + [("cache_in", f32p), ("cache_out", f32p)]
+                + [(k, f32p) for k in ("dw_w", "dw_bias", "bn_mean", "bn_rstd", "bn_g", "bn_b")]
+                + [("ldo", C.c_int64), ("out_words", C.c_int64), ("out", f32p), ("form", C.c_int32)])
+
+
+SMALLM_KERNELS = ("chain", "rt2", "ln")
+
+
+def smallm_form(v):
+    """A GemmSmallmForm value (kernels.hpp; PK_DIAG_SMALLM_*) -> (kernel, epi, ring depth or K / 64, sig, dw, pre)"""
+    epi = {n: k for k, n in EPI.items()}[(v >> 9) & 7]
+    return SMALLM_KERNELS[v >> 12], epi, (v >> 3) & 63, bool(v & 4), bool(v & 2), bool(v & 1)
+
+
+def diag_gemm_smallm_forms():
+    """pk_diag_gemm_smallm_forms: every form launch_gemm_smallm can take, as smallm_form tuples.  Host arithmetic."""
+    n = lib().pk_diag_gemm_smallm_forms(None, 0)
+    out = np.zeros(n, np.int32)
+    lib().pk_diag_gemm_smallm_forms(_i(out), n)
+    return [smallm_form(int(v)) for v in out]
+
+
+def diag_gemm_smallm(A, W, bias=None, epi="none", resid=None, alpha=1.0, w_sig=False, a_sigma=False, sigma_cols=0, remap=None, ldo=None, out_words=None,
+                     ln=None, pre=None, eps=1e-5, dw=None, fused=True, lda_cols=None):
+    """pk_diag_gemm_smallm: one product of the fp32 small-M family alone (include/parakeet_amd.h).  A [M][lda >= K] (K = lda_cols or A's width), W natural;
+    remap = (rows, gs, rs, cs); ln = (gamma, beta); pre = (gamma, beta); dw = dict(c, has_cache, out_sigma, cache_in [S][8][d], cache_streams, w [9][d], bias,
+    bn_mean, bn_rstd, bn_g, bn_b).  Returns dict(out = the WHOLE output buffer as uint32 words [out_words] exactly as the launches left it (SKINNY_FILL32
+    where nothing was stored), form = smallm_form tuple, pre_out [M][K] words, cache_out [cache_streams][8][d] words)."""
+    A, W = _c(A), _c(W)
+    M, lda = A.shape
+    K = int(lda_cols) if lda_cols is not None else lda
+    N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
+    assert W.shape[1] == K
+    keep = [A, W]
+
+    def opt(a):
+        if a is None:
+            return None
+        a = _c(a)
+        keep.append(a)
+        return _f(a)
+
+    d = PkSmallmGemmDiag()
+    d.M, d.N, d.K, d.epi, d.w_sig, d.a_sigma, d.sigma_cols, d.fused = M, N, K, EPI[epi], int(bool(w_sig)), int(bool(a_sigma)), int(sigma_cols), int(bool(fused))
+    d.A, d.lda, d.W, d.bias, d.resid, d.alpha = _f(A), lda, _f(W), opt(bias), opt(resid), alpha
+    if remap is not None:
+        d.remap_rows, d.remap_gs, d.remap_rs, d.remap_cs = (int(v) for v in remap)
+    d.eps = eps
+    if ln is not None:
+        d.ln_g, d.ln_b = opt(ln[0]), opt(ln[1])
+    pre_out = None
+    if pre is not None:
+        pre_out = np.zeros((M, K), np.uint32)
+        d.pre_g, d.pre_b, d.pre_out = opt(pre[0]), opt(pre[1]), pre_out.ctypes.data_as(f32p)
+    cache_out = None
+    if dw is not None:
+        ns = int(dw.get("cache_streams", M // dw["c"]))
+        cache_out = np.zeros((ns, 8, N), np.uint32)
+        d.dw, d.dw_c, d.dw_has_cache, d.dw_out_sigma, d.cache_streams = 1, int(dw["c"]), int(bool(dw["has_cache"])), int(bool(dw.get("out_sigma"))), ns
+        d.cache_in, d.cache_out = opt(dw["cache_in"]), cache_out.ctypes.data_as(f32p)
+        d.dw_w, d.dw_bias, d.bn_mean, d.bn_rstd, d.bn_g, d.bn_b = (opt(dw[k]) for k in ("w", "bias", "bn_mean", "bn_rstd", "bn_g", "bn_b"))
+    d.ldo = int(ldo) if ldo is not None else N
+    d.out_words = int(out_words) if out_words is not None else M * d.ldo
+    out = np.zeros(d.out_words, np.uint32)
+    d.out = out.ctypes.data_as(f32p)
+    d.form = -1
+    L = lib()
+    L.pk_diag_gemm_smallm.argtypes = [C.POINTER(PkSmallmGemmDiag)]
+    check(L.pk_diag_gemm_smallm(C.byref(d)))
+    return dict(out=out, form=smallm_form(d.form), pre_out=pre_out, cache_out=cache_out)
+
+
+def diag_sigma_copy(src, K=None):
+    """pk_diag_sigma_copy: src [rows][ld >= K] -> the rows x K floats of the W_sig tiling (launch_sigma_copy)."""
+    src = _c(src)
+    rows, ld = src.shape
+    K = ld if K is None else int(K)
+    dst = np.empty(rows * K, np.float32)
+    L = lib()
+    L.pk_diag_sigma_copy.argtypes = [f32p, C.c_int64, C.c_int, C.c_int64, f32p]
+    check(L.pk_diag_sigma_copy(_f(src), rows, K, ld, _f(dst)))
+    return dst
+
+
+def diag_layernorm_sigma(x, g, b, eps=1e-5):
+    """pk_diag_layernorm_sigma: launch_layernorm mode 2 -- LayerNorm with the output columns in the sigma order."""
+    x, g, b = _c(x), _c(g), _c(b)
+    y = np.empty_like(x)
+    L = lib()
+    L.pk_diag_layernorm_sigma.argtypes = [f32p, C.c_int64, C.c_int, f32p, f32p, C.c_float, f32p]
+    check(L.pk_diag_layernorm_sigma(_f(x), x.shape[0], x.shape[1], _f(g), _f(b), eps, _f(y)))
+    return y
+
+
+def diag_layernorm2(x, g1, b1, g2, b2, y2_sigma=False, eps=1e-5):
+    """pk_diag_layernorm2: (y1 = LN(x; g1, b1), y2 = LN(y1; g2, b2)) in one launch; y2_sigma: y2's columns in the sigma order."""
+    x, g1, b1, g2, b2 = (_c(v) for v in (x, g1, b1, g2, b2))
+    y1, y2 = np.empty_like(x), np.empty_like(x)
+    L = lib()
+    L.pk_diag_layernorm2.argtypes = [f32p, C.c_int64, C.c_int] + [f32p] * 4 + [C.c_float, C.c_int, f32p, f32p]
+    check(L.pk_diag_layernorm2(_f(x), x.shape[0], x.shape[1], _f(g1), _f(b1), _f(g2), _f(b2), eps, int(bool(y2_sigma)), _f(y1), _f(y2)))
+    return y1, y2
+
+
 class Batch:
     """pk_batch: the resident pipeline (clips of one length stay in HBM; decode(k) overlaps encoder(k+1))."""
 

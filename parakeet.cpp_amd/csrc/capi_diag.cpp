@@ -538,6 +538,185 @@ pk_status pk_diag_layernorm(const float *x, int64_t rows, int d, const float *ga
     });
 }
 
+static void diag_layernorm(const float *x, int64_t rows, int d, const float *gamma, const float *beta, float eps, float *y, int mode) {
+    need(x && gamma && beta && y && rows > 0 && d > 0 && d <= 1024, "x/gamma/beta/y/rows/d (d <= 1024)");
+    need(mode == 0 || d % 16 == 0, "sigma columns: d must be a multiple of 16");
+    need_device();
+    DevBuf xb, gb, yb;
+    up(xb, x, (size_t)rows * d * 4);
+    up_rows(gb, {gamma, beta}, d);
+    yb.reserve((size_t)rows * d * 4);
+    launch_layernorm(xb.as<float>(), rows, d, gb.as<float>(), gb.as<float>() + d, eps, yb.as<float>(), nullptr, mode);
+    PK_CHECK_LAUNCH();
+    down(y, yb, (size_t)rows * d * 4);
+}
+
+pk_status pk_diag_layernorm_sigma(const float *x, int64_t rows, int d, const float *gamma, const float *beta, float eps, float *y) {
+    return guard([&] { diag_layernorm(x, rows, d, gamma, beta, eps, y, 2); });
+}
+
+pk_status pk_diag_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
+                             int y2_sigma, float *y1, float *y2) {
+    return guard([&] {
+        need(x && g1 && b1 && g2 && b2 && y1 && y2 && rows > 0 && d > 0 && d <= 1024, "x/g1/b1/g2/b2/y1/y2/rows/d (d <= 1024)");
+        need(!y2_sigma || d % 16 == 0, "sigma columns: d must be a multiple of 16");
+        need_device();
+        DevBuf xb, gb, o1, o2;
+        up(xb, x, (size_t)rows * d * 4);
+        up_rows(gb, {g1, b1, g2, b2}, d);
+        const float *p = gb.as<float>();
+        o1.reserve((size_t)rows * d * 4);
+        o2.reserve((size_t)rows * d * 4);
+        launch_layernorm2(xb.as<float>(), rows, d, p, p + d, p + 2 * (size_t)d, p + 3 * (size_t)d, eps, o1.as<float>(), o2.as<float>(), nullptr, y2_sigma ? 2 : 0);
+        PK_CHECK_LAUNCH();
+        down(y1, o1, (size_t)rows * d * 4);
+        down(y2, o2, (size_t)rows * d * 4);
+    });
+}
+
+pk_status pk_diag_sigma_copy(const float *src, int64_t rows, int K, int64_t ld, float *dst) {
+    return guard([&] {
+        need(src && dst && rows > 0 && rows % 16 == 0 && K > 0 && K % 64 == 0 && ld >= K, "src/dst, rows % 16 == 0, K % 64 == 0, ld >= K");
+        need_device();
+        DevBuf a, b;
+        up(a, src, (size_t)rows * ld * 4);
+        b.reserve((size_t)rows * K * 4);
+        launch_sigma_copy(a.as<float>(), b.as<float>(), rows, K, ld, nullptr);
+        PK_CHECK_LAUNCH();
+        down(dst, b, (size_t)rows * K * 4);
+    });
+}
+
+int pk_diag_gemm_smallm_forms(int32_t *out, int cap) {
+    for (int i = 0; out && i < kGemmSmallmForms.n && i < cap; ++i) out[i] = (int32_t)kGemmSmallmForms.v[i];
+    return kGemmSmallmForms.n;
+}
+
+// One product of the small-M family, staged the way a streaming session / the single-clip encoder stages it (stream.cpp ln_gemm, engine.cpp run_gemm).
+pk_status pk_diag_gemm_smallm(pk_smallm_gemm_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const int M = d->M, N = d->N, K = d->K, epi = d->epi;
+        need(d->A && d->W && d->out && M > 0 && N > 0 && K > 0, "A/W/out/M/N/K");
+        need(M <= kSmallMRows && K % 64 == 0, "the small-M family: M <= 1536, K % 64 == 0");
+        need(epi >= EPI_NONE && epi <= EPI_GLU, "epi");
+        need(epi != EPI_RESID || d->resid, "resid");
+        need(d->lda >= K, "lda >= K");
+        need(!d->w_sig || N % 16 == 0, "w_sig: N must be a multiple of 16 (launch_sigma_copy)");
+        need(d->sigma_cols >= 0 && d->sigma_cols % 16 == 0 && d->sigma_cols <= N, "sigma_cols: a multiple of 16, <= N");
+        need((d->ln_g != nullptr) == (d->ln_b != nullptr) && (d->pre_g != nullptr) == (d->pre_b != nullptr), "gamma and beta: both or neither");
+        need(!d->pre_g || (d->ln_g && d->pre_out), "pre_g comes with ln_g and pre_out");
+        need(!d->ln_g || K <= 1024, "LayerNorm: K <= 1024");
+        const bool dw = d->dw != 0;
+        const int c = d->dw_c, S = dw && c > 0 ? M / c : 0;
+        if (dw) {
+            need(d->ln_g && epi == EPI_GLU && N == K && c > 0 && M % c == 0, "dw: ln_g, epi glu, N == K, M a multiple of dw_c");
+            need(d->cache_in && d->cache_out && d->cache_streams >= S && d->dw_w && d->dw_bias && d->bn_mean && d->bn_rstd && d->bn_g && d->bn_b, "dw: caches / conv vectors");
+            need(!d->dw_out_sigma || N % 16 == 0, "dw_out_sigma: d must be a multiple of 16");
+            need(d->remap_rows == 0 && d->sigma_cols == 0, "dw: row-major activations");
+        }
+        // every offset the product may write lies inside out
+        if (d->remap_rows > 0) {
+            need(d->remap_gs >= 0 && d->remap_rs >= 0 && d->remap_cs >= 0, "remap strides");
+            const int64_t last = (int64_t)((M - 1) / d->remap_rows) * d->remap_gs + (int64_t)(std::min(M, d->remap_rows) - 1) * d->remap_rs + (int64_t)(N - 1) * d->remap_cs;
+            need(last < d->out_words, "out_words: the remapped output must fit");
+        } else {
+            need(d->remap_rows == 0 && d->ldo >= N && (int64_t)(M - 1) * d->ldo + N <= d->out_words, "ldo >= N, out_words >= (M - 1) ldo + N");
+        }
+        need_device();
+        const int wrows = epi == EPI_GLU ? 2 * N : N;
+        const bool sigA = d->a_sigma != 0, ln = d->ln_g != nullptr, fold = ln && d->fused;
+        DevBuf a, w, ws, b, r, o, gb, nrm, po, ci, co, par, glu;
+        // A: the rows the first launch reads.  A separate LayerNorm reads dense rows; the product reads them at the caller's pitch, in the sigma order
+        // when nothing in front of it writes them so.
+        const int64_t lda = (ln && !fold) ? K : d->lda;
+        {
+            std::vector<float> h((size_t)M * lda);
+            for (int i = 0; i < M; ++i)
+                for (int64_t k = 0; k < lda; ++k) h[(size_t)i * lda + ((sigA && !ln && k < K) ? dec_sigma((int)k) : k)] = d->A[(size_t)i * d->lda + k];
+            up(a, h.data(), h.size() * 4);
+        }
+        up(w, d->W, (size_t)wrows * K * 4);
+        if (d->w_sig) {
+            ws.reserve((size_t)wrows * K * 4);
+            launch_sigma_copy(w.as<float>(), ws.as<float>(), wrows, K, K, nullptr);
+        }
+        if (d->bias) up(b, d->bias, (size_t)wrows * 4);
+        if (d->resid) up(r, d->resid, (size_t)M * N * 4);
+        if (ln) up_rows(gb, {d->ln_g, d->ln_b, d->pre_g, d->pre_b}, K);
+        const float *dg = gb.as<float>(), *db = dg + K, *dpg = dg + 2 * (size_t)K, *dpb = dg + 3 * (size_t)K;
+        o.reserve((size_t)d->out_words * 4);
+        PK_HIP(hipMemsetD32(o.p, 0x7fc5a5a5, (size_t)d->out_words));
+        if (d->pre_g) {
+            po.reserve((size_t)M * K * 4);
+            PK_HIP(hipMemsetD32(po.p, 0x7fc5a5a5, (size_t)M * K));
+        }
+        GemmArgs g{a.as<float>(), lda, w.as<float>(), K, d->bias ? b.as<float>() : nullptr, o.as<float>(), d->ldo,
+                   d->resid ? r.as<float>() : nullptr, N, d->alpha, M, N, K};
+        g.remap_rows = d->remap_rows; g.remap_gs = d->remap_gs; g.remap_rs = d->remap_rs; g.remap_cs = d->remap_cs;
+        g.sigma_cols = d->sigma_cols;
+        g.W_sig = d->w_sig ? ws.as<float>() : nullptr;
+        g.a_sigma = sigA ? 1 : 0;
+        DwTail tail{};
+        if (dw) {
+            const size_t nd = (size_t)N;
+            up(ci, d->cache_in, (size_t)S * 8 * nd * 4);
+            co.reserve((size_t)d->cache_streams * 8 * nd * 4);
+            PK_HIP(hipMemsetD32(co.p, 0x7fc5a5a5, (size_t)d->cache_streams * 8 * nd));
+            par.reserve((size_t)(9 + 5) * nd * 4);                     // the depthwise weights [9][d], then the five per-channel vectors
+            float *pp = par.as<float>();
+            PK_HIP(hipMemcpy(pp, d->dw_w, 9 * nd * 4, hipMemcpyHostToDevice));
+            const float *five[5] = {d->dw_bias, d->bn_mean, d->bn_rstd, d->bn_g, d->bn_b};
+            for (int i = 0; i < 5; ++i) PK_HIP(hipMemcpy(pp + (9 + i) * nd, five[i], nd * 4, hipMemcpyHostToDevice));
+            tail = DwTail{ci.as<float>(), co.as<float>(), d->dw_has_cache ? 1 : 0, c, pp, pp + 9 * nd, pp + 10 * nd, pp + 11 * nd, pp + 12 * nd, pp + 13 * nd,
+                          d->dw_out_sigma ? 1 : 0};
+        }
+        if (fold) {                                                    // what ln_gemm launches when the norm folds: the un-normalised natural rows
+            g.a_sigma = 0; g.ln_g = dg; g.ln_b = db; g.ln_eps = d->eps;
+            if (!gemm_smallm_ln_applies(g, epi))
+                fail(PK_ERR_UNSUPPORTED, "pk_diag_gemm_smallm: the folded LayerNorm takes natural rows, w_sig, K = 512 / 1024, N %% 16 == 0, epi none / relu / silu / glu");
+            if (d->pre_g) {
+                g.pre_g = dpg; g.pre_b = dpb; g.pre_out = po.as<float>(); g.pre_ldo = K;
+                if (!gemm_smallm_pre_applies(g, epi)) fail(PK_ERR_UNSUPPORTED, "pk_diag_gemm_smallm: the norm in front takes epi silu, N >= 512 and a single round of workgroups");
+            }
+            if (dw) {
+                if (!gemm_smallm_dw_applies(g, epi, c, 9)) fail(PK_ERR_UNSUPPORTED, "pk_diag_gemm_smallm: the conv tail takes dw_c = 1, 2 or 4 and a single round of workgroups");
+                g.dw_tail = &tail;
+            }
+        } else {
+            if (g.a_sigma && !(g.W_sig && N % 16 == 0)) fail(PK_ERR_UNSUPPORTED, "pk_diag_gemm_smallm: sigma-K activations need the sigma-K weight copy (w_sig)");
+            if (dw && stream_dwconv_inst(9) == STREAM_DW_N) fail(PK_ERR_UNSUPPORTED, "pk_diag_gemm_smallm: no streaming conv kernel of 9 taps");
+            if (ln) {
+                nrm.reserve((size_t)M * K * 4);
+                const int mode = sigA ? 2 : 0;
+                if (d->pre_g) launch_layernorm2(a.as<float>(), M, K, dpg, dpb, dg, db, d->eps, po.as<float>(), nrm.as<float>(), nullptr, mode);
+                else launch_layernorm(a.as<float>(), M, K, dg, db, d->eps, nrm.as<float>(), nullptr, mode);
+                g.A = nrm.as<float>();
+            }
+            if (dw) {
+                glu.reserve((size_t)M * N * 4);
+                g.out = glu.as<float>(); g.ldo = N;
+            }
+        }
+        d->form = (int32_t)gemm_smallm_form(g, epi);
+        launch_gemm(g, epi, nullptr);
+        if (dw && !fold)
+            launch_stream_dwconv(glu.as<float>(), tail.cache_in, tail.has_cache, S, c, N, 9, tail.w, tail.bias, tail.bn_mean, tail.bn_rstd, tail.bn_g, tail.bn_b,
+                                 o.as<float>(), tail.cache_out, nullptr, tail.out_sigma);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(d->out, o, (size_t)d->out_words * 4);
+        if (d->pre_g) down(d->pre_out, po, (size_t)M * K * 4);
+        if (dw) down(d->cache_out, co, (size_t)d->cache_streams * 8 * N * 4);
+        static_assert(PK_DIAG_SMALLM_KERNEL(gemm_smallm_form_of(SMALLM_LN, EPI_GLU, 16, true, true, false)) == SMALLM_LN &&
+                      PK_DIAG_SMALLM_EPI(gemm_smallm_form_of(SMALLM_LN, EPI_GLU, 16, true, true, false)) == EPI_GLU &&
+                      PK_DIAG_SMALLM_RING(gemm_smallm_form_of(SMALLM_LN, EPI_GLU, 16, true, true, false)) == 16 &&
+                      PK_DIAG_SMALLM_SIG(gemm_smallm_form_of(SMALLM_LN, EPI_GLU, 16, true, true, false)) == 1 &&
+                      PK_DIAG_SMALLM_DW(gemm_smallm_form_of(SMALLM_LN, EPI_GLU, 16, true, true, false)) == 1 &&
+                      PK_DIAG_SMALLM_PRE(gemm_smallm_form_of(SMALLM_RT2, EPI_RESID, 4, true, false, true)) == 1, "form fields");
+    });
+}
+
 pk_status pk_diag_ln_gemm(int M, int N, int K, const float *A, const float *pre_gamma, const float *pre_beta, const float *gamma, const float *beta, float eps,
                           const float *W, const float *bias, int epi, int fold, float *out, float *y1) {
     return guard([&] {

@@ -16,8 +16,8 @@
 //    v_permlane16_swap / v_permlane32_swap exchange the odd 16-lane rows of one register with the even rows of another -- two
 //    swaps per register pair, four per float4, eight per 16-k block, issued beside the block's four MFMAs (128 clocks).
 //    (Semantics pinned on the hardware by tools/ubench/permlane_probe.cpp.)
-//  * a register ring of DEPTH = 8 chunks of 64 k (8 loads per chunk and lane; 4 / 2 / 1 when K / 64 is not a multiple of 8):
-//    7 x 512 chain clocks of cover for the weight stream, 56 loads in flight -- below vmcnt's 6-bit limit.
+//  * a register ring of DEPTH = 8 chunks of 64 k (8 loads per chunk and lane; 2 when K / 64 is even but no multiple of 8 -- K = 256 runs
+//    depth 2 --, 1 when it is odd; gemm_smallm_form): 7 x 512 chain clocks of cover for the weight stream, 56 loads in flight -- below vmcnt's 6-bit limit.
 //  * one wave per workgroup -- with a few hundred waves on 1024 SIMDs every chain gets a SIMD and an L1 of its own (four row-tile waves in
 //    one workgroup, sharing the W lines through one L1, lost: the L1 is at its 64 B/clk with four chains); GLU: the value and the gate
 //    tile of the same 16 columns are the two waves of a workgroup (two chains side by side instead of one of double length), the gate sums
@@ -25,6 +25,8 @@
 //  * SIG (GemmArgs::a_sigma + W_sig): both operands already in MFMA order -- no transposes at all; the weights TILED so that a load
 //    instruction reads 1 KB of consecutive addresses (the streaming encoder, csrc/stream.cpp; Model::sigma_weights).
 #include "../pk_devmath.h"
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 #include "kernels.hpp"
 
@@ -473,45 +475,52 @@ bool gemm_smallm_ln_applies(const GemmArgs &a, int epi) {
     return epi == EPI_NONE || epi == EPI_RELU || epi == EPI_SILU || epi == EPI_GLU;
 }
 
-template <int EPI>
-static void launch_smallm_ln(const GemmArgs &a, hipStream_t s) {
+// Which instantiation a product takes (kernels.hpp: GemmSmallmForm).  The launchers below switch on this function's result and pk_diag_gemm_smallm
+// reports it: every threshold of the family lives here and nowhere else.
+GemmSmallmForm gemm_smallm_form(const GemmArgs &a, int epi) {
+    const int nkc = a.K / 64;
+    if (a.ln_g)                                                     // LayerNorm folded in (the caller checked gemm_smallm_ln_applies: K = 512 / 1024)
+        return gemm_smallm_form_of(SMALLM_LN, epi, a.K == 512 ? 8 : 16, true, epi == EPI_GLU && a.dw_tail, epi == EPI_SILU && a.pre_g);
+    const bool sig = a.a_sigma && a.W_sig;
+    // more waves than SIMDs (1024): two row tiles per wave (gemm_smallm_rt2_kernel)
+    const int64_t col_tiles = (a.N + 15) / 16, row_tiles = (a.M + 15) / 16;
+    if (sig && epi != EPI_GLU && nkc % 4 == 0 && row_tiles >= 4 && col_tiles * row_tiles >= 768) return gemm_smallm_form_of(SMALLM_RT2, epi, 4, true);
+    return gemm_smallm_form_of(SMALLM_CHAIN, epi, nkc % 8 == 0 ? 8 : nkc % 2 == 0 ? 2 : 1, sig);
+}
+[[noreturn]] static void smallm_no_form(int form) {
+    fprintf(stderr, "parakeet_amd: internal error: launch_gemm_smallm has no kernel for form %d\n", form);
+    abort();
+}
+
+template <int EPI, int PER_LANE, bool DW, bool PRE>
+static void launch_smallm_ln_inst(const GemmArgs &a, hipStream_t s) {
     const int tiles = a.N / 16;
     const dim3 grid(EPI == EPI_GLU ? tiles : (tiles + 1) / 2, (a.M + 15) / 16), block(256);
     const size_t lds = (size_t)16 * (a.K + 4) * sizeof(float);
-    static DynLdsSlots slots8, slots16;
+    static DynLdsSlots slots;                                       // (one per instantiation)
+    ensure_dyn_lds(slots, reinterpret_cast<const void *>(&gemm_smallm_ln_kernel<EPI, PER_LANE, DW, PRE>), lds);
+    hipLaunchKernelGGL((gemm_smallm_ln_kernel<EPI, PER_LANE, DW, PRE>), grid, block, lds, s, a, DW ? *a.dw_tail : DwTail{});
+}
+template <int EPI>
+static void launch_smallm_ln(const GemmArgs &a, hipStream_t s) {
+    const int form = gemm_smallm_form(a, EPI), per_lane = gemm_smallm_form_ring(form);
+    if (per_lane != 8 && per_lane != 16) smallm_no_form(form);
     if constexpr (EPI == EPI_SILU) {
-        if (a.pre_g) {
-            static DynLdsSlots pslots8, pslots16;
-            if (a.K == 512) {
-                ensure_dyn_lds(pslots8, reinterpret_cast<const void *>(&gemm_smallm_ln_kernel<EPI, 8, false, true>), lds);
-                hipLaunchKernelGGL((gemm_smallm_ln_kernel<EPI, 8, false, true>), grid, block, lds, s, a, DwTail{});
-            } else {
-                ensure_dyn_lds(pslots16, reinterpret_cast<const void *>(&gemm_smallm_ln_kernel<EPI, 16, false, true>), lds);
-                hipLaunchKernelGGL((gemm_smallm_ln_kernel<EPI, 16, false, true>), grid, block, lds, s, a, DwTail{});
-            }
+        if (gemm_smallm_form_pre(form)) {
+            if (per_lane == 8) launch_smallm_ln_inst<EPI, 8, false, true>(a, s);
+            else launch_smallm_ln_inst<EPI, 16, false, true>(a, s);
             return;
         }
     }
     if constexpr (EPI == EPI_GLU) {
-        if (a.dw_tail) {
-            static DynLdsSlots dslots8, dslots16;
-            if (a.K == 512) {
-                ensure_dyn_lds(dslots8, reinterpret_cast<const void *>(&gemm_smallm_ln_kernel<EPI, 8, true>), lds);
-                hipLaunchKernelGGL((gemm_smallm_ln_kernel<EPI, 8, true>), grid, block, lds, s, a, *a.dw_tail);
-            } else {
-                ensure_dyn_lds(dslots16, reinterpret_cast<const void *>(&gemm_smallm_ln_kernel<EPI, 16, true>), lds);
-                hipLaunchKernelGGL((gemm_smallm_ln_kernel<EPI, 16, true>), grid, block, lds, s, a, *a.dw_tail);
-            }
+        if (gemm_smallm_form_dw(form)) {
+            if (per_lane == 8) launch_smallm_ln_inst<EPI, 8, true, false>(a, s);
+            else launch_smallm_ln_inst<EPI, 16, true, false>(a, s);
             return;
         }
     }
-    if (a.K == 512) {
-        ensure_dyn_lds(slots8, reinterpret_cast<const void *>(&gemm_smallm_ln_kernel<EPI, 8>), lds);
-        hipLaunchKernelGGL((gemm_smallm_ln_kernel<EPI, 8>), grid, block, lds, s, a, DwTail{});
-    } else {
-        ensure_dyn_lds(slots16, reinterpret_cast<const void *>(&gemm_smallm_ln_kernel<EPI, 16>), lds);
-        hipLaunchKernelGGL((gemm_smallm_ln_kernel<EPI, 16>), grid, block, lds, s, a, DwTail{});
-    }
+    if (per_lane == 8) launch_smallm_ln_inst<EPI, 8, false, false>(a, s);
+    else launch_smallm_ln_inst<EPI, 16, false, false>(a, s);
 }
 
 // W_sig of GemmArgs: dst[tile = row / 16][chunk = k / 64][q][lane = (row % 16) + 16 kq][e] = src[row][64 chunk + 16 q + 4 e + kq]
@@ -535,23 +544,24 @@ static void launch_smallm_epi(const GemmArgs &a, hipStream_t s) {
     constexpr int NB = (EPI == EPI_GLU) ? 2 : 1;
     // one wave per workgroup (GLU: the value / gate pair): with a few hundred waves on 1024 SIMDs every chain gets a SIMD and an L1 of its own
     const dim3 grid((a.N + 15) / 16, (a.M + 15) / 16), block(64 * NB);
-    const int nkc = a.K / 64;
-    if (a.a_sigma && a.W_sig) {
-        const int row_tiles = (a.M + 15) / 16;
-        if constexpr (EPI != EPI_GLU) {
-            // more waves than SIMDs (1024): two row tiles per wave (gemm_smallm_rt2_kernel)
-            if (nkc % 4 == 0 && row_tiles >= 4 && (int64_t)grid.x * row_tiles >= 768) {
-                hipLaunchKernelGGL((gemm_smallm_rt2_kernel<EPI>), dim3(grid.x, (row_tiles + 1) / 2), dim3(64), 0, s, a);
-                return;
-            }
+    const int form = gemm_smallm_form(a, EPI), ring = gemm_smallm_form_ring(form);
+    if constexpr (EPI != EPI_GLU) {
+        if (gemm_smallm_form_kernel(form) == SMALLM_RT2) {
+            hipLaunchKernelGGL((gemm_smallm_rt2_kernel<EPI>), dim3(grid.x, (grid.y + 1) / 2), dim3(64), 0, s, a);
+            return;
         }
-        if (nkc % 8 == 0) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 8, true>), grid, block, 0, s, a);
-        else if (nkc % 2 == 0) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 2, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 1, true>), grid, block, 0, s, a);
+    }
+    if (gemm_smallm_form_kernel(form) != SMALLM_CHAIN) smallm_no_form(form);
+    if (gemm_smallm_form_sig(form)) {
+        if (ring == 8) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 8, true>), grid, block, 0, s, a);
+        else if (ring == 2) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 2, true>), grid, block, 0, s, a);
+        else if (ring == 1) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 1, true>), grid, block, 0, s, a);
+        else smallm_no_form(form);
     } else {
-        if (nkc % 8 == 0) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 8, false>), grid, block, 0, s, a);
-        else if (nkc % 2 == 0) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 2, false>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 1, false>), grid, block, 0, s, a);
+        if (ring == 8) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 8, false>), grid, block, 0, s, a);
+        else if (ring == 2) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 2, false>), grid, block, 0, s, a);
+        else if (ring == 1) hipLaunchKernelGGL((gemm_smallm_kernel<EPI, 1, false>), grid, block, 0, s, a);
+        else smallm_no_form(form);
     }
 }
 

@@ -171,6 +171,44 @@ bool gemm_bf16_blocked_handoff(int M, int N, int K, int epi, bool producer);
 bool gemm_smallm_ln_applies(const GemmArgs &a, int epi);
 bool gemm_smallm_pre_applies(const GemmArgs &a, int epi);                      // ... with GemmArgs::pre_g (a second norm in front, bit for bit the separate LayerNorm launch)
 bool gemm_smallm_dw_applies(const GemmArgs &a, int epi, int c, int kc);        // ... with GemmArgs::dw_tail (GLU, conv kernel 9, c = 1 / 2 / 4 frames per stream)
+// The form of a small-M launch (kernels/gemm_smallm.hip), by the function launch_gemm_smallm switches on: value = gemm_smallm_form_of(...).
+//   kernel: gemm_smallm_kernel (one wave per 16 x 16 tile), gemm_smallm_rt2_kernel (two row tiles per wave), gemm_smallm_ln_kernel (LayerNorm folded in)
+//   epi:    the epilogue the kernel is instantiated for (GemmEpi)
+//   ring:   chain: DEPTH, the chunks of 64 k in the register ring -- 8 / 2 / 1 by K / 64; rt2: its fixed 4; ln: PER_LANE = K / 64, 8 or 16
+//   sig:    the operands in the sigma K order, the weights tiled (a_sigma + W_sig; ln: W_sig only, the kernel writes the sigma rows itself)
+//   dw:     ln + GLU with GemmArgs::dw_tail;  pre: ln + SiLU with GemmArgs::pre_g
+enum GemmSmallmKernel { SMALLM_CHAIN = 0, SMALLM_RT2 = 1, SMALLM_LN = 2 };
+enum GemmSmallmForm : int {};
+constexpr GemmSmallmForm gemm_smallm_form_of(int kernel, int epi, int ring, bool sig, bool dw = false, bool pre = false) {
+    return (GemmSmallmForm)(kernel * 4096 + epi * 512 + ring * 8 + (sig ? 4 : 0) + (dw ? 2 : 0) + (pre ? 1 : 0));
+}
+constexpr int gemm_smallm_form_kernel(int f) { return f >> 12; }
+constexpr int gemm_smallm_form_epi(int f) { return (f >> 9) & 7; }
+constexpr int gemm_smallm_form_ring(int f) { return (f >> 3) & 63; }
+constexpr bool gemm_smallm_form_sig(int f) { return (f & 4) != 0; }
+constexpr bool gemm_smallm_form_dw(int f) { return (f & 2) != 0; }
+constexpr bool gemm_smallm_form_pre(int f) { return (f & 1) != 0; }
+GemmSmallmForm gemm_smallm_form(const GemmArgs &a, int epi);   // of a product launch_gemm sends there (M <= kSmallMRows, K % 64 == 0; ln_g: gemm_smallm_ln_applies)
+// Every form launch_gemm_smallm can take = every instantiation of the three kernels: chain 5 epilogues x 3 ring depths x natural / sigma; rt2 the four
+// epilogues without GLU; ln none / relu / silu / glu x K = 512 / 1024, then SiLU with the norm in front and GLU with the conv tail at both K.
+constexpr int kGemmSmallmFormCount = 5 * 3 * 2 + 4 + 4 * 2 + 2 + 2;
+struct GemmSmallmForms { GemmSmallmForm v[kGemmSmallmFormCount]; int n; };
+constexpr GemmSmallmForms gemm_smallm_forms() {
+    GemmSmallmForms t{};
+    constexpr int ring[3] = {8, 2, 1}, ln_epi[4] = {EPI_NONE, EPI_RELU, EPI_SILU, EPI_GLU};
+    for (int epi = EPI_NONE; epi <= EPI_GLU; ++epi)
+        for (int r = 0; r < 3; ++r)
+            for (int sig = 0; sig < 2; ++sig) t.v[t.n++] = gemm_smallm_form_of(SMALLM_CHAIN, epi, ring[r], sig != 0);
+    for (int epi = EPI_NONE; epi <= EPI_RESID; ++epi) t.v[t.n++] = gemm_smallm_form_of(SMALLM_RT2, epi, 4, true);
+    for (int per_lane = 8; per_lane <= 16; per_lane += 8) {
+        for (int e = 0; e < 4; ++e) t.v[t.n++] = gemm_smallm_form_of(SMALLM_LN, ln_epi[e], per_lane, true);
+        t.v[t.n++] = gemm_smallm_form_of(SMALLM_LN, EPI_SILU, per_lane, true, false, true);
+        t.v[t.n++] = gemm_smallm_form_of(SMALLM_LN, EPI_GLU, per_lane, true, true, false);
+    }
+    return t;
+}
+constexpr GemmSmallmForms kGemmSmallmForms = gemm_smallm_forms();
+static_assert(kGemmSmallmForms.n == kGemmSmallmFormCount, "kGemmSmallmForms must list every instantiation");
 // same contract with bf16 operands and fp32 accumulation: a.W points to bf16 weights [N][K] (rounded once at upload), A is
 // rounded to bf16 while it is staged; K % 64 == 0.  Not bit-identical to the fp32 chain (kernels/gemm_bf16.hpp).
 void launch_gemm_bf16(const GemmArgs &a, int epi, hipStream_t s);

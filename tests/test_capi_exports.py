@@ -79,6 +79,15 @@ def test_no_gpu_is_a_loud_error(tmp_path):
     with pytest.raises(capi.PkError) as e:
         capi.diag_ctc_greedy(np.zeros((4, 9), np.float32), 9, 8, B=1, T=4)
     assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:             # the small-M GEMM diagnostics: valid arguments, no device
+        capi.diag_gemm_smallm(np.zeros((4, 64), np.float32), np.zeros((16, 64), np.float32), w_sig=True, a_sigma=True)
+    assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_sigma_copy(np.zeros((16, 64), np.float32))
+    assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_layernorm_sigma(np.zeros((2, 128), np.float32), np.ones(128, np.float32), np.zeros(128, np.float32))
+    assert e.value.code == -4
     with pytest.raises(capi.PkError) as e:             # the multi-GPU entry point as well
         capi.Group(str(wp), cfg)
     assert e.value.code == -4
@@ -98,6 +107,29 @@ def test_strict_weight_loading_errors(tmp_path):
     with pytest.raises(capi.PkError) as e:             # reference: std::runtime_error("Cannot open vocab file: ...") vocab.cpp:12-14
         capi.Model(str(wp), cfg, vocab_path=str(tmp_path / "no_vocab.txt"))
     assert "Cannot open vocab file" in str(e.value)
+
+
+def test_smallm_gemm_form_table_and_argument_checks_need_no_device():
+    """pk_diag_gemm_smallm_forms (what tests/test_gpu_smallm_gemm.py::test_every_form_has_a_case compares its cases with) is host arithmetic: one form
+    per instantiation of the three kernels; and pk_diag_gemm_smallm refuses malformed arguments before it looks for a device."""
+    every = capi.diag_gemm_smallm_forms()
+    assert len(every) == 46 and len(set(every)) == 46
+    chain = [f for f in every if f[0] == "chain"]
+    assert {(e, r, s) for _, e, r, s, _, _ in chain} == {(e, r, s) for e in capi.EPI for r in (8, 2, 1) for s in (False, True)}
+    assert all(not dw and not pre for *_, dw, pre in chain)
+    assert sorted(f[1:] for f in every if f[0] == "rt2") == sorted((e, 4, True, False, False) for e in ("none", "relu", "silu", "resid"))
+    ln = [f for f in every if f[0] == "ln"]
+    assert {f[2] for f in ln} == {8, 16} and all(f[3] for f in ln) and "resid" not in {f[1] for f in ln}
+    assert {f[1] for f in ln if f[4]} == {"glu"} and {f[1] for f in ln if f[5]} == {"silu"} and not any(f[4] and f[5] for f in ln)
+    A, W = np.zeros((4, 64), np.float32), np.zeros((40, 64), np.float32)
+    for bad in (dict(w_sig=True), dict(sigma_cols=8), dict(sigma_cols=48), dict(epi="resid"), dict(ldo=39), dict(out_words=4 * 40 - 1),
+                dict(remap=(2, 80, 1, 2), out_words=159), dict(pre=(np.ones(64, np.float32), np.zeros(64, np.float32)))):
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_gemm_smallm(A, W, **bad)
+        assert e.value.code == -1, bad
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_gemm_smallm(np.zeros((4, 96), np.float32), np.zeros((16, 96), np.float32))
+    assert e.value.code == -1
 
 
 def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
