@@ -754,6 +754,42 @@ pk_status pk_diag_sigma_copy(const float *src, int64_t rows, int K, int64_t ld, 
 pk_status pk_diag_layernorm_sigma(const float *x, int64_t rows, int d, const float *gamma, const float *beta, float eps, float *y);
 pk_status pk_diag_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
                              int y2_sigma, float *y1, float *y2);
+/* ONE product of the fp32 tile GEMM family alone (kernels/gemm.hip, gemm_pipe.hpp; kernels.hpp GemmArgs): out = epi(X W^T + bias) for a product
+ * launch_gemm keeps on a tile kernel (M > 1536 or K % 64 != 0); epi as above (glu: W [2N][ldw], bias [2N]).
+ *   A [M][lda] (lda >= K), W [N or 2N][ldw] (ldw >= K), resid [M][ldr] (ldr >= N): host arrays AT THOSE PITCHES; on the device every word of a row past
+ *            K (resid: N) is replaced by the NaN pattern 0x7FC5A5A5 before the launch.
+ *   sigma_cols / remap_*: as for pk_diag_gemm_smallm.  ldo >= N; out (out_words floats: every offset the product may write lies inside) comes back WHOLE,
+ *            exactly as the launch left it; its device buffer is filled with 0x7FC5A5A5 first.
+ *   ln_g / ln_b / eps: X = LayerNorm(A), run as the statistics pass (launch_layernorm_stats) + the fold into the A staging (GemmArgs::ln_stats).
+ * form receives the form of the launch, by the function launch_gemm switches on (kernels.hpp gemm_tile_form): PK_DIAG_TILE_KERNEL 0 gemm_nt_kernel /
+ * 1 gemm_pipe_kernel, PK_DIAG_TILE_WGM x _WGN waves of _TM x _TN 32 x 32 accumulators (the tile is 32 WGM TM x 32 WGN TN), PK_DIAG_TILE_NBUF, _LNA, _SCHED,
+ * PK_DIAG_TILE_EPI.  pk_diag_gemm_tile_forms lists every form the launcher can take; pk_diag_gemm_tile_form answers for a shape (ln != 0: with the LayerNorm
+ * fold) what pk_diag_gemm_tile would launch -- both host arithmetic, no device.
+ * Refused before anything is launched, PK_ERR_UNSUPPORTED: a shape of the small-M family; what no tile kernel can do -- glu or resid with sigma_cols != 0,
+ * K % 32 != 0, lda or ldw no multiple of 4 --; a LayerNorm outside gemm_ln_stats_applies.  PK_ERR_INVALID: malformed arguments. */
+#define PK_DIAG_TILE_KERNEL(form) ((form) >> 20)
+#define PK_DIAG_TILE_WGM(form) (((form) >> 17) & 7)
+#define PK_DIAG_TILE_WGN(form) (((form) >> 14) & 7)
+#define PK_DIAG_TILE_TM(form) (((form) >> 11) & 7)
+#define PK_DIAG_TILE_TN(form) (((form) >> 8) & 7)
+#define PK_DIAG_TILE_NBUF(form) (((form) >> 6) & 3)
+#define PK_DIAG_TILE_LNA(form) (((form) >> 5) & 1)
+#define PK_DIAG_TILE_SCHED(form) (((form) >> 3) & 3)
+#define PK_DIAG_TILE_EPI(form) ((form) & 7)
+typedef struct pk_gemm_tile_diag {
+    int32_t M, N, K, epi, sigma_cols;
+    const float *A; int64_t lda;
+    const float *W; int64_t ldw;
+    const float *bias;
+    const float *resid; int64_t ldr; float alpha;
+    int32_t remap_rows; int64_t remap_gs, remap_rs, remap_cs;
+    const float *ln_g, *ln_b; float eps;
+    int64_t ldo, out_words; float *out;
+    int32_t form;
+} pk_gemm_tile_diag;
+pk_status pk_diag_gemm_tile(pk_gemm_tile_diag *a);
+int pk_diag_gemm_tile_forms(int32_t *out, int cap);
+pk_status pk_diag_gemm_tile_form(int M, int N, int K, int64_t lda, int64_t ldw, int epi, int ln, int32_t *form);
 
 #ifdef __cplusplus
 }

@@ -1062,6 +1062,92 @@ def diag_layernorm2(x, g1, b1, g2, b2, y2_sigma=False, eps=1e-5):
     return y1, y2
 
 
+class PkGemmTileDiag(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("M", "N", "K", "epi", "sigma_cols")]
+                + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),
+                   ("remap_rows", C.c_int32), ("remap_gs", C.c_int64), ("remap_rs", C.c_int64), ("remap_cs", C.c_int64),
+                   ("ln_g", f32p), ("ln_b", f32p), ("eps", C.c_float), ("ldo", C.c_int64), ("out_words", C.c_int64), ("out", f32p), ("form", C.c_int32)])
+
+
+def tile_form(v):
+    """A GemmTileForm value (kernels.hpp; PK_DIAG_TILE_*) -> (kernel, tile, NBUF, LNA, SCHED, epi): kernel "nt" (gemm_nt_kernel, tile = (BM, BN)) or "pipe"
+    (gemm_pipe_kernel, tile = (WGM, WGN, TM, TN): WGM x WGN waves of TM x TN 32 x 32 accumulators)"""
+    epi = {n: k for k, n in EPI.items()}[v & 7]
+    wgm, wgn, tm, tn = (v >> 17) & 7, (v >> 14) & 7, (v >> 11) & 7, (v >> 8) & 7
+    kernel = ("nt", "pipe")[v >> 20]
+    tile = (32 * wgm * tm, 32 * wgn * tn) if kernel == "nt" else (wgm, wgn, tm, tn)
+    return kernel, tile, (v >> 6) & 3, bool(v & 32), (v >> 3) & 3, epi
+
+
+def diag_gemm_tile_forms():
+    """pk_diag_gemm_tile_forms: every form launch_gemm can take on the tile kernels, as tile_form tuples.  Host arithmetic."""
+    n = lib().pk_diag_gemm_tile_forms(None, 0)
+    out = np.zeros(n, np.int32)
+    lib().pk_diag_gemm_tile_forms(_i(out), n)
+    return [tile_form(int(v)) for v in out]
+
+
+def diag_gemm_tile_form(M, N, K, lda=None, ldw=None, epi="none", ln=False):
+    """pk_diag_gemm_tile_form: the form pk_diag_gemm_tile would launch for this product (ln: with the LayerNorm fold).  Host arithmetic; the refusals
+    of pk_diag_gemm_tile that depend on the shape alone raise here too."""
+    form = C.c_int32(-1)
+    L = lib()
+    L.pk_diag_gemm_tile_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    check(L.pk_diag_gemm_tile_form(M, N, K, K if lda is None else lda, K if ldw is None else ldw, EPI[epi], int(bool(ln)), C.byref(form)))
+    return tile_form(form.value)
+
+
+def diag_gemm_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, sigma_cols=0, remap=None, ldo=None, out_words=None, ln=None, eps=1e-5,
+                   lda=None, ldw=None, ldr=None):
+    """pk_diag_gemm_tile: one product of the fp32 tile GEMM family alone (include/parakeet_amd.h).  A [M][K], W [N or 2N][K], resid [M][N] dense; lda / ldw /
+    ldr: the pitches they are staged at (the padding holds a NaN pattern on the device); remap = (rows, gs, rs, cs); ln = (gamma, beta).
+    Returns dict(out = the WHOLE output buffer as uint32 words [out_words] exactly as the launch left it (SKINNY_FILL32 where nothing was stored),
+    form = tile_form tuple)."""
+    A, W = _c(A), _c(W)
+    M, K = A.shape
+    N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
+    assert W.shape[1] == K
+
+    def pitched(a, ld):
+        if ld is None or ld == a.shape[1]:
+            return a
+        p = np.zeros((a.shape[0], int(ld)), np.float32)
+        n = min(a.shape[1], int(ld))
+        p[:, :n] = a[:, :n]
+        return p
+
+    d = PkGemmTileDiag()
+    A, W = pitched(A, lda), pitched(W, ldw)
+    keep = [A, W]
+
+    def opt(a):
+        if a is None:
+            return None
+        a = _c(a)
+        keep.append(a)
+        return _f(a)
+
+    d.M, d.N, d.K, d.epi, d.sigma_cols = M, N, K, EPI[epi], int(sigma_cols)
+    d.A, d.lda, d.W, d.ldw, d.bias, d.alpha = _f(A), A.shape[1], _f(W), W.shape[1], opt(bias), alpha
+    if resid is not None:
+        resid = pitched(_c(resid), ldr)
+        d.resid, d.ldr = opt(resid), resid.shape[1]
+    if remap is not None:
+        d.remap_rows, d.remap_gs, d.remap_rs, d.remap_cs = (int(v) for v in remap)
+    d.eps = eps
+    if ln is not None:
+        d.ln_g, d.ln_b = opt(ln[0]), opt(ln[1])
+    d.ldo = int(ldo) if ldo is not None else N
+    d.out_words = int(out_words) if out_words is not None else M * d.ldo
+    out = np.zeros(max(d.out_words, 1), np.uint32)
+    d.out = out.ctypes.data_as(f32p)
+    d.form = -1
+    L = lib()
+    L.pk_diag_gemm_tile.argtypes = [C.POINTER(PkGemmTileDiag)]
+    check(L.pk_diag_gemm_tile(C.byref(d)))
+    return dict(out=out[:d.out_words], form=tile_form(d.form))
+
+
 class Batch:
     """pk_batch: the resident pipeline (clips of one length stay in HBM; decode(k) overlaps encoder(k+1))."""
 

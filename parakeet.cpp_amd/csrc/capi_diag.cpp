@@ -717,6 +717,104 @@ pk_status pk_diag_gemm_smallm(pk_smallm_gemm_diag *d) {
     });
 }
 
+// the PK_DIAG_TILE_* macros of include/parakeet_amd.h decode what gemm_tile_form_of (kernels.hpp) encodes
+constexpr int kTileFormProbe = gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, true, 2, EPI_GLU);
+static_assert(PK_DIAG_TILE_KERNEL(kTileFormProbe) == TILE_PIPE && PK_DIAG_TILE_WGM(kTileFormProbe) == 4 && PK_DIAG_TILE_WGN(kTileFormProbe) == 2 &&
+              PK_DIAG_TILE_TM(kTileFormProbe) == 1 && PK_DIAG_TILE_TN(kTileFormProbe) == 2 && PK_DIAG_TILE_NBUF(kTileFormProbe) == 1 &&
+              PK_DIAG_TILE_LNA(kTileFormProbe) == 1 && PK_DIAG_TILE_SCHED(kTileFormProbe) == 2 && PK_DIAG_TILE_EPI(kTileFormProbe) == EPI_GLU &&
+              PK_DIAG_TILE_KERNEL(gemm_tile_nt_form(128, 128, EPI_RESID)) == TILE_NT && PK_DIAG_TILE_TM(gemm_tile_nt_form(128, 128, EPI_RESID)) == 2,
+              "PK_DIAG_TILE_* must decode gemm_tile_form_of");
+
+int pk_diag_gemm_tile_forms(int32_t *out, int cap) {
+    for (int i = 0; out && i < kGemmTileForms.n && i < cap; ++i) out[i] = (int32_t)kGemmTileForms.v[i];
+    return kGemmTileForms.n;
+}
+
+// What both tile diagnostics refuse for a product, before either looks for a device: a shape of the small-M family, what no tile kernel can do
+// (gemm_tile_refusal: launch_gemm aborts on those), a LayerNorm fold outside gemm_ln_stats_applies.  ln: g comes back with placeholder norm pointers.
+static void tile_product_checks(GemmArgs &g, int epi, bool ln, const char *who) {
+    need(g.M > 0 && g.N > 0 && g.K > 0, "M/N/K");
+    need(epi >= EPI_NONE && epi <= EPI_GLU, "epi");
+    need(g.lda >= g.K && g.ldw >= g.K, "lda >= K, ldw >= K");
+    if (!gemm_tile_applies(g)) fail(PK_ERR_UNSUPPORTED, "%s: M <= %d with K %% 64 == 0 runs on the small-M kernels (pk_diag_gemm_smallm)", who, kSmallMRows);
+    if (const char *why = gemm_tile_refusal(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: %s", who, why);
+    if (ln) {
+        static const float none[2] = {0.0f, 0.0f};                     // (never read: the form function and gemm_ln_stats_applies look at the pointers only)
+        g.ln_g = g.ln_b = g.ln_stats = none;
+        if (!gemm_ln_stats_applies(g, epi))
+            fail(PK_ERR_UNSUPPORTED, "%s: the LayerNorm fold needs epi none / relu / silu on a wide product (M >= 1024, N >= 1024, not the long-K tile) or glu, K >= 64", who);
+    }
+}
+
+pk_status pk_diag_gemm_tile_form(int M, int N, int K, int64_t lda, int64_t ldw, int epi, int ln, int32_t *form) {
+    return guard([&] {
+        need(form, "form");
+        GemmArgs g{nullptr, lda, nullptr, ldw, nullptr, nullptr, N, nullptr, N, 1.0f, M, N, K};
+        tile_product_checks(g, epi, ln != 0, "pk_diag_gemm_tile_form");
+        *form = (int32_t)gemm_tile_form(g, epi);
+    });
+}
+
+pk_status pk_diag_gemm_tile(pk_gemm_tile_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const int M = d->M, N = d->N, K = d->K, epi = d->epi;
+        need(d->A && d->W && d->out, "A/W/out");
+        const bool ln = d->ln_g != nullptr;
+        need(ln == (d->ln_b != nullptr), "gamma and beta: both or neither");
+        need(!ln || K <= 1024, "LayerNorm: K <= 1024");
+        GemmArgs g{nullptr, d->lda, nullptr, d->ldw, nullptr, nullptr, d->ldo, nullptr, d->ldr, d->alpha, M, N, K};
+        g.remap_rows = d->remap_rows; g.remap_gs = d->remap_gs; g.remap_rs = d->remap_rs; g.remap_cs = d->remap_cs;
+        g.sigma_cols = d->sigma_cols;
+        need(d->sigma_cols >= 0 && d->sigma_cols % 16 == 0 && d->sigma_cols <= N, "sigma_cols: a multiple of 16, <= N");
+        need(epi != EPI_RESID || (d->resid && d->ldr >= N), "resid, ldr >= N");
+        tile_product_checks(g, epi, ln, "pk_diag_gemm_tile");
+        // every offset the product may write lies inside out
+        if (d->remap_rows > 0) {
+            need(d->remap_gs >= 0 && d->remap_rs >= 0 && d->remap_cs >= 0 && d->sigma_cols == 0, "remap strides (and no sigma_cols)");
+            const int64_t last = (int64_t)((M - 1) / d->remap_rows) * d->remap_gs + (int64_t)(std::min(M, d->remap_rows) - 1) * d->remap_rs + (int64_t)(N - 1) * d->remap_cs;
+            need(last < d->out_words, "out_words: the remapped output must fit");
+        } else {
+            need(d->remap_rows == 0 && d->ldo >= N && (int64_t)(M - 1) * d->ldo + N <= d->out_words, "ldo >= N, out_words >= (M - 1) ldo + N");
+        }
+        need_device();
+        const int wrows = epi == EPI_GLU ? 2 * N : N;
+        // an operand at its pitch, the words of every row past `cols` replaced by the NaN pattern
+        auto up_padded = [](DevBuf &buf, const float *src, int64_t rows, int64_t cols, int64_t ld) {
+            std::vector<float> h(src, src + (size_t)rows * ld);
+            const uint32_t nan_word = 0x7fc5a5a5u;
+            for (int64_t i = 0; i < rows; ++i)
+                for (int64_t k = cols; k < ld; ++k) memcpy(&h[(size_t)i * ld + k], &nan_word, 4);
+            up(buf, h.data(), h.size() * 4);
+        };
+        DevBuf a, w, b, r, o, gb, st, dense;
+        up_padded(a, d->A, M, K, d->lda);
+        up_padded(w, d->W, wrows, K, d->ldw);
+        if (d->bias) up(b, d->bias, (size_t)wrows * 4);
+        if (epi == EPI_RESID) up_padded(r, d->resid, M, N, d->ldr);
+        o.reserve((size_t)d->out_words * 4);
+        PK_HIP(hipMemsetD32(o.p, 0x7fc5a5a5, (size_t)d->out_words));
+        g.A = a.as<float>(); g.W = w.as<float>(); g.bias = d->bias ? b.as<float>() : nullptr; g.out = o.as<float>();
+        g.resid = epi == EPI_RESID ? r.as<float>() : nullptr;
+        if (ln) {                                                      // the statistics pass reads dense rows
+            const float *X = a.as<float>();
+            if (d->lda != K) {
+                dense.reserve((size_t)M * K * 4);
+                PK_HIP(hipMemcpy2D(dense.p, (size_t)K * 4, a.p, (size_t)d->lda * 4, (size_t)K * 4, (size_t)M, hipMemcpyDeviceToDevice));
+                X = dense.as<float>();
+            }
+            up_rows(gb, {d->ln_g, d->ln_b}, K);
+            st.reserve((size_t)M * 2 * 4);
+            launch_layernorm_stats(X, M, K, d->eps, st.as<float>(), nullptr);
+            g.ln_g = gb.as<float>(); g.ln_b = gb.as<float>() + K; g.ln_eps = d->eps; g.ln_stats = st.as<float>();
+        }
+        d->form = (int32_t)launch_gemm_tile(g, epi, nullptr);           // launch_gemm's own tile branch: the form it hands back is the one it switched on
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(d->out, o, (size_t)d->out_words * 4);
+    });
+}
+
 pk_status pk_diag_ln_gemm(int M, int N, int K, const float *A, const float *pre_gamma, const float *pre_beta, const float *gamma, const float *beta, float eps,
                           const float *W, const float *bias, int epi, int fold, float *out, float *y1) {
     return guard([&] {

@@ -206,33 +206,76 @@ static void launch_one(const GemmArgs &a, hipStream_t s) {
 // behind SCHED = 2 or level on every shape; the GLU product without the fold is the only level one (139.0 / 139.2 TF).  One exception, from the
 // kernel trace of the bench (profiles/r07_kernel_stats_ab.txt): the long-K tile without an epilogue function (sub_proj, once per step) is
 // slower with it (172 -> 185 us), so that product keeps the compiler-placed loop.
-constexpr int kSbSched = 2;
-template <int EPI>
-static void launch_epi(const GemmArgs &a, hipStream_t s) {
-    if (a.K < 64) { launch_one<64, 64, EPI>(a, s); return; }           // pipelined kernels need >= 2 K tiles
+constexpr int kSbSched = kGemmTileSched;
+// Which instantiation a product takes (kernels.hpp: GemmTileForm).  launch_gemm switches on this function's result and pk_diag_gemm_tile reports it:
+// every threshold of the tile kernels lives here and nowhere else.
+GemmTileForm gemm_tile_form(const GemmArgs &a, int epi) {
+    const bool lna = a.ln_stats != nullptr;
+    if (epi == EPI_GLU) {
+        if (a.K < 64) return gemm_tile_nt_form(128, 128, EPI_GLU);
+        return gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, lna, kSbSched, EPI_GLU);
+    }
+    if (a.K < 64) return gemm_tile_nt_form(64, 64, epi);                // pipelined kernels need >= 2 K tiles
     // measured table: profiles/r01_gemm_sweep_v5.txt (128x128 tile on 8 waves of 32x64 wins for every wide output and for the
     // 321k-row subsampling products; long-K / narrow-N products like fc2 of the 110M model take 128x64)
     // long-K products whose 128x128 tiles fill the chip exactly once (fc2 / sub_proj of the 110M model: 252 tiles for 256 CUs): one
     // 8-wave workgroup per CU, single-buffered -- 8 waves of 64 x 32, BK 32 (round 6): 2-3 % ahead of the BK 64 tile of 32 x 64 waves in the sweep
     // (profiles/r06_gemm_sweep_fc2_variants.txt: 137 vs 140.5 us), which was itself -6 % against two 128x64 workgroups
     const int64_t tiles128 = (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (a.M >= 1024 && a.N >= 256 && a.K >= 1024 && a.K % 64 == 0 && tiles128 <= 256) { launch_gemm_pipe<2, 4, 2, 1, 32, EPI, 1, false, EPI == EPI_NONE ? 0 : kSbSched>(a, s); return; }
+    if (a.M >= 1024 && a.N >= 256 && a.K >= 1024 && a.K % 64 == 0 && tiles128 <= 256)
+        return gemm_tile_form_of(TILE_PIPE, 2, 4, 2, 1, 1, false, epi == EPI_NONE ? 0 : kSbSched, epi);
     // round 2: the SINGLE-buffered loop (template parameter NBUF = 1: half the LDS, two barriers per K tile) is ahead of the double-buffered
     // one on every large shape, in the micro-benchmark (tools/ubench/gemm_sweep ml: main loop 130-135 vs 118-125 TF) and, by less, in the
     // engine (fc2 -8 %, fc1 -3.6 %, qkv -5 %, GLU -3 %).
-    if constexpr (EPI == EPI_NONE || EPI == EPI_RELU || EPI == EPI_SILU) {
-        if (a.ln_stats) { launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, true, kSbSched>(a, s); return; }    // (gemm_ln_stats_applies: the wide-output tile below, LayerNorm applied while staging A)
+    const GemmTileForm wide = gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, false, kSbSched, epi);
+    if (lna && epi != EPI_RESID) return gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, true, kSbSched, epi);   // (gemm_ln_stats_applies: the wide-output tile, LayerNorm applied while staging A)
+    if (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))) return wide;
+    if (a.M >= 1024 && a.N >= 256 && a.K >= 1024) return gemm_tile_form_of(TILE_PIPE, 2, 2, 2, 1, 2, false, 0, epi);
+    if (a.M >= 1024 && a.N >= 256) return wide;                         // out_proj / pw2 on 128x128 / 8 waves (0.81 -> 0.77 ms per step)
+    return gemm_tile_form_of(TILE_PIPE, 2, 2, 1, 1, 2, false, 0, epi);
+}
+[[noreturn]] static void tile_no_form(int form, int epi) {
+    fprintf(stderr, "parakeet_amd: internal error: launch_gemm has no tile kernel for form %d with epilogue %d\n", form, epi);
+    abort();
+}
+// One case per tile geometry and loop; the `if constexpr` beside it names the epilogues that geometry is instantiated for (kGemmTileForms).
+template <int EPI>
+static void launch_tile(const GemmArgs &a, GemmTileForm f, hipStream_t s) {
+    if (gemm_tile_form_epi(f) != EPI) tile_no_form(f, EPI);
+    switch (gemm_tile_form_shape(f)) {
+    case gemm_tile_form_shape(gemm_tile_nt_form(64, 64, 0)):
+        if constexpr (EPI != EPI_GLU) { launch_one<64, 64, EPI>(a, s); return; }
+        break;
+    case gemm_tile_form_shape(gemm_tile_nt_form(128, 128, 0)):
+        if constexpr (EPI == EPI_GLU) { launch_one<128, 128, EPI>(a, s); return; }
+        break;
+    case gemm_tile_form_shape(gemm_tile_form_of(TILE_PIPE, 2, 4, 2, 1, 1, false, 0, 0)):
+        if constexpr (EPI == EPI_NONE) { launch_gemm_pipe<2, 4, 2, 1, 32, EPI, 1, false, 0>(a, s); return; }
+        break;
+    case gemm_tile_form_shape(gemm_tile_form_of(TILE_PIPE, 2, 4, 2, 1, 1, false, kSbSched, 0)):
+        if constexpr (EPI == EPI_RELU || EPI == EPI_SILU || EPI == EPI_RESID) { launch_gemm_pipe<2, 4, 2, 1, 32, EPI, 1, false, kSbSched>(a, s); return; }
+        break;
+    case gemm_tile_form_shape(gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, false, kSbSched, 0)):
+        launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, false, kSbSched>(a, s);
+        return;
+    case gemm_tile_form_shape(gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, true, kSbSched, 0)):
+        if constexpr (EPI != EPI_RESID) { launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, true, kSbSched>(a, s); return; }
+        break;
+    case gemm_tile_form_shape(gemm_tile_form_of(TILE_PIPE, 2, 2, 2, 1, 2, false, 0, 0)):
+        if constexpr (EPI != EPI_GLU) { launch_gemm_pipe<2, 2, 2, 1, 32, EPI>(a, s); return; }
+        break;
+    case gemm_tile_form_shape(gemm_tile_form_of(TILE_PIPE, 2, 2, 1, 1, 2, false, 0, 0)):
+        if constexpr (EPI != EPI_GLU) { launch_gemm_pipe<2, 2, 1, 1, 32, EPI>(a, s); return; }
+        break;
+    default: break;
     }
-    if (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, false, kSbSched>(a, s);
-    else if (a.M >= 1024 && a.N >= 256 && a.K >= 1024) launch_gemm_pipe<2, 2, 2, 1, 32, EPI>(a, s);
-    else if (a.M >= 1024 && a.N >= 256) launch_gemm_pipe<4, 2, 1, 2, 32, EPI, 1, false, kSbSched>(a, s);   // out_proj / pw2 on 128x128 / 8 waves (0.81 -> 0.77 ms per step)
-    else launch_gemm_pipe<2, 2, 1, 1, 32, EPI>(a, s);
+    tile_no_form(f, EPI);
 }
 
 void launch_gemm_smallm(const GemmArgs &a, int epi, hipStream_t s);   // kernels/gemm_smallm.hip
 
-// The products whose LayerNorm can ride on the A staging of the fp32 tile kernel (GemmArgs::ln_stats): exactly the shapes launch_epi / launch_gemm
-// send to the single-buffered 128 x 128 / BK 32 tile -- wide outputs of large batches (fc1, qkv) and the GLU product.
+// The products whose LayerNorm can ride on the A staging of the fp32 tile kernel (GemmArgs::ln_stats): exactly the shapes gemm_tile_form
+// sends to the single-buffered 128 x 128 / BK 32 tile -- wide outputs of large batches (fc1, qkv) and the GLU product.
 bool gemm_ln_stats_applies(const GemmArgs &a, int epi) {
     if (!a.ln_g || !a.ln_b || !a.ln_stats || a.a_bf16 || a.out_bf16 || a.fast_act || a.a_sigma || a.W_sig) return false;
     if (a.M <= kSmallMRows || a.K < 64 || a.K % 32 != 0 || (a.lda & 3) != 0 || (a.ldw & 3) != 0) return false;
@@ -243,24 +286,38 @@ bool gemm_ln_stats_applies(const GemmArgs &a, int epi) {
     return a.M >= 1024 && a.N >= 1024;
 }
 
+bool gemm_tile_applies(const GemmArgs &a) { return !(a.M <= kSmallMRows && a.K % 64 == 0); }
+
+const char *gemm_tile_refusal(const GemmArgs &a, int epi) {
+    if (epi == EPI_GLU && a.sigma_cols != 0) return "a GLU product with sigma_cols on a tile kernel (the wide epilogue reads the sigma columns without the GLU column mapping)";
+    if (epi == EPI_RESID && a.sigma_cols != 0) return "a residual product with sigma_cols on a tile kernel (the wide epilogue adds the residual by output position, the scalar one by natural column)";
+    if (a.K < 32 || a.K % 32 != 0) return "K is no positive multiple of 32 (the tile kernels run K / 32 whole K tiles)";
+    if ((a.lda & 3) != 0 || (a.ldw & 3) != 0) return "lda or ldw is no multiple of 4 (the tile kernels stage their operands with 16-byte loads)";
+    return nullptr;
+}
+
+// A product on the tile kernels (gemm_tile_applies).  Returns the form it launched: the one value both the dispatch below and pk_diag_gemm_tile's report come from.
+GemmTileForm launch_gemm_tile(const GemmArgs &a, int epi, hipStream_t s) {
+    if (const char *why = gemm_tile_refusal(a, epi)) { fprintf(stderr, "parakeet_amd: internal error: %s\n", why); abort(); }
+    const GemmTileForm f = gemm_tile_form(a, epi);
+    switch (epi) {
+    case EPI_NONE: launch_tile<EPI_NONE>(a, f, s); break;
+    case EPI_RELU: launch_tile<EPI_RELU>(a, f, s); break;
+    case EPI_SILU: launch_tile<EPI_SILU>(a, f, s); break;
+    case EPI_RESID: launch_tile<EPI_RESID>(a, f, s); break;
+    case EPI_GLU: launch_tile<EPI_GLU>(a, f, s); break;
+    default: break;
+    }
+    return f;
+}
+
 void launch_gemm(const GemmArgs &a, int epi, hipStream_t s) {
     if (a.ln_stats && !gemm_ln_stats_applies(a, epi)) { fprintf(stderr, "parakeet_amd: internal error: GemmArgs::ln_stats on a product the tile kernel does not fold it into\n"); abort(); }
     // up to a few hundred rows (streaming chunks, ONE utterance of up to a minute -- the reference's own benchmark protocol is batch 1):
     // one wavefront per 16x16 tile ((M/16)(N/16) independent waves) instead of a few dozen fat workgroups with a long K loop each.
     // Measured with tools/bench_reference_protocol.py: 10 s clip (M = 126) 6.3 -> 2.9 ms, 30 s (M = 376) 6.7 -> 4.3 ms per encoder pass.
-    if (a.M <= kSmallMRows && a.K % 64 == 0) { launch_gemm_smallm(a, epi, s); return; }
-    switch (epi) {
-    case EPI_NONE: launch_epi<EPI_NONE>(a, s); break;
-    case EPI_RELU: launch_epi<EPI_RELU>(a, s); break;
-    case EPI_SILU: launch_epi<EPI_SILU>(a, s); break;
-    case EPI_RESID: launch_epi<EPI_RESID>(a, s); break;
-    case EPI_GLU:
-        if (a.K < 64) launch_one<128, 128, EPI_GLU>(a, s);
-        else if (a.ln_stats) launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1, true, kSbSched>(a, s);
-        else launch_gemm_pipe<4, 2, 1, 2, 32, EPI_GLU, 1, false, kSbSched>(a, s);
-        break;
-    default: break;
-    }
+    if (!gemm_tile_applies(a)) { launch_gemm_smallm(a, epi, s); return; }
+    launch_gemm_tile(a, epi, s);
 }
 
 // bf16 operands / fp32 accumulate (a.W points to bf16 weights [N][K]); K % 64 == 0

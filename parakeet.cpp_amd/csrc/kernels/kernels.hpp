@@ -209,6 +209,49 @@ constexpr GemmSmallmForms gemm_smallm_forms() {
 }
 constexpr GemmSmallmForms kGemmSmallmForms = gemm_smallm_forms();
 static_assert(kGemmSmallmForms.n == kGemmSmallmFormCount, "kGemmSmallmForms must list every instantiation");
+// The form of a tile-kernel launch (kernels/gemm.hip, gemm_pipe.hpp), by the function launch_gemm switches on for every product it does not send to
+// the small-M kernels: value = gemm_tile_form_of(...).
+//   kernel: gemm_nt_kernel (K < 64: one K tile) or gemm_pipe_kernel
+//   wgm x wgn waves of tm x tn 32 x 32 accumulators: the tile is (32 wgm tm) x (32 wgn tn); gemm_nt_kernel<BM, BN> is 2 x 2 waves of (BM / 64) x (BN / 64)
+//   nbuf:   LDS staging buffers (NBUF; gemm_nt_kernel: 2);  lna: the LayerNorm applied while A is staged (GemmArgs::ln_stats);  sched: SCHED of gemm_pipe_kernel
+//   epi:    the epilogue the kernel is instantiated for (GemmEpi)
+enum GemmTileKernel { TILE_NT = 0, TILE_PIPE = 1 };
+enum GemmTileForm : int {};
+constexpr GemmTileForm gemm_tile_form_of(int kernel, int wgm, int wgn, int tm, int tn, int nbuf, bool lna, int sched, int epi) {
+    return (GemmTileForm)((kernel << 20) | (wgm << 17) | (wgn << 14) | (tm << 11) | (tn << 8) | (nbuf << 6) | ((lna ? 1 : 0) << 5) | (sched << 3) | epi);
+}
+constexpr GemmTileForm gemm_tile_nt_form(int bm, int bn, int epi) { return gemm_tile_form_of(TILE_NT, 2, 2, bm / 64, bn / 64, 2, false, 0, epi); }
+constexpr int gemm_tile_form_epi(int f) { return f & 7; }
+constexpr int gemm_tile_form_shape(int f) { return f & ~7; }       // everything but the epilogue: what launch_gemm's switch has one case for
+GemmTileForm gemm_tile_form(const GemmArgs &a, int epi);          // of a product launch_gemm keeps (gemm_tile_applies; ln_stats: gemm_ln_stats_applies)
+bool gemm_tile_applies(const GemmArgs &a);                        // launch_gemm does NOT send the product to the small-M kernels
+// What no tile kernel can do (nullptr: nothing): a GLU or a residual product with sigma_cols (the wide epilogue's sigma read has no GLU column mapping,
+// and it adds the residual by output position where the scalar epilogue and the small-M kernels add it by natural column), K < 32 or
+// K % 32 != 0 (the K loop runs K / 32 whole tiles), lda / ldw no multiple of 4 (float4 staging loads).  launch_gemm aborts on these.
+const char *gemm_tile_refusal(const GemmArgs &a, int epi);
+// launch_gemm's tile branch alone: aborts on gemm_tile_refusal, launches, and returns the form it switched on (callers checked gemm_tile_applies and,
+// with ln_stats, gemm_ln_stats_applies)
+GemmTileForm launch_gemm_tile(const GemmArgs &a, int epi, hipStream_t s);
+constexpr int kGemmTileSched = 2;                                 // SCHED of every single-buffered tile (gemm.hip: the measurements)
+// Every form launch_gemm can take = every instantiation of the two kernels it launches: the 64 x 64 one-K-tile kernel without GLU and its 128 x 128 GLU
+// form; the long-K single-round tile (2 x 4 waves of 2 x 1; SCHED 0 without an epilogue function) without GLU; the wide single-buffered tile (4 x 2 waves
+// of 1 x 2) with every epilogue, and with the LayerNorm fold without the residual one; the double-buffered 128 x 64 and 64 x 64 tiles without GLU.
+constexpr int kGemmTileFormCount = 4 + 1 + 4 + 5 + 4 + 4 + 4;
+struct GemmTileForms { GemmTileForm v[kGemmTileFormCount]; int n; };
+constexpr GemmTileForms gemm_tile_forms() {
+    GemmTileForms t{};
+    for (int epi = EPI_NONE; epi <= EPI_RESID; ++epi) t.v[t.n++] = gemm_tile_nt_form(64, 64, epi);
+    t.v[t.n++] = gemm_tile_nt_form(128, 128, EPI_GLU);
+    for (int epi = EPI_NONE; epi <= EPI_RESID; ++epi) t.v[t.n++] = gemm_tile_form_of(TILE_PIPE, 2, 4, 2, 1, 1, false, epi == EPI_NONE ? 0 : kGemmTileSched, epi);
+    for (int epi = EPI_NONE; epi <= EPI_GLU; ++epi) t.v[t.n++] = gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, false, kGemmTileSched, epi);
+    for (int epi = EPI_NONE; epi <= EPI_GLU; ++epi)
+        if (epi != EPI_RESID) t.v[t.n++] = gemm_tile_form_of(TILE_PIPE, 4, 2, 1, 2, 1, true, kGemmTileSched, epi);
+    for (int epi = EPI_NONE; epi <= EPI_RESID; ++epi) t.v[t.n++] = gemm_tile_form_of(TILE_PIPE, 2, 2, 2, 1, 2, false, 0, epi);
+    for (int epi = EPI_NONE; epi <= EPI_RESID; ++epi) t.v[t.n++] = gemm_tile_form_of(TILE_PIPE, 2, 2, 1, 1, 2, false, 0, epi);
+    return t;
+}
+constexpr GemmTileForms kGemmTileForms = gemm_tile_forms();
+static_assert(kGemmTileForms.n == kGemmTileFormCount, "kGemmTileForms must list every instantiation");
 // same contract with bf16 operands and fp32 accumulation: a.W points to bf16 weights [N][K] (rounded once at upload), A is
 // rounded to bf16 while it is staged; K % 64 == 0.  Not bit-identical to the fp32 chain (kernels/gemm_bf16.hpp).
 void launch_gemm_bf16(const GemmArgs &a, int epi, hipStream_t s);

@@ -88,6 +88,9 @@ def test_no_gpu_is_a_loud_error(tmp_path):
     with pytest.raises(capi.PkError) as e:
         capi.diag_layernorm_sigma(np.zeros((2, 128), np.float32), np.ones(128, np.float32), np.zeros(128, np.float32))
     assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:             # the tile GEMM diagnostic: valid arguments, no device
+        capi.diag_gemm_tile(np.zeros((4, 96), np.float32), np.zeros((16, 96), np.float32))
+    assert e.value.code == -4
     with pytest.raises(capi.PkError) as e:             # the multi-GPU entry point as well
         capi.Group(str(wp), cfg)
     assert e.value.code == -4
@@ -130,6 +133,57 @@ def test_smallm_gemm_form_table_and_argument_checks_need_no_device():
     with pytest.raises(capi.PkError) as e:
         capi.diag_gemm_smallm(np.zeros((4, 96), np.float32), np.zeros((16, 96), np.float32))
     assert e.value.code == -1
+
+
+def test_tile_gemm_form_table_queries_and_argument_checks_need_no_device():
+    """pk_diag_gemm_tile_forms (what tests/test_gpu_tile_gemm.py::test_every_form_has_a_case compares its cases with) and pk_diag_gemm_tile_form are host
+    arithmetic: one form per instantiation launch_gemm can take, the tiles the comments of tests/test_gpu_gemm_schedule.py name for its shapes; and
+    pk_diag_gemm_tile refuses what no tile kernel can do, and malformed arguments, before it looks for a device."""
+    NT64, NT128, LONGK, WIDE, T128X64, T64X64 = (64, 64), (128, 128), (2, 4, 2, 1), (4, 2, 1, 2), (2, 2, 2, 1), (2, 2, 1, 1)
+    four = ("none", "relu", "silu", "resid")
+    want = {("nt", NT64, 2, False, 0, e) for e in four} | {("nt", NT128, 2, False, 0, "glu")}
+    want |= {("pipe", LONGK, 1, False, 0 if e == "none" else 2, e) for e in four}
+    want |= {("pipe", WIDE, 1, False, 2, e) for e in capi.EPI} | {("pipe", WIDE, 1, True, 2, e) for e in ("none", "relu", "silu", "glu")}
+    want |= {("pipe", T128X64, 2, False, 0, e) for e in four} | {("pipe", T64X64, 2, False, 0, e) for e in four}
+    every = capi.diag_gemm_tile_forms()
+    assert len(every) == 26 and set(every) == want              # (no duplicates; every entry decodes to an instantiation that exists)
+    q = capi.diag_gemm_tile_form
+    assert q(8064, 512, 2048, epi="resid") == ("pipe", LONGK, 1, False, 2, "resid")      # fc2: the long-K single-round tile
+    assert q(8064, 512, 2048) == ("pipe", LONGK, 1, False, 0, "none")                    # ... without an epilogue function: the compiler-placed loop
+    assert q(8064, 2048, 512, epi="silu") == ("pipe", WIDE, 1, False, 2, "silu")         # fc1: the wide tile
+    assert q(8064, 2048, 512, epi="silu", ln=True) == ("pipe", WIDE, 1, True, 2, "silu")
+    assert q(8064, 512, 512, epi="resid") == ("pipe", WIDE, 1, False, 2, "resid")        # out_proj / pw2
+    assert q(8064, 512, 512, epi="glu", ln=True) == ("pipe", WIDE, 1, True, 2, "glu")
+    assert q(1601, 2048, 512, epi="silu") == ("pipe", WIDE, 1, False, 2, "silu")         # the smallest M past the small-M kernels
+    assert q(16128, 512, 2048, epi="resid") == ("pipe", T128X64, 2, False, 0, "resid")   # fc2 at twice the rows: 504 tiles of 128 x 128 are no single round
+    assert q(65536, 256, 1024) == ("pipe", WIDE, 1, False, 2, "none")
+    assert q(1537, 512, 512, epi="relu")[0] == "pipe" and q(1, 5, 32) == ("nt", NT64, 2, False, 0, "none")
+    for bad in (dict(M=1536, N=512, K=512), dict(M=126, N=512, K=512),                   # the small-M family
+                dict(M=2000, N=64, K=48), dict(M=2000, N=64, K=80), dict(M=2000, N=64, K=16),   # K % 32 != 0
+                dict(M=2000, N=64, K=96, lda=98), dict(M=2000, N=64, K=96, ldw=97), dict(M=2000, N=64, K=96, lda=101),
+                dict(M=8064, N=512, K=2048, ln=True), dict(M=8064, N=512, K=512, epi="resid", ln=True), dict(M=8064, N=512, K=512, ln=True),
+                dict(M=8064, N=2048, K=32, ln=True)):
+        with pytest.raises(capi.PkError) as e:
+            q(**bad)
+        assert e.value.code == -7, bad
+    for bad in (dict(M=0, N=5, K=32), dict(M=2000, N=64, K=96, lda=92), dict(M=2000, N=64, K=96, ldw=64)):
+        with pytest.raises(capi.PkError) as e:
+            q(**bad)
+        assert e.value.code == -1, bad
+    A, W = np.zeros((4, 96), np.float32), np.zeros((40, 96), np.float32)
+    for bad in (dict(epi="glu", sigma_cols=16), dict(epi="resid", resid=np.zeros((4, 40), np.float32), sigma_cols=16), dict(lda=98), dict(ldw=99), dict(ln=(np.ones(96, np.float32), np.zeros(96, np.float32)))):
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_gemm_tile(A, W, **bad)
+        assert e.value.code == -7, bad
+    for bad in (np.zeros((4, 40), np.float32), np.zeros((4, 64), np.float32)):           # K % 32 != 0; a small-M shape
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_gemm_tile(bad, np.zeros((40, bad.shape[1]), np.float32))
+        assert e.value.code == -7
+    for bad in (dict(sigma_cols=8), dict(sigma_cols=48), dict(epi="resid"), dict(ldo=39), dict(out_words=4 * 40 - 1), dict(remap=(2, 80, 1, 2), out_words=159),
+                dict(epi="resid", resid=np.zeros((4, 40), np.float32), ldr=36)):
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_gemm_tile(A, W, **bad)
+        assert e.value.code == -1, bad
 
 
 def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
