@@ -592,7 +592,7 @@ int pk_diag_gemm_smallm_forms(int32_t *out, int cap) {
     return kGemmSmallmForms.n;
 }
 
-// One product of the small-M family, staged the way a streaming session / the single-clip encoder stages it (stream.cpp ln_gemm, engine.cpp run_gemm).
+// One product of the small-M family, staged the way a streaming session / the single-clip encoder stages it (conformer_block.hpp ln_gemm, engine.cpp run_gemm).
 pk_status pk_diag_gemm_smallm(pk_smallm_gemm_diag *d) {
     return guard([&] {
         need(d, "args");

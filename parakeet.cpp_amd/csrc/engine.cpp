@@ -1,5 +1,7 @@
-// parakeet.cpp_amd/csrc/engine.cpp -- model lifetime, weight upload / derived tables, stage drivers.
+// parakeet.cpp_amd/csrc/engine.cpp -- model lifetime, weight upload / derived tables, stage drivers.  (The Conformer block's products, FFNs and
+// norms are conformer_block.hpp's, shared with the streaming encoder; run_layers keeps attention and the depthwise conv.)
 #include "engine.hpp"
+#include "conformer_block.hpp"
 #include "dec_pack.hpp"
 
 #include <algorithm>
@@ -843,60 +845,10 @@ void Model::run_subsample(Workspace &w, const float *d_feats, int B, int Tm, flo
     (void)W1; (void)H1;
 }
 
-// y = LayerNorm(x) -> n, then the product g (A = n) -- or, for a handful of rows on the fp32 chain kernels, the product with the norm folded in
-// (gemm_smallm_ln_kernel: bit for bit the same; one launch instead of two).  kLnFoldRows: beyond about one round of its workgroups the redundant
-// normalisation (every 32-column workgroup normalises its 16 rows) costs more than the LayerNorm launch it saves.
+// The LayerNorm in front of a product folds into it (conformer_block.hpp: ln_folds; gemm_smallm_ln_kernel, bit for bit the same, one launch instead
+// of two) for a handful of rows only.  kLnFoldRows: beyond about one round of its workgroups the redundant normalisation (every 32-column
+// workgroup normalises its 16 rows) costs more than the LayerNorm launch it saves.  (This encoder only; not re-measured since.)
 static constexpr int kLnFoldRows = 256;
-bool Model::ln_folds(const GemmArgs &g, int epi, int64_t rows) const {
-    return !cfg.gemm_bf16 && rows <= kLnFoldRows && g.W_sig && gemm_smallm_ln_applies(g, epi);
-}
-// Large fp32 batches (round 6; round-5 verdict item 4): the LayerNorm in front of a wide product as a STATISTICS pass (launch_layernorm_stats: one read of x,
-// {mean, rstd} per row into the buffer the normalised rows used to occupy) with the product's tile kernel normalising while it stages A (gemm_pipe.hpp: LNA)
-// -- the same values bit for bit (tests/test_gpu_primitives.py), without the write and the re-read of the normalised tensor.
-// MEASURED SLOWER, so OFF in production: the LayerNorm launches of a 64 x 10 s step go from 0.87 to 0.68 ms (statistics 7.2 us against 13 us per launch), but the
-// products that take the norm pay more than that -- fc1 152 -> 163 us with the three operations per element in front of the staging stores, 167 us with
-// them moved under the MFMAs of an earlier sub-step (the wait for the K tile in flight moves with them), qkv + 5 %, pw1 + 8-12 %: the step 18.46 -> 18.87 / 19.1 ms
-// (profiles/r06_ln_stats_fold_ab.txt).  The global -> VGPR -> LDS staging is what the fp32 loop is bound by; anything added to it costs more
-// than a memory-bound launch of 13 us.  (The engine's statistics path existed up to 4fb176f, switched on by PK_LN_STATS=1 in EXPERIMENTAL builds; the
-// kernels stay, reached by pk_diag_ln_gemm.)
-// norm_done: n holds the normalised rows already (a previous kernel wrote them)
-void Model::ln_gemm(const char *name, const GemmArgs &g, int epi, const float *ng, const float *nb, bool norm_done, int ymode, const float *x, float *n,
-                    int64_t rows, hipStream_t s) {
-    const int d = cfg.hidden_size;
-    if (!norm_done) {
-        GemmArgs fg = g;
-        fg.A = x; fg.lda = d; fg.a_sigma = 0; fg.a_bf16 = 0; fg.ln_g = ng; fg.ln_b = nb; fg.ln_eps = 1e-5f;
-        if (ln_folds(fg, epi, rows)) { run_gemm(name, fg, epi, s); return; }
-        KL("layernorm", 0.0, (cfg.gemm_bf16 ? 1.5 : 2.0) * rows * d * 4, launch_layernorm(x, rows, d, ng, nb, 1e-5f, n, s, ymode));
-    }
-    run_gemm(name, g, epi, s);
-}
-
-// FeedForward::forward (src/encoder.cpp:39-46): x += 0.5 * fc2(silu(fc1(LN(x))))
-void Model::ffn(Workspace &w, const LayerW &L, bool second, int64_t rows, hipStream_t s, bool norm_done, const SigW *sg) {
-    const int d = cfg.hidden_size, f = cfg.ffn_intermediate;
-    float *x = w.x.as<float>(), *n = w.n.as<float>(), *h = w.hbuf.as<float>();
-    // bf16 mode: the normalised rows and the fc1 activations exist only as GEMM operands -- their producers round them to bf16 (RNE, the
-    // rounding the GEMM's staging path would apply: same operand values) and store HALF the bytes in the same buffers.
-    // sg (small batches, fp32): the same buffers in the sigma K layout, the products on the tiled weight copies (run_layers).
-    const int a16 = cfg.gemm_bf16 ? 1 : 0;
-    GemmArgs g1{n, d, second ? L.ffn2_w1 : L.ffn1_w1, d, second ? L.ffn2_b1 : L.ffn1_b1, h, f, nullptr, 0, 1.0f, (int)rows, f, d};
-    g1.a_bf16 = a16; g1.out_bf16 = a16;
-    g1.fast_act = a16;
-    // bf16 mode, large batches: the fc1 activations live in 32 x 16 blocks between fc1's register epilogue and fc2's LDS-DMA
-    // (GemmArgs::out_blocked / a_blocked: every store instruction of the epilogue writes one contiguous KB); h holds rows rounded up to 32
-    const bool blocked = a16 && !sg && gemm_bf16_blocked_handoff((int)rows, f, d, EPI_SILU, true) && gemm_bf16_blocked_handoff((int)rows, d, f, EPI_RESID, false) &&
-                         (size_t)((rows + 31) / 32 * 32) * f * 2 <= w.hbuf.cap;
-    g1.out_blocked = blocked ? 1 : 0;
-    if (sg) { g1.a_sigma = 1; g1.W_sig = second ? sg->ffn2_w1 : sg->ffn1_w1; g1.sigma_cols = f; }
-    // (the first FFN's norm rides on the previous block's final_norm_ kernel, see run_layers -- unless the product folds it in: ln_gemm)
-    ln_gemm("ffn_fc1_silu", g1, EPI_SILU, second ? L.ffn2_ng : L.ffn1_ng, second ? L.ffn2_nb : L.ffn1_nb, norm_done, sg ? 2 : a16, x, n, rows, s);
-    GemmArgs g2{h, f, second ? L.ffn2_w2 : L.ffn1_w2, f, second ? L.ffn2_b2 : L.ffn1_b2, x, d, x, d, 0.5f, (int)rows, d, f};
-    g2.a_bf16 = a16;
-    g2.a_blocked = blocked ? 1 : 0;
-    if (sg) { g2.a_sigma = 1; g2.W_sig = second ? sg->ffn2_w2 : sg->ffn1_w2; }
-    run_gemm("ffn_fc2_resid", g2, EPI_RESID, s);
-}
 
 // FastConformerEncoder::forward (src/encoder.cpp:253-271) -> w.x [B][T][d]
 void Model::run_encoder(Workspace &w, const float *d_feats, int B, int Tm, int stop_layer, int stop_stage, hipStream_t s) {
@@ -912,7 +864,6 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
     const int d = cfg.hidden_size, T = w.t_max();
     if (rg) B = w.rag.B;
     const int64_t rows = w.rows(B);
-    float *x = w.x.as<float>(), *n = w.n.as<float>();
     if (stop_layer < 0 || stop_layer > cfg.num_layers) { stop_layer = cfg.num_layers; stop_stage = 0; }
     if (stop_layer == 0 && stop_stage == 0) return;
     float *att_scratch_p = nullptr;
@@ -933,7 +884,7 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
     const int pos_T = ptab.T, P = 2 * pos_T - 1;                     // its rows (built for pos_T >= T frames)
     const DevBuf &pos_proj = ptab.proj, &pos_cvec = ptab.cvec;
     const int P_loc = att_left + att_right + 1;                      // local mode: rows of the local table
-    const int a16 = cfg.gemm_bf16 ? 1 : 0;                           // bf16 mode: LayerNorm outputs stored as bf16 GEMM operands (ffn())
+    const int a16 = cfg.gemm_bf16 ? 1 : 0;                           // bf16 mode: LayerNorm outputs stored as bf16 GEMM operands (ConformerBlock::ffn)
     const bool att16 = attn_bf16(T);                                 // ... and q / k / v as bf16 for the bf16-MFMA attention kernel
     if (rg) {
         const int want = att16 ? relpos_attention_bf16_block_rows(d / cfg.num_heads) : 32;
@@ -941,32 +892,24 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
         w.rv.att.pos_T = pos_T;
     }
     const SeqRag no_rag;
-    // Small batches (rows <= kSmallMRows: one clip, the reference's own benchmark protocol): every product is a latency-bound chain of
-    // dependent MFMAs (kernels/gemm_smallm.hip).  They run on the tiled sigma-K weight copies with sigma-K activations -- written that way by
-    // their producers (LayerNorm mode 2, sigma_cols of fc1, the attention context, the depthwise conv) -- so nothing but the MFMAs is on the
-    // chain; the residual stream x stays natural.  Same arithmetic, same bits.
+    // Small batches (rows <= kSmallMRows: one clip, the reference's own benchmark protocol) run on the tiled sigma-K weight copies with sigma-K
+    // activations, so nothing but the MFMAs is on the chain (BlockMode::sigma).  Same arithmetic, same bits.
     const std::vector<SigW> *sigv = (!a16 && rows <= kSmallMRows) ? &sigma_weights() : nullptr;
     const bool sgm = sigv && !sigv->empty();
-    const int ymode = sgm ? 2 : a16;                                 // LayerNorm / attention / conv output mode: 0 fp32, 1 bf16, 2 fp32 sigma
-    bool ffn1_norm_done = false;                                     // (ln_gemm: n holds the next ffn1's normalised rows)
+    BlockMode mode;                                                  // (conformer_block.hpp: what each field means and which encoder sets what)
+    mode.bf16 = a16; mode.sigma = sgm; mode.copies = sgm ? sigv : nullptr;
+    mode.fold_max_rows = kLnFoldRows; mode.handoff = BlockMode::BLOCKED; mode.fast_act = a16;
+    mode.qkv_sigma_cols = att16 ? 0 : 2 * d; mode.qkv_out_bf16 = att16; mode.ctx_bf16 = a16;
+    const int ymode = mode.act_mode();                               // LayerNorm / attention / conv output mode: 0 fp32, 1 bf16, 2 fp32 sigma
+    ConformerBlock blk{*this, mode, s, rows, w.x.as<float>(), w.n.as<float>(), w.hbuf.as<float>(), w.hbuf.cap};
     for (int l = first_layer; l < cfg.num_layers; ++l) {
         if (l > stop_layer || (l == stop_layer && stop_stage == 0)) break;
         const LayerW &L = layers[l];
         const int stage_cap = (l == stop_layer) ? stop_stage : 5;
-        const SigW *sg = sgm ? &(*sigv)[l] : nullptr;
-        ffn(w, L, false, rows, s, ffn1_norm_done, sg);                               // ffn1_  :197
-        ffn1_norm_done = false;
+        blk.ffn(l, false);                                           // ffn1_  :197
         if (stage_cap == 1) break;
-        // ConformerAttention::forward  :180-186
-        {
-            // q and k columns in the sigma layout (MFMA operands of the attention kernel), v natural
-            GemmArgs g{n, d, L.wqkv, d, L.bqkv, w.qkv.as<float>(), 3 * d, nullptr, 0, 1.0f, (int)rows, 3 * d, d};
-            g.sigma_cols = att16 ? 0 : 2 * d;
-            g.a_bf16 = a16;
-            g.out_bf16 = att16 ? 1 : 0;
-            if (sg) { g.a_sigma = 1; g.W_sig = sg->wqkv; }
-            ln_gemm("attn_qkv", g, EPI_NONE, L.att_ng, L.att_nb, false, ymode, x, n, rows, s);
-        }
+        // ConformerAttention::forward  :180-186 (q and k columns in the sigma layout -- MFMA operands of the attention kernel --, v natural; or all bf16)
+        blk.qkv(l, w.qkv.as<float>());
         const int hd = d / cfg.num_heads;
         double fl = 0.0;                                             // QK^T + QP^T (needed band) + AV over every (utterance, head)
         if (local) {                                                 // local mode: the band's (query, key) pairs instead of T^2
@@ -993,47 +936,19 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
                launch_relpos_attention(w.qkv.as<float>(), B, T, d, cfg.num_heads, pos_proj.as<float>() + (size_t)l * P * d, L.pos_u, L.pos_v,
                                        w.ctx.as<float>(), s, 0.0f, att_scratch_p, ymode, pos_T - T, rg ? w.rv.att : no_rag));
         }
-        {
-            GemmArgs g{w.ctx.as<float>(), d, L.wo, d, L.bo, x, d, x, d, 1.0f, (int)rows, d, d};
-            g.a_bf16 = a16;
-            if (sg) { g.a_sigma = 1; g.W_sig = sg->wo; }
-            run_gemm("attn_out_resid", g, EPI_RESID, s);
-        }
+        blk.att_out(l, w.ctx.as<float>());
         if (stage_cap == 2) break;
         // ConformerConvModule::forward  :59-75
-        {
-            GemmArgs g{n, d, L.pw1_w, d, L.pw1_b, w.g.as<float>(), d, nullptr, 0, 1.0f, (int)rows, d, d};
-            g.a_bf16 = a16;
-            g.fast_act = a16;
-            if (sg) { g.a_sigma = 1; g.W_sig = sg->pw1; }
-            ln_gemm("conv_pw1_glu", g, EPI_GLU, L.cv_ng, L.cv_nb, false, ymode, x, n, rows, s);
-        }
+        blk.pw1(l, blk.pw1_args(l, w.g.as<float>()));
         KL("dwconv_bn_silu", (double)rows * d * cfg.conv_kernel_size * 2.0, 2.0 * rows * d * 4,
            launch_dwconv_bn_silu(w.g.as<float>(), rg ? 1 : B, rg ? (int)rows : T, d, cfg.conv_kernel_size, L.dw_w, L.dw_b, L.bn_mean, L.bn_rstd, L.bn_g, L.bn_b,
                                  w.dwb.as<float>(), s, ymode, rg ? w.rv.dwc : no_rag));
-        {
-            GemmArgs g{w.dwb.as<float>(), d, L.pw2_w, d, L.pw2_b, x, d, x, d, 1.0f, (int)rows, d, d};
-            g.a_bf16 = a16;
-            if (sg) { g.a_sigma = 1; g.W_sig = sg->pw2; }
-            run_gemm("conv_pw2_resid", g, EPI_RESID, s);
-        }
+        blk.pw2(l, w.dwb.as<float>());
         if (stage_cap == 3) break;
-        ffn(w, L, true, rows, s, false, sg);                                         // ffn2_  :201
+        blk.ffn(l, true);                                            // ffn2_  :201
         if (stage_cap == 4) break;
-        const bool next_runs = l + 1 < cfg.num_layers && !(l + 1 > stop_layer || (l + 1 == stop_layer && stop_stage == 0));
-        bool next_folds = false;   // the next block's fc1 folds its own norm in (small fp32 batches): final_norm_ alone here
-        if (next_runs && sg) {
-            GemmArgs pg{x, d, layers[l + 1].ffn1_w1, d, nullptr, w.hbuf.as<float>(), cfg.ffn_intermediate, nullptr, 0, 1.0f, (int)rows, cfg.ffn_intermediate, d};
-            pg.W_sig = (*sigv)[l + 1].ffn1_w1; pg.ln_g = layers[l + 1].ffn1_ng; pg.ln_b = layers[l + 1].ffn1_nb;
-            next_folds = ln_folds(pg, EPI_SILU, rows);
-        }
-        if (next_runs && !next_folds) {   // final_norm_ :202 and the next block's ffn1_ norm :40 in one pass over the rows
-            KL("layernorm", 0.0, 3.0 * rows * d * 4,
-               launch_layernorm2(x, rows, d, L.fin_g, L.fin_b, layers[l + 1].ffn1_ng, layers[l + 1].ffn1_nb, 1e-5f, x, n, s, ymode));
-            ffn1_norm_done = true;
-        } else {
-            KL("layernorm", 0.0, 2.0 * rows * d * 4, launch_layernorm(x, rows, d, L.fin_g, L.fin_b, 1e-5f, x, s));   // final_norm_ :202
-        }
+        // final_norm_ :202 (with the next block's ffn1_ norm when that block runs and does not fold its own)
+        blk.end_block(l, l + 1 < cfg.num_layers && !(l + 1 > stop_layer || (l + 1 == stop_layer && stop_stage == 0)));
     }
 }
 

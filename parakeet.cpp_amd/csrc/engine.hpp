@@ -138,8 +138,6 @@ struct Workspace {
     int64_t rag_cap_samples = 0, rag_cap_clip = 0;
 };
 
-class StreamBatch;
-
 class Model {
   public:
     Model(const std::string &weights_path, const std::string &vocab_path, const pk_config &cfg);
@@ -249,8 +247,6 @@ class Model {
     const HostTensor &host_tensor(const std::string &name, const std::vector<int64_t> &expect_shape);
     float *dev_alloc(size_t n_floats);
 
-    friend class StreamBatch;
-
   private:
     std::unique_ptr<SafeTensors> st_;
     void validate_config();
@@ -258,11 +254,6 @@ class Model {
     void upload_weights();
     void gemm(const char *name, const float *A, int64_t lda, const float *W, int64_t ldw, const float *bias, float *out, int64_t ldo,
               int M, int N, int K, int epi, const float *resid, int64_t ldr, float alpha, hipStream_t s, int a_bf16 = 0, int out_bf16 = 0);
-    // LayerNorm + product, folded into one launch where the fp32 chain kernel can (engine.cpp)
-    bool ln_folds(const GemmArgs &g, int epi, int64_t rows) const;
-    void ln_gemm(const char *name, const GemmArgs &g, int epi, const float *ng, const float *nb, bool norm_done, int ymode, const float *x, float *n,
-                 int64_t rows, hipStream_t s);
-    void ffn(Workspace &w, const LayerW &L, bool second, int64_t rows, hipStream_t s, bool norm_done = false, const SigW *sg = nullptr);
 };
 
 // thread-local error slot of the C ABI

@@ -9,6 +9,8 @@
 // keeps only the pre-emphasis carry and the < 560 overlap samples per stream.  The per-chunk work is tiny (1-3 encoder frames
 // per stream): FFN / projection products run on the MFMA GEMM with M = S*c rows, the cached attention and causal conv are
 // exact-chain VALU kernels (kernels/stream.hip).  Bit-identical to the oracle's Stream (tests/test_gpu_stream.py).
+// The Conformer block's products, FFNs and norms are conformer_block.hpp's, shared with the offline encoder; encode_device keeps the cached
+// attention and the cached depthwise conv (or its fused tail).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +18,7 @@
 #include <utility>
 
 #include "capi_util.hpp"
+#include "conformer_block.hpp"
 #include "stream.hpp"
 
 namespace pk {
@@ -160,150 +163,61 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
     PK_HIP(hipMemcpy2DAsync(enc_in_.p, (size_t)consumable * rowb, mel_all_.p, (size_t)total * rowb, (size_t)consumable * rowb, S, hipMemcpyDeviceToDevice, st));
     ws_.size_for(cfg, S, 0, consumable);
     const int c = ws_.T;
-    float *x = ws_.x.as<float>(), *n = ws_.n.as<float>();
-    m_.run_subsample(ws_, enc_in_.as<float>(), S, consumable, x, st);
+    m_.run_subsample(ws_, enc_in_.as<float>(), S, consumable, ws_.x.as<float>(), st);
     const int Tp = left_ + c, P = 2 * Tp - 1;
     const float *ptab = pos_table(Tp);
     const int64_t rows = (int64_t)S * c;
     const int cache_rows = left_ > 0 ? left_ : 1;
-    // rows <= kSmallMRows: every product of the chunk is a gemm_smallm chain -- run them on the sigma-K weight copies with sigma-K activations (the
-    // producers below write that layout; x, the residual stream, stays natural)
+    // How this chunk runs the block (conformer_block.hpp: BlockMode says what each field means and which encoder sets what)
     const bool have_sig = sig_ && !sig_->empty();                  // (built at the top of this function by the first chunk that qualifies)
     const int sg = (!cfg.gemm_bf16 && rows <= kSmallMRows && have_sig) ? 1 : 0;
     // (tolerance-class mode: the copies are the bf16 operand tiles of the small-M bf16 kernel, GemmArgs::W_t16 -- a weight load reads one contiguous KB)
     const bool wt = cfg.gemm_bf16 && rows <= kSmallMRowsBf16 && have_sig;
     // Tolerance-class mode (pk_config.gemm_bf16; specification: the oracle's Stream in its gemm_bf16 mode): every product of the chunk takes bf16
-    // operands (kernels/gemm_smallm_bf16.hip for these few rows); the rows that exist only as GEMM operands -- LayerNorm outputs, the fc1
-    // activations -- are stored as bf16 by their producers (RNE, the rounding the GEMM would apply: same operand values, half the bytes);
-    // attention, depthwise conv and the caches stay fp32 arithmetic on the products' fp32 outputs.
+    // operands; attention, depthwise conv and the caches stay fp32 arithmetic on the products' fp32 outputs.
     const int a16 = cfg.gemm_bf16 ? 1 : 0;
-    const int lnm = a16 ? 1 : (sg ? 2 : 0);                                                               // launch_layernorm's output mode
-    const int f = cfg.ffn_intermediate;
-    float *hb = ws_.hbuf.as<float>();
-    // LayerNorm(x) -> n, then the product on n -- or, where the small-M bf16 kernel can fold the norm in, the product straight on x
-    // the previous block's final norm, when it rides on this block's first product (set at the end of a block, consumed by the next ffn1 fc1)
-    const float *pend_g = nullptr, *pend_b = nullptr;
-    float *x_other = nullptr;
-    // The LayerNorm of a product's input rows folds into the product where the kernel can (GemmArgs::ln_g; tolerance-class mode:
-    // kernels/gemm_smallm_bf16.hip, exact mode: gemm_smallm_ln_kernel in kernels/gemm_smallm.hip, bit for bit) -- four of a block's fifteen launches go.
-    auto ln_gemm = [&](const char *name, const GemmArgs &g, int epi, const float *ng, const float *nb, bool norm_done) {
-        if (!norm_done) {
-            GemmArgs fg = g;
-            fg.A = x; fg.lda = d; fg.a_bf16 = 0; fg.a_sigma = 0; fg.ln_g = ng; fg.ln_b = nb; fg.ln_eps = 1e-5f;
-            if (pend_g) {                                            // (checked when it was set: gemm_smallm_bf16_pre_applies)
-                fg.pre_g = pend_g; fg.pre_b = pend_b; fg.pre_out = x_other; fg.pre_ldo = d;
-                m_.run_gemm(name, fg, epi, st);
-                std::swap(x, x_other);                               // the normalised rows are the residual stream from here on
-                pend_g = pend_b = nullptr;
-                return;
-            }
-            // tolerance-class mode: gemm_smallm_bf16.hip; exact mode (tiled weight copies present): gemm_smallm_ln_kernel -- bit for bit norm + product
-            if (a16 ? gemm_smallm_bf16_ln_applies(fg, epi) : (sg && gemm_smallm_ln_applies(fg, epi))) { m_.run_gemm(name, fg, epi, st); return; }
-        }
-        if (!norm_done) launch_layernorm(x, rows, d, ng, nb, 1e-5f, n, st, lnm);
-        m_.run_gemm(name, g, epi, st);
-    };
-    bool ln_folds = false;                                                                                // the next block's ffn1 norm will be folded into its fc1
-    {
-        GemmArgs pg{x, d, m_.layers[0].ffn1_w1, d, nullptr, hb, f, nullptr, 0, 1.0f, (int)rows, f, d};
-        pg.ln_g = m_.layers[0].ffn1_ng; pg.ln_b = m_.layers[0].ffn1_nb; pg.out_bf16 = a16;
-        if (sg) pg.W_sig = (*sig_)[0].ffn1_w1;
-        if (wt) pg.W_t16 = (*sig_)[0].ffn1_w1;
-        ln_folds = a16 ? gemm_smallm_bf16_ln_applies(pg, EPI_SILU) : (sg && gemm_smallm_ln_applies(pg, EPI_SILU));
-    }
-    // ... and the block's final norm with it (GemmArgs::pre_g: that product normalises twice and its first column tile writes the normalised rows -- the
-    // next block's residual stream -- into the other of two buffers): one launch less per block (both modes; the exact mode's kernel normalises exactly
-    // as the separate launch does: bit-identical)
-    bool fin_folds = false;
-    if (ln_folds && cfg.num_layers > 1) {
+    BlockMode mode;
+    mode.bf16 = a16; mode.sigma = sg; mode.copies = (sg || wt) ? sig_ : nullptr; mode.copies_t16 = wt;
+    mode.fold_bf16 = true; mode.handoff = BlockMode::TILES8;
+    ConformerBlock blk{m_, mode, st, rows, ws_.x.as<float>(), ws_.n.as<float>(), ws_.hbuf.as<float>(), ws_.hbuf.cap};
+    if (cfg.num_layers > 1 && blk.fc1_folds(1)) {   // the blocks' ffn1 fc1 fold their norm: the final norms in front can ride on them (BlockMode::x_other)
         x_alt_.reserve((size_t)rows * d * 4);
-        x_other = x_alt_.as<float>();
-        GemmArgs pg{x, d, m_.layers[1].ffn1_w1, d, nullptr, hb, f, nullptr, 0, 1.0f, (int)rows, f, d};
-        pg.ln_g = m_.layers[1].ffn1_ng; pg.ln_b = m_.layers[1].ffn1_nb; pg.out_bf16 = a16; pg.ln_eps = 1e-5f;
-        if (sg) pg.W_sig = (*sig_)[1].ffn1_w1;
-        pg.pre_g = m_.layers[0].fin_g; pg.pre_b = m_.layers[0].fin_b; pg.pre_out = x_other; pg.pre_ldo = d;
-        fin_folds = a16 ? gemm_smallm_bf16_pre_applies(pg, EPI_SILU) : (sg && gemm_smallm_pre_applies(pg, EPI_SILU));
+        mode.x_other = x_alt_.as<float>();
     }
-    auto ffn = [&](const LayerW &L, const Model::SigW &Ls, bool second, bool norm_done) {                // FeedForward (src/encoder.cpp:36-46)
-        GemmArgs g1{n, d, second ? L.ffn2_w1 : L.ffn1_w1, d, second ? L.ffn2_b1 : L.ffn1_b1, hb, f, nullptr, 0, 1.0f, (int)rows, f, d};
-        g1.a_sigma = sg; (wt ? g1.W_t16 : g1.W_sig) = second ? Ls.ffn2_w1 : Ls.ffn1_w1;
-        g1.a_bf16 = a16; g1.out_bf16 = a16;
-        // tolerance-class mode, both products on the small-M bf16 kernel: the fc1 -> fc2 activations in its 8-row operand tiles (GemmArgs::out_t8 / a_t8)
-        GemmArgs p1 = g1, p2{hb, f, second ? L.ffn2_w2 : L.ffn1_w2, f, nullptr, x, d, x, d, 0.5f, (int)rows, d, f};
-        p1.out_t8 = 1; p2.a_bf16 = 1; p2.a_t8 = 1;
-        const bool t8 = a16 && gemm_smallm_bf16_applies(p1, EPI_SILU) && gemm_smallm_bf16_applies(p2, EPI_RESID);
-        g1.out_t8 = t8;
-        g1.sigma_cols = sg ? f : 0;                                                                       // h is fc2's A operand
-        ln_gemm("ffn_fc1_silu", g1, EPI_SILU, second ? L.ffn2_ng : L.ffn1_ng, second ? L.ffn2_nb : L.ffn1_nb, norm_done);
-        GemmArgs g2{hb, f, second ? L.ffn2_w2 : L.ffn1_w2, f, second ? L.ffn2_b2 : L.ffn1_b2, x, d, x, d, 0.5f, (int)rows, d, f};
-        g2.a_sigma = sg; (wt ? g2.W_t16 : g2.W_sig) = second ? Ls.ffn2_w2 : Ls.ffn1_w2;
-        g2.a_bf16 = a16; g2.a_t8 = t8;
-        m_.run_gemm("ffn_fc2_resid", g2, EPI_RESID, st);
-    };
-    bool ffn1_norm_done = false;
     for (int l = 0; l < cfg.num_layers; ++l) {
         const LayerW &L = m_.layers[l];
         LayerState &Ls = *layers_[l];
-        static const Model::SigW no_sig{};
-        const Model::SigW &Sg = (sg || wt) ? (*sig_)[l] : no_sig;
-        ffn(L, Sg, false, ffn1_norm_done);                                                             // ffn1_ (:294)
-        // StreamingConformerAttention::forward_cached (:162-272)
-        {
-            GemmArgs g{n, d, L.wqkv, d, L.bqkv, ws_.qkv.as<float>(), 3 * d, nullptr, 0, 1.0f, (int)rows, 3 * d, d};
-            g.a_sigma = sg; (wt ? g.W_t16 : g.W_sig) = Sg.wqkv;
-            g.a_bf16 = a16;
-            ln_gemm("attn_qkv", g, EPI_NONE, L.att_ng, L.att_nb, false);                              // natural columns (no sigma layout here)
-        }
+        blk.ffn(l, false);                                                                             // ffn1_ (:294)
+        // StreamingConformerAttention::forward_cached (:162-272): natural columns (no sigma layout here)
+        blk.qkv(l, ws_.qkv.as<float>());
         const float *kc = Ls.k[Ls.cur].as<float>(), *vc = Ls.v[Ls.cur].as<float>();
         // attention of the chunk's rows + (same launch, extra blocks) the rotation of the K / V caches into the other buffer pair
         launch_stream_attention(ws_.qkv.as<float>(), kc, vc, cache_rows, S, c, Ls.n_kv, d, cfg.num_heads, ptab + (size_t)l * P * d, P, L.pos_u, L.pos_v,
                                 left_, right_, ws_.ctx.as<float>(), st, Ls.k[Ls.cur ^ 1].as<float>(), Ls.v[Ls.cur ^ 1].as<float>(), left_, sg);
         Ls.cur ^= 1;
         Ls.n_kv = (Ls.n_kv + c > left_) ? left_ : Ls.n_kv + c;
-        {
-            GemmArgs g{ws_.ctx.as<float>(), d, L.wo, d, L.bo, x, d, x, d, 1.0f, (int)rows, d, d};
-            g.a_sigma = sg; (wt ? g.W_t16 : g.W_sig) = Sg.wo;
-            m_.run_gemm("attn_out_resid", g, EPI_RESID, st);
-        }
+        blk.att_out(l, ws_.ctx.as<float>());
         // CausalConformerConvModule::forward_cached (:41-78)
         {
-            GemmArgs g{n, d, L.pw1_w, d, L.pw1_b, ws_.g.as<float>(), d, nullptr, 0, 1.0f, (int)rows, d, d};
-            g.a_sigma = sg; (wt ? g.W_t16 : g.W_sig) = Sg.pw1;
-            g.a_bf16 = a16;
-            // the depthwise conv in pw1's epilogue where the small-M bf16 kernel can (rows stream-major, c = 1 / 2 / 4 frames per stream)
+            GemmArgs g = blk.pw1_args(l, ws_.g.as<float>());
             DwTail tail{Ls.conv[Ls.ccur].as<float>(), Ls.conv[Ls.ccur ^ 1].as<float>(), Ls.has_conv, c, L.dw_w, L.dw_b, L.bn_mean, L.bn_rstd, L.bn_g, L.bn_b, sg};
             // The depthwise conv + BatchNorm + SiLU of the conv module in the GLU epilogue of pw1 (kernels.hpp: DwTail) -- one launch less per block,
-            // bit-identical to the separate kernel (both modes)
-            GemmArgs probe = g;                                                                          // what ln_gemm will launch when the norm folds
-            probe.A = x; probe.a_bf16 = 0; probe.a_sigma = 0; probe.ln_g = L.cv_ng; probe.ln_b = L.cv_nb; probe.ln_eps = 1e-5f;
+            // bit-identical to the separate kernel (both modes) -- where the small-M kernels can (rows stream-major, c = 1 / 2 / 4 frames per stream)
+            const GemmArgs probe = blk.folded(g, L.cv_ng, L.cv_nb);                                      // what ln_gemm will launch when the norm folds
             // (tolerance-class mode: with or without the folded norm; exact mode: the tail lives in the kernel with the norm folded in)
             const bool fused_dw = a16 ? gemm_smallm_bf16_dw_applies(probe, EPI_GLU, c, K) && gemm_smallm_bf16_dw_applies(g, EPI_GLU, c, K)
                                       : sg && gemm_smallm_dw_applies(probe, EPI_GLU, c, K);
             if (fused_dw) { g.dw_tail = &tail; g.out = ws_.dwb.as<float>(); }
-            ln_gemm("conv_pw1_glu", g, EPI_GLU, L.cv_ng, L.cv_nb, false);
+            blk.pw1(l, g);
             if (!fused_dw)
                 launch_stream_dwconv(ws_.g.as<float>(), Ls.conv[Ls.ccur].as<float>(), Ls.has_conv, S, c, d, K, L.dw_w, L.dw_b, L.bn_mean, L.bn_rstd, L.bn_g, L.bn_b,
                                      ws_.dwb.as<float>(), Ls.conv[Ls.ccur ^ 1].as<float>(), st, sg);
         }
-        {
-            Ls.ccur ^= 1;
-            Ls.has_conv = 1;
-        }
-        {
-            GemmArgs g{ws_.dwb.as<float>(), d, L.pw2_w, d, L.pw2_b, x, d, x, d, 1.0f, (int)rows, d, d};
-            g.a_sigma = sg; (wt ? g.W_t16 : g.W_sig) = Sg.pw2;
-            m_.run_gemm("conv_pw2_resid", g, EPI_RESID, st);
-        }
-        ffn(L, Sg, true, false);                                                                       // ffn2_
-        if (l + 1 < cfg.num_layers && !ln_folds) {   // final_norm_ and the next block's ffn1_ norm in one pass over the rows (as the offline encoder)
-            launch_layernorm2(x, rows, d, L.fin_g, L.fin_b, m_.layers[l + 1].ffn1_ng, m_.layers[l + 1].ffn1_nb, 1e-5f, x, n, st, lnm);
-            ffn1_norm_done = true;
-        } else if (l + 1 < cfg.num_layers && fin_folds) {
-            pend_g = L.fin_g; pend_b = L.fin_b;      // final_norm_ rides on the next block's fc1 (ln_gemm above)
-        } else {                                     // (ln_folds: the next block's fc1 normalises its own input rows)
-            launch_layernorm(x, rows, d, L.fin_g, L.fin_b, 1e-5f, ws_.x.as<float>(), st);            // final_norm_ (the last block's lands in ws_.x)
-            x = ws_.x.as<float>();
-        }
+        Ls.ccur ^= 1;
+        Ls.has_conv = 1;
+        blk.pw2(l, ws_.dwb.as<float>());
+        blk.ffn(l, true);                                                                              // ffn2_
+        blk.end_block(l, l + 1 < cfg.num_layers);                                                      // final_norm_ (the last block's lands in ws_.x)
     }
     PK_CHECK_LAUNCH();
     return c;

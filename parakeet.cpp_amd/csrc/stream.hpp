@@ -58,7 +58,7 @@ class StreamBatch {
     float *pin_pcm_ = nullptr;
     size_t pin_pcm_floats_ = 0;
     int mel_impl(const float *pcm, int n_samples, float *out, int cap_frames, bool sync);
-    DevBuf x_alt_;              // second residual-stream buffer: a block's final norm folded into the next block's first product writes it (stream.cpp)
+    DevBuf x_alt_;              // second residual-stream buffer: a block's final norm folded into the next block's first product writes it (BlockMode::x_other)
     std::map<int, std::unique_ptr<DevBuf>> pos_tables_;   // Tp -> pos_proj of every layer [L][2Tp-1][d], natural columns
     int encode_device(const float *d_mel, int n_frames);                    // -> ws_.x [S*c][d], returns c
     const float *pos_table(int Tp);
