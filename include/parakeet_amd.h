@@ -352,6 +352,45 @@ pk_status pk_transcribe_pcm_nbest(pk_model *m, const float *pcm, const int64_t *
                                   pk_nbest **results);
 void pk_nbest_free(pk_nbest *results, int n_clips);
 
+/* ---- CTC forced alignment of a GIVEN transcript ---------------------------------------------------------------------------
+ * Given the log-probs and the token string that was said: when was each token said.  The alignment is the max-plus (Viterbi) path on the
+ * 2 L + 1 state CTC lattice, specified operation by operation in DESIGN.md section 5.5.1 (tests/ctc_align_ref.py is that specification in
+ * Python; the device result equals it bit for bit): fp32, one add per cell, predecessor ties stay / previous state / skip, a skip only onto
+ * a token that differs from the token before it, end state the last blank unless the last token's state is strictly better.
+ * All of it runs on the device (kernels/ctc_align.hip).  pk_group and streaming sessions have no alignment variant; the TDT head has none.
+ *
+ * pk_ctc_align: HOST log-probs in.  Needs a device, no model.  logp / n_frames / B / T / V / blank as pk_ctc_beam_search.  ids: the token
+ * strings of the B utterances packed, utterance b = ids[id_offsets[b] .. id_offsets[b+1]) (id_offsets[0] = 0; an empty string is valid).
+ * Outputs: start / end / conf packed as ids (first and last frame of every token, conf = exp(logp[start][id])); score[B] the path's
+ * log-probability; total[B] (optional, NULL: not computed) the CTC log-likelihood of the string, the forward algorithm on the same lattice
+ * (>= score); ok[B] = 1, or 0 where the string cannot be aligned (more tokens + adjacent repeats than frames, or every path -inf): then
+ * score = -inf and the utterance's start / end / conf are 0.
+ * PK_ERR_INVALID (before any device work): B < 1, offsets that decrease, an id outside [0, V) or equal to blank.
+ * PK_ERR_UNSUPPORTED (before anything is allocated): a string of more than 16383 tokens, or more than 1 GiB of back-pointers
+ * (sum over the utterances of T_b * ceil((2 L_b + 1) / 16) * 4 bytes; one hour of audio, T = 45000, with L = 15000 takes 338 MB). */
+pk_status pk_ctc_align(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const int32_t *ids, const int32_t *id_offsets,
+                       int32_t *start, int32_t *end, float *conf, float *score, float *total, int32_t *ok);
+/* CTC head + log-softmax (the kernels of pk_ctc_decode) + the alignment on the model's stream; the log-probs never leave the device.
+ * enc [B][T][hidden] resp. packed with n_frames[B].  PK_ERR_UNSUPPORTED for a model without a CTC head.  A boost trie set on the model does
+ * not matter: the alignment reads the unboosted log-softmax rows. */
+pk_status pk_ctc_align_decode(pk_model *m, const float *enc, int B, int T, const int32_t *ids, const int32_t *id_offsets, int32_t *start,
+                              int32_t *end, float *conf, float *score, float *total, int32_t *ok);
+pk_status pk_ctc_align_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                                     int32_t *start, int32_t *end, float *conf, float *score, float *total, int32_t *ok);
+/* Stage timers of the alignment (tools/bench_ctc_align.py): the CTC head + log-softmax + greedy collapse, then the alignment (uploads of the
+ * token strings, zero-fills and the kernel), each between hipEvents on the model's stream; medians of `reps` passes after one warm-up.
+ * n_frames NULL: uniform [B][T].  ms[0] = CTC stage, ms[1] = alignment stage. */
+pk_status pk_ctc_align_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids,
+                                    const int32_t *id_offsets, int want_total, int reps, float ms[2]);
+/* One call from PCM and transcripts to timestamps: clips of any length packed into ragged batches by the policy of pk_transcribe_pcm
+ * (pk_plan_batches), encoded (the attention context set on the model applies: that is how an hour-long clip gets through), aligned.
+ * The transcripts: texts[n_clips] UTF-8 (tokenised as pk_tokenize does; needs the model's vocabulary), or, with texts == NULL, ids packed with
+ * id_offsets[n_clips + 1].  results[i]: a pk_result as pk_transcribe_pcm fills it with timestamps on (words through the grouping of
+ * pk_group_timestamps), owned by the library until pk_results_free; a clip with ok = 0 gets its text and ids but NULL timestamp arrays and no
+ * words.  score / total (either optional) / ok: [n_clips], as pk_ctc_align. */
+pk_status pk_align_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts_or_null,
+                       const int32_t *ids_or_null, const int32_t *id_offsets, pk_result **results, float *score, float *total, int32_t *ok);
+
 /* ---- one node, several GPUs: utterance shards (the reference has no multi-device path, README.md:513) ----------
  * A pk_group is one model REPLICA per device of this process: the safetensors file is mapped once and every replica is built from that
  * one host image by its own host thread (each device uploads over its own PCIe link).  pk_group_transcribe_pcm deals the clips, longest

@@ -183,6 +183,11 @@ _LATE_SIGNATURES = {
     "pk_ctc_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), C.c_int, f32p],
     "pk_transcribe_pcm_nbest": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkBeamOptions), C.POINTER(C.POINTER(PkNbest))],
     "pk_nbest_free": [C.POINTER(PkNbest), C.c_int],
+    "pk_ctc_align": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
+    "pk_ctc_align_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
+    "pk_ctc_align_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
+    "pk_ctc_align_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.c_int, f32p],
+    "pk_align_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.POINTER(C.POINTER(PkResult)), f32p, f32p, i32p],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -266,6 +271,44 @@ def ctc_beam_search(logp, blank, beam_width=None, token_prune=None, n_best=None,
     lp = _c(logp)
     B, T, V = lp.shape
     return _beam_call(lib().pk_ctc_beam_search, (_f(lp), None, B, T, V, blank), B, T, o)
+
+
+# ---- CTC forced alignment of given token strings (include/parakeet_amd.h) ------
+def _pack_ids(ids_list):
+    off = np.zeros(len(ids_list) + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in ids_list])
+    ids = np.zeros(max(1, int(off[-1])), np.int32)
+    if off[-1]:
+        ids[: off[-1]] = np.concatenate([np.asarray(x, np.int32).ravel() for x in ids_list])
+    return ids, off
+
+
+def _align_call(fn, head, ids_list, total):
+    """-> list (one dict per utterance) of start / end / conf arrays [L_b], score, ok and, when asked for, total."""
+    B = len(ids_list)
+    ids, off = _pack_ids(ids_list)
+    st = np.zeros(len(ids), np.int32); en = np.zeros(len(ids), np.int32); cf = np.zeros(len(ids), np.float32)
+    sc = np.zeros(B, np.float32); tt = np.zeros(B, np.float32); ok = np.zeros(B, np.int32)
+    check(fn(*head, _i(ids), _i(off), _i(st), _i(en), _f(cf), _f(sc), _f(tt) if total else None, _i(ok)))
+    out = []
+    for b in range(B):
+        d = dict(start=st[off[b]:off[b + 1]].copy(), end=en[off[b]:off[b + 1]].copy(), conf=cf[off[b]:off[b + 1]].copy(), score=sc[b], ok=int(ok[b]))
+        if total:
+            d["total"] = tt[b]
+        out.append(d)
+    return out
+
+
+def ctc_align(logp, ids, blank, total=True):
+    """pk_ctc_align: logp [B][T][V] (uniform) or a list of [T_b][V] matrices (ragged); ids: one token sequence per utterance.
+    Needs a device, no model."""
+    if isinstance(logp, (list, tuple)):
+        T = np.asarray([x.shape[0] for x in logp], np.int32)
+        lp = _c(np.concatenate([_c(x) for x in logp], axis=0))
+        return _align_call(lib().pk_ctc_align, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), ids, total)
+    lp = _c(logp)
+    B, T, V = lp.shape
+    return _align_call(lib().pk_ctc_align, (_f(lp), None, B, T, V, blank), ids, total)
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -1546,6 +1589,63 @@ class Model:
         x = _c(enc)
         B, T, _ = x.shape
         return _beam_call(lib().pk_ctc_beam_decode, (self._h, _f(x), B, T), B, T, o)
+
+    def ctc_align_decode(self, enc, ids, total=True):
+        """pk_ctc_align_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_align."""
+        if isinstance(enc, (list, tuple)):
+            T = np.asarray([e.shape[0] for e in enc], np.int32)
+            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
+            return _align_call(lib().pk_ctc_align_decode_ragged, (self._h, _f(x), _i(T), len(T)), ids, total)
+        x = _c(enc)
+        B, T, _ = x.shape
+        return _align_call(lib().pk_ctc_align_decode, (self._h, _f(x), B, T), ids, total)
+
+    def ctc_align_decode_timed(self, enc, ids, total=False, reps=5):
+        """pk_ctc_align_decode_timed -> (CTC stage ms, alignment stage ms), HIP events, medians of reps passes."""
+        pid, poff = _pack_ids(ids)
+        ms = np.zeros(2, np.float32)
+        if isinstance(enc, (list, tuple)):
+            T = np.asarray([e.shape[0] for e in enc], np.int32)
+            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
+            check(lib().pk_ctc_align_decode_timed(self._h, _f(x), _i(T), len(T), 0, _i(pid), _i(poff), int(total), reps, _f(ms)))
+        else:
+            x = _c(enc)
+            check(lib().pk_ctc_align_decode_timed(self._h, _f(x), None, x.shape[0], x.shape[1], _i(pid), _i(poff), int(total), reps, _f(ms)))
+        return float(ms[0]), float(ms[1])
+
+    def align(self, clips, texts=None, ids=None, total=True):
+        """pk_align_pcm: the clips (list, or packed (pcm, offsets)) against their transcripts, given as texts (needs the vocabulary) or as
+        token id sequences -> list of dicts as transcribe_pcm(timestamps=True) returns them + "score", "ok" (and "total"); a clip that
+        cannot be aligned has ok = 0 and no timestamp entries."""
+        assert (texts is None) != (ids is None), "texts or ids"
+        if isinstance(clips, tuple):
+            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
+        else:
+            pcm, off = pack_clips(clips)
+        n = len(off) - 1
+        sc = np.zeros(n, np.float32); tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
+        res = C.POINTER(PkResult)()
+        if texts is not None:
+            keep = (C.c_char_p * n)(*[t.encode() for t in texts])
+            tail = (keep, None, None)
+        else:
+            pid, poff = _pack_ids(ids)
+            tail = (None, _i(pid), _i(poff))
+        check(lib().pk_align_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, C.byref(res), _f(sc), _f(tt) if total else None, _i(ok)))
+        out = []
+        for i in range(n):
+            r = res[i]
+            d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(sc[i]), ok=int(ok[i]))
+            if total:
+                d["total"] = float(tt[i])
+            if ok[i]:
+                d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
+                d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
+                d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
+                d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
+            out.append(d)
+        lib().pk_results_free(res, n)
+        return out
 
     def ctc_beam_decode_timed(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, reps=5):
         """pk_ctc_beam_decode_timed -> (greedy CTC stage ms, beam search stage ms), HIP events, medians of reps passes."""

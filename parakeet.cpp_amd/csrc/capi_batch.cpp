@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_batch.cpp -- the resident two-stream batch pipeline (pk_batch_*) and the one-call API on top of it:
-// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest and the result stores they hand out.
+// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest, pk_align_pcm and the result stores they hand out.
 #include <algorithm>
 #include <cstring>
 
@@ -867,6 +867,25 @@ struct NbestStore {           // owns everything a pk_nbest array points into
 };
 }  // namespace
 
+// One planned batch of the one-call entry points that work on the CTC rows (clips order[0 .. nc) of the call) from PCM to the log-softmax
+// rows, left on the device in m.ws.ctc_lp (packed; extents in r and m.ws.rv.seq).  sized(r), if given, runs once the extents are known and
+// before anything is allocated or queued.
+static void encode_batch_ctc(Model &m, const float *pcm, const int64_t *offsets, const int *order, int nc, RagBatch &r,
+                             const std::function<void(const RagBatch &)> &sized = nullptr) {
+    std::vector<int64_t> blens(nc);
+    for (int i = 0; i < nc; ++i) blens[i] = offsets[order[i] + 1] - offsets[order[i]];
+    const int64_t longest = blens[0];
+    r.build_from_samples(blens.data(), nc, att_block_rows_of(m, pk_encoder_num_frames(pk_mel_num_frames(longest))));
+    if (sized) sized(r);
+    m.ws.size_ragged(m.cfg, nc, r.n_samples, longest, /*own_pcm=*/true);
+    m.ws.set_ragged(r, m.stream);
+    for (int i = 0; i < nc; ++i)
+        PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[order[i]], (size_t)blens[i] * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), nc, m.stream);
+    m.run_encoder(m.ws, m.ws.feats.as<float>(), nc, 0, -1, 0, m.stream);
+    m.run_ctc(m.ws, m.ws.x.as<float>(), nc, r.T_max, true, m.stream);
+}
+
 pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
                                   pk_nbest **results) {
     return guard([&] {
@@ -885,22 +904,11 @@ pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *
         plan_batches(clip_len.data(), n_clips, order, bstart);
         std::vector<int32_t> ids, lens, st, en;
         std::vector<float> sc, cf;
-        std::vector<int64_t> blens;
         for (size_t k = 0; k + 1 < bstart.size(); ++k) {
             const int c0 = bstart[k], nc = bstart[k + 1] - c0;
-            blens.resize(nc);
-            for (int i = 0; i < nc; ++i) blens[i] = clip_len[order[c0 + i]];
-            const int64_t longest = blens[0];
             RagBatch r;
-            r.build_from_samples(blens.data(), nc, att_block_rows_of(m, pk_encoder_num_frames(pk_mel_num_frames(longest))));
-            m.ws.size_ragged(m.cfg, nc, r.n_samples, longest, /*own_pcm=*/true);
-            m.ws.set_ragged(r, m.stream);
-            for (int i = 0; i < nc; ++i)
-                PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[order[c0 + i]], (size_t)blens[i] * 4, hipMemcpyHostToDevice, m.stream));
-            m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), nc, m.stream);
-            m.run_encoder(m.ws, m.ws.feats.as<float>(), nc, 0, -1, 0, m.stream);
+            encode_batch_ctc(m, pcm, offsets, order.data() + c0, nc, r);
             const int T = r.T_max;
-            m.run_ctc(m.ws, m.ws.x.as<float>(), nc, T, true, m.stream);
             run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream);
             PK_CHECK_LAUNCH();
             const size_t hyps = (size_t)nc * N, tok = hyps * T;
@@ -929,6 +937,70 @@ pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *
         tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
         *results = store->out.data();
         store.release();
+    });
+}
+
+pk_status pk_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
+                       const int32_t *id_offsets_in, pk_result **results, float *score, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && pcm && offsets && results && ok && n_clips > 0, "model/pcm/offsets/results/ok/n_clips");
+        need(texts || id_offsets_in, "texts or ids/id_offsets");
+        Model &m = *h->m;
+        if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC alignment needs one");
+        const int V = m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;
+        std::vector<int32_t> all_ids, all_off(n_clips + 1, 0);      // the transcripts, packed in the caller's clip order
+        if (texts) {
+            need(m.tok.loaded(), "aligning text needs the model's vocabulary");
+            for (int c = 0; c < n_clips; ++c) {
+                need(texts[c] != nullptr, "texts[c]");
+                for (int v : m.tok.encode(texts[c])) all_ids.push_back(v);
+                all_off[c + 1] = (int32_t)all_ids.size();
+            }
+            align_check_args(all_ids.data(), all_off.data(), n_clips, V, blank);
+        } else {
+            align_check_args(ids_in, id_offsets_in, n_clips, V, blank);
+            all_off.assign(id_offsets_in, id_offsets_in + n_clips + 1);
+            all_ids.assign(ids_in, ids_in + all_off[n_clips]);
+        }
+        m.require_gpu();
+        std::vector<int64_t> clip_len(n_clips);
+        for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+        std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
+        plan_batches(clip_len.data(), n_clips, order, bstart);
+        auto store = new_store(n_clips);
+        std::vector<int32_t> bids, boff, nfr, st, en, okv;
+        std::vector<float> cf, sc, tt;
+        for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+            const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+            boff.assign(nc + 1, 0); bids.clear();
+            for (int i = 0; i < nc; ++i) {
+                const int c = order[c0 + i];
+                bids.insert(bids.end(), all_ids.begin() + all_off[c], all_ids.begin() + all_off[c + 1]);
+                boff[i + 1] = (int32_t)bids.size();
+            }
+            RagBatch r;
+            encode_batch_ctc(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
+                nfr.assign(rb.T.begin(), rb.T.begin() + nc);
+                align_plan(m.align, nfr.data(), nc, rb.T_max, boff.data());     // (refuses before the batch is encoded)
+            });
+            run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, bids.data(), total != nullptr, m.stream);
+            PK_CHECK_LAUNCH();
+            const size_t n = bids.size();
+            st.assign(n + 1, 0); en.assign(n + 1, 0); cf.assign(n + 1, 0.0f); sc.resize(nc); tt.resize(nc); okv.resize(nc);
+            align_copy_out(m.align, st.data(), en.data(), cf.data(), sc.data(), total ? tt.data() : nullptr, okv.data(), m.stream);
+            for (int i = 0; i < nc; ++i) {
+                const int c = order[c0 + i], o0 = boff[i], L = boff[i + 1] - o0;
+                const bool good = okv[i] != 0;
+                store_tokens(m, *store, c, L, bids.data() + o0, good ? st.data() + o0 : nullptr, good ? en.data() + o0 : nullptr, good ? cf.data() + o0 : nullptr);
+                ok[c] = okv[i];
+                if (score) score[c] = sc[i];
+                if (total) total[c] = tt[i];
+            }
+        }
+        pk_result *out = publish_store(std::move(store), n_clips, true);
+        for (int c = 0; c < n_clips; ++c)
+            if (!ok[c]) out[c].start_frame = out[c].end_frame = nullptr, out[c].confidence = nullptr;
+        *results = out;
     });
 }
 

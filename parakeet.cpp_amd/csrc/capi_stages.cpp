@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_stages.cpp -- the stage entry points of the C boundary on caller buffers: mel, subsample, encode, conformer blocks,
-// CTC / TDT decode and scoring (uniform and ragged forms), and the CTC prefix beam search.
+// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix beam search and the CTC forced alignment.
 #include <algorithm>
 #include <cstring>
 
@@ -124,6 +124,31 @@ static void ctc_beam_decode(Model &m, const float *enc, const int32_t *n_frames,
     PK_CHECK_LAUNCH();
     const bool ts = o.timestamps != 0;
     beam_copy_out(m.beam, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, m.stream);
+}
+
+// the alignment's model checks (include/parakeet_amd.h); -> the CTC vocabulary and its blank.  A boost trie does not matter: run_ctc writes the
+// unboosted log-softmax rows, and those are what is aligned.
+static void align_model_checks(Model &m, int &V, int &blank) {
+    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC alignment needs one");
+    V = m.cfg.ctc_vocab_size;
+    blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;           // (as Model::run_ctc)
+}
+
+static void ctc_align_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids, const int32_t *id_offsets,
+                             int32_t *start, int32_t *end, float *conf, float *score, float *total, int32_t *ok) {
+    int V = 0, blank = 0;
+    align_model_checks(m, V, blank);
+    align_check_args(ids, id_offsets, B, V, blank);
+    if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+    m.require_gpu();
+    align_plan(m.align, n_frames, B, T, id_offsets);
+    size_t rows;
+    T = size_ws(m, n_frames, B, T, rows);
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+    run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), B, T, n_frames ? m.ws.rv.seq : SeqRag(), V, blank, ids, total != nullptr, m.stream);
+    PK_CHECK_LAUNCH();
+    align_copy_out(m.align, start, end, conf, score, total, ok, m.stream);
 }
 
 extern "C" {
@@ -420,6 +445,97 @@ pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t 
         }
         std::sort(greedy.begin(), greedy.end()); std::sort(beam.begin(), beam.end());
         ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
+    });
+}
+
+/* ---- CTC forced alignment of given token strings (kernels/ctc_align.hip) ------------------------------------------------------------ */
+pk_status pk_ctc_align(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const int32_t *ids, const int32_t *id_offsets,
+                       int32_t *start, int32_t *end, float *conf, float *score, float *total, int32_t *ok) {
+    return guard([&] {
+        align_check_args(ids, id_offsets, B, V, blank);
+        need(logp && score && ok, "logp/score/ok");
+        need(id_offsets[B] == 0 || (start && end && conf), "start/end/conf");
+        need(n_frames || T > 0, "T");
+        int64_t rows = (int64_t)B * T;
+        std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
+        if (n_frames) {
+            tab.resize(2 * (size_t)B + 1);
+            rows = 0; T = 0;
+            for (int b = 0; b < B; ++b) {
+                need(n_frames[b] > 0, "n_frames[b] must be positive");
+                tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
+                rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
+                need(rows < ((int64_t)1 << 31), "too many frames");
+            }
+            tab[2 * (size_t)B] = (int32_t)rows;
+        }
+        need_device();
+        AlignWs ws;
+        align_plan(ws, n_frames, B, T, id_offsets);                // (refuses before anything is allocated)
+        DevBuf d_lp, d_tab;
+        d_lp.reserve((size_t)rows * V * 4);
+        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
+        SeqRag rag;
+        if (n_frames) {
+            d_tab.reserve(tab.size() * 4);
+            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
+        }
+        run_ctc_align(ws, d_lp.as<float>(), B, T, rag, V, blank, ids, total != nullptr, nullptr);
+        PK_CHECK_LAUNCH();
+        align_copy_out(ws, start, end, conf, score, total, ok, nullptr);
+    });
+}
+
+pk_status pk_ctc_align_decode(pk_model *h, const float *enc, int B, int T, const int32_t *ids, const int32_t *id_offsets, int32_t *start,
+                              int32_t *end, float *conf, float *score, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && score && ok && T > 0, "model/enc/score/ok/T");
+        ctc_align_decode(*h->m, enc, nullptr, B, T, ids, id_offsets, start, end, conf, score, total, ok);
+    });
+}
+
+pk_status pk_ctc_align_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                                     int32_t *start, int32_t *end, float *conf, float *score, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && n_frames && score && ok, "model/enc/n_frames/score/ok");
+        ctc_align_decode(*h->m, enc, n_frames, B, 0, ids, id_offsets, start, end, conf, score, total, ok);
+    });
+}
+
+pk_status pk_ctc_align_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids,
+                                    const int32_t *id_offsets, int want_total, int reps, float ms[2]) {
+    return guard([&] {
+        need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
+        Model &m = *h->m;
+        int V = 0, blank = 0;
+        align_model_checks(m, V, blank);
+        align_check_args(ids, id_offsets, B, V, blank);
+        if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+        m.require_gpu();
+        align_plan(m.align, n_frames, B, T, id_offsets);
+        size_t rows;
+        T = size_ws(m, n_frames, B, T, rows);
+        const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        std::vector<float> head, align;
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+            m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), B, T, rag, V, blank, ids, want_total != 0, m.stream);
+            PK_HIP(hipEventRecord(ev.e[2], m.stream));
+            PK_HIP(hipStreamSynchronize(m.stream));
+            PK_CHECK_LAUNCH();
+            float a = 0, b = 0;
+            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+            if (r > 0) { head.push_back(a); align.push_back(b); }
+        }
+        std::sort(head.begin(), head.end()); std::sort(align.begin(), align.end());
+        ms[0] = head[head.size() / 2]; ms[1] = align[align.size() / 2];
     });
 }
 

@@ -403,6 +403,23 @@ struct BeamAlignArgs {
     SeqRag rg;
 };
 void launch_ctc_beam_align(const BeamAlignArgs &a, hipStream_t s);
+// CTC forced alignment of GIVEN token strings (kernels/ctc_align.hip) over the same rows.  One workgroup per utterance;
+// every thread keeps a strip of lattice states in registers.  The three shapes (threads x states per thread): 64 x 4, 256 x 8, 1024 x 32.
+constexpr int kAlignThreads[3] = {64, 256, 1024}, kAlignStrip[3] = {4, 8, 32};
+constexpr int kAlignMaxStates = 1024 * 32;      // 2 L + 1 <= this (L <= 16383)
+constexpr int kAlignBpCells = 16;               // lattice cells per back-pointer dword (2 bits each)
+constexpr int kAlignTraceFrames = 64;           // frames of back-pointer rows staged in LDS per step of the back-trace
+struct CtcAlignArgs {
+    const float *lp; int V, blank;
+    int B, T;                                   // uniform extents (rg.T == nullptr), else T = the longest utterance
+    const int *ids, *id_off;                    // packed token strings, id_off[B + 1]
+    unsigned *bp; const int64_t *bp_off;        // back-pointers: utterance b owns T_b rows of ceil((2 L_b + 1) / 16) dwords from dword bp_off[b]
+    int *start, *end; float *conf;              // packed as ids (zero-filled by the caller: an utterance with ok = 0 writes none)
+    float *score, *total; int *ok;              // [B]; total == nullptr: the forward pass is not run
+    SeqRag rg;
+};
+// shape: index into kAlignThreads / kAlignStrip; every utterance of the batch needs 2 L + 1 <= kAlignThreads[shape] * kAlignStrip[shape]
+void launch_ctc_align(const CtcAlignArgs &a, int shape, hipStream_t s);
 struct TdtState {
     int B, T, V, D, L, Hp, blank, max_symbols, max_tokens, max_steps;
     TrieDev trie;

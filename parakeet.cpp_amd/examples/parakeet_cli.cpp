@@ -2,10 +2,14 @@
 // arguments, --model types and options; every model type runs through the drop-in facade classes.
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K]]
+//                [--align "text" | --align-file path.txt]
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
+// New: --align "text" / --align-file path.txt (tdt-ctc-110m, tdt-600m) aligns the given transcript with the audio (CTC forced alignment) and
+// prints its word timestamps in the format of --timestamps.
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
 #include <chrono>
 #include <cstdio>
+#include <fstream>
 #include <iomanip>
 #include <iostream>
 #include <string>
@@ -21,6 +25,7 @@ static void usage(const char *prog) {
               << "  --model TYPE   tdt-ctc-110m (default), tdt-600m, rnnt-600m, eou-120m, nemotron-600m, sortformer, diarized\n"
               << "  --ctc | --tdt | --decoder ctc|tdt  decoder (default: TDT)\n"
               << "  --beam W [--nbest N] [--prune K]  CTC prefix beam search (needs the CTC decoder), N best hypotheses\n"
+              << "  --align \"text\" | --align-file path.txt  CTC forced alignment of a known transcript: its word timestamps\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
 }
@@ -36,6 +41,21 @@ static void print_result(const TranscribeResult &r, bool timestamps, double ms) 
         for (const auto &w : r.word_timestamps)
             std::cout << "  [" << std::fixed << std::setprecision(2) << w.start << "s - " << w.end << "s] (" << std::setprecision(3) << w.confidence << ") " << w.word << "\n";
     }
+}
+
+// --align: the given transcript's word timestamps, in the format of --timestamps
+template <class T>
+static int run_align(T &t, const std::string &audio_path, const std::string &text) {
+    const auto t0 = Clock::now();
+    const auto r = t.align(audio_path, text);
+    const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+    if (!r.aligned) {
+        std::cerr << "Error: the transcript (" << r.token_ids.size() << " tokens) cannot be aligned with this audio\n";
+        return 1;
+    }
+    std::cout << "Alignment: score " << std::setprecision(9) << std::defaultfloat << r.score << " log-likelihood " << r.total << "\n";
+    print_result(r, true, ms);
+    return 0;
 }
 
 template <class T>
@@ -62,8 +82,8 @@ int main(int argc, char **argv) {
     if (argc < 3) { usage(argv[0]); return 1; }
     try {
         const std::string weights = argv[1], audio_path = argv[2];
-        std::string model = "tdt-ctc-110m", vocab, sf_weights;
-        bool use_ctc = false, timestamps = false;
+        std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text;
+        bool use_ctc = false, timestamps = false, align = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
         std::vector<std::string> boost;
         float boost_score = 5.0f;
@@ -78,6 +98,14 @@ int main(int argc, char **argv) {
                 use_ctc = d == "ctc";
             }
             else if (a == "--beam" && i + 1 < argc) beam = std::stoi(argv[++i]);
+            else if (a == "--align" && i + 1 < argc) { align_text = argv[++i]; align = true; }
+            else if (a == "--align-file" && i + 1 < argc) {
+                std::ifstream f(argv[++i]);
+                if (!f) { std::cerr << "Error: cannot open " << argv[i] << "\n"; return 1; }
+                align_text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+                while (!align_text.empty() && (align_text.back() == '\n' || align_text.back() == '\r')) align_text.pop_back();
+                align = true;
+            }
             else if (a == "--nbest" && i + 1 < argc) nbest = std::stoi(argv[++i]);
             else if (a == "--prune" && i + 1 < argc) prune = std::stoi(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
@@ -95,10 +123,13 @@ int main(int argc, char **argv) {
         opts.timestamps = timestamps;
         opts.boost_phrases = boost;
         opts.boost_score = boost_score;
+        if (align && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --align needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
+        if (align && vocab.empty()) { std::cerr << "Error: --align needs --vocab\n"; return 1; }
         std::cout << "Loading model: " << model << std::endl;
         if (model == "tdt-ctc-110m") {
             Transcriber t(weights, vocab);
             t.to_gpu();
+            if (align) return run_align(t, audio_path, align_text);
             if (!boost.empty()) std::cout << "Phrase boost: " << boost.size() << " phrases\n";
             if (beam > 0) {
                 if (!use_ctc) { std::cerr << "Error: --beam needs the CTC decoder (--ctc / --decoder ctc)\n"; return 1; }
@@ -121,6 +152,7 @@ int main(int argc, char **argv) {
         } else if (model == "tdt-600m") {
             TDTTranscriber t(weights, vocab);
             t.to_gpu();
+            if (align) return run_align(t, audio_path, align_text);
             const auto t0 = Clock::now();
             const auto r = t.transcribe(audio_path, opts);
             print_result(r, timestamps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());

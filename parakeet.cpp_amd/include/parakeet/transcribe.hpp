@@ -46,6 +46,14 @@ struct ScoredResult {
     TranscribeResult result;
     float score = 0.0f;
 };
+/// New: what Transcriber::align returns (pk_align_pcm): the given transcript with token and word timestamps from the CTC forced alignment,
+/// the alignment path's log-probability and the CTC log-likelihood of the transcript.  aligned == false: the transcript does not fit the
+/// audio (more tokens + adjacent repeats than frames); text and token_ids are filled, the timestamps are empty, score is -inf.
+struct AlignResult : TranscribeResult {
+    float score = 0.0f;
+    float total = 0.0f;
+    bool aligned = false;
+};
 /// Parameters of Transcriber::transcribe_nbest (pk_beam_options); TranscribeOptions is untouched.
 struct BeamOptions {
     int beam_width = 8;     // prefixes kept per frame, 1..32
@@ -177,6 +185,36 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return run_nbest(pcm, (size_t)n, opts);
     }
 
+    // pk_align_pcm on one clip: the CTC forced alignment of `text` (tokenised by the model's vocabulary); single device
+    AlignResult run_align(const float *pcm, size_t n, const std::string &text) {
+        if (!on_gpu_) to_gpu(0);
+        const int64_t offsets[2] = {0, (int64_t)n};
+        const char *texts[1] = {text.c_str()};
+        pk_result *res = nullptr;
+        float score = 0.0f, total = 0.0f;
+        int32_t ok = 0;
+        check(pk_align_pcm(m_, pcm, offsets, 1, texts, nullptr, nullptr, &res, &score, &total, &ok));
+        const pk_result &r = res[0];
+        AlignResult out;
+        out.score = score; out.total = total; out.aligned = ok != 0;
+        out.text = r.text ? r.text : "";
+        out.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
+        if (ok) {
+            for (int k = 0; k < r.n_tokens; ++k) out.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
+            for (int k = 0; k < r.n_words; ++k) out.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
+        }
+        pk_results_free(res, 1);
+        return out;
+    }
+    AlignResult run_align_file(const std::string &audio_path, const std::string &text) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_align(pcm, (size_t)n, text);
+    }
+
     TranscribeResult run_file(const std::string &audio_path, const TranscribeOptions &opts) {
         float *pcm = nullptr;
         int64_t n = 0;
@@ -247,6 +285,11 @@ class Transcriber {
 
     const Tokenizer &tokenizer() const { return eng_.tokenizer(); }
     const TDTCTCConfig &config() const { return config_; }
+    /// New: CTC forced alignment of a known transcript (pk_align_pcm): when was each token / word of `text` said.  Needs the vocabulary.
+    AlignResult align(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text); }
+    AlignResult align(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text); }
+    AlignResult align(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text); }
+
     pk_model *model() { return eng_.handle(); }   // the engine handle (the reference returns its ParakeetTDTCTC module tree)
 
   private:
@@ -294,6 +337,12 @@ class TDTTranscriber {
 
     const Tokenizer &tokenizer() const { return eng_.tokenizer(); }
     const TDTConfig &config() const { return config_; }
+    /// New: CTC forced alignment of a known transcript (pk_align_pcm): when was each token / word of `text` said.  Needs the vocabulary and a model
+    /// with a CTC head (the tdt-600m preset has none: the call throws).
+    AlignResult align(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text); }
+    AlignResult align(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text); }
+    AlignResult align(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text); }
+
     pk_model *model() { return eng_.handle(); }
 
   private:
