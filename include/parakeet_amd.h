@@ -357,7 +357,7 @@ void pk_nbest_free(pk_nbest *results, int n_clips);
  * 2 L + 1 state CTC lattice, specified operation by operation in DESIGN.md section 5.5.1 (tests/ctc_align_ref.py is that specification in
  * Python; the device result equals it bit for bit): fp32, one add per cell, predecessor ties stay / previous state / skip, a skip only onto
  * a token that differs from the token before it, end state the last blank unless the last token's state is strictly better.
- * All of it runs on the device (kernels/ctc_align.hip).  pk_group and streaming sessions have no alignment variant; the TDT head has none.
+ * All of it runs on the device (kernels/ctc_align.hip).  pk_group and streaming sessions have no alignment variant; the TDT head: pk_tdt_align* below.
  *
  * pk_ctc_align: HOST log-probs in.  Needs a device, no model.  logp / n_frames / B / T / V / blank as pk_ctc_beam_search.  ids: the token
  * strings of the B utterances packed, utterance b = ids[id_offsets[b] .. id_offsets[b+1]) (id_offsets[0] = 0; an empty string is valid).
@@ -390,6 +390,58 @@ pk_status pk_ctc_align_decode_timed(pk_model *m, const float *enc, const int32_t
  * words.  score / total (either optional) / ok: [n_clips], as pk_ctc_align. */
 pk_status pk_align_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts_or_null,
                        const int32_t *ids_or_null, const int32_t *id_offsets, pk_result **results, float *score, float *total, int32_t *ok);
+
+/* ---- TDT forced alignment of a GIVEN transcript ---------------------------------------------------------------------------
+ * The same question through the TDT head (label + duration joint), for the models without a CTC head.  The lattice of an utterance of T frames
+ * and U tokens is T x (U + 1) joint evaluations -- cell (t, u): frame t, the prediction net having consumed ids[:u] -- with the arcs of the
+ * greedy loop (src/tdt.cpp:62-106): blank with duration i to (t + max(dur[i], 1), u), label ids[u] with duration i to (t + dur[i], u + 1), an
+ * arc past the last frame ends the utterance when all U tokens are out.  The alignment is the max-plus path, specified operation by operation in
+ * DESIGN.md section 5.5.2 (tests/tdt_align_ref.py is that specification; the device result equals it bit for bit).  max_symbols_per_step is
+ * not part of the lattice (as in pk_tdt_score).  No forward-algorithm total.  All of it runs on the device (kernels/tdt_align.hip).
+ *
+ * pk_tdt_align: the walk alone on a HOST lattice.  Needs a device, no model.  Utterance b has n_frames[b] >= 1 frames and the tokens
+ * id_offsets[b] .. id_offsets[b+1] (id_offsets[0] = 0; U = 0 is valid); its values are packed utterance after utterance:
+ * lab [T_b][U_b], blk [T_b][U_b + 1], dl [T_b][U_b + 1][D].  durations[D], 1 <= D <= 8.
+ * Outputs: start / end / dur_idx / conf packed as the tokens (token k emitted at frame start[k] with duration index dur_idx[k],
+ * end[k] = min(start[k] + max(dur, 1) - 1, T - 1), conf[k] = exp(lab[start[k]][k])), score[B] the path's log-probability, ok[B] = 1, or 0
+ * where no path reaches the end: then score = -inf and the utterance's arrays are 0.
+ * PK_ERR_INVALID (before any device work): B < 1, n_frames[b] < 1, offsets that decrease.
+ * PK_ERR_UNSUPPORTED (before anything is allocated): D outside [1, 8], a duration outside [0, 8], more than 1535 tokens in an utterance, or
+ * more than 1 GiB of scratch: with cells = sum_b T_b (U_b + 1) and labs = sum_b T_b U_b, 4 (labs + cells (1 + D)) + cells bytes. */
+pk_status pk_tdt_align(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int B,
+                       const int32_t *id_offsets, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, float *score, int32_t *ok);
+/* Prediction net over every prefix + enc_proj + the lattice (joint of every cell in row chunks: the [cells][V + D] logits never exist at once)
+ * + the walk, on the model's stream.  enc [B][T][hidden] resp. packed with n_frames[B]; ids packed with id_offsets[B + 1].
+ * PK_ERR_INVALID: an id outside [0, V) or equal to blank, decreasing offsets.  PK_ERR_UNSUPPORTED: a model without a TDT joint (RNN-T head,
+ * encoder-only), a gemm_bf16 model (its decode weights exist only rounded), or past the limits above; the scratch then also counts
+ * chunk_rows (V + D + J) 4 bytes of the rows chunk and (U_max + 1) B (J + 1) 4 bytes of the prediction net's outputs.  A boost trie set on
+ * the model does not matter. */
+pk_status pk_tdt_align_decode(pk_model *m, const float *enc, int B, int T, const int32_t *ids, const int32_t *id_offsets, int32_t *start,
+                              int32_t *end, int32_t *dur_idx, float *conf, float *score, int32_t *ok);
+pk_status pk_tdt_align_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids,
+                                     const int32_t *id_offsets, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, float *score,
+                                     int32_t *ok);
+/* Stage timers (tools/bench_tdt_align.py), each between hipEvents on the model's stream, medians of `reps` passes after one warm-up:
+ * ms[0] = prediction net (uploads, U_max + 1 lock-step steps), ms[1] = lattice (enc_proj + activation + heads product + reduction, all
+ * chunks), ms[2] = the walk and back-trace, ms[3] = the heads product of ONE chunk alone (min(chunk_rows, cells) x (V + D) x J, timed on its
+ * own after the passes: what the lattice stage's activation and reduction kernels cost on top of it).  n_frames NULL: uniform [B][T]. */
+pk_status pk_tdt_align_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids,
+                                    const int32_t *id_offsets, int reps, float ms[4]);
+/* One call from PCM and transcripts to timestamps, as pk_align_pcm (same packing, same result layout; the attention context set on the model
+ * applies), through the TDT head: works for models without a CTC head.  score (optional) / ok: [n_clips]. */
+pk_status pk_tdt_align_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts_or_null,
+                           const int32_t *ids_or_null, const int32_t *id_offsets, pk_result **results, float *score, int32_t *ok);
+/* Diagnostic: the lattice values of a ragged batch as pk_tdt_align takes them, brought back to the host.  chunk_rows > 0 overrides the
+ * engine's chunk size (lattice rows per heads product), 0 keeps it.  lab / blk / dl receive labs / cells / cells D floats FOLLOWED BY
+ * PK_DIAG_TDT_LATTICE_GUARD more each: the device buffers are filled with the pattern 0x7FC5A5A5 before the first launch and copied back
+ * whole, so a word the launches did not write comes back as that pattern. */
+#define PK_DIAG_TDT_LATTICE_GUARD 64
+pk_status pk_diag_tdt_lattice(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                              int chunk_rows, float *lab, float *blk, float *dl);
+/* Diagnostic: out[0] / out[1] = free / total bytes of the current device (hipMemGetInfo), out[2] = the bytes of device memory the grow-only
+ * buffers of m's stage entry points hold (workspace, io scratch, TDT alignment scratch; 0 with m == NULL): what a call that promises to
+ * allocate nothing must leave unchanged. */
+pk_status pk_diag_mem_info(pk_model *m, uint64_t out[3]);
 
 /* ---- one node, several GPUs: utterance shards (the reference has no multi-device path, README.md:513) ----------
  * A pk_group is one model REPLICA per device of this process: the safetensors file is mapped once and every replica is built from that

@@ -188,6 +188,13 @@ _LATE_SIGNATURES = {
     "pk_ctc_align_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
     "pk_ctc_align_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.c_int, f32p],
     "pk_align_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.POINTER(C.POINTER(PkResult)), f32p, f32p, i32p],
+    "pk_tdt_align": [f32p, f32p, f32p, i32p, C.c_int, i32p, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, i32p],
+    "pk_tdt_align_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, i32p, f32p, f32p, i32p],
+    "pk_tdt_align_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, i32p, i32p, f32p, f32p, i32p],
+    "pk_tdt_align_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, f32p],
+    "pk_diag_mem_info": [C.c_void_p, C.POINTER(C.c_uint64)],
+    "pk_tdt_align_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.POINTER(C.POINTER(PkResult)), f32p, i32p],
+    "pk_diag_tdt_lattice": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, f32p, f32p, f32p],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -309,6 +316,39 @@ def ctc_align(logp, ids, blank, total=True):
     lp = _c(logp)
     B, T, V = lp.shape
     return _align_call(lib().pk_ctc_align, (_f(lp), None, B, T, V, blank), ids, total)
+
+
+# ---- TDT forced alignment of given token strings (include/parakeet_amd.h) ------
+TDT_LATTICE_GUARD = 64                                              # PK_DIAG_TDT_LATTICE_GUARD
+
+
+def _tdt_align_call(fn, head, off):
+    """-> list (one dict per utterance) of start / end / dur_idx / conf arrays [U_b], score, ok.  head: the arguments in front of id_offsets."""
+    B = len(off) - 1
+    n = max(1, int(off[-1]))
+    st = np.zeros(n, np.int32); en = np.zeros(n, np.int32); di = np.zeros(n, np.int32); cf = np.zeros(n, np.float32)
+    sc = np.zeros(B, np.float32); ok = np.zeros(B, np.int32)
+    check(fn(*head, _i(off), _i(st), _i(en), _i(di), _f(cf), _f(sc), _i(ok)))
+    return [dict(start=st[off[b]:off[b + 1]].copy(), end=en[off[b]:off[b + 1]].copy(), dur_idx=di[off[b]:off[b + 1]].copy(),
+                 conf=cf[off[b]:off[b + 1]].copy(), score=sc[b], ok=int(ok[b])) for b in range(B)]
+
+
+def mem_info(model=None):
+    """pk_diag_mem_info -> (free bytes, total bytes of the device, bytes the model's grow-only stage buffers hold)"""
+    out = (C.c_uint64 * 3)()
+    check(lib().pk_diag_mem_info(model._h if model is not None else None, out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def tdt_align(lattices, durations):
+    """pk_tdt_align: lattices = one (lab [T][U], blk [T][U+1], dl [T][U+1][D]) per utterance.  Needs a device, no model."""
+    T = np.asarray([x[1].shape[0] for x in lattices], np.int32)
+    off = np.zeros(len(lattices) + 1, np.int32)
+    off[1:] = np.cumsum([x[1].shape[1] - 1 for x in lattices])
+    cat = lambda k: _c(np.concatenate([_c(x[k]).ravel() for x in lattices] + [np.zeros(1, np.float32)]))
+    lab, blk, dl = cat(0), cat(1), cat(2)
+    dur = np.ascontiguousarray(durations, np.int32)
+    return _tdt_align_call(lib().pk_tdt_align, (_f(lab), _f(blk), _f(dl), _i(dur), len(dur), _i(T), len(T)), off)
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -1638,6 +1678,82 @@ class Model:
             d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(sc[i]), ok=int(ok[i]))
             if total:
                 d["total"] = float(tt[i])
+            if ok[i]:
+                d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
+                d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
+                d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
+                d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
+            out.append(d)
+        lib().pk_results_free(res, n)
+        return out
+
+    def _enc_head(self, enc):
+        """(ragged?, packed rows, T[B]) of enc [B][T][d] or a list of [T_b][d] matrices"""
+        if isinstance(enc, (list, tuple)):
+            T = np.asarray([e.shape[0] for e in enc], np.int32)
+            return True, _c(np.concatenate([_c(e) for e in enc], axis=0)), T
+        x = _c(enc)
+        return False, x, np.full(x.shape[0], x.shape[1], np.int32)
+
+    def tdt_align_decode(self, enc, ids):
+        """pk_tdt_align_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch); ids: one token sequence per
+        utterance -> as capi.tdt_align."""
+        rag, x, T = self._enc_head(enc)
+        pid, off = _pack_ids(ids)
+        if rag:
+            return _tdt_align_call(lib().pk_tdt_align_decode_ragged, (self._h, _f(x), _i(T), len(T), _i(pid)), off)
+        return _tdt_align_call(lib().pk_tdt_align_decode, (self._h, _f(x), x.shape[0], x.shape[1], _i(pid)), off)
+
+    def tdt_align_decode_timed(self, enc, ids, reps=5):
+        """pk_tdt_align_decode_timed -> (prediction net ms, lattice ms, walk ms, heads product of one chunk alone ms), HIP events, medians of
+        reps passes."""
+        rag, x, T = self._enc_head(enc)
+        pid, off = _pack_ids(ids)
+        ms = np.zeros(4, np.float32)
+        check(lib().pk_tdt_align_decode_timed(self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], _i(pid), _i(off), reps, _f(ms)))
+        return float(ms[0]), float(ms[1]), float(ms[2]), float(ms[3])
+
+    def tdt_lattice(self, enc, ids, chunk_rows=0):
+        """pk_diag_tdt_lattice: enc a list of [T_b][d] matrices (or [B][T][d]) -> list of dicts lab [T][U], blk [T][U+1], dl [T][U+1][D], and
+        "guard": the three buffers' words past the written extent as uint32 (the fill pattern 0x7FC5A5A5 when nothing wrote there)."""
+        _, x, T = self._enc_head(enc)
+        pid, off = _pack_ids(ids)
+        U = np.diff(off).astype(np.int64)
+        D = len(self.cfg.durations)
+        cells, labs = int((T * (U + 1)).sum()), int((T * U).sum())
+        G = TDT_LATTICE_GUARD
+        lab = np.zeros(labs + G, np.float32); blk = np.zeros(cells + G, np.float32); dl = np.zeros(cells * D + G, np.float32)
+        check(lib().pk_diag_tdt_lattice(self._h, _f(x), _i(T), len(T), _i(pid), _i(off), int(chunk_rows), _f(lab), _f(blk), _f(dl)))
+        out, c0, l0 = [], 0, 0
+        for b in range(len(T)):
+            t, u = int(T[b]), int(U[b])
+            out.append(dict(lab=lab[l0:l0 + t * u].reshape(t, u).copy(), blk=blk[c0:c0 + t * (u + 1)].reshape(t, u + 1).copy(),
+                            dl=dl[c0 * D:(c0 + t * (u + 1)) * D].reshape(t, u + 1, D).copy()))
+            c0 += t * (u + 1); l0 += t * u
+        guard = np.concatenate([lab[labs:], blk[cells:], dl[cells * D:]]).view(np.uint32)
+        return out, guard
+
+    def align_tdt(self, clips, texts=None, ids=None):
+        """pk_tdt_align_pcm: Model.align through the TDT head (no CTC head needed) -> list of dicts as align() returns them, without "total"."""
+        assert (texts is None) != (ids is None), "texts or ids"
+        if isinstance(clips, tuple):
+            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
+        else:
+            pcm, off = pack_clips(clips)
+        n = len(off) - 1
+        sc = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
+        res = C.POINTER(PkResult)()
+        if texts is not None:
+            keep = (C.c_char_p * n)(*[t.encode() for t in texts])
+            tail = (keep, None, None)
+        else:
+            pid, poff = _pack_ids(ids)
+            tail = (None, _i(pid), _i(poff))
+        check(lib().pk_tdt_align_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, C.byref(res), _f(sc), _i(ok)))
+        out = []
+        for i in range(n):
+            r = res[i]
+            d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(sc[i]), ok=int(ok[i]))
             if ok[i]:
                 d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
                 d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]

@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_batch.cpp -- the resident two-stream batch pipeline (pk_batch_*) and the one-call API on top of it:
-// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest, pk_align_pcm and the result stores they hand out.
+// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest, pk_align_pcm, pk_tdt_align_pcm and the result stores they hand out.
 #include <algorithm>
 #include <cstring>
 
@@ -867,11 +867,11 @@ struct NbestStore {           // owns everything a pk_nbest array points into
 };
 }  // namespace
 
-// One planned batch of the one-call entry points that work on the CTC rows (clips order[0 .. nc) of the call) from PCM to the log-softmax
-// rows, left on the device in m.ws.ctc_lp (packed; extents in r and m.ws.rv.seq).  sized(r), if given, runs once the extents are known and
-// before anything is allocated or queued.
-static void encode_batch_ctc(Model &m, const float *pcm, const int64_t *offsets, const int *order, int nc, RagBatch &r,
-                             const std::function<void(const RagBatch &)> &sized = nullptr) {
+// One planned batch of the one-call entry points that work on the encoder's rows (clips order[0 .. nc) of the call) from PCM to the encoder
+// output m.ws.x and, with ctc, the log-softmax rows of the CTC head, left on the device in m.ws.ctc_lp (packed; extents in r and m.ws.rv.seq).
+// sized(r), if given, runs once the extents are known and before anything is allocated or queued.
+static void encode_batch(Model &m, const float *pcm, const int64_t *offsets, const int *order, int nc, RagBatch &r,
+                             const std::function<void(const RagBatch &)> &sized = nullptr, bool ctc = true) {
     std::vector<int64_t> blens(nc);
     for (int i = 0; i < nc; ++i) blens[i] = offsets[order[i] + 1] - offsets[order[i]];
     const int64_t longest = blens[0];
@@ -883,7 +883,7 @@ static void encode_batch_ctc(Model &m, const float *pcm, const int64_t *offsets,
         PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[order[i]], (size_t)blens[i] * 4, hipMemcpyHostToDevice, m.stream));
     m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), nc, m.stream);
     m.run_encoder(m.ws, m.ws.feats.as<float>(), nc, 0, -1, 0, m.stream);
-    m.run_ctc(m.ws, m.ws.x.as<float>(), nc, r.T_max, true, m.stream);
+    if (ctc) m.run_ctc(m.ws, m.ws.x.as<float>(), nc, r.T_max, true, m.stream);
 }
 
 pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
@@ -907,7 +907,7 @@ pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *
         for (size_t k = 0; k + 1 < bstart.size(); ++k) {
             const int c0 = bstart[k], nc = bstart[k + 1] - c0;
             RagBatch r;
-            encode_batch_ctc(m, pcm, offsets, order.data() + c0, nc, r);
+            encode_batch(m, pcm, offsets, order.data() + c0, nc, r);
             const int T = r.T_max;
             run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream);
             PK_CHECK_LAUNCH();
@@ -940,6 +940,80 @@ pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *
     });
 }
 
+// pk_align_pcm / pk_tdt_align_pcm: the transcripts of the call (texts tokenised, or the given ids checked) packed in the caller's clip order
+static void align_transcripts(Model &m, int n_clips, const char *const *texts, const int32_t *ids_in, const int32_t *id_offsets_in, int V, int blank,
+                              std::vector<int32_t> &all_ids, std::vector<int32_t> &all_off) {
+    all_ids.clear(); all_off.assign(n_clips + 1, 0);
+    if (texts) {
+        need(m.tok.loaded(), "aligning text needs the model's vocabulary");
+        for (int c = 0; c < n_clips; ++c) {
+            need(texts[c] != nullptr, "texts[c]");
+            for (int v : m.tok.encode(texts[c])) all_ids.push_back(v);
+            all_off[c + 1] = (int32_t)all_ids.size();
+        }
+        align_check_args(all_ids.data(), all_off.data(), n_clips, V, blank);
+    } else {
+        align_check_args(ids_in, id_offsets_in, n_clips, V, blank);
+        all_off.assign(id_offsets_in, id_offsets_in + n_clips + 1);
+        all_ids.assign(ids_in, ids_in + all_off[n_clips]);
+    }
+}
+
+// The body of both: plan the batches as pk_transcribe_pcm does, encode each, align it through the chosen head, store tokens and words.
+static void align_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids,
+                      const std::vector<int32_t> &all_off, pk_result **results, float *score, float *total, int32_t *ok) {
+    const int V = m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;      // (CTC head only)
+    std::vector<int64_t> clip_len(n_clips);
+    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+    std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
+    plan_batches(clip_len.data(), n_clips, order, bstart);
+    auto store = new_store(n_clips);
+    std::vector<int32_t> bids, boff, nfr, st, en, di, okv;
+    std::vector<float> cf, sc, tt;
+    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+        boff.assign(nc + 1, 0); bids.clear();
+        for (int i = 0; i < nc; ++i) {
+            const int c = order[c0 + i];
+            bids.insert(bids.end(), all_ids.begin() + all_off[c], all_ids.begin() + all_off[c + 1]);
+            boff[i + 1] = (int32_t)bids.size();
+        }
+        RagBatch r;
+        encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
+            nfr.assign(rb.T.begin(), rb.T.begin() + nc);               // (the plans refuse before the batch is encoded)
+            if (tdt) tdt_align_plan(m.talign, nfr.data(), nc, rb.T_max, boff.data(), m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden);
+            else align_plan(m.align, nfr.data(), nc, rb.T_max, boff.data());
+        }, !tdt);
+        const size_t n = bids.size();
+        st.assign(n + 1, 0); en.assign(n + 1, 0); di.assign(n + 1, 0); cf.assign(n + 1, 0.0f); sc.resize(nc); tt.resize(nc); okv.resize(nc);
+        if (tdt) {
+            tdt_align_upload(m.talign, bids.data(), m.stream);
+            run_tdt_align_pred(m, m.talign, bids.data(), m.stream);
+            m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
+            run_tdt_align_lattice(m, m.talign, m.ws.ep.as<float>(), m.stream);
+            run_tdt_align_dp(m.talign, m.stream);
+            PK_CHECK_LAUNCH();
+            tdt_align_copy_out(m.talign, st.data(), en.data(), di.data(), cf.data(), sc.data(), okv.data(), m.stream);
+        } else {
+            run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, bids.data(), total != nullptr, m.stream);
+            PK_CHECK_LAUNCH();
+            align_copy_out(m.align, st.data(), en.data(), cf.data(), sc.data(), total ? tt.data() : nullptr, okv.data(), m.stream);
+        }
+        for (int i = 0; i < nc; ++i) {
+            const int c = order[c0 + i], o0 = boff[i], L = boff[i + 1] - o0;
+            const bool good = okv[i] != 0;
+            store_tokens(m, *store, c, L, bids.data() + o0, good ? st.data() + o0 : nullptr, good ? en.data() + o0 : nullptr, good ? cf.data() + o0 : nullptr);
+            ok[c] = okv[i];
+            if (score) score[c] = sc[i];
+            if (total) total[c] = tt[i];
+        }
+    }
+    pk_result *out = publish_store(std::move(store), n_clips, true);
+    for (int c = 0; c < n_clips; ++c)
+        if (!ok[c]) out[c].start_frame = out[c].end_frame = nullptr, out[c].confidence = nullptr;
+    *results = out;
+}
+
 pk_status pk_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
                        const int32_t *id_offsets_in, pk_result **results, float *score, float *total, int32_t *ok) {
     return guard([&] {
@@ -948,59 +1022,24 @@ pk_status pk_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets, in
         Model &m = *h->m;
         if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC alignment needs one");
         const int V = m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;
-        std::vector<int32_t> all_ids, all_off(n_clips + 1, 0);      // the transcripts, packed in the caller's clip order
-        if (texts) {
-            need(m.tok.loaded(), "aligning text needs the model's vocabulary");
-            for (int c = 0; c < n_clips; ++c) {
-                need(texts[c] != nullptr, "texts[c]");
-                for (int v : m.tok.encode(texts[c])) all_ids.push_back(v);
-                all_off[c + 1] = (int32_t)all_ids.size();
-            }
-            align_check_args(all_ids.data(), all_off.data(), n_clips, V, blank);
-        } else {
-            align_check_args(ids_in, id_offsets_in, n_clips, V, blank);
-            all_off.assign(id_offsets_in, id_offsets_in + n_clips + 1);
-            all_ids.assign(ids_in, ids_in + all_off[n_clips]);
-        }
+        std::vector<int32_t> all_ids, all_off;
+        align_transcripts(m, n_clips, texts, ids_in, id_offsets_in, V, blank, all_ids, all_off);
         m.require_gpu();
-        std::vector<int64_t> clip_len(n_clips);
-        for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
-        std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
-        plan_batches(clip_len.data(), n_clips, order, bstart);
-        auto store = new_store(n_clips);
-        std::vector<int32_t> bids, boff, nfr, st, en, okv;
-        std::vector<float> cf, sc, tt;
-        for (size_t k = 0; k + 1 < bstart.size(); ++k) {
-            const int c0 = bstart[k], nc = bstart[k + 1] - c0;
-            boff.assign(nc + 1, 0); bids.clear();
-            for (int i = 0; i < nc; ++i) {
-                const int c = order[c0 + i];
-                bids.insert(bids.end(), all_ids.begin() + all_off[c], all_ids.begin() + all_off[c + 1]);
-                boff[i + 1] = (int32_t)bids.size();
-            }
-            RagBatch r;
-            encode_batch_ctc(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
-                nfr.assign(rb.T.begin(), rb.T.begin() + nc);
-                align_plan(m.align, nfr.data(), nc, rb.T_max, boff.data());     // (refuses before the batch is encoded)
-            });
-            run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, bids.data(), total != nullptr, m.stream);
-            PK_CHECK_LAUNCH();
-            const size_t n = bids.size();
-            st.assign(n + 1, 0); en.assign(n + 1, 0); cf.assign(n + 1, 0.0f); sc.resize(nc); tt.resize(nc); okv.resize(nc);
-            align_copy_out(m.align, st.data(), en.data(), cf.data(), sc.data(), total ? tt.data() : nullptr, okv.data(), m.stream);
-            for (int i = 0; i < nc; ++i) {
-                const int c = order[c0 + i], o0 = boff[i], L = boff[i + 1] - o0;
-                const bool good = okv[i] != 0;
-                store_tokens(m, *store, c, L, bids.data() + o0, good ? st.data() + o0 : nullptr, good ? en.data() + o0 : nullptr, good ? cf.data() + o0 : nullptr);
-                ok[c] = okv[i];
-                if (score) score[c] = sc[i];
-                if (total) total[c] = tt[i];
-            }
-        }
-        pk_result *out = publish_store(std::move(store), n_clips, true);
-        for (int c = 0; c < n_clips; ++c)
-            if (!ok[c]) out[c].start_frame = out[c].end_frame = nullptr, out[c].confidence = nullptr;
-        *results = out;
+        align_pcm(m, false, pcm, offsets, n_clips, all_ids, all_off, results, score, total, ok);
+    });
+}
+
+pk_status pk_tdt_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
+                           const int32_t *id_offsets_in, pk_result **results, float *score, int32_t *ok) {
+    return guard([&] {
+        need(h && pcm && offsets && results && ok && n_clips > 0, "model/pcm/offsets/results/ok/n_clips");
+        need(texts || id_offsets_in, "texts or ids/id_offsets");
+        Model &m = *h->m;
+        tdt_align_model_checks(m);
+        std::vector<int32_t> all_ids, all_off;
+        align_transcripts(m, n_clips, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
+        m.require_gpu();
+        align_pcm(m, true, pcm, offsets, n_clips, all_ids, all_off, results, score, nullptr, ok);
     });
 }
 

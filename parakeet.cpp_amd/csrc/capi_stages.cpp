@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_stages.cpp -- the stage entry points of the C boundary on caller buffers: mel, subsample, encode, conformer blocks,
-// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix beam search and the CTC forced alignment.
+// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix beam search and the CTC and TDT forced alignments.
 #include <algorithm>
 #include <cstring>
 
@@ -149,6 +149,41 @@ static void ctc_align_decode(Model &m, const float *enc, const int32_t *n_frames
     run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), B, T, n_frames ? m.ws.rv.seq : SeqRag(), V, blank, ids, total != nullptr, m.stream);
     PK_CHECK_LAUNCH();
     align_copy_out(m.align, start, end, conf, score, total, ok, m.stream);
+}
+
+// Sizes the workspace for and queues one planned (tdt_align_checks) TDT alignment of enc (host rows, uniform or packed) on the model's stream; results stay in m.talign.
+// ev (optional, 4 events): recorded before the prediction net, the lattice, the walk and after it.
+static void tdt_align_queue(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids, bool walk,
+                            hipEvent_t *ev = nullptr, bool upload_enc = true) {
+    size_t rows;
+    T = size_ws(m, n_frames, B, T, rows);
+    if (upload_enc) PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    if (ev) PK_HIP(hipEventRecord(ev[0], m.stream));
+    tdt_align_upload(m.talign, ids, m.stream);
+    run_tdt_align_pred(m, m.talign, ids, m.stream);
+    if (ev) PK_HIP(hipEventRecord(ev[1], m.stream));
+    m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
+    run_tdt_align_lattice(m, m.talign, m.ws.ep.as<float>(), m.stream);
+    if (ev) PK_HIP(hipEventRecord(ev[2], m.stream));
+    if (walk) run_tdt_align_dp(m.talign, m.stream);
+    if (ev) PK_HIP(hipEventRecord(ev[3], m.stream));
+}
+
+static void tdt_align_checks(Model &m, const int32_t *n_frames, int B, int T, const int32_t *ids, const int32_t *id_offsets, int chunk_rows) {
+    tdt_align_model_checks(m);
+    align_check_args(ids, id_offsets, B, m.cfg.vocab_size, m.cfg.blank_id);
+    if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+    need(chunk_rows >= 0, "chunk_rows");
+    m.require_gpu();
+    tdt_align_plan(m.talign, n_frames, B, T, id_offsets, m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden, chunk_rows);
+}
+
+static void tdt_align_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids, const int32_t *id_offsets,
+                             int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, float *score, int32_t *ok) {
+    tdt_align_checks(m, n_frames, B, T, ids, id_offsets, 0);
+    tdt_align_queue(m, enc, n_frames, B, T, ids, true);
+    PK_CHECK_LAUNCH();
+    tdt_align_copy_out(m.talign, start, end, dur_idx, conf, score, ok, m.stream);
 }
 
 extern "C" {
@@ -536,6 +571,107 @@ pk_status pk_ctc_align_decode_timed(pk_model *h, const float *enc, const int32_t
         }
         std::sort(head.begin(), head.end()); std::sort(align.begin(), align.end());
         ms[0] = head[head.size() / 2]; ms[1] = align[align.size() / 2];
+    });
+}
+
+/* ---- TDT forced alignment of given token strings (kernels/tdt_align.hip) ------------------------------------------------------------ */
+pk_status pk_tdt_align(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int B,
+                       const int32_t *id_offsets, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, float *score, int32_t *ok) {
+    return guard([&] {
+        need(B >= 1 && id_offsets && n_frames && durations, "B/id_offsets/n_frames/durations");
+        need(id_offsets[0] == 0, "id_offsets[0] must be 0");
+        for (int b = 0; b < B; ++b) {
+            need(id_offsets[b + 1] >= id_offsets[b], "id_offsets decrease");
+            need(n_frames[b] > 0, "n_frames[b] must be positive");
+        }
+        need(blk && dl && score && ok, "blk/dl/score/ok");
+        need(id_offsets[B] == 0 || (lab && start && end && dur_idx && conf), "lab/start/end/dur_idx/conf");
+        TdtAlignWs ws;
+        tdt_align_plan(ws, n_frames, B, 0, id_offsets, durations, D);          // (host only: refuses before a device is looked for or anything is allocated)
+        need_device();
+        tdt_align_upload(ws, nullptr, nullptr);
+        if (ws.labs) PK_HIP(hipMemcpyAsync(ws.lab.p, lab, (size_t)ws.labs * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.blk.p, blk, (size_t)ws.cells * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.dl.p, dl, (size_t)ws.cells * D * 4, hipMemcpyHostToDevice, nullptr));
+        run_tdt_align_dp(ws, nullptr);
+        PK_CHECK_LAUNCH();
+        tdt_align_copy_out(ws, start, end, dur_idx, conf, score, ok, nullptr);
+    });
+}
+
+pk_status pk_tdt_align_decode(pk_model *h, const float *enc, int B, int T, const int32_t *ids, const int32_t *id_offsets, int32_t *start,
+                              int32_t *end, int32_t *dur_idx, float *conf, float *score, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && score && ok && T > 0, "model/enc/score/ok/T");
+        tdt_align_decode(*h->m, enc, nullptr, B, T, ids, id_offsets, start, end, dur_idx, conf, score, ok);
+    });
+}
+
+pk_status pk_tdt_align_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *ids,
+                                     const int32_t *id_offsets, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, float *score,
+                                     int32_t *ok) {
+    return guard([&] {
+        need(h && enc && n_frames && score && ok, "model/enc/n_frames/score/ok");
+        tdt_align_decode(*h->m, enc, n_frames, B, 0, ids, id_offsets, start, end, dur_idx, conf, score, ok);
+    });
+}
+
+pk_status pk_tdt_align_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids,
+                                    const int32_t *id_offsets, int reps, float ms[4]) {
+    return guard([&] {
+        need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
+        Model &m = *h->m;
+        tdt_align_checks(m, n_frames, B, T, ids, id_offsets, 0);
+        struct Ev { hipEvent_t e[4] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        std::vector<float> t[3];
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            tdt_align_queue(m, enc, n_frames, B, T, ids, true, ev.e, r == 0);
+            PK_HIP(hipStreamSynchronize(m.stream));
+            PK_CHECK_LAUNCH();
+            for (int k = 0; k < 3; ++k) {
+                float v = 0;
+                PK_HIP(hipEventElapsedTime(&v, ev.e[k], ev.e[k + 1]));
+                if (r > 0) t[k].push_back(v);
+            }
+        }
+        for (int k = 0; k < 3; ++k) { std::sort(t[k].begin(), t[k].end()); ms[k] = t[k][t[k].size() / 2]; }
+        // the heads product of ONE chunk alone (the rows the last pass left in the activation buffer), for the lattice stage's overhead over it
+        const int n = (int)std::min<int64_t>(m.talign.chunk_rows, m.talign.cells);
+        std::vector<float> hp;
+        for (int r = 0; r <= reps; ++r) {
+            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+            run_tdt_align_heads(m, m.talign, n, m.stream);
+            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            PK_HIP(hipStreamSynchronize(m.stream));
+            PK_CHECK_LAUNCH();
+            float v = 0;
+            PK_HIP(hipEventElapsedTime(&v, ev.e[0], ev.e[1]));
+            if (r > 0) hp.push_back(v);
+        }
+        std::sort(hp.begin(), hp.end());
+        ms[3] = hp[hp.size() / 2];
+    });
+}
+
+pk_status pk_diag_tdt_lattice(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                              int chunk_rows, float *lab, float *blk, float *dl) {
+    return guard([&] {
+        need(h && enc && n_frames && lab && blk && dl, "model/enc/n_frames/lab/blk/dl");
+        Model &m = *h->m;
+        tdt_align_checks(m, n_frames, B, 0, ids, id_offsets, chunk_rows);
+        TdtAlignWs &ws = m.talign;
+        const size_t G = PK_DIAG_TDT_LATTICE_GUARD, nl = (size_t)ws.labs + G, nb = (size_t)ws.cells + G, nd = (size_t)ws.cells * ws.D + G;
+        ws.lab.reserve(nl * 4); ws.blk.reserve(nb * 4); ws.dl.reserve(nd * 4);
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.lab.p, 0x7FC5A5A5, nl, m.stream));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.blk.p, 0x7FC5A5A5, nb, m.stream));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.dl.p, 0x7FC5A5A5, nd, m.stream));
+        tdt_align_queue(m, enc, n_frames, B, 0, ids, /*walk=*/false);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(lab, ws.lab.p, nl * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipMemcpyAsync(blk, ws.blk.p, nb * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipMemcpyAsync(dl, ws.dl.p, nd * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
     });
 }
 

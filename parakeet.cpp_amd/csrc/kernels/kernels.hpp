@@ -420,6 +420,36 @@ struct CtcAlignArgs {
 };
 // shape: index into kAlignThreads / kAlignStrip; every utterance of the batch needs 2 L + 1 <= kAlignThreads[shape] * kAlignStrip[shape]
 void launch_ctc_align(const CtcAlignArgs &a, int shape, hipStream_t s);
+
+// TDT forced alignment of GIVEN token strings (kernels/tdt_align.hip).  The lattice of utterance b is T_b x (U_b + 1)
+// cells, cell (t, u) = the joint at frame t with the prediction net having consumed ids[:u]; cell c = t (U_b + 1) + u of the utterance sits at
+// element cell_off[b] + c of blk, (cell_off[b] + c) * D of dl and -- for u < U_b -- lab_off[b] + t U_b + u of lab.
+constexpr int kTdtAlignThreads[2] = {64, 256};  // workgroup width of the walk: one wave while the longest diagonal (U + 1 cells) fits it
+constexpr int kTdtAlignMaxDur = 8;              // largest duration value: the ring of diagonals holds kTdtAlignMaxDur + 2 of them at most
+constexpr int kTdtAlignMaxTokens = 1535;        // U <= this: (kTdtAlignMaxDur + 2) diagonals x (U + 1) cells x 4 bytes <= 61440 bytes of LDS
+struct TdtLattice {
+    int B, D;
+    int durations[8];
+    const int *T;                               // [B] frames
+    const int *id_off;                          // [B + 1] packed token strings
+    const int64_t *cell_off, *lab_off;          // [B + 1]
+    float *lab, *blk, *dl;
+};
+struct TdtAlignArgs {
+    TdtLattice lt;
+    unsigned char *bp;                          // one byte per cell, utterance b from byte cell_off[b]: i = blank arc i, D + i = label arc i, 255 none
+    int *start, *end, *dur_idx; float *conf;    // packed as ids (zero-filled by the caller: an utterance with ok = 0 writes none)
+    float *score; int *ok;                      // [B]
+    int u_max, dur_max;                         // over the batch: the dynamic LDS is (dur_max + 2) * (u_max + 1) floats
+};
+void launch_tdt_align(const TdtAlignArgs &a, hipStream_t s);
+// Lattice rows [row0, row0 + n) of the batch (row = cell_off[b] + t (U_b + 1) + u): z[i][J] = relu(ep[ep_row0[b] + t][J] + pp[u B + b][J]), the
+// joint's hidden activation (natural columns: the A operand of the heads product)
+void launch_tdt_lattice_act(const TdtLattice &lt, const int *ep_row0, const float *ep, const float *pp, int J, int64_t row0, int n, float *z, hipStream_t s);
+// ... and the same rows of the heads product's output, logits[i][V + D], taken to their 2 + D kept values: canonical log-softmax over the V label
+// columns and over the D duration columns, gathered at ids[u] (u < U_b) and blank
+void launch_tdt_lattice_keep(const TdtLattice &lt, const int *ids, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s);
+
 struct TdtState {
     int B, T, V, D, L, Hp, blank, max_symbols, max_tokens, max_steps;
     TrieDev trie;

@@ -1,0 +1,248 @@
+// parakeet.cpp_amd/csrc/kernels/tdt_align.hip -- TDT forced alignment of a GIVEN token string on the device.
+//
+// The specification is tests/tdt_align_ref.py: the T x (U + 1) lattice of joint evaluations (frame t, prediction net after ids[:u]), blank arc i
+// to (t + max(dur[i], 1), u), label arc i to (t + dur[i], u + 1), one terminal END; a max-plus walk in pull form, candidates blank 0 .. D-1 then
+// label 0 .. D-1, each alpha[src] + (x + dl) as two fp32 adds, strict > (the earlier candidate stays).  Every value is compared bit for bit.
+//
+//   tdt_lattice_act_kernel    z = relu(enc_proj[t] + pred_proj[u]) for a chunk of lattice rows, as the decode loop's joint activation forms it
+//       (decode_dev.hpp SK_ACT: enc_proj + (pred_proj [+ bias]), > 0 ? s : 0), natural columns: the A operand of the heads product on the fp32
+//       GEMM.  One wave per row, float4 where J allows.
+//   tdt_lattice_keep_kernel   one wave per row of the heads product's output [V + D]: the canonical log-softmax (row maximum, dexpf_nonpos,
+//       64 strided partial sums in index order, wave_sum64, dlogf; the duration head through wave_logsoftmax_argmax's low-8 form, exactly the
+//       decision kernel's) and only 2 + D values leave: the label log-prob of ids[u], the blank's, the D duration log-probs.  The chunk's logits
+//       are the only place a whole row exists.
+//   tdt_align_kernel<NT>      one workgroup of NT threads per utterance, advancing by anti-diagonals d = t + u: every predecessor of a cell lies
+//       on an earlier diagonal (blank i on d - max(dur, 1), label i on d - dur - 1, so also the dur = 0 label arc from (t, u - 1)).  alpha lives
+//       in LDS as a ring of dur_max + 2 diagonals of u_max + 1 floats, indexed [d % ring][u]; ONE barrier per diagonal (diagonal d + 1 overwrites
+//       the slot of d - dur_max - 1, which diagonal d was the last to read).  Thread i takes the cells u = lo + i, lo + i + NT, ... of the
+//       diagonal; a cell's 2 D candidates read the source cell's values from memory (L2: 2 + D floats per cell) and its alpha from the ring.
+//       Back-pointers: one byte per cell in global memory (the arc's index, 255 = unreachable).  END is evaluated by thread 0 from the alpha of
+//       the last kTdtAlignMaxDur frames of columns U - 1 and U, kept in a small LDS table; the back-trace is thread 0 walking the bytes (one
+//       dependent load per arc, <= T + U of them), conf[k] = dexpf(lab[start[k]][k]) by all threads afterwards.
+//
+// Limits (host side: tdt_align.cpp refuses with PK_ERR_UNSUPPORTED before anything is allocated):
+//   durations 0 <= dur[i] <= kTdtAlignMaxDur = 8, 1 <= D <= 8; U_b <= kTdtAlignMaxTokens = 1535 -- from the LDS arithmetic
+//   (8 + 2) diagonals x 1536 cells x 4 bytes = 61440 bytes <= the 64 KB a workgroup may take, not from a measurement;
+//   scratch of a call <= 1 GiB (formula: tdt_align.hpp).
+//
+// Code objects (hipcc -O3 --offload-arch=gfx950, from the .s of -save-temps):
+//   tdt_align_kernel< 64>       39 VGPR 106 SGPR  LDS 80 B + the ring  scratch 0 B; 0 VGPR spills, 47 SGPRs spilled to VGPR lanes
+//   tdt_align_kernel<256>       39 VGPR 106 SGPR  LDS 80 B + the ring  scratch 0 B; 0 VGPR spills, 47 SGPRs spilled to VGPR lanes
+//   (the durations and blank steps are wave-uniform and live in SGPRs; the back-trace indexes the durations through the kernel argument, so no
+//    array is indexed by a run-time value and nothing goes to private memory)
+//   tdt_lattice_act_kernel      46 VGPR  24 SGPR  LDS  0 B             scratch 0 B; 0 VGPR spills, 0 SGPR spills
+//   tdt_lattice_keep_kernel     47 VGPR  36 SGPR  LDS  0 B             scratch 0 B; 0 VGPR spills, 0 SGPR spills
+//   (the ring: (dur_max + 2) (u_max + 1) 4 bytes of dynamic LDS, 3 KB for 90 tokens and durations up to 4, 61440 bytes at the limits)
+#include "decode_dev.hpp"
+
+namespace pk {
+
+namespace {
+
+// utterance of lattice row r: the last b with cell_off[b] <= r (cell_off ascending, cell_off[B] = rows in all)
+__device__ __forceinline__ int lattice_utt(const int64_t *__restrict__ cell_off, int B, int64_t r) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cell_off[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void tdt_lattice_act_kernel(TdtLattice lt, const int *__restrict__ ep_row0, const float *__restrict__ ep,
+                                                              const float *__restrict__ pp, int J, int64_t row0, int n, float *__restrict__ z) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int64_t r = row0 + i;
+    const int b = lattice_utt(lt.cell_off, lt.B, r);
+    const int U1 = lt.id_off[b + 1] - lt.id_off[b] + 1;
+    const int64_t c = r - lt.cell_off[b];
+    const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
+    const float *er = ep + ((int64_t)ep_row0[b] + t) * J, *pr = pp + ((int64_t)u * lt.B + b) * J;
+    float *zr = z + i * J;
+    if ((J & 3) == 0) {
+        for (int j = 4 * lane; j < J; j += 256) {
+            const float4 e = *reinterpret_cast<const float4 *>(er + j), p = *reinterpret_cast<const float4 *>(pr + j);
+            float4 s;
+            s.x = e.x + p.x; s.y = e.y + p.y; s.z = e.z + p.z; s.w = e.w + p.w;
+            s.x = s.x > 0.0f ? s.x : 0.0f; s.y = s.y > 0.0f ? s.y : 0.0f; s.z = s.z > 0.0f ? s.z : 0.0f; s.w = s.w > 0.0f ? s.w : 0.0f;
+            *reinterpret_cast<float4 *>(zr + j) = s;
+        }
+    } else {
+        for (int j = lane; j < J; j += 64) {
+            const float s = er[j] + pr[j];
+            zr[j] = s > 0.0f ? s : 0.0f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void tdt_lattice_keep_kernel(TdtLattice lt, const int *__restrict__ ids, const float *__restrict__ logits, int V,
+                                                               int blank, int64_t row0, int n) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int64_t r = row0 + i;
+    const int b = lattice_utt(lt.cell_off, lt.B, r);
+    const int U = lt.id_off[b + 1] - lt.id_off[b], U1 = U + 1;
+    const int64_t c = r - lt.cell_off[b];
+    const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
+    const float *x = logits + i * (int64_t)(V + lt.D);
+    // the canonical row log-softmax (decode_dev.hpp wave_logsoftmax_argmax, n > 8): 8 loads in flight per lane, the adds in index order
+    float m = -__builtin_huge_valf();
+    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) m = fmaxf(m, v[q]);
+    }
+    m = wave_max64(m);
+    float p = 0.0f;
+    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { if (i0 + 64 * q < V) p = p + dexpf_nonpos(v[q] - m); }
+    }
+    const float lse = dlogf(wave_sum64(p));
+    if (lane == 0) lt.blk[r] = (x[blank] - m) - lse;
+    if (lane == 1 && u < U) lt.lab[lt.lab_off[b] + (int64_t)t * U + u] = (x[ids[lt.id_off[b] + u]] - m) - lse;
+    wave_logsoftmax_argmax(x + V, lt.D, lt.dl + r * lt.D, lane);    // (D <= 8: lanes 0 .. D-1 store the duration log-probs)
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void tdt_align_kernel(TdtAlignArgs a) {
+    extern __shared__ float ring[];                                 // [dur_max + 2][u_max + 1]
+    __shared__ float tail[2][kTdtAlignMaxDur];                      // alpha[T - 8 + j][U - 1 + c]: what END pulls from
+    __shared__ int s_end[4];
+    const TdtLattice &lt = a.lt;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int T = lt.T[b], i0 = lt.id_off[b], U = lt.id_off[b + 1] - i0, U1 = U + 1, D = lt.D;
+    const int64_t c0 = lt.cell_off[b];
+    const float *lab = lt.lab + lt.lab_off[b], *blk = lt.blk + c0, *dl = lt.dl + c0 * D;
+    unsigned char *bp = a.bp + c0;
+    const int R = a.dur_max + 2, pitch = a.u_max + 1;
+    const float NEG = -__builtin_huge_valf();
+    int dur[8], bstep[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { dur[i] = i < D ? lt.durations[i] : 1; bstep[i] = dur[i] > 1 ? dur[i] : 1; }
+    if (tid < 2 * kTdtAlignMaxDur) (&tail[0][0])[tid] = NEG;
+    __syncthreads();
+    const int t_tail = T - kTdtAlignMaxDur;
+    int dm = 0;                                                     // d % R, kept by increment: the slot of diagonal d - k is dm - k (+ R when negative)
+    auto slot = [&](int k) { const int q = dm - k; return (q < 0 ? q + R : q) * pitch; };
+    for (int d = 0; d < T + U; ++d, dm = dm + 1 == R ? 0 : dm + 1) {
+        const int lo = d - (T - 1) > 0 ? d - (T - 1) : 0, hi = d < U ? d : U;
+        float *cur = ring + dm * pitch;
+        for (int u = lo + tid; u <= hi; u += NT) {
+            const int t = d - u;
+            float best = NEG;
+            int arg = 255;
+            if (d == 0) best = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int ts = t - bstep[i];
+                if (i < D && ts >= 0) {
+                    const int64_t sc = (int64_t)ts * U1 + u;
+                    const float w = blk[sc] + dl[sc * D + i];
+                    const float cand = ring[slot(bstep[i]) + u] + w;
+                    if (cand > best) { best = cand; arg = i; }
+                }
+            }
+            if (u >= 1) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int ts = t - dur[i];
+                    if (i < D && ts >= 0) {
+                        const int64_t sc = (int64_t)ts * U1 + (u - 1);
+                        const float w = lab[(int64_t)ts * U + (u - 1)] + dl[sc * D + i];
+                        const float cand = ring[slot(dur[i] + 1) + (u - 1)] + w;
+                        if (cand > best) { best = cand; arg = D + i; }
+                    }
+                }
+            }
+            cur[u] = best;
+            bp[(int64_t)t * U1 + u] = (unsigned char)arg;
+            if (u >= U - 1 && t >= t_tail) tail[u - (U - 1)][t - t_tail] = best;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        float end = NEG;
+        int et = 0, ecode = 255;
+        for (int t = t_tail > 0 ? t_tail : 0; t < T; ++t) {
+            for (int i = 0; i < D; ++i) {
+                if (t + bstep[i] >= T) {
+                    const int64_t sc = (int64_t)t * U1 + U;
+                    const float cand = tail[1][t - t_tail] + (blk[sc] + dl[sc * D + i]);
+                    if (cand > end) { end = cand; et = t; ecode = i; }
+                }
+            }
+            if (U >= 1) {
+                for (int i = 0; i < D; ++i) {
+                    if (t + dur[i] >= T) {
+                        const int64_t sc = (int64_t)t * U1 + (U - 1);
+                        const float cand = tail[0][t - t_tail] + (lab[(int64_t)t * U + (U - 1)] + dl[sc * D + i]);
+                        if (cand > end) { end = cand; et = t; ecode = D + i; }
+                    }
+                }
+            }
+        }
+        const int ok = end > NEG ? 1 : 0;
+        a.score[b] = end;
+        a.ok[b] = ok;
+        s_end[0] = ok;
+        if (ok) {
+            int t = et, u = U, code = ecode;
+            for (int guard = 0; guard <= T + U; ++guard) {          // every arc moves to an earlier diagonal: at most T + U of them
+                const bool label = code >= D;
+                const int i = label ? code - D : code;
+                if (label) {
+                    if (u == 0) break;                              // (no label arc enters column 0; keeps the stores inside the utterance's arrays)
+                    --u;
+                    const int di = lt.durations[i];                 // (through the kernel argument: dur[] / bstep[] are indexed by constants only and stay in registers)
+                    const int e = t + (di > 1 ? di : 1) - 1;
+                    a.start[i0 + u] = t;
+                    a.end[i0 + u] = e < T ? e : T - 1;
+                    a.dur_idx[i0 + u] = i;
+                }
+                if ((t == 0 && u == 0) || u < 0) break;
+                code = bp[(int64_t)t * U1 + u];
+                if (code == 255) break;                             // (unreachable from a finite END; keeps the walk inside the lattice)
+                const int dc = lt.durations[code >= D ? code - D : code];
+                t -= code >= D ? dc : (dc > 1 ? dc : 1);
+                if (t < 0) break;
+            }
+        }
+    }
+    __syncthreads();
+    if (s_end[0]) {
+        for (int k = tid; k < U; k += NT) a.conf[i0 + k] = dexpf(lab[(int64_t)a.start[i0 + k] * U + k]);
+    }
+}
+
+void launch_tdt_lattice_act(const TdtLattice &lt, const int *ep_row0, const float *ep, const float *pp, int J, int64_t row0, int n, float *z, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(tdt_lattice_act_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, lt, ep_row0, ep, pp, J, row0, n, z);
+}
+
+void launch_tdt_lattice_keep(const TdtLattice &lt, const int *ids, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(tdt_lattice_keep_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, lt, ids, logits, V, blank, row0, n);
+}
+
+void launch_tdt_align(const TdtAlignArgs &a, hipStream_t s) {
+    if (a.dur_max < 0 || a.dur_max > kTdtAlignMaxDur || a.u_max < 0 || a.u_max > kTdtAlignMaxTokens || a.lt.D < 1 || a.lt.D > 8) {
+        fprintf(stderr, "parakeet_amd: internal error: launch_tdt_align outside the kernel's limits (dur_max %d, u_max %d, D %d)\n", a.dur_max, a.u_max, a.lt.D);
+        abort();
+    }
+    const size_t lds = (size_t)(a.dur_max + 2) * (a.u_max + 1) * sizeof(float);
+    if (a.u_max + 1 <= kTdtAlignThreads[0]) hipLaunchKernelGGL(tdt_align_kernel<64>, dim3(a.lt.B), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL(tdt_align_kernel<256>, dim3(a.lt.B), dim3(256), lds, s, a);
+}
+
+}  // namespace pk

@@ -2,10 +2,11 @@
 // arguments, --model types and options; every model type runs through the drop-in facade classes.
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K]]
-//                [--align "text" | --align-file path.txt]
+//                [--align "text" | --align-file path.txt] [--align-head ctc|tdt]
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
 // New: --align "text" / --align-file path.txt (tdt-ctc-110m, tdt-600m) aligns the given transcript with the audio (CTC forced alignment) and
-// prints its word timestamps in the format of --timestamps.
+// prints its word timestamps in the format of --timestamps.  --align-head tdt aligns through the TDT head instead (the default stays ctc): the one
+// that works for tdt-600m, which has no CTC head.
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
 #include <chrono>
 #include <cstdio>
@@ -26,6 +27,7 @@ static void usage(const char *prog) {
               << "  --ctc | --tdt | --decoder ctc|tdt  decoder (default: TDT)\n"
               << "  --beam W [--nbest N] [--prune K]  CTC prefix beam search (needs the CTC decoder), N best hypotheses\n"
               << "  --align \"text\" | --align-file path.txt  CTC forced alignment of a known transcript: its word timestamps\n"
+              << "  --align-head ctc|tdt  the head --align goes through (default: ctc; tdt needs no CTC head)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
 }
@@ -45,15 +47,16 @@ static void print_result(const TranscribeResult &r, bool timestamps, double ms) 
 
 // --align: the given transcript's word timestamps, in the format of --timestamps
 template <class T>
-static int run_align(T &t, const std::string &audio_path, const std::string &text) {
+static int run_align(T &t, const std::string &audio_path, const std::string &text, bool tdt_head) {
     const auto t0 = Clock::now();
-    const auto r = t.align(audio_path, text);
+    const auto r = tdt_head ? t.align_tdt(audio_path, text) : t.align(audio_path, text);
     const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
     if (!r.aligned) {
         std::cerr << "Error: the transcript (" << r.token_ids.size() << " tokens) cannot be aligned with this audio\n";
         return 1;
     }
-    std::cout << "Alignment: score " << std::setprecision(9) << std::defaultfloat << r.score << " log-likelihood " << r.total << "\n";
+    if (tdt_head) std::cout << "Alignment (tdt): score " << std::setprecision(9) << std::defaultfloat << r.score << "\n";
+    else std::cout << "Alignment: score " << std::setprecision(9) << std::defaultfloat << r.score << " log-likelihood " << r.total << "\n";
     print_result(r, true, ms);
     return 0;
 }
@@ -83,7 +86,7 @@ int main(int argc, char **argv) {
     try {
         const std::string weights = argv[1], audio_path = argv[2];
         std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text;
-        bool use_ctc = false, timestamps = false, align = false;
+        bool use_ctc = false, timestamps = false, align = false, align_tdt = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
         std::vector<std::string> boost;
         float boost_score = 5.0f;
@@ -105,6 +108,11 @@ int main(int argc, char **argv) {
                 align_text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
                 while (!align_text.empty() && (align_text.back() == '\n' || align_text.back() == '\r')) align_text.pop_back();
                 align = true;
+            }
+            else if (a == "--align-head" && i + 1 < argc) {
+                const std::string hd = argv[++i];
+                if (hd != "ctc" && hd != "tdt") { std::cerr << "Unknown alignment head: " << hd << "\n"; return 1; }
+                align_tdt = hd == "tdt";
             }
             else if (a == "--nbest" && i + 1 < argc) nbest = std::stoi(argv[++i]);
             else if (a == "--prune" && i + 1 < argc) prune = std::stoi(argv[++i]);
@@ -129,7 +137,7 @@ int main(int argc, char **argv) {
         if (model == "tdt-ctc-110m") {
             Transcriber t(weights, vocab);
             t.to_gpu();
-            if (align) return run_align(t, audio_path, align_text);
+            if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (!boost.empty()) std::cout << "Phrase boost: " << boost.size() << " phrases\n";
             if (beam > 0) {
                 if (!use_ctc) { std::cerr << "Error: --beam needs the CTC decoder (--ctc / --decoder ctc)\n"; return 1; }
@@ -152,7 +160,7 @@ int main(int argc, char **argv) {
         } else if (model == "tdt-600m") {
             TDTTranscriber t(weights, vocab);
             t.to_gpu();
-            if (align) return run_align(t, audio_path, align_text);
+            if (align) return run_align(t, audio_path, align_text, align_tdt);
             const auto t0 = Clock::now();
             const auto r = t.transcribe(audio_path, opts);
             print_result(r, timestamps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());

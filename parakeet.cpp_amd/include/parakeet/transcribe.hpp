@@ -186,14 +186,16 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     }
 
     // pk_align_pcm on one clip: the CTC forced alignment of `text` (tokenised by the model's vocabulary); single device
-    AlignResult run_align(const float *pcm, size_t n, const std::string &text) {
+    // tdt_head: pk_tdt_align_pcm, the TDT forced alignment (no CTC head needed; AlignResult::total stays 0: that head has no forward pass)
+    AlignResult run_align(const float *pcm, size_t n, const std::string &text, bool tdt_head = false) {
         if (!on_gpu_) to_gpu(0);
         const int64_t offsets[2] = {0, (int64_t)n};
         const char *texts[1] = {text.c_str()};
         pk_result *res = nullptr;
         float score = 0.0f, total = 0.0f;
         int32_t ok = 0;
-        check(pk_align_pcm(m_, pcm, offsets, 1, texts, nullptr, nullptr, &res, &score, &total, &ok));
+        if (tdt_head) check(pk_tdt_align_pcm(m_, pcm, offsets, 1, texts, nullptr, nullptr, &res, &score, &ok));
+        else check(pk_align_pcm(m_, pcm, offsets, 1, texts, nullptr, nullptr, &res, &score, &total, &ok));
         const pk_result &r = res[0];
         AlignResult out;
         out.score = score; out.total = total; out.aligned = ok != 0;
@@ -206,13 +208,13 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         pk_results_free(res, 1);
         return out;
     }
-    AlignResult run_align_file(const std::string &audio_path, const std::string &text) {
+    AlignResult run_align_file(const std::string &audio_path, const std::string &text, bool tdt_head = false) {
         float *pcm = nullptr;
         int64_t n = 0;
         int sr = 0;
         check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
         struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_align(pcm, (size_t)n, text);
+        return run_align(pcm, (size_t)n, text, tdt_head);
     }
 
     TranscribeResult run_file(const std::string &audio_path, const TranscribeOptions &opts) {
@@ -289,6 +291,10 @@ class Transcriber {
     AlignResult align(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text); }
     AlignResult align(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text); }
     AlignResult align(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text); }
+    /// New: the same through the TDT head (pk_tdt_align_pcm): works without a CTC head.  AlignResult::total is 0.
+    AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
+    AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
+    AlignResult align_tdt(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text, true); }
 
     pk_model *model() { return eng_.handle(); }   // the engine handle (the reference returns its ParakeetTDTCTC module tree)
 
@@ -342,6 +348,10 @@ class TDTTranscriber {
     AlignResult align(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text); }
     AlignResult align(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text); }
     AlignResult align(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text); }
+    /// New: the same through the TDT head (pk_tdt_align_pcm): works without a CTC head.  AlignResult::total is 0.
+    AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
+    AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
+    AlignResult align_tdt(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text, true); }
 
     pk_model *model() { return eng_.handle(); }
 
