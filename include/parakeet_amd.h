@@ -605,7 +605,8 @@ int pk_group_timestamps(const pk_model *m, const int32_t *ids, const int32_t *st
 
 /* ---- diagnostics used by the GPU parity tests (single kernels behind the same ABI) ------------------------ */
 /* Device math, elementwise: fn 0 exp, 1 log, 2 tanh, 3 sigmoid, 4 silu, 5 sqrt, 6 reciprocal, 7 relu, 8 / 9 sigmoid / silu as the GEMM
- * epilogues evaluate them (guarded short sequences, pk_devmath.h). */
+ * epilogues evaluate them (guarded short sequences, pk_devmath.h), 20 / 21 sigmoid / silu on the hardware exp2 and rcp (GemmArgs::fast_act: the
+ * bf16 mode's epilogues; within a derived bound of the exact value, tests/test_gpu_bf16_tile_gemm.py). */
 pk_status pk_diag_math(int fn, const float *in, float *out, int64_t n);
 /* Every one of the 2^32 bit patterns of x through a device-side identity (kernels/norm.hip, math_exhaustive_kernel): fn 3 / 4 = wherever the
  * short sigmoid / SiLU instruction sequences of the GEMM epilogues claim validity they equal the specification's value; fn 13 / 14 = the guarded
@@ -881,6 +882,47 @@ typedef struct pk_gemm_tile_diag {
 pk_status pk_diag_gemm_tile(pk_gemm_tile_diag *a);
 int pk_diag_gemm_tile_forms(int32_t *out, int cap);
 pk_status pk_diag_gemm_tile_form(int M, int N, int K, int64_t lda, int64_t ldw, int epi, int ln, int32_t *form);
+/* ONE product of the bf16 tile GEMM family alone (kernels/gemm.hip launch_gemm_bf16, gemm_bf16.hpp, gemm_bf16_glds.hpp; kernels.hpp GemmArgs):
+ * out = epi(bf16(A) bf16(W)^T + bias), fp32 accumulation, for a product launch_gemm_bf16 keeps on a tile kernel (not gemm_smallm_bf16_applies).
+ *   A [M][lda] fp32 (a_bf16 != 0: rounded to bf16 on the host, nearest even, and read as bf16; lda % 8 == 0, else % 4), W [N or 2N][ldw] (rounded to
+ *            bf16; ldw % 8 == 0), resid [M][ldr] fp32: host arrays AT THOSE PITCHES; K % 64 == 0.  On the device every element of a row past K (resid: N)
+ *            is a NaN (fp32 0x7FC5A5A5, bf16 0x7FC5).
+ *   a_blocked: A (a_bf16) is staged in the blocked hand-off layout -- block (row / 32, k / 16) holds 32 x 16 bf16 row-major, blocks ordered
+ *            [row / 32][lda / 16], rows rounded up to 32 (the rows past M are NaN); lda % 16 == 0.
+ *   fast_act, out_bf16, out_blocked, sigma_cols, remap_*: GemmArgs's.  out_bf16: out holds bf16 rows [M][ldo] (out_blocked: blocks [ceil(M / 32)][ldo / 16],
+ *            ldo % 16 == 0), two to a word.
+ *   out (out_words 32-bit words: every offset the product may write lies inside) comes back WHOLE, exactly as the launch left it; its device buffer is
+ *            filled with 0x7FC5A5A5 first.
+ * form receives the form of the launch, by the function launch_gemm_bf16 switches on (kernels.hpp gemm_bf16_form): PK_DIAG_BF16_KERNEL 0 gemm_bf16_kernel
+ * (register-staged) / 1 gemm_bf16_glds_kernel (direct-to-LDS), PK_DIAG_BF16_WGM x _WGN waves of _TM x _TN 32 x 32 accumulators, PK_DIAG_BF16_A16,
+ * PK_DIAG_BF16_EFO 0 the LDS epilogue / 1 the register epilogue on one tile per workgroup / 2 the persistent walk with the register epilogue / 3 the
+ * register residual epilogue, PK_DIAG_BF16_EPI.  pk_diag_gemm_bf16_tile_forms lists every form the launcher can take; pk_diag_gemm_bf16_tile_form
+ * answers what pk_diag_gemm_bf16_tile would launch for a filled-in struct (pointers are looked at for null only) -- both host arithmetic, no device.
+ * Refused before anything is launched, PK_ERR_UNSUPPORTED: a shape of the small-M bf16 kernel; what the launcher aborts on (out_blocked on a product the
+ * register epilogue does not take, out_blocked / a_blocked on the register-staged kernel); out_bf16 with a remap, sigma_cols, glu, resid, or ldo / N no
+ * multiple of 4 (Model::run_gemm's check); glu or resid with sigma_cols.  PK_ERR_INVALID: malformed arguments. */
+#define PK_DIAG_BF16_KERNEL(form) ((form) >> 18)
+#define PK_DIAG_BF16_WGM(form) (((form) >> 15) & 7)
+#define PK_DIAG_BF16_WGN(form) (((form) >> 12) & 7)
+#define PK_DIAG_BF16_TM(form) (((form) >> 9) & 7)
+#define PK_DIAG_BF16_TN(form) (((form) >> 6) & 7)
+#define PK_DIAG_BF16_A16(form) (((form) >> 5) & 1)
+#define PK_DIAG_BF16_EFO(form) (((form) >> 3) & 3)
+#define PK_DIAG_BF16_EPI(form) ((form) & 7)
+typedef struct pk_gemm_bf16_tile_diag {
+    int32_t M, N, K, epi, sigma_cols;
+    int32_t a_bf16, a_blocked, out_bf16, out_blocked, fast_act;
+    const float *A; int64_t lda;
+    const float *W; int64_t ldw;
+    const float *bias;
+    const float *resid; int64_t ldr; float alpha;
+    int32_t remap_rows; int64_t remap_gs, remap_rs, remap_cs;
+    int64_t ldo, out_words; uint32_t *out;
+    int32_t form;
+} pk_gemm_bf16_tile_diag;
+pk_status pk_diag_gemm_bf16_tile(pk_gemm_bf16_tile_diag *a);
+int pk_diag_gemm_bf16_tile_forms(int32_t *out, int cap);
+pk_status pk_diag_gemm_bf16_tile_form(pk_gemm_bf16_tile_diag *a);
 
 #ifdef __cplusplus
 }

@@ -352,7 +352,7 @@ def tdt_align(lattices, durations):
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
-MATH_FN = {"exp": 0, "log": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "sqrt": 5, "rcp": 6, "sigmoid4": 8, "silu4": 9}
+MATH_FN = {"exp": 0, "log": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "sqrt": 5, "rcp": 6, "sigmoid4": 8, "silu4": 9, "fast_sigmoid": 20, "fast_silu": 21}
 EPI = {"none": 0, "relu": 1, "silu": 2, "resid": 3, "glu": 4}
 
 
@@ -1229,6 +1229,99 @@ def diag_gemm_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, sigma_col
     L.pk_diag_gemm_tile.argtypes = [C.POINTER(PkGemmTileDiag)]
     check(L.pk_diag_gemm_tile(C.byref(d)))
     return dict(out=out[:d.out_words], form=tile_form(d.form))
+
+
+class PkGemmBf16TileDiag(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("M", "N", "K", "epi", "sigma_cols", "a_bf16", "a_blocked", "out_bf16", "out_blocked", "fast_act")]
+                + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),
+                   ("remap_rows", C.c_int32), ("remap_gs", C.c_int64), ("remap_rs", C.c_int64), ("remap_cs", C.c_int64),
+                   ("ldo", C.c_int64), ("out_words", C.c_int64), ("out", C.POINTER(C.c_uint32)), ("form", C.c_int32)])
+
+
+BF16_EPILOGUES = ("lds", "direct", "persist", "resid_reg")
+
+
+def bf16_form(v):
+    """A GemmBf16Form value (kernels.hpp; PK_DIAG_BF16_*) -> (kernel, (WGM, WGN, TM, TN), a16, epilogue form, epi): kernel "reg" (gemm_bf16_kernel,
+    register-staged) or "glds" (gemm_bf16_glds_kernel, direct-to-LDS); WGM x WGN waves of TM x TN 32 x 32 accumulators; epilogue form one of BF16_EPILOGUES"""
+    epi = {n: k for k, n in EPI.items()}[v & 7]
+    return ("reg", "glds")[v >> 18], ((v >> 15) & 7, (v >> 12) & 7, (v >> 9) & 7, (v >> 6) & 7), bool(v & 32), BF16_EPILOGUES[(v >> 3) & 3], epi
+
+
+def diag_gemm_bf16_tile_forms():
+    """pk_diag_gemm_bf16_tile_forms: every form launch_gemm_bf16 can take on the tile kernels, as bf16_form tuples.  Host arithmetic."""
+    n = lib().pk_diag_gemm_bf16_tile_forms(None, 0)
+    out = np.zeros(n, np.int32)
+    lib().pk_diag_gemm_bf16_tile_forms(_i(out), n)
+    return [bf16_form(int(v)) for v in out]
+
+
+def _bf16_tile_args(M, N, K, epi, a16, bias, resid, alpha, lda, ldw, ldo, ldr, sigma_cols, remap, fast_act, out_bf16, out_blocked, a_blocked, out_words):
+    d = PkGemmBf16TileDiag()
+    d.M, d.N, d.K, d.epi, d.sigma_cols = M, N, K, EPI[epi], int(sigma_cols)
+    d.a_bf16, d.a_blocked, d.out_bf16, d.out_blocked, d.fast_act = (int(bool(v)) for v in (a16, a_blocked, out_bf16, out_blocked, fast_act))
+    d.lda, d.ldw, d.ldr, d.alpha = int(lda or K), int(ldw or K), int(ldr or N), alpha
+    if remap is not None:
+        d.remap_rows, d.remap_gs, d.remap_rs, d.remap_cs = (int(v) for v in remap)
+    d.ldo = int(ldo) if ldo is not None else N
+    if out_words is None:
+        rows = (M + 31) // 32 * 32 if out_blocked else M
+        out_words = (rows * d.ldo + 1) // 2 if out_bf16 else rows * d.ldo
+    d.out_words = int(out_words)
+    d.form = -1
+    return d
+
+
+def diag_gemm_bf16_tile_form(M, N, K, epi="none", a16=False, bias=True, alpha=1.0, lda=None, ldw=None, ldo=None, ldr=None, sigma_cols=0, remap=None,
+                             fast_act=False, out_bf16=False, out_blocked=False, a_blocked=False, out_words=None):
+    """pk_diag_gemm_bf16_tile_form: the form pk_diag_gemm_bf16_tile would launch for this product.  Host arithmetic, no device; every refusal of
+    pk_diag_gemm_bf16_tile raises here too."""
+    d = _bf16_tile_args(M, N, K, epi, a16, bias, None, alpha, lda, ldw, ldo, ldr, sigma_cols, remap, fast_act, out_bf16, out_blocked, a_blocked, out_words)
+    one = np.zeros(1, np.float32)                                   # (looked at for null only)
+    d.bias = _f(one) if bias else None
+    d.resid = _f(one) if epi == "resid" else None
+    L = lib()
+    L.pk_diag_gemm_bf16_tile_form.argtypes = [C.POINTER(PkGemmBf16TileDiag)]
+    check(L.pk_diag_gemm_bf16_tile_form(C.byref(d)))
+    return bf16_form(d.form)
+
+
+def diag_gemm_bf16_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, a16=False, lda=None, ldw=None, ldo=None, ldr=None, sigma_cols=0, remap=None,
+                        fast_act=False, out_bf16=False, out_blocked=False, a_blocked=False, out_words=None):
+    """pk_diag_gemm_bf16_tile: one product of the bf16 tile GEMM family alone (include/parakeet_amd.h).  A [M][K], W [N or 2N][K], resid [M][N] dense fp32
+    (the entry rounds W, and A with a16, to bf16); lda / ldw / ldr: the pitches they are staged at (NaN behind every row on the device); a_blocked: A staged
+    in 32 x 16 blocks; remap = (rows, gs, rs, cs).  Returns dict(out = the WHOLE output buffer as uint32 words [out_words] exactly as the launch left it
+    (SKINNY_FILL32 where nothing was stored; out_bf16: two bf16 to a word), form = bf16_form tuple)."""
+    A, W = _c(A), _c(W)
+    M, K = A.shape
+    N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
+    assert W.shape[1] == K
+
+    def pitched(a, ld):
+        if ld is None or ld == a.shape[1]:
+            return a
+        p = np.zeros((a.shape[0], int(ld)), np.float32)
+        n = min(a.shape[1], int(ld))
+        p[:, :n] = a[:, :n]
+        return p
+
+    A, W = pitched(A, lda), pitched(W, ldw)
+    d = _bf16_tile_args(M, N, K, epi, a16, bias is not None, resid, alpha, A.shape[1], W.shape[1], ldo, ldr, sigma_cols, remap, fast_act, out_bf16,
+                        out_blocked, a_blocked, out_words)
+    keep = [A, W]
+    d.A, d.W = _f(A), _f(W)
+    if bias is not None:
+        keep.append(_c(bias))
+        d.bias = _f(keep[-1])
+    if resid is not None:
+        keep.append(pitched(_c(resid), ldr))
+        d.resid, d.ldr = _f(keep[-1]), keep[-1].shape[1]
+    out = np.zeros(max(d.out_words, 1), np.uint32)
+    d.out = out.ctypes.data_as(C.POINTER(C.c_uint32))
+    L = lib()
+    L.pk_diag_gemm_bf16_tile.argtypes = [C.POINTER(PkGemmBf16TileDiag)]
+    check(L.pk_diag_gemm_bf16_tile(C.byref(d)))
+    return dict(out=out[:d.out_words], form=bf16_form(d.form))
 
 
 class Batch:

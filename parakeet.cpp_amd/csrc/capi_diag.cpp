@@ -815,6 +815,108 @@ pk_status pk_diag_gemm_tile(pk_gemm_tile_diag *d) {
     });
 }
 
+// the PK_DIAG_BF16_* macros of include/parakeet_amd.h decode what gemm_bf16_form_of (kernels.hpp) encodes
+constexpr int kBf16FormProbe = gemm_bf16_form_of(BF16_GLDS, 2, 4, 3, 2, true, BF16_EPI_PERSIST, EPI_GLU);
+static_assert(PK_DIAG_BF16_KERNEL(kBf16FormProbe) == BF16_GLDS && PK_DIAG_BF16_WGM(kBf16FormProbe) == 2 && PK_DIAG_BF16_WGN(kBf16FormProbe) == 4 &&
+              PK_DIAG_BF16_TM(kBf16FormProbe) == 3 && PK_DIAG_BF16_TN(kBf16FormProbe) == 2 && PK_DIAG_BF16_A16(kBf16FormProbe) == 1 &&
+              PK_DIAG_BF16_EFO(kBf16FormProbe) == BF16_EPI_PERSIST && PK_DIAG_BF16_EPI(kBf16FormProbe) == EPI_GLU &&
+              PK_DIAG_BF16_KERNEL(gemm_bf16_form_of(BF16_REG, 4, 2, 1, 2, false, BF16_EPI_LDS, EPI_RESID)) == BF16_REG,
+              "PK_DIAG_BF16_* must decode gemm_bf16_form_of");
+
+int pk_diag_gemm_bf16_tile_forms(int32_t *out, int cap) {
+    for (int i = 0; out && i < kGemmBf16Forms.n && i < cap; ++i) out[i] = (int32_t)kGemmBf16Forms.v[i];
+    return kGemmBf16Forms.n;
+}
+
+// What both bf16 tile diagnostics check for a product before either looks for a device, and the GemmArgs (null operands replaced by a placeholder: the form
+// function and the refusals look at the pointers for null only) they hand to gemm_bf16_form.
+static GemmArgs bf16_tile_product(const pk_gemm_bf16_tile_diag *d, const char *who) {
+    static const float some[1] = {0.0f};
+    const int M = d->M, N = d->N, K = d->K, epi = d->epi;
+    need(M > 0 && N > 0 && K > 0 && K % 64 == 0, "M/N/K (K a multiple of 64)");
+    need(epi >= EPI_NONE && epi <= EPI_GLU, "epi");
+    need(d->lda >= K && d->ldw >= K && d->ldw % 8 == 0 && d->lda % (d->a_bf16 ? 8 : 4) == 0, "lda >= K, ldw >= K; ldw % 8 == 0, lda % 8 == 0 (fp32 A: % 4)");
+    need(epi != EPI_RESID || (d->resid && d->ldr >= N), "resid, ldr >= N");
+    need(d->sigma_cols >= 0 && d->sigma_cols % 16 == 0 && d->sigma_cols <= N, "sigma_cols: a multiple of 16, <= N");
+    need(!d->a_blocked || (d->a_bf16 && d->lda % 16 == 0), "a_blocked: bf16 A, lda % 16 == 0");
+    need(!d->out_blocked || (d->out_bf16 && d->ldo % 16 == 0 && d->ldo >= N), "out_blocked: bf16 rows out, ldo % 16 == 0");
+    GemmArgs g{some, d->lda, some, d->ldw, d->bias ? some : nullptr, nullptr, d->ldo, epi == EPI_RESID ? some : nullptr, d->ldr, d->alpha, M, N, K};
+    g.remap_rows = d->remap_rows; g.remap_gs = d->remap_gs; g.remap_rs = d->remap_rs; g.remap_cs = d->remap_cs;
+    g.sigma_cols = d->sigma_cols;
+    g.a_bf16 = d->a_bf16 ? 1 : 0; g.out_bf16 = d->out_bf16 ? 1 : 0; g.out_blocked = d->out_blocked ? 1 : 0; g.a_blocked = d->a_blocked ? 1 : 0;
+    g.fast_act = d->fast_act ? 1 : 0;
+    if (gemm_smallm_bf16_applies(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: M <= %d with K %% 256 == 0 runs on the small-M bf16 kernel", who, kSmallMRowsBf16);
+    if (const char *why = gemm_bf16_refusal(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: %s", who, why);
+    if (g.out_bf16 && (g.remap_rows != 0 || (g.ldo & 3) != 0 || (g.N & 3) != 0 || g.sigma_cols != 0 || epi == EPI_RESID || epi == EPI_GLU))
+        fail(PK_ERR_UNSUPPORTED, "%s: a bf16 output needs the row-major wide epilogue (no remap, no sigma_cols, no glu, no resid, ldo and N multiples of 4)", who);
+    if ((epi == EPI_GLU || epi == EPI_RESID) && g.sigma_cols != 0)
+        fail(PK_ERR_UNSUPPORTED, "%s: glu or resid with sigma_cols (the wide epilogue reads the sigma columns without the GLU mapping and adds the residual by output position)", who);
+    // every offset the product may write lies inside out (bf16 rows: two elements to a word)
+    const int64_t cap = d->out_words * (g.out_bf16 ? 2 : 1);
+    if (d->remap_rows > 0) {
+        need(d->remap_gs >= 0 && d->remap_rs >= 0 && d->remap_cs >= 0 && d->sigma_cols == 0, "remap strides (and no sigma_cols)");
+        const int64_t last = (int64_t)((M - 1) / d->remap_rows) * d->remap_gs + (int64_t)(std::min(M, d->remap_rows) - 1) * d->remap_rs + (int64_t)(N - 1) * d->remap_cs;
+        need(last < cap, "out_words: the remapped output must fit");
+    } else if (g.out_blocked) {
+        need((int64_t)((M + 31) / 32) * 32 * d->ldo <= cap, "out_words: the blocked output (rows rounded up to 32) must fit");
+    } else {
+        need(d->remap_rows == 0 && d->ldo >= N && (int64_t)(M - 1) * d->ldo + N <= cap, "ldo >= N, out_words >= (M - 1) ldo + N elements");
+    }
+    return g;
+}
+
+pk_status pk_diag_gemm_bf16_tile_form(pk_gemm_bf16_tile_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const GemmArgs g = bf16_tile_product(d, "pk_diag_gemm_bf16_tile_form");
+        d->form = (int32_t)gemm_bf16_form(g, d->epi);
+    });
+}
+
+pk_status pk_diag_gemm_bf16_tile(pk_gemm_bf16_tile_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        need(d->A && d->W && d->out, "A/W/out");
+        GemmArgs g = bf16_tile_product(d, "pk_diag_gemm_bf16_tile");
+        const int M = d->M, N = d->N, K = d->K, epi = d->epi;
+        need_device();
+        const int wrows = epi == EPI_GLU ? 2 * N : N;
+        const uint32_t nan_word = 0x7fc5a5a5u;
+        const uint16_t nan_half = 0x7fc5;
+        // a bf16 operand at its pitch: rounded on the host, every element of a row past `cols` a NaN; blocked: in 32 x 16 blocks, the rows past `rows` NaN too
+        auto up16_padded = [&](DevBuf &buf, const float *src, int64_t rows, int64_t cols, int64_t ld, bool blocked) {
+            const int64_t prow = blocked ? (rows + 31) / 32 * 32 : rows;
+            std::vector<uint16_t> h((size_t)prow * ld, nan_half);
+            for (int64_t i = 0; i < rows; ++i)
+                for (int64_t k = 0; k < cols; ++k) {
+                    const size_t at = blocked ? (size_t)((i >> 5) * (ld >> 4) + (k >> 4)) * 512 + (size_t)(i & 31) * 16 + (size_t)(k & 15) : (size_t)i * ld + k;
+                    h[at] = bf16_rne(src[(size_t)i * ld + k]);
+                }
+            up(buf, h.data(), h.size() * 2);
+        };
+        auto up_padded = [&](DevBuf &buf, const float *src, int64_t rows, int64_t cols, int64_t ld) {
+            std::vector<float> h(src, src + (size_t)rows * ld);
+            for (int64_t i = 0; i < rows; ++i)
+                for (int64_t k = cols; k < ld; ++k) memcpy(&h[(size_t)i * ld + k], &nan_word, 4);
+            up(buf, h.data(), h.size() * 4);
+        };
+        DevBuf a, w, b, r, o;
+        if (g.a_bf16) up16_padded(a, d->A, M, K, d->lda, g.a_blocked != 0);
+        else up_padded(a, d->A, M, K, d->lda);
+        up16_padded(w, d->W, wrows, K, d->ldw, false);
+        if (d->bias) up(b, d->bias, (size_t)wrows * 4);
+        if (epi == EPI_RESID) up_padded(r, d->resid, M, N, d->ldr);
+        o.reserve((size_t)d->out_words * 4);
+        PK_HIP(hipMemsetD32(o.p, nan_word, (size_t)d->out_words));
+        g.A = a.as<float>(); g.W = w.as<float>(); g.bias = d->bias ? b.as<float>() : nullptr; g.out = o.as<float>();
+        g.resid = epi == EPI_RESID ? r.as<float>() : nullptr;
+        d->form = (int32_t)launch_gemm_bf16_tile(g, epi, nullptr);      // launch_gemm_bf16's own tile branch: the form it hands back is the one it switched on
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(d->out, o, (size_t)d->out_words * 4);
+    });
+}
+
 pk_status pk_diag_ln_gemm(int M, int N, int K, const float *A, const float *pre_gamma, const float *pre_beta, const float *gamma, const float *beta, float eps,
                           const float *W, const float *bias, int epi, int fold, float *out, float *y1) {
     return guard([&] {

@@ -349,7 +349,7 @@ void launch_gemm(const GemmArgs &a, int epi, hipStream_t s) {
 // workgroup otherwise, the register residual epilogue for the residual products (round 6), and hand-counted fragment reads (ASMFRAG: bit-identical,
 // -0.7 % per tdt-600m step, profiles/r05_bf16_asmfrag_ab.txt).
 
-// the one rule both launch_bf16_epi and gemm_bf16_blocked_handoff apply: the product runs on the tile-height-per-product direct-to-LDS kernels
+// the one rule both gemm_bf16_form and gemm_bf16_blocked_handoff apply: the product runs on the tile-height-per-product direct-to-LDS kernels
 static bool bf16_glds_rule(int M, int N, int K) {
     return M >= 8192 && N >= 512 && K >= 128 && (int64_t)N * K >= (int64_t)1024 * 1024 && (N & 3) == 0;
 }
@@ -358,60 +358,97 @@ bool gemm_bf16_blocked_handoff(int M, int N, int K, int epi, bool producer) {
     if (!producer) return true;                                     // every gemm_bf16_glds_kernel form reads the blocked A
     return epi != EPI_RESID && (int64_t)(M + 31) * N < ((int64_t)1 << 31);   // the register epilogue writes it (callers set fast_act: bf16 mode)
 }
-[[noreturn]] static void bf16_layout_bug(const char *what) {
-    fprintf(stderr, "parakeet_amd: internal error: %s (GemmArgs::out_blocked / a_blocked on a kernel that does not implement it)\n", what);
-    abort();
-}
 
-template <int EPI, bool A16>
-static void launch_bf16_epi(const GemmArgs &a, hipStream_t s) {
-    if constexpr (A16) {
-        if (a.M >= 8192 && a.N >= 512 && a.K >= 128 && (a.lda % 8) == 0 && (a.ldw % 8) == 0 && a.remap_rows == 0 && (a.ldo & 3) == 0 && (a.N & 3) == 0 &&
-            (int64_t)a.N * a.K >= (int64_t)1024 * 1024) {
-            // One tile per CU and round (128 KB of LDS): the kernel's time is rounds x (tile's K loop + ~12 us of prologue / epilogue), so the tile
-            // HEIGHT is chosen per product for the fewest, fullest rounds of the 256 CUs (tools/ubench/gemm_bf16_k.cpp, profiles/r03_gemm_bf16_k.txt:
-            // main loop 1.3 PF on either tile).  tdt-600m (M = 12032): fc1 (N 4096) 752 tiles of 256 rows = 2.94 rounds; fc2 / out / pw2 (N 1024) 252
-            // tiles of 192 rows = ONE round (188 of 256 rows leave 68 CUs idle: 113 -> 99 us); qkv (N 3072) 756 of 192 = 2.95 rounds (564 of 256 = 2.2).
-            constexpr int NOUT = (EPI == EPI_GLU) ? 128 : 256;
-            auto est = [&](int R) {
-                const int64_t tiles = (int64_t)((a.M + R - 1) / R) * ((a.N + NOUT - 1) / NOUT);
-                return (double)((tiles + 255) / 256) * ((double)R * a.K * 1.008e-4 + 12.0);
-            };
-            if (est(192) < est(256)) launch_gemm_bf16_glds<2, 4, 3, 2, EPI>(a, s);
-            else launch_gemm_bf16_glds<4, 2, 2, 4, EPI>(a, s);
-            return;
-        }
+// Which instantiation a product takes (kernels.hpp: GemmBf16Form).  launch_gemm_bf16 switches on this function's result and pk_diag_gemm_bf16_tile reports
+// it: every threshold of the bf16 tile kernels lives here (the register epilogues' predicates: gl_epilogue_form) and nowhere else.
+GemmBf16Form gemm_bf16_form(const GemmArgs &a, int epi) {
+    const bool a16 = a.a_bf16 != 0;
+    if (a16 && bf16_glds_rule(a.M, a.N, a.K) && (a.lda % 8) == 0 && (a.ldw % 8) == 0 && a.remap_rows == 0 && (a.ldo & 3) == 0) {
+        // One tile per CU and round (128 KB of LDS): the kernel's time is rounds x (tile's K loop + ~12 us of prologue / epilogue), so the tile
+        // HEIGHT is chosen per product for the fewest, fullest rounds of the 256 CUs (tools/ubench/gemm_bf16_k.cpp, profiles/r03_gemm_bf16_k.txt:
+        // main loop 1.3 PF on either tile).  tdt-600m (M = 12032): fc1 (N 4096) 752 tiles of 256 rows = 2.94 rounds; fc2 / out / pw2 (N 1024) 252
+        // tiles of 192 rows = ONE round (188 of 256 rows leave 68 CUs idle: 113 -> 99 us); qkv (N 3072) 756 of 192 = 2.95 rounds (564 of 256 = 2.2).
+        const int NOUT = (epi == EPI_GLU) ? 128 : 256;
+        auto est = [&](int R) {
+            const int64_t tiles = (int64_t)((a.M + R - 1) / R) * ((a.N + NOUT - 1) / NOUT);
+            return (double)((tiles + 255) / 256) * ((double)R * a.K * 1.008e-4 + 12.0);
+        };
+        if (est(192) < est(256)) return gemm_bf16_form_of(BF16_GLDS, 2, 4, 3, 2, true, gl_epilogue_form(a, epi, 192), epi);
+        return gemm_bf16_form_of(BF16_GLDS, 4, 2, 2, 4, true, gl_epilogue_form(a, epi, 256), epi);
     }
-    if (a.out_blocked || a.a_blocked) bf16_layout_bug("blocked activation layout requested for the register-staged bf16 kernel");
     // round 2: the staging stores decide the rate of this kernel.  As 16-byte ds_write_b128 the 128x128 tile ran at 320-340 TF and 256x256
     // macro tiles were the way to 450 (profiles/r02_gemm_bf16_tiles.txt); the SAME 16 bytes written as a ds_write2_b64 pair
     // (gemm_bf16.hpp, lstore) take the 128x128 tile to 580 TF in the sweep and 510-600 TF in the engine (profiles/r02_gemm_bf16_ablation.txt)
     // -- the 16-byte LDS store is pathologically slow next to fragment reads on gfx950, as the fp32 kernel had already shown.
-    if constexpr (EPI == EPI_GLU) {
-        launch_gemm_bf16_t<4, 2, 1, 2, EPI_GLU, A16>(a, s);
-    } else {
-        if (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))) launch_gemm_bf16_t<4, 2, 1, 2, EPI, A16>(a, s);      // 128x128 on 8 waves of 32x64 (also the 1.4 M-row subsampling products)
-        else if (a.M >= 1024 && a.N >= 256) launch_gemm_bf16_t<2, 2, 2, 1, EPI, A16>(a, s);
-        else launch_gemm_bf16_t<2, 2, 1, 1, EPI, A16>(a, s);
-    }
+    if (epi == EPI_GLU || (a.M >= 1024 && (a.N >= 1024 || (a.M >= 65536 && a.N >= 256))))
+        return gemm_bf16_form_of(BF16_REG, 4, 2, 1, 2, a16, BF16_EPI_LDS, epi);      // 128x128 on 8 waves of 32x64 (also the 1.4 M-row subsampling products)
+    if (a.M >= 1024 && a.N >= 256) return gemm_bf16_form_of(BF16_REG, 2, 2, 2, 1, a16, BF16_EPI_LDS, epi);
+    return gemm_bf16_form_of(BF16_REG, 2, 2, 1, 1, a16, BF16_EPI_LDS, epi);
 }
-template <bool A16>
-static void launch_gemm_bf16_a(const GemmArgs &a, int epi, hipStream_t s) {
-    switch (epi) {
-    case EPI_NONE: launch_bf16_epi<EPI_NONE, A16>(a, s); break;
-    case EPI_RELU: launch_bf16_epi<EPI_RELU, A16>(a, s); break;
-    case EPI_SILU: launch_bf16_epi<EPI_SILU, A16>(a, s); break;
-    case EPI_RESID: launch_bf16_epi<EPI_RESID, A16>(a, s); break;
-    case EPI_GLU: launch_bf16_epi<EPI_GLU, A16>(a, s); break;
+static const char *bf16_form_refusal(const GemmArgs &a, GemmBf16Form f) {
+    if ((f >> 18) == BF16_REG)
+        return (a.out_blocked || a.a_blocked) ? "blocked activation layout requested for the register-staged bf16 kernel (GemmArgs::out_blocked / a_blocked on a kernel that does not implement it)" : nullptr;
+    const int efo = (f >> 3) & 3;                                  // (only gl_epilogue_direct writes the blocked layout)
+    return (a.out_blocked && efo != BF16_EPI_DIRECT && efo != BF16_EPI_PERSIST) ? "blocked output on the LDS epilogue" : nullptr;
+}
+const char *gemm_bf16_refusal(const GemmArgs &a, int epi) { return bf16_form_refusal(a, gemm_bf16_form(a, epi)); }
+[[noreturn]] static void bf16_no_form(int form, int epi) {
+    fprintf(stderr, "parakeet_amd: internal error: launch_gemm_bf16 has no tile kernel for form %d with epilogue %d\n", form, epi);
+    abort();
+}
+// One case per kernel, geometry and A type; the `if constexpr` beside it names the epilogue functions that geometry is instantiated for (kGemmBf16Forms).
+template <int EPI>
+static void launch_bf16_tile(const GemmArgs &a, GemmBf16Form f, hipStream_t s) {
+    if (gemm_bf16_form_epi(f) != EPI) bf16_no_form(f, EPI);
+    const int efo = (f >> 3) & 3;
+    switch (gemm_bf16_form_shape(f) & ~(3 << 3)) {
+    case gemm_bf16_form_of(BF16_GLDS, 2, 4, 3, 2, true, 0, 0):
+        if (launch_gemm_bf16_glds<2, 4, 3, 2, EPI>(a, efo, s)) return;
+        break;
+    case gemm_bf16_form_of(BF16_GLDS, 4, 2, 2, 4, true, 0, 0):
+        if (launch_gemm_bf16_glds<4, 2, 2, 4, EPI>(a, efo, s)) return;
+        break;
+    case gemm_bf16_form_of(BF16_REG, 4, 2, 1, 2, false, 0, 0):
+        if (efo == BF16_EPI_LDS) { launch_gemm_bf16_t<4, 2, 1, 2, EPI, false>(a, s); return; }
+        break;
+    case gemm_bf16_form_of(BF16_REG, 4, 2, 1, 2, true, 0, 0):
+        if (efo == BF16_EPI_LDS) { launch_gemm_bf16_t<4, 2, 1, 2, EPI, true>(a, s); return; }
+        break;
+    case gemm_bf16_form_of(BF16_REG, 2, 2, 2, 1, false, 0, 0):
+        if constexpr (EPI != EPI_GLU) { if (efo == BF16_EPI_LDS) { launch_gemm_bf16_t<2, 2, 2, 1, EPI, false>(a, s); return; } }
+        break;
+    case gemm_bf16_form_of(BF16_REG, 2, 2, 2, 1, true, 0, 0):
+        if constexpr (EPI != EPI_GLU) { if (efo == BF16_EPI_LDS) { launch_gemm_bf16_t<2, 2, 2, 1, EPI, true>(a, s); return; } }
+        break;
+    case gemm_bf16_form_of(BF16_REG, 2, 2, 1, 1, false, 0, 0):
+        if constexpr (EPI != EPI_GLU) { if (efo == BF16_EPI_LDS) { launch_gemm_bf16_t<2, 2, 1, 1, EPI, false>(a, s); return; } }
+        break;
+    case gemm_bf16_form_of(BF16_REG, 2, 2, 1, 1, true, 0, 0):
+        if constexpr (EPI != EPI_GLU) { if (efo == BF16_EPI_LDS) { launch_gemm_bf16_t<2, 2, 1, 1, EPI, true>(a, s); return; } }
+        break;
     default: break;
     }
+    bf16_no_form(f, EPI);
+}
+// A product on the bf16 tile kernels.  Returns the form it launched: the one value both the dispatch above and pk_diag_gemm_bf16_tile's report come from.
+GemmBf16Form launch_gemm_bf16_tile(const GemmArgs &a, int epi, hipStream_t s) {
+    const GemmBf16Form f = gemm_bf16_form(a, epi);
+    if (const char *why = bf16_form_refusal(a, f)) { fprintf(stderr, "parakeet_amd: internal error: %s\n", why); abort(); }
+    switch (epi) {
+    case EPI_NONE: launch_bf16_tile<EPI_NONE>(a, f, s); break;
+    case EPI_RELU: launch_bf16_tile<EPI_RELU>(a, f, s); break;
+    case EPI_SILU: launch_bf16_tile<EPI_SILU>(a, f, s); break;
+    case EPI_RESID: launch_bf16_tile<EPI_RESID>(a, f, s); break;
+    case EPI_GLU: launch_bf16_tile<EPI_GLU>(a, f, s); break;
+    default: break;
+    }
+    return f;
 }
 void launch_gemm_bf16(const GemmArgs &a, int epi, hipStream_t s) {
     // (a bf16 output goes through the wide epilogue only -- row-major, 4-column groups: Model::run_gemm checks)
     // a handful of rows (the streaming encoder's chunks): the weight-stream kernel of gemm_smallm_bf16.hip
     if (gemm_smallm_bf16_applies(a, epi)) { launch_gemm_smallm_bf16(a, epi, s); return; }
-    if (a.a_bf16) launch_gemm_bf16_a<true>(a, epi, s);
-    else launch_gemm_bf16_a<false>(a, epi, s);
+    launch_gemm_bf16_tile(a, epi, s);
 }
 
 double gemm_flops(const GemmArgs &a, int epi) {

@@ -493,30 +493,46 @@ static void launch_gl_kernel(const GemmArgs &a, hipStream_t s, int grid, int til
     ensure_dyn_lds(slots, reinterpret_cast<const void *>(kern), lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WGM * WGN), lds, s, a, tiles_n, n_tiles);
 }
+// The epilogue form of a product on this kernel with BM-row tiles (gemm.hip: gemm_bf16_form calls it once the tile height is chosen): every predicate of
+// the register epilogues lives here and nowhere else.
+inline int gl_epilogue_form(const GemmArgs &a, int epi, int BM) {
+    const int NOUT = epi == EPI_GLU ? 128 : 256;
+    const int64_t n_tiles = (int64_t)((a.M + BM - 1) / BM) * ((a.N + NOUT - 1) / NOUT);
+    if (epi != EPI_RESID) {
+        const bool direct_ok = a.sigma_cols == 0 && a.remap_rows == 0 && (a.N % 16) == 0 && (a.ldo % 8) == 0 &&
+                               (a.fast_act || (epi != EPI_SILU && epi != EPI_GLU)) && ((int64_t)(a.M + 31) * a.ldo < ((int64_t)1 << 31));
+        if (direct_ok) return n_tiles > 256 ? BF16_EPI_PERSIST : BF16_EPI_DIRECT;
+        return BF16_EPI_LDS;
+    }
+    // the register residual epilogue (gl_resid_init / gl_epilogue_resid_direct): row-major fp32 in and out, whole 16-column groups, 32-bit offsets
+    const bool rd_ok = a.resid && a.alpha != 0.0f && !a.out_bf16 && a.sigma_cols == 0 && a.remap_rows == 0 &&
+                       (a.N % 16) == 0 && (a.ldo % 4) == 0 && (a.ldr % 4) == 0 && ((int64_t)(a.M + 31) * a.ldo < ((int64_t)1 << 31)) &&
+                       ((int64_t)(a.M + 31) * a.ldr < ((int64_t)1 << 31));
+    return rd_ok ? BF16_EPI_RESID_REG : BF16_EPI_LDS;
+}
+// One case per epilogue form; the `if constexpr` beside it names the epilogue functions that form is instantiated for (kGemmBf16Forms).  false: no such kernel.
 template <int WGM, int WGN, int TM, int TN, int EPI>
-static void launch_gemm_bf16_glds(const GemmArgs &a, hipStream_t s) {
+static bool launch_gemm_bf16_glds(const GemmArgs &a, int efo, hipStream_t s) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
     constexpr int NOUT = (EPI == EPI_GLU) ? BN / 2 : BN;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + NOUT - 1) / NOUT;
     const int n_tiles = tiles_m * tiles_n;
-    if constexpr (EPI != EPI_RESID) {
-        const bool direct_ok = a.sigma_cols == 0 && a.remap_rows == 0 && (a.N % 16) == 0 && (a.ldo % 8) == 0 &&
-                               (a.fast_act || (EPI != EPI_SILU && EPI != EPI_GLU)) && ((int64_t)(a.M + 31) * a.ldo < ((int64_t)1 << 31));
-        if (direct_ok) {
-            if (n_tiles > 256) launch_gl_kernel<WGM, WGN, TM, TN, EPI, true, true, true>(a, s, 256, tiles_n, n_tiles);
-            else launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, true, false>(a, s, n_tiles, tiles_n, n_tiles);
-            return;
-        }
+    switch (efo) {
+    case BF16_EPI_PERSIST:
+        if constexpr (EPI != EPI_RESID) { launch_gl_kernel<WGM, WGN, TM, TN, EPI, true, true, true>(a, s, 256, tiles_n, n_tiles); return true; }
+        break;
+    case BF16_EPI_DIRECT:
+        if constexpr (EPI != EPI_RESID) { launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, true, false>(a, s, n_tiles, tiles_n, n_tiles); return true; }
+        break;
+    case BF16_EPI_RESID_REG:
+        if constexpr (EPI == EPI_RESID) { launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, true, true>(a, s, n_tiles, tiles_n, n_tiles); return true; }
+        break;
+    case BF16_EPI_LDS:
+        launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, false, true>(a, s, n_tiles, tiles_n, n_tiles);
+        return true;
+    default: break;
     }
-    if (a.out_blocked) { fprintf(stderr, "parakeet_amd: internal error: blocked output on the LDS epilogue\n"); abort(); }
-    if constexpr (EPI == EPI_RESID) {
-        // the register residual epilogue (gl_resid_init / gl_epilogue_resid_direct): row-major fp32 in and out, whole 16-column groups, 32-bit offsets
-        const bool rd_ok = a.resid && a.alpha != 0.0f && !a.out_bf16 && a.sigma_cols == 0 && a.remap_rows == 0 &&
-                           (a.N % 16) == 0 && (a.ldo % 4) == 0 && (a.ldr % 4) == 0 && ((int64_t)(a.M + 31) * a.ldo < ((int64_t)1 << 31)) &&
-                           ((int64_t)(a.M + 31) * a.ldr < ((int64_t)1 << 31));
-        if (rd_ok) { launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, true, true>(a, s, n_tiles, tiles_n, n_tiles); return; }
-    }
-    launch_gl_kernel<WGM, WGN, TM, TN, EPI, false, false, true>(a, s, n_tiles, tiles_n, n_tiles);
+    return false;
 }
 
 }  // namespace pk

@@ -255,6 +255,49 @@ static_assert(kGemmTileForms.n == kGemmTileFormCount, "kGemmTileForms must list 
 // same contract with bf16 operands and fp32 accumulation: a.W points to bf16 weights [N][K] (rounded once at upload), A is
 // rounded to bf16 while it is staged; K % 64 == 0.  Not bit-identical to the fp32 chain (kernels/gemm_bf16.hpp).
 void launch_gemm_bf16(const GemmArgs &a, int epi, hipStream_t s);
+// The form of a bf16 tile launch (kernels/gemm.hip, gemm_bf16.hpp, gemm_bf16_glds.hpp), by the function launch_gemm_bf16 switches on for every product it
+// does not send to the small-M bf16 kernel: value = gemm_bf16_form_of(...).
+//   kernel: gemm_bf16_kernel (register-staged) or gemm_bf16_glds_kernel (direct-to-LDS; A already bf16)
+//   wgm x wgn waves of tm x tn 32 x 32 accumulators: the tile is (32 wgm tm) x (32 wgn tn)
+//   a16:    A read as bf16 (GemmArgs::a_bf16); fp32 rows are rounded while they are staged (register-staged kernel only)
+//   efo:    the epilogue form -- through LDS (gp_epilogue: wide or scalar), the register epilogue on one tile per workgroup, the persistent walk with the
+//           register epilogue, the register residual epilogue.  The register-staged kernel has the LDS one only.
+//   epi:    the epilogue function the kernel is instantiated for (GemmEpi)
+enum GemmBf16Kernel { BF16_REG = 0, BF16_GLDS = 1 };
+enum GemmBf16Epilogue { BF16_EPI_LDS = 0, BF16_EPI_DIRECT = 1, BF16_EPI_PERSIST = 2, BF16_EPI_RESID_REG = 3 };
+enum GemmBf16Form : int {};
+constexpr GemmBf16Form gemm_bf16_form_of(int kernel, int wgm, int wgn, int tm, int tn, bool a16, int efo, int epi) {
+    return (GemmBf16Form)((kernel << 18) | (wgm << 15) | (wgn << 12) | (tm << 9) | (tn << 6) | ((a16 ? 1 : 0) << 5) | (efo << 3) | epi);
+}
+constexpr int gemm_bf16_form_epi(int f) { return f & 7; }
+constexpr int gemm_bf16_form_shape(int f) { return f & ~7; }       // everything but the epilogue function: what the launcher's switch has one case for
+GemmBf16Form gemm_bf16_form(const GemmArgs &a, int epi);          // of a product launch_gemm_bf16 keeps (gemm_smallm_bf16_applies goes first)
+// What the kernel a product is sent to does not implement (nullptr: nothing): the blocked activation layout (GemmArgs::out_blocked / a_blocked) on the
+// register-staged kernel, a blocked output on the LDS epilogue of the direct-to-LDS kernel.  launch_gemm_bf16 aborts on these.
+const char *gemm_bf16_refusal(const GemmArgs &a, int epi);
+// launch_gemm_bf16 behind the small-M branch: aborts on gemm_bf16_refusal, launches, and returns the form it switched on
+GemmBf16Form launch_gemm_bf16_tile(const GemmArgs &a, int epi, hipStream_t s);
+// Every form launch_gemm_bf16_tile can take = every instantiation of the two kernels: register-staged 128 x 128 (4 x 2 waves of 1 x 2) with every epilogue
+// function, 128 x 64 (2 x 2 of 2 x 1) and 64 x 64 (2 x 2 of 1 x 1) without GLU, each with fp32 or bf16 A; direct-to-LDS 192 x 256 (2 x 4 of 3 x 2) and 256 x 256
+// (4 x 2 of 2 x 4): none / relu / silu / glu on the LDS, the one-tile register and the persistent register epilogue, resid on the LDS and the register residual one.
+constexpr int kGemmBf16FormCount = 2 * (5 + 4 + 4) + 2 * (4 * 3 + 2);
+struct GemmBf16Forms { GemmBf16Form v[kGemmBf16FormCount]; int n; };
+constexpr GemmBf16Forms gemm_bf16_forms() {
+    GemmBf16Forms t{};
+    for (int a16 = 0; a16 < 2; ++a16) {
+        for (int epi = EPI_NONE; epi <= EPI_GLU; ++epi) t.v[t.n++] = gemm_bf16_form_of(BF16_REG, 4, 2, 1, 2, a16 != 0, BF16_EPI_LDS, epi);
+        for (int epi = EPI_NONE; epi <= EPI_RESID; ++epi) t.v[t.n++] = gemm_bf16_form_of(BF16_REG, 2, 2, 2, 1, a16 != 0, BF16_EPI_LDS, epi);
+        for (int epi = EPI_NONE; epi <= EPI_RESID; ++epi) t.v[t.n++] = gemm_bf16_form_of(BF16_REG, 2, 2, 1, 1, a16 != 0, BF16_EPI_LDS, epi);
+    }
+    for (int tall = 0; tall < 2; ++tall)
+        for (int epi = EPI_NONE; epi <= EPI_GLU; ++epi)
+            for (int efo = BF16_EPI_LDS; efo <= BF16_EPI_RESID_REG; ++efo)
+                if (epi == EPI_RESID ? (efo == BF16_EPI_LDS || efo == BF16_EPI_RESID_REG) : efo != BF16_EPI_RESID_REG)
+                    t.v[t.n++] = tall ? gemm_bf16_form_of(BF16_GLDS, 4, 2, 2, 4, true, efo, epi) : gemm_bf16_form_of(BF16_GLDS, 2, 4, 3, 2, true, efo, epi);
+    return t;
+}
+constexpr GemmBf16Forms kGemmBf16Forms = gemm_bf16_forms();
+static_assert(kGemmBf16Forms.n == kGemmBf16FormCount, "kGemmBf16Forms must list every instantiation");
 // the same for a handful of rows (streaming chunks in the tolerance-class mode): kernels/gemm_smallm_bf16.hip -- one workgroup per 16 output
 // columns, K split over its waves, every weight byte requested up front.  launch_gemm_bf16 routes the shapes gemm_smallm_bf16_applies() accepts
 // (M <= kSmallMRowsBf16, K % 256 == 0, row-major output) there.
@@ -568,7 +611,7 @@ void launch_layernorm_stats(const float *x, int64_t rows, int d, float eps, floa
 // y1 = LN(x; g1, b1) written out (may alias x) + the statistics of y1's rows (what launch_layernorm2's second pass would start from)
 void launch_layernorm_then_stats(const float *x, int64_t rows, int d, const float *g1, const float *b1, float eps, float *y1, float *stats, hipStream_t s);
 void launch_sum64_rows(const float *x, int rows, int n, float *out, hipStream_t s);
-void launch_math(int fn, const float *in, float *out, int64_t n, hipStream_t s);   // 0 exp 1 log 2 tanh 3 sigmoid 4 silu 5 sqrt 6 recip 7 relu
+void launch_math(int fn, const float *in, float *out, int64_t n, hipStream_t s);   // 0 exp 1 log 2 tanh 3 sigmoid 4 silu 5 sqrt 6 recip 7 relu 8 sigmoid4 9 silu4 20 fast_sigmoid 21 fast_silu
 void launch_math_exhaustive(int fn, unsigned long long *out3, hipStream_t s);   // out3 must hold {0, 0, 1 << 32} on entry
 void launch_scale(float *x, int64_t n, float a, hipStream_t s);
 

@@ -238,6 +238,8 @@ __global__ void math_kernel(int fn, const float *__restrict__ in, float *__restr
         case 7: y = x > 0.0f ? x : 0.0f; break;
         case 8: { float v[4] = {x, x, x, x}; dsigmoid4(v); y = v[0]; break; }   // the GEMM epilogues' guarded four-at-a-time forms
         case 9: { float v[4] = {x, x, x, x}; dsilu4(v); y = v[0]; break; }
+        case 20: y = fast_sigmoidf(x); break;                                   // GemmArgs::fast_act: the hardware exp2 / rcp forms of the bf16 mode's epilogues
+        case 21: y = fast_siluf(x); break;
         default: y = x;
         }
         out[i] = y;

@@ -186,6 +186,45 @@ def test_tile_gemm_form_table_queries_and_argument_checks_need_no_device():
         assert e.value.code == -1, bad
 
 
+def test_bf16_tile_gemm_form_table_queries_and_refusals_need_no_device():
+    """pk_diag_gemm_bf16_tile_forms (what tests/test_gpu_bf16_tile_gemm.py::test_every_form_has_a_case compares its cases with) and
+    pk_diag_gemm_bf16_tile_form are host arithmetic: one form per instantiation launch_gemm_bf16 can take, the production products of tdt-600m on the forms
+    gemm.hip's comments name; and both entries refuse what the launcher aborts on, and what Model::run_gemm refuses, before they look for a device."""
+    R64, R128X64, R128, G192, G256 = (2, 2, 1, 1), (2, 2, 2, 1), (4, 2, 1, 2), (2, 4, 3, 2), (4, 2, 2, 4)
+    four = ("none", "relu", "silu", "resid")
+    want = {("reg", t, a, "lds", e) for t in (R64, R128X64, R128) for a in (False, True) for e in four} | {("reg", R128, a, "lds", "glu") for a in (False, True)}
+    want |= {("glds", g, True, f, e) for g in (G192, G256) for f in ("lds", "direct", "persist") for e in ("none", "relu", "silu", "glu")}
+    want |= {("glds", g, True, f, "resid") for g in (G192, G256) for f in ("lds", "resid_reg")}
+    every = capi.diag_gemm_bf16_tile_forms()
+    assert len(every) == 54 and set(every) == want
+    q = capi.diag_gemm_bf16_tile_form
+    M = 12032                                                        # tdt-600m, 32 clips of 30 s
+    assert q(M, 4096, 1024, epi="silu", a16=True, fast_act=True, out_bf16=True, out_blocked=True) == ("glds", G256, True, "persist", "silu")   # fc1
+    assert q(M, 1024, 4096, epi="resid", a16=True, alpha=0.5, a_blocked=True, lda=4096) == ("glds", G192, True, "resid_reg", "resid")        # fc2: one round
+    assert q(M, 3072, 1024, a16=True) == ("glds", G192, True, "persist", "none")                                                            # qkv
+    assert q(M, 4096, 1024, epi="silu", a16=True) == ("glds", G256, True, "lds", "silu")              # polynomial activations: the LDS epilogue
+    assert q(M, 1024, 1024, epi="resid", a16=True, ldr=1025) == ("glds", G192, True, "lds", "resid")
+    assert q(M, 1024, 1024, epi="silu") == ("reg", R128, False, "lds", "silu")                        # fp32 rows of A: the register-staged kernel
+    assert q(2000, 512, 512, a16=True) == ("reg", R128X64, True, "lds", "none") and q(2000, 128, 512) == ("reg", R64, False, "lds", "none")
+    for bad in (dict(M=M, N=4096, K=1024, epi="silu", a16=True, out_bf16=True, out_blocked=True),    # blocked rows need the register epilogue (fast_act)
+                dict(M=2000, N=512, K=512, a16=True, out_bf16=True, out_blocked=True), dict(M=2000, N=512, K=512, a16=True, a_blocked=True),
+                dict(M=M, N=1024, K=1024, epi="glu", a16=True, fast_act=True, out_bf16=True), dict(M=M, N=1024, K=1024, epi="resid", a16=True, out_bf16=True),
+                dict(M=M, N=1024, K=1024, a16=True, out_bf16=True, sigma_cols=16), dict(M=2000, N=510, K=512, out_bf16=True, ldo=510),
+                dict(M=2000, N=512, K=512, epi="glu", sigma_cols=16), dict(M=2000, N=512, K=512, epi="resid", sigma_cols=16), dict(M=128, N=512, K=512)):
+        with pytest.raises(capi.PkError) as e:
+            q(**bad)
+        assert e.value.code == -7, bad
+    for bad in (dict(M=2000, N=512, K=96), dict(M=2000, N=512, K=512, a16=True, lda=516), dict(M=2000, N=512, K=512, ldw=516), dict(M=2000, N=512, K=512, sigma_cols=8),
+                dict(M=2000, N=512, K=512, ldo=500), dict(M=2000, N=512, K=512, out_words=100), dict(M=M, N=1024, K=1024, a_blocked=True),
+                dict(M=M + 8, N=1024, K=1024, a16=True, fast_act=True, epi="silu", out_bf16=True, out_blocked=True, out_words=(M + 8) * 512)):   # rows rounded up to 32
+        with pytest.raises(capi.PkError) as e:
+            q(**bad)
+        assert e.value.code == -1, bad
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_gemm_bf16_tile(np.zeros((2000, 512), np.float32), np.zeros((512, 512), np.float32), a16=True, a_blocked=True)
+    assert e.value.code == -7
+
+
 def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
     """pk_diag_conv_variants / pk_diag_conv_instantiations (what tests/test_gpu_conv_variants.py asks before it compares bits) need no device:
     every reported variant is a row of the list, a ragged batch of equal lengths is the uniform batch, and T describes pk_conformer_blocks' input."""
