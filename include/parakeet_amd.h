@@ -397,7 +397,8 @@ pk_status pk_align_pcm(pk_model *m, const float *pcm, const int64_t *offsets, in
  * greedy loop (src/tdt.cpp:62-106): blank with duration i to (t + max(dur[i], 1), u), label ids[u] with duration i to (t + dur[i], u + 1), an
  * arc past the last frame ends the utterance when all U tokens are out.  The alignment is the max-plus path, specified operation by operation in
  * DESIGN.md section 5.5.2 (tests/tdt_align_ref.py is that specification; the device result equals it bit for bit).  max_symbols_per_step is
- * not part of the lattice (as in pk_tdt_score).  No forward-algorithm total.  All of it runs on the device (kernels/tdt_align.hip).
+ * not part of the lattice (as in pk_tdt_score).  The forward-algorithm total of the same lattice: pk_tdt_total* below.  All of it runs on the device
+ * (kernels/tdt_align.hip).
  *
  * pk_tdt_align: the walk alone on a HOST lattice.  Needs a device, no model.  Utterance b has n_frames[b] >= 1 frames and the tokens
  * id_offsets[b] .. id_offsets[b+1] (id_offsets[0] = 0; U = 0 is valid); its values are packed utterance after utterance:
@@ -438,8 +439,67 @@ pk_status pk_tdt_align_pcm(pk_model *m, const float *pcm, const int64_t *offsets
 #define PK_DIAG_TDT_LATTICE_GUARD 64
 pk_status pk_diag_tdt_lattice(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
                               int chunk_rows, float *lab, float *blk, float *dl);
+/* ---- TDT log-likelihood of a GIVEN transcript, and CTC n-best rescored with it ------------------------------------------------
+ * How probable is this token string under the TDT head: the forward algorithm on the lattice of pk_tdt_align (same cells, same arcs; a blank of
+ * duration 0 and a blank of duration 1 are two arcs to the next frame and both are summed), specified operation by operation in DESIGN.md
+ * section 5.5.3 (tests/tdt_total_ref.py is that specification; the device result equals it bit for bit).  No length normalisation, no language
+ * model, no bf16 form, no RNN-T head; pk_group and streaming sessions have no variant.  All of it runs on the device (kernels/tdt_total.hip).
+ *
+ * pk_tdt_total: the walk alone on a HOST lattice, packed as for pk_tdt_align.  Needs a device, no model.  total[B] = the log-sum over every path
+ * to the end (>= the alignment's score), ok[B] = 1, or 0 where no path reaches the end (total = -inf).  Refusals as pk_tdt_align; the scratch
+ * formula is the alignment's without its back-pointer bytes: 4 (labs + cells (1 + D)) <= 1 GiB. */
+pk_status pk_tdt_total(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int B,
+                       const int32_t *id_offsets, float *total, int32_t *ok);
+/* Prediction net over every prefix + enc_proj + lattice + walk on the model's stream, for n_hyp token strings over n_clips clips:
+ * hypothesis h reads the frames of clip clip_of[h], so several transcripts of one clip share its rows and enc_proj runs once per clip.
+ * enc [n_clips][T][hidden] resp. packed with n_frames[n_clips]; ids packed with id_offsets[n_hyp + 1]; total / ok [n_hyp].
+ * clip_of == NULL: hypothesis h on clip h, and n_hyp must equal n_clips.
+ * The hypotheses are walked in groups of consecutive ones: at most 256, and as many as keep the group's scratch (the formula above plus the rows
+ * chunk and the prediction net's outputs, as pk_tdt_align_decode counts them) under 1 GiB.  Grouping changes no bit of any result.
+ * PK_ERR_INVALID: a clip_of entry outside [0, n_clips), n_hyp != n_clips without clip_of, an id outside [0, V) or equal to blank, decreasing
+ * offsets.  PK_ERR_UNSUPPORTED exactly where pk_tdt_align_decode refuses: no TDT joint, gemm_bf16, D / durations / 1535 tokens, or one
+ * hypothesis whose own scratch exceeds the cap.  A boost trie set on the model does not matter. */
+pk_status pk_tdt_total_decode(pk_model *m, const float *enc, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets,
+                              const int32_t *clip_of_or_null, int n_hyp, float *total, int32_t *ok);
+pk_status pk_tdt_total_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int n_clips, const int32_t *ids,
+                                     const int32_t *id_offsets, const int32_t *clip_of_or_null, int n_hyp, float *total, int32_t *ok);
+/* Stage timers (tools/bench_tdt_rescore.py), between hipEvents on the model's stream, summed over the groups of the call, medians of `reps`
+ * passes after one warm-up: ms[0] = prediction net (with the host-to-device copies of every group's token strings and tables, as the
+ * alignment's timer counts them; U_max + 1 lock-step steps per group), ms[1] = lattice (activation + heads product + reduction, all chunks), ms[2] = the forward
+ * pass.  n_frames NULL: uniform [n_clips][T]. */
+pk_status pk_tdt_total_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int n_clips, int T, const int32_t *ids,
+                                    const int32_t *id_offsets, const int32_t *clip_of_or_null, int n_hyp, int reps, float ms[3]);
+/* One call from PCM and one or more transcripts per clip to log-likelihoods: clips packed and encoded as pk_tdt_align_pcm does it (the
+ * attention context set on the model applies); texts[n_hyp] UTF-8, or ids packed with id_offsets[n_hyp + 1]; clip_of as above (a clip without a
+ * transcript is allowed); total / ok [n_hyp]. */
+pk_status pk_tdt_score_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts_or_null,
+                           const int32_t *ids_or_null, const int32_t *id_offsets, const int32_t *clip_of_or_null, int n_hyp, float *total,
+                           int32_t *ok);
+/* The reference's roadmap line "N-best reranking" (README.md:514) with the model's own stronger head as the second opinion:
+ * pk_transcribe_pcm_nbest, then every returned hypothesis scored under the TDT head (an empty hypothesis is U = 0, which is valid), then each
+ * clip's list re-ordered by combined = fl(fl((1 - w) ctc) + fl(w tdt)), w = tdt_weight, all in fp32: stable, descending, ties keep the beam's
+ * order; a hypothesis the TDT head cannot score (ok = 0) sorts after every scored one and carries combined = -inf.  score[j] of the pk_nbest is
+ * combined; ctc_score / tdt_total (optional, [n_clips][N], N = n_best) carry the parts in the returned order, -inf in the slots past n_hyp.
+ * rescore_opt == NULL: tdt_weight 0.5.  tdt_weight 0 returns the beam's own list.
+ * PK_ERR_UNSUPPORTED for a model without both heads (or whose heads do not share a vocabulary), and wherever the two stages refuse.  The model
+ * refusals come before any work.  The limits of the total (a hypothesis over 1535 tokens, one whose own scratch exceeds 1 GiB) depend on what
+ * the search returns, so they are checked LATE: after a batch has been encoded and searched, and after earlier batches of the call were fully
+ * processed.  The call then fails as a whole and returns no list; only clips of more than 1535 encoder frames (about two minutes) can reach
+ * them.  pk_tdt_score_pcm and pk_tdt_align_pcm, whose strings are given, refuse before encoding. */
+typedef struct pk_rescore_options {
+    float tdt_weight;           /* w: weight of the TDT log-likelihood, 1 - w that of the CTC score; finite */
+} pk_rescore_options;
+pk_status pk_transcribe_pcm_nbest_rescored(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *beam_opt,
+                                           const pk_rescore_options *rescore_opt, pk_nbest **results, float *ctc_score, float *tdt_total);
+/* Diagnostics, host arithmetic (no device, no model): the groups pk_tdt_total_decode would walk n_hyp hypotheses of n_frames_of_hyp[h] frames in
+ * (group_of[n_hyp]; V / J the vocabulary and joint width, max_hyps <= 0: the engine's 256), and the ordering rule above on the N slots of one
+ * clip in beam order (order[j] = the slot at position j, combined[] by slot). */
+pk_status pk_diag_tdt_total_groups(const int32_t *n_frames_of_hyp, const int32_t *id_offsets, int n_hyp, const int32_t *durations, int D, int V, int J,
+                                   int max_hyps, int32_t *group_of, int *n_groups);
+pk_status pk_diag_rescore_order(const int32_t *lens, const float *ctc_score, const float *tdt_total, const int32_t *ok, int N, float tdt_weight,
+                                int32_t *order, float *combined);
 /* Diagnostic: out[0] / out[1] = free / total bytes of the current device (hipMemGetInfo), out[2] = the bytes of device memory the grow-only
- * buffers of m's stage entry points hold (workspace, io scratch, TDT alignment scratch; 0 with m == NULL): what a call that promises to
+ * buffers of m's stage entry points hold (workspace, io scratch, TDT alignment and TDT total scratch; 0 with m == NULL): what a call that promises to
  * allocate nothing must leave unchanged. */
 pk_status pk_diag_mem_info(pk_model *m, uint64_t out[3]);
 

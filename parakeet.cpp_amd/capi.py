@@ -64,6 +64,10 @@ class PkBeamOptions(C.Structure):
     _fields_ = [("beam_width", C.c_int32), ("token_prune", C.c_int32), ("n_best", C.c_int32), ("timestamps", C.c_int32)]
 
 
+class PkRescoreOptions(C.Structure):
+    _fields_ = [("tdt_weight", C.c_float)]
+
+
 class PkNbest(C.Structure):
     _fields_ = [("n_hyp", C.c_int32), ("hyp", C.POINTER(PkResult)), ("score", f32p)]
 
@@ -193,6 +197,15 @@ _LATE_SIGNATURES = {
     "pk_tdt_align_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, i32p, i32p, f32p, f32p, i32p],
     "pk_tdt_align_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, f32p],
     "pk_diag_mem_info": [C.c_void_p, C.POINTER(C.c_uint64)],
+    "pk_tdt_total": [f32p, f32p, f32p, i32p, C.c_int, i32p, C.c_int, i32p, f32p, i32p],
+    "pk_tdt_total_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_int, f32p, i32p],
+    "pk_tdt_total_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, C.c_int, f32p, i32p],
+    "pk_tdt_total_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_int, C.c_int, f32p],
+    "pk_tdt_score_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, i32p, C.c_int, f32p, i32p],
+    "pk_transcribe_pcm_nbest_rescored": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkBeamOptions), C.POINTER(PkRescoreOptions),
+                                         C.POINTER(C.POINTER(PkNbest)), f32p, f32p],
+    "pk_diag_tdt_total_groups": [i32p, i32p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.POINTER(C.c_int)],
+    "pk_diag_rescore_order": [i32p, f32p, f32p, i32p, C.c_int, C.c_float, i32p, f32p],
     "pk_tdt_align_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.POINTER(C.POINTER(PkResult)), f32p, i32p],
     "pk_diag_tdt_lattice": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, f32p, f32p, f32p],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -349,6 +362,41 @@ def tdt_align(lattices, durations):
     lab, blk, dl = cat(0), cat(1), cat(2)
     dur = np.ascontiguousarray(durations, np.int32)
     return _tdt_align_call(lib().pk_tdt_align, (_f(lab), _f(blk), _f(dl), _i(dur), len(dur), _i(T), len(T)), off)
+
+
+# ---- TDT log-likelihood of given token strings, n-best rescoring (include/parakeet_amd.h) ------
+def tdt_total(lattices, durations):
+    """pk_tdt_total: lattices as capi.tdt_align takes them -> list (one dict per utterance) of total, ok.  Needs a device, no model."""
+    T = np.asarray([x[1].shape[0] for x in lattices], np.int32)
+    off = np.zeros(len(lattices) + 1, np.int32)
+    off[1:] = np.cumsum([x[1].shape[1] - 1 for x in lattices])
+    cat = lambda k: _c(np.concatenate([_c(x[k]).ravel() for x in lattices] + [np.zeros(1, np.float32)]))
+    lab, blk, dl = cat(0), cat(1), cat(2)
+    dur = np.ascontiguousarray(durations, np.int32)
+    tt = np.zeros(len(T), np.float32); ok = np.zeros(len(T), np.int32)
+    check(lib().pk_tdt_total(_f(lab), _f(blk), _f(dl), _i(dur), len(dur), _i(T), len(T), _i(off), _f(tt), _i(ok)))
+    return [dict(total=tt[b], ok=int(ok[b])) for b in range(len(T))]
+
+
+def tdt_total_groups(n_frames_of_hyp, lengths, durations, V, J, max_hyps=0):
+    """pk_diag_tdt_total_groups: the group every hypothesis (n_frames_of_hyp[h] frames, lengths[h] tokens) is walked in.  Host arithmetic."""
+    T = np.ascontiguousarray(n_frames_of_hyp, np.int32)
+    off = np.zeros(len(T) + 1, np.int32)
+    off[1:] = np.cumsum(lengths)
+    dur = np.ascontiguousarray(durations, np.int32)
+    g = np.zeros(len(T), np.int32); n = C.c_int(0)
+    check(lib().pk_diag_tdt_total_groups(_i(T), _i(off), len(T), _i(dur), len(dur), int(V), int(J), int(max_hyps), _i(g), C.byref(n)))
+    return g, n.value
+
+
+def rescore_order(lens, ctc, tdt, ok, tdt_weight):
+    """pk_diag_rescore_order: the ordering rule of pk_transcribe_pcm_nbest_rescored on the N slots of one clip -> (order, combined by slot).
+    Host arithmetic."""
+    lens, ok = np.ascontiguousarray(lens, np.int32), np.ascontiguousarray(ok, np.int32)
+    ctc, tdt = np.ascontiguousarray(ctc, np.float32), np.ascontiguousarray(tdt, np.float32)
+    order = np.zeros(len(ctc), np.int32); comb = np.zeros(len(ctc), np.float32)
+    check(lib().pk_diag_rescore_order(_i(lens), _f(ctc), _f(tdt), _i(ok), len(ctc), float(tdt_weight), _i(order), _f(comb)))
+    return order.tolist(), comb
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -1854,6 +1902,83 @@ class Model:
                 d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
             out.append(d)
         lib().pk_results_free(res, n)
+        return out
+
+    def _total_args(self, enc, ids, clip_of):
+        rag, x, T = self._enc_head(enc)
+        pid, off = _pack_ids(ids)
+        co = None if clip_of is None else np.ascontiguousarray(clip_of, np.int32)
+        return rag, x, T, pid, off, co
+
+    def tdt_total_decode(self, enc, ids, clip_of=None):
+        """pk_tdt_total_decode(_ragged): enc [n_clips][T][d] or a list of [T_c][d] matrices; ids: one token sequence per hypothesis;
+        clip_of[h]: the clip hypothesis h is scored on (None: hypothesis h on clip h) -> list of dicts total, ok."""
+        rag, x, T, pid, off, co = self._total_args(enc, ids, clip_of)
+        n = len(off) - 1
+        tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
+        tail = (_i(pid), _i(off), _i(co) if co is not None else None, n, _f(tt), _i(ok))
+        if rag:
+            check(lib().pk_tdt_total_decode_ragged(self._h, _f(x), _i(T), len(T), *tail))
+        else:
+            check(lib().pk_tdt_total_decode(self._h, _f(x), x.shape[0], x.shape[1], *tail))
+        return [dict(total=tt[b], ok=int(ok[b])) for b in range(n)]
+
+    def tdt_total_decode_timed(self, enc, ids, clip_of=None, reps=5):
+        """pk_tdt_total_decode_timed -> (prediction net ms, lattice ms, forward pass ms), HIP events, medians of reps passes."""
+        rag, x, T, pid, off, co = self._total_args(enc, ids, clip_of)
+        ms = np.zeros(3, np.float32)
+        check(lib().pk_tdt_total_decode_timed(self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], _i(pid), _i(off),
+                                              _i(co) if co is not None else None, len(off) - 1, reps, _f(ms)))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def score_tdt(self, clips, texts=None, ids=None, clip_of=None):
+        """pk_tdt_score_pcm: the TDT log-likelihood of one or more transcripts per clip (texts need the vocabulary) -> list of dicts total, ok."""
+        assert (texts is None) != (ids is None), "texts or ids"
+        if isinstance(clips, tuple):
+            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
+        else:
+            pcm, off = pack_clips(clips)
+        n = len(texts) if texts is not None else len(ids)
+        co = None if clip_of is None else np.ascontiguousarray(clip_of, np.int32)
+        tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
+        if texts is not None:
+            keep = (C.c_char_p * n)(*[t.encode() for t in texts])
+            tail = (keep, None, None)
+        else:
+            pid, poff = _pack_ids(ids)
+            tail = (None, _i(pid), _i(poff))
+        check(lib().pk_tdt_score_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), len(off) - 1, *tail, _i(co) if co is not None else None, n, _f(tt), _i(ok)))
+        return [dict(total=tt[b], ok=int(ok[b])) for b in range(n)]
+
+    def transcribe_nbest_rescored(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False, tdt_weight=0.5):
+        """pk_transcribe_pcm_nbest_rescored: transcribe_nbest re-ranked by the TDT head: per clip a list of dicts as transcribe_nbest returns
+        them, "score" the combined value, + "ctc_score" and "tdt_total"."""
+        if isinstance(clips, tuple):
+            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
+        else:
+            pcm, off = pack_clips(clips)
+        n = len(off) - 1
+        o = beam_options(beam_width, token_prune, n_best, timestamps)
+        ro = PkRescoreOptions(float(tdt_weight))
+        N = max(1, o.n_best)
+        cs = np.zeros((n, N), np.float32); tt = np.zeros((n, N), np.float32)
+        res = C.POINTER(PkNbest)()
+        check(lib().pk_transcribe_pcm_nbest_rescored(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(ro), C.byref(res), _f(cs), _f(tt)))
+        out = []
+        for i in range(n):
+            hyps = []
+            for j in range(res[i].n_hyp):
+                r = res[i].hyp[j]
+                d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]),
+                         ctc_score=float(cs[i, j]), tdt_total=float(tt[i, j]))
+                if timestamps:
+                    d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
+                    d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
+                    d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
+                    d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
+                hyps.append(d)
+            out.append(hyps)
+        lib().pk_nbest_free(res, n)
         return out
 
     def ctc_beam_decode_timed(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, reps=5):

@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_batch.cpp -- the resident two-stream batch pipeline (pk_batch_*) and the one-call API on top of it:
-// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest, pk_align_pcm, pk_tdt_align_pcm and the result stores they hand out.
+// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest(_rescored), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm and the result stores they hand out.
 #include <algorithm>
 #include <cstring>
 
@@ -886,57 +886,163 @@ static void encode_batch(Model &m, const float *pcm, const int64_t *offsets, con
     if (ctc) m.run_ctc(m.ws, m.ws.x.as<float>(), nc, r.T_max, true, m.stream);
 }
 
+// The body of pk_transcribe_pcm_nbest and pk_transcribe_pcm_nbest_rescored.  tdt_weight != nullptr: every returned hypothesis of a batch is scored
+// under the TDT head on the batch's encoder rows (tdt_total.hpp; enc_proj once per batch, hypotheses of a clip share its rows) and each clip's list
+// is re-ordered by rescore_order; ctc_out / tdt_out (optional, [n_clips][N]) take the parts in the returned order.
+static void nbest_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt, const float *tdt_weight,
+                      pk_nbest **results, float *ctc_out, float *tdt_out) {
+    const pk_beam_options o = beam_options_of(opt);
+    int V = 0, blank = 0;
+    beam_model_checks(m, o, V, blank);
+    const bool ts = o.timestamps != 0;
+    const int N = o.n_best;
+    auto store = std::make_unique<NbestStore>();
+    store->out.resize((size_t)n_clips + 1); store->clip.resize(n_clips); store->score.resize(n_clips);
+    std::vector<int64_t> clip_len(n_clips);
+    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+    std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
+    plan_batches(clip_len.data(), n_clips, order, bstart);
+    std::vector<int32_t> ids, lens, st, en, hids, hoff, hclip, hslot, okv, ord;
+    std::vector<float> sc, cf, tt, comb;
+    const float NEGF = -__builtin_huge_valf();
+    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+        RagBatch r;
+        encode_batch(m, pcm, offsets, order.data() + c0, nc, r);
+        const int T = r.T_max;
+        run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream);
+        PK_CHECK_LAUNCH();
+        const size_t hyps = (size_t)nc * N, tok = hyps * T;
+        ids.resize(tok); lens.resize(hyps); sc.resize(hyps);
+        if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
+        beam_copy_out(m.beam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, ts ? cf.data() : nullptr, m.stream);
+        if (tdt_weight) {
+            // the filled slots of the batch as one packed call of the total: hypothesis (i, j) on the rows of the batch's clip i
+            hids.clear(); hoff.assign(1, 0); hclip.clear(); hslot.clear();
+            for (int i = 0; i < nc; ++i)
+                for (int j = 0; j < N && sc[(size_t)i * N + j] > NEGF; ++j) {
+                    const size_t hy = (size_t)i * N + j;
+                    hids.insert(hids.end(), ids.begin() + hy * T, ids.begin() + hy * T + lens[hy]);
+                    hoff.push_back((int32_t)hids.size()); hclip.push_back(i); hslot.push_back((int32_t)hy);
+                }
+            tt.assign(hyps, NEGF); okv.assign(hyps, 0);
+            const int nh_all = (int)hclip.size();
+            if (nh_all > 0) {
+                hids.push_back(0);                              // (never read: keeps data() valid when every hypothesis is empty)
+                // the total's limits (1535 tokens, the scratch cap) depend on the search's output: this is the earliest they can be checked (header)
+                align_check_args(hids.data(), hoff.data(), nh_all, m.cfg.vocab_size, m.cfg.blank_id);
+                tdt_total_plan_call(m, m.ttotal, r.T.data(), nc, 0, hoff.data(), hclip.data(), nh_all);
+                m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
+                run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), hids.data(), hoff.data());
+                PK_CHECK_LAUNCH();
+                for (int q = 0; q < nh_all; ++q) { tt[hslot[q]] = m.ttotal.total[q]; okv[hslot[q]] = m.ttotal.ok[q]; }
+            }
+        }
+        for (int i = 0; i < nc; ++i) {
+            const int c = order[c0 + i];
+            int nh = 0;
+            while (nh < N && sc[(size_t)i * N + nh] > NEGF) ++nh;
+            store->clip[c] = new_store(nh);
+            ResultStore &R = *store->clip[c];
+            ord.resize(N); comb.resize(N);
+            for (int j = 0; j < N; ++j) { ord[j] = j; comb[j] = sc[(size_t)i * N + j]; }
+            if (tdt_weight)
+                rescore_order(lens.data() + (size_t)i * N, sc.data() + (size_t)i * N, tt.data() + (size_t)i * N, okv.data() + (size_t)i * N, N, *tdt_weight,
+                              ord.data(), comb.data());
+            store->score[c].resize(nh);
+            for (int j = 0; j < N; ++j) {                       // position j of the returned list holds the beam's slot ord[j]; the nh filled slots come first
+                const size_t hy = (size_t)i * N + ord[j], o0 = hy * T;
+                if (ctc_out) ctc_out[(size_t)c * N + j] = j < nh ? sc[hy] : NEGF;
+                if (tdt_out) tdt_out[(size_t)c * N + j] = j < nh ? tt[hy] : NEGF;
+                if (j >= nh) continue;
+                store->score[c][j] = comb[ord[j]];
+                store_tokens(m, R, j, lens[hy], ids.data() + o0, ts ? st.data() + o0 : nullptr, ts ? en.data() + o0 : nullptr, ts ? cf.data() + o0 : nullptr);
+            }
+            point_results(R, nh, ts);
+            store->out[c].n_hyp = nh;
+            store->out[c].hyp = R.res.data();
+            store->out[c].score = store->score[c].data();
+        }
+    }
+    pk_nbest &tail = store->out[n_clips];
+    tail.n_hyp = 0; tail.score = nullptr;
+    tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
+    *results = store->out.data();
+    store.release();
+}
+
 pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
                                   pk_nbest **results) {
     return guard([&] {
         need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
+        nbest_pcm(*h->m, pcm, offsets, n_clips, opt, nullptr, results, nullptr, nullptr);
+    });
+}
+
+pk_status pk_transcribe_pcm_nbest_rescored(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *beam_opt,
+                                           const pk_rescore_options *rescore_opt, pk_nbest **results, float *ctc_score, float *tdt_total) {
+    return guard([&] {
+        need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
         Model &m = *h->m;
-        const pk_beam_options o = beam_options_of(opt);
-        int V = 0, blank = 0;
-        beam_model_checks(m, o, V, blank);
-        const bool ts = o.timestamps != 0;
-        const int N = o.n_best;
-        auto store = std::make_unique<NbestStore>();
-        store->out.resize((size_t)n_clips + 1); store->clip.resize(n_clips); store->score.resize(n_clips);
-        std::vector<int64_t> clip_len(n_clips);
-        for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
-        std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
-        plan_batches(clip_len.data(), n_clips, order, bstart);
-        std::vector<int32_t> ids, lens, st, en;
-        std::vector<float> sc, cf;
-        for (size_t k = 0; k + 1 < bstart.size(); ++k) {
-            const int c0 = bstart[k], nc = bstart[k + 1] - c0;
-            RagBatch r;
-            encode_batch(m, pcm, offsets, order.data() + c0, nc, r);
-            const int T = r.T_max;
-            run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream);
-            PK_CHECK_LAUNCH();
-            const size_t hyps = (size_t)nc * N, tok = hyps * T;
-            ids.resize(tok); lens.resize(hyps); sc.resize(hyps);
-            if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
-            beam_copy_out(m.beam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, ts ? cf.data() : nullptr, m.stream);
-            for (int i = 0; i < nc; ++i) {
-                const int c = order[c0 + i];
-                int nh = 0;
-                while (nh < N && sc[(size_t)i * N + nh] > -__builtin_huge_valf()) ++nh;
-                store->clip[c] = new_store(nh);
-                ResultStore &R = *store->clip[c];
-                store->score[c].assign(sc.begin() + (size_t)i * N, sc.begin() + (size_t)i * N + nh);
-                for (int j = 0; j < nh; ++j) {
-                    const size_t hy = (size_t)i * N + j, o0 = hy * T;
-                    store_tokens(m, R, j, lens[hy], ids.data() + o0, ts ? st.data() + o0 : nullptr, ts ? en.data() + o0 : nullptr, ts ? cf.data() + o0 : nullptr);
-                }
-                point_results(R, nh, ts);
-                store->out[c].n_hyp = nh;
-                store->out[c].hyp = R.res.data();
-                store->out[c].score = store->score[c].data();
+        const float w = rescore_opt ? rescore_opt->tdt_weight : 0.5f;
+        need(w == w && w > -__builtin_huge_valf() && w < __builtin_huge_valf(), "tdt_weight must be finite");
+        if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: the rescored n-best needs the CTC head for the search");
+        tdt_align_model_checks(m);
+        if (m.cfg.ctc_vocab_size != m.cfg.vocab_size)
+            fail(PK_ERR_UNSUPPORTED, "the CTC head (%d) and the TDT head (%d) of this model do not share a vocabulary", m.cfg.ctc_vocab_size, m.cfg.vocab_size);
+        nbest_pcm(m, pcm, offsets, n_clips, beam_opt, &w, results, ctc_score, tdt_total);
+    });
+}
+
+static void align_transcripts(Model &m, int n_clips, const char *const *texts, const int32_t *ids_in, const int32_t *id_offsets_in, int V, int blank,
+                              std::vector<int32_t> &all_ids, std::vector<int32_t> &all_off);
+
+// The body of pk_tdt_score_pcm: the batches of pk_transcribe_pcm; the transcripts of a batch's clips are scored on its encoder rows.
+static void score_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids, const std::vector<int32_t> &all_off,
+                      const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    std::vector<int64_t> clip_len(n_clips);
+    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+    std::vector<int> order, bstart;
+    plan_batches(clip_len.data(), n_clips, order, bstart);
+    std::vector<std::vector<int>> hyps_of(n_clips);
+    for (int q = 0; q < n_hyp; ++q) hyps_of[clip_of ? clip_of[q] : q].push_back(q);
+    std::vector<int32_t> bids, boff, bclip, bhyp, nfr;
+    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+        bids.clear(); boff.assign(1, 0); bclip.clear(); bhyp.clear();
+        for (int i = 0; i < nc; ++i)
+            for (int q : hyps_of[order[c0 + i]]) {
+                bids.insert(bids.end(), all_ids.begin() + all_off[q], all_ids.begin() + all_off[q + 1]);
+                boff.push_back((int32_t)bids.size()); bclip.push_back(i); bhyp.push_back(q);
             }
-        }
-        pk_nbest &tail = store->out[n_clips];
-        tail.n_hyp = 0; tail.score = nullptr;
-        tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
-        *results = store->out.data();
-        store.release();
+        const int nh = (int)bhyp.size();
+        if (nh == 0) continue;                                      // (no transcript for any clip of this batch: nothing to encode)
+        bids.push_back(0);
+        RagBatch r;
+        encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
+            nfr.assign(rb.T.begin(), rb.T.begin() + nc);               // (the plan refuses before the batch is encoded)
+            tdt_total_plan_call(m, m.ttotal, nfr.data(), nc, 0, boff.data(), bclip.data(), nh);
+        }, /*ctc=*/false);
+        m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
+        run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), bids.data(), boff.data());
+        PK_CHECK_LAUNCH();
+        for (int q = 0; q < nh; ++q) { total[bhyp[q]] = m.ttotal.total[q]; ok[bhyp[q]] = m.ttotal.ok[q]; }
+    }
+}
+
+pk_status pk_tdt_score_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
+                           const int32_t *id_offsets_in, const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && pcm && offsets && total && ok && n_clips > 0 && n_hyp > 0, "model/pcm/offsets/total/ok/n_clips/n_hyp");
+        need(texts || id_offsets_in, "texts or ids/id_offsets");
+        Model &m = *h->m;
+        tdt_align_model_checks(m);
+        if (clip_of) for (int q = 0; q < n_hyp; ++q) need(clip_of[q] >= 0 && clip_of[q] < n_clips, "clip_of[h] outside [0, n_clips)");
+        else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
+        std::vector<int32_t> all_ids, all_off;
+        align_transcripts(m, n_hyp, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
+        m.require_gpu();
+        score_pcm(m, pcm, offsets, n_clips, all_ids, all_off, clip_of, n_hyp, total, ok);
     });
 }
 

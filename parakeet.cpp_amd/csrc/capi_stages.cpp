@@ -676,3 +676,126 @@ pk_status pk_diag_tdt_lattice(pk_model *h, const float *enc, const int32_t *n_fr
 }
 
 }  // extern "C"
+
+/* ---- the forward-algorithm total of given token strings under the TDT head (kernels/tdt_total.hip) ------------------------------------ */
+// the argument checks of the model entry points; -> after them the call is planned (host only) in m.ttotal
+static void tdt_total_checks(Model &m, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of,
+                             int n_hyp) {
+    tdt_align_model_checks(m);
+    need(n_clips >= 1 && n_hyp >= 1, "n_clips/n_hyp");
+    if (clip_of) for (int h = 0; h < n_hyp; ++h) need(clip_of[h] >= 0 && clip_of[h] < n_clips, "clip_of[h] outside [0, n_clips)");
+    else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
+    align_check_args(ids, id_offsets, n_hyp, m.cfg.vocab_size, m.cfg.blank_id);
+    if (n_frames) for (int b = 0; b < n_clips; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+    m.require_gpu();
+    tdt_total_plan_call(m, m.ttotal, n_frames, n_clips, T, id_offsets, clip_of, n_hyp);
+}
+
+// uploads enc, runs enc_proj ONCE over the clips' rows, then the planned groups
+static void tdt_total_run(Model &m, const float *enc, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets,
+                          hipEvent_t *ev = nullptr, float *ms = nullptr) {
+    size_t rows;
+    size_ws(m, n_frames, n_clips, T, rows);
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
+    run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), ids, id_offsets, ev, ms);
+    PK_CHECK_LAUNCH();
+}
+
+static void tdt_total_decode(Model &m, const float *enc, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets,
+                             const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    tdt_total_checks(m, n_frames, n_clips, T, ids, id_offsets, clip_of, n_hyp);
+    tdt_total_run(m, enc, n_frames, n_clips, T, ids, id_offsets);
+    std::copy(m.ttotal.total.begin(), m.ttotal.total.end(), total);
+    std::copy(m.ttotal.ok.begin(), m.ttotal.ok.end(), ok);
+}
+
+extern "C" {
+
+pk_status pk_tdt_total(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int B,
+                       const int32_t *id_offsets, float *total, int32_t *ok) {
+    return guard([&] {
+        need(B >= 1 && id_offsets && n_frames && durations, "B/id_offsets/n_frames/durations");
+        need(id_offsets[0] == 0, "id_offsets[0] must be 0");
+        for (int b = 0; b < B; ++b) {
+            need(id_offsets[b + 1] >= id_offsets[b], "id_offsets decrease");
+            need(n_frames[b] > 0, "n_frames[b] must be positive");
+        }
+        need(blk && dl && total && ok, "blk/dl/total/ok");
+        need(id_offsets[B] == 0 || lab, "lab");
+        TdtAlignWs ws;
+        tdt_lattice_plan(ws, n_frames, nullptr, B, 0, id_offsets, durations, D, 0, 0, 0, /*back_pointers=*/false, "TDT total");   // (host only: refuses before a device is looked for)
+        need_device();
+        tdt_total_upload(ws, nullptr, nullptr);
+        if (ws.labs) PK_HIP(hipMemcpyAsync(ws.lab.p, lab, (size_t)ws.labs * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.blk.p, blk, (size_t)ws.cells * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.dl.p, dl, (size_t)ws.cells * D * 4, hipMemcpyHostToDevice, nullptr));
+        run_tdt_total_dp(ws, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(total, ws.out.p, (size_t)B * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(ok, ws.out.as<int>() + B, (size_t)B * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
+pk_status pk_tdt_total_decode(pk_model *h, const float *enc, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of,
+                              int n_hyp, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && total && ok && T > 0, "model/enc/total/ok/T");
+        tdt_total_decode(*h->m, enc, nullptr, n_clips, T, ids, id_offsets, clip_of, n_hyp, total, ok);
+    });
+}
+
+pk_status pk_tdt_total_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int n_clips, const int32_t *ids, const int32_t *id_offsets,
+                                     const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && n_frames && total && ok, "model/enc/n_frames/total/ok");
+        tdt_total_decode(*h->m, enc, n_frames, n_clips, 0, ids, id_offsets, clip_of, n_hyp, total, ok);
+    });
+}
+
+pk_status pk_tdt_total_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int n_clips, int T, const int32_t *ids,
+                                    const int32_t *id_offsets, const int32_t *clip_of, int n_hyp, int reps, float ms[3]) {
+    return guard([&] {
+        need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
+        Model &m = *h->m;
+        tdt_total_checks(m, n_frames, n_clips, T, ids, id_offsets, clip_of, n_hyp);
+        struct Ev { hipEvent_t e[4] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        std::vector<float> t[3];
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            float v[3] = {0, 0, 0};                                // per stage, summed over the groups of the call
+            tdt_total_run(m, enc, n_frames, n_clips, T, ids, id_offsets, ev.e, v);
+            if (r > 0) for (int k = 0; k < 3; ++k) t[k].push_back(v[k]);
+        }
+        for (int k = 0; k < 3; ++k) { std::sort(t[k].begin(), t[k].end()); ms[k] = t[k][t[k].size() / 2]; }
+    });
+}
+
+pk_status pk_diag_tdt_total_groups(const int32_t *n_frames_of_hyp, const int32_t *id_offsets, int n_hyp, const int32_t *durations, int D, int V, int J,
+                                   int max_hyps, int32_t *group_of, int *n_groups) {
+    return guard([&] {
+        need(n_frames_of_hyp && id_offsets && durations && group_of && n_hyp >= 1, "n_frames_of_hyp/id_offsets/durations/group_of/n_hyp");
+        need(id_offsets[0] == 0 && V >= 0 && J >= 0, "id_offsets[0]/V/J");
+        for (int b = 0; b < n_hyp; ++b) {
+            need(id_offsets[b + 1] >= id_offsets[b], "id_offsets decrease");
+            need(n_frames_of_hyp[b] > 0, "n_frames_of_hyp[b] must be positive");
+        }
+        std::vector<int32_t> gs;
+        tdt_total_groups(gs, n_frames_of_hyp, id_offsets, n_hyp, durations, D, V, J, max_hyps);
+        for (size_t g = 0; g + 1 < gs.size(); ++g)
+            for (int i = gs[g]; i < gs[g + 1]; ++i) group_of[i] = (int32_t)g;
+        if (n_groups) *n_groups = (int)gs.size() - 1;
+    });
+}
+
+pk_status pk_diag_rescore_order(const int32_t *lens, const float *ctc_score, const float *tdt_total, const int32_t *ok, int N, float tdt_weight,
+                                int32_t *order, float *combined) {
+    return guard([&] {
+        need(lens && ctc_score && tdt_total && ok && order && combined && N >= 1, "lens/ctc_score/tdt_total/ok/order/combined/N");
+        need(tdt_weight == tdt_weight && tdt_weight > -__builtin_huge_valf() && tdt_weight < __builtin_huge_valf(), "tdt_weight must be finite");
+        rescore_order(lens, ctc_score, tdt_total, ok, N, tdt_weight, order, combined);
+    });
+}
+
+}  // extern "C"

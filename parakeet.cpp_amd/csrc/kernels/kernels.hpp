@@ -493,6 +493,15 @@ void launch_tdt_lattice_act(const TdtLattice &lt, const int *ep_row0, const floa
 // columns and over the D duration columns, gathered at ids[u] (u < U_b) and blank
 void launch_tdt_lattice_keep(const TdtLattice &lt, const int *ids, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s);
 
+// The forward-algorithm total of GIVEN token strings on the same lattice (kernels/tdt_total.hip): the log-sum over every
+// path to END.  One workgroup per hypothesis, widths kTdtAlignThreads, the alignment's limits.
+struct TdtTotalArgs {
+    TdtLattice lt;
+    float *total; int *ok;                      // [B]: ok = total > -inf
+    int u_max, dur_max;                         // over the batch: the dynamic LDS is (dur_max + 2) * (u_max + 1) floats
+};
+void launch_tdt_total(const TdtTotalArgs &a, hipStream_t s);
+
 struct TdtState {
     int B, T, V, D, L, Hp, blank, max_symbols, max_tokens, max_steps;
     TrieDev trie;

@@ -19,12 +19,18 @@ TdtLattice TdtAlignWs::lattice() const {
 
 void tdt_align_plan(TdtAlignWs &ws, const int32_t *n_frames, int B, int T, const int32_t *id_offsets, const int32_t *durations, int D, int V, int J,
                     int chunk_rows) {
-    if (D < 1 || D > 8) fail(PK_ERR_UNSUPPORTED, "TDT alignment: %d durations, the kernel is built for 1 to 8", D);
+    tdt_lattice_plan(ws, n_frames, nullptr, B, T, id_offsets, durations, D, V, J, chunk_rows, /*back_pointers=*/true, "TDT alignment");
+}
+
+void tdt_lattice_plan(TdtAlignWs &ws, const int32_t *n_frames, const int32_t *row0, int B, int T, const int32_t *id_offsets, const int32_t *durations,
+                      int D, int V, int J, int chunk_rows, bool back_pointers, const char *what) {
+    const size_t bpb = back_pointers ? 1 : 0;
+    if (D < 1 || D > 8) fail(PK_ERR_UNSUPPORTED, "%s: %d durations, the kernel is built for 1 to 8", what, D);
     ws.dur_max = 0;
     for (int i = 0; i < 8; ++i) ws.durations[i] = 0;
     for (int i = 0; i < D; ++i) {
         if (durations[i] < 0 || durations[i] > kTdtAlignMaxDur)
-            fail(PK_ERR_UNSUPPORTED, "TDT alignment: duration %d, the kernel is built for 0 to %d", durations[i], kTdtAlignMaxDur);
+            fail(PK_ERR_UNSUPPORTED, "%s: duration %d, the kernel is built for 0 to %d", what, durations[i], kTdtAlignMaxDur);
         ws.durations[i] = durations[i];
         ws.dur_max = std::max(ws.dur_max, (int)durations[i]);
     }
@@ -37,24 +43,24 @@ void tdt_align_plan(TdtAlignWs &ws, const int32_t *n_frames, int B, int T, const
     for (int b = 0; b < B; ++b) {
         const int64_t U = id_offsets[b + 1] - id_offsets[b], Tb = n_frames ? n_frames[b] : T;
         if (U > kTdtAlignMaxTokens)
-            fail(PK_ERR_UNSUPPORTED, "TDT alignment: %lld tokens in utterance %d, at most %d can be aligned", (long long)U, b, kTdtAlignMaxTokens);
+            fail(PK_ERR_UNSUPPORTED, "%s: %lld tokens in utterance %d, at most %d can be aligned", what, (long long)U, b, kTdtAlignMaxTokens);
         ws.u_max = std::max(ws.u_max, (int)U);
-        hT[b] = (int32_t)Tb; hoff[b] = id_offsets[b]; hrow[b] = (int32_t)rows;
+        hT[b] = (int32_t)Tb; hoff[b] = id_offsets[b]; hrow[b] = row0 ? row0[b] : (int32_t)rows;
         hcell[b] = cells; hlab[b] = labs;
         cells += Tb * (U + 1); labs += Tb * U; rows += Tb;
-        if ((size_t)cells * (5 + 4 * (size_t)D) > kTdtAlignMaxScratch) break;        // (refused below; keeps the sums far from overflow)
+        if ((size_t)cells * (4 + bpb + 4 * (size_t)D) > kTdtAlignMaxScratch) break;        // (refused below; keeps the sums far from overflow)
     }
     hoff[B] = id_offsets[B]; hcell[B] = cells; hlab[B] = labs;
     ws.chunk_rows = 0;
-    size_t bytes = 4 * ((size_t)labs + (size_t)cells * (1 + D)) + (size_t)cells;
+    size_t bytes = 4 * ((size_t)labs + (size_t)cells * (1 + D)) + (size_t)cells * bpb;
     if (V > 0) {
         ws.chunk_rows = chunk_rows > 0 ? chunk_rows : tdt_align_chunk_rows(V + D);
         if ((int64_t)ws.chunk_rows > cells) ws.chunk_rows = (int)std::max<int64_t>(cells, 1);
         bytes += (size_t)ws.chunk_rows * (size_t)(V + D + J) * 4 + (size_t)(ws.u_max + 1) * B * ((size_t)J + 1) * 4;
     }
     if (bytes > kTdtAlignMaxScratch)
-        fail(PK_ERR_UNSUPPORTED, "TDT alignment: the scratch of this call (lattice values, back-pointers%s) exceeds the cap of %zu bytes",
-             V > 0 ? ", rows chunk, prediction net" : "", kTdtAlignMaxScratch);
+        fail(PK_ERR_UNSUPPORTED, "%s: the scratch of this call (lattice values%s%s) exceeds the cap of %zu bytes", what,
+             back_pointers ? ", back-pointers" : "", V > 0 ? ", rows chunk, prediction net" : "", kTdtAlignMaxScratch);
     ws.B = B; ws.D = D; ws.n_ids = (size_t)id_offsets[B]; ws.cells = cells; ws.labs = labs;
 }
 
@@ -74,7 +80,7 @@ void tdt_align_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s) {
     PK_HIP(hipMemsetAsync(ws.conf.p, 0, n * 4, s));
 }
 
-void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_t s) {
+void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_t s, float *const *state) {
     const pk_config &c = m.cfg;
     const int B = ws.B, Hp = c.pred_hidden, J = c.joint_hidden, L = c.num_lstm_layers, steps = ws.u_max + 1;
     Workspace &w = m.ws;
@@ -88,9 +94,10 @@ void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_
         for (int u = 1; u <= off[b + 1] - off[b]; ++u) ws.h_tok[(size_t)u * B + b] = ids[off[b] + u - 1];
     PK_HIP(hipMemcpyAsync(ws.tok.p, ws.h_tok.data(), ws.h_tok.size() * 4, hipMemcpyHostToDevice, s));
     const size_t st = (size_t)L * B * Hp;
-    PK_HIP(hipMemsetAsync(w.h.p, 0, st * 4, s));
-    PK_HIP(hipMemsetAsync(w.c.p, 0, st * 4, s));
-    float *hb[2] = {w.h.as<float>(), w.hn.as<float>()}, *cb[2] = {w.c.as<float>(), w.cn.as<float>()};
+    float *hb[2] = {state ? state[0] : w.h.as<float>(), state ? state[1] : w.hn.as<float>()};
+    float *cb[2] = {state ? state[2] : w.c.as<float>(), state ? state[3] : w.cn.as<float>()};
+    PK_HIP(hipMemsetAsync(hb[0], 0, st * 4, s));
+    PK_HIP(hipMemsetAsync(cb[0], 0, st * 4, s));
     for (int u = 0; u < steps; ++u) {
         const float *hs = hb[u & 1], *cs = cb[u & 1];
         float *hd = hb[(u + 1) & 1], *cd = cb[(u + 1) & 1];          // every step commits: the candidates of step u are the state of step u + 1

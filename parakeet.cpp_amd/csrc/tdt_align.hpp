@@ -40,11 +40,16 @@ struct TdtAlignWs {
 // (V, J: vocabulary and joint width; chunk_rows > 0 overrides the chunk size).
 void tdt_align_plan(TdtAlignWs &ws, const int32_t *n_frames, int B, int T, const int32_t *id_offsets, const int32_t *durations, int D, int V = 0,
                     int J = 0, int chunk_rows = 0);
+// The same plan for any walk over the lattice (the alignment, the forward-algorithm total of tdt_total.hpp).  row0 != nullptr: utterance b reads the
+// encoder rows from row0[b] on (several token strings may share one clip's frames) instead of its own packed rows; back_pointers: the walk keeps one
+// byte per cell; what: the name the refusals carry.
+void tdt_lattice_plan(TdtAlignWs &ws, const int32_t *n_frames, const int32_t *row0, int B, int T, const int32_t *id_offsets, const int32_t *durations,
+                      int D, int V, int J, int chunk_rows, bool back_pointers, const char *what);
 // reserves the buffers, uploads the tables and the token strings on s, zero-fills the result arrays
 void tdt_align_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s);
 // pred_proj of every prefix: U_max + 1 lock-step steps of the prediction net over [blank, ids...] on the decode loop's skinny products -> ws.pp.
-// Uses m.ws's LSTM state buffers (sized for B utterances by the caller).
-void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_t s);
+// Uses m.ws's LSTM state buffers (sized for B utterances by the caller), or state = {h, hn, c, cn}, each [L][B][Hp] floats.
+void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_t s, float *const *state = nullptr);
 // the lattice values from ep = enc_proj of the packed frames (ws.tab's ep_row0), in chunks of ws.chunk_rows rows -> ws.lab / blk / dl
 void run_tdt_align_lattice(Model &m, TdtAlignWs &ws, const float *d_ep, hipStream_t s);
 // the heads product of the first n rows of ws.z alone -> ws.logits (what run_tdt_align_lattice runs per chunk; the timed entry point measures it on its own)

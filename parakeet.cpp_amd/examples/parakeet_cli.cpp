@@ -2,12 +2,16 @@
 // arguments, --model types and options; every model type runs through the drop-in facade classes.
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K]]
-//                [--align "text" | --align-file path.txt] [--align-head ctc|tdt]
+//                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
 // New: --align "text" / --align-file path.txt (tdt-ctc-110m, tdt-600m) aligns the given transcript with the audio (CTC forced alignment) and
 // prints its word timestamps in the format of --timestamps.  --align-head tdt aligns through the TDT head instead (the default stays ctc): the one
 // that works for tdt-600m, which has no CTC head.
+// New: --score "text" (tdt-ctc-110m, tdt-600m) prints the log-likelihood of the given transcript under the TDT head (the forward algorithm on the
+// alignment's lattice).  --nbest N --rescore-tdt W (tdt-ctc-110m) prints the N best hypotheses of the CTC beam search re-ranked by
+// (1 - W) * CTC score + W * TDT log-likelihood, with both parts.
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <fstream>
@@ -28,6 +32,8 @@ static void usage(const char *prog) {
               << "  --beam W [--nbest N] [--prune K]  CTC prefix beam search (needs the CTC decoder), N best hypotheses\n"
               << "  --align \"text\" | --align-file path.txt  CTC forced alignment of a known transcript: its word timestamps\n"
               << "  --align-head ctc|tdt  the head --align goes through (default: ctc; tdt needs no CTC head)\n"
+              << "  --score \"text\"  log-likelihood of a known transcript under the TDT head\n"
+              << "  --nbest N --rescore-tdt W  the N best hypotheses re-ranked by (1 - W) * CTC score + W * TDT log-likelihood\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
 }
@@ -61,6 +67,21 @@ static int run_align(T &t, const std::string &audio_path, const std::string &tex
     return 0;
 }
 
+// --score: the transcript's log-likelihood under the TDT head
+template <class T>
+static int run_score(T &t, const std::string &audio_path, const std::string &text) {
+    const auto r = t.score(audio_path, text, /*tdt_head=*/true);
+    if (!r.scored) {
+        std::cerr << "Error: no path of the TDT head emits the transcript (" << r.token_ids.size() << " tokens) on this audio\n";
+        return 1;
+    }
+    std::cout << "Score (tdt): log-likelihood " << std::fixed << std::setprecision(4) << r.log_likelihood << "\n";
+    std::cout << "Tokens (" << r.token_ids.size() << "):";
+    for (int id : r.token_ids) std::cout << ' ' << id;
+    std::cout << "\n";
+    return 0;
+}
+
 template <class T>
 static int run_stream(T &t, const std::string &audio_path, bool timestamps) {
     t.to_gpu();
@@ -85,9 +106,10 @@ int main(int argc, char **argv) {
     if (argc < 3) { usage(argv[0]); return 1; }
     try {
         const std::string weights = argv[1], audio_path = argv[2];
-        std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text;
-        bool use_ctc = false, timestamps = false, align = false, align_tdt = false;
+        std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text, score_text;
+        bool use_ctc = false, timestamps = false, align = false, align_tdt = false, score = false, rescore = false, nbest_given = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
+        float rescore_w = 0.5f;
         std::vector<std::string> boost;
         float boost_score = 5.0f;
         for (int i = 3; i < argc; ++i) {
@@ -114,7 +136,9 @@ int main(int argc, char **argv) {
                 if (hd != "ctc" && hd != "tdt") { std::cerr << "Unknown alignment head: " << hd << "\n"; return 1; }
                 align_tdt = hd == "tdt";
             }
-            else if (a == "--nbest" && i + 1 < argc) nbest = std::stoi(argv[++i]);
+            else if (a == "--nbest" && i + 1 < argc) { nbest = std::stoi(argv[++i]); nbest_given = true; }
+            else if (a == "--score" && i + 1 < argc) { score_text = argv[++i]; score = true; }
+            else if (a == "--rescore-tdt" && i + 1 < argc) { rescore_w = std::stof(argv[++i]); rescore = true; }
             else if (a == "--prune" && i + 1 < argc) prune = std::stoi(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
@@ -133,11 +157,29 @@ int main(int argc, char **argv) {
         opts.boost_score = boost_score;
         if (align && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --align needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (align && vocab.empty()) { std::cerr << "Error: --align needs --vocab\n"; return 1; }
+        if (score && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --score needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
+        if (score && vocab.empty()) { std::cerr << "Error: --score needs --vocab\n"; return 1; }
+        if (rescore && !nbest_given) { std::cerr << "Error: --rescore-tdt needs --nbest N\n"; return 1; }
+        if (rescore && model != "tdt-ctc-110m") { std::cerr << "Error: --rescore-tdt needs a model with both heads (--model tdt-ctc-110m)\n"; return 1; }
         std::cout << "Loading model: " << model << std::endl;
         if (model == "tdt-ctc-110m") {
             Transcriber t(weights, vocab);
             t.to_gpu();
             if (align) return run_align(t, audio_path, align_text, align_tdt);
+            if (score) return run_score(t, audio_path, score_text);
+            if (rescore) {                                          // the beam's list re-ranked by the TDT head; --beam W optional (default 8)
+                if (!boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
+                BeamOptions bo;
+                bo.beam_width = beam > 0 ? beam : std::max(8, nbest); bo.n_best = nbest; bo.token_prune = prune;
+                RescoreOptions ro;
+                ro.tdt_weight = rescore_w;
+                const auto hyps = t.transcribe_nbest(audio_path, bo, ro);
+                std::cout << "Rescored beam search: width " << bo.beam_width << ", TDT weight " << std::defaultfloat << rescore_w << ", " << hyps.size() << " hypotheses\n";
+                for (size_t j = 0; j < hyps.size(); ++j)
+                    std::cout << "#" << j + 1 << " [" << std::fixed << std::setprecision(4) << hyps[j].score << "] ctc " << hyps[j].ctc_score << " tdt "
+                              << hyps[j].tdt_total << " " << hyps[j].result.text << "\n";
+                return 0;
+            }
             if (!boost.empty()) std::cout << "Phrase boost: " << boost.size() << " phrases\n";
             if (beam > 0) {
                 if (!use_ctc) { std::cerr << "Error: --beam needs the CTC decoder (--ctc / --decoder ctc)\n"; return 1; }
@@ -161,6 +203,7 @@ int main(int argc, char **argv) {
             TDTTranscriber t(weights, vocab);
             t.to_gpu();
             if (align) return run_align(t, audio_path, align_text, align_tdt);
+            if (score) return run_score(t, audio_path, score_text);
             const auto t0 = Clock::now();
             const auto r = t.transcribe(audio_path, opts);
             print_result(r, timestamps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());

@@ -20,6 +20,7 @@
 // Errors surface as std::runtime_error with the reference's trigger conditions (unreadable vocab / audio, ...).
 #pragma once
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -60,6 +61,24 @@ struct BeamOptions {
     int token_prune = 16;   // most probable non-blank tokens considered per frame, 1..32
     int n_best = 1;         // hypotheses returned, 1..beam_width
     bool timestamps = false;
+};
+
+/// New: parameters of the TDT rescoring of an n-best list (pk_rescore_options).
+struct RescoreOptions {
+    float tdt_weight = 0.5f;   // w: hypotheses are ordered by (1 - w) * CTC score + w * TDT log-likelihood
+};
+/// New: one hypothesis of transcribe_nbest(audio, beam, rescore): score is the combined value, ctc_score / tdt_total its parts.
+struct RescoredResult : ScoredResult {
+    float ctc_score = 0.0f;
+    float tdt_total = 0.0f;
+};
+/// New: what Transcriber::score returns: the log-likelihood of the given transcript under the TDT head (pk_tdt_score_pcm: the forward algorithm
+/// on the alignment's lattice).  scored == false: no path emits the transcript on this audio, log_likelihood is -inf.
+struct ScoreResult {
+    std::string text;
+    std::vector<int> token_ids;
+    float log_likelihood = 0.0f;
+    bool scored = false;
 };
 
 struct TranscribeOptions {
@@ -185,6 +204,65 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return run_nbest(pcm, (size_t)n, opts);
     }
 
+    // pk_transcribe_pcm_nbest_rescored on one clip: run_nbest's list re-ranked by the TDT head's log-likelihood of every hypothesis
+    std::vector<RescoredResult> run_nbest_rescored(const float *pcm, size_t n, const BeamOptions &opts, const RescoreOptions &rescore) {
+        if (!on_gpu_) to_gpu(0);
+        pk_beam_options o;
+        pk_beam_options_default(&o);
+        o.beam_width = opts.beam_width; o.token_prune = opts.token_prune; o.n_best = opts.n_best; o.timestamps = opts.timestamps ? 1 : 0;
+        pk_rescore_options ro{rescore.tdt_weight};
+        const int64_t offsets[2] = {0, (int64_t)n};
+        pk_nbest *res = nullptr;
+        std::vector<float> ctc((size_t)std::max(1, opts.n_best)), tdt(ctc.size());
+        check(pk_transcribe_pcm_nbest_rescored(m_, pcm, offsets, 1, &o, &ro, &res, ctc.data(), tdt.data()));
+        std::vector<RescoredResult> out(res[0].n_hyp);
+        for (int j = 0; j < res[0].n_hyp; ++j) {
+            const pk_result &r = res[0].hyp[j];
+            out[j].score = res[0].score[j]; out[j].ctc_score = ctc[j]; out[j].tdt_total = tdt[j];
+            out[j].result.text = r.text ? r.text : "";
+            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
+            if (opts.timestamps) {
+                for (int k = 0; k < r.n_tokens; ++k)
+                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
+                for (int k = 0; k < r.n_words; ++k)
+                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
+            }
+        }
+        pk_nbest_free(res, 1);
+        return out;
+    }
+    std::vector<RescoredResult> run_nbest_rescored_file(const std::string &audio_path, const BeamOptions &opts, const RescoreOptions &rescore) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_nbest_rescored(pcm, (size_t)n, opts, rescore);
+    }
+
+    // the log-likelihood of `text` (tokenised by the model's vocabulary) on one clip under the TDT head: pk_tdt_score_pcm
+    ScoreResult run_score(const float *pcm, size_t n, const std::string &text, bool tdt_head) {
+        if (!tdt_head) throw std::invalid_argument("score: only the TDT head is scored here; the CTC head's log-likelihood is AlignResult::total of align()");
+        if (!on_gpu_) to_gpu(0);
+        const int64_t offsets[2] = {0, (int64_t)n};
+        const char *texts[1] = {text.c_str()};
+        ScoreResult out;
+        out.text = text;
+        for (int v : tok_.encode(text)) out.token_ids.push_back(v);
+        int32_t ok = 0;
+        check(pk_tdt_score_pcm(m_, pcm, offsets, 1, texts, nullptr, nullptr, nullptr, 1, &out.log_likelihood, &ok));
+        out.scored = ok != 0;
+        return out;
+    }
+    ScoreResult run_score_file(const std::string &audio_path, const std::string &text, bool tdt_head) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_score(pcm, (size_t)n, text, tdt_head);
+    }
+
     // pk_align_pcm on one clip: the CTC forced alignment of `text` (tokenised by the model's vocabulary); single device
     // tdt_head: pk_tdt_align_pcm, the TDT forced alignment (no CTC head needed; AlignResult::total stays 0: that head has no forward pass)
     AlignResult run_align(const float *pcm, size_t n, const std::string &text, bool tdt_head = false) {
@@ -295,6 +373,20 @@ class Transcriber {
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
     AlignResult align_tdt(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text, true); }
+    /// New: the log-likelihood of a given transcript: tdt_head = true through the TDT head's forward algorithm
+    /// (pk_tdt_score_pcm; no CTC head needed).  false throws std::invalid_argument: the CTC head's log-likelihood is align()'s AlignResult::total.
+    ScoreResult score(const std::string &audio_path, const std::string &text, bool tdt_head = true) { return eng_.run_score_file(audio_path, text, tdt_head); }
+    ScoreResult score(const float *pcm, size_t n, const std::string &text, bool tdt_head = true) { return eng_.run_score(pcm, n, text, tdt_head); }
+    ScoreResult score(const std::vector<float> &samples, const std::string &text, bool tdt_head = true) {
+        return eng_.run_score(samples.data(), samples.size(), text, tdt_head);
+    }
+    /// New: the n-best list re-ranked by the TDT head (pk_transcribe_pcm_nbest_rescored): needs both heads.
+    std::vector<RescoredResult> transcribe_nbest(const std::string &audio_path, const BeamOptions &opts, const RescoreOptions &rescore) {
+        return eng_.run_nbest_rescored_file(audio_path, opts, rescore);
+    }
+    std::vector<RescoredResult> transcribe_nbest(const float *pcm, size_t n, const BeamOptions &opts, const RescoreOptions &rescore) {
+        return eng_.run_nbest_rescored(pcm, n, opts, rescore);
+    }
 
     pk_model *model() { return eng_.handle(); }   // the engine handle (the reference returns its ParakeetTDTCTC module tree)
 
@@ -352,6 +444,13 @@ class TDTTranscriber {
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
     AlignResult align_tdt(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text, true); }
+    /// New: the log-likelihood of a given transcript: tdt_head = true through the TDT head's forward algorithm
+    /// (pk_tdt_score_pcm; no CTC head needed).  false throws std::invalid_argument: the CTC head's log-likelihood is align()'s AlignResult::total.
+    ScoreResult score(const std::string &audio_path, const std::string &text, bool tdt_head = true) { return eng_.run_score_file(audio_path, text, tdt_head); }
+    ScoreResult score(const float *pcm, size_t n, const std::string &text, bool tdt_head = true) { return eng_.run_score(pcm, n, text, tdt_head); }
+    ScoreResult score(const std::vector<float> &samples, const std::string &text, bool tdt_head = true) {
+        return eng_.run_score(samples.data(), samples.size(), text, tdt_head);
+    }
 
     pk_model *model() { return eng_.handle(); }
 
