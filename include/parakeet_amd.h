@@ -499,9 +499,61 @@ pk_status pk_diag_tdt_total_groups(const int32_t *n_frames_of_hyp, const int32_t
 pk_status pk_diag_rescore_order(const int32_t *lens, const float *ctc_score, const float *tdt_total, const int32_t *ok, int N, float tdt_weight,
                                 int32_t *order, float *combined);
 /* Diagnostic: out[0] / out[1] = free / total bytes of the current device (hipMemGetInfo), out[2] = the bytes of device memory the grow-only
- * buffers of m's stage entry points hold (workspace, io scratch, TDT alignment and TDT total scratch; 0 with m == NULL): what a call that promises to
+ * buffers of m's stage entry points hold (workspace, io scratch, TDT alignment, TDT total and keyword-spotting scratch; 0 with m == NULL): what a call that promises to
  * allocate nothing must leave unchanged. */
 pk_status pk_diag_mem_info(pk_model *m, uint64_t out[3]);
+
+/* ---- CTC keyword spotting: is a phrase said anywhere in this audio, and when ---------------------------------------------------
+ * Given the log-probs and a list of keywords (token strings): the best non-overlapping spans in which each keyword was said.  A keyword's
+ * lattice is the CTC lattice of its L tokens without the leading and the trailing blank (2 L - 1 states; arcs stay / previous state / skip,
+ * a skip only onto a token that differs from the token before it), walked max-plus with a FREE start (the first state may be entered at any
+ * frame with value +0.0) and a FREE end (the last state is read at every frame).  The cost of a symbol at a frame is its log-prob minus the
+ * frame's largest log-prob, so a score is the log-ratio of the keyword's best path over a span to the unconstrained best path over the same
+ * span: <= 0, without a bias towards short spans, and exactly +0.0 where the greedy path over the span IS the keyword.  The hits of a
+ * (utterance, keyword) pair are picked greedily: the best end frame (ties: the earliest), its span [start, end], then every end frame whose
+ * span meets that one is out; up to max_hits times, in the order picked.  Specified operation by operation in DESIGN.md section 5.5.4
+ * (tests/ctc_kws_ref.py is that specification in Python; the device result equals it bit for bit).  All of it runs on the device
+ * (kernels/ctc_kws.hip).  Matching is on token strings: "cat" matches inside "category" unless the tokenisation differs.  No threshold is
+ * applied unless the caller sets one.  pk_group and streaming sessions have no spotting variant; the TDT head has none.
+ * PRECONDITION: every row of the log-probs has a finite maximum (a true log-softmax row always has one).
+ *
+ * pk_ctc_kws: HOST log-probs in.  Needs a device, no model.  logp / n_frames / B / T / V / blank as pk_ctc_beam_search.  kw_ids: the n_kw keywords
+ * packed, keyword k = kw_ids[kw_offsets[k] .. kw_offsets[k+1]) (kw_offsets[0] = 0).  Every keyword is searched in every utterance.
+ * Outputs: n_hits [B][n_kw]; start / end (encoder frames, inclusive) and score [B][n_kw][max_hits]; unused slots are start = end = 0,
+ * score = -inf.
+ * PK_ERR_INVALID (before any device work): B < 1, n_kw < 1, an empty keyword, offsets that decrease, an id outside [0, V) or equal to blank,
+ * min_score > 0 or NaN.
+ * PK_ERR_UNSUPPORTED (before anything is allocated): a keyword of more than 64 tokens, max_hits outside 1 .. 16, more than 65535 utterances, or
+ * more than 1 GiB of scratch (8 * n_kw * sum of T_b bytes: 128 keywords over one hour, T = 45000, take 46 MB). */
+typedef struct pk_kws_options {
+    int32_t max_hits;           /* hits reported per (utterance, keyword), 1 .. 16 */
+    float min_score;            /* only end frames with score >= min_score are picked; <= 0, -inf: no threshold */
+} pk_kws_options;
+/* the defaults: max_hits = 1, min_score = -inf (the best span is reported and the caller applies a threshold).  opt == NULL means the defaults. */
+void pk_kws_options_default(pk_kws_options *out);
+pk_status pk_ctc_kws(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const int32_t *kw_ids, const int32_t *kw_offsets,
+                     int n_kw, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score);
+/* CTC head + log-softmax (the kernels of pk_ctc_decode) + the spotting on the model's stream; the log-probs never leave the device.
+ * enc [B][T][hidden] resp. packed with n_frames[B].  PK_ERR_UNSUPPORTED for a model without a CTC head.  A boost trie set on the model does
+ * not matter: the spotting reads the unboosted log-softmax rows. */
+pk_status pk_ctc_kws_decode(pk_model *m, const float *enc, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
+                            const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score);
+pk_status pk_ctc_kws_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *kw_ids, const int32_t *kw_offsets,
+                                   int n_kw, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score);
+/* Stage timers of the spotting (tools/bench_ctc_kws.py): the CTC head + log-softmax + greedy collapse, then the spotting (uploads of the
+ * keywords, the row maxima, the walk and the picking), each between hipEvents on the model's stream; medians of `reps` passes after one
+ * warm-up.  n_frames NULL: uniform [B][T].  ms[0] = CTC stage, ms[1] = spotting stage. */
+pk_status pk_ctc_kws_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids,
+                                  const int32_t *kw_offsets, int n_kw, const pk_kws_options *opt, int reps, float ms[2]);
+/* One call from PCM and phrases to hits: clips of any length packed into ragged batches by the policy of pk_transcribe_pcm (pk_plan_batches)
+ * exactly as pk_align_pcm packs them, encoded (the attention context set on the model applies), spotted.  The keywords: phrases[n_kw] UTF-8
+ * (tokenised as pk_tokenize does; needs the model's vocabulary), or, with phrases == NULL, ids packed with kw_offsets[n_kw + 1].  Every keyword
+ * is searched in every clip.  n_hits [n_clips][n_kw]; start_s / end_s / score [n_clips][n_kw][max_hits] in the caller's clip order.  Times are
+ * seconds by the rule of the timestamps (frame * 0.08 s): start_s is the start of the first frame, end_s the END of the last frame
+ * ((end + 1) * 0.08 s); unused slots 0 / 0 / -inf. */
+pk_status pk_spot_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *phrases_or_null,
+                      const int32_t *ids_or_null, const int32_t *kw_offsets, int n_kw, const pk_kws_options *opt, int32_t *n_hits, float *start_s,
+                      float *end_s, float *score);
 
 /* ---- one node, several GPUs: utterance shards (the reference has no multi-device path, README.md:513) ----------
  * A pk_group is one model REPLICA per device of this process: the safetensors file is mapped once and every replica is built from that

@@ -68,6 +68,10 @@ class PkRescoreOptions(C.Structure):
     _fields_ = [("tdt_weight", C.c_float)]
 
 
+class PkKwsOptions(C.Structure):
+    _fields_ = [("max_hits", C.c_int32), ("min_score", C.c_float)]
+
+
 class PkNbest(C.Structure):
     _fields_ = [("n_hyp", C.c_int32), ("hyp", C.POINTER(PkResult)), ("score", f32p)]
 
@@ -208,6 +212,12 @@ _LATE_SIGNATURES = {
     "pk_diag_rescore_order": [i32p, f32p, f32p, i32p, C.c_int, C.c_float, i32p, f32p],
     "pk_tdt_align_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.POINTER(C.POINTER(PkResult)), f32p, i32p],
     "pk_diag_tdt_lattice": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, f32p, f32p, f32p],
+    "pk_kws_options_default": [C.POINTER(PkKwsOptions)],
+    "pk_ctc_kws": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
+    "pk_ctc_kws_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
+    "pk_ctc_kws_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
+    "pk_ctc_kws_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), C.c_int, f32p],
+    "pk_spot_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, f32p, f32p, f32p],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -397,6 +407,40 @@ def rescore_order(lens, ctc, tdt, ok, tdt_weight):
     order = np.zeros(len(ctc), np.int32); comb = np.zeros(len(ctc), np.float32)
     check(lib().pk_diag_rescore_order(_i(lens), _f(ctc), _f(tdt), _i(ok), len(ctc), float(tdt_weight), _i(order), _f(comb)))
     return order.tolist(), comb
+
+
+# ---- CTC keyword spotting (include/parakeet_amd.h) -----------------------------
+def kws_options(max_hits=None, min_score=None):
+    """pk_kws_options: the library's defaults (max_hits = 1, min_score = -inf) with the given fields replaced."""
+    o = PkKwsOptions()
+    lib().pk_kws_options_default(C.byref(o))
+    if max_hits is not None:
+        o.max_hits = max_hits
+    if min_score is not None:
+        o.min_score = min_score
+    return o
+
+
+def _kws_call(fn, head, B, keywords, o):
+    """-> dict of n_hits [B][n_kw], start / end / score [B][n_kw][max_hits] (unused slots 0 / 0 / -inf)."""
+    ids, off = _pack_ids(keywords)
+    K, H = len(keywords), max(1, o.max_hits)
+    nh = np.zeros((B, K), np.int32); st = np.zeros((B, K, H), np.int32); en = np.zeros((B, K, H), np.int32); sc = np.zeros((B, K, H), np.float32)
+    check(fn(*head, _i(ids), _i(off), K, C.byref(o), _i(nh), _i(st), _i(en), _f(sc)))
+    return dict(n_hits=nh, start=st, end=en, score=sc)
+
+
+def ctc_kws(logp, keywords, blank, max_hits=None, min_score=None):
+    """pk_ctc_kws: logp [B][T][V] (uniform) or a list of [T_b][V] matrices (ragged); keywords: a list of token sequences, every one searched
+    in every utterance.  Needs a device, no model."""
+    o = kws_options(max_hits, min_score)
+    if isinstance(logp, (list, tuple)):
+        T = np.asarray([x.shape[0] for x in logp], np.int32)
+        lp = _c(np.concatenate([_c(x) for x in logp], axis=0))
+        return _kws_call(lib().pk_ctc_kws, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), len(T), keywords, o)
+    lp = _c(logp)
+    B, T, V = lp.shape
+    return _kws_call(lib().pk_ctc_kws, (_f(lp), None, B, T, V, blank), B, keywords, o)
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -1980,6 +2024,52 @@ class Model:
             out.append(hyps)
         lib().pk_nbest_free(res, n)
         return out
+
+    def ctc_kws_decode(self, enc, keywords, max_hits=None, min_score=None):
+        """pk_ctc_kws_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_kws."""
+        o = kws_options(max_hits, min_score)
+        if isinstance(enc, (list, tuple)):
+            T = np.asarray([e.shape[0] for e in enc], np.int32)
+            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
+            return _kws_call(lib().pk_ctc_kws_decode_ragged, (self._h, _f(x), _i(T), len(T)), len(T), keywords, o)
+        x = _c(enc)
+        B, T, _ = x.shape
+        return _kws_call(lib().pk_ctc_kws_decode, (self._h, _f(x), B, T), B, keywords, o)
+
+    def ctc_kws_decode_timed(self, enc, keywords, max_hits=None, min_score=None, reps=5):
+        """pk_ctc_kws_decode_timed -> (CTC stage ms, spotting stage ms), HIP events, medians of reps passes."""
+        o = kws_options(max_hits, min_score)
+        pid, poff = _pack_ids(keywords)
+        ms = np.zeros(2, np.float32)
+        if isinstance(enc, (list, tuple)):
+            T = np.asarray([e.shape[0] for e in enc], np.int32)
+            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
+            check(lib().pk_ctc_kws_decode_timed(self._h, _f(x), _i(T), len(T), 0, _i(pid), _i(poff), len(keywords), C.byref(o), reps, _f(ms)))
+        else:
+            x = _c(enc)
+            check(lib().pk_ctc_kws_decode_timed(self._h, _f(x), None, x.shape[0], x.shape[1], _i(pid), _i(poff), len(keywords), C.byref(o), reps, _f(ms)))
+        return float(ms[0]), float(ms[1])
+
+    def spot(self, clips, phrases=None, ids=None, max_hits=None, min_score=None):
+        """pk_spot_pcm: every phrase (texts: needs the vocabulary; or token id sequences) searched in every clip (list, or packed
+        (pcm, offsets)) -> per clip, per phrase, a list of (start_s, end_s, score), best first."""
+        assert (phrases is None) != (ids is None), "phrases or ids"
+        if isinstance(clips, tuple):
+            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
+        else:
+            pcm, off = pack_clips(clips)
+        n = len(off) - 1
+        o = kws_options(max_hits, min_score)
+        K, H = len(phrases if phrases is not None else ids), max(1, o.max_hits)
+        if phrases is not None:
+            keep = (C.c_char_p * K)(*[t.encode() for t in phrases])
+            tail = (keep, None, None)
+        else:
+            pid, poff = _pack_ids(ids)
+            tail = (None, _i(pid), _i(poff))
+        nh = np.zeros((n, K), np.int32); st = np.zeros((n, K, H), np.float32); en = np.zeros((n, K, H), np.float32); sc = np.zeros((n, K, H), np.float32)
+        check(lib().pk_spot_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, K, C.byref(o), _i(nh), _f(st), _f(en), _f(sc)))
+        return [[[(float(st[c, k, j]), float(en[c, k, j]), float(sc[c, k, j])) for j in range(nh[c, k])] for k in range(K)] for c in range(n)]
 
     def ctc_beam_decode_timed(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, reps=5):
         """pk_ctc_beam_decode_timed -> (greedy CTC stage ms, beam search stage ms), HIP events, medians of reps passes."""

@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_batch.cpp -- the resident two-stream batch pipeline (pk_batch_*) and the one-call API on top of it:
-// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest(_rescored), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm and the result stores they hand out.
+// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest(_rescored), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm, pk_spot_pcm and the result stores they hand out.
 #include <algorithm>
 #include <cstring>
 
@@ -1146,6 +1146,69 @@ pk_status pk_tdt_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets
         align_transcripts(m, n_clips, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
         m.require_gpu();
         align_pcm(m, true, pcm, offsets, n_clips, all_ids, all_off, results, score, nullptr, ok);
+    });
+}
+
+pk_status pk_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *phrases, const int32_t *ids_in,
+                      const int32_t *kw_offsets_in, int n_kw, const pk_kws_options *opt, int32_t *n_hits, float *start_s, float *end_s, float *score) {
+    return guard([&] {
+        need(h && pcm && offsets && n_hits && start_s && end_s && score && n_clips > 0, "model/pcm/offsets/n_hits/start_s/end_s/score/n_clips");
+        need(phrases || (ids_in && kw_offsets_in), "phrases or ids/kw_offsets");
+        Model &m = *h->m;
+        if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC keyword spotting needs one");
+        const int V = m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;
+        const pk_kws_options o = kws_options_of(opt);
+        std::vector<int32_t> ids, off;                             // the keywords, packed; the same for every batch
+        if (phrases) {
+            need(n_kw >= 1, "n_kw");
+            need(m.tok.loaded(), "spotting phrases needs the model's vocabulary");
+            off.assign(1, 0);
+            for (int k = 0; k < n_kw; ++k) {
+                need(phrases[k] != nullptr, "phrases[k]");
+                for (int v : m.tok.encode(phrases[k])) ids.push_back(v);
+                off.push_back((int32_t)ids.size());
+            }
+            ids.push_back(0);                                      // (never read: keeps data() non-null for a list of empty phrases)
+            kws_check_args(ids.data(), off.data(), n_kw, n_clips, V, blank, o);
+        } else {
+            kws_check_args(ids_in, kw_offsets_in, n_kw, n_clips, V, blank, o);
+            off.assign(kw_offsets_in, kw_offsets_in + n_kw + 1);
+            ids.assign(ids_in, ids_in + off[n_kw]);
+        }
+        m.require_gpu();
+        std::vector<int64_t> clip_len(n_clips);
+        for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+        std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
+        plan_batches(clip_len.data(), n_clips, order, bstart);
+        const size_t H = (size_t)o.max_hits, per_clip = (size_t)n_kw * H;
+        std::vector<int32_t> nfr, nh, st, en;
+        std::vector<float> sc;
+        for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+            const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+            RagBatch r;
+            encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
+                nfr.assign(rb.T.begin(), rb.T.begin() + nc);
+                kws_plan(m.kws, nfr.data(), nc, rb.T_max, off.data(), n_kw, o);     // (refuses before the batch is encoded)
+            });
+            run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, ids.data(), m.stream);
+            PK_CHECK_LAUNCH();
+            nh.resize((size_t)nc * n_kw); st.resize(nc * per_clip); en.resize(nc * per_clip); sc.resize(nc * per_clip);
+            kws_copy_out(m.kws, nh.data(), st.data(), en.data(), sc.data(), m.stream);
+            for (int i = 0; i < nc; ++i) {
+                const size_t c = (size_t)order[c0 + i];
+                for (int q = 0; q < n_kw; ++q) {
+                    const int n = nh[(size_t)i * n_kw + q];
+                    n_hits[c * n_kw + q] = n;
+                    for (size_t j = 0; j < H; ++j) {
+                        const size_t src = i * per_clip + q * H + j, dst = c * per_clip + q * H + j;
+                        const bool hit = (int)j < n;
+                        start_s[dst] = hit ? frame_to_seconds(st[src]) : 0.0f;
+                        end_s[dst] = hit ? frame_to_seconds(en[src] + 1) : 0.0f;     // the END of the last frame
+                        score[dst] = sc[src];
+                    }
+                }
+            }
+        }
     });
 }
 

@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_stages.cpp -- the stage entry points of the C boundary on caller buffers: mel, subsample, encode, conformer blocks,
-// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix beam search and the CTC and TDT forced alignments.
+// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix beam search, the CTC and TDT forced alignments and the CTC keyword spotting.
 #include <algorithm>
 #include <cstring>
 
@@ -184,6 +184,32 @@ static void tdt_align_decode(Model &m, const float *enc, const int32_t *n_frames
     tdt_align_queue(m, enc, n_frames, B, T, ids, true);
     PK_CHECK_LAUNCH();
     tdt_align_copy_out(m.talign, start, end, dur_idx, conf, score, ok, m.stream);
+}
+
+// the spotting's model checks (include/parakeet_amd.h); -> the CTC vocabulary and its blank.  A boost trie does not matter: run_ctc writes the
+// unboosted log-softmax rows, and those are what is walked.
+static void kws_model_checks(Model &m, int &V, int &blank) {
+    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC keyword spotting needs one");
+    V = m.cfg.ctc_vocab_size;
+    blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;           // (as Model::run_ctc)
+}
+
+static void ctc_kws_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
+                           const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    const pk_kws_options o = kws_options_of(opt);
+    int V = 0, blank = 0;
+    kws_model_checks(m, V, blank);
+    kws_check_args(kw_ids, kw_offsets, n_kw, B, V, blank, o);
+    if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+    m.require_gpu();
+    kws_plan(m.kws, n_frames, B, T, kw_offsets, n_kw, o);
+    size_t rows;
+    T = size_ws(m, n_frames, B, T, rows);
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+    run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), B, T, n_frames ? m.ws.rv.seq : SeqRag(), V, blank, kw_ids, m.stream);
+    PK_CHECK_LAUNCH();
+    kws_copy_out(m.kws, n_hits, start, end, score, m.stream);
 }
 
 extern "C" {
@@ -795,6 +821,103 @@ pk_status pk_diag_rescore_order(const int32_t *lens, const float *ctc_score, con
         need(lens && ctc_score && tdt_total && ok && order && combined && N >= 1, "lens/ctc_score/tdt_total/ok/order/combined/N");
         need(tdt_weight == tdt_weight && tdt_weight > -__builtin_huge_valf() && tdt_weight < __builtin_huge_valf(), "tdt_weight must be finite");
         rescore_order(lens, ctc_score, tdt_total, ok, N, tdt_weight, order, combined);
+    });
+}
+
+/* ---- CTC keyword spotting (kernels/ctc_kws.hip) --------------------------------------------------------------------------------------- */
+void pk_kws_options_default(pk_kws_options *out) {
+    if (!out) return;
+    *out = kws_options_of(nullptr);
+}
+
+pk_status pk_ctc_kws(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const int32_t *kw_ids, const int32_t *kw_offsets,
+                     int n_kw, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    return guard([&] {
+        const pk_kws_options o = kws_options_of(opt);
+        kws_check_args(kw_ids, kw_offsets, n_kw, B, V, blank, o);
+        need(logp && n_hits && start && end && score, "logp/n_hits/start/end/score");
+        need(n_frames || T > 0, "T");
+        int64_t rows = (int64_t)B * T;
+        std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
+        if (n_frames) {
+            tab.resize(2 * (size_t)B + 1);
+            rows = 0; T = 0;
+            for (int b = 0; b < B; ++b) {
+                need(n_frames[b] > 0, "n_frames[b] must be positive");
+                tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
+                rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
+                need(rows < ((int64_t)1 << 31), "too many frames");
+            }
+            tab[2 * (size_t)B] = (int32_t)rows;
+        }
+        need_device();
+        KwsWs ws;
+        kws_plan(ws, n_frames, B, T, kw_offsets, n_kw, o);         // (refuses before anything is allocated)
+        DevBuf d_lp, d_tab;
+        d_lp.reserve((size_t)rows * V * 4);
+        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
+        SeqRag rag;
+        if (n_frames) {
+            d_tab.reserve(tab.size() * 4);
+            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
+        }
+        run_ctc_kws(ws, d_lp.as<float>(), B, T, rag, V, blank, kw_ids, nullptr);
+        PK_CHECK_LAUNCH();
+        kws_copy_out(ws, n_hits, start, end, score, nullptr);
+    });
+}
+
+pk_status pk_ctc_kws_decode(pk_model *h, const float *enc, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
+                            const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    return guard([&] {
+        need(h && enc && n_hits && start && end && score && T > 0, "model/enc/n_hits/start/end/score/T");
+        ctc_kws_decode(*h->m, enc, nullptr, B, T, kw_ids, kw_offsets, n_kw, opt, n_hits, start, end, score);
+    });
+}
+
+pk_status pk_ctc_kws_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *kw_ids, const int32_t *kw_offsets,
+                                   int n_kw, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    return guard([&] {
+        need(h && enc && n_frames && n_hits && start && end && score, "model/enc/n_frames/n_hits/start/end/score");
+        ctc_kws_decode(*h->m, enc, n_frames, B, 0, kw_ids, kw_offsets, n_kw, opt, n_hits, start, end, score);
+    });
+}
+
+pk_status pk_ctc_kws_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids,
+                                  const int32_t *kw_offsets, int n_kw, const pk_kws_options *opt, int reps, float ms[2]) {
+    return guard([&] {
+        need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
+        Model &m = *h->m;
+        const pk_kws_options o = kws_options_of(opt);
+        int V = 0, blank = 0;
+        kws_model_checks(m, V, blank);
+        kws_check_args(kw_ids, kw_offsets, n_kw, B, V, blank, o);
+        if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+        m.require_gpu();
+        kws_plan(m.kws, n_frames, B, T, kw_offsets, n_kw, o);
+        size_t rows;
+        T = size_ws(m, n_frames, B, T, rows);
+        const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        std::vector<float> head, spot;
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+            m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
+            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), B, T, rag, V, blank, kw_ids, m.stream);
+            PK_HIP(hipEventRecord(ev.e[2], m.stream));
+            PK_HIP(hipStreamSynchronize(m.stream));
+            PK_CHECK_LAUNCH();
+            float a = 0, b = 0;
+            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+            if (r > 0) { head.push_back(a); spot.push_back(b); }
+        }
+        std::sort(head.begin(), head.end()); std::sort(spot.begin(), spot.end());
+        ms[0] = head[head.size() / 2]; ms[1] = spot[spot.size() / 2];
     });
 }
 

@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "ctc_align.hpp"
 #include "ctc_beam.hpp"
+#include "ctc_kws.hpp"
 #include "kernels/kernels.hpp"
 #include "safetensors.hpp"
 #include "tdt_align.hpp"
@@ -237,6 +238,7 @@ class Model {
     Workspace ws;       // workspace of the host-buffer stage entry points
     BeamWs beam;        // scratch and results of the CTC prefix beam search entry points (ctc_beam.hpp)
     AlignWs align;      // scratch and results of the CTC forced-alignment entry points (ctc_align.hpp)
+    KwsWs kws;          // scratch and results of the CTC keyword-spotting entry points (ctc_kws.hpp)
     TdtAlignWs talign;  // scratch and results of the TDT forced-alignment entry points (tdt_align.hpp)
     TdtTotalWs ttotal;  // scratch and results of the TDT total / rescoring entry points (tdt_total.hpp)
     int decode_loop = PK_DECODE_LOOP_PHASES;   // pk_model_set_decode_loop: how run_tdt_loop issues the greedy loop

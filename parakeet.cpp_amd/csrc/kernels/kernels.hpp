@@ -463,6 +463,24 @@ struct CtcAlignArgs {
 };
 // shape: index into kAlignThreads / kAlignStrip; every utterance of the batch needs 2 L + 1 <= kAlignThreads[shape] * kAlignStrip[shape]
 void launch_ctc_align(const CtcAlignArgs &a, int shape, hipStream_t s);
+// CTC keyword spotting (kernels/ctc_kws.hip) over the same rows: every keyword in every utterance, one wave per pair.
+constexpr int kKwsMaxLen = 64;                  // tokens of a keyword: one lane each
+constexpr int kKwsMaxHits = 16;
+constexpr int kKwsAhead = 8;                    // frames whose log-probs are requested ahead of the walk
+struct CtcKwsArgs {
+    const float *lp; int V, blank;
+    int B, T, n_kw;                             // uniform extents (rg.T == nullptr), else T = the longest utterance
+    const int *ids, *kw_off;                    // packed keywords, kw_off[n_kw + 1]
+    const float *g;                             // row maxima of lp (launch_ctc_rowmax), one per row
+    int2 *eb;                                   // scratch: (score bits, start frame) per end frame, [B][n_kw][T_b]: entry n_kw * T_off[b] + k * T_b + t
+    int max_hits; float min_score;
+    int *n_hits;                                // [B][n_kw]
+    int *start, *end; float *score;             // [B][n_kw][max_hits], written whole (unused slots 0 / 0 / -inf)
+    SeqRag rg;
+};
+void launch_ctc_rowmax(const float *lp, float *g, int64_t rows, int V, hipStream_t s);
+// every keyword needs 1 <= L <= kKwsMaxLen, max_hits 1 .. kKwsMaxHits, B <= 65535 (grid.y); g filled first
+void launch_ctc_kws(const CtcKwsArgs &a, hipStream_t s);
 
 // TDT forced alignment of GIVEN token strings (kernels/tdt_align.hip).  The lattice of utterance b is T_b x (U_b + 1)
 // cells, cell (t, u) = the joint at frame t with the prediction net having consumed ids[:u]; cell c = t (U_b + 1) + u of the utterance sits at

@@ -3,6 +3,7 @@
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
+//                [--spot "phrase"]... [--spot-file path.txt] [--spot-hits N] [--spot-min-score X]
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
 // New: --align "text" / --align-file path.txt (tdt-ctc-110m, tdt-600m) aligns the given transcript with the audio (CTC forced alignment) and
 // prints its word timestamps in the format of --timestamps.  --align-head tdt aligns through the TDT head instead (the default stays ctc): the one
@@ -10,6 +11,9 @@
 // New: --score "text" (tdt-ctc-110m, tdt-600m) prints the log-likelihood of the given transcript under the TDT head (the forward algorithm on the
 // alignment's lattice).  --nbest N --rescore-tdt W (tdt-ctc-110m) prints the N best hypotheses of the CTC beam search re-ranked by
 // (1 - W) * CTC score + W * TDT log-likelihood, with both parts.
+// New: --spot "phrase" (repeatable) / --spot-file path.txt (one phrase per line) (tdt-ctc-110m) searches the audio for every phrase (CTC keyword
+// spotting) and prints one line per hit: phrase<TAB>start<TAB>end<TAB>score (seconds; score <= 0, 0 = the greedy path over the span is the phrase).
+// --spot-hits N: up to N non-overlapping hits per phrase (default 1); --spot-min-score X: only hits with score >= X (default: no threshold).
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
 #include <algorithm>
 #include <chrono>
@@ -34,6 +38,8 @@ static void usage(const char *prog) {
               << "  --align-head ctc|tdt  the head --align goes through (default: ctc; tdt needs no CTC head)\n"
               << "  --score \"text\"  log-likelihood of a known transcript under the TDT head\n"
               << "  --nbest N --rescore-tdt W  the N best hypotheses re-ranked by (1 - W) * CTC score + W * TDT log-likelihood\n"
+              << "  --spot \"phrase\" (repeatable) | --spot-file path.txt  where was each phrase said: phrase<TAB>start<TAB>end<TAB>score per hit\n"
+              << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
 }
@@ -82,6 +88,17 @@ static int run_score(T &t, const std::string &audio_path, const std::string &tex
     return 0;
 }
 
+// --spot: one line per hit, phrase<TAB>start<TAB>end<TAB>score, phrases in the order given, a phrase's hits best first
+template <class T>
+static int run_spot(T &t, const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &so) {
+    const auto hits = t.spot(audio_path, phrases, so);
+    std::cout << "Spotting: " << phrases.size() << " phrases\n";
+    for (size_t k = 0; k < phrases.size(); ++k)
+        for (const auto &h : hits[k])
+            std::cout << phrases[k] << '\t' << std::setprecision(9) << std::defaultfloat << h.start << '\t' << h.end << '\t' << h.score << "\n";
+    return 0;
+}
+
 template <class T>
 static int run_stream(T &t, const std::string &audio_path, bool timestamps) {
     t.to_gpu();
@@ -110,7 +127,8 @@ int main(int argc, char **argv) {
         bool use_ctc = false, timestamps = false, align = false, align_tdt = false, score = false, rescore = false, nbest_given = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
         float rescore_w = 0.5f;
-        std::vector<std::string> boost;
+        std::vector<std::string> boost, spot;
+        SpotOptions spot_opts;
         float boost_score = 5.0f;
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -139,6 +157,17 @@ int main(int argc, char **argv) {
             else if (a == "--nbest" && i + 1 < argc) { nbest = std::stoi(argv[++i]); nbest_given = true; }
             else if (a == "--score" && i + 1 < argc) { score_text = argv[++i]; score = true; }
             else if (a == "--rescore-tdt" && i + 1 < argc) { rescore_w = std::stof(argv[++i]); rescore = true; }
+            else if (a == "--spot" && i + 1 < argc) spot.push_back(argv[++i]);
+            else if (a == "--spot-file" && i + 1 < argc) {
+                std::ifstream f(argv[++i]);
+                if (!f) { std::cerr << "Error: cannot open " << argv[i] << "\n"; return 1; }
+                for (std::string line; std::getline(f, line);) {
+                    while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+                    if (!line.empty()) spot.push_back(line);
+                }
+            }
+            else if (a == "--spot-hits" && i + 1 < argc) spot_opts.max_hits = std::stoi(argv[++i]);
+            else if (a == "--spot-min-score" && i + 1 < argc) spot_opts.min_score = std::stof(argv[++i]);
             else if (a == "--prune" && i + 1 < argc) prune = std::stoi(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
@@ -159,6 +188,8 @@ int main(int argc, char **argv) {
         if (align && vocab.empty()) { std::cerr << "Error: --align needs --vocab\n"; return 1; }
         if (score && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --score needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (score && vocab.empty()) { std::cerr << "Error: --score needs --vocab\n"; return 1; }
+        if (!spot.empty() && model != "tdt-ctc-110m") { std::cerr << "Error: --spot needs a model with a CTC head (--model tdt-ctc-110m)\n"; return 1; }
+        if (!spot.empty() && vocab.empty()) { std::cerr << "Error: --spot needs --vocab\n"; return 1; }
         if (rescore && !nbest_given) { std::cerr << "Error: --rescore-tdt needs --nbest N\n"; return 1; }
         if (rescore && model != "tdt-ctc-110m") { std::cerr << "Error: --rescore-tdt needs a model with both heads (--model tdt-ctc-110m)\n"; return 1; }
         std::cout << "Loading model: " << model << std::endl;
@@ -167,6 +198,7 @@ int main(int argc, char **argv) {
             t.to_gpu();
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);
+            if (!spot.empty()) return run_spot(t, audio_path, spot, spot_opts);
             if (rescore) {                                          // the beam's list re-ranked by the TDT head; --beam W optional (default 8)
                 if (!boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
                 BeamOptions bo;

@@ -21,6 +21,7 @@
 #pragma once
 
 #include <algorithm>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -54,6 +55,19 @@ struct AlignResult : TranscribeResult {
     float score = 0.0f;
     float total = 0.0f;
     bool aligned = false;
+};
+/// New: one occurrence of a phrase found by Transcriber::spot (pk_spot_pcm): seconds from the start of the clip (end = the end of the last
+/// frame) and the score, the log-ratio of the phrase's best path over the span to the unconstrained best path over it (<= 0; 0: the greedy
+/// CTC path over the span is the phrase).
+struct SpotHit {
+    float start = 0.0f;
+    float end = 0.0f;
+    float score = 0.0f;
+};
+/// Parameters of Transcriber::spot (pk_kws_options).
+struct SpotOptions {
+    int max_hits = 1;                                               // hits per phrase, 1..16, best first, non-overlapping
+    float min_score = -std::numeric_limits<float>::infinity();      // report only hits with score >= min_score (<= 0); -inf: no threshold
 };
 /// Parameters of Transcriber::transcribe_nbest (pk_beam_options); TranscribeOptions is untouched.
 struct BeamOptions {
@@ -295,6 +309,34 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return run_align(pcm, (size_t)n, text, tdt_head);
     }
 
+    // pk_spot_pcm on one clip: every phrase (tokenised by the model's vocabulary) -> its hits, best first; single device
+    std::vector<std::vector<SpotHit>> run_spot(const float *pcm, size_t n, const std::vector<std::string> &phrases, const SpotOptions &opts) {
+        if (!on_gpu_) to_gpu(0);
+        std::vector<std::vector<SpotHit>> out(phrases.size());
+        if (phrases.empty()) return out;
+        const int64_t offsets[2] = {0, (int64_t)n};
+        std::vector<const char *> texts;
+        for (const auto &p : phrases) texts.push_back(p.c_str());
+        pk_kws_options o;
+        pk_kws_options_default(&o);
+        o.max_hits = opts.max_hits; o.min_score = opts.min_score;
+        const size_t K = phrases.size(), H = (size_t)(opts.max_hits > 0 ? opts.max_hits : 1);
+        std::vector<int32_t> n_hits(K);
+        std::vector<float> st(K * H), en(K * H), sc(K * H);
+        check(pk_spot_pcm(m_, pcm, offsets, 1, texts.data(), nullptr, nullptr, (int)K, &o, n_hits.data(), st.data(), en.data(), sc.data()));
+        for (size_t k = 0; k < K; ++k)
+            for (int j = 0; j < n_hits[k]; ++j) out[k].push_back({st[k * H + j], en[k * H + j], sc[k * H + j]});
+        return out;
+    }
+    std::vector<std::vector<SpotHit>> run_spot_file(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_spot(pcm, (size_t)n, phrases, opts);
+    }
+
     TranscribeResult run_file(const std::string &audio_path, const TranscribeOptions &opts) {
         float *pcm = nullptr;
         int64_t n = 0;
@@ -369,6 +411,17 @@ class Transcriber {
     AlignResult align(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text); }
     AlignResult align(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text); }
     AlignResult align(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text); }
+    /// New: CTC keyword spotting (pk_spot_pcm): where in the audio was each phrase said; result[k] = the hits of phrases[k], best first.
+    /// Needs the vocabulary.
+    std::vector<std::vector<SpotHit>> spot(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot_file(audio_path, phrases, opts);
+    }
+    std::vector<std::vector<SpotHit>> spot(const float *pcm, size_t n, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(pcm, n, phrases, opts);
+    }
+    std::vector<std::vector<SpotHit>> spot(const std::vector<float> &samples, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(samples.data(), samples.size(), phrases, opts);
+    }
     /// New: the same through the TDT head (pk_tdt_align_pcm): works without a CTC head.  AlignResult::total is 0.
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
@@ -440,6 +493,17 @@ class TDTTranscriber {
     AlignResult align(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text); }
     AlignResult align(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text); }
     AlignResult align(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text); }
+    /// New: CTC keyword spotting (pk_spot_pcm): where in the audio was each phrase said; result[k] = the hits of phrases[k], best first.
+    /// Needs the vocabulary and a model with a CTC head (the tdt-600m preset has none: the call throws).
+    std::vector<std::vector<SpotHit>> spot(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot_file(audio_path, phrases, opts);
+    }
+    std::vector<std::vector<SpotHit>> spot(const float *pcm, size_t n, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(pcm, n, phrases, opts);
+    }
+    std::vector<std::vector<SpotHit>> spot(const std::vector<float> &samples, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(samples.data(), samples.size(), phrases, opts);
+    }
     /// New: the same through the TDT head (pk_tdt_align_pcm): works without a CTC head.  AlignResult::total is 0.
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
