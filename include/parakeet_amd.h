@@ -352,6 +352,47 @@ pk_status pk_transcribe_pcm_nbest(pk_model *m, const float *pcm, const int64_t *
                                   pk_nbest **results);
 void pk_nbest_free(pk_nbest *results, int n_clips);
 
+/* ---- TDT beam search with n-best output ----------------------------------------------------------------------------------
+ * The other half of the reference's roadmap line "Beam search decoding -- CTC prefix beam search and TDT/RNNT beam search with configurable
+ * width" (README.md:494), for models whose only decoder is the TDT head (tdt-600m).  A max-path search over the lattice of DESIGN.md section
+ * 5.5.2: a hypothesis is one concrete path (token prefix, frame pointer, fp32 score = the path's left-to-right sum, each arc
+ * score + (label log-prob + duration log-prob)); two paths reaching the same (prefix, frame) are one state and the better one stays.  Every
+ * step, tie rule and the duplicate rule are specified in DESIGN.md section 5.5.5 (tests/tdt_beam_ref.py is that specification in Python; the
+ * device result equals it bit for bit).  max_symbols_per_step is not part of the search.  The score of a hypothesis is ONE alignment's
+ * log-probability, at most pk_tdt_align_decode's score for the same ids; pk_tdt_total_decode on the returned ids gives the log-likelihood
+ * summed over every alignment.  RNN-T heads, gemm_bf16, boosting inside the beam, language models, pk_group and streaming sessions: no variant. */
+typedef struct pk_tdt_beam_options {
+    int32_t beam_width;         /* W: hypotheses kept per step, 1..16 */
+    int32_t label_prune;        /* K: non-blank labels expanded per hypothesis (the K most probable) next to the blank, 1..16, clamped to V - 1 */
+    int32_t duration_prune;     /* Kd: durations expanded per label (the Kd most probable), 1..8, clamped to D */
+    int32_t n_best;             /* N: hypotheses returned per utterance, 1..beam_width */
+} pk_tdt_beam_options;
+/* The defaults W = 8, K = 8, Kd = 2, N = 1: choices, not measurements of accuracy or speed */
+void pk_tdt_beam_options_default(pk_tdt_beam_options *out);
+/* enc_proj once per clip, then the search on the model's stream (a host loop of ordinary launches with a hard cap of Tmax + max_tokens
+ * steps).  enc [B][T][hidden] resp. packed with n_frames[B].  Outputs: ids / start / end / dur_idx / conf [B][N][max_tokens] (start / end /
+ * dur_idx / conf optional) as pk_tdt_align defines them, lens / score [B][N], ok [B] (optional) = 0 when no hypothesis of the clip reached the
+ * last frame; hypotheses in beam order (scores descend), distinct token strings.  A slot the beam cannot fill has lens 0 and score -inf;
+ * unused token slots are 0.  A hypothesis holds at most max_tokens tokens.  opt == NULL: the defaults.  With W = K = Kd = 1 this is the greedy
+ * loop of pk_tdt_decode without its max_symbols_per_step.
+ * PK_ERR_UNSUPPORTED (before anything is allocated): a model without a TDT joint (RNN-T head, encoder only), gemm_bf16, a boost trie set,
+ * options out of range, or more than 1 GiB of scratch (formula: csrc/tdt_beam.hpp). */
+pk_status pk_tdt_beam_decode(pk_model *m, const float *enc, int B, int T, const pk_tdt_beam_options *opt, int max_tokens, int32_t *ids,
+                             int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, int32_t *ok);
+pk_status pk_tdt_beam_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const pk_tdt_beam_options *opt, int max_tokens,
+                                    int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf,
+                                    int32_t *ok);
+/* Stage timers (tools/bench_tdt_beam.py): the greedy TDT stage (enc_proj + the greedy loop, what pk_tdt_decode runs), then the search stage
+ * (enc_proj + the search + back-trace), each between hipEvents on the model's stream; medians of `reps` passes after one warm-up.  n_frames
+ * NULL: uniform [B][T].  ms[0] = greedy TDT stage, ms[1] = beam search stage. */
+pk_status pk_tdt_beam_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt,
+                                   int max_tokens, int reps, float ms[2]);
+/* One call from PCM to n-best through the TDT head: clips packed as pk_transcribe_pcm_nbest packs them, encoded, searched with
+ * max_tokens = (frames of the batch's longest clip) * max_symbols_per_step.  results as pk_transcribe_pcm_nbest fills them (timestamps != 0:
+ * start / end / confidence and words), score[j] the hypothesis's path log-probability; freed with pk_nbest_free. */
+pk_status pk_transcribe_pcm_nbest_tdt(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt,
+                                      int timestamps, pk_nbest **results);
+
 /* ---- CTC forced alignment of a GIVEN transcript ---------------------------------------------------------------------------
  * Given the log-probs and the token string that was said: when was each token said.  The alignment is the max-plus (Viterbi) path on the
  * 2 L + 1 state CTC lattice, specified operation by operation in DESIGN.md section 5.5.1 (tests/ctc_align_ref.py is that specification in

@@ -64,6 +64,10 @@ class PkBeamOptions(C.Structure):
     _fields_ = [("beam_width", C.c_int32), ("token_prune", C.c_int32), ("n_best", C.c_int32), ("timestamps", C.c_int32)]
 
 
+class PkTdtBeamOptions(C.Structure):
+    _fields_ = [("beam_width", C.c_int32), ("label_prune", C.c_int32), ("duration_prune", C.c_int32), ("n_best", C.c_int32)]
+
+
 class PkRescoreOptions(C.Structure):
     _fields_ = [("tdt_weight", C.c_float)]
 
@@ -185,12 +189,17 @@ _LATE_SIGNATURES = {
     "pk_group_last_stats": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), i32p],
     "pk_group_verify_exchange": [C.c_void_p, C.POINTER(PkResult), C.c_int, C.POINTER(C.c_int)],
     "pk_beam_options_default": [C.POINTER(PkBeamOptions)],
+    "pk_tdt_beam_options_default": [C.POINTER(PkTdtBeamOptions)],
     "pk_ctc_beam_search": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p],
     "pk_ctc_beam_decode": [C.c_void_p, f32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p],
     "pk_ctc_beam_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p],
     "pk_ctc_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), C.c_int, f32p],
     "pk_transcribe_pcm_nbest": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkBeamOptions), C.POINTER(C.POINTER(PkNbest))],
     "pk_nbest_free": [C.POINTER(PkNbest), C.c_int],
+    "pk_tdt_beam_decode": [C.c_void_p, f32p, C.c_int, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, i32p, i32p, f32p, i32p, i32p, i32p, f32p, i32p],
+    "pk_tdt_beam_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, i32p, i32p, f32p, i32p, i32p, i32p, f32p, i32p],
+    "pk_tdt_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, C.c_int, f32p],
+    "pk_transcribe_pcm_nbest_tdt": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, C.POINTER(C.POINTER(PkNbest))],
     "pk_ctc_align": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
     "pk_ctc_align_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
     "pk_ctc_align_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
@@ -279,6 +288,16 @@ def beam_options(beam_width=None, token_prune=None, n_best=None, timestamps=Fals
     if n_best is not None:
         o.n_best = n_best
     o.timestamps = 1 if timestamps else 0
+    return o
+
+
+def tdt_beam_options(beam_width=None, label_prune=None, duration_prune=None, n_best=None):
+    """pk_tdt_beam_options: the library's defaults (W = 8, K = 8, Kd = 2, N = 1) with the given fields replaced."""
+    o = PkTdtBeamOptions()
+    lib().pk_tdt_beam_options_default(C.byref(o))
+    for k, v in (("beam_width", beam_width), ("label_prune", label_prune), ("duration_prune", duration_prune), ("n_best", n_best)):
+        if v is not None:
+            setattr(o, k, v)
     return o
 
 
@@ -1814,6 +1833,58 @@ class Model:
         x = _c(enc)
         B, T, _ = x.shape
         return _beam_call(lib().pk_ctc_beam_decode, (self._h, _f(x), B, T), B, T, o)
+
+    def tdt_beam_decode(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None):
+        """pk_tdt_beam_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> dict of ids / start / end /
+        dur_idx / conf [B][N][max_tokens], lens / score [B][N], ok [B].  max_tokens None: (longest clip) * max_symbols_per_step."""
+        o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
+        rag, x, T = self._enc_head(enc)
+        B, N = len(T), max(1, o.n_best)
+        mt = int(max_tokens or int(T.max()) * self.cfg.max_symbols_per_step)
+        ids = np.zeros((B, N, mt), np.int32); st = np.zeros((B, N, mt), np.int32); en = np.zeros((B, N, mt), np.int32)
+        di = np.zeros((B, N, mt), np.int32); cf = np.zeros((B, N, mt), np.float32)
+        lens = np.zeros((B, N), np.int32); score = np.zeros((B, N), np.float32); ok = np.zeros(B, np.int32)
+        tail = (C.byref(o), mt, _i(ids), _i(lens), _f(score), _i(st), _i(en), _i(di), _f(cf), _i(ok))
+        if rag:
+            check(lib().pk_tdt_beam_decode_ragged(self._h, _f(x), _i(T), B, *tail))
+        else:
+            check(lib().pk_tdt_beam_decode(self._h, _f(x), x.shape[0], x.shape[1], *tail))
+        return dict(ids=ids, lens=lens, score=score, start=st, end=en, dur_idx=di, conf=cf, ok=ok)
+
+    def tdt_beam_decode_timed(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None, reps=5):
+        """pk_tdt_beam_decode_timed -> (greedy TDT stage ms, beam search stage ms), HIP events, medians of reps passes."""
+        o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
+        rag, x, T = self._enc_head(enc)
+        mt = int(max_tokens or int(T.max()) * self.cfg.max_symbols_per_step)
+        ms = np.zeros(2, np.float32)
+        check(lib().pk_tdt_beam_decode_timed(self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], C.byref(o), mt, reps, _f(ms)))
+        return float(ms[0]), float(ms[1])
+
+    def transcribe_nbest_tdt(self, clips, beam_width=None, label_prune=None, duration_prune=None, n_best=None, timestamps=False):
+        """pk_transcribe_pcm_nbest_tdt: per clip a list of hypotheses through the TDT head, best first: dicts as transcribe_nbest returns them."""
+        if isinstance(clips, tuple):
+            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
+        else:
+            pcm, off = pack_clips(clips)
+        n = len(off) - 1
+        o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
+        res = C.POINTER(PkNbest)()
+        check(lib().pk_transcribe_pcm_nbest_tdt(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res)))
+        out = []
+        for i in range(n):
+            hyps = []
+            for j in range(res[i].n_hyp):
+                r = res[i].hyp[j]
+                d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]))
+                if timestamps:
+                    d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
+                    d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
+                    d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
+                    d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
+                hyps.append(d)
+            out.append(hyps)
+        lib().pk_nbest_free(res, n)
+        return out
 
     def ctc_align_decode(self, enc, ids, total=True):
         """pk_ctc_align_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_align."""

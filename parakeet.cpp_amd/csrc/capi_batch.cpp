@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_batch.cpp -- the resident two-stream batch pipeline (pk_batch_*) and the one-call API on top of it:
-// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest(_rescored), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm, pk_spot_pcm and the result stores they hand out.
+// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest(_rescored, _tdt), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm, pk_spot_pcm and the result stores they hand out.
 #include <algorithm>
 #include <cstring>
 
@@ -991,6 +991,72 @@ pk_status pk_transcribe_pcm_nbest_rescored(pk_model *h, const float *pcm, const 
         if (m.cfg.ctc_vocab_size != m.cfg.vocab_size)
             fail(PK_ERR_UNSUPPORTED, "the CTC head (%d) and the TDT head (%d) of this model do not share a vocabulary", m.cfg.ctc_vocab_size, m.cfg.vocab_size);
         nbest_pcm(m, pcm, offsets, n_clips, beam_opt, &w, results, ctc_score, tdt_total);
+    });
+}
+
+// The body of pk_transcribe_pcm_nbest_tdt: the batches of pk_transcribe_pcm_nbest; every batch is searched through the TDT head (tdt_beam.hpp) on
+// its encoder rows, enc_proj once per batch.
+static void nbest_tdt_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt, bool ts, pk_nbest **results) {
+    const pk_tdt_beam_options o = tdt_beam_options_of(opt);
+    tdt_beam_model_checks(m, o);
+    m.require_gpu();
+    const int N = o.n_best;
+    auto store = std::make_unique<NbestStore>();
+    store->out.resize((size_t)n_clips + 1); store->clip.resize(n_clips); store->score.resize(n_clips);
+    std::vector<int64_t> clip_len(n_clips);
+    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+    std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
+    plan_batches(clip_len.data(), n_clips, order, bstart);
+    std::vector<int32_t> ids, lens, st, en;
+    std::vector<float> sc, cf;
+    const float NEGF = -__builtin_huge_valf();
+    const int sym = m.cfg.max_symbols_per_step > 0 ? m.cfg.max_symbols_per_step : 10;
+    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+        RagBatch r;
+        int MT = 0;
+        encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
+            MT = rb.T_max * sym;
+            tdt_beam_plan(m.tbeam, m, rb.T.data(), nc, 0, o, MT);       // (refuses before the batch is allocated or queued)
+        }, /*ctc=*/false);
+        m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
+        run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream);
+        PK_CHECK_LAUNCH();
+        const size_t hyps = (size_t)nc * N, tok = hyps * MT;
+        ids.resize(tok); lens.resize(hyps); sc.resize(hyps);
+        if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
+        tdt_beam_copy_out(m.tbeam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, nullptr, ts ? cf.data() : nullptr,
+                          nullptr, m.stream);
+        for (int i = 0; i < nc; ++i) {
+            const int c = order[c0 + i];
+            int nh = 0;
+            while (nh < N && sc[(size_t)i * N + nh] > NEGF) ++nh;
+            store->clip[c] = new_store(nh);
+            ResultStore &R = *store->clip[c];
+            store->score[c].resize(nh);
+            for (int j = 0; j < nh; ++j) {
+                const size_t hy = (size_t)i * N + j, o0 = hy * MT;
+                store->score[c][j] = sc[hy];
+                store_tokens(m, R, j, lens[hy], ids.data() + o0, ts ? st.data() + o0 : nullptr, ts ? en.data() + o0 : nullptr, ts ? cf.data() + o0 : nullptr);
+            }
+            point_results(R, nh, ts);
+            store->out[c].n_hyp = nh;
+            store->out[c].hyp = R.res.data();
+            store->out[c].score = store->score[c].data();
+        }
+    }
+    pk_nbest &tail = store->out[n_clips];
+    tail.n_hyp = 0; tail.score = nullptr;
+    tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
+    *results = store->out.data();
+    store.release();
+}
+
+pk_status pk_transcribe_pcm_nbest_tdt(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt,
+                                      int timestamps, pk_nbest **results) {
+    return guard([&] {
+        need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
+        nbest_tdt_pcm(*h->m, pcm, offsets, n_clips, opt, timestamps != 0, results);
     });
 }
 

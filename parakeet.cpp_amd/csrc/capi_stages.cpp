@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_stages.cpp -- the stage entry points of the C boundary on caller buffers: mel, subsample, encode, conformer blocks,
-// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix beam search, the CTC and TDT forced alignments and the CTC keyword spotting.
+// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix and TDT beam searches, the CTC and TDT forced alignments and the CTC keyword spotting.
 #include <algorithm>
 #include <cstring>
 
@@ -496,6 +496,82 @@ pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t 
             m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
             PK_HIP(hipEventRecord(ev.e[1], m.stream));
             run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, rag, V, blank, o, m.stream);
+            PK_HIP(hipEventRecord(ev.e[2], m.stream));
+            PK_HIP(hipStreamSynchronize(m.stream));
+            PK_CHECK_LAUNCH();
+            float a = 0, b = 0;
+            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+            if (r > 0) { greedy.push_back(a); beam.push_back(b); }
+        }
+        std::sort(greedy.begin(), greedy.end()); std::sort(beam.begin(), beam.end());
+        ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
+    });
+}
+
+/* ---- TDT beam search (kernels/tdt_beam.hip; reference roadmap README.md:494) ----------------------------------------------------- */
+void pk_tdt_beam_options_default(pk_tdt_beam_options *out) {
+    if (!out) return;
+    out->beam_width = 8; out->label_prune = 8; out->duration_prune = 2; out->n_best = 1;
+}
+
+// checks and sizes one search (host only: every refusal comes before anything is allocated)
+static void tdt_beam_checks(Model &m, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options &o, int max_tokens) {
+    tdt_beam_model_checks(m, o);
+    if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+    m.require_gpu();
+    tdt_beam_plan(m.tbeam, m, n_frames, B, T, o, max_tokens);
+}
+
+static void tdt_beam_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt, int max_tokens, int32_t *ids,
+                            int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, int32_t *ok) {
+    const pk_tdt_beam_options o = tdt_beam_options_of(opt);
+    tdt_beam_checks(m, n_frames, B, T, o, max_tokens);
+    size_t rows;
+    size_ws(m, n_frames, B, T, rows);
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
+    run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream);
+    PK_CHECK_LAUNCH();
+    tdt_beam_copy_out(m.tbeam, ids, lens, score, start, end, dur_idx, conf, ok, m.stream);
+}
+
+pk_status pk_tdt_beam_decode(pk_model *h, const float *enc, int B, int T, const pk_tdt_beam_options *opt, int max_tokens, int32_t *ids,
+                             int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && ids && lens && score && B > 0 && T > 0 && max_tokens > 0, "model/enc/ids/lens/score/B/T/max_tokens");
+        tdt_beam_decode(*h->m, enc, nullptr, B, T, opt, max_tokens, ids, lens, score, start, end, dur_idx, conf, ok);
+    });
+}
+
+pk_status pk_tdt_beam_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const pk_tdt_beam_options *opt, int max_tokens,
+                                    int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf,
+                                    int32_t *ok) {
+    return guard([&] {
+        need(h && enc && n_frames && ids && lens && score && B > 0 && max_tokens > 0, "model/enc/n_frames/ids/lens/score/B/max_tokens");
+        tdt_beam_decode(*h->m, enc, n_frames, B, 0, opt, max_tokens, ids, lens, score, start, end, dur_idx, conf, ok);
+    });
+}
+
+pk_status pk_tdt_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt,
+                                   int max_tokens, int reps, float ms[2]) {
+    return guard([&] {
+        need(h && enc && ms && B > 0 && reps > 0 && max_tokens > 0 && (n_frames || T > 0), "model/enc/ms/B/T/max_tokens/reps");
+        Model &m = *h->m;
+        const pk_tdt_beam_options o = tdt_beam_options_of(opt);
+        tdt_beam_checks(m, n_frames, B, T, o, max_tokens);
+        size_t rows;
+        T = size_ws(m, n_frames, B, T, rows);
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        std::vector<float> greedy, beam;
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+            m.run_tdt(m.ws, m.ws.x.as<float>(), B, T, m.ws.max_tokens, m.stream);
+            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
+            run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream);
             PK_HIP(hipEventRecord(ev.e[2], m.stream));
             PK_HIP(hipStreamSynchronize(m.stream));
             PK_CHECK_LAUNCH();

@@ -18,6 +18,7 @@
 #include "kernels/kernels.hpp"
 #include "safetensors.hpp"
 #include "tdt_align.hpp"
+#include "tdt_beam.hpp"
 #include "tdt_total.hpp"
 #include "text.hpp"
 
@@ -241,6 +242,7 @@ class Model {
     KwsWs kws;          // scratch and results of the CTC keyword-spotting entry points (ctc_kws.hpp)
     TdtAlignWs talign;  // scratch and results of the TDT forced-alignment entry points (tdt_align.hpp)
     TdtTotalWs ttotal;  // scratch and results of the TDT total / rescoring entry points (tdt_total.hpp)
+    TdtBeamWs tbeam;    // scratch and results of the TDT beam search entry points (tdt_beam.hpp)
     int decode_loop = PK_DECODE_LOOP_PHASES;   // pk_model_set_decode_loop: how run_tdt_loop issues the greedy loop
     int *h_done = nullptr;   // pinned host word for the decode loop's "all utterances finished" poll
     // the two-stream batch pipeline of the one-call API (struct pk_batch, capi_batch.cpp), owned by the model; freed first in ~Model

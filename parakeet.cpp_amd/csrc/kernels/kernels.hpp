@@ -520,6 +520,38 @@ struct TdtTotalArgs {
 };
 void launch_tdt_total(const TdtTotalArgs &a, hipStream_t s);
 
+// TDT beam search with n-best output (kernels/tdt_beam.hip).  R = B W rows, beam slot w of clip b is row b W + w.  The
+// beam exists in two copies (step s reads copy s & 1 and writes the other): every per-row array below is [2][R].
+constexpr int kTdtBeamMaxWidth = 16, kTdtBeamMaxLabels = 16, kTdtBeamMaxDurs = 8;
+struct TdtBeamDev {
+    int B, W, K, Kd, N, V, D, blank, max_tokens, J, L, Hp;
+    int durations[8];
+    const int *T, *row0;                        // [B]: frames, first enc_proj row
+    int *valid, *t, *len, *par, *born, *tok;    // the beam: slot filled, frame pointer, tokens, parent row, born from a label arc (its token: tok, else the blank)
+    float *score;
+    unsigned long long *hash;                   // of the token string (a filter in front of the exact comparison)
+    int *prefix;                                // [2][R][max_tokens] token strings
+    int *lab_id; float *lab_lp;                 // [R][K + 1] the row's K best labels and the blank, sorted (id -1: no such label)
+    int *dur_i; float *dur_lp;                  // [R][Kd] the row's best durations, sorted
+    float *cand;                                // [R][(K + 1) Kd] candidate scores, label rank then duration rank
+    int4 *bp;                                   // [steps][R] per step and new slot: parent slot, token or -1, emission frame * 8 + duration index, label log-prob bits
+    int *live, *steps_done;                     // [B] live hypotheses of the clip's beam, steps the clip has taken
+    int *live_total;                            // [step cap + 1] live hypotheses of the batch after s steps (zeroed by the host)
+    float *hG[2], *cG[2], *ppG[2];              // gathered state of step s in copy s & 1: h, c [L][R][Hp] (h in the sigma layout), pred_proj [R][J]
+    float *hN, *cN, *ppN;                       // the prediction-net step's outputs on the gathered state
+};
+struct TdtBeamOut {
+    int *ids, *start, *end, *dur_idx; float *conf;      // [B][N][max_tokens], zero-filled by the caller
+    int *lens; float *score;                            // [B][N]
+    int *ok;                                            // [B]
+};
+void launch_tdt_beam_init(const TdtBeamDev &a, hipStream_t s);
+void launch_tdt_beam_gather(const TdtBeamDev &a, int step, hipStream_t s);
+void launch_tdt_beam_act(const TdtBeamDev &a, int step, const float *ep, float *z, hipStream_t s);
+void launch_tdt_beam_expand(const TdtBeamDev &a, int step, const float *logits, hipStream_t s);
+void launch_tdt_beam_prune(const TdtBeamDev &a, int step, hipStream_t s);
+void launch_tdt_beam_trace(const TdtBeamDev &a, const TdtBeamOut &o, hipStream_t s);
+
 struct TdtState {
     int B, T, V, D, L, Hp, blank, max_symbols, max_tokens, max_steps;
     TrieDev trie;

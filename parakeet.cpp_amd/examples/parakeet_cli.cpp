@@ -1,7 +1,7 @@
 // examples/parakeet_cli.cpp -- the reference's command line (src/main.cpp:12-37, :642-727) on the MI355X engine: same positional
 // arguments, --model types and options; every model type runs through the drop-in facade classes.
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
-//                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K]]
+//                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K] [--beam-head ctc|tdt]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
 //                [--spot "phrase"]... [--spot-file path.txt] [--spot-hits N] [--spot-min-score X]
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
@@ -35,6 +35,7 @@ static void usage(const char *prog) {
               << "  --ctc | --tdt | --decoder ctc|tdt  decoder (default: TDT)\n"
               << "  --beam W [--nbest N] [--prune K]  CTC prefix beam search (needs the CTC decoder), N best hypotheses\n"
               << "  --align \"text\" | --align-file path.txt  CTC forced alignment of a known transcript: its word timestamps\n"
+              << "  --beam W --beam-head tdt [--nbest N]  TDT beam search (tdt-ctc-110m, tdt-600m), N best hypotheses with path scores\n"
               << "  --align-head ctc|tdt  the head --align goes through (default: ctc; tdt needs no CTC head)\n"
               << "  --score \"text\"  log-likelihood of a known transcript under the TDT head\n"
               << "  --nbest N --rescore-tdt W  the N best hypotheses re-ranked by (1 - W) * CTC score + W * TDT log-likelihood\n"
@@ -124,7 +125,7 @@ int main(int argc, char **argv) {
     try {
         const std::string weights = argv[1], audio_path = argv[2];
         std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text, score_text;
-        bool use_ctc = false, timestamps = false, align = false, align_tdt = false, score = false, rescore = false, nbest_given = false;
+        bool use_ctc = false, timestamps = false, align = false, align_tdt = false, beam_tdt = false, score = false, rescore = false, nbest_given = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
         float rescore_w = 0.5f;
         std::vector<std::string> boost, spot;
@@ -153,6 +154,11 @@ int main(int argc, char **argv) {
                 const std::string hd = argv[++i];
                 if (hd != "ctc" && hd != "tdt") { std::cerr << "Unknown alignment head: " << hd << "\n"; return 1; }
                 align_tdt = hd == "tdt";
+            }
+            else if (a == "--beam-head" && i + 1 < argc) {
+                const std::string hd = argv[++i];
+                if (hd != "ctc" && hd != "tdt") { std::cerr << "Unknown beam head: " << hd << "\n"; return 1; }
+                beam_tdt = hd == "tdt";
             }
             else if (a == "--nbest" && i + 1 < argc) { nbest = std::stoi(argv[++i]); nbest_given = true; }
             else if (a == "--score" && i + 1 < argc) { score_text = argv[++i]; score = true; }
@@ -192,6 +198,19 @@ int main(int argc, char **argv) {
         if (!spot.empty() && vocab.empty()) { std::cerr << "Error: --spot needs --vocab\n"; return 1; }
         if (rescore && !nbest_given) { std::cerr << "Error: --rescore-tdt needs --nbest N\n"; return 1; }
         if (rescore && model != "tdt-ctc-110m") { std::cerr << "Error: --rescore-tdt needs a model with both heads (--model tdt-ctc-110m)\n"; return 1; }
+        if (beam_tdt && beam <= 0) { std::cerr << "Error: --beam-head needs --beam W\n"; return 1; }
+        if (beam_tdt && !boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
+        // --beam W --beam-head tdt: the TDT beam search's N best hypotheses, each with its path log-probability
+        auto print_tdt_beam = [&](const std::vector<ScoredResult> &hyps, double ms) {
+            std::cout << "Beam search (tdt): width " << beam << ", " << hyps.size() << " hypotheses\n";
+            for (size_t j = 0; j < hyps.size(); ++j) {
+                std::cout << "\n=== Hypothesis " << j << " score " << std::setprecision(9) << std::defaultfloat << hyps[j].score << " ===\n";
+                print_result(hyps[j].result, timestamps, ms);
+            }
+            return 0;
+        };
+        TdtBeamOptions tbo;
+        tbo.beam_width = beam; tbo.n_best = nbest; tbo.timestamps = timestamps;
         std::cout << "Loading model: " << model << std::endl;
         if (model == "tdt-ctc-110m") {
             Transcriber t(weights, vocab);
@@ -213,6 +232,11 @@ int main(int argc, char **argv) {
                 return 0;
             }
             if (!boost.empty()) std::cout << "Phrase boost: " << boost.size() << " phrases\n";
+            if (beam > 0 && beam_tdt) {
+                const auto t0 = Clock::now();
+                const auto hyps = t.transcribe_nbest_tdt(audio_path, tbo);
+                return print_tdt_beam(hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+            }
             if (beam > 0) {
                 if (!use_ctc) { std::cerr << "Error: --beam needs the CTC decoder (--ctc / --decoder ctc)\n"; return 1; }
                 if (!boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
@@ -236,6 +260,12 @@ int main(int argc, char **argv) {
             t.to_gpu();
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);
+            if (beam > 0) {
+                if (!beam_tdt) { std::cerr << "Error: this model has no CTC head: --beam needs --beam-head tdt\n"; return 1; }
+                const auto t0 = Clock::now();
+                const auto hyps = t.transcribe_nbest(audio_path, tbo);
+                return print_tdt_beam(hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+            }
             const auto t0 = Clock::now();
             const auto r = t.transcribe(audio_path, opts);
             print_result(r, timestamps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());

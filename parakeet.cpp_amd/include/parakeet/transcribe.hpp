@@ -77,6 +77,15 @@ struct BeamOptions {
     bool timestamps = false;
 };
 
+/// New: parameters of TDTTranscriber::transcribe_nbest (pk_tdt_beam_options).
+struct TdtBeamOptions {
+    int beam_width = 8;      // hypotheses kept per step, 1..16
+    int label_prune = 8;     // most probable non-blank labels expanded per hypothesis, 1..16
+    int duration_prune = 2;  // most probable durations expanded per label, 1..8
+    int n_best = 1;          // hypotheses returned, 1..beam_width
+    bool timestamps = false;
+};
+
 /// New: parameters of the TDT rescoring of an n-best list (pk_rescore_options).
 struct RescoreOptions {
     float tdt_weight = 0.5f;   // w: hypotheses are ordered by (1 - w) * CTC score + w * TDT log-likelihood
@@ -216,6 +225,40 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
         struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
         return run_nbest(pcm, (size_t)n, opts);
+    }
+
+    // pk_transcribe_pcm_nbest_tdt on one clip: the TDT beam search's hypotheses, best first; score is the path's log-probability
+    std::vector<ScoredResult> run_nbest_tdt(const float *pcm, size_t n, const TdtBeamOptions &opts) {
+        if (!on_gpu_) to_gpu(0);
+        pk_tdt_beam_options o;
+        pk_tdt_beam_options_default(&o);
+        o.beam_width = opts.beam_width; o.label_prune = opts.label_prune; o.duration_prune = opts.duration_prune; o.n_best = opts.n_best;
+        const int64_t offsets[2] = {0, (int64_t)n};
+        pk_nbest *res = nullptr;
+        check(pk_transcribe_pcm_nbest_tdt(m_, pcm, offsets, 1, &o, opts.timestamps ? 1 : 0, &res));
+        std::vector<ScoredResult> out(res[0].n_hyp);
+        for (int j = 0; j < res[0].n_hyp; ++j) {
+            const pk_result &r = res[0].hyp[j];
+            out[j].score = res[0].score[j];
+            out[j].result.text = r.text ? r.text : "";
+            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
+            if (opts.timestamps) {
+                for (int k = 0; k < r.n_tokens; ++k)
+                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
+                for (int k = 0; k < r.n_words; ++k)
+                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
+            }
+        }
+        pk_nbest_free(res, 1);
+        return out;
+    }
+    std::vector<ScoredResult> run_nbest_tdt_file(const std::string &audio_path, const TdtBeamOptions &opts) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_nbest_tdt(pcm, (size_t)n, opts);
     }
 
     // pk_transcribe_pcm_nbest_rescored on one clip: run_nbest's list re-ranked by the TDT head's log-likelihood of every hypothesis
@@ -426,6 +469,9 @@ class Transcriber {
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
     AlignResult align_tdt(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text, true); }
+    /// New: the same search through this model's TDT head (TDTTranscriber::transcribe_nbest)
+    std::vector<ScoredResult> transcribe_nbest_tdt(const std::string &audio_path, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt_file(audio_path, opts); }
+    std::vector<ScoredResult> transcribe_nbest_tdt(const float *pcm, size_t n, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt(pcm, n, opts); }
     /// New: the log-likelihood of a given transcript: tdt_head = true through the TDT head's forward algorithm
     /// (pk_tdt_score_pcm; no CTC head needed).  false throws std::invalid_argument: the CTC head's log-likelihood is align()'s AlignResult::total.
     ScoreResult score(const std::string &audio_path, const std::string &text, bool tdt_head = true) { return eng_.run_score_file(audio_path, text, tdt_head); }
@@ -508,6 +554,12 @@ class TDTTranscriber {
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
     AlignResult align_tdt(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text, true); }
+    /// New: TDT beam search with n-best output: hypotheses best first, score = the path's log-probability.
+    std::vector<ScoredResult> transcribe_nbest(const std::string &audio_path, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt_file(audio_path, opts); }
+    std::vector<ScoredResult> transcribe_nbest(const float *pcm, size_t n, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt(pcm, n, opts); }
+    std::vector<ScoredResult> transcribe_nbest(const std::vector<float> &samples, const TdtBeamOptions &opts = {}) {
+        return eng_.run_nbest_tdt(samples.data(), samples.size(), opts);
+    }
     /// New: the log-likelihood of a given transcript: tdt_head = true through the TDT head's forward algorithm
     /// (pk_tdt_score_pcm; no CTC head needed).  false throws std::invalid_argument: the CTC head's log-likelihood is align()'s AlignResult::total.
     ScoreResult score(const std::string &audio_path, const std::string &text, bool tdt_head = true) { return eng_.run_score_file(audio_path, text, tdt_head); }
