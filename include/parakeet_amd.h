@@ -310,7 +310,7 @@ void pk_results_free(pk_result *results, int n_clips);
  * its "N-gram LM shallow fusion" :495 and "Neural LM rescoring -- N-best reranking" :514 lines, which need an n-best list with scores).  The search, its per-frame token pruning, every tie rule and the
  * forced alignment that gives a hypothesis its timestamps are specified operation by operation in DESIGN.md section 5.5
  * (tests/ctc_beam_ref.py is that specification in Python; the device result equals it bit for bit).  All of it runs on the device
- * (kernels/ctc_beam.hip).  No language model, no phrase boost inside the beam; pk_group and streaming sessions have no beam variant. */
+ * (kernels/ctc_beam.hip).  No phrase boost inside the beam (a language model: the _lm entry points below); pk_group and streaming sessions have no beam variant. */
 typedef struct pk_beam_options {
     int32_t beam_width;         /* W: prefixes kept per frame, 1..32 */
     int32_t token_prune;        /* K: non-blank tokens considered per frame (the K most probable), 1..32, clamped to V - 1 */
@@ -351,6 +351,67 @@ typedef struct pk_nbest {
 pk_status pk_transcribe_pcm_nbest(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
                                   pk_nbest **results);
 void pk_nbest_free(pk_nbest *results, int n_clips);
+
+/* ---- N-gram language-model shallow fusion of the CTC prefix beam search ---------------------------------------------------
+ * The reference's roadmap line "N-gram LM shallow fusion: load ARPA language models, score partial hypotheses during beam search"
+ * (README.md:495).  A back-off n-gram model over the acoustic model's TOKEN IDS (the words of the ARPA text are decimal ids, "17", plus <s>,
+ * </s> and <unk>: what an n-gram trainer makes of tools/make_token_corpus.py's output), orders 1..5, log10 values, a missing back-off
+ * column is 0; probabilities are not checked for normalisation.  Every value is converted once (strtod -> * 2.302585092994046 in double ->
+ * fp32): natural-log fp32 is what everything below sees.  The model compiles to a back-off automaton, and
+ *   lookup(s, c): acc = 0; while (s, c) has no arc and s is not the empty context: acc = acc + backoff_weight[s], s = backoff[s];
+ *                 -> acc + p(arc) and the arc's next state; a miss in the empty context scores <unk>'s unigram and goes to the empty context
+ * is the one scoring rule of pk_lm_score and of the fused search (tests/ngram_lm_ref.py and tests/ctc_beam_lm_ref.py
+ * are the specification in Python; host and device results equal them bit for bit).  Word-level models, binary KenLM files, neural models,
+ * the </s> term inside the search, fusion inside the TDT beam (rescore its n-best list with pk_lm_score), pk_group / streaming variants and
+ * boosting together with a model: no variant. */
+typedef struct pk_lm pk_lm;
+/* Parses and compiles ARPA text from a file resp. from n_bytes of memory (no terminator needed).  Host only.  PK_ERR_INVALID with the line
+ * named in pk_last_error for: a word that is neither a decimal id nor <s> / </s> / <unk>; an id >= 2^24; "ngram k=" counts that disagree with
+ * the sections (or an order past 5); an n-gram whose first k - 1 words are not an entry themselves; a duplicate n-gram; a value that is not a
+ * finite number; an id without a unigram in a model without <unk>; text that ends before \end\.  PK_ERR_IO when the file cannot be read. */
+pk_status pk_lm_load(const char *path, pk_lm **out);
+pk_status pk_lm_load_buffer(const char *text, size_t n_bytes, pk_lm **out);
+/* Frees the model and its device copies (one per device, made on the first fused search there). */
+void pk_lm_free(pk_lm *lm);
+int pk_lm_order(const pk_lm *lm);                       /* 1..5; 0 for NULL */
+int64_t pk_lm_num_ngrams(const pk_lm *lm);              /* entries of all orders */
+/* Host only, no device: logp[i] = the fp32 left-to-right sum of lookup over string i = ids[id_offsets[i] .. id_offsets[i + 1]), from the
+ * context <s> with bos != 0 (when the file has <s>; else, and with bos == 0, from the empty context), plus the </s> term with eos != 0.  An
+ * empty string scores 0 (resp. its </s> term).  What a caller rescores an n-best list with, the TDT beam's included.  PK_ERR_INVALID for a
+ * negative id, an id >= 2^24, or an id without a unigram under a model without <unk>. */
+pk_status pk_lm_score(const pk_lm *lm, const int32_t *ids, const int32_t *id_offsets, int n_strings, int bos, int eos, float *logp);
+typedef struct pk_lm_options {
+    float alpha;                /* weight of the model's log-probability */
+    float beta;                 /* added per token (a length reward when positive) */
+} pk_lm_options;
+/* alpha = 0.5, beta = 0.0: a choice, not a measurement of accuracy on any data */
+void pk_lm_options_default(pk_lm_options *out);
+/* The entry points of the unfused search with a model: the arguments of pk_ctc_beam_search / _decode / _decode_ragged / _decode_timed resp.
+ * pk_transcribe_pcm_nbest, then the model, its weights (NULL: the defaults) and one more output, lm_score [B][N] (optional).  A beam entry
+ * carries the automaton's state after its prefix and the prefix's LM score lm (start: the start state, 0); extending by token c:
+ * (lp, s2) = lookup(state, c), lm2 = lm + ((alpha * lp) + beta), three separately rounded fp32 operations.  A candidate is selectable exactly
+ * when the unfused search selects it, and ranks by score + lm (one fp32 add) where the unfused search ranks by score; token pruning stays
+ * acoustic, merges are the unfused search's (lm is a function of the token string alone), </s> is never proposed.  Hypotheses come back in fused
+ * order; score keeps its meaning (the prefix's acoustic log-probability), lm_score is lm; a slot the beam cannot fill has lm_score 0.
+ * Refusals beyond the unfused entry point's: PK_ERR_INVALID for lm == NULL, a non-finite alpha or beta, a model that names the blank id or an
+ * id >= V, or one with neither <unk> nor a unigram for every non-blank id of the vocabulary. */
+pk_status pk_ctc_beam_search_lm(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
+                                int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf, const pk_lm *lm,
+                                const pk_lm_options *lm_opt, float *lm_score);
+/* PK_ERR_UNSUPPORTED for a model without a CTC head or with a boost trie set, as pk_ctc_beam_decode. */
+pk_status pk_ctc_beam_decode_lm(pk_model *m, const float *enc, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
+                                float *score, int32_t *start, int32_t *end, float *conf, const pk_lm *lm, const pk_lm_options *lm_opt,
+                                float *lm_score);
+pk_status pk_ctc_beam_decode_lm_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const pk_beam_options *opt, int32_t *ids,
+                                       int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf, const pk_lm *lm,
+                                       const pk_lm_options *lm_opt, float *lm_score);
+/* Stage timers as pk_ctc_beam_decode_timed (tools/bench_ctc_beam_lm.py): ms[1] = top-K + fused walk + back-trace / alignment. */
+pk_status pk_ctc_beam_decode_lm_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
+                                      float ms[2], const pk_lm *lm, const pk_lm_options *lm_opt);
+/* pk_transcribe_pcm_nbest through the fused search: results[i].score[j] stays the acoustic score, lm_score (optional, [n_clips][N], N =
+ * opt->n_best) takes the LM scores beside it: lm_score[i * N + j] belongs to results[i].hyp[j], slots past n_hyp read 0.  pk_nbest is unchanged. */
+pk_status pk_transcribe_pcm_nbest_lm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
+                                     pk_nbest **results, const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score);
 
 /* ---- TDT beam search with n-best output ----------------------------------------------------------------------------------
  * The other half of the reference's roadmap line "Beam search decoding -- CTC prefix beam search and TDT/RNNT beam search with configurable

@@ -80,6 +80,10 @@ class PkNbest(C.Structure):
     _fields_ = [("n_hyp", C.c_int32), ("hyp", C.POINTER(PkResult)), ("score", f32p)]
 
 
+class PkLmOptions(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("beta", C.c_float)]
+
+
 def to_pk_config(cfg: ModelConfig) -> PkConfig:
     c = PkConfig()
     c.mel_bins, c.subsampling_channels, c.hidden_size = cfg.mel_bins, cfg.subsampling_channels, cfg.hidden_size
@@ -196,6 +200,22 @@ _LATE_SIGNATURES = {
     "pk_ctc_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), C.c_int, f32p],
     "pk_transcribe_pcm_nbest": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkBeamOptions), C.POINTER(C.POINTER(PkNbest))],
     "pk_nbest_free": [C.POINTER(PkNbest), C.c_int],
+    "pk_lm_load": [C.c_char_p, C.POINTER(C.c_void_p)],
+    "pk_lm_load_buffer": [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)],
+    "pk_lm_free": [C.c_void_p],
+    "pk_lm_order": [C.c_void_p],
+    "pk_lm_num_ngrams": [C.c_void_p],
+    "pk_lm_score": [C.c_void_p, i32p, i32p, C.c_int, C.c_int, C.c_int, f32p],
+    "pk_lm_options_default": [C.POINTER(PkLmOptions)],
+    "pk_ctc_beam_search_lm": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p,
+                              C.c_void_p, C.POINTER(PkLmOptions), f32p],
+    "pk_ctc_beam_decode_lm": [C.c_void_p, f32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p,
+                              C.c_void_p, C.POINTER(PkLmOptions), f32p],
+    "pk_ctc_beam_decode_lm_ragged": [C.c_void_p, f32p, i32p, C.c_int, C.POINTER(PkBeamOptions), i32p, i32p, f32p, i32p, i32p, f32p,
+                                     C.c_void_p, C.POINTER(PkLmOptions), f32p],
+    "pk_ctc_beam_decode_lm_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), C.c_int, f32p, C.c_void_p, C.POINTER(PkLmOptions)],
+    "pk_transcribe_pcm_nbest_lm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkBeamOptions), C.POINTER(C.POINTER(PkNbest)),
+                                   C.c_void_p, C.POINTER(PkLmOptions), f32p],
     "pk_tdt_beam_decode": [C.c_void_p, f32p, C.c_int, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, i32p, i32p, f32p, i32p, i32p, i32p, f32p, i32p],
     "pk_tdt_beam_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, i32p, i32p, f32p, i32p, i32p, i32p, f32p, i32p],
     "pk_tdt_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, C.c_int, f32p],
@@ -301,25 +321,92 @@ def tdt_beam_options(beam_width=None, label_prune=None, duration_prune=None, n_b
     return o
 
 
-def _beam_call(fn, head, B, tmax, o):
+def lm_options(alpha=None, beta=None):
+    """pk_lm_options: the library's defaults (alpha = 0.5, beta = 0.0) with the given fields replaced."""
+    o = PkLmOptions()
+    lib().pk_lm_options_default(C.byref(o))
+    if alpha is not None:
+        o.alpha = alpha
+    if beta is not None:
+        o.beta = beta
+    return o
+
+
+class Lm:
+    """pk_lm: a back-off n-gram language model over token ids (ARPA text; include/parakeet_amd.h)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def load(cls, path):
+        h = C.c_void_p()
+        check(lib().pk_lm_load(os.fspath(path).encode(), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_text(cls, text):
+        raw = text if isinstance(text, (bytes, bytearray)) else text.encode()
+        h = C.c_void_p()
+        check(lib().pk_lm_load_buffer(bytes(raw), len(raw), C.byref(h)))
+        return cls(h)
+
+    @property
+    def order(self):
+        return int(lib().pk_lm_order(self._h))
+
+    @property
+    def num_ngrams(self):
+        fn = lib().pk_lm_num_ngrams
+        fn.restype = C.c_int64
+        return int(fn(self._h))
+
+    def score(self, id_lists, bos=True, eos=False):
+        """pk_lm_score: the fp32 log-probability (natural log) of every id list -> float32 array."""
+        ids, off = _pack_ids(id_lists)
+        out = np.zeros(len(id_lists), np.float32)
+        check(lib().pk_lm_score(self._h, _i(ids), _i(off), len(id_lists), int(bool(bos)), int(bool(eos)), _f(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().pk_lm_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _beam_call(fn, head, B, tmax, o, lm=None, lm_alpha=None, lm_beta=None):
+    """lm given: fn is the _lm form of the entry point; the result gains "lm_score" [B][N]."""
     N = max(1, o.n_best)
     ids = np.zeros((B, N, tmax), np.int32); st = np.zeros((B, N, tmax), np.int32); en = np.zeros((B, N, tmax), np.int32)
     cf = np.zeros((B, N, tmax), np.float32); lens = np.zeros((B, N), np.int32); score = np.zeros((B, N), np.float32)
-    check(fn(*head, C.byref(o), _i(ids), _i(lens), _f(score), _i(st), _i(en), _f(cf)))
-    return dict(ids=ids, lens=lens, score=score, start=st, end=en, conf=cf)
+    if lm is None:
+        check(fn(*head, C.byref(o), _i(ids), _i(lens), _f(score), _i(st), _i(en), _f(cf)))
+        return dict(ids=ids, lens=lens, score=score, start=st, end=en, conf=cf)
+    lo = lm_options(lm_alpha, lm_beta)
+    lms = np.zeros((B, N), np.float32)
+    check(fn(*head, C.byref(o), _i(ids), _i(lens), _f(score), _i(st), _i(en), _f(cf), lm._h, C.byref(lo), _f(lms)))
+    return dict(ids=ids, lens=lens, score=score, start=st, end=en, conf=cf, lm_score=lms)
 
 
-def ctc_beam_search(logp, blank, beam_width=None, token_prune=None, n_best=None, timestamps=False):
+def ctc_beam_search(logp, blank, beam_width=None, token_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None, lm_beta=None):
     """pk_ctc_beam_search: logp [B][T][V] (uniform) or a list of [T_b][V] matrices (ragged) -> dict of ids / start / end / conf
-    [B][N][Tmax], lens / score [B][N]; hypotheses best first, an unfilled slot has lens 0 and score -inf.  Needs a device, no model."""
+    [B][N][Tmax], lens / score [B][N]; hypotheses best first, an unfilled slot has lens 0 and score -inf.  Needs a device, no model.
+    lm (an Lm): pk_ctc_beam_search_lm, shallow fusion with weights lm_alpha / lm_beta (None: the defaults); adds lm_score [B][N]."""
     o = beam_options(beam_width, token_prune, n_best, timestamps)
+    fn = lib().pk_ctc_beam_search if lm is None else lib().pk_ctc_beam_search_lm
     if isinstance(logp, (list, tuple)):
         T = np.asarray([x.shape[0] for x in logp], np.int32)
         lp = _c(np.concatenate([_c(x) for x in logp], axis=0))
-        return _beam_call(lib().pk_ctc_beam_search, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), len(T), int(T.max()), o)
+        return _beam_call(fn, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), len(T), int(T.max()), o, lm, lm_alpha, lm_beta)
     lp = _c(logp)
     B, T, V = lp.shape
-    return _beam_call(lib().pk_ctc_beam_search, (_f(lp), None, B, T, V, blank), B, T, o)
+    return _beam_call(fn, (_f(lp), None, B, T, V, blank), B, T, o, lm, lm_alpha, lm_beta)
 
 
 # ---- CTC forced alignment of given token strings (include/parakeet_amd.h; DESIGN.md section 5.5.1) ------
@@ -1823,16 +1910,19 @@ class Model:
         """pk_transcribe_pcm: Transcriber::transcribe (transcribe.hpp:91-180) on in-memory clips -> list of dicts."""
         return _transcribe(lib().pk_transcribe_pcm, self._h, clips, decoder, timestamps, boost_phrases, boost_score)
 
-    def ctc_beam_decode(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False):
-        """pk_ctc_beam_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_beam_search."""
+    def ctc_beam_decode(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None, lm_beta=None):
+        """pk_ctc_beam_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_beam_search.
+        lm (an Lm): pk_ctc_beam_decode_lm(_ragged)."""
         o = beam_options(beam_width, token_prune, n_best, timestamps)
+        L = lib()
         if isinstance(enc, (list, tuple)):
             T = np.asarray([e.shape[0] for e in enc], np.int32)
             x = _c(np.concatenate([_c(e) for e in enc], axis=0))
-            return _beam_call(lib().pk_ctc_beam_decode_ragged, (self._h, _f(x), _i(T), len(T)), len(T), int(T.max()), o)
+            fn = L.pk_ctc_beam_decode_ragged if lm is None else L.pk_ctc_beam_decode_lm_ragged
+            return _beam_call(fn, (self._h, _f(x), _i(T), len(T)), len(T), int(T.max()), o, lm, lm_alpha, lm_beta)
         x = _c(enc)
         B, T, _ = x.shape
-        return _beam_call(lib().pk_ctc_beam_decode, (self._h, _f(x), B, T), B, T, o)
+        return _beam_call(L.pk_ctc_beam_decode if lm is None else L.pk_ctc_beam_decode_lm, (self._h, _f(x), B, T), B, T, o, lm, lm_alpha, lm_beta)
 
     def tdt_beam_decode(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None):
         """pk_tdt_beam_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> dict of ids / start / end /
@@ -2142,21 +2232,28 @@ class Model:
         check(lib().pk_spot_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, K, C.byref(o), _i(nh), _f(st), _f(en), _f(sc)))
         return [[[(float(st[c, k, j]), float(en[c, k, j]), float(sc[c, k, j])) for j in range(nh[c, k])] for k in range(K)] for c in range(n)]
 
-    def ctc_beam_decode_timed(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, reps=5):
-        """pk_ctc_beam_decode_timed -> (greedy CTC stage ms, beam search stage ms), HIP events, medians of reps passes."""
+    def ctc_beam_decode_timed(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, reps=5, lm=None, lm_alpha=None, lm_beta=None):
+        """pk_ctc_beam_decode_timed -> (greedy CTC stage ms, beam search stage ms), HIP events, medians of reps passes.
+        lm (an Lm): pk_ctc_beam_decode_lm_timed, the beam stage with the fused walk."""
         o = beam_options(beam_width, token_prune, n_best, timestamps)
         ms = np.zeros(2, np.float32)
         if isinstance(enc, (list, tuple)):
             T = np.asarray([e.shape[0] for e in enc], np.int32)
             x = _c(np.concatenate([_c(e) for e in enc], axis=0))
-            check(lib().pk_ctc_beam_decode_timed(self._h, _f(x), _i(T), len(T), 0, C.byref(o), reps, _f(ms)))
+            head = (self._h, _f(x), _i(T), len(T), 0, C.byref(o), reps, _f(ms))
         else:
             x = _c(enc)
-            check(lib().pk_ctc_beam_decode_timed(self._h, _f(x), None, x.shape[0], x.shape[1], C.byref(o), reps, _f(ms)))
+            head = (self._h, _f(x), None, x.shape[0], x.shape[1], C.byref(o), reps, _f(ms))
+        if lm is None:
+            check(lib().pk_ctc_beam_decode_timed(*head))
+        else:
+            lo = lm_options(lm_alpha, lm_beta)
+            check(lib().pk_ctc_beam_decode_lm_timed(*head, lm._h, C.byref(lo)))
         return float(ms[0]), float(ms[1])
 
-    def transcribe_nbest(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False):
-        """pk_transcribe_pcm_nbest: per clip a list of hypotheses, best first: dicts as transcribe_pcm returns them + "score"."""
+    def transcribe_nbest(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None, lm_beta=None):
+        """pk_transcribe_pcm_nbest: per clip a list of hypotheses, best first: dicts as transcribe_pcm returns them + "score".
+        lm (an Lm): pk_transcribe_pcm_nbest_lm; lists in fused order, every dict gains "lm_score"."""
         if isinstance(clips, tuple):
             pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
         else:
@@ -2164,13 +2261,20 @@ class Model:
         n = len(off) - 1
         o = beam_options(beam_width, token_prune, n_best, timestamps)
         res = C.POINTER(PkNbest)()
-        check(lib().pk_transcribe_pcm_nbest(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res)))
+        if lm is None:
+            check(lib().pk_transcribe_pcm_nbest(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res)))
+        else:
+            lo = lm_options(lm_alpha, lm_beta)
+            lms = np.zeros((n, max(1, o.n_best)), np.float32)
+            check(lib().pk_transcribe_pcm_nbest_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res), lm._h, C.byref(lo), _f(lms)))
         out = []
         for i in range(n):
             hyps = []
             for j in range(res[i].n_hyp):
                 r = res[i].hyp[j]
                 d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]))
+                if lm is not None:
+                    d["lm_score"] = float(lms[i, j])
                 if timestamps:
                     d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
                     d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]

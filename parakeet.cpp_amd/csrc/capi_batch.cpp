@@ -889,11 +889,19 @@ static void encode_batch(Model &m, const float *pcm, const int64_t *offsets, con
 // The body of pk_transcribe_pcm_nbest and pk_transcribe_pcm_nbest_rescored.  tdt_weight != nullptr: every returned hypothesis of a batch is scored
 // under the TDT head on the batch's encoder rows (tdt_total.hpp; enc_proj once per batch, hypotheses of a clip share its rows) and each clip's list
 // is re-ordered by rescore_order; ctc_out / tdt_out (optional, [n_clips][N]) take the parts in the returned order.
+// fused: the body of pk_transcribe_pcm_nbest_lm too: the search runs with the language model lm (lists stay in the
+// search's fused order) and lm_out (optional, [n_clips][N]) takes every returned hypothesis's LM score, 0 past n_hyp.
 static void nbest_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt, const float *tdt_weight,
-                      pk_nbest **results, float *ctc_out, float *tdt_out) {
+                      pk_nbest **results, float *ctc_out, float *tdt_out, bool fused = false, const pk_lm *lm = nullptr,
+                      const pk_lm_options *lm_opt = nullptr, float *lm_out = nullptr) {
     const pk_beam_options o = beam_options_of(opt);
     int V = 0, blank = 0;
     beam_model_checks(m, o, V, blank);
+    LmDev lmd{};
+    if (fused) {
+        lm_fusion_checks(lm, lm_opt, V, blank);
+        lmd = lm_device_view(lm, lm_opt);
+    }
     const bool ts = o.timestamps != 0;
     const int N = o.n_best;
     auto store = std::make_unique<NbestStore>();
@@ -903,19 +911,20 @@ static void nbest_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_
     std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
     plan_batches(clip_len.data(), n_clips, order, bstart);
     std::vector<int32_t> ids, lens, st, en, hids, hoff, hclip, hslot, okv, ord;
-    std::vector<float> sc, cf, tt, comb;
+    std::vector<float> sc, cf, tt, comb, lms;
     const float NEGF = -__builtin_huge_valf();
     for (size_t k = 0; k + 1 < bstart.size(); ++k) {
         const int c0 = bstart[k], nc = bstart[k + 1] - c0;
         RagBatch r;
         encode_batch(m, pcm, offsets, order.data() + c0, nc, r);
         const int T = r.T_max;
-        run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream);
+        run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream, fused ? &lmd : nullptr);
         PK_CHECK_LAUNCH();
         const size_t hyps = (size_t)nc * N, tok = hyps * T;
-        ids.resize(tok); lens.resize(hyps); sc.resize(hyps);
+        ids.resize(tok); lens.resize(hyps); sc.resize(hyps); lms.assign(hyps, 0.0f);
         if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
-        beam_copy_out(m.beam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, ts ? cf.data() : nullptr, m.stream);
+        beam_copy_out(m.beam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, ts ? cf.data() : nullptr, m.stream,
+                      fused ? lms.data() : nullptr);
         if (tdt_weight) {
             // the filled slots of the batch as one packed call of the total: hypothesis (i, j) on the rows of the batch's clip i
             hids.clear(); hoff.assign(1, 0); hclip.clear(); hslot.clear();
@@ -954,6 +963,7 @@ static void nbest_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_
                 const size_t hy = (size_t)i * N + ord[j], o0 = hy * T;
                 if (ctc_out) ctc_out[(size_t)c * N + j] = j < nh ? sc[hy] : NEGF;
                 if (tdt_out) tdt_out[(size_t)c * N + j] = j < nh ? tt[hy] : NEGF;
+                if (lm_out) lm_out[(size_t)c * N + j] = j < nh ? lms[hy] : 0.0f;
                 if (j >= nh) continue;
                 store->score[c][j] = comb[ord[j]];
                 store_tokens(m, R, j, lens[hy], ids.data() + o0, ts ? st.data() + o0 : nullptr, ts ? en.data() + o0 : nullptr, ts ? cf.data() + o0 : nullptr);
@@ -976,6 +986,14 @@ pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *
     return guard([&] {
         need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
         nbest_pcm(*h->m, pcm, offsets, n_clips, opt, nullptr, results, nullptr, nullptr);
+    });
+}
+
+pk_status pk_transcribe_pcm_nbest_lm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
+                                     pk_nbest **results, const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score) {
+    return guard([&] {
+        need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
+        nbest_pcm(*h->m, pcm, offsets, n_clips, opt, nullptr, results, nullptr, nullptr, true, lm, lm_opt, lm_score);
     });
 }
 

@@ -111,19 +111,26 @@ void pk::beam_model_checks(Model &m, const pk_beam_options &o, int &V, int &blan
     beam_check_options(o, V, blank);
 }
 
+// fused: the _lm entry points (lm must be given), else lm / lm_opt / lm_score are not looked at
 static void ctc_beam_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
-                            float *score, int32_t *start, int32_t *end, float *conf) {
+                            float *score, int32_t *start, int32_t *end, float *conf, bool fused = false, const pk_lm *lm = nullptr,
+                            const pk_lm_options *lm_opt = nullptr, float *lm_score = nullptr) {
     const pk_beam_options o = beam_options_of(opt);
     int V = 0, blank = 0;
     beam_model_checks(m, o, V, blank);
+    LmDev lmd{};
+    if (fused) {
+        lm_fusion_checks(lm, lm_opt, V, blank);
+        lmd = lm_device_view(lm, lm_opt);
+    }
     size_t rows;
     T = size_ws(m, n_frames, B, T, rows);                          // the token arrays are [B][N][T], T = the longest utterance
     PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
     m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
-    run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, n_frames ? m.ws.rv.seq : SeqRag(), V, blank, o, m.stream);
+    run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, n_frames ? m.ws.rv.seq : SeqRag(), V, blank, o, m.stream, fused ? &lmd : nullptr);
     PK_CHECK_LAUNCH();
     const bool ts = o.timestamps != 0;
-    beam_copy_out(m.beam, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, m.stream);
+    beam_copy_out(m.beam, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, m.stream, fused ? lm_score : nullptr);
 }
 
 // the alignment's model checks (include/parakeet_amd.h); -> the CTC vocabulary and its blank.  A boost trie does not matter: run_ctc writes the
@@ -422,14 +429,19 @@ void pk_beam_options_default(pk_beam_options *out) {
     out->beam_width = 8; out->token_prune = 16; out->n_best = 1; out->timestamps = 0;
 }
 
-pk_status pk_ctc_beam_search(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
-                             int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf) {
+// the body of pk_ctc_beam_search and pk_ctc_beam_search_lm (fused: as ctc_beam_decode)
+static pk_status ctc_beam_search(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
+                                 int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf, bool fused,
+                                 const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score) {
     return guard([&] {
         need(logp && ids && lens && B > 0, "logp/ids/lens/B");
         need(n_frames || T > 0, "T");
         const pk_beam_options o = beam_options_of(opt);
         beam_check_options(o, V, blank);
+        if (fused) lm_fusion_checks(lm, lm_opt, V, blank);
         need_device();
+        LmDev lmd{};
+        if (fused) lmd = lm_device_view(lm, lm_opt);
         int64_t rows = (int64_t)B * T;
         std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
         if (n_frames) {
@@ -453,11 +465,22 @@ pk_status pk_ctc_beam_search(const float *logp, const int32_t *n_frames, int B, 
             PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
             rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
         }
-        run_ctc_beam(ws, d_lp.as<float>(), B, T, rows, rag, V, blank, o, nullptr);
+        run_ctc_beam(ws, d_lp.as<float>(), B, T, rows, rag, V, blank, o, nullptr, fused ? &lmd : nullptr);
         PK_CHECK_LAUNCH();
         const bool ts = o.timestamps != 0;
-        beam_copy_out(ws, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, nullptr);
+        beam_copy_out(ws, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, nullptr, fused ? lm_score : nullptr);
     });
+}
+
+pk_status pk_ctc_beam_search(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
+                             int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf) {
+    return ctc_beam_search(logp, n_frames, B, T, V, blank, opt, ids, lens, score, start, end, conf, false, nullptr, nullptr, nullptr);
+}
+
+pk_status pk_ctc_beam_search_lm(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const pk_beam_options *opt,
+                                int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf, const pk_lm *lm,
+                                const pk_lm_options *lm_opt, float *lm_score) {
+    return ctc_beam_search(logp, n_frames, B, T, V, blank, opt, ids, lens, score, start, end, conf, true, lm, lm_opt, lm_score);
 }
 
 pk_status pk_ctc_beam_decode(pk_model *h, const float *enc, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
@@ -476,14 +499,38 @@ pk_status pk_ctc_beam_decode_ragged(pk_model *h, const float *enc, const int32_t
     });
 }
 
-pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
-                                   float ms[2]) {
+pk_status pk_ctc_beam_decode_lm(pk_model *h, const float *enc, int B, int T, const pk_beam_options *opt, int32_t *ids, int32_t *lens,
+                                float *score, int32_t *start, int32_t *end, float *conf, const pk_lm *lm, const pk_lm_options *lm_opt,
+                                float *lm_score) {
+    return guard([&] {
+        need(h && enc && ids && lens && B > 0 && T > 0, "model/enc/ids/lens/B/T");
+        ctc_beam_decode(*h->m, enc, nullptr, B, T, opt, ids, lens, score, start, end, conf, true, lm, lm_opt, lm_score);
+    });
+}
+
+pk_status pk_ctc_beam_decode_lm_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const pk_beam_options *opt, int32_t *ids,
+                                       int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf, const pk_lm *lm,
+                                       const pk_lm_options *lm_opt, float *lm_score) {
+    return guard([&] {
+        need(h && enc && n_frames && ids && lens && B > 0, "model/enc/n_frames/ids/lens/B");
+        ctc_beam_decode(*h->m, enc, n_frames, B, 0, opt, ids, lens, score, start, end, conf, true, lm, lm_opt, lm_score);
+    });
+}
+
+// the body of pk_ctc_beam_decode_timed and pk_ctc_beam_decode_lm_timed (fused: as ctc_beam_decode)
+static pk_status ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
+                                       float ms[2], bool fused, const pk_lm *lm, const pk_lm_options *lm_opt) {
     return guard([&] {
         need(h && enc && ms && B > 0 && reps > 0 && (n_frames || T > 0), "model/enc/ms/B/T/reps");
         Model &m = *h->m;
         const pk_beam_options o = beam_options_of(opt);
         int V = 0, blank = 0;
         beam_model_checks(m, o, V, blank);
+        LmDev lmd{};
+        if (fused) {
+            lm_fusion_checks(lm, lm_opt, V, blank);
+            lmd = lm_device_view(lm, lm_opt);
+        }
         size_t rows;
         T = size_ws(m, n_frames, B, T, rows);
         const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
@@ -495,7 +542,7 @@ pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t 
             PK_HIP(hipEventRecord(ev.e[0], m.stream));
             m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
             PK_HIP(hipEventRecord(ev.e[1], m.stream));
-            run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, rag, V, blank, o, m.stream);
+            run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, rag, V, blank, o, m.stream, fused ? &lmd : nullptr);
             PK_HIP(hipEventRecord(ev.e[2], m.stream));
             PK_HIP(hipStreamSynchronize(m.stream));
             PK_CHECK_LAUNCH();
@@ -507,6 +554,16 @@ pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t 
         std::sort(greedy.begin(), greedy.end()); std::sort(beam.begin(), beam.end());
         ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
     });
+}
+
+pk_status pk_ctc_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
+                                   float ms[2]) {
+    return ctc_beam_decode_timed(h, enc, n_frames, B, T, opt, reps, ms, false, nullptr, nullptr);
+}
+
+pk_status pk_ctc_beam_decode_lm_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_beam_options *opt, int reps,
+                                      float ms[2], const pk_lm *lm, const pk_lm_options *lm_opt) {
+    return ctc_beam_decode_timed(h, enc, n_frames, B, T, opt, reps, ms, true, lm, lm_opt);
 }
 
 /* ---- TDT beam search (kernels/tdt_beam.hip; reference roadmap README.md:494) ----------------------------------------------------- */

@@ -60,6 +60,12 @@ std::vector<std::vector<int>> encode_phrases(Model &m, const char *const *phrase
 pk_beam_options beam_options_of(const pk_beam_options *opt);
 void beam_model_checks(Model &m, const pk_beam_options &o, int &V, int &blank);
 
+// capi_lm.cpp: what the fused CTC beam entry points refuse about a language model for a vocabulary of V entries (host only: lm NULL, non-finite
+// weights, ids outside the vocabulary, the blank, missing coverage; PK_ERR_INVALID), and the model's arrays on the current device (uploaded on
+// first use there) with the weights of opt (NULL: the defaults).
+void lm_fusion_checks(const pk_lm *lm, const pk_lm_options *opt, int V, int blank);
+LmDev lm_device_view(const pk_lm *lm, const pk_lm_options *opt);
+
 // capi_batch.cpp: the one-call transcription of some clips of a call through the model's pipeline, used by every rank of a pk_group too.
 // ResultStore owns everything a pk_result array points into; only capi_batch.cpp sees inside it.
 struct ResultStore;

@@ -14,7 +14,7 @@ void beam_check_options(const pk_beam_options &opt, int V, int blank) {
 }
 
 void run_ctc_beam(BeamWs &ws, const float *d_lp, int B, int T, int64_t rows, const SeqRag &rag, int V, int blank, const pk_beam_options &opt,
-                  hipStream_t s) {
+                  hipStream_t s, const LmDev *lm) {
     beam_check_options(opt, V, blank);
     const int W = opt.beam_width, K = std::min(opt.token_prune, V - 1), N = opt.n_best;
     const bool ts = opt.timestamps != 0;
@@ -49,7 +49,14 @@ void run_ctc_beam(BeamWs &ws, const float *d_lp, int B, int T, int64_t rows, con
     wa.nodes = ws.nodes.as<int2>(); wa.node_pitch = node_pitch;
     wa.hyp_node = ws.hyp.as<int>(); wa.hyp_len = wa.hyp_node + hyps; wa.hyp_score = reinterpret_cast<float *>(wa.hyp_len + hyps);
     wa.rg = rag;
-    launch_ctc_beam_walk(wa, s);
+    if (lm) {
+        ws.hyp_lm.reserve(hyps * 4);
+        BeamLmWalkArgs la{};
+        la.w = wa; la.lm = *lm; la.hyp_lm = ws.hyp_lm.as<float>();
+        launch_ctc_beam_lm_walk(la, s);
+    } else {
+        launch_ctc_beam_walk(wa, s);
+    }
     BeamAlignArgs aa{};
     aa.lp = d_lp; aa.V = V; aa.blank = blank;
     aa.nodes = wa.nodes; aa.node_pitch = node_pitch;
@@ -63,11 +70,13 @@ void run_ctc_beam(BeamWs &ws, const float *d_lp, int B, int T, int64_t rows, con
     launch_ctc_beam_align(aa, s);
 }
 
-void beam_copy_out(const BeamWs &ws, int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf, hipStream_t s) {
+void beam_copy_out(const BeamWs &ws, int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, float *conf, hipStream_t s,
+                   float *lm_score) {
     const size_t hyps = (size_t)ws.B * ws.N, tok = hyps * ws.pitch;
     if (ids) PK_HIP(hipMemcpyAsync(ids, ws.ids.p, tok * 4, hipMemcpyDeviceToHost, s));
     if (lens) PK_HIP(hipMemcpyAsync(lens, ws.lens.p, hyps * 4, hipMemcpyDeviceToHost, s));
     if (score) PK_HIP(hipMemcpyAsync(score, ws.score(), hyps * 4, hipMemcpyDeviceToHost, s));
+    if (lm_score) PK_HIP(hipMemcpyAsync(lm_score, ws.hyp_lm.p, hyps * 4, hipMemcpyDeviceToHost, s));
     if (start) PK_HIP(hipMemcpyAsync(start, ws.start.p, tok * 4, hipMemcpyDeviceToHost, s));
     if (end) PK_HIP(hipMemcpyAsync(end, ws.end.p, tok * 4, hipMemcpyDeviceToHost, s));
     if (conf) PK_HIP(hipMemcpyAsync(conf, ws.conf.p, tok * 4, hipMemcpyDeviceToHost, s));

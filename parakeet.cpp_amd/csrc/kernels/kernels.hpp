@@ -435,6 +435,20 @@ struct BeamWalkArgs {
     SeqRag rg;
 };
 void launch_ctc_beam_walk(const BeamWalkArgs &a, hipStream_t s);
+// The walk with n-gram LM shallow fusion.  LmDev: the back-off automaton of ngram_lm.hpp in device memory -- state
+// records (arc_lo, arc_n, back-off weight bits, back-off state), the arcs' tokens (sorted per state) and (log-prob bits, next state) records,
+// and the dense table of the empty context over ids 0 .. U - 1 (U <= V; an id past it scores unk_lp and goes to state 0).
+struct LmDev {
+    const int4 *state; const int *arc_tok; const int2 *arc; const int2 *uni;
+    int U; float unk_lp; int start;
+    float alpha, beta;                          // a prefix's LM score grows by alpha * lookup + beta per token
+};
+struct BeamLmWalkArgs {
+    BeamWalkArgs w;
+    LmDev lm;
+    float *hyp_lm;                              // [B][N]: the LM score of hyp_node's prefix (a slot the beam does not fill: 0)
+};
+void launch_ctc_beam_lm_walk(const BeamLmWalkArgs &a, hipStream_t s);
 struct BeamAlignArgs {
     const float *lp; int V, blank;
     const int2 *nodes; int64_t node_pitch;

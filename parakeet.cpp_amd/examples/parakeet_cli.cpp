@@ -3,7 +3,7 @@
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K] [--beam-head ctc|tdt]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
-//                [--spot "phrase"]... [--spot-file path.txt] [--spot-hits N] [--spot-min-score X]
+//                [--spot "phrase"]... [--spot-file path.txt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
 // New: --align "text" / --align-file path.txt (tdt-ctc-110m, tdt-600m) aligns the given transcript with the audio (CTC forced alignment) and
 // prints its word timestamps in the format of --timestamps.  --align-head tdt aligns through the TDT head instead (the default stays ctc): the one
@@ -14,6 +14,9 @@
 // New: --spot "phrase" (repeatable) / --spot-file path.txt (one phrase per line) (tdt-ctc-110m) searches the audio for every phrase (CTC keyword
 // spotting) and prints one line per hit: phrase<TAB>start<TAB>end<TAB>score (seconds; score <= 0, 0 = the greedy path over the span is the phrase).
 // --spot-hits N: up to N non-overlapping hits per phrase (default 1); --spot-min-score X: only hits with score >= X (default: no threshold).
+// New: --lm file.arpa (with --beam W and the CTC decoder) fuses an n-gram language model over token ids into the beam search (shallow fusion):
+// hypotheses rank by acoustic score + LM score, LM score = sum per token of A * log p + B (--lm-alpha A, default 0.5; --lm-beta B, default 0);
+// both parts are printed.  tools/make_token_corpus.py turns text into the id lines an n-gram trainer makes such a file from.
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
 #include <algorithm>
 #include <chrono>
@@ -40,6 +43,7 @@ static void usage(const char *prog) {
               << "  --score \"text\"  log-likelihood of a known transcript under the TDT head\n"
               << "  --nbest N --rescore-tdt W  the N best hypotheses re-ranked by (1 - W) * CTC score + W * TDT log-likelihood\n"
               << "  --spot \"phrase\" (repeatable) | --spot-file path.txt  where was each phrase said: phrase<TAB>start<TAB>end<TAB>score per hit\n"
+              << "  --beam W --lm file.arpa [--lm-alpha A] [--lm-beta B]  the CTC beam search fused with an n-gram model over token ids\n"
               << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
@@ -124,7 +128,8 @@ int main(int argc, char **argv) {
     if (argc < 3) { usage(argv[0]); return 1; }
     try {
         const std::string weights = argv[1], audio_path = argv[2];
-        std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text, score_text;
+        std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text, score_text, lm_path;
+        LmOptions lm_opts;
         bool use_ctc = false, timestamps = false, align = false, align_tdt = false, beam_tdt = false, score = false, rescore = false, nbest_given = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
         float rescore_w = 0.5f;
@@ -175,6 +180,9 @@ int main(int argc, char **argv) {
             else if (a == "--spot-hits" && i + 1 < argc) spot_opts.max_hits = std::stoi(argv[++i]);
             else if (a == "--spot-min-score" && i + 1 < argc) spot_opts.min_score = std::stof(argv[++i]);
             else if (a == "--prune" && i + 1 < argc) prune = std::stoi(argv[++i]);
+            else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
+            else if (a == "--lm-alpha" && i + 1 < argc) lm_opts.alpha = std::stof(argv[++i]);
+            else if (a == "--lm-beta" && i + 1 < argc) lm_opts.beta = std::stof(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
             else if (a == "--latency" && i + 1 < argc) latency = std::stoi(argv[++i]);
@@ -198,6 +206,10 @@ int main(int argc, char **argv) {
         if (!spot.empty() && vocab.empty()) { std::cerr << "Error: --spot needs --vocab\n"; return 1; }
         if (rescore && !nbest_given) { std::cerr << "Error: --rescore-tdt needs --nbest N\n"; return 1; }
         if (rescore && model != "tdt-ctc-110m") { std::cerr << "Error: --rescore-tdt needs a model with both heads (--model tdt-ctc-110m)\n"; return 1; }
+        if (!lm_path.empty() && (beam <= 0 || beam_tdt || rescore || model != "tdt-ctc-110m")) {
+            std::cerr << "Error: --lm needs --beam W with the CTC head of --model tdt-ctc-110m (no TDT beam, no --rescore-tdt)\n";
+            return 1;
+        }
         if (beam_tdt && beam <= 0) { std::cerr << "Error: --beam-head needs --beam W\n"; return 1; }
         if (beam_tdt && !boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
         // --beam W --beam-head tdt: the TDT beam search's N best hypotheses, each with its path log-probability
@@ -242,6 +254,20 @@ int main(int argc, char **argv) {
                 if (!boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
                 BeamOptions bo;
                 bo.beam_width = beam; bo.n_best = nbest; bo.token_prune = prune; bo.timestamps = timestamps;
+                if (!lm_path.empty()) {                              // shallow fusion: the lists come back in fused order, both parts printed
+                    const LanguageModel lm(lm_path);
+                    const auto t0 = Clock::now();
+                    const auto hyps = t.transcribe_nbest(audio_path, bo, lm, lm_opts);
+                    const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+                    std::cout << "Beam search: width " << beam << ", " << lm.order() << "-gram model (" << lm.num_ngrams() << " n-grams), alpha "
+                              << std::defaultfloat << lm_opts.alpha << " beta " << lm_opts.beta << ", " << hyps.size() << " hypotheses\n";
+                    for (size_t j = 0; j < hyps.size(); ++j) {
+                        std::cout << "\n=== Hypothesis " << j << " score " << std::setprecision(9) << std::defaultfloat << hyps[j].score << " lm "
+                                  << hyps[j].lm_score << " ===\n";
+                        print_result(hyps[j].result, timestamps, ms);
+                    }
+                    return 0;
+                }
                 const auto t0 = Clock::now();
                 const auto hyps = t.transcribe_nbest(audio_path, bo);
                 const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();

@@ -95,6 +95,47 @@ struct RescoredResult : ScoredResult {
     float ctc_score = 0.0f;
     float tdt_total = 0.0f;
 };
+/// New: an n-gram language model over the acoustic model's token ids (pk_lm: ARPA text whose words are decimal ids).
+class LanguageModel {
+  public:
+    explicit LanguageModel(const std::string &arpa_path) {
+        if (pk_lm_load(arpa_path.c_str(), &lm_) != PK_OK) {
+            char msg[1024];
+            pk_last_error(msg, sizeof msg);
+            throw std::runtime_error(msg);
+        }
+    }
+    ~LanguageModel() { pk_lm_free(lm_); }
+    LanguageModel(const LanguageModel &) = delete;
+    LanguageModel &operator=(const LanguageModel &) = delete;
+    int order() const { return pk_lm_order(lm_); }
+    int64_t num_ngrams() const { return pk_lm_num_ngrams(lm_); }
+    /// pk_lm_score of one token string: its fp32 natural-log probability (host only); what an n-best list of either beam is rescored with
+    float score(const std::vector<int> &token_ids, bool bos = true, bool eos = false) const {
+        std::vector<int32_t> ids(token_ids.begin(), token_ids.end());
+        const int32_t off[2] = {0, (int32_t)ids.size()};
+        float out = 0.0f;
+        if (pk_lm_score(lm_, ids.data(), off, 1, bos ? 1 : 0, eos ? 1 : 0, &out) != PK_OK) {
+            char msg[1024];
+            pk_last_error(msg, sizeof msg);
+            throw std::runtime_error(msg);
+        }
+        return out;
+    }
+    const pk_lm *handle() const { return lm_; }
+
+  private:
+    pk_lm *lm_ = nullptr;
+};
+/// New: weights of the shallow fusion (pk_lm_options): hypotheses rank by score + lm_score, lm_score = sum per token of alpha * log p + beta.
+struct LmOptions {
+    float alpha = 0.5f;
+    float beta = 0.0f;
+};
+/// New: one hypothesis of transcribe_nbest(audio, beam, lm): score stays the acoustic log-probability, lm_score is the model's part.
+struct LmScoredResult : ScoredResult {
+    float lm_score = 0.0f;
+};
 /// New: what Transcriber::score returns: the log-likelihood of the given transcript under the TDT head (pk_tdt_score_pcm: the forward algorithm
 /// on the alignment's lattice).  scored == false: no path emits the transcript on this audio, log_likelihood is -inf.
 struct ScoreResult {
@@ -225,6 +266,43 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
         struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
         return run_nbest(pcm, (size_t)n, opts);
+    }
+
+    // pk_transcribe_pcm_nbest_lm on one clip: the search with n-gram LM shallow fusion, hypotheses in fused order
+    std::vector<LmScoredResult> run_nbest_lm(const float *pcm, size_t n, const BeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
+        if (!on_gpu_) to_gpu(0);
+        pk_beam_options o;
+        pk_beam_options_default(&o);
+        o.beam_width = opts.beam_width; o.token_prune = opts.token_prune; o.n_best = opts.n_best; o.timestamps = opts.timestamps ? 1 : 0;
+        const pk_lm_options lo{lmo.alpha, lmo.beta};
+        const int64_t offsets[2] = {0, (int64_t)n};
+        std::vector<float> lms((size_t)std::max(1, opts.n_best), 0.0f);
+        pk_nbest *res = nullptr;
+        check(pk_transcribe_pcm_nbest_lm(m_, pcm, offsets, 1, &o, &res, lm.handle(), &lo, lms.data()));
+        std::vector<LmScoredResult> out(res[0].n_hyp);
+        for (int j = 0; j < res[0].n_hyp; ++j) {
+            const pk_result &r = res[0].hyp[j];
+            out[j].score = res[0].score[j];
+            out[j].lm_score = lms[j];
+            out[j].result.text = r.text ? r.text : "";
+            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
+            if (opts.timestamps) {
+                for (int k = 0; k < r.n_tokens; ++k)
+                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
+                for (int k = 0; k < r.n_words; ++k)
+                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
+            }
+        }
+        pk_nbest_free(res, 1);
+        return out;
+    }
+    std::vector<LmScoredResult> run_nbest_lm_file(const std::string &audio_path, const BeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_nbest_lm(pcm, (size_t)n, opts, lm, lmo);
     }
 
     // pk_transcribe_pcm_nbest_tdt on one clip: the TDT beam search's hypotheses, best first; score is the path's log-probability
@@ -469,6 +547,13 @@ class Transcriber {
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
     AlignResult align_tdt(const std::vector<float> &samples, const std::string &text) { return eng_.run_align(samples.data(), samples.size(), text, true); }
+    /// New: the search with n-gram LM shallow fusion (pk_transcribe_pcm_nbest_lm): hypotheses in fused order, score + lm_score per hypothesis
+    std::vector<LmScoredResult> transcribe_nbest(const std::string &audio_path, const BeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {
+        return eng_.run_nbest_lm_file(audio_path, opts, lm, lm_opts);
+    }
+    std::vector<LmScoredResult> transcribe_nbest(const float *pcm, size_t n, const BeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {
+        return eng_.run_nbest_lm(pcm, n, opts, lm, lm_opts);
+    }
     /// New: the same search through this model's TDT head (TDTTranscriber::transcribe_nbest)
     std::vector<ScoredResult> transcribe_nbest_tdt(const std::string &audio_path, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt_file(audio_path, opts); }
     std::vector<ScoredResult> transcribe_nbest_tdt(const float *pcm, size_t n, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt(pcm, n, opts); }
