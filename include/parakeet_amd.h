@@ -362,8 +362,8 @@ void pk_nbest_free(pk_nbest *results, int n_clips);
  *                 -> acc + p(arc) and the arc's next state; a miss in the empty context scores <unk>'s unigram and goes to the empty context
  * is the one scoring rule of pk_lm_score and of the fused search (tests/ngram_lm_ref.py and tests/ctc_beam_lm_ref.py
  * are the specification in Python; host and device results equal them bit for bit).  Word-level models, binary KenLM files, neural models,
- * the </s> term inside the search, fusion inside the TDT beam (rescore its n-best list with pk_lm_score), pk_group / streaming variants and
- * boosting together with a model: no variant. */
+ * the </s> term inside the search, pk_group / streaming variants and boosting together with a model: no variant.  Fusion inside the TDT beam
+ * search: the _lm entry points of its section below. */
 typedef struct pk_lm pk_lm;
 /* Parses and compiles ARPA text from a file resp. from n_bytes of memory (no terminator needed).  Host only.  PK_ERR_INVALID with the line
  * named in pk_last_error for: a word that is neither a decimal id nor <s> / </s> / <unk>; an id >= 2^24; "ngram k=" counts that disagree with
@@ -377,7 +377,7 @@ int pk_lm_order(const pk_lm *lm);                       /* 1..5; 0 for NULL */
 int64_t pk_lm_num_ngrams(const pk_lm *lm);              /* entries of all orders */
 /* Host only, no device: logp[i] = the fp32 left-to-right sum of lookup over string i = ids[id_offsets[i] .. id_offsets[i + 1]), from the
  * context <s> with bos != 0 (when the file has <s>; else, and with bos == 0, from the empty context), plus the </s> term with eos != 0.  An
- * empty string scores 0 (resp. its </s> term).  What a caller rescores an n-best list with, the TDT beam's included.  PK_ERR_INVALID for a
+ * empty string scores 0 (resp. its </s> term).  What a caller rescores an n-best list with.  PK_ERR_INVALID for a
  * negative id, an id >= 2^24, or an id without a unigram under a model without <unk>. */
 pk_status pk_lm_score(const pk_lm *lm, const int32_t *ids, const int32_t *id_offsets, int n_strings, int bos, int eos, float *logp);
 typedef struct pk_lm_options {
@@ -421,7 +421,8 @@ pk_status pk_transcribe_pcm_nbest_lm(pk_model *m, const float *pcm, const int64_
  * step, tie rule and the duplicate rule are specified in DESIGN.md section 5.5.5 (tests/tdt_beam_ref.py is that specification in Python; the
  * device result equals it bit for bit).  max_symbols_per_step is not part of the search.  The score of a hypothesis is ONE alignment's
  * log-probability, at most pk_tdt_align_decode's score for the same ids; pk_tdt_total_decode on the returned ids gives the log-likelihood
- * summed over every alignment.  RNN-T heads, gemm_bf16, boosting inside the beam, language models, pk_group and streaming sessions: no variant. */
+ * summed over every alignment.  RNN-T heads, gemm_bf16, boosting inside the beam, pk_group and streaming sessions: no variant.  An n-gram
+ * language model inside the search: the _lm entry points at the end of this section. */
 typedef struct pk_tdt_beam_options {
     int32_t beam_width;         /* W: hypotheses kept per step, 1..16 */
     int32_t label_prune;        /* K: non-blank labels expanded per hypothesis (the K most probable) next to the blank, 1..16, clamped to V - 1 */
@@ -453,6 +454,36 @@ pk_status pk_tdt_beam_decode_timed(pk_model *m, const float *enc, const int32_t 
  * start / end / confidence and words), score[j] the hypothesis's path log-probability; freed with pk_nbest_free. */
 pk_status pk_transcribe_pcm_nbest_tdt(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt,
                                       int timestamps, pk_nbest **results);
+/* The search with n-gram LM shallow fusion (tests/tdt_beam_lm_ref.py is the specification in Python, the device
+ * result equals it bit for bit): the arguments of the unfused entry point, then the model, its weights (NULL: the defaults) and one more
+ * output, lm_score [B][N] (optional).  A hypothesis carries the automaton's state after its prefix and the prefix's LM score lm (start: the
+ * start state, 0).  A blank arc inherits both; a label arc with token c has (lp, s2) = lookup(state, c), lm2 = lm + ((alpha * lp) + beta), three
+ * separately rounded fp32 operations, one lookup for all durations of the label.  Label and duration pruning stay acoustic and a candidate's
+ * score stays the acoustic one; the duplicate rule and the choice of the W best decide by score + lm (one fp32 add) where the unfused search
+ * decides by score.  </s> is never proposed.  Hypotheses come back in fused order; score keeps its meaning (the path's acoustic
+ * log-probability), lm_score is lm; a slot the beam cannot fill has score -inf and lm_score 0.  With alpha = beta = 0 every output equals the
+ * unfused search's bit for bit.
+ * Refusals, before anything is allocated (the model's device copy included): PK_ERR_UNSUPPORTED as the unfused entry point (the scratch formula grows by the fused terms);
+ * PK_ERR_INVALID for lm == NULL, a non-finite alpha or beta, a model that names the blank id or an id >= V, or one with neither <unk> nor a
+ * unigram for every non-blank id of the vocabulary.  Still no variant: the </s> term, word-level models, RNN-T heads, gemm_bf16, boosting
+ * together with a model, pk_group and streaming sessions. */
+pk_status pk_tdt_beam_decode_lm(pk_model *m, const float *enc, int B, int T, const pk_tdt_beam_options *opt, int max_tokens, int32_t *ids,
+                                int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, int32_t *ok,
+                                const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score);
+pk_status pk_tdt_beam_decode_lm_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const pk_tdt_beam_options *opt, int max_tokens,
+                                       int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf,
+                                       int32_t *ok, const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score);
+/* Stage timers as pk_tdt_beam_decode_timed (tools/bench_tdt_beam_lm.py): ms[1] = enc_proj + the fused search + back-trace. */
+pk_status pk_tdt_beam_decode_lm_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt,
+                                      int max_tokens, int reps, float ms[2], const pk_lm *lm, const pk_lm_options *lm_opt);
+/* Steps (expand + prune rounds of the host loop) that the model's last TDT beam search enqueued, fused or not, _timed calls included: the
+ * search stops between groups of 8 steps once no hypothesis of the batch is live, so the count is a multiple of 8 or the cap Tmax + max_tokens.
+ * What tools/bench_tdt_beam_lm.py divides the fused stage's extra time by.  0 before the first search and for NULL. */
+int pk_tdt_beam_last_steps(const pk_model *m);
+/* pk_transcribe_pcm_nbest_tdt through the fused search: results[i].score[j] stays the acoustic score, lm_score (optional, [n_clips][N], N =
+ * opt->n_best) takes the LM scores beside it: lm_score[i * N + j] belongs to results[i].hyp[j], slots past n_hyp read 0.  pk_nbest is unchanged. */
+pk_status pk_transcribe_pcm_nbest_tdt_lm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt,
+                                         int timestamps, pk_nbest **results, const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score);
 
 /* ---- CTC forced alignment of a GIVEN transcript ---------------------------------------------------------------------------
  * Given the log-probs and the token string that was said: when was each token said.  The alignment is the max-plus (Viterbi) path on the

@@ -220,6 +220,15 @@ _LATE_SIGNATURES = {
     "pk_tdt_beam_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, i32p, i32p, f32p, i32p, i32p, i32p, f32p, i32p],
     "pk_tdt_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, C.c_int, f32p],
     "pk_transcribe_pcm_nbest_tdt": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, C.POINTER(C.POINTER(PkNbest))],
+    "pk_tdt_beam_decode_lm": [C.c_void_p, f32p, C.c_int, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, i32p, i32p, f32p, i32p, i32p, i32p, f32p, i32p,
+                              C.c_void_p, C.POINTER(PkLmOptions), f32p],
+    "pk_tdt_beam_decode_lm_ragged": [C.c_void_p, f32p, i32p, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, i32p, i32p, f32p, i32p, i32p, i32p, f32p, i32p,
+                                     C.c_void_p, C.POINTER(PkLmOptions), f32p],
+    "pk_tdt_beam_decode_lm_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, C.c_int, f32p, C.c_void_p,
+                                    C.POINTER(PkLmOptions)],
+    "pk_tdt_beam_last_steps": [C.c_void_p],
+    "pk_transcribe_pcm_nbest_tdt_lm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkTdtBeamOptions), C.c_int, C.POINTER(C.POINTER(PkNbest)),
+                                       C.c_void_p, C.POINTER(PkLmOptions), f32p],
     "pk_ctc_align": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
     "pk_ctc_align_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
     "pk_ctc_align_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, f32p, i32p],
@@ -1924,9 +1933,11 @@ class Model:
         B, T, _ = x.shape
         return _beam_call(L.pk_ctc_beam_decode if lm is None else L.pk_ctc_beam_decode_lm, (self._h, _f(x), B, T), B, T, o, lm, lm_alpha, lm_beta)
 
-    def tdt_beam_decode(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None):
+    def tdt_beam_decode(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None, lm=None, lm_alpha=None,
+                        lm_beta=None):
         """pk_tdt_beam_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> dict of ids / start / end /
-        dur_idx / conf [B][N][max_tokens], lens / score [B][N], ok [B].  max_tokens None: (longest clip) * max_symbols_per_step."""
+        dur_idx / conf [B][N][max_tokens], lens / score [B][N], ok [B].  max_tokens None: (longest clip) * max_symbols_per_step.
+        lm (an Lm): pk_tdt_beam_decode_lm(_ragged), shallow fusion with weights lm_alpha / lm_beta (None: the defaults); adds lm_score [B][N]."""
         o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
         rag, x, T = self._enc_head(enc)
         B, N = len(T), max(1, o.n_best)
@@ -1935,23 +1946,42 @@ class Model:
         di = np.zeros((B, N, mt), np.int32); cf = np.zeros((B, N, mt), np.float32)
         lens = np.zeros((B, N), np.int32); score = np.zeros((B, N), np.float32); ok = np.zeros(B, np.int32)
         tail = (C.byref(o), mt, _i(ids), _i(lens), _f(score), _i(st), _i(en), _i(di), _f(cf), _i(ok))
+        out = dict(ids=ids, lens=lens, score=score, start=st, end=en, dur_idx=di, conf=cf, ok=ok)
+        L = lib()
+        if lm is not None:
+            lo = lm_options(lm_alpha, lm_beta)
+            out["lm_score"] = np.zeros((B, N), np.float32)
+            tail += (lm._h, C.byref(lo), _f(out["lm_score"]))
         if rag:
-            check(lib().pk_tdt_beam_decode_ragged(self._h, _f(x), _i(T), B, *tail))
+            check((L.pk_tdt_beam_decode_ragged if lm is None else L.pk_tdt_beam_decode_lm_ragged)(self._h, _f(x), _i(T), B, *tail))
         else:
-            check(lib().pk_tdt_beam_decode(self._h, _f(x), x.shape[0], x.shape[1], *tail))
-        return dict(ids=ids, lens=lens, score=score, start=st, end=en, dur_idx=di, conf=cf, ok=ok)
+            check((L.pk_tdt_beam_decode if lm is None else L.pk_tdt_beam_decode_lm)(self._h, _f(x), x.shape[0], x.shape[1], *tail))
+        return out
 
-    def tdt_beam_decode_timed(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None, reps=5):
-        """pk_tdt_beam_decode_timed -> (greedy TDT stage ms, beam search stage ms), HIP events, medians of reps passes."""
+    def tdt_beam_decode_timed(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None, reps=5, lm=None,
+                              lm_alpha=None, lm_beta=None):
+        """pk_tdt_beam_decode_timed -> (greedy TDT stage ms, beam search stage ms), HIP events, medians of reps passes.
+        lm (an Lm): pk_tdt_beam_decode_lm_timed, the second stage is the fused search."""
         o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
         rag, x, T = self._enc_head(enc)
         mt = int(max_tokens or int(T.max()) * self.cfg.max_symbols_per_step)
         ms = np.zeros(2, np.float32)
-        check(lib().pk_tdt_beam_decode_timed(self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], C.byref(o), mt, reps, _f(ms)))
+        head = (self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], C.byref(o), mt, reps, _f(ms))
+        if lm is None:
+            check(lib().pk_tdt_beam_decode_timed(*head))
+        else:
+            lo = lm_options(lm_alpha, lm_beta)
+            check(lib().pk_tdt_beam_decode_lm_timed(*head, lm._h, C.byref(lo)))
         return float(ms[0]), float(ms[1])
 
-    def transcribe_nbest_tdt(self, clips, beam_width=None, label_prune=None, duration_prune=None, n_best=None, timestamps=False):
-        """pk_transcribe_pcm_nbest_tdt: per clip a list of hypotheses through the TDT head, best first: dicts as transcribe_nbest returns them."""
+    def tdt_beam_last_steps(self):
+        """pk_tdt_beam_last_steps: steps the last TDT beam search of this model enqueued (fused or not, timed calls included)."""
+        return int(lib().pk_tdt_beam_last_steps(self._h))
+
+    def transcribe_nbest_tdt(self, clips, beam_width=None, label_prune=None, duration_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None,
+                             lm_beta=None):
+        """pk_transcribe_pcm_nbest_tdt: per clip a list of hypotheses through the TDT head, best first: dicts as transcribe_nbest returns them.
+        lm (an Lm): pk_transcribe_pcm_nbest_tdt_lm; lists in fused order, every dict gains "lm_score"."""
         if isinstance(clips, tuple):
             pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
         else:
@@ -1959,13 +1989,22 @@ class Model:
         n = len(off) - 1
         o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
         res = C.POINTER(PkNbest)()
-        check(lib().pk_transcribe_pcm_nbest_tdt(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res)))
+        lms = None
+        if lm is None:
+            check(lib().pk_transcribe_pcm_nbest_tdt(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res)))
+        else:
+            lo = lm_options(lm_alpha, lm_beta)
+            lms = np.zeros((n, max(1, o.n_best)), np.float32)
+            check(lib().pk_transcribe_pcm_nbest_tdt_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res), lm._h,
+                                                       C.byref(lo), _f(lms)))
         out = []
         for i in range(n):
             hyps = []
             for j in range(res[i].n_hyp):
                 r = res[i].hyp[j]
                 d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]))
+                if lms is not None:
+                    d["lm_score"] = float(lms[i, j])
                 if timestamps:
                     d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
                     d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]

@@ -1013,11 +1013,16 @@ pk_status pk_transcribe_pcm_nbest_rescored(pk_model *h, const float *pcm, const 
 }
 
 // The body of pk_transcribe_pcm_nbest_tdt: the batches of pk_transcribe_pcm_nbest; every batch is searched through the TDT head (tdt_beam.hpp) on
-// its encoder rows, enc_proj once per batch.
-static void nbest_tdt_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt, bool ts, pk_nbest **results) {
+// its encoder rows, enc_proj once per batch.  fused: pk_transcribe_pcm_nbest_tdt_lm (lm must be given), lists in fused
+// order and lm_out [n_clips][N] beside them; else lm / lm_opt / lm_out are not looked at.
+static void nbest_tdt_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt, bool ts, pk_nbest **results,
+                          bool fused = false, const pk_lm *lm = nullptr, const pk_lm_options *lm_opt = nullptr, float *lm_out = nullptr) {
     const pk_tdt_beam_options o = tdt_beam_options_of(opt);
     tdt_beam_model_checks(m, o);
+    if (fused) lm_fusion_checks(lm, lm_opt, m.cfg.vocab_size, m.cfg.blank_id);
     m.require_gpu();
+    LmDev lmd{};
+    bool have_lmd = false;                                     // the device copy is made after the first batch's plan: a refusal allocates nothing
     const int N = o.n_best;
     auto store = std::make_unique<NbestStore>();
     store->out.resize((size_t)n_clips + 1); store->clip.resize(n_clips); store->score.resize(n_clips);
@@ -1026,7 +1031,7 @@ static void nbest_tdt_pcm(Model &m, const float *pcm, const int64_t *offsets, in
     std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
     plan_batches(clip_len.data(), n_clips, order, bstart);
     std::vector<int32_t> ids, lens, st, en;
-    std::vector<float> sc, cf;
+    std::vector<float> sc, cf, lms;
     const float NEGF = -__builtin_huge_valf();
     const int sym = m.cfg.max_symbols_per_step > 0 ? m.cfg.max_symbols_per_step : 10;
     for (size_t k = 0; k + 1 < bstart.size(); ++k) {
@@ -1035,16 +1040,17 @@ static void nbest_tdt_pcm(Model &m, const float *pcm, const int64_t *offsets, in
         int MT = 0;
         encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
             MT = rb.T_max * sym;
-            tdt_beam_plan(m.tbeam, m, rb.T.data(), nc, 0, o, MT);       // (refuses before the batch is allocated or queued)
+            tdt_beam_plan(m.tbeam, m, rb.T.data(), nc, 0, o, MT, fused);        // (refuses before the batch is allocated or queued)
+            if (fused && !have_lmd) { lmd = lm_device_view(lm, lm_opt); have_lmd = true; }
         }, /*ctc=*/false);
         m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
-        run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream);
+        run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream, fused ? &lmd : nullptr);
         PK_CHECK_LAUNCH();
         const size_t hyps = (size_t)nc * N, tok = hyps * MT;
-        ids.resize(tok); lens.resize(hyps); sc.resize(hyps);
+        ids.resize(tok); lens.resize(hyps); sc.resize(hyps); lms.assign(hyps, 0.0f);
         if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
         tdt_beam_copy_out(m.tbeam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, nullptr, ts ? cf.data() : nullptr,
-                          nullptr, m.stream);
+                          nullptr, m.stream, fused ? lms.data() : nullptr);
         for (int i = 0; i < nc; ++i) {
             const int c = order[c0 + i];
             int nh = 0;
@@ -1052,6 +1058,7 @@ static void nbest_tdt_pcm(Model &m, const float *pcm, const int64_t *offsets, in
             store->clip[c] = new_store(nh);
             ResultStore &R = *store->clip[c];
             store->score[c].resize(nh);
+            if (lm_out) for (int j = 0; j < N; ++j) lm_out[(size_t)c * N + j] = j < nh ? lms[(size_t)i * N + j] : 0.0f;
             for (int j = 0; j < nh; ++j) {
                 const size_t hy = (size_t)i * N + j, o0 = hy * MT;
                 store->score[c][j] = sc[hy];
@@ -1075,6 +1082,14 @@ pk_status pk_transcribe_pcm_nbest_tdt(pk_model *h, const float *pcm, const int64
     return guard([&] {
         need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
         nbest_tdt_pcm(*h->m, pcm, offsets, n_clips, opt, timestamps != 0, results);
+    });
+}
+
+pk_status pk_transcribe_pcm_nbest_tdt_lm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt,
+                                         int timestamps, pk_nbest **results, const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score) {
+    return guard([&] {
+        need(h && pcm && offsets && results && n_clips > 0, "model/pcm/offsets/results/n_clips");
+        nbest_tdt_pcm(*h->m, pcm, offsets, n_clips, opt, timestamps != 0, results, true, lm, lm_opt, lm_score);
     });
 }
 

@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_lm.cpp -- the n-gram language model at the C boundary: pk_lm_load(_buffer), pk_lm_free, pk_lm_score, and the device
-// copies the fused CTC beam search reads (one per device, made on first use).
+// copies the fused CTC and TDT beam searches read (one per device, made on first use).
 #include <cmath>
 #include <cstdio>
 #include <map>

@@ -572,25 +572,31 @@ void pk_tdt_beam_options_default(pk_tdt_beam_options *out) {
     out->beam_width = 8; out->label_prune = 8; out->duration_prune = 2; out->n_best = 1;
 }
 
-// checks and sizes one search (host only: every refusal comes before anything is allocated)
-static void tdt_beam_checks(Model &m, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options &o, int max_tokens) {
+// checks and sizes one search (host only: every refusal comes before anything is allocated).  fused: the _lm entry points (lm must be given;
+// DESIGN.md section 5.5.7): what the unfused search refuses, then what lm_fusion_checks refuses; else lm / lm_opt are not looked at
+static void tdt_beam_checks(Model &m, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options &o, int max_tokens, bool fused = false,
+                            const pk_lm *lm = nullptr, const pk_lm_options *lm_opt = nullptr) {
     tdt_beam_model_checks(m, o);
+    if (fused) lm_fusion_checks(lm, lm_opt, m.cfg.vocab_size, m.cfg.blank_id);
     if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
     m.require_gpu();
-    tdt_beam_plan(m.tbeam, m, n_frames, B, T, o, max_tokens);
+    tdt_beam_plan(m.tbeam, m, n_frames, B, T, o, max_tokens, fused);
 }
 
 static void tdt_beam_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt, int max_tokens, int32_t *ids,
-                            int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, int32_t *ok) {
+                            int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, int32_t *ok, bool fused = false,
+                            const pk_lm *lm = nullptr, const pk_lm_options *lm_opt = nullptr, float *lm_score = nullptr) {
     const pk_tdt_beam_options o = tdt_beam_options_of(opt);
-    tdt_beam_checks(m, n_frames, B, T, o, max_tokens);
+    tdt_beam_checks(m, n_frames, B, T, o, max_tokens, fused, lm, lm_opt);
+    LmDev lmd{};
+    if (fused) lmd = lm_device_view(lm, lm_opt);
     size_t rows;
     size_ws(m, n_frames, B, T, rows);
     PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
     m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
-    run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream);
+    run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream, fused ? &lmd : nullptr);
     PK_CHECK_LAUNCH();
-    tdt_beam_copy_out(m.tbeam, ids, lens, score, start, end, dur_idx, conf, ok, m.stream);
+    tdt_beam_copy_out(m.tbeam, ids, lens, score, start, end, dur_idx, conf, ok, m.stream, fused ? lm_score : nullptr);
 }
 
 pk_status pk_tdt_beam_decode(pk_model *h, const float *enc, int B, int T, const pk_tdt_beam_options *opt, int max_tokens, int32_t *ids,
@@ -610,13 +616,33 @@ pk_status pk_tdt_beam_decode_ragged(pk_model *h, const float *enc, const int32_t
     });
 }
 
-pk_status pk_tdt_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt,
-                                   int max_tokens, int reps, float ms[2]) {
+pk_status pk_tdt_beam_decode_lm(pk_model *h, const float *enc, int B, int T, const pk_tdt_beam_options *opt, int max_tokens, int32_t *ids,
+                                int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, int32_t *ok,
+                                const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score) {
+    return guard([&] {
+        need(h && enc && ids && lens && score && B > 0 && T > 0 && max_tokens > 0, "model/enc/ids/lens/score/B/T/max_tokens");
+        tdt_beam_decode(*h->m, enc, nullptr, B, T, opt, max_tokens, ids, lens, score, start, end, dur_idx, conf, ok, true, lm, lm_opt, lm_score);
+    });
+}
+
+pk_status pk_tdt_beam_decode_lm_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const pk_tdt_beam_options *opt, int max_tokens,
+                                       int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf,
+                                       int32_t *ok, const pk_lm *lm, const pk_lm_options *lm_opt, float *lm_score) {
+    return guard([&] {
+        need(h && enc && n_frames && ids && lens && score && B > 0 && max_tokens > 0, "model/enc/n_frames/ids/lens/score/B/max_tokens");
+        tdt_beam_decode(*h->m, enc, n_frames, B, 0, opt, max_tokens, ids, lens, score, start, end, dur_idx, conf, ok, true, lm, lm_opt, lm_score);
+    });
+}
+
+static pk_status tdt_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt,
+                                       int max_tokens, int reps, float ms[2], bool fused, const pk_lm *lm, const pk_lm_options *lm_opt) {
     return guard([&] {
         need(h && enc && ms && B > 0 && reps > 0 && max_tokens > 0 && (n_frames || T > 0), "model/enc/ms/B/T/max_tokens/reps");
         Model &m = *h->m;
         const pk_tdt_beam_options o = tdt_beam_options_of(opt);
-        tdt_beam_checks(m, n_frames, B, T, o, max_tokens);
+        tdt_beam_checks(m, n_frames, B, T, o, max_tokens, fused, lm, lm_opt);
+        LmDev lmd{};
+        if (fused) lmd = lm_device_view(lm, lm_opt);
         size_t rows;
         T = size_ws(m, n_frames, B, T, rows);
         PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
@@ -628,7 +654,7 @@ pk_status pk_tdt_beam_decode_timed(pk_model *h, const float *enc, const int32_t 
             m.run_tdt(m.ws, m.ws.x.as<float>(), B, T, m.ws.max_tokens, m.stream);
             PK_HIP(hipEventRecord(ev.e[1], m.stream));
             m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
-            run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream);
+            run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream, fused ? &lmd : nullptr);
             PK_HIP(hipEventRecord(ev.e[2], m.stream));
             PK_HIP(hipStreamSynchronize(m.stream));
             PK_CHECK_LAUNCH();
@@ -641,6 +667,18 @@ pk_status pk_tdt_beam_decode_timed(pk_model *h, const float *enc, const int32_t 
         ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
     });
 }
+
+pk_status pk_tdt_beam_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt,
+                                   int max_tokens, int reps, float ms[2]) {
+    return tdt_beam_decode_timed(h, enc, n_frames, B, T, opt, max_tokens, reps, ms, false, nullptr, nullptr);
+}
+
+pk_status pk_tdt_beam_decode_lm_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options *opt,
+                                      int max_tokens, int reps, float ms[2], const pk_lm *lm, const pk_lm_options *lm_opt) {
+    return tdt_beam_decode_timed(h, enc, n_frames, B, T, opt, max_tokens, reps, ms, true, lm, lm_opt);
+}
+
+int pk_tdt_beam_last_steps(const pk_model *h) { return h && h->m ? h->m->tbeam.steps_run : 0; }
 
 /* ---- CTC forced alignment of given token strings (kernels/ctc_align.hip) ------------------------------------------------------------ */
 pk_status pk_ctc_align(const float *logp, const int32_t *n_frames, int B, int T, int V, int blank, const int32_t *ids, const int32_t *id_offsets,

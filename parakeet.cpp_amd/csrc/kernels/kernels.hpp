@@ -553,11 +553,16 @@ struct TdtBeamDev {
     int *live_total;                            // [step cap + 1] live hypotheses of the batch after s steps (zeroed by the host)
     float *hG[2], *cG[2], *ppG[2];              // gathered state of step s in copy s & 1: h, c [L][R][Hp] (h in the sigma layout), pred_proj [R][J]
     float *hN, *cN, *ppN;                       // the prediction-net step's outputs on the gathered state
+    // n-gram LM shallow fusion: lmstate == nullptr is the unfused search, and none of the fields below is looked at
+    int *lmstate; float *lm;                    // [2][R] the beam: the automaton's state after the slot's prefix, the prefix's LM score
+    int *lab_ls; float *lab_lm;                 // [R][K + 1] beside lab_id: the state and LM score after the label (the blank: the row's own)
+    LmDev ngram;
 };
 struct TdtBeamOut {
     int *ids, *start, *end, *dur_idx; float *conf;      // [B][N][max_tokens], zero-filled by the caller
     int *lens; float *score;                            // [B][N]
     int *ok;                                            // [B]
+    float *lm_score;                                    // [B][N], the fused search only (a slot the beam does not fill: 0)
 };
 void launch_tdt_beam_init(const TdtBeamDev &a, hipStream_t s);
 void launch_tdt_beam_gather(const TdtBeamDev &a, int step, hipStream_t s);

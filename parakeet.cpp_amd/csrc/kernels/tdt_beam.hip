@@ -32,7 +32,20 @@
 //   tdt_beam_prune_kernel    60 VGPR 85 SGPR  LDS 18784 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
 //   tdt_beam_gather_kernel   19 VGPR 31 SGPR, tdt_beam_act_kernel 38 VGPR 15 SGPR, tdt_beam_trace_kernel 29 VGPR 35 SGPR, tdt_beam_init_kernel 23 VGPR
 //   36 SGPR: no LDS, no scratch, no spills
+//
+// With n-gram LM shallow fusion (the specification is tests/tdt_beam_lm_ref.py): init, expand, prune and trace are
+// templates on kLm, and the <false> instantiations are the kernels above, instruction for instruction (their figures did not move); the
+// launchers take the <true> ones when TdtBeamDev::lmstate is set.  A beam slot carries two more words, the LM automaton's state after its
+// prefix and the prefix's LM score.  The fused expand: after the K + 1 labels are sorted, lane i <= K that holds a non-blank id runs
+// beam_lm_lookup (ngram_lm_dev.hpp, the fused CTC walk's) -- at most 16 lanes of the wave walk the automaton side by side, the row pays the
+// longest chain once -- and stores lm2 = lm + ((alpha * lp) + beta) and the next state beside the label; the blank's entry holds the row's
+// own.  The fused prune builds its keys from f = score + lm (a finished entry's own two values, a candidate's cand + lm2 of its label), so
+// duplicates and the W best are decided by f; score, lm and the state of a chosen entry go to the new beam.  The fused trace writes lm_score.
+//   tdt_beam_expand_kernel<true>  39 VGPR 70 SGPR  LDS     0 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
+//   tdt_beam_prune_kernel<true>   68 VGPR 86 SGPR  LDS 19040 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
+//   tdt_beam_init_kernel<true> 28 VGPR 42 SGPR, tdt_beam_trace_kernel<true> 29 VGPR 35 SGPR: no LDS, no scratch, no spills
 #include "decode_dev.hpp"
+#include "ngram_lm_dev.hpp"
 
 namespace pk {
 
@@ -51,6 +64,7 @@ __device__ __forceinline__ u64 hash_push(u64 h, int tok) { return (h ^ (u64)(uns
 
 }  // namespace
 
+template <bool kLm>
 __global__ __launch_bounds__(256) void tdt_beam_init_kernel(TdtBeamDev a) {
     const int r = blockIdx.x * 256 + threadIdx.x, R = a.B * a.W;
     if (r < R) {
@@ -59,6 +73,7 @@ __global__ __launch_bounds__(256) void tdt_beam_init_kernel(TdtBeamDev a) {
             const int i = p * R + r;
             a.valid[i] = p == 0 && first; a.t[i] = 0; a.len[i] = 0; a.par[i] = r; a.born[i] = p == 0; a.tok[i] = a.blank;
             a.score[i] = p == 0 && first ? 0.0f : -__builtin_huge_valf(); a.hash[i] = 0;
+            if constexpr (kLm) { a.lmstate[i] = a.ngram.start; a.lm[i] = 0.0f; }
         }
     }
     if (r < a.B) { a.live[r] = 1; a.steps_done[r] = 0; }
@@ -97,6 +112,7 @@ __global__ __launch_bounds__(256) void tdt_beam_act_kernel(TdtBeamDev a, int s, 
     }
 }
 
+template <bool kLm>
 __global__ __launch_bounds__(256) void tdt_beam_expand_kernel(TdtBeamDev a, int s, const float *__restrict__ logits) {
     const int lane = threadIdx.x & 63, R = a.B * a.W;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -180,6 +196,20 @@ __global__ __launch_bounds__(256) void tdt_beam_expand_kernel(TdtBeamDev a, int 
     const float slp = lane < nb ? plp : lane == nb ? lb : ulp;
     const int sid = lane < nb ? pid : lane == nb ? blank : uid;
     if (lane <= K) { a.lab_id[(int64_t)r * (K + 1) + lane] = sid; a.lab_lp[(int64_t)r * (K + 1) + lane] = slp; }
+    if constexpr (kLm) {
+        // one lookup per label: the lanes of the K labels walk the automaton side by side, the row pays the longest chain once
+        if (lane <= K) {
+            int ls = a.lmstate[p * R + r];
+            float lmv = a.lm[p * R + r];
+            if (sid >= 0 && sid != blank) {
+                int nx = 0;
+                const float lp = beam_lm_lookup(a.ngram, ls, sid, nx);
+                lmv = __fadd_rn(lmv, __fadd_rn(__fmul_rn(a.ngram.alpha, lp), a.ngram.beta));    // three roundings, no fma
+                ls = nx;
+            }
+            a.lab_ls[(int64_t)r * (K + 1) + lane] = ls; a.lab_lm[(int64_t)r * (K + 1) + lane] = lmv;
+        }
+    }
     const float sc = a.score[p * R + r];
     const int C = (K + 1) * Kd;
     for (int c0 = 0; c0 < C; c0 += 64) {
@@ -189,6 +219,7 @@ __global__ __launch_bounds__(256) void tdt_beam_expand_kernel(TdtBeamDev a, int 
     }
 }
 
+template <bool kLm>
 __global__ __launch_bounds__(256) void tdt_beam_prune_kernel(TdtBeamDev a, int s) {
     __shared__ u64 key[kPool];
     __shared__ u64 wbest[4];
@@ -197,6 +228,8 @@ __global__ __launch_bounds__(256) void tdt_beam_prune_kernel(TdtBeamDev a, int s
     __shared__ float bs[kTdtBeamMaxWidth];
     __shared__ int sel_w[kTdtBeamMaxWidth], sel_tok[kTdtBeamMaxWidth], sel_t[kTdtBeamMaxWidth], sel_len[kTdtBeamMaxWidth], sel_rec[kTdtBeamMaxWidth];
     __shared__ float sel_score[kTdtBeamMaxWidth], sel_lp[kTdtBeamMaxWidth];
+    __shared__ float blm[kTdtBeamMaxWidth], sel_lm[kTdtBeamMaxWidth];         // (kLm only: the unfused kernel never names them)
+    __shared__ int bls[kTdtBeamMaxWidth], sel_ls[kTdtBeamMaxWidth];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     if (!a.live[b]) return;
     const int W = a.W, K = a.K, Kd = a.Kd, R = a.B * W, MT = a.max_tokens, blank = a.blank;
@@ -207,18 +240,23 @@ __global__ __launch_bounds__(256) void tdt_beam_prune_kernel(TdtBeamDev a, int s
     if (tid < W) {
         const int i = p * R + base + tid;
         bv[tid] = a.valid[i]; bt[tid] = a.t[i]; bl[tid] = a.len[i]; bs[tid] = a.score[i]; bh[tid] = a.hash[i];
+        if constexpr (kLm) { blm[tid] = a.lm[i]; bls[tid] = a.lmstate[i]; }
     }
     __syncthreads();
     u64 mybest = 0;
     for (int pos = tid; pos < P; pos += 256) {
         u64 k = 0;
         if (pos < W) {
-            if (bv[pos] && bt[pos] >= T) k = pool_key(bs[pos], pos);
+            if (bv[pos] && bt[pos] >= T) k = pool_key(kLm ? __fadd_rn(bs[pos], blm[pos]) : bs[pos], pos);
         } else {
             const int w = (pos - W) / C, c = (pos - W) - w * C;
             if (bv[w] && bt[w] < T) {
                 const int id = a.lab_id[(int64_t)(base + w) * (K + 1) + c / Kd];
-                if (id >= 0 && (id == blank || bl[w] < MT)) k = pool_key(a.cand[(int64_t)(base + w) * C + c], pos);
+                if (id >= 0 && (id == blank || bl[w] < MT)) {
+                    float f = a.cand[(int64_t)(base + w) * C + c];
+                    if constexpr (kLm) f = __fadd_rn(f, a.lab_lm[(int64_t)(base + w) * (K + 1) + c / Kd]);      // the keys order by f = score + lm
+                    k = pool_key(f, pos);
+                }
             }
         }
         key[pos] = k;
@@ -240,16 +278,19 @@ __global__ __launch_bounds__(256) void tdt_beam_prune_kernel(TdtBeamDev a, int s
         const int pos = (int)(0xFFFFFFFFu - (unsigned)v);
         // what the entry is
         int w, tok = -1, rec = 0, tn, ln;
-        float lp = 0.0f, sc;
+        float lp = 0.0f, sc, lmv = 0.0f;
+        int lms = 0;
         u64 hn;
         if (pos < W) {
             w = pos; tn = bt[w]; ln = bl[w]; sc = bs[w]; hn = bh[w];
+            if constexpr (kLm) { lmv = blm[w]; lms = bls[w]; }
         } else {
             w = (pos - W) / C;
             const int c = (pos - W) - w * C, li = c / Kd, dr = c - li * Kd;
             const int id = a.lab_id[(int64_t)(base + w) * (K + 1) + li], dix = a.dur_i[(int64_t)(base + w) * Kd + dr];
             const int dur = a.durations[dix];
             sc = a.cand[(int64_t)(base + w) * C + c];
+            if constexpr (kLm) { lmv = a.lab_lm[(int64_t)(base + w) * (K + 1) + li]; lms = a.lab_ls[(int64_t)(base + w) * (K + 1) + li]; }
             if (id == blank) { tn = bt[w] + (dur > 1 ? dur : 1); ln = bl[w]; hn = bh[w]; }
             else {
                 tok = id; lp = a.lab_lp[(int64_t)(base + w) * (K + 1) + li]; rec = bt[w] * 8 + dix;
@@ -276,6 +317,7 @@ __global__ __launch_bounds__(256) void tdt_beam_prune_kernel(TdtBeamDev a, int s
             if (!dup) {
                 sel_w[nsel] = w; sel_tok[nsel] = tok; sel_t[nsel] = tn; sel_len[nsel] = ln; sel_hash[nsel] = hn; sel_score[nsel] = sc;
                 sel_lp[nsel] = lp; sel_rec[nsel] = rec;
+                if constexpr (kLm) { sel_lm[nsel] = lmv; sel_ls[nsel] = lms; }
             }
         }
         __syncthreads();
@@ -298,6 +340,7 @@ __global__ __launch_bounds__(256) void tdt_beam_prune_kernel(TdtBeamDev a, int s
         a.valid[i] = on; a.t[i] = on ? sel_t[tid] : 0; a.len[i] = on ? sel_len[tid] : 0; a.score[i] = on ? sel_score[tid] : -__builtin_huge_valf();
         a.hash[i] = on ? sel_hash[tid] : 0; a.par[i] = base + (on ? sel_w[tid] : tid); a.born[i] = on && sel_tok[tid] >= 0;
         a.tok[i] = on && sel_tok[tid] >= 0 ? sel_tok[tid] : blank;
+        if constexpr (kLm) { a.lm[i] = on ? sel_lm[tid] : 0.0f; a.lmstate[i] = on ? sel_ls[tid] : 0; }
         a.bp[(int64_t)s * R + base + tid] = make_int4(on ? sel_w[tid] : tid, on ? sel_tok[tid] : -1, on ? sel_rec[tid] : 0, on ? __float_as_int(sel_lp[tid]) : 0);
     }
     if (tid == 0) {
@@ -308,6 +351,7 @@ __global__ __launch_bounds__(256) void tdt_beam_prune_kernel(TdtBeamDev a, int s
     }
 }
 
+template <bool kLm>
 __global__ __launch_bounds__(64) void tdt_beam_trace_kernel(TdtBeamDev a, TdtBeamOut o) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= a.B * a.N) return;
@@ -322,6 +366,7 @@ __global__ __launch_bounds__(64) void tdt_beam_trace_kernel(TdtBeamDev a, TdtBea
         }
     }
     if (n == 0) o.ok[b] = any;
+    if constexpr (kLm) o.lm_score[i] = slot < 0 ? 0.0f : a.lm[p * R + base + slot];
     if (slot < 0) { o.lens[i] = 0; o.score[i] = -__builtin_huge_valf(); return; }        // (the token arrays are zero-filled by the host)
     int u = a.len[p * R + base + slot];
     o.lens[i] = u; o.score[i] = a.score[p * R + base + slot];
@@ -341,7 +386,8 @@ __global__ __launch_bounds__(64) void tdt_beam_trace_kernel(TdtBeamDev a, TdtBea
 
 void launch_tdt_beam_init(const TdtBeamDev &a, hipStream_t s) {
     const int n = a.B * a.W;
-    hipLaunchKernelGGL(tdt_beam_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    if (a.lmstate) hipLaunchKernelGGL(tdt_beam_init_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(tdt_beam_init_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
 }
 void launch_tdt_beam_gather(const TdtBeamDev &a, int step, hipStream_t s) {
     hipLaunchKernelGGL(tdt_beam_gather_kernel, dim3((unsigned)(a.B * a.W)), dim3(256), 0, s, a, step);
@@ -350,7 +396,8 @@ void launch_tdt_beam_act(const TdtBeamDev &a, int step, const float *ep, float *
     hipLaunchKernelGGL(tdt_beam_act_kernel, dim3((unsigned)((a.B * a.W + 3) / 4)), dim3(256), 0, s, a, step, ep, z);
 }
 void launch_tdt_beam_expand(const TdtBeamDev &a, int step, const float *logits, hipStream_t s) {
-    hipLaunchKernelGGL(tdt_beam_expand_kernel, dim3((unsigned)((a.B * a.W + 3) / 4)), dim3(256), 0, s, a, step, logits);
+    if (a.lmstate) hipLaunchKernelGGL(tdt_beam_expand_kernel<true>, dim3((unsigned)((a.B * a.W + 3) / 4)), dim3(256), 0, s, a, step, logits);
+    else hipLaunchKernelGGL(tdt_beam_expand_kernel<false>, dim3((unsigned)((a.B * a.W + 3) / 4)), dim3(256), 0, s, a, step, logits);
 }
 void launch_tdt_beam_prune(const TdtBeamDev &a, int step, hipStream_t s) {
     if (a.W < 1 || a.W > kTdtBeamMaxWidth || a.K < 1 || a.K > kTdtBeamMaxLabels || a.Kd < 1 || a.Kd > kTdtBeamMaxDurs || a.D < 1 || a.D > 8 || a.Kd > a.D ||
@@ -358,10 +405,12 @@ void launch_tdt_beam_prune(const TdtBeamDev &a, int step, hipStream_t s) {
         fprintf(stderr, "parakeet_amd: internal error: launch_tdt_beam_prune outside the kernel's limits (W %d, K %d, Kd %d, D %d)\n", a.W, a.K, a.Kd, a.D);
         abort();
     }
-    hipLaunchKernelGGL(tdt_beam_prune_kernel, dim3((unsigned)a.B), dim3(256), 0, s, a, step);
+    if (a.lmstate) hipLaunchKernelGGL(tdt_beam_prune_kernel<true>, dim3((unsigned)a.B), dim3(256), 0, s, a, step);
+    else hipLaunchKernelGGL(tdt_beam_prune_kernel<false>, dim3((unsigned)a.B), dim3(256), 0, s, a, step);
 }
 void launch_tdt_beam_trace(const TdtBeamDev &a, const TdtBeamOut &o, hipStream_t s) {
-    hipLaunchKernelGGL(tdt_beam_trace_kernel, dim3((unsigned)((a.B * a.N + 63) / 64)), dim3(64), 0, s, a, o);
+    if (a.lmstate) hipLaunchKernelGGL(tdt_beam_trace_kernel<true>, dim3((unsigned)((a.B * a.N + 63) / 64)), dim3(64), 0, s, a, o);
+    else hipLaunchKernelGGL(tdt_beam_trace_kernel<false>, dim3((unsigned)((a.B * a.N + 63) / 64)), dim3(64), 0, s, a, o);
 }
 
 }  // namespace pk

@@ -29,7 +29,7 @@ void tdt_beam_model_checks(const Model &m, const pk_tdt_beam_options &o) {
     if (o.n_best < 1 || o.n_best > o.beam_width) fail(PK_ERR_UNSUPPORTED, "TDT beam search: n_best %d outside 1..beam_width", o.n_best);
 }
 
-size_t tdt_beam_scratch(const Model &m, int B, int t_max, int W, int K, int Kd, int N, int max_tokens) {
+size_t tdt_beam_scratch(const Model &m, int B, int t_max, int W, int K, int Kd, int N, int max_tokens, bool fused) {
     const pk_config &c = m.cfg;
     const size_t R = (size_t)B * W, C = (size_t)(K + 1) * Kd, cap = (size_t)t_max + max_tokens, MT = (size_t)max_tokens;
     size_t n = 2 * R * (36 + 4 * MT);
@@ -38,10 +38,11 @@ size_t tdt_beam_scratch(const Model &m, int B, int t_max, int W, int K, int Kd, 
     n += (6 * (size_t)c.num_lstm_layers * R * c.pred_hidden + 3 * R * c.joint_hidden) * 4;
     n += R * ((size_t)c.joint_hidden + c.vocab_size + c.num_durations) * 4;
     n += (size_t)B * N * (5 * MT + 2) * 4 + (4 * (size_t)B + cap + 1) * 4;
+    if (fused) n += 2 * R * 8 + R * 8 * (size_t)(K + 1) + (size_t)B * N * 4;
     return n;
 }
 
-void tdt_beam_plan(TdtBeamWs &ws, const Model &m, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options &o, int max_tokens) {
+void tdt_beam_plan(TdtBeamWs &ws, const Model &m, const int32_t *n_frames, int B, int T, const pk_tdt_beam_options &o, int max_tokens, bool fused) {
     const int V = m.cfg.vocab_size, D = m.cfg.num_durations;
     const int K = std::min<int>(o.label_prune, V - 1), Kd = std::min<int>(o.duration_prune, D);
     int t_max = 0;
@@ -55,10 +56,11 @@ void tdt_beam_plan(TdtBeamWs &ws, const Model &m, const int32_t *n_frames, int B
     }
     // (every factor is bounded first: the byte count below then stays far from overflow)
     if ((int64_t)max_tokens > ((int64_t)1 << 24) || (int64_t)B * o.beam_width > ((int64_t)1 << 24) ||
-        tdt_beam_scratch(m, B, t_max, o.beam_width, K, Kd, o.n_best, max_tokens) > kTdtBeamMaxScratch)
+        tdt_beam_scratch(m, B, t_max, o.beam_width, K, Kd, o.n_best, max_tokens, fused) > kTdtBeamMaxScratch)
         fail(PK_ERR_UNSUPPORTED, "TDT beam search: the scratch of this call (beam, back-pointers, state, products) exceeds the cap of %zu bytes", kTdtBeamMaxScratch);
     ws.h_tab.swap(tab);
     ws.B = B; ws.W = o.beam_width; ws.K = K; ws.Kd = Kd; ws.N = o.n_best; ws.max_tokens = max_tokens; ws.t_max = t_max; ws.cap = t_max + max_tokens;
+    ws.fused = fused;
 }
 
 TdtBeamDev TdtBeamWs::dev(const Model &m) const {
@@ -80,6 +82,10 @@ TdtBeamDev TdtBeamWs::dev(const Model &m) const {
     a.hG[0] = f; a.hG[1] = f + hs; a.hN = f + 2 * hs; a.cG[0] = f + 3 * hs; a.cG[1] = f + 4 * hs; a.cN = f + 5 * hs;
     f += 6 * hs;
     a.ppG[0] = f; a.ppG[1] = f + ps; a.ppN = f + 2 * ps;
+    if (fused) {
+        a.lmstate = lmslot.as<int>(); a.lm = reinterpret_cast<float *>(a.lmstate + 2 * R);
+        a.lab_ls = lmlab.as<int>(); a.lab_lm = reinterpret_cast<float *>(a.lab_ls + R * (K + 1));
+    }
     return a;
 }
 
@@ -89,10 +95,12 @@ TdtBeamOut TdtBeamWs::out_view() const {
     int *p = out.as<int>();
     o.ids = p; o.start = p + tok; o.end = p + 2 * tok; o.dur_idx = p + 3 * tok; o.conf = reinterpret_cast<float *>(p + 4 * tok);
     o.lens = p + 5 * tok; o.score = reinterpret_cast<float *>(p + 5 * tok + hy); o.ok = p + 5 * tok + 2 * hy;
+    if (fused) o.lm_score = reinterpret_cast<float *>(o.ok + B);
     return o;
 }
 
-void run_tdt_beam(Model &m, TdtBeamWs &ws, const float *d_ep, hipStream_t s) {
+void run_tdt_beam(Model &m, TdtBeamWs &ws, const float *d_ep, hipStream_t s, const LmDev *lm) {
+    if ((lm != nullptr) != ws.fused) fail(PK_ERR_INVALID, "internal error: run_tdt_beam and tdt_beam_plan disagree about the language model");
     const pk_config &c = m.cfg;
     const int B = ws.B, W = ws.W, K = ws.K, Kd = ws.Kd, N = ws.N, MT = ws.max_tokens, cap = ws.cap;
     const int V = c.vocab_size, D = c.num_durations, J = c.joint_hidden, L = c.num_lstm_layers, Hp = c.pred_hidden;
@@ -107,8 +115,10 @@ void run_tdt_beam(Model &m, TdtBeamWs &ws, const float *d_ep, hipStream_t s) {
     ws.state.reserve((6 * hs + 3 * ps) * 4);
     ws.z.reserve(R * J * 4); ws.logits.reserve(R * (size_t)(V + D) * 4);
     const size_t tok = (size_t)B * N * MT, hy = (size_t)B * N;
-    ws.out.reserve((5 * tok + 2 * hy + B) * 4);
-    const TdtBeamDev a = ws.dev(m);
+    ws.out.reserve((5 * tok + 2 * hy + B + (lm ? hy : 0)) * 4);
+    if (lm) { ws.lmslot.reserve(4 * R * 4); ws.lmlab.reserve(2 * R * (K + 1) * 4); }
+    TdtBeamDev a = ws.dev(m);
+    if (lm) a.ngram = *lm;
     const TdtBeamOut o = ws.out_view();
     PK_HIP(hipMemcpyAsync(ws.tab.p, ws.h_tab.data(), ws.h_tab.size() * 4, hipMemcpyHostToDevice, s));
     PK_HIP(hipMemsetAsync(ws.ctl.p, 0, (2 * (size_t)B + cap + 1) * 4, s));
@@ -150,7 +160,7 @@ void run_tdt_beam(Model &m, TdtBeamWs &ws, const float *d_ep, hipStream_t s) {
 }
 
 void tdt_beam_copy_out(const TdtBeamWs &ws, int32_t *ids, int32_t *lens, float *score, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf,
-                       int32_t *ok, hipStream_t s) {
+                       int32_t *ok, hipStream_t s, float *lm_score) {
     const size_t tok = (size_t)ws.B * ws.N * ws.max_tokens, hy = (size_t)ws.B * ws.N;
     const TdtBeamOut o = ws.out_view();
     if (ids) PK_HIP(hipMemcpyAsync(ids, o.ids, tok * 4, hipMemcpyDeviceToHost, s));
@@ -161,13 +171,14 @@ void tdt_beam_copy_out(const TdtBeamWs &ws, int32_t *ids, int32_t *lens, float *
     if (lens) PK_HIP(hipMemcpyAsync(lens, o.lens, hy * 4, hipMemcpyDeviceToHost, s));
     if (score) PK_HIP(hipMemcpyAsync(score, o.score, hy * 4, hipMemcpyDeviceToHost, s));
     if (ok) PK_HIP(hipMemcpyAsync(ok, o.ok, (size_t)ws.B * 4, hipMemcpyDeviceToHost, s));
+    if (lm_score && o.lm_score) PK_HIP(hipMemcpyAsync(lm_score, o.lm_score, hy * 4, hipMemcpyDeviceToHost, s));
     PK_HIP(hipStreamSynchronize(s));
 }
 
 size_t tdt_beam_bytes(const TdtBeamWs &ws) {
     size_t n = 0;
     for (const DevBuf *b : {&ws.tab, &ws.ints, &ws.score, &ws.hash, &ws.prefix, &ws.lab_id, &ws.lab_lp, &ws.dur_i, &ws.dur_lp, &ws.cand, &ws.bp, &ws.ctl, &ws.state,
-                            &ws.z, &ws.logits, &ws.out})
+                            &ws.z, &ws.logits, &ws.out, &ws.lmslot, &ws.lmlab})
         n += b->cap;
     return n;
 }

@@ -14,7 +14,7 @@
 // New: --spot "phrase" (repeatable) / --spot-file path.txt (one phrase per line) (tdt-ctc-110m) searches the audio for every phrase (CTC keyword
 // spotting) and prints one line per hit: phrase<TAB>start<TAB>end<TAB>score (seconds; score <= 0, 0 = the greedy path over the span is the phrase).
 // --spot-hits N: up to N non-overlapping hits per phrase (default 1); --spot-min-score X: only hits with score >= X (default: no threshold).
-// New: --lm file.arpa (with --beam W and the CTC decoder) fuses an n-gram language model over token ids into the beam search (shallow fusion):
+// New: --lm file.arpa (with --beam W and the CTC decoder, or with --beam W --beam-head tdt) fuses an n-gram language model over token ids into the beam search (shallow fusion):
 // hypotheses rank by acoustic score + LM score, LM score = sum per token of A * log p + B (--lm-alpha A, default 0.5; --lm-beta B, default 0);
 // both parts are printed.  tools/make_token_corpus.py turns text into the id lines an n-gram trainer makes such a file from.
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
@@ -44,6 +44,7 @@ static void usage(const char *prog) {
               << "  --nbest N --rescore-tdt W  the N best hypotheses re-ranked by (1 - W) * CTC score + W * TDT log-likelihood\n"
               << "  --spot \"phrase\" (repeatable) | --spot-file path.txt  where was each phrase said: phrase<TAB>start<TAB>end<TAB>score per hit\n"
               << "  --beam W --lm file.arpa [--lm-alpha A] [--lm-beta B]  the CTC beam search fused with an n-gram model over token ids\n"
+              << "  --beam W --beam-head tdt --lm file.arpa [--lm-alpha A] [--lm-beta B]  the TDT beam search fused with the model; both scores per hypothesis\n"
               << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
@@ -206,8 +207,9 @@ int main(int argc, char **argv) {
         if (!spot.empty() && vocab.empty()) { std::cerr << "Error: --spot needs --vocab\n"; return 1; }
         if (rescore && !nbest_given) { std::cerr << "Error: --rescore-tdt needs --nbest N\n"; return 1; }
         if (rescore && model != "tdt-ctc-110m") { std::cerr << "Error: --rescore-tdt needs a model with both heads (--model tdt-ctc-110m)\n"; return 1; }
-        if (!lm_path.empty() && (beam <= 0 || beam_tdt || rescore || model != "tdt-ctc-110m")) {
-            std::cerr << "Error: --lm needs --beam W with the CTC head of --model tdt-ctc-110m (no TDT beam, no --rescore-tdt)\n";
+        if (!lm_path.empty() && (beam <= 0 || rescore || (beam_tdt ? model != "tdt-ctc-110m" && model != "tdt-600m" : model != "tdt-ctc-110m"))) {
+            std::cerr << "Error: --lm needs --beam W with the CTC head of --model tdt-ctc-110m, or --beam W --beam-head tdt with --model tdt-ctc-110m or "
+                         "tdt-600m (no --rescore-tdt)\n";
             return 1;
         }
         if (beam_tdt && beam <= 0) { std::cerr << "Error: --beam-head needs --beam W\n"; return 1; }
@@ -223,6 +225,17 @@ int main(int argc, char **argv) {
         };
         TdtBeamOptions tbo;
         tbo.beam_width = beam; tbo.n_best = nbest; tbo.timestamps = timestamps;
+        // ... with --lm: the fused search, lists in fused order, the acoustic and the LM score of every hypothesis
+        auto print_tdt_beam_lm = [&](const LanguageModel &lm, const std::vector<LmScoredResult> &hyps, double ms) {
+            std::cout << "Beam search (tdt): width " << beam << ", " << lm.order() << "-gram model (" << lm.num_ngrams() << " n-grams), alpha "
+                      << std::defaultfloat << lm_opts.alpha << " beta " << lm_opts.beta << ", " << hyps.size() << " hypotheses\n";
+            for (size_t j = 0; j < hyps.size(); ++j) {
+                std::cout << "\n=== Hypothesis " << j << " score " << std::setprecision(9) << std::defaultfloat << hyps[j].score << " lm " << hyps[j].lm_score
+                          << " ===\n";
+                print_result(hyps[j].result, timestamps, ms);
+            }
+            return 0;
+        };
         std::cout << "Loading model: " << model << std::endl;
         if (model == "tdt-ctc-110m") {
             Transcriber t(weights, vocab);
@@ -245,6 +258,12 @@ int main(int argc, char **argv) {
             }
             if (!boost.empty()) std::cout << "Phrase boost: " << boost.size() << " phrases\n";
             if (beam > 0 && beam_tdt) {
+                if (!lm_path.empty()) {
+                    const LanguageModel lm(lm_path);
+                    const auto t0 = Clock::now();
+                    const auto hyps = t.transcribe_nbest_tdt(audio_path, tbo, lm, lm_opts);
+                    return print_tdt_beam_lm(lm, hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+                }
                 const auto t0 = Clock::now();
                 const auto hyps = t.transcribe_nbest_tdt(audio_path, tbo);
                 return print_tdt_beam(hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
@@ -288,6 +307,12 @@ int main(int argc, char **argv) {
             if (score) return run_score(t, audio_path, score_text);
             if (beam > 0) {
                 if (!beam_tdt) { std::cerr << "Error: this model has no CTC head: --beam needs --beam-head tdt\n"; return 1; }
+                if (!lm_path.empty()) {
+                    const LanguageModel lm(lm_path);
+                    const auto t0 = Clock::now();
+                    const auto hyps = t.transcribe_nbest(audio_path, tbo, lm, lm_opts);
+                    return print_tdt_beam_lm(lm, hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+                }
                 const auto t0 = Clock::now();
                 const auto hyps = t.transcribe_nbest(audio_path, tbo);
                 return print_tdt_beam(hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());

@@ -110,7 +110,7 @@ class LanguageModel {
     LanguageModel &operator=(const LanguageModel &) = delete;
     int order() const { return pk_lm_order(lm_); }
     int64_t num_ngrams() const { return pk_lm_num_ngrams(lm_); }
-    /// pk_lm_score of one token string: its fp32 natural-log probability (host only); what an n-best list of either beam is rescored with
+    /// pk_lm_score of one token string: its fp32 natural-log probability (host only); what an n-best list is rescored with
     float score(const std::vector<int> &token_ids, bool bos = true, bool eos = false) const {
         std::vector<int32_t> ids(token_ids.begin(), token_ids.end());
         const int32_t off[2] = {0, (int32_t)ids.size()};
@@ -339,6 +339,43 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return run_nbest_tdt(pcm, (size_t)n, opts);
     }
 
+    // pk_transcribe_pcm_nbest_tdt_lm on one clip: the TDT beam search with n-gram LM shallow fusion, hypotheses in fused order
+    std::vector<LmScoredResult> run_nbest_tdt_lm(const float *pcm, size_t n, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
+        if (!on_gpu_) to_gpu(0);
+        pk_tdt_beam_options o;
+        pk_tdt_beam_options_default(&o);
+        o.beam_width = opts.beam_width; o.label_prune = opts.label_prune; o.duration_prune = opts.duration_prune; o.n_best = opts.n_best;
+        pk_lm_options lo{lmo.alpha, lmo.beta};
+        const int64_t offsets[2] = {0, (int64_t)n};
+        std::vector<float> lms((size_t)std::max(1, opts.n_best), 0.0f);
+        pk_nbest *res = nullptr;
+        check(pk_transcribe_pcm_nbest_tdt_lm(m_, pcm, offsets, 1, &o, opts.timestamps ? 1 : 0, &res, lm.handle(), &lo, lms.data()));
+        std::vector<LmScoredResult> out(res[0].n_hyp);
+        for (int j = 0; j < res[0].n_hyp; ++j) {
+            const pk_result &r = res[0].hyp[j];
+            out[j].score = res[0].score[j];
+            out[j].lm_score = lms[j];
+            out[j].result.text = r.text ? r.text : "";
+            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
+            if (opts.timestamps) {
+                for (int k = 0; k < r.n_tokens; ++k)
+                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
+                for (int k = 0; k < r.n_words; ++k)
+                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
+            }
+        }
+        pk_nbest_free(res, 1);
+        return out;
+    }
+    std::vector<LmScoredResult> run_nbest_tdt_lm_file(const std::string &audio_path, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return run_nbest_tdt_lm(pcm, (size_t)n, opts, lm, lmo);
+    }
+
     // pk_transcribe_pcm_nbest_rescored on one clip: run_nbest's list re-ranked by the TDT head's log-likelihood of every hypothesis
     std::vector<RescoredResult> run_nbest_rescored(const float *pcm, size_t n, const BeamOptions &opts, const RescoreOptions &rescore) {
         if (!on_gpu_) to_gpu(0);
@@ -557,6 +594,13 @@ class Transcriber {
     /// New: the same search through this model's TDT head (TDTTranscriber::transcribe_nbest)
     std::vector<ScoredResult> transcribe_nbest_tdt(const std::string &audio_path, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt_file(audio_path, opts); }
     std::vector<ScoredResult> transcribe_nbest_tdt(const float *pcm, size_t n, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt(pcm, n, opts); }
+    /// New: the TDT beam search with n-gram LM shallow fusion (pk_transcribe_pcm_nbest_tdt_lm): fused order, score + lm_score
+    std::vector<LmScoredResult> transcribe_nbest_tdt(const std::string &audio_path, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {
+        return eng_.run_nbest_tdt_lm_file(audio_path, opts, lm, lm_opts);
+    }
+    std::vector<LmScoredResult> transcribe_nbest_tdt(const float *pcm, size_t n, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {
+        return eng_.run_nbest_tdt_lm(pcm, n, opts, lm, lm_opts);
+    }
     /// New: the log-likelihood of a given transcript: tdt_head = true through the TDT head's forward algorithm
     /// (pk_tdt_score_pcm; no CTC head needed).  false throws std::invalid_argument: the CTC head's log-likelihood is align()'s AlignResult::total.
     ScoreResult score(const std::string &audio_path, const std::string &text, bool tdt_head = true) { return eng_.run_score_file(audio_path, text, tdt_head); }
@@ -644,6 +688,13 @@ class TDTTranscriber {
     std::vector<ScoredResult> transcribe_nbest(const float *pcm, size_t n, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt(pcm, n, opts); }
     std::vector<ScoredResult> transcribe_nbest(const std::vector<float> &samples, const TdtBeamOptions &opts = {}) {
         return eng_.run_nbest_tdt(samples.data(), samples.size(), opts);
+    }
+    /// New: the search with n-gram LM shallow fusion (pk_transcribe_pcm_nbest_tdt_lm): fused order, score + lm_score
+    std::vector<LmScoredResult> transcribe_nbest(const std::string &audio_path, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {
+        return eng_.run_nbest_tdt_lm_file(audio_path, opts, lm, lm_opts);
+    }
+    std::vector<LmScoredResult> transcribe_nbest(const float *pcm, size_t n, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {
+        return eng_.run_nbest_tdt_lm(pcm, n, opts, lm, lm_opts);
     }
     /// New: the log-likelihood of a given transcript: tdt_head = true through the TDT head's forward algorithm
     /// (pk_tdt_score_pcm; no CTC head needed).  false throws std::invalid_argument: the CTC head's log-likelihood is align()'s AlignResult::total.
