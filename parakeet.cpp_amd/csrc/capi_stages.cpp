@@ -33,6 +33,77 @@ static int size_ws(Model &m, const int32_t *n_frames, int B, int T, size_t &rows
     return T;
 }
 
+namespace {
+
+// The events of a _timed entry point: destroyed on every exit path.
+template <int N>
+struct Events {
+    hipEvent_t e[N] = {};
+    void create() { for (auto &x : e) PK_HIP(hipEventCreate(&x)); }
+    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+float median_of(std::vector<float> &v) {
+    std::sort(v.begin(), v.end());
+    return v[v.size() / 2];
+}
+// Times S stages that follow each other on the model's stream.  queue(ev) queues them once and records ev[k] before stage k, ev[S] after the
+// last.  reps + 1 passes, each waited for and checked; the first warms the buffers up and is not counted.  -> ms[k]: the median of stage k.
+template <int S, class Queue>
+void time_stages(Model &m, int reps, float *ms, Queue &&queue) {
+    Events<S + 1> ev;
+    ev.create();
+    std::vector<float> t[S];
+    for (int r = 0; r <= reps; ++r) {
+        queue(ev.e);
+        PK_HIP(hipStreamSynchronize(m.stream));
+        PK_CHECK_LAUNCH();
+        for (int k = 0; k < S; ++k) {
+            float v = 0;
+            PK_HIP(hipEventElapsedTime(&v, ev.e[k], ev.e[k + 1]));
+            if (r > 0) t[k].push_back(v);
+        }
+    }
+    for (int k = 0; k < S; ++k) ms[k] = median_of(t[k]);
+}
+
+// The log-prob rows of the entry points that take them from the host (pk_ctc_beam_search, pk_ctc_align, pk_ctc_kws): [B][T], or packed with
+// n_frames[b] rows of utterance b.  Two halves, so that a caller can refuse (no device, a plan that does not fit) between them.
+struct HostRows {
+    int64_t rows = 0;                                              // frames of the batch
+    int T = 0;                                                     // the longest utterance
+    std::vector<int32_t> tab;                                      // ragged: T[B] then T_off[B + 1]
+    DevBuf d_lp, d_tab;                                            // alive for the call
+
+    // host only: checks n_frames, counts the rows and builds the table
+    void plan(const int32_t *n_frames, int B, int T_uniform) {
+        rows = (int64_t)B * T_uniform; T = T_uniform;
+        if (!n_frames) return;
+        tab.resize(2 * (size_t)B + 1);
+        rows = 0; T = 0;
+        for (int b = 0; b < B; ++b) {
+            need(n_frames[b] > 0, "n_frames[b] must be positive");
+            tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
+            rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
+            need(rows < ((int64_t)1 << 31), "too many frames");
+        }
+        tab[2 * (size_t)B] = (int32_t)rows;
+    }
+    // uploads logp [rows][V] (-> d_lp) and the table; -> the ragged extents on the device (uniform: none)
+    SeqRag upload(const float *logp, int B, int V) {
+        d_lp.reserve((size_t)rows * V * 4);
+        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
+        SeqRag rag;
+        if (!tab.empty()) {
+            d_tab.reserve(tab.size() * 4);
+            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
+        }
+        return rag;
+    }
+};
+
+}  // namespace
+
 static void conformer_blocks(Model &m, const float *x_in, const int32_t *n_frames, int B, int T, int first_layer, int n_layers, float *x_out) {
     m.require_gpu();
     need(first_layer >= 0 && n_layers >= 0 && first_layer + n_layers <= m.cfg.num_layers, "layer range");
@@ -442,30 +513,11 @@ static pk_status ctc_beam_search(const float *logp, const int32_t *n_frames, int
         need_device();
         LmDev lmd{};
         if (fused) lmd = lm_device_view(lm, lm_opt);
-        int64_t rows = (int64_t)B * T;
-        std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
-        if (n_frames) {
-            tab.resize(2 * (size_t)B + 1);
-            rows = 0; T = 0;
-            for (int b = 0; b < B; ++b) {
-                need(n_frames[b] > 0, "n_frames[b] must be positive");
-                tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
-                rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
-                need(rows < ((int64_t)1 << 31), "too many frames");
-            }
-            tab[2 * (size_t)B] = (int32_t)rows;
-        }
+        HostRows in;
+        in.plan(n_frames, B, T);
         BeamWs ws;
-        DevBuf d_lp, d_tab;
-        d_lp.reserve((size_t)rows * V * 4);
-        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
-        SeqRag rag;
-        if (n_frames) {
-            d_tab.reserve(tab.size() * 4);
-            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
-        }
-        run_ctc_beam(ws, d_lp.as<float>(), B, T, rows, rag, V, blank, o, nullptr, fused ? &lmd : nullptr);
+        const SeqRag rag = in.upload(logp, B, V);
+        run_ctc_beam(ws, in.d_lp.as<float>(), B, in.T, in.rows, rag, V, blank, o, nullptr, fused ? &lmd : nullptr);
         PK_CHECK_LAUNCH();
         const bool ts = o.timestamps != 0;
         beam_copy_out(ws, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, nullptr, fused ? lm_score : nullptr);
@@ -535,24 +587,13 @@ static pk_status ctc_beam_decode_timed(pk_model *h, const float *enc, const int3
         T = size_ws(m, n_frames, B, T, rows);
         const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
         PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
-        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
-        std::vector<float> greedy, beam;
-        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
-            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+        time_stages<2>(m, reps, ms, [&](hipEvent_t *ev) {          // the greedy head, the search
+            PK_HIP(hipEventRecord(ev[0], m.stream));
             m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
-            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            PK_HIP(hipEventRecord(ev[1], m.stream));
             run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), B, T, (int64_t)rows, rag, V, blank, o, m.stream, fused ? &lmd : nullptr);
-            PK_HIP(hipEventRecord(ev.e[2], m.stream));
-            PK_HIP(hipStreamSynchronize(m.stream));
-            PK_CHECK_LAUNCH();
-            float a = 0, b = 0;
-            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-            if (r > 0) { greedy.push_back(a); beam.push_back(b); }
-        }
-        std::sort(greedy.begin(), greedy.end()); std::sort(beam.begin(), beam.end());
-        ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
+            PK_HIP(hipEventRecord(ev[2], m.stream));
+        });
     });
 }
 
@@ -646,25 +687,14 @@ static pk_status tdt_beam_decode_timed(pk_model *h, const float *enc, const int3
         size_t rows;
         T = size_ws(m, n_frames, B, T, rows);
         PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
-        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
-        std::vector<float> greedy, beam;
-        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
-            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+        time_stages<2>(m, reps, ms, [&](hipEvent_t *ev) {          // the greedy decode, the search
+            PK_HIP(hipEventRecord(ev[0], m.stream));
             m.run_tdt(m.ws, m.ws.x.as<float>(), B, T, m.ws.max_tokens, m.stream);
-            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            PK_HIP(hipEventRecord(ev[1], m.stream));
             m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
             run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream, fused ? &lmd : nullptr);
-            PK_HIP(hipEventRecord(ev.e[2], m.stream));
-            PK_HIP(hipStreamSynchronize(m.stream));
-            PK_CHECK_LAUNCH();
-            float a = 0, b = 0;
-            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-            if (r > 0) { greedy.push_back(a); beam.push_back(b); }
-        }
-        std::sort(greedy.begin(), greedy.end()); std::sort(beam.begin(), beam.end());
-        ms[0] = greedy[greedy.size() / 2]; ms[1] = beam[beam.size() / 2];
+            PK_HIP(hipEventRecord(ev[2], m.stream));
+        });
     });
 }
 
@@ -688,32 +718,13 @@ pk_status pk_ctc_align(const float *logp, const int32_t *n_frames, int B, int T,
         need(logp && score && ok, "logp/score/ok");
         need(id_offsets[B] == 0 || (start && end && conf), "start/end/conf");
         need(n_frames || T > 0, "T");
-        int64_t rows = (int64_t)B * T;
-        std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
-        if (n_frames) {
-            tab.resize(2 * (size_t)B + 1);
-            rows = 0; T = 0;
-            for (int b = 0; b < B; ++b) {
-                need(n_frames[b] > 0, "n_frames[b] must be positive");
-                tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
-                rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
-                need(rows < ((int64_t)1 << 31), "too many frames");
-            }
-            tab[2 * (size_t)B] = (int32_t)rows;
-        }
+        HostRows in;
+        in.plan(n_frames, B, T);
         need_device();
         AlignWs ws;
-        align_plan(ws, n_frames, B, T, id_offsets);                // (refuses before anything is allocated)
-        DevBuf d_lp, d_tab;
-        d_lp.reserve((size_t)rows * V * 4);
-        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
-        SeqRag rag;
-        if (n_frames) {
-            d_tab.reserve(tab.size() * 4);
-            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
-        }
-        run_ctc_align(ws, d_lp.as<float>(), B, T, rag, V, blank, ids, total != nullptr, nullptr);
+        align_plan(ws, n_frames, B, in.T, id_offsets);             // (refuses before anything is allocated)
+        const SeqRag rag = in.upload(logp, B, V);
+        run_ctc_align(ws, in.d_lp.as<float>(), B, in.T, rag, V, blank, ids, total != nullptr, nullptr);
         PK_CHECK_LAUNCH();
         align_copy_out(ws, start, end, conf, score, total, ok, nullptr);
     });
@@ -750,24 +761,13 @@ pk_status pk_ctc_align_decode_timed(pk_model *h, const float *enc, const int32_t
         T = size_ws(m, n_frames, B, T, rows);
         const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
         PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
-        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
-        std::vector<float> head, align;
-        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
-            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+        time_stages<2>(m, reps, ms, [&](hipEvent_t *ev) {          // the head, the alignment
+            PK_HIP(hipEventRecord(ev[0], m.stream));
             m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
-            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            PK_HIP(hipEventRecord(ev[1], m.stream));
             run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), B, T, rag, V, blank, ids, want_total != 0, m.stream);
-            PK_HIP(hipEventRecord(ev.e[2], m.stream));
-            PK_HIP(hipStreamSynchronize(m.stream));
-            PK_CHECK_LAUNCH();
-            float a = 0, b = 0;
-            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-            if (r > 0) { head.push_back(a); align.push_back(b); }
-        }
-        std::sort(head.begin(), head.end()); std::sort(align.begin(), align.end());
-        ms[0] = head[head.size() / 2]; ms[1] = align[align.size() / 2];
+            PK_HIP(hipEventRecord(ev[2], m.stream));
+        });
     });
 }
 
@@ -819,35 +819,18 @@ pk_status pk_tdt_align_decode_timed(pk_model *h, const float *enc, const int32_t
         need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
         Model &m = *h->m;
         tdt_align_checks(m, n_frames, B, T, ids, id_offsets, 0);
-        struct Ev { hipEvent_t e[4] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
-        std::vector<float> t[3];
-        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
-            tdt_align_queue(m, enc, n_frames, B, T, ids, true, ev.e, r == 0);
-            PK_HIP(hipStreamSynchronize(m.stream));
-            PK_CHECK_LAUNCH();
-            for (int k = 0; k < 3; ++k) {
-                float v = 0;
-                PK_HIP(hipEventElapsedTime(&v, ev.e[k], ev.e[k + 1]));
-                if (r > 0) t[k].push_back(v);
-            }
-        }
-        for (int k = 0; k < 3; ++k) { std::sort(t[k].begin(), t[k].end()); ms[k] = t[k][t[k].size() / 2]; }
+        bool first = true;                                         // enc is uploaded by the first pass alone
+        time_stages<3>(m, reps, ms, [&](hipEvent_t *ev) {          // the prediction net, the lattice, the walk
+            tdt_align_queue(m, enc, n_frames, B, T, ids, true, ev, first);
+            first = false;
+        });
         // the heads product of ONE chunk alone (the rows the last pass left in the activation buffer), for the lattice stage's overhead over it
         const int n = (int)std::min<int64_t>(m.talign.chunk_rows, m.talign.cells);
-        std::vector<float> hp;
-        for (int r = 0; r <= reps; ++r) {
-            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+        time_stages<1>(m, reps, ms + 3, [&](hipEvent_t *ev) {
+            PK_HIP(hipEventRecord(ev[0], m.stream));
             run_tdt_align_heads(m, m.talign, n, m.stream);
-            PK_HIP(hipEventRecord(ev.e[1], m.stream));
-            PK_HIP(hipStreamSynchronize(m.stream));
-            PK_CHECK_LAUNCH();
-            float v = 0;
-            PK_HIP(hipEventElapsedTime(&v, ev.e[0], ev.e[1]));
-            if (r > 0) hp.push_back(v);
-        }
-        std::sort(hp.begin(), hp.end());
-        ms[3] = hp[hp.size() / 2];
+            PK_HIP(hipEventRecord(ev[1], m.stream));
+        });
     });
 }
 
@@ -957,15 +940,15 @@ pk_status pk_tdt_total_decode_timed(pk_model *h, const float *enc, const int32_t
         need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
         Model &m = *h->m;
         tdt_total_checks(m, n_frames, n_clips, T, ids, id_offsets, clip_of, n_hyp);
-        struct Ev { hipEvent_t e[4] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
+        Events<4> ev;
+        ev.create();
         std::vector<float> t[3];
         for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
-            float v[3] = {0, 0, 0};                                // per stage, summed over the groups of the call
+            float v[3] = {0, 0, 0};                                // per stage, summed over the groups of the call: not time_stages' one pass of events
             tdt_total_run(m, enc, n_frames, n_clips, T, ids, id_offsets, ev.e, v);
             if (r > 0) for (int k = 0; k < 3; ++k) t[k].push_back(v[k]);
         }
-        for (int k = 0; k < 3; ++k) { std::sort(t[k].begin(), t[k].end()); ms[k] = t[k][t[k].size() / 2]; }
+        for (int k = 0; k < 3; ++k) ms[k] = median_of(t[k]);
     });
 }
 
@@ -1008,32 +991,13 @@ pk_status pk_ctc_kws(const float *logp, const int32_t *n_frames, int B, int T, i
         kws_check_args(kw_ids, kw_offsets, n_kw, B, V, blank, o);
         need(logp && n_hits && start && end && score, "logp/n_hits/start/end/score");
         need(n_frames || T > 0, "T");
-        int64_t rows = (int64_t)B * T;
-        std::vector<int32_t> tab;                                  // ragged: T[B] then T_off[B + 1]
-        if (n_frames) {
-            tab.resize(2 * (size_t)B + 1);
-            rows = 0; T = 0;
-            for (int b = 0; b < B; ++b) {
-                need(n_frames[b] > 0, "n_frames[b] must be positive");
-                tab[b] = n_frames[b]; tab[B + b] = (int32_t)rows;
-                rows += n_frames[b]; T = std::max(T, (int)n_frames[b]);
-                need(rows < ((int64_t)1 << 31), "too many frames");
-            }
-            tab[2 * (size_t)B] = (int32_t)rows;
-        }
+        HostRows in;
+        in.plan(n_frames, B, T);
         need_device();
         KwsWs ws;
-        kws_plan(ws, n_frames, B, T, kw_offsets, n_kw, o);         // (refuses before anything is allocated)
-        DevBuf d_lp, d_tab;
-        d_lp.reserve((size_t)rows * V * 4);
-        PK_HIP(hipMemcpy(d_lp.p, logp, (size_t)rows * V * 4, hipMemcpyHostToDevice));
-        SeqRag rag;
-        if (n_frames) {
-            d_tab.reserve(tab.size() * 4);
-            PK_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-            rag.T = d_tab.as<int>(); rag.T_off = rag.T + B; rag.T_max = T;
-        }
-        run_ctc_kws(ws, d_lp.as<float>(), B, T, rag, V, blank, kw_ids, nullptr);
+        kws_plan(ws, n_frames, B, in.T, kw_offsets, n_kw, o);      // (refuses before anything is allocated)
+        const SeqRag rag = in.upload(logp, B, V);
+        run_ctc_kws(ws, in.d_lp.as<float>(), B, in.T, rag, V, blank, kw_ids, nullptr);
         PK_CHECK_LAUNCH();
         kws_copy_out(ws, n_hits, start, end, score, nullptr);
     });
@@ -1071,24 +1035,13 @@ pk_status pk_ctc_kws_decode_timed(pk_model *h, const float *enc, const int32_t *
         T = size_ws(m, n_frames, B, T, rows);
         const SeqRag rag = n_frames ? m.ws.rv.seq : SeqRag();
         PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
-        struct Ev { hipEvent_t e[3] = {}; ~Ev() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-        for (auto &x : ev.e) PK_HIP(hipEventCreate(&x));
-        std::vector<float> head, spot;
-        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
-            PK_HIP(hipEventRecord(ev.e[0], m.stream));
+        time_stages<2>(m, reps, ms, [&](hipEvent_t *ev) {          // the head, the spotting
+            PK_HIP(hipEventRecord(ev[0], m.stream));
             m.run_ctc(m.ws, m.ws.x.as<float>(), B, T, true, m.stream);
-            PK_HIP(hipEventRecord(ev.e[1], m.stream));
+            PK_HIP(hipEventRecord(ev[1], m.stream));
             run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), B, T, rag, V, blank, kw_ids, m.stream);
-            PK_HIP(hipEventRecord(ev.e[2], m.stream));
-            PK_HIP(hipStreamSynchronize(m.stream));
-            PK_CHECK_LAUNCH();
-            float a = 0, b = 0;
-            PK_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-            PK_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-            if (r > 0) { head.push_back(a); spot.push_back(b); }
-        }
-        std::sort(head.begin(), head.end()); std::sort(spot.begin(), spot.end());
-        ms[0] = head[head.size() / 2]; ms[1] = spot[spot.size() / 2];
+            PK_HIP(hipEventRecord(ev[2], m.stream));
+        });
     });
 }
 

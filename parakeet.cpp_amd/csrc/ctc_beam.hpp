@@ -24,7 +24,7 @@ void beam_check_options(const pk_beam_options &opt, int V, int blank);
 
 // The whole search on stream s over device log-probs d_lp: uniform (rag.T == nullptr: B x T rows) or packed (rag set, T = the longest
 // utterance).  rows = total frames.  Results stay on the device in ws (token arrays zero-filled first: unused slots read 0).
-// lm != nullptr: the fused walk (ctc_beam_lm_walk_kernel) over that model takes the place of the unfused one and fills ws.hyp_lm.
+// lm != nullptr: the fused walk (ctc_beam_walk_kernel<true>) over that model takes the place of the unfused one and fills ws.hyp_lm.
 void run_ctc_beam(BeamWs &ws, const float *d_lp, int B, int T, int64_t rows, const SeqRag &rag, int V, int blank, const pk_beam_options &opt,
                   hipStream_t s, const LmDev *lm = nullptr);
 

@@ -1,6 +1,6 @@
 // parakeet.cpp_amd/csrc/kernels/ctc_beam.hip -- CTC prefix beam search on the device.
 //
-// The reference's roadmap "Beam search decoding -- CTC prefix beam search ... with configurable width" (README.md:494).  Three kernels over the [rows][V]
+// The reference's roadmap "Beam search decoding -- CTC prefix beam search ... with configurable width" (README.md:494).  Three kernels (the walk in two instantiations) over the [rows][V]
 // log-softmax rows that logsoftmax_argmax_kernel writes; every value they produce is specified operation by operation
 // (tests/ctc_beam_ref.py is that specification in Python) and compared bit for bit.
 //
@@ -18,7 +18,7 @@
 //                          Prefix identity = (64-bit chained hash of the token string, length), kept per beam entry together with the
 //                          parent string's hash: an extension that equals a beam prefix is found by hash however its nodes were linked.
 //                          TWO barriers per frame: candidates -> [barrier] -> rank / next beam / next frame's tokens -> [barrier].
-//   ctc_beam_lm_walk_kernel  the walk with n-gram LM shallow fusion: a beam entry carries two more values, the LM
+//     <kLm = true>         the same walk with n-gram LM shallow fusion: a beam entry carries two more values, the LM
 //                          automaton's state and the prefix's LM score (512 bytes of LDS more); an extension costs one lookup -- per back-off
 //                          level a 16-byte state record, a binary search over the state's sorted arc tokens and an 8-byte arc record, all
 //                          dependent global loads of the candidate's own thread, ended by the dense table of the empty context -- and only
@@ -30,9 +30,11 @@
 // Code objects (hipcc -O3 --offload-arch=gfx950, from the .s of -save-temps):
 //   ctc_topk_kernel<20>    56 VGPR   70 SGPR  LDS 0        no scratch, no spill
 //   ctc_topk_kernel<0>     24 VGPR   34 SGPR  LDS 0        no scratch, no spill
-//   ctc_beam_walk_kernel   91 VGPR  106 SGPR  LDS 11536 B  no scratch; 0 VGPR spills, 2 SGPRs spilled to VGPR lanes
-//   ctc_beam_lm_walk_kernel 103 VGPR 106 SGPR  LDS 12048 B  no scratch; 0 VGPR spills, 13 SGPRs spilled to VGPR lanes
+//   ctc_beam_walk_kernel<false>  91 VGPR  106 SGPR  LDS 11536 B  no scratch; 0 VGPR spills, 2 SGPRs spilled to VGPR lanes
+//   ctc_beam_walk_kernel<true>  103 VGPR  106 SGPR  LDS 12048 B  no scratch; 0 VGPR spills, 13 SGPRs spilled to VGPR lanes
 //   ctc_beam_align_kernel  18 VGPR   57 SGPR  LDS dynamic (5 Tmax + 2 words with timestamps, else 0)  no scratch, no spill
+#include <type_traits>
+
 #include "kernels.hpp"
 #include "ngram_lm_dev.hpp"
 #include "../pk_devmath.h"
@@ -134,10 +136,26 @@ struct BeamLds {
     int fid[2][kBeamMaxPrune];
     int nb[2];
 };
+// n-gram LM shallow fusion (kLm): two more values per beam entry, the LM automaton's state after the prefix and the
+// prefix's LM score lm = sum over its tokens of (alpha * lookup + beta), a function of the token string alone
+struct BeamLmLds {
+    BeamLds b;
+    int lmstate[2][kBeamMaxWidth];
+    float lm[2][kBeamMaxWidth];
+};
+__device__ __forceinline__ BeamLds &beam_lds(BeamLds &s) { return s; }
+__device__ __forceinline__ BeamLds &beam_lds(BeamLmLds &s) { return s.b; }
+__device__ __forceinline__ const BeamWalkArgs &beam_args(const BeamWalkArgs &a) { return a; }
+__device__ __forceinline__ const BeamWalkArgs &beam_args(const BeamLmWalkArgs &a) { return a.w; }
 }  // namespace
 
-__global__ __launch_bounds__(256) void ctc_beam_walk_kernel(BeamWalkArgs a) {
-    __shared__ BeamLds s;
+// kLm: a candidate is selectable exactly as without; its key orders by f = sc + lm where the unfused walk orders by sc.  Merges, node pool,
+// hashes and barriers are one code.  (The unfused instantiation takes BeamWalkArgs alone: its kernarg is not the fused one's.)
+template <bool kLm>
+__global__ __launch_bounds__(256) void ctc_beam_walk_kernel(std::conditional_t<kLm, BeamLmWalkArgs, BeamWalkArgs> la) {
+    __shared__ std::conditional_t<kLm, BeamLmLds, BeamLds> sl;
+    BeamLds &s = beam_lds(sl);
+    const BeamWalkArgs &a = beam_args(la);
     const int b = blockIdx.x, tid = threadIdx.x;
     int T = a.T;
     int64_t in0 = (int64_t)b * T;                                   // first frame of this utterance in the (packed) frame axis
@@ -156,6 +174,7 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(BeamWalkArgs a) {
         s.pb[0][0] = 0.0f; s.pnb[0][0] = NEG; s.tot[0][0] = 0.0f;
         s.node[0][0] = 0; s.last[0][0] = -1; s.len[0][0] = 0;
         s.hash[0][0] = 0x243F6A8885A308D3ull; s.phash[0][0] = 0;
+        if constexpr (kLm) { sl.lmstate[0][0] = la.lm.start; sl.lm[0][0] = 0.0f; }
         s.nb[0] = 1;
         nodes[0] = make_int2(-1, -1);                               // the empty prefix
     }
@@ -173,13 +192,14 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(BeamWalkArgs a) {
             else if (tid == K) pv = a.lpb[in0 + t + 1];
         }
         const int nb = s.nb[cur];
-        float npb[kBeamCPT], npnb[kBeamCPT], sc[kBeamCPT];
+        float npb[kBeamCPT], npnb[kBeamCPT], sc[kBeamCPT], nlm[kBeamCPT];         // (nlm / nls: kLm only)
+        int nls[kBeamCPT];
         unsigned long long key[kBeamCPT];
 #pragma unroll
         for (int u = 0; u < kBeamCPT; ++u) {
             const int i = ci[u], j = cj[u];
             key[u] = kBeamDead;
-            npb[u] = NEG; npnb[u] = NEG; sc[u] = NEG;
+            npb[u] = NEG; npnb[u] = NEG; sc[u] = NEG; nlm[u] = 0.0f; nls[u] = 0;
             if (i >= nb) continue;
             const int last = s.last[cur][i], len = s.len[cur][i];
             bool dead = false;
@@ -200,15 +220,25 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(BeamWalkArgs a) {
                 }
                 npnb[u] = beam_lae(rep, mrg);
                 sc[u] = beam_lae(npb[u], npnb[u]);
+                if constexpr (kLm) { nlm[u] = sl.lm[cur][i]; nls[u] = sl.lmstate[cur][i]; }           // its LM state and score stay with it
             } else {                                                // p + c
                 tok = s.fid[cur][j - 1];
                 npnb[u] = (tok == last ? s.pb[cur][i] : s.tot[cur][i]) + s.fval[cur][j - 1];
                 sc[u] = npnb[u];
                 const unsigned long long h2 = beam_hash(s.hash[cur][i], tok);
                 for (int q = 0; q < nb; ++q) dead = dead || (s.len[cur][q] == len + 1 && s.hash[cur][q] == h2);
+                if constexpr (kLm) {                                // one lookup, only for a live extension that is not merged away
+                    if (!dead && sc[u] > NEG) {
+                        const float lp = beam_lm_lookup(la.lm, sl.lmstate[cur][i], tok, nls[u]);
+                        nlm[u] = __fadd_rn(sl.lm[cur][i], __fadd_rn(__fmul_rn(la.lm.alpha, lp), la.lm.beta));    // three roundings, no fma
+                    }
+                }
             }
-            if (!dead && sc[u] > NEG)
-                key[u] = ((unsigned long long)beam_ord_desc(sc[u]) << 32) | ((unsigned)i << 25) | (j ? (1u << 24) : 0u) | (unsigned)tok;
+            if (!dead && sc[u] > NEG) {
+                float f = sc[u];
+                if constexpr (kLm) f = __fadd_rn(sc[u], nlm[u]);
+                key[u] = ((unsigned long long)beam_ord_desc(f) << 32) | ((unsigned)i << 25) | (j ? (1u << 24) : 0u) | (unsigned)tok;
+            }
             s.key[tid + 256 * u] = key[u];
         }
         __syncthreads();                                            // barrier 1 of 2: every candidate's key is in LDS
@@ -228,6 +258,7 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(BeamWalkArgs a) {
             if (key[u] == kBeamDead || r >= W) continue;
             const int i = ci[u], j = cj[u];
             s.pb[nxt][r] = npb[u]; s.pnb[nxt][r] = npnb[u]; s.tot[nxt][r] = sc[u];
+            if constexpr (kLm) { sl.lm[nxt][r] = nlm[u]; sl.lmstate[nxt][r] = nls[u]; }
             if (j == 0) {
                 s.node[nxt][r] = s.node[cur][i]; s.last[nxt][r] = s.last[cur][i]; s.len[nxt][r] = s.len[cur][i];
                 s.hash[nxt][r] = s.hash[cur][i]; s.phash[nxt][r] = s.phash[cur][i];
@@ -252,155 +283,14 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(BeamWalkArgs a) {
         a.hyp_node[o] = have ? s.node[fin][tid] : 0;
         a.hyp_len[o] = have ? s.len[fin][tid] : 0;
         a.hyp_score[o] = have ? s.tot[fin][tid] : NEG;
+        if constexpr (kLm) la.hyp_lm[o] = have ? sl.lm[fin][tid] : 0.0f;
     }
 }
 void launch_ctc_beam_walk(const BeamWalkArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(ctc_beam_walk_kernel, dim3(a.B), dim3(256), 0, s, a);
-}
-
-// ---- the walk with n-gram language-model shallow fusion ------------------------------------------------------
-// ctc_beam_walk_kernel with two more values per beam entry: the LM automaton's state after the prefix and the prefix's LM score
-// lm = sum over its tokens of (alpha * lookup + beta), a function of the token string alone.  A candidate is selectable exactly as above; its
-// key orders by f = sc + lm where the kernel above orders by sc.  Merges, node pool, hashes and barriers are the unfused kernel's.
-namespace {
-struct BeamLmLds {
-    BeamLds b;
-    int lmstate[2][kBeamMaxWidth];
-    float lm[2][kBeamMaxWidth];
-};
-}  // namespace
-
-__global__ __launch_bounds__(256) void ctc_beam_lm_walk_kernel(BeamLmWalkArgs la) {
-    __shared__ BeamLmLds sl;
-    BeamLds &s = sl.b;
-    const BeamWalkArgs &a = la.w;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int T = a.T;
-    int64_t in0 = (int64_t)b * T;
-    if (a.rg.T) { in0 = a.rg.T_off[b]; T = a.rg.T[b]; }
-    const int W = a.W, K = a.K, KP = K + 1;
-    const float NEG = -__builtin_huge_valf();
-    int2 *nodes = a.nodes + (int64_t)b * a.node_pitch;
-    int ci[kBeamCPT], cj[kBeamCPT];
-#pragma unroll
-    for (int u = 0; u < kBeamCPT; ++u) {
-        const int e = tid + 256 * u;
-        ci[u] = e / KP;
-        cj[u] = e - ci[u] * KP;
-    }
-    if (tid == 0) {
-        s.pb[0][0] = 0.0f; s.pnb[0][0] = NEG; s.tot[0][0] = 0.0f;
-        s.node[0][0] = 0; s.last[0][0] = -1; s.len[0][0] = 0;
-        s.hash[0][0] = 0x243F6A8885A308D3ull; s.phash[0][0] = 0;
-        sl.lmstate[0][0] = la.lm.start; sl.lm[0][0] = 0.0f;
-        s.nb[0] = 1;
-        nodes[0] = make_int2(-1, -1);
-    }
-    if (T > 0) {
-        if (tid < K) { s.fval[0][tid] = a.tk_val[in0 * K + tid]; s.fid[0][tid] = a.tk_id[in0 * K + tid]; }
-        else if (tid == K) s.flpb[0] = a.lpb[in0];
-    }
-    __syncthreads();
-    for (int t = 0; t < T; ++t) {
-        const int cur = t & 1, nxt = cur ^ 1;
-        float pv = 0.0f;
-        int pi = 0;
-        if (t + 1 < T) {
-            if (tid < K) { pv = a.tk_val[(in0 + t + 1) * K + tid]; pi = a.tk_id[(in0 + t + 1) * K + tid]; }
-            else if (tid == K) pv = a.lpb[in0 + t + 1];
-        }
-        const int nb = s.nb[cur];
-        float npb[kBeamCPT], npnb[kBeamCPT], sc[kBeamCPT], nlm[kBeamCPT];
-        int nls[kBeamCPT];
-        unsigned long long key[kBeamCPT];
-#pragma unroll
-        for (int u = 0; u < kBeamCPT; ++u) {
-            const int i = ci[u], j = cj[u];
-            key[u] = kBeamDead;
-            npb[u] = NEG; npnb[u] = NEG; sc[u] = NEG; nlm[u] = 0.0f; nls[u] = 0;
-            if (i >= nb) continue;
-            const int last = s.last[cur][i], len = s.len[cur][i];
-            bool dead = false;
-            int tok = 0;
-            if (j == 0) {                                           // p stays: its LM state and score with it
-                npb[u] = s.tot[cur][i] + s.flpb[cur];
-                float rep = NEG, mrg = NEG;
-                if (last >= 0) {
-                    int ks = -1;
-                    for (int k = 0; k < K; ++k) if (s.fid[cur][k] == last) ks = k;
-                    if (ks >= 0) {
-                        const float v = s.fval[cur][ks];
-                        rep = s.pnb[cur][i] + v;
-                        const unsigned long long ph = s.phash[cur][i];
-                        for (int q = 0; q < nb; ++q)
-                            if (s.len[cur][q] == len - 1 && s.hash[cur][q] == ph) mrg = (s.last[cur][q] == last ? s.pb[cur][q] : s.tot[cur][q]) + v;
-                    }
-                }
-                npnb[u] = beam_lae(rep, mrg);
-                sc[u] = beam_lae(npb[u], npnb[u]);
-                nlm[u] = sl.lm[cur][i]; nls[u] = sl.lmstate[cur][i];
-            } else {                                                // p + c: one lookup, only for a live extension that is not merged away
-                tok = s.fid[cur][j - 1];
-                npnb[u] = (tok == last ? s.pb[cur][i] : s.tot[cur][i]) + s.fval[cur][j - 1];
-                sc[u] = npnb[u];
-                const unsigned long long h2 = beam_hash(s.hash[cur][i], tok);
-                for (int q = 0; q < nb; ++q) dead = dead || (s.len[cur][q] == len + 1 && s.hash[cur][q] == h2);
-                if (!dead && sc[u] > NEG) {
-                    const float lp = beam_lm_lookup(la.lm, sl.lmstate[cur][i], tok, nls[u]);
-                    nlm[u] = __fadd_rn(sl.lm[cur][i], __fadd_rn(__fmul_rn(la.lm.alpha, lp), la.lm.beta));    // three roundings, no fma
-                }
-            }
-            if (!dead && sc[u] > NEG)
-                key[u] = ((unsigned long long)beam_ord_desc(__fadd_rn(sc[u], nlm[u])) << 32) | ((unsigned)i << 25) | (j ? (1u << 24) : 0u) | (unsigned)tok;
-            s.key[tid + 256 * u] = key[u];
-        }
-        __syncthreads();                                            // barrier 1 of 2: every candidate's key is in LDS
-        const int n = nb * KP;
-        int rk[kBeamCPT], valid = 0;
-#pragma unroll
-        for (int u = 0; u < kBeamCPT; ++u) rk[u] = 0;
-        for (int q = 0; q < n; ++q) {
-            const unsigned long long kq = s.key[q];
-            valid += kq != kBeamDead;
-#pragma unroll
-            for (int u = 0; u < kBeamCPT; ++u) rk[u] += kq < key[u];
-        }
-#pragma unroll
-        for (int u = 0; u < kBeamCPT; ++u) {
-            const int r = rk[u];
-            if (key[u] == kBeamDead || r >= W) continue;
-            const int i = ci[u], j = cj[u];
-            s.pb[nxt][r] = npb[u]; s.pnb[nxt][r] = npnb[u]; s.tot[nxt][r] = sc[u];
-            sl.lm[nxt][r] = nlm[u]; sl.lmstate[nxt][r] = nls[u];
-            if (j == 0) {
-                s.node[nxt][r] = s.node[cur][i]; s.last[nxt][r] = s.last[cur][i]; s.len[nxt][r] = s.len[cur][i];
-                s.hash[nxt][r] = s.hash[cur][i]; s.phash[nxt][r] = s.phash[cur][i];
-            } else {
-                const int tok = s.fid[cur][j - 1], nd = 1 + t * W + r;
-                nodes[nd] = make_int2(s.node[cur][i], tok);
-                s.node[nxt][r] = nd; s.last[nxt][r] = tok; s.len[nxt][r] = s.len[cur][i] + 1;
-                s.hash[nxt][r] = beam_hash(s.hash[cur][i], tok); s.phash[nxt][r] = s.hash[cur][i];
-            }
-        }
-        if (tid == 0) s.nb[nxt] = valid < W ? valid : W;
-        if (t + 1 < T) {
-            if (tid < K) { s.fval[nxt][tid] = pv; s.fid[nxt][tid] = pi; }
-            else if (tid == K) s.flpb[nxt] = pv;
-        }
-        __syncthreads();                                            // barrier 2 of 2: the next beam is complete
-    }
-    const int fin = T & 1, nb = s.nb[fin];
-    if (tid < a.N) {
-        const int64_t o = (int64_t)b * a.N + tid;
-        const bool have = tid < nb;
-        a.hyp_node[o] = have ? s.node[fin][tid] : 0;
-        a.hyp_len[o] = have ? s.len[fin][tid] : 0;
-        a.hyp_score[o] = have ? s.tot[fin][tid] : NEG;
-        la.hyp_lm[o] = have ? sl.lm[fin][tid] : 0.0f;
-    }
+    hipLaunchKernelGGL(ctc_beam_walk_kernel<false>, dim3(a.B), dim3(256), 0, s, a);
 }
 void launch_ctc_beam_lm_walk(const BeamLmWalkArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(ctc_beam_lm_walk_kernel, dim3(a.w.B), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ctc_beam_walk_kernel<true>, dim3(a.w.B), dim3(256), 0, s, a);
 }
 
 // ---- back-trace + forced alignment --------------------------------------------------------------------------------------

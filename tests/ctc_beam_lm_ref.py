@@ -1,5 +1,5 @@
 """CTC prefix beam search with n-gram language-model shallow fusion in plain Python: the written specification of DESIGN.md section
-5.5.6 that ctc_beam_lm_walk_kernel (kernels/ctc_beam.hip) is compared against bit for bit.
+5.5.6 that ctc_beam_walk_kernel<true> (kernels/ctc_beam.hip) is compared against bit for bit.
 
 beam_search of tests/ctc_beam_ref.py restated with the LM terms: a beam entry carries lm, the LM score of its token string (a function of
 the string alone: the left-to-right sum of alpha * lookup + beta, every operation one fp32 rounding); a stay candidate inherits it, an

@@ -1,4 +1,4 @@
-"""GPU: the CTC prefix beam search with n-gram LM shallow fusion (ctc_beam_lm_walk_kernel of kernels/ctc_beam.hip) against its written
+"""GPU: the CTC prefix beam search with n-gram LM shallow fusion (ctc_beam_walk_kernel<true> of kernels/ctc_beam.hip) against its written
 specification, tests/ctc_beam_lm_ref.py, BIT FOR BIT: token ids, lengths, score bits, lm_score bits, start / end frames and confidence
 bits of every returned hypothesis.  No case is skipped or filtered: the contract is equality."""
 import dataclasses
