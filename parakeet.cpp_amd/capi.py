@@ -389,6 +389,19 @@ class Lm:
             pass
 
 
+def _enc_head(enc):
+    """(ragged?, packed rows, T[B]) of rows [B][T][d] or a list of [T_b][d] matrices: encoder output, or log-probabilities"""
+    if isinstance(enc, (list, tuple)):
+        T = np.asarray([e.shape[0] for e in enc], np.int32)
+        return True, _c(np.concatenate([_c(e) for e in enc], axis=0)), T
+    x = _c(enc)
+    return False, x, np.full(x.shape[0], x.shape[1], np.int32)
+
+
+def _tmax(rag, x, T):
+    return int(T.max()) if rag else x.shape[1]
+
+
 def _beam_call(fn, head, B, tmax, o, lm=None, lm_alpha=None, lm_beta=None):
     """lm given: fn is the _lm form of the entry point; the result gains "lm_score" [B][N]."""
     N = max(1, o.n_best)
@@ -409,13 +422,9 @@ def ctc_beam_search(logp, blank, beam_width=None, token_prune=None, n_best=None,
     lm (an Lm): pk_ctc_beam_search_lm, shallow fusion with weights lm_alpha / lm_beta (None: the defaults); adds lm_score [B][N]."""
     o = beam_options(beam_width, token_prune, n_best, timestamps)
     fn = lib().pk_ctc_beam_search if lm is None else lib().pk_ctc_beam_search_lm
-    if isinstance(logp, (list, tuple)):
-        T = np.asarray([x.shape[0] for x in logp], np.int32)
-        lp = _c(np.concatenate([_c(x) for x in logp], axis=0))
-        return _beam_call(fn, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), len(T), int(T.max()), o, lm, lm_alpha, lm_beta)
-    lp = _c(logp)
-    B, T, V = lp.shape
-    return _beam_call(fn, (_f(lp), None, B, T, V, blank), B, T, o, lm, lm_alpha, lm_beta)
+    rag, lp, T = _enc_head(logp)
+    head = (_f(lp), _i(T) if rag else None, len(T), 0 if rag else lp.shape[1], lp.shape[-1], blank)
+    return _beam_call(fn, head, len(T), _tmax(rag, lp, T), o, lm, lm_alpha, lm_beta)
 
 
 # ---- CTC forced alignment of given token strings (include/parakeet_amd.h; DESIGN.md section 5.5.1) ------
@@ -447,13 +456,8 @@ def _align_call(fn, head, ids_list, total):
 def ctc_align(logp, ids, blank, total=True):
     """pk_ctc_align: logp [B][T][V] (uniform) or a list of [T_b][V] matrices (ragged); ids: one token sequence per utterance.
     Needs a device, no model."""
-    if isinstance(logp, (list, tuple)):
-        T = np.asarray([x.shape[0] for x in logp], np.int32)
-        lp = _c(np.concatenate([_c(x) for x in logp], axis=0))
-        return _align_call(lib().pk_ctc_align, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), ids, total)
-    lp = _c(logp)
-    B, T, V = lp.shape
-    return _align_call(lib().pk_ctc_align, (_f(lp), None, B, T, V, blank), ids, total)
+    rag, lp, T = _enc_head(logp)
+    return _align_call(lib().pk_ctc_align, (_f(lp), _i(T) if rag else None, len(T), 0 if rag else lp.shape[1], lp.shape[-1], blank), ids, total)
 
 
 # ---- TDT forced alignment of given token strings (include/parakeet_amd.h; DESIGN.md section 5.5.2) ------
@@ -549,13 +553,8 @@ def ctc_kws(logp, keywords, blank, max_hits=None, min_score=None):
     """pk_ctc_kws: logp [B][T][V] (uniform) or a list of [T_b][V] matrices (ragged); keywords: a list of token sequences, every one searched
     in every utterance.  Needs a device, no model."""
     o = kws_options(max_hits, min_score)
-    if isinstance(logp, (list, tuple)):
-        T = np.asarray([x.shape[0] for x in logp], np.int32)
-        lp = _c(np.concatenate([_c(x) for x in logp], axis=0))
-        return _kws_call(lib().pk_ctc_kws, (_f(lp), _i(T), len(T), 0, lp.shape[1], blank), len(T), keywords, o)
-    lp = _c(logp)
-    B, T, V = lp.shape
-    return _kws_call(lib().pk_ctc_kws, (_f(lp), None, B, T, V, blank), B, keywords, o)
+    rag, lp, T = _enc_head(logp)
+    return _kws_call(lib().pk_ctc_kws, (_f(lp), _i(T) if rag else None, len(T), 0 if rag else lp.shape[1], lp.shape[-1], blank), len(T), keywords, o)
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -1649,13 +1648,66 @@ def pack_clips(clips):
     return np.concatenate(clips), off
 
 
-def _transcribe(fn, handle, clips, decoder, timestamps, boost_phrases, boost_score, with_raw=None):
-    if isinstance(clips, tuple):                             # already packed: (pcm, offsets)
-        pcm, off = clips
-        pcm, off = _c(pcm), np.ascontiguousarray(off, np.int64)
-        clips = range(len(off) - 1)
+def _clips(clips):
+    """(pcm, offsets, n) of a list of clips, or of clips already packed as the tuple (pcm, offsets)"""
+    if isinstance(clips, tuple):
+        pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
     else:
         pcm, off = pack_clips(clips)
+    return pcm, off, len(off) - 1
+
+
+def _result_dict(r, timestamps):
+    """a pk_result as a dict: text, token_ids and, with timestamps, start / end / conf per token and the words"""
+    d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)])
+    if timestamps:
+        d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
+        d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
+        d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
+        d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
+    return d
+
+
+def _result_list(res, n, timestamps, with_raw=None):
+    """a pk_result array (freed here) as a list of dicts; timestamps[i]: clip i has the timestamp entries"""
+    try:
+        out = [_result_dict(res[i], timestamps[i]) for i in range(n)]
+        if with_raw is not None:
+            with_raw(res, n)                                     # e.g. pk_group_verify_exchange on the pk_result array itself
+        return out
+    finally:
+        lib().pk_results_free(res, n)
+
+
+def _nbest_list(res, n, timestamps, extra=None):
+    """a pk_nbest array (freed here) as, per clip, a list of dicts with "score"; extra: name -> [n][N] array of a further per-hypothesis entry"""
+    try:
+        out = []
+        for i in range(n):
+            hyps = []
+            for j in range(res[i].n_hyp):
+                d = _result_dict(res[i].hyp[j], timestamps)
+                d["score"] = float(res[i].score[j])
+                for k, v in (extra or {}).items():
+                    d[k] = float(v[i, j])
+                hyps.append(d)
+            out.append(hyps)
+        return out
+    finally:
+        lib().pk_nbest_free(res, n)
+
+
+def _transcript_args(texts, ids, n):
+    """the (texts, ids, id_offsets) arguments of an entry point that takes n transcripts as texts or as token id sequences"""
+    assert (texts is None) != (ids is None), "texts or ids"
+    if texts is not None:
+        return (C.c_char_p * n)(*[t.encode() for t in texts]), None, None
+    pid, poff = _pack_ids(ids)
+    return None, _i(pid), _i(poff)
+
+
+def _transcribe(fn, handle, clips, decoder, timestamps, boost_phrases, boost_score, with_raw=None):
+    pcm, off, n = _clips(clips)
     opt = PkOptions()
     opt.decoder = {"ctc": 0, "tdt": 1}[decoder]
     opt.timestamps = 1 if timestamps else 0
@@ -1664,21 +1716,8 @@ def _transcribe(fn, handle, clips, decoder, timestamps, boost_phrases, boost_sco
     opt.n_boost_phrases = len(boost_phrases)
     opt.boost_score = boost_score
     res = C.POINTER(PkResult)()
-    check(fn(handle, _f(pcm), off.ctypes.data_as(i64p), len(clips), C.byref(opt), C.byref(res)))
-    out = []
-    for i in range(len(clips)):
-        r = res[i]
-        d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)])
-        if timestamps:
-            d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
-            d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
-            d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
-            d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
-        out.append(d)
-    if with_raw is not None:
-        with_raw(res, len(clips))                            # e.g. pk_group_verify_exchange on the pk_result array itself
-    lib().pk_results_free(res, len(clips))
-    return out
+    check(fn(handle, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(opt), C.byref(res)))
+    return _result_list(res, n, [timestamps] * n, with_raw=with_raw)
 
 
 class Group:
@@ -1915,6 +1954,15 @@ class Model:
         n = lib().pk_tokenize(self._h, text.encode(), _i(ids), len(ids))
         return ids[:n].tolist()
 
+    def _rows_head(self, rag, x, T):
+        """the leading arguments of a stage entry point and of its _ragged form"""
+        return (self._h, _f(x), _i(T), len(T)) if rag else (self._h, _f(x), x.shape[0], x.shape[1])
+
+    def _timed_head(self, enc):
+        """the leading arguments of a _timed entry point, which takes both forms (a pointer made by data_as keeps its array alive)"""
+        rag, x, T = _enc_head(enc)
+        return self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1]
+
     def transcribe_pcm(self, clips, decoder="tdt", timestamps=False, boost_phrases=(), boost_score=5.0):
         """pk_transcribe_pcm: Transcriber::transcribe (transcribe.hpp:91-180) on in-memory clips -> list of dicts."""
         return _transcribe(lib().pk_transcribe_pcm, self._h, clips, decoder, timestamps, boost_phrases, boost_score)
@@ -1924,14 +1972,12 @@ class Model:
         lm (an Lm): pk_ctc_beam_decode_lm(_ragged)."""
         o = beam_options(beam_width, token_prune, n_best, timestamps)
         L = lib()
-        if isinstance(enc, (list, tuple)):
-            T = np.asarray([e.shape[0] for e in enc], np.int32)
-            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
+        rag, x, T = _enc_head(enc)
+        if rag:
             fn = L.pk_ctc_beam_decode_ragged if lm is None else L.pk_ctc_beam_decode_lm_ragged
-            return _beam_call(fn, (self._h, _f(x), _i(T), len(T)), len(T), int(T.max()), o, lm, lm_alpha, lm_beta)
-        x = _c(enc)
-        B, T, _ = x.shape
-        return _beam_call(L.pk_ctc_beam_decode if lm is None else L.pk_ctc_beam_decode_lm, (self._h, _f(x), B, T), B, T, o, lm, lm_alpha, lm_beta)
+        else:
+            fn = L.pk_ctc_beam_decode if lm is None else L.pk_ctc_beam_decode_lm
+        return _beam_call(fn, self._rows_head(rag, x, T), len(T), _tmax(rag, x, T), o, lm, lm_alpha, lm_beta)
 
     def tdt_beam_decode(self, enc, beam_width=None, label_prune=None, duration_prune=None, n_best=None, max_tokens=None, lm=None, lm_alpha=None,
                         lm_beta=None):
@@ -1939,7 +1985,7 @@ class Model:
         dur_idx / conf [B][N][max_tokens], lens / score [B][N], ok [B].  max_tokens None: (longest clip) * max_symbols_per_step.
         lm (an Lm): pk_tdt_beam_decode_lm(_ragged), shallow fusion with weights lm_alpha / lm_beta (None: the defaults); adds lm_score [B][N]."""
         o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
-        rag, x, T = self._enc_head(enc)
+        rag, x, T = _enc_head(enc)
         B, N = len(T), max(1, o.n_best)
         mt = int(max_tokens or int(T.max()) * self.cfg.max_symbols_per_step)
         ids = np.zeros((B, N, mt), np.int32); st = np.zeros((B, N, mt), np.int32); en = np.zeros((B, N, mt), np.int32)
@@ -1963,7 +2009,7 @@ class Model:
         """pk_tdt_beam_decode_timed -> (greedy TDT stage ms, beam search stage ms), HIP events, medians of reps passes.
         lm (an Lm): pk_tdt_beam_decode_lm_timed, the second stage is the fused search."""
         o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
-        rag, x, T = self._enc_head(enc)
+        rag, x, T = _enc_head(enc)
         mt = int(max_tokens or int(T.max()) * self.cfg.max_symbols_per_step)
         ms = np.zeros(2, np.float32)
         head = (self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], C.byref(o), mt, reps, _f(ms))
@@ -1982,108 +2028,50 @@ class Model:
                              lm_beta=None):
         """pk_transcribe_pcm_nbest_tdt: per clip a list of hypotheses through the TDT head, best first: dicts as transcribe_nbest returns them.
         lm (an Lm): pk_transcribe_pcm_nbest_tdt_lm; lists in fused order, every dict gains "lm_score"."""
-        if isinstance(clips, tuple):
-            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
-        else:
-            pcm, off = pack_clips(clips)
-        n = len(off) - 1
+        pcm, off, n = _clips(clips)
         o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
         res = C.POINTER(PkNbest)()
-        lms = None
         if lm is None:
             check(lib().pk_transcribe_pcm_nbest_tdt(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res)))
-        else:
-            lo = lm_options(lm_alpha, lm_beta)
-            lms = np.zeros((n, max(1, o.n_best)), np.float32)
-            check(lib().pk_transcribe_pcm_nbest_tdt_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res), lm._h,
-                                                       C.byref(lo), _f(lms)))
-        out = []
-        for i in range(n):
-            hyps = []
-            for j in range(res[i].n_hyp):
-                r = res[i].hyp[j]
-                d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]))
-                if lms is not None:
-                    d["lm_score"] = float(lms[i, j])
-                if timestamps:
-                    d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
-                    d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
-                    d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
-                    d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
-                hyps.append(d)
-            out.append(hyps)
-        lib().pk_nbest_free(res, n)
-        return out
+            return _nbest_list(res, n, timestamps)
+        lo = lm_options(lm_alpha, lm_beta)
+        lms = np.zeros((n, max(1, o.n_best)), np.float32)
+        check(lib().pk_transcribe_pcm_nbest_tdt_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res), lm._h,
+                                                   C.byref(lo), _f(lms)))
+        return _nbest_list(res, n, timestamps, dict(lm_score=lms))
 
     def ctc_align_decode(self, enc, ids, total=True):
         """pk_ctc_align_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_align."""
-        if isinstance(enc, (list, tuple)):
-            T = np.asarray([e.shape[0] for e in enc], np.int32)
-            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
-            return _align_call(lib().pk_ctc_align_decode_ragged, (self._h, _f(x), _i(T), len(T)), ids, total)
-        x = _c(enc)
-        B, T, _ = x.shape
-        return _align_call(lib().pk_ctc_align_decode, (self._h, _f(x), B, T), ids, total)
+        rag, x, T = _enc_head(enc)
+        return _align_call(lib().pk_ctc_align_decode_ragged if rag else lib().pk_ctc_align_decode, self._rows_head(rag, x, T), ids, total)
 
     def ctc_align_decode_timed(self, enc, ids, total=False, reps=5):
         """pk_ctc_align_decode_timed -> (CTC stage ms, alignment stage ms), HIP events, medians of reps passes."""
         pid, poff = _pack_ids(ids)
         ms = np.zeros(2, np.float32)
-        if isinstance(enc, (list, tuple)):
-            T = np.asarray([e.shape[0] for e in enc], np.int32)
-            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
-            check(lib().pk_ctc_align_decode_timed(self._h, _f(x), _i(T), len(T), 0, _i(pid), _i(poff), int(total), reps, _f(ms)))
-        else:
-            x = _c(enc)
-            check(lib().pk_ctc_align_decode_timed(self._h, _f(x), None, x.shape[0], x.shape[1], _i(pid), _i(poff), int(total), reps, _f(ms)))
+        check(lib().pk_ctc_align_decode_timed(*self._timed_head(enc), _i(pid), _i(poff), int(total), reps, _f(ms)))
         return float(ms[0]), float(ms[1])
 
     def align(self, clips, texts=None, ids=None, total=True):
         """pk_align_pcm: the clips (list, or packed (pcm, offsets)) against their transcripts, given as texts (needs the vocabulary) or as
         token id sequences -> list of dicts as transcribe_pcm(timestamps=True) returns them + "score", "ok" (and "total"); a clip that
         cannot be aligned has ok = 0 and no timestamp entries."""
-        assert (texts is None) != (ids is None), "texts or ids"
-        if isinstance(clips, tuple):
-            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
-        else:
-            pcm, off = pack_clips(clips)
-        n = len(off) - 1
+        pcm, off, n = _clips(clips)
         sc = np.zeros(n, np.float32); tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
         res = C.POINTER(PkResult)()
-        if texts is not None:
-            keep = (C.c_char_p * n)(*[t.encode() for t in texts])
-            tail = (keep, None, None)
-        else:
-            pid, poff = _pack_ids(ids)
-            tail = (None, _i(pid), _i(poff))
-        check(lib().pk_align_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, C.byref(res), _f(sc), _f(tt) if total else None, _i(ok)))
-        out = []
-        for i in range(n):
-            r = res[i]
-            d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(sc[i]), ok=int(ok[i]))
+        check(lib().pk_align_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *_transcript_args(texts, ids, n), C.byref(res), _f(sc),
+                                 _f(tt) if total else None, _i(ok)))
+        out = _result_list(res, n, ok)
+        for i, d in enumerate(out):
+            d.update(score=float(sc[i]), ok=int(ok[i]))
             if total:
                 d["total"] = float(tt[i])
-            if ok[i]:
-                d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
-                d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
-                d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
-                d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
-            out.append(d)
-        lib().pk_results_free(res, n)
         return out
-
-    def _enc_head(self, enc):
-        """(ragged?, packed rows, T[B]) of enc [B][T][d] or a list of [T_b][d] matrices"""
-        if isinstance(enc, (list, tuple)):
-            T = np.asarray([e.shape[0] for e in enc], np.int32)
-            return True, _c(np.concatenate([_c(e) for e in enc], axis=0)), T
-        x = _c(enc)
-        return False, x, np.full(x.shape[0], x.shape[1], np.int32)
 
     def tdt_align_decode(self, enc, ids):
         """pk_tdt_align_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch); ids: one token sequence per
         utterance -> as capi.tdt_align."""
-        rag, x, T = self._enc_head(enc)
+        rag, x, T = _enc_head(enc)
         pid, off = _pack_ids(ids)
         if rag:
             return _tdt_align_call(lib().pk_tdt_align_decode_ragged, (self._h, _f(x), _i(T), len(T), _i(pid)), off)
@@ -2092,7 +2080,7 @@ class Model:
     def tdt_align_decode_timed(self, enc, ids, reps=5):
         """pk_tdt_align_decode_timed -> (prediction net ms, lattice ms, walk ms, heads product of one chunk alone ms), HIP events, medians of
         reps passes."""
-        rag, x, T = self._enc_head(enc)
+        rag, x, T = _enc_head(enc)
         pid, off = _pack_ids(ids)
         ms = np.zeros(4, np.float32)
         check(lib().pk_tdt_align_decode_timed(self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], _i(pid), _i(off), reps, _f(ms)))
@@ -2101,7 +2089,7 @@ class Model:
     def tdt_lattice(self, enc, ids, chunk_rows=0):
         """pk_diag_tdt_lattice: enc a list of [T_b][d] matrices (or [B][T][d]) -> list of dicts lab [T][U], blk [T][U+1], dl [T][U+1][D], and
         "guard": the three buffers' words past the written extent as uint32 (the fill pattern 0x7FC5A5A5 when nothing wrote there)."""
-        _, x, T = self._enc_head(enc)
+        _, x, T = _enc_head(enc)
         pid, off = _pack_ids(ids)
         U = np.diff(off).astype(np.int64)
         D = len(self.cfg.durations)
@@ -2120,36 +2108,17 @@ class Model:
 
     def align_tdt(self, clips, texts=None, ids=None):
         """pk_tdt_align_pcm: Model.align through the TDT head (no CTC head needed) -> list of dicts as align() returns them, without "total"."""
-        assert (texts is None) != (ids is None), "texts or ids"
-        if isinstance(clips, tuple):
-            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
-        else:
-            pcm, off = pack_clips(clips)
-        n = len(off) - 1
+        pcm, off, n = _clips(clips)
         sc = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
         res = C.POINTER(PkResult)()
-        if texts is not None:
-            keep = (C.c_char_p * n)(*[t.encode() for t in texts])
-            tail = (keep, None, None)
-        else:
-            pid, poff = _pack_ids(ids)
-            tail = (None, _i(pid), _i(poff))
-        check(lib().pk_tdt_align_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, C.byref(res), _f(sc), _i(ok)))
-        out = []
-        for i in range(n):
-            r = res[i]
-            d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(sc[i]), ok=int(ok[i]))
-            if ok[i]:
-                d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
-                d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
-                d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
-                d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
-            out.append(d)
-        lib().pk_results_free(res, n)
+        check(lib().pk_tdt_align_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *_transcript_args(texts, ids, n), C.byref(res), _f(sc), _i(ok)))
+        out = _result_list(res, n, ok)
+        for i, d in enumerate(out):
+            d.update(score=float(sc[i]), ok=int(ok[i]))
         return out
 
     def _total_args(self, enc, ids, clip_of):
-        rag, x, T = self._enc_head(enc)
+        rag, x, T = _enc_head(enc)
         pid, off = _pack_ids(ids)
         co = None if clip_of is None else np.ascontiguousarray(clip_of, np.int32)
         return rag, x, T, pid, off, co
@@ -2177,96 +2146,48 @@ class Model:
 
     def score_tdt(self, clips, texts=None, ids=None, clip_of=None):
         """pk_tdt_score_pcm: the TDT log-likelihood of one or more transcripts per clip (texts need the vocabulary) -> list of dicts total, ok."""
-        assert (texts is None) != (ids is None), "texts or ids"
-        if isinstance(clips, tuple):
-            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
-        else:
-            pcm, off = pack_clips(clips)
+        pcm, off, n_clips = _clips(clips)
         n = len(texts) if texts is not None else len(ids)
         co = None if clip_of is None else np.ascontiguousarray(clip_of, np.int32)
         tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
-        if texts is not None:
-            keep = (C.c_char_p * n)(*[t.encode() for t in texts])
-            tail = (keep, None, None)
-        else:
-            pid, poff = _pack_ids(ids)
-            tail = (None, _i(pid), _i(poff))
-        check(lib().pk_tdt_score_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), len(off) - 1, *tail, _i(co) if co is not None else None, n, _f(tt), _i(ok)))
+        check(lib().pk_tdt_score_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n_clips, *_transcript_args(texts, ids, n),
+                                     _i(co) if co is not None else None, n, _f(tt), _i(ok)))
         return [dict(total=tt[b], ok=int(ok[b])) for b in range(n)]
 
     def transcribe_nbest_rescored(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False, tdt_weight=0.5):
         """pk_transcribe_pcm_nbest_rescored: transcribe_nbest re-ranked by the TDT head: per clip a list of dicts as transcribe_nbest returns
         them, "score" the combined value, + "ctc_score" and "tdt_total"."""
-        if isinstance(clips, tuple):
-            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
-        else:
-            pcm, off = pack_clips(clips)
-        n = len(off) - 1
+        pcm, off, n = _clips(clips)
         o = beam_options(beam_width, token_prune, n_best, timestamps)
         ro = PkRescoreOptions(float(tdt_weight))
         N = max(1, o.n_best)
         cs = np.zeros((n, N), np.float32); tt = np.zeros((n, N), np.float32)
         res = C.POINTER(PkNbest)()
         check(lib().pk_transcribe_pcm_nbest_rescored(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(ro), C.byref(res), _f(cs), _f(tt)))
-        out = []
-        for i in range(n):
-            hyps = []
-            for j in range(res[i].n_hyp):
-                r = res[i].hyp[j]
-                d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]),
-                         ctc_score=float(cs[i, j]), tdt_total=float(tt[i, j]))
-                if timestamps:
-                    d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
-                    d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
-                    d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
-                    d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
-                hyps.append(d)
-            out.append(hyps)
-        lib().pk_nbest_free(res, n)
-        return out
+        return _nbest_list(res, n, timestamps, dict(ctc_score=cs, tdt_total=tt))
 
     def ctc_kws_decode(self, enc, keywords, max_hits=None, min_score=None):
         """pk_ctc_kws_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_kws."""
         o = kws_options(max_hits, min_score)
-        if isinstance(enc, (list, tuple)):
-            T = np.asarray([e.shape[0] for e in enc], np.int32)
-            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
-            return _kws_call(lib().pk_ctc_kws_decode_ragged, (self._h, _f(x), _i(T), len(T)), len(T), keywords, o)
-        x = _c(enc)
-        B, T, _ = x.shape
-        return _kws_call(lib().pk_ctc_kws_decode, (self._h, _f(x), B, T), B, keywords, o)
+        rag, x, T = _enc_head(enc)
+        return _kws_call(lib().pk_ctc_kws_decode_ragged if rag else lib().pk_ctc_kws_decode, self._rows_head(rag, x, T), len(T), keywords, o)
 
     def ctc_kws_decode_timed(self, enc, keywords, max_hits=None, min_score=None, reps=5):
         """pk_ctc_kws_decode_timed -> (CTC stage ms, spotting stage ms), HIP events, medians of reps passes."""
         o = kws_options(max_hits, min_score)
         pid, poff = _pack_ids(keywords)
         ms = np.zeros(2, np.float32)
-        if isinstance(enc, (list, tuple)):
-            T = np.asarray([e.shape[0] for e in enc], np.int32)
-            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
-            check(lib().pk_ctc_kws_decode_timed(self._h, _f(x), _i(T), len(T), 0, _i(pid), _i(poff), len(keywords), C.byref(o), reps, _f(ms)))
-        else:
-            x = _c(enc)
-            check(lib().pk_ctc_kws_decode_timed(self._h, _f(x), None, x.shape[0], x.shape[1], _i(pid), _i(poff), len(keywords), C.byref(o), reps, _f(ms)))
+        check(lib().pk_ctc_kws_decode_timed(*self._timed_head(enc), _i(pid), _i(poff), len(keywords), C.byref(o), reps, _f(ms)))
         return float(ms[0]), float(ms[1])
 
     def spot(self, clips, phrases=None, ids=None, max_hits=None, min_score=None):
         """pk_spot_pcm: every phrase (texts: needs the vocabulary; or token id sequences) searched in every clip (list, or packed
         (pcm, offsets)) -> per clip, per phrase, a list of (start_s, end_s, score), best first."""
         assert (phrases is None) != (ids is None), "phrases or ids"
-        if isinstance(clips, tuple):
-            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
-        else:
-            pcm, off = pack_clips(clips)
-        n = len(off) - 1
+        pcm, off, n = _clips(clips)
         o = kws_options(max_hits, min_score)
         K, H = len(phrases if phrases is not None else ids), max(1, o.max_hits)
-        if phrases is not None:
-            keep = (C.c_char_p * K)(*[t.encode() for t in phrases])
-            tail = (keep, None, None)
-        else:
-            pid, poff = _pack_ids(ids)
-            tail = (None, _i(pid), _i(poff))
+        tail = _transcript_args(phrases, ids, K)
         nh = np.zeros((n, K), np.int32); st = np.zeros((n, K, H), np.float32); en = np.zeros((n, K, H), np.float32); sc = np.zeros((n, K, H), np.float32)
         check(lib().pk_spot_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, K, C.byref(o), _i(nh), _f(st), _f(en), _f(sc)))
         return [[[(float(st[c, k, j]), float(en[c, k, j]), float(sc[c, k, j])) for j in range(nh[c, k])] for k in range(K)] for c in range(n)]
@@ -2276,13 +2197,7 @@ class Model:
         lm (an Lm): pk_ctc_beam_decode_lm_timed, the beam stage with the fused walk."""
         o = beam_options(beam_width, token_prune, n_best, timestamps)
         ms = np.zeros(2, np.float32)
-        if isinstance(enc, (list, tuple)):
-            T = np.asarray([e.shape[0] for e in enc], np.int32)
-            x = _c(np.concatenate([_c(e) for e in enc], axis=0))
-            head = (self._h, _f(x), _i(T), len(T), 0, C.byref(o), reps, _f(ms))
-        else:
-            x = _c(enc)
-            head = (self._h, _f(x), None, x.shape[0], x.shape[1], C.byref(o), reps, _f(ms))
+        head = (*self._timed_head(enc), C.byref(o), reps, _f(ms))
         if lm is None:
             check(lib().pk_ctc_beam_decode_timed(*head))
         else:
@@ -2293,36 +2208,16 @@ class Model:
     def transcribe_nbest(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None, lm_beta=None):
         """pk_transcribe_pcm_nbest: per clip a list of hypotheses, best first: dicts as transcribe_pcm returns them + "score".
         lm (an Lm): pk_transcribe_pcm_nbest_lm; lists in fused order, every dict gains "lm_score"."""
-        if isinstance(clips, tuple):
-            pcm, off = _c(clips[0]), np.ascontiguousarray(clips[1], np.int64)
-        else:
-            pcm, off = pack_clips(clips)
-        n = len(off) - 1
+        pcm, off, n = _clips(clips)
         o = beam_options(beam_width, token_prune, n_best, timestamps)
         res = C.POINTER(PkNbest)()
         if lm is None:
             check(lib().pk_transcribe_pcm_nbest(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res)))
-        else:
-            lo = lm_options(lm_alpha, lm_beta)
-            lms = np.zeros((n, max(1, o.n_best)), np.float32)
-            check(lib().pk_transcribe_pcm_nbest_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res), lm._h, C.byref(lo), _f(lms)))
-        out = []
-        for i in range(n):
-            hyps = []
-            for j in range(res[i].n_hyp):
-                r = res[i].hyp[j]
-                d = dict(text=(r.text or b"").decode(), token_ids=[r.token_ids[k] for k in range(r.n_tokens)], score=float(res[i].score[j]))
-                if lm is not None:
-                    d["lm_score"] = float(lms[i, j])
-                if timestamps:
-                    d["start"] = [r.start_frame[k] for k in range(r.n_tokens)]
-                    d["end"] = [r.end_frame[k] for k in range(r.n_tokens)]
-                    d["conf"] = [r.confidence[k] for k in range(r.n_tokens)]
-                    d["words"] = [(r.words[k].word.decode(), r.words[k].start, r.words[k].end, r.words[k].confidence) for k in range(r.n_words)]
-                hyps.append(d)
-            out.append(hyps)
-        lib().pk_nbest_free(res, n)
-        return out
+            return _nbest_list(res, n, timestamps)
+        lo = lm_options(lm_alpha, lm_beta)
+        lms = np.zeros((n, max(1, o.n_best)), np.float32)
+        check(lib().pk_transcribe_pcm_nbest_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res), lm._h, C.byref(lo), _f(lms)))
+        return _nbest_list(res, n, timestamps, dict(lm_score=lms))
 
     def ctc_decode(self, enc, return_logp=False):
         enc = _c(enc)

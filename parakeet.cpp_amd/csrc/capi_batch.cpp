@@ -859,32 +859,98 @@ pk_status pk_transcribe_pcm(pk_model *h, const float *pcm, const int64_t *offset
     });
 }
 
+}  // extern "C"
+
 namespace {
+
+// The batch loop of every one-call entry point that works on the encoder's rows: the call's clips in the packing of
+// pk_transcribe_pcm (plan_batches: longest first, <= 256 clips / 8192 rows per batch), every batch from PCM to the encoder output m.ws.x and,
+// with ctc, the log-softmax rows of the CTC head, left on the device in m.ws.ctc_lp (packed; extents in r and m.ws.rv.seq).  Per batch of nc
+// clips, clip[i] being the caller's index of the batch's clip i:
+//   prepare(clip, nc)   false: the batch is skipped before it is encoded;
+//   sized(r, nc)        runs once the extents are known and before anything is allocated or queued: the head's plan refuses here;
+//   body(clip, nc, r)   the head on the encoded rows; results go to the caller's slots clip[i].
+template <class Prepare, class Sized, class Body>
+void for_each_batch(Model &m, const float *pcm, const int64_t *offsets, int n_clips, bool ctc, Prepare prepare, Sized sized, Body body) {
+    std::vector<int64_t> clip_len(n_clips), blens;
+    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+    std::vector<int> order, bstart;
+    plan_batches(clip_len.data(), n_clips, order, bstart);
+    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
+        const int *clip = order.data() + bstart[k];
+        const int nc = bstart[k + 1] - bstart[k];
+        if (!prepare(clip, nc)) continue;
+        blens.resize(nc);
+        for (int i = 0; i < nc; ++i) blens[i] = clip_len[clip[i]];
+        const int64_t longest = blens[0];
+        RagBatch r;
+        r.build_from_samples(blens.data(), nc, att_block_rows_of(m, pk_encoder_num_frames(pk_mel_num_frames(longest))));
+        sized(r, nc);
+        m.ws.size_ragged(m.cfg, nc, r.n_samples, longest, /*own_pcm=*/true);
+        m.ws.set_ragged(r, m.stream);
+        for (int i = 0; i < nc; ++i)
+            PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[clip[i]], (size_t)blens[i] * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), nc, m.stream);
+        m.run_encoder(m.ws, m.ws.feats.as<float>(), nc, 0, -1, 0, m.stream);
+        if (ctc) m.run_ctc(m.ws, m.ws.x.as<float>(), nc, r.T_max, true, m.stream);
+        body(clip, nc, r);
+    }
+}
+const auto every_batch = [](const int *, int) { return true; };
+const float NEGF = -__builtin_huge_valf();
+
+struct BeamHost {             // a batch's search output on the host: nc * N slots of `pitch` tokens; an unfilled slot has score -inf
+    std::vector<int32_t> ids, lens, st, en;
+    std::vector<float> sc, cf, lms;
+    size_t pitch = 0;
+    bool ts = false;
+    void size(size_t slots, size_t pitch_, bool ts_) {
+        pitch = pitch_; ts = ts_;
+        ids.resize(slots * pitch); lens.resize(slots); sc.resize(slots); lms.assign(slots, 0.0f);
+        if (ts) { st.resize(slots * pitch); en.resize(slots * pitch); cf.resize(slots * pitch); }
+    }
+    int32_t *start() { return ts ? st.data() : nullptr; }
+    int32_t *end() { return ts ? en.data() : nullptr; }
+    float *conf() { return ts ? cf.data() : nullptr; }
+};
+
 struct NbestStore {           // owns everything a pk_nbest array points into
     std::vector<pk_nbest> out;                              // one hidden trailing slot keeps the store pointer
     std::vector<ResultStorePtr> clip;                       // the hypotheses of one clip: a ResultStore of n_hyp results
     std::vector<std::vector<float>> score;
+    explicit NbestStore(int n_clips) : out((size_t)n_clips + 1), clip(n_clips), score(n_clips) {}
+    // Clip c of the call gets the filled ones of the N slots of the batch's clip i (they come first): position j of its list is slot ord[j],
+    // scored ranked[ord[j]].  Returns their number.
+    int fill(Model &m, int c, int i, int N, BeamHost &h, const int32_t *ord, const float *ranked) {
+        const size_t hy0 = (size_t)i * N;
+        int nh = 0;
+        while (nh < N && h.sc[hy0 + nh] > NEGF) ++nh;
+        clip[c] = new_store(nh);
+        ResultStore &R = *clip[c];
+        score[c].resize(nh);
+        for (int j = 0; j < nh; ++j) {
+            const size_t hy = hy0 + ord[j], o0 = hy * h.pitch;
+            score[c][j] = ranked[ord[j]];
+            store_tokens(m, R, j, h.lens[hy], h.ids.data() + o0, h.ts ? h.st.data() + o0 : nullptr, h.ts ? h.en.data() + o0 : nullptr,
+                         h.ts ? h.cf.data() + o0 : nullptr);
+        }
+        point_results(R, nh, h.ts);
+        out[c].n_hyp = nh;
+        out[c].hyp = R.res.data();
+        out[c].score = score[c].data();
+        return nh;
+    }
+    // hands the store over to the caller as a pk_nbest array (freed by pk_nbest_free)
+    static pk_nbest *publish(std::unique_ptr<NbestStore> store) {
+        pk_nbest &tail = store->out.back();
+        tail.n_hyp = 0; tail.score = nullptr;
+        tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
+        return store.release()->out.data();
+    }
 };
 }  // namespace
 
-// One planned batch of the one-call entry points that work on the encoder's rows (clips order[0 .. nc) of the call) from PCM to the encoder
-// output m.ws.x and, with ctc, the log-softmax rows of the CTC head, left on the device in m.ws.ctc_lp (packed; extents in r and m.ws.rv.seq).
-// sized(r), if given, runs once the extents are known and before anything is allocated or queued.
-static void encode_batch(Model &m, const float *pcm, const int64_t *offsets, const int *order, int nc, RagBatch &r,
-                             const std::function<void(const RagBatch &)> &sized = nullptr, bool ctc = true) {
-    std::vector<int64_t> blens(nc);
-    for (int i = 0; i < nc; ++i) blens[i] = offsets[order[i] + 1] - offsets[order[i]];
-    const int64_t longest = blens[0];
-    r.build_from_samples(blens.data(), nc, att_block_rows_of(m, pk_encoder_num_frames(pk_mel_num_frames(longest))));
-    if (sized) sized(r);
-    m.ws.size_ragged(m.cfg, nc, r.n_samples, longest, /*own_pcm=*/true);
-    m.ws.set_ragged(r, m.stream);
-    for (int i = 0; i < nc; ++i)
-        PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[order[i]], (size_t)blens[i] * 4, hipMemcpyHostToDevice, m.stream));
-    m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), nc, m.stream);
-    m.run_encoder(m.ws, m.ws.feats.as<float>(), nc, 0, -1, 0, m.stream);
-    if (ctc) m.run_ctc(m.ws, m.ws.x.as<float>(), nc, r.T_max, true, m.stream);
-}
+extern "C" {
 
 // The body of pk_transcribe_pcm_nbest and pk_transcribe_pcm_nbest_rescored.  tdt_weight != nullptr: every returned hypothesis of a batch is scored
 // under the TDT head on the batch's encoder rows (tdt_total.hpp; enc_proj once per batch, hypotheses of a clip share its rows) and each clip's list
@@ -904,34 +970,24 @@ static void nbest_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_
     }
     const bool ts = o.timestamps != 0;
     const int N = o.n_best;
-    auto store = std::make_unique<NbestStore>();
-    store->out.resize((size_t)n_clips + 1); store->clip.resize(n_clips); store->score.resize(n_clips);
-    std::vector<int64_t> clip_len(n_clips);
-    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
-    std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
-    plan_batches(clip_len.data(), n_clips, order, bstart);
-    std::vector<int32_t> ids, lens, st, en, hids, hoff, hclip, hslot, okv, ord;
-    std::vector<float> sc, cf, tt, comb, lms;
-    const float NEGF = -__builtin_huge_valf();
-    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
-        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
-        RagBatch r;
-        encode_batch(m, pcm, offsets, order.data() + c0, nc, r);
+    auto store = std::make_unique<NbestStore>(n_clips);
+    BeamHost h;
+    std::vector<int32_t> hids, hoff, hclip, hslot, okv, ord;
+    std::vector<float> tt, comb;
+    for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/true, every_batch, [](const RagBatch &, int) {}, [&](const int *clip, int nc, const RagBatch &r) {
         const int T = r.T_max;
         run_ctc_beam(m.beam, m.ws.ctc_lp.as<float>(), nc, T, r.sum_T, m.ws.rv.seq, V, blank, o, m.stream, fused ? &lmd : nullptr);
         PK_CHECK_LAUNCH();
-        const size_t hyps = (size_t)nc * N, tok = hyps * T;
-        ids.resize(tok); lens.resize(hyps); sc.resize(hyps); lms.assign(hyps, 0.0f);
-        if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
-        beam_copy_out(m.beam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, ts ? cf.data() : nullptr, m.stream,
-                      fused ? lms.data() : nullptr);
+        const size_t hyps = (size_t)nc * N;
+        h.size(hyps, T, ts);
+        beam_copy_out(m.beam, h.ids.data(), h.lens.data(), h.sc.data(), h.start(), h.end(), h.conf(), m.stream, fused ? h.lms.data() : nullptr);
         if (tdt_weight) {
             // the filled slots of the batch as one packed call of the total: hypothesis (i, j) on the rows of the batch's clip i
             hids.clear(); hoff.assign(1, 0); hclip.clear(); hslot.clear();
             for (int i = 0; i < nc; ++i)
-                for (int j = 0; j < N && sc[(size_t)i * N + j] > NEGF; ++j) {
+                for (int j = 0; j < N && h.sc[(size_t)i * N + j] > NEGF; ++j) {
                     const size_t hy = (size_t)i * N + j;
-                    hids.insert(hids.end(), ids.begin() + hy * T, ids.begin() + hy * T + lens[hy]);
+                    hids.insert(hids.end(), h.ids.begin() + hy * T, h.ids.begin() + hy * T + h.lens[hy]);
                     hoff.push_back((int32_t)hids.size()); hclip.push_back(i); hslot.push_back((int32_t)hy);
                 }
             tt.assign(hyps, NEGF); okv.assign(hyps, 0);
@@ -948,37 +1004,21 @@ static void nbest_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_
             }
         }
         for (int i = 0; i < nc; ++i) {
-            const int c = order[c0 + i];
-            int nh = 0;
-            while (nh < N && sc[(size_t)i * N + nh] > NEGF) ++nh;
-            store->clip[c] = new_store(nh);
-            ResultStore &R = *store->clip[c];
+            const int c = clip[i];
+            const size_t hy0 = (size_t)i * N;
             ord.resize(N); comb.resize(N);
-            for (int j = 0; j < N; ++j) { ord[j] = j; comb[j] = sc[(size_t)i * N + j]; }
-            if (tdt_weight)
-                rescore_order(lens.data() + (size_t)i * N, sc.data() + (size_t)i * N, tt.data() + (size_t)i * N, okv.data() + (size_t)i * N, N, *tdt_weight,
-                              ord.data(), comb.data());
-            store->score[c].resize(nh);
+            for (int j = 0; j < N; ++j) { ord[j] = j; comb[j] = h.sc[hy0 + j]; }
+            if (tdt_weight) rescore_order(h.lens.data() + hy0, h.sc.data() + hy0, tt.data() + hy0, okv.data() + hy0, N, *tdt_weight, ord.data(), comb.data());
+            const int nh = store->fill(m, c, i, N, h, ord.data(), comb.data());
             for (int j = 0; j < N; ++j) {                       // position j of the returned list holds the beam's slot ord[j]; the nh filled slots come first
-                const size_t hy = (size_t)i * N + ord[j], o0 = hy * T;
-                if (ctc_out) ctc_out[(size_t)c * N + j] = j < nh ? sc[hy] : NEGF;
+                const size_t hy = hy0 + ord[j];
+                if (ctc_out) ctc_out[(size_t)c * N + j] = j < nh ? h.sc[hy] : NEGF;
                 if (tdt_out) tdt_out[(size_t)c * N + j] = j < nh ? tt[hy] : NEGF;
-                if (lm_out) lm_out[(size_t)c * N + j] = j < nh ? lms[hy] : 0.0f;
-                if (j >= nh) continue;
-                store->score[c][j] = comb[ord[j]];
-                store_tokens(m, R, j, lens[hy], ids.data() + o0, ts ? st.data() + o0 : nullptr, ts ? en.data() + o0 : nullptr, ts ? cf.data() + o0 : nullptr);
+                if (lm_out) lm_out[(size_t)c * N + j] = j < nh ? h.lms[hy] : 0.0f;
             }
-            point_results(R, nh, ts);
-            store->out[c].n_hyp = nh;
-            store->out[c].hyp = R.res.data();
-            store->out[c].score = store->score[c].data();
         }
-    }
-    pk_nbest &tail = store->out[n_clips];
-    tail.n_hyp = 0; tail.score = nullptr;
-    tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
-    *results = store->out.data();
-    store.release();
+    });
+    *results = NbestStore::publish(std::move(store));
 }
 
 pk_status pk_transcribe_pcm_nbest(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_beam_options *opt,
@@ -1024,57 +1064,30 @@ static void nbest_tdt_pcm(Model &m, const float *pcm, const int64_t *offsets, in
     LmDev lmd{};
     bool have_lmd = false;                                     // the device copy is made after the first batch's plan: a refusal allocates nothing
     const int N = o.n_best;
-    auto store = std::make_unique<NbestStore>();
-    store->out.resize((size_t)n_clips + 1); store->clip.resize(n_clips); store->score.resize(n_clips);
-    std::vector<int64_t> clip_len(n_clips);
-    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
-    std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
-    plan_batches(clip_len.data(), n_clips, order, bstart);
-    std::vector<int32_t> ids, lens, st, en;
-    std::vector<float> sc, cf, lms;
-    const float NEGF = -__builtin_huge_valf();
+    auto store = std::make_unique<NbestStore>(n_clips);
+    BeamHost h;
+    std::vector<int32_t> identity(N);
+    for (int j = 0; j < N; ++j) identity[j] = j;
     const int sym = m.cfg.max_symbols_per_step > 0 ? m.cfg.max_symbols_per_step : 10;
-    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
-        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
-        RagBatch r;
-        int MT = 0;
-        encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
-            MT = rb.T_max * sym;
-            tdt_beam_plan(m.tbeam, m, rb.T.data(), nc, 0, o, MT, fused);        // (refuses before the batch is allocated or queued)
-            if (fused && !have_lmd) { lmd = lm_device_view(lm, lm_opt); have_lmd = true; }
-        }, /*ctc=*/false);
+    int MT = 0;
+    for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/false, every_batch, [&](const RagBatch &rb, int nc) {
+        MT = rb.T_max * sym;
+        tdt_beam_plan(m.tbeam, m, rb.T.data(), nc, 0, o, MT, fused);            // (refuses before the batch is allocated or queued)
+        if (fused && !have_lmd) { lmd = lm_device_view(lm, lm_opt); have_lmd = true; }
+    }, [&](const int *clip, int nc, const RagBatch &r) {
         m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
         run_tdt_beam(m, m.tbeam, m.ws.ep.as<float>(), m.stream, fused ? &lmd : nullptr);
         PK_CHECK_LAUNCH();
-        const size_t hyps = (size_t)nc * N, tok = hyps * MT;
-        ids.resize(tok); lens.resize(hyps); sc.resize(hyps); lms.assign(hyps, 0.0f);
-        if (ts) { st.resize(tok); en.resize(tok); cf.resize(tok); }
-        tdt_beam_copy_out(m.tbeam, ids.data(), lens.data(), sc.data(), ts ? st.data() : nullptr, ts ? en.data() : nullptr, nullptr, ts ? cf.data() : nullptr,
-                          nullptr, m.stream, fused ? lms.data() : nullptr);
+        h.size((size_t)nc * N, MT, ts);
+        tdt_beam_copy_out(m.tbeam, h.ids.data(), h.lens.data(), h.sc.data(), h.start(), h.end(), nullptr, h.conf(), nullptr, m.stream,
+                          fused ? h.lms.data() : nullptr);
         for (int i = 0; i < nc; ++i) {
-            const int c = order[c0 + i];
-            int nh = 0;
-            while (nh < N && sc[(size_t)i * N + nh] > NEGF) ++nh;
-            store->clip[c] = new_store(nh);
-            ResultStore &R = *store->clip[c];
-            store->score[c].resize(nh);
-            if (lm_out) for (int j = 0; j < N; ++j) lm_out[(size_t)c * N + j] = j < nh ? lms[(size_t)i * N + j] : 0.0f;
-            for (int j = 0; j < nh; ++j) {
-                const size_t hy = (size_t)i * N + j, o0 = hy * MT;
-                store->score[c][j] = sc[hy];
-                store_tokens(m, R, j, lens[hy], ids.data() + o0, ts ? st.data() + o0 : nullptr, ts ? en.data() + o0 : nullptr, ts ? cf.data() + o0 : nullptr);
-            }
-            point_results(R, nh, ts);
-            store->out[c].n_hyp = nh;
-            store->out[c].hyp = R.res.data();
-            store->out[c].score = store->score[c].data();
+            const int c = clip[i];
+            const int nh = store->fill(m, c, i, N, h, identity.data(), h.sc.data() + (size_t)i * N);
+            if (lm_out) for (int j = 0; j < N; ++j) lm_out[(size_t)c * N + j] = j < nh ? h.lms[(size_t)i * N + j] : 0.0f;
         }
-    }
-    pk_nbest &tail = store->out[n_clips];
-    tail.n_hyp = 0; tail.score = nullptr;
-    tail.hyp = reinterpret_cast<const pk_result *>(store.get());     // back-pointer for pk_nbest_free
-    *results = store->out.data();
-    store.release();
+    });
+    *results = NbestStore::publish(std::move(store));
 }
 
 pk_status pk_transcribe_pcm_nbest_tdt(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const pk_tdt_beam_options *opt,
@@ -1093,59 +1106,7 @@ pk_status pk_transcribe_pcm_nbest_tdt_lm(pk_model *h, const float *pcm, const in
     });
 }
 
-static void align_transcripts(Model &m, int n_clips, const char *const *texts, const int32_t *ids_in, const int32_t *id_offsets_in, int V, int blank,
-                              std::vector<int32_t> &all_ids, std::vector<int32_t> &all_off);
-
-// The body of pk_tdt_score_pcm: the batches of pk_transcribe_pcm; the transcripts of a batch's clips are scored on its encoder rows.
-static void score_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids, const std::vector<int32_t> &all_off,
-                      const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
-    std::vector<int64_t> clip_len(n_clips);
-    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
-    std::vector<int> order, bstart;
-    plan_batches(clip_len.data(), n_clips, order, bstart);
-    std::vector<std::vector<int>> hyps_of(n_clips);
-    for (int q = 0; q < n_hyp; ++q) hyps_of[clip_of ? clip_of[q] : q].push_back(q);
-    std::vector<int32_t> bids, boff, bclip, bhyp, nfr;
-    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
-        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
-        bids.clear(); boff.assign(1, 0); bclip.clear(); bhyp.clear();
-        for (int i = 0; i < nc; ++i)
-            for (int q : hyps_of[order[c0 + i]]) {
-                bids.insert(bids.end(), all_ids.begin() + all_off[q], all_ids.begin() + all_off[q + 1]);
-                boff.push_back((int32_t)bids.size()); bclip.push_back(i); bhyp.push_back(q);
-            }
-        const int nh = (int)bhyp.size();
-        if (nh == 0) continue;                                      // (no transcript for any clip of this batch: nothing to encode)
-        bids.push_back(0);
-        RagBatch r;
-        encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
-            nfr.assign(rb.T.begin(), rb.T.begin() + nc);               // (the plan refuses before the batch is encoded)
-            tdt_total_plan_call(m, m.ttotal, nfr.data(), nc, 0, boff.data(), bclip.data(), nh);
-        }, /*ctc=*/false);
-        m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
-        run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), bids.data(), boff.data());
-        PK_CHECK_LAUNCH();
-        for (int q = 0; q < nh; ++q) { total[bhyp[q]] = m.ttotal.total[q]; ok[bhyp[q]] = m.ttotal.ok[q]; }
-    }
-}
-
-pk_status pk_tdt_score_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
-                           const int32_t *id_offsets_in, const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
-    return guard([&] {
-        need(h && pcm && offsets && total && ok && n_clips > 0 && n_hyp > 0, "model/pcm/offsets/total/ok/n_clips/n_hyp");
-        need(texts || id_offsets_in, "texts or ids/id_offsets");
-        Model &m = *h->m;
-        tdt_align_model_checks(m);
-        if (clip_of) for (int q = 0; q < n_hyp; ++q) need(clip_of[q] >= 0 && clip_of[q] < n_clips, "clip_of[h] outside [0, n_clips)");
-        else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
-        std::vector<int32_t> all_ids, all_off;
-        align_transcripts(m, n_hyp, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
-        m.require_gpu();
-        score_pcm(m, pcm, offsets, n_clips, all_ids, all_off, clip_of, n_hyp, total, ok);
-    });
-}
-
-// pk_align_pcm / pk_tdt_align_pcm: the transcripts of the call (texts tokenised, or the given ids checked) packed in the caller's clip order
+// pk_align_pcm / pk_tdt_align_pcm / pk_tdt_score_pcm: the transcripts of the call (texts tokenised, or the given ids checked) packed in the caller's clip order
 static void align_transcripts(Model &m, int n_clips, const char *const *texts, const int32_t *ids_in, const int32_t *id_offsets_in, int V, int blank,
                               std::vector<int32_t> &all_ids, std::vector<int32_t> &all_off) {
     all_ids.clear(); all_off.assign(n_clips + 1, 0);
@@ -1164,31 +1125,67 @@ static void align_transcripts(Model &m, int n_clips, const char *const *texts, c
     }
 }
 
-// The body of both: plan the batches as pk_transcribe_pcm does, encode each, align it through the chosen head, store tokens and words.
+// The body of pk_tdt_score_pcm: the batches of pk_transcribe_pcm; the transcripts of a batch's clips are scored on its encoder rows.
+static void score_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids, const std::vector<int32_t> &all_off,
+                      const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    std::vector<std::vector<int>> hyps_of(n_clips);
+    for (int q = 0; q < n_hyp; ++q) hyps_of[clip_of ? clip_of[q] : q].push_back(q);
+    std::vector<int32_t> bids, boff, bclip, bhyp, nfr;
+    for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/false, [&](const int *clip, int nc) {
+        bids.clear(); boff.assign(1, 0); bclip.clear(); bhyp.clear();
+        for (int i = 0; i < nc; ++i)
+            for (int q : hyps_of[clip[i]]) {
+                bids.insert(bids.end(), all_ids.begin() + all_off[q], all_ids.begin() + all_off[q + 1]);
+                boff.push_back((int32_t)bids.size()); bclip.push_back(i); bhyp.push_back(q);
+            }
+        bids.push_back(0);
+        return !bhyp.empty();                                       // (no transcript for any clip of this batch: nothing to encode)
+    }, [&](const RagBatch &rb, int nc) {
+        nfr.assign(rb.T.begin(), rb.T.begin() + nc);                   // (the plan refuses before the batch is encoded)
+        tdt_total_plan_call(m, m.ttotal, nfr.data(), nc, 0, boff.data(), bclip.data(), (int)bhyp.size());
+    }, [&](const int *, int, const RagBatch &r) {
+        m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
+        run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), bids.data(), boff.data());
+        PK_CHECK_LAUNCH();
+        for (size_t q = 0; q < bhyp.size(); ++q) { total[bhyp[q]] = m.ttotal.total[q]; ok[bhyp[q]] = m.ttotal.ok[q]; }
+    });
+}
+
+pk_status pk_tdt_score_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
+                           const int32_t *id_offsets_in, const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && pcm && offsets && total && ok && n_clips > 0 && n_hyp > 0, "model/pcm/offsets/total/ok/n_clips/n_hyp");
+        need(texts || id_offsets_in, "texts or ids/id_offsets");
+        Model &m = *h->m;
+        tdt_align_model_checks(m);
+        if (clip_of) for (int q = 0; q < n_hyp; ++q) need(clip_of[q] >= 0 && clip_of[q] < n_clips, "clip_of[h] outside [0, n_clips)");
+        else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
+        std::vector<int32_t> all_ids, all_off;
+        align_transcripts(m, n_hyp, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
+        m.require_gpu();
+        score_pcm(m, pcm, offsets, n_clips, all_ids, all_off, clip_of, n_hyp, total, ok);
+    });
+}
+
+// The body of pk_align_pcm and pk_tdt_align_pcm: every batch aligned through the chosen head, tokens and words stored.
 static void align_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids,
                       const std::vector<int32_t> &all_off, pk_result **results, float *score, float *total, int32_t *ok) {
     const int V = m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;      // (CTC head only)
-    std::vector<int64_t> clip_len(n_clips);
-    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
-    std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
-    plan_batches(clip_len.data(), n_clips, order, bstart);
     auto store = new_store(n_clips);
     std::vector<int32_t> bids, boff, nfr, st, en, di, okv;
     std::vector<float> cf, sc, tt;
-    for (size_t k = 0; k + 1 < bstart.size(); ++k) {
-        const int c0 = bstart[k], nc = bstart[k + 1] - c0;
+    for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/!tdt, [&](const int *clip, int nc) {
         boff.assign(nc + 1, 0); bids.clear();
         for (int i = 0; i < nc; ++i) {
-            const int c = order[c0 + i];
-            bids.insert(bids.end(), all_ids.begin() + all_off[c], all_ids.begin() + all_off[c + 1]);
+            bids.insert(bids.end(), all_ids.begin() + all_off[clip[i]], all_ids.begin() + all_off[clip[i] + 1]);
             boff[i + 1] = (int32_t)bids.size();
         }
-        RagBatch r;
-        encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
-            nfr.assign(rb.T.begin(), rb.T.begin() + nc);               // (the plans refuse before the batch is encoded)
-            if (tdt) tdt_align_plan(m.talign, nfr.data(), nc, rb.T_max, boff.data(), m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden);
-            else align_plan(m.align, nfr.data(), nc, rb.T_max, boff.data());
-        }, !tdt);
+        return true;
+    }, [&](const RagBatch &rb, int nc) {
+        nfr.assign(rb.T.begin(), rb.T.begin() + nc);                   // (the plans refuse before the batch is encoded)
+        if (tdt) tdt_align_plan(m.talign, nfr.data(), nc, rb.T_max, boff.data(), m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden);
+        else align_plan(m.align, nfr.data(), nc, rb.T_max, boff.data());
+    }, [&](const int *clip, int nc, const RagBatch &r) {
         const size_t n = bids.size();
         st.assign(n + 1, 0); en.assign(n + 1, 0); di.assign(n + 1, 0); cf.assign(n + 1, 0.0f); sc.resize(nc); tt.resize(nc); okv.resize(nc);
         if (tdt) {
@@ -1205,14 +1202,14 @@ static void align_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offse
             align_copy_out(m.align, st.data(), en.data(), cf.data(), sc.data(), total ? tt.data() : nullptr, okv.data(), m.stream);
         }
         for (int i = 0; i < nc; ++i) {
-            const int c = order[c0 + i], o0 = boff[i], L = boff[i + 1] - o0;
+            const int c = clip[i], o0 = boff[i], L = boff[i + 1] - o0;
             const bool good = okv[i] != 0;
             store_tokens(m, *store, c, L, bids.data() + o0, good ? st.data() + o0 : nullptr, good ? en.data() + o0 : nullptr, good ? cf.data() + o0 : nullptr);
             ok[c] = okv[i];
             if (score) score[c] = sc[i];
             if (total) total[c] = tt[i];
         }
-    }
+    });
     pk_result *out = publish_store(std::move(store), n_clips, true);
     for (int c = 0; c < n_clips; ++c)
         if (!ok[c]) out[c].start_frame = out[c].end_frame = nullptr, out[c].confidence = nullptr;
@@ -1275,26 +1272,19 @@ pk_status pk_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int
             ids.assign(ids_in, ids_in + off[n_kw]);
         }
         m.require_gpu();
-        std::vector<int64_t> clip_len(n_clips);
-        for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
-        std::vector<int> order, bstart;                            // the packing of pk_transcribe_pcm: longest first, <= 256 clips / 8192 rows per batch
-        plan_batches(clip_len.data(), n_clips, order, bstart);
         const size_t H = (size_t)o.max_hits, per_clip = (size_t)n_kw * H;
         std::vector<int32_t> nfr, nh, st, en;
         std::vector<float> sc;
-        for (size_t k = 0; k + 1 < bstart.size(); ++k) {
-            const int c0 = bstart[k], nc = bstart[k + 1] - c0;
-            RagBatch r;
-            encode_batch(m, pcm, offsets, order.data() + c0, nc, r, [&](const RagBatch &rb) {
-                nfr.assign(rb.T.begin(), rb.T.begin() + nc);
-                kws_plan(m.kws, nfr.data(), nc, rb.T_max, off.data(), n_kw, o);     // (refuses before the batch is encoded)
-            });
+        for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/true, every_batch, [&](const RagBatch &rb, int nc) {
+            nfr.assign(rb.T.begin(), rb.T.begin() + nc);
+            kws_plan(m.kws, nfr.data(), nc, rb.T_max, off.data(), n_kw, o);         // (refuses before the batch is encoded)
+        }, [&](const int *clip, int nc, const RagBatch &r) {
             run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, ids.data(), m.stream);
             PK_CHECK_LAUNCH();
             nh.resize((size_t)nc * n_kw); st.resize(nc * per_clip); en.resize(nc * per_clip); sc.resize(nc * per_clip);
             kws_copy_out(m.kws, nh.data(), st.data(), en.data(), sc.data(), m.stream);
             for (int i = 0; i < nc; ++i) {
-                const size_t c = (size_t)order[c0 + i];
+                const size_t c = (size_t)clip[i];
                 for (int q = 0; q < n_kw; ++q) {
                     const int n = nh[(size_t)i * n_kw + q];
                     n_hits[c * n_kw + q] = n;
@@ -1307,7 +1297,7 @@ pk_status pk_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int
                     }
                 }
             }
-        }
+        });
     });
 }
 

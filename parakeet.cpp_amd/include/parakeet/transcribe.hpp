@@ -219,197 +219,83 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         if (g_) check(pk_group_transcribe_pcm(g_, pcm.data(), offsets.data(), (int)clips.size(), &o, &res));
         else check(pk_transcribe_pcm(m_, pcm.data(), offsets.data(), (int)clips.size(), &o, &res));
         std::vector<TranscribeResult> out(clips.size());
-        for (size_t i = 0; i < clips.size(); ++i) {
-            const pk_result &r = res[i];
-            out[i].text = r.text ? r.text : "";
-            out[i].token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
-            if (opts.timestamps) {
-                for (int k = 0; k < r.n_tokens; ++k)
-                    out[i].timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
-                for (int k = 0; k < r.n_words; ++k)
-                    out[i].word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
-            }
-        }
+        for (size_t i = 0; i < clips.size(); ++i) convert(res[i], opts.timestamps, out[i]);
         pk_results_free(res, (int)clips.size());
         return out;
+    }
+    TranscribeResult run_file(const std::string &audio_path, const TranscribeOptions &opts) {
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run({{pcm, n}}, opts)[0]; });
     }
 
     // pk_transcribe_pcm_nbest on one clip: the CTC prefix beam search's hypotheses, best first (single device; replicas are not used)
     std::vector<ScoredResult> run_nbest(const float *pcm, size_t n, const BeamOptions &opts) {
         if (!on_gpu_) to_gpu(0);
-        pk_beam_options o;
-        pk_beam_options_default(&o);
-        o.beam_width = opts.beam_width; o.token_prune = opts.token_prune; o.n_best = opts.n_best; o.timestamps = opts.timestamps ? 1 : 0;
+        const pk_beam_options o = beam_options(opts);
         const int64_t offsets[2] = {0, (int64_t)n};
         pk_nbest *res = nullptr;
         check(pk_transcribe_pcm_nbest(m_, pcm, offsets, 1, &o, &res));
-        std::vector<ScoredResult> out(res[0].n_hyp);
-        for (int j = 0; j < res[0].n_hyp; ++j) {
-            const pk_result &r = res[0].hyp[j];
-            out[j].score = res[0].score[j];
-            out[j].result.text = r.text ? r.text : "";
-            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
-            if (opts.timestamps) {
-                for (int k = 0; k < r.n_tokens; ++k)
-                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
-                for (int k = 0; k < r.n_words; ++k)
-                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
-            }
-        }
-        pk_nbest_free(res, 1);
-        return out;
+        return take_nbest<ScoredResult>(res, opts.timestamps, [](ScoredResult &, int) {});
     }
     std::vector<ScoredResult> run_nbest_file(const std::string &audio_path, const BeamOptions &opts) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_nbest(pcm, (size_t)n, opts);
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_nbest(pcm, n, opts); });
     }
 
     // pk_transcribe_pcm_nbest_lm on one clip: the search with n-gram LM shallow fusion, hypotheses in fused order
     std::vector<LmScoredResult> run_nbest_lm(const float *pcm, size_t n, const BeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
         if (!on_gpu_) to_gpu(0);
-        pk_beam_options o;
-        pk_beam_options_default(&o);
-        o.beam_width = opts.beam_width; o.token_prune = opts.token_prune; o.n_best = opts.n_best; o.timestamps = opts.timestamps ? 1 : 0;
-        const pk_lm_options lo{lmo.alpha, lmo.beta};
+        const pk_beam_options o = beam_options(opts);
+        const pk_lm_options lo = lm_options(lmo);
         const int64_t offsets[2] = {0, (int64_t)n};
         std::vector<float> lms((size_t)std::max(1, opts.n_best), 0.0f);
         pk_nbest *res = nullptr;
         check(pk_transcribe_pcm_nbest_lm(m_, pcm, offsets, 1, &o, &res, lm.handle(), &lo, lms.data()));
-        std::vector<LmScoredResult> out(res[0].n_hyp);
-        for (int j = 0; j < res[0].n_hyp; ++j) {
-            const pk_result &r = res[0].hyp[j];
-            out[j].score = res[0].score[j];
-            out[j].lm_score = lms[j];
-            out[j].result.text = r.text ? r.text : "";
-            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
-            if (opts.timestamps) {
-                for (int k = 0; k < r.n_tokens; ++k)
-                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
-                for (int k = 0; k < r.n_words; ++k)
-                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
-            }
-        }
-        pk_nbest_free(res, 1);
-        return out;
+        return take_nbest<LmScoredResult>(res, opts.timestamps, [&](LmScoredResult &r, int j) { r.lm_score = lms[j]; });
     }
     std::vector<LmScoredResult> run_nbest_lm_file(const std::string &audio_path, const BeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_nbest_lm(pcm, (size_t)n, opts, lm, lmo);
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_nbest_lm(pcm, n, opts, lm, lmo); });
     }
 
     // pk_transcribe_pcm_nbest_tdt on one clip: the TDT beam search's hypotheses, best first; score is the path's log-probability
     std::vector<ScoredResult> run_nbest_tdt(const float *pcm, size_t n, const TdtBeamOptions &opts) {
         if (!on_gpu_) to_gpu(0);
-        pk_tdt_beam_options o;
-        pk_tdt_beam_options_default(&o);
-        o.beam_width = opts.beam_width; o.label_prune = opts.label_prune; o.duration_prune = opts.duration_prune; o.n_best = opts.n_best;
+        const pk_tdt_beam_options o = tdt_beam_options(opts);
         const int64_t offsets[2] = {0, (int64_t)n};
         pk_nbest *res = nullptr;
         check(pk_transcribe_pcm_nbest_tdt(m_, pcm, offsets, 1, &o, opts.timestamps ? 1 : 0, &res));
-        std::vector<ScoredResult> out(res[0].n_hyp);
-        for (int j = 0; j < res[0].n_hyp; ++j) {
-            const pk_result &r = res[0].hyp[j];
-            out[j].score = res[0].score[j];
-            out[j].result.text = r.text ? r.text : "";
-            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
-            if (opts.timestamps) {
-                for (int k = 0; k < r.n_tokens; ++k)
-                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
-                for (int k = 0; k < r.n_words; ++k)
-                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
-            }
-        }
-        pk_nbest_free(res, 1);
-        return out;
+        return take_nbest<ScoredResult>(res, opts.timestamps, [](ScoredResult &, int) {});
     }
     std::vector<ScoredResult> run_nbest_tdt_file(const std::string &audio_path, const TdtBeamOptions &opts) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_nbest_tdt(pcm, (size_t)n, opts);
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_nbest_tdt(pcm, n, opts); });
     }
 
     // pk_transcribe_pcm_nbest_tdt_lm on one clip: the TDT beam search with n-gram LM shallow fusion, hypotheses in fused order
     std::vector<LmScoredResult> run_nbest_tdt_lm(const float *pcm, size_t n, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
         if (!on_gpu_) to_gpu(0);
-        pk_tdt_beam_options o;
-        pk_tdt_beam_options_default(&o);
-        o.beam_width = opts.beam_width; o.label_prune = opts.label_prune; o.duration_prune = opts.duration_prune; o.n_best = opts.n_best;
-        pk_lm_options lo{lmo.alpha, lmo.beta};
+        const pk_tdt_beam_options o = tdt_beam_options(opts);
+        const pk_lm_options lo = lm_options(lmo);
         const int64_t offsets[2] = {0, (int64_t)n};
         std::vector<float> lms((size_t)std::max(1, opts.n_best), 0.0f);
         pk_nbest *res = nullptr;
         check(pk_transcribe_pcm_nbest_tdt_lm(m_, pcm, offsets, 1, &o, opts.timestamps ? 1 : 0, &res, lm.handle(), &lo, lms.data()));
-        std::vector<LmScoredResult> out(res[0].n_hyp);
-        for (int j = 0; j < res[0].n_hyp; ++j) {
-            const pk_result &r = res[0].hyp[j];
-            out[j].score = res[0].score[j];
-            out[j].lm_score = lms[j];
-            out[j].result.text = r.text ? r.text : "";
-            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
-            if (opts.timestamps) {
-                for (int k = 0; k < r.n_tokens; ++k)
-                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
-                for (int k = 0; k < r.n_words; ++k)
-                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
-            }
-        }
-        pk_nbest_free(res, 1);
-        return out;
+        return take_nbest<LmScoredResult>(res, opts.timestamps, [&](LmScoredResult &r, int j) { r.lm_score = lms[j]; });
     }
     std::vector<LmScoredResult> run_nbest_tdt_lm_file(const std::string &audio_path, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_nbest_tdt_lm(pcm, (size_t)n, opts, lm, lmo);
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_nbest_tdt_lm(pcm, n, opts, lm, lmo); });
     }
 
     // pk_transcribe_pcm_nbest_rescored on one clip: run_nbest's list re-ranked by the TDT head's log-likelihood of every hypothesis
     std::vector<RescoredResult> run_nbest_rescored(const float *pcm, size_t n, const BeamOptions &opts, const RescoreOptions &rescore) {
         if (!on_gpu_) to_gpu(0);
-        pk_beam_options o;
-        pk_beam_options_default(&o);
-        o.beam_width = opts.beam_width; o.token_prune = opts.token_prune; o.n_best = opts.n_best; o.timestamps = opts.timestamps ? 1 : 0;
+        const pk_beam_options o = beam_options(opts);
         pk_rescore_options ro{rescore.tdt_weight};
         const int64_t offsets[2] = {0, (int64_t)n};
         pk_nbest *res = nullptr;
         std::vector<float> ctc((size_t)std::max(1, opts.n_best)), tdt(ctc.size());
         check(pk_transcribe_pcm_nbest_rescored(m_, pcm, offsets, 1, &o, &ro, &res, ctc.data(), tdt.data()));
-        std::vector<RescoredResult> out(res[0].n_hyp);
-        for (int j = 0; j < res[0].n_hyp; ++j) {
-            const pk_result &r = res[0].hyp[j];
-            out[j].score = res[0].score[j]; out[j].ctc_score = ctc[j]; out[j].tdt_total = tdt[j];
-            out[j].result.text = r.text ? r.text : "";
-            out[j].result.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
-            if (opts.timestamps) {
-                for (int k = 0; k < r.n_tokens; ++k)
-                    out[j].result.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
-                for (int k = 0; k < r.n_words; ++k)
-                    out[j].result.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
-            }
-        }
-        pk_nbest_free(res, 1);
-        return out;
+        return take_nbest<RescoredResult>(res, opts.timestamps, [&](RescoredResult &r, int j) { r.ctc_score = ctc[j]; r.tdt_total = tdt[j]; });
     }
     std::vector<RescoredResult> run_nbest_rescored_file(const std::string &audio_path, const BeamOptions &opts, const RescoreOptions &rescore) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_nbest_rescored(pcm, (size_t)n, opts, rescore);
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_nbest_rescored(pcm, n, opts, rescore); });
     }
 
     // the log-likelihood of `text` (tokenised by the model's vocabulary) on one clip under the TDT head: pk_tdt_score_pcm
@@ -427,12 +313,7 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return out;
     }
     ScoreResult run_score_file(const std::string &audio_path, const std::string &text, bool tdt_head) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_score(pcm, (size_t)n, text, tdt_head);
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_score(pcm, n, text, tdt_head); });
     }
 
     // pk_align_pcm on one clip: the CTC forced alignment of `text` (tokenised by the model's vocabulary); single device
@@ -446,25 +327,14 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         int32_t ok = 0;
         if (tdt_head) check(pk_tdt_align_pcm(m_, pcm, offsets, 1, texts, nullptr, nullptr, &res, &score, &ok));
         else check(pk_align_pcm(m_, pcm, offsets, 1, texts, nullptr, nullptr, &res, &score, &total, &ok));
-        const pk_result &r = res[0];
         AlignResult out;
         out.score = score; out.total = total; out.aligned = ok != 0;
-        out.text = r.text ? r.text : "";
-        out.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
-        if (ok) {
-            for (int k = 0; k < r.n_tokens; ++k) out.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
-            for (int k = 0; k < r.n_words; ++k) out.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
-        }
+        convert(res[0], out.aligned, out);
         pk_results_free(res, 1);
         return out;
     }
     AlignResult run_align_file(const std::string &audio_path, const std::string &text, bool tdt_head = false) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_align(pcm, (size_t)n, text, tdt_head);
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_align(pcm, n, text, tdt_head); });
     }
 
     // pk_spot_pcm on one clip: every phrase (tokenised by the model's vocabulary) -> its hits, best first; single device
@@ -487,27 +357,57 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return out;
     }
     std::vector<std::vector<SpotHit>> run_spot_file(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run_spot(pcm, (size_t)n, phrases, opts);
-    }
-
-    TranscribeResult run_file(const std::string &audio_path, const TranscribeOptions &opts) {
-        float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));   // read_audio(path): decode, downmix, resample to 16 kHz
-        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
-        return run({{pcm, (size_t)n}}, opts)[0];
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_spot(pcm, n, phrases, opts); });
     }
 
     const Tokenizer &tokenizer() const { return tok_; }
     pk_model *handle() { return m_; }
 
   private:
+    // read_audio(path): decode, downmix, resample to 16 kHz; the samples go to fn(pcm, n) and are freed when it returns or throws
+    template <class Fn>
+    static auto with_audio(const std::string &audio_path, Fn fn) -> decltype(fn((const float *)nullptr, size_t())) {
+        float *pcm = nullptr;
+        int64_t n = 0;
+        int sr = 0;
+        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        return fn(pcm, (size_t)n);
+    }
+    // text and token ids of a pk_result and, with timestamps, its timestamped tokens and words
+    static void convert(const pk_result &r, bool timestamps, TranscribeResult &out) {
+        out.text = r.text ? r.text : "";
+        out.token_ids.assign(r.token_ids, r.token_ids + r.n_tokens);
+        if (!timestamps) return;
+        for (int k = 0; k < r.n_tokens; ++k) out.timestamped_tokens.push_back({r.token_ids[k], r.start_frame[k], r.end_frame[k], r.confidence[k]});
+        for (int k = 0; k < r.n_words; ++k) out.word_timestamps.push_back({r.words[k].word, r.words[k].start, r.words[k].end, r.words[k].confidence});
+    }
+    // the hypotheses of a one-clip pk_nbest array (freed here) as Result, a ScoredResult; extra(result, j) adds what the call returned beside them
+    template <class Result, class Extra>
+    static std::vector<Result> take_nbest(pk_nbest *res, bool timestamps, Extra extra) {
+        std::vector<Result> out(res[0].n_hyp);
+        for (int j = 0; j < res[0].n_hyp; ++j) {
+            out[j].score = res[0].score[j];
+            convert(res[0].hyp[j], timestamps, out[j].result);
+            extra(out[j], j);
+        }
+        pk_nbest_free(res, 1);
+        return out;
+    }
+    static pk_beam_options beam_options(const BeamOptions &opts) {
+        pk_beam_options o;
+        pk_beam_options_default(&o);
+        o.beam_width = opts.beam_width; o.token_prune = opts.token_prune; o.n_best = opts.n_best; o.timestamps = opts.timestamps ? 1 : 0;
+        return o;
+    }
+    static pk_tdt_beam_options tdt_beam_options(const TdtBeamOptions &opts) {
+        pk_tdt_beam_options o;
+        pk_tdt_beam_options_default(&o);
+        o.beam_width = opts.beam_width; o.label_prune = opts.label_prune; o.duration_prune = opts.duration_prune; o.n_best = opts.n_best;
+        return o;
+    }
+    static pk_lm_options lm_options(const LmOptions &opts) { return pk_lm_options{opts.alpha, opts.beta}; }
+
     std::string weights_path_, vocab_path_;
     pk_config cfg_;
     pk_model *m_ = nullptr;
