@@ -1168,6 +1168,62 @@ typedef struct pk_gemm_bf16_tile_diag {
 pk_status pk_diag_gemm_bf16_tile(pk_gemm_bf16_tile_diag *a);
 int pk_diag_gemm_bf16_tile_forms(int32_t *out, int cap);
 pk_status pk_diag_gemm_bf16_tile_form(pk_gemm_bf16_tile_diag *a);
+/* ONE product of the small-M bf16 GEMM family alone (kernels/gemm_smallm_bf16.hip; kernels.hpp GemmArgs): out = epi(bf16(X) bf16(W)^T + bias), fp32
+ * accumulation, for a product gemm_smallm_bf16_applies accepts (M <= 128, K % 256 == 0); epi as above (glu: W [2N][ldw], bias [2N]).
+ *   A [M][lda] fp32 (a_bf16 != 0: rounded to bf16 on the host, nearest even, and read as bf16), W [N or 2N][ldw] (rounded to bf16), resid [M][ldr] fp32: host
+ *            arrays AT THOSE PITCHES.  On the device every element of a row past K (resid: N) is a NaN (fp32 0x7FC5A5A5, bf16 0x7FC5).
+ *   a_t8:    A (a_bf16, lda == K, M % 8 == 0, epi resid) is staged in 8-row operand tiles: element (row, k) at
+ *            ((row / 8) (lda / 32) + k / 32) 256 + ((row % 8) + 8 (k / 8 % 4)) 8 + k % 8.
+ *   w_tiles: a copy of the bf16 weights in the kernel's operand tiles is built on the device (launch_tile_copy_bf16, from W at its pitch) and handed over as
+ *            GemmArgs::W_t16 when the weight rows are a multiple of 16; the launcher takes it for N % 16 == 0.
+ *   out_bf16 / out_t8 / fast_act: GemmArgs's.  out_bf16: out holds bf16 rows [M][ldo], two to a word (out_t8: 8-row tiles as above, ldo == N, N % 32 == 0).
+ *   resid_in_place: the residual is staged INSIDE out (resid == out, ldr == ldo, as fc2 of a block runs); the rest of out holds the fill.
+ *   ln_g / ln_b / eps: X = LayerNorm(A) folded into the product (fp32 rows, K = 256 * (1 .. 8; glu: .. 4)).
+ *   pre_g / pre_b (with ln_g; epi silu, N >= 256): X = LN(LN(A; pre); ln); pre_out [M][pre_ldo] (pre_out_words words) receives LN(A; pre).
+ *   dw (epi glu; rows = [M / dw_c streams][dw_c frames], dw_c = 1 / 2 / 4; N % 16 == 0): the streaming conv module's depthwise conv (kernel 9) + BatchNorm + SiLU
+ *            over [cache_in ; GLU rows] of every stream in the epilogue (kernels.hpp DwTail): out receives the activations, cache_out the streams' new caches.
+ *            cache_in [M / dw_c][8][N], cache_out [cache_streams >= M / dw_c][8][N], dw_w [9][N], the five vectors [N].
+ * out (out_words 32-bit words), pre_out and cache_out come back WHOLE, exactly as the launch left them; their device buffers are filled with 0x7FC5A5A5
+ * first.  Every offset the product may write is checked to lie inside them.
+ * form receives the form of the launch, by the function launch_gemm_smallm_bf16 switches on (kernels.hpp gemm_smallm_bf16_form): PK_DIAG_SMALLM_BF16_EPI,
+ * _STEPS (MFMA steps of 32 k per K slice: 8 / 16), _RT (row tiles per wave: 1 / 2), _RVALID (the rows of a tile that exist: 8 / 16), _A16, _LN, _CT (column
+ * tiles per wave: 1 / 2), _WT (operand-tiled weights), _DW, _AT (a_t8), _AL (rows by LDS-DMA), _PRE.  pk_diag_gemm_smallm_bf16_forms lists every form the
+ * launcher can take; pk_diag_gemm_smallm_bf16_form answers what pk_diag_gemm_smallm_bf16 would launch for a filled-in struct (pointers are looked at for
+ * null only) -- both host arithmetic, no device.
+ * Refused before anything is launched or a device is looked for, PK_ERR_UNSUPPORTED: what gemm_smallm_bf16_applies / _ln_applies / _pre_applies / _dw_applies
+ * refuse (the message names the predicate).  PK_ERR_INVALID: malformed arguments, a buffer too small.
+ * pk_diag_tile_copy_bf16: launch_tile_copy_bf16 alone -- src [rows][ld] (rounded to bf16; NaN past K) -> dst rows x K bf16 in the operand tiles. */
+#define PK_DIAG_SMALLM_BF16_EPI(form) ((form) & 7)
+#define PK_DIAG_SMALLM_BF16_STEPS(form) ((((form) >> 3) & 1) ? 16 : 8)
+#define PK_DIAG_SMALLM_BF16_RT(form) ((((form) >> 4) & 1) + 1)
+#define PK_DIAG_SMALLM_BF16_RVALID(form) ((((form) >> 5) & 1) ? 16 : 8)
+#define PK_DIAG_SMALLM_BF16_A16(form) (((form) >> 6) & 1)
+#define PK_DIAG_SMALLM_BF16_LN(form) (((form) >> 7) & 1)
+#define PK_DIAG_SMALLM_BF16_CT(form) ((((form) >> 8) & 1) + 1)
+#define PK_DIAG_SMALLM_BF16_WT(form) (((form) >> 9) & 1)
+#define PK_DIAG_SMALLM_BF16_DW(form) (((form) >> 10) & 1)
+#define PK_DIAG_SMALLM_BF16_AT(form) (((form) >> 11) & 1)
+#define PK_DIAG_SMALLM_BF16_AL(form) (((form) >> 12) & 1)
+#define PK_DIAG_SMALLM_BF16_PRE(form) (((form) >> 13) & 1)
+typedef struct pk_gemm_smallm_bf16_diag {
+    int32_t M, N, K, epi;
+    int32_t a_bf16, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place;
+    const float *A; int64_t lda;
+    const float *W; int64_t ldw;
+    const float *bias;
+    const float *resid; int64_t ldr; float alpha;
+    const float *ln_g, *ln_b; float eps;
+    const float *pre_g, *pre_b; uint32_t *pre_out; int64_t pre_ldo, pre_out_words;
+    int32_t dw, dw_c, dw_has_cache, cache_streams;
+    const float *cache_in; uint32_t *cache_out;
+    const float *dw_w, *dw_bias, *bn_mean, *bn_rstd, *bn_g, *bn_b;
+    int64_t ldo, out_words; uint32_t *out;
+    int32_t form;
+} pk_gemm_smallm_bf16_diag;
+pk_status pk_diag_gemm_smallm_bf16(pk_gemm_smallm_bf16_diag *a);
+int pk_diag_gemm_smallm_bf16_forms(int32_t *out, int cap);
+pk_status pk_diag_gemm_smallm_bf16_form(pk_gemm_smallm_bf16_diag *a);
+pk_status pk_diag_tile_copy_bf16(const float *src, int64_t rows, int K, int64_t ld, uint16_t *dst);
 
 #ifdef __cplusplus
 }

@@ -1530,6 +1530,153 @@ def diag_gemm_bf16_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, a16=
     return dict(out=out[:d.out_words], form=bf16_form(d.form))
 
 
+class PkGemmSmallmBf16Diag(C.Structure):
+    _u32p = C.POINTER(C.c_uint32)
+    _fields_ = ([(k, C.c_int32) for k in ("M", "N", "K", "epi", "a_bf16", "out_bf16", "out_t8", "a_t8", "fast_act", "w_tiles", "resid_in_place")]
+                + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),
+                   ("ln_g", f32p), ("ln_b", f32p), ("eps", C.c_float), ("pre_g", f32p), ("pre_b", f32p), ("pre_out", _u32p), ("pre_ldo", C.c_int64),
+                   ("pre_out_words", C.c_int64)]
+                + [(k, C.c_int32) for k in ("dw", "dw_c", "dw_has_cache", "cache_streams")]
+                + [("cache_in", f32p), ("cache_out", _u32p)]
+                + [(k, f32p) for k in ("dw_w", "dw_bias", "bn_mean", "bn_rstd", "bn_g", "bn_b")]
+                + [("ldo", C.c_int64), ("out_words", C.c_int64), ("out", _u32p), ("form", C.c_int32)])
+
+
+SMALLM_BF16_FIELDS = ("epi", "steps", "rt", "rvalid", "a16", "ln", "ct", "wt", "dw", "at", "al", "pre")
+
+
+def smallm_bf16_form(v):
+    """A GemmSmallmBf16Form value (kernels.hpp; PK_DIAG_SMALLM_BF16_*) -> (epi, STEPS 8 / 16, RT 1 / 2, rvalid 8 / 16, A16, LN, CT 1 / 2, WT, DW, AT, AL, PRE):
+    SMALLM_BF16_FIELDS names the positions"""
+    epi = {n: k for k, n in EPI.items()}[v & 7]
+    bit = lambda i: bool((v >> i) & 1)  # noqa: E731
+    return (epi, 16 if bit(3) else 8, 2 if bit(4) else 1, 16 if bit(5) else 8, bit(6), bit(7), 2 if bit(8) else 1, bit(9), bit(10), bit(11), bit(12), bit(13))
+
+
+def diag_gemm_smallm_bf16_forms():
+    """pk_diag_gemm_smallm_bf16_forms: every form launch_gemm_smallm_bf16 can take, as smallm_bf16_form tuples.  Host arithmetic."""
+    n = lib().pk_diag_gemm_smallm_bf16_forms(None, 0)
+    out = np.zeros(n, np.int32)
+    lib().pk_diag_gemm_smallm_bf16_forms(_i(out), n)
+    return [smallm_bf16_form(int(v)) for v in out]
+
+
+def _smallm_bf16_args(M, N, K, epi, a16, alpha, lda, ldw, ldo, ldr, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place, eps, pre_ldo, pre_out_words,
+                      dw_c, has_cache, cache_streams, out_words):
+    d = PkGemmSmallmBf16Diag()
+    d.M, d.N, d.K, d.epi = M, N, K, EPI[epi]
+    d.a_bf16, d.out_bf16, d.out_t8, d.a_t8, d.fast_act, d.w_tiles, d.resid_in_place = (int(bool(v)) for v in (a16, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place))
+    d.ldo = int(ldo) if ldo is not None else N
+    d.lda, d.ldw, d.ldr, d.alpha, d.eps = int(lda or K), int(ldw or K), int(ldr or (d.ldo if resid_in_place else N)), alpha, eps
+    d.pre_ldo = int(pre_ldo or K)
+    d.pre_out_words = int(pre_out_words) if pre_out_words is not None else M * d.pre_ldo
+    if dw_c:
+        d.dw, d.dw_c, d.dw_has_cache = 1, int(dw_c), int(bool(has_cache))
+        d.cache_streams = int(cache_streams) if cache_streams is not None else -(-M // int(dw_c))
+    if out_words is None:
+        out_words = (M * d.ldo + 1) // 2 if out_bf16 else M * d.ldo
+    d.out_words = int(out_words)
+    d.form = -1
+    return d
+
+
+def diag_gemm_smallm_bf16_form(M, N, K, epi="none", a16=False, bias=True, alpha=1.0, lda=None, ldw=None, ldo=None, ldr=None, out_bf16=False, out_t8=False,
+                               a_t8=False, fast_act=False, w_tiles=True, resid_in_place=False, ln=False, pre=False, eps=1e-5, pre_ldo=None, pre_out_words=None,
+                               dw_c=0, has_cache=True, cache_streams=None, out_words=None):
+    """pk_diag_gemm_smallm_bf16_form: the form pk_diag_gemm_smallm_bf16 would launch for this product (ln / pre / dw_c: with the folded norm, the norm in front,
+    the conv tail).  Host arithmetic, no device; every refusal of pk_diag_gemm_smallm_bf16 that depends on the shape and the switches raises here too."""
+    d = _smallm_bf16_args(M, N, K, epi, a16, alpha, lda, ldw, ldo, ldr, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place, eps, pre_ldo, pre_out_words,
+                          dw_c, has_cache, cache_streams, out_words)
+    one = np.zeros(1, np.float32)                                   # (looked at for null only)
+    one32 = np.zeros(1, np.uint32)
+    d.bias = _f(one) if bias else None
+    d.resid = _f(one) if epi == "resid" else None
+    if ln or pre:
+        d.ln_g = d.ln_b = _f(one)
+    if pre:
+        d.pre_g = d.pre_b = _f(one)
+        d.pre_out = one32.ctypes.data_as(C.POINTER(C.c_uint32))
+    L = lib()
+    L.pk_diag_gemm_smallm_bf16_form.argtypes = [C.POINTER(PkGemmSmallmBf16Diag)]
+    check(L.pk_diag_gemm_smallm_bf16_form(C.byref(d)))
+    return smallm_bf16_form(d.form)
+
+
+def diag_gemm_smallm_bf16(A, W, bias=None, epi="none", resid=None, alpha=1.0, a16=False, lda=None, ldw=None, ldo=None, ldr=None, out_bf16=False, out_t8=False,
+                          a_t8=False, fast_act=False, w_tiles=True, resid_in_place=False, ln=None, pre=None, eps=1e-5, pre_ldo=None, pre_out_words=None,
+                          dw=None, out_words=None, into=None):
+    """pk_diag_gemm_smallm_bf16: one product of the small-M bf16 family alone (include/parakeet_amd.h).  A [M][K], W [N or 2N][K], resid [M][N] dense fp32 (the
+    entry rounds W, and A with a16, to bf16); lda / ldw / ldr: the pitches they are staged at (NaN behind every row on the device); ln = (gamma, beta);
+    pre = (gamma, beta); dw = dict(c, has_cache, cache_in [S][8][N], cache_streams, w [9][N], bias, bn_mean, bn_rstd, bn_g, bn_b).  Returns dict(out = the
+    WHOLE output buffer as uint32 words [out_words] exactly as the launch left it (SKINNY_FILL32 where nothing was stored; out_bf16: two bf16 to a word),
+    form = smallm_bf16_form tuple, pre_out [pre_out_words] words, cache_out [cache_streams 8 N] words).  into: a dict that receives the host buffers (out,
+    pre_out, cache_out; pre-filled with the word into["fill"]) and the argument struct ("args") BEFORE the call -- what a refused call left of them."""
+    A, W = _c(A), _c(W)
+    M, K = A.shape
+    N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
+    assert W.shape[1] == K
+
+    def pitched(a, ld):
+        if ld is None or ld == a.shape[1]:
+            return a
+        p = np.zeros((a.shape[0], int(ld)), np.float32)
+        n = min(a.shape[1], int(ld))
+        p[:, :n] = a[:, :n]
+        return p
+
+    A, W = pitched(A, lda), pitched(W, ldw)
+    d = _smallm_bf16_args(M, N, K, epi, a16, alpha, A.shape[1], W.shape[1], ldo, ldr, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place, eps, pre_ldo,
+                          pre_out_words, dw["c"] if dw else 0, dw["has_cache"] if dw else False, dw.get("cache_streams") if dw else None, out_words)
+    keep = [A, W]
+    u32p = C.POINTER(C.c_uint32)
+
+    def opt(a):
+        if a is None:
+            return None
+        a = _c(a)
+        keep.append(a)
+        return _f(a)
+
+    d.A, d.W, d.bias = _f(A), _f(W), opt(bias)
+    if resid is not None:
+        keep.append(pitched(_c(resid), d.ldr))
+        d.resid = _f(keep[-1])
+    if ln is not None:
+        d.ln_g, d.ln_b = opt(ln[0]), opt(ln[1])
+    pre_out = None
+    if pre is not None:
+        pre_out = np.zeros(max(d.pre_out_words, 1), np.uint32)
+        d.pre_g, d.pre_b, d.pre_out = opt(pre[0]), opt(pre[1]), pre_out.ctypes.data_as(u32p)
+    cache_out = None
+    if dw is not None:
+        cache_out = np.zeros(max(d.cache_streams, 1) * 8 * N, np.uint32)
+        d.cache_in, d.cache_out = opt(dw["cache_in"]), cache_out.ctypes.data_as(u32p)
+        d.dw_w, d.dw_bias, d.bn_mean, d.bn_rstd, d.bn_g, d.bn_b = (opt(dw[k]) for k in ("w", "bias", "bn_mean", "bn_rstd", "bn_g", "bn_b"))
+    out = np.zeros(max(d.out_words, 1), np.uint32)
+    d.out = out.ctypes.data_as(u32p)
+    if into is not None:
+        for buf in (out, pre_out, cache_out):
+            if buf is not None:
+                buf.fill(into.get("fill", 0))
+        into.update(out=out, pre_out=pre_out, cache_out=cache_out, args=d)
+    L = lib()
+    L.pk_diag_gemm_smallm_bf16.argtypes = [C.POINTER(PkGemmSmallmBf16Diag)]
+    check(L.pk_diag_gemm_smallm_bf16(C.byref(d)))
+    return dict(out=out[:d.out_words], form=smallm_bf16_form(d.form), pre_out=pre_out, cache_out=cache_out)
+
+
+def diag_tile_copy_bf16(src, K=None):
+    """pk_diag_tile_copy_bf16: src [rows][ld >= K] (rounded to bf16) -> the rows x K bf16 bit patterns of the W_t16 operand tiles (launch_tile_copy_bf16)."""
+    src = _c(src)
+    rows, ld = src.shape
+    K = ld if K is None else int(K)
+    dst = np.empty(rows * K, np.uint16)
+    L = lib()
+    L.pk_diag_tile_copy_bf16.argtypes = [f32p, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_uint16)]
+    check(L.pk_diag_tile_copy_bf16(_f(src), rows, K, ld, dst.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return dst
+
+
 class Batch:
     """pk_batch: the resident pipeline (clips of one length stay in HBM; decode(k) overlaps encoder(k+1))."""
 

@@ -845,7 +845,7 @@ static GemmArgs bf16_tile_product(const pk_gemm_bf16_tile_diag *d, const char *w
     g.sigma_cols = d->sigma_cols;
     g.a_bf16 = d->a_bf16 ? 1 : 0; g.out_bf16 = d->out_bf16 ? 1 : 0; g.out_blocked = d->out_blocked ? 1 : 0; g.a_blocked = d->a_blocked ? 1 : 0;
     g.fast_act = d->fast_act ? 1 : 0;
-    if (gemm_smallm_bf16_applies(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: M <= %d with K %% 256 == 0 runs on the small-M bf16 kernel", who, kSmallMRowsBf16);
+    if (gemm_smallm_bf16_applies(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: M <= %d with K %% 256 == 0 runs on the small-M bf16 kernel (pk_diag_gemm_smallm_bf16)", who, kSmallMRowsBf16);
     if (const char *why = gemm_bf16_refusal(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: %s", who, why);
     if (g.out_bf16 && (g.remap_rows != 0 || (g.ldo & 3) != 0 || (g.N & 3) != 0 || g.sigma_cols != 0 || epi == EPI_RESID || epi == EPI_GLU))
         fail(PK_ERR_UNSUPPORTED, "%s: a bf16 output needs the row-major wide epilogue (no remap, no sigma_cols, no glu, no resid, ldo and N multiples of 4)", who);
@@ -914,6 +914,180 @@ pk_status pk_diag_gemm_bf16_tile(pk_gemm_bf16_tile_diag *d) {
         PK_CHECK_LAUNCH();
         PK_HIP(hipDeviceSynchronize());
         down(d->out, o, (size_t)d->out_words * 4);
+    });
+}
+
+// the PK_DIAG_SMALLM_BF16_* macros of include/parakeet_amd.h decode what gemm_smallm_bf16_form_of (kernels.hpp) encodes
+constexpr int kSmallmBf16ProbeA = gemm_smallm_bf16_form_of(EPI_RESID, 16, 2, 16, true, false, 1, true, false, true, false, false);
+constexpr int kSmallmBf16ProbeB = gemm_smallm_bf16_form_of(EPI_SILU, 8, 1, 8, false, true, 2, false, false, false, true, true);
+constexpr int kSmallmBf16ProbeC = gemm_smallm_bf16_form_of(EPI_GLU, 8, 1, 16, false, false, 1, false, true, false, false, false);
+static_assert(PK_DIAG_SMALLM_BF16_EPI(kSmallmBf16ProbeA) == EPI_RESID && PK_DIAG_SMALLM_BF16_STEPS(kSmallmBf16ProbeA) == 16 && PK_DIAG_SMALLM_BF16_RT(kSmallmBf16ProbeA) == 2 &&
+              PK_DIAG_SMALLM_BF16_RVALID(kSmallmBf16ProbeA) == 16 && PK_DIAG_SMALLM_BF16_A16(kSmallmBf16ProbeA) == 1 && PK_DIAG_SMALLM_BF16_LN(kSmallmBf16ProbeA) == 0 &&
+              PK_DIAG_SMALLM_BF16_CT(kSmallmBf16ProbeA) == 1 && PK_DIAG_SMALLM_BF16_WT(kSmallmBf16ProbeA) == 1 && PK_DIAG_SMALLM_BF16_DW(kSmallmBf16ProbeA) == 0 &&
+              PK_DIAG_SMALLM_BF16_AT(kSmallmBf16ProbeA) == 1 && PK_DIAG_SMALLM_BF16_AL(kSmallmBf16ProbeA) == 0 && PK_DIAG_SMALLM_BF16_PRE(kSmallmBf16ProbeA) == 0 &&
+              PK_DIAG_SMALLM_BF16_EPI(kSmallmBf16ProbeB) == EPI_SILU && PK_DIAG_SMALLM_BF16_STEPS(kSmallmBf16ProbeB) == 8 && PK_DIAG_SMALLM_BF16_RT(kSmallmBf16ProbeB) == 1 &&
+              PK_DIAG_SMALLM_BF16_RVALID(kSmallmBf16ProbeB) == 8 && PK_DIAG_SMALLM_BF16_A16(kSmallmBf16ProbeB) == 0 && PK_DIAG_SMALLM_BF16_LN(kSmallmBf16ProbeB) == 1 &&
+              PK_DIAG_SMALLM_BF16_CT(kSmallmBf16ProbeB) == 2 && PK_DIAG_SMALLM_BF16_WT(kSmallmBf16ProbeB) == 0 && PK_DIAG_SMALLM_BF16_AL(kSmallmBf16ProbeB) == 1 &&
+              PK_DIAG_SMALLM_BF16_PRE(kSmallmBf16ProbeB) == 1 && PK_DIAG_SMALLM_BF16_DW(kSmallmBf16ProbeC) == 1 && PK_DIAG_SMALLM_BF16_EPI(kSmallmBf16ProbeC) == EPI_GLU &&
+              PK_DIAG_SMALLM_BF16_AT(kSmallmBf16ProbeC) == 0,
+              "PK_DIAG_SMALLM_BF16_* must decode gemm_smallm_bf16_form_of");
+
+int pk_diag_gemm_smallm_bf16_forms(int32_t *out, int cap) {
+    for (int i = 0; out && i < kGemmSmallmBf16Forms.n && i < cap; ++i) out[i] = (int32_t)kGemmSmallmBf16Forms.v[i];
+    return kGemmSmallmBf16Forms.n;
+}
+
+// What both small-M bf16 diagnostics check for a product before either looks for a device, and the GemmArgs (operands replaced by placeholders: the form
+// function and the predicates look at the pointers for null / for each other only) they hand to gemm_smallm_bf16_form.  tail: where g.dw_tail points.
+static GemmArgs smallm_bf16_product(const pk_gemm_smallm_bf16_diag *d, DwTail &tail, const char *who) {
+    static const float some[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    static float sink[2];
+    const int M = d->M, N = d->N, K = d->K, epi = d->epi;
+    need(M > 0 && N > 0 && K > 0, "M/N/K");
+    need(epi >= EPI_NONE && epi <= EPI_GLU, "epi");
+    need(d->lda >= K && d->ldw >= K, "lda >= K, ldw >= K");
+    need((d->ln_g != nullptr) == (d->ln_b != nullptr) && (d->pre_g != nullptr) == (d->pre_b != nullptr), "gamma and beta: both or neither");
+    need(!d->pre_g || d->ln_g, "pre_g comes with ln_g");
+    need(epi != EPI_RESID || d->resid_in_place || d->ldr >= N, "ldr >= N");
+    need(!d->resid_in_place || (epi == EPI_RESID && d->ldr == d->ldo && !d->out_bf16), "resid_in_place: epi resid, ldr == ldo, fp32 rows");
+    const bool dw = d->dw != 0;
+    const int c = d->dw_c;
+    if (dw) need(c > 0 && d->cache_streams >= (M + c - 1) / c, "dw: dw_c > 0, cache_streams >= ceil(M / dw_c)");
+    GemmArgs g{some, d->lda, some + 1, d->ldw, d->bias ? some : nullptr, sink, d->ldo, epi == EPI_RESID ? (d->resid_in_place ? sink : some) : nullptr,
+               d->resid_in_place ? d->ldo : d->ldr, d->alpha, M, N, K};
+    g.a_bf16 = d->a_bf16 ? 1 : 0; g.out_bf16 = d->out_bf16 ? 1 : 0; g.out_t8 = d->out_t8 ? 1 : 0; g.a_t8 = d->a_t8 ? 1 : 0; g.fast_act = d->fast_act ? 1 : 0;
+    const int wrows = epi == EPI_GLU ? 2 * N : N;
+    if (d->w_tiles && wrows % 16 == 0) g.W_t16 = some + 2;          // (the launcher takes it for N % 16 == 0)
+    if (d->ln_g) { g.ln_g = some; g.ln_b = some; g.ln_eps = d->eps; }
+    if (d->pre_g) { g.pre_g = some; g.pre_b = some; g.pre_out = d->pre_out ? sink + 1 : nullptr; g.pre_ldo = d->pre_ldo; }
+    if (!gemm_smallm_bf16_applies(g, epi))
+        fail(PK_ERR_UNSUPPORTED, "%s: gemm_smallm_bf16_applies refuses: M <= %d, K %% 256 == 0, ldw %% 8 == 0, lda %% 8 == 0 (fp32 A: %% 4); bf16 rows out not for resid / glu; "
+             "out_t8: bf16 rows out, M %% 8 == 0, N %% 32 == 0, ldo == N; a_t8: bf16 A, M %% 8 == 0, lda == K, epi resid", who, kSmallMRowsBf16);
+    if (d->ln_g && !gemm_smallm_bf16_ln_applies(g, epi))
+        fail(PK_ERR_UNSUPPORTED, "%s: gemm_smallm_bf16_ln_applies refuses: the folded LayerNorm takes fp32 rows, K = 256 * (1 .. 8; glu: .. 4)", who);
+    if (d->pre_g && !gemm_smallm_bf16_pre_applies(g, epi))
+        fail(PK_ERR_UNSUPPORTED, "%s: gemm_smallm_bf16_pre_applies refuses: the norm in front takes epi silu, N >= 256, pre_ldo >= K and a multiple of 4", who);
+    if (dw) {
+        if (!gemm_smallm_bf16_dw_applies(g, epi, c, 9))
+            fail(PK_ERR_UNSUPPORTED, "%s: gemm_smallm_bf16_dw_applies refuses: the conv tail takes epi glu, dw_c = 1, 2 or 4, M %% dw_c == 0, N %% 16 == 0, fp32 rows out", who);
+        tail = DwTail{some, sink, d->dw_has_cache ? 1 : 0, c, some, some, some, some, some, some};
+        g.dw_tail = &tail;
+    }
+    // every offset the product may write lies inside the buffers (bf16 rows: two elements to a word; out_t8: whole tiles, ldo == N and M % 8 == 0)
+    const int64_t cap = d->out_words * (g.out_bf16 ? 2 : 1);
+    need(d->ldo >= N && (int64_t)(M - 1) * d->ldo + N <= cap, "ldo >= N, out_words >= (M - 1) ldo + N elements");
+    if (d->pre_g && d->pre_out) need((int64_t)(M - 1) * d->pre_ldo + K <= d->pre_out_words, "pre_out_words >= (M - 1) pre_ldo + K");
+    return g;
+}
+
+pk_status pk_diag_gemm_smallm_bf16_form(pk_gemm_smallm_bf16_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        DwTail tail{};
+        const GemmArgs g = smallm_bf16_product(d, tail, "pk_diag_gemm_smallm_bf16_form");
+        d->form = (int32_t)gemm_smallm_bf16_form(g, d->epi);
+    });
+}
+
+// One product of the small-M bf16 family, launched as launch_gemm_bf16 launches it
+pk_status pk_diag_gemm_smallm_bf16(pk_gemm_smallm_bf16_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        need(d->A && d->W && d->out, "A/W/out");
+        need(d->epi != EPI_RESID || d->resid, "resid");
+        need(!d->pre_g || d->pre_out, "pre_g comes with pre_out");
+        need(!d->dw || (d->cache_in && d->cache_out && d->dw_w && d->dw_bias && d->bn_mean && d->bn_rstd && d->bn_g && d->bn_b), "dw: caches / conv vectors");
+        DwTail tail{};
+        GemmArgs g = smallm_bf16_product(d, tail, "pk_diag_gemm_smallm_bf16");
+        const int M = d->M, N = d->N, K = d->K, epi = d->epi;
+        need_device();
+        const int wrows = epi == EPI_GLU ? 2 * N : N;
+        const uint32_t nan_word = 0x7fc5a5a5u;
+        const uint16_t nan_half = 0x7fc5;
+        // a bf16 operand at its pitch: rounded on the host, every element of a row past `cols` a NaN; t8: in 8-row operand tiles (ld == cols: no padding)
+        auto up16_padded = [&](DevBuf &buf, const float *src, int64_t rows, int64_t cols, int64_t ld, bool t8) {
+            std::vector<uint16_t> h((size_t)rows * ld, nan_half);
+            for (int64_t i = 0; i < rows; ++i)
+                for (int64_t k = 0; k < cols; ++k) {
+                    const size_t at = t8 ? (size_t)((i >> 3) * (ld >> 5) + (k >> 5)) * 256 + (size_t)((i & 7) + 8 * ((k >> 3) & 3)) * 8 + (size_t)(k & 7) : (size_t)i * ld + k;
+                    h[at] = bf16_rne(src[(size_t)i * ld + k]);
+                }
+            up(buf, h.data(), h.size() * 2);
+        };
+        auto up_padded = [&](DevBuf &buf, const float *src, int64_t rows, int64_t cols, int64_t ld) {
+            std::vector<float> h(src, src + (size_t)rows * ld);
+            for (int64_t i = 0; i < rows; ++i)
+                for (int64_t k = cols; k < ld; ++k) memcpy(&h[(size_t)i * ld + k], &nan_word, 4);
+            up(buf, h.data(), h.size() * 4);
+        };
+        auto filled = [&](DevBuf &buf, int64_t words) {
+            buf.reserve((size_t)std::max<int64_t>(words, 1) * 4);
+            PK_HIP(hipMemsetD32(buf.p, nan_word, (size_t)std::max<int64_t>(words, 1)));
+        };
+        DevBuf a, w, wt, b, r, o, gb, po, ci, co, par;
+        if (g.a_bf16) up16_padded(a, d->A, M, K, d->lda, g.a_t8 != 0);
+        else up_padded(a, d->A, M, K, d->lda);
+        up16_padded(w, d->W, wrows, K, d->ldw, false);
+        if (g.W_t16) {
+            wt.reserve((size_t)wrows * K * 2);
+            launch_tile_copy_bf16(w.as<float>(), wt.as<float>(), wrows, K, d->ldw, nullptr);
+            g.W_t16 = wt.as<float>();
+        }
+        if (d->bias) up(b, d->bias, (size_t)wrows * 4);
+        filled(o, d->out_words);
+        g.A = a.as<float>(); g.W = w.as<float>(); g.bias = d->bias ? b.as<float>() : nullptr; g.out = o.as<float>();
+        g.resid = nullptr;
+        if (epi == EPI_RESID) {
+            if (d->resid_in_place) {                                   // resid == out, as fc2 of a block runs: the rows of the residual stream inside the fill
+                PK_HIP(hipMemcpy2D(o.p, (size_t)d->ldo * 4, d->resid, (size_t)d->ldr * 4, (size_t)N * 4, (size_t)M, hipMemcpyHostToDevice));
+                g.resid = o.as<float>();
+            } else {
+                up_padded(r, d->resid, M, N, d->ldr);
+                g.resid = r.as<float>();
+            }
+        }
+        if (d->ln_g) {
+            up_rows(gb, {d->ln_g, d->ln_b, d->pre_g, d->pre_b}, K);
+            const float *p = gb.as<float>();
+            g.ln_g = p; g.ln_b = p + K;
+            if (d->pre_g) {
+                filled(po, d->pre_out_words);
+                g.pre_g = p + 2 * (size_t)K; g.pre_b = p + 3 * (size_t)K; g.pre_out = po.as<float>();
+            }
+        }
+        if (d->dw) {
+            const size_t nd = (size_t)N, S = (size_t)(M / d->dw_c);
+            up(ci, d->cache_in, S * 8 * nd * 4);
+            filled(co, (int64_t)d->cache_streams * 8 * N);
+            par.reserve((size_t)(9 + 5) * nd * 4);                     // the depthwise weights [9][d], then the five per-channel vectors
+            float *pp = par.as<float>();
+            PK_HIP(hipMemcpy(pp, d->dw_w, 9 * nd * 4, hipMemcpyHostToDevice));
+            const float *five[5] = {d->dw_bias, d->bn_mean, d->bn_rstd, d->bn_g, d->bn_b};
+            for (int i = 0; i < 5; ++i) PK_HIP(hipMemcpy(pp + (9 + i) * nd, five[i], nd * 4, hipMemcpyHostToDevice));
+            tail = DwTail{ci.as<float>(), co.as<float>(), d->dw_has_cache ? 1 : 0, d->dw_c, pp, pp + 9 * nd, pp + 10 * nd, pp + 11 * nd, pp + 12 * nd, pp + 13 * nd};
+        }
+        d->form = (int32_t)launch_gemm_smallm_bf16(g, epi, nullptr);    // the form it hands back is the one it switched on
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(d->out, o, (size_t)d->out_words * 4);
+        if (d->pre_g) down(d->pre_out, po, (size_t)d->pre_out_words * 4);
+        if (d->dw) down(d->cache_out, co, (size_t)d->cache_streams * 8 * N * 4);
+    });
+}
+
+pk_status pk_diag_tile_copy_bf16(const float *src, int64_t rows, int K, int64_t ld, uint16_t *dst) {
+    return guard([&] {
+        need(src && dst && rows > 0 && rows % 16 == 0 && K > 0 && K % 32 == 0 && ld >= K && ld % 8 == 0, "src/dst, rows % 16 == 0, K % 32 == 0, ld >= K, ld % 8 == 0");
+        need_device();
+        DevBuf a, b;
+        std::vector<uint16_t> h((size_t)rows * ld, (uint16_t)0x7fc5);
+        for (int64_t i = 0; i < rows; ++i)
+            for (int64_t k = 0; k < K; ++k) h[(size_t)i * ld + k] = bf16_rne(src[(size_t)i * ld + k]);
+        up(a, h.data(), h.size() * 2);
+        b.reserve((size_t)rows * K * 2);
+        launch_tile_copy_bf16(a.as<float>(), b.as<float>(), rows, K, ld, nullptr);
+        PK_CHECK_LAUNCH();
+        down(dst, b, (size_t)rows * K * 2);
     });
 }
 

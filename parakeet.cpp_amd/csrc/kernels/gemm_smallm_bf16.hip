@@ -36,8 +36,12 @@
 //     64-byte segments of 16 rows; what a product costs is what its busiest CU pulls).  Same values in the same lanes: bit-identical results.
 // Specification = the oracle's gemm_bf16 mode (oracle/pk_oracle.c linear_t: both operands rounded to bf16, k-ordered fp32 accumulation);
 // the accumulation ORDER differs (MFMA blocks of 32 k, K slices), so results are compared within the mode's tolerance
-// (tests/test_gpu_bf16.py: against float64 of the same rounded operands; tests/test_gpu_stream.py: the streaming mode against the oracle's).
+// (tests/test_gpu_bf16.py: against float64 of the same rounded operands; tests/test_gpu_stream.py: the streaming mode against the oracle's;
+// tests/test_gpu_smallm_bf16_gemm.py: every launch form alone, at operand pitches, the whole of every output buffer handed back).
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
+#include <utility>
 #include "../pk_devmath.h"
 #include "kernels.hpp"
 
@@ -490,95 +494,74 @@ static int sb_rows_per_wg(const GemmArgs &a, int nslices, bool glu, int tiles) {
 // Launch forms measured and not kept (up to 4fb176f selected in EXPERIMENTAL builds by PK_SB_CT / PK_SB_NT / PK_SB_ROWS / PK_SB_WT / PK_SB_AL):
 // forced column tiles per wave or rows per workgroup, non-temporal weight loads, the weights in their natural layout where the operand-tile copy
 // exists, and fp32 rows by per-lane loads instead of LDS-DMA.
-template <int EPI, int STEPS, bool A16, bool LN, int CT, bool WT>
-static void launch_sb_ct(const GemmArgs &a, hipStream_t s, int R) {
-    const int nslices = a.K / (32 * STEPS);
-    const int split = nslices < kSbMaxWaves ? nslices : kSbMaxWaves;
-    const int tiles = (a.N + 16 * CT - 1) / (16 * CT);
-    if (EPI == EPI_GLU && R == 32) R = 16;
-    if (R == 32 && (CT > 1 || split < 2 || a.pre_g)) R = 16;                   // two row tiles per wave: one column tile (registers), a wave per output tile
-    const dim3 grid(tiles, (a.M + R - 1) / R), block(64 * split);
-    if constexpr (EPI == EPI_RESID && A16 && CT == 1) {
-        if (a.a_t8 && R == 32) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 2, A16, LN, 1, WT, false, true>), grid, block, 0, s, a, split, 16, DwTail{}); return; }
-    }
-    if constexpr (EPI != EPI_GLU && CT == 1) {
-        if (R == 32) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 2, A16, LN, CT, WT>), grid, block, 0, s, a, split, 16, DwTail{}); return; }
-    }
-    // a norm in front of the folded one (GemmArgs::pre_g; the caller checked gemm_smallm_bf16_pre_applies): fc1 of a streaming block
-    if constexpr (LN && EPI == EPI_SILU && STEPS == 8) {
-        if (a.pre_g) {
-            if constexpr (WT) {
-                constexpr size_t lds = (size_t)kSbMaxWaves * 16 * (4 * 32 * STEPS + 16);
-                static DynLdsSlots slots_pre;
-                ensure_dyn_lds(slots_pre, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true, true>), lds);
-                hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true, true>), grid, block, lds, s, a, split, R, DwTail{});
-            } else {
-                hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, false, true>), grid, block, 0, s, a, split, R, DwTail{});
-            }
-            return;
-        }
-    }
-    if constexpr (!A16 && STEPS == 8 && WT) {
-        // fp32 rows of one row tile: the wave's slice of the rows by LDS-DMA (template AL), with the operand-tiled weights
-        constexpr size_t lds = (size_t)kSbMaxWaves * 16 * (4 * 32 * STEPS + 16);
-        static DynLdsSlots slots, slots_dw;
-        if constexpr (EPI == EPI_GLU && CT == 1) {
-            if (a.dw_tail) {
-                ensure_dyn_lds(slots_dw, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, true, false, true>), lds);
-                hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, true, false, true>), grid, block, lds, s, a, split, R, *a.dw_tail);
-                return;
-            }
-        }
-        ensure_dyn_lds(slots, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true>), lds);
-        hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT, false, false, true>), grid, block, lds, s, a, split, R, DwTail{});
-    } else {
-        if constexpr (EPI == EPI_GLU && CT == 1) {
-            if (a.dw_tail) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, true>), grid, block, 0, s, a, split, R, *a.dw_tail); return; }
-        }
-        if constexpr (EPI == EPI_RESID && A16 && CT == 1) {
-            if (a.a_t8) { hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, 1, WT, false, true>), grid, block, 0, s, a, split, R, DwTail{}); return; }
-        }
-        hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, 1, A16, LN, CT, WT>), grid, block, 0, s, a, split, R, DwTail{});
-    }
-}
 
-template <int EPI, int STEPS, bool A16, bool LN, bool WT>
-static void launch_sb_wt(const GemmArgs &a, hipStream_t s) {
-    const int nslices = a.K / (32 * STEPS);
+// Which instantiation a product takes, and with how many rows of a tile (kernels.hpp: GemmSmallmBf16Form).  launch_gemm_smallm_bf16 switches on this
+// function's result and pk_diag_gemm_smallm_bf16 reports it: every threshold of the family lives here and nowhere else.
+GemmSmallmBf16Form gemm_smallm_bf16_form(const GemmArgs &a, int epi) {
+    const bool glu = epi == EPI_GLU;
+    const bool ln = a.ln_g != nullptr;                              // LayerNorm folded in (the caller checked gemm_smallm_bf16_ln_applies): fp32 rows
+    const bool a16 = !ln && a.a_bf16;
+    // bf16 rows: 4 registers per MFMA operand -- slices of 512 k where 256 would leave more than kSbMaxWaves of them (fc2 of the 600M models:
+    // K = 4096); not for GLU (two weight tiles per wave)
+    const int steps = (a16 && !glu && a.K % 512 == 0 && a.K / 256 > kSbMaxWaves) ? 16 : 8;
+    const bool wt = a.W_t16 && a.N % 16 == 0;
+    const int nslices = a.K / (32 * steps);
     const int split = nslices < kSbMaxWaves ? nslices : kSbMaxWaves;
     const int tiles1 = (a.N + 15) / 16;
-    const int R = sb_rows_per_wg(a, nslices, EPI == EPI_GLU, tiles1);
+    int R = sb_rows_per_wg(a, nslices, glu, tiles1), ct = 1;
     // Two column tiles per wave (the activation registers of a K slice feed both) where that lowers what the busiest CU pulls: fp32 rows (4 bytes
     // per k and row against 2 per k and column) of products wide enough to keep every CU busy with 16 rows x 32 columns per workgroup -- fc1 and
     // qkv of the 600M models: K (16 * 4 + 32 * 2) = 128 KB per CU instead of K (32 * 4 + 16 * 2) = 160 KB.
-    if constexpr (!A16 && EPI != EPI_GLU) {
-        if (R == 32 && split >= 2 && a.N % 32 == 0 && (tiles1 / 2) * ((a.M + 15) / 16) >= 192) { launch_sb_ct<EPI, STEPS, A16, LN, 2, WT>(a, s, 16); return; }
+    if (!a16 && !glu && R == 32 && split >= 2 && a.N % 32 == 0 && (tiles1 / 2) * ((a.M + 15) / 16) >= 192) { ct = 2; R = 16; }
+    if (R == 32 && (glu || split < 2 || a.pre_g)) R = 16;           // two row tiles per wave: a wave per output tile; not in front of a second norm
+    const int rt = R == 32 ? 2 : 1, rvalid = rt == 2 ? 16 : R;
+    const bool at = epi == EPI_RESID && a16 && a.a_t8;              // (instantiated for the product that takes them: fc2)
+    // a norm in front of the folded one (GemmArgs::pre_g; the caller checked gemm_smallm_bf16_pre_applies): fc1 of a streaming block
+    const bool pre = rt == 1 && ln && epi == EPI_SILU && a.pre_g;
+    const bool dw = rt == 1 && glu && a.dw_tail;
+    // fp32 rows of one row tile: the wave's slice of the rows by LDS-DMA (template AL), with the operand-tiled weights
+    const bool al = rt == 1 && !a16 && wt;
+    return gemm_smallm_bf16_form_of(epi, steps, rt, rvalid, a16, ln, ct, wt, dw, at, al, pre);
+}
+
+// one instantiation: F = a form with its rvalid field cleared (the rows of a tile that exist are a kernel argument)
+template <int F>
+static void launch_sb_inst(const GemmArgs &a, hipStream_t s, int rvalid) {
+    constexpr int EPI = gemm_smallm_bf16_form_epi(F), STEPS = gemm_smallm_bf16_form_steps(F), RT = gemm_smallm_bf16_form_rt(F), CT = gemm_smallm_bf16_form_ct(F);
+    constexpr bool A16 = gemm_smallm_bf16_form_a16(F), LN = gemm_smallm_bf16_form_ln(F), WT = gemm_smallm_bf16_form_wt(F), DW = gemm_smallm_bf16_form_dw(F);
+    constexpr bool AT = gemm_smallm_bf16_form_at(F), AL = gemm_smallm_bf16_form_al(F), PRE = gemm_smallm_bf16_form_pre(F);
+    const int nslices = a.K / (32 * STEPS);
+    const int split = nslices < kSbMaxWaves ? nslices : kSbMaxWaves;
+    const int tiles = (a.N + 16 * CT - 1) / (16 * CT), R = RT == 2 ? 32 : rvalid;
+    const dim3 grid(tiles, (a.M + R - 1) / R), block(64 * split);
+    constexpr size_t lds = AL ? (size_t)kSbMaxWaves * 16 * (4 * 32 * STEPS + 16) : 0;
+    if constexpr (AL) {
+        static DynLdsSlots slots;                                   // (one per instantiation)
+        ensure_dyn_lds(slots, reinterpret_cast<const void *>(&gemm_smallm_bf16_kernel<EPI, STEPS, RT, A16, LN, CT, WT, DW, AT, AL, PRE>), lds);
     }
-    launch_sb_ct<EPI, STEPS, A16, LN, 1, WT>(a, s, R);
+    hipLaunchKernelGGL((gemm_smallm_bf16_kernel<EPI, STEPS, RT, A16, LN, CT, WT, DW, AT, AL, PRE>), grid, block, lds, s, a, split, rvalid, DW ? *a.dw_tail : DwTail{});
 }
-
-template <int EPI, int STEPS, bool A16, bool LN>
-static void launch_sb(const GemmArgs &a, hipStream_t s) {
-    if (a.W_t16 && a.N % 16 == 0) launch_sb_wt<EPI, STEPS, A16, LN, true>(a, s);
-    else launch_sb_wt<EPI, STEPS, A16, LN, false>(a, s);
-}
-
-template <int EPI>
-static void launch_sb_epi(const GemmArgs &a, hipStream_t s) {
-    if (a.ln_g) {                                                   // LayerNorm folded in (the caller checked gemm_smallm_bf16_ln_applies)
-        launch_sb<EPI, 8, false, true>(a, s);
-    } else if (a.a_bf16) {
-        // bf16 rows: 4 registers per MFMA operand -- slices of 512 k where 256 would leave more than kSbMaxWaves of them (fc2 of the 600M models:
-        // K = 4096); not for GLU (two weight tiles per wave)
-        if constexpr (EPI != EPI_GLU) {
-            if (a.K % 512 == 0 && a.K / 256 > kSbMaxWaves) { launch_sb<EPI, 16, true, false>(a, s); return; }
-        }
-        launch_sb<EPI, 8, true, false>(a, s);
-    } else {
-        launch_sb<EPI, 8, false, false>(a, s);
+// the instantiations: the forms with their rvalid field cleared, each once (two forms that differ in the rows of a tile in use share a kernel)
+constexpr int kSbRvalidBit = gemm_smallm_bf16_form_of(0, 8, 1, 16, false, false, 1, false, false, false, false, false);
+struct SbInsts { int v[kGemmSmallmBf16FormCount]; int n; };
+constexpr SbInsts sb_insts() {
+    SbInsts t{};
+    for (int i = 0; i < kGemmSmallmBf16Forms.n; ++i) {
+        const int key = (int)kGemmSmallmBf16Forms.v[i] & ~kSbRvalidBit;
+        bool seen = false;
+        for (int j = 0; j < t.n; ++j) seen = seen || t.v[j] == key;
+        if (!seen) t.v[t.n++] = key;
     }
+    return t;
 }
-
+constexpr SbInsts kSbInsts = sb_insts();
+static_assert(kSbInsts.n == 104, "the instantiations of gemm_smallm_bf16_kernel the launcher can take");
+// launches the instantiation of `form`; false: the table has none (the form's rvalid goes to the kernel as an argument)
+template <size_t... I>
+static bool launch_sb_form(int form, const GemmArgs &a, hipStream_t s, std::index_sequence<I...>) {
+    const int key = form & ~kSbRvalidBit, rvalid = gemm_smallm_bf16_form_rvalid(form);
+    return ((key == kSbInsts.v[I] ? (launch_sb_inst<kSbInsts.v[I]>(a, s, rvalid), true) : false) || ...);
+}
 // W16 [rows][ld] (bf16) -> the operand tiles of GemmArgs::W_t16: per (16 rows, 32 k) one KB [lane = (row & 15) + 16 * (k / 8 & 3)][8 bf16]
 __global__ __launch_bounds__(256) void tile_copy_bf16_kernel(const uint4 *src, uint4 *dst, int64_t n_chunks, int ksteps, int64_t ld8 /* ld / 8 */) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // one 16-byte chunk (8 bf16) each
@@ -594,15 +577,13 @@ void launch_tile_copy_bf16(const float *src16, float *dst16, int64_t rows, int K
                        reinterpret_cast<uint4 *>(dst16), n, K / 32, ld / 8);
 }
 
-void launch_gemm_smallm_bf16(const GemmArgs &a, int epi, hipStream_t s) {
-    switch (epi) {
-    case EPI_NONE: launch_sb_epi<EPI_NONE>(a, s); break;
-    case EPI_RELU: launch_sb_epi<EPI_RELU>(a, s); break;
-    case EPI_SILU: launch_sb_epi<EPI_SILU>(a, s); break;
-    case EPI_RESID: launch_sb_epi<EPI_RESID>(a, s); break;
-    case EPI_GLU: launch_sb_epi<EPI_GLU>(a, s); break;
-    default: break;
+GemmSmallmBf16Form launch_gemm_smallm_bf16(const GemmArgs &a, int epi, hipStream_t s) {
+    const int form = gemm_smallm_bf16_form(a, epi);
+    if (epi < EPI_NONE || epi > EPI_GLU || !launch_sb_form(form, a, s, std::make_index_sequence<kSbInsts.n>{})) {
+        fprintf(stderr, "parakeet_amd: internal error: launch_gemm_smallm_bf16 has no kernel for form %d\n", form);
+        abort();
     }
+    return (GemmSmallmBf16Form)form;
 }
 
 }  // namespace pk

@@ -306,7 +306,69 @@ bool gemm_smallm_bf16_applies(const GemmArgs &a, int epi);
 bool gemm_smallm_bf16_dw_applies(const GemmArgs &a, int epi, int c, int kc);   // ... with GemmArgs::dw_tail: GLU, conv kernel 9, c = 1 / 2 / 4 frames per stream
 bool gemm_smallm_bf16_ln_applies(const GemmArgs &a, int epi);
 bool gemm_smallm_bf16_pre_applies(const GemmArgs &a, int epi);    // ... and GemmArgs::pre_g (a second norm in front): SiLU products, slices of 256 k     // ... with GemmArgs::ln_g set: K = 256 * (1 .. 8 waves; GLU: 4), fp32 rows
-void launch_gemm_smallm_bf16(const GemmArgs &a, int epi, hipStream_t s);
+// The form of a small-M bf16 launch, by the function launch_gemm_smallm_bf16 switches on: value = gemm_smallm_bf16_form_of(...) -- the template
+// parameters of gemm_smallm_bf16_kernel and the one kernel argument that selects a path of its own:
+//   epi:    the epilogue the kernel is instantiated for (GemmEpi);  steps: MFMA steps of 32 k per K slice, 8 or 16 (bf16 rows, K / 256 > 8 waves, K % 512 == 0)
+//   rt:     16-row MFMA tiles per wave, 1 or 2 (32 rows per workgroup);  rvalid: the rows of a tile that exist, 16, or 8 (rt = 1: 8 rows per workgroup)
+//   a16:    A read as bf16 rows (GemmArgs::a_bf16);  ln: the LayerNorm folded in (ln_g);  ct: 16-column tiles per wave, 1 or 2
+//   wt:     the weights from the operand-tile copy (W_t16, N % 16 == 0);  dw: GLU with the conv tail (dw_tail);  at: A in 8-row operand tiles (a_t8)
+//   al:     fp32 rows travel global -> LDS by DMA (rt = 1, fp32 rows, wt);  pre: the second norm in front of the folded one (pre_g)
+enum GemmSmallmBf16Form : int {};
+constexpr GemmSmallmBf16Form gemm_smallm_bf16_form_of(int epi, int steps, int rt, int rvalid, bool a16, bool ln, int ct, bool wt, bool dw, bool at, bool al,
+                                                      bool pre) {
+    return (GemmSmallmBf16Form)(epi | ((steps == 16 ? 1 : 0) << 3) | ((rt == 2 ? 1 : 0) << 4) | ((rvalid == 16 ? 1 : 0) << 5) | ((a16 ? 1 : 0) << 6) |
+                                ((ln ? 1 : 0) << 7) | ((ct == 2 ? 1 : 0) << 8) | ((wt ? 1 : 0) << 9) | ((dw ? 1 : 0) << 10) | ((at ? 1 : 0) << 11) |
+                                ((al ? 1 : 0) << 12) | ((pre ? 1 : 0) << 13));
+}
+constexpr int gemm_smallm_bf16_form_epi(int f) { return f & 7; }
+constexpr int gemm_smallm_bf16_form_steps(int f) { return (f >> 3) & 1 ? 16 : 8; }
+constexpr int gemm_smallm_bf16_form_rt(int f) { return (f >> 4) & 1 ? 2 : 1; }
+constexpr int gemm_smallm_bf16_form_rvalid(int f) { return (f >> 5) & 1 ? 16 : 8; }
+constexpr bool gemm_smallm_bf16_form_a16(int f) { return (f >> 6) & 1; }
+constexpr bool gemm_smallm_bf16_form_ln(int f) { return (f >> 7) & 1; }
+constexpr int gemm_smallm_bf16_form_ct(int f) { return (f >> 8) & 1 ? 2 : 1; }
+constexpr bool gemm_smallm_bf16_form_wt(int f) { return (f >> 9) & 1; }
+constexpr bool gemm_smallm_bf16_form_dw(int f) { return (f >> 10) & 1; }
+constexpr bool gemm_smallm_bf16_form_at(int f) { return (f >> 11) & 1; }
+constexpr bool gemm_smallm_bf16_form_al(int f) { return (f >> 12) & 1; }
+constexpr bool gemm_smallm_bf16_form_pre(int f) { return (f >> 13) & 1; }
+GemmSmallmBf16Form gemm_smallm_bf16_form(const GemmArgs &a, int epi);   // of a product gemm_smallm_bf16_applies accepts (ln_g / pre_g / dw_tail: their predicates)
+GemmSmallmBf16Form launch_gemm_smallm_bf16(const GemmArgs &a, int epi, hipStream_t s);   // launches, and returns the form it switched on
+// Every form launch_gemm_smallm_bf16 can take.  A form exists when its fields are consistent with the launcher's rules:
+//   slices of 512 k: bf16 rows, no GLU (two weight tiles per wave);  a folded norm reads fp32 rows
+//   two row tiles per wave: no GLU, one column tile, none of dw / al / pre;  two column tiles per wave: fp32 rows, no GLU, 16 rows per workgroup
+//   a_t8: the residual product on bf16 rows;  the conv tail: GLU;  the second norm: SiLU with the folded norm, one row tile
+//   LDS-DMA rows: exactly the fp32-row forms of one row tile on operand-tiled weights
+constexpr bool gemm_smallm_bf16_form_exists(int epi, int steps, int rt, int rvalid, bool a16, bool ln, int ct, bool wt, bool dw, bool at, bool al, bool pre) {
+    const bool glu = epi == EPI_GLU;
+    if (steps == 16 && (!a16 || glu)) return false;
+    if (ln && a16) return false;
+    if (rt == 2 && (glu || ct != 1 || rvalid != 16 || dw || al || pre)) return false;
+    if (ct == 2 && (a16 || glu || rt != 1 || rvalid != 16)) return false;
+    if (at && !(epi == EPI_RESID && a16)) return false;
+    if (dw && !glu) return false;
+    if (pre && !(ln && epi == EPI_SILU)) return false;
+    return al == (rt == 1 && !a16 && wt);
+}
+struct GemmSmallmBf16Forms { GemmSmallmBf16Form v[256]; int n; };
+constexpr GemmSmallmBf16Forms gemm_smallm_bf16_forms() {
+    GemmSmallmBf16Forms t{};
+    for (int epi = EPI_NONE; epi <= EPI_GLU; ++epi)
+        for (int bits = 0; bits < (1 << 11); ++bits) {
+            const int steps = bits & 1 ? 16 : 8, rt = bits & 2 ? 2 : 1, rvalid = bits & 4 ? 16 : 8, ct = bits & 32 ? 2 : 1;
+            const bool a16 = bits & 8, ln = bits & 16, wt = bits & 64, dw = bits & 128, at = bits & 256, al = bits & 512, pre = bits & 1024;
+            if (gemm_smallm_bf16_form_exists(epi, steps, rt, rvalid, a16, ln, ct, wt, dw, at, al, pre))
+                t.v[t.n++] = gemm_smallm_bf16_form_of(epi, steps, rt, rvalid, a16, ln, ct, wt, dw, at, al, pre);
+        }
+    return t;
+}
+constexpr GemmSmallmBf16Forms kGemmSmallmBf16Forms = gemm_smallm_bf16_forms();
+// two row tiles: 4 epilogues x (fp32 / folded norm / bf16 rows in slices of 256 / 512 k) x wt = 32, + a_t8 on both slice lengths x wt = 4;
+// one row tile, 8 or 16 rows per workgroup: fp32 / folded-norm rows 5 epilogues x 2 x wt x 2 = 40, + two column tiles 4 x 2 x wt = 16, + the second norm (one or
+// two column tiles) 2 x wt + wt = 6, + the conv tail 2 x wt x 2 = 8; bf16 rows 5 x wt x 2 + 4 x wt x 2 (slices of 512 k) = 36, + a_t8 2 x wt x 2 = 8, + the conv tail
+// wt x 2 = 4
+constexpr int kGemmSmallmBf16FormCount = 32 + 4 + 40 + 16 + 6 + 8 + 36 + 8 + 4;
+static_assert(kGemmSmallmBf16Forms.n == kGemmSmallmBf16FormCount, "kGemmSmallmBf16Forms must list every form the launcher can take");
 double gemm_flops(const GemmArgs &a, int epi);
 
 // ---- conv subsampling (src/encoder.cpp:219-241), channels-last ---------------------------------------

@@ -91,6 +91,12 @@ def test_no_gpu_is_a_loud_error(tmp_path):
     with pytest.raises(capi.PkError) as e:             # the tile GEMM diagnostic: valid arguments, no device
         capi.diag_gemm_tile(np.zeros((4, 96), np.float32), np.zeros((16, 96), np.float32))
     assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:             # the small-M bf16 GEMM diagnostics: valid arguments, no device
+        capi.diag_gemm_smallm_bf16(np.zeros((4, 256), np.float32), np.zeros((16, 256), np.float32))
+    assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_tile_copy_bf16(np.zeros((16, 32), np.float32))
+    assert e.value.code == -4
     with pytest.raises(capi.PkError) as e:             # the multi-GPU entry point as well
         capi.Group(str(wp), cfg)
     assert e.value.code == -4
@@ -223,6 +229,43 @@ def test_bf16_tile_gemm_form_table_queries_and_refusals_need_no_device():
     with pytest.raises(capi.PkError) as e:
         capi.diag_gemm_bf16_tile(np.zeros((2000, 512), np.float32), np.zeros((512, 512), np.float32), a16=True, a_blocked=True)
     assert e.value.code == -7
+
+
+def test_smallm_bf16_gemm_form_table_queries_and_refusals_need_no_device():
+    """pk_diag_gemm_smallm_bf16_forms (what tests/test_gpu_smallm_bf16_gemm.py::test_every_form_has_a_case compares its cases with) and
+    pk_diag_gemm_smallm_bf16_form are host arithmetic: the streaming products of the 600M models (16 streams x 2 frames) on the forms gemm_smallm_bf16.hip's
+    comments name; and pk_diag_gemm_smallm_bf16 refuses what the family's predicates refuse before it looks for a device."""
+    for name in ("pk_diag_gemm_smallm_bf16", "pk_diag_gemm_smallm_bf16_form", "pk_diag_gemm_smallm_bf16_forms"):
+        assert name in declared_symbols() and hasattr(capi.lib(), name)
+    every = capi.diag_gemm_smallm_bf16_forms()
+    assert len(every) == 154 and len(set(every)) == 154
+    i = {n: k for k, n in enumerate(capi.SMALLM_BF16_FIELDS)}
+    for f in every:
+        assert f[i["steps"]] == 8 or (f[i["a16"]] and f[i["epi"]] != "glu")
+        assert not (f[i["ln"]] and f[i["a16"]])
+        assert f[i["rt"]] == 1 or (f[i["epi"]] != "glu" and f[i["ct"]] == 1 and f[i["rvalid"]] == 16 and not (f[i["dw"]] or f[i["al"]] or f[i["pre"]]))
+        assert f[i["ct"]] == 1 or (not f[i["a16"]] and f[i["epi"]] != "glu" and f[i["rvalid"]] == 16)
+        assert f[i["al"]] == (f[i["rt"]] == 1 and not f[i["a16"]] and f[i["wt"]])
+        assert (not f[i["at"]] or (f[i["epi"]] == "resid" and f[i["a16"]])) and (not f[i["dw"]] or f[i["epi"]] == "glu")
+        assert not f[i["pre"]] or (f[i["ln"]] and f[i["epi"]] == "silu")
+    q = capi.diag_gemm_smallm_bf16_form
+    assert q(32, 4096, 1024, epi="silu", ln=True, pre=True, out_bf16=True, out_t8=True, fast_act=True) == ("silu", 8, 1, 16, False, True, 2, True, False, False, True, True)   # fc1
+    assert q(32, 1024, 4096, epi="resid", a16=True, a_t8=True, alpha=0.5, resid_in_place=True) == ("resid", 16, 1, 8, True, False, 1, True, False, True, False, False)        # fc2
+    assert q(32, 3072, 1024, ln=True) == ("none", 8, 1, 16, False, True, 2, True, False, False, True, False)                                                                  # qkv
+    assert q(32, 1024, 1024, epi="glu", ln=True, dw_c=2) == ("glu", 8, 1, 8, False, True, 1, True, True, False, True, False)                                                  # pw1 + conv tail
+    assert q(128, 768, 512, a16=True) == ("none", 8, 2, 16, True, False, 1, True, False, False, False, False)
+    assert q(128, 1030, 512) == ("none", 8, 2, 16, False, False, 1, False, False, False, False, False)                       # ragged N: natural weights
+    for bad in (dict(M=129, N=256, K=256), dict(M=8, N=256, K=320), dict(M=8, N=256, K=256, epi="glu", out_bf16=True), dict(M=8, N=256, K=2304, ln=True),
+                dict(M=8, N=240, K=512, epi="silu", ln=True, pre=True), dict(M=9, N=256, K=256, epi="glu", dw_c=3)):
+        with pytest.raises(capi.PkError) as e:
+            q(**bad)
+        assert e.value.code == -7, bad
+    with pytest.raises(capi.PkError) as e:                           # refused before a device is looked for
+        capi.diag_gemm_smallm_bf16(np.zeros((8, 320), np.float32), np.zeros((16, 320), np.float32))
+    assert e.value.code == -7
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_gemm_smallm_bf16(np.zeros((8, 256), np.float32), np.zeros((16, 256), np.float32), ldo=8)
+    assert e.value.code == -1
 
 
 def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
