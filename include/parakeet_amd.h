@@ -726,6 +726,42 @@ pk_status pk_read_wav(const char *path, float **pcm, int64_t *n_samples, int *sa
  * beta 7.857, 16-tap half width).  FLAC / MP3 / OGG are not decoded.  pk_resample: the resampler alone (resample(), :250-262). */
 pk_status pk_read_audio(const char *path, int target_rate, float **pcm, int64_t *n_samples, int *original_rate);
 pk_status pk_resample(const float *pcm, int64_t n, int src_rate, int dst_rate, float **out, int64_t *n_out);
+/* ---- resampling on the device (kernels/resample.hip) ---------------------------------------------------------------
+ * pk_resample's filter in polyphase form: with g = gcd(src, dst), up = dst / g and down = src / g the 32 weights of output i depend on
+ * i mod up only.  They are tabulated once per (src, dst) on the host in fp64 from pk_resample's own expressions, and one launch turns a
+ * packed ragged batch of input-rate clips into dst-rate samples, 32 fp64 multiply-adds per output.  The specification is
+ * tests/resample_ref.py, which the device reproduces bit for bit.  Against pk_resample the result is bit-identical when src / dst or
+ * dst / src is an integer; otherwise a few samples in 10 000 differ by one fp32 rounding (pk_resample rounds i * src / dst to a double
+ * before it takes the tap distances, the table takes them from the exact fraction; tests/test_resample_ref.py holds the bounds).
+ * Rates from 4000 to 384000 Hz, clips of fewer than 2^31 samples; anything else is PK_ERR_UNSUPPORTED before anything is allocated.
+ * Out of scope: resampling inside streaming sessions (it needs history and lookahead carried across chunks), int16 or multi-channel input
+ * on the device, pk_batch_* at other rates, and any change to pk_resample or to a default.
+ * pk_resample_length: samples pk_resample returns for n input samples, ceil(n * up / down) (host arithmetic; -1 for a refused argument).
+ * pk_resample_run: outputs one workgroup of the kernel owns at this pair of rates (they read run * down / up + 32 input samples); 0 if refused.
+ * pk_resample_table: the table, host only.  table (may be NULL) takes up x 32 doubles, row r = phase r, column k = the tap at input sample
+ *   c - 15 + k around the centre c; cap_rows < up: PK_ERR_INVALID, with *up / *down still set.
+ * pk_resample_device: the stage alone on `device`, host buffers in and out.  Clip i = pcm[offsets[i] .. offsets[i+1]) at src_rate; its
+ *   pk_resample_length samples go to out[out_offsets[i] ..), which must end at or before out_offsets[i+1].  out[0 .. out_offsets[n_clips]) is
+ *   uploaded before and read back after the launch, so what lies between the clips' outputs comes back as it was unless the kernel wrote
+ *   there.  Empty clips are allowed and give empty outputs.  src_rate == dst_rate copies.
+ * pk_resample_device_timed: the same launch reps times between hipEvents; *ms = the median (input already on the device, nothing read back). */
+int64_t pk_resample_length(int64_t n, int src_rate, int dst_rate);
+int pk_resample_run(int src_rate, int dst_rate);
+pk_status pk_resample_table(int src_rate, int dst_rate, double *table, int cap_rows, int *up, int *down);
+pk_status pk_resample_device(int device, const float *pcm, const int64_t *offsets, int n_clips, int src_rate, int dst_rate, float *out,
+                             const int64_t *out_offsets);
+pk_status pk_resample_device_timed(int device, const float *pcm, const int64_t *offsets, int n_clips, int src_rate, int dst_rate, int reps, float *ms);
+/* Sample rate of the PCM that the one-call entry points of this model take: pk_transcribe_pcm, pk_transcribe_pcm_nbest (and _nbest_lm,
+ * _nbest_tdt, _nbest_tdt_lm, _nbest_rescored), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm and pk_spot_pcm.  Default 16000: the path
+ * as it always was.  At another rate (4000 .. 384000, else PK_ERR_UNSUPPORTED and the previous rate stays in force) pcm and offsets of those
+ * calls count input-rate samples; batches are planned by the resampled lengths, every batch is uploaded raw and resampled on the device
+ * into the buffer the 16 kHz copy went to, and frames, timestamps and every result are those of the 16 kHz signal
+ * pk_resample_device(rate -> 16000) gives.  UNCHANGED, always 16 kHz: pk_mel*, pk_batch_* (what bench.py times), pk_stream_*,
+ * pk_sortformer_forward_pcm, pk_frontend_* and pk_resample itself.  Not to be changed while a call is in flight. */
+pk_status pk_model_set_input_rate(pk_model *m, int rate);
+pk_status pk_model_get_input_rate(const pk_model *m, int *rate);
+/* pk_model_set_input_rate on every replica of the group (pk_group_transcribe_pcm then takes input-rate PCM). */
+pk_status pk_group_set_input_rate(pk_group *g, int rate);
 /* read_audio(const uint8_t *data, size_t len, target) (audio_io.hpp:27-28): an encoded RIFF/WAVE image in memory -> mono PCM at
  * target_rate (malloc'd, pk_free). */
 pk_status pk_read_audio_memory(const void *data, size_t len, int target_rate, float **pcm, int64_t *n_samples, int *original_rate, int *n_channels);

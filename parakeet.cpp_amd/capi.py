@@ -259,6 +259,14 @@ _LATE_SIGNATURES = {
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
+    "pk_resample_length": [C.c_int64, C.c_int, C.c_int],
+    "pk_resample_run": [C.c_int, C.c_int],
+    "pk_resample_table": [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "pk_resample_device": [C.c_int, f32p, i64p, C.c_int, C.c_int, C.c_int, f32p, i64p],
+    "pk_resample_device_timed": [C.c_int, f32p, i64p, C.c_int, C.c_int, C.c_int, C.c_int, f32p],
+    "pk_model_set_input_rate": [C.c_void_p, C.c_int],
+    "pk_model_get_input_rate": [C.c_void_p, C.POINTER(C.c_int)],
+    "pk_group_set_input_rate": [C.c_void_p, C.c_int],
     "pk_diag_conv_variants": [C.c_void_p, C.c_int, C.c_int, i32p, C.c_int, i32p],
     "pk_diag_conv_instantiations": [i32p, C.c_int],
     "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
@@ -587,6 +595,63 @@ def resample(pcm, src_rate, dst_rate):
     r = np.ctypeslib.as_array(out, shape=(max(n.value, 1),))[: n.value].copy()
     L.pk_free(out)
     return r
+
+
+def resample_length(n, src_rate, dst_rate):
+    """pk_resample_length: samples pk_resample returns for n input samples (host arithmetic)."""
+    L = lib()
+    L.pk_resample_length.restype = C.c_int64
+    r = L.pk_resample_length(int(n), int(src_rate), int(dst_rate))
+    if r < 0:                      # refused: negative n is PK_ERR_INVALID, a rate or a length out of range PK_ERR_UNSUPPORTED
+        check(-1 if int(n) < 0 and all(4000 <= int(x) <= 384000 for x in (src_rate, dst_rate)) else -7)
+    return r
+
+
+def resample_run(src_rate, dst_rate):
+    """pk_resample_run: outputs one workgroup of the resampling kernel owns at this pair of rates."""
+    return lib().pk_resample_run(int(src_rate), int(dst_rate))
+
+
+def resample_table(src_rate, dst_rate):
+    """pk_resample_table: the phase table of the device resampler -> (table [up][32] float64, up, down).  Host only."""
+    up, down = C.c_int(0), C.c_int(0)
+    check(lib().pk_resample_table(int(src_rate), int(dst_rate), None, 0, C.byref(up), C.byref(down)))
+    t = np.zeros((up.value, 32), np.float64)
+    check(lib().pk_resample_table(int(src_rate), int(dst_rate), t.ctypes.data_as(C.POINTER(C.c_double)), up.value, C.byref(up), C.byref(down)))
+    return t, up.value, down.value
+
+
+def resample_device(clips, src_rate, dst_rate, device=0, out=None, out_offsets=None):
+    """pk_resample_device: a list of input-rate clips (empty ones allowed) through the device resampler -> list of dst-rate clips.
+    out / out_offsets (n + 1 entries): write into the caller's buffer instead (everything of out[: out_offsets[-1]] outside the clips'
+    outputs comes back untouched) and return it."""
+    clips = [_c(c).reshape(-1) for c in clips]
+    off = np.zeros(len(clips) + 1, np.int64)
+    off[1:] = np.cumsum([c.size for c in clips])
+    pcm = np.concatenate(clips) if off[-1] else np.zeros(1, np.float32)
+    lens = [resample_length(c.size, src_rate, dst_rate) for c in clips]
+    own = out is None
+    if own:
+        out_offsets = np.zeros(len(clips) + 1, np.int64)
+        out_offsets[1:] = np.cumsum(lens)
+        out = np.zeros(max(int(out_offsets[-1]), 1), np.float32)
+    out_offsets = np.ascontiguousarray(out_offsets, np.int64)
+    check(lib().pk_resample_device(int(device), _f(pcm), off.ctypes.data_as(i64p), len(clips), int(src_rate), int(dst_rate), _f(out),
+                                   out_offsets.ctypes.data_as(i64p)))
+    if not own:
+        return out
+    return [out[out_offsets[i]: out_offsets[i] + lens[i]].copy() for i in range(len(clips))]
+
+
+def resample_device_timed(clips, src_rate, dst_rate, reps=20, device=0):
+    """pk_resample_device_timed: median milliseconds of the resampling launch alone (hipEvents; the input is on the device)."""
+    clips = [_c(c).reshape(-1) for c in clips]
+    off = np.zeros(len(clips) + 1, np.int64)
+    off[1:] = np.cumsum([c.size for c in clips])
+    pcm = np.concatenate(clips)
+    ms = np.zeros(1, np.float32)
+    check(lib().pk_resample_device_timed(int(device), _f(pcm), off.ctypes.data_as(i64p), len(clips), int(src_rate), int(dst_rate), int(reps), _f(ms)))
+    return float(ms[0])
 
 
 def read_audio(path, target_rate=16000):
@@ -1897,6 +1962,10 @@ class Group:
         """pk_group_set_attention_context: Model.set_attention_context on every replica."""
         check(lib().pk_group_set_attention_context(self._h, int(left), int(right)))
 
+    def set_input_rate(self, rate):
+        """pk_group_set_input_rate: Model.set_input_rate on every replica."""
+        check(lib().pk_group_set_input_rate(self._h, int(rate)))
+
     def last_stats(self):
         wall, audio = C.c_double(0), C.c_double(0)
         per = np.zeros(self.size(), np.int32)
@@ -1947,6 +2016,16 @@ class Model:
         l, r = C.c_int(0), C.c_int(0)
         check(lib().pk_model_get_attention_context(self._h, C.byref(l), C.byref(r)))
         return l.value, r.value
+
+    def set_input_rate(self, rate):
+        """pk_model_set_input_rate: the one-call entry points (transcribe_pcm, the n-best forms, align_pcm, tdt_align_pcm, tdt_score_pcm,
+        spot_pcm) take PCM at this rate and resample it to 16 kHz on the device; 16000 (default) is the plain path."""
+        check(lib().pk_model_set_input_rate(self._h, int(rate)))
+
+    def input_rate(self):
+        r = C.c_int(0)
+        check(lib().pk_model_get_input_rate(self._h, C.byref(r)))
+        return r.value
 
     def set_decode_loop(self, mode):
         """pk_model_set_decode_loop: "phases" (default) | "persistent" | "graph" -- same results, different launch structure."""

@@ -338,8 +338,10 @@ pk_status pk_batch_upload_ragged(pk_batch *b, const float *pcm, const int64_t *o
 }
 
 // stages the NEXT batch into the PCM buffer the running encoder does not read, on the copy stream.  clip(i) = host pointer of clip i;
-// clips that follow each other in host memory go as one copy.
-static void batch_stage(pk_batch *b, int n_clips, const std::function<const float *(int)> &clip, const int64_t *lens = nullptr) {
+// clips that follow each other in host memory go as one copy.  raw_lens: the clips are at the model's input rate, raw_lens[i] samples each; they are
+// uploaded to the resampler's staging buffer and the kernel writes their lens[i] 16 kHz samples where the copy would have (resample.hpp).
+static void batch_stage(pk_batch *b, int n_clips, const std::function<const float *(int)> &clip, const int64_t *lens = nullptr,
+                        const int64_t *raw_lens = nullptr) {
     b->m->require_gpu();
     const int nb = b->staged >= 0 ? b->staged : (b->cur ^ 1);      // re-staging before a run overwrites the staged batch
     std::vector<int64_t> uni;
@@ -348,7 +350,11 @@ static void batch_stage(pk_batch *b, int n_clips, const std::function<const floa
     PK_HIP(hipStreamSynchronize(b->copy_stream));                  // at most one copy in flight; the previous host buffer is released here
     if (b->mel_used[nb]) PK_HIP(hipStreamWaitEvent(b->copy_stream, b->mel_done[nb], 0));   // the last mel that read this buffer
     int64_t o = 0;
-    for (int i = 0; i < n_clips;) {
+    if (raw_lens) {
+        std::vector<int64_t> out_off(n_clips);
+        for (int i = 0; i < n_clips; ++i) { out_off[i] = o; o += lens[i]; }
+        resample_stage(b->m->rs, b->m->input_rate, kModelRate, n_clips, clip, raw_lens, out_off.data(), b->pcm2[nb].as<float>(), b->copy_stream);
+    } else for (int i = 0; i < n_clips;) {
         int j = i + 1;
         int64_t run = lens[i];
         while (j < n_clips && clip(j) == clip(j - 1) + lens[j - 1]) { run += lens[j]; ++j; }
@@ -704,12 +710,20 @@ void pk::transcribe_clips(Model &m, const float *pcm, const int64_t *offsets, co
     // one lock-step group -- runs under encoder(k+1).  A batch whose clips all have the same length runs the plain uniform kernels.
     const int n_clips = (int)clips.size();
     if (n_clips == 0) return;
+    // At another input rate than 16 kHz (Model::input_rate) pcm / offsets count input-rate samples: the batches are planned by the RESAMPLED
+    // lengths and every batch is resampled on the device while it is staged (batch_stage); everything behind that sees 16 kHz samples.
+    const bool resampled = m.input_rate != kModelRate;
     std::vector<int64_t> clip_len(n_clips);
-    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[clips[i] + 1] - offsets[clips[i]];
+    for (int i = 0; i < n_clips; ++i) {
+        const int64_t raw = offsets[clips[i] + 1] - offsets[clips[i]];
+        clip_len[i] = resampled ? resample_length(raw, m.input_rate, kModelRate) : raw;
+    }
     std::vector<int> order, bstart;                                // order: positions in `clips`, longest first; bstart: first position of every batch, + the end
     plan_batches(clip_len.data(), n_clips, order, bstart);
+    std::vector<int64_t> len16(n_clips);                           // 16 kHz samples of the clip at position i of `order`
+    for (int i = 0; i < n_clips; ++i) len16[i] = clip_len[order[i]];
     for (auto &o : order) o = clips[o];                            // ... as global clip indices from here on
-    auto len_of = [&](int i) { return offsets[order[i] + 1] - offsets[order[i]]; };
+    auto len_of = [&](int i) { return len16[i]; };
     const int nb_all = (int)bstart.size() - 1;
     // The output arrays of a pipeline are pitched (clips x longest clip x max_symbols).  With the clips sorted longest first, one very long
     // file in front of many short ones would make every batch of the call carry its pitch (a 1 h file and 256 short clips: ~0.5 GB per array,
@@ -741,13 +755,17 @@ void pk::transcribe_clips(Model &m, const float *pcm, const int64_t *offsets, co
         const int64_t first_seq = b->runs;
         const int mt = b->ws[0].max_tokens;
         std::vector<char> taken(nb, 0);
-        std::vector<int64_t> blens;
+        std::vector<int64_t> blens, braw;
         const int *bs = bstart.data() + seg0;                      // (the lambdas below index the segment's batches 0 .. nb-1)
         auto stage = [&](int k) {
             const int c0 = bs[k], nc = bs[k + 1] - c0;
             blens.resize(nc);
             for (int i = 0; i < nc; ++i) blens[i] = len_of(c0 + i);
-            batch_stage(b, nc, [&](int i) { return pcm + offsets[order[c0 + i]]; }, blens.data());
+            if (resampled) {
+                braw.resize(nc);
+                for (int i = 0; i < nc; ++i) braw[i] = offsets[order[c0 + i] + 1] - offsets[order[c0 + i]];
+            }
+            batch_stage(b, nc, [&](int i) { return pcm + offsets[order[c0 + i]]; }, blens.data(), resampled ? braw.data() : nullptr);
         };
         auto drain = [&]() {                                  // every finished run of this call that has not been handed out yet
             for (const auto &L : b->done) {
@@ -872,8 +890,12 @@ namespace {
 //   body(clip, nc, r)   the head on the encoded rows; results go to the caller's slots clip[i].
 template <class Prepare, class Sized, class Body>
 void for_each_batch(Model &m, const float *pcm, const int64_t *offsets, int n_clips, bool ctc, Prepare prepare, Sized sized, Body body) {
-    std::vector<int64_t> clip_len(n_clips), blens;
-    for (int i = 0; i < n_clips; ++i) clip_len[i] = offsets[i + 1] - offsets[i];
+    const bool resampled = m.input_rate != kModelRate;            // input-rate PCM: planned by the resampled lengths, as in transcribe_clips
+    std::vector<int64_t> clip_len(n_clips), blens, braw;
+    for (int i = 0; i < n_clips; ++i) {
+        const int64_t raw = offsets[i + 1] - offsets[i];
+        clip_len[i] = resampled ? resample_length(raw, m.input_rate, kModelRate) : raw;
+    }
     std::vector<int> order, bstart;
     plan_batches(clip_len.data(), n_clips, order, bstart);
     for (size_t k = 0; k + 1 < bstart.size(); ++k) {
@@ -888,7 +910,12 @@ void for_each_batch(Model &m, const float *pcm, const int64_t *offsets, int n_cl
         sized(r, nc);
         m.ws.size_ragged(m.cfg, nc, r.n_samples, longest, /*own_pcm=*/true);
         m.ws.set_ragged(r, m.stream);
-        for (int i = 0; i < nc; ++i)
+        if (resampled) {
+            braw.resize(nc);
+            for (int i = 0; i < nc; ++i) braw[i] = offsets[clip[i] + 1] - offsets[clip[i]];
+            resample_stage(m.rs, m.input_rate, kModelRate, nc, [&](int i) { return pcm + offsets[clip[i]]; }, braw.data(), r.pcm_off.data(), m.ws.pcm.as<float>(),
+                           m.stream);
+        } else for (int i = 0; i < nc; ++i)
             PK_HIP(hipMemcpyAsync(m.ws.pcm.as<float>() + r.pcm_off[i], pcm + offsets[clip[i]], (size_t)blens[i] * 4, hipMemcpyHostToDevice, m.stream));
         m.run_mel_ws(m.ws, m.ws.pcm.as<float>(), nc, m.stream);
         m.run_encoder(m.ws, m.ws.feats.as<float>(), nc, 0, -1, 0, m.stream);

@@ -88,6 +88,13 @@ pk_status pk_group_set_attention_context(pk_group *g, int left, int right) {
         for (auto &m : g->models) m->set_attention_context(left, right);
     });
 }
+pk_status pk_group_set_input_rate(pk_group *g, int rate) {
+    return guard([&] {
+        need(g && !g->models.empty(), "group");
+        g->models[0]->set_input_rate(rate);                             // (validated once)
+        for (auto &m : g->models) m->set_input_rate(rate);
+    });
+}
 int pk_group_size(const pk_group *g) { return g ? (int)g->devices.size() : 0; }
 
 pk_status pk_group_transcribe_pcm(pk_group *g, const float *pcm, const int64_t *offsets, int n_clips, const pk_options *opt, pk_result **results) {
@@ -107,7 +114,7 @@ pk_status pk_group_transcribe_pcm(pk_group *g, const float *pcm, const int64_t *
             const int r = (int)(std::min_element(load.begin(), load.end()) - load.begin());
             shard[r].push_back(order[i]);
             load[r] += len;
-            audio += (double)len / 16000.0;
+            audio += (double)len / (double)g->models[0]->input_rate;
         }
         auto store = new_store(n_clips);
         ResultStore &R = *store;

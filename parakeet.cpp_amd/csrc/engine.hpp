@@ -16,6 +16,7 @@
 #include "ctc_beam.hpp"
 #include "ctc_kws.hpp"
 #include "kernels/kernels.hpp"
+#include "resample.hpp"
 #include "safetensors.hpp"
 #include "tdt_align.hpp"
 #include "tdt_beam.hpp"
@@ -197,6 +198,11 @@ class Model {
         DevBuf proj;                        // pos_proj_ of every layer [L][left + right + 1][d], sigma columns
     } pos_local;
     void ensure_local_pos_table(hipStream_t s);
+    // Sample rate of the PCM the one-call entry points take (pk_model_set_input_rate): at another rate than kModelRate every batch is uploaded raw and
+    // resampled on the device (resample.hpp) to where the 16 kHz copy went before.  rs is also the scratch of that stage.
+    int input_rate = kModelRate;
+    void set_input_rate(int rate) { resample_check_rates(rate, kModelRate); input_rate = rate; }
+    ResampleWs rs;
 
     // stage drivers (device pointers, enqueue on `s`, never synchronise)
     void run_mel(const float *d_pcm, int B, int64_t n_samples, float *d_logmel, float *d_feats, hipStream_t s, const RagDev *rv = nullptr);

@@ -755,4 +755,23 @@ void launch_math(int fn, const float *in, float *out, int64_t n, hipStream_t s);
 void launch_math_exhaustive(int fn, unsigned long long *out3, hipStream_t s);   // out3 must hold {0, 0, 1 << 32} on entry
 void launch_scale(float *x, int64_t n, float a, hipStream_t s);
 
+// ---- polyphase sinc resampler of input-rate PCM (kernels/resample.hip) --------------------------------------
+// One launch over a packed ragged batch.  A workgroup of kResampleThreads lanes owns `run` consecutive outputs of one clip and stages the input
+// span they read (at most span_cap floats) into LDS; output i = q * up + r of a clip reads the 32 taps around c = q * down + coff[r] with the
+// fp64 weights of table row r.  Tables of at most kResampleLdsRows rows are staged into LDS too, larger ones are read from global memory.
+constexpr int kResampleThreads = 256;
+constexpr int kResampleTaps = 32;
+constexpr int kResampleMaxRun = 1024;           // outputs per workgroup, lowered (in steps of 32) until the span fits kResampleSpanCap
+constexpr int kResampleSpanCap = 5632;          // floats of input staged per workgroup (22 KB)
+constexpr int kResampleLdsRows = 160;           // 160 rows x 33 doubles (padded) = 41.25 KB: with the span 63.9 KB, two workgroups per CU
+struct ResampleClip { int64_t in_off, in_len, out_off, out_len, wg0; };   // extents in samples; wg0: the clip's first workgroup
+struct ResampleArgs {
+    const float *x; float *y;
+    const ResampleClip *clip; int n_clips;      // clips with out_len == 0 own no workgroup
+    const double *tab; const int *coff;         // [up][32] weights, [up] centre offsets (r * down) / up
+    int up, down, run, span_cap;
+    int64_t n_wg;                               // workgroups of the launch: sum of ceil(out_len / run)
+};
+void launch_resample(const ResampleArgs &a, hipStream_t s);
+
 }  // namespace pk

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "resample.hpp"
 
 namespace pk {
 
@@ -106,31 +107,45 @@ static double kaiser_window(double n, double N, double beta) {
 }
 static int gcd_int(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
 
+// The filter of one (src, dst) pair and the weight of a tap at distance `dist` (in input samples) from the output's position: what
+// sinc_resample evaluates per tap and what the phase table of the device resampler (resample.cpp) is built from, in the same expressions.
+constexpr int HALF_WIDTH = 16;
+constexpr double BETA = 7.857;
+SincFilter sinc_filter(int src_rate, int dst_rate) {
+    SincFilter f;
+    const double ratio = (double)src_rate / dst_rate;
+    f.cutoff = std::min(1.0, 1.0 / std::max(ratio, 1.0));
+    f.filter_scale = f.cutoff;
+    f.sample_ratio = (double)dst_rate / src_rate;
+    f.width_factor = std::max(1.0, ratio);
+    return f;
+}
+// false: the tap lies outside the window and is skipped
+static inline bool sinc_tap(const SincFilter &f, double dist, double &weight) {
+    const double window_pos = dist / f.width_factor;
+    if (std::abs(window_pos) > HALF_WIDTH) return false;
+    const double w = kaiser_window(window_pos + HALF_WIDTH, 2.0 * HALF_WIDTH, BETA);
+    const double x = dist * f.cutoff * M_PI;
+    const double sinc_val = std::abs(x) < 1e-10 ? 1.0 : std::sin(x) / x;
+    weight = sinc_val * w * f.filter_scale;
+    return true;
+}
+bool sinc_tap_weight(const SincFilter &f, double dist, double *weight) { return sinc_tap(f, dist, *weight); }
+
 void sinc_resample(const float *input, size_t input_len, int src_rate, int dst_rate, std::vector<float> &output) {
     if (src_rate == dst_rate) { output.assign(input, input + input_len); return; }
     const int g = gcd_int(src_rate, dst_rate), up = dst_rate / g, down = src_rate / g;
     const size_t output_len = (size_t)(((int64_t)input_len * up + down - 1) / down);
     output.resize(output_len);
-    constexpr int HALF_WIDTH = 16;
-    constexpr double BETA = 7.857;
-    const double ratio = (double)src_rate / dst_rate;
-    const double cutoff = std::min(1.0, 1.0 / std::max(ratio, 1.0));
-    const double filter_scale = cutoff;
-    const double sample_ratio = (double)dst_rate / src_rate;
-    const double width_factor = std::max(1.0, ratio);
+    const SincFilter f = sinc_filter(src_rate, dst_rate);
     for (size_t i = 0; i < output_len; ++i) {
-        const double src_pos = (double)i / sample_ratio;
+        const double src_pos = (double)i / f.sample_ratio;
         const int center = (int)std::floor(src_pos);
         double sum = 0.0, weight_sum = 0.0;
         for (int j = center - HALF_WIDTH + 1; j <= center + HALF_WIDTH; ++j) {
             if (j < 0 || j >= (int)input_len) continue;
-            const double dist = src_pos - j;
-            const double window_pos = dist / width_factor;
-            if (std::abs(window_pos) > HALF_WIDTH) continue;
-            const double w = kaiser_window(window_pos + HALF_WIDTH, 2.0 * HALF_WIDTH, BETA);
-            const double x = dist * cutoff * M_PI;
-            const double sinc_val = std::abs(x) < 1e-10 ? 1.0 : std::sin(x) / x;
-            const double weight = sinc_val * w * filter_scale;
+            double weight;
+            if (!sinc_tap(f, src_pos - j, weight)) continue;
             sum += input[j] * weight;
             weight_sum += weight;
         }

@@ -4,6 +4,9 @@
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K] [--beam-head ctc|tdt]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
 //                [--spot "phrase"]... [--spot-file path.txt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
+//                [--device-resample]
+// New: --device-resample (tdt-ctc-110m, tdt-600m) reads the file at its own sample rate and resamples it to 16 kHz on the device, inside the call
+// (Transcriber::set_device_resampling), instead of on the host while the file is read.
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
 // New: --align "text" / --align-file path.txt (tdt-ctc-110m, tdt-600m) aligns the given transcript with the audio (CTC forced alignment) and
 // prints its word timestamps in the format of --timestamps.  --align-head tdt aligns through the TDT head instead (the default stays ctc): the one
@@ -46,6 +49,7 @@ static void usage(const char *prog) {
               << "  --beam W --lm file.arpa [--lm-alpha A] [--lm-beta B]  the CTC beam search fused with an n-gram model over token ids\n"
               << "  --beam W --beam-head tdt --lm file.arpa [--lm-alpha A] [--lm-beta B]  the TDT beam search fused with the model; both scores per hypothesis\n"
               << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold)\n"
+              << "  --device-resample  resample files that are not 16 kHz on the device instead of on the host (tdt-ctc-110m, tdt-600m)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
 }
@@ -131,7 +135,7 @@ int main(int argc, char **argv) {
         const std::string weights = argv[1], audio_path = argv[2];
         std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text, score_text, lm_path;
         LmOptions lm_opts;
-        bool use_ctc = false, timestamps = false, align = false, align_tdt = false, beam_tdt = false, score = false, rescore = false, nbest_given = false;
+        bool use_ctc = false, timestamps = false, device_resample = false, align = false, align_tdt = false, beam_tdt = false, score = false, rescore = false, nbest_given = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
         float rescore_w = 0.5f;
         std::vector<std::string> boost, spot;
@@ -184,6 +188,7 @@ int main(int argc, char **argv) {
             else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
             else if (a == "--lm-alpha" && i + 1 < argc) lm_opts.alpha = std::stof(argv[++i]);
             else if (a == "--lm-beta" && i + 1 < argc) lm_opts.beta = std::stof(argv[++i]);
+            else if (a == "--device-resample") device_resample = true;
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
             else if (a == "--latency" && i + 1 < argc) latency = std::stoi(argv[++i]);
@@ -240,6 +245,7 @@ int main(int argc, char **argv) {
         if (model == "tdt-ctc-110m") {
             Transcriber t(weights, vocab);
             t.to_gpu();
+            t.set_device_resampling(device_resample);
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);
             if (!spot.empty()) return run_spot(t, audio_path, spot, spot_opts);
@@ -303,6 +309,7 @@ int main(int argc, char **argv) {
         } else if (model == "tdt-600m") {
             TDTTranscriber t(weights, vocab);
             t.to_gpu();
+            t.set_device_resampling(device_resample);
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);
             if (beam > 0) {

@@ -197,6 +197,10 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         att_left_ = left;
         att_right_ = right;
     }
+    // New: files at another rate than 16 kHz are read at their own rate and resampled on the device on their way into the call
+    // (pk_model_set_input_rate for the duration of the call) instead of by pk_read_audio's host resampler.  Off by default: for rates that
+    // neither divide nor are divided by 16 kHz the device's samples differ from the host's by one fp32 rounding now and then.
+    void set_device_resampling(bool on) { device_resample_ = on; }
     int num_gpus() const { return g_ ? pk_group_size(g_) : (on_gpu_ ? 1 : 0); }
 
     std::vector<TranscribeResult> run(const std::vector<std::pair<const float *, size_t>> &clips, const TranscribeOptions &opts) {
@@ -364,14 +368,25 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     pk_model *handle() { return m_; }
 
   private:
-    // read_audio(path): decode, downmix, resample to 16 kHz; the samples go to fn(pcm, n) and are freed when it returns or throws
+    // read_audio(path): decode, downmix, resample to 16 kHz; the samples go to fn(pcm, n) and are freed when it returns or throws.
+    // With set_device_resampling(true) the file keeps its own rate and the model takes that rate while fn runs.
     template <class Fn>
-    static auto with_audio(const std::string &audio_path, Fn fn) -> decltype(fn((const float *)nullptr, size_t())) {
+    auto with_audio(const std::string &audio_path, Fn fn) -> decltype(fn((const float *)nullptr, size_t())) {
         float *pcm = nullptr;
-        int64_t n = 0;
-        int sr = 0;
-        check(pk_read_audio(audio_path.c_str(), 16000, &pcm, &n, &sr));
+        int64_t n = 0, frames = 0;
+        int sr = 0, rate = 16000, channels = 0;
+        if (device_resample_) check(pk_audio_info(audio_path.c_str(), &rate, &channels, &frames));
+        check(pk_read_audio(audio_path.c_str(), rate, &pcm, &n, &sr));
         struct Free { float *p; ~Free() { pk_free(p); } } guard{pcm};
+        struct Rate {
+            Engine *e; bool set;
+            ~Rate() { if (set) { (void)pk_model_set_input_rate(e->m_, 16000); if (e->g_) (void)pk_group_set_input_rate(e->g_, 16000); } }
+        } restore{this, rate != 16000};
+        if (rate != 16000) {
+            if (!g_ && !on_gpu_) to_gpu(0);
+            check(pk_model_set_input_rate(m_, rate));
+            if (g_) check(pk_group_set_input_rate(g_, rate));
+        }
         return fn(pcm, (size_t)n);
     }
     // text and token ids of a pk_result and, with timestamps, its timestamped tokens and words
@@ -412,6 +427,7 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     pk_config cfg_;
     pk_model *m_ = nullptr;
     int att_left_ = -1, att_right_ = -1;
+    bool device_resample_ = false;
     pk_group *g_ = nullptr;
     Tokenizer tok_;
     bool on_gpu_ = false;
@@ -435,6 +451,8 @@ class Transcriber {
     int num_gpus() const { return eng_.num_gpus(); }
     /// New: limited-context attention for long audio (Engine::set_attention_context); (-1, -1) restores full attention.
     void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
+    /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
+    void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
     TranscribeResult transcribe(const std::string &audio_path, Decoder decoder = Decoder::TDT, bool timestamps = false) {
         return eng_.run_file(audio_path, options(decoder, timestamps));
@@ -547,6 +565,8 @@ class TDTTranscriber {
     int num_gpus() const { return eng_.num_gpus(); }
     /// New: limited-context attention for long audio (Engine::set_attention_context); (-1, -1) restores full attention.
     void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
+    /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
+    void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
     TranscribeResult transcribe(const std::string &audio_path, bool timestamps = false) { return eng_.run_file(audio_path, options(timestamps)); }
     TranscribeResult transcribe(const std::string &audio_path, const TranscribeOptions &opts) { return eng_.run_file(audio_path, tdt(opts)); }
