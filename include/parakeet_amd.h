@@ -983,6 +983,27 @@ pk_status pk_diag_stream_attention(int S, int c, int nc, int cache_rows, int d, 
                                    const float *vcache, const float *pos, int P, const float *bias_u, const float *bias_v, int att_left,
                                    int att_right, int keep_max, int ctx_sigma, int rotate, float *ctx, float *cache_k_out, float *cache_v_out,
                                    int *form);
+/* The mel front end alone (kernels/mel.hip; reference src/audio.cpp:100-158 and :222-252), without a model: the tables come from the builder the
+ * models and pk_frontend use, for n_mels bins (1 .. 512: this entry's own limit, what one frame's LDS array holds), the window placed per stft_window_centered (switch A1), the power per power_via_abs (A2).
+ *   form PK_DIAG_MEL_UNIFORM  n_clips clips of n_samples each, pcm [n_clips][n_samples]; offsets NULL.  launch_mel_logmel, then launch_mel_normalize
+ *                             with the normalize flag: logmel = [clip][n_mels][pitch], pitch = frames rounded up to 16; feats = [clip][frames][n_mels].
+ *   form PK_DIAG_MEL_RAGGED   clip i = pcm[offsets[i] .. offsets[i + 1]) (n_samples ignored), the ragged launch of the same two: the clips' log-mel
+ *                             blocks [n_mels][pitch of clip i] one behind the other, feats packed along the frames.
+ *   form PK_DIAG_MEL_STREAM   launch_mel_stream on pcm [n_clips][n_samples] as given: an ALREADY pre-emphasised signal, frame t = samples
+ *                             [160 t, 160 t + 400); logmel = [clip][frames][n_mels], no normalise step (feats stays untouched).
+ * logmel / feats receive logmel_words / feats_words floats each: the device buffer of that many words is filled with PK_DIAG_MEL_FILL before the
+ * launch and copied back whole, so a word no launch wrote (pad columns, spare words) comes back as the fill.  Each must hold what the launches write
+ * plus at least PK_DIAG_MEL_SPARE_WORDS.  n_frames [n_clips]: the frame count of every clip; grid [6]: the log-mel launch's grid x, y and threads per
+ * workgroup, then the normalise launch's (0 0 0 for the streaming form).
+ * PK_ERR_INVALID, before anything is allocated or launched: a clip of 256 samples or fewer (offline), fewer than 400 samples (streaming), n_mels < 1;
+ * PK_ERR_UNSUPPORTED: a filterbank of more packed taps than the kernel stages (no n_mels gives one today: at most 514 taps against 768). */
+#define PK_DIAG_MEL_UNIFORM 0
+#define PK_DIAG_MEL_RAGGED 1
+#define PK_DIAG_MEL_STREAM 2
+#define PK_DIAG_MEL_FILL 0x7FC5A5A5u
+#define PK_DIAG_MEL_SPARE_WORDS 64
+pk_status pk_diag_mel(int n_mels, int normalize, int stft_window_centered, int power_via_abs, int form, const float *pcm, int n_clips, int64_t n_samples,
+                      const int64_t *offsets, float *logmel, int64_t logmel_words, float *feats, int64_t feats_words, int32_t *n_frames, int32_t *grid);
 /* Which instantiation of the convolution kernels outside the GEMM the engine launches for this model and batch, computed by the functions the
  * launchers themselves switch on (kernels/kernels.hpp: sub_conv1_dw1_inst, sub_dw_inst, dwconv_inst, stream_dwconv_inst).  Host arithmetic only: no
  * device is needed.  The batch is B utterances of Tm mel frames each (n_mel_frames = NULL), or a ragged batch of B utterances of n_mel_frames[b]

@@ -272,6 +272,7 @@ _LATE_SIGNATURES = {
     "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
                                        C.POINTER(C.c_int)],
     "pk_diag_stream_attention": [C.c_int] * 6 + [f32p] * 4 + [C.c_int, f32p, f32p] + [C.c_int] * 5 + [f32p] * 3 + [C.POINTER(C.c_int)],
+    "pk_diag_mel": [C.c_int] * 5 + [f32p, C.c_int, C.c_int64, i64p, f32p, C.c_int64, f32p, C.c_int64, i32p, i32p],
 }
 
 
@@ -1304,6 +1305,47 @@ def diag_stream_attention(qkv_new, kcache, vcache, nc, pos, bias_u, bias_v, n_he
                                          int(left), int(right), int(keep_max), int(bool(ctx_sigma)), int(bool(rotate)), _f(ctx), _f(ko), _f(vo),
                                          C.byref(form)))
     return ctx, ko, vo, STREAM_ATT_FORMS[form.value]
+
+
+MEL_FORMS = ("uniform", "ragged", "stream")     # PK_DIAG_MEL_UNIFORM / _RAGGED / _STREAM
+MEL_FILL = 0x7FC5A5A5                           # PK_DIAG_MEL_FILL: what a word no launch wrote comes back as
+MEL_SPARE_WORDS = 64                            # PK_DIAG_MEL_SPARE_WORDS
+
+
+def mel_logmel_pitch(n_frames):
+    """frames per row of a clip's log-mel block on the device (kernels.hpp mel_logmel_pitch)"""
+    return (n_frames + 15) & ~15
+
+
+def diag_mel(pcm, form="uniform", n_mels=80, normalize=True, window_centered=False, power_via_abs=True, spare=MEL_SPARE_WORDS, logmel=None, feats=None):
+    """pk_diag_mel: the mel front end alone, no model.  form "uniform": pcm [B][n] -> log-mel blocks [B][n_mels][pitch], features [B][frames][n_mels];
+    "ragged": pcm a list of clips -> blocks [n_mels][pitch of the clip] one behind the other, features packed along the frames; "stream": pcm [B][n]
+    ALREADY pre-emphasised -> log-mel [B][frames][n_mels], no features.  -> (logmel, feats, n_frames [B], grid): both buffers WHOLE and flat, what the
+    launches write plus `spare` words, every word no launch wrote holding MEL_FILL; grid = ((x, y, threads) of the log-mel launch, of the normalise
+    launch).  logmel / feats: buffers of the caller's to receive them (a refused call leaves them as they were)."""
+    f = MEL_FORMS.index(form)
+    if form == "ragged":
+        clips = [_c(c).reshape(-1) for c in pcm]
+        B, n = len(clips), 0
+        off = np.zeros(B + 1, np.int64)
+        off[1:] = np.cumsum([c.size for c in clips])
+        x = np.concatenate(clips) if B else np.zeros(0, np.float32)
+        lens = [c.size for c in clips]
+    else:
+        x = _c(pcm)
+        x = x[None] if x.ndim == 1 else x
+        B, n = x.shape
+        off, lens = None, [n] * B
+    nf = [max(0, (m - 400) // 160 + 1) if form == "stream" else 1 + m // 160 for m in lens]
+    n_lm = sum(nf) * n_mels if form == "stream" else sum(mel_logmel_pitch(t) for t in nf) * n_mels
+    n_ft = 0 if form == "stream" else sum(nf) * n_mels
+    logmel = np.empty(n_lm + spare, np.float32) if logmel is None else logmel
+    feats = np.empty(n_ft + spare, np.float32) if feats is None else feats
+    assert logmel.dtype == feats.dtype == np.float32 and logmel.flags.c_contiguous and feats.flags.c_contiguous
+    frames, grid = np.zeros(max(B, 1), np.int32), np.zeros(6, np.int32)
+    check(lib().pk_diag_mel(int(n_mels), int(bool(normalize)), int(bool(window_centered)), int(bool(power_via_abs)), f, _f(x), B, n,
+                            off.ctypes.data_as(i64p) if off is not None else None, _f(logmel), logmel.size, _f(feats), feats.size, _i(frames), _i(grid)))
+    return logmel, feats, frames[:B], (tuple(int(v) for v in grid[:3]), tuple(int(v) for v in grid[3:]))
 
 
 class PkSmallmGemmDiag(C.Structure):

@@ -1336,6 +1336,78 @@ pk_status pk_diag_stream_attention(int S, int c, int nc, int cache_rows, int d, 
     });
 }
 
+// The mel front end alone (kernels/mel.hip), launched as Model::run_mel / run_mel_ws, MelFrontend::features and StreamBatch::mel launch it: the tables
+// from the builder they share, a ragged batch described by the engine's RagBatch.  Both device buffers are filled before the launch and come back whole.
+pk_status pk_diag_mel(int n_mels, int normalize, int stft_window_centered, int power_via_abs, int form, const float *pcm, int n_clips, int64_t n_samples,
+                      const int64_t *offsets, float *logmel, int64_t logmel_words, float *feats, int64_t feats_words, int32_t *n_frames, int32_t *grid) {
+    return guard([&] {
+        need(form >= PK_DIAG_MEL_UNIFORM && form <= PK_DIAG_MEL_STREAM, "form");
+        need(pcm && logmel && feats && n_frames && grid && n_clips > 0, "pcm/logmel/feats/n_frames/grid/n_clips");
+        // (n_mels <= 512 is this entry's own limit: the offline kernel parks a frame's n_mels values in the head of its 576-word LDS array.  The engine's
+        //  entry points take 80 / 128 bins, pk_frontend up to 128.)
+        need(n_mels >= 1 && n_mels <= 512, "n_mels (1 .. 512)");
+        const bool ragged = form == PK_DIAG_MEL_RAGGED, stream = form == PK_DIAG_MEL_STREAM;
+        need(ragged == (offsets != nullptr), "offsets: with the ragged form, and only there");
+        std::vector<int64_t> lens(n_clips);
+        std::vector<int32_t> nf(n_clips);
+        int64_t total = 0, sum_nf = 0, sum_pitch = 0;
+        for (int b = 0; b < n_clips; ++b) {
+            lens[b] = ragged ? offsets[b + 1] - offsets[b] : n_samples;
+            if (stream) need(lens[b] >= 400, "streaming: at least 400 samples (one window)");
+            else need(lens[b] > 256, "every clip needs more than 256 samples (n_fft / 2: reflect padding)");
+            need(lens[b] <= ((int64_t)1 << 24), "at most 2^24 samples per clip");
+            nf[b] = stream ? (int32_t)((lens[b] - 400) / 160 + 1) : (int32_t)(1 + lens[b] / 160);
+            total += lens[b]; sum_nf += nf[b]; sum_pitch += mel_logmel_pitch(nf[b]);
+        }
+        // refuses a filterbank over kMelMaxTaps here, where nothing is allocated yet.  (No n_mels reaches that today: every FFT bin lies under at most two
+        //  triangles, 514 packed taps at the most against 768.  The check guards the builder against a change of the filterbank, not an input.)
+        const MelTablesHost th = make_mel_tables_host(n_mels, stft_window_centered != 0);
+        // what the launches write: offline [clip][n_mels][pitch] then [frames of the batch][n_mels]; streaming [clip][frames][n_mels] and no features
+        const int64_t n_lm = stream ? sum_nf * n_mels : sum_pitch * n_mels, n_ft = stream ? 0 : sum_nf * n_mels;
+        need(logmel_words >= n_lm + PK_DIAG_MEL_SPARE_WORDS && feats_words >= n_ft + PK_DIAG_MEL_SPARE_WORDS, "logmel_words / feats_words: the device buffer and 64 spare words");
+        need_device();
+        std::vector<std::unique_ptr<DevBuf>> owned;
+        MelTables tb = upload_mel_tables(th, [&](const float *h, size_t cnt) {
+            owned.push_back(std::make_unique<DevBuf>());
+            up(*owned.back(), h, (cnt ? cnt : 1) * 4);
+            return owned.back()->as<float>();
+        });
+        tb.power_via_abs = power_via_abs ? 1 : 0;
+        DevBuf x, lm, ft, img;
+        x.reserve((size_t)total * 4);
+        int64_t at = 0;
+        for (int b = 0; b < n_clips; at += lens[b], ++b)            // (the clips of a ragged batch need not be contiguous in the caller's buffer)
+            PK_HIP(hipMemcpy(x.as<float>() + at, pcm + (ragged ? offsets[b] : (int64_t)b * n_samples), (size_t)lens[b] * 4, hipMemcpyHostToDevice));
+        lm.reserve((size_t)logmel_words * 4);
+        ft.reserve((size_t)feats_words * 4);
+        PK_HIP(hipMemsetD32(lm.p, PK_DIAG_MEL_FILL, (size_t)logmel_words));
+        PK_HIP(hipMemsetD32(ft.p, PK_DIAG_MEL_FILL, (size_t)feats_words));
+        MelRag rag;
+        RagBatch r;
+        if (ragged) {                                               // the views Workspace::set_ragged forms
+            r.build_from_samples(lens.data(), n_clips, 32);
+            up(img, r.image.data(), r.image.size() * 4);
+            const int32_t *dv = img.as<int32_t>();
+            rag.pcm_off = reinterpret_cast<const int64_t *>(dv + r.o_pcm_off); rag.Tm = dv + r.o_Tm; rag.Tm_off = dv + r.o_Tm_off; rag.max_frames = r.Tm_max;
+            rag.Tm_pad_off = dv + r.o_Tm_pad_off;
+        }
+        MelGrid g1{0, 0, 0}, g2{0, 0, 0};
+        if (stream) {
+            g1 = launch_mel_stream(x.as<float>(), n_clips, n_samples, nf[0], tb, lm.as<float>(), nullptr);
+        } else {
+            g1 = launch_mel_logmel(x.as<float>(), n_clips, ragged ? 0 : n_samples, ragged ? 0 : nf[0], tb, lm.as<float>(), nullptr, rag);
+            g2 = launch_mel_normalize(lm.as<float>(), n_clips, n_mels, ragged ? 0 : nf[0], normalize ? 1 : 0, ft.as<float>(), nullptr, rag);
+        }
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        down(logmel, lm, (size_t)logmel_words * 4);
+        down(feats, ft, (size_t)feats_words * 4);
+        memcpy(n_frames, nf.data(), (size_t)n_clips * 4);
+        const int32_t gw[6] = {g1.x, g1.y, g1.threads, g2.x, g2.y, g2.threads};
+        memcpy(grid, gw, sizeof gw);
+    });
+}
+
 pk_status pk_diag_mem_info(pk_model *h, uint64_t out[3]) {
     return guard([&] {
         need(out != nullptr, "out");

@@ -131,10 +131,10 @@ const float *Model::upload_tensor(const std::string &name, std::vector<int64_t> 
 
 // Slaney filterbank, fp64 build / fp32 store -- reference src/audio.cpp:24-94 (hz_to_mel_slaney, mel_to_hz_slaney,
 // build_mel_filterbank); Hann window (periodic=false) :117; FFT twiddles per the FFT-512 specification in DESIGN.md.
-// Filterbank (src/audio.cpp:40-94), Hann window, FFT twiddles and the packed filter bands of the mel kernels; `upload` puts a host
-// array on the device and keeps ownership.  Shared by Model and the weight-free MelFrontend (preprocess_audio on its own).
-MelTables make_mel_tables(int n_mels, bool window_centered, const std::function<const float *(const float *, size_t)> &upload) {
-    MelTables mel{};
+// Filterbank (src/audio.cpp:40-94), Hann window, FFT twiddles and the packed filter bands of the mel kernels, on the host: what a filterbank the
+// kernel cannot stage is refused here, before anything is on a device.
+MelTablesHost make_mel_tables_host(int n_mels, bool window_centered) {
+    MelTablesHost t;
     const int n_fft = 512, win = 400, n_freqs = 257;
     const double sr = 16000.0, f_min = 0.0, f_max = sr / 2.0;
     auto hz2mel = [](double f) { return f < 1000.0 ? f / (200.0 / 3.0) : 15.0 + std::log(f / 1000.0) / 0.06875177742094912; };
@@ -142,8 +142,8 @@ MelTables make_mel_tables(int n_mels, bool window_centered, const std::function<
     std::vector<double> hz(n_mels + 2);
     const double m0 = hz2mel(f_min), m1 = hz2mel(f_max);
     for (int i = 0; i < n_mels + 2; ++i) hz[i] = mel2hz(m0 + (double)i * (m1 - m0) / (double)(n_mels + 1));
-    std::vector<float> fb((size_t)n_freqs * n_mels, 0.0f);
-    std::vector<int> lo(n_mels, 1), hi(n_mels, 0);
+    t.fb.assign((size_t)n_freqs * n_mels, 0.0f);
+    t.lo.assign(n_mels, 1); t.hi.assign(n_mels, 0);
     for (int m = 0; m < n_mels; ++m) {
         const double left = hz[m], center = hz[m + 1], right = hz[m + 2];
         const double enorm = 2.0 / (right - left);
@@ -154,46 +154,56 @@ MelTables make_mel_tables(int n_mels, bool window_centered, const std::function<
             if (freq >= left && freq <= center && center > left) v = (freq - left) / (center - left);
             else if (freq > center && freq <= right && right > center) v = (right - freq) / (right - center);
             const float w = (float)(v * enorm);
-            fb[(size_t)f * n_mels + m] = w;
-            if (w != 0.0f) { if (!any) lo[m] = f; hi[m] = f; any = true; }
+            t.fb[(size_t)f * n_mels + m] = w;
+            if (w != 0.0f) { if (!any) t.lo[m] = f; t.hi[m] = f; any = true; }
         }
     }
-    std::vector<float> window(n_fft, 0.0f), twr(n_fft / 2), twi(n_fft / 2);
+    t.window.assign(n_fft, 0.0f); t.window_left.assign(n_fft, 0.0f); t.twr.resize(n_fft / 2); t.twi.resize(n_fft / 2);
     // switch A1 (pk_config.stft_window_centered): left-aligned like the reference author's feature check, or centred (torch.stft)
     const int off = window_centered ? (n_fft - win) / 2 : 0;
-    for (int k = 0; k < win; ++k) window[off + k] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)(win - 1)));
+    for (int k = 0; k < win; ++k) t.window[off + k] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)(win - 1)));
+    // the streaming preprocessor's frames are win_length samples, zero-padded on the right (src/audio.cpp:222-241)
+    for (int k = 0; k < win; ++k) t.window_left[k] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)(win - 1)));
     for (int k = 0; k < n_fft / 2; ++k) {
         const double a = 2.0 * M_PI * (double)k / (double)n_fft;
-        twr[k] = (float)std::cos(a);
-        twi[k] = (float)(-std::sin(a));
+        t.twr[k] = (float)std::cos(a);
+        t.twi[k] = (float)(-std::sin(a));
     }
-    mel.window = upload(window.data(), window.size());
-    {   // the streaming preprocessor's frames are win_length samples, zero-padded on the right (src/audio.cpp:222-241)
-        std::vector<float> wl(n_fft, 0.0f);
-        for (int k = 0; k < win; ++k) wl[k] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)(win - 1)));
-        mel.window_left = upload(wl.data(), wl.size());
+    // packed bands for the LDS-staged dot products of the mel kernel
+    t.off.assign(n_mels + 1, 0);
+    for (int m = 0; m < n_mels; ++m) {
+        for (int f = t.lo[m]; f <= t.hi[m]; ++f) t.packed.push_back(t.fb[(size_t)f * n_mels + m]);
+        t.off[m + 1] = (int)t.packed.size();
     }
-    mel.tw_re = upload(twr.data(), twr.size());
-    mel.tw_im = upload(twi.data(), twi.size());
-    mel.fb = upload(fb.data(), fb.size());
-    mel.f_lo = reinterpret_cast<const int *>(upload(reinterpret_cast<const float *>(lo.data()), lo.size()));
-    mel.f_hi = reinterpret_cast<const int *>(upload(reinterpret_cast<const float *>(hi.data()), hi.size()));
-    {   // packed bands for the LDS-staged dot products of the mel kernel
-        std::vector<int> off(n_mels + 1, 0);
-        std::vector<float> packed;
-        for (int m = 0; m < n_mels; ++m) {
-            for (int f = lo[m]; f <= hi[m]; ++f) packed.push_back(fb[(size_t)f * n_mels + m]);
-            off[m + 1] = (int)packed.size();
-        }
-        if ((int)packed.size() > kMelMaxTaps) fail(PK_ERR_UNSUPPORTED, "mel filterbank has %d taps (> %d)", (int)packed.size(), kMelMaxTaps);
-        if (packed.empty()) packed.push_back(0.0f);
-        mel.fb_nnz = off[n_mels];
-        mel.fbc = upload(packed.data(), packed.size());
-        mel.fb_off = reinterpret_cast<const int *>(upload(reinterpret_cast<const float *>(off.data()), off.size()));
-    }
+    if ((int)t.packed.size() > kMelMaxTaps) fail(PK_ERR_UNSUPPORTED, "mel filterbank has %d taps (> %d)", (int)t.packed.size(), kMelMaxTaps);
+    t.n_mels = n_mels;
+    return t;
+}
+
+// ... and on the device: `upload` puts a host array there and keeps ownership.  Shared by Model, the weight-free MelFrontend (preprocess_audio
+// on its own) and pk_diag_mel.
+MelTables upload_mel_tables(const MelTablesHost &t, const std::function<const float *(const float *, size_t)> &upload) {
+    const int n_mels = t.n_mels;
+    auto upload_i = [&](const std::vector<int> &v) { return reinterpret_cast<const int *>(upload(reinterpret_cast<const float *>(v.data()), v.size())); };
+    MelTables mel{};
+    mel.window = upload(t.window.data(), t.window.size());
+    mel.window_left = upload(t.window_left.data(), t.window_left.size());
+    mel.tw_re = upload(t.twr.data(), t.twr.size());
+    mel.tw_im = upload(t.twi.data(), t.twi.size());
+    mel.fb = upload(t.fb.data(), t.fb.size());
+    mel.f_lo = upload_i(t.lo);
+    mel.f_hi = upload_i(t.hi);
+    mel.fb_nnz = t.off[n_mels];
+    const std::vector<float> none(1, 0.0f);                          // (a filterbank without a tap still gets a pointer)
+    mel.fbc = t.packed.empty() ? upload(none.data(), 1) : upload(t.packed.data(), t.packed.size());
+    mel.fb_off = upload_i(t.off);
     mel.n_mels = n_mels;
     mel.power_via_abs = 1;               // switch A2 default: abs() then square, as the reference writes it
     return mel;
+}
+
+MelTables make_mel_tables(int n_mels, bool window_centered, const std::function<const float *(const float *, size_t)> &upload) {
+    return upload_mel_tables(make_mel_tables_host(n_mels, window_centered), upload);
 }
 
 void Model::build_mel_tables() {

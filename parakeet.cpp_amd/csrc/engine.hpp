@@ -43,6 +43,15 @@ struct DecW {
     const float *ctc_w, *ctc_b;
 };
 
+// The mel front end's tables as the host builds them (MelTables: the same arrays on a device).  make_mel_tables_host refuses a filterbank of
+// more than kMelMaxTaps packed taps (PK_ERR_UNSUPPORTED); upload_mel_tables puts them on a device; make_mel_tables is the one after the other.
+struct MelTablesHost {
+    std::vector<float> window, window_left, twr, twi, fb, packed;   // [512] [512] [256] [256] [257][n_mels] [off[n_mels]]
+    std::vector<int> lo, hi, off;                                   // [n_mels] [n_mels] [n_mels + 1]
+    int n_mels = 0;
+};
+MelTablesHost make_mel_tables_host(int n_mels, bool window_centered);
+MelTables upload_mel_tables(const MelTablesHost &t, const std::function<const float *(const float *, size_t)> &upload);
 MelTables make_mel_tables(int n_mels, bool window_centered, const std::function<const float *(const float *, size_t)> &upload);
 
 // Per-kernel hipEvent timing: when a sink is attached every launch is bracketed by two events.

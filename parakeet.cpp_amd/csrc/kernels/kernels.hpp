@@ -69,11 +69,13 @@ struct MelTables {
 // workgroup stores is then one aligned 64-byte segment (the un-padded rows -- 1001 floats for 10 s -- put every run across sector boundaries:
 // 1.44x write traffic).  Only mel_normalize (and the debug read-outs of pk_mel) read it.
 __host__ __device__ inline int mel_logmel_pitch(int n_frames) { return (n_frames + 15) & ~15; }
-void launch_mel_logmel(const float *pcm, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel, hipStream_t s, const MelRag &rag = MelRag());
+// Each launcher returns the grid it launched (x, y, threads per workgroup): what pk_diag_mel reports.
+struct MelGrid { int x, y, threads; };
+MelGrid launch_mel_logmel(const float *pcm, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel, hipStream_t s, const MelRag &rag = MelRag());
 // StreamingAudioPreprocessor::process_chunk (src/audio.cpp:222-252) on pre-emphasised buffers pre[B][n_samples]:
 // n_frames = (n_samples - 400) / 160 + 1 frames -> log-mel [B][n_frames][n_mels] (no normalisation)
-void launch_mel_stream(const float *pre, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel_tf, hipStream_t s);
-void launch_mel_normalize(const float *logmel, int B, int n_mels, int n_frames, int normalize, float *feats, hipStream_t s, const MelRag &rag = MelRag());
+MelGrid launch_mel_stream(const float *pre, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel_tf, hipStream_t s);
+MelGrid launch_mel_normalize(const float *logmel, int B, int n_mels, int n_frames, int normalize, float *feats, hipStream_t s, const MelRag &rag = MelRag());
 
 // ---- fp32 MFMA GEMM: out = epi(A[M][K] * W[N][K]^T + bias), natural-k fma chains ----------------
 enum GemmEpi { EPI_NONE = 0, EPI_RELU = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_GLU = 4 };

@@ -277,22 +277,26 @@ __global__ __launch_bounds__(1024) void mel_normalize_kernel(const float *__rest
     }
 }
 
-void launch_mel_logmel(const float *pcm, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel, hipStream_t s, const MelRag &rag) {
+MelGrid launch_mel_logmel(const float *pcm, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel, hipStream_t s, const MelRag &rag) {
     constexpr int fpb = kOfflineWaves;
     if (rag.pcm_off) n_frames = rag.max_frames;
-    dim3 grid((n_frames + fpb - 1) / fpb, B);
+    const MelGrid g{(n_frames + fpb - 1) / fpb, B, 64 * fpb};
     constexpr size_t lds = mel_lds_bytes<kOfflineWaves>(true);
     static DynLdsSlots slots;
     ensure_dyn_lds(slots, reinterpret_cast<const void *>(&mel_logmel_kernel<false, kOfflineWaves>), lds);
-    hipLaunchKernelGGL((mel_logmel_kernel<false, kOfflineWaves>), grid, dim3(64 * kOfflineWaves), lds, s, pcm, n_samples, n_frames, t, logmel, rag);
+    hipLaunchKernelGGL((mel_logmel_kernel<false, kOfflineWaves>), dim3(g.x, g.y), dim3(g.threads), lds, s, pcm, n_samples, n_frames, t, logmel, rag);
+    return g;
 }
-void launch_mel_stream(const float *pre, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel_tf, hipStream_t s) {
-    dim3 grid((n_frames + kStreamWaves - 1) / kStreamWaves, B);
+MelGrid launch_mel_stream(const float *pre, int B, int64_t n_samples, int n_frames, const MelTables &t, float *logmel_tf, hipStream_t s) {
+    const MelGrid g{(n_frames + kStreamWaves - 1) / kStreamWaves, B, 64 * kStreamWaves};
     constexpr size_t lds = mel_lds_bytes<kStreamWaves>(false);
-    hipLaunchKernelGGL((mel_logmel_kernel<true, kStreamWaves>), grid, dim3(64 * kStreamWaves), lds, s, pre, n_samples, n_frames, t, logmel_tf, MelRag());
+    hipLaunchKernelGGL((mel_logmel_kernel<true, kStreamWaves>), dim3(g.x, g.y), dim3(g.threads), lds, s, pre, n_samples, n_frames, t, logmel_tf, MelRag());
+    return g;
 }
-void launch_mel_normalize(const float *logmel, int B, int n_mels, int n_frames, int normalize, float *feats, hipStream_t s, const MelRag &rag) {
-    hipLaunchKernelGGL(mel_normalize_kernel, dim3((n_mels + 15) / 16, B), dim3(1024), 0, s, logmel, n_mels, n_frames, normalize, feats, rag);
+MelGrid launch_mel_normalize(const float *logmel, int B, int n_mels, int n_frames, int normalize, float *feats, hipStream_t s, const MelRag &rag) {
+    const MelGrid g{(n_mels + 15) / 16, B, 1024};
+    hipLaunchKernelGGL(mel_normalize_kernel, dim3(g.x, g.y), dim3(g.threads), 0, s, logmel, n_mels, n_frames, normalize, feats, rag);
+    return g;
 }
 
 }  // namespace pk

@@ -97,6 +97,11 @@ def test_no_gpu_is_a_loud_error(tmp_path):
     with pytest.raises(capi.PkError) as e:
         capi.diag_tile_copy_bf16(np.zeros((16, 32), np.float32))
     assert e.value.code == -4
+    for form, pcm in (("uniform", np.zeros((2, 700), np.float32)), ("ragged", [np.zeros(700, np.float32), np.zeros(257, np.float32)]),
+                      ("stream", np.zeros((2, 400), np.float32))):   # the mel front end diagnostic: valid arguments, no device
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_mel(pcm, form, n_mels=65)
+        assert e.value.code == -4
     with pytest.raises(capi.PkError) as e:             # the multi-GPU entry point as well
         capi.Group(str(wp), cfg)
     assert e.value.code == -4
@@ -291,3 +296,34 @@ def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
         with pytest.raises(capi.PkError):
             m.conv_variants(n_mel_frames=[5, 0])
         m.close()
+
+
+def test_mel_diagnostic_refuses_before_it_looks_for_a_device():
+    """pk_diag_mel (what tests/test_gpu_mel_forms.py launches the front end through) checks its arguments on the host: a clip the reflect padding
+    cannot frame, a chunk shorter than one window, a bin count or buffers it cannot take are PK_ERR_INVALID with or without a device, and the
+    caller's buffers stay as they were."""
+    assert "pk_diag_mel" in declared_symbols()
+    ok = np.zeros(700, np.float32)
+    bad = [("uniform", np.zeros((1, 256), np.float32), {}), ("ragged", [ok, np.zeros(256, np.float32), ok], {}),
+           ("stream", np.zeros((2, 399), np.float32), {}), ("uniform", ok, dict(n_mels=0)), ("uniform", ok, dict(n_mels=513)),
+           ("uniform", ok, dict(short=(80 * 16 + 63, 5 * 80 + 64))), ("uniform", ok, dict(short=(80 * 16 + 64, 5 * 80 + 63))),
+           ("stream", ok, dict(short=(2 * 80 + 63, 64))), ("stream", ok, dict(short=(2 * 80 + 64, 63)))]
+    for form, pcm, kw in bad:
+        lm, ft = np.full(4096, -77.25, np.float32), np.full(4096, -77.25, np.float32)
+        if "short" in kw:                                           # one buffer a word short of what the launches write plus 64 spare words
+            lm, ft = lm[:kw["short"][0]], ft[:kw["short"][1]]
+            kw = {}
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_mel(pcm, form, logmel=lm, feats=ft, **kw)
+        assert e.value.code == -1, (form, kw)
+        assert np.all(lm == np.float32(-77.25)) and np.all(ft == np.float32(-77.25))
+    L = capi.lib()
+    f32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    out, nf, grid = np.zeros(4096, np.float32), np.zeros(1, np.int32), np.zeros(6, np.int32)
+    off = np.array([0, 700], np.int64)
+    assert L.pk_diag_mel(80, 1, 0, 1, 3, f32(ok), 1, 700, None, f32(out), 4096, f32(out), 4096, i32(nf), i32(grid)) == -1       # no such form
+    assert L.pk_diag_mel(80, 1, 0, 1, 1, f32(ok), 1, 700, None, f32(out), 4096, f32(out), 4096, i32(nf), i32(grid)) == -1       # ragged without offsets
+    assert L.pk_diag_mel(80, 1, 0, 1, 0, f32(ok), 1, 700, off.ctypes.data_as(C.POINTER(C.c_int64)), f32(out), 4096, f32(out), 4096, i32(nf), i32(grid)) == -1
+    assert L.pk_diag_mel(80, 1, 0, 1, 0, None, 1, 700, None, f32(out), 4096, f32(out), 4096, i32(nf), i32(grid)) == -1
+    assert not out.any()
