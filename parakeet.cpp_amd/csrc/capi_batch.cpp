@@ -1216,7 +1216,7 @@ static void align_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offse
         const size_t n = bids.size();
         st.assign(n + 1, 0); en.assign(n + 1, 0); di.assign(n + 1, 0); cf.assign(n + 1, 0.0f); sc.resize(nc); tt.resize(nc); okv.resize(nc);
         if (tdt) {
-            tdt_align_upload(m.talign, bids.data(), m.stream);
+            tdt_lattice_upload(m.talign, bids.data(), m.stream, /*token_results=*/true);
             run_tdt_align_pred(m, m.talign, bids.data(), m.stream);
             m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
             run_tdt_align_lattice(m, m.talign, m.ws.ep.as<float>(), m.stream);

@@ -172,13 +172,18 @@ pk_beam_options pk::beam_options_of(const pk_beam_options *opt) {
     if (opt) o = *opt;
     return o;
 }
-// what the model entry points refuse (include/parakeet_amd.h); -> the CTC vocabulary and its blank
-void pk::beam_model_checks(Model &m, const pk_beam_options &o, int &V, int &blank) {
-    m.require_gpu();
-    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC beam search needs one");
-    if (m.boost_on) fail(PK_ERR_UNSUPPORTED, "CTC beam search has no phrase-boosted variant: clear the boost phrases of the model first");
+// The model check of everything that walks the CTC head's rows (include/parakeet_amd.h: beam search, alignment, keyword spotting); -> the CTC vocabulary and
+// its blank.  A boost trie does not matter to the alignment and the spotting: run_ctc writes the unboosted log-softmax rows, and those are what is walked.
+static void ctc_head_of(const Model &m, const char *what, int &V, int &blank) {
+    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: %s needs one", what);
     V = m.cfg.ctc_vocab_size;
     blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;           // (as Model::run_ctc)
+}
+// what the beam search's model entry points refuse (include/parakeet_amd.h)
+void pk::beam_model_checks(Model &m, const pk_beam_options &o, int &V, int &blank) {
+    m.require_gpu();
+    ctc_head_of(m, "CTC beam search", V, blank);
+    if (m.boost_on) fail(PK_ERR_UNSUPPORTED, "CTC beam search has no phrase-boosted variant: clear the boost phrases of the model first");
     beam_check_options(o, V, blank);
 }
 
@@ -204,18 +209,10 @@ static void ctc_beam_decode(Model &m, const float *enc, const int32_t *n_frames,
     beam_copy_out(m.beam, ids, lens, score, ts ? start : nullptr, ts ? end : nullptr, ts ? conf : nullptr, m.stream, fused ? lm_score : nullptr);
 }
 
-// the alignment's model checks (include/parakeet_amd.h); -> the CTC vocabulary and its blank.  A boost trie does not matter: run_ctc writes the
-// unboosted log-softmax rows, and those are what is aligned.
-static void align_model_checks(Model &m, int &V, int &blank) {
-    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC alignment needs one");
-    V = m.cfg.ctc_vocab_size;
-    blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;           // (as Model::run_ctc)
-}
-
 static void ctc_align_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids, const int32_t *id_offsets,
                              int32_t *start, int32_t *end, float *conf, float *score, float *total, int32_t *ok) {
     int V = 0, blank = 0;
-    align_model_checks(m, V, blank);
+    ctc_head_of(m, "CTC alignment", V, blank);
     align_check_args(ids, id_offsets, B, V, blank);
     if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
     m.require_gpu();
@@ -237,7 +234,7 @@ static void tdt_align_queue(Model &m, const float *enc, const int32_t *n_frames,
     T = size_ws(m, n_frames, B, T, rows);
     if (upload_enc) PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
     if (ev) PK_HIP(hipEventRecord(ev[0], m.stream));
-    tdt_align_upload(m.talign, ids, m.stream);
+    tdt_lattice_upload(m.talign, ids, m.stream, /*token_results=*/true);
     run_tdt_align_pred(m, m.talign, ids, m.stream);
     if (ev) PK_HIP(hipEventRecord(ev[1], m.stream));
     m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
@@ -264,19 +261,11 @@ static void tdt_align_decode(Model &m, const float *enc, const int32_t *n_frames
     tdt_align_copy_out(m.talign, start, end, dur_idx, conf, score, ok, m.stream);
 }
 
-// the spotting's model checks (include/parakeet_amd.h); -> the CTC vocabulary and its blank.  A boost trie does not matter: run_ctc writes the
-// unboosted log-softmax rows, and those are what is walked.
-static void kws_model_checks(Model &m, int &V, int &blank) {
-    if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC keyword spotting needs one");
-    V = m.cfg.ctc_vocab_size;
-    blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;           // (as Model::run_ctc)
-}
-
 static void ctc_kws_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
                            const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
     const pk_kws_options o = kws_options_of(opt);
     int V = 0, blank = 0;
-    kws_model_checks(m, V, blank);
+    ctc_head_of(m, "CTC keyword spotting", V, blank);
     kws_check_args(kw_ids, kw_offsets, n_kw, B, V, blank, o);
     if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
     m.require_gpu();
@@ -752,7 +741,7 @@ pk_status pk_ctc_align_decode_timed(pk_model *h, const float *enc, const int32_t
         need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
         Model &m = *h->m;
         int V = 0, blank = 0;
-        align_model_checks(m, V, blank);
+        ctc_head_of(m, "CTC alignment", V, blank);
         align_check_args(ids, id_offsets, B, V, blank);
         if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
         m.require_gpu();
@@ -772,24 +761,36 @@ pk_status pk_ctc_align_decode_timed(pk_model *h, const float *enc, const int32_t
 }
 
 /* ---- TDT forced alignment of given token strings (kernels/tdt_align.hip) ------------------------------------------------------------ */
+// The walks alone on a HOST lattice (pk_tdt_align here, pk_tdt_total below) share two halves; the entry point's own output checks run between them, where they
+// always ran.  The first: the argument checks on the tables.
+static void tdt_host_lattice_checks(const int32_t *durations, const int32_t *n_frames, int B, const int32_t *id_offsets) {
+    need(B >= 1 && id_offsets && n_frames && durations, "B/id_offsets/n_frames/durations");
+    need(id_offsets[0] == 0, "id_offsets[0] must be 0");
+    for (int b = 0; b < B; ++b) {
+        need(id_offsets[b + 1] >= id_offsets[b], "id_offsets decrease");
+        need(n_frames[b] > 0, "n_frames[b] must be positive");
+    }
+}
+// The second: the plan -- host only: it refuses before a device is looked for or anything is allocated --, then the upload of the tables and of the three
+// lattice arrays on the null stream.
+static void tdt_host_lattice_stage(TdtAlignWs &ws, const float *lab, const float *blk, const float *dl, const int32_t *durations, int D,
+                                   const int32_t *n_frames, int B, const int32_t *id_offsets, bool back_pointers, const char *what) {
+    tdt_lattice_plan(ws, n_frames, nullptr, B, 0, id_offsets, durations, D, 0, 0, 0, back_pointers, what);
+    need_device();
+    tdt_lattice_upload(ws, nullptr, nullptr, /*token_results=*/back_pointers);
+    if (ws.labs) PK_HIP(hipMemcpyAsync(ws.lab.p, lab, (size_t)ws.labs * 4, hipMemcpyHostToDevice, nullptr));
+    PK_HIP(hipMemcpyAsync(ws.blk.p, blk, (size_t)ws.cells * 4, hipMemcpyHostToDevice, nullptr));
+    PK_HIP(hipMemcpyAsync(ws.dl.p, dl, (size_t)ws.cells * D * 4, hipMemcpyHostToDevice, nullptr));
+}
+
 pk_status pk_tdt_align(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int B,
                        const int32_t *id_offsets, int32_t *start, int32_t *end, int32_t *dur_idx, float *conf, float *score, int32_t *ok) {
     return guard([&] {
-        need(B >= 1 && id_offsets && n_frames && durations, "B/id_offsets/n_frames/durations");
-        need(id_offsets[0] == 0, "id_offsets[0] must be 0");
-        for (int b = 0; b < B; ++b) {
-            need(id_offsets[b + 1] >= id_offsets[b], "id_offsets decrease");
-            need(n_frames[b] > 0, "n_frames[b] must be positive");
-        }
+        tdt_host_lattice_checks(durations, n_frames, B, id_offsets);
         need(blk && dl && score && ok, "blk/dl/score/ok");
         need(id_offsets[B] == 0 || (lab && start && end && dur_idx && conf), "lab/start/end/dur_idx/conf");
         TdtAlignWs ws;
-        tdt_align_plan(ws, n_frames, B, 0, id_offsets, durations, D);          // (host only: refuses before a device is looked for or anything is allocated)
-        need_device();
-        tdt_align_upload(ws, nullptr, nullptr);
-        if (ws.labs) PK_HIP(hipMemcpyAsync(ws.lab.p, lab, (size_t)ws.labs * 4, hipMemcpyHostToDevice, nullptr));
-        PK_HIP(hipMemcpyAsync(ws.blk.p, blk, (size_t)ws.cells * 4, hipMemcpyHostToDevice, nullptr));
-        PK_HIP(hipMemcpyAsync(ws.dl.p, dl, (size_t)ws.cells * D * 4, hipMemcpyHostToDevice, nullptr));
+        tdt_host_lattice_stage(ws, lab, blk, dl, durations, D, n_frames, B, id_offsets, /*back_pointers=*/true, "TDT alignment");
         run_tdt_align_dp(ws, nullptr);
         PK_CHECK_LAUNCH();
         tdt_align_copy_out(ws, start, end, dur_idx, conf, score, ok, nullptr);
@@ -895,21 +896,11 @@ extern "C" {
 pk_status pk_tdt_total(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int B,
                        const int32_t *id_offsets, float *total, int32_t *ok) {
     return guard([&] {
-        need(B >= 1 && id_offsets && n_frames && durations, "B/id_offsets/n_frames/durations");
-        need(id_offsets[0] == 0, "id_offsets[0] must be 0");
-        for (int b = 0; b < B; ++b) {
-            need(id_offsets[b + 1] >= id_offsets[b], "id_offsets decrease");
-            need(n_frames[b] > 0, "n_frames[b] must be positive");
-        }
+        tdt_host_lattice_checks(durations, n_frames, B, id_offsets);
         need(blk && dl && total && ok, "blk/dl/total/ok");
         need(id_offsets[B] == 0 || lab, "lab");
         TdtAlignWs ws;
-        tdt_lattice_plan(ws, n_frames, nullptr, B, 0, id_offsets, durations, D, 0, 0, 0, /*back_pointers=*/false, "TDT total");   // (host only: refuses before a device is looked for)
-        need_device();
-        tdt_total_upload(ws, nullptr, nullptr);
-        if (ws.labs) PK_HIP(hipMemcpyAsync(ws.lab.p, lab, (size_t)ws.labs * 4, hipMemcpyHostToDevice, nullptr));
-        PK_HIP(hipMemcpyAsync(ws.blk.p, blk, (size_t)ws.cells * 4, hipMemcpyHostToDevice, nullptr));
-        PK_HIP(hipMemcpyAsync(ws.dl.p, dl, (size_t)ws.cells * D * 4, hipMemcpyHostToDevice, nullptr));
+        tdt_host_lattice_stage(ws, lab, blk, dl, durations, D, n_frames, B, id_offsets, /*back_pointers=*/false, "TDT total");
         run_tdt_total_dp(ws, nullptr);
         PK_CHECK_LAUNCH();
         PK_HIP(hipMemcpyAsync(total, ws.out.p, (size_t)B * 4, hipMemcpyDeviceToHost, nullptr));
@@ -1026,7 +1017,7 @@ pk_status pk_ctc_kws_decode_timed(pk_model *h, const float *enc, const int32_t *
         Model &m = *h->m;
         const pk_kws_options o = kws_options_of(opt);
         int V = 0, blank = 0;
-        kws_model_checks(m, V, blank);
+        ctc_head_of(m, "CTC keyword spotting", V, blank);
         kws_check_args(kw_ids, kw_offsets, n_kw, B, V, blank, o);
         if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
         m.require_gpu();

@@ -42,13 +42,6 @@ namespace {
 
 constexpr int kTraceDw = 10;                                       // dwords of one staged back-pointer row (9 can be visited, see above)
 
-// log(exp a + exp b) = m + log(1 + exp(n - m)), m = max, n = min; m where n == -inf   (lae of tests/ctc_beam_ref.py)
-__device__ __forceinline__ float align_lae(float a, float b) {
-    const float m = fmaxf(a, b), n = fminf(a, b);
-    if (!(n > -__builtin_huge_valf())) return m;
-    return m + dlogf(1.0f + dexpf(n - m));
-}
-
 }  // namespace
 
 template <int NT, int SP, bool TOTAL>
@@ -133,8 +126,8 @@ __global__ __launch_bounds__(NT) void ctc_align_kernel(CtcAlignArgs a) {
                 if constexpr (TOTAL) {
                     const float tprev = u >= 1 ? ta[u >= 1 ? u - 1 : 0] : nb.y;
                     const float tskip = u >= 2 ? ta[u >= 2 ? u - 2 : 0] : nb.y;
-                    float x = align_lae(ta[u], tprev);
-                    if (token) x = align_lae(x, may_skip ? tskip : NEG);
+                    float x = dlaef(ta[u], tprev);
+                    if (token) x = dlaef(x, may_skip ? tskip : NEG);
                     ta[u] = x + ev;
                 }
             }
@@ -170,7 +163,7 @@ __global__ __launch_bounds__(NT) void ctc_align_kernel(CtcAlignArgs a) {
         const bool okv = sc > NEG;
         a.score[b] = okv ? sc : NEG;
         a.ok[b] = okv ? 1 : 0;
-        if constexpr (TOTAL) a.total[b] = L > 0 ? align_lae(fin[0 + 2], fin[1 + 2]) : fin[2];
+        if constexpr (TOTAL) a.total[b] = L > 0 ? dlaef(fin[0 + 2], fin[1 + 2]) : fin[2];
         s_cur = okv ? se : -1;
     }
     __syncthreads();

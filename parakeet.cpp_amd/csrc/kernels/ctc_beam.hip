@@ -60,12 +60,6 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k)
     });
     return k;
 }
-// log(exp a + exp b) = m + log(1 + exp(n - m)), m = max, n = min; m where n == -inf
-__device__ __forceinline__ float beam_lae(float a, float b) {
-    const float m = fmaxf(a, b), n = fminf(a, b);
-    if (!(n > -__builtin_huge_valf())) return m;
-    return m + dlogf(1.0f + dexpf(n - m));
-}
 // hash of (string + c) from the hash of the string: the splitmix64 finaliser (a bijection) of h + golden * (c + 1)
 __device__ __forceinline__ unsigned long long beam_hash(unsigned long long h, int c) {
     unsigned long long z = h + 0x9E3779B97F4A7C15ull * (unsigned long long)(unsigned)(c + 1);
@@ -218,8 +212,8 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(std::conditional_t<k
                             if (s.len[cur][q] == len - 1 && s.hash[cur][q] == ph) mrg = (s.last[cur][q] == last ? s.pb[cur][q] : s.tot[cur][q]) + v;
                     }
                 }
-                npnb[u] = beam_lae(rep, mrg);
-                sc[u] = beam_lae(npb[u], npnb[u]);
+                npnb[u] = dlaef(rep, mrg);
+                sc[u] = dlaef(npb[u], npnb[u]);
                 if constexpr (kLm) { nlm[u] = sl.lm[cur][i]; nls[u] = sl.lmstate[cur][i]; }           // its LM state and score stay with it
             } else {                                                // p + c
                 tok = s.fid[cur][j - 1];

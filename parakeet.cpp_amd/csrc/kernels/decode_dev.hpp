@@ -343,16 +343,48 @@ struct BestLP {
     float lp;
     int idx;
 };
+// A head of n <= 8 values (the TDT durations), one wave: every lane gets the log-prob of index lane & 7, -inf where that index is past n.  Lanes 8 .. 63 would
+// carry the identities through the first three steps of every tree -- the last three steps give lanes 0 .. 7 the same bits (pk_devmath.h: wave_sum_low8).
+__device__ __forceinline__ float wave_logsoftmax_low8(const float *__restrict__ x, int n, int lane) {
+    const int i = lane & 7;
+    const bool in = i < n;
+    const float xi = in ? x[i] : -__builtin_huge_valf();
+    const float m = wave_max_low8(xi);
+    const float lse = dlogf(wave_sum_low8(in ? dexpf_nonpos(xi - m) : 0.0f));
+    return in ? (xi - m) - lse : -__builtin_huge_valf();
+}
+// The canonical log-softmax of a row of V values, one wave: the row maximum and the log of the sum of dexpf_nonpos(x - m), 64 strided partial sums with the adds in
+// index order, then wave_sum64 (the n > 8 form of wave_logsoftmax_argmax below, bit for bit) -- with 8 loads in flight per lane.  The log-prob of index i is
+// (x[i] - m) - lse.
+struct RowLse {
+    float m, lse;
+};
+__device__ __forceinline__ RowLse wave_row_max_lse(const float *__restrict__ x, int V, int lane) {
+    float m = -__builtin_huge_valf();
+    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) m = fmaxf(m, v[q]);
+    }
+    m = wave_max64(m);
+    float p = 0.0f;
+    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { if (i0 + 64 * q < V) p = p + dexpf_nonpos(v[q] - m); }
+    }
+    return {m, dlogf(wave_sum64(p))};
+}
 __device__ __forceinline__ BestLP wave_logsoftmax_argmax(const float *__restrict__ x, int n, float *__restrict__ lp_out, int lane) {
     if (n <= 8) {
-        // a head of a few values (the TDT durations): lanes 8 .. 63 would carry the identities through the first three steps of every tree -- the last three
-        // steps give lanes 0 .. 7 the same bits (pk_devmath.h: wave_sum_low8); lanes >= 8 return what lane (l & 7) returns
+        // lanes >= 8 return what lane (l & 7) returns
         const int i = lane & 7;
         const bool in = i < n;
-        const float xi = in ? x[i] : -__builtin_huge_valf();
-        const float m = wave_max_low8(xi);
-        const float lse = dlogf(wave_sum_low8(in ? dexpf_nonpos(xi - m) : 0.0f));
-        float best = in ? (xi - m) - lse : -__builtin_huge_valf();
+        float best = wave_logsoftmax_low8(x, n, lane);
         int bi = in ? i : 0x7fffffff;
         if (lp_out && in && lane < 8) lp_out[i] = best;
         auto step = [&](auto off) {

@@ -4,13 +4,12 @@
 // to (t + max(dur[i], 1), u), label arc i to (t + dur[i], u + 1), one terminal END; a max-plus walk in pull form, candidates blank 0 .. D-1 then
 // label 0 .. D-1, each alpha[src] + (x + dl) as two fp32 adds, strict > (the earlier candidate stays).  Every value is compared bit for bit.
 //
-//   tdt_lattice_act_kernel    z = relu(enc_proj[t] + pred_proj[u]) for a chunk of lattice rows, as the decode loop's joint activation forms it
-//       (decode_dev.hpp SK_ACT: enc_proj + (pred_proj [+ bias]), > 0 ? s : 0), natural columns: the A operand of the heads product on the fp32
-//       GEMM.  One wave per row, float4 where J allows.
-//   tdt_lattice_keep_kernel   one wave per row of the heads product's output [V + D]: the canonical log-softmax (row maximum, dexpf_nonpos,
-//       64 strided partial sums in index order, wave_sum64, dlogf; the duration head through wave_logsoftmax_argmax's low-8 form, exactly the
-//       decision kernel's) and only 2 + D values leave: the label log-prob of ids[u], the blank's, the D duration log-probs.  The chunk's logits
-//       are the only place a whole row exists.
+//   tdt_lattice_act_kernel    z = relu(enc_proj[t] + pred_proj[u]) for a chunk of lattice rows: the A operand of the heads product on the fp32 GEMM.
+//       One wave per row, the row itself is joint_act_row (tdt_lattice_dev.hpp; the beam search's activation calls it too).
+//   tdt_lattice_keep_kernel   one wave per row of the heads product's output [V + D]: the canonical log-softmax (decode_dev.hpp wave_row_max_lse: row
+//       maximum, dexpf_nonpos, 64 strided partial sums in index order, wave_sum64, dlogf; the duration head through wave_logsoftmax_argmax's
+//       low-8 form, exactly the decision kernel's) and only 2 + D values leave: the label log-prob of ids[u], the blank's, the D duration
+//       log-probs.  The chunk's logits are the only place a whole row exists.
 //   tdt_align_kernel<NT>      one workgroup of NT threads per utterance, advancing by anti-diagonals d = t + u: every predecessor of a cell lies
 //       on an earlier diagonal (blank i on d - max(dur, 1), label i on d - dur - 1, so also the dur = 0 label arc from (t, u - 1)).  alpha lives
 //       in LDS as a ring of dur_max + 2 diagonals of u_max + 1 floats, indexed [d % ring][u]; ONE barrier per diagonal (diagonal d + 1 overwrites
@@ -19,6 +18,9 @@
 //       Back-pointers: one byte per cell in global memory (the arc's index, 255 = unreachable).  END is evaluated by thread 0 from the alpha of
 //       the last kTdtAlignMaxDur frames of columns U - 1 and U, kept in a small LDS table; the back-trace is thread 0 walking the bytes (one
 //       dependent load per arc, <= T + U of them), conf[k] = dexpf(lab[start[k]][k]) by all threads afterwards.
+//       The walk is written out here and is, line for line, tdt_lattice_walk (tdt_lattice_dev.hpp, which tdt_total_kernel calls) with a max-plus fold
+//       and the back-pointer byte: built on that function the kernel measured 1 - 3 % slower at batch shapes (profiles/tdt_lattice_walk.md), so the
+//       two are kept apart and a fix to one walk has to be made in the other.
 //
 // Limits (host side: tdt_align.cpp refuses with PK_ERR_UNSUPPORTED before anything is allocated):
 //   durations 0 <= dur[i] <= kTdtAlignMaxDur = 8, 1 <= D <= 8; U_b <= kTdtAlignMaxTokens = 1535 -- from the LDS arithmetic
@@ -31,9 +33,10 @@
 //   (the durations and blank steps are wave-uniform and live in SGPRs; the back-trace indexes the durations through the kernel argument, so no
 //    array is indexed by a run-time value and nothing goes to private memory)
 //   tdt_lattice_act_kernel      46 VGPR  24 SGPR  LDS  0 B             scratch 0 B; 0 VGPR spills, 0 SGPR spills
-//   tdt_lattice_keep_kernel     47 VGPR  36 SGPR  LDS  0 B             scratch 0 B; 0 VGPR spills, 0 SGPR spills
+//   tdt_lattice_keep_kernel     49 VGPR  36 SGPR  LDS  0 B             scratch 0 B; 0 VGPR spills, 0 SGPR spills
 //   (the ring: (dur_max + 2) (u_max + 1) 4 bytes of dynamic LDS, 3 KB for 90 tokens and durations up to 4, 61440 bytes at the limits)
 #include "decode_dev.hpp"
+#include "tdt_lattice_dev.hpp"
 
 namespace pk {
 
@@ -61,22 +64,7 @@ __global__ __launch_bounds__(256) void tdt_lattice_act_kernel(TdtLattice lt, con
     const int U1 = lt.id_off[b + 1] - lt.id_off[b] + 1;
     const int64_t c = r - lt.cell_off[b];
     const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
-    const float *er = ep + ((int64_t)ep_row0[b] + t) * J, *pr = pp + ((int64_t)u * lt.B + b) * J;
-    float *zr = z + i * J;
-    if ((J & 3) == 0) {
-        for (int j = 4 * lane; j < J; j += 256) {
-            const float4 e = *reinterpret_cast<const float4 *>(er + j), p = *reinterpret_cast<const float4 *>(pr + j);
-            float4 s;
-            s.x = e.x + p.x; s.y = e.y + p.y; s.z = e.z + p.z; s.w = e.w + p.w;
-            s.x = s.x > 0.0f ? s.x : 0.0f; s.y = s.y > 0.0f ? s.y : 0.0f; s.z = s.z > 0.0f ? s.z : 0.0f; s.w = s.w > 0.0f ? s.w : 0.0f;
-            *reinterpret_cast<float4 *>(zr + j) = s;
-        }
-    } else {
-        for (int j = lane; j < J; j += 64) {
-            const float s = er[j] + pr[j];
-            zr[j] = s > 0.0f ? s : 0.0f;
-        }
-    }
+    joint_act_row(ep + ((int64_t)ep_row0[b] + t) * J, pp + ((int64_t)u * lt.B + b) * J, z + i * J, J, lane);
 }
 
 __global__ __launch_bounds__(256) void tdt_lattice_keep_kernel(TdtLattice lt, const int *__restrict__ ids, const float *__restrict__ logits, int V,
@@ -90,25 +78,8 @@ __global__ __launch_bounds__(256) void tdt_lattice_keep_kernel(TdtLattice lt, co
     const int64_t c = r - lt.cell_off[b];
     const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
     const float *x = logits + i * (int64_t)(V + lt.D);
-    // the canonical row log-softmax (decode_dev.hpp wave_logsoftmax_argmax, n > 8): 8 loads in flight per lane, the adds in index order
-    float m = -__builtin_huge_valf();
-    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
-        float v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) m = fmaxf(m, v[q]);
-    }
-    m = wave_max64(m);
-    float p = 0.0f;
-    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
-        float v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { if (i0 + 64 * q < V) p = p + dexpf_nonpos(v[q] - m); }
-    }
-    const float lse = dlogf(wave_sum64(p));
+    const RowLse rl = wave_row_max_lse(x, V, lane);
+    const float m = rl.m, lse = rl.lse;
     if (lane == 0) lt.blk[r] = (x[blank] - m) - lse;
     if (lane == 1 && u < U) lt.lab[lt.lab_off[b] + (int64_t)t * U + u] = (x[ids[lt.id_off[b] + u]] - m) - lse;
     wave_logsoftmax_argmax(x + V, lt.D, lt.dl + r * lt.D, lane);    // (D <= 8: lanes 0 .. D-1 store the duration log-probs)
@@ -204,10 +175,8 @@ __global__ __launch_bounds__(NT) void tdt_align_kernel(TdtAlignArgs a) {
                 if (label) {
                     if (u == 0) break;                              // (no label arc enters column 0; keeps the stores inside the utterance's arrays)
                     --u;
-                    const int di = lt.durations[i];                 // (through the kernel argument: dur[] / bstep[] are indexed by constants only and stay in registers)
-                    const int e = t + (di > 1 ? di : 1) - 1;
                     a.start[i0 + u] = t;
-                    a.end[i0 + u] = e < T ? e : T - 1;
+                    a.end[i0 + u] = tdt_token_end(t, lt.durations[i], T);      // (through the kernel argument: dur[] / bstep[] are indexed by constants only and stay in registers)
                     a.dur_idx[i0 + u] = i;
                 }
                 if ((t == 0 && u == 0) || u < 0) break;
@@ -236,11 +205,7 @@ void launch_tdt_lattice_keep(const TdtLattice &lt, const int *ids, const float *
 }
 
 void launch_tdt_align(const TdtAlignArgs &a, hipStream_t s) {
-    if (a.dur_max < 0 || a.dur_max > kTdtAlignMaxDur || a.u_max < 0 || a.u_max > kTdtAlignMaxTokens || a.lt.D < 1 || a.lt.D > 8) {
-        fprintf(stderr, "parakeet_amd: internal error: launch_tdt_align outside the kernel's limits (dur_max %d, u_max %d, D %d)\n", a.dur_max, a.u_max, a.lt.D);
-        abort();
-    }
-    const size_t lds = (size_t)(a.dur_max + 2) * (a.u_max + 1) * sizeof(float);
+    const size_t lds = tdt_walk_launch_checks("launch_tdt_align", a.lt, a.u_max, a.dur_max);
     if (a.u_max + 1 <= kTdtAlignThreads[0]) hipLaunchKernelGGL(tdt_align_kernel<64>, dim3(a.lt.B), dim3(64), lds, s, a);
     else hipLaunchKernelGGL(tdt_align_kernel<256>, dim3(a.lt.B), dim3(256), lds, s, a);
 }

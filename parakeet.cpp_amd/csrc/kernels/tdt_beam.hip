@@ -10,11 +10,11 @@
 //       from a label arc with the blank as its token, so the first step's prediction-net step consumes [blank] from the zero state.
 //   tdt_beam_gather_kernel   one workgroup per row: h, c (every LSTM layer) and pred_proj of the row's parent.  The parent's state is what
 //       the prediction-net step of the step before computed when the parent was born from a label arc, else what that step gathered.
-//   tdt_beam_act_kernel      z = relu(enc_proj[t] + pred_proj) of a live row, one wave per row: tdt_lattice_act_kernel's arithmetic, with the
-//       clip's row offset and the row's own frame pointer.
-//   tdt_beam_expand_kernel   one wave per live row of the heads product's output [V + D]: the canonical log-softmax exactly as
-//       tdt_lattice_keep_kernel forms it, then the K best non-blank labels by (log-prob down, id up) -- every lane keeps the best of its
-//       strided elements, a round is one wave argmax and a rescan by the winning lane alone --, the blank inserted by the same order, the
+//   tdt_beam_act_kernel      z = relu(enc_proj[t] + pred_proj) of a live row, one wave per row: joint_act_row (tdt_lattice_dev.hpp), the row of
+//       tdt_lattice_act_kernel, with the clip's row offset and the row's own frame pointer.
+//   tdt_beam_expand_kernel   one wave per live row of the heads product's output [V + D]: the canonical log-softmax (decode_dev.hpp
+//       wave_row_max_lse, wave_logsoftmax_low8: what tdt_lattice_keep_kernel takes), then the K best non-blank labels by (log-prob down,
+//       id up) -- every lane keeps the best of its strided elements, a round is one wave argmax and a rescan by the winning lane alone --, the blank inserted by the same order, the
 //       duration head's ranks, and the candidate scores s + (x + dl) in the order label rank, duration rank.
 //   tdt_beam_prune_kernel    one workgroup of 256 threads per clip.  The pool (finished hypotheses at positions w, the candidate c of slot
 //       w at W + w C + c, C = (K + 1) Kd) is an LDS array of 64-bit keys (order-preserving score bits, then position inverted); a round
@@ -28,9 +28,9 @@
 // scratch of a call <= 1 GiB.  Pool: 16 + 16 x 17 x 8 = 2192 keys = 17536 bytes of LDS.
 //
 // Code objects (hipcc -O3 --offload-arch=gfx950, from the .s of -save-temps):
-//   tdt_beam_expand_kernel   41 VGPR 50 SGPR  LDS     0 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
+//   tdt_beam_expand_kernel   43 VGPR 50 SGPR  LDS     0 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
 //   tdt_beam_prune_kernel    60 VGPR 85 SGPR  LDS 18784 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
-//   tdt_beam_gather_kernel   19 VGPR 31 SGPR, tdt_beam_act_kernel 38 VGPR 15 SGPR, tdt_beam_trace_kernel 29 VGPR 35 SGPR, tdt_beam_init_kernel 23 VGPR
+//   tdt_beam_gather_kernel   19 VGPR 31 SGPR, tdt_beam_act_kernel 46 VGPR 17 SGPR, tdt_beam_trace_kernel 27 VGPR 35 SGPR, tdt_beam_init_kernel 23 VGPR
 //   36 SGPR: no LDS, no scratch, no spills
 //
 // With n-gram LM shallow fusion (the specification is tests/tdt_beam_lm_ref.py): init, expand, prune and trace are
@@ -41,10 +41,11 @@
 // longest chain once -- and stores lm2 = lm + ((alpha * lp) + beta) and the next state beside the label; the blank's entry holds the row's
 // own.  The fused prune builds its keys from f = score + lm (a finished entry's own two values, a candidate's cand + lm2 of its label), so
 // duplicates and the W best are decided by f; score, lm and the state of a chosen entry go to the new beam.  The fused trace writes lm_score.
-//   tdt_beam_expand_kernel<true>  39 VGPR 70 SGPR  LDS     0 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
+//   tdt_beam_expand_kernel<true>  41 VGPR 70 SGPR  LDS     0 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
 //   tdt_beam_prune_kernel<true>   68 VGPR 86 SGPR  LDS 19040 B  scratch 0 B; 0 VGPR spills, 0 SGPR spills
-//   tdt_beam_init_kernel<true> 28 VGPR 42 SGPR, tdt_beam_trace_kernel<true> 29 VGPR 35 SGPR: no LDS, no scratch, no spills
+//   tdt_beam_init_kernel<true> 28 VGPR 42 SGPR, tdt_beam_trace_kernel<true> 27 VGPR 35 SGPR: no LDS, no scratch, no spills
 #include "decode_dev.hpp"
+#include "tdt_lattice_dev.hpp"
 #include "ngram_lm_dev.hpp"
 
 namespace pk {
@@ -104,12 +105,7 @@ __global__ __launch_bounds__(256) void tdt_beam_act_kernel(TdtBeamDev a, int s, 
     const int T = a.T[b], t = a.t[p * R + r];
     if (!a.valid[p * R + r] || t >= T) return;
     const int J = a.J;
-    const float *er = ep + ((int64_t)a.row0[b] + t) * J, *pr = (a.born[p * R + r] ? a.ppN : a.ppG[p]) + (int64_t)r * J;
-    float *zr = z + (int64_t)r * J;
-    for (int j = lane; j < J; j += 64) {
-        const float v = er[j] + pr[j];
-        zr[j] = v > 0.0f ? v : 0.0f;
-    }
+    joint_act_row(ep + ((int64_t)a.row0[b] + t) * J, (a.born[p * R + r] ? a.ppN : a.ppG[p]) + (int64_t)r * J, z + (int64_t)r * J, J, lane);
 }
 
 template <bool kLm>
@@ -123,33 +119,11 @@ __global__ __launch_bounds__(256) void tdt_beam_expand_kernel(TdtBeamDev a, int 
     const int V = a.V, D = a.D, K = a.K, Kd = a.Kd, blank = a.blank;
     const float NEG = -__builtin_huge_valf();
     const float *x = logits + (int64_t)r * (V + D);
-    // the canonical row log-softmax (tdt_lattice_keep_kernel): 8 loads in flight per lane, the adds in index order
-    float m = NEG;
-    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
-        float v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) m = fmaxf(m, v[q]);
-    }
-    m = wave_max64(m);
-    float sum = 0.0f;
-    for (int i0 = lane; i0 < V; i0 += 64 * 8) {
-        float v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { const int k = i0 + 64 * q; v[q] = x[k < V ? k : V - 1]; }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { if (i0 + 64 * q < V) sum = sum + dexpf_nonpos(v[q] - m); }
-    }
-    const float lse = dlogf(wave_sum64(sum));
+    const RowLse rl = wave_row_max_lse(x, V, lane);
+    const float m = rl.m, lse = rl.lse;
     const float lb = (x[blank] - m) - lse;
-    // the duration head (decode_dev.hpp wave_logsoftmax_argmax, n <= 8): lane l holds the log-prob of index l & 7
     const int di = lane & 7;
-    const bool din = di < D;
-    const float xd = din ? x[V + di] : NEG;
-    const float md = wave_max_low8(xd);
-    const float lsed = dlogf(wave_sum_low8(din ? dexpf_nonpos(xd - md) : 0.0f));
-    const float dlv = din ? (xd - md) - lsed : NEG;
+    const float dlv = wave_logsoftmax_low8(x + V, D, lane);         // the duration head: lane l holds the log-prob of index l & 7
     int rank = 0;
     for (int j = 0; j < D; ++j) {
         const float o = __shfl(dlv, j);
@@ -375,9 +349,8 @@ __global__ __launch_bounds__(64) void tdt_beam_trace_kernel(TdtBeamDev a, TdtBea
         const int4 rec = a.bp[(int64_t)st * R + base + slot];
         if (rec.y >= 0) {
             --u;
-            const int t = rec.z >> 3, dix = rec.z & 7, dur = a.durations[dix];
-            const int e = t + (dur > 1 ? dur : 1) - 1;
-            o.ids[o0 + u] = rec.y; o.start[o0 + u] = t; o.end[o0 + u] = e < T ? e : T - 1; o.dur_idx[o0 + u] = dix;
+            const int t = rec.z >> 3, dix = rec.z & 7;
+            o.ids[o0 + u] = rec.y; o.start[o0 + u] = t; o.end[o0 + u] = tdt_token_end(t, a.durations[dix], T); o.dur_idx[o0 + u] = dix;
             o.conf[o0 + u] = dexpf(__int_as_float(rec.w));
         }
         slot = rec.x;

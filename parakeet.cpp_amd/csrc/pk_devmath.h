@@ -98,6 +98,13 @@ __device__ __forceinline__ float dlogf(float x) {
     return r;
 }
 
+// log(exp a + exp b) = m + log(1 + exp(n - m)), m = max, n = min; m where n == -inf   (lae of tests/ctc_beam_ref.py)
+__device__ __forceinline__ float dlaef(float a, float b) {
+    const float m = fmaxf(a, b), n = fminf(a, b);
+    if (!(n > -__builtin_huge_valf())) return m;
+    return m + dlogf(1.0f + dexpf(n - m));
+}
+
 // tanh x.  |x| < 0.55: x + x^3 T(x^2); |x| > 9: +-1; otherwise 1 - 2/(e^{2|x|} + 1) with the sign restored.
 __device__ __forceinline__ float dtanhf(float x) {
     const float ax = __builtin_fabsf(x);

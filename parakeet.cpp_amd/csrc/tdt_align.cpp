@@ -64,20 +64,21 @@ void tdt_lattice_plan(TdtAlignWs &ws, const int32_t *n_frames, const int32_t *ro
     ws.B = B; ws.D = D; ws.n_ids = (size_t)id_offsets[B]; ws.cells = cells; ws.labs = labs;
 }
 
-void tdt_align_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s) {
+void tdt_lattice_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s, bool token_results) {
     const size_t n = std::max<size_t>(ws.n_ids, 1), cells = (size_t)std::max<int64_t>(ws.cells, 1);
-    ws.ids.reserve(n * 4); ws.start.reserve(n * 4); ws.end.reserve(n * 4); ws.didx.reserve(n * 4); ws.conf.reserve(n * 4);
+    ws.ids.reserve(n * 4);
     ws.tab.reserve(ws.h_tab.size() * 4); ws.tab64.reserve(ws.h_tab64.size() * 8);
     ws.lab.reserve(std::max<size_t>((size_t)ws.labs, 1) * 4); ws.blk.reserve(cells * 4); ws.dl.reserve(cells * ws.D * 4);
-    ws.bp.reserve(cells);
     ws.out.reserve((size_t)ws.B * 2 * 4);
     if (ws.n_ids && ids) PK_HIP(hipMemcpyAsync(ws.ids.p, ids, ws.n_ids * 4, hipMemcpyHostToDevice, s));      // (the walk alone reads no ids)
     PK_HIP(hipMemcpyAsync(ws.tab.p, ws.h_tab.data(), ws.h_tab.size() * 4, hipMemcpyHostToDevice, s));
     PK_HIP(hipMemcpyAsync(ws.tab64.p, ws.h_tab64.data(), ws.h_tab64.size() * 8, hipMemcpyHostToDevice, s));
-    PK_HIP(hipMemsetAsync(ws.start.p, 0, n * 4, s));
-    PK_HIP(hipMemsetAsync(ws.end.p, 0, n * 4, s));
-    PK_HIP(hipMemsetAsync(ws.didx.p, 0, n * 4, s));
-    PK_HIP(hipMemsetAsync(ws.conf.p, 0, n * 4, s));
+    if (!token_results) return;
+    ws.bp.reserve(cells);
+    for (DevBuf *b : {&ws.start, &ws.end, &ws.didx, &ws.conf}) {
+        b->reserve(n * 4);
+        PK_HIP(hipMemsetAsync(b->p, 0, n * 4, s));
+    }
 }
 
 void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_t s, float *const *state) {

@@ -32,7 +32,7 @@ struct TdtAlignWs {
     int durations[8] = {};
     size_t n_ids = 0;
     int64_t cells = 0, labs = 0;
-    TdtLattice lattice() const;                     // device view (after tdt_align_upload)
+    TdtLattice lattice() const;                     // device view (after tdt_lattice_upload)
     const int *ep_row0() const { return tab.as<int>() + 2 * (size_t)B + 1; }
 };
 
@@ -45,8 +45,9 @@ void tdt_align_plan(TdtAlignWs &ws, const int32_t *n_frames, int B, int T, const
 // byte per cell; what: the name the refusals carry.
 void tdt_lattice_plan(TdtAlignWs &ws, const int32_t *n_frames, const int32_t *row0, int B, int T, const int32_t *id_offsets, const int32_t *durations,
                       int D, int V, int J, int chunk_rows, bool back_pointers, const char *what);
-// reserves the buffers, uploads the tables and the token strings on s, zero-fills the result arrays
-void tdt_align_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s);
+// Reserves the lattice buffers of a planned walk and uploads its tables and token strings on s.  token_results (the alignment; the total keeps none):
+// also reserves the back-pointers and the per-token result arrays, and zero-fills the latter.
+void tdt_lattice_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s, bool token_results);
 // pred_proj of every prefix: U_max + 1 lock-step steps of the prediction net over [blank, ids...] on the decode loop's skinny products -> ws.pp.
 // Uses m.ws's LSTM state buffers (sized for B utterances by the caller), or state = {h, hn, c, cn}, each [L][B][Hp] floats.
 void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_t s, float *const *state = nullptr);

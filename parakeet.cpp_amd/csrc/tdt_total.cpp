@@ -45,17 +45,6 @@ void tdt_total_groups(std::vector<int32_t> &gstart, const int32_t *T_of, const i
     if (n_hyp > 0) gstart.push_back(n_hyp);
 }
 
-void tdt_total_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s) {
-    const size_t n = std::max<size_t>(ws.n_ids, 1), cells = (size_t)std::max<int64_t>(ws.cells, 1);
-    ws.ids.reserve(n * 4);
-    ws.tab.reserve(ws.h_tab.size() * 4); ws.tab64.reserve(ws.h_tab64.size() * 8);
-    ws.lab.reserve(std::max<size_t>((size_t)ws.labs, 1) * 4); ws.blk.reserve(cells * 4); ws.dl.reserve(cells * ws.D * 4);
-    ws.out.reserve((size_t)ws.B * 2 * 4);
-    if (ws.n_ids && ids) PK_HIP(hipMemcpyAsync(ws.ids.p, ids, ws.n_ids * 4, hipMemcpyHostToDevice, s));      // (the walk alone reads no ids)
-    PK_HIP(hipMemcpyAsync(ws.tab.p, ws.h_tab.data(), ws.h_tab.size() * 4, hipMemcpyHostToDevice, s));
-    PK_HIP(hipMemcpyAsync(ws.tab64.p, ws.h_tab64.data(), ws.h_tab64.size() * 8, hipMemcpyHostToDevice, s));
-}
-
 void run_tdt_total_dp(TdtAlignWs &ws, hipStream_t s) {
     TdtTotalArgs a{};
     a.lt = ws.lattice();
@@ -94,7 +83,7 @@ void run_tdt_total_call(Model &m, TdtTotalWs &ws, const float *d_ep, const int32
         ws.h.reserve(st); ws.hn.reserve(st); ws.c.reserve(st); ws.cn.reserve(st);
         float *state[4] = {ws.h.as<float>(), ws.hn.as<float>(), ws.c.as<float>(), ws.cn.as<float>()};
         if (ev) PK_HIP(hipEventRecord(ev[0], s));
-        tdt_total_upload(ws.a, gids, s);
+        tdt_lattice_upload(ws.a, gids, s, /*token_results=*/false);
         run_tdt_align_pred(m, ws.a, gids, s, state);
         if (ev) PK_HIP(hipEventRecord(ev[1], s));
         run_tdt_align_lattice(m, ws.a, d_ep, s);

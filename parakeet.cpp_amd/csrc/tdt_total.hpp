@@ -34,9 +34,8 @@ size_t tdt_total_scratch(int64_t cells, int64_t labs, int n, int u_max, int D, i
 void tdt_total_groups(std::vector<int32_t> &gstart, const int32_t *T_of, const int32_t *id_offsets, int n_hyp, const int32_t *durations, int D, int V,
                       int J, int max_hyps = 0);
 // the walk alone on a planned and uploaded lattice: results on the device in ws.out (total[B], ok[B])
+// (upload first: tdt_lattice_upload of tdt_align.hpp with token_results = false -- no back-pointers, no token arrays)
 void run_tdt_total_dp(TdtAlignWs &ws, hipStream_t s);
-// reserves the lattice buffers of a planned walk (no back-pointers, no token arrays) and uploads its tables and token strings on s
-void tdt_total_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s);
 // Plans a call of the model entry points (host only, refuses before anything is allocated): n_hyp hypotheses, hypothesis h on the frames of clip
 // clip_of[h] (nullptr: h, and n_hyp must equal n_clips); n_frames[n_clips] (nullptr: T each).
 void tdt_total_plan_call(Model &m, TdtTotalWs &ws, const int32_t *n_frames, int n_clips, int T, const int32_t *id_offsets,
