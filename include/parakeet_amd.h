@@ -762,6 +762,74 @@ pk_status pk_model_set_input_rate(pk_model *m, int rate);
 pk_status pk_model_get_input_rate(const pk_model *m, int *rate);
 /* pk_model_set_input_rate on every replica of the group (pk_group_transcribe_pcm then takes input-rate PCM). */
 pk_status pk_group_set_input_rate(pk_group *g, int rate);
+/* ---- voice-activity segmentation on the device (kernels/vad.hip) ---------------------------------------------------
+ * The reference's roadmap lines "VAD: skip silent regions, reduce compute" (README.md:512) and "Long-form audio chunking" (README.md:511): an
+ * energy detector in front of the mel front end cuts long or sparse 16 kHz audio at its pauses into pieces of at most max_piece_s seconds,
+ * and the pieces go through the ragged packer of pk_transcribe_pcm as ordinary clips, so silence is never encoded and the encoder keeps full
+ * attention.  Every rule is specified in DESIGN.md section 5.8 (tests/vad_ref.py is that specification in Python; the device result equals
+ * it bit for bit).  In short, for a clip of n samples: F = ceil(n / 160) frames of 10 ms; e[f] = the fp32 sum of squares of a frame (zeros
+ * past n, in the fixed order of section 5.8); key(e) = the bit pattern of e, 0xFFFFFFFF for a NaN; floor = the energy of rank
+ * ((F - 1) * floor_percent) / 100 in ascending key order, found exactly (a radix select on the device); speech0[f] = e[f] >
+ * fmaxf(abs_thr, floor * ratio) with abs_thr = (float)(160 * 10^(threshold_db / 10)) and ratio = (float)(10^(margin_db / 10)), both rounded
+ * once from double; then non-speech gaps shorter than min_silence between speech become speech, speech runs shorter than min_speech are
+ * dropped, and every remaining run [s, e] is padded and snapped to the encoder's 8-frame grid, s' = 8 * floor(max(0, s - pad) / 8),
+ * e' = min(F - 1, 8 * ceil((min(F - 1, e + pad) + 1) / 8) - 1), overlapping and touching runs merged.  Runs are disjoint, ascending, and
+ * start on multiples of 8 frames (1280 samples = one encoder frame).
+ * Millisecond options become frames by integer division by 10; max_piece is the integer nearest to 100 * max_piece_s.  Refused with
+ * PK_ERR_INVALID before any device work: a non-finite option, threshold_db outside [-200, 60], margin_db outside [0, 100], floor_percent
+ * outside 0 .. 100, a millisecond option outside 0 .. 3 600 000, max_piece below 16 frames (the cut window then always holds a candidate) or
+ * above 360 000.  A clip of 2^31 samples or more is PK_ERR_UNSUPPORTED.
+ * Device scratch (grow-only; counted in pk_diag_mem_info for a model's): with S = the clips' samples, each clip rounded up to 32, F = the
+ * frames and C = the chunks of pk_vad_run() frames of all clips, R = the sum of (F_i + 1) / 2,
+ *     4 S + 6 F + 24 C + 8 R + 4156 n_clips bytes;
+ * more than 1 GiB is PK_ERR_UNSUPPORTED before anything is allocated.
+ * No variant for pk_group, streaming sessions, the n-best, alignment or spotting entry points, and none on resampled audio. */
+typedef struct pk_vad_options {
+    float threshold_db;         /* absolute threshold: mean square of a frame, dB re full scale */
+    float margin_db;            /* ... or this far above the noise floor, whichever is higher */
+    int32_t floor_percent;      /* the noise floor is this percentile of the clip's frame energies */
+    int32_t min_speech_ms;
+    int32_t min_silence_ms;
+    int32_t pad_ms;
+    int32_t max_gap_ms;         /* pieces: runs at most this far apart share a piece */
+    float max_piece_s;          /* pieces: longest piece */
+} pk_vad_options;
+/* The defaults -50 dB, 9 dB, 10 %, 100 ms, 300 ms, 200 ms, 1000 ms, 30 s: choices, not measurements of accuracy or speed */
+void pk_vad_options_default(pk_vad_options *out);
+typedef struct pk_vad_piece {
+    int32_t clip;               /* index of the clip the piece was cut from */
+    int64_t begin, end;         /* samples [begin, end) of that clip; begin is a multiple of 1280 */
+} pk_vad_piece;
+/* pk_vad_run: frames one workgroup handles per pass (a chunk); clips longer than that carry the select's and the smoothing's state across chunks.
+ * pk_vad_pcm: the stage alone on `device`, host buffers in and out, no model.  Clip i = pcm[offsets[i] .. offsets[i+1]) at 16 kHz with F_i
+ *   frames.  n_runs[i] = its runs; they are frame indices run_start / run_end[r_i .. r_i + n_runs[i]) with r_i = the sum of (F_j + 1) / 2 over
+ *   the clips before i -- (F + 1) / 2 runs per clip always suffice, so both arrays hold the sum of (F_i + 1) / 2 entries.  energy (optional)
+ *   takes the sum of F_i frame energies, clip after clip.  run_start, run_end and energy are uploaded before and read back after the
+ *   launches, so every entry the kernels do not write comes back as it was.  opt == NULL: the defaults.  Empty clips are allowed.
+ * pk_vad_plan: the pieces of ONE clip from its runs and energies (host logic, no device): walking the runs in order, a run joins the open
+ *   piece when it starts at most max_gap frames after the piece's end and the joined piece spans at most max_piece frames, otherwise it
+ *   opens a new piece; a run longer than max_piece is first cut after the frame f in [s + max_piece / 2, s + max_piece - 1] with
+ *   (f + 1) % 8 == 0 whose key(e[f]) is smallest (the earliest of equals), [s, f] being a run of its own and [f + 1, e] treated again.  Piece
+ *   [s, e] is the samples [160 s, min(n_samples, 160 (e + 1))); its frame offset in encoder frames is s / 8.  energy holds F values (read
+ *   only where a run is cut).  *pieces is malloc'd (pk_free; NULL when there are none), every clip field 0.
+ * pk_vad_pcm_timed: the launches of pk_vad_pcm alone between hipEvents, reps + 1 passes, the first not counted; *ms = the median (input
+ *   already on the device, nothing read back). */
+int pk_vad_run(void);
+pk_status pk_vad_pcm(int device, const float *pcm, const int64_t *offsets, int n_clips, const pk_vad_options *opt, int32_t *n_runs,
+                     int32_t *run_start, int32_t *run_end, float *energy);
+pk_status pk_vad_plan(int64_t n_samples, const int32_t *run_start, const int32_t *run_end, int n_runs, const float *energy,
+                      const pk_vad_options *opt, pk_vad_piece **pieces, int *n_pieces);
+pk_status pk_vad_pcm_timed(int device, const float *pcm, const int64_t *offsets, int n_clips, const pk_vad_options *opt, int reps, float *ms);
+/* pk_transcribe_pcm on the speech of long or sparse clips: the VAD runs on all clips on the model's stream, pk_vad_plan cuts every clip into
+ * pieces, and all pieces of all clips are transcribed as ordinary clips of one pk_transcribe_pcm call (packed together by its policy; the
+ * pieces' samples are uploaded a second time from the host).  Clip i's pk_result is its pieces' results merged in time order: token ids
+ * concatenated; start_frame / end_frame with the piece's frame offset (begin / 1280) added; confidences unchanged; the words concatenated,
+ * start and end becoming (float)((double)t + offset * 0.08); text = the pieces' non-empty texts joined by one space.  A clip without speech
+ * has empty text, 0 tokens and 0 words.  A piece of 256 samples or fewer (only the tail of a clip can be one) is listed but not transcribed.
+ * pieces_out / n_pieces_out (optional, together): every piece in clip order, then time order (malloc'd, pk_free; NULL when there are none).
+ * A model whose input rate is not 16 kHz: PK_ERR_UNSUPPORTED before any work. */
+pk_status pk_transcribe_pcm_vad(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const pk_options *opt,
+                                const pk_vad_options *vad_opt, pk_result **results, pk_vad_piece **pieces_out, int *n_pieces_out);
 /* read_audio(const uint8_t *data, size_t len, target) (audio_io.hpp:27-28): an encoded RIFF/WAVE image in memory -> mono PCM at
  * target_rate (malloc'd, pk_free). */
 pk_status pk_read_audio_memory(const void *data, size_t len, int target_rate, float **pcm, int64_t *n_samples, int *original_rate, int *n_channels);

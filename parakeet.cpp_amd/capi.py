@@ -76,6 +76,15 @@ class PkKwsOptions(C.Structure):
     _fields_ = [("max_hits", C.c_int32), ("min_score", C.c_float)]
 
 
+class PkVadOptions(C.Structure):
+    _fields_ = [("threshold_db", C.c_float), ("margin_db", C.c_float), ("floor_percent", C.c_int32), ("min_speech_ms", C.c_int32),
+                ("min_silence_ms", C.c_int32), ("pad_ms", C.c_int32), ("max_gap_ms", C.c_int32), ("max_piece_s", C.c_float)]
+
+
+class PkVadPiece(C.Structure):
+    _fields_ = [("clip", C.c_int32), ("begin", C.c_int64), ("end", C.c_int64)]
+
+
 class PkNbest(C.Structure):
     _fields_ = [("n_hyp", C.c_int32), ("hyp", C.POINTER(PkResult)), ("score", f32p)]
 
@@ -264,6 +273,13 @@ _LATE_SIGNATURES = {
     "pk_resample_table": [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_resample_device": [C.c_int, f32p, i64p, C.c_int, C.c_int, C.c_int, f32p, i64p],
     "pk_resample_device_timed": [C.c_int, f32p, i64p, C.c_int, C.c_int, C.c_int, C.c_int, f32p],
+    "pk_vad_options_default": [C.POINTER(PkVadOptions)],
+    "pk_vad_run": [],
+    "pk_vad_pcm": [C.c_int, f32p, i64p, C.c_int, C.POINTER(PkVadOptions), i32p, i32p, i32p, f32p],
+    "pk_vad_plan": [C.c_int64, i32p, i32p, C.c_int, f32p, C.POINTER(PkVadOptions), C.POINTER(C.POINTER(PkVadPiece)), C.POINTER(C.c_int)],
+    "pk_vad_pcm_timed": [C.c_int, f32p, i64p, C.c_int, C.POINTER(PkVadOptions), C.c_int, f32p],
+    "pk_transcribe_pcm_vad": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkOptions), C.POINTER(PkVadOptions), C.POINTER(C.POINTER(PkResult)),
+                              C.POINTER(C.POINTER(PkVadPiece)), C.POINTER(C.c_int)],
     "pk_model_set_input_rate": [C.c_void_p, C.c_int],
     "pk_model_get_input_rate": [C.c_void_p, C.POINTER(C.c_int)],
     "pk_group_set_input_rate": [C.c_void_p, C.c_int],
@@ -653,6 +669,73 @@ def resample_device_timed(clips, src_rate, dst_rate, reps=20, device=0):
     ms = np.zeros(1, np.float32)
     check(lib().pk_resample_device_timed(int(device), _f(pcm), off.ctypes.data_as(i64p), len(clips), int(src_rate), int(dst_rate), int(reps), _f(ms)))
     return float(ms[0])
+
+
+def vad_options(**options):
+    """pk_vad_options: the defaults of pk_vad_options_default with the given fields replaced"""
+    o = PkVadOptions()
+    lib().pk_vad_options_default.restype = None
+    lib().pk_vad_options_default(C.byref(o))
+    for k, v in options.items():
+        if k not in dict(PkVadOptions._fields_):
+            raise TypeError(f"no VAD option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def vad_run():
+    """pk_vad_run: frames one workgroup of the VAD kernels handles per pass"""
+    return lib().pk_vad_run()
+
+
+def _vad_pieces(ptr, n):
+    """a pk_vad_piece array (freed here) as a list of (clip, begin, end)"""
+    try:
+        return [(ptr[i].clip, ptr[i].begin, ptr[i].end) for i in range(n)]
+    finally:
+        lib().pk_free.argtypes = [C.c_void_p]
+        lib().pk_free(C.cast(ptr, C.c_void_p))
+
+
+def vad(clips, device=0, run_start=None, run_end=None, energy=None, **options):
+    """pk_vad_pcm: a list of 16 kHz clips (empty ones allowed) through the device VAD -> list of dicts with runs ([n][2] int32 frame ranges,
+    ends inclusive) and energy ([F] float32).  run_start / run_end / energy: the arrays the call works in (with their contents), for tests that
+    look at what the kernels leave alone; clip i's runs start at the sum of (F_j + 1) // 2 over the clips before it."""
+    pcm, off, n = _clips(clips)
+    F = [(int(off[i + 1] - off[i]) + 159) // 160 for i in range(n)]
+    cap = [(f + 1) // 2 for f in F]
+    rs = np.zeros(max(1, sum(cap)), np.int32) if run_start is None else run_start
+    re = np.zeros(max(1, sum(cap)), np.int32) if run_end is None else run_end
+    en = np.zeros(max(1, sum(F)), np.float32) if energy is None else energy
+    nr = np.zeros(n, np.int32)
+    o = vad_options(**options)
+    check(lib().pk_vad_pcm(int(device), _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), _i(nr), _i(rs), _i(re), _f(en)))
+    out, r0, f0 = [], 0, 0
+    for i in range(n):
+        out.append(dict(runs=np.stack([rs[r0:r0 + nr[i]], re[r0:r0 + nr[i]]], axis=1), energy=en[f0:f0 + F[i]].copy()))
+        r0 += cap[i]
+        f0 += F[i]
+    return out
+
+
+def vad_timed(clips, reps=20, device=0, **options):
+    """pk_vad_pcm_timed: median milliseconds of the VAD launches alone (hipEvents; the input is on the device)."""
+    pcm, off, n = _clips(clips)
+    ms = np.zeros(1, np.float32)
+    o = vad_options(**options)
+    check(lib().pk_vad_pcm_timed(int(device), _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(reps), _f(ms)))
+    return float(ms[0])
+
+
+def vad_plan(n_samples, runs, energy, **options):
+    """pk_vad_plan: the pieces of one clip from its runs ([n][2] frame ranges) and frame energies -> list of (begin, end) samples.  Host only."""
+    runs = np.ascontiguousarray(runs, np.int32).reshape(-1, 2)
+    rs, re = np.ascontiguousarray(runs[:, 0]), np.ascontiguousarray(runs[:, 1])
+    en = None if energy is None else np.ascontiguousarray(energy, np.float32)
+    o = vad_options(**options)
+    ptr, n = C.POINTER(PkVadPiece)(), C.c_int(0)
+    check(lib().pk_vad_plan(int(n_samples), _i(rs), _i(re), len(runs), None if en is None else _f(en), C.byref(o), C.byref(ptr), C.byref(n)))
+    return [(b, e) for _, b, e in _vad_pieces(ptr, n.value)]
 
 
 def read_audio(path, target_rate=16000):
@@ -2231,9 +2314,19 @@ class Model:
         rag, x, T = _enc_head(enc)
         return self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1]
 
-    def transcribe_pcm(self, clips, decoder="tdt", timestamps=False, boost_phrases=(), boost_score=5.0):
-        """pk_transcribe_pcm: Transcriber::transcribe (transcribe.hpp:91-180) on in-memory clips -> list of dicts."""
-        return _transcribe(lib().pk_transcribe_pcm, self._h, clips, decoder, timestamps, boost_phrases, boost_score)
+    def transcribe_pcm(self, clips, decoder="tdt", timestamps=False, boost_phrases=(), boost_score=5.0, vad=None):
+        """pk_transcribe_pcm: Transcriber::transcribe (transcribe.hpp:91-180) on in-memory clips -> list of dicts.
+        vad (True, or a dict of pk_vad_options fields): pk_transcribe_pcm_vad, the clips cut at their pauses and only the speech transcribed
+        -> (list of dicts, pieces as a list of (clip, begin, end) samples)."""
+        if vad is None or vad is False:
+            return _transcribe(lib().pk_transcribe_pcm, self._h, clips, decoder, timestamps, boost_phrases, boost_score)
+        vo = vad_options(**(vad if isinstance(vad, dict) else {}))
+        ptr, n = C.POINTER(PkVadPiece)(), C.c_int(0)
+
+        def fn(handle, pcm, off, n_clips, opt, res):
+            return lib().pk_transcribe_pcm_vad(handle, pcm, off, n_clips, opt, C.byref(vo), res, C.byref(ptr), C.byref(n))
+        res = _transcribe(fn, self._h, clips, decoder, timestamps, boost_phrases, boost_score)
+        return res, _vad_pieces(ptr, n.value)
 
     def ctc_beam_decode(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None, lm_beta=None):
         """pk_ctc_beam_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch) -> as ctc_beam_search.

@@ -686,6 +686,15 @@ static void store_tokens(Model &m, ResultStore &R, int c, int n, const int32_t *
 // Transcriber::transcribe (transcribe.hpp:99-179) of the clips listed in `clips` (global indices into offsets), results into the slots
 // of the same indices of R.  One model, one device; called by pk_transcribe_pcm (all clips) and by every rank of a pk_group.
 void pk::transcribe_clips(Model &m, const float *pcm, const int64_t *offsets, const std::vector<int> &clips, const pk_options *opt, ResultStore &R) {
+    int n = 0;
+    for (int c : clips) n = std::max(n, c + 1);
+    std::vector<ClipSpan> span(n);
+    for (int c : clips) span[c] = {pcm + offsets[c], offsets[c + 1] - offsets[c]};
+    transcribe_spans(m, span.data(), clips, opt, R);
+}
+
+// ... of clips that need not follow each other in memory: clip c is the span[c].n samples at span[c].p
+void pk::transcribe_spans(Model &m, const ClipSpan *span, const std::vector<int> &clips, const pk_options *opt, ResultStore &R) {
     m.require_gpu();
     const int decoder = opt ? opt->decoder : PK_DECODER_TDT;
     const bool ts = opt && opt->timestamps;
@@ -715,7 +724,7 @@ void pk::transcribe_clips(Model &m, const float *pcm, const int64_t *offsets, co
     const bool resampled = m.input_rate != kModelRate;
     std::vector<int64_t> clip_len(n_clips);
     for (int i = 0; i < n_clips; ++i) {
-        const int64_t raw = offsets[clips[i] + 1] - offsets[clips[i]];
+        const int64_t raw = span[clips[i]].n;
         clip_len[i] = resampled ? resample_length(raw, m.input_rate, kModelRate) : raw;
     }
     std::vector<int> order, bstart;                                // order: positions in `clips`, longest first; bstart: first position of every batch, + the end
@@ -763,9 +772,9 @@ void pk::transcribe_clips(Model &m, const float *pcm, const int64_t *offsets, co
             for (int i = 0; i < nc; ++i) blens[i] = len_of(c0 + i);
             if (resampled) {
                 braw.resize(nc);
-                for (int i = 0; i < nc; ++i) braw[i] = offsets[order[c0 + i] + 1] - offsets[order[c0 + i]];
+                for (int i = 0; i < nc; ++i) braw[i] = span[order[c0 + i]].n;
             }
-            batch_stage(b, nc, [&](int i) { return pcm + offsets[order[c0 + i]]; }, blens.data(), resampled ? braw.data() : nullptr);
+            batch_stage(b, nc, [&](int i) { return span[order[c0 + i]].p; }, blens.data(), resampled ? braw.data() : nullptr);
         };
         auto drain = [&]() {                                  // every finished run of this call that has not been handed out yet
             for (const auto &L : b->done) {
@@ -834,6 +843,42 @@ pk_result *pk::publish_store(ResultStorePtr store, int n_clips, bool ts) {
     pk_result *out = R.res.data();
     store.release();
     return out;
+}
+
+// pk_transcribe_pcm_vad behind its segmentation: the pieces (piece_clip ascending, time order inside a clip; piece_off = the piece's first
+// encoder frame in its clip) go through transcribe_spans as ordinary clips, and every clip's result is its pieces' results merged in that
+// order (the rule is the header's).  A piece of 256 samples or fewer is not transcribed.
+pk_result *pk::transcribe_pieces(Model &m, const std::vector<ClipSpan> &piece, const std::vector<int> &piece_clip, const std::vector<int> &piece_off,
+                                 int n_clips, const pk_options *opt) {
+    const bool ts = opt && opt->timestamps;
+    const int np = (int)piece.size();
+    auto parts = new_store(np);
+    std::vector<int> run;
+    for (int i = 0; i < np; ++i)
+        if (piece[i].n > 256) run.push_back(i);
+    transcribe_spans(m, piece.data(), run, opt, *parts);
+    ResultStore &P = *parts;
+    auto store = new_store(n_clips);
+    ResultStore &R = *store;
+    for (int i = 0; i < np; ++i) {
+        const int c = piece_clip[i], off = piece_off[i];
+        if (!P.text[i].empty()) { if (!R.text[c].empty()) R.text[c] += ' '; R.text[c] += P.text[i]; }
+        R.ids[c].insert(R.ids[c].end(), P.ids[i].begin(), P.ids[i].end());
+        for (int32_t v : P.start[i]) R.start[c].push_back(v + off);
+        for (int32_t v : P.end[i]) R.end[c].push_back(v + off);
+        R.conf[c].insert(R.conf[c].end(), P.conf[i].begin(), P.conf[i].end());
+        for (const auto &w : P.word_text[i]) R.word_text[c].push_back(w);
+    }
+    std::vector<size_t> nw(n_clips, 0);                            // (the words point at their strings: those are all in place first)
+    for (int i = 0; i < np; ++i) {
+        const int c = piece_clip[i];
+        const double shift = piece_off[i] * 0.08;
+        for (const pk_word &w : P.words[i]) {
+            R.words[c].push_back({R.word_text[c][nw[c]].c_str(), (float)((double)w.start + shift), (float)((double)w.end + shift), w.confidence});
+            ++nw[c];
+        }
+    }
+    return publish_store(std::move(store), n_clips, ts);
 }
 
 extern "C" {

@@ -74,5 +74,10 @@ using ResultStorePtr = std::unique_ptr<ResultStore, ResultStoreDelete>;
 ResultStorePtr new_store(int n_clips);
 void transcribe_clips(Model &m, const float *pcm, const int64_t *offsets, const std::vector<int> &clips, const pk_options *opt, ResultStore &R);
 pk_result *publish_store(ResultStorePtr store, int n_clips, bool ts);   // hands the store to the caller (pk_results_free)
+// ... of clips anywhere in host memory (span[c] for every c in `clips`), and of the pieces a segmentation cut n_clips clips into, merged per clip
+struct ClipSpan { const float *p = nullptr; int64_t n = 0; };
+void transcribe_spans(Model &m, const ClipSpan *span, const std::vector<int> &clips, const pk_options *opt, ResultStore &R);
+pk_result *transcribe_pieces(Model &m, const std::vector<ClipSpan> &piece, const std::vector<int> &piece_clip, const std::vector<int> &piece_off,
+                             int n_clips, const pk_options *opt);
 
 }  // namespace pk

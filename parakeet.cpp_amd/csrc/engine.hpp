@@ -21,6 +21,7 @@
 #include "tdt_align.hpp"
 #include "tdt_beam.hpp"
 #include "tdt_total.hpp"
+#include "vad.hpp"
 #include "text.hpp"
 
 namespace pk {
@@ -212,6 +213,7 @@ class Model {
     int input_rate = kModelRate;
     void set_input_rate(int rate) { resample_check_rates(rate, kModelRate); input_rate = rate; }
     ResampleWs rs;
+    VadWs vad;                              // scratch of the voice-activity segmentation in front of pk_transcribe_pcm_vad (vad.hpp)
 
     // stage drivers (device pointers, enqueue on `s`, never synchronise)
     void run_mel(const float *d_pcm, int B, int64_t n_samples, float *d_logmel, float *d_feats, hipStream_t s, const RagDev *rv = nullptr);

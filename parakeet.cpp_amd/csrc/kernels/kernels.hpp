@@ -776,4 +776,30 @@ struct ResampleArgs {
 };
 void launch_resample(const ResampleArgs &a, hipStream_t s);
 
+// ---- voice-activity segmentation of 16 kHz PCM (kernels/vad.hip) ------------------------------------------------
+// One set of launches over a packed ragged batch.  A clip of n samples has F = ceil(n / 160) frames, cut into chunks of kVadRun frames; chunk
+// k of the launch belongs to the last clip whose chunk0 <= k (clips without frames own none).  Every per-frame array (energy, flags) is packed
+// clip after clip at frame_off, every per-chunk array at chunk0; the staged PCM of a clip starts at in_off, a multiple of 32 floats (128 bytes).
+constexpr int kVadThreads = 256;
+constexpr int kVadFrame = 160;                  // samples per frame (10 ms)
+constexpr int kVadRun = 256;                    // frames of one chunk: what one workgroup handles per pass (pk_vad_run)
+constexpr int kVadGrid = 8;                     // run starts are multiples of the encoder's 8-frame grid
+struct VadClip { int64_t in_off, n; int32_t F, rank; int64_t frame_off, chunk0, run_off; };   // rank: of the floor among the clip's keys; run_off: its first run slot
+struct VadSelect { uint32_t prefix, rank; };    // the radix select's state of one clip: key bits found so far, rank among the keys sharing them
+struct VadArgs {
+    const float *x;                             // staged PCM
+    const VadClip *clip; int n_clips;
+    int64_t n_chunks;                           // chunks of the launch: sum of ceil(F / kVadRun)
+    float *energy;                              // [sum F]
+    uint32_t *hist;                             // [n_clips][4][256], zero before the launches
+    VadSelect *sel;                             // [n_clips]
+    uint8_t *flag[2];                           // [sum F] each, ping-pong between the smoothing passes
+    int32_t *first[2], *last[2];                // [n_chunks] each: first / last flagged frame of a chunk (clip-relative; F / -1 when none)
+    int32_t *n_start, *n_end;                   // [n_chunks]: run starts / run ends inside a chunk
+    int32_t *run_start, *run_end, *n_runs;      // [sum (F + 1) / 2] x 2, [n_clips] (zero before the launches)
+    float abs_thr, ratio;
+    int min_speech, min_silence, pad;           // frames
+};
+void launch_vad(const VadArgs &a, hipStream_t s);
+
 }  // namespace pk

@@ -4,7 +4,9 @@
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K] [--beam-head ctc|tdt]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
 //                [--spot "phrase"]... [--spot-file path.txt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
-//                [--device-resample]
+//                [--device-resample] [--vad [--vad-max-piece S]]
+// New: --vad (tdt-ctc-110m, tdt-600m; 16 kHz) cuts the file at its pauses on the device and transcribes only the speech, in pieces of at most
+// S seconds (--vad-max-piece S, default 30) that share batches (TranscribeOptions::vad): for long or sparse recordings.
 // New: --device-resample (tdt-ctc-110m, tdt-600m) reads the file at its own sample rate and resamples it to 16 kHz on the device, inside the call
 // (Transcriber::set_device_resampling), instead of on the host while the file is read.
 // New: --beam W (with --ctc / --decoder ctc, tdt-ctc-110m) runs the CTC prefix beam search and prints the N best hypotheses with scores.
@@ -50,6 +52,7 @@ static void usage(const char *prog) {
               << "  --beam W --beam-head tdt --lm file.arpa [--lm-alpha A] [--lm-beta B]  the TDT beam search fused with the model; both scores per hypothesis\n"
               << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold)\n"
               << "  --device-resample  resample files that are not 16 kHz on the device instead of on the host (tdt-ctc-110m, tdt-600m)\n"
+              << "  --vad [--vad-max-piece S]  transcribe only the speech, cut at the pauses into pieces of at most S seconds (default 30)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
 }
@@ -140,7 +143,8 @@ int main(int argc, char **argv) {
         float rescore_w = 0.5f;
         std::vector<std::string> boost, spot;
         SpotOptions spot_opts;
-        float boost_score = 5.0f;
+        float boost_score = 5.0f, vad_max_piece = 30.0f;
+        bool vad = false;
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
             if (a == "--model" && i + 1 < argc) model = argv[++i];
@@ -189,6 +193,8 @@ int main(int argc, char **argv) {
             else if (a == "--lm-alpha" && i + 1 < argc) lm_opts.alpha = std::stof(argv[++i]);
             else if (a == "--lm-beta" && i + 1 < argc) lm_opts.beta = std::stof(argv[++i]);
             else if (a == "--device-resample") device_resample = true;
+            else if (a == "--vad") vad = true;
+            else if (a == "--vad-max-piece" && i + 1 < argc) vad_max_piece = std::stof(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
             else if (a == "--latency" && i + 1 < argc) latency = std::stoi(argv[++i]);
@@ -204,6 +210,10 @@ int main(int argc, char **argv) {
         opts.timestamps = timestamps;
         opts.boost_phrases = boost;
         opts.boost_score = boost_score;
+        opts.vad = vad;
+        opts.vad_max_piece_s = vad_max_piece;
+        if (vad && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --vad needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
+        if (vad && device_resample) { std::cerr << "Error: --vad works on 16 kHz audio; it does not combine with --device-resample\n"; return 1; }
         if (align && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --align needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (align && vocab.empty()) { std::cerr << "Error: --align needs --vocab\n"; return 1; }
         if (score && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --score needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }

@@ -150,6 +150,10 @@ struct TranscribeOptions {
     bool timestamps = false;
     std::vector<std::string> boost_phrases;   // ContextTrie::build of these phrases biases the greedy argmax (phrase_boost.hpp)
     float boost_score = 5.0f;
+    // New: cut the audio at its pauses on the device and transcribe only the speech, in pieces of at most vad_max_piece_s seconds that share
+    // batches (pk_transcribe_pcm_vad); for long or sparse recordings.  Single device, 16 kHz.
+    bool vad = false;
+    float vad_max_piece_s = 30.0f;
 };
 
 namespace detail {
@@ -220,7 +224,13 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         o.n_boost_phrases = (int32_t)phrases.size();
         o.boost_score = opts.boost_score;
         pk_result *res = nullptr;
-        if (g_) check(pk_group_transcribe_pcm(g_, pcm.data(), offsets.data(), (int)clips.size(), &o, &res));
+        if (opts.vad) {
+            if (g_) throw std::runtime_error("TranscribeOptions::vad has no multi-GPU variant");
+            pk_vad_options vo;
+            pk_vad_options_default(&vo);
+            vo.max_piece_s = opts.vad_max_piece_s;
+            check(pk_transcribe_pcm_vad(m_, pcm.data(), offsets.data(), (int)clips.size(), &o, &vo, &res, nullptr, nullptr));
+        } else if (g_) check(pk_group_transcribe_pcm(g_, pcm.data(), offsets.data(), (int)clips.size(), &o, &res));
         else check(pk_transcribe_pcm(m_, pcm.data(), offsets.data(), (int)clips.size(), &o, &res));
         std::vector<TranscribeResult> out(clips.size());
         for (size_t i = 0; i < clips.size(); ++i) convert(res[i], opts.timestamps, out[i]);
