@@ -1025,6 +1025,14 @@ pk_status pk_diag_sum64(const float *x, int rows, int n, float *out);
 #define PK_DIAG_ATTENTION_GUARD_ROWS 128
 pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int pos_T,
                                    const float *bias_u, const float *bias_v, float *ctx, int *variant);
+/* The fp32 kernel of pk_diag_relpos_attention with the kernel form chosen by the caller: form 0 = the one the encoder would run, 1 = the block
+ * form (32 query rows per workgroup, the score block in LDS), 2 = the strip form (one wave per 16 query rows, the scores in registers; head size
+ * 32 / 64, longest sequence <= 128 frames).  A form that does not cover the shape is PK_ERR_UNSUPPORTED, never another kernel.  out_mode: 0 fp32
+ * ctx, 1 ctx rounded to bf16 with the fast exp / reciprocal of the bf16 mode (widened here, unwritten 0x7FC50000), 2 fp32 ctx in the sigma column
+ * layout.  pos may be NULL (bias_u / bias_v / pos_T ignored): scores are the scaled content term only.  Everything else as above.
+ * form_ran (may be NULL): 1 or 2. */
+pk_status pk_diag_relpos_attention_form(int form, int out_mode, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv,
+                                        const float *pos, int pos_T, const float *bias_u, const float *bias_v, float *ctx, int *form_ran);
 /* One limited-context attention layer alone on the band kernel the encoder runs in local mode (kernels/attention_local.hip): query row i of an
  * utterance attends to keys [max(0, i - left), min(T - 1, i + right)] (left, right >= 0).  qkv, bias_u, bias_v, B, lens, T as for
  * pk_diag_relpos_attention; pos [left + right + 1][d] is the LOCAL table, row r the projected position i - j = left - r.  out_mode 0: fp32 ctx,

@@ -287,6 +287,8 @@ _LATE_SIGNATURES = {
     "pk_diag_conv_instantiations": [i32p, C.c_int],
     "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
                                        C.POINTER(C.c_int)],
+    "pk_diag_relpos_attention_form": [C.c_int, C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, f32p, f32p,
+                                      C.POINTER(C.c_int)],
     "pk_diag_stream_attention": [C.c_int] * 6 + [f32p] * 4 + [C.c_int, f32p, f32p] + [C.c_int] * 5 + [f32p] * 3 + [C.POINTER(C.c_int)],
     "pk_diag_mel": [C.c_int] * 5 + [f32p, C.c_int, C.c_int64, i64p, f32p, C.c_int64, f32p, C.c_int64, i32p, i32p],
 }
@@ -1367,6 +1369,37 @@ def diag_relpos_attention(kernel, qkv, pos, bias_u, bias_v, n_heads, B=1, lens=N
     check(lib().pk_diag_relpos_attention({"fp32": 0, "bf16": 1}[kernel], B, lp, T, d, n_heads, _f(qkv), _f(pos), pos_T, _f(bu), _f(bv), _f(out),
                                          C.byref(var)))
     return out, var.value
+
+
+ATT_FORMS = {"default": 0, "block": 1, "strip": 2}          # kernels.hpp ATT_FORM_*
+ATT_OUT_MODES = {"fp32": 0, "bf16": 1, "sigma": 2}
+
+
+def diag_relpos_attention_form(form, qkv, pos, bias_u, bias_v, n_heads, B=1, lens=None, out_mode="fp32"):
+    """pk_diag_relpos_attention_form: the fp32 attention layer on the kernel form asked for ("default", "block", "strip"; PkError if the form
+    does not cover the shape).  Arguments as diag_relpos_attention; pos None: no position term; out_mode "fp32", "bf16" (widened) or "sigma"
+    (fp32, sigma columns) -> (ctx [rows + ATT_GUARD_ROWS][d] fp32 with the guard rows, the form that ran: "block" or "strip")."""
+    qkv = _c(qkv)
+    rows, d = qkv.shape[0], qkv.shape[1] // 3
+    assert qkv.shape[1] == 3 * d
+    if pos is not None:
+        pos, bu, bv = _c(pos), _c(bias_u), _c(bias_v)
+        pos_T = (pos.shape[0] + 1) // 2
+        assert pos.shape == (2 * pos_T - 1, d) and bu.shape == (d,) and bv.shape == (d,)
+    if lens is not None:
+        ln = np.ascontiguousarray(lens, np.int32)
+        assert int(ln.sum()) == rows
+        B, T, lp = len(ln), int(ln.max()), _i(ln)
+    else:
+        assert rows % B == 0
+        T, lp = rows // B, None
+    out = np.empty((rows + ATT_GUARD_ROWS, d), np.float32)
+    ran = C.c_int(-1)
+    none = C.cast(None, f32p)
+    check(lib().pk_diag_relpos_attention_form(ATT_FORMS[form], ATT_OUT_MODES[out_mode], B, lp, T, d, n_heads, _f(qkv),
+                                              none if pos is None else _f(pos), 0 if pos is None else pos_T,
+                                              none if pos is None else _f(bu), none if pos is None else _f(bv), _f(out), C.byref(ran)))
+    return out, {1: "block", 2: "strip"}[ran.value]
 
 
 STREAM_ATT_FORMS = ("general-1w", "general-2w", "tiles-hd64", "tiles-hd128")   # PK_DIAG_STREAM_ATT_*

@@ -1258,6 +1258,50 @@ pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T
     });
 }
 
+// The fp32 attention layer with the kernel form chosen by the caller (kernels.hpp ATT_FORM_*), any of the three ctx layouts, with or without
+// the position term: what the strip form is held against the block form with.
+pk_status pk_diag_relpos_attention_form(int form, int out_mode, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos,
+                                        int pos_T, const float *bias_u, const float *bias_v, float *ctx, int *form_ran) {
+    return guard([&] {
+        need(form == ATT_FORM_AUTO || form == ATT_FORM_BLOCK || form == ATT_FORM_STRIP, "form must be 0 (default), 1 (block) or 2 (strip)");
+        need(out_mode >= 0 && out_mode <= 2, "out_mode must be 0 (fp32), 1 (bf16) or 2 (fp32, sigma columns)");
+        need(qkv && ctx && B > 0 && d > 0 && n_heads > 0 && d % n_heads == 0, "qkv/ctx/B/d/n_heads");
+        need(!pos || (bias_u && bias_v), "pos needs bias_u and bias_v");
+        const int hd = d / n_heads;
+        const int64_t rows = att_extents(lens, B, T);
+        need(T > 0 && (!pos || pos_T >= T), "T > 0 and pos_T >= T (ragged: >= max(lens))");
+        need(relpos_attention_lds_bytes(T, hd) > 0, "fp32 kernel: hd 32, 64, 96 or 128");
+        need(out_mode != 2 || d % 16 == 0, "sigma columns: d must be a multiple of 16");
+        const bool long_seq = relpos_attention_lds_bytes(T, hd) > 160 * 1024;
+        const int ran = relpos_attention_form(T, hd, long_seq, form);
+        if (ran < 0) fail(PK_ERR_UNSUPPORTED, "the strip form covers head sizes 32 and 64 up to 128 frames (got hd %d, T %d)", hd, T);
+        need_device();
+        const int64_t Ptab = 2 * (int64_t)pos_T - 1, n_ctx = (rows + PK_DIAG_ATTENTION_GUARD_ROWS) * d;
+        RagBatch r;
+        DevBuf rag_img, q, p, bu, bv, out, scratch;
+        const SeqRag rag = att_rag(r, rag_img, lens, B, 32, pos ? pos_T : T);
+        const std::vector<float> qs = att_sigma(qkv, rows, 3 * d, 2 * d);
+        up(q, qs.data(), qs.size() * 4);
+        if (pos) {
+            const std::vector<float> ps = att_sigma(pos, Ptab, d, d);
+            up(p, ps.data(), ps.size() * 4);
+            up(bu, bias_u, (size_t)d * 4);
+            up(bv, bias_v, (size_t)d * 4);
+        }
+        out.reserve((size_t)n_ctx * (out_mode == 1 ? 2 : 4));
+        if (out_mode == 1) PK_HIP(hipMemsetD16(out.p, 0x7fc5, (size_t)n_ctx));
+        else PK_HIP(hipMemsetD32(out.p, 0x7fc5a5a5, (size_t)n_ctx));
+        if (long_seq) scratch.reserve(lens ? relpos_attention_scratch_bytes_units(r.n_u_att, T, n_heads, hd) : relpos_attention_scratch_bytes(B, T, n_heads, hd));
+        launch_relpos_attention(q.as<float>(), B, T, d, n_heads, pos ? p.as<float>() : nullptr, pos ? bu.as<float>() : nullptr,
+                                pos ? bv.as<float>() : nullptr, out.as<float>(), nullptr, 0.0f, long_seq ? scratch.as<float>() : nullptr, out_mode,
+                                pos ? pos_T - T : 0, rag, form);
+        PK_CHECK_LAUNCH();
+        if (out_mode == 1) down16(ctx, out, (size_t)n_ctx);
+        else down(ctx, out, (size_t)n_ctx * 4);
+        if (form_ran) *form_ran = ran;
+    });
+}
+
 // One limited-context attention layer alone on the band kernel (kernels/attention_local.hip), launched as run_layers launches it in local mode.
 pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
                                          const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant) {

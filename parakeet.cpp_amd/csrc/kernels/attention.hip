@@ -356,6 +356,292 @@ __global__ __launch_bounds__(256, OCC) void relpos_attention_kernel(const float 
     ATT_STAMP(7);                                                   // V commit, barrier, AV, store
 }
 
+// ---- the "strip" form: T <= 128, the scores never leave the registers until they are probabilities --------------------------------------------
+// The kernel above touches every score in LDS nine times (content store, the shifted read-modify-write, three softmax sweeps, the AV read) and
+// needs two workgroup barriers only because two waves share a row strip.  Here ONE wave owns 16 query rows x all (<= 128) key columns:
+//   * the eight 16x16 content tiles are eight accumulator quads, strip[t] (32 VGPRs), each its own natural-k chain from zero: the same bits;
+//   * rel_shift is a fixed skew inside a tile.  The wave's position tile grid starts at wpmin = T - 1 - (i_s + 15), so element (row m, column c) of
+//     content tile t is element (row m, column (c - m - 1) & 15) of position tile t when c <= m and of tile t + 1 otherwise: the same register r of
+//     the same 16-lane group (C layout: row = 4 kq + r, column = lane & 15).  The SOURCE lane picks the tile (column s serves tile t when
+//     s >= 15 - m), one ds_bpermute_b32 per register rotates the row group by m + 1;
+//   * softmax in registers, in the summation tree of the kernel above: virtual lane v = j & 63 holds e[v] + e[v + 64] = strip[q] + strip[q + 4]
+//     (q = v >> 4; absent columns +0.0), the xor-32 / xor-16 stages are the register adds [q] + [q ^ 2], [q] + [q ^ 1], xor 8 .. 1 run across the
+//     16 lanes of the group; the maximum is order-independent; IEEE divide per element;
+//   * the probabilities go ONCE into a wave-private k-planar LDS region (PW columns at a time) and come back as the A operand of the AV chains
+//     (one ds_read_b128 per four k-steps): the wave's own LDS traffic is in order, no barrier.  V is staged per workgroup as above.
+// The only workgroup barriers left are those of the V chunks.  NW waves = 16 NW query rows per workgroup; the ragged form keeps the engine's
+// 32-row units (NW = 2).
+#ifdef ATT_TRACE
+#define ATT_STAMP_S(i) do { if (att_trace && (threadIdx.x & 63) == 0) att_trace[((long long)blockIdx.x * NW + (threadIdx.x >> 6)) * 8 + (i)] = clock64(); } while (0)
+#else
+#define ATT_STAMP_S(i) do { } while (0)
+#endif
+static constexpr int STRIP_T = 128;   // longest sequence of the strip form
+
+template <int HD, int VCH, int NW, int PW, bool RAG, int OCC>
+__global__ __launch_bounds__(64 * NW, OCC) void relpos_attention_strip_kernel(const float *__restrict__ qkv, int ldq, int d, int T,
+                                                                            const float *__restrict__ pos /*[2T-1][d], sigma columns*/,
+                                                                            const float *__restrict__ bias_u, const float *__restrict__ bias_v,
+                                                                            float scale, float *__restrict__ ctx, int n_rb, int n_bh, int ctx_bf16,
+                                                                            int pos_row0, SeqRag rg) {
+    __builtin_amdgcn_s_setprio(3);
+    constexpr int NT = 64 * NW, RBS = 16 * NW;
+    constexpr int KQ = HD / 4, NQ4 = HD / 16, VPIT = HD + 16, NDV = HD / 16, NLV = VCH * KQ / NT;
+    constexpr int NCT = STRIP_T / 16;                               // key tiles of a strip
+    constexpr int PPIT = PW / 4 + 4, PPLANE = 16 * PPIT + 4;        // probabilities: [4 planes][16 rows][PW / 4]; rows 16, planes 4 banks apart
+    static_assert((VCH * KQ) % NT == 0 && VCH % 16 == 0 && PW % VCH == 0 && STRIP_T % PW == 0, "V chunks tile a probability piece, pieces tile the strip");
+    static_assert(!RAG || NW == 2, "the units of a ragged batch are 32-row blocks");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int H = d / HD;
+    int h, i0;
+    int64_t row0;
+    if constexpr (RAG) {
+        const int id = blockIdx.x, xcd = id & 7, k = id >> 3;
+        h = (k / rg.units.count) * 8 + xcd;
+        if (h >= H) return;
+        const RagUnit un = rg.units.u[k % rg.units.count];
+        i0 = un.r0;
+        T = rg.T[un.b];
+        row0 = rg.T_off[un.b];
+        pos_row0 = rg.pos_T - T;
+    } else {
+        const int id = blockIdx.x, xcd = id & 7, k = id >> 3;           // the row blocks of one (utterance, head) on one XCD, as above
+        const int rbk = k % n_rb, bh = (k / n_rb) * 8 + xcd;
+        if (bh >= n_bh) return;                                      // padding slot of the grid (whole workgroup, before any barrier)
+        h = bh % H;
+        i0 = rbk * RBS;
+        row0 = (int64_t)(bh / H) * T;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l15 = lane & 15, kq = lane >> 4;
+    const int i_s = i0 + wave * 16;                                 // first query row of this wave's strip
+    const bool active = i_s < T;                                    // a strip wholly past T only helps to stage V
+    const int P = 2 * T - 1;
+    const int nct = (T + 15) / 16;
+    const float *qb = qkv + row0 * ldq + h * HD;
+    const float *kb = qb + d, *vb = qb + 2 * d;
+    const float *pb = pos + (int64_t)pos_row0 * d + h * HD;
+    float *VS = smem;                                               // [VCH][VPIT] V chunk
+    float *PS = smem + VCH * VPIT + wave * 4 * PPLANE;              // this wave's probabilities
+
+    float4 vf[NLV];
+    auto v_issue = [&](int vrow0) {
+#pragma unroll
+        for (int i = 0; i < NLV; ++i) {
+            const int e = tid + NT * i, gr = vrow0 + e / KQ;
+            vf[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (gr < T) vf[i] = *reinterpret_cast<const float4 *>(vb + (int64_t)gr * ldq + 4 * (e % KQ));
+        }
+    };
+    auto v_commit = [&]() {
+#pragma unroll
+        for (int i = 0; i < NLV; ++i) {
+            const int e = tid + NT * i;
+            lds_store16(VS + (e / KQ) * VPIT + 4 * (e % KQ), vf[i]);
+        }
+    };
+    auto load_tile = [&](const float *base, int64_t ld, int trow0, int limit, float4 (&f)[NQ4]) {
+        const int r = trow0 + l15;
+        const bool ok = r >= 0 && r < limit;
+        const float *p = base + (int64_t)(ok ? r : 0) * ld + 4 * kq;
+#pragma unroll
+        for (int q = 0; q < NQ4; ++q) f[q] = ok ? *reinterpret_cast<const float4 *>(p + 16 * q) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    };
+    // one 16x16 accumulator chain over K = HD from zero, the natural k order of mma_pair
+    auto mma_one = [&](const float4 (&a)[NQ4], const float4 (&b)[NQ4], f32x4 &c) {
+        c = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int q = 0; q < NQ4; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(a[q], e), f4e(b[q], e), c, 0, 0, 0);
+    };
+    float4 qx[NQ4];
+    auto load_q_biased = [&](const float *bias) {
+        load_tile(qb, ldq, i_s, T, qx);
+        if (pos) {
+            const float *br = bias + h * HD + kq;
+#pragma unroll
+            for (int f = 0; f < NQ4; ++f)
+                qx[f] = make_float4(qx[f].x + br[16 * f], qx[f].y + br[16 * f + 4], qx[f].z + br[16 * f + 8], qx[f].w + br[16 * f + 12]);
+        }
+    };
+    ATT_STAMP_S(0);
+    f32x4 st[NCT];                                                  // the strip: tile t, register r <-> row 4 kq + r, column 16 t + l15
+#pragma unroll
+    for (int t = 0; t < NCT; ++t) st[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (active) {
+        float4 bA[NQ4], bB[NQ4];                                    // one operand tile computing, one in flight
+        load_q_biased(bias_u);
+        ATT_STAMP_S(1);                                             // Q load + bias
+        // ---- content scores (q+u) K^T ----
+        load_tile(kb, ldq, 0, T, bA);
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) {
+            // (all NCT tiles, straight-line: a tile past T loads nothing and multiplies zeros.  Branching on nct costs registers across the
+            //  blocks -- spills at the 128 VGPRs of four workgroups per CU)
+            if (t + 1 < NCT) load_tile(kb, ldq, (t + 1) * 16, T, (t & 1) ? bA : bB);
+            mma_one(qx, (t & 1) ? bB : bA, st[t]);
+            __builtin_amdgcn_sched_barrier(0);                       // one tile ahead, no further
+        }
+        ATT_STAMP_S(2);                                             // QK^T
+        // ---- position scores (q+v) P^T, skewed into place, combined, scaled; columns >= T zero (the pad of the AV chain, +0.0 in the row sum) ----
+        if (pos) {
+            load_q_biased(bias_v);
+            const int wpmin = T - 1 - (i_s + 15);                    // may be negative: rows outside [0, P) load as zeros and are never selected
+            f32x4 pprev = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, pcur;
+            load_tile(pb, d, wpmin, P, bA);
+#pragma unroll
+            for (int u = 0; u <= NCT; ++u) {
+                if (u + 1 <= NCT) load_tile(pb, d, wpmin + (u + 1) * 16, P, (u & 1) ? bA : bB);
+                mma_one(qx, (u & 1) ? bB : bA, pcur);
+                if (u >= 1) {
+                    const int t = u - 1, j = t * 16 + l15;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int m = 4 * kq + r;
+                        const float x = l15 >= 15 - m ? pprev[r] : pcur[r];
+                        const int sl = ((lane & 48) | ((l15 - m - 1) & 15)) << 2;              // source lane: same 16-lane group, column (c - m - 1) & 15
+                        const float a = __int_as_float(__builtin_amdgcn_ds_bpermute(sl, __float_as_int(x)));
+                        st[t][r] = j < T ? (st[t][r] + a) * scale : 0.0f;                      // (content + pos) * scale, src/encoder.cpp:157-160
+                    }
+                }
+                pprev = pcur;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                const int j = t * 16 + l15;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) st[t][r] = j < T ? st[t][r] * scale : 0.0f;
+            }
+        }
+        ATT_STAMP_S(3);                                             // QP^T, skew, combine
+    } else {
+        ATT_STAMP_S(1); ATT_STAMP_S(2); ATT_STAMP_S(3);
+    }
+    v_issue(0);                                                   // first V chunk: in flight across the softmax (the score passes have no registers to spare)
+    if (active) {
+        // ---- softmax in registers (rows past T hold finite values and are never stored) ----
+        float mx[4], sm[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            mx[r] = -__builtin_huge_valf();
+#pragma unroll
+            for (int t = 0; t < NCT; ++t)
+                if (t * 16 + l15 < T) mx[r] = fmaxf(mx[r], st[t][r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], wave_xor<8>(mx[r]));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], wave_xor<4>(mx[r]));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], wave_xor<2>(mx[r]));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], wave_xor<1>(mx[r]));
+#pragma unroll
+        for (int t = 0; t < NCT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float x = st[t][r] - mx[r];
+                const float e = ctx_bf16 == 1 ? __builtin_amdgcn_exp2f(x * 1.44269502162933349609375f) : dexpf_nonpos(x);
+                st[t][r] = t * 16 + l15 < T ? e : 0.0f;
+            }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float s0 = st[0][r] + st[4][r], s1 = st[1][r] + st[5][r], s2 = st[2][r] + st[6][r], s3 = st[3][r] + st[7][r];   // j = v, then v + 64
+            const float t0 = s0 + s2, t1 = s1 + s3;                  // xor 32
+            sm[r] = t0 + t1;                                         // xor 16
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sm[r] = sm[r] + wave_xor<8>(sm[r]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sm[r] = sm[r] + wave_xor<4>(sm[r]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sm[r] = sm[r] + wave_xor<2>(sm[r]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sm[r] = sm[r] + wave_xor<1>(sm[r]);
+        if (ctx_bf16 == 1) {                                         // bf16 mode: one hardware reciprocal per row, a multiplication per element
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sm[r] = __builtin_amdgcn_rcpf(sm[r]);
+#pragma unroll
+            for (int t = 0; t < NCT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) st[t][r] = st[t][r] * sm[r];
+        } else {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) st[t][r] = st[t][r] / sm[r];
+        }
+    }
+    ATT_STAMP_S(4);                                                 // softmax
+    v_commit();
+    lds_store_fence();
+    __syncthreads();
+    ATT_STAMP_S(5);                                                 // V commit, barrier
+    // ---- ctx = softmax(S) V: NDV 16-column tiles per wave, natural key order ----
+    f32x4 acc[NDV];
+#pragma unroll
+    for (int m = 0; m < NDV; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    const float *vrow = VS + kq * VPIT + l15;                       // B: V[4s + kq - c0r][16 m + l15]
+#pragma unroll
+    for (int c = 0; c < STRIP_T / VCH; ++c) {
+        const int c0r = c * VCH;
+        if (c0r < T) {
+            const bool more = c0r + VCH < T;
+            if (more) v_issue(c0r + VCH);
+            if (active) {
+                if (c0r % PW == 0) {                                 // the next PW columns of probabilities -> this wave's k-planar region
+#pragma unroll
+                    for (int tt = 0; tt < PW / 16; ++tt) {
+                        const int t = c0r / 16 + tt;
+                        if (t < nct) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) PS[(l15 & 3) * PPLANE + (4 * kq + r) * PPIT + 4 * tt + (l15 >> 2)] = st[t][r];
+                        }
+                    }
+                    lds_store_fence();                               // wave-private: the wave's own stores, then its own reads
+                }
+                const int s_end = ((T - c0r < VCH ? T - c0r : VCH) + 3) / 4;
+                const float *sa = PS + kq * PPLANE + l15 * PPIT + (c0r % PW) / 4;    // A: row l15, k = 4s + kq at float s
+                for (int s4 = 0; s4 < s_end; s4 += 4) {
+                    const float4 a = *reinterpret_cast<const float4 *>(sa + s4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (s4 + e < s_end) {
+#pragma unroll
+                            for (int m = 0; m < NDV; ++m)
+                                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(a, e), vrow[(s4 + e) * 4 * VPIT + m * 16], acc[m], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            if (more) {
+                __syncthreads();
+                v_commit();
+                lds_store_fence();
+                __syncthreads();
+            }
+        }
+    }
+    ATT_STAMP_S(6);                                                 // P write, AV
+#pragma unroll
+    for (int m = 0; m < NDV; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i_s + 4 * kq + r;
+            if (i < T) {
+                const int64_t orow = (row0 + i) * d;
+                const int col = h * HD + m * 16 + l15;
+                if (ctx_bf16 == 1) reinterpret_cast<__bf16 *>(ctx)[orow + col] = (__bf16)acc[m][r];
+                else if (ctx_bf16 == 2) ctx[orow + ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3))] = acc[m][r];
+                else ctx[orow + col] = acc[m][r];
+            }
+        }
+    ATT_STAMP_S(7);                                                 // store
+}
+
 template <int HD, int VCH, int OCC = (HD <= 64 ? ATT_OCC : 2)>
 static void launch_att(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u, const float *bias_v,
                        float *ctx, float scale_arg, hipStream_t s, float *scratch, int ctx_bf16, int pos_row0, const SeqRag &rag) {
@@ -425,9 +711,61 @@ int relpos_attention_max_frames(int hd) {
     return T;
 }
 
+// The strip form's shape (tools/ubench/attn_bench sweeps them with -D): waves per workgroup of the uniform form, V chunk rows, columns of
+// probabilities handed to the AV chains at a time.  4 / 32 / 64: 31 KB of LDS per workgroup, four workgroups per CU.
+#ifndef ATT_STRIP_NW
+#define ATT_STRIP_NW 4
+#endif
+#ifndef ATT_STRIP_VCH
+#define ATT_STRIP_VCH 32
+#endif
+#ifndef ATT_STRIP_PW
+#define ATT_STRIP_PW 64
+#endif
+#ifndef ATT_STRIP_DEFAULT
+#define ATT_STRIP_DEFAULT 1       // 1: launches the strip form covers take it; 0: only on request (ATT_FORM_STRIP)
+#endif
+
+// Which kernel a launch runs: every threshold of the choice lives here (the launcher switches on it, pk_diag_relpos_attention_form reports
+// it).  t_longest: T of a uniform batch, the longest utterance of a ragged one.  -1: the form asked for does not cover the launch.
+int relpos_attention_form(int t_longest, int hd, bool scratch, int want) {
+    const bool strip_ok = !scratch && t_longest >= 1 && t_longest <= STRIP_T && (hd == 64 || hd == 32);
+    if (want == ATT_FORM_STRIP) return strip_ok ? ATT_FORM_STRIP : -1;
+    if (want == ATT_FORM_BLOCK) return ATT_FORM_BLOCK;
+    return (ATT_STRIP_DEFAULT && strip_ok) ? ATT_FORM_STRIP : ATT_FORM_BLOCK;
+}
+
+template <int HD>
+static void launch_att_strip(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u, const float *bias_v,
+                             float *ctx, float scale_arg, hipStream_t s, int ctx_bf16, int pos_row0, const SeqRag &rag) {
+    const float scale = scale_arg > 0.0f ? scale_arg : 1.0f / sqrtf((float)HD);
+    constexpr int VCH = ATT_STRIP_VCH, PW = ATT_STRIP_PW, NW = ATT_STRIP_NW;
+    auto lds_bytes = [](int nw) { return (size_t)(VCH * (HD + 16) + nw * 4 * (16 * (PW / 4 + 4) + 4)) * sizeof(float); };
+    if (rag.units.u) {                                              // the engine's units are 32-row blocks: two strips per workgroup
+        const dim3 grid((unsigned)(((n_heads + 7) / 8) * 8 * (int64_t)rag.units.count));
+        static DynLdsSlots slots_r;
+        ensure_dyn_lds(slots_r, reinterpret_cast<const void *>(&relpos_attention_strip_kernel<HD, VCH, 2, PW, true, 4>), lds_bytes(2));
+        hipLaunchKernelGGL((relpos_attention_strip_kernel<HD, VCH, 2, PW, true, 4>), grid, dim3(128), lds_bytes(2), s, qkv, 3 * d, d, rag.T_max, pos, bias_u, bias_v,
+                           scale, ctx, 0, 0, ctx_bf16, pos_row0, rag);
+        return;
+    }
+    const int n_rb = (T + 16 * NW - 1) / (16 * NW), n_bh = B * n_heads;
+    const dim3 grid(((n_bh + 7) / 8) * 8 * n_rb);
+    static DynLdsSlots slots;
+    ensure_dyn_lds(slots, reinterpret_cast<const void *>(&relpos_attention_strip_kernel<HD, VCH, NW, PW, false, 4>), lds_bytes(NW));
+    hipLaunchKernelGGL((relpos_attention_strip_kernel<HD, VCH, NW, PW, false, 4>), grid, dim3(64 * NW), lds_bytes(NW), s, qkv, 3 * d, d, T, pos, bias_u, bias_v,
+                       scale, ctx, n_rb, n_bh, ctx_bf16, pos_row0, rag);
+}
+
 void launch_relpos_attention(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u,
-                             const float *bias_v, float *ctx, hipStream_t s, float scale, float *scratch, int ctx_bf16, int pos_row0, const SeqRag &rag) {
+                             const float *bias_v, float *ctx, hipStream_t s, float scale, float *scratch, int ctx_bf16, int pos_row0, const SeqRag &rag,
+                             int form) {
     const int hd = d / n_heads;
+    if (relpos_attention_form(rag.units.u ? rag.T_max : T, hd, scratch != nullptr, form) == ATT_FORM_STRIP) {
+        if (hd == 64) launch_att_strip<64>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, ctx_bf16, pos_row0, rag);
+        else launch_att_strip<32>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, ctx_bf16, pos_row0, rag);
+        return;
+    }
     // V chunk rows: 64 keeps the footprint at ~39 KB for 10 s clips (4 workgroups per CU at hd = 64).  Between ~10.5 and ~16 s (T = 132 .. 200:
     // the longest clip of a mixed batch, 15 s uniform batches) the 64-row chunk costs the fourth resident workgroup; a 32-row chunk (two more
     // barriers per extra chunk, the same chains: same bits) keeps it

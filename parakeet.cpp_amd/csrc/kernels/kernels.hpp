@@ -398,7 +398,12 @@ size_t relpos_attention_scratch_bytes(int B, int T, int n_heads, int hd);   // l
 // utterance b attends over its own T[b] frames with table rows from rag.pos_T - T[b]; B / T / pos_row0 ignored, LDS sized by rag.T_max.
 void launch_relpos_attention(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u,
                              const float *bias_v, float *ctx, hipStream_t s, float scale = 0.0f, float *scratch = nullptr, int ctx_bf16 = 0,
-                             int pos_row0 = 0, const SeqRag &rag = SeqRag());
+                             int pos_row0 = 0, const SeqRag &rag = SeqRag(), int form = 0);
+// form: which fp32 kernel runs.  ATT_FORM_AUTO: relpos_attention_form decides; the other two ask for one (diagnostics, A/B).  The "strip" form
+// (one wave per 16 query rows, the scores in registers) covers hd 32 / 64 with the longest sequence of the launch <= 128 frames, LDS only.
+enum { ATT_FORM_AUTO = 0, ATT_FORM_BLOCK = 1, ATT_FORM_STRIP = 2 };
+// -> the form the launch takes (ATT_FORM_BLOCK / ATT_FORM_STRIP), or -1 when `want` does not cover it.  t_longest: T, or rag.T_max.
+int relpos_attention_form(int t_longest, int hd, bool scratch, int want);
 size_t relpos_attention_scratch_bytes_units(int64_t n_units, int T_max, int n_heads, int hd);   // ragged form of relpos_attention_scratch_bytes
 // Limited-context ("band") form, kernels/attention_local.hip: query row i attends to keys [max(0, i - left), min(T - 1, i + right)] only.
 // qkv as above (fp32, q / k sigma columns), pos = the layer's LOCAL table [left + right + 1][d] (sigma columns; row r = position i - j = left - r).
