@@ -1033,7 +1033,7 @@ pk_status pk_diag_relpos_attention(int kernel, int B, const int32_t *lens, int T
  * form_ran (may be NULL): 1 or 2. */
 pk_status pk_diag_relpos_attention_form(int form, int out_mode, int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv,
                                         const float *pos, int pos_T, const float *bias_u, const float *bias_v, float *ctx, int *form_ran);
-/* One limited-context attention layer alone on the band kernel the encoder runs in local mode (kernels/attention_local.hip): query row i of an
+/* One limited-context attention layer alone on the band kernel the encoder runs in local mode (kernels/attention.hip, BAND instantiation): query row i of an
  * utterance attends to keys [max(0, i - left), min(T - 1, i + right)] (left, right >= 0).  qkv, bias_u, bias_v, B, lens, T as for
  * pk_diag_relpos_attention; pos [left + right + 1][d] is the LOCAL table, row r the projected position i - j = left - r.  out_mode 0: fp32 ctx,
  * 1: ctx rounded to bf16 (the engine's gemm_bf16 mode; widened to fp32 here, unwritten pattern 0x7FC50000).  ctx: [rows +

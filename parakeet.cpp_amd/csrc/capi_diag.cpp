@@ -1302,7 +1302,7 @@ pk_status pk_diag_relpos_attention_form(int form, int out_mode, int B, const int
     });
 }
 
-// One limited-context attention layer alone on the band kernel (kernels/attention_local.hip), launched as run_layers launches it in local mode.
+// One limited-context attention layer alone on the band kernel (kernels/attention.hip, BAND instantiation), launched as run_layers launches it in local mode.
 pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
                                          const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant) {
     return guard([&] {

@@ -198,7 +198,7 @@ class Model {
     DevBuf att_scratch;         // score blocks of the attention kernel for sequences too long for LDS (grow-only)
     void ensure_pos_tables(int T, hipStream_t s);
     // Limited-context attention (pk_model_set_attention_context): query row i attends to keys [i - att_left, i + att_right] only, on the band
-    // kernel (kernels/attention_local.hip) with a per-layer LOCAL table of att_left + att_right + 1 rows.  (-1, -1): full attention (default).
+    // kernel (kernels/attention.hip, BAND instantiation) with a per-layer LOCAL table of att_left + att_right + 1 rows.  (-1, -1): full attention (default).
     // In local mode the 2T-1 tables are neither built nor grown, no attention scratch is reserved and attn_bf16() is false.
     int att_left = -1, att_right = -1;
     bool att_local() const { return att_left >= 0; }

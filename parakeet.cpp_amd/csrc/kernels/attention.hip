@@ -3,7 +3,7 @@
 // :85-109 applied in closed form):
 //     S[i][j] = ( (q_i + u_h) . k_j  +  (q_i + v_h) . P_h[j - i + T - 1] ) / sqrt(hd)
 //     ctx_i   = softmax_j(S[i][:]) V
-// One workgroup per (utterance, head, block of 32 query rows), 4 wavefronts.  All three contractions run on the
+// The "block" form: one workgroup per (utterance, head, block of 32 query rows), 4 wavefronts.  All three contractions run on the
 // fp32 MFMA v_mfma_f32_16x16x4_f32 (natural-k fma chains = the oracle's order); 16x16 tiles give every wave the same
 // number of tiles in each phase.
 //   * Q, K and the projected position table P arrive in the "sigma" column layout (the producing GEMMs write it: inside
@@ -19,323 +19,133 @@
 // (Round 2 also tried V as a straight-from-L2 B operand -- one dword per lane per MFMA step, a register block of 8 steps ahead: bit-equal,
 // no V copy in LDS and no chunk barriers, but the gathers are slower than the LDS copy: AV phase 10 k -> 23 k clocks per wave at T = 126,
 // 52 k -> 112 k at T = 376 / hd = 128.  Not kept.)
-#include "../pk_devmath.h"
-#include "kernels.hpp"
+//
+// The limited-context ("band") form is the SAME kernel, instantiated with BAND = true (launch_relpos_local_attention below):
+//     S[i][j] = ( (q_i + u_h) . k_j  +  (q_i + v_h) . Pl_h[j - i + left] ) / sqrt(hd)     for j in [max(0, i - left), min(T - 1, i + right)]
+//     ctx_i   = softmax_j(S[i][:]) V                                                        (keys outside the band: weight exactly 0)
+// Pl is the local position table [left + right + 1][d]: row r is the projected sinusoid of position i - j = left - r (engine.cpp:
+// ensure_local_pos_table), the same float formula as the full table, so a row is bit for bit the full table's row of that position.
+// Shared, literally (attention_dev.hpp): placement, operand loads, the content pass, the shifted pass, the softmax sweeps, the AV steps, the
+// ctx store -- all over the columns c of a key WINDOW [jlo, jhi], column c = key jlo + c.  What differs, under `if constexpr (BAND)`:
+//   * the window: the full form's is every key (jlo = 0, W = T, closed-form table rows wpmin / wpmax); the band form's is
+//     [i0 - left, i0 + 31 + right] clamped to the utterance, at most left + right + 32 columns whatever T is, the table rows clamped to Pl;
+//   * the table row the window starts at: the full form reads its table from pos_row0 (a ragged unit: rg.pos_T - T), the band form from row 0;
+//   * the softmax policy: every column (AttRowsFull) or each row's own band [clo, chi] (AttRowsBand; outside: exact zeros);
+//   * the band form has neither the global-scratch score planes (SG) nor the no-position mode (pos == nullptr).
+// So when the band covers the utterance (left, right >= T - 1) every score, every softmax sum and every ctx chain is the full form's, bit
+// for bit (tests/test_gpu_local_attention.py).
+#include "attention_dev.hpp"
 
 namespace pk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-static constexpr int RB = 32;   // query rows per workgroup
 #ifndef ATT_OCC
 #define ATT_OCC 4                 // workgroups per CU the hd <= 64 kernel is compiled for (register budget 168 / 128 VGPRs for 3 / 4)
 #endif
-
-// Phase stamps for tools/ubench/attn_bench.cpp (-DATT_TRACE): shader clock of lane 0 of every wave at the phase boundaries.  Production: nothing.
-#ifdef ATT_TRACE
-__device__ long long *att_trace;    // [workgroup][wave][8]
-#define ATT_STAMP(i) do { if (att_trace && (threadIdx.x & 63) == 0) att_trace[((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + (i)] = clock64(); } while (0)
-#else
-#define ATT_STAMP(i) do { } while (0)
-#endif
-
-__device__ __forceinline__ float f4e(const float4 &v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 
 // SG (long sequences, > ~85 s of audio): the score block of a workgroup lives in a global scratch area instead of LDS -- the same
 // code, indexing and barriers (a workgroup's own global writes are visible to it after __syncthreads()), so the same bits; slower,
 // but the length is then bounded by HBM, not by the 160 KB of LDS.
 // RAG: the ragged-batch form (per-unit utterance extents, kernels.hpp: SeqRag) is its own instantiation -- the uniform kernel sits exactly at
-// its 128-VGPR budget (four workgroups per CU) and must not carry a single extra live value (round 4: the shared form spilled 11 dwords per
-// lane instead of 4 and lost 2.5 %).
+// its 128-VGPR budget (four workgroups per CU) and must not carry a single extra live value (round 4: the shared form spilled more dwords per
+// lane and lost 2.5 %; today the hd 64 LDS builds at four workgroups per CU spill nothing uniform or in the band form and 4 dwords ragged; every
+// count: profiles/attention_phases_resources.md).
 // OCC: workgroups per CU the instantiation is register-budgeted for (128 / 168 / 256 VGPRs for 4 / 3 / 2).  The launcher picks the largest the
 // LDS footprint of the sequence length allows anyway: a 30 s utterance (T = 376: 71 KB of score planes + V chunk, two workgroups per CU)
 // gains nothing from the spills of the 128-VGPR build.
-template <int HD, int VCH, bool SG = false, bool RAG = false, int OCC = (HD <= 64 ? ATT_OCC : 2)>
+// BAND: the limited-context form (left / right; s_scratch and pos_row0 unused).  The full form ignores left / right.
+template <int HD, int VCH, bool SG = false, bool RAG = false, int OCC = (HD <= 64 ? ATT_OCC : 2), bool BAND = false>
 __global__ __launch_bounds__(256, OCC) void relpos_attention_kernel(const float *__restrict__ qkv, int ldq, int d, int T,
-                                                               const float *__restrict__ pos /*[2T-1][d], sigma columns*/,
+                                                               const float *__restrict__ pos /*[2T-1][d] (band: [left+right+1][d]), sigma columns*/,
                                                                const float *__restrict__ bias_u, const float *__restrict__ bias_v,
                                                                float scale, float *__restrict__ ctx, int PITS, int n_rb, int n_bh,
-                                                               float *__restrict__ s_scratch, int ctx_bf16, int pos_row0, SeqRag rg) {
+                                                               float *__restrict__ s_scratch, int ctx_bf16, int pos_row0, SeqRag rg, int left, int right) {
+    static_assert(!(BAND && SG), "the band form keeps its score block in LDS");
     __builtin_amdgcn_s_setprio(3);        // ahead of the overlapped decode-loop waves in the SIMD's arbitration (gemm_pipe.hpp)
-    constexpr int KQ = HD / 4;
     constexpr int NQ4 = HD / 16;          // float4 fragments per lane for K = HD (one per block of 16 features)
     constexpr int VPIT = HD + 16;         // V rows, natural layout (pitch = 16 mod 32 banks)
     constexpr int NDV = HD / 32;          // 16-wide ctx column tiles per wave (HD/16 tiles over 2 column parities)
-    constexpr int NLV = VCH * KQ / 256;   // float4 loads per thread for one V chunk
-    static_assert((VCH * KQ) % 256 == 0 && VCH % 4 == 0, "V chunk must split evenly over 256 threads");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int SPLANE = RB * PITS + 8;     // +8: the four planes start 8 banks apart (conflict-free row sweeps)
-    float *S = SG ? s_scratch + (size_t)blockIdx.x * 4 * SPLANE : smem;     // [4][SPLANE] score planes
-    float *VS = SG ? smem : smem + 4 * SPLANE;                               // [VCH][VPIT] V chunk
+    const int SPLANE = att_score_plane(PITS);
+    const AttScores sc{SG ? s_scratch + (size_t)blockIdx.x * 4 * SPLANE : smem, SPLANE, PITS};     // [4][SPLANE] score planes
+    float *VS = SG ? smem : smem + 4 * SPLANE;                                                       // [VCH][VPIT] V chunk
     const int H = d / HD;
-    // Block b runs on XCD b % 8 (observed dispatch rule).  The row blocks of one (utterance, head) share K, V and the P band:
-    // give them consecutive slots on ONE XCD so the second..last read those rows from that XCD's L2 instead of HBM.
-    int h, i0;
-    int64_t row0;                                                   // first row of this utterance in the (packed) row axis of qkv / ctx
-    if constexpr (RAG) {
-        // ragged batch (kernels.hpp: SeqRag): XCD x takes head x (+ 8, ...) of EVERY utterance, the row blocks of one utterance in consecutive
-        // slots -- the same L2 sharing; this utterance's own length, and its window of the position table built for rg.pos_T frames
-        const int id = blockIdx.x, xcd = id & 7, k = id >> 3;
-        h = (k / rg.units.count) * 8 + xcd;
-        if (h >= H) return;
-        const RagUnit un = rg.units.u[k % rg.units.count];
-        i0 = un.r0;
-        T = rg.T[un.b];
-        row0 = rg.T_off[un.b];
-        pos_row0 = rg.pos_T - T;
-    } else {
-        const int id = blockIdx.x, xcd = id & 7, k = id >> 3;
-        const int rbk = k % n_rb, bh = (k / n_rb) * 8 + xcd;
-        if (bh >= n_bh) return;                                      // padding slot of the grid (whole workgroup, before any barrier)
-        h = bh % H;
-        i0 = rbk * RB;
-        row0 = (int64_t)(bh / H) * T;
-    }
+    AttPlace pl;
+    if (!att_place<RAG, RB>(H, T, n_rb, n_bh, rg, pl)) return;
+    const int h = pl.h, i0 = pl.i0;
+    const int64_t row0 = pl.row0;
+    T = pl.T;
+    if constexpr (RAG && !BAND) pos_row0 = rg.pos_T - T;            // this utterance's window of the table built for rg.pos_T frames
     const int rows = (T - i0) < RB ? (T - i0) : RB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, kq = lane >> 4;
-    const int rt = wave & 1, cp = wave >> 1;                       // this wave's 16-row tile and tile parity
-    const int P = 2 * T - 1;
+    const AttWave w = att_wave();
+    // the key window [jlo, jhi] of this block, W columns; NP rows of position table
+    int jlo = 0, jhi = T - 1;
+    if constexpr (BAND) {
+        jlo = i0 - left > 0 ? i0 - left : 0;
+        jhi = i0 + RB - 1 + right < T - 1 ? i0 + RB - 1 + right : T - 1;
+    }
+    const int W = BAND ? jhi - jlo + 1 : T;
+    const int NP = BAND ? left + right + 1 : 2 * T - 1;
+    const bool has_pos = BAND || pos != nullptr;
     const float *qb = qkv + row0 * ldq + h * HD;                    // q rows of this (b,h) (sigma columns)
-    const float *kb = qb + d, *vb = qb + 2 * d;                     // k (sigma columns), v (natural)
-    const float *pb = pos + (int64_t)pos_row0 * d + h * HD;         // row p of THIS length's table (engine.cpp: ensure_pos_tables)
-    auto sidx = [&](int il, int j) { return (j & 3) * SPLANE + il * PITS + (j >> 2); };
-
-    // V chunk: cooperative coalesced loads -> registers -> LDS
-    float4 vf[NLV];
-    auto v_issue = [&](int row0) {
-#pragma unroll
-        for (int i = 0; i < NLV; ++i) {
-            const int e = tid + 256 * i, gr = row0 + e / KQ;
-            vf[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (gr < T) vf[i] = *reinterpret_cast<const float4 *>(vb + (int64_t)gr * ldq + 4 * (e % KQ));
-        }
-    };
-    auto v_commit = [&]() {
-#pragma unroll
-        for (int i = 0; i < NLV; ++i) {
-            const int e = tid + 256 * i;
-            lds_store16(VS + (e / KQ) * VPIT + 4 * (e % KQ), vf[i]);
-        }
-    };
-    // one 16-row operand tile straight from global: lane (row l15, quarter kq) takes float4 #kq of every 16-feature block
-    auto load_tile = [&](const float *base, int64_t ld, int row0, int limit, float4 (&f)[NQ4]) {
-#ifdef ATT_LINES_EXPERIMENT     // TIMING PROXY ONLY (wrong operands): the same number of 16-byte loads, but every instruction reads 8 rows x one whole 128-byte line
-        const int r = row0 + (lane >> 3);
-        const bool ok = r >= 0 && r + 8 < limit;
-        const float *p = base + (int64_t)(ok ? r : 0) * ld + 4 * (lane & 7);
-#pragma unroll
-        for (int q = 0; q < NQ4; ++q) f[q] = ok ? *reinterpret_cast<const float4 *>(p + (int64_t)(8 * (q & 1)) * ld + 32 * (q >> 1)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#else
-        const int r = row0 + l15;
-        const bool ok = r >= 0 && r < limit;
-        const float *p = base + (int64_t)(ok ? r : 0) * ld + 4 * kq;
-#pragma unroll
-        for (int q = 0; q < NQ4; ++q) f[q] = ok ? *reinterpret_cast<const float4 *>(p + 16 * q) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#endif
-    };
-    // two independent 16x16 accumulator chains over K = HD (natural k: step 4q+e consumes k = 16q + 4e + kq)
-    auto mma_pair = [&](const float4 (&a)[NQ4], const float4 (&b0)[NQ4], const float4 (&b1)[NQ4], f32x4 &c0, f32x4 &c1) {
-        c0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        c1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < NQ4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(a[q], e), f4e(b0[q], e), c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(a[q], e), f4e(b1[q], e), c1, 0, 0, 0);
-            }
-    };
+    const float *kb = qb + d + (int64_t)jlo * ldq, *vb = qb + 2 * d + (int64_t)jlo * ldq;   // k (sigma columns), v (natural): row c = key jlo + c
+    const float *pb = pos + (BAND ? (int64_t)0 : (int64_t)pos_row0 * d) + h * HD;           // row p of THIS length's table (engine.cpp: ensure_pos_tables)
 
     // ---- phase 0: the Q fragments of this wave's 16 rows.  Only ONE biased copy is live at a time -- (q+u) for the content scores, then
     //      q is fetched again (L2) and (q+v) formed for the position scores -- and the first V chunk is requested after the score phases:
     //      the register budget of four workgroups per CU (128 VGPRs) has no room for both copies plus the V prefetch beside the four
     //      operand tiles of the score loops (round 2: 168 -> 134 VGPRs, 86.9 -> 82.3 us per layer at T = 126).
-    float4 qx[NQ4];                                                 // (q+u), later (q+v); element e of fragment f <-> k = 16f + 4e + kq
-    auto load_q_biased = [&](const float *bias) {                   // as the reference forms them (src/encoder.cpp:141-142)
-        load_tile(qb, ldq, i0 + rt * 16, T, qx);
-        if (pos) {
-            const float *br = bias + h * HD + kq;
-#pragma unroll
-            for (int f = 0; f < NQ4; ++f)
-                qx[f] = make_float4(qx[f].x + br[16 * f], qx[f].y + br[16 * f + 4], qx[f].z + br[16 * f + 8], qx[f].w + br[16 * f + 12]);
-        }
-    };
-    ATT_STAMP(0);
-    load_q_biased(bias_u);
-    const int il_base = rt * 16 + 4 * kq;                           // C layout: column = lane & 15, row = 4*(lane>>4) + r
-    const int Tpad4 = (T + 3) & ~3;
-    ATT_STAMP(1);                                                   // Q load + bias
-    float4 bA0[NQ4], bA1[NQ4], bB0[NQ4], bB1[NQ4];                  // two operand-tile pairs: one computing, one in flight
-
-    // ---- phase 1: content scores (q+u) K^T -> S; this wave's column tiles are t = cp, cp+2, ... (pairs, one pair ahead) ----
-    {
-        const int nct = (T + 15) / 16;
-        auto store = [&](int t, const f32x4 &a0, const f32x4 &a1) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int il = il_base + r;
-                const int j0 = t * 16 + l15, j1 = j0 + 32;
-                // columns T..Tpad4-1: zero pad of the AV chain; without a position term the scale is applied here
-                if (j0 < Tpad4) S[sidx(il, j0)] = j0 < T ? (pos ? a0[r] : a0[r] * scale) : 0.0f;
-                if (t + 2 < nct && j1 < Tpad4) S[sidx(il, j1)] = j1 < T ? (pos ? a1[r] : a1[r] * scale) : 0.0f;
-            }
-        };
-        if (cp < nct) { load_tile(kb, ldq, cp * 16, T, bA0); load_tile(kb, ldq, (cp + 2) * 16, T, bA1); }
-        for (int t = cp; t < nct; t += 8) {
-            f32x4 a0, a1;
-            if (t + 4 < nct) { load_tile(kb, ldq, (t + 4) * 16, T, bB0); load_tile(kb, ldq, (t + 6) * 16, T, bB1); }
-            mma_pair(qx, bA0, bA1, a0, a1);
-            store(t, a0, a1);
-            if (t + 4 < nct) {
-                if (t + 8 < nct) { load_tile(kb, ldq, (t + 8) * 16, T, bA0); load_tile(kb, ldq, (t + 10) * 16, T, bA1); }
-                mma_pair(qx, bB0, bB1, a0, a1);
-                store(t + 4, a0, a1);
-            }
-        }
+    float4 qx[NQ4];                                                 // (q+u), later (q+v)
+    ATT_STAMP(4, 0);
+    att_load_q_biased(qb, ldq, i0 + w.rt * 16, T, bias_u, h * HD, has_pos, w.l15, w.kq, qx);
+    ATT_STAMP(4, 1);                                                // Q load + bias
+    att_content_pass(sc, w, kb, ldq, W, qx, has_pos, scale);
+    ATT_STAMP(4, 2);                                                // QK^T -> S
+    if (has_pos) att_load_q_biased(qb, ldq, i0 + w.rt * 16, T, bias_v, h * HD, true, w.l15, w.kq, qx);
+    // ---- phase 2: this wave's 16 query rows w_lo .. w_hi need the table rows p = j - i + (T - 1 | left) of their in-window keys: [wpmin, wpmax]
+    const int w_lo = i0 + w.rt * 16, w_hi = (w_lo + 15) < (T - 1) ? (w_lo + 15) : (T - 1);
+    int wpmin = T - 1 - w_hi, wpmax = 2 * T - 2 - w_lo;
+    if constexpr (BAND) {
+        wpmin = jlo - w_hi + left > 0 ? jlo - w_hi + left : 0;
+        wpmax = jhi - w_lo + left < NP - 1 ? jhi - w_lo + left : NP - 1;
     }
-    ATT_STAMP(2);                                                   // QK^T -> S
-    if (pos) load_q_biased(bias_v);
-    // ---- phase 2: position scores (q+v) P^T, shifted, combined and scaled.  This wave's 16 query rows need
-    //      p = j - i + T - 1 in [wpmin, wpmax] (T+15 rows): its own tile grid starts at wpmin, tiles t = cp, cp+2, ... ------
-    const int w_lo = i0 + rt * 16, w_hi = (w_lo + 15) < (T - 1) ? (w_lo + 15) : (T - 1);
-    const int wpmin = T - 1 - w_hi, wpmax = 2 * T - 2 - w_lo;
-    const int npt = (pos && w_lo < T) ? (wpmax - wpmin) / 16 + 1 : 0;
-    if (cp < npt) { load_tile(pb, d, wpmin + cp * 16, P, bA0); load_tile(pb, d, wpmin + (cp + 2) * 16, P, bA1); }   // in flight across the barrier
-    __syncthreads();                                              // content scores complete
-    ATT_STAMP(3);                                                   // (q+v), first P tiles requested, barrier
-    {
-        auto rmw = [&](int t, const f32x4 &a0, const f32x4 &a1) {
-            // the eight score elements are READ together, then combined, then stored (distinct addresses: four rows x two column tiles); one by one
-            // every read would wait behind the previous element's store (see the softmax sweep below)
-            int ad[8];
-            bool ok[8];
-            float v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int il = il_base + r, i = i0 + il;
-                const int pa = wpmin + t * 16 + l15, ja = pa - (T - 1) + i;
-                const int pc = pa + 32, jc = ja + 32;
-                ok[r] = i < T && pa < P && ja >= 0 && ja < T;
-                ok[4 + r] = t + 2 < npt && i < T && pc < P && jc >= 0 && jc < T;
-                ad[r] = ok[r] ? sidx(il, ja) : 0;
-                ad[4 + r] = ok[4 + r] ? sidx(il, jc) : 0;
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = S[ad[q]];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (ok[r]) S[ad[r]] = (v[r] + a0[r]) * scale;                   // (content + pos) * scale, src/encoder.cpp:157-160
-                if (ok[4 + r]) S[ad[4 + r]] = (v[4 + r] + a1[r]) * scale;
-            }
-        };
-        for (int t = cp; t < npt; t += 8) {
-            f32x4 a0, a1;
-            if (t + 4 < npt) { load_tile(pb, d, wpmin + (t + 4) * 16, P, bB0); load_tile(pb, d, wpmin + (t + 6) * 16, P, bB1); }
-            mma_pair(qx, bA0, bA1, a0, a1);
-            rmw(t, a0, a1);
-            if (t + 4 < npt) {
-                if (t + 8 < npt) { load_tile(pb, d, wpmin + (t + 8) * 16, P, bA0); load_tile(pb, d, wpmin + (t + 10) * 16, P, bA1); }
-                mma_pair(qx, bB0, bB1, a0, a1);
-                rmw(t + 4, a0, a1);
-            }
-        }
-    }
-    ATT_STAMP(4);                                                   // QP^T shifted rmw
-    v_issue(0);                                                   // first V chunk: in flight across the softmax
+    const int npt = (has_pos && w_lo < T) ? (wpmax - wpmin) / 16 + 1 : 0;
+    // (contains the barrier that completes the content scores, and stamp 3: every thread calls it, also with npt == 0 / without a table)
+    att_shift_pass(sc, w, pb, d, NP, wpmin, npt, BAND ? left + jlo : T - 1, i0, T, W, qx, scale);
+    ATT_STAMP(4, 4);                                                // QP^T shifted rmw
+    float4 vf[VCH * (HD / 4) / 256];
+    att_v_issue<HD, VCH, 256>(vb, ldq, 0, W, vf);                   // first V chunk: in flight across the softmax
     __syncthreads();
-    ATT_STAMP(5);                                                   // barrier
-    // ---- phase 3: softmax, one wavefront per row ----------------------------------------------------------------------------
-    // Each wave owns rows wave, wave+4, ...: all NSR of them go through the three sweeps TOGETHER, so the 2 x 6 dependent
-    // cross-lane butterfly stages and the exp / divide chains of different rows overlap instead of queueing up.
-    // (Rows past T in the last block hold zeros: they are swept too and never stored.)
-    {
-        constexpr int NSR = RB / 4;
-        float mx[NSR], sm[NSR];
+    ATT_STAMP(4, 5);                                                // barrier
+    if constexpr (BAND) {
+        AttRowsBand band;
 #pragma unroll
-        for (int k = 0; k < NSR; ++k) mx[k] = -__builtin_huge_valf();
-        for (int j = lane; j < T; j += 64)
-#pragma unroll
-            for (int k = 0; k < NSR; ++k) mx[k] = fmaxf(mx[k], S[sidx(wave + 4 * k, j)]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-            for (int k = 0; k < NSR; ++k) mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], off, 64));
-#pragma unroll
-        for (int k = 0; k < NSR; ++k) sm[k] = 0.0f;
-        // The NSR rows' values are READ first, then transformed, then stored: written element by element (read, exp, store, next row) the compiler
-        // has to keep every read behind the previous row's store -- both are LDS floats -- and the eight exp chains ran one after the other, each
-        // behind its own LDS round trip (round 4, from the ISA: profiles/r04_attn_phases.txt).  Same values, same per-row summation order.
-        for (int j = lane; j < T; j += 64) {
-            float e[NSR];
-#pragma unroll
-            for (int k = 0; k < NSR; ++k) e[k] = S[sidx(wave + 4 * k, j)] - mx[k];          // S <= row maximum
-            if (ctx_bf16 == 1) {    // bf16 mode (tolerance-class, see GemmArgs::fast_act): hardware exp2 instead of the fixed polynomial
-#pragma unroll
-                for (int k = 0; k < NSR; ++k) e[k] = __builtin_amdgcn_exp2f(e[k] * 1.44269502162933349609375f);
-            } else {
-#pragma unroll
-                for (int k = 0; k < NSR; ++k) e[k] = dexpf_nonpos(e[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < NSR; ++k) {
-                S[sidx(wave + 4 * k, j)] = e[k];
-                sm[k] = sm[k] + e[k];
-            }
+        for (int k = 0; k < RB / 4; ++k) {
+            const int i = i0 + w.wave + 4 * k;
+            band.clo[k] = (i - left > jlo ? i - left : jlo) - jlo;
+            band.chi[k] = i < T ? (i + right < jhi ? i + right : jhi) - jlo : -1;     // rows past T: an empty band (never stored)
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1)                      // the canonical sum64 butterfly, NSR rows side by side
-#pragma unroll
-            for (int k = 0; k < NSR; ++k) sm[k] = sm[k] + __shfl_xor(sm[k], off, 64);
-        if (ctx_bf16 == 1) {                                         // bf16 mode: one hardware reciprocal per row, a multiplication per element
-#pragma unroll
-            for (int k = 0; k < NSR; ++k) sm[k] = __builtin_amdgcn_rcpf(sm[k]);
-            for (int j = lane; j < T; j += 64) {
-                float e[NSR];
-#pragma unroll
-                for (int k = 0; k < NSR; ++k) e[k] = S[sidx(wave + 4 * k, j)] * sm[k];
-#pragma unroll
-                for (int k = 0; k < NSR; ++k) S[sidx(wave + 4 * k, j)] = e[k];
-            }
-        } else {
-            for (int j = lane; j < T; j += 64) {
-                float e[NSR];
-#pragma unroll
-                for (int k = 0; k < NSR; ++k) e[k] = S[sidx(wave + 4 * k, j)];
-#pragma unroll
-                for (int k = 0; k < NSR; ++k) e[k] = e[k] / sm[k];
-#pragma unroll
-                for (int k = 0; k < NSR; ++k) S[sidx(wave + 4 * k, j)] = e[k];
-            }
-        }
+        att_softmax(sc, w, W, ctx_bf16, band);
+    } else {
+        att_softmax(sc, w, W, ctx_bf16, AttRowsFull{});
     }
-    ATT_STAMP(6);                                                   // softmax
-    v_commit();
+    ATT_STAMP(4, 6);                                                // softmax
+    att_v_commit<HD, VCH, 256>(VS, vf);
     lds_store_fence();
     __syncthreads();
-    // ---- phase 4: ctx = softmax(S) V  (k = key index, natural order; NDV independent 16-column tiles per wave) ---------------
+    // ---- phase 4: ctx = softmax(S) V  (k = window column, natural order; NDV independent 16-column tiles per wave) ---------------
     f32x4 acc[NDV];
 #pragma unroll
     for (int m = 0; m < NDV; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const float *sa = S + kq * SPLANE + (rt * 16 + l15) * PITS;    // A: row il = rt*16 + l15, k = 4s + kq at float s
-    const float *vrow = VS + kq * VPIT + cp * 16 + l15;             // B: V[4s + kq - c0r][dv tile (cp + 2m)]
-    for (int c0r = 0; c0r < T; c0r += VCH) {
-        const bool more = c0r + VCH < T;
-        if (more) v_issue(c0r + VCH);
-        const int s_end = ((T - c0r < VCH ? T - c0r : VCH) + 3) / 4;            // k-steps in this chunk (zero rows pad the last one)
-        for (int s4 = 0; s4 < s_end; s4 += 4) {
-            const float4 a = *reinterpret_cast<const float4 *>(sa + c0r / 4 + s4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (s4 + e < s_end) {
-#pragma unroll
-                    for (int m = 0; m < NDV; ++m)
-                        acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(a, e), vrow[(s4 + e) * 4 * VPIT + m * 32], acc[m], 0, 0, 0);
-                }
-            }
-        }
+    const float *sa = sc.s + w.kq * SPLANE + (w.rt * 16 + w.l15) * PITS;     // A: row il = rt*16 + l15, k = 4s + kq at float s
+    const float *vrow = VS + w.kq * VPIT + w.cp * 16 + w.l15;                // B: V[4s + kq - c0r][dv tile (cp + 2m)]
+    for (int c0r = 0; c0r < W; c0r += VCH) {
+        const bool more = c0r + VCH < W;
+        if (more) att_v_issue<HD, VCH, 256>(vb, ldq, c0r + VCH, W, vf);
+        const int s_end = ((W - c0r < VCH ? W - c0r : VCH) + 3) / 4;            // k-steps in this chunk (zero rows pad the last one)
+        att_av_steps<NDV, VPIT, SG>(sa + c0r / 4, vrow, s_end, 32, acc);
         if (more) {
             __syncthreads();
-            v_commit();
+            att_v_commit<HD, VCH, 256>(VS, vf);
             lds_store_fence();
             __syncthreads();
         }
@@ -344,16 +154,10 @@ __global__ __launch_bounds__(256, OCC) void relpos_attention_kernel(const float 
     for (int m = 0; m < NDV; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int il = il_base + r;
-            if (il < rows) {
-                const int64_t orow = (row0 + i0 + il) * d;
-                const int col = h * HD + (cp + 2 * m) * 16 + l15;
-                if (ctx_bf16 == 1) reinterpret_cast<__bf16 *>(ctx)[orow + col] = (__bf16)acc[m][r];      // bf16 mode: out_proj's operand, rounded here (RNE)
-                else if (ctx_bf16 == 2) ctx[orow + ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3))] = acc[m][r];   // fp32, sigma K layout (GemmArgs::a_sigma)
-                else ctx[orow + col] = acc[m][r];
-            }
+            const int il = w.il_base + r;
+            if (il < rows) att_store_ctx(ctx, (row0 + i0 + il) * d, h * HD + (w.cp + 2 * m) * 16 + w.l15, acc[m][r], ctx_bf16);
         }
-    ATT_STAMP(7);                                                   // V commit, barrier, AV, store
+    ATT_STAMP(4, 7);                                                // V commit, barrier, AV, store
 }
 
 // ---- the "strip" form: T <= 128, the scores never leave the registers until they are probabilities --------------------------------------------
@@ -370,12 +174,7 @@ __global__ __launch_bounds__(256, OCC) void relpos_attention_kernel(const float 
 //   * the probabilities go ONCE into a wave-private k-planar LDS region (PW columns at a time) and come back as the A operand of the AV chains
 //     (one ds_read_b128 per four k-steps): the wave's own LDS traffic is in order, no barrier.  V is staged per workgroup as above.
 // The only workgroup barriers left are those of the V chunks.  NW waves = 16 NW query rows per workgroup; the ragged form keeps the engine's
-// 32-row units (NW = 2).
-#ifdef ATT_TRACE
-#define ATT_STAMP_S(i) do { if (att_trace && (threadIdx.x & 63) == 0) att_trace[((long long)blockIdx.x * NW + (threadIdx.x >> 6)) * 8 + (i)] = clock64(); } while (0)
-#else
-#define ATT_STAMP_S(i) do { } while (0)
-#endif
+// 32-row units (NW = 2).  Placement, operand loads, the single chain, the V stager, the AV steps and the ctx store are attention_dev.hpp's.
 static constexpr int STRIP_T = 128;   // longest sequence of the strip form
 
 template <int HD, int VCH, int NW, int PW, bool RAG, int OCC>
@@ -385,33 +184,20 @@ __global__ __launch_bounds__(64 * NW, OCC) void relpos_attention_strip_kernel(co
                                                                             float scale, float *__restrict__ ctx, int n_rb, int n_bh, int ctx_bf16,
                                                                             int pos_row0, SeqRag rg) {
     __builtin_amdgcn_s_setprio(3);
-    constexpr int NT = 64 * NW, RBS = 16 * NW;
-    constexpr int KQ = HD / 4, NQ4 = HD / 16, VPIT = HD + 16, NDV = HD / 16, NLV = VCH * KQ / NT;
+    constexpr int NT = 64 * NW;
+    constexpr int NQ4 = HD / 16, VPIT = HD + 16, NDV = HD / 16;
     constexpr int NCT = STRIP_T / 16;                               // key tiles of a strip
     constexpr int PPIT = PW / 4 + 4, PPLANE = 16 * PPIT + 4;        // probabilities: [4 planes][16 rows][PW / 4]; rows 16, planes 4 banks apart
-    static_assert((VCH * KQ) % NT == 0 && VCH % 16 == 0 && PW % VCH == 0 && STRIP_T % PW == 0, "V chunks tile a probability piece, pieces tile the strip");
+    static_assert(VCH % 16 == 0 && PW % VCH == 0 && STRIP_T % PW == 0, "V chunks tile a probability piece, pieces tile the strip");
     static_assert(!RAG || NW == 2, "the units of a ragged batch are 32-row blocks");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = d / HD;
-    int h, i0;
-    int64_t row0;
-    if constexpr (RAG) {
-        const int id = blockIdx.x, xcd = id & 7, k = id >> 3;
-        h = (k / rg.units.count) * 8 + xcd;
-        if (h >= H) return;
-        const RagUnit un = rg.units.u[k % rg.units.count];
-        i0 = un.r0;
-        T = rg.T[un.b];
-        row0 = rg.T_off[un.b];
-        pos_row0 = rg.pos_T - T;
-    } else {
-        const int id = blockIdx.x, xcd = id & 7, k = id >> 3;           // the row blocks of one (utterance, head) on one XCD, as above
-        const int rbk = k % n_rb, bh = (k / n_rb) * 8 + xcd;
-        if (bh >= n_bh) return;                                      // padding slot of the grid (whole workgroup, before any barrier)
-        h = bh % H;
-        i0 = rbk * RBS;
-        row0 = (int64_t)(bh / H) * T;
-    }
+    AttPlace pl;
+    if (!att_place<RAG, 16 * NW>(H, T, n_rb, n_bh, rg, pl)) return;
+    const int h = pl.h, i0 = pl.i0;
+    const int64_t row0 = pl.row0;
+    T = pl.T;
+    if constexpr (RAG) pos_row0 = rg.pos_T - T;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kq = lane >> 4;
     const int i_s = i0 + wave * 16;                                 // first query row of this wave's strip
@@ -424,76 +210,37 @@ __global__ __launch_bounds__(64 * NW, OCC) void relpos_attention_strip_kernel(co
     float *VS = smem;                                               // [VCH][VPIT] V chunk
     float *PS = smem + VCH * VPIT + wave * 4 * PPLANE;              // this wave's probabilities
 
-    float4 vf[NLV];
-    auto v_issue = [&](int vrow0) {
-#pragma unroll
-        for (int i = 0; i < NLV; ++i) {
-            const int e = tid + NT * i, gr = vrow0 + e / KQ;
-            vf[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (gr < T) vf[i] = *reinterpret_cast<const float4 *>(vb + (int64_t)gr * ldq + 4 * (e % KQ));
-        }
-    };
-    auto v_commit = [&]() {
-#pragma unroll
-        for (int i = 0; i < NLV; ++i) {
-            const int e = tid + NT * i;
-            lds_store16(VS + (e / KQ) * VPIT + 4 * (e % KQ), vf[i]);
-        }
-    };
-    auto load_tile = [&](const float *base, int64_t ld, int trow0, int limit, float4 (&f)[NQ4]) {
-        const int r = trow0 + l15;
-        const bool ok = r >= 0 && r < limit;
-        const float *p = base + (int64_t)(ok ? r : 0) * ld + 4 * kq;
-#pragma unroll
-        for (int q = 0; q < NQ4; ++q) f[q] = ok ? *reinterpret_cast<const float4 *>(p + 16 * q) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    };
-    // one 16x16 accumulator chain over K = HD from zero, the natural k order of mma_pair
-    auto mma_one = [&](const float4 (&a)[NQ4], const float4 (&b)[NQ4], f32x4 &c) {
-        c = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < NQ4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(a[q], e), f4e(b[q], e), c, 0, 0, 0);
-    };
+    float4 vf[VCH * (HD / 4) / NT];
     float4 qx[NQ4];
-    auto load_q_biased = [&](const float *bias) {
-        load_tile(qb, ldq, i_s, T, qx);
-        if (pos) {
-            const float *br = bias + h * HD + kq;
-#pragma unroll
-            for (int f = 0; f < NQ4; ++f)
-                qx[f] = make_float4(qx[f].x + br[16 * f], qx[f].y + br[16 * f + 4], qx[f].z + br[16 * f + 8], qx[f].w + br[16 * f + 12]);
-        }
-    };
-    ATT_STAMP_S(0);
+    ATT_STAMP(NW, 0);
     f32x4 st[NCT];                                                  // the strip: tile t, register r <-> row 4 kq + r, column 16 t + l15
 #pragma unroll
     for (int t = 0; t < NCT; ++t) st[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     if (active) {
         float4 bA[NQ4], bB[NQ4];                                    // one operand tile computing, one in flight
-        load_q_biased(bias_u);
-        ATT_STAMP_S(1);                                             // Q load + bias
+        att_load_q_biased(qb, ldq, i_s, T, bias_u, h * HD, pos != nullptr, l15, kq, qx);
+        ATT_STAMP(NW, 1);                                           // Q load + bias
         // ---- content scores (q+u) K^T ----
-        load_tile(kb, ldq, 0, T, bA);
+        att_load_tile(kb, ldq, 0, T, l15, kq, bA);
 #pragma unroll
         for (int t = 0; t < NCT; ++t) {
             // (all NCT tiles, straight-line: a tile past T loads nothing and multiplies zeros.  Branching on nct costs registers across the
             //  blocks -- spills at the 128 VGPRs of four workgroups per CU)
-            if (t + 1 < NCT) load_tile(kb, ldq, (t + 1) * 16, T, (t & 1) ? bA : bB);
-            mma_one(qx, (t & 1) ? bB : bA, st[t]);
+            if (t + 1 < NCT) att_load_tile(kb, ldq, (t + 1) * 16, T, l15, kq, (t & 1) ? bA : bB);
+            att_mma_one(qx, (t & 1) ? bB : bA, st[t]);
             __builtin_amdgcn_sched_barrier(0);                       // one tile ahead, no further
         }
-        ATT_STAMP_S(2);                                             // QK^T
+        ATT_STAMP(NW, 2);                                           // QK^T
         // ---- position scores (q+v) P^T, skewed into place, combined, scaled; columns >= T zero (the pad of the AV chain, +0.0 in the row sum) ----
         if (pos) {
-            load_q_biased(bias_v);
+            att_load_q_biased(qb, ldq, i_s, T, bias_v, h * HD, true, l15, kq, qx);
             const int wpmin = T - 1 - (i_s + 15);                    // may be negative: rows outside [0, P) load as zeros and are never selected
             f32x4 pprev = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, pcur;
-            load_tile(pb, d, wpmin, P, bA);
+            att_load_tile(pb, d, wpmin, P, l15, kq, bA);
 #pragma unroll
             for (int u = 0; u <= NCT; ++u) {
-                if (u + 1 <= NCT) load_tile(pb, d, wpmin + (u + 1) * 16, P, (u & 1) ? bA : bB);
-                mma_one(qx, (u & 1) ? bB : bA, pcur);
+                if (u + 1 <= NCT) att_load_tile(pb, d, wpmin + (u + 1) * 16, P, l15, kq, (u & 1) ? bA : bB);
+                att_mma_one(qx, (u & 1) ? bB : bA, pcur);
                 if (u >= 1) {
                     const int t = u - 1, j = t * 16 + l15;
 #pragma unroll
@@ -516,11 +263,11 @@ __global__ __launch_bounds__(64 * NW, OCC) void relpos_attention_strip_kernel(co
                 for (int r = 0; r < 4; ++r) st[t][r] = j < T ? st[t][r] * scale : 0.0f;
             }
         }
-        ATT_STAMP_S(3);                                             // QP^T, skew, combine
+        ATT_STAMP(NW, 3);                                           // QP^T, skew, combine
     } else {
-        ATT_STAMP_S(1); ATT_STAMP_S(2); ATT_STAMP_S(3);
+        ATT_STAMP(NW, 1); ATT_STAMP(NW, 2); ATT_STAMP(NW, 3);
     }
-    v_issue(0);                                                   // first V chunk: in flight across the softmax (the score passes have no registers to spare)
+    att_v_issue<HD, VCH, NT>(vb, ldq, 0, T, vf);                    // first V chunk: in flight across the softmax (the score passes have no registers to spare)
     if (active) {
         // ---- softmax in registers (rows past T hold finite values and are never stored) ----
         float mx[4], sm[4];
@@ -575,11 +322,11 @@ __global__ __launch_bounds__(64 * NW, OCC) void relpos_attention_strip_kernel(co
                 for (int r = 0; r < 4; ++r) st[t][r] = st[t][r] / sm[r];
         }
     }
-    ATT_STAMP_S(4);                                                 // softmax
-    v_commit();
+    ATT_STAMP(NW, 4);                                               // softmax
+    att_v_commit<HD, VCH, NT>(VS, vf);
     lds_store_fence();
     __syncthreads();
-    ATT_STAMP_S(5);                                                 // V commit, barrier
+    ATT_STAMP(NW, 5);                                               // V commit, barrier
     // ---- ctx = softmax(S) V: NDV 16-column tiles per wave, natural key order ----
     f32x4 acc[NDV];
 #pragma unroll
@@ -590,7 +337,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void relpos_attention_strip_kernel(co
         const int c0r = c * VCH;
         if (c0r < T) {
             const bool more = c0r + VCH < T;
-            if (more) v_issue(c0r + VCH);
+            if (more) att_v_issue<HD, VCH, NT>(vb, ldq, c0r + VCH, T, vf);
             if (active) {
                 if (c0r % PW == 0) {                                 // the next PW columns of probabilities -> this wave's k-planar region
 #pragma unroll
@@ -604,42 +351,31 @@ __global__ __launch_bounds__(64 * NW, OCC) void relpos_attention_strip_kernel(co
                     lds_store_fence();                               // wave-private: the wave's own stores, then its own reads
                 }
                 const int s_end = ((T - c0r < VCH ? T - c0r : VCH) + 3) / 4;
-                const float *sa = PS + kq * PPLANE + l15 * PPIT + (c0r % PW) / 4;    // A: row l15, k = 4s + kq at float s
-                for (int s4 = 0; s4 < s_end; s4 += 4) {
-                    const float4 a = *reinterpret_cast<const float4 *>(sa + s4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if (s4 + e < s_end) {
-#pragma unroll
-                            for (int m = 0; m < NDV; ++m)
-                                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(a, e), vrow[(s4 + e) * 4 * VPIT + m * 16], acc[m], 0, 0, 0);
-                        }
-                    }
-                }
+                att_av_steps<NDV, VPIT>(PS + kq * PPLANE + l15 * PPIT + (c0r % PW) / 4, vrow, s_end, 16, acc);    // A: row l15, k = 4s + kq at float s
             }
             if (more) {
                 __syncthreads();
-                v_commit();
+                att_v_commit<HD, VCH, NT>(VS, vf);
                 lds_store_fence();
                 __syncthreads();
             }
         }
     }
-    ATT_STAMP_S(6);                                                 // P write, AV
+    ATT_STAMP(NW, 6);                                               // P write, AV
 #pragma unroll
     for (int m = 0; m < NDV; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = i_s + 4 * kq + r;
-            if (i < T) {
-                const int64_t orow = (row0 + i) * d;
-                const int col = h * HD + m * 16 + l15;
-                if (ctx_bf16 == 1) reinterpret_cast<__bf16 *>(ctx)[orow + col] = (__bf16)acc[m][r];
-                else if (ctx_bf16 == 2) ctx[orow + ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3))] = acc[m][r];
-                else ctx[orow + col] = acc[m][r];
-            }
+            if (i < T) att_store_ctx(ctx, (row0 + i) * d, h * HD + m * 16 + l15, acc[m][r], ctx_bf16);
         }
-    ATT_STAMP_S(7);                                                 // store
+    ATT_STAMP(NW, 7);                                               // store
+}
+
+// grid of a launch: 8 XCD lanes x ceil(n_bh / 8) x n_rb row blocks; ragged: 8 XCD lanes x ceil(n_heads / 8) x the batch's 32-row units
+static dim3 att_grid(int n_bh, int n_rb, int n_heads, const SeqRag &rag) {
+    if (rag.units.u) return dim3((unsigned)(((n_heads + 7) / 8) * 8 * (int64_t)rag.units.count));
+    return dim3(((n_bh + 7) / 8) * 8 * n_rb);
 }
 
 template <int HD, int VCH, int OCC = (HD <= 64 ? ATT_OCC : 2)>
@@ -647,64 +383,33 @@ static void launch_att(const float *qkv, int B, int T, int d, int n_heads, const
                        float *ctx, float scale_arg, hipStream_t s, float *scratch, int ctx_bf16, int pos_row0, const SeqRag &rag) {
     const float scale = scale_arg > 0.0f ? scale_arg : 1.0f / sqrtf((float)HD);   // src/encoder.cpp:126
     if (rag.units.u) T = rag.T_max;                                // the score block is laid out for the longest utterance of the batch
-    int pits = (T + 3) / 4;                                        // floats per score-plane row, padded so that pits/4 is odd
-    pits = (pits + 3) & ~3;
-    if (((pits / 4) & 1) == 0) pits += 4;
+    const int pits = att_score_pitch(T);
     const int n_rb = (T + RB - 1) / RB, n_bh = B * n_heads;
-    dim3 grid(((n_bh + 7) / 8) * 8 * n_rb);                        // 8 XCD lanes x ceil(n_bh/8) pairs x n_rb row blocks
-    if (rag.units.u) grid = dim3((unsigned)(((n_heads + 7) / 8) * 8 * (int64_t)rag.units.count));
-    if (scratch) {
-        {
-            const size_t lds = (size_t)VCH * (HD + 16) * sizeof(float);
-            if (rag.units.u)
-                hipLaunchKernelGGL((relpos_attention_kernel<HD, VCH, true, true, OCC>), grid, dim3(256), lds, s, qkv, 3 * d, d, T, pos, bias_u, bias_v, scale, ctx, pits,
-                                   n_rb, n_bh, scratch, ctx_bf16, pos_row0, rag);
-            else
-                hipLaunchKernelGGL((relpos_attention_kernel<HD, VCH, true, false, OCC>), grid, dim3(256), lds, s, qkv, 3 * d, d, T, pos, bias_u, bias_v, scale, ctx, pits,
-                                   n_rb, n_bh, scratch, ctx_bf16, pos_row0, rag);
-        }
-        return;
-    }
-    const size_t lds = (size_t)(4 * (RB * pits + 8) + VCH * (HD + 16)) * sizeof(float);
-    if (rag.units.u) {
-        static DynLdsSlots slots_r;
-        ensure_dyn_lds(slots_r, reinterpret_cast<const void *>(&relpos_attention_kernel<HD, VCH, false, true, OCC>), lds);
-        hipLaunchKernelGGL((relpos_attention_kernel<HD, VCH, false, true, OCC>), grid, dim3(256), lds, s, qkv, 3 * d, d, T, pos, bias_u, bias_v, scale, ctx, pits, n_rb, n_bh,
-                           (float *)nullptr, ctx_bf16, pos_row0, rag);
-        return;
-    }
-    static DynLdsSlots slots;
-    ensure_dyn_lds(slots, reinterpret_cast<const void *>(&relpos_attention_kernel<HD, VCH, false, false, OCC>), lds);
-    hipLaunchKernelGGL((relpos_attention_kernel<HD, VCH, false, false, OCC>), grid, dim3(256), lds, s, qkv, 3 * d, d, T, pos, bias_u, bias_v, scale, ctx, pits, n_rb, n_bh,
-                       (float *)nullptr, ctx_bf16, pos_row0, rag);
+    const dim3 grid = att_grid(n_bh, n_rb, n_heads, rag);
+    auto go = [&](auto ragged) {
+        constexpr bool RAG = decltype(ragged)::value;
+        if (scratch)
+            hipLaunchKernelGGL((relpos_attention_kernel<HD, VCH, true, RAG, OCC>), grid, dim3(256), (size_t)VCH * (HD + 16) * sizeof(float), s, qkv, 3 * d, d, T, pos,
+                               bias_u, bias_v, scale, ctx, pits, n_rb, n_bh, scratch, ctx_bf16, pos_row0, rag, 0, 0);
+        else
+            att_launch_dyn_lds<relpos_attention_kernel<HD, VCH, false, RAG, OCC>>(grid, dim3(256), att_block_lds_bytes(T, HD, VCH), s, qkv, 3 * d, d, T, pos, bias_u,
+                                                                                  bias_v, scale, ctx, pits, n_rb, n_bh, (float *)nullptr, ctx_bf16, pos_row0, rag, 0, 0);
+    };
+    if (rag.units.u) go(std::true_type{});
+    else go(std::false_type{});
 }
 
 // LDS bytes one workgroup needs for T frames: the [32][T] score block (four k-planes) + one V chunk.  0: unsupported head size.
-size_t relpos_attention_lds_bytes(int T, int hd) {
-    if (hd != 32 && hd != 64 && hd != 96 && hd != 128) return 0;
-    int pits = (T + 3) / 4;
-    pits = (pits + 3) & ~3;
-    if (((pits / 4) & 1) == 0) pits += 4;
-    const int vch = hd == 128 ? 32 : 64;
-    return (size_t)(4 * (RB * pits + 8) + vch * (hd + 16)) * sizeof(float);
-}
-// longest sequence whose score block fits the 160 KB of LDS of a CU (hd 64: 1064 frames = 85 s of audio; hd 128: 1104)
+size_t relpos_attention_lds_bytes(int T, int hd) { return att_hd_supported(hd) ? att_block_lds_bytes(T, hd, att_block_vch(hd)) : 0; }
 // bytes of global scratch the long-sequence variant needs (0: unsupported head size)
 size_t relpos_attention_scratch_bytes(int B, int T, int n_heads, int hd) {
-    if (hd != 32 && hd != 64 && hd != 96 && hd != 128) return 0;
-    int pits = (T + 3) / 4;
-    pits = (pits + 3) & ~3;
-    if (((pits / 4) & 1) == 0) pits += 4;
-    const size_t n_rb = (T + RB - 1) / RB, n_bh = (size_t)B * n_heads;
-    return ((n_bh + 7) / 8) * 8 * n_rb * 4 * (size_t)(RB * pits + 8) * sizeof(float);
+    return relpos_attention_scratch_bytes_units((T + RB - 1) / RB, T, B * n_heads, hd);
 }
 size_t relpos_attention_scratch_bytes_units(int64_t n_units, int T_max, int n_heads, int hd) {
-    if (hd != 32 && hd != 64 && hd != 96 && hd != 128) return 0;
-    int pits = (T_max + 3) / 4;
-    pits = (pits + 3) & ~3;
-    if (((pits / 4) & 1) == 0) pits += 4;
-    return (size_t)((n_heads + 7) / 8) * 8 * (size_t)n_units * 4 * (size_t)(RB * pits + 8) * sizeof(float);
+    if (!att_hd_supported(hd)) return 0;
+    return (size_t)((n_heads + 7) / 8) * 8 * (size_t)n_units * 4 * (size_t)att_score_plane(att_score_pitch(T_max)) * sizeof(float);
 }
+// longest sequence whose score block fits the 160 KB of LDS of a CU (hd 64: 1064 frames = 85 s of audio; hd 128: 1104)
 int relpos_attention_max_frames(int hd) {
     int T = 0;
     while (relpos_attention_lds_bytes(T + 8, hd) && relpos_attention_lds_bytes(T + 8, hd) <= 160 * 1024) T += 8;
@@ -742,19 +447,13 @@ static void launch_att_strip(const float *qkv, int B, int T, int d, int n_heads,
     constexpr int VCH = ATT_STRIP_VCH, PW = ATT_STRIP_PW, NW = ATT_STRIP_NW;
     auto lds_bytes = [](int nw) { return (size_t)(VCH * (HD + 16) + nw * 4 * (16 * (PW / 4 + 4) + 4)) * sizeof(float); };
     if (rag.units.u) {                                              // the engine's units are 32-row blocks: two strips per workgroup
-        const dim3 grid((unsigned)(((n_heads + 7) / 8) * 8 * (int64_t)rag.units.count));
-        static DynLdsSlots slots_r;
-        ensure_dyn_lds(slots_r, reinterpret_cast<const void *>(&relpos_attention_strip_kernel<HD, VCH, 2, PW, true, 4>), lds_bytes(2));
-        hipLaunchKernelGGL((relpos_attention_strip_kernel<HD, VCH, 2, PW, true, 4>), grid, dim3(128), lds_bytes(2), s, qkv, 3 * d, d, rag.T_max, pos, bias_u, bias_v,
-                           scale, ctx, 0, 0, ctx_bf16, pos_row0, rag);
+        att_launch_dyn_lds<relpos_attention_strip_kernel<HD, VCH, 2, PW, true, 4>>(att_grid(0, 0, n_heads, rag), dim3(128), lds_bytes(2), s, qkv, 3 * d, d, rag.T_max,
+                                                                                   pos, bias_u, bias_v, scale, ctx, 0, 0, ctx_bf16, pos_row0, rag);
         return;
     }
     const int n_rb = (T + 16 * NW - 1) / (16 * NW), n_bh = B * n_heads;
-    const dim3 grid(((n_bh + 7) / 8) * 8 * n_rb);
-    static DynLdsSlots slots;
-    ensure_dyn_lds(slots, reinterpret_cast<const void *>(&relpos_attention_strip_kernel<HD, VCH, NW, PW, false, 4>), lds_bytes(NW));
-    hipLaunchKernelGGL((relpos_attention_strip_kernel<HD, VCH, NW, PW, false, 4>), grid, dim3(64 * NW), lds_bytes(NW), s, qkv, 3 * d, d, T, pos, bias_u, bias_v,
-                       scale, ctx, n_rb, n_bh, ctx_bf16, pos_row0, rag);
+    att_launch_dyn_lds<relpos_attention_strip_kernel<HD, VCH, NW, PW, false, 4>>(att_grid(n_bh, n_rb, n_heads, rag), dim3(64 * NW), lds_bytes(NW), s, qkv, 3 * d, d, T,
+                                                                                 pos, bias_u, bias_v, scale, ctx, n_rb, n_bh, ctx_bf16, pos_row0, rag);
 }
 
 void launch_relpos_attention(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u,
@@ -772,22 +471,54 @@ void launch_relpos_attention(const float *qkv, int B, int T, int d, int n_heads,
     if (hd == 64) {
         const int t_lds = rag.units.u ? rag.T_max : T;
         auto occ = [&](int vch) {
-            int pits = (t_lds + 3) / 4;
-            pits = (pits + 3) & ~3;
-            if (((pits / 4) & 1) == 0) pits += 4;
-            const size_t lds = (size_t)(4 * (RB * pits + 8) + vch * (64 + 16)) * sizeof(float);
-            const int n = (int)((size_t)160 * 1024 / lds);
+            const int n = (int)((size_t)160 * 1024 / att_block_lds_bytes(t_lds, 64, vch));
             return n < ATT_OCC ? n : ATT_OCC;
         };
         // (measured on a 5-15 s mixed batch, T_max = 185: 32-row chunks at four workgroups per CU 1.69 ms, 64-row chunks at three without spills 1.77,
         //  64-row chunks at three on the 128-VGPR build 1.85)
         if (!scratch && occ(32) > occ(64)) launch_att<64, 32>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, scratch, ctx_bf16, pos_row0, rag);
-        // LDS allows at most three workgroups per CU whatever the chunk (T > 200): the register budget of three (the kernel needs 134-140 VGPRs: no spills)
+        // LDS allows at most three workgroups per CU whatever the chunk (T > 200): the register budget of three (the kernel needs 128-136 VGPRs: no spills)
         else if (!scratch && occ(64) <= 3) launch_att<64, 64, 3>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, scratch, ctx_bf16, pos_row0, rag);
         else launch_att<64, 64>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, scratch, ctx_bf16, pos_row0, rag);
     } else if (hd == 128) launch_att<128, 32>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, scratch, ctx_bf16, pos_row0, rag);
     else if (hd == 32) launch_att<32, 64>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, scratch, ctx_bf16, pos_row0, rag);
     else if (hd == 96) launch_att<96, 64>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, scale, s, scratch, ctx_bf16, pos_row0, rag);
+}
+
+// ---- the band form's launcher ------------------------------------------------------------------------------------------------------------------
+template <int HD, int VCH, int OCC>
+static void launch_local(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u, const float *bias_v,
+                         float *ctx, hipStream_t s, int ctx_bf16, int left, int right, int W, const SeqRag &rag) {
+    const float scale = 1.0f / sqrtf((float)HD);                   // src/encoder.cpp:126
+    const int n_rb = (T + RB - 1) / RB, n_bh = B * n_heads;
+    auto go = [&](auto ragged) {
+        att_launch_dyn_lds<relpos_attention_kernel<HD, VCH, false, decltype(ragged)::value, OCC, true>>(
+            att_grid(n_bh, n_rb, n_heads, rag), dim3(256), att_block_lds_bytes(W, HD, VCH), s, qkv, 3 * d, d, T, pos, bias_u, bias_v, scale, ctx, att_score_pitch(W),
+            n_rb, n_bh, (float *)nullptr, ctx_bf16, 0, rag, left, right);
+    };
+    if (rag.units.u) go(std::true_type{});
+    else go(std::false_type{});
+}
+
+int relpos_local_attention_max_span(int hd) {
+    if (!att_hd_supported(hd)) return -1;
+    int span = -1;                                                  // left + right: the window of a block is left + right + 32 columns
+    while (att_block_lds_bytes(span + 1 + RB, hd, att_block_vch(hd)) <= 160 * 1024) ++span;
+    return span;
+}
+
+void launch_relpos_local_attention(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u, const float *bias_v,
+                                   float *ctx, hipStream_t s, int ctx_bf16, int left, int right, const SeqRag &rag) {
+    const int hd = d / n_heads;
+    const int t_lds = rag.units.u ? rag.T_max : T;
+    const int W = t_lds < left + right + RB ? t_lds : left + right + RB;   // widest window of any block of the launch (LDS sizing)
+    const int occ = (int)((size_t)160 * 1024 / att_block_lds_bytes(W, hd, att_block_vch(hd)));
+    if (hd == 64) {
+        if (occ >= 4) launch_local<64, 64, 4>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
+        else launch_local<64, 64, 3>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
+    } else if (hd == 128) launch_local<128, 32, 2>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
+    else if (hd == 32) launch_local<32, 64, 4>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
+    else if (hd == 96) launch_local<96, 64, 2>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
 }
 
 }  // namespace pk

@@ -405,7 +405,7 @@ enum { ATT_FORM_AUTO = 0, ATT_FORM_BLOCK = 1, ATT_FORM_STRIP = 2 };
 // -> the form the launch takes (ATT_FORM_BLOCK / ATT_FORM_STRIP), or -1 when `want` does not cover it.  t_longest: T, or rag.T_max.
 int relpos_attention_form(int t_longest, int hd, bool scratch, int want);
 size_t relpos_attention_scratch_bytes_units(int64_t n_units, int T_max, int n_heads, int hd);   // ragged form of relpos_attention_scratch_bytes
-// Limited-context ("band") form, kernels/attention_local.hip: query row i attends to keys [max(0, i - left), min(T - 1, i + right)] only.
+// Limited-context ("band") form, kernels/attention.hip (relpos_attention_kernel with BAND): query row i attends to keys [max(0, i - left), min(T - 1, i + right)] only.
 // qkv as above (fp32, q / k sigma columns), pos = the layer's LOCAL table [left + right + 1][d] (sigma columns; row r = position i - j = left - r).
 // rag set (units = 32-row blocks): packed rows, per-utterance T; the local table is the same for every utterance.  ctx_bf16: 0 fp32, 1 bf16, 2 fp32 sigma.
 // Every block's score block is [32][<= left + right + 32] in LDS: left + right <= relpos_local_attention_max_span(hd) (-1: unsupported head size).

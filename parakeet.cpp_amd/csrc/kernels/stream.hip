@@ -159,7 +159,7 @@ __global__ __launch_bounds__(128) void stream_attention_kernel(const float *__re
         }
         auto put = [&](int e, float acc) {                          // ctx_sigma: the out-projection reads its A operand in the sigma K layout
             const int col = h * hd + e;
-            ctx[((int64_t)sidx * c + i) * d + (ctx_sigma ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col)] = acc;
+            ctx[((int64_t)sidx * c + i) * d + (ctx_sigma ? sigma_col(col) : col)] = acc;
         };
         SA_STAMP(4);                                                // value rows loaded, chains done
         if (h0) put(e0, acc0);
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         float acc = 0.0f;
         for (int u = 0; u < kv; ++u) acc = __builtin_fmaf(pr[u], Kt[u * PITCH + tid], acc);    // (the value tile; consecutive lanes, consecutive banks)
         const int col = h * HD + tid;
-        ctx[((int64_t)sidx * c + i) * d + (ctx_sigma ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col)] = acc;
+        ctx[((int64_t)sidx * c + i) * d + (ctx_sigma ? sigma_col(col) : col)] = acc;
     }
     SA_STAMP(4);
     SA_STAMP(5);

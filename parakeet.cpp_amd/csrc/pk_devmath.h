@@ -11,6 +11,9 @@
 
 namespace pk {
 
+// The "sigma" column layout (kernels.hpp: GemmArgs::sigma_cols): inside every block of 16 features the 4x4 index matrix is transposed.
+__device__ __forceinline__ int sigma_col(int col) { return (col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3); }
+
 // e^x.  n = rne(x*log2e) by the 1.5*2^23 trick; r = x - n*ln2 in two parts; e^r = 1 + (r + r^2 E(r));
 // result scaled by 2^n in two exact steps (n/2 floor, remainder).  > 88.7228 -> +inf, < -87.3365 -> 0.
 __device__ __forceinline__ float dexpf(float x) {

@@ -54,6 +54,10 @@ def _fp32_cases():
     cases.append(("fp32", "pos", 128, 1, 1, None, 1999, 2100, 96))
     cases.append(("fp32", "random", 128, 2, 1, [1, 129, 33, 376, 128], None, 400, None))
     cases.append(("fp32", "c", 64, 2, 1, [1200, 33, 300, 2, 2], None, 1300, 64))                   # one clip past the LDS limit: ragged + scratch
+    # hd 64, uniform: the two ends of the lengths whose block form runs the 32-row V chunk (one more resident workgroup than the 64-row chunk
+    # allows), and the first length of the three-workgroups-per-CU build
+    for n, T in enumerate((133, 200, 201)):
+        cases.append(("fp32", ("large", "random", "pos")[n], 64, 2, 2, None, T, (T, T + 5, T)[n], None))
     return cases
 
 

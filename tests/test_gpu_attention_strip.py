@@ -4,7 +4,12 @@ the block form it replaces for short sequences, through pk_diag_relpos_attention
 The strip form changes the data flow, not the arithmetic: every case runs both forms on the same inputs and requires ctx -- guard rows
 included -- to be byte-identical.  A handful of shapes are also held against the float64 reference of tests/attention_ref.py (every valid
 element inside its bound, no guard row touched), and the form selector is checked: shapes the strip form does not cover run the block form
-by default and refuse a forced strip launch."""
+by default and refuse a forced strip launch.
+
+The block form itself is no longer reached by default below 129 frames, so it is held against float64 here too, forced: T in {1, 17, 32, 33,
+126} and one ragged batch, hd 64 and 128, with and without the position table, in the three ctx layouts."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -89,3 +94,41 @@ def test_uncovered_shapes_keep_the_block_form(hd, H, T, lens):
     assert ran == "block"
     with pytest.raises(capi.PkError):
         capi.diag_relpos_attention_form("strip", qkv, pos, bu, bv, H, B=1, lens=lens)
+
+
+# ---- the block form forced below 129 frames, against float64 ------------------------------------------------------------------------------
+BLOCK_LENS = [(1,), (17,), (32,), (33,), (126,), (1, 128, 33, 17)]
+BLOCK_CASES = [(hd, lens, with_pos, mode) for hd in (64, 128) for lens in BLOCK_LENS for with_pos in (True, False) for mode in ("fp32", "bf16", "sigma")]
+
+
+@functools.lru_cache(maxsize=None)
+def _block_reference(hd, lens, with_pos):
+    """inputs and the float64 reference of one shape, shared by its three output layouts.  Without the table the kernel computes
+    softmax(q K^T / sqrt(hd)) V: the reference's definition with a zero table and zero biases."""
+    H, ln = 2, list(lens)
+    n = BLOCK_LENS.index(lens)
+    qkv, pos, bu, bv = ar.make_inputs(("random", "large", "key")[(n + hd // 64) % 3], ln, hd * H, H, max(ln) + (0, 3)[n % 2], 8000 + 2 * n + with_pos)
+    if not with_pos:
+        pos, bu, bv = np.zeros_like(pos), np.zeros_like(bu), np.zeros_like(bv)
+    ref = ar.reference("fp32", qkv, pos, bu, bv, H, B=1, lens=ln if len(ln) > 1 else None, max_rows=None)
+    vmax = [float(np.abs(qkv[:, 2 * hd * H + h * hd: 2 * hd * H + (h + 1) * hd]).max()) for h in range(H)]
+    return qkv, pos, bu, bv, ref, vmax
+
+
+@pytest.mark.parametrize("case", BLOCK_CASES, ids=[f"hd{c[0]}-lens{'-'.join(map(str, c[1]))}-{'pos' if c[2] else 'nopos'}-{c[3]}" for c in BLOCK_CASES])
+def test_forced_block_vs_float64(case):
+    hd, lens, with_pos, mode = case
+    H = 2
+    qkv, pos, bu, bv, ref, vmax = _block_reference(hd, lens, with_pos)
+    args = (qkv, pos, bu, bv) if with_pos else (qkv, None, None, None)
+    got, ran = capi.diag_relpos_attention_form("block", *args, H, B=1, lens=list(lens) if len(lens) > 1 else None, out_mode=mode)
+    assert ran == "block"
+    if mode == "sigma":                                                        # the layout is its own inverse: back to natural columns
+        got = got[:, capi.sigma16(got.shape[1])]
+    if mode == "bf16":
+        # the bf16 layout's extra roundings: ctx rounded to bf16 (u16 |ctx|), one hardware reciprocal and a multiplication in place of the
+        # division (2^-21 A, A = sum_j p_j |v_jc| <= max |v| of the head); the hardware exp2 is inside the reference's 2^-21 already
+        ref = [(rows, h, ctx, bound + ar.U16 * np.abs(ctx) + ar.E_EXP * vmax[h], sigma + ar.U16 / 2 * np.abs(ctx)) for rows, h, ctx, bound, sigma in ref]
+    what = f"block hd{hd} lens {lens} {'pos' if with_pos else 'no pos'} {mode}"
+    worst, mean = ar.check("bf16" if mode == "bf16" else "fp32", got, ref, H, qkv.shape[0], what)
+    print(f"\n{what:>50}  max err/bound {worst:.4f}  mean err/sigma {mean:.4f}", end="")

@@ -14,7 +14,7 @@ from parakeet_cpp_amd import capi
 pytestmark = pytest.mark.gpu
 
 RAGGED, BAND, BF16_OUT = 2, 8, 16
-# kernels/attention_local.hip relpos_local_attention_max_span(hd): the widest left + right whose [32][left + right + 32] score block fits LDS
+# kernels/attention.hip relpos_local_attention_max_span(hd): the widest left + right whose [32][left + right + 32] score block fits LDS
 MAX_SPAN = {32: 1136, 64: 1072, 96: 1008, 128: 1072}
 PK_ERR_INVALID, PK_ERR_UNSUPPORTED = -1, -7
 
@@ -45,6 +45,17 @@ def test_covering_window_bit_equal_to_full_kernel(case):
     g, w = _bits(loc), _bits(full)
     bad = np.argwhere(g != w)
     assert bad.size == 0, f"{len(bad)} elements differ from the full kernel; first at {tuple(bad[0])}: {loc[tuple(bad[0])]!r} vs {full[tuple(bad[0])]!r}"
+
+
+def test_covering_window_bit_equal_to_forced_block_form():
+    """at T <= 128 the full kernel above is the strip form by default: the band form is also pinned to the BLOCK form it is an instantiation of"""
+    hd, H, T, left, right = 64, 2, 65, 64, 64
+    qkv, pos, bu, bv = ar.make_inputs("random", [T], hd * H, H, T, 600)
+    block, ran = capi.diag_relpos_attention_form("block", qkv, pos, bu, bv, H, B=1)
+    loc, vl = capi.diag_relpos_local_attention(qkv, lr.local_table(pos, T, left, right), bu, bv, H, left, right, B=1)
+    assert ran == "block" and vl == BAND
+    bad = np.argwhere(_bits(loc) != _bits(block))
+    assert bad.size == 0, f"{len(bad)} elements differ from the block form; first at {tuple(bad[0])}"
 
 
 def _cases():
