@@ -687,6 +687,39 @@ pk_status pk_ctc_kws_decode_timed(pk_model *m, const float *enc, const int32_t *
 pk_status pk_spot_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *phrases_or_null,
                       const int32_t *ids_or_null, const int32_t *kw_offsets, int n_kw, const pk_kws_options *opt, int32_t *n_hits, float *start_s,
                       float *end_s, float *score);
+/* ---- Keyword spotting through the TDT head (kernels/tdt_kws.hip; specification: tests/tdt_kws_ref.py) ----------
+ * The same question for a model without a CTC head.  Every (clip, keyword) pair has the lattice of pk_tdt_align, the prediction net teacher-forced
+ * over [blank, keyword...] FROM ITS INITIAL STATE: the keyword is scored as if it began the utterance (a known approximation).  An arc costs its
+ * log-prob relative to the greedy decision of its cell (token head: minus the row's largest log-prob `top`; duration head: minus its largest), the
+ * match may begin at any frame and ends on the last token's label arc at any frame.  A score is <= 0 and exactly +0.0 where greedy decoding with
+ * this context emits the keyword there.  start = the frame at which the first token is emitted (pk_tdt_align's start[0]), end = the last frame of
+ * the last token (its end[L - 1]).  pk_kws_options and the picking are those of the CTC form.
+ * Refusals: PK_ERR_INVALID as pk_ctc_kws; PK_ERR_UNSUPPORTED, before anything is allocated: a keyword of more than 64 tokens, max_hits outside
+ * 1 .. 16, D outside 1 .. 8 or a duration outside [0, 8], a pair whose own scratch exceeds 1 GiB, an RNN-T head, a gemm_bf16 model.
+ *
+ * pk_tdt_kws: the walk and the picking alone on HOST lattices, one per pair, packed as for pk_tdt_align (pair b: n_frames[b] frames, a keyword of
+ * id_offsets[b + 1] - id_offsets[b] >= 1 tokens; column L is packed and never read) plus top, packed like blk.  Every read row needs a finite top
+ * >= its lab and blk and one finite duration log-prob.  n_hits [B]; start / end / score [B][max_hits].  Needs a device, no model. */
+pk_status pk_tdt_kws(const float *lab, const float *blk, const float *dl, const float *top, const int32_t *durations, int D, const int32_t *n_frames,
+                     int B, const int32_t *id_offsets, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score);
+/* enc_proj, the prediction net (once per distinct keyword), the lattice in chunks, the walk and the picking on the model's stream.  Arguments and
+ * results as pk_ctc_kws_decode(_ragged): every keyword in every clip, n_hits [B][n_kw], start / end / score [B][n_kw][max_hits]. */
+pk_status pk_tdt_kws_decode(pk_model *m, const float *enc, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
+                            const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score);
+pk_status pk_tdt_kws_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *kw_ids, const int32_t *kw_offsets,
+                                   int n_kw, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score);
+/* Stage timers (tools/bench_tdt_kws.py), as pk_tdt_total_decode_timed: ms[0] = prediction net (with the uploads of the tables), ms[1] = lattice,
+ * ms[2] = normalisation + walk + picking, each summed over the groups of the call; medians of `reps` passes after one warm-up. */
+pk_status pk_tdt_kws_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids,
+                                  const int32_t *kw_offsets, int n_kw, const pk_kws_options *opt, int reps, float ms[3]);
+/* pk_spot_pcm through the TDT head: same batch loop, same seconds rule, same input-rate handling, same result layout. */
+pk_status pk_tdt_spot_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *phrases_or_null,
+                          const int32_t *ids_or_null, const int32_t *kw_offsets, int n_kw, const pk_kws_options *opt, int32_t *n_hits, float *start_s,
+                          float *end_s, float *score);
+/* Diagnostic: the spotting's lattice BEFORE the normalisation, as pk_diag_tdt_lattice returns the alignment's (utterance b with its own token string
+ * of >= 1 tokens; the guard words and chunk_rows as there), plus top: cells + PK_DIAG_TDT_LATTICE_GUARD floats.  The call must fit one group. */
+pk_status pk_diag_tdt_kws_lattice(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                                  int chunk_rows, float *lab, float *blk, float *dl, float *top);
 
 /* ---- one node, several GPUs: utterance shards (the reference has no multi-device path, README.md:513) ----------
  * A pk_group is one model REPLICA per device of this process: the safetensors file is mapped once and every replica is built from that

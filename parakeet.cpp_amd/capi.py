@@ -265,6 +265,12 @@ _LATE_SIGNATURES = {
     "pk_ctc_kws_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
     "pk_ctc_kws_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), C.c_int, f32p],
     "pk_spot_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, f32p, f32p, f32p],
+    "pk_tdt_kws": [f32p, f32p, f32p, f32p, i32p, C.c_int, i32p, C.c_int, i32p, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
+    "pk_tdt_kws_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
+    "pk_tdt_kws_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
+    "pk_tdt_kws_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), C.c_int, f32p],
+    "pk_tdt_spot_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, f32p, f32p, f32p],
+    "pk_diag_tdt_kws_lattice": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, f32p, f32p, f32p, f32p],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -582,6 +588,23 @@ def ctc_kws(logp, keywords, blank, max_hits=None, min_score=None):
     o = kws_options(max_hits, min_score)
     rag, lp, T = _enc_head(logp)
     return _kws_call(lib().pk_ctc_kws, (_f(lp), _i(T) if rag else None, len(T), 0 if rag else lp.shape[1], lp.shape[-1], blank), len(T), keywords, o)
+
+
+# ---- TDT keyword spotting (include/parakeet_amd.h) -----------------------------
+def tdt_kws(lattices, durations, max_hits=None, min_score=None):
+    """pk_tdt_kws: lattices = one (lab [T][L], blk [T][L+1], dl [T][L+1][D], top [T][L+1]) per (clip, keyword) pair -> dict of n_hits [B],
+    start / end / score [B][max_hits] (unused slots 0 / 0 / -inf).  Needs a device, no model."""
+    o = kws_options(max_hits, min_score)
+    T = np.asarray([x[1].shape[0] for x in lattices], np.int32)
+    off = np.zeros(len(lattices) + 1, np.int32)
+    off[1:] = np.cumsum([x[1].shape[1] - 1 for x in lattices])
+    cat = lambda k: _c(np.concatenate([_c(x[k]).ravel() for x in lattices] + [np.zeros(1, np.float32)]))
+    lab, blk, dl, top = cat(0), cat(1), cat(2), cat(3)
+    dur = np.ascontiguousarray(durations, np.int32)
+    B, H = len(T), max(1, o.max_hits)
+    nh = np.zeros(B, np.int32); st = np.zeros((B, H), np.int32); en = np.zeros((B, H), np.int32); sc = np.zeros((B, H), np.float32)
+    check(lib().pk_tdt_kws(_f(lab), _f(blk), _f(dl), _f(top), _i(dur), len(dur), _i(T), B, _i(off), C.byref(o), _i(nh), _i(st), _i(en), _f(sc)))
+    return dict(n_hits=nh, start=st, end=en, score=sc)
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -2584,6 +2607,51 @@ class Model:
         tail = _transcript_args(phrases, ids, K)
         nh = np.zeros((n, K), np.int32); st = np.zeros((n, K, H), np.float32); en = np.zeros((n, K, H), np.float32); sc = np.zeros((n, K, H), np.float32)
         check(lib().pk_spot_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, K, C.byref(o), _i(nh), _f(st), _f(en), _f(sc)))
+        return [[[(float(st[c, k, j]), float(en[c, k, j]), float(sc[c, k, j])) for j in range(nh[c, k])] for k in range(K)] for c in range(n)]
+
+    def tdt_kws_decode(self, enc, keywords, max_hits=None, min_score=None):
+        """pk_tdt_kws_decode(_ragged): ctc_kws_decode through the TDT head (no CTC head needed) -> as ctc_kws."""
+        o = kws_options(max_hits, min_score)
+        rag, x, T = _enc_head(enc)
+        return _kws_call(lib().pk_tdt_kws_decode_ragged if rag else lib().pk_tdt_kws_decode, self._rows_head(rag, x, T), len(T), keywords, o)
+
+    def tdt_kws_decode_timed(self, enc, keywords, max_hits=None, min_score=None, reps=5):
+        """pk_tdt_kws_decode_timed -> (prediction net ms, lattice ms, walk + picking ms), HIP events, medians of reps passes."""
+        o = kws_options(max_hits, min_score)
+        pid, poff = _pack_ids(keywords)
+        ms = np.zeros(3, np.float32)
+        check(lib().pk_tdt_kws_decode_timed(*self._timed_head(enc), _i(pid), _i(poff), len(keywords), C.byref(o), reps, _f(ms)))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def tdt_kws_lattice(self, enc, ids, chunk_rows=0):
+        """pk_diag_tdt_kws_lattice: as tdt_lattice, every dict with "top" [T][U+1] too, before the spotting's normalisation."""
+        _, x, T = _enc_head(enc)
+        pid, off = _pack_ids(ids)
+        U = np.diff(off).astype(np.int64)
+        D = len(self.cfg.durations)
+        cells, labs = int((T * (U + 1)).sum()), int((T * U).sum())
+        G = TDT_LATTICE_GUARD
+        lab = np.zeros(labs + G, np.float32); blk = np.zeros(cells + G, np.float32); dl = np.zeros(cells * D + G, np.float32)
+        top = np.zeros(cells + G, np.float32)
+        check(lib().pk_diag_tdt_kws_lattice(self._h, _f(x), _i(T), len(T), _i(pid), _i(off), int(chunk_rows), _f(lab), _f(blk), _f(dl), _f(top)))
+        out, c0, l0 = [], 0, 0
+        for b in range(len(T)):
+            t, u = int(T[b]), int(U[b])
+            out.append(dict(lab=lab[l0:l0 + t * u].reshape(t, u).copy(), blk=blk[c0:c0 + t * (u + 1)].reshape(t, u + 1).copy(),
+                            dl=dl[c0 * D:(c0 + t * (u + 1)) * D].reshape(t, u + 1, D).copy(), top=top[c0:c0 + t * (u + 1)].reshape(t, u + 1).copy()))
+            c0 += t * (u + 1); l0 += t * u
+        guard = np.concatenate([lab[labs:], blk[cells:], dl[cells * D:], top[cells:]]).view(np.uint32)
+        return out, guard
+
+    def spot_tdt(self, clips, phrases=None, ids=None, max_hits=None, min_score=None):
+        """pk_tdt_spot_pcm: Model.spot through the TDT head (no CTC head needed) -> as spot()."""
+        assert (phrases is None) != (ids is None), "phrases or ids"
+        pcm, off, n = _clips(clips)
+        o = kws_options(max_hits, min_score)
+        K, H = len(phrases if phrases is not None else ids), max(1, o.max_hits)
+        tail = _transcript_args(phrases, ids, K)
+        nh = np.zeros((n, K), np.int32); st = np.zeros((n, K, H), np.float32); en = np.zeros((n, K, H), np.float32); sc = np.zeros((n, K, H), np.float32)
+        check(lib().pk_tdt_spot_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *tail, K, C.byref(o), _i(nh), _f(st), _f(en), _f(sc)))
         return [[[(float(st[c, k, j]), float(en[c, k, j]), float(sc[c, k, j])) for j in range(nh[c, k])] for k in range(K)] for c in range(n)]
 
     def ctc_beam_decode_timed(self, enc, beam_width=None, token_prune=None, n_best=None, timestamps=False, reps=5, lm=None, lm_alpha=None, lm_beta=None):

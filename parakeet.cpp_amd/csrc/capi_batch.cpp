@@ -1317,6 +1317,75 @@ pk_status pk_tdt_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets
     });
 }
 
+}  // extern "C"
+
+// The body of pk_spot_pcm and pk_tdt_spot_pcm: the keywords (phrases or ids), the batches of pk_transcribe_pcm, the head's spotting on every batch's
+// rows, frames to seconds.  tdt: through the TDT head (tdt_kws.hpp) instead of the CTC head's log-probs.
+static void spot_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offsets, int n_clips, const char *const *phrases, const int32_t *ids_in,
+                     const int32_t *kw_offsets_in, int n_kw, const pk_kws_options *opt, int32_t *n_hits, float *start_s, float *end_s, float *score) {
+    const char *what = tdt ? "TDT keyword spotting" : "CTC keyword spotting";
+    const int V = tdt ? m.cfg.vocab_size : m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;
+    const pk_kws_options o = kws_options_of(opt);
+    std::vector<int32_t> ids, off;                             // the keywords, packed; the same for every batch
+    if (phrases) {
+        need(n_kw >= 1, "n_kw");
+        need(m.tok.loaded(), "spotting phrases needs the model's vocabulary");
+        off.assign(1, 0);
+        for (int k = 0; k < n_kw; ++k) {
+            need(phrases[k] != nullptr, "phrases[k]");
+            for (int v : m.tok.encode(phrases[k])) ids.push_back(v);
+            off.push_back((int32_t)ids.size());
+        }
+        ids.push_back(0);                                      // (never read: keeps data() non-null for a list of empty phrases)
+        kws_check_args(ids.data(), off.data(), n_kw, n_clips, V, blank, o, what);
+    } else {
+        kws_check_args(ids_in, kw_offsets_in, n_kw, n_clips, V, blank, o, what);
+        off.assign(kw_offsets_in, kw_offsets_in + n_kw + 1);
+        ids.assign(ids_in, ids_in + off[n_kw]);
+    }
+    m.require_gpu();
+    const size_t H = (size_t)o.max_hits, per_clip = (size_t)n_kw * H;
+    std::vector<int32_t> nfr, nh, st, en;
+    std::vector<float> sc;
+    for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/!tdt, every_batch, [&](const RagBatch &rb, int nc) {
+        nfr.assign(rb.T.begin(), rb.T.begin() + nc);                                // (the plan refuses before the batch is encoded)
+        if (tdt) tdt_kws_plan_call(m.tkws, m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden, nfr.data(), nc, 0, ids.data(), off.data(),
+                                   n_kw, nullptr, nullptr, nc * n_kw, o);
+        else kws_plan(m.kws, nfr.data(), nc, rb.T_max, off.data(), n_kw, o);
+    }, [&](const int *clip, int nc, const RagBatch &r) {
+        const int32_t *bnh, *bst, *ben;
+        const float *bsc;
+        if (tdt) {
+            m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
+            run_tdt_kws_call(m, m.tkws, m.ws.ep.as<float>(), ids.data(), off.data());
+            PK_CHECK_LAUNCH();
+            bnh = m.tkws.n_hits.data(); bst = m.tkws.start.data(); ben = m.tkws.end.data(); bsc = m.tkws.score.data();
+        } else {
+            run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, ids.data(), m.stream);
+            PK_CHECK_LAUNCH();
+            nh.resize((size_t)nc * n_kw); st.resize(nc * per_clip); en.resize(nc * per_clip); sc.resize(nc * per_clip);
+            kws_copy_out(m.kws, nh.data(), st.data(), en.data(), sc.data(), m.stream);
+            bnh = nh.data(); bst = st.data(); ben = en.data(); bsc = sc.data();
+        }
+        for (int i = 0; i < nc; ++i) {
+            const size_t c = (size_t)clip[i];
+            for (int q = 0; q < n_kw; ++q) {
+                const int n = bnh[(size_t)i * n_kw + q];
+                n_hits[c * n_kw + q] = n;
+                for (size_t j = 0; j < H; ++j) {
+                    const size_t src = i * per_clip + q * H + j, dst = c * per_clip + q * H + j;
+                    const bool hit = (int)j < n;
+                    start_s[dst] = hit ? frame_to_seconds(bst[src]) : 0.0f;
+                    end_s[dst] = hit ? frame_to_seconds(ben[src] + 1) : 0.0f;       // the END of the last frame
+                    score[dst] = bsc[src];
+                }
+            }
+        }
+    });
+}
+
+extern "C" {
+
 pk_status pk_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *phrases, const int32_t *ids_in,
                       const int32_t *kw_offsets_in, int n_kw, const pk_kws_options *opt, int32_t *n_hits, float *start_s, float *end_s, float *score) {
     return guard([&] {
@@ -1324,52 +1393,18 @@ pk_status pk_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int
         need(phrases || (ids_in && kw_offsets_in), "phrases or ids/kw_offsets");
         Model &m = *h->m;
         if (m.cfg.ctc_vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no ctc_decoder_ head: CTC keyword spotting needs one");
-        const int V = m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;
-        const pk_kws_options o = kws_options_of(opt);
-        std::vector<int32_t> ids, off;                             // the keywords, packed; the same for every batch
-        if (phrases) {
-            need(n_kw >= 1, "n_kw");
-            need(m.tok.loaded(), "spotting phrases needs the model's vocabulary");
-            off.assign(1, 0);
-            for (int k = 0; k < n_kw; ++k) {
-                need(phrases[k] != nullptr, "phrases[k]");
-                for (int v : m.tok.encode(phrases[k])) ids.push_back(v);
-                off.push_back((int32_t)ids.size());
-            }
-            ids.push_back(0);                                      // (never read: keeps data() non-null for a list of empty phrases)
-            kws_check_args(ids.data(), off.data(), n_kw, n_clips, V, blank, o);
-        } else {
-            kws_check_args(ids_in, kw_offsets_in, n_kw, n_clips, V, blank, o);
-            off.assign(kw_offsets_in, kw_offsets_in + n_kw + 1);
-            ids.assign(ids_in, ids_in + off[n_kw]);
-        }
-        m.require_gpu();
-        const size_t H = (size_t)o.max_hits, per_clip = (size_t)n_kw * H;
-        std::vector<int32_t> nfr, nh, st, en;
-        std::vector<float> sc;
-        for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/true, every_batch, [&](const RagBatch &rb, int nc) {
-            nfr.assign(rb.T.begin(), rb.T.begin() + nc);
-            kws_plan(m.kws, nfr.data(), nc, rb.T_max, off.data(), n_kw, o);         // (refuses before the batch is encoded)
-        }, [&](const int *clip, int nc, const RagBatch &r) {
-            run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, ids.data(), m.stream);
-            PK_CHECK_LAUNCH();
-            nh.resize((size_t)nc * n_kw); st.resize(nc * per_clip); en.resize(nc * per_clip); sc.resize(nc * per_clip);
-            kws_copy_out(m.kws, nh.data(), st.data(), en.data(), sc.data(), m.stream);
-            for (int i = 0; i < nc; ++i) {
-                const size_t c = (size_t)clip[i];
-                for (int q = 0; q < n_kw; ++q) {
-                    const int n = nh[(size_t)i * n_kw + q];
-                    n_hits[c * n_kw + q] = n;
-                    for (size_t j = 0; j < H; ++j) {
-                        const size_t src = i * per_clip + q * H + j, dst = c * per_clip + q * H + j;
-                        const bool hit = (int)j < n;
-                        start_s[dst] = hit ? frame_to_seconds(st[src]) : 0.0f;
-                        end_s[dst] = hit ? frame_to_seconds(en[src] + 1) : 0.0f;     // the END of the last frame
-                        score[dst] = sc[src];
-                    }
-                }
-            }
-        });
+        spot_pcm(m, false, pcm, offsets, n_clips, phrases, ids_in, kw_offsets_in, n_kw, opt, n_hits, start_s, end_s, score);
+    });
+}
+
+pk_status pk_tdt_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *phrases, const int32_t *ids_in,
+                          const int32_t *kw_offsets_in, int n_kw, const pk_kws_options *opt, int32_t *n_hits, float *start_s, float *end_s, float *score) {
+    return guard([&] {
+        need(h && pcm && offsets && n_hits && start_s && end_s && score && n_clips > 0, "model/pcm/offsets/n_hits/start_s/end_s/score/n_clips");
+        need(phrases || (ids_in && kw_offsets_in), "phrases or ids/kw_offsets");
+        Model &m = *h->m;
+        tdt_align_model_checks(m);
+        spot_pcm(m, true, pcm, offsets, n_clips, phrases, ids_in, kw_offsets_in, n_kw, opt, n_hits, start_s, end_s, score);
     });
 }
 

@@ -1462,7 +1462,7 @@ pk_status pk_diag_mem_info(pk_model *h, uint64_t out[3]) {
         if (h) {
             const Model &m = *h->m;
             const Workspace &w = m.ws;
-            size_t n = tdt_align_bytes(m.talign) + tdt_total_bytes(m.ttotal) + tdt_beam_bytes(m.tbeam) + kws_bytes(m.kws) + vad_bytes(m.vad);
+            size_t n = tdt_align_bytes(m.talign) + tdt_total_bytes(m.ttotal) + tdt_beam_bytes(m.tbeam) + kws_bytes(m.kws) + tdt_kws_bytes(m.tkws) + vad_bytes(m.vad);
             for (const DevBuf *b : {&w.pcm, &w.logmel, &w.feats, &w.a2, &w.a3, &w.a4, &w.a5, &w.flat, &w.x, &w.n, &w.hbuf, &w.qkv, &w.ctx, &w.g, &w.dwb, &w.ctc_logits,
                                     &w.ctc_lp, &w.best_idx, &w.best_lp, &w.ep, &w.gh, &w.gi, &w.pp, &w.z, &w.logits, &w.h, &w.c, &w.hn, &w.cn, &w.ints, &w.ids, &w.start,
                                     &w.end, &w.conf, &w.lens, &w.margin, &w.persist_bar, &w.trie_act, &w.ragdev, &m.io_in, &m.io_out, &m.io_tmp})

@@ -1,6 +1,7 @@
 // parakeet.cpp_amd/csrc/capi_stages.cpp -- the stage entry points of the C boundary on caller buffers: mel, subsample, encode, conformer blocks,
-// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix and TDT beam searches, the CTC and TDT forced alignments and the CTC keyword spotting.
+// CTC / TDT decode and scoring (uniform and ragged forms), the CTC prefix and TDT beam searches, the CTC and TDT forced alignments and the CTC and TDT keyword spotting.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "capi_util.hpp"
@@ -1033,6 +1034,162 @@ pk_status pk_ctc_kws_decode_timed(pk_model *h, const float *enc, const int32_t *
             run_ctc_kws(m.kws, m.ws.ctc_lp.as<float>(), B, T, rag, V, blank, kw_ids, m.stream);
             PK_HIP(hipEventRecord(ev[2], m.stream));
         });
+    });
+}
+
+}  // extern "C"
+
+/* ---- TDT keyword spotting (kernels/tdt_kws.hip) ---------------------------------------------------------------------------------------- */
+// the checks of the model entry points; -> after them the call is planned (host only) in m.tkws
+static void tdt_kws_checks(Model &m, const int32_t *n_frames, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
+                           const pk_kws_options &o) {
+    tdt_align_model_checks(m);
+    kws_check_args(kw_ids, kw_offsets, n_kw, B, m.cfg.vocab_size, m.cfg.blank_id, o, "TDT keyword spotting");
+    if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+    m.require_gpu();
+    tdt_kws_plan_call(m.tkws, m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden, n_frames, B, T, kw_ids, kw_offsets, n_kw, nullptr,
+                      nullptr, B * n_kw, o);
+}
+
+// uploads enc, runs enc_proj ONCE over the clips' rows, then the planned groups
+static void tdt_kws_run(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets,
+                        hipEvent_t *ev = nullptr, float *ms = nullptr) {
+    size_t rows;
+    size_ws(m, n_frames, B, T, rows);
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
+    run_tdt_kws_call(m, m.tkws, m.ws.ep.as<float>(), kw_ids, kw_offsets, 0, true, ev, ms);
+    PK_CHECK_LAUNCH();
+}
+
+static void tdt_kws_decode(Model &m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
+                           const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    tdt_kws_checks(m, n_frames, B, T, kw_ids, kw_offsets, n_kw, kws_options_of(opt));
+    tdt_kws_run(m, enc, n_frames, B, T, kw_ids, kw_offsets);
+    const TdtKwsWs &ws = m.tkws;
+    std::copy(ws.n_hits.begin(), ws.n_hits.end(), n_hits);
+    std::copy(ws.start.begin(), ws.start.end(), start);
+    std::copy(ws.end.begin(), ws.end.end(), end);
+    std::copy(ws.score.begin(), ws.score.end(), score);
+}
+
+extern "C" {
+
+pk_status pk_tdt_kws(const float *lab, const float *blk, const float *dl, const float *top, const int32_t *durations, int D, const int32_t *n_frames,
+                     int B, const int32_t *id_offsets, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    return guard([&] {
+        const pk_kws_options o = kws_options_of(opt);
+        tdt_host_lattice_checks(durations, n_frames, B, id_offsets);
+        need(lab && blk && dl && top && n_hits && start && end && score, "lab/blk/dl/top/n_hits/start/end/score");
+        if (std::isnan(o.min_score) || o.min_score > 0.0f)
+            fail(PK_ERR_INVALID, "invalid argument: min_score %g: a score is a log-ratio <= 0, so min_score must be <= 0", (double)o.min_score);
+        for (int b = 0; b < B; ++b) {
+            if (id_offsets[b + 1] == id_offsets[b]) fail(PK_ERR_INVALID, "invalid argument: keyword %d is empty", b);
+            if (id_offsets[b + 1] - id_offsets[b] > kKwsMaxLen)
+                fail(PK_ERR_UNSUPPORTED, "TDT keyword spotting: %d tokens in keyword %d, at most %d can be spotted", id_offsets[b + 1] - id_offsets[b], b,
+                     kKwsMaxLen);
+        }
+        if (o.max_hits < 1 || o.max_hits > kKwsMaxHits)
+            fail(PK_ERR_UNSUPPORTED, "TDT keyword spotting: max_hits = %d, supported 1 .. %d", o.max_hits, kKwsMaxHits);
+        TdtKwsWs ws;
+        ws.max_hits = o.max_hits; ws.min_score = o.min_score;
+        // (the plan and the cap are host only: they refuse before a device is looked for or anything is allocated)
+        tdt_lattice_plan(ws.a, n_frames, nullptr, B, 0, id_offsets, durations, D, 0, 0, 0, /*back_pointers=*/false, "TDT keyword spotting");
+        if (tdt_kws_scratch(ws.a.cells, ws.a.labs, B, ws.a.u_max, D, 0, 0) > kTdtAlignMaxScratch)
+            fail(PK_ERR_UNSUPPORTED, "TDT keyword spotting: the scratch of this call (lattice values, exit rows) exceeds the cap of %zu bytes",
+                 kTdtAlignMaxScratch);
+        need_device();
+        tdt_lattice_upload(ws.a, nullptr, nullptr, /*token_results=*/false);
+        ws.top.reserve((size_t)ws.a.cells * 4);
+        PK_HIP(hipMemcpyAsync(ws.a.lab.p, lab, (size_t)ws.a.labs * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.a.blk.p, blk, (size_t)ws.a.cells * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.a.dl.p, dl, (size_t)ws.a.cells * D * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.top.p, top, (size_t)ws.a.cells * 4, hipMemcpyHostToDevice, nullptr));
+        run_tdt_kws_dp(ws, nullptr);
+        PK_CHECK_LAUNCH();
+        const size_t H = (size_t)o.max_hits;
+        ws.n_hits.assign(B, 0); ws.start.assign(B * H, 0); ws.end.assign(B * H, 0); ws.score.assign(B * H, 0.0f);
+        tdt_kws_gather(ws, 0, nullptr);
+        std::copy(ws.n_hits.begin(), ws.n_hits.end(), n_hits);
+        std::copy(ws.start.begin(), ws.start.end(), start);
+        std::copy(ws.end.begin(), ws.end.end(), end);
+        std::copy(ws.score.begin(), ws.score.end(), score);
+    });
+}
+
+pk_status pk_tdt_kws_decode(pk_model *h, const float *enc, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
+                            const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    return guard([&] {
+        need(h && enc && n_hits && start && end && score && T > 0, "model/enc/n_hits/start/end/score/T");
+        tdt_kws_decode(*h->m, enc, nullptr, B, T, kw_ids, kw_offsets, n_kw, opt, n_hits, start, end, score);
+    });
+}
+
+pk_status pk_tdt_kws_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *kw_ids, const int32_t *kw_offsets,
+                                   int n_kw, const pk_kws_options *opt, int32_t *n_hits, int32_t *start, int32_t *end, float *score) {
+    return guard([&] {
+        need(h && enc && n_frames && n_hits && start && end && score, "model/enc/n_frames/n_hits/start/end/score");
+        tdt_kws_decode(*h->m, enc, n_frames, B, 0, kw_ids, kw_offsets, n_kw, opt, n_hits, start, end, score);
+    });
+}
+
+pk_status pk_tdt_kws_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *kw_ids,
+                                  const int32_t *kw_offsets, int n_kw, const pk_kws_options *opt, int reps, float ms[3]) {
+    return guard([&] {
+        need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
+        Model &m = *h->m;
+        tdt_kws_checks(m, n_frames, B, T, kw_ids, kw_offsets, n_kw, kws_options_of(opt));
+        Events<4> ev;
+        ev.create();
+        std::vector<float> t[3];
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            float v[3] = {0, 0, 0};                                // per stage, summed over the groups of the call
+            tdt_kws_run(m, enc, n_frames, B, T, kw_ids, kw_offsets, ev.e, v);
+            if (r > 0) for (int k = 0; k < 3; ++k) t[k].push_back(v[k]);
+        }
+        for (int k = 0; k < 3; ++k) ms[k] = median_of(t[k]);
+    });
+}
+
+pk_status pk_diag_tdt_kws_lattice(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                                  int chunk_rows, float *lab, float *blk, float *dl, float *top) {
+    return guard([&] {
+        need(h && enc && n_frames && lab && blk && dl && top && chunk_rows >= 0, "model/enc/n_frames/lab/blk/dl/top/chunk_rows");
+        Model &m = *h->m;
+        tdt_align_model_checks(m);
+        const pk_kws_options o = kws_options_of(nullptr);
+        kws_check_args(ids, id_offsets, B, B, m.cfg.vocab_size, m.cfg.blank_id, o, "TDT keyword spotting");
+        for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+        m.require_gpu();
+        std::vector<int32_t> self(B);
+        for (int b = 0; b < B; ++b) self[b] = b;
+        TdtKwsWs &ws = m.tkws;
+        tdt_kws_plan_call(ws, m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden, n_frames, B, 0, ids, id_offsets, B, self.data(),
+                          self.data(), B, o);
+        need(ws.gstart.size() == 2, "the call must fit one group");
+        int64_t cells = 0, labs = 0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t U = id_offsets[b + 1] - id_offsets[b];
+            cells += (int64_t)n_frames[b] * (U + 1); labs += (int64_t)n_frames[b] * U;
+        }
+        const int D = m.cfg.num_durations;
+        const size_t G = PK_DIAG_TDT_LATTICE_GUARD, nl = (size_t)labs + G, nb = (size_t)cells + G, nd = (size_t)cells * D + G;
+        ws.a.lab.reserve(nl * 4); ws.a.blk.reserve(nb * 4); ws.a.dl.reserve(nd * 4); ws.top.reserve(nb * 4);
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.a.lab.p, 0x7FC5A5A5, nl, m.stream));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.a.blk.p, 0x7FC5A5A5, nb, m.stream));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.a.dl.p, 0x7FC5A5A5, nd, m.stream));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.top.p, 0x7FC5A5A5, nb, m.stream));
+        size_t rows;
+        size_ws(m, n_frames, B, 0, rows);
+        PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+        m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
+        run_tdt_kws_call(m, ws, m.ws.ep.as<float>(), ids, id_offsets, chunk_rows, /*walk=*/false);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(lab, ws.a.lab.p, nl * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipMemcpyAsync(blk, ws.a.blk.p, nb * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipMemcpyAsync(dl, ws.a.dl.p, nd * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipMemcpyAsync(top, ws.top.p, nb * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
     });
 }
 

@@ -15,7 +15,7 @@ pk_kws_options kws_options_of(const pk_kws_options *opt) {
     return o;
 }
 
-void kws_check_args(const int32_t *ids, const int32_t *kw_offsets, int n_kw, int B, int V, int blank, const pk_kws_options &opt) {
+void kws_check_args(const int32_t *ids, const int32_t *kw_offsets, int n_kw, int B, int V, int blank, const pk_kws_options &opt, const char *what) {
     if (B < 1) fail(PK_ERR_INVALID, "invalid argument: B = %d", B);
     if (n_kw < 1) fail(PK_ERR_INVALID, "invalid argument: n_kw = %d", n_kw);
     if (!kw_offsets || !ids) fail(PK_ERR_INVALID, "invalid argument: kw_ids/kw_offsets");
@@ -33,12 +33,11 @@ void kws_check_args(const int32_t *ids, const int32_t *kw_offsets, int n_kw, int
         if (ids[i] == blank) fail(PK_ERR_INVALID, "invalid argument: token id at %d is the blank (%d)", i, blank);
     }
     if (opt.max_hits < 1 || opt.max_hits > kKwsMaxHits)
-        fail(PK_ERR_UNSUPPORTED, "CTC keyword spotting: max_hits = %d, supported 1 .. %d", opt.max_hits, kKwsMaxHits);
+        fail(PK_ERR_UNSUPPORTED, "%s: max_hits = %d, supported 1 .. %d", what, opt.max_hits, kKwsMaxHits);
     for (int k = 0; k < n_kw; ++k)
         if (kw_offsets[k + 1] - kw_offsets[k] > kKwsMaxLen)
-            fail(PK_ERR_UNSUPPORTED, "CTC keyword spotting: %d tokens in keyword %d, at most %d can be spotted", kw_offsets[k + 1] - kw_offsets[k], k,
-                 kKwsMaxLen);
-    if (B > 65535) fail(PK_ERR_UNSUPPORTED, "CTC keyword spotting: %d utterances in one call, at most 65535", B);
+            fail(PK_ERR_UNSUPPORTED, "%s: %d tokens in keyword %d, at most %d can be spotted", what, kw_offsets[k + 1] - kw_offsets[k], k, kKwsMaxLen);
+    if (B > 65535) fail(PK_ERR_UNSUPPORTED, "%s: %d utterances in one call, at most 65535", what, B);
 }
 
 void kws_plan(KwsWs &ws, const int32_t *n_frames, int B, int T, const int32_t *kw_offsets, int n_kw, const pk_kws_options &opt) {

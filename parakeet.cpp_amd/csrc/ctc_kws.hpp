@@ -24,7 +24,9 @@ pk_kws_options kws_options_of(const pk_kws_options *opt);
 
 // PK_ERR_INVALID: B < 1, n_kw < 1, kw_offsets that decrease (kw_offsets[0] must be 0), an empty keyword, an id outside [0, V) or equal to blank,
 // blank outside [0, V), min_score > 0 or NaN.  PK_ERR_UNSUPPORTED: a keyword of more than kKwsMaxLen tokens, max_hits outside 1 .. kKwsMaxHits.
-void kws_check_args(const int32_t *ids, const int32_t *kw_offsets, int n_kw, int B, int V, int blank, const pk_kws_options &opt);
+// `what`: the name the refusals carry (the TDT spotting of tdt_kws.hpp runs the same checks).
+void kws_check_args(const int32_t *ids, const int32_t *kw_offsets, int n_kw, int B, int V, int blank, const pk_kws_options &opt,
+                    const char *what = "CTC keyword spotting");
 
 // Sizes the call (host only); PK_ERR_UNSUPPORTED past the scratch cap.  n_frames == nullptr: every utterance T frames.  kws_check_args comes first.
 void kws_plan(KwsWs &ws, const int32_t *n_frames, int B, int T, const int32_t *kw_offsets, int n_kw, const pk_kws_options &opt);

@@ -20,6 +20,7 @@
 #include "safetensors.hpp"
 #include "tdt_align.hpp"
 #include "tdt_beam.hpp"
+#include "tdt_kws.hpp"
 #include "tdt_total.hpp"
 #include "vad.hpp"
 #include "text.hpp"
@@ -259,6 +260,7 @@ class Model {
     KwsWs kws;          // scratch and results of the CTC keyword-spotting entry points (ctc_kws.hpp)
     TdtAlignWs talign;  // scratch and results of the TDT forced-alignment entry points (tdt_align.hpp)
     TdtTotalWs ttotal;  // scratch and results of the TDT total / rescoring entry points (tdt_total.hpp)
+    TdtKwsWs tkws;      // scratch and results of the TDT keyword-spotting entry points (tdt_kws.hpp)
     TdtBeamWs tbeam;    // scratch and results of the TDT beam search entry points (tdt_beam.hpp)
     int decode_loop = PK_DECODE_LOOP_PHASES;   // pk_model_set_decode_loop: how run_tdt_loop issues the greedy loop
     int *h_done = nullptr;   // pinned host word for the decode loop's "all utterances finished" poll

@@ -603,6 +603,28 @@ struct TdtTotalArgs {
 };
 void launch_tdt_total(const TdtTotalArgs &a, hipStream_t s);
 
+// TDT keyword spotting (kernels/tdt_kws.hip): "utterance" b of the lattice is one (clip, keyword) pair, packed as for the
+// alignment (column U_b = L is packed and never read), plus top[cell]: the largest token log-prob of the row.  One wave per pair, lane u owns column u.
+struct TdtKwsArgs {
+    TdtLattice lt;                              // lab / blk / dl NORMALISED in place by launch_tdt_kws_norm
+    int4 *eb;                                   // scratch: (score bits, start frame, end frame, 0) per emission frame of the last token; pair b from entry
+                                                // cell_off[b] - lab_off[b] (= the frames of the pairs before it)
+    int max_hits; float min_score;
+    int *n_hits;                                // [B]
+    int *start, *end; float *score;             // [B][max_hits], written whole (unused slots 0 / 0 / -inf)
+    int dur_max;                                // over the durations: the dynamic LDS is (dur_max + 2) * (2 D + 1) * 64 dwords
+};
+// z of lattice rows [row0, row0 + n) as launch_tdt_lattice_act forms it, the prediction net's rows taken through an indirection: pair b reads
+// pp[(u n_net + net_of[b])][J] (the net is run once per distinct keyword, not once per pair)
+void launch_tdt_kws_act(const TdtLattice &lt, const int *ep_row0, const float *ep, const float *pp, const int *net_of, int n_net, int J, int64_t row0, int n,
+                        float *z, hipStream_t s);
+// launch_tdt_lattice_keep that also stores top[row]
+void launch_tdt_kws_keep(const TdtLattice &lt, float *top, const int *ids, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s);
+// lab -= top, blk -= top, dl[i] -= max_i dl[i], per cell, in place (the arc costs relative to the greedy decision)
+void launch_tdt_kws_norm(const TdtLattice &lt, const float *top, int64_t cells, hipStream_t s);
+// every pair needs 1 <= U_b <= kKwsMaxLen, max_hits 1 .. kKwsMaxHits, durations in [0, kTdtAlignMaxDur]
+void launch_tdt_kws(const TdtKwsArgs &a, hipStream_t s);
+
 // TDT beam search with n-best output (kernels/tdt_beam.hip).  R = B W rows, beam slot w of clip b is row b W + w.  The
 // beam exists in two copies (step s reads copy s & 1 and writes the other): every per-row array below is [2][R].
 constexpr int kTdtBeamMaxWidth = 16, kTdtBeamMaxLabels = 16, kTdtBeamMaxDurs = 8;

@@ -3,7 +3,7 @@
 //   parakeet_cli <model.safetensors> <audio.wav> [--model TYPE] [--ctc|--tdt] [--vocab PATH] [--timestamps] [--boost PHRASE]...
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K] [--beam-head ctc|tdt]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
-//                [--spot "phrase"]... [--spot-file path.txt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
+//                [--spot "phrase"]... [--spot-file path.txt] [--spot-head ctc|tdt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
 //                [--device-resample] [--vad [--vad-max-piece S]]
 // New: --vad (tdt-ctc-110m, tdt-600m; 16 kHz) cuts the file at its pauses on the device and transcribes only the speech, in pieces of at most
 // S seconds (--vad-max-piece S, default 30) that share batches (TranscribeOptions::vad): for long or sparse recordings.
@@ -19,6 +19,7 @@
 // New: --spot "phrase" (repeatable) / --spot-file path.txt (one phrase per line) (tdt-ctc-110m) searches the audio for every phrase (CTC keyword
 // spotting) and prints one line per hit: phrase<TAB>start<TAB>end<TAB>score (seconds; score <= 0, 0 = the greedy path over the span is the phrase).
 // --spot-hits N: up to N non-overlapping hits per phrase (default 1); --spot-min-score X: only hits with score >= X (default: no threshold).
+// New: --spot-head tdt (tdt-ctc-110m, tdt-600m) spots through the TDT head, which needs no CTC head; a phrase is scored as if it began the utterance.
 // New: --lm file.arpa (with --beam W and the CTC decoder, or with --beam W --beam-head tdt) fuses an n-gram language model over token ids into the beam search (shallow fusion):
 // hypotheses rank by acoustic score + LM score, LM score = sum per token of A * log p + B (--lm-alpha A, default 0.5; --lm-beta B, default 0);
 // both parts are printed.  tools/make_token_corpus.py turns text into the id lines an n-gram trainer makes such a file from.
@@ -50,7 +51,7 @@ static void usage(const char *prog) {
               << "  --spot \"phrase\" (repeatable) | --spot-file path.txt  where was each phrase said: phrase<TAB>start<TAB>end<TAB>score per hit\n"
               << "  --beam W --lm file.arpa [--lm-alpha A] [--lm-beta B]  the CTC beam search fused with an n-gram model over token ids\n"
               << "  --beam W --beam-head tdt --lm file.arpa [--lm-alpha A] [--lm-beta B]  the TDT beam search fused with the model; both scores per hypothesis\n"
-              << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold)\n"
+              << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold), --spot-head ctc|tdt (default ctc; tdt works for tdt-600m)\n"
               << "  --device-resample  resample files that are not 16 kHz on the device instead of on the host (tdt-ctc-110m, tdt-600m)\n"
               << "  --vad [--vad-max-piece S]  transcribe only the speech, cut at the pauses into pieces of at most S seconds (default 30)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
@@ -103,9 +104,9 @@ static int run_score(T &t, const std::string &audio_path, const std::string &tex
 
 // --spot: one line per hit, phrase<TAB>start<TAB>end<TAB>score, phrases in the order given, a phrase's hits best first
 template <class T>
-static int run_spot(T &t, const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &so) {
-    const auto hits = t.spot(audio_path, phrases, so);
-    std::cout << "Spotting: " << phrases.size() << " phrases\n";
+static int run_spot(T &t, const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &so, bool tdt) {
+    const auto hits = tdt ? t.spot_tdt(audio_path, phrases, so) : t.spot(audio_path, phrases, so);
+    std::cout << "Spotting" << (tdt ? " (tdt): " : ": ") << phrases.size() << " phrases\n";
     for (size_t k = 0; k < phrases.size(); ++k)
         for (const auto &h : hits[k])
             std::cout << phrases[k] << '\t' << std::setprecision(9) << std::defaultfloat << h.start << '\t' << h.end << '\t' << h.score << "\n";
@@ -144,7 +145,7 @@ int main(int argc, char **argv) {
         std::vector<std::string> boost, spot;
         SpotOptions spot_opts;
         float boost_score = 5.0f, vad_max_piece = 30.0f;
-        bool vad = false;
+        bool vad = false, spot_tdt = false;
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
             if (a == "--model" && i + 1 < argc) model = argv[++i];
@@ -186,6 +187,11 @@ int main(int argc, char **argv) {
                     if (!line.empty()) spot.push_back(line);
                 }
             }
+            else if (a == "--spot-head" && i + 1 < argc) {
+                const std::string hd = argv[++i];
+                if (hd != "ctc" && hd != "tdt") { std::cerr << "Unknown spot head: " << hd << "\n"; return 1; }
+                spot_tdt = hd == "tdt";
+            }
             else if (a == "--spot-hits" && i + 1 < argc) spot_opts.max_hits = std::stoi(argv[++i]);
             else if (a == "--spot-min-score" && i + 1 < argc) spot_opts.min_score = std::stof(argv[++i]);
             else if (a == "--prune" && i + 1 < argc) prune = std::stoi(argv[++i]);
@@ -218,7 +224,11 @@ int main(int argc, char **argv) {
         if (align && vocab.empty()) { std::cerr << "Error: --align needs --vocab\n"; return 1; }
         if (score && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --score needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (score && vocab.empty()) { std::cerr << "Error: --score needs --vocab\n"; return 1; }
-        if (!spot.empty() && model != "tdt-ctc-110m") { std::cerr << "Error: --spot needs a model with a CTC head (--model tdt-ctc-110m)\n"; return 1; }
+        if (!spot.empty() && !spot_tdt && model != "tdt-ctc-110m") {
+            std::cerr << "Error: --spot needs a model with a CTC head (--model tdt-ctc-110m), or --spot-head tdt\n";
+            return 1;
+        }
+        if (!spot.empty() && spot_tdt && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --spot-head tdt needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (!spot.empty() && vocab.empty()) { std::cerr << "Error: --spot needs --vocab\n"; return 1; }
         if (rescore && !nbest_given) { std::cerr << "Error: --rescore-tdt needs --nbest N\n"; return 1; }
         if (rescore && model != "tdt-ctc-110m") { std::cerr << "Error: --rescore-tdt needs a model with both heads (--model tdt-ctc-110m)\n"; return 1; }
@@ -258,7 +268,7 @@ int main(int argc, char **argv) {
             t.set_device_resampling(device_resample);
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);
-            if (!spot.empty()) return run_spot(t, audio_path, spot, spot_opts);
+            if (!spot.empty()) return run_spot(t, audio_path, spot, spot_opts, spot_tdt);
             if (rescore) {                                          // the beam's list re-ranked by the TDT head; --beam W optional (default 8)
                 if (!boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
                 BeamOptions bo;
@@ -322,6 +332,7 @@ int main(int argc, char **argv) {
             t.set_device_resampling(device_resample);
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);
+            if (!spot.empty()) return run_spot(t, audio_path, spot, spot_opts, true);
             if (beam > 0) {
                 if (!beam_tdt) { std::cerr << "Error: this model has no CTC head: --beam needs --beam-head tdt\n"; return 1; }
                 if (!lm_path.empty()) {

@@ -351,8 +351,8 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_align(pcm, n, text, tdt_head); });
     }
 
-    // pk_spot_pcm on one clip: every phrase (tokenised by the model's vocabulary) -> its hits, best first; single device
-    std::vector<std::vector<SpotHit>> run_spot(const float *pcm, size_t n, const std::vector<std::string> &phrases, const SpotOptions &opts) {
+    // pk_spot_pcm (tdt: pk_tdt_spot_pcm) on one clip: every phrase (tokenised by the model's vocabulary) -> its hits, best first; single device
+    std::vector<std::vector<SpotHit>> run_spot(const float *pcm, size_t n, const std::vector<std::string> &phrases, const SpotOptions &opts, bool tdt = false) {
         if (!on_gpu_) to_gpu(0);
         std::vector<std::vector<SpotHit>> out(phrases.size());
         if (phrases.empty()) return out;
@@ -365,13 +365,13 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         const size_t K = phrases.size(), H = (size_t)(opts.max_hits > 0 ? opts.max_hits : 1);
         std::vector<int32_t> n_hits(K);
         std::vector<float> st(K * H), en(K * H), sc(K * H);
-        check(pk_spot_pcm(m_, pcm, offsets, 1, texts.data(), nullptr, nullptr, (int)K, &o, n_hits.data(), st.data(), en.data(), sc.data()));
+        check((tdt ? pk_tdt_spot_pcm : pk_spot_pcm)(m_, pcm, offsets, 1, texts.data(), nullptr, nullptr, (int)K, &o, n_hits.data(), st.data(), en.data(), sc.data()));
         for (size_t k = 0; k < K; ++k)
             for (int j = 0; j < n_hits[k]; ++j) out[k].push_back({st[k * H + j], en[k * H + j], sc[k * H + j]});
         return out;
     }
-    std::vector<std::vector<SpotHit>> run_spot_file(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts) {
-        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_spot(pcm, n, phrases, opts); });
+    std::vector<std::vector<SpotHit>> run_spot_file(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts, bool tdt = false) {
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_spot(pcm, n, phrases, opts, tdt); });
     }
 
     const Tokenizer &tokenizer() const { return tok_; }
@@ -508,6 +508,17 @@ class Transcriber {
     std::vector<std::vector<SpotHit>> spot(const std::vector<float> &samples, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
         return eng_.run_spot(samples.data(), samples.size(), phrases, opts);
     }
+    /// New: keyword spotting through the TDT head (pk_tdt_spot_pcm): works without a CTC head.  A phrase is scored as if it
+    /// began the utterance; score 0: greedy TDT decoding with that context emits the phrase there.
+    std::vector<std::vector<SpotHit>> spot_tdt(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot_file(audio_path, phrases, opts, true);
+    }
+    std::vector<std::vector<SpotHit>> spot_tdt(const float *pcm, size_t n, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(pcm, n, phrases, opts, true);
+    }
+    std::vector<std::vector<SpotHit>> spot_tdt(const std::vector<float> &samples, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(samples.data(), samples.size(), phrases, opts, true);
+    }
     /// New: the same through the TDT head (pk_tdt_align_pcm): works without a CTC head.  AlignResult::total is 0.
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
     AlignResult align_tdt(const float *pcm, size_t n, const std::string &text) { return eng_.run_align(pcm, n, text, true); }
@@ -608,6 +619,17 @@ class TDTTranscriber {
     }
     std::vector<std::vector<SpotHit>> spot(const std::vector<float> &samples, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
         return eng_.run_spot(samples.data(), samples.size(), phrases, opts);
+    }
+    /// New: keyword spotting through the TDT head (pk_tdt_spot_pcm): works without a CTC head.  A phrase is scored as if it
+    /// began the utterance; score 0: greedy TDT decoding with that context emits the phrase there.
+    std::vector<std::vector<SpotHit>> spot_tdt(const std::string &audio_path, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot_file(audio_path, phrases, opts, true);
+    }
+    std::vector<std::vector<SpotHit>> spot_tdt(const float *pcm, size_t n, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(pcm, n, phrases, opts, true);
+    }
+    std::vector<std::vector<SpotHit>> spot_tdt(const std::vector<float> &samples, const std::vector<std::string> &phrases, const SpotOptions &opts = {}) {
+        return eng_.run_spot(samples.data(), samples.size(), phrases, opts, true);
     }
     /// New: the same through the TDT head (pk_tdt_align_pcm): works without a CTC head.  AlignResult::total is 0.
     AlignResult align_tdt(const std::string &audio_path, const std::string &text) { return eng_.run_align_file(audio_path, text, true); }
