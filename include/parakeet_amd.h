@@ -1257,6 +1257,41 @@ pk_status pk_diag_sigma_copy(const float *src, int64_t rows, int K, int64_t ld, 
 pk_status pk_diag_layernorm_sigma(const float *x, int64_t rows, int d, const float *gamma, const float *beta, float eps, float *y);
 pk_status pk_diag_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
                              int y2_sigma, float *y1, float *y2);
+/* ONE launch of the LayerNorm family alone (kernels/norm.hip), exactly one launcher per call:
+ *   launcher PK_DIAG_LN_NORM        launch_layernorm:            y = LN(x; g1, b1)                            mode 0 fp32 / 1 bf16 (RNE) / 2 fp32, sigma columns
+ *            PK_DIAG_LN_NORM2       launch_layernorm2:           y = LN(x; g1, b1) (fp32), y2 = LN(y; g2, b2)  mode: y2's, as above
+ *            PK_DIAG_LN_STATS       launch_layernorm_stats:      stats[row] = {mean, rstd} of x's rows
+ *            PK_DIAG_LN_THEN_STATS  launch_layernorm_then_stats: y = LN(x; g1, b1), stats of y's rows
+ *   x [rows][d] fp32, 0 < d <= 1024 (mode 2: d % 16 == 0); g1 / b1 / g2 / b2 [d] where the launcher reads them.
+ *   in_place: y aliases the device copy of x (launch_layernorm in mode 0; y1 of the other two), as the encoders call them.
+ *   y / y2 / stats: caller-sized buffers of y_words / y2_words / stats_words 32-bit words, each LONGER than what the launch may write (rows * d elements --
+ *            a bf16 buffer holds two to a word --; 2 * rows for stats).  Their device buffers are filled with 0x7FC5A5A5 before the launch and come back
+ *            WHOLE, exactly as the launch left them.  Buffers the launcher does not write are ignored.
+ * form receives the form of the launch, as the launcher itself reports it (kernels.hpp layernorm_form and its kin): PK_DIAG_LN_LAUNCHER, _PER_LANE (values
+ * of the row per lane: 2 / 8 / 16), _RPW (rows per wavefront), _THEN, and PK_DIAG_LN_BATCH: launch_layernorm's branch for rows >= 4096.
+ * pk_diag_layernorm_forms lists every form the launchers can take; pk_diag_layernorm_form_of answers for a shape -- both host arithmetic, no device.
+ * PK_ERR_UNSUPPORTED: d > 1024 (a row lives in one wavefront's registers).  PK_ERR_INVALID: malformed arguments.  Both before a device is looked for. */
+#define PK_DIAG_LN_NORM 0
+#define PK_DIAG_LN_NORM2 1
+#define PK_DIAG_LN_STATS 2
+#define PK_DIAG_LN_THEN_STATS 3
+#define PK_DIAG_LN_LAUNCHER(form) ((form) >> 12)
+#define PK_DIAG_LN_BATCH(form) (((form) >> 11) & 1)
+#define PK_DIAG_LN_THEN(form) (((form) >> 10) & 1)
+#define PK_DIAG_LN_RPW(form) (((form) >> 5) & 31)
+#define PK_DIAG_LN_PER_LANE(form) ((form) & 31)
+typedef struct pk_layernorm_diag {
+    int32_t launcher, d, mode, in_place;
+    int64_t rows; float eps;
+    const float *x, *g1, *b1, *g2, *b2;
+    uint32_t *y; int64_t y_words;
+    uint32_t *y2; int64_t y2_words;
+    uint32_t *stats; int64_t stats_words;
+    int32_t form;
+} pk_layernorm_diag;
+pk_status pk_diag_layernorm_form(pk_layernorm_diag *a);
+int pk_diag_layernorm_forms(int32_t *out, int cap);
+pk_status pk_diag_layernorm_form_of(int launcher, int64_t rows, int d, int32_t *form);
 /* ONE product of the fp32 tile GEMM family alone (kernels/gemm.hip, gemm_pipe.hpp; kernels.hpp GemmArgs): out = epi(X W^T + bias) for a product
  * launch_gemm keeps on a tile kernel (M > 1536 or K % 64 != 0); epi as above (glu: W [2N][ldw], bias [2N]).
  *   A [M][lda] (lda >= K), W [N or 2N][ldw] (ldw >= K), resid [M][ldr] (ldr >= N): host arrays AT THOSE PITCHES; on the device every word of a row past

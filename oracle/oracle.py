@@ -61,6 +61,7 @@ def lib():
     L.orc_linear.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p]
     L.orc_linear_scalar.argtypes = L.orc_linear.argtypes
     L.orc_layer_norm.argtypes = [f32p, C.c_int64, C.c_int, f32p, f32p, C.c_float, f32p]
+    L.orc_layer_norm_stats.argtypes = [f32p, C.c_int64, C.c_int, C.c_float, f32p]
     L.orc_model_new.restype = C.c_void_p
     L.orc_model_new.argtypes = [C.POINTER(OrcConfig)]
     L.orc_model_free.argtypes = [C.c_void_p]
@@ -132,6 +133,14 @@ def layer_norm(x, g, b, eps=1e-5):
     y = _out(x.shape)
     lib().orc_layer_norm(_f(x), x.size // x.shape[-1], x.shape[-1], _f(g), _f(b), eps, _f(y))
     return y
+
+
+def layer_norm_stats(x, eps=1e-5):
+    """[..][2] = {mean, rstd} of every row of x over its last axis: the numbers layer_norm normalises with (one body in pk_oracle.c)"""
+    x = _c(x)
+    st = _out(x.shape[:-1] + (2,))
+    lib().orc_layer_norm_stats(_f(x), x.size // x.shape[-1], x.shape[-1], eps, _f(st))
+    return st
 
 
 def mel_filterbank(n_mels=80, n_freqs=257, sr=16000.0, f_min=0.0, f_max=8000.0):

@@ -642,21 +642,33 @@ int orc_subsampling(orc_model *m, const float *feats, int B, int Tm, float *out,
 /* ------------------------------------------------------------------------- */
 /* LayerNorm (axiom nn::LayerNorm, default eps -- switch A3)                  */
 /* ------------------------------------------------------------------------- */
-static void layer_norm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y) {
+/* One body for the values and the statistics: y (may be NULL) receives the normalised rows, stats (may be NULL) the {mean, rstd} pairs those rows were
+ * normalised with -- the very numbers, not a second computation of them. */
+static void layer_norm_rows(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y, float *stats) {
     float *tmp = (float *)malloc((size_t)d * sizeof(float));
     for (int64_t r = 0; r < rows; ++r) {
         const float *xr = x + r * d;
-        float *yr = y + r * d;
         const float mean = orc_sum64(xr, d, 1) / (float)d;
         for (int i = 0; i < d; ++i) { const float c = xr[i] - mean; tmp[i] = c * c; }
         const float var = orc_sum64(tmp, d, 1) / (float)d;
         const float rstd = 1.0f / sqrtf(var + eps);
-        for (int i = 0; i < d; ++i) yr[i] = fmaf((xr[i] - mean) * rstd, g[i], b[i]);
+        if (stats) { stats[2 * r] = mean; stats[2 * r + 1] = rstd; }
+        if (y) {
+            float *yr = y + r * d;
+            for (int i = 0; i < d; ++i) yr[i] = fmaf((xr[i] - mean) * rstd, g[i], b[i]);
+        }
     }
     free(tmp);
 }
+static void layer_norm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y) {
+    layer_norm_rows(x, rows, d, g, b, eps, y, NULL);
+}
 void orc_layer_norm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y) {
     layer_norm(x, rows, d, g, b, eps, y);
+}
+/* stats[rows][2] = {mean, rstd} of every row, as orc_layer_norm computes them (what the product's statistics kernels hand to a GEMM) */
+void orc_layer_norm_stats(const float *x, int64_t rows, int d, float eps, float *stats) {
+    layer_norm_rows(x, rows, d, NULL, NULL, eps, NULL, stats);
 }
 
 /* a5: FeedForward::forward -- src/encoder.cpp:39-46 : x + 0.5*fc2(silu(fc1(LN(x)))) */

@@ -53,6 +53,7 @@ float orc_sum64_f(const float *x, int64_t n);
 void orc_linear(int M, int N, int K, const float *A, const float *W, const float *bias, float *out);
 void orc_linear_scalar(int M, int N, int K, const float *A, const float *W, const float *bias, float *out);
 void orc_layer_norm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y);
+void orc_layer_norm_stats(const float *x, int64_t rows, int d, float eps, float *stats);   /* [rows][2] = {mean, rstd}, the numbers orc_layer_norm normalises with */
 
 orc_model *orc_model_new(const orc_config *cfg);
 void orc_model_free(orc_model *m);

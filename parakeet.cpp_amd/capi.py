@@ -1597,6 +1597,81 @@ def diag_layernorm2(x, g1, b1, g2, b2, y2_sigma=False, eps=1e-5):
     return y1, y2
 
 
+class PkLayernormDiag(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("launcher", "d", "mode", "in_place")] + [("rows", C.c_int64), ("eps", C.c_float)]
+                + [(k, f32p) for k in ("x", "g1", "b1", "g2", "b2")]
+                + [("y", C.POINTER(C.c_uint32)), ("y_words", C.c_int64), ("y2", C.POINTER(C.c_uint32)), ("y2_words", C.c_int64),
+                   ("stats", C.POINTER(C.c_uint32)), ("stats_words", C.c_int64), ("form", C.c_int32)])
+
+
+LN_LAUNCHERS = ("norm", "norm2", "stats", "then_stats")       # PK_DIAG_LN_NORM .. PK_DIAG_LN_THEN_STATS
+LN_PAD_WORDS = 67                                               # spare words behind every output buffer of diag_layernorm_form (any positive count will do)
+
+
+def ln_form(v):
+    """A LayerNorm form value (kernels.hpp ln_form_of; PK_DIAG_LN_*) -> (launcher, PER_LANE, RPW, THEN, batch branch)"""
+    return LN_LAUNCHERS[v >> 12], v & 31, (v >> 5) & 31, bool((v >> 10) & 1), bool((v >> 11) & 1)
+
+
+def diag_layernorm_forms():
+    """pk_diag_layernorm_forms: every form the four LayerNorm launchers can take, as ln_form tuples.  Host arithmetic."""
+    n = lib().pk_diag_layernorm_forms(None, 0)
+    out = np.zeros(n, np.int32)
+    lib().pk_diag_layernorm_forms(_i(out), n)
+    return [ln_form(int(v)) for v in out]
+
+
+def diag_layernorm_form_of(launcher, rows, d):
+    """pk_diag_layernorm_form_of: the form `launcher` (one of LN_LAUNCHERS) takes for rows x d.  Host arithmetic."""
+    form = C.c_int32(-1)
+    L = lib()
+    L.pk_diag_layernorm_form_of.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
+    check(L.pk_diag_layernorm_form_of(LN_LAUNCHERS.index(launcher), int(rows), int(d), C.byref(form)))
+    return ln_form(form.value)
+
+
+def diag_layernorm_form(launcher, x, g1=None, b1=None, g2=None, b2=None, eps=1e-5, mode=0, in_place=False, pad_words=LN_PAD_WORDS):
+    """pk_diag_layernorm_form: one launch of one LayerNorm launcher (one of LN_LAUNCHERS) alone (include/parakeet_amd.h).  x [rows][d]; mode 0 fp32 /
+    1 bf16 / 2 fp32 sigma columns (of y for "norm", of y2 for "norm2"); in_place: y / y1 aliases the device copy of x.  Returns dict(form = ln_form tuple,
+    and for every buffer the launcher writes -- y (y1 of "norm2" / "then_stats"), y2, stats -- the WHOLE buffer as uint32 words exactly as the launch left
+    it: the payload followed by pad_words words, SKINNY_FILL32 wherever nothing was stored; a bf16 buffer holds two elements to a word)."""
+    x = _c(x)
+    rows, d = x.shape
+    keep = [x]
+
+    def opt(a):
+        if a is None:
+            return None
+        a = _c(a)
+        keep.append(a)
+        return _f(a)
+
+    a = PkLayernormDiag()
+    a.launcher, a.d, a.mode, a.in_place, a.rows, a.eps = LN_LAUNCHERS.index(launcher), d, int(mode), int(bool(in_place)), rows, eps
+    a.x, a.g1, a.b1, a.g2, a.b2 = _f(x), opt(g1), opt(b1), opt(g2), opt(b2)
+    n = rows * d
+    out = {}
+
+    def buf(name, words):
+        b = np.zeros(words + pad_words, np.uint32)
+        out[name] = b
+        setattr(a, name, b.ctypes.data_as(C.POINTER(C.c_uint32)))
+        setattr(a, name + "_words", b.size)
+
+    if launcher != "stats":
+        buf("y", (n + 1) // 2 if (launcher == "norm" and mode == 1) else n)
+    if launcher == "norm2":
+        buf("y2", (n + 1) // 2 if mode == 1 else n)
+    if launcher in ("stats", "then_stats"):
+        buf("stats", 2 * rows)
+    a.form = -1
+    L = lib()
+    L.pk_diag_layernorm_form.argtypes = [C.POINTER(PkLayernormDiag)]
+    check(L.pk_diag_layernorm_form(C.byref(a)))
+    out["form"] = ln_form(a.form)
+    return out
+
+
 class PkGemmTileDiag(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("M", "N", "K", "epi", "sigma_cols")]
                 + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),

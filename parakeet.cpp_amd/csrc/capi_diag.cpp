@@ -574,6 +574,90 @@ pk_status pk_diag_layernorm2(const float *x, int64_t rows, int d, const float *g
     });
 }
 
+// the PK_DIAG_LN_* macros of include/parakeet_amd.h decode what ln_form_of (kernels.hpp) encodes
+constexpr int kLnFormProbe = ln_form_of(LN_THEN_STATS, 16, 3, true, true);
+static_assert(PK_DIAG_LN_LAUNCHER(kLnFormProbe) == LN_THEN_STATS && PK_DIAG_LN_BATCH(kLnFormProbe) == 1 && PK_DIAG_LN_THEN(kLnFormProbe) == 1 &&
+              PK_DIAG_LN_RPW(kLnFormProbe) == 3 && PK_DIAG_LN_PER_LANE(kLnFormProbe) == 16 && PK_DIAG_LN_THEN(ln_form_of(LN_NORM2, 8, 1, false, false)) == 0 &&
+              PK_DIAG_LN_NORM == LN_NORM && PK_DIAG_LN_NORM2 == LN_NORM2 && PK_DIAG_LN_STATS == LN_STATS && PK_DIAG_LN_THEN_STATS == LN_THEN_STATS,
+              "PK_DIAG_LN_* must decode ln_form_of");
+
+int pk_diag_layernorm_forms(int32_t *out, int cap) {
+    for (int i = 0; out && i < kLnFormCount && i < cap; ++i) out[i] = (int32_t)kLnForms[i];
+    return kLnFormCount;
+}
+
+// the form the launcher would take: the launcher's own function (host arithmetic)
+static int ln_diag_form(int launcher, int64_t rows, int d) {
+    need(launcher >= 0 && launcher < LN_LAUNCHERS, "launcher (PK_DIAG_LN_NORM .. PK_DIAG_LN_THEN_STATS)");
+    need(rows > 0 && d > 0, "rows/d");
+    const int form = launcher == LN_NORM ? layernorm_form(rows, d) : launcher == LN_NORM2 ? layernorm2_form(rows, d)
+                   : launcher == LN_STATS ? layernorm_stats_form(rows, d) : layernorm_then_stats_form(rows, d);
+    if (form < 0) fail(PK_ERR_UNSUPPORTED, "pk_diag_layernorm_form: a row of %d columns (the LayerNorm kernels hold at most %d)", d, kLnMaxCols);
+    return form;
+}
+
+pk_status pk_diag_layernorm_form_of(int launcher, int64_t rows, int d, int32_t *form) {
+    return guard([&] {
+        need(form, "form");
+        *form = (int32_t)ln_diag_form(launcher, rows, d);
+    });
+}
+
+pk_status pk_diag_layernorm_form(pk_layernorm_diag *a) {
+    return guard([&] {
+        need(a, "args");
+        const int launcher = a->launcher, d = a->d, mode = a->mode;
+        const int64_t rows = a->rows;
+        (void)ln_diag_form(launcher, rows, d);                         // refuses what the launcher would refuse, before a device is looked for
+        const bool norm = launcher == LN_NORM, norm2 = launcher == LN_NORM2, stats = launcher == LN_STATS || launcher == LN_THEN_STATS;
+        const bool has_y = launcher != LN_STATS;                       // y: launch_layernorm's y, y1 of the other two
+        need(a->x, "x");
+        need(!(norm || norm2 || launcher == LN_THEN_STATS) || (a->g1 && a->b1), "g1/b1");
+        need(!norm2 || (a->g2 && a->b2), "g2/b2");
+        need(mode >= 0 && mode <= 2 && (mode == 0 || norm || norm2), "mode: 0, or 1 / 2 with launch_layernorm / launch_layernorm2");
+        need(mode != 2 || d % 16 == 0, "sigma columns: d must be a multiple of 16");
+        need(!a->in_place || (has_y && !(norm && mode != 0)), "in_place: launch_layernorm in mode 0, y1 of launch_layernorm2 / launch_layernorm_then_stats");
+        // every buffer the launch writes is longer than what it may write: the words past the end come back as the fill pattern
+        const int64_t n = rows * d;
+        const int64_t y_need = (norm && mode == 1) ? n / 2 + 1 : n + 1, y2_need = mode == 1 ? n / 2 + 1 : n + 1;
+        need(!has_y || (a->y && a->y_words >= y_need), "y / y_words: longer than rows * d elements");
+        need(!norm2 || (a->y2 && a->y2_words >= y2_need), "y2 / y2_words: longer than rows * d elements");
+        need(!stats || (a->stats && a->stats_words > 2 * rows), "stats / stats_words: longer than 2 * rows");
+        need_device();
+        DevBuf xb, gb, yb, y2b, sb;
+        auto filled = [](DevBuf &buf, int64_t words) {
+            buf.reserve((size_t)words * 4);
+            PK_HIP(hipMemsetD32(buf.p, 0x7fc5a5a5, (size_t)words));
+        };
+        if (has_y) filled(yb, a->y_words);
+        if (norm2) filled(y2b, a->y2_words);
+        if (stats) filled(sb, a->stats_words);
+        const float *x;
+        if (a->in_place) {                                             // x lives at the start of the y / y1 buffer
+            PK_HIP(hipMemcpy(yb.p, a->x, (size_t)n * 4, hipMemcpyHostToDevice));
+            x = yb.as<float>();
+        } else {
+            up(xb, a->x, (size_t)n * 4);
+            x = xb.as<float>();
+        }
+        up_rows(gb, {a->g1, a->b1, a->g2, a->b2}, d);
+        const float *p = gb.as<float>();
+        int form = -1;
+        switch (launcher) {
+        case LN_NORM: form = launch_layernorm(x, rows, d, p, p + d, a->eps, yb.as<float>(), nullptr, mode); break;
+        case LN_NORM2: form = launch_layernorm2(x, rows, d, p, p + d, p + 2 * (size_t)d, p + 3 * (size_t)d, a->eps, yb.as<float>(), y2b.as<float>(), nullptr, mode); break;
+        case LN_STATS: form = launch_layernorm_stats(x, rows, d, a->eps, sb.as<float>(), nullptr); break;
+        default: form = launch_layernorm_then_stats(x, rows, d, p, p + d, a->eps, yb.as<float>(), sb.as<float>(), nullptr); break;
+        }
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        a->form = (int32_t)form;                                       // what the launcher switched on, not a second evaluation here
+        if (has_y) down(a->y, yb, (size_t)a->y_words * 4);
+        if (norm2) down(a->y2, y2b, (size_t)a->y2_words * 4);
+        if (stats) down(a->stats, sb, (size_t)a->stats_words * 4);
+    });
+}
+
 pk_status pk_diag_sigma_copy(const float *src, int64_t rows, int K, int64_t ld, float *dst) {
     return guard([&] {
         need(src && dst && rows > 0 && rows % 16 == 0 && K > 0 && K % 64 == 0 && ld >= K, "src/dst, rows % 16 == 0, K % 64 == 0, ld >= K");

@@ -55,7 +55,7 @@ void Model::validate_config() {
     if (cfg.mel_bins > 128 || cfg.mel_bins % 8) fail(PK_ERR_UNSUPPORTED, "mel_bins must be a multiple of 8 and <= 128");
     if (cfg.conv_kernel_size != 9 && cfg.conv_kernel_size != 31) fail(PK_ERR_UNSUPPORTED, "conv_kernel_size must be 9 or 31");
     if (cfg.vocab_size > 0 && (cfg.num_lstm_layers < 1 || cfg.num_lstm_layers > 4)) fail(PK_ERR_UNSUPPORTED, "num_lstm_layers must be 1..4");
-    if (cfg.hidden_size > 1024) fail(PK_ERR_UNSUPPORTED, "hidden_size > 1024");
+    if (cfg.hidden_size > kLnMaxCols) fail(PK_ERR_UNSUPPORTED, "hidden_size > 1024");   // the LayerNorm family's row width (kernels.hpp)
     if (cfg.num_lstm_layers * cfg.pred_hidden > 12 * 256) fail(PK_ERR_UNSUPPORTED, "num_lstm_layers * pred_hidden > 3072");
     if (cfg.pred_hidden % 64 || cfg.joint_hidden % 64) fail(PK_ERR_UNSUPPORTED, "pred_hidden / joint_hidden must be multiples of 64 (decode GEMV K chunk)");
     if (cfg.num_durations < 0 || cfg.num_durations > 8) fail(PK_ERR_INVALID, "num_durations must be 0..8");

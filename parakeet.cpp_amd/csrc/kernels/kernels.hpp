@@ -770,15 +770,50 @@ size_t tdt_persistent_lds_bytes(const TdtState &st);
 void launch_tdt_persistent(const TdtPersist &p, hipStream_t s);
 
 // ---- LayerNorm, canonical reductions, math diagnostics ------------------------------------------
-void launch_layernorm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y, hipStream_t s, int y_bf16 = 0);   // y_bf16 = 1: y is a bf16 buffer (RNE); 2: fp32, columns in the sigma layout (GemmArgs::a_sigma)
+// A row lives in the registers of one wavefront, PER_LANE values per lane: kLnMaxCols columns is the widest row the family holds (every caller checks it:
+// Model::validate_config, TransformerEncoder, the diagnostics).  The form of a launch, by the functions the four launchers switch on: which launcher,
+// PER_LANE (2 / 8 / 16: d <= 128 / <= 512 / <= 1024), RPW (rows per wavefront; layernorm_kernel only), THEN (layernorm_stats_kernel) and, for
+// launch_layernorm, which of its two branches took it (batch: rows >= kLnBatchRows -- PK_LN_RPW is 1, so both branches pick the same template today; the
+// form still names the branch).  kLnForms lists every one; pk_diag_layernorm_form reports the form it launched (tests/test_gpu_layernorm.py).
+#ifndef PK_LN_RPW
+#define PK_LN_RPW 1                      // rows per wavefront of launch_layernorm's batch branch (kernels/norm.hip says why it stays 1)
+#endif
+constexpr int kLnMaxCols = 1024;
+constexpr int64_t kLnBatchRows = 4096;
+enum LnLauncher { LN_NORM, LN_NORM2, LN_STATS, LN_THEN_STATS, LN_LAUNCHERS };
+constexpr int ln_form_of(int launcher, int per_lane, int rpw, bool then, bool batch) {
+    return launcher << 12 | (batch ? 1 : 0) << 11 | (then ? 1 : 0) << 10 | rpw << 5 | per_lane;
+}
+constexpr int ln_form_per_lane(int form) { return form & 31; }
+constexpr bool ln_form_batch(int form) { return (form >> 11) & 1; }
+constexpr int ln_per_lane(int d) { return d <= 128 ? 2 : d <= 512 ? 8 : 16; }
+constexpr bool ln_shape_ok(int64_t rows, int d) { return rows > 0 && d > 0 && d <= kLnMaxCols; }
+// -> the form the launcher takes for this shape, -1 for a shape the family does not hold (the launchers refuse it)
+constexpr int layernorm_form(int64_t rows, int d) {
+    return !ln_shape_ok(rows, d) ? -1 : rows >= kLnBatchRows ? ln_form_of(LN_NORM, ln_per_lane(d), PK_LN_RPW, false, true) : ln_form_of(LN_NORM, ln_per_lane(d), 1, false, false);
+}
+constexpr int layernorm2_form(int64_t rows, int d) { return ln_shape_ok(rows, d) ? ln_form_of(LN_NORM2, ln_per_lane(d), 1, false, false) : -1; }
+constexpr int layernorm_stats_form(int64_t rows, int d) { return ln_shape_ok(rows, d) ? ln_form_of(LN_STATS, ln_per_lane(d), 1, false, false) : -1; }
+constexpr int layernorm_then_stats_form(int64_t rows, int d) { return ln_shape_ok(rows, d) ? ln_form_of(LN_THEN_STATS, ln_per_lane(d), 1, true, false) : -1; }
+constexpr int kLnForms[] = {
+    ln_form_of(LN_NORM, 2, 1, false, false), ln_form_of(LN_NORM, 8, 1, false, false), ln_form_of(LN_NORM, 16, 1, false, false),
+    ln_form_of(LN_NORM, 2, PK_LN_RPW, false, true), ln_form_of(LN_NORM, 8, PK_LN_RPW, false, true), ln_form_of(LN_NORM, 16, PK_LN_RPW, false, true),
+    ln_form_of(LN_NORM2, 2, 1, false, false), ln_form_of(LN_NORM2, 8, 1, false, false), ln_form_of(LN_NORM2, 16, 1, false, false),
+    ln_form_of(LN_STATS, 2, 1, false, false), ln_form_of(LN_STATS, 8, 1, false, false), ln_form_of(LN_STATS, 16, 1, false, false),
+    ln_form_of(LN_THEN_STATS, 2, 1, true, false), ln_form_of(LN_THEN_STATS, 8, 1, true, false), ln_form_of(LN_THEN_STATS, 16, 1, true, false),
+};
+constexpr int kLnFormCount = 3 * (LN_LAUNCHERS + 1);      // three PER_LANE x (four launchers + launch_layernorm's batch branch)
+static_assert(sizeof(kLnForms) / sizeof(kLnForms[0]) == kLnFormCount, "kLnForms must list every instantiation");
+// Every launcher returns the form it launched (the value its form function gives for the shape).
+int launch_layernorm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y, hipStream_t s, int y_bf16 = 0);   // y_bf16 = 1: y is a bf16 buffer (RNE); 2: fp32, columns in the sigma layout (GemmArgs::a_sigma); y may alias x (mode 0)
 // y1 = LN(x; g1, b1), y2 = LN(y1; g2, b2) in one pass (y1 may alias x)
-void launch_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
-                       float *y1, float *y2, hipStream_t s, int y2_bf16 = 0);
+int launch_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
+                      float *y1, float *y2, hipStream_t s, int y2_bf16 = 0);
 // Statistics only (round 6): stats[row] = {mean, rstd} of x's rows -- layernorm_kernel's reductions (same sum64 butterflies, same divisions), no output tensor:
 // the consumer normalises while it stages the rows (GemmArgs::ln_stats).
-void launch_layernorm_stats(const float *x, int64_t rows, int d, float eps, float *stats, hipStream_t s);
+int launch_layernorm_stats(const float *x, int64_t rows, int d, float eps, float *stats, hipStream_t s);
 // y1 = LN(x; g1, b1) written out (may alias x) + the statistics of y1's rows (what launch_layernorm2's second pass would start from)
-void launch_layernorm_then_stats(const float *x, int64_t rows, int d, const float *g1, const float *b1, float eps, float *y1, float *stats, hipStream_t s);
+int launch_layernorm_then_stats(const float *x, int64_t rows, int d, const float *g1, const float *b1, float eps, float *y1, float *stats, hipStream_t s);
 void launch_sum64_rows(const float *x, int rows, int n, float *out, hipStream_t s);
 void launch_math(int fn, const float *in, float *out, int64_t n, hipStream_t s);   // 0 exp 1 log 2 tanh 3 sigmoid 4 silu 5 sqrt 6 recip 7 relu 8 sigmoid4 9 silu4 20 fast_sigmoid 21 fast_silu
 void launch_math_exhaustive(int fn, unsigned long long *out3, hipStream_t s);   // out3 must hold {0, 0, 1 << 32} on entry

@@ -4,6 +4,7 @@
 // one wavefront per row, the row lives in registers, mean and variance are canonical sum64
 // reductions (strided per-lane accumulate + xor butterfly), y = fma((x-mean)*rstd, gamma, beta).
 #include "../pk_devmath.h"
+#include "../common.hpp"
 #include "kernels.hpp"
 
 namespace pk {
@@ -11,9 +12,7 @@ namespace pk {
 // RPW rows per wavefront.  Round 4 measured 1 / 2 / 4 on the batch shapes (tools/experiments/ln_rpw_ab.sh, profiles/r04_ln_rpw_ab.txt): sharing one
 // load of gamma / beta between the rows of a wave does NOT pay -- tdt-ctc-110m 0.87 / 0.92 / 1.02 ms of LayerNorm per step, tdt-600m bf16 2.23 /
 // -- / 2.39: the kernel wants the most independent waves it can get (it runs at ~4 TB/s of combined read + write).  One row per wave it stays.
-#ifndef PK_LN_RPW
-#define PK_LN_RPW 1
-#endif
+// (PK_LN_RPW itself: kernels.hpp, where the table of the family's forms names it.)
 template <int PER_LANE, int RPW>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict__ x, int64_t rows, int d,
                                                         const float *__restrict__ g, const float *__restrict__ b,
@@ -174,42 +173,70 @@ __global__ __launch_bounds__(256) void layernorm_stats_kernel(const float *__res
         }
     }
 }
-void launch_layernorm_stats(const float *x, int64_t rows, int d, float eps, float *stats, hipStream_t s) {
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    if (d <= 128) hipLaunchKernelGGL((layernorm_stats_kernel<2, false>), grid, dim3(256), 0, s, x, rows, d, nullptr, nullptr, eps, nullptr, stats);
-    else if (d <= 512) hipLaunchKernelGGL((layernorm_stats_kernel<8, false>), grid, dim3(256), 0, s, x, rows, d, nullptr, nullptr, eps, nullptr, stats);
-    else hipLaunchKernelGGL((layernorm_stats_kernel<16, false>), grid, dim3(256), 0, s, x, rows, d, nullptr, nullptr, eps, nullptr, stats);
+// The launchers switch on the form functions of kernels.hpp (layernorm_form and its kin) and return the form they launched; a shape the family does not
+// hold (d > kLnMaxCols: the row would not fit its wave's registers) is refused.
+static int ln_refuse(const char *who, int64_t rows, int d) {
+    fail(PK_ERR_UNSUPPORTED, "%s: %lld rows of %d columns (rows > 0, 0 < d <= %d)", who, (long long)rows, d, kLnMaxCols);
+    return -1;
 }
-void launch_layernorm_then_stats(const float *x, int64_t rows, int d, const float *g1, const float *b1, float eps, float *y1, float *stats, hipStream_t s) {
+int launch_layernorm_stats(const float *x, int64_t rows, int d, float eps, float *stats, hipStream_t s) {
+    const int form = layernorm_stats_form(rows, d);
     const dim3 grid((unsigned)((rows + 3) / 4));
-    if (d <= 128) hipLaunchKernelGGL((layernorm_stats_kernel<2, true>), grid, dim3(256), 0, s, x, rows, d, g1, b1, eps, y1, stats);
-    else if (d <= 512) hipLaunchKernelGGL((layernorm_stats_kernel<8, true>), grid, dim3(256), 0, s, x, rows, d, g1, b1, eps, y1, stats);
-    else hipLaunchKernelGGL((layernorm_stats_kernel<16, true>), grid, dim3(256), 0, s, x, rows, d, g1, b1, eps, y1, stats);
+    switch (form < 0 ? -1 : ln_form_per_lane(form)) {
+    case 2: hipLaunchKernelGGL((layernorm_stats_kernel<2, false>), grid, dim3(256), 0, s, x, rows, d, nullptr, nullptr, eps, nullptr, stats); break;
+    case 8: hipLaunchKernelGGL((layernorm_stats_kernel<8, false>), grid, dim3(256), 0, s, x, rows, d, nullptr, nullptr, eps, nullptr, stats); break;
+    case 16: hipLaunchKernelGGL((layernorm_stats_kernel<16, false>), grid, dim3(256), 0, s, x, rows, d, nullptr, nullptr, eps, nullptr, stats); break;
+    default: return ln_refuse("launch_layernorm_stats", rows, d);
+    }
+    return form;
+}
+int launch_layernorm_then_stats(const float *x, int64_t rows, int d, const float *g1, const float *b1, float eps, float *y1, float *stats, hipStream_t s) {
+    const int form = layernorm_then_stats_form(rows, d);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    switch (form < 0 ? -1 : ln_form_per_lane(form)) {
+    case 2: hipLaunchKernelGGL((layernorm_stats_kernel<2, true>), grid, dim3(256), 0, s, x, rows, d, g1, b1, eps, y1, stats); break;
+    case 8: hipLaunchKernelGGL((layernorm_stats_kernel<8, true>), grid, dim3(256), 0, s, x, rows, d, g1, b1, eps, y1, stats); break;
+    case 16: hipLaunchKernelGGL((layernorm_stats_kernel<16, true>), grid, dim3(256), 0, s, x, rows, d, g1, b1, eps, y1, stats); break;
+    default: return ln_refuse("launch_layernorm_then_stats", rows, d);
+    }
+    return form;
 }
 
-void launch_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
-                       float *y1, float *y2, hipStream_t s, int y2_bf16) {
+int launch_layernorm2(const float *x, int64_t rows, int d, const float *g1, const float *b1, const float *g2, const float *b2, float eps,
+                      float *y1, float *y2, hipStream_t s, int y2_bf16) {
+    const int form = layernorm2_form(rows, d);
     const dim3 grid((unsigned)((rows + 3) / 4));
-    if (d <= 128) hipLaunchKernelGGL(layernorm2_kernel<2>, grid, dim3(256), 0, s, x, rows, d, g1, b1, g2, b2, eps, y1, y2, y2_bf16);
-    else if (d <= 512) hipLaunchKernelGGL(layernorm2_kernel<8>, grid, dim3(256), 0, s, x, rows, d, g1, b1, g2, b2, eps, y1, y2, y2_bf16);
-    else hipLaunchKernelGGL(layernorm2_kernel<16>, grid, dim3(256), 0, s, x, rows, d, g1, b1, g2, b2, eps, y1, y2, y2_bf16);
+    switch (form < 0 ? -1 : ln_form_per_lane(form)) {
+    case 2: hipLaunchKernelGGL(layernorm2_kernel<2>, grid, dim3(256), 0, s, x, rows, d, g1, b1, g2, b2, eps, y1, y2, y2_bf16); break;
+    case 8: hipLaunchKernelGGL(layernorm2_kernel<8>, grid, dim3(256), 0, s, x, rows, d, g1, b1, g2, b2, eps, y1, y2, y2_bf16); break;
+    case 16: hipLaunchKernelGGL(layernorm2_kernel<16>, grid, dim3(256), 0, s, x, rows, d, g1, b1, g2, b2, eps, y1, y2, y2_bf16); break;
+    default: return ln_refuse("launch_layernorm2", rows, d);
+    }
+    return form;
 }
 
-void launch_layernorm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y, hipStream_t s, int y_bf16) {
-    // few rows (streaming chunks, single clips): one row per wave -- the launch is latency-bound and wants every wave it can get;
-    // batches: PK_LN_RPW rows per wave share one load of gamma / beta
-    if (rows < 4096) {
+// few rows (streaming chunks, single clips): one row per wave -- the launch is latency-bound and wants every wave it can get;
+// batches: PK_LN_RPW rows per wave share one load of gamma / beta
+template <int PER_LANE>
+static void launch_layernorm_inst(bool batch, const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y, hipStream_t s, int y_bf16) {
+    if (!batch) {
         const dim3 grid((unsigned)((rows + 3) / 4));
-        if (d <= 128) hipLaunchKernelGGL((layernorm_kernel<2, 1>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
-        else if (d <= 512) hipLaunchKernelGGL((layernorm_kernel<8, 1>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
-        else hipLaunchKernelGGL((layernorm_kernel<16, 1>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
+        hipLaunchKernelGGL((layernorm_kernel<PER_LANE, 1>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
         return;
     }
     constexpr int RPW = PK_LN_RPW;
     const dim3 grid((unsigned)((rows + 4 * RPW - 1) / (4 * RPW)));
-    if (d <= 128) hipLaunchKernelGGL((layernorm_kernel<2, RPW>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
-    else if (d <= 512) hipLaunchKernelGGL((layernorm_kernel<8, RPW>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
-    else hipLaunchKernelGGL((layernorm_kernel<16, RPW>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
+    hipLaunchKernelGGL((layernorm_kernel<PER_LANE, RPW>), grid, dim3(256), 0, s, x, rows, d, g, b, eps, y, y_bf16);
+}
+int launch_layernorm(const float *x, int64_t rows, int d, const float *g, const float *b, float eps, float *y, hipStream_t s, int y_bf16) {
+    const int form = layernorm_form(rows, d);
+    switch (form < 0 ? -1 : ln_form_per_lane(form)) {
+    case 2: launch_layernorm_inst<2>(ln_form_batch(form), x, rows, d, g, b, eps, y, s, y_bf16); break;
+    case 8: launch_layernorm_inst<8>(ln_form_batch(form), x, rows, d, g, b, eps, y, s, y_bf16); break;
+    case 16: launch_layernorm_inst<16>(ln_form_batch(form), x, rows, d, g, b, eps, y, s, y_bf16); break;
+    default: return ln_refuse("launch_layernorm", rows, d);
+    }
+    return form;
 }
 
 __global__ __launch_bounds__(64) void sum64_rows_kernel(const float *__restrict__ x, int n, float *__restrict__ out) {

@@ -28,6 +28,7 @@ TransformerEncoder::TransformerEncoder(const std::string &weights_path, const st
     const int d = c.hidden_size, H = c.num_heads, f = c.ffn_intermediate;
     if (d <= 0 || H <= 0 || d % H || c.num_layers <= 0 || f <= 0) fail(PK_ERR_INVALID, "bad transformer config");
     if (d % 32 || f % 32) fail(PK_ERR_UNSUPPORTED, "hidden_size / ffn_intermediate must be multiples of 32 (MFMA K tile)");
+    if (d > kLnMaxCols) fail(PK_ERR_UNSUPPORTED, "hidden_size > %d (a LayerNorm row lives in one wavefront's registers)", kLnMaxCols);   // as Model::validate_config
     const int hd = d / H;
     hdp_ = (hd + 31) / 32 * 32;
     if (hdp_ > 128) fail(PK_ERR_UNSUPPORTED, "head_dim > 128");

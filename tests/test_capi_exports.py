@@ -102,6 +102,12 @@ def test_no_gpu_is_a_loud_error(tmp_path):
         with pytest.raises(capi.PkError) as e:
             capi.diag_mel(pcm, form, n_mels=65)
         assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:             # the LayerNorm family's diagnostic: valid arguments, no device
+        capi.diag_layernorm_form("norm2", np.zeros((5, 160), np.float32), *[np.ones(160, np.float32)] * 4, mode=1, in_place=True)
+    assert e.value.code == -4
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_layernorm_form("stats", np.zeros((5, 63), np.float32))
+    assert e.value.code == -4
     with pytest.raises(capi.PkError) as e:             # the multi-GPU entry point as well
         capi.Group(str(wp), cfg)
     assert e.value.code == -4
@@ -271,6 +277,55 @@ def test_smallm_bf16_gemm_form_table_queries_and_refusals_need_no_device():
     with pytest.raises(capi.PkError) as e:
         capi.diag_gemm_smallm_bf16(np.zeros((8, 256), np.float32), np.zeros((16, 256), np.float32), ldo=8)
     assert e.value.code == -1
+
+
+def test_layernorm_form_table_queries_and_refusals_need_no_device():
+    """pk_diag_layernorm_forms (what tests/test_gpu_layernorm.py::test_every_form_has_a_case compares its cases with) and pk_diag_layernorm_form_of are
+    host arithmetic: three PER_LANE instantiations of every launcher, launch_layernorm's two branches listed apart; and pk_diag_layernorm_form refuses a
+    row wider than the family holds, and malformed arguments, before it looks for a device."""
+    for name in ("pk_diag_layernorm_form", "pk_diag_layernorm_forms", "pk_diag_layernorm_form_of"):
+        assert name in declared_symbols() and hasattr(capi.lib(), name)
+    every = capi.diag_layernorm_forms()
+    want = {("norm", p, 1, False, batch) for p in (2, 8, 16) for batch in (False, True)}
+    want |= {(l, p, 1, l == "then_stats", False) for l in ("norm2", "stats", "then_stats") for p in (2, 8, 16)}
+    assert len(every) == 15 and set(every) == want
+    q = capi.diag_layernorm_form_of
+    assert q("norm", 4095, 128) == ("norm", 2, 1, False, False) and q("norm", 4096, 128) == ("norm", 2, 1, False, True)
+    assert q("norm", 1, 129) == ("norm", 8, 1, False, False) and q("norm2", 70000, 512) == ("norm2", 8, 1, False, False)
+    assert q("stats", 1, 513) == ("stats", 16, 1, False, False) and q("then_stats", 8064, 1024) == ("then_stats", 16, 1, True, False)
+    x, one = np.zeros((3, 64), np.float32), np.ones(64, np.float32)
+    for launcher in capi.LN_LAUNCHERS:
+        with pytest.raises(capi.PkError) as e:
+            q(launcher, 4, 1025)
+        assert e.value.code == -7, launcher
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_layernorm_form(launcher, np.zeros((2, 1056), np.float32), *[np.ones(1056, np.float32)] * 4)
+        assert e.value.code == -7, launcher
+    for bad in (dict(rows=0, d=64), dict(rows=4, d=0)):
+        with pytest.raises(capi.PkError) as e:
+            q("norm", **bad)
+        assert e.value.code == -1, bad
+    for launcher, args, kw in (("norm", (one,), {}), ("norm2", (one, one), {}), ("then_stats", (), {}),          # gamma / beta missing
+                               ("stats", (), dict(mode=1)), ("then_stats", (one, one), dict(mode=2)),            # a mode the launcher does not have
+                               ("norm", (one, one), dict(mode=3)), ("norm", (one, one), dict(mode=1, in_place=True)), ("stats", (), dict(in_place=True)),
+                               ("norm", (one, one), dict(pad_words=0)), ("stats", (), dict(pad_words=0))):          # a buffer no longer than the rows
+        with pytest.raises(capi.PkError) as e:
+            capi.diag_layernorm_form(launcher, x, *args, **kw)
+        assert e.value.code == -1, (launcher, kw)
+    with pytest.raises(capi.PkError) as e:                           # sigma columns come in blocks of 16
+        capi.diag_layernorm_form("norm", np.zeros((3, 40), np.float32), np.ones(40, np.float32), np.ones(40, np.float32), mode=2)
+    assert e.value.code == -1
+
+
+def test_transformer_refuses_a_hidden_size_past_the_layernorm_row_width(tmp_path):
+    """hidden_size 1536 with 12 heads passes every other configuration check (a multiple of 32, head size 128): the LayerNorm kernels hold rows of at
+    most 1024 columns, so it is PK_ERR_UNSUPPORTED like Model::validate_config's -- decided before a device is looked for, with or without one."""
+    with pytest.raises(capi.PkError) as e:
+        capi.Transformer(str(tmp_path / "none.safetensors"), "t.", 1536, 1, 12, 3072)
+    assert e.value.code == -7 and "1024" in str(e.value)
+    with pytest.raises(capi.PkError) as e:                           # the widest row is still a configuration the checks let through
+        capi.Transformer(str(tmp_path / "none.safetensors"), "t.", 1024, 1, 8, 2048)
+    assert e.value.code in (-4, -2)                                  # no device; with one: the weights file does not exist
 
 
 def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
