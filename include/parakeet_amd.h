@@ -647,7 +647,7 @@ pk_status pk_diag_mem_info(pk_model *m, uint64_t out[3]);
  * span meets that one is out; up to max_hits times, in the order picked.  Specified operation by operation in DESIGN.md section 5.5.4
  * (tests/ctc_kws_ref.py is that specification in Python; the device result equals it bit for bit).  All of it runs on the device
  * (kernels/ctc_kws.hip).  Matching is on token strings: "cat" matches inside "category" unless the tokenisation differs.  No threshold is
- * applied unless the caller sets one.  pk_group and streaming sessions have no spotting variant; the TDT head has none.
+ * applied unless the caller sets one.  pk_group has no spotting variant; streaming sessions spot through the TDT head (pk_stream_set_keywords below).
  * PRECONDITION: every row of the log-probs has a finite maximum (a true log-softmax row always has one).
  *
  * pk_ctc_kws: HOST log-probs in.  Needs a device, no model.  logp / n_frames / B / T / V / blank as pk_ctc_beam_search.  kw_ids: the n_kw keywords
@@ -905,6 +905,60 @@ pk_status pk_stream_decode(pk_stream *s, const float *enc, int n_frames, int max
  * n_done[n_streams] (may be NULL) = steps walked (= n_steps[s] for a path the reference's loop can take on this chunk). */
 pk_status pk_stream_score(pk_stream *s, const float *enc, int n_frames, const int32_t *labels, const int32_t *dur_idx, const int32_t *n_steps,
                           int cap, float *label_logp, float *dur_logp, int32_t *n_done);
+
+/* ---- streaming TDT keyword spotting: wake words on live audio (kernels/tdt_kws_stream.hip) ------------------
+ * The walk of pk_tdt_kws, stopped at every chunk boundary and picked up again from a state carried on the device, and a hit rule that needs no
+ * future frame.  Specification: tests/tdt_kws_stream_ref.py (ChunkWalk + OnlinePick), matched bit for bit.  The rule keeps one pending hit per
+ * (stream, keyword) pair, fed frame by frame: (1) a pending hit leaves when t > its end + patience; (2) frame t qualifies when E[t] > -inf,
+ * E[t] >= min_score and Bs[t] lies after the end of the last hit that left; (3) with nothing pending it becomes the pending hit; (4) where its span [Bs[t], Ee[t]] meets the pending span it replaces the
+ * pending hit only when E[t] is strictly larger; (5) where it does not, the pending hit leaves and the frame becomes pending.  This is an online
+ * approximation of pk_tdt_kws's greedy picking: a pending hit that was replaced is never reported.  Frames count from the start of the session
+ * (the last reset), spans are inclusive, and a span's end is t + max(duration, 1) - 1 without a clamp: it may lie past the frames seen so far.
+ * PK_ERR_INVALID: whatever pk_tdt_kws refuses that way (an empty keyword, an id outside [0, V) or equal to blank, min_score > 0 or NaN), patience < 0,
+ * n_frames < 1.  PK_ERR_UNSUPPORTED, before anything is allocated: a keyword of more than 64 tokens, D outside 1 .. 8, a duration outside [0, 8], more
+ * than 256 keywords or 65536 pairs, more than 62 frames in one call, more than 1 GiB of carried state plus lattice at the 62-frame limit, and for
+ * a session: a model without a TDT joint, gemm_bf16. */
+typedef struct pk_stream_kws_options {
+    float min_score;           /* -inf: every frame with a path qualifies */
+    int32_t patience;          /* 0: frames to wait after a pending hit's end before it leaves */
+} pk_stream_kws_options;
+typedef struct pk_kws_event {
+    int32_t stream, keyword, start, end;   /* frames since the stream began, inclusive */
+    float score;
+} pk_kws_event;
+void pk_stream_kws_options_default(pk_stream_kws_options *out);
+/* The chunked walk and the online rule alone, on host lattices (no model): the counterpart of pk_tdt_kws.  n_pairs walks, pair p with a keyword
+ * of kw_len[p] tokens.  A push hands every pair the lattice rows of the next c frames (1 <= c <= 62), packed as for pk_tdt_kws with n_frames = c
+ * for every pair.  E / Bs / Ee [n_pairs][c] (each may be NULL): the exit rows of the push.  events: ordered by pair, then by emission; the first
+ * `cap` are written and *n_events is the total (cap = n_pairs * c never truncates); an event names its pair in `keyword` (stream = 0). */
+typedef struct pk_tdt_kws_chunk pk_tdt_kws_chunk;
+pk_status pk_tdt_kws_chunk_create(const int32_t *durations, int D, int n_pairs, const int32_t *kw_len, const pk_stream_kws_options *opt,
+                                  pk_tdt_kws_chunk **out);
+pk_status pk_tdt_kws_chunk_push(pk_tdt_kws_chunk *w, const float *lab, const float *blk, const float *dl, const float *top, int c, float *E,
+                                int32_t *Bs, int32_t *Ee, pk_kws_event *events, int cap, int *n_events);
+/* emits every pending hit (ordered by pair) */
+pk_status pk_tdt_kws_chunk_flush(pk_tdt_kws_chunk *w, pk_kws_event *events, int cap, int *n_events);
+/* back to frame 0: the carried state and the pending hits are cleared */
+pk_status pk_tdt_kws_chunk_reset(pk_tdt_kws_chunk *w);
+void pk_tdt_kws_chunk_free(pk_tdt_kws_chunk *w);
+/* On a streaming session: every keyword is watched in every stream, pair = stream * n_kw + keyword.  Keywords as phrases (needs the model's
+ * vocabulary) or as ids + kw_offsets[n_kw + 1]; n_kw = 0 clears the set.  The prediction net runs here, once per distinct keyword.  A refused call
+ * leaves the set in place as it was.  pk_stream_reset keeps the keywords, clears the walk and the pending hits and restarts the frame numbering.
+ * pk_stream_push, pk_stream_decode and pk_stream_reset return what they return without keywords; they do not feed the walk: a session that spots
+ * hands every chunk to pk_stream_spot or pk_stream_push_spot, and an event's frames count the frames those calls have seen. */
+pk_status pk_stream_set_keywords(pk_stream *s, const char *const *phrases_or_null, const int32_t *ids_or_null, const int32_t *kw_offsets, int n_kw,
+                                 const pk_stream_kws_options *opt);
+/* Stage form: enc [n_streams][n_frames][hidden] on the host, as pk_stream_decode takes it (1 <= n_frames <= 62).  E / Bs / Ee
+ * [n_streams * n_kw][n_frames], each may be NULL. */
+pk_status pk_stream_spot(pk_stream *s, const float *enc, int n_frames, float *E, int32_t *Bs, int32_t *Ee, pk_kws_event *events, int cap,
+                         int *n_events);
+/* pk_stream_push that also walks the chunk's frames: the same tokens, and the events of this push in the same host round trip. */
+pk_status pk_stream_push_spot(pk_stream *s, const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start,
+                              int32_t *end, float *conf, pk_kws_event *events, int cap, int *n_events);
+pk_status pk_stream_spot_flush(pk_stream *s, pk_kws_event *events, int cap, int *n_events);
+/* Stage timers (tools/bench_stream_kws.py): pk_stream_spot `reps` times after one warm-up on the same rows, HIP events, medians: ms[0] = enc_proj +
+ * lattice, ms[1] = normalisation + walk + rule.  The walk's state advances by reps + 1 chunks. */
+pk_status pk_stream_spot_timed(pk_stream *s, const float *enc, int n_frames, int reps, float ms[2]);
 
 /* ---- plain Transformer encoder: TransformerEncoder::forward / TransformerBlock::forward (src/transformer.cpp:15-88) ------------ */
 /* include/parakeet/transformer.hpp:12-21 (TransformerConfig), dropout omitted (inference). */

@@ -76,6 +76,14 @@ class PkKwsOptions(C.Structure):
     _fields_ = [("max_hits", C.c_int32), ("min_score", C.c_float)]
 
 
+class PkStreamKwsOptions(C.Structure):
+    _fields_ = [("min_score", C.c_float), ("patience", C.c_int32)]
+
+
+class PkKwsEvent(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("keyword", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("score", C.c_float)]
+
+
 class PkVadOptions(C.Structure):
     _fields_ = [("threshold_db", C.c_float), ("margin_db", C.c_float), ("floor_percent", C.c_int32), ("min_speech_ms", C.c_int32),
                 ("min_silence_ms", C.c_int32), ("pad_ms", C.c_int32), ("max_gap_ms", C.c_int32), ("max_piece_s", C.c_float)]
@@ -271,6 +279,17 @@ _LATE_SIGNATURES = {
     "pk_tdt_kws_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), C.c_int, f32p],
     "pk_tdt_spot_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, f32p, f32p, f32p],
     "pk_diag_tdt_kws_lattice": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, f32p, f32p, f32p, f32p],
+    "pk_stream_kws_options_default": [C.POINTER(PkStreamKwsOptions)],
+    "pk_tdt_kws_chunk_create": [i32p, C.c_int, C.c_int, i32p, C.POINTER(PkStreamKwsOptions), C.POINTER(C.c_void_p)],
+    "pk_tdt_kws_chunk_push": [C.c_void_p, f32p, f32p, f32p, f32p, C.c_int, f32p, i32p, i32p, C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_tdt_kws_chunk_flush": [C.c_void_p, C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_tdt_kws_chunk_reset": [C.c_void_p],
+    "pk_tdt_kws_chunk_free": [C.c_void_p],
+    "pk_stream_set_keywords": [C.c_void_p, C.POINTER(C.c_char_p), i32p, i32p, C.c_int, C.POINTER(PkStreamKwsOptions)],
+    "pk_stream_spot": [C.c_void_p, f32p, C.c_int, f32p, i32p, i32p, C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_stream_push_spot": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_stream_spot_flush": [C.c_void_p, C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_stream_spot_timed": [C.c_void_p, f32p, C.c_int, C.c_int, f32p],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -605,6 +624,69 @@ def tdt_kws(lattices, durations, max_hits=None, min_score=None):
     nh = np.zeros(B, np.int32); st = np.zeros((B, H), np.int32); en = np.zeros((B, H), np.int32); sc = np.zeros((B, H), np.float32)
     check(lib().pk_tdt_kws(_f(lab), _f(blk), _f(dl), _f(top), _i(dur), len(dur), _i(T), B, _i(off), C.byref(o), _i(nh), _i(st), _i(en), _f(sc)))
     return dict(n_hits=nh, start=st, end=en, score=sc)
+
+
+# ---- streaming TDT keyword spotting (include/parakeet_amd.h) --------------------
+KWS_CHUNK_MAX = 62
+
+
+def stream_kws_options(min_score=None, patience=None):
+    """pk_stream_kws_options: the library's defaults (min_score = -inf, patience = 0) with the given fields replaced."""
+    o = PkStreamKwsOptions()
+    lib().pk_stream_kws_options_default(C.byref(o))
+    if min_score is not None:
+        o.min_score = min_score
+    if patience is not None:
+        o.patience = patience
+    return o
+
+
+def _events(buf, n):
+    """-> [(stream, keyword, start, end, score as np.float32)...]"""
+    return [(e.stream, e.keyword, e.start, e.end, np.float32(e.score)) for e in buf[:n]]
+
+
+class TdtKwsChunkWalk:
+    """pk_tdt_kws_chunk_*: the chunked walk and the online rule alone on host lattices, n pairs with keywords of kw_len[p] tokens.  Needs a
+    device, no model."""
+
+    def __init__(self, kw_len, durations, min_score=None, patience=None):
+        self.kw_len = np.ascontiguousarray(kw_len, np.int32)
+        self.dur = np.ascontiguousarray(durations, np.int32)
+        self.n = len(self.kw_len)
+        o = stream_kws_options(min_score, patience)
+        self._h = C.c_void_p()
+        check(lib().pk_tdt_kws_chunk_create(_i(self.dur), len(self.dur), self.n, _i(self.kw_len), C.byref(o), C.byref(self._h)))
+
+    def push(self, lattices, rows=True, cap=None, c=None):
+        """lattices: one (lab [c][L], blk [c][L+1], dl [c][L+1][D], top [c][L+1]) per pair, the next c frames -> dict(E, Bs, Ee [n][c] (rows),
+        events (the first cap), n_events (the total))."""
+        assert len(lattices) == self.n
+        c = lattices[0][1].shape[0] if c is None else c
+        cat = lambda k: _c(np.concatenate([_c(x[k]).ravel() for x in lattices] + [np.zeros(1, np.float32)]))
+        lab, blk, dl, top = cat(0), cat(1), cat(2), cat(3)
+        cap = self.n * max(c, 1) if cap is None else cap
+        ev = (PkKwsEvent * max(cap, 1))()
+        n = C.c_int(0)
+        cc = max(c, 1)
+        E = np.zeros((self.n, cc), np.float32); Bs = np.zeros((self.n, cc), np.int32); Ee = np.zeros((self.n, cc), np.int32)
+        check(lib().pk_tdt_kws_chunk_push(self._h, _f(lab), _f(blk), _f(dl), _f(top), c, _f(E) if rows else None, _i(Bs) if rows else None,
+                                          _i(Ee) if rows else None, ev, cap, C.byref(n)))
+        return dict(E=E, Bs=Bs, Ee=Ee, events=_events(ev, min(n.value, cap)), n_events=n.value)
+
+    def flush(self):
+        ev = (PkKwsEvent * self.n)()
+        n = C.c_int(0)
+        check(lib().pk_tdt_kws_chunk_flush(self._h, ev, self.n, C.byref(n)))
+        return _events(ev, n.value)
+
+    def reset(self):
+        check(lib().pk_tdt_kws_chunk_reset(self._h))
+
+    def close(self):
+        if self._h:
+            lib().pk_tdt_kws_chunk_free(self._h)
+            self._h = None
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -1098,6 +1180,7 @@ class Stream:
         L.pk_stream_encode.argtypes = [C.c_void_p, f32p, C.c_int, f32p, C.c_int, C.POINTER(C.c_int)]
         L.pk_stream_decode.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p]
         self.model, self.S = model, n_streams
+        self.n_kw = 0
         self._h = C.c_void_p()
         check(L.pk_stream_create(model._h, n_streams, att_context_left, att_context_right, C.byref(self._h)))
 
@@ -1149,6 +1232,64 @@ class Stream:
         nd = np.zeros(self.S, np.int32)
         check(L.pk_stream_score(self._h, _f(enc), enc.shape[1], _i(labels), _i(dur_idx), _i(n_steps), cap, _f(llp) if rows else None, _f(dlp), _i(nd)))
         return dict(label_lp=llp, dur_lp=dlp, n=nd)
+
+    def set_keywords(self, phrases=None, ids=None, min_score=None, patience=None):
+        """pk_stream_set_keywords: phrases (needs the model's vocabulary) or ids (a list of token sequences); neither, or an empty list, clears
+        the set.  Every keyword is watched in every stream: pair = stream * n_kw + keyword."""
+        o = stream_kws_options(min_score, patience)
+        if phrases:
+            arr = (C.c_char_p * len(phrases))(*[p.encode() for p in phrases])
+            check(lib().pk_stream_set_keywords(self._h, arr, None, None, len(phrases), C.byref(o)))
+            self.n_kw = len(phrases)
+        elif ids:
+            pid, off = _pack_ids(ids)
+            check(lib().pk_stream_set_keywords(self._h, None, _i(pid), _i(off), len(ids), C.byref(o)))
+            self.n_kw = len(ids)
+        else:
+            check(lib().pk_stream_set_keywords(self._h, None, None, None, 0, C.byref(o)))
+            self.n_kw = 0
+
+    def spot(self, enc, rows=False):
+        """pk_stream_spot: the stage form on this chunk's enc [S][c][d] -> dict(events [(stream, keyword, start, end, score)...], n_events and,
+        with rows, E / Bs / Ee [S * n_kw][c])."""
+        enc = _c(enc)
+        c, P = enc.shape[1], self.S * self.n_kw
+        cap = P * max(c, 1)
+        ev = (PkKwsEvent * max(cap, 1))()
+        n = C.c_int(0)
+        E = np.zeros((P, max(c, 1)), np.float32); Bs = np.zeros((P, max(c, 1)), np.int32); Ee = np.zeros((P, max(c, 1)), np.int32)
+        check(lib().pk_stream_spot(self._h, _f(enc), c, _f(E) if rows else None, _i(Bs) if rows else None, _i(Ee) if rows else None, ev, cap, C.byref(n)))
+        out = dict(events=_events(ev, n.value), n_events=n.value)
+        if rows:
+            out.update(E=E, Bs=Bs, Ee=Ee)
+        return out
+
+    def push_spot(self, pcm, max_tokens=64):
+        """pk_stream_push_spot: push() that also walks the chunk's frames -> push()'s dict with events / n_events."""
+        pcm = _c(pcm)
+        assert pcm.shape[0] == self.S
+        mt = max_tokens
+        ids = np.zeros((self.S, mt), np.int32); st = np.zeros((self.S, mt), np.int32); en = np.zeros((self.S, mt), np.int32)
+        cf = np.zeros((self.S, mt), np.float32); lens = np.zeros(self.S, np.int32)
+        cap = self.S * self.n_kw * KWS_CHUNK_MAX
+        ev = (PkKwsEvent * max(cap, 1))()
+        n = C.c_int(0)
+        check(lib().pk_stream_push_spot(self._h, _f(pcm), pcm.shape[1], mt, _i(ids), _i(lens), _i(st), _i(en), _f(cf), ev, cap, C.byref(n)))
+        return dict(ids=ids, lens=lens, start=st, end=en, conf=cf, events=_events(ev, n.value), n_events=n.value)
+
+    def spot_flush(self):
+        cap = self.S * self.n_kw
+        ev = (PkKwsEvent * max(cap, 1))()
+        n = C.c_int(0)
+        check(lib().pk_stream_spot_flush(self._h, ev, cap, C.byref(n)))
+        return _events(ev, n.value)
+
+    def spot_timed(self, enc, reps=3):
+        """pk_stream_spot_timed -> (enc_proj + lattice ms, walk + rule ms), HIP events, medians of reps passes."""
+        enc = _c(enc)
+        ms = np.zeros(2, np.float32)
+        check(lib().pk_stream_spot_timed(self._h, _f(enc), enc.shape[1], reps, _f(ms)))
+        return float(ms[0]), float(ms[1])
 
     def reset(self):
         check(lib().pk_stream_reset(self._h))

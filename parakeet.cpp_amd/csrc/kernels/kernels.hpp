@@ -625,6 +625,21 @@ void launch_tdt_kws_norm(const TdtLattice &lt, const float *top, int64_t cells, 
 // every pair needs 1 <= U_b <= kKwsMaxLen, max_hits 1 .. kKwsMaxHits, durations in [0, kTdtAlignMaxDur]
 void launch_tdt_kws(const TdtKwsArgs &a, hipStream_t s);
 
+// Streaming TDT keyword spotting (kernels/tdt_kws_stream.hip): the same walk over the next c frames of every (stream, keyword)
+// pair, picked up from the pair's CARRIED ring, and the online hit rule on the chunk's exit rows.  Every pair of the lattice has T = c frames.
+constexpr int kKwsChunkMaxFrames = 62;          // frames of one push (the streaming decode workspace's limit)
+struct TdtKwsChunkArgs {
+    TdtLattice lt;                              // lab / blk / dl NORMALISED in place by launch_tdt_kws_norm
+    float *ring;                                // carried: pair b from dword (dur_max + 2) (2 D + 1) id_off[b], [frame % (dur_max + 2)][2 D + 1][L_b]
+    int4 *pend;                                 // carried, [B]: the pending hit (score bits, start, end, 1) or (.., .., .., 0)
+    int *last_end;                              // carried, [B]: the end of the last hit that left (-1: none yet)
+    int4 *ev; int *n_ev;                        // this push: [B][c] events (score bits, start, end, 0) in the order emitted, and their number [B]
+    int4 *rows;                                 // optional, [B][c]: (E bits, Bs, Ee, 0) per frame
+    int t0, c;                                  // the chunk is frames [t0, t0 + c) since the session began
+    int dur_max, patience; float min_score;
+};
+void launch_tdt_kws_chunk(const TdtKwsChunkArgs &a, hipStream_t s);
+
 // TDT beam search with n-best output (kernels/tdt_beam.hip).  R = B W rows, beam slot w of clip b is row b W + w.  The
 // beam exists in two copies (step s reads copy s & 1 and writes the other): every per-row array below is [2][R].
 constexpr int kTdtBeamMaxWidth = 16, kTdtBeamMaxLabels = 16, kTdtBeamMaxDurs = 8;

@@ -19,6 +19,7 @@
 
 #include "capi_util.hpp"
 #include "conformer_block.hpp"
+#include "ctc_kws.hpp"
 #include "stream.hpp"
 
 namespace pk {
@@ -57,6 +58,10 @@ void StreamBatch::reset() {
     PK_HIP(hipMemset(wd_.c.p, 0, (size_t)Ln * S * Hp * 4));
     std::vector<int> tok(S, m_.cfg.blank_id);                       // last_token = blank (src/eou.cpp:33-35)
     PK_HIP(hipMemcpy(wd_.ints.p, tok.data(), (size_t)S * 4, hipMemcpyHostToDevice));
+    if (kws_) {                                                     // the keywords stay; the walk and the pending hits start over at frame 0
+        kws_->w.clear(m_.stream);
+        PK_HIP(hipStreamSynchronize(m_.stream));
+    }
 }
 
 // ---- StreamingAudioPreprocessor::process_chunk --------------------------------------------------------------------------------
@@ -374,6 +379,11 @@ void StreamBatch::score(const float *enc, int c, const int32_t *labels, const in
 }
 
 void StreamBatch::push(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf) {
+    push_impl(pcm, n_samples, max_tokens, ids, lens, start, end, conf, /*spot=*/false);
+}
+
+void StreamBatch::push_impl(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf,
+                            bool spot) {
     // Validate BEFORE any carried state (pre-emphasis carry, overlap samples, caches) is touched: a rejected push must leave the streams
     // exactly where they were.  Bound on the encoder frames this push can produce: < 8 leftover mel frames + (559 overlap + n_samples) / 160 + 1
     // new ones, / 8, + 1 -- at most dec_cap_frames_ when n_samples <= (dec_cap_frames_ - 2) * 8 hops.
@@ -387,6 +397,8 @@ void StreamBatch::push(const float *pcm, int n_samples, int max_tokens, int32_t 
     const int c = encode_device(mel_dev_.as<float>(), n_frames);
     if (c == 0) { PK_HIP(hipStreamSynchronize(m_.stream)); return; }
     void *pin = pinned_tokens((size_t)S * (1 + 4 * (size_t)max_tokens) * 4);
+    // (the walk of the chunk's frames and the copy of its events are queued in front of the decode loop, on the same stream: the loop's poll waits for both)
+    if (spot) kws_->enqueue(ws_.x.as<float>(), c, /*rows=*/false);
     {
         struct Hook { Workspace &w; ~Hook() { w.before_poll = nullptr; } } hook{wd_};
         wd_.poll_hit = false;
@@ -397,11 +409,59 @@ void StreamBatch::push(const float *pcm, int n_samples, int max_tokens, int32_t 
     frame_offset_ += c;
 }
 
+// ---- streaming keyword spotting (stream_kws.hpp) ---------------------------------------------------------------------------------------
+void StreamBatch::set_keywords(const int32_t *ids, const int32_t *kw_offsets, int n_kw, const pk_stream_kws_options *opt) {
+    if (n_kw == 0) { kws_.reset(); return; }
+    tdt_align_model_checks(m_);
+    const pk_stream_kws_options o = stream_kws_options_of(opt);
+    pk_kws_options ko;
+    ko.max_hits = 1; ko.min_score = o.min_score;
+    kws_check_args(ids, kw_offsets, n_kw, S, m_.cfg.vocab_size, m_.cfg.blank_id, ko, "streaming TDT keyword spotting");
+    stream_kws_check_options(o);
+    m_.require_gpu();
+    auto next = std::make_unique<StreamKws>(m_, S, ids, kw_offsets, n_kw, o);      // (a refused set leaves the one in place as it was)
+    kws_ = std::move(next);
+}
+
+void StreamBatch::spot(const float *enc, int c, float *E, int32_t *Bs, int32_t *Ee, pk_kws_event *events, int cap, int *n_events, float *ms) {
+    m_.require_gpu();
+    if (!kws_) fail(PK_ERR_INVALID, "invalid argument: no keywords are set on this session (pk_stream_set_keywords)");
+    if (c <= 0) fail(PK_ERR_INVALID, "invalid argument: n_frames");
+    if (c > kKwsChunkMaxFrames) fail(PK_ERR_UNSUPPORTED, "a chunk of %d encoder frames: at most %d can be spotted in one call", c, kKwsChunkMaxFrames);
+    const int d = m_.cfg.hidden_size;
+    hipStream_t st = m_.stream;
+    enc_in_.reserve((size_t)S * c * d * 4);
+    PK_HIP(hipMemcpyAsync(enc_in_.p, enc, (size_t)S * c * d * 4, hipMemcpyHostToDevice, st));
+    hipEvent_t ev[3] = {};
+    if (ms) for (auto &e : ev) PK_HIP(hipEventCreate(&e));
+    kws_->enqueue(enc_in_.as<float>(), c, E || Bs || Ee, ms ? ev : nullptr);
+    PK_CHECK_LAUNCH();
+    PK_HIP(hipStreamSynchronize(st));
+    if (ms) {
+        for (int k = 0; k < 2; ++k) PK_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        for (auto &e : ev) (void)hipEventDestroy(e);
+    }
+    kws_->w.collect(events, cap, n_events, E, Bs, Ee);
+}
+
+void StreamBatch::push_spot(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf,
+                            pk_kws_event *events, int cap, int *n_events) {
+    if (!kws_) fail(PK_ERR_INVALID, "invalid argument: no keywords are set on this session (pk_stream_set_keywords)");
+    *n_events = 0;
+    const int before = kws_->w.t0;
+    push_impl(pcm, n_samples, max_tokens, ids, lens, start, end, conf, /*spot=*/true);
+    if (kws_->w.t0 != before) kws_->w.collect(events, cap, n_events, nullptr, nullptr, nullptr);     // (a push that buffered everything walked no frame)
+}
+
+void StreamBatch::spot_flush(pk_kws_event *events, int cap, int *n_events) {
+    m_.require_gpu();
+    if (!kws_) fail(PK_ERR_INVALID, "invalid argument: no keywords are set on this session (pk_stream_set_keywords)");
+    kws_->w.flush(events, cap, n_events, m_.stream);
+}
+
 }  // namespace pk
 
 using namespace pk;
-
-struct pk_stream { std::unique_ptr<StreamBatch> s; };
 
 extern "C" {
 

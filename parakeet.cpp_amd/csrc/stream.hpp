@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "stream_kws.hpp"
 
 namespace pk {
 
@@ -29,6 +30,16 @@ class StreamBatch {
                float *dur_logp, int32_t *n_done);
     // NemotronTranscriber::transcribe_chunk for S streams; device-resident between the stages
     void push(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf);
+    // Streaming keyword spotting (stream_kws.hpp).  set_keywords: n_kw keywords for every stream (n_kw = 0 clears the set); the walk starts
+    // at frame 0 of the spot calls that follow.  spot: the stage form on host enc rows [S][c][d], as decode; E / Bs / Ee [S n_kw][c] optional.  push_spot: push
+    // that also walks the chunk's frames; the events ride on the push's one host round trip.  spot_flush: emits the pending hits.  Frames of an event count
+    // the frames the spot calls have seen since the last reset (push and decode do not feed the walk: a session that spots hands every chunk to a spot call).
+    void set_keywords(const int32_t *ids, const int32_t *kw_offsets, int n_kw, const pk_stream_kws_options *opt);
+    void spot(const float *enc, int c, float *E, int32_t *Bs, int32_t *Ee, pk_kws_event *events, int cap, int *n_events, float *ms = nullptr);
+    void push_spot(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf,
+                   pk_kws_event *events, int cap, int *n_events);
+    void spot_flush(pk_kws_event *events, int cap, int *n_events);
+    Model &model() { return m_; }
     int S;
 
   private:
@@ -63,6 +74,10 @@ class StreamBatch {
     int encode_device(const float *d_mel, int n_frames);                    // -> ws_.x [S*c][d], returns c
     const float *pos_table(int Tp);
     void decode_device(const float *d_enc, int c, int max_tokens);
+    std::unique_ptr<StreamKws> kws_;                      // the keyword set and its carried walk (nullptr: none set)
+    void push_impl(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf, bool spot);
 };
 
 }  // namespace pk
+
+struct pk_stream { std::unique_ptr<pk::StreamBatch> s; };

@@ -1,15 +1,31 @@
 // examples/stream_wav.cpp -- the reference's streaming usage (README "Streaming": NemotronTranscriber t(weights, vocab, cfg);
 // t.to_gpu(); while (...) text += t.transcribe_chunk(pcm, n);) on the MI355X engine.
 // usage: stream_wav <model.safetensors> <vocab.txt> <audio.wav> <layers> [chunk_samples=2560] [latency_frames=1]
+//        [--spot "phrase"]... [--spot-min-score x] [--spot-patience frames]
+// --spot (repeatable) watches the audio for the phrase while it is transcribed; every hit is printed on stderr as it leaves.
 // (<layers>: number of encoder layers of the weights file -- tests use a 2-layer cut of the nemotron-600m architecture).
 // Prints one JSON object: the chunk texts joined, get_text(), and the token ids with their absolute frames.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
+#include <vector>
 
 #include <parakeet/parakeet.hpp>
 
 int main(int argc, char **argv) {
+    std::vector<std::string> phrases;
+    parakeet::StreamSpotOptions spot;
+    {   // the options leave argv; the positional arguments keep their places
+        int k = 1;
+        for (int i = 1; i < argc; ++i) {
+            if (!std::strcmp(argv[i], "--spot") && i + 1 < argc) phrases.push_back(argv[++i]);
+            else if (!std::strcmp(argv[i], "--spot-min-score") && i + 1 < argc) spot.min_score = (float)std::atof(argv[++i]);
+            else if (!std::strcmp(argv[i], "--spot-patience") && i + 1 < argc) spot.patience = std::atoi(argv[++i]);
+            else argv[k++] = argv[i];
+        }
+        argc = k;
+    }
     if (argc < 5) {
         std::fprintf(stderr, "usage: %s model.safetensors vocab.txt audio.wav layers [chunk_samples] [latency_frames]\n", argv[0]);
         return 2;
@@ -25,7 +41,19 @@ int main(int argc, char **argv) {
         int sr = 0;
         parakeet::detail::check(pk_read_wav(argv[3], &pcm, &n, &sr));
         std::string joined;
-        for (int64_t off = 0; off + chunk <= n; off += chunk) joined += t.transcribe_chunk(pcm + off, (size_t)chunk);
+        if (!phrases.empty()) t.set_keywords(phrases, spot);
+        std::vector<parakeet::SpotEvent> hits;
+        size_t shown = 0;
+        auto show = [&] {
+            for (; shown < hits.size(); ++shown)
+                std::fprintf(stderr, "spot: \"%s\" %.2f s .. %.2f s  score %.4f\n", phrases[hits[shown].keyword].c_str(), hits[shown].start, hits[shown].end,
+                             hits[shown].score);
+        };
+        for (int64_t off = 0; off + chunk <= n; off += chunk) {
+            if (phrases.empty()) joined += t.transcribe_chunk(pcm + off, (size_t)chunk);
+            else { joined += t.transcribe_chunk_spot(pcm + off, (size_t)chunk, hits); show(); }
+        }
+        if (!phrases.empty()) { t.flush_spots(hits); show(); }
         pk_free(pcm);
         auto esc = [](const std::string &s) { std::string o; for (char c : s) { if (c == '"' || c == '\\') o += '\\'; o += c; } return o; };
         std::printf("{\"joined\": \"%s\", \"text\": \"%s\", \"tokens\": [", esc(joined).c_str(), esc(t.get_text()).c_str());

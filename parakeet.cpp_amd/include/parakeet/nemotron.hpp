@@ -11,6 +11,7 @@
 // called); weights load strictly.  The decode quirk of the reference is kept: transcribe_chunk decodes with the DEFAULT blank id
 // of rnnt_streaming_decode_chunk, 1024 (nemotron.cpp:40-42, eou.hpp:91-94), whatever the vocabulary size.
 #pragma once
+#include <limits>
 
 #include <functional>
 #include <string>
@@ -67,6 +68,18 @@ inline EOUConfig make_eou_120m_config() {          // eou.hpp:34-56
     return cfg;
 }
 
+/// Options of the streaming keyword spotting (pk_stream_kws_options) and one hit as it leaves: seconds by the rule of the word timestamps,
+/// start_frame * 0.08 and (end_frame + 1) * 0.08, frames counted from the start of the session.
+struct StreamSpotOptions {
+    float min_score = -std::numeric_limits<float>::infinity();
+    int patience = 0;
+};
+struct SpotEvent {
+    int keyword = 0;
+    float start = 0.0f, end = 0.0f, score = 0.0f;
+    int start_frame = 0, end_frame = 0;
+};
+
 namespace detail {
 
 /// One streaming session on pk_stream_* : the body shared by NemotronTranscriber and StreamingTranscriber (both are
@@ -92,6 +105,12 @@ class StreamSession {
         std::vector<float> conf(mt);
         int32_t len = 0;
         detail::check(pk_stream_push(stream_, data, (int)num_samples, mt, ids.data(), &len, start.data(), end.data(), conf.data()));
+        return take_tokens(ids, start, end, conf, len);
+    }
+
+  private:
+    std::string take_tokens(const std::vector<int32_t> &ids, const std::vector<int32_t> &start, const std::vector<int32_t> &end,
+                            const std::vector<float> &conf, int32_t len) {
         if (len <= 0) return "";
         std::vector<int> fresh(ids.begin(), ids.begin() + len);
         tokens_.insert(tokens_.end(), fresh.begin(), fresh.end());
@@ -101,6 +120,50 @@ class StreamSession {
         if (partial_callback_) partial_callback_(text);
         return text;
     }
+    static void append_events(const std::vector<pk_kws_event> &ev, int n, std::vector<SpotEvent> &out) {
+        for (int i = 0; i < n && i < (int)ev.size(); ++i) {
+            SpotEvent e;
+            e.keyword = ev[i].keyword; e.score = ev[i].score; e.start_frame = ev[i].start; e.end_frame = ev[i].end;
+            e.start = (float)ev[i].start * 0.08f; e.end = (float)(ev[i].end + 1) * 0.08f;
+            out.push_back(e);
+        }
+    }
+
+  public:
+    /// Wake words on live audio (pk_stream_set_keywords): the phrases are watched by every transcribe_chunk_spot from here on; an empty list clears them.
+    void set_keywords(const std::vector<std::string> &phrases, const StreamSpotOptions &opts = StreamSpotOptions()) {
+        ensure_stream();
+        std::vector<const char *> p;
+        for (const std::string &s : phrases) p.push_back(s.c_str());
+        pk_stream_kws_options o;
+        o.min_score = opts.min_score; o.patience = opts.patience;
+        detail::check(pk_stream_set_keywords(stream_, p.data(), nullptr, nullptr, (int)p.size(), &o));
+        n_kw_ = (int)p.size();
+    }
+    /// transcribe_chunk that also spots the keywords in the chunk's frames: the hits that leave with this chunk are appended to `events`.
+    std::string transcribe_chunk_spot(const float *data, size_t num_samples, std::vector<SpotEvent> &events) {
+        if (num_samples == 0) return "";
+        ensure_stream();
+        const int mt = 256, cap = n_kw_ * 62;
+        std::vector<int32_t> ids(mt), start(mt), end(mt);
+        std::vector<float> conf(mt);
+        std::vector<pk_kws_event> ev(cap > 0 ? cap : 1);
+        int32_t len = 0;
+        int n_ev = 0;
+        detail::check(pk_stream_push_spot(stream_, data, (int)num_samples, mt, ids.data(), &len, start.data(), end.data(), conf.data(), ev.data(), cap,
+                                          &n_ev));
+        append_events(ev, n_ev, events);
+        return take_tokens(ids, start, end, conf, len);
+    }
+    /// The hits still held back (pk_stream_spot_flush): call at the end of the audio.
+    void flush_spots(std::vector<SpotEvent> &events) {
+        if (!stream_ || n_kw_ == 0) return;
+        std::vector<pk_kws_event> ev(n_kw_);
+        int n_ev = 0;
+        detail::check(pk_stream_spot_flush(stream_, ev.data(), n_kw_, &n_ev));
+        append_events(ev, n_ev, events);
+    }
+
     /// int16 PCM convenience overload (nemotron.hpp:99-105)
     std::string transcribe_chunk(const int16_t *data, size_t num_samples) {
         std::vector<float> f(num_samples);
@@ -129,6 +192,7 @@ class StreamSession {
     detail::Engine eng_;
     pk_stream *stream_ = nullptr;
     bool on_gpu_ = false;
+    int n_kw_ = 0;
     std::vector<int> tokens_;
     std::vector<TimestampedToken> timestamped_;
     PartialResultCallback partial_callback_;
