@@ -960,6 +960,73 @@ pk_status pk_stream_spot_flush(pk_stream *s, pk_kws_event *events, int cap, int 
  * lattice, ms[1] = normalisation + walk + rule.  The walk's state advances by reps + 1 chunks. */
 pk_status pk_stream_spot_timed(pk_stream *s, const float *enc, int n_frames, int reps, float ms[2]);
 
+/* ---- endpointing on live audio: utterance boundaries in streaming pushes (kernels/endpoint.hip) -------------
+ * When did the speaker start, and when have they finished: START / END events on the log-mel rows a streaming push already leaves on the device
+ * ([n_frames][n_mels] raw ln(mel + 2^-24) per stream, as pk_stream_mel returns them; 10 ms per frame).  Specification: tests/endpoint_ref.py, matched
+ * bit for bit.  Per frame: the level (the fp32 sum of the frame's bins in a fixed order), the noise floor (the exact minimum of the last floor_window
+ * levels: causal, where pk_vad's percentile needs the whole clip), speech0 = level > fmaxf(n_mels threshold_db ln10/10, floor + n_mels margin_db ln10/10).
+ * The rule, frame by frame: min_speech speech frames in a row open an utterance (START; start = the first of them); inside one, min_silence frames
+ * without speech in a row end it (END / SILENCE; end = the last speech frame), else its max_utterance-th frame ends it (END / MAX_LENGTH; end = that
+ * frame).  At most one event per frame and stream; they do not depend on how the audio was cut into pushes.  Token rule (eou_token_id >= 0, sessions
+ * only): a push that returns that token id for a stream emits END / TOKEN for it (start = the open utterance's, or the event's own frame where none is
+ * open; end = at = the last mel frame the push fed) and closes the stream's acoustic state (outside an utterance, no speech run).  Close: with
+ * reset_decoder set, a stream for which any END fired in a push has its prediction-net state put back to what pk_stream_reset gives it (h = c = 0, last
+ * token = blank) after that push's decode and before the next push's: the tokens the push returned belong to the utterance that ended, and because the
+ * close takes effect at a push boundary the transcript after it depends on the chunking (the acoustic events do not).  The noise-floor window, the
+ * encoder caches, the mel leftovers, the frame numbering and a keyword walk are not touched.
+ * Frames count the mel frames the endpoint calls have seen since the last reset; the encoder frame of a mel frame is frame / 8.
+ * The defaults are choices, not measurements (as pk_vad_options' are): threshold_db and margin_db are section 5.8's figures read as the mean
+ * log-mel power per bin.
+ * PK_ERR_INVALID: min_speech_ms < 10, min_silence_ms < 10, floor_window_ms < 10, max_utterance_s * 100 < min_speech frames + 1, a NaN threshold_db or
+ * margin_db, eou_token_id outside [-1, vocabulary) or equal to the blank, a call with no rows, endpointing with no options set, kws outputs with no
+ * keywords set.  PK_ERR_UNSUPPORTED, before anything is allocated: floor_window above 1024 frames, more than 512 frames in one call, n_mels > 512, a
+ * gemm_bf16 model.  A refused set leaves the previous options in place. */
+typedef struct pk_endpoint_options {
+    float threshold_db;        /* -50: absolute level below which a frame is never speech (mean log-mel power per bin, dB) */
+    float margin_db;           /* 9: ... and it must exceed the noise floor by this much */
+    int32_t floor_window_ms;   /* 3000 */
+    int32_t min_speech_ms;     /* 100 */
+    int32_t min_silence_ms;    /* 500 */
+    float max_utterance_s;     /* 30 */
+    int32_t eou_token_id;      /* -1: no token rule */
+    int32_t reset_decoder;     /* 1 */
+} pk_endpoint_options;
+enum { PK_ENDPOINT_START = 1, PK_ENDPOINT_END = 2 };
+enum { PK_ENDPOINT_NONE = 0, PK_ENDPOINT_SILENCE = 1, PK_ENDPOINT_MAX_LENGTH = 2, PK_ENDPOINT_TOKEN = 3 };
+typedef struct pk_endpoint_event {
+    int32_t stream, kind, reason;
+    int32_t start, end, at;    /* mel frames since the reset, inclusive; at: the frame at which the event was emitted */
+} pk_endpoint_event;
+void pk_endpoint_options_default(pk_endpoint_options *out);
+/* The kernel and the rule alone, on host rows (needs a device, no model).  A push hands every stream its next n rows: rows [n_streams][n][n_mels],
+ * 1 <= n <= 512.  level / floor / speech0 [n_streams][n] (each may be NULL).  events: ordered by stream, then by emission; the first `cap` are
+ * written and *n_events is the total (cap = n_streams * n never truncates).  _close: the acoustic close of the streams with mask[s] != 0. */
+typedef struct pk_endpoint_chunk pk_endpoint_chunk;
+pk_status pk_endpoint_chunk_create(int n_streams, int n_mels, const pk_endpoint_options *opt, pk_endpoint_chunk **out);
+pk_status pk_endpoint_chunk_push(pk_endpoint_chunk *w, const float *rows, int n, float *level, float *floor, int32_t *speech0,
+                                 pk_endpoint_event *events, int cap, int *n_events);
+pk_status pk_endpoint_chunk_close(pk_endpoint_chunk *w, const uint8_t *mask);
+/* back to frame 0: the window and the rule's state are cleared, the options stay */
+pk_status pk_endpoint_chunk_reset(pk_endpoint_chunk *w);
+void pk_endpoint_chunk_free(pk_endpoint_chunk *w);
+/* On a streaming session.  opt NULL clears the endpointer; a set starts it at frame 0 of the endpoint calls that follow.  pk_stream_reset keeps the
+ * options and clears the state.  pk_stream_push, pk_stream_push_spot and pk_stream_decode return what they return without it and do not feed it. */
+pk_status pk_stream_set_endpointing(pk_stream *s, const pk_endpoint_options *opt_or_null);
+/* Stage form: mel_rows [n_streams][n_frames][n_mels] on the host, as pk_stream_mel returns them.  No token rule (no tokens). */
+pk_status pk_stream_endpoint(pk_stream *s, const float *mel_rows, int n_frames, float *level, float *floor, int32_t *speech0,
+                             pk_endpoint_event *events, int cap, int *n_events);
+/* pk_stream_push that also feeds the endpointer the push's mel frames: the same tokens, and the events in the same host round trip.  With
+ * kws_events / kws_n_events non-NULL the call is pk_stream_push_spot too (keywords must be set): wake word, transcript and end of turn from one push. */
+pk_status pk_stream_push_endpoint(pk_stream *s, const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start,
+                                  int32_t *end, float *conf, pk_endpoint_event *events, int cap, int *n_events, pk_kws_event *kws_events,
+                                  int kws_cap, int *kws_n_events);
+/* The close without the endpointer: the prediction-net state of the streams with mask[s] != 0 becomes what pk_stream_reset gives it; nothing else
+ * is touched.  For a caller with an end-of-turn policy of its own. */
+pk_status pk_stream_reset_decoder(pk_stream *s, const uint8_t *mask);
+/* Stage timer (tools/bench_stream_endpoint.py): the chunk kernel alone on the given rows `reps` times after one warm-up, HIP events, the median in
+ * ms[0].  The endpointer's state advances by reps + 1 chunks. */
+pk_status pk_stream_endpoint_timed(pk_stream *s, const float *mel_rows, int n_frames, int reps, float ms[1]);
+
 /* ---- plain Transformer encoder: TransformerEncoder::forward / TransformerBlock::forward (src/transformer.cpp:15-88) ------------ */
 /* include/parakeet/transformer.hpp:12-21 (TransformerConfig), dropout omitted (inference). */
 typedef struct pk_transformer_config {

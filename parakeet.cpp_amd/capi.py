@@ -84,6 +84,15 @@ class PkKwsEvent(C.Structure):
     _fields_ = [("stream", C.c_int32), ("keyword", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("score", C.c_float)]
 
 
+class PkEndpointOptions(C.Structure):
+    _fields_ = [("threshold_db", C.c_float), ("margin_db", C.c_float), ("floor_window_ms", C.c_int32), ("min_speech_ms", C.c_int32),
+                ("min_silence_ms", C.c_int32), ("max_utterance_s", C.c_float), ("eou_token_id", C.c_int32), ("reset_decoder", C.c_int32)]
+
+
+class PkEndpointEvent(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("kind", C.c_int32), ("reason", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("at", C.c_int32)]
+
+
 class PkVadOptions(C.Structure):
     _fields_ = [("threshold_db", C.c_float), ("margin_db", C.c_float), ("floor_percent", C.c_int32), ("min_speech_ms", C.c_int32),
                 ("min_silence_ms", C.c_int32), ("pad_ms", C.c_int32), ("max_gap_ms", C.c_int32), ("max_piece_s", C.c_float)]
@@ -290,6 +299,18 @@ _LATE_SIGNATURES = {
     "pk_stream_push_spot": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
     "pk_stream_spot_flush": [C.c_void_p, C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
     "pk_stream_spot_timed": [C.c_void_p, f32p, C.c_int, C.c_int, f32p],
+    "pk_endpoint_options_default": [C.POINTER(PkEndpointOptions)],
+    "pk_endpoint_chunk_create": [C.c_int, C.c_int, C.POINTER(PkEndpointOptions), C.POINTER(C.c_void_p)],
+    "pk_endpoint_chunk_push": [C.c_void_p, f32p, C.c_int, f32p, f32p, i32p, C.POINTER(PkEndpointEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_endpoint_chunk_close": [C.c_void_p, C.POINTER(C.c_uint8)],
+    "pk_endpoint_chunk_reset": [C.c_void_p],
+    "pk_endpoint_chunk_free": [C.c_void_p],
+    "pk_stream_set_endpointing": [C.c_void_p, C.POINTER(PkEndpointOptions)],
+    "pk_stream_endpoint": [C.c_void_p, f32p, C.c_int, f32p, f32p, i32p, C.POINTER(PkEndpointEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_stream_push_endpoint": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, C.POINTER(PkEndpointEvent), C.c_int,
+                                C.POINTER(C.c_int), C.POINTER(PkKwsEvent), C.c_int, C.POINTER(C.c_int)],
+    "pk_stream_reset_decoder": [C.c_void_p, C.POINTER(C.c_uint8)],
+    "pk_stream_endpoint_timed": [C.c_void_p, f32p, C.c_int, C.c_int, f32p],
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
@@ -687,6 +708,100 @@ class TdtKwsChunkWalk:
         if self._h:
             lib().pk_tdt_kws_chunk_free(self._h)
             self._h = None
+
+
+# ---- endpointing on live audio (include/parakeet_amd.h) ------------------------
+ENDPOINT_START, ENDPOINT_END = 1, 2
+ENDPOINT_NONE, ENDPOINT_SILENCE, ENDPOINT_MAX_LENGTH, ENDPOINT_TOKEN = 0, 1, 2, 3
+ENDPOINT_MAX_FRAMES = 512
+
+
+def endpoint_options(**kw):
+    """pk_endpoint_options: the library's defaults with the given fields replaced."""
+    o = PkEndpointOptions()
+    lib().pk_endpoint_options_default(C.byref(o))
+    for k, v in kw.items():
+        if v is not None:
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+    return o
+
+
+def _ep_events(buf, n):
+    """-> [(stream, kind, reason, start, end, at)...]"""
+    return [(e.stream, e.kind, e.reason, e.start, e.end, e.at) for e in buf[:n]]
+
+
+def _mask(mask, S):
+    m = np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8)
+    assert m.shape == (S,)
+    return m, m.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+class EndpointChunk:
+    """pk_endpoint_chunk_*: the endpointing kernel and its rule alone on host rows, n_streams independent streams of n_mels bins.  Needs a device,
+    no model."""
+
+    def __init__(self, n_streams, n_mels, **options):
+        self.S, self.F = n_streams, n_mels
+        o = endpoint_options(**options)
+        self._h = C.c_void_p()
+        check(lib().pk_endpoint_chunk_create(n_streams, n_mels, C.byref(o), C.byref(self._h)))
+
+    def push(self, rows, want_rows=True, cap=None):
+        """rows [S][n][F], the next n frames of every stream -> dict(level, floor, speech0 [S][n] (want_rows), events (the first cap), n_events (the
+        total))."""
+        rows = _c(rows)
+        assert rows.ndim == 3 and rows.shape[0] == self.S and rows.shape[2] == self.F
+        n = rows.shape[1]
+        cap = self.S * max(n, 1) if cap is None else cap
+        ev = (PkEndpointEvent * max(cap, 1))()
+        ne = C.c_int(0)
+        lv = np.zeros((self.S, max(n, 1)), np.float32); fl = np.zeros((self.S, max(n, 1)), np.float32); sp = np.zeros((self.S, max(n, 1)), np.int32)
+        padded = _c(np.concatenate([rows.ravel(), np.zeros(1, np.float32)]))
+        check(lib().pk_endpoint_chunk_push(self._h, _f(padded), n, _f(lv) if want_rows else None, _f(fl) if want_rows else None,
+                                           _i(sp) if want_rows else None, ev, cap, C.byref(ne)))
+        return dict(level=lv, floor=fl, speech0=sp, events=_ep_events(ev, min(ne.value, cap)), n_events=ne.value)
+
+    def close_streams(self, mask):
+        """pk_endpoint_chunk_close: the acoustic close of the streams with mask[s] set."""
+        m, p = _mask(mask, self.S)
+        check(lib().pk_endpoint_chunk_close(self._h, p))
+
+    def reset(self):
+        check(lib().pk_endpoint_chunk_reset(self._h))
+
+    def close(self):
+        if self._h:
+            lib().pk_endpoint_chunk_free(self._h)
+            self._h = None
+
+
+class Utterances:
+    """Collects the tokens of every stream of a session that pushes through Stream.push_endpoint and yields the utterances that finished: feed(r) with
+    push_endpoint's dict -> [dict(stream, ids, text (None without a vocabulary), start, end (seconds: frame * 0.01), reason)...].  The tokens a push
+    returns belong to the utterance that ended in it."""
+
+    def __init__(self, stream):
+        self.stream = stream
+        self.ids = [[] for _ in range(stream.S)]
+
+    def feed(self, r):
+        out = []
+        for s in range(self.stream.S):
+            self.ids[s] += r["ids"][s, :r["lens"][s]].tolist()
+        for (s, kind, reason, start, end, at) in r["events"]:
+            if kind != ENDPOINT_END:
+                continue
+            ids, self.ids[s] = self.ids[s], []
+            text = None
+            if lib().pk_vocab_size(self.stream.model._h) > 0:
+                arr = np.ascontiguousarray(ids + [0], np.int32)
+                buf = C.create_string_buffer(lib().pk_detokenize(self.stream.model._h, _i(arr), len(ids), None, 0) + 1)
+                lib().pk_detokenize(self.stream.model._h, _i(arr), len(ids), buf, len(buf))
+                text = buf.value.decode("utf-8", "replace")
+            out.append(dict(stream=s, ids=ids, text=text, start=start * 0.01, end=end * 0.01, reason=reason))
+        return out
 
 
 # ---- diagnostics ---------------------------------------------------------------------------------
@@ -1290,6 +1405,63 @@ class Stream:
         ms = np.zeros(2, np.float32)
         check(lib().pk_stream_spot_timed(self._h, _f(enc), enc.shape[1], reps, _f(ms)))
         return float(ms[0]), float(ms[1])
+
+    def set_endpointing(self, enable=True, **options):
+        """pk_stream_set_endpointing: the library's defaults with the given pk_endpoint_options fields replaced; enable=False clears it."""
+        if not enable:
+            check(lib().pk_stream_set_endpointing(self._h, None))
+            return
+        o = endpoint_options(**options)
+        check(lib().pk_stream_set_endpointing(self._h, C.byref(o)))
+
+    def endpoint(self, mel, want_rows=False):
+        """pk_stream_endpoint: the stage form on this chunk's mel rows [S][n][F] -> dict(events [(stream, kind, reason, start, end, at)...], n_events
+        and, with want_rows, level / floor / speech0 [S][n])."""
+        mel = _c(mel)
+        n = mel.shape[1]
+        cap = self.S * max(n, 1)
+        ev = (PkEndpointEvent * cap)()
+        ne = C.c_int(0)
+        lv = np.zeros((self.S, max(n, 1)), np.float32); fl = np.zeros((self.S, max(n, 1)), np.float32); sp = np.zeros((self.S, max(n, 1)), np.int32)
+        check(lib().pk_stream_endpoint(self._h, _f(mel), n, _f(lv) if want_rows else None, _f(fl) if want_rows else None,
+                                       _i(sp) if want_rows else None, ev, cap, C.byref(ne)))
+        out = dict(events=_ep_events(ev, ne.value), n_events=ne.value)
+        if want_rows:
+            out.update(level=lv, floor=fl, speech0=sp)
+        return out
+
+    def push_endpoint(self, pcm, max_tokens=64, spot=False):
+        """pk_stream_push_endpoint: push() that also feeds the endpointer -> push()'s dict with events / n_events (the endpoint events) and, with
+        spot, kws_events / kws_n_events (what push_spot returns as events)."""
+        pcm = _c(pcm)
+        assert pcm.shape[0] == self.S
+        mt = max_tokens
+        ids = np.zeros((self.S, mt), np.int32); st = np.zeros((self.S, mt), np.int32); en = np.zeros((self.S, mt), np.int32)
+        cf = np.zeros((self.S, mt), np.float32); lens = np.zeros(self.S, np.int32)
+        cap = self.S * (ENDPOINT_MAX_FRAMES + 1)
+        ev = (PkEndpointEvent * cap)()
+        ne = C.c_int(0)
+        kcap = self.S * self.n_kw * KWS_CHUNK_MAX
+        kev = (PkKwsEvent * max(kcap, 1))()
+        kn = C.c_int(0)
+        check(lib().pk_stream_push_endpoint(self._h, _f(pcm), pcm.shape[1], mt, _i(ids), _i(lens), _i(st), _i(en), _f(cf), ev, cap, C.byref(ne),
+                                            kev if spot else None, kcap if spot else 0, C.byref(kn) if spot else None))
+        out = dict(ids=ids, lens=lens, start=st, end=en, conf=cf, events=_ep_events(ev, ne.value), n_events=ne.value)
+        if spot:
+            out.update(kws_events=_events(kev, kn.value), kws_n_events=kn.value)
+        return out
+
+    def reset_decoder(self, mask):
+        """pk_stream_reset_decoder: the prediction-net state of the streams with mask[s] set becomes what reset() gives it; nothing else is touched."""
+        m, p = _mask(mask, self.S)
+        check(lib().pk_stream_reset_decoder(self._h, p))
+
+    def endpoint_timed(self, mel, reps=3):
+        """pk_stream_endpoint_timed -> the chunk kernel's ms, HIP events, median of reps passes."""
+        mel = _c(mel)
+        ms = np.zeros(1, np.float32)
+        check(lib().pk_stream_endpoint_timed(self._h, _f(mel), mel.shape[1], reps, _f(ms)))
+        return float(ms[0])
 
     def reset(self):
         check(lib().pk_stream_reset(self._h))

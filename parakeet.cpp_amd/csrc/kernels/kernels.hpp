@@ -640,6 +640,27 @@ struct TdtKwsChunkArgs {
 };
 void launch_tdt_kws_chunk(const TdtKwsChunkArgs &a, hipStream_t s);
 
+// Endpointing on live audio (kernels/endpoint.hip): the level of the next n log-mel rows of every stream, the exact sliding
+// minimum of the last W levels as the noise floor, the raw decision and the online START / END rule, one workgroup per stream.
+constexpr int kEndpointMaxFrames = 512;         // rows of one call (a push of the streaming decode workspace's limit feeds about 500)
+constexpr int kEndpointMaxWindow = 1024;        // floor_window in frames
+constexpr int kEndpointMaxBins = 512;
+constexpr int kEndpointStateWords = 8;          // carried per stream: in_utt, run_speech, run_sil, utt_start, last_speech, 3 spare
+struct EndpointChunkArgs {
+    const float *rows;                          // [S][n][F]: ln(mel + 2^-24), not normalised
+    unsigned *ring;                             // carried, [S][W]: the key of frame f in slot f % W
+    int *state;                                 // carried, [S][kEndpointStateWords]
+    int4 *ev; int *n_ev;                        // this call: [S][n] events (kind | reason << 8, start, end, at) in the order emitted, and their number [S]
+    float *level, *floor; int *speech0;         // optional, [S][n]
+    int S, t0, n, F, W;                         // the rows are frames [t0, t0 + n) since the reset
+    int min_speech, min_silence, max_utterance;
+    float abs_thr, margin;
+};
+void launch_endpoint_chunk(const EndpointChunkArgs &a, hipStream_t s);
+// The close of the streams s with mask[s] != 0 (a DEVICE array [S]).  Bit 0: the prediction net's rows of h / c [Ln][S][Hp] become 0 and token[s] the blank
+// (h == nullptr: there is no decoder); bit 1: the acoustic state becomes "outside an utterance, run_speech = 0" (state == nullptr: there is no endpointer).
+void launch_endpoint_close(const unsigned char *mask, int S, float *h, float *c, int Ln, int Hp, int *token, int blank, int *state, hipStream_t s);
+
 // TDT beam search with n-best output (kernels/tdt_beam.hip).  R = B W rows, beam slot w of clip b is row b W + w.  The
 // beam exists in two copies (step s reads copy s & 1 and writes the other): every per-row array below is [2][R].
 constexpr int kTdtBeamMaxWidth = 16, kTdtBeamMaxLabels = 16, kTdtBeamMaxDurs = 8;

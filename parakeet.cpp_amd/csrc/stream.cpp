@@ -62,6 +62,10 @@ void StreamBatch::reset() {
         kws_->w.clear(m_.stream);
         PK_HIP(hipStreamSynchronize(m_.stream));
     }
+    if (ep_) {                                                      // the options stay; the window, the rule's state and the frame numbering start over
+        ep_->clear(m_.stream);
+        PK_HIP(hipStreamSynchronize(m_.stream));
+    }
 }
 
 // ---- StreamingAudioPreprocessor::process_chunk --------------------------------------------------------------------------------
@@ -383,7 +387,7 @@ void StreamBatch::push(const float *pcm, int n_samples, int max_tokens, int32_t 
 }
 
 void StreamBatch::push_impl(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf,
-                            bool spot) {
+                            bool spot, bool endpoint) {
     // Validate BEFORE any carried state (pre-emphasis carry, overlap samples, caches) is touched: a rejected push must leave the streams
     // exactly where they were.  Bound on the encoder frames this push can produce: < 8 leftover mel frames + (559 overlap + n_samples) / 160 + 1
     // new ones, / 8, + 1 -- at most dec_cap_frames_ when n_samples <= (dec_cap_frames_ - 2) * 8 hops.
@@ -394,6 +398,9 @@ void StreamBatch::push_impl(const float *pcm, int n_samples, int max_tokens, int
     for (int s = 0; s < S; ++s) lens[s] = 0;
     const int n_frames = mel_impl(pcm, n_samples, nullptr, 0, /*sync=*/false);
     if (n_frames == 0) return;
+    // (the endpointer takes the push's mel rows, whether or not the encoder has eight of them to consume: queued here, in front of the encoder and the
+    //  decode loop on the same stream, so that the push's one synchronisation brings its events; a valid push feeds at most 497 frames)
+    if (endpoint) ep_->run(mel_dev_.as<float>(), n_frames, /*rows=*/false, m_.stream);
     const int c = encode_device(mel_dev_.as<float>(), n_frames);
     if (c == 0) { PK_HIP(hipStreamSynchronize(m_.stream)); return; }
     void *pin = pinned_tokens((size_t)S * (1 + 4 * (size_t)max_tokens) * 4);
@@ -457,6 +464,92 @@ void StreamBatch::spot_flush(pk_kws_event *events, int cap, int *n_events) {
     m_.require_gpu();
     if (!kws_) fail(PK_ERR_INVALID, "invalid argument: no keywords are set on this session (pk_stream_set_keywords)");
     kws_->w.flush(events, cap, n_events, m_.stream);
+}
+
+// ---- endpointing (stream_endpoint.hpp) ----------------------------------------------------------------------------------------------------
+void StreamBatch::set_endpointing(const pk_endpoint_options *opt) {
+    if (!opt) { ep_.reset(); return; }
+    const EndpointParams p = endpoint_params(*opt, m_.cfg.mel_bins, m_.cfg.vocab_size, m_.cfg.blank_id);
+    if (m_.cfg.gemm_bf16) fail(PK_ERR_UNSUPPORTED, "endpointing is not built for the gemm_bf16 streaming mode");
+    m_.require_gpu();
+    auto next = std::make_unique<EndpointChunk>();                  // (a refused set leaves the options in place as they were)
+    next->setup(S, m_.cfg.mel_bins, p);
+    next->alloc(m_.stream);
+    PK_HIP(hipStreamSynchronize(m_.stream));
+    ep_ = std::move(next);
+}
+
+void StreamBatch::endpoint(const float *mel_rows, int n, float *level, float *floor, int32_t *speech0, pk_endpoint_event *events, int cap,
+                           int *n_events, float *ms) {
+    m_.require_gpu();
+    if (!ep_) fail(PK_ERR_INVALID, "invalid argument: no endpointing options are set on this session (pk_stream_set_endpointing)");
+    ep_->check_frames(n);
+    hipStream_t st = m_.stream;
+    const size_t bytes = (size_t)S * n * m_.cfg.mel_bins * 4;
+    ep_in_.reserve(bytes);
+    PK_HIP(hipMemcpyAsync(ep_in_.p, mel_rows, bytes, hipMemcpyHostToDevice, st));
+    hipEvent_t ev[2] = {};
+    if (ms) for (auto &e : ev) PK_HIP(hipEventCreate(&e));
+    ep_->run(ep_in_.as<float>(), n, level || floor || speech0, st, ms ? ev : nullptr);
+    PK_CHECK_LAUNCH();
+    PK_HIP(hipStreamSynchronize(st));
+    if (ms) {
+        PK_HIP(hipEventElapsedTime(ms, ev[0], ev[1]));
+        for (auto &e : ev) (void)hipEventDestroy(e);
+    }
+    std::vector<std::vector<pk_endpoint_event>> per;
+    ep_->take(per);
+    put_endpoint_events(per, events, cap, n_events);
+    ep_->take_rows(level, floor, speech0);
+}
+
+void StreamBatch::push_endpoint(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end,
+                                float *conf, pk_endpoint_event *events, int cap, int *n_events, pk_kws_event *kws_events, int kws_cap,
+                                int *kws_n_events) {
+    if (!ep_) fail(PK_ERR_INVALID, "invalid argument: no endpointing options are set on this session (pk_stream_set_endpointing)");
+    const bool spot = kws_n_events != nullptr;
+    if (spot && !kws_) fail(PK_ERR_INVALID, "invalid argument: no keywords are set on this session (pk_stream_set_keywords)");
+    *n_events = 0;
+    if (spot) *kws_n_events = 0;
+    const int before = ep_->t0, kws_before = spot ? kws_->w.t0 : 0;
+    push_impl(pcm, n_samples, max_tokens, ids, lens, start, end, conf, spot, /*endpoint=*/true);
+    if (spot && kws_->w.t0 != kws_before) kws_->w.collect(kws_events, kws_cap, kws_n_events, nullptr, nullptr, nullptr);
+    if (ep_->t0 == before) return;                                  // (a push that buffered everything fed no frame)
+    std::vector<std::vector<pk_endpoint_event>> per;
+    ep_->take(per);
+    // the token rule and the decision to close, on the host: bit 0 restarts the stream's prediction net, bit 1 closes its acoustic state
+    std::vector<unsigned char> bits(S, 0);
+    bool any = false;
+    const EndpointParams &p = ep_->p;
+    for (int s = 0; s < S; ++s) {
+        bool ended = false;
+        for (const pk_endpoint_event &e : per[s]) ended = ended || e.kind == PK_ENDPOINT_END;
+        if (p.eou_token_id >= 0)
+            for (int i = 0; i < lens[s]; ++i)
+                if (ids[(size_t)s * max_tokens + i] == p.eou_token_id) {
+                    const int at = ep_->t0 - 1;
+                    pk_endpoint_event e;
+                    e.stream = s; e.kind = PK_ENDPOINT_END; e.reason = PK_ENDPOINT_TOKEN; e.start = ep_->in_utt(s) ? ep_->utt_start(s) : at; e.end = at; e.at = at;
+                    per[s].push_back(e);
+                    bits[s] |= 2;
+                    ended = true;
+                    break;
+                }
+        if (ended && p.reset_decoder) bits[s] |= 1;
+        any = any || bits[s];
+    }
+    if (any) {                                                      // (about once per utterance: the wait is not on the steady path)
+        ep_->close(bits, wd_.h.as<float>(), wd_.c.as<float>(), m_.cfg.num_lstm_layers, m_.cfg.pred_hidden, wd_.ints.as<int>(), m_.cfg.blank_id, m_.stream);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipStreamSynchronize(m_.stream));
+    }
+    put_endpoint_events(per, events, cap, n_events);
+}
+
+void StreamBatch::reset_decoder(const uint8_t *mask) {
+    m_.require_gpu();
+    reset_decoder_rows(mask, S, wd_.h.as<float>(), wd_.c.as<float>(), m_.cfg.num_lstm_layers, m_.cfg.pred_hidden, wd_.ints.as<int>(), m_.cfg.blank_id,
+                       dec_mask_, m_.stream);
 }
 
 }  // namespace pk

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "stream_endpoint.hpp"
 #include "stream_kws.hpp"
 
 namespace pk {
@@ -39,6 +40,16 @@ class StreamBatch {
     void push_spot(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf,
                    pk_kws_event *events, int cap, int *n_events);
     void spot_flush(pk_kws_event *events, int cap, int *n_events);
+    // Endpointing (stream_endpoint.hpp).  set_endpointing: nullptr clears it; a set starts at frame 0 of the endpoint calls that follow.
+    // endpoint: the stage form on host mel rows [S][n][F], as mel returns them (no token rule and no close: there is no decode in it).  push_endpoint: push
+    // that also feeds the endpointer the push's mel frames, applies the token rule to the tokens it returns and closes the streams whose utterance ended;
+    // with kws outputs it is push_spot too.  reset_decoder: the close of the prediction net alone, for a caller with a policy of its own.
+    void set_endpointing(const pk_endpoint_options *opt);
+    void endpoint(const float *mel_rows, int n, float *level, float *floor, int32_t *speech0, pk_endpoint_event *events, int cap, int *n_events,
+                  float *ms = nullptr);
+    void push_endpoint(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf,
+                       pk_endpoint_event *events, int cap, int *n_events, pk_kws_event *kws_events, int kws_cap, int *kws_n_events);
+    void reset_decoder(const uint8_t *mask);
     Model &model() { return m_; }
     int S;
 
@@ -75,7 +86,10 @@ class StreamBatch {
     const float *pos_table(int Tp);
     void decode_device(const float *d_enc, int c, int max_tokens);
     std::unique_ptr<StreamKws> kws_;                      // the keyword set and its carried walk (nullptr: none set)
-    void push_impl(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf, bool spot);
+    std::unique_ptr<EndpointChunk> ep_;                   // the endpointer and its carried state (nullptr: no options set)
+    DevBuf ep_in_, dec_mask_;
+    void push_impl(const float *pcm, int n_samples, int max_tokens, int32_t *ids, int32_t *lens, int32_t *start, int32_t *end, float *conf, bool spot,
+                   bool endpoint = false);
 };
 
 }  // namespace pk

@@ -80,6 +80,22 @@ struct SpotEvent {
     int start_frame = 0, end_frame = 0;
 };
 
+/// Options of the endpointing on live audio (pk_endpoint_options; the defaults are the library's, choices and not measurements) and one finished
+/// utterance: the tokens returned since the previous one ended, seconds at frame * 0.01 (10 ms mel frames counted from the start of the session).
+struct EndpointOptions {
+    float threshold_db = -50.0f, margin_db = 9.0f;
+    int floor_window_ms = 3000, min_speech_ms = 100, min_silence_ms = 500;
+    float max_utterance_s = 30.0f;
+    int eou_token_id = -1;
+    bool reset_decoder = true;
+};
+struct Utterance {
+    std::string text;
+    std::vector<int> ids;
+    float start = 0.0f, end = 0.0f;
+    int reason = 0;             ///< PK_ENDPOINT_SILENCE / _MAX_LENGTH / _TOKEN
+};
+
 namespace detail {
 
 /// One streaming session on pk_stream_* : the body shared by NemotronTranscriber and StreamingTranscriber (both are
@@ -164,6 +180,41 @@ class StreamSession {
         append_events(ev, n_ev, events);
     }
 
+    /// End of turn on live audio (pk_stream_set_endpointing): every transcribe_chunk_endpoint from here on feeds the endpointer.
+    void set_endpointing(const EndpointOptions &opts = EndpointOptions()) {
+        ensure_stream();
+        pk_endpoint_options o;
+        o.threshold_db = opts.threshold_db; o.margin_db = opts.margin_db; o.floor_window_ms = opts.floor_window_ms;
+        o.min_speech_ms = opts.min_speech_ms; o.min_silence_ms = opts.min_silence_ms; o.max_utterance_s = opts.max_utterance_s;
+        o.eou_token_id = opts.eou_token_id; o.reset_decoder = opts.reset_decoder ? 1 : 0;
+        detail::check(pk_stream_set_endpointing(stream_, &o));
+        utt_ids_.clear();
+    }
+    /// transcribe_chunk that also watches for the end of the utterance: an utterance that ended in this chunk is appended to `finished` with the tokens
+    /// returned since the previous one ended (this chunk's included).
+    std::string transcribe_chunk_endpoint(const float *data, size_t num_samples, std::vector<Utterance> &finished) {
+        if (num_samples == 0) return "";
+        ensure_stream();
+        const int mt = 256, cap = 513;
+        std::vector<int32_t> ids(mt), start(mt), end(mt);
+        std::vector<float> conf(mt);
+        std::vector<pk_endpoint_event> ev(cap);
+        int32_t len = 0;
+        int n_ev = 0;
+        detail::check(pk_stream_push_endpoint(stream_, data, (int)num_samples, mt, ids.data(), &len, start.data(), end.data(), conf.data(), ev.data(), cap,
+                                              &n_ev, nullptr, 0, nullptr));
+        utt_ids_.insert(utt_ids_.end(), ids.begin(), ids.begin() + (len > 0 ? len : 0));
+        for (int i = 0; i < n_ev && i < cap; ++i) {
+            if (ev[i].kind != PK_ENDPOINT_END) continue;
+            Utterance u;
+            u.ids.swap(utt_ids_);
+            u.start = (float)ev[i].start * 0.01f; u.end = (float)ev[i].end * 0.01f; u.reason = ev[i].reason;
+            if (eng_.tokenizer().loaded() && !u.ids.empty()) u.text = eng_.tokenizer().decode(u.ids);
+            finished.push_back(std::move(u));
+        }
+        return take_tokens(ids, start, end, conf, len);
+    }
+
     /// int16 PCM convenience overload (nemotron.hpp:99-105)
     std::string transcribe_chunk(const int16_t *data, size_t num_samples) {
         std::vector<float> f(num_samples);
@@ -176,6 +227,7 @@ class StreamSession {
         if (stream_) detail::check(pk_stream_reset(stream_));
         tokens_.clear();
         timestamped_.clear();
+        utt_ids_.clear();
     }
     /// Full transcription so far (nemotron.cpp:60-65)
     std::string get_text() const { return (eng_.tokenizer().loaded() && !tokens_.empty()) ? eng_.tokenizer().decode(tokens_) : ""; }
@@ -193,7 +245,7 @@ class StreamSession {
     pk_stream *stream_ = nullptr;
     bool on_gpu_ = false;
     int n_kw_ = 0;
-    std::vector<int> tokens_;
+    std::vector<int> tokens_, utt_ids_;
     std::vector<TimestampedToken> timestamped_;
     PartialResultCallback partial_callback_;
 };
