@@ -5,8 +5,8 @@
 // label 0 .. D-1, each alpha[src] + (x + dl) as two fp32 adds, strict > (the earlier candidate stays).  Every value is compared bit for bit.
 //
 //   tdt_lattice_act_kernel    z = relu(enc_proj[t] + pred_proj[u]) for a chunk of lattice rows: the A operand of the heads product on the fp32 GEMM.
-//       One wave per row, the row itself is joint_act_row (tdt_lattice_dev.hpp; the beam search's activation calls it too).
-//   tdt_lattice_keep_kernel   one wave per row of the heads product's output [V + D]: the canonical log-softmax (decode_dev.hpp wave_row_max_lse: row
+//       One wave per row: lattice_act_row<false> (tdt_lattice_dev.hpp; the keyword spotting's kernel is the <true> form), the row itself joint_act_row.
+//   tdt_lattice_keep_kernel   one wave per row of the heads product's output [V + D]: the canonical log-softmax (wave_row_max_lse: row
 //       maximum, dexpf_nonpos, 64 strided partial sums in index order, wave_sum64, dlogf; the duration head through wave_logsoftmax_argmax's
 //       low-8 form, exactly the decision kernel's) and only 2 + D values leave: the label log-prob of ids[u], the blank's, the D duration
 //       log-probs.  The chunk's logits are the only place a whole row exists.
@@ -40,31 +40,9 @@
 
 namespace pk {
 
-namespace {
-
-// utterance of lattice row r: the last b with cell_off[b] <= r (cell_off ascending, cell_off[B] = rows in all)
-__device__ __forceinline__ int lattice_utt(const int64_t *__restrict__ cell_off, int B, int64_t r) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (cell_off[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(256) void tdt_lattice_act_kernel(TdtLattice lt, const int *__restrict__ ep_row0, const float *__restrict__ ep,
                                                               const float *__restrict__ pp, int J, int64_t row0, int n, float *__restrict__ z) {
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const int64_t r = row0 + i;
-    const int b = lattice_utt(lt.cell_off, lt.B, r);
-    const int U1 = lt.id_off[b + 1] - lt.id_off[b] + 1;
-    const int64_t c = r - lt.cell_off[b];
-    const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
-    joint_act_row(ep + ((int64_t)ep_row0[b] + t) * J, pp + ((int64_t)u * lt.B + b) * J, z + i * J, J, lane);
+    lattice_act_row<false>(lt, ep_row0, ep, pp, nullptr, 0, J, row0, n, z);
 }
 
 __global__ __launch_bounds__(256) void tdt_lattice_keep_kernel(TdtLattice lt, const int *__restrict__ ids, const float *__restrict__ logits, int V,
@@ -73,7 +51,7 @@ __global__ __launch_bounds__(256) void tdt_lattice_keep_kernel(TdtLattice lt, co
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const int64_t r = row0 + i;
-    const int b = lattice_utt(lt.cell_off, lt.B, r);
+    const int b = lattice_row_owner(lt.cell_off, lt.B, r);
     const int U = lt.id_off[b + 1] - lt.id_off[b], U1 = U + 1;
     const int64_t c = r - lt.cell_off[b];
     const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);

@@ -7,10 +7,11 @@
 // frame; max-plus in pull form, candidates blank 0 .. D-1 then label 0 .. D-1, strict >; every state carries the frame at which its first token was
 // emitted, so there are no back-pointers.  Every score is compared bit for bit, every span and count exactly.
 //
-//   tdt_kws_act_kernel    tdt_lattice_act_kernel with one indirection: pair b takes the prediction net's rows of slot net_of[b], so the net runs once per
-//       distinct keyword of a group and not once per pair.  The row itself is joint_act_row (tdt_lattice_dev.hpp).
+//   tdt_kws_act_kernel    lattice_act_row<true> (tdt_lattice_dev.hpp): the alignment's row with one indirection, pair b takes the prediction net's rows of
+//       slot net_of[b], so the net runs once per distinct keyword of a group and not once per pair.
 //   tdt_kws_keep_kernel   tdt_lattice_keep_kernel that also stores top = fl(+0.0 - lse), the log-prob of the row's largest token logit
-//       (fl(fl(m - m) - lse) with the m, lse of wave_row_max_lse).  A copy, not a template: the alignment's code object stays what it was.
+//       (fl(fl(m - m) - lse) with the m, lse of wave_row_max_lse).  A copy: built on one row template both kernels came out of the compiler in another
+//       instruction order (profiles/kws_shared_walk.md), and the alignment's code object stays what it was.
 //   tdt_kws_norm_kernel   one thread per cell, in place: lab -= top, blk -= top, dl[i] -= max_i dl[i].  A pass of its own so that the host-lattice entry
 //       point and the model's share one walk, and the diagnostic entry point can return the values before it.
 //   tdt_kws_kernel        ONE WAVE per pair, lane u owns column u (L <= 64), advancing by anti-diagonals d = t + u as tdt_align_kernel does.  A finished
@@ -39,32 +40,10 @@
 
 namespace pk {
 
-namespace {
-
-// pair of lattice row r: the last b with cell_off[b] <= r (cell_off ascending, cell_off[B] = rows in all)
-__device__ __forceinline__ int kws_pair_of(const int64_t *__restrict__ cell_off, int B, int64_t r) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (cell_off[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(256) void tdt_kws_act_kernel(TdtLattice lt, const int *__restrict__ ep_row0, const float *__restrict__ ep,
                                                           const float *__restrict__ pp, const int *__restrict__ net_of, int n_net, int J, int64_t row0,
                                                           int n, float *__restrict__ z) {
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const int64_t r = row0 + i;
-    const int b = kws_pair_of(lt.cell_off, lt.B, r);
-    const int U1 = lt.id_off[b + 1] - lt.id_off[b] + 1;
-    const int64_t c = r - lt.cell_off[b];
-    const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
-    joint_act_row(ep + ((int64_t)ep_row0[b] + t) * J, pp + ((int64_t)u * n_net + net_of[b]) * J, z + i * J, J, lane);
+    lattice_act_row<true>(lt, ep_row0, ep, pp, net_of, n_net, J, row0, n, z);
 }
 
 __global__ __launch_bounds__(256) void tdt_kws_keep_kernel(TdtLattice lt, float *__restrict__ top, const int *__restrict__ ids,
@@ -73,7 +52,7 @@ __global__ __launch_bounds__(256) void tdt_kws_keep_kernel(TdtLattice lt, float 
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const int64_t r = row0 + i;
-    const int b = kws_pair_of(lt.cell_off, lt.B, r);
+    const int b = lattice_row_owner(lt.cell_off, lt.B, r);
     const int U = lt.id_off[b + 1] - lt.id_off[b], U1 = U + 1;
     const int64_t c = r - lt.cell_off[b];
     const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
@@ -89,7 +68,7 @@ __global__ __launch_bounds__(256) void tdt_kws_keep_kernel(TdtLattice lt, float 
 __global__ __launch_bounds__(256) void tdt_kws_norm_kernel(TdtLattice lt, const float *__restrict__ top, int64_t cells) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= cells) return;
-    const int b = kws_pair_of(lt.cell_off, lt.B, r);
+    const int b = lattice_row_owner(lt.cell_off, lt.B, r);
     const int U = lt.id_off[b + 1] - lt.id_off[b], U1 = U + 1, D = lt.D;
     const int64_t c = r - lt.cell_off[b];
     const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
@@ -231,13 +210,12 @@ void launch_tdt_kws_norm(const TdtLattice &lt, const float *top, int64_t cells, 
 }
 
 void launch_tdt_kws(const TdtKwsArgs &a, hipStream_t s) {
-    if (a.dur_max < 0 || a.dur_max > kTdtAlignMaxDur || a.lt.D < 1 || a.lt.D > 8 || a.max_hits < 1 || a.max_hits > kKwsMaxHits) {
+    if (!kws_ring_limits_ok(a.lt, a.dur_max) || a.max_hits < 1 || a.max_hits > kKwsMaxHits) {
         fprintf(stderr, "parakeet_amd: internal error: launch_tdt_kws outside the kernel's limits (dur_max %d, D %d, max_hits %d)\n", a.dur_max, a.lt.D,
                 a.max_hits);
         abort();
     }
-    const size_t lds = (size_t)(a.dur_max + 2) * (2 * a.lt.D + 1) * 64 * sizeof(float);
-    hipLaunchKernelGGL(tdt_kws_kernel, dim3(a.lt.B), dim3(64), lds, s, a);
+    hipLaunchKernelGGL(tdt_kws_kernel, dim3(a.lt.B), dim3(64), kws_ring_lds_bytes(a.dur_max, a.lt.D), s, a);
 }
 
 }  // namespace pk

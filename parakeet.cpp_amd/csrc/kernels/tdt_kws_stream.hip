@@ -146,12 +146,12 @@ __global__ __launch_bounds__(64) void tdt_kws_chunk_kernel(TdtKwsChunkArgs a) {
 }
 
 void launch_tdt_kws_chunk(const TdtKwsChunkArgs &a, hipStream_t s) {
-    if (a.dur_max < 0 || a.dur_max > kTdtAlignMaxDur || a.lt.D < 1 || a.lt.D > 8 || a.c < 1 || a.c > kKwsChunkMaxFrames || a.t0 < 0 || a.patience < 0) {
+    if (!kws_ring_limits_ok(a.lt, a.dur_max) || a.c < 1 || a.c > kKwsChunkMaxFrames || a.t0 < 0 || a.patience < 0) {
         fprintf(stderr, "parakeet_amd: internal error: launch_tdt_kws_chunk outside the kernel's limits (dur_max %d, D %d, c %d, t0 %d, patience %d)\n",
                 a.dur_max, a.lt.D, a.c, a.t0, a.patience);
         abort();
     }
-    const size_t lds = (size_t)(a.dur_max + 2) * (2 * a.lt.D + 1) * 64 * sizeof(float) + (size_t)a.c * 3 * sizeof(int);
+    const size_t lds = kws_ring_lds_bytes(a.dur_max, a.lt.D) + (size_t)a.c * 3 * sizeof(int);
     hipLaunchKernelGGL(tdt_kws_chunk_kernel, dim3(a.lt.B), dim3(64), lds, s, a);
 }
 

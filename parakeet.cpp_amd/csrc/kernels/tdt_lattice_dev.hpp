@@ -1,12 +1,11 @@
 // parakeet.cpp_amd/csrc/kernels/tdt_lattice_dev.hpp -- code shared by the kernels over the TDT lattice (DESIGN.md sections 5.5.2, 5.5.3, 5.5.5): the
 // anti-diagonal walk as a function template over its fold (tdt_total_kernel calls it), the launch checks of the two walk kernels, the joint activation row of
-// the lattice and of the beam, a label arc's end frame.
+// the lattice and of the beam, the activation row body of the alignment's and the keyword spotting's lattice kernels, a label arc's end frame.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
 
-#include "../pk_devmath.h"
-#include "kernels.hpp"
+#include "decode_dev.hpp"
 
 namespace pk {
 
@@ -28,6 +27,36 @@ __device__ __forceinline__ void joint_act_row(const float *__restrict__ er, cons
             zr[j] = s > 0.0f ? s : 0.0f;
         }
     }
+}
+
+// owner (utterance, or keyword spotting pair) of lattice row r: the last b with cell_off[b] <= r (cell_off ascending, cell_off[B] = rows in all)
+__device__ __forceinline__ int lattice_row_owner(const int64_t *__restrict__ cell_off, int B, int64_t r) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cell_off[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The body of a kernel over lattice rows [row0, row0 + n), one wave per row, four rows per workgroup of 256: z[i] = joint_act_row of the row's frame and
+// prediction-net row.  Owner b reads the net's rows pp[u B + b], or with NET_OF pp[u n_net + net_of[b]] (the net run once per distinct keyword).
+template <bool NET_OF>
+__device__ __forceinline__ void lattice_act_row(const TdtLattice &lt, const int *__restrict__ ep_row0, const float *__restrict__ ep,
+                                                const float *__restrict__ pp, const int *__restrict__ net_of, int n_net, int J, int64_t row0, int n,
+                                                float *__restrict__ z) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int64_t r = row0 + i;
+    const int b = lattice_row_owner(lt.cell_off, lt.B, r);
+    const int U1 = lt.id_off[b + 1] - lt.id_off[b] + 1;
+    const int64_t c = r - lt.cell_off[b];
+    const int t = (int)(c / U1), u = (int)(c - (int64_t)t * U1);
+    int64_t pr;
+    if constexpr (NET_OF) pr = (int64_t)u * n_net + net_of[b];
+    else pr = (int64_t)u * lt.B + b;
+    joint_act_row(ep + ((int64_t)ep_row0[b] + t) * J, pp + pr * J, z + i * J, J, lane);
 }
 
 // last frame of a token emitted at frame t by a label arc of duration dur, in an utterance of T frames
@@ -131,5 +160,10 @@ inline size_t tdt_walk_launch_checks(const char *who, const TdtLattice &lt, int 
     }
     return (size_t)(dur_max + 2) * (u_max + 1) * sizeof(float);
 }
+
+// The spotting walks' LDS ring (tdt_kws.hip, tdt_kws_stream.hip), [dur_max + 2][2 D + 1][64] dwords: the limits it is built for (refused by the host before
+// anything is allocated; each launcher adds its own) and its dynamic LDS in bytes.
+inline bool kws_ring_limits_ok(const TdtLattice &lt, int dur_max) { return dur_max >= 0 && dur_max <= kTdtAlignMaxDur && lt.D >= 1 && lt.D <= 8; }
+inline size_t kws_ring_lds_bytes(int dur_max, int D) { return (size_t)(dur_max + 2) * (2 * D + 1) * 64 * sizeof(float); }
 
 }  // namespace pk

@@ -202,24 +202,13 @@ StreamKws::StreamKws(Model &m, int S, const int32_t *ids, const int32_t *kw_offs
 }
 
 void StreamKws::enqueue(const float *d_enc, int c, bool rows, hipEvent_t *ev) {
-    const pk_config &cfg = m_.cfg;
-    const int V = cfg.vocab_size, J = cfg.joint_hidden;
+    const int J = m_.cfg.joint_hidden;
     hipStream_t s = m_.stream;
     if (ev) PK_HIP(hipEventRecord(ev[0], s));
     ep_.reserve((size_t)S_ * c * J * 4);
     m_.run_enc_proj(d_enc, (int64_t)S_ * c, ep_.as<float>(), s);
     w.plan(c, pid_.data(), s);
-    TdtAlignWs &a = w.a;
-    const int CH = a.chunk_rows;
-    a.z.reserve((size_t)CH * J * 4);
-    a.logits.reserve((size_t)CH * (V + a.D) * 4);
-    const TdtLattice lt = a.lattice();
-    for (int64_t r0 = 0; r0 < a.cells; r0 += CH) {
-        const int nr = (int)std::min<int64_t>(CH, a.cells - r0);
-        launch_tdt_kws_act(lt, a.ep_row0(), ep_.as<float>(), net_.pp.as<float>(), net_of_.as<int>(), n_net_, J, r0, nr, a.z.as<float>(), s);
-        run_tdt_align_heads(m_, a, nr, s);
-        launch_tdt_kws_keep(lt, w.top.as<float>(), a.ids.as<int>(), a.logits.as<float>(), V, cfg.blank_id, r0, nr, s);
-    }
+    tdt_kws_build_lattice(m_, w.a, w.top.as<float>(), ep_.as<float>(), net_, net_of_.as<int>(), n_net_, s);
     if (ev) PK_HIP(hipEventRecord(ev[1], s));
     w.walk(rows, s);
     if (ev) PK_HIP(hipEventRecord(ev[2], s));

@@ -75,6 +75,20 @@ void tdt_kws_gather(TdtKwsWs &ws, int g0, hipStream_t s) {
     PK_HIP(hipStreamSynchronize(s));
 }
 
+void tdt_kws_build_lattice(Model &m, TdtAlignWs &a, float *top, const float *ep, const TdtAlignWs &net, const int *net_of, int n_net, hipStream_t s) {
+    const pk_config &c = m.cfg;
+    const int V = c.vocab_size, J = c.joint_hidden, CH = a.chunk_rows;
+    a.z.reserve((size_t)CH * J * 4);
+    a.logits.reserve((size_t)CH * (V + a.D) * 4);
+    const TdtLattice lt = a.lattice();
+    for (int64_t r0 = 0; r0 < a.cells; r0 += CH) {
+        const int nr = (int)std::min<int64_t>(CH, a.cells - r0);
+        launch_tdt_kws_act(lt, a.ep_row0(), ep, net.pp.as<float>(), net_of, n_net, J, r0, nr, a.z.as<float>(), s);
+        run_tdt_align_heads(m, a, nr, s);
+        launch_tdt_kws_keep(lt, top, a.ids.as<int>(), a.logits.as<float>(), V, c.blank_id, r0, nr, s);
+    }
+}
+
 void run_tdt_kws_call(Model &m, TdtKwsWs &ws, const float *d_ep, const int32_t *kw_ids, const int32_t *kw_offsets, int chunk_rows, bool walk,
                       hipEvent_t *ev, float *ms) {
     const pk_config &c = m.cfg;
@@ -114,16 +128,7 @@ void run_tdt_kws_call(Model &m, TdtKwsWs &ws, const float *d_ep, const int32_t *
         PK_HIP(hipMemcpyAsync(ws.net_of.p, ws.h_net_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
         run_tdt_align_pred(m, ws.net, ws.kids.data(), s, state);
         if (ev) PK_HIP(hipEventRecord(ev[1], s));
-        const int CH = ws.a.chunk_rows;
-        ws.a.z.reserve((size_t)CH * J * 4);
-        ws.a.logits.reserve((size_t)CH * (V + ws.a.D) * 4);
-        const TdtLattice lt = ws.a.lattice();
-        for (int64_t r0 = 0; r0 < ws.a.cells; r0 += CH) {
-            const int nr = (int)std::min<int64_t>(CH, ws.a.cells - r0);
-            launch_tdt_kws_act(lt, ws.a.ep_row0(), d_ep, ws.net.pp.as<float>(), ws.net_of.as<int>(), nk, J, r0, nr, ws.a.z.as<float>(), s);
-            run_tdt_align_heads(m, ws.a, nr, s);
-            launch_tdt_kws_keep(lt, ws.top.as<float>(), ws.a.ids.as<int>(), ws.a.logits.as<float>(), V, c.blank_id, r0, nr, s);
-        }
+        tdt_kws_build_lattice(m, ws.a, ws.top.as<float>(), d_ep, ws.net, ws.net_of.as<int>(), nk, s);
         if (ev) PK_HIP(hipEventRecord(ev[2], s));
         if (walk) run_tdt_kws_dp(ws, s);
         if (ev) PK_HIP(hipEventRecord(ev[3], s));

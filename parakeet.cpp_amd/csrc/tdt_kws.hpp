@@ -42,6 +42,9 @@ void tdt_kws_plan_call(TdtKwsWs &ws, const int32_t *durations, int D, int V, int
 void run_tdt_kws_dp(TdtKwsWs &ws, hipStream_t s);
 // copies the n results of the walk just queued to ws.n_hits / start / end / score from pair g0 on and waits for the stream
 void tdt_kws_gather(TdtKwsWs &ws, int g0, hipStream_t s);
+// Queues the lattice of the pairs planned and uploaded in `a` (its values, and top[cells]) in chunks of a.chunk_rows rows: activation, heads product, kept
+// values.  ep = enc_proj of the frames a.ep_row0() points into; pair b reads the rows of slot net_of[b] (device, [pairs]) of net.pp, which holds n_net slots.
+void tdt_kws_build_lattice(Model &m, TdtAlignWs &a, float *top, const float *ep, const TdtAlignWs &net, const int *net_of, int n_net, hipStream_t s);
 // Queues the planned call on the model's stream: d_ep = enc_proj of the call's packed frames.  Group by group: prediction net, lattice, walk (walk == false:
 // the lattice of the LAST group is left in ws.a / ws.top, not normalised).  ev (optional, 4 events), ms[3] accumulates the three stages over the groups.
 void run_tdt_kws_call(Model &m, TdtKwsWs &ws, const float *d_ep, const int32_t *kw_ids, const int32_t *kw_offsets, int chunk_rows = 0, bool walk = true,

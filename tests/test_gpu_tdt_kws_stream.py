@@ -95,6 +95,30 @@ def test_pushes_equal_reference(dname, family, chunking):
         w.close()
 
 
+@pytest.mark.parametrize("family", ["ties", "holes"])
+@pytest.mark.parametrize("dname", ["d01234", "d08"])
+def test_offline_walk_equals_whole_session_chunk_walk(dname, family):
+    """The offline kernel and the chunk kernel each hold the recurrence: the offline spotting's single hit is, bit for bit in score and exactly in
+    span, the hit picked from the rows of the whole session pushed as ONE chunk, with Ee clamped to T - 1."""
+    lats, rows, _ = case(dname, family)
+    dur = DURS[dname]
+    # on the reference alone: the case is not vacuous
+    assert any(R.pick(E, Bs, np.minimum(Ee, T - 1))[0] == 1 for E, Bs, Ee in rows), "no pair has a hit"
+    assert any(np.any((E > NEG) & (Ee > T - 1)) for E, _, Ee in rows), "the clamp changes no row"
+    w = capi.TdtKwsChunkWalk(LS, dur)
+    try:
+        got = w.push(lats, rows=True)
+    finally:
+        w.close()
+    off = capi.tdt_kws(lats, dur, max_hits=1, min_score=None)
+    for p in range(len(LS)):
+        n, st, en, sc = R.pick(got["E"][p], got["Bs"][p], np.minimum(got["Ee"][p], T - 1))
+        what = f"{dname} {family} pair {p}"
+        assert off["n_hits"][p] == n, what
+        assert off["start"][p, 0] == st[0] and off["end"][p, 0] == en[0], f"{what}: [{off['start'][p, 0]}, {off['end'][p, 0]}] vs [{st[0]}, {en[0]}]"
+        assert bits(off["score"][p, 0]) == bits(sc[0]), what
+
+
 def test_reset_in_mid_stream_equals_a_fresh_walker():
     lats, rows, median = case("d01234", "ties")
     chunks = SR.chunks_of(T, CHUNKINGS["mix"])
