@@ -1314,6 +1314,36 @@ typedef struct pk_tdt_decide_diag {
     float *score_lab, *score_dur; int64_t score_rows;
 } pk_tdt_decide_diag;
 pk_status pk_diag_tdt_decide(const pk_tdt_decide_diag *a, int *form);
+/* ONE step of the TDT beam search's own kernels (kernels/tdt_beam.hip; kernels.hpp TdtBeamDev) on rows the CALLER gives, without a model: launch_tdt_beam_init
+ * when init != 0 (then step must be 0), one launch_tdt_beam_expand and one launch_tdt_beam_prune for `step`, then launch_tdt_beam_trace when trace != 0.  Nothing
+ * else is launched.  logits [R][V + D] (R = B W) are the raw fp32 rows the heads product would have written: the kernels' own log-softmax runs on them.
+ * Every array below is BOTH input and output, as pk_diag_tdt_decide's: copied up whole, copied back whole, so a caller carries a search from step to step.
+ *   the beam, both copies: valid, t, len, par, born, tok, score, hash [2][R], prefix [2][R][max_tokens]; with lm set also lmstate, lmv (the prefix's LM score) [2][R].
+ *       hash is opaque: carried, never made up -- a search begins with init = 1.
+ *   live, steps_done [B]; live_total [cap + 1] (zeros before the first step); bp [cap][R][4] (step < cap).
+ *   the step's intermediates, `rows` >= R rows each (the rows past R show stray stores): lab_id, lab_lp [rows][K + 1], dur_i, dur_lp [rows][Kd],
+ *       cand [rows][(K + 1) Kd]; with lm set also lab_ls, lab_lm [rows][K + 1].
+ *   the back-trace (trace != 0): ids, start, end, dur_idx, conf [B][N][max_tokens] (the search's host zero-fills them: the kernel writes filled slots only),
+ *       lens, out_score [B][N], ok [B]; with lm set also out_lm [B][N].
+ * lm (may be NULL) with alpha / beta selects the fused instantiations.
+ * Refused before anything is allocated or launched.  PK_ERR_UNSUPPORTED: W, K outside 1..16, Kd or D outside 1..8, N outside 1..W (what the search's entry
+ * points refuse).  PK_ERR_INVALID: Kd > D, K > V - 1, blank outside 0..V - 1, max_tokens < 1, T[b] < 1, step outside 0..cap - 1, rows < R, a missing array, what
+ * lm_fusion refuses about the model, and -- init == 0 -- carried state the kernels would index with: len outside 0..max_tokens, t < 0, steps_done outside 0..cap
+ * (a live clip: != step), an lmstate that is no state of the model, a back-pointer record of a step taken whose parent slot is outside 0..W - 1. */
+typedef struct pk_tdt_beam_step_diag {
+    int32_t B, W, K, Kd, N, V, D, blank, max_tokens;
+    int32_t durations[8];
+    int32_t step, init, trace, rows, cap;
+    const int32_t *T;
+    const float *logits;
+    int32_t *valid, *t, *len, *par, *born, *tok; float *score; uint64_t *hash; int32_t *prefix;
+    int32_t *live, *steps_done, *live_total, *bp;
+    int32_t *lab_id; float *lab_lp; int32_t *dur_i; float *dur_lp, *cand;
+    const pk_lm *lm; float alpha, beta;
+    int32_t *lmstate; float *lmv; int32_t *lab_ls; float *lab_lm;
+    int32_t *ids, *start, *end, *dur_idx; float *conf; int32_t *lens; float *out_score; int32_t *ok; float *out_lm;
+} pk_tdt_beam_step_diag;
+pk_status pk_diag_tdt_beam_step(const pk_tdt_beam_step_diag *a);
 /* The CTC greedy kernels alone (kernels/decode.hip): the row log-softmax + first-max argmax over logits [frames][ld] (n <= ld values per row), once without and
  * once with the log-prob rows (best_idx2 / best_lp2, then lp / best_idx / best_lp), then the collapse -- or, trie_off set, the boosted walk over lp.  B utterances
  * of T frames, or n_frames[b] frames each, packed.  All outputs are in/out as above: lp [lp_rows][n], best_* [lp_rows] (lp_rows >= frames), ids / start / end /

@@ -1215,6 +1215,79 @@ def diag_tdt_decide(sc, logits, hn, cn, st, pad_rows=3, guard=32):
     return out
 
 
+class PkTdtBeamStepDiag(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("B", "W", "K", "Kd", "N", "V", "D", "blank", "max_tokens")]
+                + [("durations", C.c_int32 * 8)] + [(k, C.c_int32) for k in ("step", "init", "trace", "rows", "cap")]
+                + [("T", i32p), ("logits", f32p)]
+                + [(k, i32p) for k in ("valid", "t", "len", "par", "born", "tok")] + [("score", f32p), ("hash", C.POINTER(C.c_uint64)), ("prefix", i32p)]
+                + [(k, i32p) for k in ("live", "steps_done", "live_total", "bp")]
+                + [("lab_id", i32p), ("lab_lp", f32p), ("dur_i", i32p), ("dur_lp", f32p), ("cand", f32p)]
+                + [("lm", C.c_void_p), ("alpha", C.c_float), ("beta", C.c_float), ("lmstate", i32p), ("lmv", f32p), ("lab_ls", i32p), ("lab_lm", f32p)]
+                + [("ids", i32p), ("start", i32p), ("end", i32p), ("dur_idx", i32p), ("conf", f32p), ("lens", i32p), ("out_score", f32p), ("ok", i32p),
+                   ("out_lm", f32p)])
+
+
+TDT_BEAM_STEP_SCALARS = ("B", "W", "K", "Kd", "N", "V", "D", "blank", "max_tokens")
+
+
+def tdt_beam_step_state(sc, T, cap, fused=False, pad_rows=3):
+    """The arrays of pk_diag_tdt_beam_step for a search that has not begun, every one filled with the pattern SKINNY_FILL32 except live_total (zeros: the
+    search's host zeroes it) and the back-trace's token arrays (zeros, likewise).  sc: the scalars B, W, K, Kd, N, V, D, blank, max_tokens and durations; T [B]
+    frames per clip; cap: the steps bp / live_total hold.  The intermediates have pad_rows rows more than the beam."""
+    B, W, K, Kd, N, MT = (int(sc[k]) for k in ("B", "W", "K", "Kd", "N", "max_tokens"))
+    R, rows = B * W, B * W + pad_rows
+    fill = lambda shape, dt: np.full(shape, SKINNY_FILL32, np.uint32).view(dt)
+    st = dict(T=_c(T, np.int32), cap=int(cap), rows=rows, fused=bool(fused))
+    for k in ("valid", "t", "len", "par", "born", "tok"):
+        st[k] = fill((2, R), np.int32)
+    st["score"], st["prefix"] = fill((2, R), np.float32), fill((2, R, MT), np.int32)
+    st["hash"] = np.full((2, R), (SKINNY_FILL32 << 32) | SKINNY_FILL32, np.uint64)
+    st["live"], st["steps_done"], st["live_total"], st["bp"] = fill(B, np.int32), fill(B, np.int32), np.zeros(cap + 1, np.int32), fill((cap, R, 4), np.int32)
+    st["lab_id"], st["lab_lp"] = fill((rows, K + 1), np.int32), fill((rows, K + 1), np.float32)
+    st["dur_i"], st["dur_lp"], st["cand"] = fill((rows, Kd), np.int32), fill((rows, Kd), np.float32), fill((rows, (K + 1) * Kd), np.float32)
+    if fused:
+        st["lmstate"], st["lmv"] = fill((2, R), np.int32), fill((2, R), np.float32)
+        st["lab_ls"], st["lab_lm"] = fill((rows, K + 1), np.int32), fill((rows, K + 1), np.float32)
+    for k in ("ids", "start", "end", "dur_idx"):
+        st[k] = np.zeros((B, N, MT), np.int32)
+    st["conf"] = np.zeros((B, N, MT), np.float32)
+    st["lens"], st["out_score"], st["ok"], st["out_lm"] = fill((B, N), np.int32), fill((B, N), np.float32), fill(B, np.int32), fill((B, N), np.float32)
+    return st
+
+
+TDT_BEAM_STEP_SCRATCH = ("lab_id", "lab_lp", "dur_i", "dur_lp", "cand", "lab_ls", "lab_lm")
+
+
+def diag_tdt_beam_step(sc, st, logits, step, init=False, trace=False, lm=None, alpha=0.0, beta=0.0):
+    """pk_diag_tdt_beam_step (include/parakeet_amd.h) on the arrays of tdt_beam_step_state, CHANGED IN PLACE: (init,) expand + prune of `step` on the rows
+    logits [B W][V + D], (the back-trace).  The step's intermediates are refilled with the pattern before the call, so what comes back is this step's."""
+    logits = _c(logits)
+    d = PkTdtBeamStepDiag()
+    for k in TDT_BEAM_STEP_SCALARS:
+        setattr(d, k, int(sc[k]))
+    for i, v in enumerate(list(sc["durations"])[:8]):
+        d.durations[i] = int(v)
+    R = d.B * d.W
+    assert logits.shape == (R, d.V + d.D), (logits.shape, R, d.V + d.D)
+    d.step, d.init, d.trace, d.rows, d.cap = int(step), int(bool(init)), int(bool(trace)), int(st["rows"]), int(st["cap"])
+    for k in TDT_BEAM_STEP_SCRATCH:
+        if k in st:
+            st[k].view(np.uint32)[...] = SKINNY_FILL32
+    d.T, d.logits = _i(st["T"]), _f(logits)
+    for k, ty in PkTdtBeamStepDiag._fields_:                       # every in / out array the state holds
+        a = st.get(k)
+        if k in ("T", "logits", "lm") or not isinstance(a, np.ndarray) or (lm is None and k == "out_lm"):
+            continue
+        assert a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"], k
+        setattr(d, k, a.ctypes.data_as(ty))
+    if lm is not None:
+        d.lm, d.alpha, d.beta = lm._h, float(alpha), float(beta)
+    L = lib()
+    L.pk_diag_tdt_beam_step.argtypes = [C.POINTER(PkTdtBeamStepDiag)]
+    check(L.pk_diag_tdt_beam_step(C.byref(d)))
+    return st
+
+
 def diag_ctc_greedy(logits, n, blank, B=None, T=0, n_frames=None, pitch=None, trie=None, pad_rows=3):
     """pk_diag_ctc_greedy: logits [frames][ld] (the first n columns of a row are its values).  Uniform batch: B x T frames; ragged: n_frames [B], packed.
     trie = (off, tok, node, boost): the boosted kernel instead of the collapse.  Returns the whole pattern-filled buffers: lp [frames + pad][n], best_idx /

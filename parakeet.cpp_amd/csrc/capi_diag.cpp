@@ -468,6 +468,125 @@ pk_status pk_diag_tdt_decide(const pk_tdt_decide_diag *d, int *form) {
     });
 }
 
+pk_status pk_diag_tdt_beam_step(const pk_tdt_beam_step_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const int B = d->B, W = d->W, K = d->K, Kd = d->Kd, N = d->N, V = d->V, D = d->D, MT = d->max_tokens, s = d->step, cap = d->cap;
+        const bool fused = d->lm != nullptr, init = d->init != 0, trace = d->trace != 0;
+        // what the search's entry points refuse (tdt_beam.cpp), then what launch_tdt_beam_prune would abort on
+        if (W < 1 || W > kTdtBeamMaxWidth) fail(PK_ERR_UNSUPPORTED, "TDT beam step: beam_width %d outside 1..%d", W, kTdtBeamMaxWidth);
+        if (K < 1 || K > kTdtBeamMaxLabels) fail(PK_ERR_UNSUPPORTED, "TDT beam step: label_prune %d outside 1..%d", K, kTdtBeamMaxLabels);
+        if (Kd < 1 || Kd > kTdtBeamMaxDurs) fail(PK_ERR_UNSUPPORTED, "TDT beam step: duration_prune %d outside 1..%d", Kd, kTdtBeamMaxDurs);
+        if (D < 1 || D > 8) fail(PK_ERR_UNSUPPORTED, "TDT beam step: %d durations, the kernel is built for 1 to 8", D);
+        if (N < 1 || N > W) fail(PK_ERR_UNSUPPORTED, "TDT beam step: n_best %d outside 1..beam_width", N);
+        need(Kd <= D, "duration_prune <= D");
+        need(V >= 2 && V <= (1 << 20) && K <= V - 1, "label_prune <= V - 1 (V <= 2^20)");
+        need(d->blank >= 0 && d->blank < V, "blank outside 0..V - 1");
+        need(MT >= 1 && MT <= (1 << 20), "max_tokens (1..2^20)");
+        need(B >= 1 && (int64_t)B * W <= (1 << 16), "B (B W <= 2^16)");
+        const int R = B * W;
+        need(cap >= 1 && cap <= (1 << 20) && s >= 0 && s < cap && d->rows >= R && d->rows <= R + 64, "cap / step (0..cap - 1) / rows (R..R + 64)");
+        need((int64_t)R * MT <= (1 << 24) && (int64_t)cap * R <= (1 << 24) && (int64_t)R * (V + D) <= (1 << 26), "R max_tokens, cap R <= 2^24; R (V + D) <= 2^26");
+        need(!init || s == 0, "init: the search begins at step 0");
+        need(d->T && d->logits, "T/logits");
+        need(d->valid && d->t && d->len && d->par && d->born && d->tok && d->score && d->hash && d->prefix, "beam arrays");
+        need(d->live && d->steps_done && d->live_total && d->bp, "live/steps_done/live_total/bp");
+        need(d->lab_id && d->lab_lp && d->dur_i && d->dur_lp && d->cand, "lab_id/lab_lp/dur_i/dur_lp/cand");
+        need(!fused || (d->lmstate && d->lmv && d->lab_ls && d->lab_lm), "lm: lmstate/lmv/lab_ls/lab_lm");
+        need(!trace || (d->ids && d->start && d->end && d->dur_idx && d->conf && d->lens && d->out_score && d->ok && (!fused || d->out_lm)), "trace: output arrays");
+        for (int b = 0; b < B; ++b) need(d->T[b] >= 1, "T[b] must be positive");
+        pk_lm_options lo{d->alpha, d->beta};
+        if (fused) lm_fusion_checks(d->lm, &lo, V, d->blank);
+        if (!init) {                                                // carried state the kernels index with
+            for (int i = 0; i < 2 * R; ++i) {
+                need(d->len[i] >= 0 && d->len[i] <= MT && d->t[i] >= 0, "carried beam: len outside 0..max_tokens or t < 0");
+                need(!fused || (d->lmstate[i] >= 0 && d->lmstate[i] < lm_num_states(d->lm)), "carried beam: lmstate is no state of the model");
+            }
+            for (int b = 0; b < B; ++b) {
+                const int sd = d->steps_done[b];
+                need(sd >= 0 && sd <= cap && (!d->live[b] || sd == s), "steps_done outside 0..cap, or a live clip whose steps_done is not step");
+                for (int st = 0; st < sd; ++st)
+                    for (int w = 0; w < W; ++w) {
+                        const int x = d->bp[((size_t)st * R + (size_t)b * W + w) * 4];
+                        need(x >= 0 && x < W, "bp: the parent slot of a step taken is outside 0..W - 1");
+                    }
+            }
+        }
+        need_device();
+        const size_t nR = (size_t)R, rows = (size_t)d->rows, C_ = (size_t)(K + 1) * Kd, hy = (size_t)B * N, tok = hy * MT;
+        DevBuf Tb, lg, ints, score, hash, prefix, ctl, bp, lab_id, lab_lp, dur_i, dur_lp, cand, lmslot, lmlab, out;
+        up(Tb, d->T, (size_t)B * 4);
+        up(lg, d->logits, nR * (size_t)(V + D) * 4);
+        ints.reserve(12 * nR * 4);
+        int32_t *const beam_ints[6] = {d->valid, d->t, d->len, d->par, d->born, d->tok};
+        for (int k = 0; k < 6; ++k) PK_HIP(hipMemcpy(ints.as<int>() + 2 * nR * k, beam_ints[k], 2 * nR * 4, hipMemcpyHostToDevice));
+        up(score, d->score, 2 * nR * 4); up(hash, d->hash, 2 * nR * 8); up(prefix, d->prefix, 2 * nR * MT * 4);
+        ctl.reserve((2 * (size_t)B + cap + 1) * 4);
+        PK_HIP(hipMemcpy(ctl.as<int>(), d->live, (size_t)B * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(ctl.as<int>() + B, d->steps_done, (size_t)B * 4, hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(ctl.as<int>() + 2 * B, d->live_total, ((size_t)cap + 1) * 4, hipMemcpyHostToDevice));
+        up(bp, d->bp, (size_t)cap * nR * 16);
+        up(lab_id, d->lab_id, rows * (K + 1) * 4); up(lab_lp, d->lab_lp, rows * (K + 1) * 4);
+        up(dur_i, d->dur_i, rows * Kd * 4); up(dur_lp, d->dur_lp, rows * Kd * 4); up(cand, d->cand, rows * C_ * 4);
+        TdtBeamDev a{};
+        a.B = B; a.W = W; a.K = K; a.Kd = Kd; a.N = N; a.V = V; a.D = D; a.blank = d->blank; a.max_tokens = MT;
+        for (int i = 0; i < 8; ++i) a.durations[i] = i < D ? d->durations[i] : 0;
+        a.T = Tb.as<int>(); a.row0 = nullptr;
+        int *iv = ints.as<int>();
+        a.valid = iv; a.t = iv + 2 * nR; a.len = iv + 4 * nR; a.par = iv + 6 * nR; a.born = iv + 8 * nR; a.tok = iv + 10 * nR;
+        a.score = score.as<float>(); a.hash = hash.as<unsigned long long>(); a.prefix = prefix.as<int>();
+        a.lab_id = lab_id.as<int>(); a.lab_lp = lab_lp.as<float>(); a.dur_i = dur_i.as<int>(); a.dur_lp = dur_lp.as<float>(); a.cand = cand.as<float>();
+        a.bp = bp.as<int4>();
+        a.live = ctl.as<int>(); a.steps_done = a.live + B; a.live_total = a.live + 2 * (size_t)B;
+        if (fused) {
+            lmslot.reserve(4 * nR * 4); lmlab.reserve(2 * rows * (K + 1) * 4);
+            a.lmstate = lmslot.as<int>(); a.lm = reinterpret_cast<float *>(a.lmstate + 2 * nR);
+            a.lab_ls = lmlab.as<int>(); a.lab_lm = reinterpret_cast<float *>(a.lab_ls + rows * (K + 1));
+            PK_HIP(hipMemcpy(a.lmstate, d->lmstate, 2 * nR * 4, hipMemcpyHostToDevice)); PK_HIP(hipMemcpy(a.lm, d->lmv, 2 * nR * 4, hipMemcpyHostToDevice));
+            PK_HIP(hipMemcpy(a.lab_ls, d->lab_ls, rows * (K + 1) * 4, hipMemcpyHostToDevice));
+            PK_HIP(hipMemcpy(a.lab_lm, d->lab_lm, rows * (K + 1) * 4, hipMemcpyHostToDevice));
+            a.ngram = lm_device_view(d->lm, &lo);
+        }
+        TdtBeamOut o{};
+        if (trace) {
+            out.reserve((5 * tok + 3 * hy + B) * 4);
+            int *p = out.as<int>();
+            o.ids = p; o.start = p + tok; o.end = p + 2 * tok; o.dur_idx = p + 3 * tok; o.conf = reinterpret_cast<float *>(p + 4 * tok);
+            o.lens = p + 5 * tok; o.score = reinterpret_cast<float *>(p + 5 * tok + hy); o.ok = p + 5 * tok + 2 * hy;
+            if (fused) o.lm_score = reinterpret_cast<float *>(o.ok + B);
+            const void *const src[9] = {d->ids, d->start, d->end, d->dur_idx, d->conf, d->lens, d->out_score, d->ok, d->out_lm};
+            void *const dst[9] = {o.ids, o.start, o.end, o.dur_idx, o.conf, o.lens, o.score, o.ok, o.lm_score};
+            const size_t n[9] = {tok, tok, tok, tok, tok, hy, hy, (size_t)B, hy};
+            for (int k = 0; k < (fused ? 9 : 8); ++k) PK_HIP(hipMemcpy(dst[k], src[k], n[k] * 4, hipMemcpyHostToDevice));
+        }
+        if (init) launch_tdt_beam_init(a, nullptr);
+        launch_tdt_beam_expand(a, s, lg.as<float>(), nullptr);
+        launch_tdt_beam_prune(a, s, nullptr);
+        if (trace) launch_tdt_beam_trace(a, o, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        for (int k = 0; k < 6; ++k) PK_HIP(hipMemcpy(beam_ints[k], ints.as<int>() + 2 * nR * k, 2 * nR * 4, hipMemcpyDeviceToHost));
+        down(d->score, score, 2 * nR * 4); down(d->hash, hash, 2 * nR * 8); down(d->prefix, prefix, 2 * nR * MT * 4);
+        PK_HIP(hipMemcpy(d->live, ctl.as<int>(), (size_t)B * 4, hipMemcpyDeviceToHost));
+        PK_HIP(hipMemcpy(d->steps_done, ctl.as<int>() + B, (size_t)B * 4, hipMemcpyDeviceToHost));
+        PK_HIP(hipMemcpy(d->live_total, ctl.as<int>() + 2 * B, ((size_t)cap + 1) * 4, hipMemcpyDeviceToHost));
+        down(d->bp, bp, (size_t)cap * nR * 16);
+        down(d->lab_id, lab_id, rows * (K + 1) * 4); down(d->lab_lp, lab_lp, rows * (K + 1) * 4);
+        down(d->dur_i, dur_i, rows * Kd * 4); down(d->dur_lp, dur_lp, rows * Kd * 4); down(d->cand, cand, rows * C_ * 4);
+        if (fused) {
+            PK_HIP(hipMemcpy(d->lmstate, a.lmstate, 2 * nR * 4, hipMemcpyDeviceToHost)); PK_HIP(hipMemcpy(d->lmv, a.lm, 2 * nR * 4, hipMemcpyDeviceToHost));
+            PK_HIP(hipMemcpy(d->lab_ls, a.lab_ls, rows * (K + 1) * 4, hipMemcpyDeviceToHost));
+            PK_HIP(hipMemcpy(d->lab_lm, a.lab_lm, rows * (K + 1) * 4, hipMemcpyDeviceToHost));
+        }
+        if (trace) {
+            void *const dst[9] = {d->ids, d->start, d->end, d->dur_idx, d->conf, d->lens, d->out_score, d->ok, d->out_lm};
+            const void *const src[9] = {o.ids, o.start, o.end, o.dur_idx, o.conf, o.lens, o.score, o.ok, o.lm_score};
+            const size_t n[9] = {tok, tok, tok, tok, tok, hy, hy, (size_t)B, hy};
+            for (int k = 0; k < (fused ? 9 : 8); ++k) PK_HIP(hipMemcpy(dst[k], src[k], n[k] * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
 pk_status pk_diag_ctc_greedy(const pk_ctc_greedy_diag *d) {
     return guard([&] {
         need(d, "args");

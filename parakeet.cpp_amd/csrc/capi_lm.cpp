@@ -57,6 +57,8 @@ LmDev pk::lm_device_view(const pk_lm *lm, const pk_lm_options *opt) {
     return d;
 }
 
+int pk::lm_num_states(const pk_lm *lm) { return (int)lm->lm.state.size(); }
+
 void pk_lm_options_default(pk_lm_options *out) {
     if (!out) return;
     out->alpha = 0.5f; out->beta = 0.0f;

@@ -65,6 +65,7 @@ void beam_model_checks(Model &m, const pk_beam_options &o, int &V, int &blank);
 // first use there) with the weights of opt (NULL: the defaults).
 void lm_fusion_checks(const pk_lm *lm, const pk_lm_options *opt, int V, int blank);
 LmDev lm_device_view(const pk_lm *lm, const pk_lm_options *opt);
+int lm_num_states(const pk_lm *lm);         // the states of the automaton: what a carried LM state may index (capi_diag.cpp)
 
 // capi_batch.cpp: the one-call transcription of some clips of a call through the model's pipeline, used by every rank of a pk_group too.
 // ResultStore owns everything a pk_result array points into; only capi_batch.cpp sees inside it.

@@ -26,10 +26,11 @@ F = np.float32
 NEG = R.NEG
 
 
-def step(beam, joint, lm, alpha, beta, T, blank, durations, W, K, Kd, max_tokens):
-    """One step: beam = [(prefix, t, score, toks, hist, lm)] -> the new beam (at most W entries)."""
+def step(beam, joint, lm, alpha, beta, T, blank, durations, W, K, Kd, max_tokens, info=None):
+    """One step: beam = [(prefix, t, score, toks, hist, lm)] -> the new beam (at most W entries).  info: as tdt_beam_ref.step's."""
     pool = [h for h in beam if h[1] >= T]
-    for prefix, t, score, toks, hist, lmv in beam:
+    src = [w for w, h in enumerate(beam) if h[1] >= T]
+    for w, (prefix, t, score, toks, hist, lmv) in enumerate(beam):
         if t >= T:
             continue
         logp, dl = joint(t, prefix)
@@ -48,6 +49,7 @@ def step(beam, joint, lm, alpha, beta, T, blank, durations, W, K, Kd, max_tokens
                     pool.append((prefix, min(t + max(int(durations[d]), 1), T), s, toks, hist, lmv))
                 else:
                     pool.append((prefix + (i,), min(t + int(durations[d]), T), s, toks + ((t, d, x),), hist + (i,), lm2))
+                src.append(w)
     with np.errstate(all="ignore"):
         f = [F(h[2] + h[5]) for h in pool]
     state = {}                                                      # (prefix, t) -> pool position of the entry that stays
@@ -56,6 +58,7 @@ def step(beam, joint, lm, alpha, beta, T, blank, durations, W, K, Kd, max_tokens
         if key not in state or f[pos] > f[state[key]]:
             state[key] = pos
     kept = sorted(state.values(), key=lambda pos: (-float(f[pos]), pos))
+    R._report(info, pool, src, state, kept[:W])
     return [pool[pos] for pos in kept[:W]]
 
 

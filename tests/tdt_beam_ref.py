@@ -40,10 +40,13 @@ def expand_row(logp, dl, blank, K, Kd):
     return [(i, F(logp[i])) for i in labs], [(i, F(dl[i])) for i in durs]
 
 
-def step(beam, joint, T, blank, durations, W, K, Kd, max_tokens):
-    """One step: beam = [(prefix, t, score, toks)] -> the new beam (at most W entries)."""
+def step(beam, joint, T, blank, durations, W, K, Kd, max_tokens, info=None):
+    """One step: beam = [(prefix, t, score, toks)] -> the new beam (at most W entries).  info (a dict) receives what the step decided beside
+    the beam: "parent", the old beam's slot every new entry came from, and "merged", one (tokens, t, the entry that stays came from another
+    slot) per pool entry that left as the duplicate of a state."""
     pool = [h for h in beam if h[1] >= T]
-    for prefix, t, score, toks in beam:
+    src = [w for w, h in enumerate(beam) if h[1] >= T]             # the beam slot every pool entry came from
+    for w, (prefix, t, score, toks) in enumerate(beam):
         if t >= T:
             continue
         logp, dl = joint(t, prefix)
@@ -59,13 +62,21 @@ def step(beam, joint, T, blank, durations, W, K, Kd, max_tokens):
                 else:
                     t2, p2, k2 = t + int(durations[d]), prefix + (i,), toks + ((t, d, x),)
                 pool.append((p2, min(t2, T), s, k2))
+                src.append(w)
     state = {}                                                      # (prefix, t) -> pool position of the entry that stays
     for pos, h in enumerate(pool):
         key = (h[0], h[1])
         if key not in state or h[2] > pool[state[key]][2]:
             state[key] = pos
     kept = sorted(state.values(), key=lambda pos: (-float(pool[pos][2]), pos))
+    _report(info, pool, src, state, kept[:W])
     return [pool[pos] for pos in kept[:W]]
+
+
+def _report(info, pool, src, state, kept):
+    if info is not None:
+        info["parent"] = [src[pos] for pos in kept]
+        info["merged"] = [(len(h[0]), h[1], src[pos] != src[state[(h[0], h[1])]]) for pos, h in enumerate(pool) if state[(h[0], h[1])] != pos]
 
 
 def search(joint, T, blank, durations, W, K, Kd, N, max_tokens, trace=None):

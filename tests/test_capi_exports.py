@@ -79,6 +79,10 @@ def test_no_gpu_is_a_loud_error(tmp_path):
     with pytest.raises(capi.PkError) as e:
         capi.diag_ctc_greedy(np.zeros((4, 9), np.float32), 9, 8, B=1, T=4)
     assert e.value.code == -4
+    sc = dict(B=1, W=2, K=2, Kd=1, N=1, V=5, D=2, blank=4, max_tokens=3, durations=[0, 1])       # the beam step diagnostics: valid arguments, no device
+    with pytest.raises(capi.PkError) as e:
+        capi.diag_tdt_beam_step(sc, capi.tdt_beam_step_state(sc, [2], 5), np.zeros((2, 7), np.float32), 0, init=True, trace=True)
+    assert e.value.code == -4
     with pytest.raises(capi.PkError) as e:             # the small-M GEMM diagnostics: valid arguments, no device
         capi.diag_gemm_smallm(np.zeros((4, 64), np.float32), np.zeros((16, 64), np.float32), w_sig=True, a_sigma=True)
     assert e.value.code == -4
