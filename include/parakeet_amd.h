@@ -1577,6 +1577,72 @@ int pk_diag_gemm_smallm_bf16_forms(int32_t *out, int cap);
 pk_status pk_diag_gemm_smallm_bf16_form(pk_gemm_smallm_bf16_diag *a);
 pk_status pk_diag_tile_copy_bf16(const float *src, int64_t rows, int K, int64_t ld, uint16_t *dst);
 
+/* ---- neural LM rescoring: n-best reranking with a Transformer LM after beam search (the reference's roadmap, README.md "Neural LM rescoring") ------
+ * A causal Transformer LM over the acoustic model's own token ids plus BOS and EOS: token and position embeddings, the blocks of
+ * pk_transformer_* under a causal mask (ReLU feed-forwards, pre- or post-norm), an output projection.  fp32 throughout.  DESIGN.md section 5.5.11.
+ * Tensors under <prefix>: tok_emb_.weight [Vlm][d], pos_emb_.weight [max_positions][d] (a sinusoidal table is stored as a tensor by whoever
+ * converts the model), emb_norm_.{weight,bias} [d] (optional), the layers_.<i>.* / final_norm_.* tree of pk_transformer_load,
+ * lm_head_.weight [Vlm][d] and lm_head_.bias [Vlm] (untied head; the bias is optional).
+ *
+ * The scoring rule for a token string ids[0..n):
+ *   inputs     x_0 = bos_id, x_i = ids[i-1].  With an end term (eos_id >= 0) there are P = n + 1 positions, otherwise P = n.
+ *   embedding  h_i = tok_emb[x_i] + pos_emb[i] (one fp32 add), then emb_norm_ if present.
+ *   blocks     TransformerEncoder's, with attention softmax(scale q_i . k_j over j <= i) V, scale = 1 / sqrt(real head dim); then final_norm_ if present.
+ *   head       logit_i[c] = h_i . W[c] (+ b[c]), a k-ordered fp32 fma chain from zero; lp_i = logit_i[target_i] - logsumexp_c logit_i[c], target_i = ids[i]
+ *              for i < n and eos_id for i = n.
+ *   total      the left-to-right fp32 sum of lp_i.  The empty string scores 0 without an end term and lp(eos | bos) with one.
+ *   too long   a string with P > max_positions is not scored: ok = 0, total = -inf.
+ *   bad ids    an id < 0, >= Vlm, or equal to bos_id: PK_ERR_INVALID for the call.
+ * No padded position is computed: the strings of a call are packed like the clips of a ragged encoder batch, and a string's bits do not depend
+ * on what it is packed with.  A call whose scratch would pass 1 GiB is cut into groups of whole strings on the host. */
+typedef struct pk_nlm_config {
+    int32_t vocab_size;        /* Vlm: rows of the embedding and of the head */
+    int32_t max_positions;     /* rows of the position table; <= 512 */
+    pk_transformer_config transformer;   /* hidden, layers, heads, ffn, pre_ln, has_final_norm, eps */
+    int32_t has_emb_norm;      /* LayerNorm after token + position embedding */
+    int32_t tied_head;         /* 1: the head is tok_emb_.weight; 0: lm_head_.weight (+ optional lm_head_.bias) */
+    int32_t bos_id;            /* fed at position 0 */
+    int32_t eos_id;            /* < 0: no end-of-string term */
+} pk_nlm_config;
+typedef struct pk_nlm pk_nlm;
+/* Fills what the tensor shapes determine: vocab_size, hidden_size, num_layers, ffn_intermediate, max_positions, has_emb_norm, has_final_norm,
+ * tied_head.  The caller's num_heads, pre_ln, bos_id, eos_id and layer_norm_eps stay as given.  Host only. */
+pk_status pk_nlm_config_infer(const char *safetensors_path, const char *prefix, pk_nlm_config *io);
+/* Refused before anything is allocated: what pk_transformer_load refuses about the configuration, max_positions > 512 (PK_ERR_UNSUPPORTED), bos_id
+ * outside [0, Vlm) or eos_id >= Vlm or eos_id == bos_id (PK_ERR_INVALID), a missing or mis-shaped tensor (PK_ERR_WEIGHTS). */
+pk_status pk_nlm_load(const char *safetensors_path, const char *prefix, const pk_nlm_config *cfg, int device, pk_nlm **out);
+void pk_nlm_free(pk_nlm *nlm);
+/* ids packed, id_offsets[n_strings + 1].  total / ok [n_strings].  token_logp (optional): string b's lp_i at token_logp[id_offsets[b] + b + i],
+ * i.e. packed by id_offsets plus one slot per string for the end term (0 where the model has none); the slots of a string that is not scored read 0. */
+pk_status pk_nlm_score(pk_nlm *nlm, const int32_t *ids, const int32_t *id_offsets, int n_strings, float *total, int32_t *ok, float *token_logp);
+/* Stage timers (tools/bench_nlm_rescore.py): pk_nlm_score run reps + 1 times, hipEvents on the handle's stream around the stages of every group,
+ * summed over the groups, medians of the last reps passes: ms[0] = embedding (+ emb_norm_), ms[1] = blocks (+ final_norm_), ms[2] = head. */
+pk_status pk_nlm_score_timed(pk_nlm *nlm, const int32_t *ids, const int32_t *id_offsets, int n_strings, int reps, float ms[3]);
+/* Re-ranking of the lists of pk_transcribe_pcm_nbest, _nbest_lm, _nbest_tdt or _nbest_tdt_lm, in place: every hypothesis is scored by pk_nlm_score,
+ * combined = am + ((alpha * nlm) + (beta * len)) in four separately rounded fp32 operations (am = the list's score[j], len = n_tokens), and each
+ * clip's list is re-ordered stably, descending, ties keeping the incoming order; a hypothesis that is not scored (ok = 0), or whose combined is
+ * NaN, goes after every scored one with combined = -inf.  score[j] becomes combined; hyp[j] (text, ids, words, timestamps) moves with its slot,
+ * unchanged.  alpha == 0 and beta == 0 leaves every list bit for bit as it was.  am_score / nlm_score (optional): [n_clips][N], N = the n_best
+ * of the search that made the lists, in the returned order, -inf in the slots past n_hyp.  opt == NULL: alpha 0.5, beta 0 (a choice, not a
+ * measurement).  An id the LM refuses fails the call before any list is touched. */
+typedef struct pk_nlm_rescore_options { float alpha, beta; } pk_nlm_rescore_options;
+pk_status pk_nbest_rescore_nlm(pk_nbest *results, int n_clips, pk_nlm *nlm, const pk_nlm_rescore_options *opt, float *am_score, float *nlm_score);
+/* Diagnostics.  pk_diag_nlm_order: the ordering rule above on the N slots of one list, host arithmetic only (order[j] = the slot at position j,
+ * combined[] by slot).  pk_diag_nlm_set_scratch_cap: the scratch cap of pk_nlm_score's grouping in bytes (0: back to 1 GiB); a group always holds
+ * at least one string.  pk_diag_nlm_groups (may be called after a pk_nlm_score): the number of groups the last call ran. */
+pk_status pk_diag_nlm_order(const float *am, const float *nlm, const int32_t *lens, const int32_t *ok, int N, float alpha, float beta,
+                            int32_t *order, float *combined);
+pk_status pk_diag_nlm_set_scratch_cap(pk_nlm *nlm, uint64_t bytes);
+int pk_diag_nlm_groups(const pk_nlm *nlm);
+/* The causal attention kernel alone (kernels/attention.hip, CAUSAL instantiation) on B packed sequences of lens[b] <= 512 positions:
+ * ctx_i = softmax_j<=i(scale q_i . k_j) V, no position term.  qkv [rows][3 d] natural columns (q | k | v), hd = d / n_heads in {32, 64, 96, 128}
+ * (a narrower head is zero-padded by the caller, as TransformerEncoder does; scale is the caller's).  ctx receives
+ * [rows + PK_DIAG_ATTENTION_GUARD_ROWS][d] floats; the device buffer is filled with 0x7FC5A5A5 before the launch. */
+pk_status pk_diag_causal_attention(int B, const int32_t *lens, int d, int n_heads, float scale, const float *qkv, float *ctx);
+/* The head kernel alone: lp[r] = logit_r[targets[r]] - logsumexp_c logit_r[c], logit_r[c] = h_r . W_c (+ bias[c]).  h [rows][d], W [V][d], bias [V]
+ * or NULL, targets [rows] in [0, V); d a multiple of 32, V >= 1.  lp receives rows + PK_DIAG_ATTENTION_GUARD_ROWS floats, 0x7FC5A5A5-filled before the launch. */
+pk_status pk_diag_nlm_head_logp(const float *h, const float *W, const float *bias, const int32_t *targets, int64_t rows, int V, int d, float *lp);
+
 #ifdef __cplusplus
 }
 #endif

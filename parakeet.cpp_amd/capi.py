@@ -110,6 +110,15 @@ class PkLmOptions(C.Structure):
     _fields_ = [("alpha", C.c_float), ("beta", C.c_float)]
 
 
+class PkNlmConfig(C.Structure):
+    _fields_ = [("vocab_size", C.c_int32), ("max_positions", C.c_int32), ("transformer", PkTransformerConfig), ("has_emb_norm", C.c_int32),
+                ("tied_head", C.c_int32), ("bos_id", C.c_int32), ("eos_id", C.c_int32)]
+
+
+class PkNlmRescoreOptions(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("beta", C.c_float)]
+
+
 def to_pk_config(cfg: ModelConfig) -> PkConfig:
     c = PkConfig()
     c.mel_bins, c.subsampling_channels, c.hidden_size = cfg.mel_bins, cfg.subsampling_channels, cfg.hidden_size
@@ -226,6 +235,17 @@ _LATE_SIGNATURES = {
     "pk_ctc_beam_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, C.POINTER(PkBeamOptions), C.c_int, f32p],
     "pk_transcribe_pcm_nbest": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(PkBeamOptions), C.POINTER(C.POINTER(PkNbest))],
     "pk_nbest_free": [C.POINTER(PkNbest), C.c_int],
+    "pk_nlm_config_infer": [C.c_char_p, C.c_char_p, C.POINTER(PkNlmConfig)],
+    "pk_nlm_load": [C.c_char_p, C.c_char_p, C.POINTER(PkNlmConfig), C.c_int, C.POINTER(C.c_void_p)],
+    "pk_nlm_free": [C.c_void_p],
+    "pk_nlm_score": [C.c_void_p, i32p, i32p, C.c_int, f32p, i32p, f32p],
+    "pk_nlm_score_timed": [C.c_void_p, i32p, i32p, C.c_int, C.c_int, f32p],
+    "pk_nbest_rescore_nlm": [C.POINTER(PkNbest), C.c_int, C.c_void_p, C.POINTER(PkNlmRescoreOptions), f32p, f32p],
+    "pk_diag_nlm_order": [f32p, f32p, i32p, i32p, C.c_int, C.c_float, C.c_float, i32p, f32p],
+    "pk_diag_nlm_set_scratch_cap": [C.c_void_p, C.c_uint64],
+    "pk_diag_nlm_groups": [C.c_void_p],
+    "pk_diag_causal_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_float, f32p, f32p],
+    "pk_diag_nlm_head_logp": [f32p, f32p, f32p, i32p, C.c_int64, C.c_int, C.c_int, f32p],
     "pk_lm_load": [C.c_char_p, C.POINTER(C.c_void_p)],
     "pk_lm_load_buffer": [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)],
     "pk_lm_free": [C.c_void_p],
@@ -2551,6 +2571,22 @@ def _nbest_list(res, n, timestamps, extra=None):
         lib().pk_nbest_free(res, n)
 
 
+def _nlm_rerank(res, n, N, nlm, alpha, beta):
+    """pk_nbest_rescore_nlm on a pk_nbest array in place (nlm None: nothing) -> the extra per-hypothesis entries for _nbest_list.  The array is freed
+    here when the call fails."""
+    if nlm is None:
+        return None
+    am, ns = np.zeros((n, max(1, N)), np.float32), np.zeros((n, max(1, N)), np.float32)
+    o = nlm_rescore_options(alpha, beta)
+    st = lib().pk_nbest_rescore_nlm(res, n, nlm._h, C.byref(o), _f(am), _f(ns))
+    if st != 0:
+        try:
+            check(st)
+        finally:
+            lib().pk_nbest_free(res, n)
+    return dict(am_score=am, nlm_score=ns)
+
+
 def _transcript_args(texts, ids, n):
     """the (texts, ids, id_offsets) arguments of an entry point that takes n transcripts as texts or as token id sequences"""
     assert (texts is None) != (ids is None), "texts or ids"
@@ -2903,15 +2939,18 @@ class Model:
         return int(lib().pk_tdt_beam_last_steps(self._h))
 
     def transcribe_nbest_tdt(self, clips, beam_width=None, label_prune=None, duration_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None,
-                             lm_beta=None):
+                             lm_beta=None, nlm=None, nlm_alpha=None, nlm_beta=None):
         """pk_transcribe_pcm_nbest_tdt: per clip a list of hypotheses through the TDT head, best first: dicts as transcribe_nbest returns them.
-        lm (an Lm): pk_transcribe_pcm_nbest_tdt_lm; lists in fused order, every dict gains "lm_score"."""
+        lm (an Lm): pk_transcribe_pcm_nbest_tdt_lm; lists in fused order, every dict gains "lm_score".
+        nlm (a NeuralLm): the lists re-ranked by pk_nbest_rescore_nlm before they are returned; every dict gains "am_score" and "nlm_score"."""
+        if lm is not None and nlm is not None:
+            raise ValueError("lm= and nlm= together: run the fused search, then NeuralLm.rescore on the returned lists (lm_score is in search order)")
         pcm, off, n = _clips(clips)
         o = tdt_beam_options(beam_width, label_prune, duration_prune, n_best)
         res = C.POINTER(PkNbest)()
         if lm is None:
             check(lib().pk_transcribe_pcm_nbest_tdt(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res)))
-            return _nbest_list(res, n, timestamps)
+            return _nbest_list(res, n, timestamps, _nlm_rerank(res, n, o.n_best, nlm, nlm_alpha, nlm_beta))
         lo = lm_options(lm_alpha, lm_beta)
         lms = np.zeros((n, max(1, o.n_best)), np.float32)
         check(lib().pk_transcribe_pcm_nbest_tdt_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), int(timestamps), C.byref(res), lm._h,
@@ -3128,15 +3167,19 @@ class Model:
             check(lib().pk_ctc_beam_decode_lm_timed(*head, lm._h, C.byref(lo)))
         return float(ms[0]), float(ms[1])
 
-    def transcribe_nbest(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None, lm_beta=None):
+    def transcribe_nbest(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False, lm=None, lm_alpha=None, lm_beta=None, nlm=None,
+                         nlm_alpha=None, nlm_beta=None):
         """pk_transcribe_pcm_nbest: per clip a list of hypotheses, best first: dicts as transcribe_pcm returns them + "score".
-        lm (an Lm): pk_transcribe_pcm_nbest_lm; lists in fused order, every dict gains "lm_score"."""
+        lm (an Lm): pk_transcribe_pcm_nbest_lm; lists in fused order, every dict gains "lm_score".
+        nlm (a NeuralLm): the lists re-ranked by pk_nbest_rescore_nlm before they are returned; every dict gains "am_score" and "nlm_score"."""
+        if lm is not None and nlm is not None:
+            raise ValueError("lm= and nlm= together: run the fused search, then NeuralLm.rescore on the returned lists (lm_score is in search order)")
         pcm, off, n = _clips(clips)
         o = beam_options(beam_width, token_prune, n_best, timestamps)
         res = C.POINTER(PkNbest)()
         if lm is None:
             check(lib().pk_transcribe_pcm_nbest(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res)))
-            return _nbest_list(res, n, timestamps)
+            return _nbest_list(res, n, timestamps, _nlm_rerank(res, n, o.n_best, nlm, nlm_alpha, nlm_beta))
         lo = lm_options(lm_alpha, lm_beta)
         lms = np.zeros((n, max(1, o.n_best)), np.float32)
         check(lib().pk_transcribe_pcm_nbest_lm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, C.byref(o), C.byref(res), lm._h, C.byref(lo), _f(lms)))
@@ -3177,3 +3220,107 @@ class Model:
             if lib().pk_decode_margins(self._h, _f(mg), B) == 0:
                 r["min_margin"] = mg                         # smallest top-1 / top-2 label log-prob margin per utterance
         return r
+
+
+# ---- neural LM rescoring (include/parakeet_amd.h "neural LM rescoring") -------------------------------------------------
+def nlm_rescore_options(alpha=None, beta=None):
+    """pk_nlm_rescore_options with the header's defaults (alpha 0.5, beta 0)"""
+    return PkNlmRescoreOptions(0.5 if alpha is None else alpha, 0.0 if beta is None else beta)
+
+
+def nlm_config(vocab_size=0, max_positions=0, hidden_size=0, num_layers=0, num_heads=1, ffn_intermediate=0, pre_ln=True, has_final_norm=False,
+               layer_norm_eps=1e-5, has_emb_norm=False, tied_head=True, bos_id=0, eos_id=-1):
+    return PkNlmConfig(vocab_size, max_positions, PkTransformerConfig(hidden_size, num_layers, num_heads, ffn_intermediate, int(pre_ln),
+                                                                      int(has_final_norm), layer_norm_eps), int(has_emb_norm), int(tied_head), bos_id, eos_id)
+
+
+def nlm_config_infer(weights_path, prefix="", num_heads=1, pre_ln=True, bos_id=0, eos_id=-1, layer_norm_eps=1e-5):
+    """pk_nlm_config_infer: what the tensor shapes determine, the rest as given.  Host only."""
+    c = nlm_config(num_heads=num_heads, pre_ln=pre_ln, bos_id=bos_id, eos_id=eos_id, layer_norm_eps=layer_norm_eps)
+    check(lib().pk_nlm_config_infer(weights_path.encode(), prefix.encode(), C.byref(c)))
+    return c
+
+
+def diag_nlm_order(am, nlm, lens, ok, alpha, beta):
+    """pk_diag_nlm_order: the re-ranking rule on one list -> (order, combined by slot).  Host arithmetic only."""
+    am, nlm, lens, ok = _c(am), _c(nlm), _c(lens, np.int32), _c(ok, np.int32)
+    N = len(am)
+    order, comb = np.zeros(max(1, N), np.int32), np.zeros(max(1, N), np.float32)
+    check(lib().pk_diag_nlm_order(_f(am), _f(nlm), _i(lens), _i(ok), N, alpha, beta, _i(order), _f(comb)))
+    return order[:N], comb[:N]
+
+
+def diag_causal_attention(qkv, lens, n_heads, scale):
+    """pk_diag_causal_attention: qkv [rows][3 d] of packed sequences -> ctx [rows + guard][d] as uint32-viewable floats (unwritten: 0x7FC5A5A5)."""
+    qkv, lens = _c(qkv), _c(lens, np.int32)
+    rows, d = qkv.shape[0], qkv.shape[1] // 3
+    assert rows == int(lens.sum())
+    ctx = np.zeros((rows + ATT_GUARD_ROWS, d), np.float32)
+    check(lib().pk_diag_causal_attention(len(lens), _i(lens), d, n_heads, scale, _f(qkv), _f(ctx)))
+    return ctx
+
+
+def diag_nlm_head_logp(h, W, bias, targets):
+    """pk_diag_nlm_head_logp: h [rows][d], W [V][d], bias [V] or None, targets [rows] -> lp [rows + guard] (unwritten: 0x7FC5A5A5)."""
+    h, W, targets = _c(h), _c(W), _c(targets, np.int32)
+    bias = None if bias is None else _c(bias)
+    rows, d = h.shape
+    lp = np.zeros(rows + ATT_GUARD_ROWS, np.float32)
+    check(lib().pk_diag_nlm_head_logp(_f(h), _f(W), _f(bias) if bias is not None else None, _i(targets), rows, W.shape[0], d, _f(lp)))
+    return lp
+
+
+class NeuralLm:
+    """pk_nlm: a causal Transformer LM over token ids for n-best rescoring."""
+
+    def __init__(self, weights_path, cfg, prefix="", device=0):
+        lib().pk_nlm_free.restype = None
+        self.cfg = cfg
+        self._h = C.c_void_p()
+        check(lib().pk_nlm_load(weights_path.encode(), prefix.encode(), C.byref(cfg), device, C.byref(self._h)))
+
+    def score(self, strings, token_logp=False):
+        """pk_nlm_score -> (total [n], ok [n]) and, with token_logp, per string the array of its P log-probabilities (None where ok = 0)"""
+        ids, off = _pack_ids(strings)
+        n = len(strings)
+        total, ok = np.zeros(max(1, n), np.float32), np.zeros(max(1, n), np.int32)
+        tl = np.zeros(int(off[-1]) + n + 1, np.float32)
+        check(lib().pk_nlm_score(self._h, _i(ids), _i(off), n, _f(total), _i(ok), _f(tl) if token_logp else None))
+        if not token_logp:
+            return total[:n], ok[:n]
+        end = 1 if self.cfg.eos_id >= 0 else 0
+        per = [tl[off[b] + b: off[b + 1] + b + end].copy() if ok[b] else None for b in range(n)]
+        return total[:n], ok[:n], per
+
+    def score_timed(self, strings, reps=5):
+        """pk_nlm_score_timed -> (embedding ms, blocks ms, head ms), HIP events, medians of reps passes"""
+        ids, off = _pack_ids(strings)
+        ms = np.zeros(3, np.float32)
+        check(lib().pk_nlm_score_timed(self._h, _i(ids), _i(off), len(strings), reps, _f(ms)))
+        return tuple(float(x) for x in ms)
+
+    def rescore(self, nbest, alpha=None, beta=None):
+        """The two-call route on lists already in Python (what transcribe_nbest* returned): pk_nlm_score on every hypothesis's ids, then the rule of
+        pk_diag_nlm_order per clip -> new lists of the same dicts with "score" = combined and "am_score" / "nlm_score" added."""
+        o = nlm_rescore_options(alpha, beta)
+        flat = [h["token_ids"] for hyps in nbest for h in hyps]
+        total, ok = self.score(flat) if flat else (np.zeros(0, np.float32), np.zeros(0, np.int32))
+        out, q = [], 0
+        for hyps in nbest:
+            k = len(hyps)
+            am = np.asarray([h["score"] for h in hyps], np.float32)
+            order, comb = diag_nlm_order(am, total[q:q + k], [len(h["token_ids"]) for h in hyps], ok[q:q + k], o.alpha, o.beta)
+            out.append([dict(hyps[j], score=float(comb[j]), am_score=float(am[j]), nlm_score=float(total[q + j])) for j in order])
+            q += k
+        return out
+
+    def set_scratch_cap(self, nbytes):
+        check(lib().pk_diag_nlm_set_scratch_cap(self._h, nbytes))
+
+    def last_groups(self):
+        return int(lib().pk_diag_nlm_groups(self._h))
+
+    def close(self):
+        if self._h:
+            lib().pk_nlm_free(self._h)
+            self._h = None

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "capi_util.hpp"
+#include "neural_lm.hpp"
 
 using namespace pk;
 
@@ -990,11 +991,13 @@ struct NbestStore {           // owns everything a pk_nbest array points into
     std::vector<pk_nbest> out;                              // one hidden trailing slot keeps the store pointer
     std::vector<ResultStorePtr> clip;                       // the hypotheses of one clip: a ResultStore of n_hyp results
     std::vector<std::vector<float>> score;
+    int N = 0;                                              // the n_best of the search that filled it (pk_nbest_rescore_nlm pitches its outputs by it)
     explicit NbestStore(int n_clips) : out((size_t)n_clips + 1), clip(n_clips), score(n_clips) {}
     // Clip c of the call gets the filled ones of the N slots of the batch's clip i (they come first): position j of its list is slot ord[j],
     // scored ranked[ord[j]].  Returns their number.
     int fill(Model &m, int c, int i, int N, BeamHost &h, const int32_t *ord, const float *ranked) {
         const size_t hy0 = (size_t)i * N;
+        this->N = N;
         int nh = 0;
         while (nh < N && h.sc[hy0 + nh] > NEGF) ++nh;
         clip[c] = new_store(nh);
@@ -1405,6 +1408,53 @@ pk_status pk_tdt_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets,
         Model &m = *h->m;
         tdt_align_model_checks(m);
         spot_pcm(m, true, pcm, offsets, n_clips, phrases, ids_in, kw_offsets_in, n_kw, opt, n_hits, start_s, end_s, score);
+    });
+}
+
+// Re-ranking of n-best lists with the Transformer LM (neural_lm.hpp; the rule is the header's): every hypothesis of the call scored in ONE packed
+// pk_nlm_score, then each clip's slots permuted in the store -- the pk_result structs (pointers into per-slot vectors that stay where they are) and
+// the scores.
+pk_status pk_nbest_rescore_nlm(pk_nbest *results, int n_clips, pk_nlm *nlm, const pk_nlm_rescore_options *opt, float *am_score, float *nlm_score) {
+    return guard([&] {
+        need(results && nlm && n_clips > 0, "results/nlm/n_clips");
+        const float alpha = opt ? opt->alpha : 0.5f, beta = opt ? opt->beta : 0.0f;
+        need(alpha == alpha && beta == beta, "options: alpha / beta must not be NaN");
+        NbestStore &S = *reinterpret_cast<NbestStore *>(const_cast<pk_result *>(results[n_clips].hyp));
+        need(S.out.data() == results && (int)S.clip.size() == n_clips, "results / n_clips: not a list of the n-best entry points");
+        const int N = S.N;
+        std::vector<int32_t> ids, off(1, 0);
+        for (int c = 0; c < n_clips; ++c)
+            for (int j = 0; j < results[c].n_hyp; ++j) {
+                const pk_result &r = results[c].hyp[j];
+                ids.insert(ids.end(), r.token_ids, r.token_ids + r.n_tokens);
+                off.push_back((int32_t)ids.size());
+            }
+        const int nh_all = (int)off.size() - 1;
+        ids.push_back(0);                                        // (never read: keeps data() valid when every hypothesis is empty)
+        std::vector<float> tot(nh_all + 1);
+        std::vector<int32_t> okv(nh_all + 1);
+        nlm->lm->score(ids.data(), off.data(), nh_all, tot.data(), okv.data(), nullptr);   // (refuses bad ids before any list is touched)
+        const bool identity = alpha == 0.0f && beta == 0.0f;
+        std::vector<int32_t> ord, lens;
+        std::vector<float> comb, am;
+        std::vector<pk_result> tmp;
+        int q0 = 0;
+        for (int c = 0; c < n_clips; ++c) {
+            const int nh = results[c].n_hyp;
+            ord.resize(nh); lens.resize(nh); comb.resize(nh); am.assign(S.score[c].begin(), S.score[c].end());
+            for (int j = 0; j < nh; ++j) lens[j] = results[c].hyp[j].n_tokens;
+            nlm_order(am.data(), tot.data() + q0, lens.data(), okv.data() + q0, nh, alpha, beta, ord.data(), comb.data());
+            if (!identity) {
+                ResultStore &R = *S.clip[c];
+                tmp.assign(R.res.begin(), R.res.begin() + nh);
+                for (int j = 0; j < nh; ++j) { R.res[j] = tmp[ord[j]]; S.score[c][j] = comb[ord[j]]; }
+            }
+            for (int j = 0; j < N; ++j) {
+                if (am_score) am_score[(size_t)c * N + j] = j < nh ? am[ord[j]] : NEGF;
+                if (nlm_score) nlm_score[(size_t)c * N + j] = j < nh ? tot[q0 + ord[j]] : NEGF;
+            }
+            q0 += nh;
+        }
     });
 }
 

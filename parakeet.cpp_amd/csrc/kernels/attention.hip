@@ -53,13 +53,17 @@ namespace pk {
 // LDS footprint of the sequence length allows anyway: a 30 s utterance (T = 376: 71 KB of score planes + V chunk, two workgroups per CU)
 // gains nothing from the spills of the 128-VGPR build.
 // BAND: the limited-context form (left / right; s_scratch and pos_row0 unused).  The full form ignores left / right.
-template <int HD, int VCH, bool SG = false, bool RAG = false, int OCC = (HD <= 64 ? ATT_OCC : 2), bool BAND = false>
+// CAUSAL (neural_lm.cpp: the Transformer LM's attention): the band form without a position term and with left = i, right = 0 for query row i --
+// the window of a block is keys [0, i0 + 31], so key tiles wholly above the diagonal are neither loaded nor multiplied, and inside the diagonal tile
+// AttRowsBand keeps a row's columns j > i out of its maximum and turns them into exact zeros.  pos / bias_u / bias_v / left / right are unused.
+template <int HD, int VCH, bool SG = false, bool RAG = false, int OCC = (HD <= 64 ? ATT_OCC : 2), bool BAND = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, OCC) void relpos_attention_kernel(const float *__restrict__ qkv, int ldq, int d, int T,
                                                                const float *__restrict__ pos /*[2T-1][d] (band: [left+right+1][d]), sigma columns*/,
                                                                const float *__restrict__ bias_u, const float *__restrict__ bias_v,
                                                                float scale, float *__restrict__ ctx, int PITS, int n_rb, int n_bh,
                                                                float *__restrict__ s_scratch, int ctx_bf16, int pos_row0, SeqRag rg, int left, int right) {
     static_assert(!(BAND && SG), "the band form keeps its score block in LDS");
+    static_assert(!CAUSAL || BAND, "the causal form is an instantiation of the band form");
     __builtin_amdgcn_s_setprio(3);        // ahead of the overlapped decode-loop waves in the SIMD's arbitration (gemm_pipe.hpp)
     constexpr int NQ4 = HD / 16;          // float4 fragments per lane for K = HD (one per block of 16 features)
     constexpr int VPIT = HD + 16;         // V rows, natural layout (pitch = 16 mod 32 banks)
@@ -79,16 +83,17 @@ __global__ __launch_bounds__(256, OCC) void relpos_attention_kernel(const float 
     const AttWave w = att_wave();
     // the key window [jlo, jhi] of this block, W columns; NP rows of position table
     int jlo = 0, jhi = T - 1;
+    if constexpr (CAUSAL) { left = i0 + RB; right = 0; }            // every key up to the row itself: jlo = 0, jhi = the block's last row
     if constexpr (BAND) {
         jlo = i0 - left > 0 ? i0 - left : 0;
         jhi = i0 + RB - 1 + right < T - 1 ? i0 + RB - 1 + right : T - 1;
     }
     const int W = BAND ? jhi - jlo + 1 : T;
     const int NP = BAND ? left + right + 1 : 2 * T - 1;
-    const bool has_pos = BAND || pos != nullptr;
+    const bool has_pos = !CAUSAL && (BAND || pos != nullptr);
     const float *qb = qkv + row0 * ldq + h * HD;                    // q rows of this (b,h) (sigma columns)
     const float *kb = qb + d + (int64_t)jlo * ldq, *vb = qb + 2 * d + (int64_t)jlo * ldq;   // k (sigma columns), v (natural): row c = key jlo + c
-    const float *pb = pos + (BAND ? (int64_t)0 : (int64_t)pos_row0 * d) + h * HD;           // row p of THIS length's table (engine.cpp: ensure_pos_tables)
+    const float *pb = CAUSAL ? nullptr : pos + (BAND ? (int64_t)0 : (int64_t)pos_row0 * d) + h * HD;           // row p of THIS length's table (engine.cpp: ensure_pos_tables)
 
     // ---- phase 0: the Q fragments of this wave's 16 rows.  Only ONE biased copy is live at a time -- (q+u) for the content scores, then
     //      q is fetched again (L2) and (q+v) formed for the position scores -- and the first V chunk is requested after the score phases:
@@ -519,6 +524,23 @@ void launch_relpos_local_attention(const float *qkv, int B, int T, int d, int n_
     } else if (hd == 128) launch_local<128, 32, 2>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
     else if (hd == 32) launch_local<32, 64, 4>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
     else if (hd == 96) launch_local<96, 64, 2>(qkv, B, T, d, n_heads, pos, bias_u, bias_v, ctx, s, ctx_bf16, left, right, W, rag);
+}
+
+// ---- the causal form's launcher (always ragged: packed sequences of rag.T[b] <= 512 positions) ----------------------------------------------------
+template <int HD, int VCH>
+static void launch_causal(const float *qkv, int d, int n_heads, float scale, float *ctx, hipStream_t s, const SeqRag &rag) {
+    const int W = rag.T_max;                                        // the widest window of any block: every key of the longest sequence
+    att_launch_dyn_lds<relpos_attention_kernel<HD, VCH, false, true, 2, true, true>>(
+        att_grid(0, 0, n_heads, rag), dim3(256), att_block_lds_bytes(W, HD, VCH), s, qkv, 3 * d, d, rag.T_max, (const float *)nullptr, (const float *)nullptr,
+        (const float *)nullptr, scale, ctx, att_score_pitch(W), 0, 0, (float *)nullptr, 0, 0, rag, 0, 0);
+}
+size_t causal_attention_lds_bytes(int T_max, int hd) { return att_hd_supported(hd) ? att_block_lds_bytes(T_max, hd, att_block_vch(hd)) : 0; }
+void launch_causal_attention(const float *qkv, int d, int n_heads, float scale, float *ctx, hipStream_t s, const SeqRag &rag) {
+    const int hd = d / n_heads;
+    if (hd == 64) launch_causal<64, 64>(qkv, d, n_heads, scale, ctx, s, rag);
+    else if (hd == 128) launch_causal<128, 32>(qkv, d, n_heads, scale, ctx, s, rag);
+    else if (hd == 32) launch_causal<32, 64>(qkv, d, n_heads, scale, ctx, s, rag);
+    else if (hd == 96) launch_causal<96, 64>(qkv, d, n_heads, scale, ctx, s, rag);
 }
 
 }  // namespace pk

@@ -412,6 +412,22 @@ size_t relpos_attention_scratch_bytes_units(int64_t n_units, int T_max, int n_he
 int relpos_local_attention_max_span(int hd);
 void launch_relpos_local_attention(const float *qkv, int B, int T, int d, int n_heads, const float *pos, const float *bias_u, const float *bias_v,
                                    float *ctx, hipStream_t s, int ctx_bf16, int left, int right, const SeqRag &rag = SeqRag());
+// Causal form (relpos_attention_kernel with BAND and CAUSAL; the Transformer LM of neural_lm.cpp): ctx_i = softmax_j<=i(scale q_i . k_j) V over PACKED
+// sequences -- rag is required (units = 32-row blocks, rag.T[b] positions each, rag.T_max the longest) -- with no position term.  qkv [rows][3 d]
+// (q / k sigma columns), ctx [rows][d] fp32 natural columns.  hd = d / n_heads in {32, 64, 96, 128}; the [32][T_max] score block lives in LDS:
+// causal_attention_lds_bytes(T_max, hd) <= 160 KB (0: unsupported head size; 512 positions fit at every head size).
+size_t causal_attention_lds_bytes(int T_max, int hd);
+void launch_causal_attention(const float *qkv, int d, int n_heads, float scale, float *ctx, hipStream_t s, const SeqRag &rag);
+// ---- Transformer LM (kernels/neural_lm.hip) ----
+// Packed positions of n strings: row r belongs to string b = row_str[r] at position i = r - row_off[b]; its input token is bos at i = 0 and
+// ids[id_off[b] + i - 1] behind it, its target ids[id_off[b] + i] for i < the string's length and eos at the end term.
+// h[r][:] = tok_emb[input][:] + pos_emb[i][:] (one fp32 add; d a multiple of 4), tgt[r] = the target.
+void launch_nlm_embed(const float *tok_emb, const float *pos_emb, const int32_t *ids, const int32_t *id_off, const int32_t *row_off, const int32_t *row_str,
+                      int bos, int eos, int d, int64_t rows, float *h, int32_t *tgt, hipStream_t s);
+// lp[r] = logit_r[tgt[r]] - logsumexp_c logit_r[c], logit_r[c] = the natural-k fma chain h_r . W_c from zero (+ bias[c], one add), c < V.  The logits
+// are never stored.  d a multiple of 32, ldh / ldw multiples of 4, V >= 1, any rows >= 1, 0 <= tgt[r] < V.
+void launch_nlm_head_logp(const float *h, int64_t ldh, const float *W, int64_t ldw, const float *bias, const int32_t *tgt, int64_t rows, int V, int d,
+                          float *lp, hipStream_t s);
 // The tolerance-class (pk_config.gemm_bf16) attention, kernels/attention_bf16.hip: q / k / v as bf16 [B*T][3d] (natural columns, written by the
 // qkv GEMM), the projected position table of the layer as bf16 [2T-1][d], cvec[h][p] = (v_h - u_h) . P_p (fp32, launch_pos_cvec), ctx as bf16.
 // Head sizes 64 and 128; relpos_attention_bf16_lds_bytes returns 0 for any other.

@@ -23,15 +23,20 @@ const float *TransformerEncoder::upload(const float *h, size_t n) {
     return static_cast<const float *>(p);
 }
 
-TransformerEncoder::TransformerEncoder(const std::string &weights_path, const std::string &prefix, const pk_transformer_config &c, int device)
-    : cfg(c) {
+void TransformerEncoder::check_config(const pk_transformer_config &c) {
     const int d = c.hidden_size, H = c.num_heads, f = c.ffn_intermediate;
     if (d <= 0 || H <= 0 || d % H || c.num_layers <= 0 || f <= 0) fail(PK_ERR_INVALID, "bad transformer config");
     if (d % 32 || f % 32) fail(PK_ERR_UNSUPPORTED, "hidden_size / ffn_intermediate must be multiples of 32 (MFMA K tile)");
     if (d > kLnMaxCols) fail(PK_ERR_UNSUPPORTED, "hidden_size > %d (a LayerNorm row lives in one wavefront's registers)", kLnMaxCols);   // as Model::validate_config
+    if ((d / H + 31) / 32 * 32 > 128) fail(PK_ERR_UNSUPPORTED, "head_dim > 128");
+}
+
+TransformerEncoder::TransformerEncoder(const std::string &weights_path, const std::string &prefix, const pk_transformer_config &c, int device)
+    : cfg(c) {
+    check_config(c);
+    const int d = c.hidden_size, H = c.num_heads, f = c.ffn_intermediate;
     const int hd = d / H;
     hdp_ = (hd + 31) / 32 * 32;
-    if (hdp_ > 128) fail(PK_ERR_UNSUPPORTED, "head_dim > 128");
     dp_ = H * hdp_;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) fail(PK_ERR_NO_DEVICE, "no HIP device available (this engine has no CPU path)");
@@ -100,13 +105,13 @@ void TransformerEncoder::forward(const float *x_host, int B, int T, float *y_hos
     PK_HIP(hipStreamSynchronize(stream_));
 }
 
-void TransformerEncoder::forward_dev(float *x, int B, int T, hipStream_t s) {
+void TransformerEncoder::forward_dev(float *x, int B, int T, hipStream_t s, const SeqRag *causal, int64_t causal_rows) {
     const int d = cfg.hidden_size, H = cfg.num_heads, f = cfg.ffn_intermediate, hd = d / H;
-    const int64_t rows = (int64_t)B * T;
+    const int64_t rows = causal ? causal_rows : (int64_t)B * T;
     const float eps = cfg.layer_norm_eps > 0.0f ? cfg.layer_norm_eps : 1e-5f;
     const float scale = 1.0f / sqrtf((float)hd);                              // src/transformer.cpp:27 (the REAL head dim)
     float *scratch = nullptr;
-    if (relpos_attention_lds_bytes(T, hdp_) > 160 * 1024) {          // long sequence: score blocks in global scratch (attention.hip)
+    if (!causal && relpos_attention_lds_bytes(T, hdp_) > 160 * 1024) {          // long sequence: score blocks in global scratch (attention.hip)
         const size_t need = relpos_attention_scratch_bytes(B, T, H, hdp_);
         if (need == 0 || need > ((size_t)64 << 30)) fail(PK_ERR_UNSUPPORTED, "sequence of %d frames x %d: attention scratch of %.1f GB", T, B, need / 1e9);
         att_scratch_.reserve(need);
@@ -122,7 +127,8 @@ void TransformerEncoder::forward_dev(float *x, int B, int T, hipStream_t s) {
             g.sigma_cols = 2 * dp_;
             launch_gemm(g, EPI_NONE, s);
         }
-        launch_relpos_attention(qkv_.as<float>(), B, T, dp_, H, nullptr, nullptr, nullptr, ctx_.as<float>(), s, scale, scratch);   // :38-45
+        if (causal) launch_causal_attention(qkv_.as<float>(), dp_, H, scale, ctx_.as<float>(), s, *causal);
+        else launch_relpos_attention(qkv_.as<float>(), B, T, dp_, H, nullptr, nullptr, nullptr, ctx_.as<float>(), s, scale, scratch);   // :38-45
         {   // out_proj + residual (:49-51)
             GemmArgs g{ctx_.as<float>(), dp_, L.wo, dp_, L.bo, x, d, x, d, 1.0f, (int)rows, d, dp_};
             launch_gemm(g, EPI_RESID, s);

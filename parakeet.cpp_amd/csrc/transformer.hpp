@@ -18,7 +18,15 @@ class TransformerEncoder {
     ~TransformerEncoder();
     void forward(const float *x_host, int B, int T, float *y_host);
     // x[B*T][hidden] on the device, in place, enqueued on `s` (never synchronises)
-    void forward_dev(float *x, int B, int T, hipStream_t s);
+    // causal (neural_lm.cpp): x holds causal->T_off[B] PACKED rows of B sequences and every attention launch is the causal form over them
+    // (launch_causal_attention; B / T are ignored).  nullptr: the launches of the line above, unchanged.
+    void forward_dev(float *x, int B, int T, hipStream_t s, const SeqRag *causal = nullptr, int64_t causal_rows = 0);
+    // what the constructor refuses about a configuration, before it looks for a device or a file
+    static void check_config(const pk_transformer_config &c);
+    // bytes of grow-only scratch forward_dev holds per row of x (n, qkv, ctx, h)
+    size_t scratch_bytes_per_row() const { return ((size_t)cfg.hidden_size + 4 * (size_t)dp_ + cfg.ffn_intermediate) * sizeof(float); }
+    hipStream_t stream() const { return stream_; }
+    int device() const { return device_; }
     pk_transformer_config cfg;
 
   private:

@@ -5,6 +5,7 @@
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
 //                [--spot "phrase"]... [--spot-file path.txt] [--spot-head ctc|tdt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
 //                [--device-resample] [--vad [--vad-max-piece S]]
+//                [--nlm file.safetensors --nlm-heads H --nlm-bos ID [--nlm-eos ID] [--nlm-alpha A] [--nlm-beta B]]
 // New: --vad (tdt-ctc-110m, tdt-600m; 16 kHz) cuts the file at its pauses on the device and transcribes only the speech, in pieces of at most
 // S seconds (--vad-max-piece S, default 30) that share batches (TranscribeOptions::vad): for long or sparse recordings.
 // New: --device-resample (tdt-ctc-110m, tdt-600m) reads the file at its own sample rate and resamples it to 16 kHz on the device, inside the call
@@ -23,6 +24,9 @@
 // New: --lm file.arpa (with --beam W and the CTC decoder, or with --beam W --beam-head tdt) fuses an n-gram language model over token ids into the beam search (shallow fusion):
 // hypotheses rank by acoustic score + LM score, LM score = sum per token of A * log p + B (--lm-alpha A, default 0.5; --lm-beta B, default 0);
 // both parts are printed.  tools/make_token_corpus.py turns text into the id lines an n-gram trainer makes such a file from.
+// New: --nlm file.safetensors --nlm-heads H --nlm-bos ID [--nlm-eos ID] (with --beam W and the CTC decoder, or with --beam W --beam-head tdt) re-ranks the
+// N best hypotheses with a causal Transformer LM over token ids: combined = acoustic + A * LM + B * tokens (--nlm-alpha A,
+// default 0.5; --nlm-beta B, default 0); the rest of the LM's configuration is read off the file's tensor shapes; all three values are printed.
 // Differences: --gpu is accepted and implied (there is no CPU path); --features (a .npy of pre-computed features) is not supported.
 #include <algorithm>
 #include <chrono>
@@ -51,6 +55,8 @@ static void usage(const char *prog) {
               << "  --spot \"phrase\" (repeatable) | --spot-file path.txt  where was each phrase said: phrase<TAB>start<TAB>end<TAB>score per hit\n"
               << "  --beam W --lm file.arpa [--lm-alpha A] [--lm-beta B]  the CTC beam search fused with an n-gram model over token ids\n"
               << "  --beam W --beam-head tdt --lm file.arpa [--lm-alpha A] [--lm-beta B]  the TDT beam search fused with the model; both scores per hypothesis\n"
+              << "  --beam W [--beam-head tdt] --nbest N --nlm file.safetensors --nlm-heads H --nlm-bos ID [--nlm-eos ID] [--nlm-alpha A] [--nlm-beta B]\n"
+              << "                      the N best hypotheses re-ranked by a Transformer LM over token ids: am + A * nlm + B * tokens\n"
               << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold), --spot-head ctc|tdt (default ctc; tdt works for tdt-600m)\n"
               << "  --device-resample  resample files that are not 16 kHz on the device instead of on the host (tdt-ctc-110m, tdt-600m)\n"
               << "  --vad [--vad-max-piece S]  transcribe only the speech, cut at the pauses into pieces of at most S seconds (default 30)\n"
@@ -137,8 +143,10 @@ int main(int argc, char **argv) {
     if (argc < 3) { usage(argv[0]); return 1; }
     try {
         const std::string weights = argv[1], audio_path = argv[2];
-        std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text, score_text, lm_path;
+        std::string model = "tdt-ctc-110m", vocab, sf_weights, align_text, score_text, lm_path, nlm_path;
         LmOptions lm_opts;
+        NlmOptions nlm_opts;
+        int nlm_heads = 0, nlm_bos = -1, nlm_eos = -1;
         bool use_ctc = false, timestamps = false, device_resample = false, align = false, align_tdt = false, beam_tdt = false, score = false, rescore = false, nbest_given = false;
         int latency = 0, beam = 0, nbest = 1, prune = 16;
         float rescore_w = 0.5f;
@@ -198,6 +206,12 @@ int main(int argc, char **argv) {
             else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
             else if (a == "--lm-alpha" && i + 1 < argc) lm_opts.alpha = std::stof(argv[++i]);
             else if (a == "--lm-beta" && i + 1 < argc) lm_opts.beta = std::stof(argv[++i]);
+            else if (a == "--nlm" && i + 1 < argc) nlm_path = argv[++i];
+            else if (a == "--nlm-heads" && i + 1 < argc) nlm_heads = std::stoi(argv[++i]);
+            else if (a == "--nlm-bos" && i + 1 < argc) nlm_bos = std::stoi(argv[++i]);
+            else if (a == "--nlm-eos" && i + 1 < argc) nlm_eos = std::stoi(argv[++i]);
+            else if (a == "--nlm-alpha" && i + 1 < argc) nlm_opts.alpha = std::stof(argv[++i]);
+            else if (a == "--nlm-beta" && i + 1 < argc) nlm_opts.beta = std::stof(argv[++i]);
             else if (a == "--device-resample") device_resample = true;
             else if (a == "--vad") vad = true;
             else if (a == "--vad-max-piece" && i + 1 < argc) vad_max_piece = std::stof(argv[++i]);
@@ -237,6 +251,12 @@ int main(int argc, char **argv) {
                          "tdt-600m (no --rescore-tdt)\n";
             return 1;
         }
+        if (!nlm_path.empty() && (beam <= 0 || rescore || !lm_path.empty() || nlm_heads <= 0 || nlm_bos < 0 ||
+                                  (beam_tdt ? model != "tdt-ctc-110m" && model != "tdt-600m" : model != "tdt-ctc-110m"))) {
+            std::cerr << "Error: --nlm needs --nlm-heads H, --nlm-bos ID and --beam W with the CTC head of --model tdt-ctc-110m, or --beam W --beam-head tdt "
+                         "with --model tdt-ctc-110m or tdt-600m (no --rescore-tdt, no --lm)\n";
+            return 1;
+        }
         if (beam_tdt && beam <= 0) { std::cerr << "Error: --beam-head needs --beam W\n"; return 1; }
         if (beam_tdt && !boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
         // --beam W --beam-head tdt: the TDT beam search's N best hypotheses, each with its path log-probability
@@ -257,6 +277,19 @@ int main(int argc, char **argv) {
             for (size_t j = 0; j < hyps.size(); ++j) {
                 std::cout << "\n=== Hypothesis " << j << " score " << std::setprecision(9) << std::defaultfloat << hyps[j].score << " lm " << hyps[j].lm_score
                           << " ===\n";
+                print_result(hyps[j].result, timestamps, ms);
+            }
+            return 0;
+        };
+        // ... with --nlm: either search's list re-ranked by a Transformer LM, the combined score and both parts of every hypothesis
+        auto print_beam_nlm = [&](const char *head, const NeuralLanguageModel &nlm, const std::vector<NlmScoredResult> &hyps, double ms) {
+            const pk_nlm_config &c = nlm.config();
+            std::cout << "Beam search (" << head << "): width " << beam << ", re-ranked by a Transformer LM (" << c.transformer.num_layers << " layers, d "
+                      << c.transformer.hidden_size << ", vocabulary " << c.vocab_size << "), alpha " << std::defaultfloat << nlm_opts.alpha << " beta "
+                      << nlm_opts.beta << ", " << hyps.size() << " hypotheses\n";
+            for (size_t j = 0; j < hyps.size(); ++j) {
+                std::cout << "\n=== Hypothesis " << j << " score " << std::setprecision(9) << std::defaultfloat << hyps[j].score << " am " << hyps[j].am_score
+                          << " nlm " << hyps[j].nlm_score << " ===\n";
                 print_result(hyps[j].result, timestamps, ms);
             }
             return 0;
@@ -284,6 +317,12 @@ int main(int argc, char **argv) {
             }
             if (!boost.empty()) std::cout << "Phrase boost: " << boost.size() << " phrases\n";
             if (beam > 0 && beam_tdt) {
+                if (!nlm_path.empty()) {
+                    const NeuralLanguageModel nlm(nlm_path, nlm_heads, nlm_bos, nlm_eos);
+                    const auto t0 = Clock::now();
+                    const auto hyps = t.transcribe_nbest_tdt(audio_path, tbo, nlm, nlm_opts);
+                    return print_beam_nlm("tdt", nlm, hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+                }
                 if (!lm_path.empty()) {
                     const LanguageModel lm(lm_path);
                     const auto t0 = Clock::now();
@@ -299,6 +338,12 @@ int main(int argc, char **argv) {
                 if (!boost.empty()) { std::cerr << "Error: --beam has no phrase-boosted variant\n"; return 1; }
                 BeamOptions bo;
                 bo.beam_width = beam; bo.n_best = nbest; bo.token_prune = prune; bo.timestamps = timestamps;
+                if (!nlm_path.empty()) {
+                    const NeuralLanguageModel nlm(nlm_path, nlm_heads, nlm_bos, nlm_eos);
+                    const auto t0 = Clock::now();
+                    const auto hyps = t.transcribe_nbest(audio_path, bo, nlm, nlm_opts);
+                    return print_beam_nlm("ctc", nlm, hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+                }
                 if (!lm_path.empty()) {                              // shallow fusion: the lists come back in fused order, both parts printed
                     const LanguageModel lm(lm_path);
                     const auto t0 = Clock::now();
@@ -335,6 +380,12 @@ int main(int argc, char **argv) {
             if (!spot.empty()) return run_spot(t, audio_path, spot, spot_opts, true);
             if (beam > 0) {
                 if (!beam_tdt) { std::cerr << "Error: this model has no CTC head: --beam needs --beam-head tdt\n"; return 1; }
+                if (!nlm_path.empty()) {
+                    const NeuralLanguageModel nlm(nlm_path, nlm_heads, nlm_bos, nlm_eos);
+                    const auto t0 = Clock::now();
+                    const auto hyps = t.transcribe_nbest(audio_path, tbo, nlm, nlm_opts);
+                    return print_beam_nlm("tdt", nlm, hyps, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+                }
                 if (!lm_path.empty()) {
                     const LanguageModel lm(lm_path);
                     const auto t0 = Clock::now();

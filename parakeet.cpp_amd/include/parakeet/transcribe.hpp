@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <limits>
 #include <stdexcept>
+#include <type_traits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -135,6 +136,45 @@ struct LmOptions {
 /// New: one hypothesis of transcribe_nbest(audio, beam, lm): score stays the acoustic log-probability, lm_score is the model's part.
 struct LmScoredResult : ScoredResult {
     float lm_score = 0.0f;
+};
+/// New: a causal Transformer LM over the acoustic model's token ids plus BOS / EOS (pk_nlm) that re-ranks n-best lists.
+/// The file's tensor shapes give the rest of the configuration (pk_nlm_config_infer); eos_id < 0: no end-of-string term.
+class NeuralLanguageModel {
+  public:
+    NeuralLanguageModel(const std::string &safetensors_path, int num_heads, int bos_id, int eos_id = -1, bool pre_ln = true, const std::string &prefix = "",
+                        int device = 0) {
+        cfg_ = pk_nlm_config{};
+        cfg_.transformer.num_heads = num_heads;
+        cfg_.transformer.pre_ln = pre_ln ? 1 : 0;
+        cfg_.transformer.layer_norm_eps = 1e-5f;
+        cfg_.bos_id = bos_id;
+        cfg_.eos_id = eos_id;
+        if (pk_nlm_config_infer(safetensors_path.c_str(), prefix.c_str(), &cfg_) != PK_OK ||
+            pk_nlm_load(safetensors_path.c_str(), prefix.c_str(), &cfg_, device, &nlm_) != PK_OK) {
+            char msg[1024];
+            pk_last_error(msg, sizeof msg);
+            throw std::runtime_error(msg);
+        }
+    }
+    ~NeuralLanguageModel() { pk_nlm_free(nlm_); }
+    NeuralLanguageModel(const NeuralLanguageModel &) = delete;
+    NeuralLanguageModel &operator=(const NeuralLanguageModel &) = delete;
+    const pk_nlm_config &config() const { return cfg_; }
+    pk_nlm *handle() const { return nlm_; }
+
+  private:
+    pk_nlm_config cfg_;
+    pk_nlm *nlm_ = nullptr;
+};
+/// New: weights of the re-ranking (pk_nlm_rescore_options): combined = am + alpha * nlm + beta * tokens.
+struct NlmOptions {
+    float alpha = 0.5f;
+    float beta = 0.0f;
+};
+/// New: one hypothesis of transcribe_nbest(audio, beam, nlm): score is the combined value, am_score / nlm_score its parts.
+struct NlmScoredResult : ScoredResult {
+    float am_score = 0.0f;
+    float nlm_score = 0.0f;
 };
 /// New: what Transcriber::score returns: the log-likelihood of the given transcript under the TDT head (pk_tdt_score_pcm: the forward algorithm
 /// on the alignment's lattice).  scored == false: no path emits the transcript on this audio, log_likelihood is -inf.
@@ -295,6 +335,31 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     }
     std::vector<LmScoredResult> run_nbest_tdt_lm_file(const std::string &audio_path, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lmo) {
         return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_nbest_tdt_lm(pcm, n, opts, lm, lmo); });
+    }
+
+    // the list of run_nbest (tdt false) or run_nbest_tdt (tdt true) re-ranked by a Transformer LM: pk_nbest_rescore_nlm on the list before it is taken
+    template <class Options>
+    std::vector<NlmScoredResult> run_nbest_nlm(const float *pcm, size_t n, const Options &opts, const NeuralLanguageModel &nlm, const NlmOptions &no) {
+        if (!on_gpu_) to_gpu(0);
+        const int64_t offsets[2] = {0, (int64_t)n};
+        pk_nbest *res = nullptr;
+        if constexpr (std::is_same<Options, TdtBeamOptions>::value) {
+            const pk_tdt_beam_options o = tdt_beam_options(opts);
+            check(pk_transcribe_pcm_nbest_tdt(m_, pcm, offsets, 1, &o, opts.timestamps ? 1 : 0, &res));
+        } else {
+            const pk_beam_options o = beam_options(opts);
+            check(pk_transcribe_pcm_nbest(m_, pcm, offsets, 1, &o, &res));
+        }
+        const pk_nlm_rescore_options ro{no.alpha, no.beta};
+        std::vector<float> am((size_t)std::max(1, opts.n_best)), ns(am.size());
+        const pk_status st = pk_nbest_rescore_nlm(res, 1, nlm.handle(), &ro, am.data(), ns.data());
+        if (st != PK_OK) pk_nbest_free(res, 1);
+        check(st);
+        return take_nbest<NlmScoredResult>(res, opts.timestamps, [&](NlmScoredResult &r, int j) { r.am_score = am[j]; r.nlm_score = ns[j]; });
+    }
+    template <class Options>
+    std::vector<NlmScoredResult> run_nbest_nlm_file(const std::string &audio_path, const Options &opts, const NeuralLanguageModel &nlm, const NlmOptions &no) {
+        return with_audio(audio_path, [&](const float *pcm, size_t n) { return run_nbest_nlm(pcm, n, opts, nlm, no); });
     }
 
     // pk_transcribe_pcm_nbest_rescored on one clip: run_nbest's list re-ranked by the TDT head's log-likelihood of every hypothesis
@@ -530,6 +595,13 @@ class Transcriber {
     std::vector<LmScoredResult> transcribe_nbest(const float *pcm, size_t n, const BeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {
         return eng_.run_nbest_lm(pcm, n, opts, lm, lm_opts);
     }
+    /// New: the list of either search re-ranked by a Transformer LM (pk_nbest_rescore_nlm): score + am_score + nlm_score
+    std::vector<NlmScoredResult> transcribe_nbest(const std::string &audio_path, const BeamOptions &opts, const NeuralLanguageModel &nlm, const NlmOptions &no = {}) {
+        return eng_.run_nbest_nlm_file(audio_path, opts, nlm, no);
+    }
+    std::vector<NlmScoredResult> transcribe_nbest_tdt(const std::string &audio_path, const TdtBeamOptions &opts, const NeuralLanguageModel &nlm, const NlmOptions &no = {}) {
+        return eng_.run_nbest_nlm_file(audio_path, opts, nlm, no);
+    }
     /// New: the same search through this model's TDT head (TDTTranscriber::transcribe_nbest)
     std::vector<ScoredResult> transcribe_nbest_tdt(const std::string &audio_path, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt_file(audio_path, opts); }
     std::vector<ScoredResult> transcribe_nbest_tdt(const float *pcm, size_t n, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt(pcm, n, opts); }
@@ -640,6 +712,10 @@ class TDTTranscriber {
     std::vector<ScoredResult> transcribe_nbest(const float *pcm, size_t n, const TdtBeamOptions &opts = {}) { return eng_.run_nbest_tdt(pcm, n, opts); }
     std::vector<ScoredResult> transcribe_nbest(const std::vector<float> &samples, const TdtBeamOptions &opts = {}) {
         return eng_.run_nbest_tdt(samples.data(), samples.size(), opts);
+    }
+    /// New: the list re-ranked by a Transformer LM (pk_nbest_rescore_nlm): score + am_score + nlm_score
+    std::vector<NlmScoredResult> transcribe_nbest(const std::string &audio_path, const TdtBeamOptions &opts, const NeuralLanguageModel &nlm, const NlmOptions &no = {}) {
+        return eng_.run_nbest_nlm_file(audio_path, opts, nlm, no);
     }
     /// New: the search with n-gram LM shallow fusion (pk_transcribe_pcm_nbest_tdt_lm): fused order, score + lm_score
     std::vector<LmScoredResult> transcribe_nbest(const std::string &audio_path, const TdtBeamOptions &opts, const LanguageModel &lm, const LmOptions &lm_opts = {}) {

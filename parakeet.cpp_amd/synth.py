@@ -115,6 +115,35 @@ def synth_sortformer_weights(sf, seed: int = 42) -> dict:
     return W
 
 
+def synth_nlm_weights(cfg, seed: int = 42, prefix: str = "") -> dict:
+    """State dict of a Transformer LM for capi.NeuralLm (cfg: capi.PkNlmConfig; tensor names: INTEGRATION.md).  Scales: the rows that reach the
+    head are LayerNorm outputs (norm about sqrt(d)) and the head rows are N(0, 1.5^2 / d), so logits have a standard deviation of about 1.5: the
+    softmax over the vocabulary spreads (top probability of a few percent at Vlm = 67) instead of going one-hot; q_proj is tripled as in
+    synth_sortformer_weights so that attention is not uniform either."""
+    rng = np.random.default_rng(seed + 2000)
+    t = cfg.transformer
+    d, ffn, V = t.hidden_size, t.ffn_intermediate, cfg.vocab_size
+    lin = lambda o, i, s=1.0: (s * rng.standard_normal((o, i)) / np.sqrt(i)).astype(np.float32)
+    vec = lambda n, s=0.02: (s * rng.standard_normal(n)).astype(np.float32)
+    W = {"tok_emb_.weight": lin(V, d, 1.5), "pos_emb_.weight": lin(cfg.max_positions, d, 0.75)}
+    if cfg.has_emb_norm:
+        W["emb_norm_.weight"], W["emb_norm_.bias"] = (1 + vec(d)).astype(np.float32), vec(d)
+    for l in range(t.num_layers):
+        p = f"layers_.{l}."
+        for n in ("norm1_", "norm2_"):
+            W[p + n + ".weight"] = (1 + vec(d)).astype(np.float32); W[p + n + ".bias"] = vec(d)
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            W[p + "mha_." + n + ".weight"] = lin(d, d); W[p + "mha_." + n + ".bias"] = vec(d)
+        W[p + "mha_.q_proj.weight"] *= np.float32(3.0)
+        W[p + "fc1_.weight"] = lin(ffn, d); W[p + "fc1_.bias"] = vec(ffn)
+        W[p + "fc2_.weight"] = lin(d, ffn); W[p + "fc2_.bias"] = vec(d)
+    if t.has_final_norm:
+        W["final_norm_.weight"], W["final_norm_.bias"] = (1 + vec(d)).astype(np.float32), vec(d)
+    if not cfg.tied_head:
+        W["lm_head_.weight"], W["lm_head_.bias"] = lin(V, d, 1.5), vec(V, 0.5)
+    return {prefix + k: v for k, v in W.items()}
+
+
 def save_weights(path: str, W: dict):
     from safetensors.numpy import save_file
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
