@@ -966,6 +966,7 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
 // ContextTrie::insert / build (src/phrase_boost.cpp:11-37) on the host, flattened to CSR for the decode kernels.
 void Model::set_boost(const std::vector<std::vector<int>> &phrases, float score) {
     require_gpu();
+    ++boost_gen;                                                   // a captured decode graph carries the trie by value (run_tdt_loop: its key holds this counter)
     boost_phrases = phrases;
     boost_score = score;
     boost_on = !phrases.empty();
@@ -1210,14 +1211,39 @@ void Model::run_tdt_loop(Workspace &w, int B, int T, int max_tokens, hipStream_t
     // (teacher-forced scoring launches another decision kernel on per-call arrays: it never shares a captured graph with the decode loop)
     const bool want_graph = decode_loop == PK_DECODE_LOOP_GRAPH && !w.force_label;
     if (want_graph && !prof) {
-        // key = the pointer / size arguments the captured launches carry, field by field (no struct padding in the comparison) + the model's
-        // weight generation (a graph never outlives the weights it was captured against: the workspace is keyed by model + stream)
+        // key = EVERY argument the captured launches carry, listed field by field (the values' bytes one after the other: no struct padding in the
+        // comparison): the whole TdtState the decision launch takes -- the trie record and the boost score's bits, the prediction-net cache and
+        // frame window, the forced-path fields -- and the whole SkinnyArgs record of every product in use (cell[0 .. L-1], act, heads); then what
+        // chooses the launches (chunk length, fp32 or bf16 products) and whom the graph belongs to (model, stream, the model's trie generation:
+        // set_boost bumps it, so no graph captured against an earlier trie -- whose buffers set_boost may have freed -- is ever replayed).
+        // A new field of either struct goes into put_state / put_skinny below.
         std::vector<unsigned char> key;
-        auto put = [&key](const void *p, size_t n) { const unsigned char *c = static_cast<const unsigned char *>(p); key.insert(key.end(), c, c + n); };
-        const void *ptrs[] = {this, s, st.logits, st.h, st.c, st.hn, st.cn, st.token, st.lens, st.ids, st.start, st.end, st.conf, P.act.ep, P.heads.W, P.act.W, P.cell[0].W, P.cell[0].gi, st.Tb, st.row0};
-        const int ints[] = {B, T, V, D, L, Hp, J, max_tokens, st.blank, st.max_symbols, st.max_steps, st.keep_state, boost_on ? 1 : 0, pred_cache ? 1 : 0, st.F};
-        put(ptrs, sizeof ptrs);
-        put(ints, sizeof ints);
+        auto put = [&key](auto v) { const unsigned char *c = reinterpret_cast<const unsigned char *>(&v); key.insert(key.end(), c, c + sizeof v); };
+        auto put_state = [&put](const TdtState &a) {
+            put(a.B); put(a.T); put(a.V); put(a.D); put(a.L); put(a.Hp); put(a.blank); put(a.max_symbols); put(a.max_tokens); put(a.max_steps);
+            put(a.trie.off); put(a.trie.tok); put(a.trie.node); put(a.trie.n_nodes); put(a.trie.boost); put(a.trie.act); put(a.trie.n_act);
+            put(a.keep_state);
+            for (int d : a.durations) put(d);
+            put(a.logits); put(a.h); put(a.c); put(a.hn); put(a.cn);
+            put(a.token); put(a.t); put(a.nsym); put(a.n_out); put(a.steps); put(a.done); put(a.lens); put(a.done_count);
+            put(a.ids); put(a.start); put(a.end); put(a.conf);
+            put(a.h_bf16); put(a.margin);
+            put(a.need); put(a.pp); put(a.ep); put(a.z); put(a.J); put(a.F);
+            put(a.Tb); put(a.row0);
+            put(a.force_label); put(a.force_dur); put(a.n_force); put(a.score_lab); put(a.score_dur); put(a.n_force_b); put(a.force_stride);
+        };
+        auto put_skinny = [&put](const SkinnyArgs &a) {
+            put(a.X); put(a.W); put(a.B); put(a.N); put(a.K); put(a.bias); put(a.out); put(a.ldo);
+            put(a.ep); put(a.t); put(a.T); put(a.F);
+            put(a.gi); put(a.gi_ld); put(a.gi_row); put(a.c); put(a.cn); put(a.Hp);
+            put(a.X2); put(a.W2); put(a.bias2);
+            put(a.need); put(a.pp_out); put(a.Tb); put(a.row0);
+        };
+        put(static_cast<const void *>(this)); put(s); put(boost_gen); put(chunk); put(dec16 ? 1 : 0);
+        put_state(st);
+        for (int l = 0; l < L; ++l) put_skinny(P.cell[l]);
+        put_skinny(P.act);
+        put_skinny(P.heads);
         if (!w.dec_graph || key != w.dec_graph_key) {
             if (w.dec_graph) { (void)hipGraphExecDestroy(w.dec_graph); w.dec_graph = nullptr; }
             hipGraph_t graph = nullptr;

@@ -235,6 +235,7 @@ class Model {
     bool boost_on = false;
     float boost_score = 0.0f;
     int trie_nodes = 0;
+    unsigned long long boost_gen = 0;                 // bumped by every set_boost: part of the captured decode graph's key (run_tdt_loop)
     std::vector<std::vector<int>> boost_phrases;      // what the trie was built from (per-call overrides restore it)
     DevBuf trie_off, trie_tok, trie_node;
     TrieDev trie_dev(Workspace &w, int B);

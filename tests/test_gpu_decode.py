@@ -162,7 +162,8 @@ def test_single_utterance_frame_window(tmp_path_factory):
     """One utterance per call decodes through the frame window (TdtState::F: the joint of the next frames in the heads product's spare rows, tdt_decide walking
     through the blanks inside it).  Every output word -- ids, frames, confidences, the count of joint evaluations -- against the oracle's one-decision-at-a-time loop:
     ordinary weights, weights pushed towards blanks of duration 1 (long walks, windows that run out), blanks of duration 4 (the window ends at the first blank),
-    sequences shorter than the window, the RNNT head (no durations), two LSTM layers, and the 110m decoder shapes (K = 640 kernels, vocabulary 1025)."""
+    sequences shorter than the window, the RNNT head (no durations), two LSTM layers, and the 110m decoder shapes (K = 640 kernels, vocabulary 1025).
+    Only B = 1 takes the window (kDecodeWindowRows = 1 in csrc/engine.cpp); the B = 2 and B = 3 batches decode the same edited models without one."""
     tmp = tmp_path_factory.mktemp("win")
     pre = "tdt_joint_."
 
