@@ -357,7 +357,19 @@ _LATE_SIGNATURES = {
                                       C.POINTER(C.c_int)],
     "pk_diag_stream_attention": [C.c_int] * 6 + [f32p] * 4 + [C.c_int, f32p, f32p] + [C.c_int] * 5 + [f32p] * 3 + [C.POINTER(C.c_int)],
     "pk_diag_mel": [C.c_int] * 5 + [f32p, C.c_int, C.c_int64, i64p, f32p, C.c_int64, f32p, C.c_int64, i32p, i32p],
-}
+    "pk_diag_ln_gemm_bf16": [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_float, f32p, f32p, C.c_int, f32p, C.c_float, f32p],
+    "pk_diag_ln2_gemm_bf16": [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p],
+    "pk_diag_smallm_bf16_tiles": [C.c_int],
+    "pk_diag_pred_cache": [C.c_int],
+    "pk_diag_ffn_bf16_smallm": [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p, C.c_int, f32p],
+    "pk_diag_glu_dwconv_bf16": [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_float, f32p, f32p, f32p, C.c_int] + [f32p] * 6 + [C.c_int, f32p, f32p],
+    "pk_diag_sigma_copy": [f32p, C.c_int64, C.c_int, C.c_int64, f32p],
+    "pk_diag_tile_copy_bf16": [f32p, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_uint16)],
+    "pk_diag_layernorm_sigma": [f32p, C.c_int64, C.c_int, f32p, f32p, C.c_float, f32p],
+    "pk_diag_layernorm2": [f32p, C.c_int64, C.c_int] + [f32p] * 4 + [C.c_float, C.c_int, f32p, f32p],
+    "pk_diag_layernorm_form_of": [C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)],
+    "pk_diag_gemm_tile_form": [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32)],
+}   # (the entries that take a struct are added where the struct is defined; lib() runs after the module has loaded)
 
 
 def _f(a):
@@ -370,6 +382,53 @@ def _i(a):
 
 def _c(a, dt=np.float32):
     return np.ascontiguousarray(a, dtype=dt)
+
+
+def _pitched(a, ld):
+    """a [rows][cols] at a row pitch of ld floats (zeros behind every row); a itself when ld is None or its width"""
+    if ld is None or ld == a.shape[1]:
+        return a
+    p = np.zeros((a.shape[0], int(ld)), np.float32)
+    n = min(a.shape[1], int(ld))
+    p[:, :n] = a[:, :n]
+    return p
+
+
+class _Keep:
+    """The arrays an argument struct points into, held until the wrapper returns.  opt(a): an optional array converted, retained -> its pointer (None: None)."""
+
+    def __init__(self, *arrays):
+        self.arrays = list(arrays)
+
+    def opt(self, a, dt=np.float32):
+        if a is None:
+            return None
+        a = _c(a, dt)
+        self.arrays.append(a)
+        return a.ctypes.data_as(f32p if dt == np.float32 else i32p)
+
+
+def _forms(fn_name, decode):
+    """a pk_diag_*_forms(out, cap) listing, every entry through `decode`"""
+    fn = getattr(lib(), fn_name)
+    out = np.zeros(fn(None, 0), np.int32)
+    fn(_i(out), out.size)
+    return [decode(int(v)) for v in out]
+
+
+def _set_remap(d, remap):
+    """remap = (rows, gs, rs, cs) or None into the remap_* fields of a product's argument struct"""
+    if remap is not None:
+        d.remap_rows, d.remap_gs, d.remap_rs, d.remap_cs = (int(v) for v in remap)
+
+
+def _out_words_default(d, M, N, ldo, out_words, half=False, blocked=False):
+    """d.ldo (default N) and d.out_words (default: the words of M rows at that pitch; half: two bf16 to a word; blocked: the rows rounded up to 32)"""
+    d.ldo = int(ldo) if ldo is not None else N
+    if out_words is None:
+        rows = (M + 31) // 32 * 32 if blocked else M
+        out_words = (rows * d.ldo + 1) // 2 if half else rows * d.ldo
+    d.out_words = int(out_words)
 
 
 def check(st):
@@ -1012,10 +1071,8 @@ def diag_ln_gemm_bf16(A, gamma, beta, W, bias=None, epi="none", resid=None, alph
     b = _c(bias) if bias is not None else None
     r = _c(resid) if resid is not None else None
     out = np.empty((M, N), np.float32)
-    L = lib()
-    L.pk_diag_ln_gemm_bf16.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_float, f32p, f32p, C.c_int, f32p, C.c_float, f32p]
-    check(L.pk_diag_ln_gemm_bf16(M, N, K, _f(A), _f(gamma), _f(beta), eps, _f(W), _f(b) if b is not None else None, EPI[epi],
-                                 _f(r) if r is not None else None, alpha, _f(out)))
+    check(lib().pk_diag_ln_gemm_bf16(M, N, K, _f(A), _f(gamma), _f(beta), eps, _f(W), _f(b) if b is not None else None, EPI[epi],
+                                     _f(r) if r is not None else None, alpha, _f(out)))
     return out
 
 
@@ -1025,17 +1082,13 @@ def diag_ln2_gemm_bf16(A, pre_gamma, pre_beta, gamma, beta, W, bias, eps=1e-5):
     M, K = A.shape
     N = W.shape[0]
     out = np.empty((M, N), np.float32); pre = np.empty((M, K), np.float32)
-    L = lib()
-    L.pk_diag_ln2_gemm_bf16.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p]
-    check(L.pk_diag_ln2_gemm_bf16(M, N, K, _f(A), _f(pg), _f(pb), _f(g), _f(b), eps, _f(W), _f(bias), _f(out), _f(pre)))
+    check(lib().pk_diag_ln2_gemm_bf16(M, N, K, _f(A), _f(pg), _f(pb), _f(g), _f(b), eps, _f(W), _f(bias), _f(out), _f(pre)))
     return out, pre
 
 
 def diag_smallm_bf16_tiles(on):
     """pk_diag_smallm_bf16_tiles: the bf16 diag products with / without the operand-tiled weight copy (test switch, process-wide)."""
-    L = lib()
-    L.pk_diag_smallm_bf16_tiles.argtypes = [C.c_int]
-    check(L.pk_diag_smallm_bf16_tiles(int(on)))
+    check(lib().pk_diag_smallm_bf16_tiles(int(on)))
 
 
 class PkSkinnyDiag(C.Structure):
@@ -1045,6 +1098,9 @@ class PkSkinnyDiag(C.Structure):
                 ("X2", f32p), ("W2", f32p), ("bias2", f32p),
                 ("ep", f32p), ("ep_rows", C.c_int64), ("t", i32p), ("T", C.c_int32), ("Tb", i32p), ("row0", i32p), ("F", C.c_int32),
                 ("need", i32p), ("out_rows", C.c_int32), ("ldo", C.c_int32), ("out", C.c_void_p), ("cn", f32p), ("pp_out", f32p)]
+
+
+_LATE_SIGNATURES["pk_diag_skinny_gemm"] = [C.POINTER(PkSkinnyDiag)]
 
 
 SKINNY_EPI = {"bias": 0, "act": 1, "cell": 2}
@@ -1069,14 +1125,7 @@ def diag_skinny_gemm(epi, X, W, bias=None, bf16=False, gi=None, gi_row=None, c=N
     N = W.shape[0] // 4 if epi == "cell" else W.shape[0]
     F = int(F) if epi == "act" else 1
     rows = B * F + pad_rows
-    keep = [X, W]
-
-    def opt(a, dt=np.float32):
-        if a is None:
-            return None
-        a = _c(a, dt)
-        keep.append(a)
-        return a.ctypes.data_as(f32p if dt == np.float32 else i32p)
+    opt = _Keep(X, W).opt
 
     d = PkSkinnyDiag()
     d.bf16, d.epi, d.B, d.N, d.K = int(bool(bf16)), e, B, N, K
@@ -1099,9 +1148,7 @@ def diag_skinny_gemm(epi, X, W, bias=None, bf16=False, gi=None, gi_row=None, c=N
     d.out_rows, d.ldo, d.out = rows, ld, out.ctypes.data_as(C.c_void_p)
     d.cn = cn.ctypes.data_as(f32p) if cn is not None else None
     d.pp_out = pp.ctypes.data_as(f32p) if pp is not None else None
-    L = lib()
-    L.pk_diag_skinny_gemm.argtypes = [C.POINTER(PkSkinnyDiag)]
-    check(L.pk_diag_skinny_gemm(C.byref(d)))
+    check(lib().pk_diag_skinny_gemm(C.byref(d)))
     if not half and epi != "bias":
         out = np.ascontiguousarray(out[:, sigma16(N)])
     return dict(out=out, cn=cn, pp=pp)
@@ -1121,11 +1168,17 @@ class PkTdtDecideDiag(C.Structure):
                    ("score_lab", f32p), ("score_dur", f32p), ("score_rows", C.c_int64)])
 
 
+_LATE_SIGNATURES["pk_diag_tdt_decide"] = [C.POINTER(PkTdtDecideDiag), C.POINTER(C.c_int)]
+
+
 class PkCtcGreedyDiag(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("B", "T", "n", "ld", "blank", "pitch", "out_rows")]
                 + [("n_frames", i32p), ("logits", f32p), ("lp_rows", C.c_int64), ("lp", f32p), ("best_idx", i32p), ("best_lp", f32p), ("best_idx2", i32p), ("best_lp2", f32p),
                    ("ids", i32p), ("lens", i32p), ("start", i32p), ("end", i32p), ("conf", f32p),
                    ("trie_off", i32p), ("trie_tok", i32p), ("trie_node", i32p), ("trie_nodes", C.c_int32), ("boost", C.c_float)])
+
+
+_LATE_SIGNATURES["pk_diag_ctc_greedy"] = [C.POINTER(PkCtcGreedyDiag)]
 
 
 TDT_KERNELS = ("exact", "fast", "boost", "score")                  # PK_DIAG_TDT_KERNEL
@@ -1225,9 +1278,7 @@ def diag_tdt_decide(sc, logits, hn, cn, st, pad_rows=3, guard=32):
                 setattr(d, k, _f(out[k]))
                 d.score_rows = out[k].shape[0]
     form = C.c_int(-1)
-    L = lib()
-    L.pk_diag_tdt_decide.argtypes = [C.POINTER(PkTdtDecideDiag), C.POINTER(C.c_int)]
-    check(L.pk_diag_tdt_decide(C.byref(d), C.byref(form)))
+    check(lib().pk_diag_tdt_decide(C.byref(d), C.byref(form)))
     if "z" in out and not sc.get("h_bf16"):
         body = out["z"][: B * F * J].reshape(B * F, J)[:, sigma16(J)]
         out["z"] = np.concatenate([body.reshape(-1), out["z"][B * F * J:]])
@@ -1245,6 +1296,9 @@ class PkTdtBeamStepDiag(C.Structure):
                 + [("lm", C.c_void_p), ("alpha", C.c_float), ("beta", C.c_float), ("lmstate", i32p), ("lmv", f32p), ("lab_ls", i32p), ("lab_lm", f32p)]
                 + [("ids", i32p), ("start", i32p), ("end", i32p), ("dur_idx", i32p), ("conf", f32p), ("lens", i32p), ("out_score", f32p), ("ok", i32p),
                    ("out_lm", f32p)])
+
+
+_LATE_SIGNATURES["pk_diag_tdt_beam_step"] = [C.POINTER(PkTdtBeamStepDiag)]
 
 
 TDT_BEAM_STEP_SCALARS = ("B", "W", "K", "Kd", "N", "V", "D", "blank", "max_tokens")
@@ -1302,9 +1356,7 @@ def diag_tdt_beam_step(sc, st, logits, step, init=False, trace=False, lm=None, a
         setattr(d, k, a.ctypes.data_as(ty))
     if lm is not None:
         d.lm, d.alpha, d.beta = lm._h, float(alpha), float(beta)
-    L = lib()
-    L.pk_diag_tdt_beam_step.argtypes = [C.POINTER(PkTdtBeamStepDiag)]
-    check(L.pk_diag_tdt_beam_step(C.byref(d)))
+    check(lib().pk_diag_tdt_beam_step(C.byref(d)))
     return st
 
 
@@ -1334,17 +1386,13 @@ def diag_ctc_greedy(logits, n, blank, B=None, T=0, n_frames=None, pitch=None, tr
         off, tok, node, boost = trie
         keep = [_c(off, np.int32), _c(tok if len(tok) else [0], np.int32), _c(node if len(node) else [0], np.int32)]
         d.trie_off, d.trie_tok, d.trie_node, d.trie_nodes, d.boost = _i(keep[0]), _i(keep[1]), _i(keep[2]), len(off) - 1, float(boost)
-    L = lib()
-    L.pk_diag_ctc_greedy.argtypes = [C.POINTER(PkCtcGreedyDiag)]
-    check(L.pk_diag_ctc_greedy(C.byref(d)))
+    check(lib().pk_diag_ctc_greedy(C.byref(d)))
     return o
 
 
 def diag_pred_cache(on):
     """pk_diag_pred_cache: prediction-net caching of the per-phase decode loop on / off (test switch, process-wide, default on)."""
-    L = lib()
-    L.pk_diag_pred_cache.argtypes = [C.c_int]
-    check(L.pk_diag_pred_cache(int(on)))
+    check(lib().pk_diag_pred_cache(int(on)))
 
 
 def diag_ffn_bf16_smallm(x, gamma, beta, W1, b1, W2, b2, act_tiles, eps=1e-5):
@@ -1353,9 +1401,7 @@ def diag_ffn_bf16_smallm(x, gamma, beta, W1, b1, W2, b2, act_tiles, eps=1e-5):
     M, d = x.shape
     f = W1.shape[0]
     out = np.empty((M, d), np.float32)
-    L = lib()
-    L.pk_diag_ffn_bf16_smallm.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_float, f32p, f32p, f32p, f32p, C.c_int, f32p]
-    check(L.pk_diag_ffn_bf16_smallm(M, d, f, _f(x), _f(gamma), _f(beta), eps, _f(W1), _f(b1), _f(W2), _f(b2), int(act_tiles), _f(out)))
+    check(lib().pk_diag_ffn_bf16_smallm(M, d, f, _f(x), _f(gamma), _f(beta), eps, _f(W1), _f(b1), _f(W2), _f(b2), int(act_tiles), _f(out)))
     return out
 
 
@@ -1367,10 +1413,8 @@ def diag_glu_dwconv_bf16(A, W, bias, cache_in, has_cache, dw_w, dw_bias, bn_mean
     ps = [_c(v) for v in (dw_w, dw_bias, bn_mean, bn_rstd, bn_g, bn_b)]
     g, b = (_c(gamma), _c(beta)) if gamma is not None else (None, None)
     out = np.empty((M, d), np.float32); cache_out = np.empty((S, 8, d), np.float32)
-    L = lib()
-    L.pk_diag_glu_dwconv_bf16.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_float, f32p, f32p, f32p, C.c_int] + [f32p] * 6 + [C.c_int, f32p, f32p]
-    check(L.pk_diag_glu_dwconv_bf16(S, c, d, _f(A), _f(g) if g is not None else None, _f(b) if b is not None else None, eps, _f(W), _f(bias), _f(cache_in),
-                                    int(has_cache), *[_f(v) for v in ps], int(fused), _f(out), _f(cache_out)))
+    check(lib().pk_diag_glu_dwconv_bf16(S, c, d, _f(A), _f(g) if g is not None else None, _f(b) if b is not None else None, eps, _f(W), _f(bias), _f(cache_in),
+                                        int(has_cache), *[_f(v) for v in ps], int(fused), _f(out), _f(cache_out)))
     return out, cache_out
 
 
@@ -1904,6 +1948,9 @@ class PkSmallmGemmDiag(C.Structure):
                 + [("ldo", C.c_int64), ("out_words", C.c_int64), ("out", f32p), ("form", C.c_int32)])
 
 
+_LATE_SIGNATURES["pk_diag_gemm_smallm"] = [C.POINTER(PkSmallmGemmDiag)]
+
+
 SMALLM_KERNELS = ("chain", "rt2", "ln")
 
 
@@ -1915,10 +1962,7 @@ def smallm_form(v):
 
 def diag_gemm_smallm_forms():
     """pk_diag_gemm_smallm_forms: every form launch_gemm_smallm can take, as smallm_form tuples.  Host arithmetic."""
-    n = lib().pk_diag_gemm_smallm_forms(None, 0)
-    out = np.zeros(n, np.int32)
-    lib().pk_diag_gemm_smallm_forms(_i(out), n)
-    return [smallm_form(int(v)) for v in out]
+    return _forms("pk_diag_gemm_smallm_forms", smallm_form)
 
 
 def diag_gemm_smallm(A, W, bias=None, epi="none", resid=None, alpha=1.0, w_sig=False, a_sigma=False, sigma_cols=0, remap=None, ldo=None, out_words=None,
@@ -1932,20 +1976,11 @@ def diag_gemm_smallm(A, W, bias=None, epi="none", resid=None, alpha=1.0, w_sig=F
     K = int(lda_cols) if lda_cols is not None else lda
     N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
     assert W.shape[1] == K
-    keep = [A, W]
-
-    def opt(a):
-        if a is None:
-            return None
-        a = _c(a)
-        keep.append(a)
-        return _f(a)
-
+    opt = _Keep(A, W).opt
     d = PkSmallmGemmDiag()
     d.M, d.N, d.K, d.epi, d.w_sig, d.a_sigma, d.sigma_cols, d.fused = M, N, K, EPI[epi], int(bool(w_sig)), int(bool(a_sigma)), int(sigma_cols), int(bool(fused))
     d.A, d.lda, d.W, d.bias, d.resid, d.alpha = _f(A), lda, _f(W), opt(bias), opt(resid), alpha
-    if remap is not None:
-        d.remap_rows, d.remap_gs, d.remap_rs, d.remap_cs = (int(v) for v in remap)
+    _set_remap(d, remap)
     d.eps = eps
     if ln is not None:
         d.ln_g, d.ln_b = opt(ln[0]), opt(ln[1])
@@ -1960,14 +1995,11 @@ def diag_gemm_smallm(A, W, bias=None, epi="none", resid=None, alpha=1.0, w_sig=F
         d.dw, d.dw_c, d.dw_has_cache, d.dw_out_sigma, d.cache_streams = 1, int(dw["c"]), int(bool(dw["has_cache"])), int(bool(dw.get("out_sigma"))), ns
         d.cache_in, d.cache_out = opt(dw["cache_in"]), cache_out.ctypes.data_as(f32p)
         d.dw_w, d.dw_bias, d.bn_mean, d.bn_rstd, d.bn_g, d.bn_b = (opt(dw[k]) for k in ("w", "bias", "bn_mean", "bn_rstd", "bn_g", "bn_b"))
-    d.ldo = int(ldo) if ldo is not None else N
-    d.out_words = int(out_words) if out_words is not None else M * d.ldo
+    _out_words_default(d, M, N, ldo, out_words)
     out = np.zeros(d.out_words, np.uint32)
     d.out = out.ctypes.data_as(f32p)
     d.form = -1
-    L = lib()
-    L.pk_diag_gemm_smallm.argtypes = [C.POINTER(PkSmallmGemmDiag)]
-    check(L.pk_diag_gemm_smallm(C.byref(d)))
+    check(lib().pk_diag_gemm_smallm(C.byref(d)))
     return dict(out=out, form=smallm_form(d.form), pre_out=pre_out, cache_out=cache_out)
 
 
@@ -1977,9 +2009,7 @@ def diag_sigma_copy(src, K=None):
     rows, ld = src.shape
     K = ld if K is None else int(K)
     dst = np.empty(rows * K, np.float32)
-    L = lib()
-    L.pk_diag_sigma_copy.argtypes = [f32p, C.c_int64, C.c_int, C.c_int64, f32p]
-    check(L.pk_diag_sigma_copy(_f(src), rows, K, ld, _f(dst)))
+    check(lib().pk_diag_sigma_copy(_f(src), rows, K, ld, _f(dst)))
     return dst
 
 
@@ -1987,9 +2017,7 @@ def diag_layernorm_sigma(x, g, b, eps=1e-5):
     """pk_diag_layernorm_sigma: launch_layernorm mode 2 -- LayerNorm with the output columns in the sigma order."""
     x, g, b = _c(x), _c(g), _c(b)
     y = np.empty_like(x)
-    L = lib()
-    L.pk_diag_layernorm_sigma.argtypes = [f32p, C.c_int64, C.c_int, f32p, f32p, C.c_float, f32p]
-    check(L.pk_diag_layernorm_sigma(_f(x), x.shape[0], x.shape[1], _f(g), _f(b), eps, _f(y)))
+    check(lib().pk_diag_layernorm_sigma(_f(x), x.shape[0], x.shape[1], _f(g), _f(b), eps, _f(y)))
     return y
 
 
@@ -1997,9 +2025,7 @@ def diag_layernorm2(x, g1, b1, g2, b2, y2_sigma=False, eps=1e-5):
     """pk_diag_layernorm2: (y1 = LN(x; g1, b1), y2 = LN(y1; g2, b2)) in one launch; y2_sigma: y2's columns in the sigma order."""
     x, g1, b1, g2, b2 = (_c(v) for v in (x, g1, b1, g2, b2))
     y1, y2 = np.empty_like(x), np.empty_like(x)
-    L = lib()
-    L.pk_diag_layernorm2.argtypes = [f32p, C.c_int64, C.c_int] + [f32p] * 4 + [C.c_float, C.c_int, f32p, f32p]
-    check(L.pk_diag_layernorm2(_f(x), x.shape[0], x.shape[1], _f(g1), _f(b1), _f(g2), _f(b2), eps, int(bool(y2_sigma)), _f(y1), _f(y2)))
+    check(lib().pk_diag_layernorm2(_f(x), x.shape[0], x.shape[1], _f(g1), _f(b1), _f(g2), _f(b2), eps, int(bool(y2_sigma)), _f(y1), _f(y2)))
     return y1, y2
 
 
@@ -2008,6 +2034,9 @@ class PkLayernormDiag(C.Structure):
                 + [(k, f32p) for k in ("x", "g1", "b1", "g2", "b2")]
                 + [("y", C.POINTER(C.c_uint32)), ("y_words", C.c_int64), ("y2", C.POINTER(C.c_uint32)), ("y2_words", C.c_int64),
                    ("stats", C.POINTER(C.c_uint32)), ("stats_words", C.c_int64), ("form", C.c_int32)])
+
+
+_LATE_SIGNATURES["pk_diag_layernorm_form"] = [C.POINTER(PkLayernormDiag)]
 
 
 LN_LAUNCHERS = ("norm", "norm2", "stats", "then_stats")       # PK_DIAG_LN_NORM .. PK_DIAG_LN_THEN_STATS
@@ -2021,18 +2050,13 @@ def ln_form(v):
 
 def diag_layernorm_forms():
     """pk_diag_layernorm_forms: every form the four LayerNorm launchers can take, as ln_form tuples.  Host arithmetic."""
-    n = lib().pk_diag_layernorm_forms(None, 0)
-    out = np.zeros(n, np.int32)
-    lib().pk_diag_layernorm_forms(_i(out), n)
-    return [ln_form(int(v)) for v in out]
+    return _forms("pk_diag_layernorm_forms", ln_form)
 
 
 def diag_layernorm_form_of(launcher, rows, d):
     """pk_diag_layernorm_form_of: the form `launcher` (one of LN_LAUNCHERS) takes for rows x d.  Host arithmetic."""
     form = C.c_int32(-1)
-    L = lib()
-    L.pk_diag_layernorm_form_of.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
-    check(L.pk_diag_layernorm_form_of(LN_LAUNCHERS.index(launcher), int(rows), int(d), C.byref(form)))
+    check(lib().pk_diag_layernorm_form_of(LN_LAUNCHERS.index(launcher), int(rows), int(d), C.byref(form)))
     return ln_form(form.value)
 
 
@@ -2043,15 +2067,7 @@ def diag_layernorm_form(launcher, x, g1=None, b1=None, g2=None, b2=None, eps=1e-
     it: the payload followed by pad_words words, SKINNY_FILL32 wherever nothing was stored; a bf16 buffer holds two elements to a word)."""
     x = _c(x)
     rows, d = x.shape
-    keep = [x]
-
-    def opt(a):
-        if a is None:
-            return None
-        a = _c(a)
-        keep.append(a)
-        return _f(a)
-
+    opt = _Keep(x).opt
     a = PkLayernormDiag()
     a.launcher, a.d, a.mode, a.in_place, a.rows, a.eps = LN_LAUNCHERS.index(launcher), d, int(mode), int(bool(in_place)), rows, eps
     a.x, a.g1, a.b1, a.g2, a.b2 = _f(x), opt(g1), opt(b1), opt(g2), opt(b2)
@@ -2071,9 +2087,7 @@ def diag_layernorm_form(launcher, x, g1=None, b1=None, g2=None, b2=None, eps=1e-
     if launcher in ("stats", "then_stats"):
         buf("stats", 2 * rows)
     a.form = -1
-    L = lib()
-    L.pk_diag_layernorm_form.argtypes = [C.POINTER(PkLayernormDiag)]
-    check(L.pk_diag_layernorm_form(C.byref(a)))
+    check(lib().pk_diag_layernorm_form(C.byref(a)))
     out["form"] = ln_form(a.form)
     return out
 
@@ -2083,6 +2097,9 @@ class PkGemmTileDiag(C.Structure):
                 + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),
                    ("remap_rows", C.c_int32), ("remap_gs", C.c_int64), ("remap_rs", C.c_int64), ("remap_cs", C.c_int64),
                    ("ln_g", f32p), ("ln_b", f32p), ("eps", C.c_float), ("ldo", C.c_int64), ("out_words", C.c_int64), ("out", f32p), ("form", C.c_int32)])
+
+
+_LATE_SIGNATURES["pk_diag_gemm_tile"] = [C.POINTER(PkGemmTileDiag)]
 
 
 def tile_form(v):
@@ -2097,19 +2114,14 @@ def tile_form(v):
 
 def diag_gemm_tile_forms():
     """pk_diag_gemm_tile_forms: every form launch_gemm can take on the tile kernels, as tile_form tuples.  Host arithmetic."""
-    n = lib().pk_diag_gemm_tile_forms(None, 0)
-    out = np.zeros(n, np.int32)
-    lib().pk_diag_gemm_tile_forms(_i(out), n)
-    return [tile_form(int(v)) for v in out]
+    return _forms("pk_diag_gemm_tile_forms", tile_form)
 
 
 def diag_gemm_tile_form(M, N, K, lda=None, ldw=None, epi="none", ln=False):
     """pk_diag_gemm_tile_form: the form pk_diag_gemm_tile would launch for this product (ln: with the LayerNorm fold).  Host arithmetic; the refusals
     of pk_diag_gemm_tile that depend on the shape alone raise here too."""
     form = C.c_int32(-1)
-    L = lib()
-    L.pk_diag_gemm_tile_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32)]
-    check(L.pk_diag_gemm_tile_form(M, N, K, K if lda is None else lda, K if ldw is None else ldw, EPI[epi], int(bool(ln)), C.byref(form)))
+    check(lib().pk_diag_gemm_tile_form(M, N, K, K if lda is None else lda, K if ldw is None else ldw, EPI[epi], int(bool(ln)), C.byref(form)))
     return tile_form(form.value)
 
 
@@ -2123,44 +2135,23 @@ def diag_gemm_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, sigma_col
     M, K = A.shape
     N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
     assert W.shape[1] == K
-
-    def pitched(a, ld):
-        if ld is None or ld == a.shape[1]:
-            return a
-        p = np.zeros((a.shape[0], int(ld)), np.float32)
-        n = min(a.shape[1], int(ld))
-        p[:, :n] = a[:, :n]
-        return p
-
     d = PkGemmTileDiag()
-    A, W = pitched(A, lda), pitched(W, ldw)
-    keep = [A, W]
-
-    def opt(a):
-        if a is None:
-            return None
-        a = _c(a)
-        keep.append(a)
-        return _f(a)
-
+    A, W = _pitched(A, lda), _pitched(W, ldw)
+    opt = _Keep(A, W).opt
     d.M, d.N, d.K, d.epi, d.sigma_cols = M, N, K, EPI[epi], int(sigma_cols)
     d.A, d.lda, d.W, d.ldw, d.bias, d.alpha = _f(A), A.shape[1], _f(W), W.shape[1], opt(bias), alpha
     if resid is not None:
-        resid = pitched(_c(resid), ldr)
+        resid = _pitched(_c(resid), ldr)
         d.resid, d.ldr = opt(resid), resid.shape[1]
-    if remap is not None:
-        d.remap_rows, d.remap_gs, d.remap_rs, d.remap_cs = (int(v) for v in remap)
+    _set_remap(d, remap)
     d.eps = eps
     if ln is not None:
         d.ln_g, d.ln_b = opt(ln[0]), opt(ln[1])
-    d.ldo = int(ldo) if ldo is not None else N
-    d.out_words = int(out_words) if out_words is not None else M * d.ldo
+    _out_words_default(d, M, N, ldo, out_words)
     out = np.zeros(max(d.out_words, 1), np.uint32)
     d.out = out.ctypes.data_as(f32p)
     d.form = -1
-    L = lib()
-    L.pk_diag_gemm_tile.argtypes = [C.POINTER(PkGemmTileDiag)]
-    check(L.pk_diag_gemm_tile(C.byref(d)))
+    check(lib().pk_diag_gemm_tile(C.byref(d)))
     return dict(out=out[:d.out_words], form=tile_form(d.form))
 
 
@@ -2169,6 +2160,10 @@ class PkGemmBf16TileDiag(C.Structure):
                 + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),
                    ("remap_rows", C.c_int32), ("remap_gs", C.c_int64), ("remap_rs", C.c_int64), ("remap_cs", C.c_int64),
                    ("ldo", C.c_int64), ("out_words", C.c_int64), ("out", C.POINTER(C.c_uint32)), ("form", C.c_int32)])
+
+
+_LATE_SIGNATURES["pk_diag_gemm_bf16_tile_form"] = [C.POINTER(PkGemmBf16TileDiag)]
+_LATE_SIGNATURES["pk_diag_gemm_bf16_tile"] = [C.POINTER(PkGemmBf16TileDiag)]
 
 
 BF16_EPILOGUES = ("lds", "direct", "persist", "resid_reg")
@@ -2183,10 +2178,7 @@ def bf16_form(v):
 
 def diag_gemm_bf16_tile_forms():
     """pk_diag_gemm_bf16_tile_forms: every form launch_gemm_bf16 can take on the tile kernels, as bf16_form tuples.  Host arithmetic."""
-    n = lib().pk_diag_gemm_bf16_tile_forms(None, 0)
-    out = np.zeros(n, np.int32)
-    lib().pk_diag_gemm_bf16_tile_forms(_i(out), n)
-    return [bf16_form(int(v)) for v in out]
+    return _forms("pk_diag_gemm_bf16_tile_forms", bf16_form)
 
 
 def _bf16_tile_args(M, N, K, epi, a16, bias, resid, alpha, lda, ldw, ldo, ldr, sigma_cols, remap, fast_act, out_bf16, out_blocked, a_blocked, out_words):
@@ -2194,13 +2186,8 @@ def _bf16_tile_args(M, N, K, epi, a16, bias, resid, alpha, lda, ldw, ldo, ldr, s
     d.M, d.N, d.K, d.epi, d.sigma_cols = M, N, K, EPI[epi], int(sigma_cols)
     d.a_bf16, d.a_blocked, d.out_bf16, d.out_blocked, d.fast_act = (int(bool(v)) for v in (a16, a_blocked, out_bf16, out_blocked, fast_act))
     d.lda, d.ldw, d.ldr, d.alpha = int(lda or K), int(ldw or K), int(ldr or N), alpha
-    if remap is not None:
-        d.remap_rows, d.remap_gs, d.remap_rs, d.remap_cs = (int(v) for v in remap)
-    d.ldo = int(ldo) if ldo is not None else N
-    if out_words is None:
-        rows = (M + 31) // 32 * 32 if out_blocked else M
-        out_words = (rows * d.ldo + 1) // 2 if out_bf16 else rows * d.ldo
-    d.out_words = int(out_words)
+    _set_remap(d, remap)
+    _out_words_default(d, M, N, ldo, out_words, half=out_bf16, blocked=out_blocked)
     d.form = -1
     return d
 
@@ -2213,9 +2200,7 @@ def diag_gemm_bf16_tile_form(M, N, K, epi="none", a16=False, bias=True, alpha=1.
     one = np.zeros(1, np.float32)                                   # (looked at for null only)
     d.bias = _f(one) if bias else None
     d.resid = _f(one) if epi == "resid" else None
-    L = lib()
-    L.pk_diag_gemm_bf16_tile_form.argtypes = [C.POINTER(PkGemmBf16TileDiag)]
-    check(L.pk_diag_gemm_bf16_tile_form(C.byref(d)))
+    check(lib().pk_diag_gemm_bf16_tile_form(C.byref(d)))
     return bf16_form(d.form)
 
 
@@ -2229,31 +2214,17 @@ def diag_gemm_bf16_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, a16=
     M, K = A.shape
     N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
     assert W.shape[1] == K
-
-    def pitched(a, ld):
-        if ld is None or ld == a.shape[1]:
-            return a
-        p = np.zeros((a.shape[0], int(ld)), np.float32)
-        n = min(a.shape[1], int(ld))
-        p[:, :n] = a[:, :n]
-        return p
-
-    A, W = pitched(A, lda), pitched(W, ldw)
+    A, W = _pitched(A, lda), _pitched(W, ldw)
     d = _bf16_tile_args(M, N, K, epi, a16, bias is not None, resid, alpha, A.shape[1], W.shape[1], ldo, ldr, sigma_cols, remap, fast_act, out_bf16,
                         out_blocked, a_blocked, out_words)
-    keep = [A, W]
-    d.A, d.W = _f(A), _f(W)
-    if bias is not None:
-        keep.append(_c(bias))
-        d.bias = _f(keep[-1])
+    opt = _Keep(A, W).opt
+    d.A, d.W, d.bias = _f(A), _f(W), opt(bias)
     if resid is not None:
-        keep.append(pitched(_c(resid), ldr))
-        d.resid, d.ldr = _f(keep[-1]), keep[-1].shape[1]
+        resid = _pitched(_c(resid), ldr)
+        d.resid, d.ldr = opt(resid), resid.shape[1]
     out = np.zeros(max(d.out_words, 1), np.uint32)
     d.out = out.ctypes.data_as(C.POINTER(C.c_uint32))
-    L = lib()
-    L.pk_diag_gemm_bf16_tile.argtypes = [C.POINTER(PkGemmBf16TileDiag)]
-    check(L.pk_diag_gemm_bf16_tile(C.byref(d)))
+    check(lib().pk_diag_gemm_bf16_tile(C.byref(d)))
     return dict(out=out[:d.out_words], form=bf16_form(d.form))
 
 
@@ -2269,6 +2240,10 @@ class PkGemmSmallmBf16Diag(C.Structure):
                 + [("ldo", C.c_int64), ("out_words", C.c_int64), ("out", _u32p), ("form", C.c_int32)])
 
 
+_LATE_SIGNATURES["pk_diag_gemm_smallm_bf16_form"] = [C.POINTER(PkGemmSmallmBf16Diag)]
+_LATE_SIGNATURES["pk_diag_gemm_smallm_bf16"] = [C.POINTER(PkGemmSmallmBf16Diag)]
+
+
 SMALLM_BF16_FIELDS = ("epi", "steps", "rt", "rvalid", "a16", "ln", "ct", "wt", "dw", "at", "al", "pre")
 
 
@@ -2282,10 +2257,7 @@ def smallm_bf16_form(v):
 
 def diag_gemm_smallm_bf16_forms():
     """pk_diag_gemm_smallm_bf16_forms: every form launch_gemm_smallm_bf16 can take, as smallm_bf16_form tuples.  Host arithmetic."""
-    n = lib().pk_diag_gemm_smallm_bf16_forms(None, 0)
-    out = np.zeros(n, np.int32)
-    lib().pk_diag_gemm_smallm_bf16_forms(_i(out), n)
-    return [smallm_bf16_form(int(v)) for v in out]
+    return _forms("pk_diag_gemm_smallm_bf16_forms", smallm_bf16_form)
 
 
 def _smallm_bf16_args(M, N, K, epi, a16, alpha, lda, ldw, ldo, ldr, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place, eps, pre_ldo, pre_out_words,
@@ -2293,16 +2265,13 @@ def _smallm_bf16_args(M, N, K, epi, a16, alpha, lda, ldw, ldo, ldr, out_bf16, ou
     d = PkGemmSmallmBf16Diag()
     d.M, d.N, d.K, d.epi = M, N, K, EPI[epi]
     d.a_bf16, d.out_bf16, d.out_t8, d.a_t8, d.fast_act, d.w_tiles, d.resid_in_place = (int(bool(v)) for v in (a16, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place))
-    d.ldo = int(ldo) if ldo is not None else N
+    _out_words_default(d, M, N, ldo, out_words, half=out_bf16)
     d.lda, d.ldw, d.ldr, d.alpha, d.eps = int(lda or K), int(ldw or K), int(ldr or (d.ldo if resid_in_place else N)), alpha, eps
     d.pre_ldo = int(pre_ldo or K)
     d.pre_out_words = int(pre_out_words) if pre_out_words is not None else M * d.pre_ldo
     if dw_c:
         d.dw, d.dw_c, d.dw_has_cache = 1, int(dw_c), int(bool(has_cache))
         d.cache_streams = int(cache_streams) if cache_streams is not None else -(-M // int(dw_c))
-    if out_words is None:
-        out_words = (M * d.ldo + 1) // 2 if out_bf16 else M * d.ldo
-    d.out_words = int(out_words)
     d.form = -1
     return d
 
@@ -2323,9 +2292,7 @@ def diag_gemm_smallm_bf16_form(M, N, K, epi="none", a16=False, bias=True, alpha=
     if pre:
         d.pre_g = d.pre_b = _f(one)
         d.pre_out = one32.ctypes.data_as(C.POINTER(C.c_uint32))
-    L = lib()
-    L.pk_diag_gemm_smallm_bf16_form.argtypes = [C.POINTER(PkGemmSmallmBf16Diag)]
-    check(L.pk_diag_gemm_smallm_bf16_form(C.byref(d)))
+    check(lib().pk_diag_gemm_smallm_bf16_form(C.byref(d)))
     return smallm_bf16_form(d.form)
 
 
@@ -2342,32 +2309,14 @@ def diag_gemm_smallm_bf16(A, W, bias=None, epi="none", resid=None, alpha=1.0, a1
     M, K = A.shape
     N = W.shape[0] // 2 if epi == "glu" else W.shape[0]
     assert W.shape[1] == K
-
-    def pitched(a, ld):
-        if ld is None or ld == a.shape[1]:
-            return a
-        p = np.zeros((a.shape[0], int(ld)), np.float32)
-        n = min(a.shape[1], int(ld))
-        p[:, :n] = a[:, :n]
-        return p
-
-    A, W = pitched(A, lda), pitched(W, ldw)
+    A, W = _pitched(A, lda), _pitched(W, ldw)
     d = _smallm_bf16_args(M, N, K, epi, a16, alpha, A.shape[1], W.shape[1], ldo, ldr, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place, eps, pre_ldo,
                           pre_out_words, dw["c"] if dw else 0, dw["has_cache"] if dw else False, dw.get("cache_streams") if dw else None, out_words)
-    keep = [A, W]
+    opt = _Keep(A, W).opt
     u32p = C.POINTER(C.c_uint32)
-
-    def opt(a):
-        if a is None:
-            return None
-        a = _c(a)
-        keep.append(a)
-        return _f(a)
-
     d.A, d.W, d.bias = _f(A), _f(W), opt(bias)
     if resid is not None:
-        keep.append(pitched(_c(resid), d.ldr))
-        d.resid = _f(keep[-1])
+        d.resid = opt(_pitched(_c(resid), d.ldr))
     if ln is not None:
         d.ln_g, d.ln_b = opt(ln[0]), opt(ln[1])
     pre_out = None
@@ -2386,9 +2335,7 @@ def diag_gemm_smallm_bf16(A, W, bias=None, epi="none", resid=None, alpha=1.0, a1
             if buf is not None:
                 buf.fill(into.get("fill", 0))
         into.update(out=out, pre_out=pre_out, cache_out=cache_out, args=d)
-    L = lib()
-    L.pk_diag_gemm_smallm_bf16.argtypes = [C.POINTER(PkGemmSmallmBf16Diag)]
-    check(L.pk_diag_gemm_smallm_bf16(C.byref(d)))
+    check(lib().pk_diag_gemm_smallm_bf16(C.byref(d)))
     return dict(out=out[:d.out_words], form=smallm_bf16_form(d.form), pre_out=pre_out, cache_out=cache_out)
 
 
@@ -2398,9 +2345,7 @@ def diag_tile_copy_bf16(src, K=None):
     rows, ld = src.shape
     K = ld if K is None else int(K)
     dst = np.empty(rows * K, np.uint16)
-    L = lib()
-    L.pk_diag_tile_copy_bf16.argtypes = [f32p, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_uint16)]
-    check(L.pk_diag_tile_copy_bf16(_f(src), rows, K, ld, dst.ctypes.data_as(C.POINTER(C.c_uint16))))
+    check(lib().pk_diag_tile_copy_bf16(_f(src), rows, K, ld, dst.ctypes.data_as(C.POINTER(C.c_uint16))))
     return dst
 
 
