@@ -1250,6 +1250,11 @@ pk_status pk_diag_mel(int n_mels, int normalize, int stft_window_centered, int p
 #define PK_DIAG_CONV_VARIANT_WORDS 17
 pk_status pk_diag_conv_variants(const pk_model *m, int B, int Tm, const int32_t *n_mel_frames, int stream_c, int32_t *out);
 int pk_diag_conv_instantiations(int32_t *out, int cap_rows);
+/* The sequence lengths the model's two resident relative-position table sets were built for: out[0] the fp32 set's, out[1] the bf16 attention's
+ * (0: not built yet).  A set holds 2 T - 1 rows per layer, is rebuilt when a call's longest utterance exceeds T, and serves every shorter one from a
+ * window of its rows; limited-context attention (pk_model_set_attention_context) uses neither.  Reads two host integers: no device is needed.
+ * (tests/test_gpu_call_history.py asserts with it that a call ran on a table built for a longer one.) */
+pk_status pk_diag_pos_table_frames(const pk_model *m, int32_t out[2]);
 /* ONE launch of a skinny product of the TDT / RNNT decode loop (kernels/decode_gemv.hip, kernels/decode_gemv_bf16.hip; kernels.hpp SkinnyArgs).
  * Every operand is given in its NATURAL layout as fp32 and packed here by the functions the loader packs with (csrc/dec_pack.hpp): fp32 mode = the
  * sigma K order of X / W / X2 / W2; bf16 mode = X / X2 rounded to bf16 (RNE), W / W2 in the kernel's per-lane tile order, rounded to bf16.
@@ -1486,6 +1491,8 @@ pk_status pk_diag_gemm_tile_form(int M, int N, int K, int64_t lda, int64_t ldw, 
  *            is a NaN (fp32 0x7FC5A5A5, bf16 0x7FC5).
  *   a_blocked: A (a_bf16) is staged in the blocked hand-off layout -- block (row / 32, k / 16) holds 32 x 16 bf16 row-major, blocks ordered
  *            [row / 32][lda / 16], rows rounded up to 32 (the rows past M are NaN); lda % 16 == 0.
+ *   one_form: GemmArgs's -- the product takes the register-staged 64 x 64 tile at every M (M <= 128 with K % 256 == 0 included, which is then no shape of
+ *            the small-M kernel); not with glu (PK_ERR_UNSUPPORTED).
  *   fast_act, out_bf16, out_blocked, sigma_cols, remap_*: GemmArgs's.  out_bf16: out holds bf16 rows [M][ldo] (out_blocked: blocks [ceil(M / 32)][ldo / 16],
  *            ldo % 16 == 0), two to a word.
  *   out (out_words 32-bit words: every offset the product may write lies inside) comes back WHOLE, exactly as the launch left it; its device buffer is
@@ -1516,6 +1523,7 @@ typedef struct pk_gemm_bf16_tile_diag {
     int32_t remap_rows; int64_t remap_gs, remap_rs, remap_cs;
     int64_t ldo, out_words; uint32_t *out;
     int32_t form;
+    int32_t one_form;
 } pk_gemm_bf16_tile_diag;
 pk_status pk_diag_gemm_bf16_tile(pk_gemm_bf16_tile_diag *a);
 int pk_diag_gemm_bf16_tile_forms(int32_t *out, int cap);
@@ -1528,6 +1536,7 @@ pk_status pk_diag_gemm_bf16_tile_form(pk_gemm_bf16_tile_diag *a);
  *            ((row / 8) (lda / 32) + k / 32) 256 + ((row % 8) + 8 (k / 8 % 4)) 8 + k % 8.
  *   w_tiles: a copy of the bf16 weights in the kernel's operand tiles is built on the device (launch_tile_copy_bf16, from W at its pitch) and handed over as
  *            GemmArgs::W_t16 when the weight rows are a multiple of 16; the launcher takes it for N % 16 == 0.
+ *   one_form: GemmArgs's -- gemm_smallm_bf16_applies refuses every product that sets it (PK_ERR_UNSUPPORTED).
  *   out_bf16 / out_t8 / fast_act: GemmArgs's.  out_bf16: out holds bf16 rows [M][ldo], two to a word (out_t8: 8-row tiles as above, ldo == N, N % 32 == 0).
  *   resid_in_place: the residual is staged INSIDE out (resid == out, ldr == ldo, as fc2 of a block runs); the rest of out holds the fill.
  *   ln_g / ln_b / eps: X = LayerNorm(A) folded into the product (fp32 rows, K = 256 * (1 .. 8; glu: .. 4)).
@@ -1571,6 +1580,7 @@ typedef struct pk_gemm_smallm_bf16_diag {
     const float *dw_w, *dw_bias, *bn_mean, *bn_rstd, *bn_g, *bn_b;
     int64_t ldo, out_words; uint32_t *out;
     int32_t form;
+    int32_t one_form;
 } pk_gemm_smallm_bf16_diag;
 pk_status pk_diag_gemm_smallm_bf16(pk_gemm_smallm_bf16_diag *a);
 int pk_diag_gemm_smallm_bf16_forms(int32_t *out, int cap);

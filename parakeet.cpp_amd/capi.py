@@ -351,6 +351,7 @@ _LATE_SIGNATURES = {
     "pk_group_set_input_rate": [C.c_void_p, C.c_int],
     "pk_diag_conv_variants": [C.c_void_p, C.c_int, C.c_int, i32p, C.c_int, i32p],
     "pk_diag_conv_instantiations": [i32p, C.c_int],
+    "pk_diag_pos_table_frames": [C.c_void_p, i32p],
     "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
                                        C.POINTER(C.c_int)],
     "pk_diag_relpos_attention_form": [C.c_int, C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, f32p, f32p,
@@ -2159,7 +2160,7 @@ class PkGemmBf16TileDiag(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("M", "N", "K", "epi", "sigma_cols", "a_bf16", "a_blocked", "out_bf16", "out_blocked", "fast_act")]
                 + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),
                    ("remap_rows", C.c_int32), ("remap_gs", C.c_int64), ("remap_rs", C.c_int64), ("remap_cs", C.c_int64),
-                   ("ldo", C.c_int64), ("out_words", C.c_int64), ("out", C.POINTER(C.c_uint32)), ("form", C.c_int32)])
+                   ("ldo", C.c_int64), ("out_words", C.c_int64), ("out", C.POINTER(C.c_uint32)), ("form", C.c_int32), ("one_form", C.c_int32)])
 
 
 _LATE_SIGNATURES["pk_diag_gemm_bf16_tile_form"] = [C.POINTER(PkGemmBf16TileDiag)]
@@ -2193,19 +2194,20 @@ def _bf16_tile_args(M, N, K, epi, a16, bias, resid, alpha, lda, ldw, ldo, ldr, s
 
 
 def diag_gemm_bf16_tile_form(M, N, K, epi="none", a16=False, bias=True, alpha=1.0, lda=None, ldw=None, ldo=None, ldr=None, sigma_cols=0, remap=None,
-                             fast_act=False, out_bf16=False, out_blocked=False, a_blocked=False, out_words=None):
+                             fast_act=False, out_bf16=False, out_blocked=False, a_blocked=False, out_words=None, one_form=False):
     """pk_diag_gemm_bf16_tile_form: the form pk_diag_gemm_bf16_tile would launch for this product.  Host arithmetic, no device; every refusal of
     pk_diag_gemm_bf16_tile raises here too."""
     d = _bf16_tile_args(M, N, K, epi, a16, bias, None, alpha, lda, ldw, ldo, ldr, sigma_cols, remap, fast_act, out_bf16, out_blocked, a_blocked, out_words)
     one = np.zeros(1, np.float32)                                   # (looked at for null only)
     d.bias = _f(one) if bias else None
     d.resid = _f(one) if epi == "resid" else None
+    d.one_form = int(bool(one_form))
     check(lib().pk_diag_gemm_bf16_tile_form(C.byref(d)))
     return bf16_form(d.form)
 
 
 def diag_gemm_bf16_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, a16=False, lda=None, ldw=None, ldo=None, ldr=None, sigma_cols=0, remap=None,
-                        fast_act=False, out_bf16=False, out_blocked=False, a_blocked=False, out_words=None):
+                        fast_act=False, out_bf16=False, out_blocked=False, a_blocked=False, out_words=None, one_form=False):
     """pk_diag_gemm_bf16_tile: one product of the bf16 tile GEMM family alone (include/parakeet_amd.h).  A [M][K], W [N or 2N][K], resid [M][N] dense fp32
     (the entry rounds W, and A with a16, to bf16); lda / ldw / ldr: the pitches they are staged at (NaN behind every row on the device); a_blocked: A staged
     in 32 x 16 blocks; remap = (rows, gs, rs, cs).  Returns dict(out = the WHOLE output buffer as uint32 words [out_words] exactly as the launch left it
@@ -2224,6 +2226,7 @@ def diag_gemm_bf16_tile(A, W, bias=None, epi="none", resid=None, alpha=1.0, a16=
         d.resid, d.ldr = opt(resid), resid.shape[1]
     out = np.zeros(max(d.out_words, 1), np.uint32)
     d.out = out.ctypes.data_as(C.POINTER(C.c_uint32))
+    d.one_form = int(bool(one_form))
     check(lib().pk_diag_gemm_bf16_tile(C.byref(d)))
     return dict(out=out[:d.out_words], form=bf16_form(d.form))
 
@@ -2237,7 +2240,7 @@ class PkGemmSmallmBf16Diag(C.Structure):
                 + [(k, C.c_int32) for k in ("dw", "dw_c", "dw_has_cache", "cache_streams")]
                 + [("cache_in", f32p), ("cache_out", _u32p)]
                 + [(k, f32p) for k in ("dw_w", "dw_bias", "bn_mean", "bn_rstd", "bn_g", "bn_b")]
-                + [("ldo", C.c_int64), ("out_words", C.c_int64), ("out", _u32p), ("form", C.c_int32)])
+                + [("ldo", C.c_int64), ("out_words", C.c_int64), ("out", _u32p), ("form", C.c_int32), ("one_form", C.c_int32)])
 
 
 _LATE_SIGNATURES["pk_diag_gemm_smallm_bf16_form"] = [C.POINTER(PkGemmSmallmBf16Diag)]
@@ -2278,7 +2281,7 @@ def _smallm_bf16_args(M, N, K, epi, a16, alpha, lda, ldw, ldo, ldr, out_bf16, ou
 
 def diag_gemm_smallm_bf16_form(M, N, K, epi="none", a16=False, bias=True, alpha=1.0, lda=None, ldw=None, ldo=None, ldr=None, out_bf16=False, out_t8=False,
                                a_t8=False, fast_act=False, w_tiles=True, resid_in_place=False, ln=False, pre=False, eps=1e-5, pre_ldo=None, pre_out_words=None,
-                               dw_c=0, has_cache=True, cache_streams=None, out_words=None):
+                               dw_c=0, has_cache=True, cache_streams=None, out_words=None, one_form=False):
     """pk_diag_gemm_smallm_bf16_form: the form pk_diag_gemm_smallm_bf16 would launch for this product (ln / pre / dw_c: with the folded norm, the norm in front,
     the conv tail).  Host arithmetic, no device; every refusal of pk_diag_gemm_smallm_bf16 that depends on the shape and the switches raises here too."""
     d = _smallm_bf16_args(M, N, K, epi, a16, alpha, lda, ldw, ldo, ldr, out_bf16, out_t8, a_t8, fast_act, w_tiles, resid_in_place, eps, pre_ldo, pre_out_words,
@@ -2292,6 +2295,7 @@ def diag_gemm_smallm_bf16_form(M, N, K, epi="none", a16=False, bias=True, alpha=
     if pre:
         d.pre_g = d.pre_b = _f(one)
         d.pre_out = one32.ctypes.data_as(C.POINTER(C.c_uint32))
+    d.one_form = int(bool(one_form))
     check(lib().pk_diag_gemm_smallm_bf16_form(C.byref(d)))
     return smallm_bf16_form(d.form)
 
@@ -2759,6 +2763,12 @@ class Model:
         if stream_c > 0:
             r.update(stream=(3, v[12], v[13], v[14], 0), stream_body=v[15], stream_fusable=bool(v[16]))
         return r
+
+    def pos_table_frames(self):
+        """pk_diag_pos_table_frames: (T the fp32 relative-position tables were built for, T of the bf16 attention's set); 0 = not built yet."""
+        out = np.zeros(2, np.int32)
+        check(lib().pk_diag_pos_table_frames(self._h, _i(out)))
+        return int(out[0]), int(out[1])
 
     def subsample(self, feats):
         feats = _c(feats)

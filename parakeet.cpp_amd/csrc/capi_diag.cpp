@@ -603,6 +603,13 @@ int pk_diag_conv_instantiations(int32_t *out, int cap_rows) {
     }
     return n;
 }
+pk_status pk_diag_pos_table_frames(const pk_model *h, int32_t out[2]) {
+    return guard([&] {
+        need(h && out, "model/out");
+        out[0] = h->m->pos32.T;
+        out[1] = h->m->pos16.T;
+    });
+}
 
 /* ---- one attention layer alone ------------------------------------------------------------------------------------------------------ */
 // The batch of an attention diagnostic: B utterances of T frames, or (lens) of lens[b] frames each, packed.  -> the frames of the batch; T

@@ -407,7 +407,8 @@ static GemmArgs bf16_tile_product(const pk_gemm_bf16_tile_diag *d, const char *w
     GemmArgs g{some, d->lda, some, d->ldw, d->bias ? some : nullptr, nullptr, d->ldo, epi == EPI_RESID ? some : nullptr, d->ldr, d->alpha, M, N, K};
     set_remap(g, *d);
     g.a_bf16 = d->a_bf16 ? 1 : 0; g.out_bf16 = d->out_bf16 ? 1 : 0; g.out_blocked = d->out_blocked ? 1 : 0; g.a_blocked = d->a_blocked ? 1 : 0;
-    g.fast_act = d->fast_act ? 1 : 0;
+    g.fast_act = d->fast_act ? 1 : 0; g.one_form = d->one_form ? 1 : 0;
+    if (g.one_form && epi == EPI_GLU) fail(PK_ERR_UNSUPPORTED, "%s: one_form with glu (the 64 x 64 tile has no GLU instantiation; Model::run_gemm refuses it too)", who);
     if (gemm_smallm_bf16_applies(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: M <= %d with K %% 256 == 0 runs on the small-M bf16 kernel (pk_diag_gemm_smallm_bf16)", who, kSmallMRowsBf16);
     if (const char *why = gemm_bf16_refusal(g, epi)) fail(PK_ERR_UNSUPPORTED, "%s: %s", who, why);
     if (g.out_bf16 && (g.remap_rows != 0 || (g.ldo & 3) != 0 || (g.N & 3) != 0 || g.sigma_cols != 0 || epi == EPI_RESID || epi == EPI_GLU))
@@ -488,12 +489,13 @@ static GemmArgs smallm_bf16_product(const pk_gemm_smallm_bf16_diag *d, DwTail &t
     GemmArgs g{some, d->lda, some + 1, d->ldw, d->bias ? some : nullptr, sink, d->ldo, epi == EPI_RESID ? (d->resid_in_place ? sink : some) : nullptr,
                d->resid_in_place ? d->ldo : d->ldr, d->alpha, M, N, K};
     g.a_bf16 = d->a_bf16 ? 1 : 0; g.out_bf16 = d->out_bf16 ? 1 : 0; g.out_t8 = d->out_t8 ? 1 : 0; g.a_t8 = d->a_t8 ? 1 : 0; g.fast_act = d->fast_act ? 1 : 0;
+    g.one_form = d->one_form ? 1 : 0;
     const int wrows = epi == EPI_GLU ? 2 * N : N;
     if (d->w_tiles && wrows % 16 == 0) g.W_t16 = some + 2;          // (the launcher takes it for N % 16 == 0)
     if (d->ln_g) { g.ln_g = some; g.ln_b = some; g.ln_eps = d->eps; }
     if (d->pre_g) { g.pre_g = some; g.pre_b = some; g.pre_out = d->pre_out ? sink + 1 : nullptr; g.pre_ldo = d->pre_ldo; }
     if (!gemm_smallm_bf16_applies(g, epi))
-        fail(PK_ERR_UNSUPPORTED, "%s: gemm_smallm_bf16_applies refuses: M <= %d, K %% 256 == 0, ldw %% 8 == 0, lda %% 8 == 0 (fp32 A: %% 4); bf16 rows out not for resid / glu; "
+        fail(PK_ERR_UNSUPPORTED, "%s: gemm_smallm_bf16_applies refuses: M <= %d, K %% 256 == 0, no one_form, ldw %% 8 == 0, lda %% 8 == 0 (fp32 A: %% 4); bf16 rows out not for resid / glu; "
              "out_t8: bf16 rows out, M %% 8 == 0, N %% 32 == 0, ldo == N; a_t8: bf16 A, M %% 8 == 0, lda == K, epi resid", who, kSmallMRowsBf16);
     if (d->ln_g && !gemm_smallm_bf16_ln_applies(g, epi))
         fail(PK_ERR_UNSUPPORTED, "%s: gemm_smallm_bf16_ln_applies refuses: the folded LayerNorm takes fp32 rows, K = 256 * (1 .. 8; glu: .. 4)", who);

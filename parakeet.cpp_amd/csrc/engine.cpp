@@ -408,6 +408,8 @@ void Model::run_gemm(const char *name, const GemmArgs &g, int epi, hipStream_t s
         fail(PK_ERR_INVALID, "%s: a folded LayerNorm needs one of the small-M kernels (gemm_smallm_ln_applies / gemm_smallm_bf16_ln_applies)", name);
     if (g.pre_g && !((cfg.gemm_bf16 && !fp32_weight) ? gemm_smallm_bf16_pre_applies(g, epi) : gemm_smallm_pre_applies(g, epi)))
         fail(PK_ERR_INVALID, "%s: a norm in front of the folded LayerNorm needs one of the small-M kernels (gemm_smallm_pre_applies / gemm_smallm_bf16_pre_applies)", name);
+    if (g.one_form && (!cfg.gemm_bf16 || fp32_weight || epi == EPI_GLU))
+        fail(PK_ERR_INVALID, "%s: one_form is a rule of the bf16 tile kernels (bf16 mode, not for GLU)", name);
     if (cfg.gemm_bf16 && !fp32_weight) {
         if (g.K % 64) fail(PK_ERR_UNSUPPORTED, "gemm_bf16 needs K %% 64 == 0 (%s has K = %d)", name, g.K);
         if (g.out_bf16 && (g.remap_rows != 0 || (g.ldo & 3) != 0 || (g.N & 3) != 0 || g.sigma_cols != 0 || epi == EPI_RESID || epi == EPI_GLU))
@@ -741,8 +743,11 @@ bool Model::attn_bf16(int T) const {
 
 // The tables are kept for the LONGEST sequence seen so far: row p of the table of a T-frame sequence (position T - 1 - p) is row
 // p + (pos_T - T) of the table built for pos_T >= T frames -- the same float position, hence the same sin / cos values and the same row of
-// the row-wise pos_proj_ product.  Shorter sequences and the utterances of a ragged batch read their window of it (launch_relpos_attention:
-// pos_row0 / SeqRag::pos_T); the tables are rebuilt only when a longer sequence arrives.
+// the row-wise pos_proj_ product -- as long as that product sums a row the same way at every M: the fp32 kernels do (one k-ordered chain per
+// element in both families); of the bf16 ones the small-M kernel splits K over its waves, and now and then an element of a 512- or 1024-wide table
+// then rounds to another bf16 value than the tile kernel's (test_bf16_table_rows_have_one_form_at_every_m counts them), hence GemmArgs::one_form below (tests/test_gpu_call_history.py holds a model with
+// a history to a fresh one bit for bit).  Shorter sequences and the utterances of a ragged batch read their window of it
+// (launch_relpos_attention: pos_row0 / SeqRag::pos_T); the tables are rebuilt only when a longer sequence arrives.
 void Model::ensure_pos_tables(int T, hipStream_t s) {
     const bool want16 = attn_bf16(T);
     PosTab &tab_set = want16 ? pos16 : pos32;
@@ -771,6 +776,7 @@ void Model::ensure_pos_tables(int T, hipStream_t s) {
             __bf16 *tab = reinterpret_cast<__bf16 *>(pos_proj.p) + (size_t)l * P * d;
             GemmArgs g{pos_pe.as<float>(), d, layers[l].wpos, d, nullptr, reinterpret_cast<float *>(tab), d, nullptr, 0, 1.0f, P, d, d};
             g.out_bf16 = 1;
+            g.one_form = 1;                // the same bits in a row whether 2 T - 1 <= kSmallMRowsBf16 or not (once per growth: its speed does not matter)
             run_gemm("pos_proj", g, EPI_NONE, s);
             launch_pos_cvec(tab, layers[l].pos_u, layers[l].pos_v, P, d, H, pos_cvec.as<float>() + (size_t)l * H * P, s);
         }
@@ -781,6 +787,7 @@ void Model::ensure_pos_tables(int T, hipStream_t s) {
         // written in the sigma column layout the attention kernel loads its MFMA operands in (kernels.hpp: GemmArgs::sigma_cols)
         GemmArgs g{pos_pe.as<float>(), d, layers[l].wpos, d, nullptr, pos_proj.as<float>() + (size_t)l * P * d, d, nullptr, 0, 1.0f, P, d, d};
         g.sigma_cols = d;
+        g.one_form = cfg.gemm_bf16 ? 1 : 0;   // (bf16 mode with the fp32 attention: the bf16 tile kernels, whose form would change at 1024 rows)
         run_gemm("pos_proj", g, EPI_NONE, s);
     }
     pos_T = T;

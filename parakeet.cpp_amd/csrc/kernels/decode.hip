@@ -5,10 +5,12 @@
 // TDT / RNNT (src/tdt.cpp:36-201, src/rnnt.cpp:56-177, src/lstm.cpp:11-29): the whole greedy loop stays on
 //      the GPU -- the reference does 2 device->host scalar syncs per symbol.  All utterances of a batch
 //      advance in lock-step; one "step" = one joint evaluation per live utterance:
-//        gemm  GH = h W_hh^T            (MFMA)           -> lstm_cell   (gates, c', h' candidates)
-//        gemm  PP = h' W_pred^T         (MFMA)           -> joint_act   z = relu(enc_proj[t_b] + PP)
+//        gemm  GH = h W_hh^T            (MFMA)           -> LSTM cell   (gates, c', h' candidates)
+//        gemm  PP = h' W_pred^T         (MFMA)           -> joint act.  z = relu(enc_proj[t_b] + PP)
 //        gemm  LOG = z [W_label;W_dur]^T + b (MFMA)      -> tdt_decide  log-softmax, argmax, control,
 //                                                                        commit / revert of the LSTM state
+//      The cell and the joint activation are epilogues of their products (kernels/decode_gemv.hip, kernels.hpp SkinnyArgs: epi 2 / epi 1);
+//      this file holds the decision.
 #include <cstdio>
 #include <cstdlib>
 #include "decode_dev.hpp"
@@ -168,49 +170,6 @@ void launch_ctc_boosted(const float *logp, int B, int T, int V, int blank, const
 }
 
 // ---- TDT / RNNT step kernels --------------------------------------------------------------------------
-// LSTMCell::forward (src/lstm.cpp:11-29), gate order i,f,g,o.  gi = W_ih x + b (layer 0: row `token` of the
-// precomputed table g1 = W_ih E + b), gh = W_hh h.  Writes CANDIDATE states hn/cn; tdt_decide commits them.
-__global__ __launch_bounds__(256) void lstm_cell_kernel(const float *__restrict__ gi, int gi_ld, const int *__restrict__ gi_row,
-                                                        const float *__restrict__ gh, const float *__restrict__ c,
-                                                        int B, int Hp, float *__restrict__ hn, float *__restrict__ cn) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= B * Hp) return;
-    const int b = idx / Hp, j = idx % Hp;
-    const float *gir = gi + (int64_t)(gi_row ? gi_row[b] : b) * gi_ld;
-    const float *ghr = gh + (int64_t)b * 4 * Hp;
-    const float ig = dsigmoidf(gir[j] + ghr[j]);
-    const float fg = dsigmoidf(gir[Hp + j] + ghr[Hp + j]);
-    const float gg = dtanhf(gir[2 * Hp + j] + ghr[2 * Hp + j]);
-    const float og = dsigmoidf(gir[3 * Hp + j] + ghr[3 * Hp + j]);
-    const float t1 = fg * c[idx];
-    const float t2 = ig * gg;
-    const float cnew = t1 + t2;
-    cn[idx] = cnew;
-    hn[idx] = og * dtanhf(cnew);
-}
-void launch_lstm_cell(const float *gi, int gi_ld, const int *gi_row, const float *gh, const float *c, int B, int Hp, float *hn,
-                      float *cn, hipStream_t s) {
-    hipLaunchKernelGGL(lstm_cell_kernel, dim3((B * Hp + 255) / 256), dim3(256), 0, s, gi, gi_ld, gi_row, gh, c, B, Hp, hn, cn);
-}
-
-// TDTJoint::forward first half (src/tdt.cpp:17-18): z = relu(enc_proj(enc_t) + pred_proj(pred) [+ bp, switch A5])
-__global__ __launch_bounds__(256) void joint_act_kernel(const float *__restrict__ ep, const int *__restrict__ t, int T, int J,
-                                                        const float *__restrict__ pp, const float *__restrict__ bp, int B,
-                                                        float *__restrict__ z) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= B * J) return;
-    const int b = idx / J, j = idx % J;
-    int tt = t[b];
-    tt = tt < T ? tt : T - 1;
-    float p = pp[idx];
-    if (bp) p = p + bp[j];
-    const float s = ep[((int64_t)b * T + tt) * J + j] + p;
-    z[idx] = s > 0.0f ? s : 0.0f;
-}
-void launch_joint_act(const float *ep, const int *t, int T, int J, const float *pp, const float *bp, int B, float *z, hipStream_t s) {
-    hipLaunchKernelGGL(joint_act_kernel, dim3((B * J + 255) / 256), dim3(256), 0, s, ep, t, T, J, pp, bp, B, z);
-}
-
 // One 256-thread workgroup per utterance: heads' log-softmax + first-max argmax, then the control flow of
 // tdt_greedy_decode (src/tdt.cpp:62-106; timestamps :157-187) or rnnt_greedy_decode (src/rnnt.cpp:75-107).
 // The logits row is staged in LDS once; exp() is evaluated by all four wavefronts, the canonical sum64 by one

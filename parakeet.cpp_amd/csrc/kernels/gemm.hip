@@ -363,6 +363,7 @@ bool gemm_bf16_blocked_handoff(int M, int N, int K, int epi, bool producer) {
 // it: every threshold of the bf16 tile kernels lives here (the register epilogues' predicates: gl_epilogue_form) and nowhere else.
 GemmBf16Form gemm_bf16_form(const GemmArgs &a, int epi) {
     const bool a16 = a.a_bf16 != 0;
+    if (a.one_form && epi != EPI_GLU) return gemm_bf16_form_of(BF16_REG, 2, 2, 1, 1, a16, BF16_EPI_LDS, epi);   // (GemmArgs::one_form: no threshold in M)
     if (a16 && bf16_glds_rule(a.M, a.N, a.K) && (a.lda % 8) == 0 && (a.ldw % 8) == 0 && a.remap_rows == 0 && (a.ldo & 3) == 0) {
         // One tile per CU and round (128 KB of LDS): the kernel's time is rounds x (tile's K loop + ~12 us of prologue / epilogue), so the tile
         // HEIGHT is chosen per product for the fewest, fullest rounds of the 256 CUs (tools/ubench/gemm_bf16_k.cpp, profiles/r03_gemm_bf16_k.txt:

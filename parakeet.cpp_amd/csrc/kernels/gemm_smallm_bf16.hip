@@ -458,7 +458,7 @@ __global__ __launch_bounds__(64 * kSbMaxWaves) void gemm_smallm_bf16_kernel(Gemm
 
 // the shapes this kernel takes (everything else stays on the tile kernels of gemm_bf16.hpp)
 bool gemm_smallm_bf16_applies(const GemmArgs &a, int epi) {
-    if (a.M > kSmallMRowsBf16 || a.M <= 0 || a.K % 256 != 0 || a.remap_rows != 0 || a.sigma_cols != 0) return false;
+    if (a.M > kSmallMRowsBf16 || a.M <= 0 || a.K % 256 != 0 || a.remap_rows != 0 || a.sigma_cols != 0 || a.one_form) return false;
     if ((a.ldw % 8) != 0 || (a.lda % (a.a_bf16 ? 8 : 4)) != 0) return false;
     if (a.out_bf16 && (epi == EPI_RESID || epi == EPI_GLU)) return false;
     if (a.out_t8 && !(a.out_bf16 && a.M % 8 == 0 && a.N % 32 == 0 && a.ldo == a.N)) return false;

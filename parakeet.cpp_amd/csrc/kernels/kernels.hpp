@@ -127,6 +127,11 @@ struct GemmArgs {
     // numerics contract -- that mode is compared with the oracle within a bf16-epsilon-class tolerance, not bit for bit, and at bf16 MFMA rates
     // the 38-operation SiLU is as expensive as the product itself (fc1 of tdt-600m: ~48 us of VALU against 40 us of MFMA).
     int fast_act = 0;
+    // bf16 mode only: the product runs on ONE kernel form whatever M is -- never the small-M bf16 kernel (with K > 256 it splits K over its waves and adds
+    // the partial sums afterwards: not the fp32 sum the tile kernels form), always the register-staged 64 x 64 tile -- so that a row of the output has the
+    // same bits at every M.  Set for products whose rows are read again under another M: the relative-position tables (Model::ensure_pos_tables), built
+    // once for the longest sequence and read by windows.  Not for the hot path: the form is not the fastest one for most shapes.  (EPI_GLU: ignored.)
+    int one_form = 0;
     // small-M kernel (gemm_smallm.hip, M <= kSmallMRows) only: W_sig = a copy of W (launch_sigma_copy; N % 16 == 0, K % 64 == 0) tiled in the kernel's load
     // order -- per (16-row tile, 64-k chunk) one 4 KB block [q][lane][4] with the K axis in the sigma layout; a_sigma = A's K axis is in the sigma
     // layout (its producer wrote it that way: sigma_cols, LayerNorm mode 2, the streaming attention / conv kernels).  Both set: a lane's 16-byte
@@ -762,9 +767,6 @@ void launch_tdt_init(const TdtState &st, hipStream_t s);
 // Tb_out[i] / row0_out[i], i < n: frames and first enc_proj row (row_base + its offset) of the utterances of one run; T == nullptr: a uniform
 // run of T_uniform frames each
 void launch_rag_decode_tables(const int *T, const int *T_off, int T_uniform, int n, int row_base, int *Tb_out, int *row0_out, hipStream_t s);
-void launch_lstm_cell(const float *gi, int gi_ld, const int *gi_row, const float *gh, const float *c, int B, int Hp, float *hn,
-                      float *cn, hipStream_t s);
-void launch_joint_act(const float *ep, const int *t, int T, int J, const float *pp, const float *bp, int B, float *z, hipStream_t s);
 void launch_tdt_decide(const TdtState &st, hipStream_t s);
 // The form of a decision launch, by the function the launcher switches on: value = kernel * 16 + slots * 4 + row.
 //   kernel: tdt_decide_kernel's instantiation -- the exact greedy step, the register-resident step of the tolerance-class mode (h_bf16), phrase boosting, forced scoring

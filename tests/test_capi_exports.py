@@ -357,6 +357,41 @@ def test_conv_variant_diagnostics_are_host_arithmetic(tmp_path):
         m.close()
 
 
+def test_bf16_one_form_is_one_tile_at_every_m_and_no_small_m_shape():
+    """GemmArgs::one_form (the relative-position tables of the bf16 mode: rows built under one M, read under another) through the two form queries: the
+    register-staged 64 x 64 tile whatever M is -- where the dispatch would take the small-M bf16 kernel, the 128 x 64 or the 128 x 128 tile --, refused by
+    gemm_smallm_bf16_applies, refused with GLU.  Host arithmetic."""
+    R64 = ("reg", (2, 2, 1, 1), False, "lds", "none")
+    q, qs = capi.diag_gemm_bf16_tile_form, capi.diag_gemm_smallm_bf16_form
+    for d in (128, 256, 512, 1024):
+        for M in (1, 64, 127, 128, 129, 1023, 1024, 1025, 20001):
+            assert q(M, d, d, bias=False, out_bf16=True, one_form=True) == R64, (M, d)
+            assert q(M, d, d, bias=False, sigma_cols=d, one_form=True) == R64, (M, d)       # the fp32-attention table of the bf16 mode
+    assert q(1025, 512, 512, bias=False, out_bf16=True) == ("reg", (2, 2, 2, 1), False, "lds", "none")
+    assert q(1025, 1024, 1024, bias=False, out_bf16=True) == ("reg", (4, 2, 1, 2), False, "lds", "none")
+    assert qs(127, 512, 512, bias=False, out_bf16=True)[0] == "none"
+    for bad in (lambda: qs(127, 512, 512, bias=False, out_bf16=True, one_form=True), lambda: q(127, 512, 512, bias=False, out_bf16=True),
+                lambda: q(2000, 512, 512, epi="glu", one_form=True)):
+        with pytest.raises(capi.PkError) as e:
+            bad()
+        assert e.value.code == -7
+
+
+def test_pos_table_diagnostic_reads_a_model_without_a_device(tmp_path):
+    """pk_diag_pos_table_frames (what tests/test_gpu_call_history.py asserts after every call) reads two host integers: a model that has run nothing
+    reports (0, 0), with or without a device, and null arguments are PK_ERR_INVALID."""
+    assert "pk_diag_pos_table_frames" in declared_symbols() and hasattr(capi.lib(), "pk_diag_pos_table_frames")
+    cfg = pk.make_tiny_config()
+    wp = tmp_path / "t.safetensors"
+    synth.save_weights(str(wp), synth.synth_weights(cfg))
+    m = capi.Model(str(wp), cfg)
+    assert m.pos_table_frames() == (0, 0)
+    out = np.full(2, 7, np.int32)
+    assert capi.lib().pk_diag_pos_table_frames(None, out.ctypes.data_as(C.POINTER(C.c_int32))) == -1
+    assert capi.lib().pk_diag_pos_table_frames(m._h, None) == -1 and out.tolist() == [7, 7]
+    m.close()
+
+
 def test_mel_diagnostic_refuses_before_it_looks_for_a_device():
     """pk_diag_mel (what tests/test_gpu_mel_forms.py launches the front end through) checks its arguments on the host: a clip the reflect padding
     cannot frame, a chunk shorter than one window, a bin count or buffers it cannot take are PK_ERR_INVALID with or without a device, and the
