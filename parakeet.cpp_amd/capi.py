@@ -1109,7 +1109,7 @@ SKINNY_FILL32, SKINNY_FILL16 = 0x7FC5A5A5, 0x7FC5          # what an element no 
 
 
 def sigma16(n):
-    """the fp32 decode kernels' column order (decode_dev.hpp sigma16; its own inverse): the 4x4 index transpose inside every block of 16"""
+    """the fp32 decode kernels' column order (pk_devmath.h sigma_col; its own inverse): the 4x4 index transpose inside every block of 16"""
     k = np.arange(n)
     return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3)
 

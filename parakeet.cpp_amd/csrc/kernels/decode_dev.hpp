@@ -49,9 +49,6 @@ template <bool COH> __device__ __forceinline__ void dd_sti(int *p, int v) {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-
-__device__ __forceinline__ int sigma16(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-
 // Compact list of the utterances whose need flag is set, ascending (TdtState::need): lst[0 .. count).  One 256-thread workgroup, B <= kMaxListRows;
 // every thread of the workgroup must call it (two barriers).
 template <bool COH>
@@ -286,7 +283,7 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
                 if (a.pp_out) a.pp_out[(int64_t)b * a.N + n] = p;           // cached for the steps after a blank (TdtState::pp)
                 const float s = e_ep[r] + p;
                 if constexpr (WF > 1) {
-                    float *zr = a.out + (int64_t)b * a.F * a.N + sigma16(n);
+                    float *zr = a.out + (int64_t)b * a.F * a.N + sigma_col(n);
                     dd_stf<COH>(zr, s > 0.0f ? s : 0.0f);
 #pragma unroll
                     for (int f = 1; f < WF; ++f) {
@@ -296,7 +293,7 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
                         }
                     }
                 } else {
-                    dd_stf<COH>(a.out + (int64_t)b * a.N + sigma16(n), s > 0.0f ? s : 0.0f);
+                    dd_stf<COH>(a.out + (int64_t)b * a.N + sigma_col(n), s > 0.0f ? s : 0.0f);
                 }
             }
         }
@@ -332,7 +329,7 @@ __device__ __forceinline__ void skinny_tile(const SkinnyArgs &a, int nt, int mgr
             const float t2 = ig * gg;
             const float cnew = t1 + t2;
             dd_stf<COH>(a.cn + (int64_t)b * a.Hp + j, cnew);
-            dd_stf<COH>(a.out + (int64_t)b * a.Hp + sigma16(j), og * dtanhf(cnew));   // h' in sigma layout (it is only ever a GEMV operand)
+            dd_stf<COH>(a.out + (int64_t)b * a.Hp + sigma_col(j), og * dtanhf(cnew));   // h' in sigma layout (it is only ever a GEMV operand)
         }
     }
 }
@@ -915,7 +912,7 @@ __device__ __forceinline__ void tdt_decide_one(const TdtState &st, int b, float 
                                 const float sv = epv[fw][q] + ppv[q];
                                 const float zv = sv > 0.0f ? sv : 0.0f;
                                 if (st.h_bf16) reinterpret_cast<__bf16 *>(st.z)[zr + n] = (__bf16)zv;
-                                else dd_stf<COH>(st.z + zr + sigma16(n), zv);
+                                else dd_stf<COH>(st.z + zr + sigma_col(n), zv);
                             }
                         }
                     }
@@ -925,7 +922,7 @@ __device__ __forceinline__ void tdt_decide_one(const TdtState &st, int b, float 
                 const float sv = epr[n] + ppr[n];
                 const float zv = sv > 0.0f ? sv : 0.0f;
                 if (st.h_bf16) reinterpret_cast<__bf16 *>(st.z)[(int64_t)b * st.J + n] = (__bf16)zv;
-                else dd_stf<COH>(st.z + (int64_t)b * st.J + sigma16(n), zv);
+                else dd_stf<COH>(st.z + (int64_t)b * st.J + sigma_col(n), zv);
             }
         }
     }

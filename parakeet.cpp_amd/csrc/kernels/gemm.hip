@@ -143,41 +143,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs g, int tiles_n, i
         __syncthreads();
     }
 
-    // epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    const int lc = lane & 31, lr = 4 * (lane >> 5);
-    constexpr int TNO = (EPI == EPI_GLU) ? TN / 2 : TN;
-#pragma unroll
-    for (int j = 0; j < TNO; ++j) {
-        const int col = n0 + wn * (EPI == EPI_GLU ? WN / 2 : WN) + j * 32 + lc;
-        if (col >= g.N) continue;
-        const float bias = g.bias ? g.bias[col] : 0.0f;
-        float bias_g = 0.0f;
-        if constexpr (EPI == EPI_GLU) bias_g = g.bias ? g.bias[g.N + col] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + lr;
-                if (row >= g.M) continue;
-                float v = acc[i][j][r];
-                if (g.bias) v = v + bias;
-                if constexpr (EPI == EPI_RELU) {
-                    v = v > 0.0f ? v : 0.0f;
-                } else if constexpr (EPI == EPI_SILU) {
-                    v = dsiluf(v);
-                } else if constexpr (EPI == EPI_RESID) {
-                    const float y = v * g.alpha;
-                    v = g.resid[(int64_t)row * g.ldr + col] + y;
-                } else if constexpr (EPI == EPI_GLU) {
-                    float gt = acc[i][j + TN / 2][r];
-                    if (g.bias) gt = gt + bias_g;
-                    v = v * dsigmoidf(gt);
-                }
-                if (g.remap_rows) g.out[(int64_t)(row / g.remap_rows) * g.remap_gs + (int64_t)(row % g.remap_rows) * g.remap_rs + (int64_t)col * g.remap_cs] = v;
-                else g.out[(int64_t)row * g.ldo + (col < g.sigma_cols ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col)] = v;
-            }
-        }
-    }
+    epilogue_scalar_32x32<TM, TN, WN, EPI>(g, acc, m0, n0, wm, wn, lane, false);   // (an fp32-contract kernel: the polynomial activations)
 }
 
 template <int BM, int BN, int EPI>

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include "../pk_devmath.h"
 #include "kernels.hpp"
+#include "gemm_epi.hpp"
 
 namespace pk {
 
@@ -44,43 +45,6 @@ __device__ __forceinline__ void gp_epilogue(const GemmArgs &g_, gp_f32x16 (&acc)
     constexpr int NOUT = (EPI == EPI_GLU) ? BN / 2 : BN;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
-    // epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    auto epilogue_scalar = [&](int m0, int n0) {
-        const int lc = lane & 31, lr = 4 * (lane >> 5);
-        constexpr int TNO = (EPI == EPI_GLU) ? TN / 2 : TN;
-#pragma unroll
-        for (int j = 0; j < TNO; ++j) {
-            const int col = n0 + wn * (EPI == EPI_GLU ? WN / 2 : WN) + j * 32 + lc;
-            if (col >= g.N) continue;
-            const float bias = g.bias ? g.bias[col] : 0.0f;
-            float bias_g = 0.0f;
-            if constexpr (EPI == EPI_GLU) bias_g = g.bias ? g.bias[g.N + col] : 0.0f;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + lr;
-                    if (row >= g.M) continue;
-                    float v = acc[i][j][r];
-                    if (g.bias) v = v + bias;
-                    if constexpr (EPI == EPI_RELU) {
-                        v = v > 0.0f ? v : 0.0f;
-                    } else if constexpr (EPI == EPI_SILU) {
-                        v = gf.fast_act ? fast_siluf(v) : dsiluf(v);
-                    } else if constexpr (EPI == EPI_RESID) {
-                        const float y = v * g.alpha;
-                        v = g.resid[(int64_t)row * g.ldr + col] + y;
-                    } else if constexpr (EPI == EPI_GLU) {
-                        float gt = acc[i][j + TN / 2][r];
-                        if (g.bias) gt = gt + bias_g;
-                        v = v * (gf.fast_act ? fast_sigmoidf(gt) : dsigmoidf(gt));
-                    }
-                    if (g.remap_rows) g.out[(int64_t)(row / g.remap_rows) * g.remap_gs + (int64_t)(row % g.remap_rows) * g.remap_rs + (int64_t)col * g.remap_cs] = v;
-                    else g.out[(int64_t)row * g.ldo + (col < g.sigma_cols ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col)] = v;
-                }
-            }
-        }
-    };
     // Wide epilogue (row-major outputs whose rows are 16-byte aligned): the accumulators go through LDS (the staging buffers
     // are free by now) so that every thread finishes 4 CONSECUTIVE output columns -- one 16-byte store per 4 results, a
     // wave writes whole 256-512 B row segments instead of 32 x 128 B slivers, the residual arrives as float4 too.
@@ -214,7 +178,7 @@ __device__ __forceinline__ void gp_epilogue(const GemmArgs &g_, gp_f32x16 (&acc)
     };
     const bool wide = g.remap_rows == 0 && (g.ldo & 3) == 0 && (g.N & 3) == 0 && (EPI != EPI_RESID || (g.ldr & 3) == 0);   // (out_bf16 requires it: launcher)
     if (wide) epilogue_wide(m0, n0);
-    else epilogue_scalar(m0, n0);
+    else epilogue_scalar_32x32<TM, TN, WN, EPI>(g, acc, m0, n0, wm, wn, lane, gf.fast_act != 0);
 }
 
 // LNA (round 6): the LayerNorm of the product's input rows applied WHILE THE A TILE IS STAGED -- A = the un-normalised rows, GemmArgs::ln_stats = {mean, rstd}

@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "kernels.hpp"
+#include "gemm_epi.hpp"
 
 namespace pk {
 
@@ -129,22 +130,9 @@ __global__ __launch_bounds__(128) void gemm_smallm_kernel(GemmArgs g) {
     for (int i = 0; i < 4; ++i) {
         const int row = m0 + 4 * kq + i;
         if (row >= g.M) continue;
-        float v = acc[i];
-        if (g.bias) v = v + bias;
-        if constexpr (EPI == EPI_RELU) {
-            v = v > 0.0f ? v : 0.0f;
-        } else if constexpr (EPI == EPI_SILU) {
-            v = dsiluf(v);
-        } else if constexpr (EPI == EPI_RESID) {
-            const float y = v * g.alpha;
-            v = res[i] + y;
-        } else if constexpr (EPI == EPI_GLU) {
-            float gt = gate[lane][i];
-            if (g.bias) gt = gt + bias_g;
-            v = v * dsigmoidf(gt);
-        }
-        if (g.remap_rows) g.out[(int64_t)(row / g.remap_rows) * g.remap_gs + (int64_t)(row % g.remap_rows) * g.remap_rs + (int64_t)col * g.remap_cs] = v;
-        else g.out[(int64_t)row * g.ldo + (col < g.sigma_cols ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col)] = v;
+        float gt = 0.0f;
+        if constexpr (EPI == EPI_GLU) gt = gate[lane][i];
+        gemm_store(g, row, col, epi_finish<EPI>(acc[i], g.bias != nullptr, bias, gt, bias_g, res[i], g.alpha, false));
     }
 }
 
@@ -219,32 +207,21 @@ __global__ __launch_bounds__(64) void gemm_smallm_rt2_kernel(GemmArgs g) {
         for (int i = 0; i < 4; ++i) {
             const int row = m0 + 16 * t + 4 * kq + i;
             if (row >= g.M) continue;
-            float v = acc[t][i];
-            if (g.bias) v = v + bias;
-            if constexpr (EPI == EPI_RELU) {
-                v = v > 0.0f ? v : 0.0f;
-            } else if constexpr (EPI == EPI_SILU) {
-                v = dsiluf(v);
-            } else if constexpr (EPI == EPI_RESID) {
-                const float y = v * g.alpha;
-                v = res[t][i] + y;
-            }
-            if (g.remap_rows) g.out[(int64_t)(row / g.remap_rows) * g.remap_gs + (int64_t)(row % g.remap_rows) * g.remap_rs + (int64_t)col * g.remap_cs] = v;
-            else g.out[(int64_t)row * g.ldo + (col < g.sigma_cols ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col)] = v;
+            gemm_store(g, row, col, epi_finish<EPI>(acc[t][i], g.bias != nullptr, bias, 0.0f, 0.0f, res[t][i], g.alpha, false));   // (no GLU form: two row tiles share W)
         }
 }
 
 // The chain kernel with the LayerNorm of its input rows folded in (GemmArgs::ln_g / ln_b / ln_eps; A = the UN-normalised rows x[M][K], K = the
 // row length, 512 or 1024): out = epi(LayerNorm(x) W^T + bias), bit for bit what layernorm_kernel followed by gemm_smallm_kernel<.., SIG> give.
 // Round 3 folded the norm into the one-wave-per-tile kernel and lost (every wave re-derived the statistics of its 16 rows alone: 3-4 us in front
-// of its chain).  Here a workgroup is FOUR waves: each normalises four of the tile's 16 rows exactly as layernorm_kernel does (one wave per row,
-// lane l holds elements l + 64 j, the canonical sum64 butterflies, y = fma((x - mean) rstd, gamma, beta)) and stores them to LDS in the sigma K
+// of its chain).  Here a workgroup is FOUR waves: each normalises four of the tile's 16 rows the way layernorm_kernel does (one wave per row,
+// lane l holds elements l + 64 j, ln_row_stats of pk_devmath.h, y = fma((x - mean) rstd, gamma, beta)) and stores them to LDS in the sigma K
 // order at a pitch of K + 4 floats; after one barrier waves 0 and 1 run the dependent MFMA chains of two column tiles (GLU: the value and the
 // gate tile of the same 16 columns) with their A fragments from LDS (one chunk ahead of the chain, conflict-free ds_read_b128) and the tiled
 // weight stream in the same 8-chunk register ring as gemm_smallm_kernel -- requested BEFORE the rows, so the weights' HBM round trip covers the
 // normalisation.  Saves the LayerNorm launch (~5 us of a 32-row streaming chunk's ~360) for ~1 us in front of the chain.
 // DW (EPI_GLU; kernels.hpp DwTail): the streaming conv module's depthwise conv + BatchNorm + SiLU run by the lane that finishes (stream, channel) --
-// the same operations in the same order as stream_dwconv_kernel (kernels/stream.hip), one launch less per block.
+// every point is the dwconv_point (pk_devmath.h) that stream_dwconv_kernel (kernels/stream.hip) calls; one launch less per block.
 // PRE (GemmArgs::pre_g): another LayerNorm in front of the folded one.  Both are template parameters: as run-time branches they cost every
 // instantiation 64 VGPRs (K = 1024: 240 -> 304, one workgroup per CU instead of two -- 64 sessions ran 14 % slower for it).
 template <int EPI, int PER_LANE /* K / 64 */, bool DW = false, bool PRE = false>
@@ -279,6 +256,7 @@ __global__ __launch_bounds__(256) void gemm_smallm_ln_kernel(GemmArgs g, DwTail 
         for (int j = 0; j < DEPTH - 1; ++j) wload(j, j);
     }
     // conv tail: the cached rows of this lane's streams (rows m0 + 4 kq .. + 3 = 4 / c streams of c frames) and the conv's parameters of its channel
+    // (mirrors DwTailRegs::load / finish of gemm_epi.hpp, written out here: through the struct the K = 1024 instantiation spills 8 VGPRs instead of 4)
     [[maybe_unused]] float dpre[4][8], dwk[9], dbs = 0.0f, dmu = 0.0f, drs = 0.0f, dbg = 0.0f, dbb = 0.0f;
     if constexpr (DW) {
         if (chain && half == 0 && col < g.N) {
@@ -296,7 +274,7 @@ __global__ __launch_bounds__(256) void gemm_smallm_ln_kernel(GemmArgs g, DwTail 
             dbs = dw.bias[col]; dmu = dw.bn_mean[col]; drs = dw.bn_rstd[col]; dbg = dw.bn_g[col]; dbb = dw.bn_b[col];
         }
     }
-    // ---- every wave: LayerNorm of rows m0 + 4 wave .. + 3, exactly as layernorm_kernel<PER_LANE, 1> (one wave per row) ----
+    // ---- every wave: LayerNorm of rows m0 + 4 wave .. + 3, one wave per row with layernorm_kernel's ln_row_stats ----
     {
         float gv[PER_LANE], bv[PER_LANE], v[4][PER_LANE];
 #pragma unroll
@@ -308,7 +286,7 @@ __global__ __launch_bounds__(256) void gemm_smallm_ln_kernel(GemmArgs g, DwTail 
             for (int j = 0; j < PER_LANE; ++j) v[rr][j] = xr[lane + 64 * j];
         }
         // A norm in front of the folded one (GemmArgs::pre_g: a block's final_norm_ riding on the next block's first product; streaming): the wave
-        // normalises its rows exactly as layernorm_kernel would have (same sums, same fma) -- bit for bit the separate launch -- keeps them in
+        // normalises its rows (ln_row_stats, layernorm_kernel's fma: the bits of the separate launch), keeps them in
         // registers, and the first K / 64 column-tile workgroups write them out, one 64-element chunk of every row each: the residual stream of the block that starts here.
         if constexpr (PRE) {
 #pragma unroll
@@ -318,18 +296,8 @@ __global__ __launch_bounds__(256) void gemm_smallm_ln_kernel(GemmArgs g, DwTail 
             }
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-                float p = 0.0f;
-#pragma unroll
-                for (int j = 0; j < PER_LANE; ++j) p = p + v[rr][j];
-                const float mean = wave_sum64(p) / (float)K;
-                float q = 0.0f;
-#pragma unroll
-                for (int j = 0; j < PER_LANE; ++j) {
-                    const float c = v[rr][j] - mean;
-                    q = q + c * c;
-                }
-                const float var = wave_sum64(q) / (float)K;
-                const float rstd = 1.0f / __builtin_sqrtf(var + g.ln_eps);
+                float mean, rstd;
+                ln_row_stats<PER_LANE>(v[rr], lane, K, g.ln_eps, mean, rstd);
                 const int row = m0 + 4 * wave + rr;
                 const bool put = g.pre_out && row < g.M;
 #pragma unroll
@@ -346,24 +314,11 @@ __global__ __launch_bounds__(256) void gemm_smallm_ln_kernel(GemmArgs g, DwTail 
         }
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
-            float p = 0.0f;
-#pragma unroll
-            for (int j = 0; j < PER_LANE; ++j) p = p + v[rr][j];
-            const float mean = wave_sum64(p) / (float)K;
-            float q = 0.0f;
-#pragma unroll
-            for (int j = 0; j < PER_LANE; ++j) {
-                const float c = v[rr][j] - mean;
-                q = q + c * c;
-            }
-            const float var = wave_sum64(q) / (float)K;
-            const float rstd = 1.0f / __builtin_sqrtf(var + g.ln_eps);
+            float mean, rstd;
+            ln_row_stats<PER_LANE>(v[rr], lane, K, g.ln_eps, mean, rstd);
             float *yr = At + (4 * wave + rr) * PITCH;
 #pragma unroll
-            for (int j = 0; j < PER_LANE; ++j) {
-                const int i = lane + 64 * j;
-                yr[(i & ~15) | ((i & 3) << 2) | ((i >> 2) & 3)] = __builtin_fmaf((v[rr][j] - mean) * rstd, gv[j], bv[j]);
-            }
+            for (int j = 0; j < PER_LANE; ++j) yr[sigma_col(lane + 64 * j)] = __builtin_fmaf((v[rr][j] - mean) * rstd, gv[j], bv[j]);
         }
     }
     __syncthreads();
@@ -406,23 +361,14 @@ __global__ __launch_bounds__(256) void gemm_smallm_ln_kernel(GemmArgs g, DwTail 
     for (int i = 0; i < 4; ++i) {
         const int row = m0 + 4 * kq + i;
         if (row >= g.M) continue;
-        float v = acc[i];
-        if (g.bias) v = v + bias;
-        if constexpr (EPI == EPI_RELU) {
-            v = v > 0.0f ? v : 0.0f;
-        } else if constexpr (EPI == EPI_SILU) {
-            v = dsiluf(v);
-        } else if constexpr (EPI == EPI_GLU) {
-            float gt = gate[lane][i];
-            if (g.bias) gt = gt + bias_g;
-            v = v * dsigmoidf(gt);
-        }
-        if constexpr (DW) { glu[i] = v; continue; }
-        if (g.remap_rows) g.out[(int64_t)(row / g.remap_rows) * g.remap_gs + (int64_t)(row % g.remap_rows) * g.remap_rs + (int64_t)col * g.remap_cs] = v;
-        else g.out[(int64_t)row * g.ldo + (col < g.sigma_cols ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col)] = v;
+        float gt = 0.0f;
+        if constexpr (EPI == EPI_GLU) gt = gate[lane][i];
+        const float v = epi_finish<EPI>(acc[i], g.bias != nullptr, bias, gt, bias_g, 0.0f, 0.0f, false);   // (no residual form)
+        if constexpr (DW) glu[i] = v;
+        else gemm_store(g, row, col, v);
     }
     if constexpr (DW) {
-        const int ocol = dw.out_sigma ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col;
+        const int ocol = dw.out_sigma ? sigma_col(col) : col;
         auto tail = [&](auto cc) {
             constexpr int C = decltype(cc)::value;
 #pragma unroll
@@ -436,14 +382,7 @@ __global__ __launch_bounds__(256) void gemm_smallm_ln_kernel(GemmArgs g, DwTail 
 #pragma unroll
                 for (int f = 0; f < C; ++f) cat[8 + f] = glu[j * C + f];
 #pragma unroll
-                for (int f = 0; f < C; ++f) {
-                    float a2 = 0.0f;
-#pragma unroll
-                    for (int kk = 0; kk < 9; ++kk) a2 = __builtin_fmaf(dwk[kk], cat[f + kk], a2);      // depthwise, no padding (:71)
-                    float y = a2 + dbs;
-                    y = __builtin_fmaf((y - dmu) * drs, dbg, dbb);
-                    g.out[(int64_t)(rw0 + f) * g.ldo + ocol] = dsiluf(y);
-                }
+                for (int f = 0; f < C; ++f) g.out[(int64_t)(rw0 + f) * g.ldo + ocol] = dwconv_point<9>(dwk, cat + f, dbs, dmu, drs, dbg, dbb);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) dw.cache_out[(sidx * 8 + q) * g.N + col] = cat[q + C];
             }

@@ -40,10 +40,10 @@
 // tests/test_gpu_smallm_bf16_gemm.py: every launch form alone, at operand pitches, the whole of every output buffer handed back).
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 #include <utility>
 #include "../pk_devmath.h"
 #include "kernels.hpp"
+#include "gemm_epi.hpp"
 
 namespace pk {
 
@@ -115,22 +115,9 @@ __global__ __launch_bounds__(64 * kSbMaxWaves) void gemm_smallm_bf16_kernel(Gemm
     }
     // conv tail: the cached rows of this lane's streams (rows m0 + 4 kq .. + 3 = 4 / c streams of c frames) and the conv's parameters of its
     // channel, requested before the weight stream like the operands above
-    [[maybe_unused]] float dpre[4][8], dwk[9], dbs = 0.0f, dmu = 0.0f, drs = 0.0f, dbg = 0.0f, dbb = 0.0f;
+    [[maybe_unused]] DwTailRegs tail;
     if constexpr (DW) {
-        if (wave == 0 && col < g.N && 4 * kq < rvalid) {
-            const int nstr = 4 / dw.c;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int rw = m0 + 4 * kq + j * dw.c;
-                const bool on = j < nstr && rw < g.M && dw.has_cache;
-                const int64_t sidx = on ? rw / dw.c : 0;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) dpre[j][q] = on ? dw.cache_in[(sidx * 8 + q) * g.N + col] : 0.0f;   // (first chunk: zero left padding, :55-63)
-            }
-#pragma unroll
-            for (int kk = 0; kk < 9; ++kk) dwk[kk] = dw.w[kk * g.N + col];
-            dbs = dw.bias[col]; dmu = dw.bn_mean[col]; drs = dw.bn_rstd[col]; dbg = dw.bn_g[col]; dbb = dw.bn_b[col];
-        }
+        if (wave == 0 && col < g.N && 4 * kq < rvalid) tail.load(dw, g, m0, kq, col);
     }
 
     sb_f32x4 acc[NW][CT][RT];
@@ -261,8 +248,9 @@ __global__ __launch_bounds__(64 * kSbMaxWaves) void gemm_smallm_bf16_kernel(Gemm
                     *reinterpret_cast<float4 *>(&bet[wave][4 * lane]) = bv;
                 }
             };
-            // statistics of the rows (oracle layer_norm: the mean, then the mean of the squared deviations), two passes over the registers; the
-            // slices' partial sums meet in LDS, added in wave order (two barriers, executed by every wave)
+            // statistics of the rows, two passes over the registers; the slices' partial sums meet in LDS, added in wave order (two barriers,
+            // executed by every wave).  A decomposition of its own (K slices across waves), not the one-wave-per-row ln_row_stats of the fp32 kernels:
+            // the specification is layer_norm of oracle/pk_oracle.c (the mean, then the mean of the squared deviations), within the mode's tolerance.
             auto row_stats = [&]() {
 #pragma unroll
                 for (int t = 0; t < RT; ++t) {
@@ -400,20 +388,7 @@ __global__ __launch_bounds__(64 * kSbMaxWaves) void gemm_smallm_bf16_kernel(Gemm
     for (int i = 0; i < 4; ++i) {
         const int row = m0 + 16 * t + 4 * kq + i;
         if (4 * kq + i >= rvalid || row >= g.M) continue;
-        float o = v[i];
-        if (g.bias) o = o + bias;
-        if constexpr (EPI == EPI_RELU) {
-            o = o > 0.0f ? o : 0.0f;
-        } else if constexpr (EPI == EPI_SILU) {
-            o = g.fast_act ? fast_siluf(o) : dsiluf(o);
-        } else if constexpr (EPI == EPI_RESID) {
-            const float y = o * g.alpha;
-            o = res[i] + y;
-        } else if constexpr (EPI == EPI_GLU) {
-            float gg = gt[i];
-            if (g.bias) gg = gg + bias_g;
-            o = o * (g.fast_act ? fast_sigmoidf(gg) : dsigmoidf(gg));
-        }
+        const float o = epi_finish<EPI>(v[i], g.bias != nullptr, bias, gt[i], bias_g, res[i], g.alpha, g.fast_act != 0);
         if constexpr (DW) { glu[i] = o; continue; }
         if (g.out_t8) reinterpret_cast<__bf16 *>(g.out)[((int64_t)(row >> 3) * (g.ldo >> 5) + (col >> 5)) * 256 + ((row & 7) + 8 * ((col & 31) >> 3)) * 8 + (col & 7)] = (__bf16)o;
         else if (g.out_bf16) reinterpret_cast<__bf16 *>(g.out)[(int64_t)row * g.ldo + col] = (__bf16)o;
@@ -421,37 +396,9 @@ __global__ __launch_bounds__(64 * kSbMaxWaves) void gemm_smallm_bf16_kernel(Gemm
     }
     if constexpr (DW) {
         // depthwise conv over [cached 8 rows ; the c new GLU rows] of (stream, channel), BatchNorm, SiLU; the last 8 rows of the concatenation
-        // are the stream's cache for the next chunk (stream_dwconv_kernel, kernels/stream.hip: the same operations in the same order)
+        // are the stream's cache for the next chunk (DwTailRegs, gemm_epi.hpp)
         if (4 * kq >= rvalid) return;
-        const int ocol = dw.out_sigma ? ((col & ~15) | ((col & 3) << 2) | ((col >> 2) & 3)) : col;
-        auto tail = [&](auto cc) {
-            constexpr int C = decltype(cc)::value;
-#pragma unroll
-            for (int j = 0; j < 4 / C; ++j) {
-                const int rw = m0 + 4 * kq + j * C;
-                if (rw >= g.M) continue;
-                const int64_t sidx = rw / C;
-                float cat[8 + C];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) cat[q] = dpre[j][q];
-#pragma unroll
-                for (int f = 0; f < C; ++f) cat[8 + f] = glu[j * C + f];
-#pragma unroll
-                for (int f = 0; f < C; ++f) {
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int kk = 0; kk < 9; ++kk) acc = __builtin_fmaf(dwk[kk], cat[f + kk], acc);
-                    float y = acc + dbs;
-                    y = __builtin_fmaf((y - dmu) * drs, dbg, dbb);
-                    g.out[(int64_t)(rw + f) * g.ldo + ocol] = dsiluf(y);
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) dw.cache_out[(sidx * 8 + q) * g.N + col] = cat[q + C];
-            }
-        };
-        if (dw.c == 1) tail(std::integral_constant<int, 1>{});
-        else if (dw.c == 2) tail(std::integral_constant<int, 2>{});
-        else tail(std::integral_constant<int, 4>{});
+        tail.finish(dw, g, m0, kq, col, glu);
     }
     SB_STAMP(6);
 }

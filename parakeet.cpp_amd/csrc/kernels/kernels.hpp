@@ -84,7 +84,7 @@ enum GemmEpi { EPI_NONE = 0, EPI_RELU = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_GLU 
 // gemm_smallm_bf16.hip; exact mode: gemm_smallm_ln_kernel of gemm_smallm.hip): the lane that
 // finishes column ch of a stream's c new frames holds everything the conv of (stream, ch) needs next to the stream's cached 8 frames -- no
 // exchange, one launch less per block.  Rows of the product = [S][c] stream-major; GemmArgs::out receives the conv module's activations
-// (the GLU values themselves are not stored).  Same operations in the same order as stream_dwconv_kernel: bit-identical.
+// (the GLU values themselves are not stored).  Both tails (gemm_epi.hpp: DwTailRegs) call the dwconv_point that stream_dwconv_kernel calls.
 struct DwTail {
     const float *cache_in = nullptr; float *cache_out = nullptr;     // [S][8][d]: the last 8 GLU rows of every stream before / after this chunk
     int has_cache = 0, c = 0;                                        // first chunk: zero left padding; c = new frames per stream (1, 2 or 4)

@@ -42,22 +42,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
     for (int r = 0; r < RPW; ++r) {
         const int64_t row = row0 + r;
         if (row >= rows) break;
-        float p = 0.0f;
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j)
-            if (lane + 64 * j < d) p = p + v[r][j];
-        const float mean = wave_sum64(p) / (float)d;
-        float q = 0.0f;
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j) {
-            const int i = lane + 64 * j;
-            if (i < d) {
-                const float c = v[r][j] - mean;
-                q = q + c * c;
-            }
-        }
-        const float var = wave_sum64(q) / (float)d;
-        const float rstd = 1.0f / __builtin_sqrtf(var + eps);
+        float mean, rstd;
+        ln_row_stats<PER_LANE>(v[r], lane, d, eps, mean, rstd);
         float *yr = y + row * d;
         __bf16 *yh = reinterpret_cast<__bf16 *>(y) + row * d;      // bf16 mode: the consuming GEMM's operand, rounded here instead of there
 #pragma unroll
@@ -66,7 +52,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
             if (i < d) {
                 const float o = __builtin_fmaf((v[r][j] - mean) * rstd, gv[j], bv[j]);
                 if (y_bf16 == 1) yh[i] = (__bf16)o;
-                else if (y_bf16 == 2) yr[(i & ~15) | ((i & 3) << 2) | ((i >> 2) & 3)] = o;   // sigma K layout (kernels.hpp: GemmArgs::a_sigma)
+                else if (y_bf16 == 2) yr[sigma_col(i)] = o;   // sigma K layout (kernels.hpp: GemmArgs::a_sigma)
                 else yr[i] = o;
             }
         }
@@ -75,7 +61,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
 
 // Two LayerNorms back to back on the same row: y1 = LN(x; g1, b1) (a block's final_norm_, src/encoder.cpp:202) and
 // y2 = LN(y1; g2, b2) (the next block's ffn1_ norm, :40) -- the row stays in registers, one read of x instead of two, one launch
-// instead of two.  Every value goes through exactly the operations of two layernorm_kernel passes (same sum64 butterflies).
+// instead of two.  Every value goes through the operations of two layernorm_kernel passes (the same ln_row_stats, the same fma).
 template <int PER_LANE>
 __global__ __launch_bounds__(256) void layernorm2_kernel(const float *__restrict__ x, int64_t rows, int d, const float *__restrict__ g1,
                                                          const float *__restrict__ b1, const float *__restrict__ g2,
@@ -97,35 +83,22 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(const float *__restrict
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         float *yr = (pass ? y2 : y1) + row * d;
-        float p = 0.0f;
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j)
-            if (lane + 64 * j < d) p = p + v[j];
-        const float mean = wave_sum64(p) / (float)d;
-        float q = 0.0f;
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j)
-            if (lane + 64 * j < d) {
-                const float c = v[j] - mean;
-                q = q + c * c;
-            }
-        const float var = wave_sum64(q) / (float)d;
-        const float rstd = 1.0f / __builtin_sqrtf(var + eps);
+        float mean, rstd;
+        ln_row_stats<PER_LANE>(v, lane, d, eps, mean, rstd);
 #pragma unroll
         for (int j = 0; j < PER_LANE; ++j) {
             const int i = lane + 64 * j;
             if (i < d) {
                 v[j] = __builtin_fmaf((v[j] - mean) * rstd, gv[pass][j], bv[pass][j]);
                 if (pass && y2_bf16 == 1) (reinterpret_cast<__bf16 *>(y2) + row * d)[i] = (__bf16)v[j];
-                else if (pass && y2_bf16 == 2) yr[(i & ~15) | ((i & 3) << 2) | ((i >> 2) & 3)] = v[j];
+                else if (pass && y2_bf16 == 2) yr[sigma_col(i)] = v[j];
                 else yr[i] = v[j];
             }
         }
     }
 }
 // Statistics of the rows of x -- or, THEN = true, y1 = LN(x; g1, b1) written out and the statistics of y1's rows: the first half of layernorm_kernel /
-// the first one and a half passes of layernorm2_kernel, operation for operation (the same strided partial sums, the same wave_sum64 butterflies, the
-// same divisions and the same 1 / sqrt) -- stats[row] = {mean, rstd}.  The consumer (gemm_pipe.hpp, LNA) applies fma((x - mean) * rstd, gamma, beta).
+// the first one and a half passes of layernorm2_kernel (the ln_row_stats they call) -- stats[row] = {mean, rstd}.  The consumer (gemm_pipe.hpp, LNA) applies fma((x - mean) * rstd, gamma, beta).
 template <int PER_LANE, bool THEN>
 __global__ __launch_bounds__(256) void layernorm_stats_kernel(const float *__restrict__ x, int64_t rows, int d, const float *__restrict__ g1,
                                                               const float *__restrict__ b1, float eps, float *__restrict__ y1, float *__restrict__ stats) {
@@ -144,20 +117,8 @@ __global__ __launch_bounds__(256) void layernorm_stats_kernel(const float *__res
     }
 #pragma unroll
     for (int pass = 0; pass < (THEN ? 2 : 1); ++pass) {
-        float p = 0.0f;
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j)
-            if (lane + 64 * j < d) p = p + v[j];
-        const float mean = wave_sum64(p) / (float)d;
-        float q = 0.0f;
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j)
-            if (lane + 64 * j < d) {
-                const float c = v[j] - mean;
-                q = q + c * c;
-            }
-        const float var = wave_sum64(q) / (float)d;
-        const float rstd = 1.0f / __builtin_sqrtf(var + eps);
+        float mean, rstd;
+        ln_row_stats<PER_LANE>(v, lane, d, eps, mean, rstd);
         if (pass == (THEN ? 1 : 0)) {
             if (lane == 0) *reinterpret_cast<float2 *>(stats + 2 * row) = make_float2(mean, rstd);
         } else {

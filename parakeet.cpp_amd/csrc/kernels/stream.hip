@@ -341,7 +341,8 @@ void launch_stream_attention(const float *qkv_new, const float *kcache, const fl
 
 // One thread per (stream, channel).  Everything the thread reads -- its column of [cache ; g] (KC - 1 + c values), the KC taps, bias and the four
 // BatchNorm parameters -- is requested in ONE round trip (the first version walked the frames one by one: a dependent round trip per frame and one
-// more for the cache copy; c <= CMAX, longer chunks take the frame loop below).  Same taps in the same order: same bits.
+// more for the cache copy; c <= CMAX, longer chunks take the frame loop below, which reads its operands per tap).  Every output of the
+// register path is a dwconv_point (pk_devmath.h) -- what the conv tails of the small-M GEMMs call (gemm_epi.hpp: DwTailRegs).
 template <int KC, int CMAX>
 __global__ void stream_dwconv_kernel(const float *__restrict__ g, const float *__restrict__ cache_in, int has_cache, int c, int d,
                                      const float *__restrict__ w /*[KC][d]*/, const float *__restrict__ bias, const float *__restrict__ bn_mean,
@@ -351,7 +352,7 @@ __global__ void stream_dwconv_kernel(const float *__restrict__ g, const float *_
     if (idx >= n) return;
     const int ch = (int)(idx % d), sidx = (int)(idx / d);
     constexpr int CL = KC - 1;
-    const int ocol = out_sigma ? ((ch & ~15) | ((ch & 3) << 2) | ((ch >> 2) & 3)) : ch;
+    const int ocol = out_sigma ? sigma_col(ch) : ch;
     if (c <= CMAX) {
         // (no branch around a load: clamped indices, the first chunk's zero left padding (:55-63) applied after the loads)
         float cat[CL + CMAX], wk[KC];
@@ -368,14 +369,7 @@ __global__ void stream_dwconv_kernel(const float *__restrict__ g, const float *_
         }
 #pragma unroll
         for (int t = 0; t < CMAX; ++t) {
-            if (t < c) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int kk = 0; kk < KC; ++kk) acc = __builtin_fmaf(wk[kk], cat[t + kk], acc);      // depthwise, no padding (:71)
-                float v = acc + bs;
-                v = __builtin_fmaf((v - mu) * rs, bg, bb);
-                out[((int64_t)sidx * c + t) * d + ocol] = dsiluf(v);
-            }
+            if (t < c) out[((int64_t)sidx * c + t) * d + ocol] = dwconv_point<KC>(wk, cat + t, bs, mu, rs, bg, bb);   // depthwise, no padding (:71)
         }
         // last KC - 1 rows of the concatenation (:66-69): rows c .. c + CL - 1
 #pragma unroll

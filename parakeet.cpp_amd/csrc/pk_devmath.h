@@ -292,4 +292,35 @@ __device__ __forceinline__ float wave_max64(float p) {
     return p;
 }
 
+// LayerNorm statistics of one row of d elements held by one wave, lane l holding elements l + 64 j in v[j]: the strided partial sum and the
+// canonical sum64 butterfly for the mean, the same over the centred squares for the variance, rstd = 1 / sqrt(var + eps).  Every kernel that
+// promises layernorm_kernel's bits calls this.
+template <int PER_LANE>
+__device__ __forceinline__ void ln_row_stats(const float (&v)[PER_LANE], int lane, int d, float eps, float &mean, float &rstd) {
+    float p = 0.0f;
+#pragma unroll
+    for (int j = 0; j < PER_LANE; ++j)
+        if (lane + 64 * j < d) p = p + v[j];
+    mean = wave_sum64(p) / (float)d;
+    float q = 0.0f;
+#pragma unroll
+    for (int j = 0; j < PER_LANE; ++j)
+        if (lane + 64 * j < d) {
+            const float c = v[j] - mean;
+            q = q + c * c;
+        }
+    const float var = wave_sum64(q) / (float)d;
+    rstd = 1.0f / __builtin_sqrtf(var + eps);
+}
+
+// One output of the conv module's depthwise conv (no padding) + bias + BatchNorm + SiLU: KC fmas in tap order over cat[0 .. KC - 1].
+template <int KC>
+__device__ __forceinline__ float dwconv_point(const float (&wk)[KC], const float *cat, float bs, float mu, float rs, float bg, float bb) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) acc = __builtin_fmaf(wk[kk], cat[kk], acc);
+    const float v = acc + bs;
+    return dsiluf(__builtin_fmaf((v - mu) * rs, bg, bb));
+}
+
 }  // namespace pk
