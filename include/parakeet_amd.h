@@ -1255,6 +1255,12 @@ int pk_diag_conv_instantiations(int32_t *out, int cap_rows);
  * window of its rows; limited-context attention (pk_model_set_attention_context) uses neither.  Reads two host integers: no device is needed.
  * (tests/test_gpu_call_history.py asserts with it that a call ran on a table built for a longer one.) */
 pk_status pk_diag_pos_table_frames(const pk_model *m, int32_t out[2]);
+/* How the last chunk of a streaming session ran its Conformer blocks: out[0] the chunk's rows (streams x encoder frames), out[1] 1 if the fp32
+ * small-M family ran it (ctx and conv output in the sigma layout, tiled weight copies), out[2] 1 if the bf16 mode ran it on the bf16 operand
+ * tiles, out[3] 1 if the depthwise conv rode on the epilogue of the pw1 product.  A push that buffered everything (no encoder frame) leaves the
+ * words as they were; all zero before the first chunk, and pk_stream_reset does not clear them.  Reads four host integers: no device is needed.
+ * (tests/test_gpu_stream_history.py asserts with it that a session ran on both sides of the row-count switch.) */
+pk_status pk_diag_stream_chunk_form(const pk_stream *s, int32_t out[4]);
 /* ONE launch of a skinny product of the TDT / RNNT decode loop (kernels/decode_gemv.hip, kernels/decode_gemv_bf16.hip; kernels.hpp SkinnyArgs).
  * Every operand is given in its NATURAL layout as fp32 and packed here by the functions the loader packs with (csrc/dec_pack.hpp): fp32 mode = the
  * sigma K order of X / W / X2 / W2; bf16 mode = X / X2 rounded to bf16 (RNE), W / W2 in the kernel's per-lane tile order, rounded to bf16.

@@ -352,6 +352,7 @@ _LATE_SIGNATURES = {
     "pk_diag_conv_variants": [C.c_void_p, C.c_int, C.c_int, i32p, C.c_int, i32p],
     "pk_diag_conv_instantiations": [i32p, C.c_int],
     "pk_diag_pos_table_frames": [C.c_void_p, i32p],
+    "pk_diag_stream_chunk_form": [C.c_void_p, i32p],
     "pk_diag_relpos_local_attention": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p,
                                        C.POINTER(C.c_int)],
     "pk_diag_relpos_attention_form": [C.c_int, C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, f32p, f32p,
@@ -1600,6 +1601,12 @@ class Stream:
         ms = np.zeros(1, np.float32)
         check(lib().pk_stream_endpoint_timed(self._h, _f(mel), mel.shape[1], reps, _f(ms)))
         return float(ms[0])
+
+    def chunk_form(self):
+        """pk_diag_stream_chunk_form: how the last chunk ran its blocks -> dict(rows, sg, wt, fused_conv); zeros before the first chunk."""
+        out = np.zeros(4, np.int32)
+        check(lib().pk_diag_stream_chunk_form(self._h, _i(out)))
+        return dict(rows=int(out[0]), sg=int(out[1]), wt=int(out[2]), fused_conv=int(out[3]))
 
     def reset(self):
         check(lib().pk_stream_reset(self._h))

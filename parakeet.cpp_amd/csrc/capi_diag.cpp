@@ -2,6 +2,7 @@
 // operands the caller hands over, for the kernel-level tests: math, LayerNorm, attention, mel, conv, decode and memory (the products are in
 // capi_diag_gemm.cpp).  Nothing here is kept between calls: every call stages its operands afresh, through the helpers of capi_diag_util.hpp.
 #include "capi_diag_util.hpp"
+#include "stream.hpp"
 
 using namespace pk;
 using namespace pk::diag;
@@ -608,6 +609,12 @@ pk_status pk_diag_pos_table_frames(const pk_model *h, int32_t out[2]) {
         need(h && out, "model/out");
         out[0] = h->m->pos32.T;
         out[1] = h->m->pos16.T;
+    });
+}
+pk_status pk_diag_stream_chunk_form(const pk_stream *h, int32_t out[4]) {
+    return guard([&] {
+        need(h && out, "stream/out");
+        memcpy(out, h->s->chunk_form(), 4 * sizeof(int32_t));
     });
 }
 

@@ -185,6 +185,7 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
     // Tolerance-class mode (pk_config.gemm_bf16; specification: the oracle's Stream in its gemm_bf16 mode): every product of the chunk takes bf16
     // operands; attention, depthwise conv and the caches stay fp32 arithmetic on the products' fp32 outputs.
     const int a16 = cfg.gemm_bf16 ? 1 : 0;
+    chunk_form_[0] = (int32_t)rows; chunk_form_[1] = sg; chunk_form_[2] = wt ? 1 : 0; chunk_form_[3] = 0;
     BlockMode mode;
     mode.bf16 = a16; mode.sigma = sg; mode.copies = (sg || wt) ? sig_ : nullptr; mode.copies_t16 = wt;
     mode.fold_bf16 = true; mode.handoff = BlockMode::TILES8;
@@ -216,7 +217,7 @@ int StreamBatch::encode_device(const float *d_mel, int n_frames) {
             // (tolerance-class mode: with or without the folded norm; exact mode: the tail lives in the kernel with the norm folded in)
             const bool fused_dw = a16 ? gemm_smallm_bf16_dw_applies(probe, EPI_GLU, c, K) && gemm_smallm_bf16_dw_applies(g, EPI_GLU, c, K)
                                       : sg && gemm_smallm_dw_applies(probe, EPI_GLU, c, K);
-            if (fused_dw) { g.dw_tail = &tail; g.out = ws_.dwb.as<float>(); }
+            if (fused_dw) { g.dw_tail = &tail; g.out = ws_.dwb.as<float>(); chunk_form_[3] = 1; }
             blk.pw1(l, g);
             if (!fused_dw)
                 launch_stream_dwconv(ws_.g.as<float>(), Ls.conv[Ls.ccur].as<float>(), Ls.has_conv, S, c, d, K, L.dw_w, L.dw_b, L.bn_mean, L.bn_rstd, L.bn_g, L.bn_b,

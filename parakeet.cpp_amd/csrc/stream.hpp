@@ -51,6 +51,8 @@ class StreamBatch {
                        pk_endpoint_event *events, int cap, int *n_events, pk_kws_event *kws_events, int kws_cap, int *kws_n_events);
     void reset_decoder(const uint8_t *mask);
     Model &model() { return m_; }
+    // {rows, sg, wt, conv fused into pw1} of the last chunk encode_device ran the blocks for (zeros before the first); pk_diag_stream_chunk_form
+    const int32_t *chunk_form() const { return chunk_form_; }
     int S;
 
   private:
@@ -66,6 +68,7 @@ class StreamBatch {
     std::vector<std::unique_ptr<LayerState>> layers_;
     const std::vector<Model::SigW> *sig_ = nullptr;      // the model's tiled weight copies (Model::sigma_weights); empty: natural operands
     int frame_offset_ = 0;
+    int32_t chunk_form_[4] = {0, 0, 0, 0};
     Workspace ws_;              // encoder workspace of the current chunk
     Workspace wd_;              // decode workspace: h / c / token persist across chunks (never re-allocated)
     int dec_cap_frames_ = 0;

@@ -392,6 +392,14 @@ def test_pos_table_diagnostic_reads_a_model_without_a_device(tmp_path):
     m.close()
 
 
+def test_stream_chunk_form_diagnostic_is_exported_and_refuses_null():
+    """pk_diag_stream_chunk_form (what tests/test_gpu_stream_history.py asks after every chunk) reads four host integers of a session: declared,
+    exported, bound, and null arguments are PK_ERR_INVALID with the caller's words left alone (a session itself needs a device)."""
+    assert "pk_diag_stream_chunk_form" in declared_symbols() and hasattr(capi.lib(), "pk_diag_stream_chunk_form")
+    out = np.full(4, 7, np.int32)
+    assert capi.lib().pk_diag_stream_chunk_form(None, out.ctypes.data_as(C.POINTER(C.c_int32))) == -1 and out.tolist() == [7, 7, 7, 7]
+
+
 def test_mel_diagnostic_refuses_before_it_looks_for_a_device():
     """pk_diag_mel (what tests/test_gpu_mel_forms.py launches the front end through) checks its arguments on the host: a clip the reflect padding
     cannot frame, a chunk shorter than one window, a bin count or buffers it cannot take are PK_ERR_INVALID with or without a device, and the
