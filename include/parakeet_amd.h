@@ -132,6 +132,14 @@ pk_status pk_model_set_decode_loop(pk_model *m, int mode);
  * Switching back to (-1, -1) gives exactly the results of a model that never set it.  Not to be changed while a batch is in flight. */
 pk_status pk_model_set_attention_context(pk_model *m, int left, int right);
 pk_status pk_model_get_attention_context(const pk_model *m, int *left, int *right);
+/* MXFP8 feed-forward products (opt-in, gemm_bf16 models only; any other model: PK_ERR_UNSUPPORTED -- the fp32 mode's contract is bit equality).
+ * on != 0: fc1 + SiLU and fc2 + residual of every Conformer block of the offline encoder run on gfx950's block-scaled matrix instruction with both
+ * operands in the OCP MX format MXFP8 (e4m3 elements, one E8M0 scale per 32 k), for batches of more rows than the small-M bf16
+ * kernel takes (128).  The first call quantises the feed-forward weights once (+ 0.52 of their bf16 bytes in HBM).  Smaller batches, every other
+ * product and the streaming path keep their kernels and their bits; on = 0 gives exactly the results of a model that never set it.  Results are in
+ * the tolerance class of the gemm_bf16 mode, farther from fp32 than bf16 is (tests/test_gpu_ffn_mxfp8.py).  Not to be changed while a batch is in flight. */
+pk_status pk_model_set_ffn_mxfp8(pk_model *m, int on);
+pk_status pk_model_get_ffn_mxfp8(const pk_model *m, int *on);
 
 /* ---- stage entry points (host buffers; used by the parity tests and the C++ facade) ----------------------- */
 /* preprocess_audio (src/audio.cpp:100-158): n_clips clips of n_samples each -> feats[n_clips][n_frames][mel_bins],
@@ -1592,6 +1600,27 @@ pk_status pk_diag_gemm_smallm_bf16(pk_gemm_smallm_bf16_diag *a);
 int pk_diag_gemm_smallm_bf16_forms(int32_t *out, int cap);
 pk_status pk_diag_gemm_smallm_bf16_form(pk_gemm_smallm_bf16_diag *a);
 pk_status pk_diag_tile_copy_bf16(const float *src, int64_t rows, int K, int64_t ld, uint16_t *dst);
+/* The MXFP8 kernels alone (kernels/gemm_mxfp8.hip; the format: DESIGN.md section 5.2.1).  An MX operand of `rows` rows x K elements comes back as its WHOLE
+ * device buffers with the layout's permutation undone: element bytes [R][128 ceil(K / 128)] and scale bytes [R][8 ceil(K / 256)], R = rows rounded up to
+ * 8, k ascending in a row; both buffers are filled with 0x7FC5A5A5 before the launch, so what it never wrote (rows past `rows`, k past K) shows the fill.
+ * pk_diag_mx_quantize: the quantiser on src [rows][ld] at that pitch (NaN behind every row on the device) -- fp32 rows (ld % 4 == 0: the weights' form),
+ *   or, src_bf16 != 0, rounded to bf16 on the host first and read as bf16 (ld % 8 == 0: the LayerNorm rows' form).  K % 32 == 0.
+ * pk_diag_gemm_mxfp8: ONE product.  A [M][lda] (rounded to bf16 on the host, quantised by the row quantiser), W [N][ldw] fp32 (quantised by the weight
+ *   quantiser), K % 64 == 0, N % 32 == 0.  epi 0: out [M][ldo] fp32 = acc + bias; epi 2: out = resid [M][ldr] + alpha (acc + bias); both come back as the
+ *   whole out_words words (filled first).  epi 1: the output (silu != 0: SiLU of it, on the hardware exp2 / rcp) quantised by the tile itself into an MX
+ *   operand of M rows x N elements -> outq / outs as above.  bm / bn receive the tile of the launch.  PK_ERR_INVALID: malformed arguments. */
+pk_status pk_diag_mx_quantize(const float *src, int64_t rows, int K, int64_t ld, int src_bf16, uint8_t *q, uint8_t *scales);
+typedef struct pk_gemm_mxfp8_diag {
+    int32_t M, N, K, epi, silu;
+    const float *A; int64_t lda;
+    const float *W; int64_t ldw;
+    const float *bias;
+    const float *resid; int64_t ldr; float alpha;
+    int64_t ldo, out_words; uint32_t *out;
+    uint8_t *outq, *outs;
+    int32_t bm, bn;
+} pk_gemm_mxfp8_diag;
+pk_status pk_diag_gemm_mxfp8(pk_gemm_mxfp8_diag *a);
 
 /* ---- neural LM rescoring: n-best reranking with a Transformer LM after beam search (the reference's roadmap, README.md "Neural LM rescoring") ------
  * A causal Transformer LM over the acoustic model's own token ids plus BOS and EOS: token and position embeddings, the blocks of

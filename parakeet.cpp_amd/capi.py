@@ -334,6 +334,8 @@ _LATE_SIGNATURES = {
     "pk_model_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_get_attention_context": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
+    "pk_model_set_ffn_mxfp8": [C.c_void_p, C.c_int],
+    "pk_model_get_ffn_mxfp8": [C.c_void_p, C.POINTER(C.c_int)],
     "pk_resample_length": [C.c_int64, C.c_int, C.c_int],
     "pk_resample_run": [C.c_int, C.c_int],
     "pk_resample_table": [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -2360,6 +2362,62 @@ def diag_tile_copy_bf16(src, K=None):
     return dst
 
 
+class PkGemmMxfp8Diag(C.Structure):
+    _u8p = C.POINTER(C.c_uint8)
+    _fields_ = ([(k, C.c_int32) for k in ("M", "N", "K", "epi", "silu")]
+                + [("A", f32p), ("lda", C.c_int64), ("W", f32p), ("ldw", C.c_int64), ("bias", f32p), ("resid", f32p), ("ldr", C.c_int64), ("alpha", C.c_float),
+                   ("ldo", C.c_int64), ("out_words", C.c_int64), ("out", C.POINTER(C.c_uint32)), ("outq", _u8p), ("outs", _u8p), ("bm", C.c_int32), ("bn", C.c_int32)])
+
+
+_LATE_SIGNATURES["pk_diag_gemm_mxfp8"] = [C.POINTER(PkGemmMxfp8Diag)]
+_LATE_SIGNATURES["pk_diag_mx_quantize"] = [f32p, C.c_int64, C.c_int, C.c_int64, C.c_int, PkGemmMxfp8Diag._u8p, PkGemmMxfp8Diag._u8p]
+MX_EPI = {"f32": 0, "mx": 1, "resid": 2}
+
+
+def _mx_back(rows, K):
+    """the two arrays an MX operand of rows x K comes back in (include/parakeet_amd.h): bytes [R][128 ceil(K / 128)], scale bytes [R][8 ceil(K / 256)]"""
+    R = (rows + 7) // 8 * 8
+    return np.zeros((R, (K + 127) // 128 * 128), np.uint8), np.zeros((R, (K + 255) // 256 * 8), np.uint8)
+
+
+def diag_mx_quantize(src, K=None, src_bf16=False):
+    """pk_diag_mx_quantize: the MXFP8 quantiser on src [rows][ld >= K] (src_bf16: rounded to bf16 first, the LayerNorm rows' form) -> (bytes, scale bytes),
+    the WHOLE device buffers row-major: what the launch never wrote (rows past `rows`, k past K) holds the bytes of SKINNY_FILL32."""
+    src = _c(src)
+    rows, ld = src.shape
+    K = ld if K is None else int(K)
+    q, s = _mx_back(rows, K)
+    u8p = PkGemmMxfp8Diag._u8p
+    check(lib().pk_diag_mx_quantize(_f(src), rows, K, ld, int(bool(src_bf16)), q.ctypes.data_as(u8p), s.ctypes.data_as(u8p)))
+    return q, s
+
+
+def diag_gemm_mxfp8(A, W, bias=None, epi="f32", silu=False, resid=None, alpha=1.0, lda=None, ldw=None, ldo=None, ldr=None, out_words=None):
+    """pk_diag_gemm_mxfp8: one MXFP8 product alone.  A [M][K] (rounded to bf16, then the row quantiser), W [N][K] fp32 (the weight quantiser), staged at the
+    pitches lda / ldw / ldr.  Returns dict(tile = (bm, bn)) with out = the WHOLE fp32 output buffer as uint32 words (epi "f32" / "resid"), or q, s = the
+    output as an MX operand (epi "mx"; silu: SiLU first), as diag_mx_quantize returns one."""
+    A, W = _c(A), _c(W)
+    (M, K), N = A.shape, W.shape[0]
+    assert W.shape[1] == K
+    A, W = _pitched(A, lda), _pitched(W, ldw)
+    keep = _Keep(A, W)
+    d = PkGemmMxfp8Diag()
+    d.M, d.N, d.K, d.epi, d.silu = M, N, K, MX_EPI[epi], int(bool(silu))
+    d.A, d.lda, d.W, d.ldw, d.bias, d.alpha = _f(A), A.shape[1], _f(W), W.shape[1], keep.opt(bias), alpha
+    if resid is not None:
+        resid = _pitched(_c(resid), ldr)
+        d.resid, d.ldr = keep.opt(resid), resid.shape[1]
+    _out_words_default(d, M, N, ldo, out_words)
+    out = np.zeros(max(d.out_words, 1), np.uint32)
+    q, s = _mx_back(M, N)
+    u8p = PkGemmMxfp8Diag._u8p
+    d.out, d.outq, d.outs = out.ctypes.data_as(C.POINTER(C.c_uint32)), q.ctypes.data_as(u8p), s.ctypes.data_as(u8p)
+    check(lib().pk_diag_gemm_mxfp8(C.byref(d)))
+    r = dict(tile=(d.bm, d.bn))
+    r.update(dict(q=q, s=s) if epi == "mx" else dict(out=out[:d.out_words]))
+    return r
+
+
 class Batch:
     """pk_batch: the resident pipeline (clips of one length stay in HBM; decode(k) overlaps encoder(k+1))."""
 
@@ -2650,6 +2708,15 @@ class Model:
         l, r = C.c_int(0), C.c_int(0)
         check(lib().pk_model_get_attention_context(self._h, C.byref(l), C.byref(r)))
         return l.value, r.value
+
+    def set_ffn_mxfp8(self, on=True):
+        """pk_model_set_ffn_mxfp8: the feed-forward products of the offline encoder on MXFP8 operands (gemm_bf16 models only; batches of more than 128 rows)."""
+        check(lib().pk_model_set_ffn_mxfp8(self._h, int(bool(on))))
+
+    def ffn_mxfp8(self):
+        on = C.c_int(0)
+        check(lib().pk_model_get_ffn_mxfp8(self._h, C.byref(on)))
+        return bool(on.value)
 
     def set_input_rate(self, rate):
         """pk_model_set_input_rate: the one-call entry points (transcribe_pcm, the n-best forms, align_pcm, tdt_align_pcm, tdt_score_pcm,

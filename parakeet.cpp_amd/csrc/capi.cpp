@@ -121,6 +121,14 @@ pk_status pk_model_get_attention_context(const pk_model *m, int *left, int *righ
     });
 }
 
+pk_status pk_model_set_ffn_mxfp8(pk_model *m, int on) {
+    return guard([&] { need(m, "model"); m->m->set_ffn_mxfp8(on != 0); });
+}
+
+pk_status pk_model_get_ffn_mxfp8(const pk_model *m, int *on) {
+    return guard([&] { need(m && on, "model/on"); *on = m->m->ffn_mxfp8 ? 1 : 0; });
+}
+
 pk_status pk_model_config(const pk_model *m, pk_config *out) {
     return guard([&] { need(m && out, "model/out"); *out = m->m->cfg; });
 }

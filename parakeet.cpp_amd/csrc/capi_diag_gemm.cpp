@@ -592,6 +592,86 @@ pk_status pk_diag_tile_copy_bf16(const float *src, int64_t rows, int K, int64_t 
     });
 }
 
+// ---- MXFP8 (kernels/gemm_mxfp8.hip) ----
+// An MX operand's two device buffers, filled with the pattern, and their way back: the WHOLE buffers, the layout's permutation undone -- elements
+// [mx_rows(rows)][128 mx_ktiles(K)], scale bytes [mx_rows(rows)][8 ceil(K / 256)], both row-major in k; what the launch never wrote holds the fill.
+struct MxDev {
+    DevBuf q, s;
+    int64_t rows; int K;
+    MxDev(int64_t rows_, int K_) : rows(rows_), K(K_) {
+        filled(q, (int64_t)(mx_elem_bytes(rows, K) / 4));
+        filled(s, (int64_t)((mx_scale_bytes(rows, K) + 3) / 4));
+    }
+    uint8_t *qp() { return static_cast<uint8_t *>(q.p); }
+    uint8_t *sp() { return static_cast<uint8_t *>(s.p); }
+    void back(uint8_t *hq, uint8_t *hs) const {
+        const int64_t R = mx_rows(rows);
+        const int KP = (int)mx_ktiles(K) * 128, SB = ((K + 255) >> 8) * 8;
+        std::vector<uint8_t> tq(mx_elem_bytes(rows, K)), ts(mx_scale_bytes(rows, K));
+        down(tq.data(), q, tq.size());
+        down(ts.data(), s, ts.size());
+        for (int64_t r = 0; r < R; ++r) {
+            for (int k = 0; k < KP; ++k) hq[(size_t)r * KP + k] = tq[mx_elem_at(r, k, K)];
+            for (int kb = 0; kb < SB; ++kb) hs[(size_t)r * SB + kb] = ts[mx_scale_at(r, kb, rows)];
+        }
+    }
+};
+// src [rows][ld] on the host -> the device at that pitch (bf16: rounded on the host), the pads the pattern -> one quantiser launch
+static void mx_quantize_host(MxDev &o, DevBuf &stage, const float *src, int64_t rows, int K, int64_t ld, bool src_bf16) {
+    if (src_bf16) up16_padded(stage, src, rows, K, ld);
+    else up_padded(stage, src, rows, K, ld);
+    launch_mx_quantize(stage.p, src_bf16 ? 1 : 0, rows, K, ld, o.qp(), o.sp(), nullptr);
+}
+
+pk_status pk_diag_mx_quantize(const float *src, int64_t rows, int K, int64_t ld, int src_bf16, uint8_t *q, uint8_t *scales) {
+    return guard([&] {
+        need(src && q && scales && rows > 0 && rows <= (1 << 24) && K > 0 && K % 32 == 0 && ld >= K && ld % (src_bf16 ? 8 : 4) == 0,
+             "src/q/scales, rows > 0, K % 32 == 0, ld >= K and a multiple of 16 bytes");
+        need_device();
+        MxDev o(rows, K);
+        DevBuf st;
+        mx_quantize_host(o, st, src, rows, K, ld, src_bf16 != 0);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        o.back(q, scales);
+    });
+}
+
+pk_status pk_diag_gemm_mxfp8(pk_gemm_mxfp8_diag *d) {
+    return guard([&] {
+        need(d, "args");
+        const int M = d->M, N = d->N, K = d->K, epi = d->epi;
+        need(d->A && d->W && M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 32 == 0, "A/W, M/N/K > 0, K % 64 == 0, N % 32 == 0");
+        need(epi >= MX_EPI_F32 && epi <= MX_EPI_RESID, "epi: 0 fp32 rows, 1 MX rows, 2 resid");
+        need(d->lda >= K && d->lda % 8 == 0 && d->ldw >= K && d->ldw % 4 == 0, "lda >= K, a multiple of 8; ldw >= K, a multiple of 4");
+        need(!d->silu || epi == MX_EPI_MX, "silu comes with the MX output");
+        need(epi != MX_EPI_RESID || (d->resid && d->ldr >= N && d->ldr % 4 == 0), "resid, ldr >= N and a multiple of 4");
+        if (epi == MX_EPI_MX) need(d->outq && d->outs, "outq/outs");
+        else {
+            need(d->out && d->ldo % 4 == 0, "out, ldo a multiple of 4");
+            need_output_fits(M, N, 0, 0, 0, 0, d->ldo, d->out_words);
+        }
+        const MxTile t = gemm_mxfp8_tile(epi);
+        d->bm = t.bm; d->bn = t.bn;
+        need_device();
+        MxDev a(M, K), w(N, K), oq(M, epi == MX_EPI_MX ? N : 32);
+        DevBuf sa, sw, b, r, o;
+        mx_quantize_host(a, sa, d->A, M, K, d->lda, true);             // the row quantiser on bf16 rows, as the engine runs it
+        mx_quantize_host(w, sw, d->W, N, K, d->ldw, false);            // the weight quantiser on fp32 rows
+        if (d->bias) up(b, d->bias, (size_t)N * 4);
+        if (epi == MX_EPI_RESID) up_padded(r, d->resid, M, N, d->ldr);
+        if (epi != MX_EPI_MX) filled(o, d->out_words);
+        MxGemmArgs g{a.qp(), a.sp(), w.qp(), w.sp(), d->bias ? b.as<float>() : nullptr, M, N, K, d->silu ? 1 : 0,
+                     epi != MX_EPI_MX ? o.as<float>() : nullptr, d->ldo, epi == MX_EPI_RESID ? r.as<float>() : nullptr, d->ldr, d->alpha,
+                     epi == MX_EPI_MX ? oq.qp() : nullptr, epi == MX_EPI_MX ? oq.sp() : nullptr};
+        launch_gemm_mxfp8(g, epi, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipDeviceSynchronize());
+        if (epi == MX_EPI_MX) oq.back(d->outq, d->outs);
+        else down(d->out, o, (size_t)d->out_words * 4);
+    });
+}
+
 pk_status pk_diag_ln_gemm(int M, int N, int K, const float *A, const float *pre_gamma, const float *pre_beta, const float *gamma, const float *beta, float eps,
                           const float *W, const float *bias, int epi, int fold, float *out, float *y1) {
     return guard([&] {

@@ -104,8 +104,35 @@ struct ConformerBlock {
     // hand-off flags aside: the *_ln_applies / *_pre_applies predicates must stay blind to bias, fast_act, W_t16 and the out_t8 / out_blocked flags.)
     GemmArgs fc1_folded(int l) const { return folded(fc1_args(l, false), m.layers[l].ffn1_ng, m.layers[l].ffn1_nb); }
     bool fc1_folds(int l) const { return ln_folds(mode, fc1_folded(l), EPI_SILU); }
+    // The MXFP8 mode (Model::set_ffn_mxfp8) takes the two products of an FFN when the bf16 TILE kernels would: offline batches of the tolerance-class
+    // mode above the small-M bf16 kernel's rows.  (Streaming keeps its own kernels and activations at every row count.)
+    bool ffn_is_mx() const { return m.ffn_mxfp8 && mode.bf16 && mode.handoff == BlockMode::BLOCKED && rows > kSmallMRowsBf16; }
+    // LN -> bf16 rows (n) -> MX rows -> fc1 + SiLU, its tiles quantising their own output into fc2's A operand -> fc2 + residual.  h holds, one behind
+    // the other, the MX rows of the norm and of the activations, elements then scale bytes: about (d + f) * 33 / 32 bytes per row of its 4 f.
+    void ffn_mx(int l, bool second) {
+        const LayerW &L = m.layers[l];
+        const Model::MxLayerW &X = m.mx_layers_[l];
+        const Model::MxW &w1 = second ? X.ffn2_w1 : X.ffn1_w1, &w2 = second ? X.ffn2_w2 : X.ffn1_w2;
+        auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        uint8_t *aq = reinterpret_cast<uint8_t *>(h), *as = aq + mx_elem_bytes(rows, d), *hq = as + r16(mx_scale_bytes(rows, d)), *hs = hq + mx_elem_bytes(rows, f);
+        if ((size_t)(hs - aq) + mx_scale_bytes(rows, f) > h_cap) fail(PK_ERR_INVALID, "internal: the activation buffer is too small for the MX rows of %lld rows", (long long)rows);
+        if (second || !norm_done) timed(1.5 * rows * d * 4, [&] { launch_layernorm(x, rows, d, second ? L.ffn2_ng : L.ffn1_ng, second ? L.ffn2_nb : L.ffn1_nb, 1e-5f, n, s, 1); });
+        if (!second) norm_done = false;
+        m.klaunch_begin("mx_quantize", 0.0, (double)rows * d * (2.0 + 33.0 / 32.0), s);
+        launch_mx_quantize(n, /*src_bf16=*/1, rows, d, d, aq, as, s);
+        m.klaunch_end(s);
+        MxGemmArgs g1{aq, as, w1.q, w1.s, second ? L.ffn2_b1 : L.ffn1_b1, (int)rows, f, d, /*silu=*/1, nullptr, 0, nullptr, 0, 1.0f, hq, hs};
+        m.klaunch_begin("ffn_fc1_silu", 2.0 * rows * f * d, 0.0, s);
+        launch_gemm_mxfp8(g1, MX_EPI_MX, s);
+        m.klaunch_end(s);
+        MxGemmArgs g2{hq, hs, w2.q, w2.s, second ? L.ffn2_b2 : L.ffn1_b2, (int)rows, d, f, 0, x, d, x, d, 0.5f, nullptr, nullptr};
+        m.klaunch_begin("ffn_fc2_resid", 2.0 * rows * f * d, 0.0, s);
+        launch_gemm_mxfp8(g2, MX_EPI_RESID, s);
+        m.klaunch_end(s);
+    }
     // FeedForward::forward (src/encoder.cpp:39-46): x += 0.5 * fc2(silu(fc1(LN(x))))
     void ffn(int l, bool second) {
+        if (ffn_is_mx()) { ffn_mx(l, second); return; }
         const LayerW &L = m.layers[l];
         GemmArgs g1 = fc1_args(l, second), g2{h, f, second ? L.ffn2_w2 : L.ffn1_w2, f, second ? L.ffn2_b2 : L.ffn1_b2, x, d, x, d, 0.5f, (int)rows, d, f};
         g2.a_bf16 = mode.bf16;

@@ -473,6 +473,42 @@ const std::vector<Model::SigW> &Model::sigma_weights() {
     return sig_layers_;
 }
 
+// The MX copies of the feed-forward weights (engine.hpp), made when the mode is first switched on -- as the tiled copies above, nothing half-built survives.
+void Model::set_ffn_mxfp8(bool on) {
+    if (on && !cfg.gemm_bf16)
+        fail(PK_ERR_UNSUPPORTED, "MXFP8 feed-forward products need a gemm_bf16 model: the fp32 mode's contract is bit equality with the reference");
+    const int d = cfg.hidden_size, f = cfg.ffn_intermediate;
+    if (on && (d % 64 || f % 64)) fail(PK_ERR_UNSUPPORTED, "MXFP8 feed-forward products need hidden_size and ffn_intermediate to be multiples of 64");
+    if (on && mx_layers_.empty() && cfg.num_layers > 0) {
+        require_gpu();
+        // every quantiser output starts at a multiple of 16 bytes: the element blocks are KB, the scale bytes a multiple of 8 per 256 k -- rounded up here
+        auto r16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+        const size_t up_q = mx_elem_bytes(f, d), up_s = r16(mx_scale_bytes(f, d)), dn_q = mx_elem_bytes(d, f), dn_s = r16(mx_scale_bytes(d, f));
+        std::vector<MxLayerW> built(cfg.num_layers);
+        try {
+            mx_buf_.reserve((size_t)cfg.num_layers * 2 * (up_q + up_s + dn_q + dn_s));
+            uint8_t *p = static_cast<uint8_t *>(mx_buf_.p);
+            for (int l = 0; l < cfg.num_layers; ++l) {
+                auto quant = [&](const float *w16, int rows, int K, size_t qb, size_t sb) {
+                    MxW r{p, p + qb};
+                    launch_mx_quantize(w16, /*src_bf16=*/1, rows, K, K, p, p + qb, stream);
+                    p += qb + sb;
+                    return r;
+                };
+                built[l].ffn1_w1 = quant(layers[l].ffn1_w1, f, d, up_q, up_s); built[l].ffn1_w2 = quant(layers[l].ffn1_w2, d, f, dn_q, dn_s);
+                built[l].ffn2_w1 = quant(layers[l].ffn2_w1, f, d, up_q, up_s); built[l].ffn2_w2 = quant(layers[l].ffn2_w2, d, f, dn_q, dn_s);
+            }
+            PK_CHECK_LAUNCH();
+            PK_HIP(hipStreamSynchronize(stream));
+        } catch (...) {
+            if (mx_buf_.p) { (void)hipFree(mx_buf_.p); mx_buf_.p = nullptr; mx_buf_.cap = 0; }
+            throw;
+        }
+        mx_layers_ = std::move(built);
+    }
+    ffn_mxfp8 = on;
+}
+
 // ---- workspace ----------------------------------------------------------------------------------------------
 static inline int sub_len(int n) { return (n - 1) / 2 + 1; }        // one stride-2 stage of the subsampling (src/encoder.cpp:208-217)
 

@@ -249,6 +249,16 @@ class Model {
     DevBuf sig_buf_;
     bool sig_built_ = false;
 
+    // MXFP8 feed-forward products (pk_model_set_ffn_mxfp8; kernels/gemm_mxfp8.hip): in the tolerance-class mode, fc1 + SiLU and fc2 + residual of the
+    // offline encoder's batches above the small-M bf16 kernel's range run on the block-scaled MFMA (ConformerBlock::ffn).  The MX copies of the four
+    // feed-forward weights per layer are quantised from the resident bf16 weights when the mode is first switched on: + 0.52 of their bf16 bytes in HBM.
+    struct MxW { const uint8_t *q = nullptr, *s = nullptr; };
+    struct MxLayerW { MxW ffn1_w1, ffn1_w2, ffn2_w1, ffn2_w2; };
+    bool ffn_mxfp8 = false;
+    void set_ffn_mxfp8(bool on);
+    std::vector<MxLayerW> mx_layers_;
+    DevBuf mx_buf_;
+
     ProfileSink *prof = nullptr;
     void klaunch_begin(const char *name, double flops, double bytes, hipStream_t s);
     void klaunch_end(hipStream_t s);

@@ -918,4 +918,40 @@ struct VadArgs {
 };
 void launch_vad(const VadArgs &a, hipStream_t s);
 
+// ---- MXFP8 products on v_mfma_scale_f32_32x32x64_f8f6f4 (kernels/gemm_mxfp8.hip) ----------------------------------
+// An MX operand of `rows` rows of K elements (K % 64 == 0; as an output, K % 32 == 0) lives in the order the product's loads want:
+//   elements: 1 KB blocks of 8 rows x 128 k, blocks ordered [row / 8][k / 128] (mx_ktiles(K) per block row); inside a block row r holds its eight
+//             16-byte chunks XOR-swizzled: element (r, k) is byte (r & 7) * 128 + ((((k & 127) >> 4) ^ ((r >> 1) & 7)) << 4) + (k & 15) -- one DMA
+//             instruction copies a block to LDS as it lies, and the image is the conflict-free one of gemm_bf16_glds.hpp
+//   scales:   one E8M0 byte per (row, 32 k), eight per (row, 256 k) ordered so that a lane's dword is its scale of four consecutive MFMA steps:
+//             block kb = k / 32 of row r is byte ((kb >> 3) * mx_rows(rows) + r) * 8 + 4 * (kb & 1) + ((kb >> 1) & 3)
+// (The diagnostics hand both back row-major: capi_diag_gemm.cpp MxDev::back.)  Rows past `rows` (up to mx_rows) and k past K (up to a multiple of 128 / 256) are never written and never used.
+constexpr int64_t mx_rows(int64_t rows) { return (rows + 7) & ~(int64_t)7; }
+constexpr int64_t mx_ktiles(int K) { return (K + 127) >> 7; }
+constexpr size_t mx_elem_bytes(int64_t rows, int K) { return (size_t)(mx_rows(rows) >> 3) * mx_ktiles(K) * 1024; }
+constexpr size_t mx_scale_bytes(int64_t rows, int K) { return (size_t)((K + 255) >> 8) * mx_rows(rows) * 8; }
+constexpr size_t mx_elem_at(int64_t r, int k, int K) {
+    return (size_t)((r >> 3) * mx_ktiles(K) + (k >> 7)) * 1024 + (size_t)(r & 7) * 128 + (size_t)(((((k & 127) >> 4) ^ ((r >> 1) & 7)) << 4) + (k & 15));
+}
+constexpr size_t mx_scale_at(int64_t r, int kb, int64_t rows) { return (size_t)((kb >> 3) * mx_rows(rows) + r) * 8 + 4 * (kb & 1) + ((kb >> 1) & 3); }
+// The quantiser (one launch; both the weights' -- once per model -- and the LayerNorm rows'): src [rows][ld] fp32 (src_bf16 = 0) or bf16 -> q, sc.
+// Per 32-element block: e = clamp(floor(log2(amax)) - 8, -127, 127) (-127 for amax == 0), scale byte e + 127, element = e4m3 (OCP, fn) of
+// clamp(v / 2^e, -448, 448), round to nearest even; v / 2^e is exact.  NaN / Inf inputs are out of scope (a block holding one has no defined result).
+void launch_mx_quantize(const void *src, int src_bf16, int64_t rows, int K, int64_t ld, uint8_t *q, uint8_t *sc, hipStream_t s);
+// out = epi(sum over blocks of 2^(ea + ew) sum_k qa qw + bias), fp32 accumulation.  M, N, K > 0, K % 64 == 0, N % 32 == 0.
+enum MxEpi { MX_EPI_F32 = 0, MX_EPI_MX = 1, MX_EPI_RESID = 2 };
+struct MxGemmArgs {
+    const uint8_t *Aq, *As;     // [M][K] MX
+    const uint8_t *Wq, *Ws;     // [N][K] MX
+    const float *bias;          // [N] or nullptr
+    int M, N, K;
+    int silu;                   // SiLU (the hardware exp2 / rcp one: GemmArgs::fast_act) before the output is formed (MX_EPI_F32 / MX_EPI_MX)
+    float *out; int64_t ldo;    // MX_EPI_F32: fp32 rows (ldo % 4 == 0); MX_EPI_RESID: out = resid + alpha * (acc + bias), in place allowed
+    const float *resid; int64_t ldr; float alpha;   // (ldr % 4 == 0)
+    uint8_t *outq, *outs;       // MX_EPI_MX: the output as an MX operand of M rows x N elements -- the next product's A
+};
+struct MxTile { int bm, bn; };
+MxTile gemm_mxfp8_tile(int epi);                                   // the tile the launcher takes for that epilogue
+void launch_gemm_mxfp8(const MxGemmArgs &a, int epi, hipStream_t s);
+
 }  // namespace pk

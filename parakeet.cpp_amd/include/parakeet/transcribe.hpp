@@ -241,6 +241,9 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
         att_left_ = left;
         att_right_ = right;
     }
+    // New: the feed-forward products of the offline encoder on MXFP8 operands (pk_model_set_ffn_mxfp8; gemm_bf16 models only).  This engine's
+    // model; the replicas of to_all_gpus keep the bf16 products (pk_group has no such switch).
+    void set_ffn_mxfp8(bool on) { check(pk_model_set_ffn_mxfp8(m_, on ? 1 : 0)); }
     // New: files at another rate than 16 kHz are read at their own rate and resampled on the device on their way into the call
     // (pk_model_set_input_rate for the duration of the call) instead of by pk_read_audio's host resampler.  Off by default: for rates that
     // neither divide nor are divided by 16 kHz the device's samples differ from the host's by one fp32 rounding now and then.
@@ -526,6 +529,8 @@ class Transcriber {
     int num_gpus() const { return eng_.num_gpus(); }
     /// New: limited-context attention for long audio (Engine::set_attention_context); (-1, -1) restores full attention.
     void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
+    /// New: MXFP8 feed-forward products (Engine::set_ffn_mxfp8).
+    void set_ffn_mxfp8(bool on) { eng_.set_ffn_mxfp8(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
@@ -658,6 +663,8 @@ class TDTTranscriber {
     int num_gpus() const { return eng_.num_gpus(); }
     /// New: limited-context attention for long audio (Engine::set_attention_context); (-1, -1) restores full attention.
     void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
+    /// New: MXFP8 feed-forward products (Engine::set_ffn_mxfp8).
+    void set_ffn_mxfp8(bool on) { eng_.set_ffn_mxfp8(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
