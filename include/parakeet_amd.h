@@ -128,7 +128,8 @@ pk_status pk_model_set_decode_loop(pk_model *m, int mode);
  * instead of 2 T - 1.  left + right must fit the band kernel's LDS score block ([32][left + right + 32]): at most 1136 / 1072 / 1008 / 1072
  * at head size 32 / 64 / 96 / 128, otherwise PK_ERR_UNSUPPORTED.  Applies to pk_encode*, pk_conformer_blocks*, pk_transcribe_* and
  * the batch API of this model; not to the streaming path, pk_transformer_* or Sortformer.  fp32 mode: bit-identical to full attention when
- * the band covers the utterance (left, right >= T - 1).  gemm_bf16 mode: the attention runs on the fp32 band kernel with a bf16 context.
+ * the band covers the utterance (left, right >= T - 1).  gemm_bf16 mode: the attention runs on the fp32 band kernel with a bf16 context,
+ * or, with pk_model_set_local_attention_bf16, on the bf16-MFMA band kernel.
  * Switching back to (-1, -1) gives exactly the results of a model that never set it.  Not to be changed while a batch is in flight. */
 pk_status pk_model_set_attention_context(pk_model *m, int left, int right);
 pk_status pk_model_get_attention_context(const pk_model *m, int *left, int *right);
@@ -140,6 +141,15 @@ pk_status pk_model_get_attention_context(const pk_model *m, int *left, int *righ
  * the tolerance class of the gemm_bf16 mode, farther from fp32 than bf16 is (tests/test_gpu_ffn_mxfp8.py).  Not to be changed while a batch is in flight. */
 pk_status pk_model_set_ffn_mxfp8(pk_model *m, int on);
 pk_status pk_model_get_ffn_mxfp8(const pk_model *m, int *on);
+/* bf16 limited-context attention (opt-in, gemm_bf16 models with head size 64 or 128 only; any other model: PK_ERR_UNSUPPORTED -- the fp32 mode's
+ * contract is bit equality).  on != 0: while pk_model_set_attention_context holds a window, the attention of the offline encoder runs on the band
+ * form of the bf16-MFMA attention kernel (kernels/attention_local_bf16.hip): q, k, v and the local position table as bf16,
+ * fp32 accumulation and softmax, a bf16 context -- the operands and roundings of the full-attention kernel of this mode -- and the qkv product
+ * writes bf16.  Results stay in the tolerance class of the gemm_bf16 mode but are not the bits of the fp32 band kernel, hence a switch; on = 0
+ * (the default) gives exactly the results of a model that never set it.  Without a window the switch changes nothing.  It can be set before or
+ * after the window.  pk_group replicas and the streaming path are not covered.  Not to be changed while a batch is in flight. */
+pk_status pk_model_set_local_attention_bf16(pk_model *m, int on);
+pk_status pk_model_get_local_attention_bf16(const pk_model *m, int *on);
 
 /* ---- stage entry points (host buffers; used by the parity tests and the C++ facade) ----------------------- */
 /* preprocess_audio (src/audio.cpp:100-158): n_clips clips of n_samples each -> feats[n_clips][n_frames][mel_bins],
@@ -1203,6 +1213,12 @@ pk_status pk_diag_relpos_attention_form(int form, int out_mode, int B, const int
  * pk_model_set_attention_context.  variant (may be NULL): bit 1 = ragged instantiation, bit 3 = the band kernel ran, bit 4 = bf16 output. */
 pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left, int right,
                                          const float *bias_u, const float *bias_v, int out_mode, float *ctx, int *variant);
+/* The same layer on the bf16-MFMA band kernel (kernels/attention_local_bf16.hip; pk_model_set_local_attention_bf16), staged like the bf16 kernel of
+ * pk_diag_relpos_attention: qkv and the local table pos [left + right + 1][d] rounded to bf16 on the way in, c = (v - u) . Pl formed on the device,
+ * ctx bf16 (widened here, unwritten pattern 0x7FC50000) with the guard rows.  Any left, right >= 0 (negative: PK_ERR_INVALID); head size 64 or 128
+ * (any other: PK_ERR_UNSUPPORTED).  variant (may be NULL): 8 | 4 | (lens ? 2 : 0) -- band kernel, bf16 kernel, ragged instantiation. */
+pk_status pk_diag_relpos_local_attention_bf16(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left,
+                                              int right, const float *bias_u, const float *bias_v, float *ctx, int *variant);
 /* The cached attention of the streaming encoder alone (kernels/stream.hip; reference src/streaming_encoder.cpp:162-272), launched as a session
  * launches it for S lock-step streams: qkv_new [S c][3 d] natural columns (q | k | v of the chunk's c rows per stream), kcache / vcache
  * [S][cache_rows][d] of which the first nc rows of every stream are valid, pos [P][d] the projected position table (the kernel reads its last

@@ -336,6 +336,10 @@ _LATE_SIGNATURES = {
     "pk_group_set_attention_context": [C.c_void_p, C.c_int, C.c_int],
     "pk_model_set_ffn_mxfp8": [C.c_void_p, C.c_int],
     "pk_model_get_ffn_mxfp8": [C.c_void_p, C.POINTER(C.c_int)],
+    "pk_model_set_local_attention_bf16": [C.c_void_p, C.c_int],
+    "pk_model_get_local_attention_bf16": [C.c_void_p, C.POINTER(C.c_int)],
+    "pk_diag_relpos_local_attention_bf16": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, f32p,
+                                            C.POINTER(C.c_int)],
     "pk_resample_length": [C.c_int64, C.c_int, C.c_int],
     "pk_resample_run": [C.c_int, C.c_int],
     "pk_resample_table": [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -1816,6 +1820,28 @@ def diag_relpos_local_attention(qkv, pos, bias_u, bias_v, n_heads, left, right, 
     return out, var.value
 
 
+def diag_relpos_local_attention_bf16(qkv, pos, bias_u, bias_v, n_heads, left, right, B=1, lens=None):
+    """pk_diag_relpos_local_attention_bf16: one limited-context attention layer on the bf16-MFMA band kernel.  Arguments as
+    diag_relpos_local_attention (operands are rounded to bf16 on the way in) -> (ctx [rows + ATT_GUARD_ROWS][d] bf16 widened, with the guard
+    rows, variant bits: 2 ragged, 4 bf16 kernel, 8 band kernel)."""
+    qkv, pos, bu, bv = _c(qkv), _c(pos), _c(bias_u), _c(bias_v)
+    rows, d = qkv.shape[0], qkv.shape[1] // 3
+    assert qkv.shape[1] == 3 * d and pos.shape[1] == d and bu.shape == (d,) and bv.shape == (d,)
+    assert left < 0 or right < 0 or pos.shape[0] == left + right + 1
+    if lens is not None:
+        ln = np.ascontiguousarray(lens, np.int32)
+        assert int(ln.sum()) == rows
+        B, T, lp = len(ln), int(ln.max()), _i(ln)
+    else:
+        assert rows % B == 0
+        T, lp = rows // B, None
+    out = np.empty((rows + ATT_GUARD_ROWS, d), np.float32)
+    var = C.c_int(-1)
+    check(lib().pk_diag_relpos_local_attention_bf16(B, lp, T, d, n_heads, _f(qkv), _f(pos), int(left), int(right), _f(bu), _f(bv), _f(out),
+                                                    C.byref(var)))
+    return out, var.value
+
+
 CONV_VARIANT_WORDS = 17                  # PK_DIAG_CONV_VARIANT_WORDS
 
 
@@ -2716,6 +2742,16 @@ class Model:
     def ffn_mxfp8(self):
         on = C.c_int(0)
         check(lib().pk_model_get_ffn_mxfp8(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_local_attention_bf16(self, on=True):
+        """pk_model_set_local_attention_bf16: limited-context attention (set_attention_context) on the bf16-MFMA band kernel (gemm_bf16 models,
+        head size 64 / 128 only)."""
+        check(lib().pk_model_set_local_attention_bf16(self._h, int(bool(on))))
+
+    def local_attention_bf16(self):
+        on = C.c_int(0)
+        check(lib().pk_model_get_local_attention_bf16(self._h, C.byref(on)))
         return bool(on.value)
 
     def set_input_rate(self, rate):

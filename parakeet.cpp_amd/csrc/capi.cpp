@@ -129,6 +129,14 @@ pk_status pk_model_get_ffn_mxfp8(const pk_model *m, int *on) {
     return guard([&] { need(m && on, "model/on"); *on = m->m->ffn_mxfp8 ? 1 : 0; });
 }
 
+pk_status pk_model_set_local_attention_bf16(pk_model *m, int on) {
+    return guard([&] { need(m, "model"); m->m->set_local_attention_bf16(on != 0); });
+}
+
+pk_status pk_model_get_local_attention_bf16(const pk_model *m, int *on) {
+    return guard([&] { need(m && on, "model/on"); *on = m->m->local_attention_bf16 ? 1 : 0; });
+}
+
 pk_status pk_model_config(const pk_model *m, pk_config *out) {
     return guard([&] { need(m && out, "model/out"); *out = m->m->cfg; });
 }

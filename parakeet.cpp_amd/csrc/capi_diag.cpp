@@ -778,6 +778,36 @@ pk_status pk_diag_relpos_local_attention(int B, const int32_t *lens, int T, int 
     });
 }
 
+// ... on the bf16 band kernel (kernels/attention_local_bf16.hip), staged like the bf16 branch of pk_diag_relpos_attention
+pk_status pk_diag_relpos_local_attention_bf16(int B, const int32_t *lens, int T, int d, int n_heads, const float *qkv, const float *pos, int left,
+                                              int right, const float *bias_u, const float *bias_v, float *ctx, int *variant) {
+    return guard([&] {
+        need(qkv && pos && bias_u && bias_v && ctx && B > 0 && d > 0 && n_heads > 0 && d % n_heads == 0, "qkv/pos/bias_u/bias_v/ctx/B/d/n_heads");
+        need(left >= 0 && right >= 0 && (int64_t)left + right < (1 << 24), "left / right: both >= 0");
+        const int hd = d / n_heads;
+        if (relpos_local_attention_bf16_lds_bytes(left, right, hd) == 0) fail(PK_ERR_UNSUPPORTED, "bf16 band kernel: hd 64 or 128 (got %d)", hd);
+        const int64_t rows = att_extents(lens, B, T);
+        need(T > 0, "T > 0 (ragged: lens > 0)");
+        need_device();
+        const int Ptab = left + right + 1;
+        const int64_t n_ctx = (rows + PK_DIAG_ATTENTION_GUARD_ROWS) * d;
+        RagBatch r;
+        DevBuf rag_img, q, p, bu, bv, cvec, out;
+        const SeqRag rag = att_rag(r, rag_img, lens, B, relpos_local_attention_bf16_block_rows(hd), /*pos_T=*/0);
+        up(bu, bias_u, (size_t)d * 4);
+        up(bv, bias_v, (size_t)d * 4);
+        up16(q, qkv, (size_t)rows * 3 * d);
+        up16(p, pos, (size_t)Ptab * d);
+        cvec.reserve((size_t)n_heads * Ptab * 4);
+        filled16(out, n_ctx);
+        launch_pos_cvec(p.p, bu.as<float>(), bv.as<float>(), Ptab, d, n_heads, cvec.as<float>(), nullptr);
+        launch_relpos_local_attention_bf16(q.p, B, T, d, n_heads, p.p, cvec.as<float>(), bu.as<float>(), out.p, nullptr, left, right, rag);
+        PK_CHECK_LAUNCH();
+        down16(ctx, out, (size_t)n_ctx);
+        if (variant) *variant = 8 | 4 | (lens ? 2 : 0);
+    });
+}
+
 // The cached attention of a streaming chunk alone, launched as StreamBatch::encode launches it (stream.cpp): natural columns, the rotation of
 // the caches into a second buffer pair riding on the same launch.
 pk_status pk_diag_stream_attention(int S, int c, int nc, int cache_rows, int d, int n_heads, const float *qkv_new, const float *kcache,

@@ -50,7 +50,7 @@ void zero_tail(T *a, const int32_t *lens, int B, int pitch) {
 
 // rows of one attention block in a ragged batch whose longest utterance has T_max encoder frames
 inline int att_block_rows_of(Model &m, int T_max) {
-    return m.attn_bf16(T_max) ? relpos_attention_bf16_block_rows(m.cfg.hidden_size / m.cfg.num_heads) : 32;
+    return m.att_block_rows(T_max);
 }
 
 // capi.cpp

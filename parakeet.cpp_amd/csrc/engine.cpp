@@ -776,6 +776,20 @@ bool Model::attn_bf16(int T) const {
     const size_t lds = relpos_attention_bf16_lds_bytes(T, cfg.hidden_size / cfg.num_heads);
     return lds > 0 && lds <= (size_t)150 * 1024;
 }
+int Model::att_block_rows(int T) const {
+    const int hd = cfg.hidden_size / cfg.num_heads;
+    if (att_local_bf16()) return relpos_local_attention_bf16_block_rows(hd);
+    return attn_bf16(T) ? relpos_attention_bf16_block_rows(hd) : 32;
+}
+
+void Model::set_local_attention_bf16(bool on) {
+    if (on && !cfg.gemm_bf16)
+        fail(PK_ERR_UNSUPPORTED, "bf16 limited-context attention needs a gemm_bf16 model: the fp32 mode's contract is bit equality with the reference");
+    const int hd = cfg.hidden_size / cfg.num_heads;
+    if (on && relpos_local_attention_bf16_lds_bytes(0, 0, hd) == 0)
+        fail(PK_ERR_UNSUPPORTED, "bf16 limited-context attention: head size %d (the bf16 band kernel takes 64 or 128)", hd);
+    local_attention_bf16 = on;
+}
 
 // The tables are kept for the LONGEST sequence seen so far: row p of the table of a T-frame sequence (position T - 1 - p) is row
 // p + (pos_T - T) of the table built for pos_T >= T frames -- the same float position, hence the same sin / cos values and the same row of
@@ -844,9 +858,12 @@ void Model::set_attention_context(int left, int right) {
 }
 
 // The local table: row r is the sinusoid of position i - j = left - r (src/encoder.cpp:9-30, the float math of ensure_pos_tables: bit for bit
-// the full table's row of that position), through each layer's pos_proj_ into the sigma columns the band kernel loads.  Rebuilt when (left, right) changes.
+// the full table's row of that position), through each layer's pos_proj_ into the sigma columns the band kernel loads -- or, for the bf16 band
+// kernel (att_local_bf16()), as bf16 in natural columns with its c vector, the way ensure_pos_tables builds pos16.  Rebuilt when (left, right) or
+// that format changes.
 void Model::ensure_local_pos_table(hipStream_t s) {
-    if (pos_local.left == att_left && pos_local.right == att_right) return;
+    const bool want16 = att_local_bf16();
+    if (pos_local.left == att_left && pos_local.right == att_right && pos_local.bf16 == want16) return;
     const int d = cfg.hidden_size, P = att_left + att_right + 1;
     std::vector<float> pe((size_t)P * d);
     for (int p = 0; p < P; ++p) {
@@ -861,13 +878,28 @@ void Model::ensure_local_pos_table(hipStream_t s) {
     pos_pe.reserve(pe.size() * 4);
     pos_local.proj.reserve((size_t)cfg.num_layers * P * d * 4);
     PK_HIP(hipMemcpy(pos_pe.p, pe.data(), pe.size() * 4, hipMemcpyHostToDevice));
-    for (int l = 0; l < cfg.num_layers; ++l) {
-        GemmArgs g{pos_pe.as<float>(), d, layers[l].wpos, d, nullptr, pos_local.proj.as<float>() + (size_t)l * P * d, d, nullptr, 0, 1.0f, P, d, d};
-        g.sigma_cols = d;
-        run_gemm("pos_proj", g, EPI_NONE, s);
+    pos_local.left = pos_local.right = -1;     // (nothing half-built is taken for a table if a launch below throws)
+    if (want16) {
+        const int H = cfg.num_heads;
+        pos_local.cvec.reserve((size_t)cfg.num_layers * H * P * 4);
+        for (int l = 0; l < cfg.num_layers; ++l) {
+            __bf16 *tab = reinterpret_cast<__bf16 *>(pos_local.proj.p) + (size_t)l * P * d;
+            GemmArgs g{pos_pe.as<float>(), d, layers[l].wpos, d, nullptr, reinterpret_cast<float *>(tab), d, nullptr, 0, 1.0f, P, d, d};
+            g.out_bf16 = 1;
+            g.one_form = 1;                    // a row's bits do not depend on how many rows the window has
+            run_gemm("pos_proj", g, EPI_NONE, s);
+            launch_pos_cvec(tab, layers[l].pos_u, layers[l].pos_v, P, d, H, pos_local.cvec.as<float>() + (size_t)l * H * P, s);
+        }
+    } else {
+        for (int l = 0; l < cfg.num_layers; ++l) {
+            GemmArgs g{pos_pe.as<float>(), d, layers[l].wpos, d, nullptr, pos_local.proj.as<float>() + (size_t)l * P * d, d, nullptr, 0, 1.0f, P, d, d};
+            g.sigma_cols = d;
+            run_gemm("pos_proj", g, EPI_NONE, s);
+        }
     }
     pos_local.left = att_left;
     pos_local.right = att_right;
+    pos_local.bf16 = want16;
 }
 
 void Model::run_subsample(Workspace &w, const float *d_feats, int B, int Tm, float *d_x, hipStream_t s) {
@@ -938,9 +970,10 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
     const DevBuf &pos_proj = ptab.proj, &pos_cvec = ptab.cvec;
     const int P_loc = att_left + att_right + 1;                      // local mode: rows of the local table
     const int a16 = cfg.gemm_bf16 ? 1 : 0;                           // bf16 mode: LayerNorm outputs stored as bf16 GEMM operands (ConformerBlock::ffn)
-    const bool att16 = attn_bf16(T);                                 // ... and q / k / v as bf16 for the bf16-MFMA attention kernel
+    const bool loc16 = att_local_bf16();                             // local mode on the bf16 band kernel (set_local_attention_bf16)
+    const bool att16 = attn_bf16(T) || loc16;                        // ... and q / k / v as bf16 for the bf16-MFMA attention kernels
     if (rg) {
-        const int want = att16 ? relpos_attention_bf16_block_rows(d / cfg.num_heads) : 32;
+        const int want = att_block_rows(T);
         if (w.rag.att_rows != want) fail(PK_ERR_INVALID, "internal: the ragged batch's attention blocks hold %d rows, the kernel takes %d", w.rag.att_rows, want);
         w.rv.att.pos_T = pos_T;
     }
@@ -976,7 +1009,12 @@ void Model::run_layers(Workspace &w, int B, int first_layer, int stop_layer, int
             else fl = (double)B * cfg.num_heads * 6.0 * pairs(T) * hd;
         } else if (rg) for (int tb : w.rag.T) fl += (double)cfg.num_heads * (2.0 * tb * tb * hd * 2 + 2.0 * tb * tb * hd);
         else fl = (double)B * cfg.num_heads * (2.0 * T * T * hd * 2 + 2.0 * T * T * hd);
-        if (local) {
+        if (loc16) {
+            KL("relpos_attention", fl, 0.0,
+               launch_relpos_local_attention_bf16(w.qkv.p, B, T, d, cfg.num_heads, reinterpret_cast<const __bf16 *>(pos_local.proj.p) + (size_t)l * P_loc * d,
+                                                  pos_local.cvec.as<float>() + (size_t)l * cfg.num_heads * P_loc, L.pos_u, w.ctx.p, s, att_left, att_right,
+                                                  rg ? w.rv.att : no_rag));
+        } else if (local) {
             KL("relpos_attention", fl, 0.0,
                launch_relpos_local_attention(w.qkv.as<float>(), B, T, d, cfg.num_heads, pos_local.proj.as<float>() + (size_t)l * P_loc * d, L.pos_u, L.pos_v,
                                              w.ctx.as<float>(), s, ymode, att_left, att_right, rg ? w.rv.att : no_rag));

@@ -200,15 +200,27 @@ class Model {
     void ensure_pos_tables(int T, hipStream_t s);
     // Limited-context attention (pk_model_set_attention_context): query row i attends to keys [i - att_left, i + att_right] only, on the band
     // kernel (kernels/attention.hip, BAND instantiation) with a per-layer LOCAL table of att_left + att_right + 1 rows.  (-1, -1): full attention (default).
-    // In local mode the 2T-1 tables are neither built nor grown, no attention scratch is reserved and attn_bf16() is false.
+    // In local mode the 2T-1 tables are neither built nor grown, no attention scratch is reserved and attn_bf16() is false (the bf16 band kernel has
+    // its own predicate, att_local_bf16() below).
     int att_left = -1, att_right = -1;
     bool att_local() const { return att_left >= 0; }
     void set_attention_context(int left, int right);
     struct LocalPosTab {
         int left = -1, right = -1;          // the (left, right) it was built for
-        DevBuf proj;                        // pos_proj_ of every layer [L][left + right + 1][d], sigma columns
+        bool bf16 = false;                  // ... and the format: fp32 sigma columns, or (att_local_bf16()) bf16 natural columns + cvec
+        DevBuf proj;                        // pos_proj_ of every layer [L][left + right + 1][d]
+        DevBuf cvec;                        // bf16 band kernel: (v_h - u_h) . Pl_r per (layer, head, r)
     } pos_local;
     void ensure_local_pos_table(hipStream_t s);
+    // The bf16-MFMA band kernel for limited-context attention (pk_model_set_local_attention_bf16; kernels/attention_local_bf16.hip), off by default:
+    // gemm_bf16 models with head size 64 / 128 only.  On, local mode runs the block mode attn_bf16() sets for full attention (q / k / v from the qkv
+    // product as bf16, natural columns; bf16 ctx) and ragged batches are built in that kernel's 128-row attention blocks.  Off, every path and bit is
+    // the fp32 band kernel's.  Not to be changed while a batch is in flight.
+    bool local_attention_bf16 = false;
+    void set_local_attention_bf16(bool on);
+    bool att_local_bf16() const { return att_local() && local_attention_bf16; }
+    // rows of a ragged batch's attention blocks for the kernel a batch whose longest utterance has T frames runs on
+    int att_block_rows(int T) const;
     // Sample rate of the PCM the one-call entry points take (pk_model_set_input_rate): at another rate than kModelRate every batch is uploaded raw and
     // resampled on the device (resample.hpp) to where the 16 kHz copy went before.  rs is also the scratch of that stage.
     int input_rate = kModelRate;

@@ -443,6 +443,15 @@ void launch_pos_cvec(const void *pos_bf16, const float *bias_u, const float *bia
 int relpos_attention_bf16_block_rows(int hd);
 void launch_relpos_attention_bf16(const void *qkv_bf16, int B, int T, int d, int n_heads, const void *pos_bf16, const float *cvec, const float *bias_u,
                                   void *ctx_bf16, hipStream_t s, int pos_T = 0, const SeqRag &rag = SeqRag());
+// Its limited-context ("band") form, kernels/attention_local_bf16.hip: query row i attends to keys [max(0, i - left), min(T - 1, i + right)] only.
+// qkv / ctx as above; pos_bf16 = the layer's LOCAL table [left + right + 1][d] as bf16, natural columns (row r = position left - r), cvec[h][r] =
+// (v_h - u_h) . Pl_r of that table (launch_pos_cvec with P = left + right + 1).  Any left, right >= 0 and any T: a workgroup walks only the key
+// tiles of its rows' bands and nothing of size T or of the window is in LDS but a c band of 32 (tiles walked) + 128 floats.  Head sizes 64 and
+// 128 (relpos_local_attention_bf16_lds_bytes returns 0 for any other).  rag set: units = relpos_local_attention_bf16_block_rows() rows.
+size_t relpos_local_attention_bf16_lds_bytes(int left, int right, int hd);
+int relpos_local_attention_bf16_block_rows(int hd);
+void launch_relpos_local_attention_bf16(const void *qkv_bf16, int B, int T, int d, int n_heads, const void *pos_bf16, const float *cvec, const float *bias_u,
+                                        void *ctx_bf16, hipStream_t s, int left, int right, const SeqRag &rag = SeqRag());
 void launch_dwconv_bn_silu(const float *g, int B, int T, int d, int kc, const float *w, const float *bias, const float *bn_mean,
                            const float *bn_rstd, const float *bn_g, const float *bn_b, float *out, hipStream_t s, int out_bf16 = 0,
                            const SeqRag &rag = SeqRag());

@@ -4,8 +4,11 @@
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K] [--beam-head ctc|tdt]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
 //                [--spot "phrase"]... [--spot-file path.txt] [--spot-head ctc|tdt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
-//                [--device-resample] [--vad [--vad-max-piece S]]
+//                [--device-resample] [--vad [--vad-max-piece S]] [--attention-context L,R [--local-attention-bf16]]
 //                [--nlm file.safetensors --nlm-heads H --nlm-bos ID [--nlm-eos ID] [--nlm-alpha A] [--nlm-beta B]]
+// New: --attention-context L,R (tdt-ctc-110m, tdt-600m) limits the encoder's attention to the L frames before and the R frames after each frame
+// (Transcriber::set_attention_context: long recordings).  --local-attention-bf16 (only with --attention-context) asks for the bf16-MFMA band
+// kernel (set_local_attention_bf16): the engine accepts it on a gemm_bf16 model with head size 64 / 128 and refuses it on any other.
 // New: --vad (tdt-ctc-110m, tdt-600m; 16 kHz) cuts the file at its pauses on the device and transcribes only the speech, in pieces of at most
 // S seconds (--vad-max-piece S, default 30) that share batches (TranscribeOptions::vad): for long or sparse recordings.
 // New: --device-resample (tdt-ctc-110m, tdt-600m) reads the file at its own sample rate and resamples it to 16 kHz on the device, inside the call
@@ -59,6 +62,7 @@ static void usage(const char *prog) {
               << "                      the N best hypotheses re-ranked by a Transformer LM over token ids: am + A * nlm + B * tokens\n"
               << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold), --spot-head ctc|tdt (default ctc; tdt works for tdt-600m)\n"
               << "  --device-resample  resample files that are not 16 kHz on the device instead of on the host (tdt-ctc-110m, tdt-600m)\n"
+              << "  --attention-context L,R [--local-attention-bf16]  limited-context attention for long audio; the bf16 band kernel needs a bf16 model\n"
               << "  --vad [--vad-max-piece S]  transcribe only the speech, cut at the pauses into pieces of at most S seconds (default 30)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
@@ -153,7 +157,8 @@ int main(int argc, char **argv) {
         std::vector<std::string> boost, spot;
         SpotOptions spot_opts;
         float boost_score = 5.0f, vad_max_piece = 30.0f;
-        bool vad = false, spot_tdt = false;
+        bool vad = false, spot_tdt = false, local_bf16 = false;
+        int att_left = -1, att_right = -1;
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
             if (a == "--model" && i + 1 < argc) model = argv[++i];
@@ -214,6 +219,13 @@ int main(int argc, char **argv) {
             else if (a == "--nlm-beta" && i + 1 < argc) nlm_opts.beta = std::stof(argv[++i]);
             else if (a == "--device-resample") device_resample = true;
             else if (a == "--vad") vad = true;
+            else if (a == "--attention-context" && i + 1 < argc) {
+                const std::string w = argv[++i];
+                const size_t comma = w.find(',');
+                if (comma == std::string::npos) { std::cerr << "Error: --attention-context takes L,R\n"; return 1; }
+                att_left = std::stoi(w.substr(0, comma)); att_right = std::stoi(w.substr(comma + 1));
+            }
+            else if (a == "--local-attention-bf16") local_bf16 = true;
             else if (a == "--vad-max-piece" && i + 1 < argc) vad_max_piece = std::stof(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
@@ -232,6 +244,14 @@ int main(int argc, char **argv) {
         opts.boost_score = boost_score;
         opts.vad = vad;
         opts.vad_max_piece_s = vad_max_piece;
+        const bool att_ctx = att_left != -1 || att_right != -1;
+        if (att_ctx && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --attention-context needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
+        if (local_bf16 && !att_ctx) { std::cerr << "Error: --local-attention-bf16 needs --attention-context L,R\n"; return 1; }
+        // (the engine refuses the bf16 band kernel on a model that is not gemm_bf16: the error names the reason)
+        auto set_attention = [&](auto &t) {
+            if (att_ctx) t.set_attention_context(att_left, att_right);
+            if (local_bf16) t.set_local_attention_bf16(true);
+        };
         if (vad && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --vad needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (vad && device_resample) { std::cerr << "Error: --vad works on 16 kHz audio; it does not combine with --device-resample\n"; return 1; }
         if (align && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --align needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
@@ -298,6 +318,7 @@ int main(int argc, char **argv) {
         if (model == "tdt-ctc-110m") {
             Transcriber t(weights, vocab);
             t.to_gpu();
+            set_attention(t);
             t.set_device_resampling(device_resample);
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);
@@ -374,6 +395,7 @@ int main(int argc, char **argv) {
         } else if (model == "tdt-600m") {
             TDTTranscriber t(weights, vocab);
             t.to_gpu();
+            set_attention(t);
             t.set_device_resampling(device_resample);
             if (align) return run_align(t, audio_path, align_text, align_tdt);
             if (score) return run_score(t, audio_path, score_text);

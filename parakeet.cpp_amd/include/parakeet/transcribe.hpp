@@ -244,6 +244,9 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     // New: the feed-forward products of the offline encoder on MXFP8 operands (pk_model_set_ffn_mxfp8; gemm_bf16 models only).  This engine's
     // model; the replicas of to_all_gpus keep the bf16 products (pk_group has no such switch).
     void set_ffn_mxfp8(bool on) { check(pk_model_set_ffn_mxfp8(m_, on ? 1 : 0)); }
+    // New: limited-context attention (set_attention_context) on the bf16-MFMA band kernel (pk_model_set_local_attention_bf16; gemm_bf16 models with
+    // head size 64 / 128 only, any other is refused).  This engine's model; the replicas of to_all_gpus keep the fp32 band kernel.
+    void set_local_attention_bf16(bool on) { check(pk_model_set_local_attention_bf16(m_, on ? 1 : 0)); }
     // New: files at another rate than 16 kHz are read at their own rate and resampled on the device on their way into the call
     // (pk_model_set_input_rate for the duration of the call) instead of by pk_read_audio's host resampler.  Off by default: for rates that
     // neither divide nor are divided by 16 kHz the device's samples differ from the host's by one fp32 rounding now and then.
@@ -531,6 +534,8 @@ class Transcriber {
     void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
     /// New: MXFP8 feed-forward products (Engine::set_ffn_mxfp8).
     void set_ffn_mxfp8(bool on) { eng_.set_ffn_mxfp8(on); }
+    /// New: limited-context attention on the bf16-MFMA band kernel (Engine::set_local_attention_bf16).
+    void set_local_attention_bf16(bool on) { eng_.set_local_attention_bf16(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
@@ -665,6 +670,8 @@ class TDTTranscriber {
     void set_attention_context(int left, int right) { eng_.set_attention_context(left, right); }
     /// New: MXFP8 feed-forward products (Engine::set_ffn_mxfp8).
     void set_ffn_mxfp8(bool on) { eng_.set_ffn_mxfp8(on); }
+    /// New: limited-context attention on the bf16-MFMA band kernel (Engine::set_local_attention_bf16).
+    void set_local_attention_bf16(bool on) { eng_.set_local_attention_bf16(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
