@@ -649,6 +649,57 @@ pk_status pk_diag_tdt_total_groups(const int32_t *n_frames_of_hyp, const int32_t
                                    int max_hyps, int32_t *group_of, int *n_groups);
 pk_status pk_diag_rescore_order(const int32_t *lens, const float *ctc_score, const float *tdt_total, const int32_t *ok, int N, float tdt_weight,
                                 int32_t *order, float *combined);
+/* ---- forced alignment and log-likelihood of a GIVEN transcript under the plain RNN-T head --------------------------------------
+ * The two questions above for a model whose joint is the plain RNN-T one (rnnt_head = 1: one [V] head, no durations, no CTC head), which the TDT
+ * and CTC entry points refuse.  The lattice of an utterance of T frames and U tokens is T x (U + 1) joint evaluations -- cell (t, u): frame t, the
+ * prediction net having consumed ids[:u] -- with the arcs of the greedy loop (src/rnnt.cpp): blank to (t + 1, u), label ids[u] to (t, u + 1); the
+ * blank out of (T - 1, U) ends the utterance.  max_symbols_per_step is not part of the lattice.  The alignment is the max-plus path, the total the
+ * log-sum over every path, both specified operation by operation in DESIGN.md section 5.5.12 (tests/rnnt_lattice_ref.py is that specification; the
+ * device results equal it bit for bit).  No beam search, no keyword spotting, no streaming or pk_group variant, no bf16 form.  All of it runs on the
+ * device (kernels/rnnt_lattice.hip).
+ *
+ * pk_rnnt_align / pk_rnnt_total: the walk alone on a HOST lattice.  Needs a device, no model.  Utterance b has n_frames[b] >= 1 frames and the
+ * tokens id_offsets[b] .. id_offsets[b+1] (id_offsets[0] = 0; U = 0 is valid); its values are packed utterance after utterance: lab [T_b][U_b],
+ * blk [T_b][U_b + 1].  Outputs: start / end / conf packed as the tokens (token k emitted at frame start[k] = end[k], conf[k] = exp(lab[start[k]][k])),
+ * score[B] the path's log-probability resp. total[B] >= it, ok[B] = 1, or 0 where no path reaches the end: then score / total = -inf and the
+ * utterance's arrays are 0.
+ * PK_ERR_INVALID (before any device work): B < 1, n_frames[b] < 1, offsets that decrease.
+ * PK_ERR_UNSUPPORTED (before anything is allocated): more than 1023 tokens in an utterance, or more than 1 GiB of scratch: with cells =
+ * sum_b T_b (U_b + 1), labs = sum_b T_b U_b and, for the alignment, words = sum_b (U_b + 1) ceil(T_b / 32): 4 (labs + cells + words) bytes. */
+pk_status pk_rnnt_align(const float *lab, const float *blk, const int32_t *n_frames, int B, const int32_t *id_offsets, int32_t *start, int32_t *end,
+                        float *conf, float *score, int32_t *ok);
+pk_status pk_rnnt_total(const float *lab, const float *blk, const int32_t *n_frames, int B, const int32_t *id_offsets, float *total, int32_t *ok);
+/* Prediction net over every prefix + enc_proj + the lattice (joint of every cell in row chunks: the [cells][V] logits never exist at once) + the
+ * walk, on the model's stream; arguments as pk_tdt_align_decode (without dur_idx) and pk_tdt_total_decode.  The utterances are walked in groups
+ * of consecutive ones: at most 256, and as many as keep the group's scratch (the formula above plus chunk_rows (V + J) 4 bytes of the rows chunk
+ * and (U_max + 1) n (J + 1) 4 bytes of the prediction net's outputs) under 1 GiB.  Grouping changes no bit of any result.
+ * PK_ERR_INVALID: an id outside [0, V) or equal to blank, decreasing offsets, a clip_of entry outside [0, n_clips), n_hyp != n_clips without
+ * clip_of.  PK_ERR_UNSUPPORTED: a model without an RNN-T head (a TDT joint: use pk_tdt_align* / pk_tdt_total*; encoder-only), a gemm_bf16 model,
+ * more than 1023 tokens, or one utterance whose own scratch exceeds the cap. */
+pk_status pk_rnnt_align_decode(pk_model *m, const float *enc, int B, int T, const int32_t *ids, const int32_t *id_offsets, int32_t *start, int32_t *end,
+                               float *conf, float *score, int32_t *ok);
+pk_status pk_rnnt_align_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                                      int32_t *start, int32_t *end, float *conf, float *score, int32_t *ok);
+pk_status pk_rnnt_total_decode(pk_model *m, const float *enc, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets,
+                               const int32_t *clip_of_or_null, int n_hyp, float *total, int32_t *ok);
+pk_status pk_rnnt_total_decode_ragged(pk_model *m, const float *enc, const int32_t *n_frames, int n_clips, const int32_t *ids,
+                                      const int32_t *id_offsets, const int32_t *clip_of_or_null, int n_hyp, float *total, int32_t *ok);
+/* Stage timers (tools/bench_rnnt_align.py), between hipEvents on the model's stream, summed over the groups of the call, medians of `reps` passes
+ * after one warm-up: ms[0] = prediction net (with the uploads of the tables and token strings), ms[1] = lattice (activation + heads product +
+ * reduction, all chunks), ms[2] = the walk, ms[3] = the back-trace.  n_frames NULL: uniform [B][T]. */
+pk_status pk_rnnt_align_decode_timed(pk_model *m, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids,
+                                     const int32_t *id_offsets, int reps, float ms[4]);
+/* One call from PCM and transcripts to timestamps resp. log-likelihoods, as pk_tdt_align_pcm and pk_tdt_score_pcm (same packing, same result
+ * layout; the attention context set on the model applies), through the RNN-T head. */
+pk_status pk_rnnt_align_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts_or_null,
+                            const int32_t *ids_or_null, const int32_t *id_offsets, pk_result **results, float *score, int32_t *ok);
+pk_status pk_rnnt_score_pcm(pk_model *m, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts_or_null,
+                            const int32_t *ids_or_null, const int32_t *id_offsets, const int32_t *clip_of_or_null, int n_hyp, float *total,
+                            int32_t *ok);
+/* Diagnostic: the lattice values of a ragged batch as pk_rnnt_align takes them, brought back to the host, as pk_diag_tdt_lattice does it (chunk_rows,
+ * the PK_DIAG_TDT_LATTICE_GUARD words behind labs resp. cells floats).  The call must fit one group. */
+pk_status pk_diag_rnnt_lattice(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                               int chunk_rows, float *lab, float *blk);
 /* Diagnostic: out[0] / out[1] = free / total bytes of the current device (hipMemGetInfo), out[2] = the bytes of device memory the grow-only
  * buffers of m's stage entry points hold (workspace, io scratch, TDT alignment, TDT total and keyword-spotting scratch; 0 with m == NULL): what a call that promises to
  * allocate nothing must leave unchanged. */

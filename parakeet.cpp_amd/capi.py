@@ -296,6 +296,16 @@ _LATE_SIGNATURES = {
     "pk_diag_rescore_order": [i32p, f32p, f32p, i32p, C.c_int, C.c_float, i32p, f32p],
     "pk_tdt_align_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.POINTER(C.POINTER(PkResult)), f32p, i32p],
     "pk_diag_tdt_lattice": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, f32p, f32p, f32p],
+    "pk_rnnt_align": [f32p, f32p, i32p, C.c_int, i32p, i32p, i32p, f32p, f32p, i32p],
+    "pk_rnnt_total": [f32p, f32p, i32p, C.c_int, i32p, f32p, i32p],
+    "pk_rnnt_align_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, i32p],
+    "pk_rnnt_align_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, i32p, f32p, f32p, i32p],
+    "pk_rnnt_total_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_int, f32p, i32p],
+    "pk_rnnt_total_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, C.c_int, f32p, i32p],
+    "pk_rnnt_align_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, f32p],
+    "pk_rnnt_align_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, C.POINTER(C.POINTER(PkResult)), f32p, i32p],
+    "pk_rnnt_score_pcm": [C.c_void_p, f32p, i64p, C.c_int, C.POINTER(C.c_char_p), i32p, i32p, i32p, C.c_int, f32p, i32p],
+    "pk_diag_rnnt_lattice": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, C.c_int, f32p, f32p],
     "pk_kws_options_default": [C.POINTER(PkKwsOptions)],
     "pk_ctc_kws": [f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
     "pk_ctc_kws_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(PkKwsOptions), i32p, i32p, i32p, f32p],
@@ -664,6 +674,41 @@ def tdt_total(lattices, durations):
     dur = np.ascontiguousarray(durations, np.int32)
     tt = np.zeros(len(T), np.float32); ok = np.zeros(len(T), np.int32)
     check(lib().pk_tdt_total(_f(lab), _f(blk), _f(dl), _i(dur), len(dur), _i(T), len(T), _i(off), _f(tt), _i(ok)))
+    return [dict(total=tt[b], ok=int(ok[b])) for b in range(len(T))]
+
+
+# ---- forced alignment and log-likelihood under the plain RNN-T head (include/parakeet_amd.h; DESIGN.md section 5.5.12) ------
+def _rnnt_pack(lattices):
+    """[(lab [T][U], blk [T][U+1])] -> the packed arrays of pk_rnnt_align: lab, blk, n_frames[B], id_offsets[B + 1]."""
+    T = np.asarray([x[1].shape[0] for x in lattices], np.int32)
+    off = np.zeros(len(lattices) + 1, np.int32)
+    off[1:] = np.cumsum([x[1].shape[1] - 1 for x in lattices])
+    cat = lambda k: _c(np.concatenate([_c(x[k]).ravel() for x in lattices] + [np.zeros(1, np.float32)]))
+    return cat(0), cat(1), T, off
+
+
+def _rnnt_align_call(fn, head, off):
+    """-> list (one dict per utterance) of start / end / conf arrays [U_b], score, ok.  head: the arguments in front of id_offsets."""
+    B = len(off) - 1
+    n = max(1, int(off[-1]))
+    st = np.zeros(n, np.int32); en = np.zeros(n, np.int32); cf = np.zeros(n, np.float32)
+    sc = np.zeros(B, np.float32); ok = np.zeros(B, np.int32)
+    check(fn(*head, _i(off), _i(st), _i(en), _f(cf), _f(sc), _i(ok)))
+    return [dict(start=st[off[b]:off[b + 1]].copy(), end=en[off[b]:off[b + 1]].copy(), conf=cf[off[b]:off[b + 1]].copy(), score=sc[b], ok=int(ok[b]))
+            for b in range(B)]
+
+
+def rnnt_align(lattices):
+    """pk_rnnt_align: lattices = one (lab [T][U], blk [T][U+1]) per utterance.  Needs a device, no model."""
+    lab, blk, T, off = _rnnt_pack(lattices)
+    return _rnnt_align_call(lib().pk_rnnt_align, (_f(lab), _f(blk), _i(T), len(T)), off)
+
+
+def rnnt_total(lattices):
+    """pk_rnnt_total: lattices as capi.rnnt_align takes them -> list (one dict per utterance) of total, ok.  Needs a device, no model."""
+    lab, blk, T, off = _rnnt_pack(lattices)
+    tt = np.zeros(len(T), np.float32); ok = np.zeros(len(T), np.int32)
+    check(lib().pk_rnnt_total(_f(lab), _f(blk), _i(T), len(T), _i(off), _f(tt), _i(ok)))
     return [dict(total=tt[b], ok=int(ok[b])) for b in range(len(T))]
 
 
@@ -3134,6 +3179,73 @@ class Model:
         tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
         check(lib().pk_tdt_score_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n_clips, *_transcript_args(texts, ids, n),
                                      _i(co) if co is not None else None, n, _f(tt), _i(ok)))
+        return [dict(total=tt[b], ok=int(ok[b])) for b in range(n)]
+
+    def rnnt_align_decode(self, enc, ids):
+        """pk_rnnt_align_decode(_ragged): enc [B][T][d], or a list of [T_b][d] matrices (one packed batch); ids: one token sequence per
+        utterance -> as capi.rnnt_align."""
+        rag, x, T = _enc_head(enc)
+        pid, off = _pack_ids(ids)
+        if rag:
+            return _rnnt_align_call(lib().pk_rnnt_align_decode_ragged, (self._h, _f(x), _i(T), len(T), _i(pid)), off)
+        return _rnnt_align_call(lib().pk_rnnt_align_decode, (self._h, _f(x), x.shape[0], x.shape[1], _i(pid)), off)
+
+    def rnnt_align_decode_timed(self, enc, ids, reps=5):
+        """pk_rnnt_align_decode_timed -> (prediction net ms, lattice ms, walk ms, back-trace ms), HIP events, medians of reps passes."""
+        rag, x, T = _enc_head(enc)
+        pid, off = _pack_ids(ids)
+        ms = np.zeros(4, np.float32)
+        check(lib().pk_rnnt_align_decode_timed(self._h, _f(x), _i(T) if rag else None, len(T), 0 if rag else x.shape[1], _i(pid), _i(off), reps, _f(ms)))
+        return tuple(float(v) for v in ms)
+
+    def rnnt_total_decode(self, enc, ids, clip_of=None):
+        """pk_rnnt_total_decode(_ragged): arguments and result as tdt_total_decode."""
+        rag, x, T, pid, off, co = self._total_args(enc, ids, clip_of)
+        n = len(off) - 1
+        tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
+        tail = (_i(pid), _i(off), _i(co) if co is not None else None, n, _f(tt), _i(ok))
+        if rag:
+            check(lib().pk_rnnt_total_decode_ragged(self._h, _f(x), _i(T), len(T), *tail))
+        else:
+            check(lib().pk_rnnt_total_decode(self._h, _f(x), x.shape[0], x.shape[1], *tail))
+        return [dict(total=tt[b], ok=int(ok[b])) for b in range(n)]
+
+    def rnnt_lattice(self, enc, ids, chunk_rows=0):
+        """pk_diag_rnnt_lattice: enc a list of [T_b][d] matrices (or [B][T][d]) -> list of (lab [T][U], blk [T][U+1]) as capi.rnnt_align takes
+        them, and "guard": the two buffers' words past the written extent as uint32 (the fill pattern 0x7FC5A5A5 when nothing wrote there)."""
+        _, x, T = _enc_head(enc)
+        pid, off = _pack_ids(ids)
+        U = np.diff(off).astype(np.int64)
+        cells, labs = int((T * (U + 1)).sum()), int((T * U).sum())
+        G = TDT_LATTICE_GUARD
+        lab = np.zeros(labs + G, np.float32); blk = np.zeros(cells + G, np.float32)
+        check(lib().pk_diag_rnnt_lattice(self._h, _f(x), _i(T), len(T), _i(pid), _i(off), int(chunk_rows), _f(lab), _f(blk)))
+        out, c0, l0 = [], 0, 0
+        for b in range(len(T)):
+            t, u = int(T[b]), int(U[b])
+            out.append((lab[l0:l0 + t * u].reshape(t, u).copy(), blk[c0:c0 + t * (u + 1)].reshape(t, u + 1).copy()))
+            c0 += t * (u + 1); l0 += t * u
+        return out, np.concatenate([lab[labs:], blk[cells:]]).view(np.uint32)
+
+    def align_rnnt(self, clips, texts=None, ids=None):
+        """pk_rnnt_align_pcm: Model.align through the plain RNN-T head -> list of dicts as align_tdt() returns them."""
+        pcm, off, n = _clips(clips)
+        sc = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
+        res = C.POINTER(PkResult)()
+        check(lib().pk_rnnt_align_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n, *_transcript_args(texts, ids, n), C.byref(res), _f(sc), _i(ok)))
+        out = _result_list(res, n, ok)
+        for i, d in enumerate(out):
+            d.update(score=float(sc[i]), ok=int(ok[i]))
+        return out
+
+    def score_rnnt(self, clips, texts=None, ids=None, clip_of=None):
+        """pk_rnnt_score_pcm: the RNN-T log-likelihood of one or more transcripts per clip (texts need the vocabulary) -> list of dicts total, ok."""
+        pcm, off, n_clips = _clips(clips)
+        n = len(texts) if texts is not None else len(ids)
+        co = None if clip_of is None else np.ascontiguousarray(clip_of, np.int32)
+        tt = np.zeros(n, np.float32); ok = np.zeros(n, np.int32)
+        check(lib().pk_rnnt_score_pcm(self._h, _f(pcm), off.ctypes.data_as(i64p), n_clips, *_transcript_args(texts, ids, n),
+                                      _i(co) if co is not None else None, n, _f(tt), _i(ok)))
         return [dict(total=tt[b], ok=int(ok[b])) for b in range(n)]
 
     def transcribe_nbest_rescored(self, clips, beam_width=None, token_prune=None, n_best=None, timestamps=False, tdt_weight=0.5):

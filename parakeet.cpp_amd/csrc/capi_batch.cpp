@@ -1,5 +1,5 @@
 // parakeet.cpp_amd/csrc/capi_batch.cpp -- the resident two-stream batch pipeline (pk_batch_*) and the one-call API on top of it:
-// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest(_rescored, _tdt), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm, pk_spot_pcm and the result stores they hand out.
+// the packing policy (pk_plan_batches), pk_transcribe_pcm, pk_transcribe_pcm_nbest(_rescored, _tdt), pk_align_pcm, pk_tdt_align_pcm, pk_tdt_score_pcm, pk_rnnt_align_pcm, pk_rnnt_score_pcm, pk_spot_pcm and the result stores they hand out.
 #include <algorithm>
 #include <cstring>
 
@@ -1200,8 +1200,9 @@ static void align_transcripts(Model &m, int n_clips, const char *const *texts, c
     }
 }
 
-// The body of pk_tdt_score_pcm: the batches of pk_transcribe_pcm; the transcripts of a batch's clips are scored on its encoder rows.
-static void score_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids, const std::vector<int32_t> &all_off,
+// The body of pk_tdt_score_pcm and pk_rnnt_score_pcm: the batches of pk_transcribe_pcm; the transcripts of a batch's clips are scored on its encoder rows
+// under the TDT head, or (rnnt) under the plain RNN-T head (rnnt_lattice.hpp).
+static void score_pcm(Model &m, bool rnnt, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids, const std::vector<int32_t> &all_off,
                       const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
     std::vector<std::vector<int>> hyps_of(n_clips);
     for (int q = 0; q < n_hyp; ++q) hyps_of[clip_of ? clip_of[q] : q].push_back(q);
@@ -1217,12 +1218,16 @@ static void score_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_
         return !bhyp.empty();                                       // (no transcript for any clip of this batch: nothing to encode)
     }, [&](const RagBatch &rb, int nc) {
         nfr.assign(rb.T.begin(), rb.T.begin() + nc);                   // (the plan refuses before the batch is encoded)
-        tdt_total_plan_call(m, m.ttotal, nfr.data(), nc, 0, boff.data(), bclip.data(), (int)bhyp.size());
+        if (rnnt) rnnt_plan_call(m, m.rnnt, nfr.data(), nc, 0, boff.data(), bclip.data(), (int)bhyp.size(), /*align=*/false);
+        else tdt_total_plan_call(m, m.ttotal, nfr.data(), nc, 0, boff.data(), bclip.data(), (int)bhyp.size());
     }, [&](const int *, int, const RagBatch &r) {
         m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
-        run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), bids.data(), boff.data());
+        if (rnnt) run_rnnt_call(m, m.rnnt, m.ws.ep.as<float>(), bids.data(), boff.data());
+        else run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), bids.data(), boff.data());
         PK_CHECK_LAUNCH();
-        for (size_t q = 0; q < bhyp.size(); ++q) { total[bhyp[q]] = m.ttotal.total[q]; ok[bhyp[q]] = m.ttotal.ok[q]; }
+        const std::vector<float> &tv = rnnt ? m.rnnt.value : m.ttotal.total;
+        const std::vector<int32_t> &ov = rnnt ? m.rnnt.ok : m.ttotal.ok;
+        for (size_t q = 0; q < bhyp.size(); ++q) { total[bhyp[q]] = tv[q]; ok[bhyp[q]] = ov[q]; }
     });
 }
 
@@ -1238,18 +1243,36 @@ pk_status pk_tdt_score_pcm(pk_model *h, const float *pcm, const int64_t *offsets
         std::vector<int32_t> all_ids, all_off;
         align_transcripts(m, n_hyp, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
         m.require_gpu();
-        score_pcm(m, pcm, offsets, n_clips, all_ids, all_off, clip_of, n_hyp, total, ok);
+        score_pcm(m, false, pcm, offsets, n_clips, all_ids, all_off, clip_of, n_hyp, total, ok);
     });
 }
 
-// The body of pk_align_pcm and pk_tdt_align_pcm: every batch aligned through the chosen head, tokens and words stored.
-static void align_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids,
+pk_status pk_rnnt_score_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
+                            const int32_t *id_offsets_in, const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && pcm && offsets && total && ok && n_clips > 0 && n_hyp > 0, "model/pcm/offsets/total/ok/n_clips/n_hyp");
+        need(texts || id_offsets_in, "texts or ids/id_offsets");
+        Model &m = *h->m;
+        rnnt_model_checks(m);
+        if (clip_of) for (int q = 0; q < n_hyp; ++q) need(clip_of[q] >= 0 && clip_of[q] < n_clips, "clip_of[h] outside [0, n_clips)");
+        else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
+        std::vector<int32_t> all_ids, all_off;
+        align_transcripts(m, n_hyp, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
+        m.require_gpu();
+        score_pcm(m, true, pcm, offsets, n_clips, all_ids, all_off, clip_of, n_hyp, total, ok);
+    });
+}
+
+// The body of pk_align_pcm, pk_tdt_align_pcm and pk_rnnt_align_pcm: every batch aligned through the chosen head, tokens and words stored.
+enum { ALIGN_CTC = 0, ALIGN_TDT = 1, ALIGN_RNNT = 2 };
+static void align_pcm(Model &m, int head, const float *pcm, const int64_t *offsets, int n_clips, const std::vector<int32_t> &all_ids,
                       const std::vector<int32_t> &all_off, pk_result **results, float *score, float *total, int32_t *ok) {
     const int V = m.cfg.ctc_vocab_size, blank = m.cfg.blank_id < V ? m.cfg.blank_id : V - 1;      // (CTC head only)
     auto store = new_store(n_clips);
     std::vector<int32_t> bids, boff, nfr, st, en, di, okv;
     std::vector<float> cf, sc, tt;
-    for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/!tdt, [&](const int *clip, int nc) {
+    const bool tdt = head == ALIGN_TDT, rnnt = head == ALIGN_RNNT;
+    for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/head == ALIGN_CTC, [&](const int *clip, int nc) {
         boff.assign(nc + 1, 0); bids.clear();
         for (int i = 0; i < nc; ++i) {
             bids.insert(bids.end(), all_ids.begin() + all_off[clip[i]], all_ids.begin() + all_off[clip[i] + 1]);
@@ -1259,6 +1282,7 @@ static void align_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offse
     }, [&](const RagBatch &rb, int nc) {
         nfr.assign(rb.T.begin(), rb.T.begin() + nc);                   // (the plans refuse before the batch is encoded)
         if (tdt) tdt_align_plan(m.talign, nfr.data(), nc, rb.T_max, boff.data(), m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden);
+        else if (rnnt) rnnt_plan_call(m, m.rnnt, nfr.data(), nc, 0, boff.data(), nullptr, nc, /*align=*/true);
         else align_plan(m.align, nfr.data(), nc, rb.T_max, boff.data());
     }, [&](const int *clip, int nc, const RagBatch &r) {
         const size_t n = bids.size();
@@ -1271,6 +1295,14 @@ static void align_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offse
             run_tdt_align_dp(m.talign, m.stream);
             PK_CHECK_LAUNCH();
             tdt_align_copy_out(m.talign, st.data(), en.data(), di.data(), cf.data(), sc.data(), okv.data(), m.stream);
+        } else if (rnnt) {
+            m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
+            run_rnnt_call(m, m.rnnt, m.ws.ep.as<float>(), bids.data(), boff.data());
+            PK_CHECK_LAUNCH();
+            const RnntLatticeWs &w = m.rnnt;
+            std::copy(w.h_start.begin(), w.h_start.end(), st.begin()); std::copy(w.h_end.begin(), w.h_end.end(), en.begin());
+            std::copy(w.h_conf.begin(), w.h_conf.end(), cf.begin());
+            std::copy(w.value.begin(), w.value.end(), sc.begin()); std::copy(w.ok.begin(), w.ok.end(), okv.begin());
         } else {
             run_ctc_align(m.align, m.ws.ctc_lp.as<float>(), nc, r.T_max, m.ws.rv.seq, V, blank, bids.data(), total != nullptr, m.stream);
             PK_CHECK_LAUNCH();
@@ -1302,7 +1334,7 @@ pk_status pk_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets, in
         std::vector<int32_t> all_ids, all_off;
         align_transcripts(m, n_clips, texts, ids_in, id_offsets_in, V, blank, all_ids, all_off);
         m.require_gpu();
-        align_pcm(m, false, pcm, offsets, n_clips, all_ids, all_off, results, score, total, ok);
+        align_pcm(m, ALIGN_CTC, pcm, offsets, n_clips, all_ids, all_off, results, score, total, ok);
     });
 }
 
@@ -1316,7 +1348,21 @@ pk_status pk_tdt_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets
         std::vector<int32_t> all_ids, all_off;
         align_transcripts(m, n_clips, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
         m.require_gpu();
-        align_pcm(m, true, pcm, offsets, n_clips, all_ids, all_off, results, score, nullptr, ok);
+        align_pcm(m, ALIGN_TDT, pcm, offsets, n_clips, all_ids, all_off, results, score, nullptr, ok);
+    });
+}
+
+pk_status pk_rnnt_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets, int n_clips, const char *const *texts, const int32_t *ids_in,
+                            const int32_t *id_offsets_in, pk_result **results, float *score, int32_t *ok) {
+    return guard([&] {
+        need(h && pcm && offsets && results && ok && n_clips > 0, "model/pcm/offsets/results/ok/n_clips");
+        need(texts || id_offsets_in, "texts or ids/id_offsets");
+        Model &m = *h->m;
+        rnnt_model_checks(m);
+        std::vector<int32_t> all_ids, all_off;
+        align_transcripts(m, n_clips, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
+        m.require_gpu();
+        align_pcm(m, ALIGN_RNNT, pcm, offsets, n_clips, all_ids, all_off, results, score, nullptr, ok);
     });
 }
 

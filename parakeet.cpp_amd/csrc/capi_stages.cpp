@@ -970,6 +970,158 @@ pk_status pk_diag_rescore_order(const int32_t *lens, const float *ctc_score, con
     });
 }
 
+}  // extern "C"
+
+/* ---- forced alignment and total of given token strings under the plain RNN-T head (kernels/rnnt_lattice.hip) -------------------------- */
+// pk_rnnt_align / pk_rnnt_total: the walk alone on a HOST lattice, one group, no model
+static void rnnt_host_walk(bool align, const float *lab, const float *blk, const int32_t *n_frames, int B, const int32_t *id_offsets, int32_t *start,
+                           int32_t *end, float *conf, float *value, int32_t *ok) {
+    need(B >= 1 && id_offsets && n_frames, "B/id_offsets/n_frames");
+    need(id_offsets[0] == 0, "id_offsets[0] must be 0");
+    for (int b = 0; b < B; ++b) {
+        need(id_offsets[b + 1] >= id_offsets[b], "id_offsets decrease");
+        need(n_frames[b] > 0, "n_frames[b] must be positive");
+    }
+    need(blk && value && ok, "blk/score or total/ok");
+    need(id_offsets[B] == 0 || (lab && (!align || (start && end && conf))), "lab/start/end/conf");
+    RnntLatticeWs ws;
+    rnnt_lattice_plan(ws, n_frames, nullptr, B, id_offsets, 0, 0, align);      // (host only: refuses before a device is looked for)
+    need_device();
+    rnnt_lattice_upload(ws, nullptr, nullptr);
+    if (ws.a.labs) PK_HIP(hipMemcpyAsync(ws.a.lab.p, lab, (size_t)ws.a.labs * 4, hipMemcpyHostToDevice, nullptr));
+    PK_HIP(hipMemcpyAsync(ws.a.blk.p, blk, (size_t)ws.a.cells * 4, hipMemcpyHostToDevice, nullptr));
+    run_rnnt_walk(ws, nullptr);
+    PK_CHECK_LAUNCH();
+    rnnt_copy_out(ws, start, end, conf, value, ok, nullptr);
+}
+
+// the argument checks of the model entry points; after them the call is planned (host only) in m.rnnt
+static void rnnt_checks(Model &m, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of,
+                        int n_hyp, bool align, int chunk_rows = 0) {
+    rnnt_model_checks(m);
+    need(n_clips >= 1 && n_hyp >= 1 && chunk_rows >= 0, "n_clips/n_hyp/chunk_rows");
+    if (clip_of) for (int h = 0; h < n_hyp; ++h) need(clip_of[h] >= 0 && clip_of[h] < n_clips, "clip_of[h] outside [0, n_clips)");
+    else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
+    align_check_args(ids, id_offsets, n_hyp, m.cfg.vocab_size, m.cfg.blank_id);
+    if (n_frames) for (int b = 0; b < n_clips; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
+    m.require_gpu();
+    rnnt_plan_call(m, m.rnnt, n_frames, n_clips, T, id_offsets, clip_of, n_hyp, align, chunk_rows);
+}
+
+// uploads enc and runs enc_proj ONCE over the clips' rows
+static void rnnt_enc_proj(Model &m, const float *enc, const int32_t *n_frames, int n_clips, int T) {
+    size_t rows;
+    size_ws(m, n_frames, n_clips, T, rows);
+    PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
+    m.run_enc_proj(m.ws.x.as<float>(), (int64_t)rows, m.ws.ep.as<float>(), m.stream);
+}
+
+static void rnnt_decode(Model &m, bool align, const float *enc, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets,
+                        const int32_t *clip_of, int n_hyp, int32_t *start, int32_t *end, float *conf, float *value, int32_t *ok) {
+    rnnt_checks(m, n_frames, n_clips, T, ids, id_offsets, clip_of, n_hyp, align);
+    need(!align || id_offsets[n_hyp] == 0 || (start && end && conf), "start/end/conf");
+    rnnt_enc_proj(m, enc, n_frames, n_clips, T);
+    run_rnnt_call(m, m.rnnt, m.ws.ep.as<float>(), ids, id_offsets);
+    PK_CHECK_LAUNCH();
+    const RnntLatticeWs &w = m.rnnt;
+    std::copy(w.value.begin(), w.value.end(), value);
+    std::copy(w.ok.begin(), w.ok.end(), ok);
+    if (!align) return;
+    const size_t n = (size_t)id_offsets[n_hyp];
+    std::copy(w.h_start.begin(), w.h_start.begin() + n, start);
+    std::copy(w.h_end.begin(), w.h_end.begin() + n, end);
+    std::copy(w.h_conf.begin(), w.h_conf.begin() + n, conf);
+}
+
+extern "C" {
+
+pk_status pk_rnnt_align(const float *lab, const float *blk, const int32_t *n_frames, int B, const int32_t *id_offsets, int32_t *start, int32_t *end,
+                        float *conf, float *score, int32_t *ok) {
+    return guard([&] { rnnt_host_walk(true, lab, blk, n_frames, B, id_offsets, start, end, conf, score, ok); });
+}
+
+pk_status pk_rnnt_total(const float *lab, const float *blk, const int32_t *n_frames, int B, const int32_t *id_offsets, float *total, int32_t *ok) {
+    return guard([&] { rnnt_host_walk(false, lab, blk, n_frames, B, id_offsets, nullptr, nullptr, nullptr, total, ok); });
+}
+
+pk_status pk_rnnt_align_decode(pk_model *h, const float *enc, int B, int T, const int32_t *ids, const int32_t *id_offsets, int32_t *start, int32_t *end,
+                               float *conf, float *score, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && score && ok && T > 0, "model/enc/score/ok/T");
+        rnnt_decode(*h->m, true, enc, nullptr, B, T, ids, id_offsets, nullptr, B, start, end, conf, score, ok);
+    });
+}
+
+pk_status pk_rnnt_align_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                                      int32_t *start, int32_t *end, float *conf, float *score, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && n_frames && score && ok, "model/enc/n_frames/score/ok");
+        rnnt_decode(*h->m, true, enc, n_frames, B, 0, ids, id_offsets, nullptr, B, start, end, conf, score, ok);
+    });
+}
+
+pk_status pk_rnnt_total_decode(pk_model *h, const float *enc, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of,
+                               int n_hyp, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && total && ok && T > 0, "model/enc/total/ok/T");
+        rnnt_decode(*h->m, false, enc, nullptr, n_clips, T, ids, id_offsets, clip_of, n_hyp, nullptr, nullptr, nullptr, total, ok);
+    });
+}
+
+pk_status pk_rnnt_total_decode_ragged(pk_model *h, const float *enc, const int32_t *n_frames, int n_clips, const int32_t *ids, const int32_t *id_offsets,
+                                      const int32_t *clip_of, int n_hyp, float *total, int32_t *ok) {
+    return guard([&] {
+        need(h && enc && n_frames && total && ok, "model/enc/n_frames/total/ok");
+        rnnt_decode(*h->m, false, enc, n_frames, n_clips, 0, ids, id_offsets, clip_of, n_hyp, nullptr, nullptr, nullptr, total, ok);
+    });
+}
+
+pk_status pk_rnnt_align_decode_timed(pk_model *h, const float *enc, const int32_t *n_frames, int B, int T, const int32_t *ids, const int32_t *id_offsets,
+                                     int reps, float ms[4]) {
+    return guard([&] {
+        need(h && enc && ms && reps > 0 && (n_frames || T > 0), "model/enc/ms/T/reps");
+        Model &m = *h->m;
+        rnnt_checks(m, n_frames, B, T, ids, id_offsets, nullptr, B, /*align=*/true);
+        rnnt_enc_proj(m, enc, n_frames, B, T);
+        Events<5> ev;
+        ev.create();
+        std::vector<float> t[4];
+        for (int r = 0; r <= reps; ++r) {                          // (the first pass warms the buffers up and is not counted)
+            float v[4] = {0, 0, 0, 0};                             // per stage, summed over the groups of the call
+            run_rnnt_call(m, m.rnnt, m.ws.ep.as<float>(), ids, id_offsets, ev.e, v);
+            PK_CHECK_LAUNCH();
+            if (r > 0) for (int k = 0; k < 4; ++k) t[k].push_back(v[k]);
+        }
+        for (int k = 0; k < 4; ++k) ms[k] = median_of(t[k]);
+    });
+}
+
+pk_status pk_diag_rnnt_lattice(pk_model *h, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
+                               int chunk_rows, float *lab, float *blk) {
+    return guard([&] {
+        need(h && enc && n_frames && lab && blk, "model/enc/n_frames/lab/blk");
+        Model &m = *h->m;
+        rnnt_checks(m, n_frames, B, 0, ids, id_offsets, nullptr, B, /*align=*/false, chunk_rows);
+        RnntLatticeWs &ws = m.rnnt;
+        if (ws.gstart.size() != 2) fail(PK_ERR_UNSUPPORTED, "pk_diag_rnnt_lattice: the call must fit one group (at most 256 utterances, 1 GiB of scratch)");
+        size_t labs = 0, cells = 0;
+        for (int b = 0; b < B; ++b) {
+            const size_t U = (size_t)(id_offsets[b + 1] - id_offsets[b]);
+            labs += (size_t)n_frames[b] * U; cells += (size_t)n_frames[b] * (U + 1);
+        }
+        const size_t G = PK_DIAG_TDT_LATTICE_GUARD, nl = labs + G, nb = cells + G;
+        ws.a.lab.reserve(nl * 4); ws.a.blk.reserve(nb * 4);
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.a.lab.p, 0x7FC5A5A5, nl, m.stream));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.a.blk.p, 0x7FC5A5A5, nb, m.stream));
+        rnnt_enc_proj(m, enc, n_frames, B, 0);
+        run_rnnt_group_lattice(m, ws, 0, m.ws.ep.as<float>(), ids, id_offsets);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(lab, ws.a.lab.p, nl * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipMemcpyAsync(blk, ws.a.blk.p, nb * 4, hipMemcpyDeviceToHost, m.stream));
+        PK_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
 /* ---- CTC keyword spotting (kernels/ctc_kws.hip) --------------------------------------------------------------------------------------- */
 void pk_kws_options_default(pk_kws_options *out) {
     if (!out) return;

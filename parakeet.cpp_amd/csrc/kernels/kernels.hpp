@@ -633,6 +633,25 @@ struct TdtTotalArgs {
 };
 void launch_tdt_total(const TdtTotalArgs &a, hipStream_t s);
 
+// Forced alignment and forward-algorithm total of GIVEN token strings under the plain RNN-T head (kernels/rnnt_lattice.hip).
+// The lattice is packed as the TDT one with D = 0 (no dl): blank arc (t, u) -> (t + 1, u), label arc (t, u) -> (t, u + 1).
+constexpr int kRnntMaxTokens = 1023;            // U <= this: one thread per column, at most 16 waves per workgroup
+enum { RNNT_FOLD_MAX = 0, RNNT_FOLD_SUM = 1 };  // the alignment (max-plus, back-pointer bits) / the total (log-sum)
+struct RnntWalkArgs {
+    TdtLattice lt;                              // D = 0, dl unused
+    const int64_t *bits_off;                    // [B + 1], in dwords: utterance b's bits are [U_b + 1][ceil(T_b / 32)] dwords from bits_off[b]
+    unsigned *bits;                             // bit t & 31 of dword [u][t >> 5]: 1 = cell (t, u) took the label arc (RNNT_FOLD_MAX only)
+    float *value; int *ok;                      // [B]: the alignment's score / the total; ok = value > -inf
+    int *start, *end; float *conf;              // packed as ids (zero-filled by the caller: an utterance with ok = 0 writes none); the trace only
+    int u_max;                                  // over the batch: the workgroup is 64 ceil((u_max + 1) / 64) threads
+};
+// the walk: value[B] (and, for RNNT_FOLD_SUM, ok[B]); RNNT_FOLD_MAX also fills bits
+void launch_rnnt_walk(const RnntWalkArgs &a, int fold, hipStream_t s);
+// after a RNNT_FOLD_MAX walk: ok[B], and start / end / conf of every utterance with ok = 1
+void launch_rnnt_trace(const RnntWalkArgs &a, hipStream_t s);
+// rows [row0, row0 + n) of the RNN-T heads product's output, logits[i][V], taken to their two kept values (launch_tdt_lattice_keep without durations)
+void launch_rnnt_lattice_keep(const TdtLattice &lt, const int *ids, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s);
+
 // TDT keyword spotting (kernels/tdt_kws.hip): "utterance" b of the lattice is one (clip, keyword) pair, packed as for the
 // alignment (column U_b = L is packed and never read), plus top[cell]: the largest token log-prob of the row.  One wave per pair, lane u owns column u.
 struct TdtKwsArgs {
