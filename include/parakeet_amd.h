@@ -150,6 +150,17 @@ pk_status pk_model_get_ffn_mxfp8(const pk_model *m, int *on);
  * after the window.  pk_group replicas and the streaming path are not covered.  Not to be changed while a batch is in flight. */
 pk_status pk_model_set_local_attention_bf16(pk_model *m, int on);
 pk_status pk_model_get_local_attention_bf16(const pk_model *m, int *on);
+/* bf16 TDT lattice (opt-in, gemm_bf16 models with a TDT joint whose joint_hidden is a multiple of 32 and at most 1120; any other model:
+ * PK_ERR_UNSUPPORTED -- the fp32 mode's contract is bit equality).  on != 0: pk_tdt_align_decode(_ragged), pk_tdt_align_pcm,
+ * pk_tdt_total_decode(_ragged), pk_tdt_score_pcm, their _timed forms and pk_diag_tdt_lattice (whose chunk_rows is then ignored) accept this model
+ * instead of refusing it as gemm_bf16, and the lattice values come from ONE launch of kernels/tdt_lattice_bf16.hip:
+ * z = bf16(relu(enc_proj + pred_proj)) against a bf16 copy of the heads weights on the MFMA, fp32 accumulation, bias and log-softmax; no
+ * activation or logits buffer.  The prediction net runs on its fp32 weights, the walks are unchanged and exact on the rows they get.  The first
+ * on makes the bf16 weight copy (+ (V + D) J 2 bytes of device memory).  Results are in the tolerance class of the gemm_bf16 mode
+ * (tests/test_gpu_tdt_lattice_bf16.py).  on = 0 (the default): every path, bit and refusal of a model that never set it.  Keyword spotting, the TDT
+ * beam, streaming, pk_group and pk_transcribe_pcm_nbest_rescored keep refusing a gemm_bf16 model.  Not to be changed while a batch is in flight. */
+pk_status pk_model_set_tdt_lattice_bf16(pk_model *m, int on);
+pk_status pk_model_get_tdt_lattice_bf16(const pk_model *m, int *on);
 
 /* ---- stage entry points (host buffers; used by the parity tests and the C++ facade) ----------------------- */
 /* preprocess_audio (src/audio.cpp:100-158): n_clips clips of n_samples each -> feats[n_clips][n_frames][mel_bins],
@@ -590,6 +601,13 @@ pk_status pk_tdt_align_pcm(pk_model *m, const float *pcm, const int64_t *offsets
 #define PK_DIAG_TDT_LATTICE_GUARD 64
 pk_status pk_diag_tdt_lattice(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
                               int chunk_rows, float *lab, float *blk, float *dl);
+/* Diagnostic: the bf16 lattice kernel (kernels/tdt_lattice_bf16.hip; pk_model_set_tdt_lattice_bf16) alone on operands from the host, no model:
+ * ep = the packed frames' enc_proj rows [sum_b n_frames[b]][J], pp = the prediction net's rows [(U_max + 1) B][J] (row u B + b: utterance b after
+ * ids[:u]), wld [V + D][J] / bld [V + D] = the label rows then the duration rows of the heads, fp32.  The weight is rounded to bf16 and packed
+ * as the engine packs it, then the ONE launch fills lab / blk / dl, returned with the guard words of pk_diag_tdt_lattice.
+ * PK_ERR_INVALID: D outside [1, 8], blank or an id outside [0, V), bad tables.  PK_ERR_UNSUPPORTED: J no multiple of 32 or above 1120. */
+pk_status pk_diag_tdt_lattice_bf16(const float *ep, const float *pp, const float *wld, const float *bld, const int32_t *ids, const int32_t *n_frames,
+                                   const int32_t *id_offsets, int B, int V, int D, int J, int blank, float *lab, float *blk, float *dl);
 /* ---- TDT log-likelihood of a GIVEN transcript, and CTC n-best rescored with it ------------------------------------------------
  * How probable is this token string under the TDT head: the forward algorithm on the lattice of pk_tdt_align (same cells, same arcs; a blank of
  * duration 0 and a blank of duration 1 are two arcs to the next frame and both are summed), specified operation by operation in DESIGN.md

@@ -350,6 +350,9 @@ _LATE_SIGNATURES = {
     "pk_model_get_local_attention_bf16": [C.c_void_p, C.POINTER(C.c_int)],
     "pk_diag_relpos_local_attention_bf16": [C.c_int, i32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, f32p, f32p,
                                             C.POINTER(C.c_int)],
+    "pk_model_set_tdt_lattice_bf16": [C.c_void_p, C.c_int],
+    "pk_model_get_tdt_lattice_bf16": [C.c_void_p, C.POINTER(C.c_int)],
+    "pk_diag_tdt_lattice_bf16": [f32p, f32p, f32p, f32p, i32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p],
     "pk_resample_length": [C.c_int64, C.c_int, C.c_int],
     "pk_resample_run": [C.c_int, C.c_int],
     "pk_resample_table": [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -1887,6 +1890,24 @@ def diag_relpos_local_attention_bf16(qkv, pos, bias_u, bias_v, n_heads, left, ri
     return out, var.value
 
 
+def tdt_lattice_bf16(ep, pp, wld, bld, ids, n_frames, V, D, blank):
+    """pk_diag_tdt_lattice_bf16: the bf16 lattice kernel alone, no model.  ep [sum T][J] packed frames, pp [(U_max + 1) B][J] (row u B + b), wld
+    [V + D][J], bld [V + D], ids a list of B id lists -> (lab [labs + G], blk [cells + G], dl [cells D + G]) flat, G = TDT_LATTICE_GUARD words of
+    the fill pattern 0x7FC5A5A5 behind each."""
+    ep, pp, wld, bld = _c(ep), _c(pp), _c(wld), _c(bld)
+    pid, off = _pack_ids(ids)
+    T = np.ascontiguousarray(n_frames, np.int32)
+    U = np.diff(off).astype(np.int64)
+    J = ep.shape[1]
+    assert wld.shape == (V + D, J) and bld.shape == (V + D,) and ep.shape[0] == int(T.sum()) and pp.shape == ((int(U.max()) + 1) * len(T), J)
+    cells, labs = int((T * (U + 1)).sum()), int((T * U).sum())
+    G = TDT_LATTICE_GUARD
+    lab = np.zeros(labs + G, np.float32); blk = np.zeros(cells + G, np.float32); dl = np.zeros(cells * D + G, np.float32)
+    check(lib().pk_diag_tdt_lattice_bf16(_f(ep), _f(pp), _f(wld), _f(bld), _i(pid), _i(T), _i(off), len(T), int(V), int(D), J, int(blank),
+                                         _f(lab), _f(blk), _f(dl)))
+    return lab, blk, dl
+
+
 CONV_VARIANT_WORDS = 17                  # PK_DIAG_CONV_VARIANT_WORDS
 
 
@@ -2797,6 +2818,16 @@ class Model:
     def local_attention_bf16(self):
         on = C.c_int(0)
         check(lib().pk_model_get_local_attention_bf16(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_tdt_lattice_bf16(self, on=True):
+        """pk_model_set_tdt_lattice_bf16: TDT alignment and scoring of a gemm_bf16 model through the one-launch bf16 lattice kernel (tdt_align_decode,
+        align_tdt, tdt_total_decode, score_tdt, tdt_lattice; off: they refuse a gemm_bf16 model)."""
+        check(lib().pk_model_set_tdt_lattice_bf16(self._h, int(bool(on))))
+
+    def tdt_lattice_bf16(self):
+        on = C.c_int(0)
+        check(lib().pk_model_get_tdt_lattice_bf16(self._h, C.byref(on)))
         return bool(on.value)
 
     def set_input_rate(self, rate):

@@ -1237,7 +1237,7 @@ pk_status pk_tdt_score_pcm(pk_model *h, const float *pcm, const int64_t *offsets
         need(h && pcm && offsets && total && ok && n_clips > 0 && n_hyp > 0, "model/pcm/offsets/total/ok/n_clips/n_hyp");
         need(texts || id_offsets_in, "texts or ids/id_offsets");
         Model &m = *h->m;
-        tdt_align_model_checks(m);
+        tdt_align_model_checks(m, /*lattice_bf16_ok=*/true);
         if (clip_of) for (int q = 0; q < n_hyp; ++q) need(clip_of[q] >= 0 && clip_of[q] < n_clips, "clip_of[h] outside [0, n_clips)");
         else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
         std::vector<int32_t> all_ids, all_off;
@@ -1344,7 +1344,7 @@ pk_status pk_tdt_align_pcm(pk_model *h, const float *pcm, const int64_t *offsets
         need(h && pcm && offsets && results && ok && n_clips > 0, "model/pcm/offsets/results/ok/n_clips");
         need(texts || id_offsets_in, "texts or ids/id_offsets");
         Model &m = *h->m;
-        tdt_align_model_checks(m);
+        tdt_align_model_checks(m, /*lattice_bf16_ok=*/true);
         std::vector<int32_t> all_ids, all_off;
         align_transcripts(m, n_clips, texts, ids_in, id_offsets_in, m.cfg.vocab_size, m.cfg.blank_id, all_ids, all_off);
         m.require_gpu();

@@ -246,7 +246,7 @@ static void tdt_align_queue(Model &m, const float *enc, const int32_t *n_frames,
 }
 
 static void tdt_align_checks(Model &m, const int32_t *n_frames, int B, int T, const int32_t *ids, const int32_t *id_offsets, int chunk_rows) {
-    tdt_align_model_checks(m);
+    tdt_align_model_checks(m, /*lattice_bf16_ok=*/true);
     align_check_args(ids, id_offsets, B, m.cfg.vocab_size, m.cfg.blank_id);
     if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
     need(chunk_rows >= 0, "chunk_rows");
@@ -827,6 +827,7 @@ pk_status pk_tdt_align_decode_timed(pk_model *h, const float *enc, const int32_t
             first = false;
         });
         // the heads product of ONE chunk alone (the rows the last pass left in the activation buffer), for the lattice stage's overhead over it
+        if (m.tdt_lattice_bf16) { ms[3] = 0.0f; return; }          // (the bf16 lattice kernel has no heads product of its own to time)
         const int n = (int)std::min<int64_t>(m.talign.chunk_rows, m.talign.cells);
         time_stages<1>(m, reps, ms + 3, [&](hipEvent_t *ev) {
             PK_HIP(hipEventRecord(ev[0], m.stream));
@@ -857,13 +858,55 @@ pk_status pk_diag_tdt_lattice(pk_model *h, const float *enc, const int32_t *n_fr
     });
 }
 
+// kernels/tdt_lattice_bf16.hip alone on the caller's operands: the weight packed as Model::set_tdt_lattice_bf16 packs it, the one launch, the
+// outputs staged as above.  No model.
+pk_status pk_diag_tdt_lattice_bf16(const float *ep, const float *pp, const float *wld, const float *bld, const int32_t *ids, const int32_t *n_frames,
+                                   const int32_t *id_offsets, int B, int V, int D, int J, int blank, float *lab, float *blk, float *dl) {
+    return guard([&] {
+        need(ep && pp && wld && bld && lab && blk && dl && V >= 1 && J >= 1, "ep/pp/wld/bld/lab/blk/dl/V/J");
+        need(D >= 1 && D <= 8 && blank >= 0 && blank < V, "D 1 .. 8, blank inside [0, V)");
+        const int32_t durations[8] = {};                             // (the walk's durations play no part in the lattice values)
+        tdt_host_lattice_checks(durations, n_frames, B, id_offsets);
+        need(id_offsets[B] == 0 || ids, "ids");
+        for (int i = 0; i < id_offsets[B]; ++i) need(ids[i] >= 0 && ids[i] < V, "ids outside [0, V)");
+        if (tdt_lattice_bf16_rows(J) == 0) fail(PK_ERR_UNSUPPORTED, "the bf16 TDT lattice kernel: J %d (a multiple of 32, at most 1120)", J);
+        TdtAlignWs ws;
+        tdt_lattice_plan(ws, n_frames, nullptr, B, 0, id_offsets, durations, D, 0, 0, 0, /*back_pointers=*/false, "TDT lattice (bf16)");
+        need_device();
+        const size_t G = PK_DIAG_TDT_LATTICE_GUARD, nl = (size_t)ws.labs + G, nb = (size_t)ws.cells + G, nd = (size_t)ws.cells * D + G;
+        ws.lab.reserve(nl * 4); ws.blk.reserve(nb * 4); ws.dl.reserve(nd * 4);
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.lab.p, 0x7FC5A5A5, nl, nullptr));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.blk.p, 0x7FC5A5A5, nb, nullptr));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.dl.p, 0x7FC5A5A5, nd, nullptr));
+        tdt_lattice_upload(ws, ids, nullptr, /*token_results=*/false);
+        int64_t rows = 0;
+        for (int b = 0; b < B; ++b) rows += n_frames[b];
+        const size_t VD = (size_t)V + D, n_ep = (size_t)rows * J, n_pp = (size_t)(ws.u_max + 1) * B * J;
+        DevBuf d_ep, d_pp, d_w, d_b, d_w16;
+        d_ep.reserve(n_ep * 4); d_pp.reserve(n_pp * 4); d_w.reserve(VD * J * 4); d_b.reserve(VD * 4);
+        d_w16.reserve(tdt_lattice_bf16_weight_bytes((int)VD, J));
+        PK_HIP(hipMemcpyAsync(d_ep.p, ep, n_ep * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_pp.p, pp, n_pp * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_w.p, wld, VD * J * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_b.p, bld, VD * 4, hipMemcpyHostToDevice, nullptr));
+        launch_tdt_lattice_bf16_pack(d_w.as<float>(), (int)VD, J, d_w16.p, nullptr);
+        TdtLatticeBf16Args a{ws.lattice(), ws.ep_row0(), ws.ids.as<int>(), d_ep.as<float>(), d_pp.as<float>(), d_w16.p, d_b.as<float>(), V, J, blank, ws.cells};
+        launch_tdt_lattice_bf16(a, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(lab, ws.lab.p, nl * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(blk, ws.blk.p, nb * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(dl, ws.dl.p, nd * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
 }  // extern "C"
 
 /* ---- the forward-algorithm total of given token strings under the TDT head (kernels/tdt_total.hip) ------------------------------------ */
 // the argument checks of the model entry points; -> after them the call is planned (host only) in m.ttotal
 static void tdt_total_checks(Model &m, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of,
                              int n_hyp) {
-    tdt_align_model_checks(m);
+    tdt_align_model_checks(m, /*lattice_bf16_ok=*/true);
     need(n_clips >= 1 && n_hyp >= 1, "n_clips/n_hyp");
     if (clip_of) for (int h = 0; h < n_hyp; ++h) need(clip_of[h] >= 0 && clip_of[h] < n_clips, "clip_of[h] outside [0, n_clips)");
     else need(n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");

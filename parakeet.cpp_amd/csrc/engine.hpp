@@ -272,6 +272,14 @@ class Model {
     std::vector<MxLayerW> mx_layers_;
     DevBuf mx_buf_;
 
+    // The bf16 lattice kernel of TDT alignment and scoring (pk_model_set_tdt_lattice_bf16; kernels/tdt_lattice_bf16.hip), off by default: gemm_bf16
+    // models with a TDT joint whose width the kernel takes only.  On, tdt_align_model_checks lets this model through for the alignment and total
+    // entry points and run_tdt_align_lattice launches the one kernel instead of act / heads / keep.  The load-order bf16 copy of wld is made from
+    // the resident fp32 rows when the mode is first switched on: + (V + D, up to 64) J 2 bytes in HBM.  Not to be changed while a batch is in flight.
+    bool tdt_lattice_bf16 = false;
+    void set_tdt_lattice_bf16(bool on);
+    DevBuf wld_tl16_;
+
     ProfileSink *prof = nullptr;
     void klaunch_begin(const char *name, double flops, double bytes, hipStream_t s);
     void klaunch_end(hipStream_t s);

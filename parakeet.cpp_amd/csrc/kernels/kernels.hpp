@@ -623,6 +623,23 @@ void launch_tdt_lattice_act(const TdtLattice &lt, const int *ep_row0, const floa
 // ... and the same rows of the heads product's output, logits[i][V + D], taken to their 2 + D kept values: canonical log-softmax over the V label
 // columns and over the D duration columns, gathered at ids[u] (u < U_b) and blank
 void launch_tdt_lattice_keep(const TdtLattice &lt, const int *ids, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s);
+// The three launches above as ONE kernel of the tolerance-class mode (kernels/tdt_lattice_bf16.hip; pk_model_set_tdt_lattice_bf16): every lattice row
+// of the batch from ep / pp to lab / blk / dl, z and the heads weights as bf16 on the MFMA, fp32 accumulation, bias and log-softmax; no z and no
+// logits buffer.  w16 = the load-order bf16 copy of wld [V + D][J] that launch_tdt_lattice_bf16_pack writes (tdt_lattice_bf16_weight_bytes of it).
+// tdt_lattice_bf16_rows: lattice rows per workgroup at joint width J, 0 where the kernel does not apply (J % 32 != 0 or J > 1120).
+struct TdtLatticeBf16Args {
+    TdtLattice lt;
+    const int *ep_row0, *ids;
+    const float *ep, *pp;                       // enc_proj rows; prediction-net rows pp[u B + b]
+    const void *w16;
+    const float *bld;                           // [V + D]
+    int V, J, blank;
+    int64_t cells;                              // lattice rows in all (cell_off[B])
+};
+int tdt_lattice_bf16_rows(int J);
+size_t tdt_lattice_bf16_weight_bytes(int VD, int J);
+void launch_tdt_lattice_bf16_pack(const float *wld, int VD, int J, void *w16, hipStream_t s);
+void launch_tdt_lattice_bf16(const TdtLatticeBf16Args &a, hipStream_t s);
 
 // The forward-algorithm total of GIVEN token strings on the same lattice (kernels/tdt_total.hip): the log-sum over every
 // path to END.  One workgroup per hypothesis, widths kTdtAlignThreads, the alignment's limits.

@@ -118,11 +118,11 @@ void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_
     }
 }
 
-void tdt_align_model_checks(const Model &m) {
+void tdt_align_model_checks(const Model &m, bool lattice_bf16_ok) {
     if (m.cfg.vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no prediction net / joint (encoder-only configuration): TDT alignment needs a TDT joint");
     if (m.cfg.rnnt_head || m.cfg.num_durations <= 0)
         fail(PK_ERR_UNSUPPORTED, "TDT alignment needs a TDT joint (label + duration heads): this model has an RNN-T head");
-    if (m.cfg.gemm_bf16) fail(PK_ERR_UNSUPPORTED, "TDT alignment has no gemm_bf16 form: the decode weights of this model exist only rounded to bf16");
+    if (m.cfg.gemm_bf16 && !(lattice_bf16_ok && m.tdt_lattice_bf16)) fail(PK_ERR_UNSUPPORTED, "TDT alignment has no gemm_bf16 form: the decode weights of this model exist only rounded to bf16");
 }
 
 size_t tdt_align_bytes(const TdtAlignWs &ws) {
@@ -142,6 +142,11 @@ void run_tdt_align_heads(Model &m, TdtAlignWs &ws, int n, hipStream_t s) {
 void run_tdt_align_lattice(Model &m, TdtAlignWs &ws, const float *d_ep, hipStream_t s) {
     const pk_config &c = m.cfg;
     const int V = c.vocab_size, D = ws.D, J = c.joint_hidden, CH = ws.chunk_rows;
+    if (m.tdt_lattice_bf16) {          // (a gemm_bf16 model: the model check admits no other with the switch on) one launch, no z, no logits
+        TdtLatticeBf16Args a{ws.lattice(), ws.ep_row0(), ws.ids.as<int>(), d_ep, ws.pp.as<float>(), m.wld_tl16_.p, m.bld, V, J, c.blank_id, ws.cells};
+        launch_tdt_lattice_bf16(a, s);
+        return;
+    }
     ws.z.reserve((size_t)CH * J * 4);
     ws.logits.reserve((size_t)CH * (V + D) * 4);
     const TdtLattice lt = ws.lattice();

@@ -51,12 +51,15 @@ void tdt_lattice_upload(TdtAlignWs &ws, const int32_t *ids, hipStream_t s, bool 
 // pred_proj of every prefix: U_max + 1 lock-step steps of the prediction net over [blank, ids...] on the decode loop's skinny products -> ws.pp.
 // Uses m.ws's LSTM state buffers (sized for B utterances by the caller), or state = {h, hn, c, cn}, each [L][B][Hp] floats.
 void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_t s, float *const *state = nullptr);
-// the lattice values from ep = enc_proj of the packed frames (ws.tab's ep_row0), in chunks of ws.chunk_rows rows -> ws.lab / blk / dl
+// the lattice values from ep = enc_proj of the packed frames (ws.tab's ep_row0), in chunks of ws.chunk_rows rows -> ws.lab / blk / dl; with
+// Model::tdt_lattice_bf16 on, ONE launch of kernels/tdt_lattice_bf16.hip over all rows instead (ws.chunk_rows, ws.z and ws.logits unused)
 void run_tdt_align_lattice(Model &m, TdtAlignWs &ws, const float *d_ep, hipStream_t s);
 // the heads product of the first n rows of ws.z alone -> ws.logits (what run_tdt_align_lattice runs per chunk; the timed entry point measures it on its own)
 void run_tdt_align_heads(Model &m, TdtAlignWs &ws, int n, hipStream_t s);
-// what the model entry points refuse (include/parakeet_amd.h): no TDT joint (encoder-only, RNN-T head), gemm_bf16
-void tdt_align_model_checks(const Model &m);
+// what the model entry points refuse (include/parakeet_amd.h): no TDT joint (encoder-only, RNN-T head), gemm_bf16.  lattice_bf16_ok: the caller
+// computes its lattice with run_tdt_align_lattice alone (the alignment and total entry points), which a gemm_bf16 model with
+// pk_model_set_tdt_lattice_bf16 on serves; keyword spotting, the beam and streaming pass false and keep refusing.
+void tdt_align_model_checks(const Model &m, bool lattice_bf16_ok = false);
 // bytes of device memory the alignment's buffers hold (pk_diag_mem_info)
 size_t tdt_align_bytes(const TdtAlignWs &ws);
 // the walk and the back-trace over ws.lab / blk / dl; results stay on the device in ws

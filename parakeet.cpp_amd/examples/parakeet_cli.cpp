@@ -4,8 +4,10 @@
 //                [--boost-score N] [--sortformer-weights PATH] [--latency N] [--streaming] [--gpu] [--beam W [--nbest N] [--prune K] [--beam-head ctc|tdt]]
 //                [--align "text" | --align-file path.txt] [--align-head ctc|tdt] [--score "text"] [--nbest N --rescore-tdt W]
 //                [--spot "phrase"]... [--spot-file path.txt] [--spot-head ctc|tdt] [--spot-hits N] [--spot-min-score X] [--lm file.arpa [--lm-alpha A] [--lm-beta B]]
-//                [--device-resample] [--vad [--vad-max-piece S]] [--attention-context L,R [--local-attention-bf16]]
+//                [--device-resample] [--vad [--vad-max-piece S]] [--attention-context L,R [--local-attention-bf16]] [--tdt-lattice-bf16]
 //                [--nlm file.safetensors --nlm-heads H --nlm-bos ID [--nlm-eos ID] [--nlm-alpha A] [--nlm-beta B]]
+// New: --tdt-lattice-bf16 (tdt-ctc-110m, tdt-600m) asks for the bf16 TDT lattice kernel under --align ... --align-head tdt and --score
+// (set_tdt_lattice_bf16): the engine accepts it on a gemm_bf16 model and refuses it on any other.
 // New: --attention-context L,R (tdt-ctc-110m, tdt-600m) limits the encoder's attention to the L frames before and the R frames after each frame
 // (Transcriber::set_attention_context: long recordings).  --local-attention-bf16 (only with --attention-context) asks for the bf16-MFMA band
 // kernel (set_local_attention_bf16): the engine accepts it on a gemm_bf16 model with head size 64 / 128 and refuses it on any other.
@@ -63,6 +65,7 @@ static void usage(const char *prog) {
               << "  --spot-hits N (default 1), --spot-min-score X (<= 0; default: no threshold), --spot-head ctc|tdt (default ctc; tdt works for tdt-600m)\n"
               << "  --device-resample  resample files that are not 16 kHz on the device instead of on the host (tdt-ctc-110m, tdt-600m)\n"
               << "  --attention-context L,R [--local-attention-bf16]  limited-context attention for long audio; the bf16 band kernel needs a bf16 model\n"
+              << "  --tdt-lattice-bf16  TDT alignment and scoring on the bf16 lattice kernel; needs a bf16 model\n"
               << "  --vad [--vad-max-piece S]  transcribe only the speech, cut at the pauses into pieces of at most S seconds (default 30)\n"
               << "  --boost PHRASE (repeatable), --boost-score N (default 5.0)\n"
               << "  --vocab PATH, --sortformer-weights PATH, --timestamps, --streaming, --latency N (0/1/6/13), --gpu\n";
@@ -157,7 +160,7 @@ int main(int argc, char **argv) {
         std::vector<std::string> boost, spot;
         SpotOptions spot_opts;
         float boost_score = 5.0f, vad_max_piece = 30.0f;
-        bool vad = false, spot_tdt = false, local_bf16 = false;
+        bool vad = false, spot_tdt = false, local_bf16 = false, tdt_lat_bf16 = false;
         int att_left = -1, att_right = -1;
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -226,6 +229,7 @@ int main(int argc, char **argv) {
                 att_left = std::stoi(w.substr(0, comma)); att_right = std::stoi(w.substr(comma + 1));
             }
             else if (a == "--local-attention-bf16") local_bf16 = true;
+            else if (a == "--tdt-lattice-bf16") tdt_lat_bf16 = true;
             else if (a == "--vad-max-piece" && i + 1 < argc) vad_max_piece = std::stof(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
@@ -251,6 +255,7 @@ int main(int argc, char **argv) {
         auto set_attention = [&](auto &t) {
             if (att_ctx) t.set_attention_context(att_left, att_right);
             if (local_bf16) t.set_local_attention_bf16(true);
+            if (tdt_lat_bf16) t.set_tdt_lattice_bf16(true);
         };
         if (vad && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --vad needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (vad && device_resample) { std::cerr << "Error: --vad works on 16 kHz audio; it does not combine with --device-resample\n"; return 1; }

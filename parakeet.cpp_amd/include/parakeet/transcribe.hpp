@@ -247,6 +247,9 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     // New: limited-context attention (set_attention_context) on the bf16-MFMA band kernel (pk_model_set_local_attention_bf16; gemm_bf16 models with
     // head size 64 / 128 only, any other is refused).  This engine's model; the replicas of to_all_gpus keep the fp32 band kernel.
     void set_local_attention_bf16(bool on) { check(pk_model_set_local_attention_bf16(m_, on ? 1 : 0)); }
+    // New: TDT alignment and scoring (align_tdt, score) of a gemm_bf16 model through the one-launch bf16 lattice kernel
+    // (pk_model_set_tdt_lattice_bf16; any other model is refused).  This engine's model; pk_group replicas have no such switch.
+    void set_tdt_lattice_bf16(bool on) { check(pk_model_set_tdt_lattice_bf16(m_, on ? 1 : 0)); }
     // New: files at another rate than 16 kHz are read at their own rate and resampled on the device on their way into the call
     // (pk_model_set_input_rate for the duration of the call) instead of by pk_read_audio's host resampler.  Off by default: for rates that
     // neither divide nor are divided by 16 kHz the device's samples differ from the host's by one fp32 rounding now and then.
@@ -536,6 +539,8 @@ class Transcriber {
     void set_ffn_mxfp8(bool on) { eng_.set_ffn_mxfp8(on); }
     /// New: limited-context attention on the bf16-MFMA band kernel (Engine::set_local_attention_bf16).
     void set_local_attention_bf16(bool on) { eng_.set_local_attention_bf16(on); }
+    /// New: TDT alignment and scoring on the bf16 lattice kernel (Engine::set_tdt_lattice_bf16).
+    void set_tdt_lattice_bf16(bool on) { eng_.set_tdt_lattice_bf16(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
@@ -672,6 +677,8 @@ class TDTTranscriber {
     void set_ffn_mxfp8(bool on) { eng_.set_ffn_mxfp8(on); }
     /// New: limited-context attention on the bf16-MFMA band kernel (Engine::set_local_attention_bf16).
     void set_local_attention_bf16(bool on) { eng_.set_local_attention_bf16(on); }
+    /// New: TDT alignment and scoring on the bf16 lattice kernel (Engine::set_tdt_lattice_bf16).
+    void set_tdt_lattice_bf16(bool on) { eng_.set_tdt_lattice_bf16(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 

@@ -9,7 +9,9 @@ the CTC alignment stage (pk_ctc_align_decode_timed on the clip's greedy CTC outp
 timer of pk_tdt_align_decode_timed: the same launch the lattice stage makes per chunk, between its own events; pk_diag_gemm runs that product
 too but has no device timer) with its flop rate and, scaled by cells / chunk_rows, what the bare products of the whole lattice would take.
 Writes profiles/tdt_align.md with --write.
-usage: python tools/bench_tdt_align.py [--reps 3] [--write]"""
+--bf16: instead, the lattice stage of a gemm_bf16 model with pk_model_set_tdt_lattice_bf16 on (kernels/tdt_lattice_bf16.hip) next to the fp32
+model's at the first two shapes, the two taking turns; writes profiles/tdt_lattice_bf16.md with --write.
+usage: python tools/bench_tdt_align.py [--reps 3] [--write] [--bf16]"""
 import argparse
 import dataclasses
 import json
@@ -36,14 +38,73 @@ NOTES = """
 """
 
 
+NOTES16 = """
+## Reading the figures
+
+- Both columns are `ms[1]` of `pk_tdt_align_decode_timed`, the lattice stage (enc_proj + everything up to lab / blk / dl), one pass per call, the
+  fp32 model and the gemm_bf16 model with `pk_model_set_tdt_lattice_bf16` on taking turns; medians over the turns.  Same weights file, same
+  encoder rows (the fp32 model's) and the same transcripts for both.
+- `*_heads_tflops` counts `2 cells (V + D) J` against the whole stage.
+- `weight_stream_gb` is what the bf16 kernel's workgroups read of the packed weights in all: `ceil(cells / rows_per_wg) (V + D) J 2` bytes.
+"""
+
+
+def bench_bf16(a, pk, capi, synth):
+    """--bf16: the lattice stage of the bf16 kernel (gemm_bf16 model, switch on) next to the fp32 lattice at the same shapes, interleaved."""
+    rng = np.random.default_rng(1)
+    lines = []
+    with tempfile.TemporaryDirectory() as td:
+        for preset, label, n, sec in (("tdt-ctc-110m", "64 x 10 s", 64, 10.0), ("tdt-600m", "32 x 30 s", 32, 30.0)):
+            cfg = dataclasses.replace(pk.make_110m_config() if preset == "tdt-ctc-110m" else pk.make_tdt_600m_config(), num_layers=1)
+            wp = os.path.join(td, preset + ".safetensors")
+            synth.save_weights(wp, synth.synth_weights(cfg, seed=42))
+            m32 = capi.Model(wp, cfg, device=0)
+            m16 = capi.Model(wp, dataclasses.replace(cfg, gemm_bf16=True), device=0)
+            m16.set_tdt_lattice_bf16(True)
+            enc = m32.encode(m32.mel(synth.synth_pcm(n, int(sec * 16000), seed=3)))
+            T = int(enc.shape[1])
+            ids = [rng.integers(0, cfg.blank_id, size=min(T // 4, 1535)).astype(np.int32) for _ in range(n)]      # one token per four frames
+            t32, t16 = [], []
+            for m in (m32, m16):
+                m.tdt_align_decode(enc, ids)                                           # warm-up of the buffers
+            for _ in range(a.reps):
+                t32.append(m32.tdt_align_decode_timed(enc, ids, reps=1)[1])
+                t16.append(m16.tdt_align_decode_timed(enc, ids, reps=1)[1])
+            V, D, J = cfg.vocab_size, len(cfg.durations), cfg.joint_hidden
+            cells = int(sum(T * (len(i) + 1) for i in ids))
+            rows = 128 if J <= 512 else 96 if J <= 736 else 64                         # tdt_lattice_bf16_rows
+            f32, f16 = float(np.median(t32)), float(np.median(t16))
+            out = {"metric": "tdt lattice stage ms", "config": preset + " (1 layer)", "batch": label, "frames": T, "tokens_per_clip": len(ids[0]),
+                   "lattice_cells": cells, "turns": a.reps, "fp32_lattice_ms": round(f32, 3), "bf16_lattice_ms": round(f16, 3),
+                   "fp32_min_max_ms": [round(min(t32), 3), round(max(t32), 3)], "bf16_min_max_ms": [round(min(t16), 3), round(max(t16), 3)],
+                   "speedup": round(f32 / f16, 2), "fp32_heads_tflops": round(2.0 * cells * (V + D) * J / (f32 * 1e-3) / 1e12, 1),
+                   "bf16_heads_tflops": round(2.0 * cells * (V + D) * J / (f16 * 1e-3) / 1e12, 1), "rows_per_wg": rows,
+                   "weight_stream_gb": round(-(-cells // rows) * (V + D) * J * 2 / 1e9, 2)}
+            lines.append(out)
+            print(json.dumps(out), flush=True)
+            m32.close(); m16.close()
+    if a.write:
+        with open(os.path.join(ROOT, "profiles", "tdt_lattice_bf16.md"), "w") as f:
+            f.write("# The bf16 TDT lattice kernel: lattice stage on one MI355X\n\n`python tools/bench_tdt_align.py --bf16 --reps %d --write` (synthetic weights and "
+                    "audio, random transcripts of one token per four frames).\n\n" % a.reps)
+            keys = [k for k in lines[0] if k != "metric"]
+            f.write("| " + " | ".join(keys) + " |\n|" + "---|" * len(keys) + "\n")
+            for o in lines:
+                f.write("| " + " | ".join(str(o[k]) for k in keys) + " |\n")
+            f.write("\n```\n" + "\n".join(json.dumps(o) for o in lines) + "\n```\n" + NOTES16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--write", action="store_true")
+    ap.add_argument("--bf16", action="store_true", help="the bf16 lattice kernel next to the fp32 lattice (profiles/tdt_lattice_bf16.md)")
     a = ap.parse_args()
     import pkload
     pk = pkload.load()
     from parakeet_cpp_amd import capi, synth
+    if a.bf16:
+        return bench_bf16(a, pk, capi, synth)
     rng = np.random.default_rng(1)
     lines = []
     with tempfile.TemporaryDirectory() as td:
