@@ -161,6 +161,14 @@ pk_status pk_model_get_local_attention_bf16(const pk_model *m, int *on);
  * beam, streaming, pk_group and pk_transcribe_pcm_nbest_rescored keep refusing a gemm_bf16 model.  Not to be changed while a batch is in flight. */
 pk_status pk_model_set_tdt_lattice_bf16(pk_model *m, int on);
 pk_status pk_model_get_tdt_lattice_bf16(const pk_model *m, int *on);
+/* Prefix-shared TDT total (opt-in, fp32 models with a TDT joint; a gemm_bf16 model or one without a TDT joint: PK_ERR_UNSUPPORTED).  on != 0:
+ * pk_tdt_total_decode(_ragged), pk_tdt_total_decode_timed, pk_tdt_score_pcm and pk_transcribe_pcm_nbest_rescored score the transcripts of a clip on
+ * ONE prefix tree per clip (kernels/tdt_tree.hip): a lattice column is (clip, ids[:u]), computed once however many
+ * hypotheses share it.  Every total and ok word equals the unshared path's bit for bit.  Groups are whole clips; a clip whose tree has more than 1536
+ * nodes is refused (PK_ERR_UNSUPPORTED).  on = 0 (the default): every kernel and launch of a model that never set it.  Not to be changed while a batch
+ * is in flight; pk_group replicas have no such switch. */
+pk_status pk_model_set_tdt_total_shared(pk_model *m, int on);
+pk_status pk_model_get_tdt_total_shared(const pk_model *m, int *on);
 
 /* ---- stage entry points (host buffers; used by the parity tests and the C++ facade) ----------------------- */
 /* preprocess_audio (src/audio.cpp:100-158): n_clips clips of n_samples each -> feats[n_clips][n_frames][mel_bins],
@@ -619,6 +627,21 @@ pk_status pk_diag_tdt_lattice_bf16(const float *ep, const float *pp, const float
  * formula is the alignment's without its back-pointer bytes: 4 (labs + cells (1 + D)) <= 1 GiB. */
 pk_status pk_tdt_total(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int B,
                        const int32_t *id_offsets, float *total, int32_t *ok);
+/* pk_tdt_total_tree: the prefix-tree walk (kernels/tdt_tree.hip) alone on a HOST tree lattice.  Needs a device, no model.
+ * Clip c owns nodes [node_offsets[c], node_offsets[c + 1]), n_c >= 1 of them: node 0 is the empty prefix (parent -1), parent[k] < k (clip-local).
+ * Values are packed clip after clip: blk [T_c][n_c], dl [T_c][n_c][D], lab [T_c][n_c - 1] whose column k - 1 holds the log-prob of the token on the
+ * edge into k at the cell of parent[k] -- a tree that is a single chain is pk_tdt_total's packing.  Hypothesis h of clip clip_of[h] (NULL: h) ends at
+ * the clip-local node end_node[h]; a clip without a hypothesis is not walked.  total / ok [n_hyp] equal pk_tdt_total's on each hypothesis's chain of
+ * columns bit for bit.  PK_ERR_INVALID: parent[k] outside [0, k), a bad end_node or clip_of.  PK_ERR_UNSUPPORTED: n_c > 1536, D or a duration out
+ * of range, 4 (labs + cells (1 + D)) > 1 GiB.
+ * pk_diag_tdt_prefix_tree: the builder alone, host arithmetic (no device, no model): the trees of n_hyp strings over n_clips clips in that layout.
+ * node_offsets [n_clips + 1], parent / token [at most n_clips + id_offsets[n_hyp]] (token of a root: -1), end_node [n_hyp].  Equal strings end at
+ * the same node, a prefix of another string at an inner node, an empty string at node 0; a clip without a string has its root alone. */
+pk_status pk_tdt_total_tree(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int n_clips,
+                            const int32_t *node_offsets, const int32_t *parent, const int32_t *end_node, const int32_t *clip_of_or_null, int n_hyp,
+                            float *total, int32_t *ok);
+pk_status pk_diag_tdt_prefix_tree(const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of_or_null, int n_clips, int n_hyp,
+                                  int32_t *node_offsets, int32_t *parent, int32_t *token, int32_t *end_node);
 /* Prediction net over every prefix + enc_proj + lattice + walk on the model's stream, for n_hyp token strings over n_clips clips:
  * hypothesis h reads the frames of clip clip_of[h], so several transcripts of one clip share its rows and enc_proj runs once per clip.
  * enc [n_clips][T][hidden] resp. packed with n_frames[n_clips]; ids packed with id_offsets[n_hyp + 1]; total / ok [n_hyp].

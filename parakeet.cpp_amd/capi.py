@@ -286,6 +286,8 @@ _LATE_SIGNATURES = {
     "pk_tdt_align_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, f32p],
     "pk_diag_mem_info": [C.c_void_p, C.POINTER(C.c_uint64)],
     "pk_tdt_total": [f32p, f32p, f32p, i32p, C.c_int, i32p, C.c_int, i32p, f32p, i32p],
+    "pk_tdt_total_tree": [f32p, f32p, f32p, i32p, C.c_int, i32p, C.c_int, i32p, i32p, i32p, i32p, C.c_int, f32p, i32p],
+    "pk_diag_tdt_prefix_tree": [i32p, i32p, i32p, C.c_int, C.c_int, i32p, i32p, i32p, i32p],
     "pk_tdt_total_decode": [C.c_void_p, f32p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_int, f32p, i32p],
     "pk_tdt_total_decode_ragged": [C.c_void_p, f32p, i32p, C.c_int, i32p, i32p, i32p, C.c_int, f32p, i32p],
     "pk_tdt_total_decode_timed": [C.c_void_p, f32p, i32p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_int, C.c_int, f32p],
@@ -352,6 +354,8 @@ _LATE_SIGNATURES = {
                                             C.POINTER(C.c_int)],
     "pk_model_set_tdt_lattice_bf16": [C.c_void_p, C.c_int],
     "pk_model_get_tdt_lattice_bf16": [C.c_void_p, C.POINTER(C.c_int)],
+    "pk_model_set_tdt_total_shared": [C.c_void_p, C.c_int],
+    "pk_model_get_tdt_total_shared": [C.c_void_p, C.POINTER(C.c_int)],
     "pk_diag_tdt_lattice_bf16": [f32p, f32p, f32p, f32p, i32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p],
     "pk_resample_length": [C.c_int64, C.c_int, C.c_int],
     "pk_resample_run": [C.c_int, C.c_int],
@@ -678,6 +682,39 @@ def tdt_total(lattices, durations):
     tt = np.zeros(len(T), np.float32); ok = np.zeros(len(T), np.int32)
     check(lib().pk_tdt_total(_f(lab), _f(blk), _f(dl), _i(dur), len(dur), _i(T), len(T), _i(off), _f(tt), _i(ok)))
     return [dict(total=tt[b], ok=int(ok[b])) for b in range(len(T))]
+
+
+def tdt_prefix_tree(ids, clip_of=None, n_clips=None):
+    """pk_diag_tdt_prefix_tree: ids = one token sequence per hypothesis, hypothesis h on clip clip_of[h] (None: h) -> node_offsets [n_clips + 1],
+    parent, token (packed clip after clip, clip-local), end_node [n_hyp].  Host arithmetic."""
+    n_hyp = len(ids)
+    n_clips = n_hyp if n_clips is None and clip_of is None else int(n_clips)
+    off = np.zeros(n_hyp + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in ids])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32).ravel() for x in ids] + [np.zeros(1, np.int32)]), np.int32)
+    cl = None if clip_of is None else np.ascontiguousarray(clip_of, np.int32)
+    cap = n_clips + int(off[-1])
+    no = np.zeros(n_clips + 1, np.int32); par = np.zeros(cap, np.int32); tok = np.zeros(cap, np.int32); en = np.zeros(max(n_hyp, 1), np.int32)
+    check(lib().pk_diag_tdt_prefix_tree(_i(flat), _i(off), None if cl is None else _i(cl), n_clips, n_hyp, _i(no), _i(par), _i(tok), _i(en)))
+    return no, par[:no[-1]].copy(), tok[:no[-1]].copy(), en[:n_hyp].copy()
+
+
+def tdt_total_tree(lattices, parents, end_node, durations, clip_of=None):
+    """pk_tdt_total_tree: lattices = one (lab [T][n - 1], blk [T][n], dl [T][n][D]) per clip over the clip's tree parents[c] [n] (parent[0] = -1);
+    hypothesis h ends at node end_node[h] of clip clip_of[h] (None: h) -> (total [n_hyp], ok [n_hyp]).  Needs a device, no model."""
+    T = np.asarray([x[1].shape[0] for x in lattices], np.int32)
+    no = np.zeros(len(lattices) + 1, np.int32)
+    no[1:] = np.cumsum([len(p) for p in parents])
+    cat = lambda k: _c(np.concatenate([_c(x[k]).ravel() for x in lattices] + [np.zeros(1, np.float32)]))
+    lab, blk, dl = cat(0), cat(1), cat(2)
+    par = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in parents]), np.int32)
+    en = np.ascontiguousarray(end_node, np.int32)
+    cl = None if clip_of is None else np.ascontiguousarray(clip_of, np.int32)
+    dur = np.ascontiguousarray(durations, np.int32)
+    tt = np.zeros(len(en), np.float32); ok = np.zeros(len(en), np.int32)
+    check(lib().pk_tdt_total_tree(_f(lab), _f(blk), _f(dl), _i(dur), len(dur), _i(T), len(T), _i(no), _i(par), _i(en), None if cl is None else _i(cl),
+                                  len(en), _f(tt), _i(ok)))
+    return tt, ok
 
 
 # ---- forced alignment and log-likelihood under the plain RNN-T head (include/parakeet_amd.h; DESIGN.md section 5.5.12) ------
@@ -2828,6 +2865,16 @@ class Model:
     def tdt_lattice_bf16(self):
         on = C.c_int(0)
         check(lib().pk_model_get_tdt_lattice_bf16(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_tdt_total_shared(self, on=True):
+        """pk_model_set_tdt_total_shared: tdt_total_decode, tdt_total_decode_timed, score_tdt and the rescored n-best score the transcripts of a clip
+        on one prefix tree per clip (bit for bit the unshared totals; fp32 models with a TDT joint only)."""
+        check(lib().pk_model_set_tdt_total_shared(self._h, int(bool(on))))
+
+    def tdt_total_shared(self):
+        on = C.c_int(0)
+        check(lib().pk_model_get_tdt_total_shared(self._h, C.byref(on)))
         return bool(on.value)
 
     def set_input_rate(self, rate):

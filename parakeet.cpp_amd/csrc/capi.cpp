@@ -145,6 +145,14 @@ pk_status pk_model_get_tdt_lattice_bf16(const pk_model *m, int *on) {
     return guard([&] { need(m && on, "model/on"); *on = m->m->tdt_lattice_bf16 ? 1 : 0; });
 }
 
+pk_status pk_model_set_tdt_total_shared(pk_model *m, int on) {
+    return guard([&] { need(m, "model"); m->m->set_tdt_total_shared(on != 0); });
+}
+
+pk_status pk_model_get_tdt_total_shared(const pk_model *m, int *on) {
+    return guard([&] { need(m && on, "model/on"); *on = m->m->tdt_total_shared ? 1 : 0; });
+}
+
 pk_status pk_model_config(const pk_model *m, pk_config *out) {
     return guard([&] { need(m && out, "model/out"); *out = m->m->cfg; });
 }

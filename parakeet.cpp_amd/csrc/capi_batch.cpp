@@ -1071,7 +1071,7 @@ static void nbest_pcm(Model &m, const float *pcm, const int64_t *offsets, int n_
                 hids.push_back(0);                              // (never read: keeps data() valid when every hypothesis is empty)
                 // the total's limits (1535 tokens, the scratch cap) depend on the search's output: this is the earliest they can be checked (header)
                 align_check_args(hids.data(), hoff.data(), nh_all, m.cfg.vocab_size, m.cfg.blank_id);
-                tdt_total_plan_call(m, m.ttotal, r.T.data(), nc, 0, hoff.data(), hclip.data(), nh_all);
+                tdt_total_plan_call(m, m.ttotal, r.T.data(), nc, 0, hids.data(), hoff.data(), hclip.data(), nh_all);
                 m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
                 run_tdt_total_call(m, m.ttotal, m.ws.ep.as<float>(), hids.data(), hoff.data());
                 PK_CHECK_LAUNCH();
@@ -1219,7 +1219,7 @@ static void score_pcm(Model &m, bool rnnt, const float *pcm, const int64_t *offs
     }, [&](const RagBatch &rb, int nc) {
         nfr.assign(rb.T.begin(), rb.T.begin() + nc);                   // (the plan refuses before the batch is encoded)
         if (rnnt) rnnt_plan_call(m, m.rnnt, nfr.data(), nc, 0, boff.data(), bclip.data(), (int)bhyp.size(), /*align=*/false);
-        else tdt_total_plan_call(m, m.ttotal, nfr.data(), nc, 0, boff.data(), bclip.data(), (int)bhyp.size());
+        else tdt_total_plan_call(m, m.ttotal, nfr.data(), nc, 0, bids.data(), boff.data(), bclip.data(), (int)bhyp.size());
     }, [&](const int *, int, const RagBatch &r) {
         m.run_enc_proj(m.ws.x.as<float>(), r.sum_T, m.ws.ep.as<float>(), m.stream);
         if (rnnt) run_rnnt_call(m, m.rnnt, m.ws.ep.as<float>(), bids.data(), boff.data());

@@ -913,7 +913,7 @@ static void tdt_total_checks(Model &m, const int32_t *n_frames, int n_clips, int
     align_check_args(ids, id_offsets, n_hyp, m.cfg.vocab_size, m.cfg.blank_id);
     if (n_frames) for (int b = 0; b < n_clips; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
     m.require_gpu();
-    tdt_total_plan_call(m, m.ttotal, n_frames, n_clips, T, id_offsets, clip_of, n_hyp);
+    tdt_total_plan_call(m, m.ttotal, n_frames, n_clips, T, ids, id_offsets, clip_of, n_hyp);
 }
 
 // uploads enc, runs enc_proj ONCE over the clips' rows, then the planned groups
@@ -950,6 +950,76 @@ pk_status pk_tdt_total(const float *lab, const float *blk, const float *dl, cons
         PK_HIP(hipMemcpyAsync(total, ws.out.p, (size_t)B * 4, hipMemcpyDeviceToHost, nullptr));
         PK_HIP(hipMemcpyAsync(ok, ws.out.as<int>() + B, (size_t)B * 4, hipMemcpyDeviceToHost, nullptr));
         PK_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
+// the walk of kernels/tdt_tree.hip alone on a HOST tree lattice: one group of every clip, no model
+pk_status pk_tdt_total_tree(const float *lab, const float *blk, const float *dl, const int32_t *durations, int D, const int32_t *n_frames, int n_clips,
+                            const int32_t *node_offsets, const int32_t *parent, const int32_t *end_node, const int32_t *clip_of, int n_hyp, float *total,
+                            int32_t *ok) {
+    return guard([&] {
+        need(n_clips >= 1 && n_hyp >= 1 && n_frames && durations && node_offsets && parent && end_node, "n_clips/n_hyp/n_frames/durations/node_offsets/parent/end_node");
+        need(blk && dl && total && ok, "blk/dl/total/ok");
+        need(clip_of || n_hyp == n_clips, "clip_of == NULL needs n_hyp == n_clips");
+        need(node_offsets[0] == 0, "node_offsets[0] must be 0");
+        for (int c = 0; c < n_clips; ++c) {
+            need(n_frames[c] > 0, "n_frames[c] must be positive");
+            const int n = node_offsets[c + 1] - node_offsets[c];
+            need(n >= 1, "every clip has at least its root node");
+            need(parent[node_offsets[c]] == -1, "parent[0] of a clip must be -1");
+            for (int k = 1; k < n; ++k) need(parent[node_offsets[c] + k] >= 0 && parent[node_offsets[c] + k] < k, "parent[k] outside [0, k)");
+        }
+        need(node_offsets[n_clips] == n_clips || lab, "lab");
+        TdtTreeWs ws;
+        ws.hc_off.assign(n_clips + 1, 0); ws.hc_list.resize(n_hyp);
+        for (int h = 0; h < n_hyp; ++h) {
+            const int c = clip_of ? clip_of[h] : h;
+            need(c >= 0 && c < n_clips, "clip_of[h] outside [0, n_clips)");
+            need(end_node[h] >= 0 && end_node[h] < node_offsets[c + 1] - node_offsets[c], "end_node[h] outside its clip's tree");
+            ++ws.hc_off[c + 1];
+        }
+        for (int c = 0; c < n_clips; ++c) ws.hc_off[c + 1] += ws.hc_off[c];
+        std::vector<int32_t> fill(ws.hc_off.begin(), ws.hc_off.end() - 1), all(n_clips);
+        for (int h = 0; h < n_hyp; ++h) ws.hc_list[fill[clip_of ? clip_of[h] : h]++] = h;
+        for (int c = 0; c < n_clips; ++c) all[c] = c;
+        ws.pt.node_off.assign(node_offsets, node_offsets + n_clips + 1);
+        ws.pt.parent.assign(parent, parent + node_offsets[n_clips]);
+        ws.pt.end_node.assign(end_node, end_node + n_hyp);
+        tdt_tree_stage(ws, all.data(), n_clips, n_frames, nullptr, ws.pt, ws.hc_off.data(), ws.hc_list.data(), durations, D, 0, 0, 0);   // (host only: refuses first)
+        need_device();
+        tdt_tree_upload(ws, nullptr);
+        if (ws.labs) PK_HIP(hipMemcpyAsync(ws.lab.p, lab, (size_t)ws.labs * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.blk.p, blk, (size_t)ws.cells * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.dl.p, dl, (size_t)ws.cells * D * 4, hipMemcpyHostToDevice, nullptr));
+        run_tdt_tree_dp(ws, nullptr);
+        PK_CHECK_LAUNCH();
+        std::vector<float> gt(n_hyp);
+        std::vector<int32_t> gk(n_hyp);
+        PK_HIP(hipMemcpyAsync(gt.data(), ws.out.p, (size_t)n_hyp * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(gk.data(), ws.out.as<int>() + n_hyp, (size_t)n_hyp * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipStreamSynchronize(nullptr));
+        for (int i = 0; i < n_hyp; ++i) { total[ws.slot_hyp[i]] = gt[i]; ok[ws.slot_hyp[i]] = gk[i]; }
+    });
+}
+
+pk_status pk_diag_tdt_prefix_tree(const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of, int n_clips, int n_hyp, int32_t *node_offsets,
+                                  int32_t *parent, int32_t *token, int32_t *end_node) {
+    return guard([&] {
+        need(id_offsets && node_offsets && parent && token && n_clips >= 1 && n_hyp >= 0, "id_offsets/node_offsets/parent/token/n_clips/n_hyp");
+        need(n_hyp == 0 || end_node, "end_node");
+        need(clip_of || n_hyp == n_clips || n_hyp == 0, "clip_of == NULL needs n_hyp == n_clips");
+        need(id_offsets[0] == 0, "id_offsets[0] must be 0");
+        for (int h = 0; h < n_hyp; ++h) {
+            need(id_offsets[h + 1] >= id_offsets[h], "id_offsets decrease");
+            if (clip_of) need(clip_of[h] >= 0 && clip_of[h] < n_clips, "clip_of[h] outside [0, n_clips)");
+        }
+        need(id_offsets[n_hyp] == 0 || ids, "ids");
+        TdtPrefixTree t;
+        tdt_prefix_tree_build(t, ids, id_offsets, clip_of, n_clips, n_hyp);
+        std::copy(t.node_off.begin(), t.node_off.end(), node_offsets);
+        std::copy(t.parent.begin(), t.parent.end(), parent);
+        std::copy(t.token.begin(), t.token.end(), token);
+        std::copy(t.end_node.begin(), t.end_node.end(), end_node);
     });
 }
 

@@ -533,6 +533,14 @@ void Model::set_tdt_lattice_bf16(bool on) {
     tdt_lattice_bf16 = on;
 }
 
+void Model::set_tdt_total_shared(bool on) {
+    if (on && (cfg.vocab_size <= 0 || cfg.rnnt_head || cfg.num_durations <= 0))
+        fail(PK_ERR_UNSUPPORTED, "the prefix-tree TDT total needs a TDT joint (label + duration heads)");
+    if (on && cfg.gemm_bf16)
+        fail(PK_ERR_UNSUPPORTED, "the prefix-tree TDT total is fp32: the bf16 lattice kernel of a gemm_bf16 model keeps its per-hypothesis layout");
+    tdt_total_shared = on;
+}
+
 // ---- workspace ----------------------------------------------------------------------------------------------
 static inline int sub_len(int n) { return (n - 1) / 2 + 1; }        // one stride-2 stage of the subsampling (src/encoder.cpp:208-217)
 

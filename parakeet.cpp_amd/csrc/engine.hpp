@@ -280,6 +280,12 @@ class Model {
     void set_tdt_lattice_bf16(bool on);
     DevBuf wld_tl16_;
 
+    // The prefix-tree path of the TDT total (pk_model_set_tdt_total_shared; kernels/tdt_tree.hip), off by default: fp32 models with a
+    // TDT joint only.  On, tdt_total_plan_call / run_tdt_total_call score the transcripts of a clip on one prefix tree per clip; every total and ok
+    // word equals the unshared path's bit for bit.  Not to be changed while a batch is in flight.
+    bool tdt_total_shared = false;
+    void set_tdt_total_shared(bool on);
+
     ProfileSink *prof = nullptr;
     void klaunch_begin(const char *name, double flops, double bytes, hipStream_t s);
     void klaunch_end(hipStream_t s);

@@ -650,6 +650,38 @@ struct TdtTotalArgs {
 };
 void launch_tdt_total(const TdtTotalArgs &a, hipStream_t s);
 
+// The same totals on ONE prefix tree per clip (kernels/tdt_tree.hip): a lattice column is a tree node (clip, ids[:u]).
+// Clip c owns nodes [node_off[c], node_off[c + 1]) (n_c of them, node 0 the empty prefix, parent < node); row cell_off[c] + t n_c + k of blk, times D
+// of dl; lab_off[c] + t (n_c - 1) + k - 1 of lab holds the log-prob of token[k] at the cell of parent[k].  Every per-node table is indexed
+// node_off[c] + k and holds clip-local node numbers.
+constexpr int kTdtTreeMaxNodes = kTdtAlignMaxTokens + 1;   // n_c <= this: the chain walk's U + 1 limit
+struct TdtTree {
+    int C, D;
+    int durations[8];
+    const int *T, *node_off, *row0;             // [C] frames, [C + 1], [C] first enc_proj row (the model path only)
+    const int64_t *cell_off, *lab_off;          // [C + 1]
+    const int *parent;                          // -1 at node 0
+    const int *token, *ppos;                    // the model path only: the token on the edge into the node; the node's row of the prediction net's output
+    const int *child_off, *child;               // CSR of every node's children: child_off[nodes + 1], children of node g at child[child_off[g] ..)
+    const int *s_node, *s_parent, *s_depth;     // the clip's nodes in depth order (stable): entry node_off[c] + e
+    const int *dstart;                          // first depth-ordered entry of every depth: clip c from dstart[node_off[c] + c], depth_max + 2 values
+    float *lab, *blk, *dl;
+};
+struct TdtTreeTotalArgs {
+    TdtTree tr;
+    const int *hyp_off, *hyp_end;               // hypotheses grouped by clip: [C + 1], and the clip-local end node of each
+    float *total; int *ok;                      // in that order: ok = total > -inf
+    int n_max, dur_max;                         // over the launch: the dynamic LDS is tdt_tree_total_lds_bytes(n_max, dur_max)
+};
+size_t tdt_tree_total_lds_bytes(int n_max, int dur_max);
+void launch_tdt_tree_total(const TdtTreeTotalArgs &a, hipStream_t s);
+// rows [row0, row0 + n) of the tree lattice: z[i][J] = relu(ep[tr.row0[c] + t][J] + pp[tr.ppos[node]][J]) ...
+void launch_tdt_tree_act(const TdtTree &tr, const float *ep, const float *pp, int J, int64_t row0, int n, float *z, hipStream_t s);
+// ... and the same rows of the heads product's output taken to blk, dl[D] and one lab value per child of the node
+void launch_tdt_tree_keep(const TdtTree &tr, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s);
+// one depth step of the prediction net over the tree: row j < n of hd / cd [L][stride / Hp][Hp] = row pslot[j] of hs / cs (pslot[j] < 0: zeros)
+void launch_tdt_tree_gather(const int *pslot, int n, int L, int Hp, int64_t stride, const float *hs, const float *cs, float *hd, float *cd, hipStream_t s);
+
 // Forced alignment and forward-algorithm total of GIVEN token strings under the plain RNN-T head (kernels/rnnt_lattice.hip).
 // The lattice is packed as the TDT one with D = 0 (no dl): blank arc (t, u) -> (t + 1, u), label arc (t, u) -> (t, u + 1).
 constexpr int kRnntMaxTokens = 1023;            // U <= this: one thread per column, at most 16 waves per workgroup

@@ -53,8 +53,9 @@ void run_tdt_total_dp(TdtAlignWs &ws, hipStream_t s) {
     launch_tdt_total(a, s);
 }
 
-void tdt_total_plan_call(Model &m, TdtTotalWs &ws, const int32_t *n_frames, int n_clips, int T, const int32_t *id_offsets,
+void tdt_total_plan_call(Model &m, TdtTotalWs &ws, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets,
                          const int32_t *clip_of, int n_hyp) {
+    if (m.tdt_total_shared) { tdt_tree_plan_call(m, ws.tree, n_frames, n_clips, T, ids, id_offsets, clip_of, n_hyp); return; }
     std::vector<int32_t> row0(n_clips);
     int64_t rows = 0;
     for (int c = 0; c < n_clips; ++c) { row0[c] = (int32_t)rows; rows += n_frames ? n_frames[c] : T; }
@@ -68,6 +69,7 @@ void tdt_total_plan_call(Model &m, TdtTotalWs &ws, const int32_t *n_frames, int 
 }
 
 void run_tdt_total_call(Model &m, TdtTotalWs &ws, const float *d_ep, const int32_t *ids, const int32_t *id_offsets, hipEvent_t *ev, float *ms) {
+    if (m.tdt_total_shared) { run_tdt_tree_call(m, ws.tree, d_ep, ws.total, ws.ok, ev, ms); return; }
     const pk_config &c = m.cfg;
     const int n_hyp = (int)ws.T_of.size();
     ws.total.assign(n_hyp, 0.0f); ws.ok.assign(n_hyp, 0);
@@ -103,7 +105,7 @@ void run_tdt_total_call(Model &m, TdtTotalWs &ws, const float *d_ep, const int32
 }
 
 size_t tdt_total_bytes(const TdtTotalWs &ws) {
-    size_t n = tdt_align_bytes(ws.a);
+    size_t n = tdt_align_bytes(ws.a) + tdt_tree_bytes(ws.tree);
     for (const DevBuf *b : {&ws.h, &ws.hn, &ws.c, &ws.cn}) n += b->cap;
     return n;
 }

@@ -2,6 +2,7 @@
 // rescoring on top of it (kernels/tdt_total.hip).
 #pragma once
 #include "tdt_align.hpp"
+#include "tdt_tree.hpp"
 
 namespace pk {
 
@@ -25,6 +26,7 @@ struct TdtTotalWs {
     std::vector<int32_t> T_of, row0_of, off, gstart;   // of the call: frames and first enc_proj row of every hypothesis, group-local offsets, group starts
     std::vector<float> total;                       // results of the call, gathered group by group
     std::vector<int32_t> ok;
+    TdtTreeWs tree;                                 // the call's plan and scratch on the prefix-tree path (Model::tdt_total_shared; tdt_tree.hpp)
 };
 
 // scratch bytes of n hypotheses with these sums (V = 0: a host lattice)
@@ -37,8 +39,9 @@ void tdt_total_groups(std::vector<int32_t> &gstart, const int32_t *T_of, const i
 // (upload first: tdt_lattice_upload of tdt_align.hpp with token_results = false -- no back-pointers, no token arrays)
 void run_tdt_total_dp(TdtAlignWs &ws, hipStream_t s);
 // Plans a call of the model entry points (host only, refuses before anything is allocated): n_hyp hypotheses, hypothesis h on the frames of clip
-// clip_of[h] (nullptr: h, and n_hyp must equal n_clips); n_frames[n_clips] (nullptr: T each).
-void tdt_total_plan_call(Model &m, TdtTotalWs &ws, const int32_t *n_frames, int n_clips, int T, const int32_t *id_offsets,
+// clip_of[h] (nullptr: h, and n_hyp must equal n_clips); n_frames[n_clips] (nullptr: T each).  With Model::tdt_total_shared on, the plan is the
+// prefix-tree path's (tdt_tree_plan_call, which reads ids) and run_tdt_total_call runs that path; ws.total / ws.ok are filled either way.
+void tdt_total_plan_call(Model &m, TdtTotalWs &ws, const int32_t *n_frames, int n_clips, int T, const int32_t *ids, const int32_t *id_offsets,
                          const int32_t *clip_of, int n_hyp);
 // Queues the planned call on the model's stream: d_ep = enc_proj of the call's packed frames.  Group by group: prediction net, lattice, walk, results
 // to ws.total / ws.ok (synchronises once per group).  ev (optional, 4 events per group, recorded around the three stages), ms[3] accumulates them.

@@ -7,7 +7,10 @@ weights and audio, the encoder's own output), beam width W = 8, N in {1, 4, 8} h
   not compute twice.
 Next to them, on the same batch in the same run, pk_tdt_align_decode_timed of the best hypothesis of every clip (one string per clip: the parent
 feature's figures for scale).  Writes profiles/tdt_rescore.md with --write.
-usage: python tools/bench_tdt_rescore.py [--reps 3] [--write]"""
+--shared: instead, the three stages of pk_tdt_total_decode_timed with pk_model_set_tdt_total_shared off and on (kernels/tdt_tree.hip, DESIGN.md
+section 5.5.3a), interleaved off / on / off / on ... in this one process on the same hypotheses, the totals compared bit for bit, and the share of
+lattice columns the prefix trees save.  Writes profiles/tdt_rescore_shared.md with --write (its bench.py section is kept).
+usage: python tools/bench_tdt_rescore.py [--reps 3] [--write] [--shared [--rounds 3]]"""
 import argparse
 import json
 import os
@@ -43,10 +46,58 @@ def shared_share(hyps_of_clip):
     return cols, shared / max(cols, 1)
 
 
+def shared_rounds(gm, capi, enc, ids, clip_of, n_clips, reps, rounds):
+    """-> dict: per-stage medians over the rounds of (off, on) run alternately, every round's pair, and the columns the trees save."""
+    off = gm.tdt_total_decode(enc, ids, clip_of)
+    gm.set_tdt_total_shared(True)
+    on = gm.tdt_total_decode(enc, ids, clip_of)
+    same = all(np.float32(x["total"]).view(np.uint32) == np.float32(y["total"]).view(np.uint32) and x["ok"] == y["ok"] for x, y in zip(off, on))
+    pairs = []
+    for _ in range(rounds):
+        gm.set_tdt_total_shared(False)
+        t_off = gm.tdt_total_decode_timed(enc, ids, clip_of, reps=reps)
+        gm.set_tdt_total_shared(True)
+        t_on = gm.tdt_total_decode_timed(enc, ids, clip_of, reps=reps)
+        pairs.append([[round(float(v), 3) for v in t_off], [round(float(v), 3) for v in t_on]])
+    gm.set_tdt_total_shared(False)
+    cols = sum(len(i) + 1 for i in ids)
+    nodes = int(capi.tdt_prefix_tree(ids, clip_of, n_clips)[0][-1])
+    med = lambda k, s: round(float(np.median([p[k][s] for p in pairs])), 3)
+    out = {"bit_identical": bool(same), "lattice_columns": cols, "tree_columns": nodes, "saved_column_share": round(1.0 - nodes / max(cols, 1), 4), "rounds": pairs}
+    for s, name in enumerate(("pred_net", "lattice", "forward")):
+        out[name + "_ms_off"], out[name + "_ms_on"] = med(0, s), med(1, s)
+    out["total_ms_off"] = round(sum(out[k + "_ms_off"] for k in ("pred_net", "lattice", "forward")), 3)
+    out["total_ms_on"] = round(sum(out[k + "_ms_on"] for k in ("pred_net", "lattice", "forward")), 3)
+    return out
+
+
+SHARED_MARK = "## bench.py headline"
+
+
+def write_shared(lines, reps, rounds):
+    path = os.path.join(ROOT, "profiles", "tdt_rescore_shared.md")
+    keep = ""
+    if os.path.exists(path):
+        txt = open(path).read()
+        keep = txt[txt.index(SHARED_MARK):] if SHARED_MARK in txt else ""
+    keys = ["n_best", "hypotheses", "tokens_per_hypothesis", "lattice_columns", "tree_columns", "saved_column_share", "pred_net_ms_off", "pred_net_ms_on",
+            "lattice_ms_off", "lattice_ms_on", "forward_ms_off", "forward_ms_on", "total_ms_off", "total_ms_on", "bit_identical"]
+    with open(path, "w") as f:
+        f.write("# TDT rescoring on one prefix tree per clip: the switch off and on, one MI355X\n\n`python tools/bench_tdt_rescore.py --shared --reps %d "
+                "--rounds %d --write` (tdt-ctc-110m shapes, 64 x 10 s, W = 8, synthetic weights and audio).  Every figure is the median over the rounds of "
+                "`pk_tdt_total_decode_timed`'s HIP-event medians; off and on alternate inside one process on the same hypotheses.\n\n" % (reps, rounds))
+        f.write("| " + " | ".join(keys) + " |\n|" + "---|" * len(keys) + "\n")
+        for o in lines:
+            f.write("| " + " | ".join(str(o.get(k, "-")) for k in keys) + " |\n")
+        f.write("\n```\n" + "\n".join(json.dumps(o) for o in lines) + "\n```\n\n" + keep)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--write", action="store_true")
+    ap.add_argument("--shared", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     import pkload
     pk = pkload.load()
@@ -67,6 +118,13 @@ def main():
             hyps_of_clip = [[b["ids"][c, j, :min(int(b["lens"][c, j]), 1535)] for j in range(N) if b["score"][c, j] > -np.inf] for c in range(n)]
             ids = [h for hy in hyps_of_clip for h in hy]
             clip_of = [c for c, hy in enumerate(hyps_of_clip) for _ in hy]
+            if a.shared:
+                out = {"metric": "tdt rescoring, prefix tree off / on, ms", "config": "tdt-ctc-110m", "batch": "64 x 10 s", "frames": T, "beam_width": W,
+                       "n_best": N, "hypotheses": len(ids), "tokens_per_hypothesis": round(float(np.mean([len(i) for i in ids])), 1), "reps": a.reps}
+                out.update(shared_rounds(gm, capi, enc, ids, clip_of, n, a.reps, a.rounds))
+                lines.append(out)
+                print(json.dumps(out), flush=True)
+                continue
             r = gm.tdt_total_decode(enc, ids, clip_of)                                # warm-up of the buffers
             pred, lat, fwd = gm.tdt_total_decode_timed(enc, ids, clip_of, reps=a.reps)
             groups = capi.tdt_total_groups([T] * len(ids), [len(i) for i in ids], list(cfg.durations), V, J)[1]
@@ -83,7 +141,9 @@ def main():
             lines.append(out)
             print(json.dumps(out), flush=True)
         gm.close()
-    if a.write:
+    if a.write and a.shared:
+        write_shared(lines, a.reps, a.rounds)
+    elif a.write:
         with open(os.path.join(ROOT, "profiles", "tdt_rescore.md"), "w") as f:
             f.write("# CTC n-best rescored by the TDT head: stage times on one MI355X\n\n`python tools/bench_tdt_rescore.py --reps %d --write` (synthetic weights "
                     "and audio; HIP-event medians).\n\n" % a.reps)
