@@ -161,6 +161,18 @@ pk_status pk_model_get_local_attention_bf16(const pk_model *m, int *on);
  * beam, streaming, pk_group and pk_transcribe_pcm_nbest_rescored keep refusing a gemm_bf16 model.  Not to be changed while a batch is in flight. */
 pk_status pk_model_set_tdt_lattice_bf16(pk_model *m, int on);
 pk_status pk_model_get_tdt_lattice_bf16(const pk_model *m, int *on);
+/* bf16 TDT keyword spotting (opt-in, gemm_bf16 models with a TDT joint whose joint_hidden is a multiple of 32 and at most 1152; any other model:
+ * PK_ERR_UNSUPPORTED).  on != 0: pk_tdt_kws_decode(_ragged), pk_tdt_kws_decode_timed, pk_tdt_spot_pcm and pk_diag_tdt_kws_lattice (whose chunk_rows
+ * is then ignored) accept this model instead of refusing it as gemm_bf16, and the arcs the walk reads come from ONE launch of
+ * kernels/tdt_kws_bf16.hip: z = bf16(relu(enc_proj + pred_proj)) against the bf16 copy of the heads weights on the MFMA,
+ * fp32 accumulation and bias, then logit - row maximum directly -- no log-softmax, no activation, logits or top buffer, no normalisation pass.  The
+ * prediction net runs on its fp32 weights; the walk and the picking are unchanged and exact on the arcs they get.  pk_diag_tdt_kws_lattice then
+ * returns the normalised arcs with top = 0.  Independent of pk_model_set_tdt_lattice_bf16 (neither opens the other's entry points; they share the
+ * packed weight copy, made by whichever is switched on first).  Results are in the tolerance class of the gemm_bf16 mode
+ * (tests/test_gpu_tdt_kws_bf16.py).  on = 0 (the default): every path, bit and refusal of a model that never set it.  Streaming spotting, the TDT
+ * beam, the RNN-T head and pk_group keep refusing a gemm_bf16 model.  Not to be changed while a batch is in flight. */
+pk_status pk_model_set_tdt_kws_bf16(pk_model *m, int on);
+pk_status pk_model_get_tdt_kws_bf16(const pk_model *m, int *on);
 /* Prefix-shared TDT total (opt-in, fp32 models with a TDT joint; a gemm_bf16 model or one without a TDT joint: PK_ERR_UNSUPPORTED).  on != 0:
  * pk_tdt_total_decode(_ragged), pk_tdt_total_decode_timed, pk_tdt_score_pcm and pk_transcribe_pcm_nbest_rescored score the transcripts of a clip on
  * ONE prefix tree per clip (kernels/tdt_tree.hip): a lattice column is (clip, ids[:u]), computed once however many
@@ -830,6 +842,18 @@ pk_status pk_tdt_spot_pcm(pk_model *m, const float *pcm, const int64_t *offsets,
  * of >= 1 tokens; the guard words and chunk_rows as there), plus top: cells + PK_DIAG_TDT_LATTICE_GUARD floats.  The call must fit one group. */
 pk_status pk_diag_tdt_kws_lattice(pk_model *m, const float *enc, const int32_t *n_frames, int B, const int32_t *ids, const int32_t *id_offsets,
                                   int chunk_rows, float *lab, float *blk, float *dl, float *top);
+/* Diagnostic: the bf16 spotting lattice kernel (kernels/tdt_kws_bf16.hip; pk_model_set_tdt_kws_bf16) alone on operands from the host, no model.
+ * Pair p spots the keyword ids[id_offsets[p] .. id_offsets[p + 1]) (1 .. 64 tokens) on the n_frames[p] frames whose enc_proj rows start at row
+ * ep_row0[p] of ep [max_p (ep_row0[p] + n_frames[p])][J] (pairs on one clip share rows), with the prediction net's rows of slot net_of[p]:
+ * pp [(L_max + 1) n_net][J], row u n_net + k = slot k after u tokens.  wld [V + D][J] / bld [V + D] = the label rows then the duration rows of the
+ * heads, fp32; the weight is rounded to bf16 and packed as the engine packs it.  The ONE launch fills the NORMALISED arcs, packed as pk_tdt_kws takes
+ * its lattice: lab = logit[ids[u]] - M, blk = logit[blank] - M, dl[i] = logit[V + i] - Md (M / Md the row's largest label / duration logit), every
+ * value <= +0.0, returned with the guard words of pk_diag_tdt_lattice.  Every refusal comes before a device is looked for.
+ * PK_ERR_INVALID: D outside [1, 8], blank or an id outside [0, V), an empty keyword, bad tables.  PK_ERR_UNSUPPORTED: a keyword of more than 64
+ * tokens, J no multiple of 32 or above 1152. */
+pk_status pk_diag_tdt_kws_lattice_bf16(const float *ep, const float *pp, const float *wld, const float *bld, const int32_t *ids, const int32_t *id_offsets,
+                                       const int32_t *n_frames, const int32_t *ep_row0, const int32_t *net_of, int n_pairs, int n_net, int V, int D, int J,
+                                       int blank, float *lab, float *blk, float *dl);
 
 /* ---- one node, several GPUs: utterance shards (the reference has no multi-device path, README.md:513) ----------
  * A pk_group is one model REPLICA per device of this process: the safetensors file is mapped once and every replica is built from that

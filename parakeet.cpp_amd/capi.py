@@ -354,6 +354,10 @@ _LATE_SIGNATURES = {
                                             C.POINTER(C.c_int)],
     "pk_model_set_tdt_lattice_bf16": [C.c_void_p, C.c_int],
     "pk_model_get_tdt_lattice_bf16": [C.c_void_p, C.POINTER(C.c_int)],
+    "pk_model_set_tdt_kws_bf16": [C.c_void_p, C.c_int],
+    "pk_model_get_tdt_kws_bf16": [C.c_void_p, C.POINTER(C.c_int)],
+    "pk_diag_tdt_kws_lattice_bf16": [f32p, f32p, f32p, f32p, i32p, i32p, i32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     f32p, f32p, f32p],
     "pk_model_set_tdt_total_shared": [C.c_void_p, C.c_int],
     "pk_model_get_tdt_total_shared": [C.c_void_p, C.POINTER(C.c_int)],
     "pk_diag_tdt_lattice_bf16": [f32p, f32p, f32p, f32p, i32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p],
@@ -1945,6 +1949,25 @@ def tdt_lattice_bf16(ep, pp, wld, bld, ids, n_frames, V, D, blank):
     return lab, blk, dl
 
 
+def tdt_kws_lattice_bf16(ep, pp, wld, bld, ids, n_frames, ep_row0, net_of, n_net, V, D, blank):
+    """pk_diag_tdt_kws_lattice_bf16: the bf16 spotting lattice kernel alone, no model.  Pair p: keyword ids[p] on the n_frames[p] rows of ep [rows][J]
+    from ep_row0[p], prediction-net slot net_of[p] of pp [(L_max + 1) n_net][J] (row u n_net + k); wld [V + D][J], bld [V + D] -> the normalised arcs
+    (lab [labs + G], blk [cells + G], dl [cells D + G]) flat, G = TDT_LATTICE_GUARD words of the fill pattern 0x7FC5A5A5 behind each."""
+    ep, pp, wld, bld = _c(ep), _c(pp), _c(wld), _c(bld)
+    pid, off = _pack_ids(ids)
+    T, r0, net = (np.ascontiguousarray(x, np.int32) for x in (n_frames, ep_row0, net_of))
+    L = np.diff(off).astype(np.int64)
+    J = ep.shape[1] if ep.ndim == 2 else 0
+    assert wld.shape == (V + D, J) and bld.shape == (V + D,) and len(T) == len(r0) == len(net) == len(L)
+    assert ep.shape[0] >= int((r0 + T).max()) and pp.shape == ((int(L.max()) + 1) * n_net, J)
+    cells, labs = int((T * (L + 1)).sum()), int((T * L).sum())
+    G = TDT_LATTICE_GUARD
+    lab = np.zeros(labs + G, np.float32); blk = np.zeros(cells + G, np.float32); dl = np.zeros(cells * max(D, 0) + G, np.float32)
+    check(lib().pk_diag_tdt_kws_lattice_bf16(_f(ep), _f(pp), _f(wld), _f(bld), _i(pid), _i(off), _i(T), _i(r0), _i(net), len(T), int(n_net), int(V),
+                                             int(D), J, int(blank), _f(lab), _f(blk), _f(dl)))
+    return lab, blk, dl
+
+
 CONV_VARIANT_WORDS = 17                  # PK_DIAG_CONV_VARIANT_WORDS
 
 
@@ -2865,6 +2888,16 @@ class Model:
     def tdt_lattice_bf16(self):
         on = C.c_int(0)
         check(lib().pk_model_get_tdt_lattice_bf16(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_tdt_kws_bf16(self, on=True):
+        """pk_model_set_tdt_kws_bf16: TDT keyword spotting of a gemm_bf16 model through the one-launch bf16 spotting lattice kernel (tdt_kws_decode,
+        tdt_kws_decode_timed, spot_tdt, tdt_kws_lattice; off: they refuse a gemm_bf16 model).  Independent of set_tdt_lattice_bf16."""
+        check(lib().pk_model_set_tdt_kws_bf16(self._h, int(bool(on))))
+
+    def tdt_kws_bf16(self):
+        on = C.c_int(0)
+        check(lib().pk_model_get_tdt_kws_bf16(self._h, C.byref(on)))
         return bool(on.value)
 
     def set_tdt_total_shared(self, on=True):

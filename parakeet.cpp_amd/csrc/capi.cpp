@@ -145,6 +145,14 @@ pk_status pk_model_get_tdt_lattice_bf16(const pk_model *m, int *on) {
     return guard([&] { need(m && on, "model/on"); *on = m->m->tdt_lattice_bf16 ? 1 : 0; });
 }
 
+pk_status pk_model_set_tdt_kws_bf16(pk_model *m, int on) {
+    return guard([&] { need(m, "model"); m->m->set_tdt_kws_bf16(on != 0); });
+}
+
+pk_status pk_model_get_tdt_kws_bf16(const pk_model *m, int *on) {
+    return guard([&] { need(m && on, "model/on"); *on = m->m->tdt_kws_bf16 ? 1 : 0; });
+}
+
 pk_status pk_model_set_tdt_total_shared(pk_model *m, int on) {
     return guard([&] { need(m, "model"); m->m->set_tdt_total_shared(on != 0); });
 }

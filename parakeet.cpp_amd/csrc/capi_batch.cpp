@@ -1399,7 +1399,7 @@ static void spot_pcm(Model &m, bool tdt, const float *pcm, const int64_t *offset
     for_each_batch(m, pcm, offsets, n_clips, /*ctc=*/!tdt, every_batch, [&](const RagBatch &rb, int nc) {
         nfr.assign(rb.T.begin(), rb.T.begin() + nc);                                // (the plan refuses before the batch is encoded)
         if (tdt) tdt_kws_plan_call(m.tkws, m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden, nfr.data(), nc, 0, ids.data(), off.data(),
-                                   n_kw, nullptr, nullptr, nc * n_kw, o);
+                                   n_kw, nullptr, nullptr, nc * n_kw, o, m.tdt_kws_bf16);
         else kws_plan(m.kws, nfr.data(), nc, rb.T_max, off.data(), n_kw, o);
     }, [&](const int *clip, int nc, const RagBatch &r) {
         const int32_t *bnh, *bst, *ben;
@@ -1452,7 +1452,7 @@ pk_status pk_tdt_spot_pcm(pk_model *h, const float *pcm, const int64_t *offsets,
         need(h && pcm && offsets && n_hits && start_s && end_s && score && n_clips > 0, "model/pcm/offsets/n_hits/start_s/end_s/score/n_clips");
         need(phrases || (ids_in && kw_offsets_in), "phrases or ids/kw_offsets");
         Model &m = *h->m;
-        tdt_align_model_checks(m);
+        tdt_align_model_checks(m, /*lattice_bf16_ok=*/false, /*kws_bf16_ok=*/true);
         spot_pcm(m, true, pcm, offsets, n_clips, phrases, ids_in, kw_offsets_in, n_kw, opt, n_hits, start_s, end_s, score);
     });
 }

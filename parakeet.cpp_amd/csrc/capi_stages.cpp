@@ -1308,12 +1308,12 @@ pk_status pk_ctc_kws_decode_timed(pk_model *h, const float *enc, const int32_t *
 // the checks of the model entry points; -> after them the call is planned (host only) in m.tkws
 static void tdt_kws_checks(Model &m, const int32_t *n_frames, int B, int T, const int32_t *kw_ids, const int32_t *kw_offsets, int n_kw,
                            const pk_kws_options &o) {
-    tdt_align_model_checks(m);
+    tdt_align_model_checks(m, /*lattice_bf16_ok=*/false, /*kws_bf16_ok=*/true);
     kws_check_args(kw_ids, kw_offsets, n_kw, B, m.cfg.vocab_size, m.cfg.blank_id, o, "TDT keyword spotting");
     if (n_frames) for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
     m.require_gpu();
     tdt_kws_plan_call(m.tkws, m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden, n_frames, B, T, kw_ids, kw_offsets, n_kw, nullptr,
-                      nullptr, B * n_kw, o);
+                      nullptr, B * n_kw, o, m.tdt_kws_bf16);
 }
 
 // uploads enc, runs enc_proj ONCE over the clips' rows, then the planned groups
@@ -1421,7 +1421,7 @@ pk_status pk_diag_tdt_kws_lattice(pk_model *h, const float *enc, const int32_t *
     return guard([&] {
         need(h && enc && n_frames && lab && blk && dl && top && chunk_rows >= 0, "model/enc/n_frames/lab/blk/dl/top/chunk_rows");
         Model &m = *h->m;
-        tdt_align_model_checks(m);
+        tdt_align_model_checks(m, /*lattice_bf16_ok=*/false, /*kws_bf16_ok=*/true);
         const pk_kws_options o = kws_options_of(nullptr);
         kws_check_args(ids, id_offsets, B, B, m.cfg.vocab_size, m.cfg.blank_id, o, "TDT keyword spotting");
         for (int b = 0; b < B; ++b) need(n_frames[b] > 0, "n_frames[b] must be positive");
@@ -1430,7 +1430,7 @@ pk_status pk_diag_tdt_kws_lattice(pk_model *h, const float *enc, const int32_t *
         for (int b = 0; b < B; ++b) self[b] = b;
         TdtKwsWs &ws = m.tkws;
         tdt_kws_plan_call(ws, m.cfg.durations, m.cfg.num_durations, m.cfg.vocab_size, m.cfg.joint_hidden, n_frames, B, 0, ids, id_offsets, B, self.data(),
-                          self.data(), B, o);
+                          self.data(), B, o, m.tdt_kws_bf16);
         need(ws.gstart.size() == 2, "the call must fit one group");
         int64_t cells = 0, labs = 0;
         for (int b = 0; b < B; ++b) {
@@ -1444,6 +1444,8 @@ pk_status pk_diag_tdt_kws_lattice(pk_model *h, const float *enc, const int32_t *
         PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.a.blk.p, 0x7FC5A5A5, nb, m.stream));
         PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.a.dl.p, 0x7FC5A5A5, nd, m.stream));
         PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.top.p, 0x7FC5A5A5, nb, m.stream));
+        // (the bf16 lattice kernel writes normalised arcs and no top: the rows come back with top = 0, which tdt_kws_ref.normalise maps onto themselves)
+        if (ws.bf16) PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.top.p, 0, (size_t)cells, m.stream));
         size_t rows;
         size_ws(m, n_frames, B, 0, rows);
         PK_HIP(hipMemcpyAsync(m.ws.x.p, enc, rows * m.cfg.hidden_size * 4, hipMemcpyHostToDevice, m.stream));
@@ -1455,6 +1457,58 @@ pk_status pk_diag_tdt_kws_lattice(pk_model *h, const float *enc, const int32_t *
         PK_HIP(hipMemcpyAsync(dl, ws.a.dl.p, nd * 4, hipMemcpyDeviceToHost, m.stream));
         PK_HIP(hipMemcpyAsync(top, ws.top.p, nb * 4, hipMemcpyDeviceToHost, m.stream));
         PK_HIP(hipStreamSynchronize(m.stream));
+    });
+}
+
+// kernels/tdt_kws_bf16.hip alone on the caller's operands: the weight packed as the engine packs it, the one launch, the outputs staged with the
+// guard words of pk_diag_tdt_lattice.  No model.  Every refusal comes before a device is looked for.
+pk_status pk_diag_tdt_kws_lattice_bf16(const float *ep, const float *pp, const float *wld, const float *bld, const int32_t *ids, const int32_t *id_offsets,
+                                       const int32_t *n_frames, const int32_t *ep_row0, const int32_t *net_of, int n_pairs, int n_net, int V, int D, int J,
+                                       int blank, float *lab, float *blk, float *dl) {
+    return guard([&] {
+        need(ep && pp && wld && bld && ids && ep_row0 && net_of && lab && blk && dl && V >= 1 && J >= 1 && n_net >= 1, "ep/pp/wld/bld/ids/ep_row0/net_of/lab/blk/dl/V/J/n_net");
+        need(D >= 1 && D <= 8 && blank >= 0 && blank < V, "D 1 .. 8, blank inside [0, V)");
+        const int32_t durations[8] = {};                             // (the walk's durations play no part in the lattice values)
+        tdt_host_lattice_checks(durations, n_frames, n_pairs, id_offsets);
+        int64_t ep_rows = 0;
+        int u_max = 0;
+        for (int p = 0; p < n_pairs; ++p) {
+            const int L = id_offsets[p + 1] - id_offsets[p];
+            if (L == 0) fail(PK_ERR_INVALID, "invalid argument: keyword %d is empty", p);
+            if (L > kKwsMaxLen) fail(PK_ERR_UNSUPPORTED, "TDT keyword spotting: %d tokens in keyword %d, at most %d can be spotted", L, p, kKwsMaxLen);
+            need(ep_row0[p] >= 0 && net_of[p] >= 0 && net_of[p] < n_net, "ep_row0[p] negative or net_of[p] outside [0, n_net)");
+            ep_rows = std::max<int64_t>(ep_rows, (int64_t)ep_row0[p] + n_frames[p]);
+            u_max = std::max(u_max, L);
+        }
+        for (int i = 0; i < id_offsets[n_pairs]; ++i) need(ids[i] >= 0 && ids[i] < V, "ids outside [0, V)");
+        if (tdt_kws_bf16_rows(J) == 0) fail(PK_ERR_UNSUPPORTED, "the bf16 TDT keyword spotting kernel: J %d (a multiple of 32, at most 1152)", J);
+        TdtAlignWs ws;
+        tdt_lattice_plan(ws, n_frames, ep_row0, n_pairs, 0, id_offsets, durations, D, 0, 0, 0, /*back_pointers=*/false, "TDT keyword spotting (bf16)");
+        need_device();
+        const size_t G = PK_DIAG_TDT_LATTICE_GUARD, nl = (size_t)ws.labs + G, nb = (size_t)ws.cells + G, nd = (size_t)ws.cells * D + G;
+        ws.lab.reserve(nl * 4); ws.blk.reserve(nb * 4); ws.dl.reserve(nd * 4);
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.lab.p, 0x7FC5A5A5, nl, nullptr));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.blk.p, 0x7FC5A5A5, nb, nullptr));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.dl.p, 0x7FC5A5A5, nd, nullptr));
+        tdt_lattice_upload(ws, ids, nullptr, /*token_results=*/false);
+        const size_t VD = (size_t)V + D, n_ep = (size_t)ep_rows * J, n_pp = (size_t)(u_max + 1) * n_net * J;
+        DevBuf d_ep, d_pp, d_w, d_b, d_w16, d_net;
+        d_ep.reserve(n_ep * 4); d_pp.reserve(n_pp * 4); d_w.reserve(VD * J * 4); d_b.reserve(VD * 4); d_net.reserve((size_t)n_pairs * 4);
+        d_w16.reserve(tdt_lattice_bf16_weight_bytes((int)VD, J));
+        PK_HIP(hipMemcpyAsync(d_ep.p, ep, n_ep * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_pp.p, pp, n_pp * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_w.p, wld, VD * J * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_b.p, bld, VD * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_net.p, net_of, (size_t)n_pairs * 4, hipMemcpyHostToDevice, nullptr));
+        launch_tdt_lattice_bf16_pack(d_w.as<float>(), (int)VD, J, d_w16.p, nullptr);
+        TdtKwsBf16Args a{ws.lattice(), ws.ep_row0(), ws.ids.as<int>(), d_net.as<int>(), d_ep.as<float>(), d_pp.as<float>(), d_w16.p, d_b.as<float>(),
+                         n_net, V, J, blank, ws.cells};
+        launch_tdt_kws_bf16(a, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(lab, ws.lab.p, nl * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(blk, ws.blk.p, nb * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(dl, ws.dl.p, nd * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipStreamSynchronize(nullptr));
     });
 }
 

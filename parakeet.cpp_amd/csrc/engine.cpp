@@ -517,20 +517,35 @@ void Model::set_tdt_lattice_bf16(bool on) {
         fail(PK_ERR_UNSUPPORTED, "the bf16 TDT lattice kernel needs a TDT joint (label + duration heads)");
     if (on && tdt_lattice_bf16_rows(cfg.joint_hidden) == 0)
         fail(PK_ERR_UNSUPPORTED, "the bf16 TDT lattice kernel: joint_hidden %d (a multiple of 32, at most 1120)", cfg.joint_hidden);
-    if (on && !wld_tl16_.p) {
-        require_gpu();
-        const int VD = cfg.vocab_size + cfg.num_durations, J = cfg.joint_hidden;
-        try {
-            wld_tl16_.reserve(tdt_lattice_bf16_weight_bytes(VD, J));
-            launch_tdt_lattice_bf16_pack(wld, VD, J, wld_tl16_.p, stream);
-            PK_CHECK_LAUNCH();
-            PK_HIP(hipStreamSynchronize(stream));
-        } catch (...) {
-            if (wld_tl16_.p) { (void)hipFree(wld_tl16_.p); wld_tl16_.p = nullptr; wld_tl16_.cap = 0; }
-            throw;
-        }
-    }
+    if (on) ensure_tdt_w16();
     tdt_lattice_bf16 = on;
+}
+
+void Model::ensure_tdt_w16() {
+    if (wld_tl16_.p) return;
+    require_gpu();
+    const int VD = cfg.vocab_size + cfg.num_durations, J = cfg.joint_hidden;
+    try {
+        wld_tl16_.reserve(tdt_lattice_bf16_weight_bytes(VD, J));
+        launch_tdt_lattice_bf16_pack(wld, VD, J, wld_tl16_.p, stream);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipStreamSynchronize(stream));
+    } catch (...) {
+        if (wld_tl16_.p) { (void)hipFree(wld_tl16_.p); wld_tl16_.p = nullptr; wld_tl16_.cap = 0; }
+        throw;
+    }
+}
+
+// The spotting kernel's switch: the same refusals for its own limits, the same packed copy.
+void Model::set_tdt_kws_bf16(bool on) {
+    if (on && !cfg.gemm_bf16)
+        fail(PK_ERR_UNSUPPORTED, "the bf16 TDT keyword spotting kernel needs a gemm_bf16 model: the fp32 mode's contract is bit equality with the reference");
+    if (on && (cfg.vocab_size <= 0 || cfg.rnnt_head || cfg.num_durations <= 0))
+        fail(PK_ERR_UNSUPPORTED, "the bf16 TDT keyword spotting kernel needs a TDT joint (label + duration heads)");
+    if (on && tdt_kws_bf16_rows(cfg.joint_hidden) == 0)
+        fail(PK_ERR_UNSUPPORTED, "the bf16 TDT keyword spotting kernel: joint_hidden %d (a multiple of 32, at most 1152)", cfg.joint_hidden);
+    if (on) ensure_tdt_w16();
+    tdt_kws_bf16 = on;
 }
 
 void Model::set_tdt_total_shared(bool on) {

@@ -279,6 +279,13 @@ class Model {
     bool tdt_lattice_bf16 = false;
     void set_tdt_lattice_bf16(bool on);
     DevBuf wld_tl16_;
+    // The bf16 lattice kernel of TDT keyword spotting (pk_model_set_tdt_kws_bf16; kernels/tdt_kws_bf16.hip), off by default and independent of the
+    // switch above: gemm_bf16 models with a TDT joint whose width the kernel takes only.  On, tdt_align_model_checks lets this model through for the
+    // offline spotting entry points and run_tdt_kws_call launches the one kernel instead of act / heads / keep / norm.  It reads the same packed
+    // weight copy (wld_tl16_, made by whichever switch asks first: ensure_tdt_w16).  Not to be changed while a batch is in flight.
+    bool tdt_kws_bf16 = false;
+    void set_tdt_kws_bf16(bool on);
+    void ensure_tdt_w16();
 
     // The prefix-tree path of the TDT total (pk_model_set_tdt_total_shared; kernels/tdt_tree.hip), off by default: fp32 models with a
     // TDT joint only.  On, tdt_total_plan_call / run_tdt_total_call score the transcripts of a clip on one prefix tree per clip; every total and ok

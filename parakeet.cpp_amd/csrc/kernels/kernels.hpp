@@ -722,6 +722,21 @@ void launch_tdt_kws_keep(const TdtLattice &lt, float *top, const int *ids, const
 void launch_tdt_kws_norm(const TdtLattice &lt, const float *top, int64_t cells, hipStream_t s);
 // every pair needs 1 <= U_b <= kKwsMaxLen, max_hits 1 .. kKwsMaxHits, durations in [0, kTdtAlignMaxDur]
 void launch_tdt_kws(const TdtKwsArgs &a, hipStream_t s);
+// act, heads product, keep and norm as ONE kernel of the tolerance-class mode (kernels/tdt_kws_bf16.hip; pk_model_set_tdt_kws_bf16): every lattice row
+// of the group from ep / pp to the NORMALISED lab / blk / dl (logit - row maximum, no log-softmax; what launch_tdt_kws_norm leaves, with top = 0), z
+// and the heads weights as bf16 on the MFMA, fp32 accumulation and bias.  w16 = the load-order copy launch_tdt_lattice_bf16_pack writes.
+// tdt_kws_bf16_rows: lattice rows per workgroup at joint width J, 0 where the kernel does not apply (J % 32 != 0 or J > 1152).
+struct TdtKwsBf16Args {
+    TdtLattice lt;
+    const int *ep_row0, *ids, *net_of;          // [pairs] first enc_proj row of the pair's clip; packed keywords (lt.id_off); [pairs] the net's slot
+    const float *ep, *pp;                       // enc_proj rows; prediction-net rows pp[u n_net + net_of[p]]
+    const void *w16;
+    const float *bld;                           // [V + D]
+    int n_net, V, J, blank;
+    int64_t cells;                              // lattice rows in all (cell_off[pairs])
+};
+int tdt_kws_bf16_rows(int J);
+void launch_tdt_kws_bf16(const TdtKwsBf16Args &a, hipStream_t s);
 
 // Streaming TDT keyword spotting (kernels/tdt_kws_stream.hip): the same walk over the next c frames of every (stream, keyword)
 // pair, picked up from the pair's CARRIED ring, and the online hit rule on the chunk's exit rows.  Every pair of the lattice has T = c frames.

@@ -118,11 +118,11 @@ void run_tdt_align_pred(Model &m, TdtAlignWs &ws, const int32_t *ids, hipStream_
     }
 }
 
-void tdt_align_model_checks(const Model &m, bool lattice_bf16_ok) {
+void tdt_align_model_checks(const Model &m, bool lattice_bf16_ok, bool kws_bf16_ok) {
     if (m.cfg.vocab_size <= 0) fail(PK_ERR_UNSUPPORTED, "this model has no prediction net / joint (encoder-only configuration): TDT alignment needs a TDT joint");
     if (m.cfg.rnnt_head || m.cfg.num_durations <= 0)
         fail(PK_ERR_UNSUPPORTED, "TDT alignment needs a TDT joint (label + duration heads): this model has an RNN-T head");
-    if (m.cfg.gemm_bf16 && !(lattice_bf16_ok && m.tdt_lattice_bf16)) fail(PK_ERR_UNSUPPORTED, "TDT alignment has no gemm_bf16 form: the decode weights of this model exist only rounded to bf16");
+    if (m.cfg.gemm_bf16 && !(lattice_bf16_ok && m.tdt_lattice_bf16) && !(kws_bf16_ok && m.tdt_kws_bf16)) fail(PK_ERR_UNSUPPORTED, "TDT alignment has no gemm_bf16 form: the decode weights of this model exist only rounded to bf16");
 }
 
 size_t tdt_align_bytes(const TdtAlignWs &ws) {

@@ -58,8 +58,9 @@ void run_tdt_align_lattice(Model &m, TdtAlignWs &ws, const float *d_ep, hipStrea
 void run_tdt_align_heads(Model &m, TdtAlignWs &ws, int n, hipStream_t s);
 // what the model entry points refuse (include/parakeet_amd.h): no TDT joint (encoder-only, RNN-T head), gemm_bf16.  lattice_bf16_ok: the caller
 // computes its lattice with run_tdt_align_lattice alone (the alignment and total entry points), which a gemm_bf16 model with
-// pk_model_set_tdt_lattice_bf16 on serves; keyword spotting, the beam and streaming pass false and keep refusing.
-void tdt_align_model_checks(const Model &m, bool lattice_bf16_ok = false);
+// pk_model_set_tdt_lattice_bf16 on serves; the beam and streaming pass false and keep refusing.  kws_bf16_ok: the caller builds its lattice with
+// run_tdt_kws_call (the offline keyword spotting entry points), which such a model serves with pk_model_set_tdt_kws_bf16 on -- that switch alone.
+void tdt_align_model_checks(const Model &m, bool lattice_bf16_ok = false, bool kws_bf16_ok = false);
 // bytes of device memory the alignment's buffers hold (pk_diag_mem_info)
 size_t tdt_align_bytes(const TdtAlignWs &ws);
 // the walk and the back-trace over ws.lab / blk / dl; results stay on the device in ws

@@ -14,8 +14,17 @@ size_t tdt_kws_scratch(int64_t cells, int64_t labs, int n, int u_max, int D, int
     return tdt_total_scratch(cells, labs, n, u_max, D, V, J) + 4 * (size_t)cells + 16 * (size_t)(cells - labs);
 }
 
+size_t tdt_kws_scratch_bf16(int64_t cells, int64_t labs, int n, int u_max, int D, int J) {
+    return 4 * ((size_t)labs + (size_t)cells * (1 + (size_t)D)) + (size_t)(u_max + 1) * (size_t)n * ((size_t)J + 1) * 4 + 16 * (size_t)(cells - labs);
+}
+
 void tdt_kws_plan_call(TdtKwsWs &ws, const int32_t *durations, int D, int V, int J, const int32_t *n_frames, int n_clips, int T, const int32_t *kw_ids,
-                       const int32_t *kw_offsets, int n_kw, const int32_t *clip_of, const int32_t *kw_of, int n_pairs, const pk_kws_options &opt) {
+                       const int32_t *kw_offsets, int n_kw, const int32_t *clip_of, const int32_t *kw_of, int n_pairs, const pk_kws_options &opt,
+                       bool bf16) {
+    ws.bf16 = bf16;
+    auto scratch = [&](int64_t cells, int64_t labs, int n, int u_max) {
+        return bf16 ? tdt_kws_scratch_bf16(cells, labs, n, u_max, D, J) : tdt_kws_scratch(cells, labs, n, u_max, D, V, J);
+    };
     if (D < 1 || D > 8) fail(PK_ERR_UNSUPPORTED, "%s: %d durations, the kernel is built for 1 to 8", kWhat, D);
     for (int i = 0; i < D; ++i)
         if (durations[i] < 0 || durations[i] > kTdtAlignMaxDur)
@@ -36,10 +45,10 @@ void tdt_kws_plan_call(TdtKwsWs &ws, const int32_t *durations, int D, int V, int
         ws.pid.insert(ws.pid.end(), kw_ids + kw_offsets[k], kw_ids + kw_offsets[k + 1]);
         ws.poff.push_back((int32_t)ws.pid.size());
         const int64_t pc = Tp * (L + 1), pl = Tp * L;
-        if (pc > (int64_t)kTdtAlignMaxScratch || tdt_kws_scratch(pc, pl, 1, (int)L, D, V, J) > kTdtAlignMaxScratch)
+        if (pc > (int64_t)kTdtAlignMaxScratch || scratch(pc, pl, 1, (int)L) > kTdtAlignMaxScratch)
             fail(PK_ERR_UNSUPPORTED, "%s: the scratch of keyword %d on clip %d alone (lattice values, exit rows%s) exceeds the cap of %zu bytes", kWhat, k, c,
-                 V > 0 ? ", rows chunk, prediction net" : "", kTdtAlignMaxScratch);
-        if (n > 0 && (n + 1 > max_pairs || tdt_kws_scratch(cells + pc, labs + pl, n + 1, std::max(u_max, (int)L), D, V, J) > kTdtAlignMaxScratch)) {
+                 bf16 ? ", prediction net" : V > 0 ? ", rows chunk, prediction net" : "", kTdtAlignMaxScratch);
+        if (n > 0 && (n + 1 > max_pairs || scratch(cells + pc, labs + pl, n + 1, std::max(u_max, (int)L)) > kTdtAlignMaxScratch)) {
             ws.gstart.push_back(p);
             cells = labs = 0; n = 0; u_max = 0;
         }
@@ -56,7 +65,7 @@ void run_tdt_kws_dp(TdtKwsWs &ws, hipStream_t s) {
     ws.out.reserve((n + 3 * slots) * 4);
     TdtKwsArgs a{};
     a.lt = ws.a.lattice();
-    launch_tdt_kws_norm(a.lt, ws.top.as<float>(), ws.a.cells, s);
+    if (!ws.bf16) launch_tdt_kws_norm(a.lt, ws.top.as<float>(), ws.a.cells, s);
     a.eb = ws.eb.as<int4>();
     a.max_hits = ws.max_hits; a.min_score = ws.min_score;
     a.n_hits = ws.out.as<int>();
@@ -103,8 +112,9 @@ void run_tdt_kws_call(Model &m, TdtKwsWs &ws, const float *d_ep, const int32_t *
         ws.off.resize(n + 1);
         for (int i = 0; i <= n; ++i) ws.off[i] = ws.poff[g0 + i] - ws.poff[g0];
         const int32_t *gids = ws.pid.data() + ws.poff[g0];
-        tdt_lattice_plan(ws.a, ws.T_of.data() + g0, ws.row0_of.data() + g0, n, 0, ws.off.data(), c.durations, c.num_durations, V, J, chunk_rows,
-                         /*back_pointers=*/false, kWhat);
+        const bool bf16 = ws.bf16;                                  // (planned so: no rows chunk, no top)
+        tdt_lattice_plan(ws.a, ws.T_of.data() + g0, ws.row0_of.data() + g0, n, 0, ws.off.data(), c.durations, c.num_durations, bf16 ? 0 : V, bf16 ? 0 : J,
+                         chunk_rows, /*back_pointers=*/false, kWhat);
         // the distinct keywords of the group, in the order of their first pair: the prediction net runs on those
         ws.slot.assign(n_kw, -1); ws.h_net_of.resize(n); ws.kids.clear(); ws.koff.assign(1, 0);
         for (int i = 0; i < n; ++i) {
@@ -122,13 +132,19 @@ void run_tdt_kws_call(Model &m, TdtKwsWs &ws, const float *d_ep, const int32_t *
         ws.h.reserve(st); ws.hn.reserve(st); ws.c.reserve(st); ws.cn.reserve(st);
         float *state[4] = {ws.h.as<float>(), ws.hn.as<float>(), ws.c.as<float>(), ws.cn.as<float>()};
         ws.net_of.reserve((size_t)n * 4);
-        ws.top.reserve((size_t)std::max<int64_t>(ws.a.cells, 1) * 4);
+        if (!bf16) ws.top.reserve((size_t)std::max<int64_t>(ws.a.cells, 1) * 4);
         if (ev) PK_HIP(hipEventRecord(ev[0], s));
         tdt_lattice_upload(ws.a, gids, s, /*token_results=*/false);
         PK_HIP(hipMemcpyAsync(ws.net_of.p, ws.h_net_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
         run_tdt_align_pred(m, ws.net, ws.kids.data(), s, state);
         if (ev) PK_HIP(hipEventRecord(ev[1], s));
-        tdt_kws_build_lattice(m, ws.a, ws.top.as<float>(), d_ep, ws.net, ws.net_of.as<int>(), nk, s);
+        if (bf16) {                                                 // one launch: no z, no logits, no top, arcs written normalised
+            TdtKwsBf16Args k{ws.a.lattice(), ws.a.ep_row0(), ws.a.ids.as<int>(), ws.net_of.as<int>(), d_ep, ws.net.pp.as<float>(), m.wld_tl16_.p, m.bld,
+                             nk, V, J, c.blank_id, ws.a.cells};
+            launch_tdt_kws_bf16(k, s);
+        } else {
+            tdt_kws_build_lattice(m, ws.a, ws.top.as<float>(), d_ep, ws.net, ws.net_of.as<int>(), nk, s);
+        }
         if (ev) PK_HIP(hipEventRecord(ev[2], s));
         if (walk) run_tdt_kws_dp(ws, s);
         if (ev) PK_HIP(hipEventRecord(ev[3], s));

@@ -28,17 +28,24 @@ struct TdtKwsWs {
     std::vector<int32_t> T_of, row0_of, kw_of, pid, poff, off, gstart, h_net_of, kids, koff, slot;
     int max_hits = 1;
     float min_score = 0.0f;
+    bool bf16 = false;                              // planned for the bf16 lattice kernel: lab / blk / dl are written normalised, top / z / logits unused
     std::vector<int32_t> n_hits, start, end;        // results of the call, gathered group by group: [pairs], [pairs][max_hits]
     std::vector<float> score;
 };
 
 // scratch bytes of n pairs with these sums (V = 0: a host lattice)
 size_t tdt_kws_scratch(int64_t cells, int64_t labs, int n, int u_max, int D, int V, int J);
+// ... with the bf16 lattice kernel (kernels/tdt_kws_bf16.hip, Model::tdt_kws_bf16): lattice values, prediction net and exit rows alone -- no rows
+// chunk (z, logits) and no top, so a group holds more pairs under the same cap
+size_t tdt_kws_scratch_bf16(int64_t cells, int64_t labs, int n, int u_max, int D, int J);
 // Plans a call (host only; refuses before anything is allocated).  n_frames[n_clips] (nullptr: T each).  clip_of / kw_of == nullptr: every keyword in every
-// clip, n_pairs = n_clips * n_kw; otherwise pair p is keyword kw_of[p] on clip clip_of[p].  kws_check_args comes first.
+// clip, n_pairs = n_clips * n_kw; otherwise pair p is keyword kw_of[p] on clip clip_of[p].  kws_check_args comes first.  bf16: sized and cut for the
+// bf16 lattice kernel (tdt_kws_scratch_bf16); run_tdt_kws_call then launches it.
 void tdt_kws_plan_call(TdtKwsWs &ws, const int32_t *durations, int D, int V, int J, const int32_t *n_frames, int n_clips, int T, const int32_t *kw_ids,
-                       const int32_t *kw_offsets, int n_kw, const int32_t *clip_of, const int32_t *kw_of, int n_pairs, const pk_kws_options &opt);
-// The normalisation, the walk and the picking over the uploaded lattice of ws.a and ws.top; results stay on the device in ws.out.
+                       const int32_t *kw_offsets, int n_kw, const int32_t *clip_of, const int32_t *kw_of, int n_pairs, const pk_kws_options &opt,
+                       bool bf16 = false);
+// The normalisation (skipped where ws.bf16: the kernel wrote normalised arcs), the walk and the picking over the uploaded lattice of ws.a and ws.top;
+// results stay on the device in ws.out.
 void run_tdt_kws_dp(TdtKwsWs &ws, hipStream_t s);
 // copies the n results of the walk just queued to ws.n_hits / start / end / score from pair g0 on and waits for the stream
 void tdt_kws_gather(TdtKwsWs &ws, int g0, hipStream_t s);
@@ -46,7 +53,8 @@ void tdt_kws_gather(TdtKwsWs &ws, int g0, hipStream_t s);
 // values.  ep = enc_proj of the frames a.ep_row0() points into; pair b reads the rows of slot net_of[b] (device, [pairs]) of net.pp, which holds n_net slots.
 void tdt_kws_build_lattice(Model &m, TdtAlignWs &a, float *top, const float *ep, const TdtAlignWs &net, const int *net_of, int n_net, hipStream_t s);
 // Queues the planned call on the model's stream: d_ep = enc_proj of the call's packed frames.  Group by group: prediction net, lattice, walk (walk == false:
-// the lattice of the LAST group is left in ws.a / ws.top, not normalised).  ev (optional, 4 events), ms[3] accumulates the three stages over the groups.
+// the lattice of the LAST group is left in ws.a / ws.top, not normalised).  A call planned with bf16 replaces the lattice stage by the ONE launch of
+// kernels/tdt_kws_bf16.hip: ws.a then holds the normalised arcs, ws.top is neither reserved nor written.  ev (optional, 4 events), ms[3] accumulates the three stages over the groups.
 void run_tdt_kws_call(Model &m, TdtKwsWs &ws, const float *d_ep, const int32_t *kw_ids, const int32_t *kw_offsets, int chunk_rows = 0, bool walk = true,
                       hipEvent_t *ev = nullptr, float *ms = nullptr);
 size_t tdt_kws_bytes(const TdtKwsWs &ws);

@@ -8,6 +8,8 @@
 //                [--nlm file.safetensors --nlm-heads H --nlm-bos ID [--nlm-eos ID] [--nlm-alpha A] [--nlm-beta B]]
 // New: --tdt-lattice-bf16 (tdt-ctc-110m, tdt-600m) asks for the bf16 TDT lattice kernel under --align ... --align-head tdt and --score
 // (set_tdt_lattice_bf16): the engine accepts it on a gemm_bf16 model and refuses it on any other.
+// New: --tdt-kws-bf16 (tdt-ctc-110m, tdt-600m) asks for the bf16 TDT spotting lattice kernel under --spot ... --spot-head tdt (set_tdt_kws_bf16),
+// with the same rule.
 // New: --attention-context L,R (tdt-ctc-110m, tdt-600m) limits the encoder's attention to the L frames before and the R frames after each frame
 // (Transcriber::set_attention_context: long recordings).  --local-attention-bf16 (only with --attention-context) asks for the bf16-MFMA band
 // kernel (set_local_attention_bf16): the engine accepts it on a gemm_bf16 model with head size 64 / 128 and refuses it on any other.
@@ -160,7 +162,7 @@ int main(int argc, char **argv) {
         std::vector<std::string> boost, spot;
         SpotOptions spot_opts;
         float boost_score = 5.0f, vad_max_piece = 30.0f;
-        bool vad = false, spot_tdt = false, local_bf16 = false, tdt_lat_bf16 = false;
+        bool vad = false, spot_tdt = false, local_bf16 = false, tdt_lat_bf16 = false, tdt_kws_bf16 = false;
         int att_left = -1, att_right = -1;
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -230,6 +232,7 @@ int main(int argc, char **argv) {
             }
             else if (a == "--local-attention-bf16") local_bf16 = true;
             else if (a == "--tdt-lattice-bf16") tdt_lat_bf16 = true;
+            else if (a == "--tdt-kws-bf16") tdt_kws_bf16 = true;
             else if (a == "--vad-max-piece" && i + 1 < argc) vad_max_piece = std::stof(argv[++i]);
             else if (a == "--gpu" || a == "--streaming") {}
             else if (a == "--timestamps") timestamps = true;
@@ -256,6 +259,7 @@ int main(int argc, char **argv) {
             if (att_ctx) t.set_attention_context(att_left, att_right);
             if (local_bf16) t.set_local_attention_bf16(true);
             if (tdt_lat_bf16) t.set_tdt_lattice_bf16(true);
+            if (tdt_kws_bf16) t.set_tdt_kws_bf16(true);
         };
         if (vad && model != "tdt-ctc-110m" && model != "tdt-600m") { std::cerr << "Error: --vad needs --model tdt-ctc-110m or tdt-600m\n"; return 1; }
         if (vad && device_resample) { std::cerr << "Error: --vad works on 16 kHz audio; it does not combine with --device-resample\n"; return 1; }

@@ -250,6 +250,9 @@ class Engine {   // owns one pk_model; shared by Transcriber and TDTTranscriber
     // New: TDT alignment and scoring (align_tdt, score) of a gemm_bf16 model through the one-launch bf16 lattice kernel
     // (pk_model_set_tdt_lattice_bf16; any other model is refused).  This engine's model; pk_group replicas have no such switch.
     void set_tdt_lattice_bf16(bool on) { check(pk_model_set_tdt_lattice_bf16(m_, on ? 1 : 0)); }
+    // New: TDT keyword spotting (spot_tdt) of a gemm_bf16 model through the one-launch bf16 spotting lattice kernel (pk_model_set_tdt_kws_bf16; any
+    // other model is refused).  Independent of the switch above.  This engine's model; pk_group replicas have no such switch.
+    void set_tdt_kws_bf16(bool on) { check(pk_model_set_tdt_kws_bf16(m_, on ? 1 : 0)); }
     // New: files at another rate than 16 kHz are read at their own rate and resampled on the device on their way into the call
     // (pk_model_set_input_rate for the duration of the call) instead of by pk_read_audio's host resampler.  Off by default: for rates that
     // neither divide nor are divided by 16 kHz the device's samples differ from the host's by one fp32 rounding now and then.
@@ -541,6 +544,8 @@ class Transcriber {
     void set_local_attention_bf16(bool on) { eng_.set_local_attention_bf16(on); }
     /// New: TDT alignment and scoring on the bf16 lattice kernel (Engine::set_tdt_lattice_bf16).
     void set_tdt_lattice_bf16(bool on) { eng_.set_tdt_lattice_bf16(on); }
+    /// New: TDT keyword spotting on the bf16 spotting lattice kernel (Engine::set_tdt_kws_bf16).
+    void set_tdt_kws_bf16(bool on) { eng_.set_tdt_kws_bf16(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 
@@ -679,6 +684,8 @@ class TDTTranscriber {
     void set_local_attention_bf16(bool on) { eng_.set_local_attention_bf16(on); }
     /// New: TDT alignment and scoring on the bf16 lattice kernel (Engine::set_tdt_lattice_bf16).
     void set_tdt_lattice_bf16(bool on) { eng_.set_tdt_lattice_bf16(on); }
+    /// New: TDT keyword spotting on the bf16 spotting lattice kernel (Engine::set_tdt_kws_bf16).
+    void set_tdt_kws_bf16(bool on) { eng_.set_tdt_kws_bf16(on); }
     /// New: resample files on the device instead of on the host (Engine::set_device_resampling); off by default.
     void set_device_resampling(bool on) { eng_.set_device_resampling(on); }
 

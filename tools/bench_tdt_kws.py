@@ -10,8 +10,13 @@ computes, T (L + 1) per pair (column L is packed and not read).  prefix_share: t
 states that another keyword of the call with the same prefix also has -- what a prefix-shared lattice could save.
 With --pcm the 60-minute clip also goes through Model.spot_tdt from PCM with attention context [128,128] (wall ms of the whole call).
 Writes the result lines and a table to --out (default profiles/tdt_kws.md).
-usage: python tools/bench_tdt_kws.py [--reps 3] [--hits 1] [--pcm] [--no-align] [--out profiles/tdt_kws.md]"""
+--bf16: instead, the three stages of a gemm_bf16 model with pk_model_set_tdt_kws_bf16 on (kernels/tdt_kws_bf16.hip) next to the fp32 model's at
+tdt-600m's shapes (one encoder layer: the stages start at the encoder's rows), the two models taking turns; prints the result lines and, with
+--out, writes them (profiles/tdt_kws_bf16.md).
+usage: python tools/bench_tdt_kws.py [--reps 3] [--hits 1] [--pcm] [--no-align] [--out profiles/tdt_kws.md]
+       python tools/bench_tdt_kws.py --bf16 [--reps 9] [--out profiles/tdt_kws_bf16.md]"""
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -23,17 +28,82 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle")]
 import numpy as np
 
 
+NOTES16 = """
+## Reading the figures
+
+- The columns are `ms[0 .. 2]` of `pk_tdt_kws_decode_timed` (prediction net; lattice; normalisation + walk + picking -- the bf16 route has no
+  normalisation pass), one pass per call, the fp32 model and the gemm_bf16 model with `pk_model_set_tdt_kws_bf16` on taking turns on one device;
+  medians over the turns, min and max beside them.  Same weights file, same encoder rows (the fp32 model's) and the same keywords for both.
+- The fp32 route (act, heads product, keep in chunks, then norm) is untouched by the switch: its column is what the code before the switch gives.
+- `*_heads_tflops` counts `2 cells (V + D) J` against the whole lattice stage, cells = sum over the pairs of T (L + 1).
+- `weight_stream_gb` is what the bf16 kernel's workgroups read of the packed weights in all: `ceil(cells / rows_per_wg) (V + D) J 2` bytes.
+"""
+
+
+def bench_bf16(a, pk, capi, synth):
+    """--bf16: the stages of the bf16 spotting lattice kernel (gemm_bf16 model, switch on) next to the fp32 route at the same shapes, interleaved."""
+    rng = np.random.default_rng(1)
+    lines = []
+    with tempfile.TemporaryDirectory() as td:
+        cfg = dataclasses.replace(pk.make_tdt_600m_config(), num_layers=1)
+        wp = os.path.join(td, "tdt-600m.safetensors")
+        synth.save_weights(wp, synth.synth_weights(cfg, seed=42))
+        m32 = capi.Model(wp, cfg, device=0)
+        m16 = capi.Model(wp, dataclasses.replace(cfg, gemm_bf16=True), device=0)
+        m16.set_tdt_kws_bf16(True)
+        V, D, J = cfg.vocab_size, len(cfg.durations), cfg.joint_hidden
+        rows = 128 if J <= 544 else 96 if J <= 736 else 64                             # tdt_kws_bf16_rows
+        for label, n, sec, n_kw in (("64 x 10 s", 64, 10.0, 16), ("32 x 30 s", 32, 30.0, 8), ("1 x 10 s", 1, 10.0, 4)):
+            enc = m32.encode(m32.mel(synth.synth_pcm(n, int(sec * 16000), seed=3)))
+            T = int(enc.shape[1])
+            kws = [rng.integers(0, cfg.blank_id, size=1 + k % 8).astype(np.int32) for k in range(n_kw)]
+            t32, t16 = [], []
+            for m in (m32, m16):
+                m.tdt_kws_decode(enc, kws, max_hits=a.hits)                             # warm-up of the buffers
+            for _ in range(a.reps):
+                t32.append(m32.tdt_kws_decode_timed(enc, kws, max_hits=a.hits, reps=1))
+                t16.append(m16.tdt_kws_decode_timed(enc, kws, max_hits=a.hits, reps=1))
+            t32, t16 = np.asarray(t32), np.asarray(t16)
+            f32, f16 = np.median(t32, 0), np.median(t16, 0)
+            cells = int(n * T * sum(len(k) + 1 for k in kws))
+            out = {"metric": "tdt keyword spotting stage ms", "config": "tdt-600m (1 layer)", "batch": label, "frames": T, "keywords": n_kw,
+                   "lattice_cells": cells, "turns": a.reps,
+                   "fp32_net_lattice_walk_ms": [round(float(v), 3) for v in f32], "bf16_net_lattice_walk_ms": [round(float(v), 3) for v in f16],
+                   "fp32_lattice_min_max_ms": [round(float(t32[:, 1].min()), 3), round(float(t32[:, 1].max()), 3)],
+                   "bf16_lattice_min_max_ms": [round(float(t16[:, 1].min()), 3), round(float(t16[:, 1].max()), 3)],
+                   "lattice_speedup": round(float(f32[1] / f16[1]), 2), "three_stage_speedup": round(float(f32.sum() / f16.sum()), 2),
+                   "fp32_heads_tflops": round(2.0 * cells * (V + D) * J / (f32[1] * 1e-3) / 1e12, 1),
+                   "bf16_heads_tflops": round(2.0 * cells * (V + D) * J / (f16[1] * 1e-3) / 1e12, 1), "rows_per_wg": rows,
+                   "weight_stream_gb": round(-(-cells // rows) * (V + D) * J * 2 / 1e9, 2)}
+            lines.append(out)
+            print(json.dumps(out), flush=True)
+        m32.close(); m16.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("# The bf16 TDT spotting lattice kernel: stage times on one MI355X\n\n`python tools/bench_tdt_kws.py --bf16 --reps %d` (synthetic weights and "
+                    "audio, random keywords of 1 .. 8 tokens, every keyword in every clip, max_hits = %d).\n\n" % (a.reps, a.hits))
+            keys = [k for k in lines[0] if k != "metric"]
+            f.write("| " + " | ".join(keys) + " |\n|" + "---|" * len(keys) + "\n")
+            for o in lines:
+                f.write("| " + " | ".join(str(o[k]) for k in keys) + " |\n")
+            f.write("\n```\n" + "\n".join(json.dumps(o) for o in lines) + "\n```\n" + NOTES16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--hits", type=int, default=1)
     ap.add_argument("--pcm", action="store_true")
     ap.add_argument("--no-align", action="store_true", help="skip the aligner's figure")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tdt_kws.md"))
+    ap.add_argument("--out", default=None, help="default profiles/tdt_kws.md (with --bf16: none, the lines are printed only)")
+    ap.add_argument("--bf16", action="store_true", help="the bf16 spotting lattice kernel next to the fp32 route (profiles/tdt_kws_bf16.md)")
     a = ap.parse_args()
     import pkload
     pk = pkload.load()
     from parakeet_cpp_amd import capi, synth
+    if a.bf16:
+        return bench_bf16(a, pk, capi, synth)
+    a.out = a.out or os.path.join(ROOT, "profiles", "tdt_kws.md")
     cfg = pk.make_110m_config()
     rng = np.random.default_rng(1)
     V, D, J = cfg.vocab_size, len(cfg.durations), cfg.joint_hidden
