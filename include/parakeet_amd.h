@@ -173,7 +173,10 @@ pk_status pk_model_get_tdt_lattice_bf16(const pk_model *m, int *on);
  * beam, the RNN-T head and pk_group keep refusing a gemm_bf16 model.  Not to be changed while a batch is in flight. */
 pk_status pk_model_set_tdt_kws_bf16(pk_model *m, int on);
 pk_status pk_model_get_tdt_kws_bf16(const pk_model *m, int *on);
-/* Prefix-shared TDT total (opt-in, fp32 models with a TDT joint; a gemm_bf16 model or one without a TDT joint: PK_ERR_UNSUPPORTED).  on != 0:
+/* Prefix-shared TDT total (opt-in; fp32 models with a TDT joint, and gemm_bf16 models on which pk_model_set_tdt_lattice_bf16 is on -- in that order:
+ * a gemm_bf16 model with the lattice switch off, or a model without a TDT joint, is PK_ERR_UNSUPPORTED, and switching the lattice kernel off on a
+ * gemm_bf16 model switches this off too).  On a gemm_bf16 model the tree lattice comes from ONE launch of kernels/tdt_tree_bf16.hip (DESIGN.md section
+ * 5.5.3b), whose values equal the per-hypothesis bf16 lattice kernel's bit for bit; pk_transcribe_pcm_nbest_rescored keeps refusing such a model.  on != 0:
  * pk_tdt_total_decode(_ragged), pk_tdt_total_decode_timed, pk_tdt_score_pcm and pk_transcribe_pcm_nbest_rescored score the transcripts of a clip on
  * ONE prefix tree per clip (kernels/tdt_tree.hip): a lattice column is (clip, ids[:u]), computed once however many
  * hypotheses share it.  Every total and ok word equals the unshared path's bit for bit.  Groups are whole clips; a clip whose tree has more than 1536
@@ -628,6 +631,16 @@ pk_status pk_diag_tdt_lattice(pk_model *m, const float *enc, const int32_t *n_fr
  * PK_ERR_INVALID: D outside [1, 8], blank or an id outside [0, V), bad tables.  PK_ERR_UNSUPPORTED: J no multiple of 32 or above 1120. */
 pk_status pk_diag_tdt_lattice_bf16(const float *ep, const float *pp, const float *wld, const float *bld, const int32_t *ids, const int32_t *n_frames,
                                    const int32_t *id_offsets, int B, int V, int D, int J, int blank, float *lab, float *blk, float *dl);
+/* Diagnostic: the bf16 prefix-tree lattice kernel (kernels/tdt_tree_bf16.hip) alone on operands from the host, no model.  The trees are packed as
+ * pk_diag_tdt_prefix_tree returns them (node_offsets [n_clips + 1], parent, token; clip-local, parent[k] < k, siblings' tokens distinct); ep = the
+ * packed frames' enc_proj rows [sum_c n_frames[c]][J], pp = ONE prediction-net row per node [node_offsets[n_clips]][J], wld / bld as above.  Every
+ * other table is built by the library's staging code.  The ONE launch fills lab / blk / dl in the tree layout of pk_tdt_total_tree (clip after clip:
+ * lab [T][n - 1], blk [T][n], dl [T][n][D]), returned with the guard words of pk_diag_tdt_lattice.
+ * PK_ERR_INVALID: D outside [1, 8], blank or a token outside [0, V), bad tables.  PK_ERR_UNSUPPORTED: J no multiple of 32 or above 1120, a tree of
+ * more than 1536 nodes. */
+pk_status pk_diag_tdt_tree_lattice_bf16(const float *ep, const float *pp, const float *wld, const float *bld, const int32_t *node_offsets,
+                                        const int32_t *parent, const int32_t *token, const int32_t *n_frames, int n_clips, int V, int D, int J, int blank,
+                                        float *lab, float *blk, float *dl);
 /* ---- TDT log-likelihood of a GIVEN transcript, and CTC n-best rescored with it ------------------------------------------------
  * How probable is this token string under the TDT head: the forward algorithm on the lattice of pk_tdt_align (same cells, same arcs; a blank of
  * duration 0 and a blank of duration 1 are two arcs to the next frame and both are summed), specified operation by operation in DESIGN.md

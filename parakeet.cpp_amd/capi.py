@@ -361,6 +361,7 @@ _LATE_SIGNATURES = {
     "pk_model_set_tdt_total_shared": [C.c_void_p, C.c_int],
     "pk_model_get_tdt_total_shared": [C.c_void_p, C.POINTER(C.c_int)],
     "pk_diag_tdt_lattice_bf16": [f32p, f32p, f32p, f32p, i32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p],
+    "pk_diag_tdt_tree_lattice_bf16": [f32p, f32p, f32p, f32p, i32p, i32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p],
     "pk_resample_length": [C.c_int64, C.c_int, C.c_int],
     "pk_resample_run": [C.c_int, C.c_int],
     "pk_resample_table": [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -1946,6 +1947,24 @@ def tdt_lattice_bf16(ep, pp, wld, bld, ids, n_frames, V, D, blank):
     lab = np.zeros(labs + G, np.float32); blk = np.zeros(cells + G, np.float32); dl = np.zeros(cells * D + G, np.float32)
     check(lib().pk_diag_tdt_lattice_bf16(_f(ep), _f(pp), _f(wld), _f(bld), _i(pid), _i(T), _i(off), len(T), int(V), int(D), J, int(blank),
                                          _f(lab), _f(blk), _f(dl)))
+    return lab, blk, dl
+
+
+def tdt_tree_lattice_bf16(ep, pp, wld, bld, node_off, parent, token, n_frames, V, D, blank):
+    """pk_diag_tdt_tree_lattice_bf16: the bf16 prefix-tree lattice kernel alone, no model.  Trees as tdt_prefix_tree returns them; ep [sum T][J] packed
+    frames, pp [nodes][J] one row per node, wld [V + D][J], bld [V + D] -> (lab [labs + G], blk [cells + G], dl [cells D + G]) flat in the tree layout
+    of tdt_total_tree, G = TDT_LATTICE_GUARD words of the fill pattern 0x7FC5A5A5 (a NaN) behind each; the library fills
+    the whole of every output with it before the launch, so a word the kernel leaves out reads as it."""
+    ep, pp, wld, bld = _c(ep), _c(pp), _c(wld), _c(bld)
+    no, par, tok, T = (np.ascontiguousarray(x, np.int32) for x in (node_off, parent, token, n_frames))
+    n = np.diff(no).astype(np.int64)
+    J = ep.shape[1]
+    assert wld.shape == (V + D, J) and bld.shape == (V + D,) and ep.shape[0] == int(T.sum()) and pp.shape == (int(no[-1]), J) and len(T) == len(n)
+    cells, labs = int((T * n).sum()), int((T * (n - 1)).sum())
+    G = TDT_LATTICE_GUARD
+    lab = np.zeros(labs + G, np.float32); blk = np.zeros(cells + G, np.float32); dl = np.zeros(cells * D + G, np.float32)
+    check(lib().pk_diag_tdt_tree_lattice_bf16(_f(ep), _f(pp), _f(wld), _f(bld), _i(no), _i(par), _i(tok), _i(T), len(T), int(V), int(D), J, int(blank),
+                                              _f(lab), _f(blk), _f(dl)))
     return lab, blk, dl
 
 

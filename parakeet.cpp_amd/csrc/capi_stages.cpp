@@ -1002,6 +1002,69 @@ pk_status pk_tdt_total_tree(const float *lab, const float *blk, const float *dl,
     });
 }
 
+// kernels/tdt_tree_bf16.hip alone on the caller's operands and trees: the tables staged as a model call stages them (the children sorted by token
+// among them), the weight packed as Model::set_tdt_lattice_bf16 packs it, the one launch, the outputs staged as pk_diag_tdt_lattice_bf16's.  No model.
+pk_status pk_diag_tdt_tree_lattice_bf16(const float *ep, const float *pp, const float *wld, const float *bld, const int32_t *node_offsets,
+                                        const int32_t *parent, const int32_t *token, const int32_t *n_frames, int n_clips, int V, int D, int J, int blank,
+                                        float *lab, float *blk, float *dl) {
+    return guard([&] {
+        need(ep && pp && wld && bld && lab && blk && dl && V >= 1 && J >= 1, "ep/pp/wld/bld/lab/blk/dl/V/J");
+        need(D >= 1 && D <= 8 && blank >= 0 && blank < V, "D 1 .. 8, blank inside [0, V)");
+        need(n_clips >= 1 && n_frames && node_offsets && parent && token && node_offsets[0] == 0, "n_clips/n_frames/node_offsets/parent/token");
+        std::vector<int32_t> all(n_clips), row0(n_clips), none(n_clips + 1, 0);
+        int64_t rows = 0;
+        for (int c = 0; c < n_clips; ++c) {
+            need(n_frames[c] > 0, "n_frames[c] must be positive");
+            const int n0 = node_offsets[c], n = node_offsets[c + 1] - n0;
+            need(n >= 1 && parent[n0] == -1, "every clip has its root node, parent -1");
+            for (int k = 1; k < n; ++k) {
+                need(parent[n0 + k] >= 0 && parent[n0 + k] < k, "parent[k] outside [0, k)");
+                need(token[n0 + k] >= 0 && token[n0 + k] < V, "token[k] outside [0, V)");
+            }
+            all[c] = c; row0[c] = (int32_t)rows; rows += n_frames[c];
+        }
+        if (tdt_tree_bf16_rows(J) == 0) fail(PK_ERR_UNSUPPORTED, "the bf16 TDT tree lattice kernel: J %d (a multiple of 32, at most 1120)", J);
+        const int32_t durations[8] = {};                             // (the walk's durations play no part in the lattice values)
+        const int N = node_offsets[n_clips];
+        TdtTreeWs ws;
+        ws.pt.node_off.assign(node_offsets, node_offsets + n_clips + 1);
+        ws.pt.parent.assign(parent, parent + N); ws.pt.token.assign(token, token + N);
+        tdt_tree_stage(ws, all.data(), n_clips, n_frames, row0.data(), ws.pt, none.data(), nullptr, durations, D, V, J, blank, /*rows_chunk=*/false);
+        const int32_t *tb = ws.h_tab.data();
+        for (int c = 0; c < n_clips; ++c)                            // siblings with one token would share a lab column's source: refuse them
+            for (int k = 0; k < node_offsets[c + 1] - node_offsets[c]; ++k)
+                for (int j = tb[ws.o_child_off + node_offsets[c] + k] + 1; j < tb[ws.o_child_off + node_offsets[c] + k + 1]; ++j)
+                    need(tb[ws.o_child_tok + j - 1] < tb[ws.o_child_tok + j], "two children of one node carry the same token");
+        need_device();
+        tdt_tree_upload(ws, nullptr);
+        const size_t G = PK_DIAG_TDT_LATTICE_GUARD, nl = (size_t)ws.labs + G, nb = (size_t)ws.cells + G, nd = (size_t)ws.cells * D + G;
+        ws.lab.reserve(nl * 4); ws.blk.reserve(nb * 4); ws.dl.reserve(nd * 4);
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.lab.p, 0x7FC5A5A5, nl, nullptr));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.blk.p, 0x7FC5A5A5, nb, nullptr));
+        PK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.dl.p, 0x7FC5A5A5, nd, nullptr));
+        // the net's rows in the order the staging gave them (depth, then clip, then node): row ppos[g] is node g's
+        std::vector<float> pps((size_t)N * J);
+        for (int g = 0; g < N; ++g) std::copy(pp + (size_t)g * J, pp + (size_t)(g + 1) * J, pps.begin() + (size_t)tb[ws.o_ppos + g] * J);
+        const size_t VD = (size_t)V + D, n_ep = (size_t)rows * J;
+        DevBuf d_ep, d_w, d_b, d_w16;
+        d_ep.reserve(n_ep * 4); ws.pp.reserve(pps.size() * 4); d_w.reserve(VD * J * 4); d_b.reserve(VD * 4);
+        d_w16.reserve(tdt_lattice_bf16_weight_bytes((int)VD, J));
+        PK_HIP(hipMemcpyAsync(d_ep.p, ep, n_ep * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(ws.pp.p, pps.data(), pps.size() * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_w.p, wld, VD * J * 4, hipMemcpyHostToDevice, nullptr));
+        PK_HIP(hipMemcpyAsync(d_b.p, bld, VD * 4, hipMemcpyHostToDevice, nullptr));
+        launch_tdt_lattice_bf16_pack(d_w.as<float>(), (int)VD, J, d_w16.p, nullptr);
+        TdtTreeLatticeBf16Args a = ws.lattice_bf16_args(d_ep.as<float>(), ws.pp.as<float>(), V, J, blank);
+        a.w16 = d_w16.p; a.bld = d_b.as<float>();
+        launch_tdt_tree_lattice_bf16(a, nullptr);
+        PK_CHECK_LAUNCH();
+        PK_HIP(hipMemcpyAsync(lab, ws.lab.p, nl * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(blk, ws.blk.p, nb * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipMemcpyAsync(dl, ws.dl.p, nd * 4, hipMemcpyDeviceToHost, nullptr));
+        PK_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
 pk_status pk_diag_tdt_prefix_tree(const int32_t *ids, const int32_t *id_offsets, const int32_t *clip_of, int n_clips, int n_hyp, int32_t *node_offsets,
                                   int32_t *parent, int32_t *token, int32_t *end_node) {
     return guard([&] {

@@ -519,6 +519,7 @@ void Model::set_tdt_lattice_bf16(bool on) {
         fail(PK_ERR_UNSUPPORTED, "the bf16 TDT lattice kernel: joint_hidden %d (a multiple of 32, at most 1120)", cfg.joint_hidden);
     if (on) ensure_tdt_w16();
     tdt_lattice_bf16 = on;
+    if (!on && cfg.gemm_bf16) tdt_total_shared = false;             // (the prefix-tree total of a gemm_bf16 model runs on this kernel's tree form alone)
 }
 
 void Model::ensure_tdt_w16() {
@@ -551,8 +552,9 @@ void Model::set_tdt_kws_bf16(bool on) {
 void Model::set_tdt_total_shared(bool on) {
     if (on && (cfg.vocab_size <= 0 || cfg.rnnt_head || cfg.num_durations <= 0))
         fail(PK_ERR_UNSUPPORTED, "the prefix-tree TDT total needs a TDT joint (label + duration heads)");
-    if (on && cfg.gemm_bf16)
-        fail(PK_ERR_UNSUPPORTED, "the prefix-tree TDT total is fp32: the bf16 lattice kernel of a gemm_bf16 model keeps its per-hypothesis layout");
+    if (on && cfg.gemm_bf16 && !tdt_lattice_bf16)
+        fail(PK_ERR_UNSUPPORTED, "the prefix-tree TDT total of a gemm_bf16 model runs on the bf16 lattice kernel: call pk_model_set_tdt_lattice_bf16(on) first, "
+                                 "then pk_model_set_tdt_total_shared(on); switching the lattice kernel off switches this off too");
     tdt_total_shared = on;
 }
 

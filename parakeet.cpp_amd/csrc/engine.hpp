@@ -288,7 +288,8 @@ class Model {
     void ensure_tdt_w16();
 
     // The prefix-tree path of the TDT total (pk_model_set_tdt_total_shared; kernels/tdt_tree.hip), off by default: fp32 models with a
-    // TDT joint only.  On, tdt_total_plan_call / run_tdt_total_call score the transcripts of a clip on one prefix tree per clip; every total and ok
+    // TDT joint, and gemm_bf16 models WHILE tdt_lattice_bf16 is on (kernels/tdt_tree_bf16.hip; set_tdt_lattice_bf16(false) clears
+    // this switch on such a model, so "bf16, shared, no bf16 lattice" never exists).  On, tdt_total_plan_call / run_tdt_total_call score the transcripts of a clip on one prefix tree per clip; every total and ok
     // word equals the unshared path's bit for bit.  Not to be changed while a batch is in flight.
     bool tdt_total_shared = false;
     void set_tdt_total_shared(bool on);

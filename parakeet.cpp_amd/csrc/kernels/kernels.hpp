@@ -679,6 +679,22 @@ void launch_tdt_tree_total(const TdtTreeTotalArgs &a, hipStream_t s);
 void launch_tdt_tree_act(const TdtTree &tr, const float *ep, const float *pp, int J, int64_t row0, int n, float *z, hipStream_t s);
 // ... and the same rows of the heads product's output taken to blk, dl[D] and one lab value per child of the node
 void launch_tdt_tree_keep(const TdtTree &tr, const float *logits, int V, int blank, int64_t row0, int n, hipStream_t s);
+// act, heads product and keep as ONE kernel of the tolerance-class mode (kernels/tdt_tree_bf16.hip; pk_model_set_tdt_total_shared on a gemm_bf16 model
+// with pk_model_set_tdt_lattice_bf16 on): every tree-lattice row from ep / pp to blk, dl[D] and one lab value per child, each
+// value bit for bit what launch_tdt_lattice_bf16 gives for the same (frame, prefix) on a chain.  child_s / child_tok: every node's children SORTED BY
+// TOKEN, laid out as tr.child (node g: entries tr.child_off[g] .. tr.child_off[g + 1]) -- the clip-local node and its token.  w16 as above.
+// tdt_tree_bf16_rows: lattice rows per workgroup at joint width J, 0 where the kernel does not apply (J % 32 != 0 or J > 1120).
+struct TdtTreeLatticeBf16Args {
+    TdtTree tr;
+    const int *child_s, *child_tok;
+    const float *ep, *pp;                       // enc_proj rows (clip c from tr.row0[c]); prediction-net rows pp[tr.ppos[node]]
+    const void *w16;
+    const float *bld;                           // [V + D]
+    int V, J, blank;
+    int64_t cells;                              // lattice rows in all (cell_off[C])
+};
+int tdt_tree_bf16_rows(int J);
+void launch_tdt_tree_lattice_bf16(const TdtTreeLatticeBf16Args &a, hipStream_t s);
 // one depth step of the prediction net over the tree: row j < n of hd / cd [L][stride / Hp][Hp] = row pslot[j] of hs / cs (pslot[j] < 0: zeros)
 void launch_tdt_tree_gather(const int *pslot, int n, int L, int Hp, int64_t stride, const float *hs, const float *cs, float *hd, float *cd, hipStream_t s);
 

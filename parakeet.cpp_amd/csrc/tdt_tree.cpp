@@ -40,10 +40,10 @@ void tdt_prefix_tree_build(TdtPrefixTree &t, const int32_t *ids, const int32_t *
     }
 }
 
-size_t tdt_tree_scratch(int64_t cells, int64_t labs, int64_t nodes, int D, int V, int J) {
+size_t tdt_tree_scratch(int64_t cells, int64_t labs, int64_t nodes, int D, int V, int J, bool rows_chunk) {
     size_t bytes = 4 * ((size_t)labs + (size_t)cells * (1 + (size_t)D));
     if (V > 0) {
-        const int64_t ch = std::min<int64_t>(tdt_align_chunk_rows(V + D), std::max<int64_t>(cells, 1));
+        const int64_t ch = rows_chunk ? std::min<int64_t>(tdt_align_chunk_rows(V + D), std::max<int64_t>(cells, 1)) : 0;
         bytes += (size_t)ch * (size_t)(V + D + J) * 4 + (size_t)nodes * ((size_t)J + 1) * 4;
     }
     return bytes;
@@ -73,8 +73,13 @@ TdtTree TdtTreeWs::tree() const {
     return tr;
 }
 
+TdtTreeLatticeBf16Args TdtTreeWs::lattice_bf16_args(const float *ep, const float *pp, int V, int J, int blank) const {
+    const int *t = tab.as<int>();
+    return TdtTreeLatticeBf16Args{tree(), t + o_child_s, t + o_child_tok, ep, pp, nullptr, nullptr, V, J, blank, cells};
+}
+
 void tdt_tree_stage(TdtTreeWs &ws, const int32_t *cl, int C, const int32_t *T_of, const int32_t *row0_of, const TdtPrefixTree &pt, const int32_t *hc_off,
-                    const int32_t *hc_list, const int32_t *durations, int D, int V, int J, int blank) {
+                    const int32_t *hc_list, const int32_t *durations, int D, int V, int J, int blank, bool rows_chunk) {
     ws.dur_max = tdt_tree_check_durations(durations, D);
     for (int i = 0; i < 8; ++i) ws.durations[i] = i < D ? durations[i] : 0;
     int64_t nodes = 0, cells = 0, labs = 0, hyps = 0;
@@ -88,17 +93,18 @@ void tdt_tree_stage(TdtTreeWs &ws, const int32_t *cl, int C, const int32_t *T_of
         n_max = std::max(n_max, (int)n);
         if ((size_t)cells * 4 * (1 + (size_t)D) > kTdtAlignMaxScratch) break;      // (refused below; keeps the sums far from overflow)
     }
-    if (tdt_tree_scratch(cells, labs, nodes, D, V, J) > kTdtAlignMaxScratch)
+    if (tdt_tree_scratch(cells, labs, nodes, D, V, J, rows_chunk) > kTdtAlignMaxScratch)
         fail(PK_ERR_UNSUPPORTED, "TDT total (shared): the scratch of %s (lattice values%s) exceeds the cap of %zu bytes", C == 1 ? "one clip's tree" : "this call",
-             V > 0 ? ", rows chunk, prediction net" : "", kTdtAlignMaxScratch);
+             V <= 0 ? "" : rows_chunk ? ", rows chunk, prediction net" : ", prediction net", kTdtAlignMaxScratch);
     ws.C = C; ws.D = D; ws.nodes = (int)nodes; ws.n_max = n_max; ws.n_hyp = (int)hyps; ws.cells = cells; ws.labs = labs;
-    ws.chunk_rows = V > 0 ? (int)std::min<int64_t>(tdt_align_chunk_rows(V + D), std::max<int64_t>(cells, 1)) : 0;
+    ws.chunk_rows = V > 0 && rows_chunk ? (int)std::min<int64_t>(tdt_align_chunk_rows(V + D), std::max<int64_t>(cells, 1)) : 0;
     const size_t N = (size_t)nodes, Cz = (size_t)C, H = (size_t)hyps;
     size_t o = 0;
     auto take = [&](size_t n) { const size_t at = o; o += n; return at; };
     ws.o_T = take(Cz); ws.o_node_off = take(Cz + 1); ws.o_row0 = take(Cz); ws.o_parent = take(N); ws.o_token = take(N); ws.o_ppos = take(N);
     ws.o_child_off = take(N + 1); ws.o_child = take(N); ws.o_s_node = take(N); ws.o_s_parent = take(N); ws.o_s_depth = take(N);
     ws.o_dstart = take(N + Cz); ws.o_hyp_off = take(Cz + 1); ws.o_hyp_end = take(H + 1); ws.o_tok_d = take(N); ws.o_pslot = take(N);
+    ws.o_child_s = take(N); ws.o_child_tok = take(N);
     ws.h_tab.assign(o, 0);
     ws.h_tab64.assign(2 * Cz + 2, 0);
     int32_t *tb = ws.h_tab.data();
@@ -129,6 +135,12 @@ void tdt_tree_stage(TdtTreeWs &ws, const int32_t *cl, int C, const int32_t *T_of
         for (int k = 0; k < n; ++k) coff[k + 1] += coff[k];
         cursor.assign(coff, coff + n);
         for (int k = 1; k < n; ++k) tb[ws.o_child + cursor[par[k]]++] = k;
+        // ... and every node's children once more, sorted by the token on their edge (siblings' tokens are distinct), with those tokens beside them
+        std::copy(tb + ws.o_child + coff[0], tb + ws.o_child + coff[n], tb + ws.o_child_s + coff[0]);
+        const int32_t *tok = tb + ws.o_token + gb;
+        for (int k = 0; k < n; ++k)
+            std::sort(tb + ws.o_child_s + coff[k], tb + ws.o_child_s + coff[k + 1], [tok](int32_t x, int32_t y) { return tok[x] < tok[y]; });
+        for (int j = coff[0]; j < coff[n]; ++j) tb[ws.o_child_tok + j] = tok[tb[ws.o_child_s + j]];
         // the clip's nodes in depth order (stable) and the first entry of every depth
         int32_t *ds = tb + ws.o_dstart + gb + g;
         for (int d = 0; d <= dmax + 1; ++d) ds[d] = 0;
@@ -205,6 +217,12 @@ void run_tdt_tree_pred(Model &m, TdtTreeWs &ws, hipStream_t s) {
 void run_tdt_tree_lattice(Model &m, TdtTreeWs &ws, const float *d_ep, hipStream_t s) {
     const pk_config &c = m.cfg;
     const int V = c.vocab_size, D = ws.D, J = c.joint_hidden, CH = ws.chunk_rows;
+    if (m.tdt_lattice_bf16) {          // (a gemm_bf16 model: Model::set_tdt_total_shared admits no other state) one launch, no z, no logits
+        TdtTreeLatticeBf16Args a = ws.lattice_bf16_args(d_ep, ws.pp.as<float>(), V, J, c.blank_id);
+        a.w16 = m.wld_tl16_.p; a.bld = m.bld;
+        launch_tdt_tree_lattice_bf16(a, s);
+        return;
+    }
     ws.z.reserve((size_t)CH * J * 4);
     ws.logits.reserve((size_t)CH * (V + D) * 4);
     const TdtTree tr = ws.tree();
@@ -230,6 +248,7 @@ void tdt_tree_plan_call(Model &m, TdtTreeWs &ws, const int32_t *n_frames, int n_
                         const int32_t *clip_of, int n_hyp) {
     const pk_config &c = m.cfg;
     const int D = c.num_durations, V = c.vocab_size, J = c.joint_hidden;
+    const bool rc = !m.tdt_lattice_bf16;                             // (the bf16 lattice kernel has no rows chunk)
     tdt_tree_check_durations(c.durations, D);
     tdt_prefix_tree_build(ws.pt, ids, id_offsets, clip_of, n_clips, n_hyp);
     ws.T_of.resize(n_clips); ws.row0_of.resize(n_clips);
@@ -249,10 +268,10 @@ void tdt_tree_plan_call(Model &m, TdtTreeWs &ws, const int32_t *n_frames, int n_
         const int64_t n = ws.pt.node_off[q + 1] - ws.pt.node_off[q], Tq = ws.T_of[q], qc = Tq * n, ql = Tq * (n - 1);
         if (n > kTdtTreeMaxNodes)
             fail(PK_ERR_UNSUPPORTED, "TDT total (shared): the prefix tree of clip %d has %lld nodes, at most %d can be walked", q, (long long)n, kTdtTreeMaxNodes);
-        if (qc > (int64_t)kTdtAlignMaxScratch || tdt_tree_scratch(qc, ql, n, D, V, J) > kTdtAlignMaxScratch)
-            fail(PK_ERR_UNSUPPORTED, "TDT total (shared): the scratch of clip %d's tree alone (lattice values, rows chunk, prediction net) exceeds the cap of %zu bytes",
-                 q, kTdtAlignMaxScratch);
-        if (in_group > 0 && (hyps + nh > kTdtTotalGroupHyps || tdt_tree_scratch(cells + qc, labs + ql, nodes + n, D, V, J) > kTdtAlignMaxScratch)) {
+        if (qc > (int64_t)kTdtAlignMaxScratch || tdt_tree_scratch(qc, ql, n, D, V, J, rc) > kTdtAlignMaxScratch)
+            fail(PK_ERR_UNSUPPORTED, "TDT total (shared): the scratch of clip %d's tree alone (lattice values%s, prediction net) exceeds the cap of %zu bytes",
+                 q, rc ? ", rows chunk" : "", kTdtAlignMaxScratch);
+        if (in_group > 0 && (hyps + nh > kTdtTotalGroupHyps || tdt_tree_scratch(cells + qc, labs + ql, nodes + n, D, V, J, rc) > kTdtAlignMaxScratch)) {
             ws.gstart.push_back((int32_t)ws.walked.size());
             cells = labs = nodes = 0; hyps = in_group = 0;
         }
@@ -273,7 +292,7 @@ void run_tdt_tree_call(Model &m, TdtTreeWs &ws, const float *d_ep, std::vector<f
         const int g0 = ws.gstart[g], C = ws.gstart[g + 1] - g0;
         if (C <= 0) continue;
         tdt_tree_stage(ws, ws.walked.data() + g0, C, ws.T_of.data(), ws.row0_of.data(), ws.pt, ws.hc_off.data(), ws.hc_list.data(), c.durations,
-                       c.num_durations, c.vocab_size, c.joint_hidden, c.blank_id);
+                       c.num_durations, c.vocab_size, c.joint_hidden, c.blank_id, /*rows_chunk=*/!m.tdt_lattice_bf16);
         if (ev) PK_HIP(hipEventRecord(ev[0], s));
         tdt_tree_upload(ws, s);
         run_tdt_tree_pred(m, ws, s);

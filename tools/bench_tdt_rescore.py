@@ -10,8 +10,12 @@ feature's figures for scale).  Writes profiles/tdt_rescore.md with --write.
 --shared: instead, the three stages of pk_tdt_total_decode_timed with pk_model_set_tdt_total_shared off and on (kernels/tdt_tree.hip, DESIGN.md
 section 5.5.3a), interleaved off / on / off / on ... in this one process on the same hypotheses, the totals compared bit for bit, and the share of
 lattice columns the prefix trees save.  Writes profiles/tdt_rescore_shared.md with --write (its bench.py section is kept).
-usage: python tools/bench_tdt_rescore.py [--reps 3] [--write] [--shared [--rounds 3]]"""
+--shared --bf16: the same off / on comparison on gemm_bf16 models with pk_model_set_tdt_lattice_bf16 on (kernels/tdt_tree_bf16.hip, DESIGN.md section
+5.5.3b) at the tdt-ctc-110m and tdt-600m head shapes (1-layer encoders; tdt-600m has no CTC head, so the n-best lists are synthetic: see
+bf16_lists), with the lattice rows of both layouts.  Writes profiles/tdt_rescore_shared_bf16.md with --write.
+usage: python tools/bench_tdt_rescore.py [--reps 3] [--write] [--shared [--rounds 3] [--bf16]]"""
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -71,6 +75,58 @@ def shared_rounds(gm, capi, enc, ids, clip_of, n_clips, reps, rounds):
     return out
 
 
+def bf16_lists(rng, n, T, N, blank):
+    """-> (ids, clip_of): N strings per clip of T // 4 tokens; string j keeps all but the last 3 j tokens of the clip's first string and ends in 3 j
+    tokens of its own -- the shape of a beam's n-best list, whose entries differ near the end."""
+    ids, clip_of = [], []
+    for c in range(n):
+        base = rng.integers(0, blank, size=min(T // 4, 1535)).astype(np.int32)
+        for j in range(N):
+            ids.append(np.concatenate([base[:len(base) - 3 * j], rng.integers(0, blank, size=3 * j).astype(np.int32)]))
+            clip_of.append(c)
+    return ids, clip_of
+
+
+def bench_shared_bf16(a, pk, capi, synth):
+    rng = np.random.default_rng(1)
+    lines = []
+    with tempfile.TemporaryDirectory() as td:
+        for preset, label, n, sec in (("tdt-ctc-110m", "64 x 10 s", 64, 10.0), ("tdt-600m", "32 x 30 s", 32, 30.0)):
+            cfg = dataclasses.replace(pk.make_110m_config() if preset == "tdt-ctc-110m" else pk.make_tdt_600m_config(), num_layers=1, gemm_bf16=True)
+            wp = os.path.join(td, preset + ".safetensors")
+            synth.save_weights(wp, synth.synth_weights(cfg, seed=42))
+            gm = capi.Model(wp, cfg, device=0)
+            gm.set_tdt_lattice_bf16(True)
+            enc = gm.encode(gm.mel(synth.synth_pcm(n, int(sec * 16000), seed=3)))
+            T = int(enc.shape[1])
+            for N in (1, 4, 8):
+                ids, clip_of = bf16_lists(rng, n, T, N, cfg.blank_id)
+                out = {"metric": "tdt rescoring on the bf16 lattice kernels, prefix tree off / on, ms", "config": preset + " (1 layer, gemm_bf16)", "batch": label,
+                       "frames": T, "n_best": N, "hypotheses": len(ids), "tokens_per_hypothesis": round(float(np.mean([len(i) for i in ids])), 1),
+                       "reps": a.reps}
+                out.update(shared_rounds(gm, capi, enc, ids, clip_of, n, a.reps, a.rounds))
+                out["lattice_rows_off"], out["lattice_rows_on"] = T * out["lattice_columns"], T * out["tree_columns"]
+                out["row_ratio"] = round(out["lattice_rows_on"] / out["lattice_rows_off"], 3)
+                out["lattice_ms_ratio"] = round(out["lattice_ms_on"] / out["lattice_ms_off"], 3)
+                lines.append(out)
+                print(json.dumps(out), flush=True)
+            gm.close()
+    if a.write:
+        keys = ["config", "n_best", "hypotheses", "tokens_per_hypothesis", "lattice_rows_off", "lattice_rows_on", "row_ratio", "lattice_ms_off", "lattice_ms_on",
+                "lattice_ms_ratio", "pred_net_ms_off", "pred_net_ms_on", "forward_ms_off", "forward_ms_on", "total_ms_off", "total_ms_on", "bit_identical"]
+        with open(os.path.join(ROOT, "profiles", "tdt_rescore_shared_bf16.md"), "w") as f:
+            f.write("# TDT rescoring on one prefix tree per clip, gemm_bf16 models on the bf16 lattice kernels: the switch off and on, one MI355X\n\n"
+                    "`python tools/bench_tdt_rescore.py --shared --bf16 --reps %d --rounds %d --write` (1-layer encoders, synthetic weights and audio; synthetic "
+                    "n-best lists: string j of a clip shares all but its last 3 j tokens with the first).  Every figure is the median over the rounds of "
+                    "`pk_tdt_total_decode_timed`'s HIP-event medians; off (kernels/tdt_lattice_bf16.hip, one lattice per hypothesis) and on "
+                    "(kernels/tdt_tree_bf16.hip, one per clip) alternate inside one process on the same hypotheses.  `lattice_rows_*` = frames x lattice "
+                    "columns of the layout; at n_best = 1 the tree is a chain and `lattice_ms_ratio` is the cost of the cursor walk.\n\n" % (a.reps, a.rounds))
+            f.write("| " + " | ".join(keys) + " |\n|" + "---|" * len(keys) + "\n")
+            for o in lines:
+                f.write("| " + " | ".join(str(o.get(k, "-")) for k in keys) + " |\n")
+            f.write("\n```\n" + "\n".join(json.dumps(o) for o in lines) + "\n```\n")
+
+
 SHARED_MARK = "## bench.py headline"
 
 
@@ -98,10 +154,13 @@ def main():
     ap.add_argument("--write", action="store_true")
     ap.add_argument("--shared", action="store_true")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--bf16", action="store_true", help="with --shared: gemm_bf16 models on the bf16 lattice kernels (profiles/tdt_rescore_shared_bf16.md)")
     a = ap.parse_args()
     import pkload
     pk = pkload.load()
     from parakeet_cpp_amd import capi, synth
+    if a.shared and a.bf16:
+        return bench_shared_bf16(a, pk, capi, synth)
     lines = []
     with tempfile.TemporaryDirectory() as td:
         cfg = pk.make_110m_config()
